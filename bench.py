@@ -17,10 +17,13 @@ batch of 1024 independent trajectories (MPC replans) with 1024 DISTINCT seeds, s
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 Rank 0 prints ONE compact JSON line LAST on stdout (<= 4 KB: compact_line()) and writes everything it measured to a detail
-file (bench_detail.json beside this script, or --detail PATH).  Besides the contract's keys the results carry
+file (bench_detail.json beside this script, or --detail PATH).  A plain run sets up, warms up, times the steps and reports
+them; `--dump-outputs DIR` also writes what the last timed step computed (dump_outputs()).  Besides the contract's keys the
+results carry
   roofline        dominant kernel (backward sweep): the binding resource is the SIMD's FP64 matrix pipe, so `bound` is
                   "mfma" (algorithmic a7 flops / HIP-event launch time vs the FP64 MFMA peak); `hbm` inside it gives the
                   HBM fractions (the kernel's own compulsory bytes, the PMC traffic, and SURVEY 8(d)'s riccati figure)
+and, with `--full` only (each of these runs or checks something of its own; --no-secondary / --no-cpu-baseline trim it),
   parity_check    K, k, predicted costs of the first seeds against the CPU oracle (outside the timed region)
   lambda_sweep    both sweeps over the reference's regularisation range and on a mixed batch, with the refresh histogram
   pcie_inclusive  SURVEY 8(d): the same iteration with the FD payload / residuals re-uploaded and K,k downloaded every
@@ -28,6 +31,7 @@ file (bench_detail.json beside this script, or --detail PATH).  Besides the cont
   secondary_configs  BASELINE configs[1], [2], [4] (and the humanoid shape) with their own roofline objects (N=1 only)
   strong_scaling_projection  configs[3] shards (512 / 256 / 128 trajectories) timed on this one GPU, x N     (N=1 only)
   materialising_pipeline, cpu_baseline (the CPU oracle = line-faithful port, timed on this box's host cores; N=1 only)
+  weak_scaling    beside a strong-scaling run with N > 1: the same job with --global-batch trajectories PER GPU
 """
 import argparse
 import json
@@ -649,6 +653,28 @@ def parity_check(p0, eng, n_check, tiled=False):
     return out
 
 
+DUMP_GAINS_BYTES = 48 << 20      # the K, k sample of dump_outputs (all files together stay under 64 MB)
+
+
+def dump_outputs(torch, eng, out_dir):
+    """What the timed path leaves a caller after its last step, as float64 .npy files in out_dir: the predicted costs of the
+    line-search alphas, delta_J and the status of every trajectory, and the gains K, k of a fixed, seeded sample of
+    trajectories (K of the headline batch alone is 2.4 GB).  The sample is gathered on the device: only it crosses the link."""
+    B, T, n, m = eng.batch, eng.T, eng.n, eng.m
+    S = int(max(1, min(B, DUMP_GAINS_BYTES // (8 * T * (n * m + m)))))
+    idx = np.sort(np.random.default_rng(0).choice(B, S, replace=False))
+    res = eng.results()                                              # (synchronises the engine's stream)
+    sel = torch.as_tensor(idx, device="cuda")
+    K = torch.as_tensor(eng.device_array(1, (B, T, n, m)), device="cuda")[sel].cpu().numpy()      # KPILQR_BUF_K
+    k = torch.as_tensor(eng.device_array(2, (B, T, m)), device="cuda")[sel].cpu().numpy()         # KPILQR_BUF_k
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"cost_pred": res["cost_pred"], "delta_J": res["delta_J"], "status": res["status"], "K_sample": K, "k_sample": k}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+    print(f"bench.py: outputs of the last timed step in {out_dir}: " + ", ".join(f"{k_}{list(a.shape)}" for k_, a in arrays.items())
+          + f"; K, k of trajectories {idx.tolist()}", file=sys.stderr)
+
+
 def pcie_inclusive(batch, steps=4):
     sys.path.insert(0, os.path.join(ROOT, "tools"))
     import pcie_inclusive as pi
@@ -721,7 +747,7 @@ def main():
     ap.add_argument("--keypoints", default="set_interval", choices=["set_interval", "adaptive_jerk", "iterative_error", "reach_velocity_change", "reach_adaptive_jerk"])
     ap.add_argument("--generic", action="store_true", help="force the generic (VALU/LDS, non-MFMA) kernels")
     ap.add_argument("--unfused", action="store_true", help="materialise A,B (interpolate) and l_* (cost_derivs) with their own kernels")
-    ap.add_argument("--no-secondary", action="store_true", help="skip every side measurement (materialising pipeline, pcie_inclusive, secondary configs, weak line)")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: skip every side measurement (materialising pipeline, pcie_inclusive, secondary configs, weak line)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--pcie-batch", type=int, default=256)
     ap.add_argument("--workload-cache", default=None, help="directory for the generated workload (.npy, memory-mapped by later runs: profiler passes)")
@@ -730,6 +756,13 @@ def main():
     ap.add_argument("--streamed-jacobians", action="store_true",
                     help="upload the residual Jacobians per step (T+1 copies per trajectory) even when the task has ONE constant matrix "
                          "(reaching): the round-1..3 form; default since round 4 is kpilqr_upload_residual_jacobians_const")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every side measurement and check: the parity check against the CPU oracle, the CPU baselines, the "
+                         "materialising pipeline, the per-step-Jacobian, lambda, PCIe-inclusive, secondary-config and scaling runs, the weak "
+                         "line beside a strong N>1 run (--no-secondary / --no-cpu-baseline trim it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float64; rank 0's shard; K, k of a seeded sample "
+                         "of trajectories)")
     args = ap.parse_args()
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
@@ -758,7 +791,7 @@ def main():
     p, p0, desc = build_problem(args.keypoints, B_local, T, args.min_N, args.task, first_b=lo, distinct=not args.tiled_seeds,
                                 cache=args.workload_cache or os.environ.get("KPILQR_WORKLOAD_CACHE"))
     pw = None
-    if world > 1 and not weak and not args.no_secondary:            # the weak-scaling line beside the strong one
+    if world > 1 and not weak and args.full and not args.no_secondary:   # the weak-scaling line beside the strong one
         pw = build_problem(args.keypoints, args.global_batch, T, args.min_N, args.task, distinct=False)[0]   # 8 seeds tiled: a side line
     t_gen = time.perf_counter() - t_gen
 
@@ -788,10 +821,12 @@ def main():
     res = eng.results()
     n_ok = int((res["status"] == 0).sum())
     tiled = args.tiled_seeds or args.keypoints != "set_interval"
-    parity = parity_check(p0, eng, min(p0["batch"], 8), tiled) if rank == 0 else None
+    if args.dump_outputs and rank == 0:
+        dump_outputs(torch, eng, args.dump_outputs)
+    parity = parity_check(p0, eng, min(p0["batch"], 8), tiled) if rank == 0 and args.full else None
     eng.close()
 
-    side = world == 1 and not args.no_secondary
+    side = args.full and world == 1 and not args.no_secondary
     weak_line = None
     if pw is not None:
         # the same job with 1024 trajectories PER GPU, for the weak-scaling curve beside the strong one
@@ -980,7 +1015,7 @@ def main():
                 out["strong_scaling_projection"] = {"note": "global batch 1024 over N GPUs, projected from shards timed on THIS GPU (no "
                                                             "inter-GPU cost: the only collective is one 64-byte all-reduce per iteration)",
                                                     "unit": "trajectory-iterations/s", "n_gpus": proj}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             try:
                 out["cpu_baseline"] = cpu_baseline(args.task, T, args.min_N)
                 out["gpu_over_cpu"] = value / out["cpu_baseline"]["value"]

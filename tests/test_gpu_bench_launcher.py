@@ -10,7 +10,7 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-ARGS = ["--gpus", "2", "--global-batch", "64", "--T", "200", "--steps", "2", "--warmup", "1", "--no-secondary", "--no-cpu-baseline"]
+ARGS = ["--gpus", "2", "--global-batch", "64", "--T", "200", "--steps", "2", "--warmup", "1", "--full", "--no-secondary", "--no-cpu-baseline"]
 
 
 def _env(**extra):

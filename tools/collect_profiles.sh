@@ -20,9 +20,9 @@ export TMPDIR=/tmp
 # under rocprofv3 the profiler has initialised the GPU before the script starts, so those passes must not fork
 WL="--workload-cache /tmp/kpilqr_workload"
 if [ "$MODE" = per_step ]; then
-  python bench.py $WL $EXTRA --no-secondary --no-cpu-baseline --detail $OUT/bench_detail.json > $OUT/bench.json 2> $OUT/bench.err || exit 1
+  python bench.py $WL $EXTRA --full --no-secondary --no-cpu-baseline --detail $OUT/bench_detail.json > $OUT/bench.json 2> $OUT/bench.err || exit 1
 else
-  python bench.py $WL --detail $OUT/bench_detail.json > $OUT/bench.json 2> $OUT/bench.err || exit 1
+  python bench.py $WL --full --detail $OUT/bench_detail.json > $OUT/bench.json 2> $OUT/bench.err || exit 1
 fi
 echo "bench done"
 if [ "$MODE" != per_step ]; then
