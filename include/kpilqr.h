@@ -35,10 +35,9 @@
  *
  *   KPILQR_FUSED_WAVES      backward sweep of a FUSED context: 1 one wavefront per trajectory | 5 consumer / helper pair.
  *                           Default: 5 while 2 x batch <= #SIMDs, else 1.  (Any other value = default.)
- *   KPILQR_FUSED_FWD_WAVES  forward sweep of a FUSED context: 1 one wave | 2 state / cost+staging pair | 3 state / cost /
- *                           staging triple | 4 state / cost pair for uniform key-point sets with 3 or 1 behind it for
- *                           per-DoF lists.  Default: 4 while 2 x batch <= #SIMDs, else 1.
- *   KPILQR_FWD_RAGGED_PAIR  1: per-DoF lists at 256 < batch <= 512 take form 2 instead of one wave behind form 4.
+ *   KPILQR_FUSED_FWD_WAVES  forward sweep of a FUSED context: 1 one wave | 3 state / cost / staging triple | 4 state /
+ *                           cost pair for uniform key-point sets with 3 or 1 behind it for per-DoF lists.
+ *                           Default: 4 while 2 x batch <= #SIMDs, else 1.  (Any other value = default.)
  *   KPILQR_FUSED_RAW        0: a key-point ordered payload is differenced by k_fd_kp_difference in front of the backward
  *                           sweep instead of inside it (default: inside, for uniform key-point sets).
  *   KPILQR_FUSED_UNI        0: the general (per-DoF list) forms of the one-wave sweeps also for uniform key-point sets.
@@ -384,7 +383,7 @@ const char *kpilqr_forward_variant(kpilqr_ctx *ctx);
 /* What the LAST backward (which = 0) / forward (which = 1) launch of this context was -- the variant above and, for the
  * KPILQR_FLAG_FUSED sweeps, the form the library picked from the batch size, the payload and the key-point lists:
  *     "<variant>:<waves>:<columns>:<lists>[:ru0][:rxc][:slopes]"          e.g. "mfma_f64_t1_fused:w1:raw:uni:ru0"
- *   waves    w1 one wavefront per trajectory | w2 control / state split | pair | triple | pairh (backward: consumer / helper pair)
+ *   waves    w1 one wavefront per trajectory | pair | triple | pairh (backward: consumer / helper pair)
  *            (forward `pair` on a uniform set: state wave with its own interpolant + scoring wave)
  *   columns  (backward only) raw: the sweep differenced the key-point ordered FD payload itself | kpc: it read the differenced
  *            key-point column store

@@ -46,15 +46,20 @@ def _same(a, b, keys=("K", "k", "delta_J", "cost"), rtol=0.0):
             assert np.max(np.abs(u - v)) <= rtol * max(float(np.max(np.abs(v))), 1e-300), (key, float(np.max(np.abs(u - v))), float(np.max(np.abs(v))))
 
 
-@pytest.fixture(params=["one_wave", "auto", "auto_roles"])
+@pytest.fixture(params=["one_wave", "auto", "auto_roles", "unknown_forms"])
 def waves(request, monkeypatch):
     """one_wave: the raw backward sweep; auto: small batches -> the consumer / helper pair, whose helper wave differences the
-    payload; auto_roles: the same with the two roles alternating with the block index."""
+    payload; auto_roles: the same with the two roles alternating with the block index; unknown_forms: form numbers the library
+    does not have (a removed backward form, no forward form at all) are ignored -- the default forms run, as with auto."""
     if request.param == "one_wave":
         monkeypatch.setenv("KPILQR_FUSED_WAVES", "1")
         monkeypatch.setenv("KPILQR_FUSED_FWD_WAVES", "1")
     elif request.param == "auto_roles":
         monkeypatch.setenv("KPILQR_ROLE_SHIFT", "0")
+        return "auto"
+    elif request.param == "unknown_forms":
+        monkeypatch.setenv("KPILQR_FUSED_WAVES", "3")
+        monkeypatch.setenv("KPILQR_FUSED_FWD_WAVES", "7")
         return "auto"
     return request.param
 
@@ -511,12 +516,10 @@ def test_general_forms_forced_on_uniform_lists(monkeypatch):
         assert relerr(ref["K"][b], o["K"]) < 1e-9
 
 
-@pytest.mark.parametrize("ragged_pair", ["0", "1"])
-def test_per_dof_lists_between_256_and_512_trajectories(monkeypatch, ragged_pair):
+def test_per_dof_lists_between_256_and_512_trajectories():
     """256 < B <= 512 with per-DoF key-point lists: backward = the consumer / helper pair on the slope store, forward = one wave
-    per trajectory (general form) or, with KPILQR_FWD_RAGGED_PAIR=1, the state / cost+staging wave pair behind the uniform pair
-    (which leaves at once): the forms are asserted, a few trajectories against the oracle, the two forward forms against each other."""
-    monkeypatch.setenv("KPILQR_FWD_RAGGED_PAIR", ragged_pair)
+    per trajectory (general form) behind the uniform pair (which leaves at once): the forms are asserted, a few trajectories
+    against the oracle, repeated trajectories against each other."""
     T, dof = 90, 7
     rng = np.random.default_rng(5)
     rows = [synth.bisect_keypoints(rng, dof, T, 2, rng.uniform(0.0, 1.0, dof)) for _ in range(8)]
@@ -528,7 +531,7 @@ def test_per_dof_lists_between_256_and_512_trajectories(monkeypatch, ragged_pair
         res = e.results(); K, k = e.gains()
         lb, lf = e.last_launch("backward"), e.last_launch("forward")
     assert ":pairh:kpc:ragged" in lb and lb.endswith(":slopes"), lb
-    assert (":pair:ragged" in lf) if ragged_pair == "1" else (":w1:ragged" in lf), lf
+    assert ":w1:ragged" in lf, lf
     for b in (0, 5, 8 * 32 + 3):
         o = pipeline.run_trajectory(p0, b % 8)
         assert res["status"][b] == 0 and relerr(K[b], o["K"]) < 1e-9 and relerr(res["cost_pred"][b], o["cost_pred"]) < 1e-9

@@ -744,15 +744,17 @@ def test_c_abi_linesearch_allreduce_single_rank():
         assert np.allclose(kd.pack_linesearch(cost, dJ, st).numpy(), v0, rtol=1e-13)
 
 
-@pytest.mark.parametrize("waves,fwd", [("1", "1"), ("5", "2"), ("5", "3")])
+@pytest.mark.parametrize("waves,fwd", [("1", "1"), ("5", "4"), ("5", "3")])
 def test_fused_two_wave_backward_variant(monkeypatch, waves, fwd):
     """The wave organisations of the fused backward pass compute the same gains:
     KPILQR_FUSED_WAVES=1 one wave per trajectory (the default above #SIMDs/2 trajectories), =5 the consumer / helper pair
     (the default up to #SIMDs/2 trajectories).  (The control / state split, the producer / consumer pair and the triple of
-    rounds 2-4 were removed in round 5: slower than the helper pair at every batch size.)"""
+    rounds 2-4 were removed in round 5: slower than the helper pair at every batch size.)  The forward forms ride along,
+    each held to the oracle under a forced switch."""
     monkeypatch.setenv("KPILQR_FUSED_WAVES", waves)
-    # forward sweep: one wave per trajectory with "1", the state / cost pair with "2", the state / cost / staging triple
-    # (the default up to #SIMDs/4 trajectories) with "3"
+    # forward sweep: one wave per trajectory with "1", with "4" the state / cost pair on uniform key-point sets (the default up
+    # to #SIMDs/2 trajectories) with the triple or one wave behind it for per-DoF lists, the state / cost / staging triple
+    # (the default behind "4" up to #SIMDs/4 trajectories) with "3"
     monkeypatch.setenv("KPILQR_FUSED_FWD_WAVES", fwd)
     if waves == "5":
         monkeypatch.setenv("KPILQR_ROLE_SHIFT", "0")             # alternate the roles with the block index

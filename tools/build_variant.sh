@@ -1,6 +1,6 @@
 #!/bin/bash
 # Builds another libkpilqr.so with extra compiler flags for kernel A/B runs:
-#   tools/build_variant.sh NAME -DKP_RECT=0 ...   ->  trajoptkp_amd/lib/variants/NAME/libkpilqr.so   (use with KPILQR_LIB=...)
+#   tools/build_variant.sh NAME -DKP_FWD_SETS=6 ...   ->  trajoptkp_amd/lib/variants/NAME/libkpilqr.so   (use with KPILQR_LIB=...)
 set -e
 NAME=$1; shift
 ROOT=$(cd "$(dirname "$0")/.." && pwd)

@@ -9,13 +9,6 @@
 
 #include "../../include/kpilqr.h"
 
-// Layout of the key-point ordered FD payload's records (kpilqr_fd_kp_layout): 1 = x+ and x- of an element side by side (round 4:
-// the sweep that differences the payload fetches both with one 16-byte load); 0 = two blocks of 3n doubles (rounds 1-3; kept as
-// a build switch for same-box A/B runs: tools/build_variant.sh NAME -DKP_RAW_PAIRS=0 -- bench.py packs whatever the library reports)
-#ifndef KP_RAW_PAIRS
-#define KP_RAW_PAIRS 1
-#endif
-
 namespace kpilqr {
 
 // ---- device layout of one "step record" (all FP64), one per (trajectory b, time t) ----------
@@ -173,7 +166,7 @@ struct Ctx {
     const char *bwd_variant = "";
     const char *fwd_variant = "";
     // what the last backward / forward launch of this context actually was (kpilqr_last_launch): wave organisation
-    // (1 one wave per trajectory, 2 control / state split, 3 pair, 4 triple; 0: not a fused launch, or none yet), whether the
+    // (1 one wave per trajectory, 3 pair, 4 triple, 5 consumer / helper pair; 0: not a fused launch, or none yet), whether the
     // sweep differenced the raw payload itself, which residual instantiation ran
     int last_bwd_form = 0, last_fwd_form = 0, last_fwd_form_ragged = 0;      // (_ragged: the form that ran instead on per-DoF lists, if another)
     bool last_bwd_raw = false, last_bwd_ru0 = false, last_fwd_ru0 = false, last_bwd_rxc = false, last_fwd_rxc = false;
@@ -184,8 +177,7 @@ struct Ctx {
     // look here.  0 = let the library choose.
     struct Tuning {
         int fused_bwd_waves = 0;   // KPILQR_FUSED_WAVES: 1 one wave, 5 consumer / helper pair (include/kpilqr.h lists every switch)
-        int fused_fwd_waves = 0;   // KPILQR_FUSED_FWD_WAVES: 1 | 2 | 3 | 4
-        int fwd_ragged_pair = 0;   // KPILQR_FWD_RAGGED_PAIR: per-DoF lists at 256 < batch <= 512 on the state / cost+staging pair (A/B)
+        int fused_fwd_waves = 0;   // KPILQR_FUSED_FWD_WAVES: 1 one wave, 3 triple, 4 pair with a form behind it for per-DoF lists
         int role_shift = 9;        // KPILQR_ROLE_SHIFT (wave-pair role placement probe)
         int tiled_nt_min = 0;      // KPILQR_TILED_NT_MIN: run the tiled kernels with more tiles than needed
         int tiled_a6 = -1;         // KPILQR_TILED_A6: -1 auto, 0 | 1
@@ -271,7 +263,7 @@ bool fused_supported(int n, int m, int nr, int dof, int T, int stride, int n_alp
 int backward_fused_form(const Ctx *c);
 int forward_fused_form(const Ctx *c);
 hipError_t launch_backward_fused(Ctx *c, int pd_stride, bool raw);
-hipError_t launch_backward_fused_waves(Ctx *c, int pd_stride, bool raw, int form);      // forms 2..5 (fused_mfma.hip, part 2)
+hipError_t launch_backward_fused_waves(Ctx *c, int pd_stride, bool raw);      // form 5 (fused_mfma.hip, part 2)
 hipError_t launch_forward_fused(Ctx *c, double *U_alpha_dev);
 hipError_t launch_backward_fused_stats(Ctx *c, int pd_stride, int *hist_dev);
 

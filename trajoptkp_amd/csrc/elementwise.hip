@@ -194,13 +194,8 @@ k_fd_kp_difference(int n, long long npairs_total, unsigned long long magic, cons
     auto column = [&](const double2 *r, int p) -> double2 {       // elements 2p, 2p + 1 of an entry's differenced columns
         const int mode = ((const int *)(r + 2 * pe))[0];
         const double den = ((mode >> (p / (n >> 1))) & 1) ? eps : 2 * eps;
-#if KP_RAW_PAIRS
         const double2 a = r[2 * p], b = r[2 * p + 1];            // (x+, x-) of elements 2p and 2p + 1
         return make_double2((a.x - a.y) / den, (b.x - b.y) / den);
-#else
-        const double2 a = r[p], b = r[pe + p];
-        return make_double2((a.x - b.x) / den, (a.y - b.y) / den);
-#endif
     };
     for (long long w = (long long)blockIdx.x * blockDim.x + threadIdx.x; w < npairs_total; w += stride) {
         const long long e = magic ? (long long)__umul64hi((unsigned long long)w, magic) : w;      // w / pe

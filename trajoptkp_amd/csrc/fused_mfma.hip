@@ -13,7 +13,7 @@
 //     its own DoF and keeps (value at segment start, slope) in registers:
 //         A_t[:,c] = A_s[:,c] + (t-s) * ((A_e[:,c] - A_s[:,c]) / (e-s))          (:898-905, :933-948)
 //     the slope is the correctly rounded quotient k_interpolate forms; the value is ONE fused multiply-add of it
-//     (KP_LERP_FMA, round 4: a single rounding where k_interpolate has two -- the sweeps are held to the oracle at 1e-9, the
+//     (lerp_nc: a single rounding where k_interpolate has two -- the sweeps are held to the oracle at 1e-9, the
 //     materialised A, B of kpilqr_interpolate keep the reference's bits).  Key-point columns of the next segment are
 //     fetched one segment ahead (time indices two ahead).
 //   * a6 (ModelTranslator::CostDerivativesFromResiduals, src/ModelTranslator/ModelTranslator.cpp:552-583):
@@ -25,8 +25,7 @@
 //         l_x'dx + dx'l_xx dx/2 = sum_k w_k Jx_k (2 r_k + Jx_k),   Jx = r_x dx      (likewise for du).
 //
 // Wave organisations (launch_backward_fused / launch_forward_fused pick by batch size):
-//   backward: one wave per trajectory (batch > #SIMDs/2) | producer / consumer pair | consumer / side / producer triple
-//             (batch <= #CUs) | control / state split (kept as a tested alternative);
+//   backward: one wave per trajectory (batch > #SIMDs/2) | consumer / helper pair;
 //   forward:  one wave -- in a form for uniform key-point sets (no LDS transpose) and a general one, chosen on the device --
 //             | state / cost pair | state / cost / staging triple.
 // Everything else (homogeneous form, LDL' solve, slow path, stores) is riccati_mfma.hip / forward_mfma.hip.
@@ -41,9 +40,6 @@ typedef unsigned int u32x2f __attribute__((ext_vector_type(2)));
 typedef unsigned long long u64;
 #define MFMA(a, b, c) __builtin_amdgcn_mfma_f64_16x16x4f64((a), (b), (c), 0, 0, 0)
 #define OOBF 0x7ffffff0
-#ifndef KP_NS
-#define KP_NS 1
-#endif
 #define BIGT 0x3fffffff
 // An offset no trajectory's slice of kpc reaches (fused_supported keeps a slice below 1 GB): a lane / register / entry with
 // nothing to load adds it instead of selecting -- BIGOFF and BIGOFF + BIGOFF are both out of range of the descriptor and do
@@ -60,9 +56,6 @@ typedef unsigned long long u64;
 #define KP_FWD_SETS_GEN 6          // ... of its general (per-DoF list) form (late round 4, same box: 3 / 4 / 5 / 6 / 8 sets = 2.37 / 2.32 / 2.30 / 2.29 / 2.46 ms
                                    // on velocity_change lists, 2.73 / 2.70 / 2.65 / 2.64 / 2.81 on adaptive_jerk lists)
 #endif
-#ifndef KP_BWD_LATE_STORE
-#define KP_BWD_LATE_STORE 1
-#endif
 #ifndef KP_FSC_SETS
 #define KP_FSC_SETS 4              // tile sets of the forward state / cost wave groups
 #endif
@@ -70,33 +63,12 @@ typedef unsigned long long u64;
 #define KP_PROBE_BWD 0
 #endif
 // The launchers (and with them the kernel instantiations) of this file compile as THREE translation units (Makefile: -DKP_FUSED_PART=1|2|3;
-// unset or 0: everything in one): 1 one wave per trajectory backward + the form choices, 2 the backward wave pairs / triple,
+// unset or 0: everything in one): 1 one wave per trajectory backward + the form choices, 2 the backward consumer / helper pair,
 // 3 the forward sweeps -- the file takes two minutes as one unit.
 #ifndef KP_FUSED_PART
 #define KP_FUSED_PART 0
 #endif
 #define KP_PART(n) (KP_FUSED_PART == 0 || KP_FUSED_PART == (n))
-#ifndef KP_KINK4
-#define KP_KINK4 1                  // 0: the step below a key-point refreshes the running inverse like every other step (round 3; A/B builds)
-#endif
-#ifndef KP_FWD_TRIM
-#define KP_FWD_TRIM 1               // 0: the one-wave forward sweep starts its control-law product from u_nom and clamps with compare-and-select (A/B builds)
-#endif
-#ifndef KP_FWD_SQW
-#define KP_FWD_SQW 1                // 0: the headline's forward sweep scores on the unscaled r_x dx (round 4; A/B builds)
-#endif
-#ifndef KP_BWD_RV2
-#define KP_BWD_RV2 1                // 0: the headline backward sweep fetches r_t with four 8-byte requests: A/B builds
-#endif
-#ifndef KP_FWD_RV2
-#define KP_FWD_RV2 1                // 0: the headline forward sweep fetches r_t with four 8-byte requests (rows in their natural order): A/B builds
-#endif
-#ifndef KP_RXC_CXX
-#define KP_RXC_CXX 1                // 0: the RXC sweeps form Lzz = Rz' W Rz with four products at every step (round 4; A/B builds)
-#endif
-#ifndef KP_SLOPES
-#define KP_SLOPES 1                 // 0: the general forms divide at their crossings (rounds 1-3) instead of reading the slope store (A/B builds)
-#endif
 #ifdef KP_PROBE_SAMEB
 #define KP_BLOCK_TRAJ ((int)(blockIdx.x & 7))
 #else
@@ -162,23 +134,13 @@ __device__ __forceinline__ double bits_and(double a, u64 mask)
 {
     return __builtin_bit_cast(double, __builtin_bit_cast(u64, a) & mask);
 }
-// start + dt*slope.  KP_LERP_FMA = 0: two instructions, never contracted -- k_interpolate's operation order, the bits the
-// materialising pipeline writes (KeyPointGenerator.cpp:933-948).  1: ONE fused multiply-add (a single rounding: at least as close
-// to the exact interpolant) -- 16 VALU instructions less per forward step and 8 per backward step on a wave that pays ~9 cycles
-// for each; the sweeps' results move by ~1e-16 relative (they are held to the oracle at 1e-9, not bit for bit: the MFMA
-// accumulation order differs from the reference's loops anyway); kpilqr_interpolate / get_AB still give the reference's bits.
-#ifndef KP_LERP_FMA
-#define KP_LERP_FMA 1
-#endif
+// start + dt*slope as ONE fused multiply-add (a single rounding where k_interpolate's un-contracted multiply and add have two:
+// at least as close to the exact interpolant) -- 16 VALU instructions less per forward step and 8 per backward step on a wave that
+// pays ~9 cycles for each; the sweeps' results move by ~1e-16 relative (they are held to the oracle at 1e-9, not bit for bit: the
+// MFMA accumulation order differs from the reference's loops anyway); kpilqr_interpolate / get_AB still give the reference's bits.
 __device__ __forceinline__ double lerp_nc(double sv, double dt, double av)
 {
-#if KP_LERP_FMA
     return __builtin_fma(dt, av, sv);
-#else
-#pragma clang fp contract(off)
-    const double p = dt * av;
-    return sv + p;
-#endif
 }
 
 struct FusedArgs {
@@ -324,12 +286,12 @@ __device__ __forceinline__ KArgF kernarg_fused()
 
 template <int R> __device__ __forceinline__ void fset_reg(d4 &v, double x) { if (R == 0) v.x = x; else if (R == 1) v.y = x; else if (R == 2) v.z = x; else v.w = x; }
 
-// PC = false: one wavefront per trajectory does everything.  PC = true: this is the CONSUMER wave of a two-wave block; the
-// step's tiles Fz, Fu, Lzz, [l_uu | l_u] come from the LDS ring filled by the producer wave (fusedpc_producer below), LDS
-// hand-offs inside the step are wave-local, and the only block barrier is the one that ends a step.
+// PC = false: one wavefront per trajectory does everything.  PC = true: this is the CONSUMER wave of the consumer / helper pair;
+// the step's tiles Fu, [l_uu | l_u] (and Lzz of the terminal step) come from the LDS ring filled by the helper wave
+// (fusedpc_producer below), which also forms the side products Quz, Qzz; two block barriers per step, mid-step and at its end.
 #define FPC_TILES 4
 #define FPC_BUF (FPC_TILES * 256)
-// behind the two ring slots (offsets from the ring base): the side wave's Quz and Qzz of the wave triple
+// behind the two ring slots (offsets from the ring base): the helper wave's Quz and Qzz
 #define FPC_SIDE_QUZ (2 * FPC_BUF)
 #define FPC_SIDE_QZZ (FPC_SIDE_QUZ + 256)
 __device__ __forceinline__ d4 lds_tile4(const double *t, int lane);
@@ -355,7 +317,7 @@ __device__ __forceinline__ void lds_store4(double *t, int lane, const d4 &v);
 // trajectory (reaching: selector rows, src/ModelTranslator/Reaching.cpp:43-54; any task whose residuals are affine in the state):
 // the Rx tile is loaded ONCE and stays in registers, the sweep issues no r_x loads (T nr n doubles per trajectory: 5.0 of the
 // 8.1 MB a trajectory's backward sweep reads at the headline shape).  Same products in the same order: bit-identical gains.
-template <int N, int M, bool PC, bool RU0 = false, bool SIDE = false, bool RAW = false, bool UNI = false, bool STATS = false, bool RXC = false>
+template <int N, int M, bool PC, bool RU0 = false, bool RAW = false, bool UNI = false, bool STATS = false, bool RXC = false>
 __device__ __forceinline__ void backward_fused_body(double *sh, const double *pcbuf, int *sflag, RecLayout L, FusedArgs F, int T,
                 const double *__restrict__ lambda, int pd_stride, double *__restrict__ Kout, double *__restrict__ kout,
                 double *__restrict__ delta_J, int *__restrict__ status, int *__restrict__ hist = nullptr)
@@ -376,7 +338,7 @@ __device__ __forceinline__ void backward_fused_body(double *sh, const double *pc
     const double lam = lambda[b];
     // (probe builds, -DKP_PROBE_BWD=bits: 1 residual loads, 2 key-point stores, 4 gain stores go to one of eight trajectories)
     const int bR = (KP_PROBE_BWD & 1) ? (int)(blockIdx.x & 7) : b, bP = (KP_PROBE_BWD & 2) ? (int)(blockIdx.x & 7) : b, bS = (KP_PROBE_BWD & 4) ? (int)(blockIdx.x & 7) : b;
-    constexpr bool RV2B = KP_BWD_RV2 && KP_RXC_CXX && RXC && RU0 && !PC;     // (see below)
+    constexpr bool RV2B = RXC && RU0 && !PC;     // (see below)
     // 4-row chunks of the residual index that hold residuals (RV2B: registers 0, 1 hold residuals 0 .. 7, registers 2, 3 residuals 8 .. 15)
     const int nr = F.nr, ncr = RV2B ? (nr > 9 ? 4 : nr > 8 ? 3 : nr > 1 ? 2 : 1) : (nr + 3) >> 2;
     constexpr int strideB = 3 * N * 8;                            // bytes of one key-point entry: three columns
@@ -403,7 +365,7 @@ __device__ __forceinline__ void backward_fused_body(double *sh, const double *pc
     for (int r = 0; r < 4; r++) {
         const int row = 4 * r + q;
         // (RXC one-wave sweeps: r[k] in EVERY column -- the lanes of column c form their part of (r_x' W r)(c) from it, see CXX below)
-        oR1[r] = (row < nr && (c == n || (KP_RXC_CXX && RXC && !PC))) ? 8 * row : OOBF;               //            ... | r[k] in column n
+        oR1[r] = (row < nr && (c == n || (RXC && !PC))) ? 8 * row : OOBF;               //            ... | r[k] in column n
         oRu[r] = (row < nr && c < m) ? 8 * (row * m + c) : OOBF;      // Ru(k=row, c) = r_u[k][c]
         oKst[r] = (row < m && c < n) ? 8 * (row + c * m) : OOBF;
         okst[r] = (row < m && c == n) ? 8 * row : OOBF;
@@ -461,14 +423,13 @@ __device__ __forceinline__ void backward_fused_body(double *sh, const double *pc
     // from the slope store k_kp_slopes wrote -- a crossing is then two register moves per value, no division on the wave's
     // serial chain (8 correctly rounded divisions + a reciprocal per lane before: the whole wave paid them on every step on which
     // ANY lane crossed, which with per-DoF lists is most steps)
-    constexpr bool SLP = KP_SLOPES && !PC && !UNI && !RAW;
+    constexpr bool SLP = !PC && !UNI && !RAW;
     // RAW: the prefetched column of the next segment start waits as x+ (in pv) and x- (pm) until the crossing differences it
     double pm[8];
     int pmode = 0;
     // the raw payload: ONE descriptor over the trajectory's records; x+ and x- of an element sit side by side (one 16-byte load
     // gives both: 9 loads per crossing instead of 17) and the mode word behind them
-    constexpr int strideR = (6 * N + 2) * 8, offMode = 6 * N * 8, offM = 3 * N * 8;
-    (void)offM;
+    constexpr int strideR = (6 * N + 2) * 8, offMode = 6 * N * 8;
     __amdgpu_buffer_rsrc_t rP = rT;                               // SLP: the trajectory's slice of the slope store: (value, slope) pairs
     ColOffsN co2 = co;
     co2.a = dbl_off(co.a); co2.al = dbl_off(co.al); co2.b = dbl_off(co.b); co2.bl = dbl_off(co.bl);
@@ -479,12 +440,7 @@ __device__ __forceinline__ void backward_fused_body(double *sh, const double *pc
     auto ebase = [&](int e_rel) { return ((unsigned)e_rel < (unsigned)NE) ? e_rel * strideB : BIGOFF; };
     auto load_raw = [&](int e_rel, double *xp_, double *xm_, int &mo) {
         const int base = ((unsigned)e_rel < (unsigned)NE) ? e_rel * strideR : BIGOFF;
-#if KP_RAW_PAIRS
         load_col2_n<N>(rP, co2, base, xp_, xm_);
-#else
-        load_col_n<N>(rP, co, base, xp_);
-        load_col_n<N>(rP, co, base + offM, xm_);
-#endif
         mo = __builtin_amdgcn_raw_buffer_load_b32(rP, base + ((c < n) ? offMode : BIGOFF), 0, 0);
     };
     double eps2 = F.eps2, rinv2 = F.rinv_2eps;
@@ -521,7 +477,7 @@ __device__ __forceinline__ void backward_fused_body(double *sh, const double *pc
     // (element (n, n), the constant of the value function, is dropped by the sweep anyway).  The terminal step (V = Lzz under the
     // terminal weights, :537-539) keeps the full product.  31.4 matrix instructions per step instead of 34.4, and a chain of four at
     // the top of the step becomes one.  The accumulation order differs from the per-step form's: results agree to ~1e-15, not bit for bit.
-    constexpr bool CXX = KP_RXC_CXX && RXC && !PC;
+    constexpr bool CXX = RXC && !PC;
     d4 Cxx = {0.0, 0.0, 0.0, 0.0}, RxW = Cxx;
     const double en2 = (c == n) ? 2.0 : 0.0;
     (void)Cxx; (void)RxW; (void)en2;
@@ -540,13 +496,8 @@ __device__ __forceinline__ void backward_fused_body(double *sh, const double *pc
     if constexpr (UNI) {
         cu.a = shift(co.a, kd * KpU * strideB); cu.al = shift(co.al, kd * KpU * strideB);
         cu.b = shift(co.b, kd * KpU * strideB); cu.bl = shift(co.bl, kd * KpU * strideB);
-#if KP_RAW_PAIRS
         cr.a = shift(co2.a, kd * KpU * strideR); cr.al = shift(co2.al, kd * KpU * strideR);      // (the payload's elements are 16 bytes)
         cr.b = shift(co2.b, kd * KpU * strideR); cr.bl = shift(co2.bl, kd * KpU * strideR);
-#else
-        cr.a = shift(co.a, kd * KpU * strideR); cr.al = shift(co.al, kd * KpU * strideR);
-        cr.b = shift(co.b, kd * KpU * strideR); cr.bl = shift(co.bl, kd * KpU * strideR);
-#endif
     }
     int up = KpU - 1;                                          // UNI: position (in every list) of the current segment's start
     int us = T, unb = T - 1, unb_v = T - 1;                    // UNI: its time, and the time of the next start (uniform; unb_v: as loaded)
@@ -555,12 +506,7 @@ __device__ __forceinline__ void backward_fused_body(double *sh, const double *pc
         // both columns of the first crossing are the last key-point's (slope 0 over the virtual segment [T-1, T])
         if constexpr (RAW) {
             rP = frsrc(F.fdk + (size_t)E0 * strideR, NE * strideR);
-#if KP_RAW_PAIRS
             load_col2_n<N>(rP, cr, up * strideR, pv, pm);
-#else
-            load_col_n<N>(rP, cr, up * strideR, pv);
-            load_col_n<N>(rP, cr, up * strideR + offM, pm);
-#endif
             pmode = __builtin_amdgcn_raw_buffer_load_b32(rP, up * strideR + kd * KpU * strideR + ((c < n) ? offMode : BIGOFF), 0, 0);
 #pragma unroll
             for (int i = 0; i < 8; i++) sv[i] = 0.0;
@@ -582,8 +528,7 @@ __device__ __forceinline__ void backward_fused_body(double *sh, const double *pc
             load_raw(e_nb, pv, pm, pmode);
         } else {
             load_col_n<N>(rT, co, ebase(e_s), sv);
-            if constexpr (SLP) load_col2_n<N>(rP, co2, ebase2(e_nb), pv, pm);
-            else load_col_n<N>(rT, co, ebase(e_nb), pv);
+            load_col2_n<N>(rP, co2, ebase2(e_nb), pv, pm);
         }
 #pragma unroll
         for (int i = 0; i < 8; i++) av[i] = 0.0;
@@ -597,12 +542,12 @@ __device__ __forceinline__ void backward_fused_body(double *sh, const double *pc
         __syncthreads();                               // the producer has published step T-1
     }
     const d4 zero = {0.0, 0.0, 0.0, 0.0};
-    d4 V = zero, accp = zero;                                  // accp (SIDE): V' of the step before, not yet symmetrised
+    d4 V = zero, accp = zero;                                  // accp (PC): V' of the step before, not yet symmetrised
     (void)accp;
     d4 W2 = {w2term[0], w2term[1], w2term[2], w2term[3]};     // terminal weights at t = T-1, running after
     int pd_counter = 0, fail = 0;
     double dJ = 0.0;
-    d4 Xinv = zero, Xprev = zero, Iu;            // running inverse of Quu + lambda I (KP_NS), the one before it, the identity of the u-block
+    d4 Xinv = zero, Xprev = zero, Iu;            // running inverse of Quu + lambda I, the one before it, the identity of the u-block
     bool haveX = false;
     Iu.x = (q == c && c < m) ? 1.0 : 0.0; Iu.y = (4 + q == c && c < m) ? 1.0 : 0.0;
     Iu.z = (8 + q == c && c < m) ? 1.0 : 0.0; Iu.w = (12 + q == c && c < m) ? 1.0 : 0.0;
@@ -648,20 +593,17 @@ __device__ __forceinline__ void backward_fused_body(double *sh, const double *pc
             const double *tb = pcbuf + (t & 1) * FPC_BUF;
             Fu = lds_tile4(tb + 256, lane);
             if constexpr (RU0) LU = zero; else LU = lds_tile4(tb + 768, lane);
-            if constexpr (SIDE) {                     // Fz, Lzz are the side wave's operands; only V = Lzz of the last step is ours
-                Fz = zero; Lzz = zero;
-                if (term) Lzz = lds_tile4(tb + 512, lane);
-                else {
-                    // (V' + V'')/2 of the step before: its transposed half is read here, behind the barrier that ended that
-                    // step, together with this step's tiles -- no write / wait / read round trip at the end of a step
-                    V.x = 0.5 * (accp.x + sh[FLDS_V + c * FVS + q]);
-                    V.y = 0.5 * (accp.y + sh[FLDS_V + c * FVS + 4 + q]);
-                    V.z = 0.5 * (accp.z + sh[FLDS_V + c * FVS + 8 + q]);
-                    V.w = 0.5 * (accp.w + sh[FLDS_V + c * FVS + 12 + q]);
-                    if (lane_nn) fset_reg<REG_NN>(V, 0.0);
-                }
-            } else {
-                Fz = lds_tile4(tb, lane); Lzz = lds_tile4(tb + 512, lane);
+            // Fz, Lzz are the helper wave's operands; only V = Lzz of the last step is ours
+            Fz = zero; Lzz = zero;
+            if (term) Lzz = lds_tile4(tb + 512, lane);
+            else {
+                // (V' + V'')/2 of the step before: its transposed half is read here, behind the barrier that ended that
+                // step, together with this step's tiles -- no write / wait / read round trip at the end of a step
+                V.x = 0.5 * (accp.x + sh[FLDS_V + c * FVS + q]);
+                V.y = 0.5 * (accp.y + sh[FLDS_V + c * FVS + 4 + q]);
+                V.z = 0.5 * (accp.z + sh[FLDS_V + c * FVS + 8 + q]);
+                V.w = 0.5 * (accp.w + sh[FLDS_V + c * FVS + 12 + q]);
+                if (lane_nn) fset_reg<REG_NN>(V, 0.0);
             }
         } else {
         // ---- a4: this step's A and B columns --------------------------------------------------------------
@@ -681,11 +623,11 @@ __device__ __forceinline__ void backward_fused_body(double *sh, const double *pc
                         asm volatile("v_mov_b64 %0, %1" : "+v"(av[i]) : "v"(pm[i]));
                         asm volatile("v_mov_b64 %0, %1" : "+v"(sv[i]) : "v"(pv[i]));
                     }
-                } else {
-                if constexpr (RAW) { const KArgF Fk = kernarg_fused(); eps2 = Fk->eps2; rinv2 = Fk->rinv_2eps; }
+                } else {                              // RAW: the slope is formed here
+                const KArgF Fk = kernarg_fused(); eps2 = Fk->eps2; rinv2 = Fk->rinv_2eps;
                 const double den = (double)(s - nb);
                 const double rinv = kp_rcp(den);
-                if constexpr (RAW) difference_arith(pv, pm, pmode);      // the prefetched x+ / x- become the column
+                difference_arith(pv, pm, pmode);        // the prefetched x+ / x- become the column
 #pragma unroll
                 for (int i = 0; i < 8; i++) {
                     av[i] = fdiv(sv[i] - pv[i], den, rinv);
@@ -733,7 +675,7 @@ __device__ __forceinline__ void backward_fused_body(double *sh, const double *pc
         __builtin_amdgcn_sched_barrier(0);
         // the step above, IN FRONT of the requests.  (The test is false only at the first step; compiling it out of the loops'
         // call sites was measured and is 0.04 ms SLOWER at B=1024 -- the scheduler's placement of the stores changes.)
-        if constexpr (KP_BWD_LATE_STORE) { if (tst >= 0) store_gains(tst, Kst); }
+        if (tst >= 0) store_gains(tst, Kst);
         if constexpr (!UNI) {
             if (cross) {                               // late_cross: the memory operations of the crossing at the top of this step
                 const KArgF Fk = kernarg_fused();      // crossing-only scalars, from the kernel-argument segment
@@ -745,10 +687,10 @@ __device__ __forceinline__ void backward_fused_body(double *sh, const double *pc
                 nb = (idx - 1 >= lo) ? Fk->kp_times[idx - 1] : -1;
                 const int e_nb = (idx - 1 >= lo) ? idx - 1 - E0 : -1;
                 if constexpr (RAW) load_raw(e_nb, pv, pm, pmode);
-                else if constexpr (SLP) {
+                else {
                     rP = frsrc(Fk->kps + (size_t)E0 * 6 * n, NE * 2 * strideB);
                     load_col2_n<N>(rP, co2, ebase2(e_nb), pv, pm);             // start column AND slope of the next segment: one load each
-                } else load_col_n<N>(rT, co, ebase(e_nb), pv);
+                }
             }
         }
         if constexpr (RAW && UNI) {
@@ -784,8 +726,8 @@ __device__ __forceinline__ void backward_fused_body(double *sh, const double *pc
         if constexpr (PC) { Qr.x += LamI.x; Qr.y += LamI.y; Qr.z += LamI.z; Qr.w += LamI.w; }
         // ---- Tz, Quz, Qzz --------------------------------------------------------------- :570-579
         d4 Quz, Qzz;
-        if constexpr (SIDE) {
-            Quz = zero; Qzz = zero;                   // the side wave forms them meanwhile (fusedpc_side): read behind the refresh
+        if constexpr (PC) {
+            Quz = zero; Qzz = zero;                   // the helper wave forms them meanwhile: read behind the refresh
         } else {
             d4 Tz = PS<NCZ>(V, Fz, zero);
             Quz = PS<NCZ>(Fu, Tz, Luz);
@@ -797,23 +739,19 @@ __device__ __forceinline__ void backward_fused_body(double *sh, const double *pc
         cyc_b += cyc_s1 - cyc_s0;
 #endif
 
-        // ---- X = (Quu + lambda I)^-1 Quz.  Fast path (KP_NS): the inverse changes little from one step to the next,
+        // ---- X = (Quu + lambda I)^-1 Quz.  Fast path: the inverse changes little from one step to the next,
         //      so it is refreshed by Newton-Schulz steps Xinv <- Xinv + Xinv (I - Q Xinv) on the matrix core (4 MFMAs
         //      each, quadratic convergence; the count is chosen from the measured residual so that it ends below
         //      1e-15) and X = Xinv Quz is one more product -- the reference, too, forms the explicit inverse and
         //      multiplies (iLQR.cpp:597-604).  The LDL' path below runs on the first step, on every checked step
         //      (it gives the PD verdict of :587-595), and whenever the residual is too large to converge fast.
         bool done = false;
-#if KP_NS
         int ns_steps = 0;
         // (segment-loop forms: the peeled step is the one right below a key-point -- known at compile time)
-        constexpr bool KINK = KP_KINK4 && UNI && !PC && decltype(may_be_first)::value;
+        constexpr bool KINK = UNI && !PC && decltype(may_be_first)::value;
         const bool refreshed = haveX && !check_pd && kp_inverse_refresh_n<NCU, KINK, PC>(Qr, Iu, Xinv, Xprev, m, STATS ? &ns_steps : nullptr);    // Xinv, Xprev: NEGATED inverses
         if constexpr (STATS) { if (refreshed) hcnt[ns_steps < 0 ? 0 : ns_steps > 3 ? 3 : ns_steps]++; }
-#else
-        const bool refreshed = false;
-#endif
-        if constexpr (SIDE) {                         // mid-step barrier of the triple: Quz, Qzz are published
+        if constexpr (PC) {                           // mid-step barrier of the pair: Quz, Qzz are published
             __syncthreads();
             Quz = lds_tile4(pcbuf + FPC_SIDE_QUZ, lane); Qzz = lds_tile4(pcbuf + FPC_SIDE_QZZ, lane);
         }
@@ -853,7 +791,6 @@ __device__ __forceinline__ void backward_fused_body(double *sh, const double *pc
 #pragma unroll
                 for (int i = 0; i < M; i++) x[i] = sh[FLDS_Z + c * FMZ + i];
                 kp_ldl_solve<M>(Lm, rd, x);
-#if KP_NS
                 // seed the fast path: column c of the inverse in lane c (c < m), as a tile
                 double y[M];
 #pragma unroll
@@ -866,7 +803,6 @@ __device__ __forceinline__ void backward_fused_body(double *sh, const double *pc
                 Xinv.x = -yr[0]; Xinv.y = -yr[1]; Xinv.z = -yr[2]; Xinv.w = -yr[3];       // the running inverse is kept negated
                 Xprev = Xinv;
                 haveX = true;
-#endif
                 if constexpr (STATS) hcnt[4]++;
             } else {
                 if constexpr (STATS) hcnt[5]++;
@@ -890,7 +826,7 @@ __device__ __forceinline__ void backward_fused_body(double *sh, const double *pc
                 if (q == (i & 3)) xr[i >> 2] = x[i];
             Kp.x = -xr[0]; Kp.y = -xr[1]; Kp.z = -xr[2]; Kp.w = -xr[3];
         }
-        if constexpr (KP_BWD_LATE_STORE && !PC) { Kst = Kp; tst = t; }
+        if constexpr (!PC) { Kst = Kp; tst = t; }
         else store_gains(t, Kp);
         // delta_J += k'Q_u + k'Q_uu k = -lambda k'k (:612-613): lanes of column n keep the squares of their rows,
         // the four row groups are added once after the sweep
@@ -915,8 +851,8 @@ __device__ __forceinline__ void backward_fused_body(double *sh, const double *pc
         sh[FLDS_V + (4 + q) * FVS + c] = acc.y;
         sh[FLDS_V + (8 + q) * FVS + c] = acc.z;
         sh[FLDS_V + (12 + q) * FVS + c] = acc.w;
-        if constexpr (SIDE) {
-            accp = acc;                                // symmetrised at the top of the next step, by this wave and by the side wave
+        if constexpr (PC) {
+            accp = acc;                                // symmetrised at the top of the next step, by this wave and by the helper wave
         } else {
             wsync();
             V.x = 0.5 * (acc.x + sh[FLDS_V + c * FVS + q]);
@@ -982,12 +918,7 @@ __device__ __forceinline__ void backward_fused_body(double *sh, const double *pc
             us = unb;
             const int pn = up > 0 ? up - 1 : 0;                    // the next start (position 0 again at the bottom: never used)
             if constexpr (RAW) {
-#if KP_RAW_PAIRS
                 load_col2_n<N>(rP, cr, pn * strideR, pv, pm);
-#else
-                load_col_n<N>(rP, cr, pn * strideR, pv);
-                load_col_n<N>(rP, cr, pn * strideR + offM, pm);
-#endif
                 pmode = __builtin_amdgcn_raw_buffer_load_b32(rP, pn * strideR + kd * KpU * strideR + ((c < n) ? offMode : BIGOFF), 0, 0);
             } else {
                 load_col_n<N>(rT, cu, pn * strideB, pv);
@@ -1013,7 +944,7 @@ __device__ __forceinline__ void backward_fused_body(double *sh, const double *pc
         if (step(T - 1, std::true_type{}))
             for (int t = T - 2; t >= 0; t--) if (!step(t, std::false_type{})) break;
     }
-    if constexpr (KP_BWD_LATE_STORE && !PC) { if (tst >= 0) store_gains(tst, Kst); }      // the last completed step
+    if constexpr (!PC) { if (tst >= 0) store_gains(tst, Kst); }      // the last completed step
     dJ *= -lam;
     dJ += __shfl_xor(dJ, 16);
     dJ += __shfl_xor(dJ, 32);
@@ -1037,7 +968,7 @@ k_backward_fused_stats(RecLayout L, FusedArgs F, int T, const double *__restrict
                        double *__restrict__ delta_J, int *__restrict__ status, int *__restrict__ hist)
 {
     __shared__ __attribute__((aligned(16))) double sh[FLDS_TOTAL];
-    backward_fused_body<N, M, false, false, false, false, false, true>(sh, nullptr, nullptr, L, F, T, lambda, pd_stride, Kout, kout, delta_J, status, hist);
+    backward_fused_body<N, M, false, false, false, false, true>(sh, nullptr, nullptr, L, F, T, lambda, pd_stride, Kout, kout, delta_J, status, hist);
 }
 
 // The one-wave backward sweep comes in two forms, launched back to back like the forward sweep's: UNI for key-point sets in
@@ -1051,7 +982,7 @@ k_backward_fused(RecLayout L, FusedArgs F, int T, const double *__restrict__ lam
 {
     __shared__ __attribute__((aligned(16))) double sh[FLDS_TOTAL];
     if ((*kp_uniform != 0) != UNI) return;
-    backward_fused_body<N, M, false, RU0, false, RAW, UNI, false, RXC>(sh, nullptr, nullptr, L, F, T, lambda, pd_stride, Kout, kout, delta_J, status);
+    backward_fused_body<N, M, false, RU0, RAW, UNI, false, RXC>(sh, nullptr, nullptr, L, F, T, lambda, pd_stride, Kout, kout, delta_J, status);
 }
 template <int N, int M, bool RU0, bool RAW, bool UNI, bool RXC = false>
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1)))
@@ -1061,7 +992,7 @@ k_backward_fused_excl(RecLayout L, FusedArgs F, int T, const double *__restrict_
 {
     __shared__ __attribute__((aligned(16))) double sh[FLDS_TOTAL];
     if ((*kp_uniform != 0) != UNI) return;
-    backward_fused_body<N, M, false, RU0, false, RAW, UNI, false, RXC>(sh, nullptr, nullptr, L, F, T, lambda, pd_stride, Kout, kout, delta_J, status);
+    backward_fused_body<N, M, false, RU0, RAW, UNI, false, RXC>(sh, nullptr, nullptr, L, F, T, lambda, pd_stride, Kout, kout, delta_J, status);
 }
 
 
@@ -1188,9 +1119,9 @@ struct DownTrackerSlp {
     __device__ __forceinline__ double value(int i, double dt) const { return lerp_nc(sv[i], dt, av[i]); }
 };
 
-// The same walking the KEY-POINT ORDERED FD PAYLOAD (producer wave of the pair / triple, RAWP): the prefetched x+ / x- of the
+// The same walking the KEY-POINT ORDERED FD PAYLOAD (helper wave of the pair, RAWP): the prefetched x+ / x- of the
 // next segment start are differenced when the lane reaches it -- (x+ - x-) / (2 eps), / eps for a one-sided job: the arithmetic
-// and the bytes of k_fd_kp_difference -- and the column goes out to kpc for the forward sweep.  The producer is a step ahead of the
+// and the bytes of k_fd_kp_difference -- and the column goes out to kpc for the forward sweep.  The helper is a step ahead of the
 // consumer and not the longer wave: the differencing costs the sweep nothing (a streaming kernel in front of it: 0.09 ... 0.41 ms
 // at 128 ... 512 trajectories).  Values 0..3 of a lane belong to its A column (kind 0 / 1), 4..7 to its B column (kind 2).
 struct DownTrackerRaw {
@@ -1198,17 +1129,13 @@ struct DownTrackerRaw {
     int offs[NV];
     int lo, idx, s, nb, nb2, pmode, bitA;
     double sv[NV], av[NV], pv[NV], pm[NV];
-    int E0, NE, strideR, offM, offMode, strideB;
+    int E0, NE, strideR, offMode, strideB;
     bool has, fresh;                             // fresh: pv / pm still hold x+ / x- (not differenced yet)
     __device__ __forceinline__ void load_raw(__amdgpu_buffer_rsrc_t rP, int e_rel, double *xp, double *xm, int &mo) const
     {
         const int base = ((unsigned)e_rel < (unsigned)NE) ? e_rel * strideR : BIGOFF;
 #pragma unroll
-#if KP_RAW_PAIRS
         for (int r = 0; r < NV; r++) fbld2(rP, base + dbl_off(offs[r]), xp[r], xm[r]);      // (x+, x-) of an element: one 16-byte load
-#else
-        for (int r = 0; r < NV; r++) { xp[r] = fbld(rP, base + offs[r]); xm[r] = fbld(rP, base + offM + offs[r]); }
-#endif
         mo = __builtin_amdgcn_raw_buffer_load_b32(rP, base + (has ? offMode : BIGOFF), 0, 0);
     }
     __device__ __forceinline__ void diff(double *xp, const double *xm, int mo, double eps2, double rinv2) const
@@ -1229,7 +1156,7 @@ struct DownTrackerRaw {
                                          size_t list, int E0_, int NE_, int n, bool pos_col, double eps2, double rinv2)
     {
         E0 = E0_; NE = NE_; has = has_;
-        strideB = 3 * n * 8; strideR = (6 * n + 2) * 8; offM = 3 * n * 8; offMode = 6 * n * 8;
+        strideB = 3 * n * 8; strideR = (6 * n + 2) * 8; offMode = 6 * n * 8;
         bitA = pos_col ? 1 : 2;
         lo = has ? kp_offsets[list] : 0;
         const int hi = has ? kp_offsets[list + 1] : 0;
@@ -1286,25 +1213,19 @@ struct DownTrackerRaw {
 };
 
 // ---------------------------------------------------------------------------------------------------------
-// Backward pass, PRODUCER / CONSUMER wave pair per trajectory.  Unlike the U/Z split above the dependency runs one
-// way only: the producer wave evaluates what does not depend on V' -- this step's A, B columns (a4) and the cost
-// tiles Lzz = Rz'WRz, [l_uu | l_u] = Ru'W[Ru | r] (a6) -- one step AHEAD of the consumer and hands them over through a
-// two-slot LDS ring; the consumer wave runs the Riccati chain proper (backward_fused_body<.., PC = true>).  One
-// s_barrier per step: at the end of step t the consumer has read slot t&1 and the producer has filled slot (t-1)&1.
-// Two waves per SIMD at batch = #SIMDs: the producer's independent MFMAs and FP64 FMAs issue into the bubbles of the
-// consumer's dependent chain.
-// HELPER (consumer / helper pair, 256 < batch <= 512: two SIMDs per trajectory): ONE wave is the triple's producer AND its side
-// wave -- at the top of step t the side products Tz = V Fz, Quz, Qzz (operands kept in registers since they were published), and,
-// between the mid-step barrier and the end of the step (while the consumer forms the gains and V'), the tiles of step t-1.
-// RU0 / RXC (helper only): r_u = 0 -- no r_u loads, no [l_uu | l_u] product, the ring's LU tiles stay zero; ONE constant r_x in
+// Backward pass, consumer / helper wave pair per trajectory (2 x batch <= #SIMDs: a SIMD each).  The consumer wave runs the
+// Riccati chain proper (backward_fused_body<.., PC = true>).  The helper wave evaluates what does not depend on the gains: this
+// step's A, B columns (a4) and the cost tiles Lzz = Rz'WRz, [l_uu | l_u] = Ru'W[Ru | r] (a6), one step AHEAD of the consumer and
+// handed over through a two-slot LDS ring, and the side products -- at the top of step t Tz = V Fz, Quz, Qzz (operands kept in
+// registers since they were published), and, between the mid-step barrier and the end of the step (while the consumer forms the
+// gains and V'), the tiles of step t-1.
+// RU0 / RXC: r_u = 0 -- no r_u loads, no [l_uu | l_u] product, the ring's LU tiles stay zero; ONE constant r_x in
 // registers (see backward_fused_body).
-// SLP (helper only, differenced column store): per-DoF lists walked on the slope store (DownTrackerSlp).
-template <int N, int M, bool TRIPLE = false, bool RAWP = false, bool HELPER = false, bool RU0 = false, bool RXC = false, bool SLP = false>
+// SLP (differenced column store): per-DoF lists walked on the slope store (DownTrackerSlp).
+template <int N, int M, bool RAWP = false, bool RU0 = false, bool RXC = false, bool SLP = false>
 __device__ __forceinline__ void fusedpc_producer(double *pcbuf, int *sflag, RecLayout L, FusedArgs F, int T, const double *sh = nullptr)
 {
-    static_assert(HELPER && TRIPLE, "only the helper wave of the consumer / helper pair is left (two barriers per step)");
-    static_assert(!SLP || (HELPER && !RAWP), "the slope store serves the helper on a differenced column store");
-    static_assert(HELPER || (!RU0 && !RXC), "RU0 / RXC are the helper's instantiations");
+    static_assert(!SLP || !RAWP, "the slope store serves the helper on a differenced column store");
     static_assert(!RXC || RU0, "RXC comes with RU0");
     constexpr int n = N, m = M;
     const int lane = threadIdx.x & 63, c = lane & 15, q = lane >> 4;
@@ -1322,7 +1243,7 @@ __device__ __forceinline__ void fusedpc_producer(double *pcbuf, int *sflag, RecL
             tr.offs[r] = (row < n && c < n) ? 8 * ((c < F.dof ? 0 : n) + row) : BIGOFF;
             tr.offs[4 + r] = (row < n && c < m) ? 8 * (2 * n + row) : BIGOFF;
             oRx[r] = (row < nr && c < n) ? 8 * (row * n + c) : OOBF;
-            oR1[r] = (row < nr && (c == n || (KP_RXC_CXX && RXC))) ? 8 * row : OOBF;      // (RXC: r[k] in every column, see CXX in backward_fused_body)
+            oR1[r] = (row < nr && (c == n || RXC)) ? 8 * row : OOBF;      // (RXC: r[k] in every column, see CXX in backward_fused_body)
             oRu[r] = (row < nr && c < m) ? 8 * (row * m + c) : OOBF;
             wr[r] = (row < nr) ? 2.0 * F.w_run[row] : 0.0;
             wt[r] = (row < nr) ? 2.0 * F.w_term[row] : 0.0;
@@ -1337,7 +1258,7 @@ __device__ __forceinline__ void fusedpc_producer(double *pcbuf, int *sflag, RecL
     const double *rxb = F.r_x + (size_t)b * (T + 1) * nr * n;
     const double *rub = F.r_u + (size_t)b * (T + 1) * nr * m;
     d4 Rx, R1, Ru;
-    // (HELPER: the steps are asked for in order, T-1 first -- running pointers, as in backward_fused_body; with the 64-bit
+    // (the steps are asked for in order, T-1 first -- running pointers, as in backward_fused_body; with the 64-bit
     // (step x size) products the compiler formed the descriptors on the VALU and wrapped every load in a waterfall loop)
     const double *pRx = rxb + (size_t)(T - 1) * nr * n, *pR1 = rb + (size_t)(T - 1) * nr, *pRu = rub + (size_t)(T - 1) * nr * m;
     (void)pRx; (void)pR1; (void)pRu;
@@ -1352,7 +1273,7 @@ __device__ __forceinline__ void fusedpc_producer(double *pcbuf, int *sflag, RecL
         if constexpr (!RU0) { Ru.x = fbld(rU, oRu[0]); Ru.y = fbld(rU, oRu[1]); Ru.z = fbld(rU, oRu[2]); Ru.w = fbld(rU, oRu[3]); }
     };
     // CXX: the constant block r_x' W r_x as a resident tile, Lzz~ = Cxx + 2 e_n (r_x' W r)' by ONE product (backward_fused_body)
-    constexpr bool CXX = KP_RXC_CXX && RXC;
+    constexpr bool CXX = RXC;
     d4 Cxx = zero, RxW = zero;
     const double en2 = (c == n) ? 2.0 : 0.0;
     const u64 mask_r1 = (c == n) ? ~0ull : 0ull;
@@ -1380,8 +1301,7 @@ __device__ __forceinline__ void fusedpc_producer(double *pcbuf, int *sflag, RecL
     (void)rP;
 #pragma unroll
     for (int r = 0; r < 4; r++) if (c == n && 4 * r + q == n) tr.sv[r] = 1.0;       // Fz(n,n) = 1
-    d4 hFz = zero, hFu = zero, hLzz = zero, hLU = zero;            // HELPER: the tiles published last, for the side products of their step
-    (void)hFz; (void)hFu; (void)hLzz; (void)hLU;
+    d4 hFz = zero, hFu = zero, hLzz = zero, hLU = zero;            // the tiles published last, for the side products of their step
     auto publish = [&](int t, const d4 &W2, auto terminal) __attribute__((always_inline)) {
         const double dt = (double)(t - tr.s);
         d4 Fz, Fu, Rz, Rur, Lzz;
@@ -1409,59 +1329,56 @@ __device__ __forceinline__ void fusedpc_producer(double *pcbuf, int *sflag, RecL
         double *tb = pcbuf + (t & 1) * FPC_BUF;
         // (Fz is the side products' operand only: it stays in this wave's registers)
         lds_store4(tb + 256, lane, Fu);
-        // (Lzz: the consumer of the triple / helper pair reads it at the terminal step only, V = Lzz(T-1); the side products take it
+        // (Lzz: the consumer of the pair reads it at the terminal step only, V = Lzz(T-1); the side products take it
         // from registers here)
         if (t == T - 1) lds_store4(tb + 512, lane, Lzz);
         if constexpr (!RU0) lds_store4(tb + 768, lane, LU);
-        if constexpr (HELPER) { hFz = Fz; hFu = Fu; hLzz = Lzz; hLU = LU; }
+        hFz = Fz; hFu = Fu; hLzz = Lzz; hLU = LU;
     };
     load_res(T - 1);
     if (lane == 0) sflag[0] = 0;
     publish(T - 1, Wt, std::true_type{});                 // terminal weights   (iLQR.cpp:537-539)
     __syncthreads();
-    if constexpr (HELPER) {
-        constexpr int NCZ = (N + 1 + 3) / 4;
-        constexpr int REG_NN = n >> 2;
-        const bool lane_nn = (c == n) && (q == (n & 3));
-        const u64 mask_n = (c == n) ? ~0ull : 0ull;
-        // everything of step t that hangs on V but not on the gains (fusedpc_side), from the tiles this wave published for it
-        auto side = [&](int t) __attribute__((always_inline)) {
-            d4 V = hLzz;                                   // V_xx = l_xx[T-1]   (iLQR.cpp:537-539)
-            if (t < T - 1) {                               // (V' + V'')/2 from the consumer's unsymmetrised image, as the consumer forms it
-                V.x = 0.5 * (sh[FLDS_V + (q) * FVS + c] + sh[FLDS_V + c * FVS + q]);
-                V.y = 0.5 * (sh[FLDS_V + (4 + q) * FVS + c] + sh[FLDS_V + c * FVS + 4 + q]);
-                V.z = 0.5 * (sh[FLDS_V + (8 + q) * FVS + c] + sh[FLDS_V + c * FVS + 8 + q]);
-                V.w = 0.5 * (sh[FLDS_V + (12 + q) * FVS + c] + sh[FLDS_V + c * FVS + 12 + q]);
-                if (lane_nn) fset_reg<REG_NN>(V, 0.0);
-            }
-            d4 Luz;
-            Luz.x = bits_and(hLU.x, mask_n); Luz.y = bits_and(hLU.y, mask_n); Luz.z = bits_and(hLU.z, mask_n); Luz.w = bits_and(hLU.w, mask_n);
-            const d4 Tz = PS<NCZ>(V, hFz, zero);
-            const d4 Quz = PS<NCZ>(hFu, Tz, Luz);
-            const d4 Qzz = PS<NCZ>(hFz, Tz, hLzz);
-            lds_store4(pcbuf + FPC_SIDE_QUZ, lane, Quz);
-            lds_store4(pcbuf + FPC_SIDE_QZZ, lane, Qzz);
-        };
-        for (int t = T - 1; t > 0; t--) {
-            side(t);
-            __syncthreads();                               // mid-step: the consumer takes Quz, Qzz
-            // the tiles of step t-1, while the consumer forms the gains and V' of step t (slot (t-1)&1 was last read at the top of step t+1)
-            // (the crossing's arithmetic in front of the wait for the residual tiles, its requests behind it)
-            // (the prefetched x+ / x- are differenced BEHIND the publish, whose wait for the residual tiles has let them arrive)
-            if constexpr (RAWP) tr.cross(rT, t - 1, F.eps2, F.rinv_2eps);
-            else tr.cross(t - 1);
-            publish(t - 1, Wr, std::false_type{});
-            if constexpr (RAWP) { tr.settle(rT, F.eps2, F.rinv_2eps); tr.request(rP, F.kp_times); }
-            else if constexpr (SLP) tr.request(rP, F.kp_times, 2 * strideB);
-            else tr.request(rT, F.kp_times, strideB);
-            __syncthreads();                               // end of step: V of step t-1 is there
-            if (__builtin_amdgcn_readfirstlane(sflag[0])) return;     // (wave-uniform: a divergent exit makes t a per-lane value and every request a waterfall loop)
+    constexpr int NCZ = (N + 1 + 3) / 4;
+    constexpr int REG_NN = n >> 2;
+    const bool lane_nn = (c == n) && (q == (n & 3));
+    const u64 mask_n = (c == n) ? ~0ull : 0ull;
+    // everything of step t that hangs on V but not on the gains, from the tiles this wave published for it
+    auto side = [&](int t) __attribute__((always_inline)) {
+        d4 V = hLzz;                                   // V_xx = l_xx[T-1]   (iLQR.cpp:537-539)
+        if (t < T - 1) {                               // (V' + V'')/2 from the consumer's unsymmetrised image, as the consumer forms it
+            V.x = 0.5 * (sh[FLDS_V + (q) * FVS + c] + sh[FLDS_V + c * FVS + q]);
+            V.y = 0.5 * (sh[FLDS_V + (4 + q) * FVS + c] + sh[FLDS_V + c * FVS + 4 + q]);
+            V.z = 0.5 * (sh[FLDS_V + (8 + q) * FVS + c] + sh[FLDS_V + c * FVS + 8 + q]);
+            V.w = 0.5 * (sh[FLDS_V + (12 + q) * FVS + c] + sh[FLDS_V + c * FVS + 12 + q]);
+            if (lane_nn) fset_reg<REG_NN>(V, 0.0);
         }
-        side(0);
-        __syncthreads();
-        __syncthreads();
-        return;
+        d4 Luz;
+        Luz.x = bits_and(hLU.x, mask_n); Luz.y = bits_and(hLU.y, mask_n); Luz.z = bits_and(hLU.z, mask_n); Luz.w = bits_and(hLU.w, mask_n);
+        const d4 Tz = PS<NCZ>(V, hFz, zero);
+        const d4 Quz = PS<NCZ>(hFu, Tz, Luz);
+        const d4 Qzz = PS<NCZ>(hFz, Tz, hLzz);
+        lds_store4(pcbuf + FPC_SIDE_QUZ, lane, Quz);
+        lds_store4(pcbuf + FPC_SIDE_QZZ, lane, Qzz);
+    };
+    for (int t = T - 1; t > 0; t--) {
+        side(t);
+        __syncthreads();                               // mid-step: the consumer takes Quz, Qzz
+        // the tiles of step t-1, while the consumer forms the gains and V' of step t (slot (t-1)&1 was last read at the top of step t+1)
+        // (the crossing's arithmetic in front of the wait for the residual tiles, its requests behind it)
+        // (the prefetched x+ / x- are differenced BEHIND the publish, whose wait for the residual tiles has let them arrive)
+        if constexpr (RAWP) tr.cross(rT, t - 1, F.eps2, F.rinv_2eps);
+        else tr.cross(t - 1);
+        publish(t - 1, Wr, std::false_type{});
+        if constexpr (RAWP) { tr.settle(rT, F.eps2, F.rinv_2eps); tr.request(rP, F.kp_times); }
+        else if constexpr (SLP) tr.request(rP, F.kp_times, 2 * strideB);
+        else tr.request(rT, F.kp_times, strideB);
+        __syncthreads();                               // end of step: V of step t-1 is there
+        if (__builtin_amdgcn_readfirstlane(sflag[0])) return;     // (wave-uniform: a divergent exit makes t a per-lane value and every request a waterfall loop)
     }
+    side(0);
+    __syncthreads();
+    __syncthreads();
 }
 
 #define FPC_RING FLDS_TOTAL
@@ -1469,7 +1386,7 @@ __device__ __forceinline__ void fusedpc_producer(double *pcbuf, int *sflag, RecL
 #define FPC_TOTAL (FPC_FLAG + 2)
 // guard: -1 run, 1 run only when the device flag says the key-point set is uniform, 0 only when it is not (the raw helper is
 // launched for uniform sets; per-DoF lists go through k_fd_kp_difference and the plain / slope-store helper, launched behind it)
-// Consumer / helper pair (2 x batch <= #SIMDs: a SIMD each): the triple's consumer, and ONE wave for its side and producer roles
+// Consumer / helper pair (2 x batch <= #SIMDs: a SIMD each)
 template <int N, int M, bool RAWP, bool RU0, bool RXC, bool SLP = false>
 __global__ void __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(1, 1)))
 k_backward_fusedph(RecLayout L, FusedArgs F, int T, int role_shift, const double *__restrict__ lambda,
@@ -1480,10 +1397,10 @@ k_backward_fusedph(RecLayout L, FusedArgs F, int T, int role_shift, const double
     if (guard >= 0 && (*kp_uniform != 0) != (guard != 0)) return;
     const bool consumer = ((__builtin_amdgcn_readfirstlane(threadIdx.x >> 6) ^ (blockIdx.x >> role_shift)) & 1) == 0;
     if (consumer)
-        backward_fused_body<N, M, true, RU0, true>(sh, sh + FPC_RING, (int *)(sh + FPC_FLAG), L, F, T, lambda, pd_stride, Kout, kout,
+        backward_fused_body<N, M, true, RU0>(sh, sh + FPC_RING, (int *)(sh + FPC_FLAG), L, F, T, lambda, pd_stride, Kout, kout,
                                                    delta_J, status);
     else
-        fusedpc_producer<N, M, true, RAWP, true, RU0, RXC, SLP>(sh + FPC_RING, (int *)(sh + FPC_FLAG), L, F, T, sh);
+        fusedpc_producer<N, M, RAWP, RU0, RXC, SLP>(sh + FPC_RING, (int *)(sh + FPC_FLAG), L, F, T, sh);
 }
 // ---------------------------------------------------------------------------------------------------------
 // Forward pass.  The column tracker walks UP in time; its tiles (row = A row, col = A column) are turned into
@@ -1544,7 +1461,7 @@ __device__ __forceinline__ void forward_fused_body(RecLayout L, FusedArgs F, int
     // so that registers (0, 1) and (2, 3) of a lane are CONSECUTIVE residuals and r_t arrives with two 16-byte requests instead of four
     // 8-byte ones (a request costs this sweep ~24 cycles of its 1 330-cycle step whatever it carries: timing probe in
     // profiles/r05_headline_ab.txt).  The order is a relabelling of the rows of the resident r_x tile and of the per-row constants.
-    constexpr bool RV2 = KP_FWD_RV2 && UNI;        // (the per-DoF list form measured 1.3 % SLOWER with it: 2.31 against 2.28 ms)
+    constexpr bool RV2 = UNI;        // (the per-DoF list form measured 1.3 % SLOWER with it: 2.31 against 2.28 ms)
     auto sig = [](int i) { return RV2 ? 8 * (i >> 3) + 2 * (i & 3) + ((i >> 2) & 1) : i; };
     const int cs = sig(c);                                                  // the residual in column c of the RxT operand
     const int oR2[2] = {(2 * q < nr) ? 16 * q : OOBF, (8 + 2 * q < nr) ? 64 + 16 * q : OOBF};
@@ -1633,9 +1550,6 @@ __device__ __forceinline__ void forward_fused_body(RecLayout L, FusedArgs F, int
     int s = has ? F.kp_times[idx] : 0;                                  // == 0 for canonical key-points
     int e = (has && idx + 1 < khi) ? F.kp_times[idx + 1] : BIGT;
     int nb = (has && idx + 2 < khi) ? F.kp_times[idx + 2] : BIGT;
-    // Walking up, a segment is entered at its START key-point, where the stored value is exact and the slope is
-    // not needed yet: the end column is requested at the crossing and the slope formed one step later
-    // (`pend`), so no second prefetch buffer is held.
     // General form (!UNI): the slope store of k_kp_slopes gives every segment's slope with its start column -- requested one
     // crossing ahead (ev, ea), so a crossing is register moves and nothing is waited for at the step behind it.
     double sv[8], ev[8], av[8], ea[8];
@@ -1643,15 +1557,12 @@ __device__ __forceinline__ void forward_fused_body(RecLayout L, FusedArgs F, int
     __amdgpu_buffer_rsrc_t rS = rT;
     load_col(rT, co, has ? idx - E0 : -1, NE, strideB, sv);
     load_col(rT, co, (has && idx + 1 < khi) ? idx + 1 - E0 : -1, NE, strideB, ev);
-    bool pend = true;
 #pragma unroll
     for (int i = 0; i < 8; i++) av[i] = 0.0;
-    constexpr bool FSLP = KP_SLOPES && !UNI;
-    if constexpr (FSLP) {
+    if constexpr (!UNI) {
         rS = frsrc(F.kps + (size_t)E0 * 6 * L.n, NE * 2 * strideB);
         load_col2(rS, co, has ? idx - E0 : -1, NE, 2 * strideB, sv, av);
         load_col2(rS, co, (has && idx + 1 < khi) ? idx + 1 - E0 : -1, NE, 2 * strideB, ev, ea);
-        pend = false;
     }
     // the identity rows of Ya (alpha and the homogeneous 1 carry over): lanes c >= n walk no list
 #pragma unroll
@@ -1673,7 +1584,7 @@ __device__ __forceinline__ void forward_fused_body(RecLayout L, FusedArgs F, int
     // A NEGATIVE weight (legal: the reference just forms w r^2) keeps its sign outside the root: the rows are scaled by sqrt|w_k|, every
     // register accumulates its own residual's terms (acc4: register r of lane (c, q) is residual 4r + q throughout), and the signs
     // join once, behind the sweep (the final step, whose terminal weights have signs of their own, is added with them directly).
-    constexpr bool SQW = KP_FWD_SQW && RXC && RU0 && UNI;
+    constexpr bool SQW = RXC && RU0 && UNI;
     double s2run[4] = {0.0, 0.0, 0.0, 0.0}, s2term[4] = {0.0, 0.0, 0.0, 0.0}, sgrun[4] = {1.0, 1.0, 1.0, 1.0}, sgterm[4] = {1.0, 1.0, 1.0, 1.0};
     double acc4[4] = {0.0, 0.0, 0.0, 0.0};
     (void)s2run; (void)s2term; (void)RxTt; (void)sgrun; (void)sgterm; (void)acc4;
@@ -1713,8 +1624,8 @@ __device__ __forceinline__ void forward_fused_body(RecLayout L, FusedArgs F, int
         Yb.x = shB[c * 17 + q];                Yb.y = NCU > 1 ? shB[c * 17 + 4 + q] : 0.0;
         Yb.z = NCU > 2 ? shB[c * 17 + 8 + q] : 0.0; Yb.w = NCU > 3 ? shB[c * 17 + 12 + q] : 0.0;
     };
-    auto advance = [&](int t) {
-        if constexpr (FSLP) {
+    auto advance = [&](int t) {             // the general form's per-lane tracker
+        if constexpr (!UNI) {
             // A lane that reaches the end key-point of its segment takes the (value, slope) pairs requested a crossing ago -- register
             // moves -- and requests the pairs of the segment after.  The REQUESTS are issued by ALL lanes, behind a wave-uniform
             // branch ("some lane crosses"): a lane that does not cross re-requests the entry it already holds.  With the loads inside
@@ -1733,22 +1644,6 @@ __device__ __forceinline__ void forward_fused_body(RecLayout L, FusedArgs F, int
                 load_col2(rS, co, en, NE, 2 * strideB, ev, ea);
                 nb = (idx + 2 < khi) ? F.kp_times[idx + 2] : BIGT;
             }
-            return;
-        }
-        if (pend) {                           // slope of the segment entered one step ago (its end column has landed)
-            const double den = (double)(e - s);
-            const double rinv = kp_rcp(den);
-#pragma unroll
-            for (int i = 0; i < 8; i++) av[i] = (e != BIGT) ? fdiv(ev[i] - sv[i], den, rinv) : 0.0;
-            pend = false;
-        }
-        if (t >= e) {                         // per lane: reached the end key-point of the segment
-#pragma unroll
-            for (int i = 0; i < 8; i++) { sv[i] = ev[i]; av[i] = 0.0; }
-            s = e; e = nb; idx++;
-            load_col(rT, co, (idx + 1 < khi) ? idx + 1 - E0 : -1, NE, strideB, ev);
-            nb = (idx + 2 < khi) ? F.kp_times[idx + 2] : BIGT;
-            pend = true;
         }
     };
     // Y operands: step t uses (Ya, Yb); during step t the tiles of step t+1 are fetched from LDS (staged during
@@ -1800,7 +1695,7 @@ __device__ __forceinline__ void forward_fused_body(RecLayout L, FusedArgs F, int
         // TRIM (round 5, the uniform form): the product starts from zero and u_nom joins on the VALU in the registers that hold
         // controls -- as the accumulator's initial value the tile had to be assembled first: seven moves per step -- and the clamp is
         // v_min / v_max: 1.74 -> 1.68 ms.  (The general form measured 3 % SLOWER with the same change and keeps the old code.)
-        constexpr bool TRIM = KP_FWD_TRIM && UNI;
+        constexpr bool TRIM = UNI;
         d4 U = PS<NCZ>(Yk, Z, TRIM ? zero : ub);       // (u_nom +) K dx + alpha k   (:879)
         __builtin_amdgcn_sched_barrier(0);
         cur.YkK.x = fblds(rK, oK[0], sK); cur.YkK.y = fblds(rK, oK[1], sK); cur.YkK.z = fblds(rK, oK[2], sK); cur.YkK.w = fblds(rK, oK[3], sK);
@@ -2169,9 +2064,9 @@ __device__ __forceinline__ void forward_sc_state(double *sh, RecLayout L, int T,
     for (int k = 0; k < KP_FSC_SETS - 1; k++) if (t + k < T) step(t + k, S[k]);
 }
 
-// ROLE 0: score and stage (second wave of the pair); 1: score only; 2: stage the A, B columns only (third wave of the triple)
+// ROLE 1: score only (the cost wave); 2: stage the A, B columns only (third wave of the triple)
 // RU0: r_u = 0 (no r_u tiles, no Ju product); RXC (with RU0): ONE constant r_x, its transposed tile in registers (forward_fused_body)
-template <int NCZ, int NCU, int ROLE = 0, bool RU0 = false, bool RXC = false>
+template <int NCZ, int NCU, int ROLE, bool RU0 = false, bool RXC = false>
 __device__ __forceinline__ void forward_sc_cost(double *sh, RecLayout L, FusedArgs F, int T, int n_alpha, double *__restrict__ cost_pred)
 {
     const int n = L.n, m = L.m;
@@ -2231,7 +2126,7 @@ __device__ __forceinline__ void forward_sc_cost(double *sh, RecLayout L, FusedAr
     int e = (has && idx + 1 < khi) ? F.kp_times[idx + 1] : BIGT;
     int nb = (has && idx + 2 < khi) ? F.kp_times[idx + 2] : BIGT;
     double sv[8], ev[8], av[8];
-    if (ROLE != 1) {
+    if (ROLE == 2) {
         load_col(rT, co, has ? idx - E0 : -1, NE, strideB, sv);
         load_col(rT, co, (has && idx + 1 < khi) ? idx + 1 - E0 : -1, NE, strideB, ev);
     }
@@ -2268,7 +2163,7 @@ __device__ __forceinline__ void forward_sc_cost(double *sh, RecLayout L, FusedAr
     // iteration t: score step t-1 (tiles re-requested for step t+1 right behind their use), then stage the A, B columns of
     // step t+1 for wave S
     auto iter = [&](int t, CTiles &s_) {               // s_ holds the tiles of step t-1
-        if (ROLE != 2 && t >= 1) {
+        if (ROLE == 1 && t >= 1) {
             const int tt = t - 1;
             const double *zs = sh + FSC_ZS + (tt & 1) * 512;
             const d4 Zt = lds_tile4(zs, lane);
@@ -2293,15 +2188,15 @@ __device__ __forceinline__ void forward_sc_cost(double *sh, RecLayout L, FusedAr
                      + wcur[2] * (Jx.z * (r2.z + Jx.z) + Ju.z * (r2.z + Ju.z))
                      + wcur[3] * (Jx.w * (r2.w + Jx.w) + Ju.w * (r2.w + Ju.w));
         }
-        if (ROLE != 1 && t + 1 < T) { advance(t + 1); stage_cols(t + 1); }
+        if (ROLE == 2 && t + 1 < T) { advance(t + 1); stage_cols(t + 1); }
         if (t < T) __syncthreads();
     };
     CTiles S[KP_FSC_SETS];                             // set k: the steps congruent k mod KP_FSC_SETS
-    if (ROLE != 2) {
+    if (ROLE == 1) {
 #pragma unroll
         for (int k = 0; k < KP_FSC_SETS; k++) request(k, S[k]);
     }
-    if (ROLE != 1) stage_cols(0);
+    if (ROLE == 2) stage_cols(0);
     __syncthreads();
     iter(0, S[KP_FSC_SETS - 1]);                       // (scores nothing: stages the columns of step 1)
     int t = 1;
@@ -2313,21 +2208,7 @@ __device__ __forceinline__ void forward_sc_cost(double *sh, RecLayout L, FusedAr
     for (int k = 0; k < KP_FSC_SETS - 1; k++) if (t + k <= T) iter(t + k, S[k]);
     partial += __shfl_xor(partial, 16);
     partial += __shfl_xor(partial, 32);
-    if (ROLE != 2 && q == 0 && c < n_alpha) cost_pred[(size_t)b * n_alpha + c] = partial;
-}
-
-template <int NCZ, int NCU, bool RU0 = false, bool RXC = false>
-__global__ void __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(1, 1)))
-k_forward_fused_sc(RecLayout L, FusedArgs F, int T, int n_alpha, const double *__restrict__ Kin,
-                   const double *__restrict__ kin, const double *__restrict__ u_nom, const double *__restrict__ ctrl_lim,
-                   const double *__restrict__ alphas, double *__restrict__ cost_pred, double *__restrict__ U_alpha,
-                   const int *__restrict__ kp_uniform, int only_ragged)
-{
-    __shared__ __attribute__((aligned(16))) double sh[FSC_TOTAL];
-    if (only_ragged && *kp_uniform != 0) return;       // (launched behind k_forward_fused_scu, which has run the uniform set)
-    const bool state = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6) == 0;
-    if (state) forward_sc_state<NCZ, NCU, RU0>(sh, L, T, n_alpha, Kin, kin, u_nom, ctrl_lim, alphas, U_alpha);
-    else       forward_sc_cost<NCZ, NCU, 0, RU0, RXC>(sh, L, F, T, n_alpha, cost_pred);
+    if (ROLE == 1 && q == 0 && c < n_alpha) cost_pred[(size_t)b * n_alpha + c] = partial;
 }
 
 // UNIFORM key-point sets: state wave (with its own a4) + scoring wave -- no staging wave, whatever the batch up to #SIMDs / 2.
@@ -2346,8 +2227,8 @@ k_forward_fused_scu(RecLayout L, FusedArgs F, int T, int n_alpha, const double *
     else       forward_sc_cost<NCZ, NCU, 1, RU0, RXC>(sh, L, F, T, n_alpha, cost_pred);
 }
 
-// state + cost + staging waves (4 x batch <= #SIMDs: one 3-wave workgroup per CU): the cost wave of the pair is the longer
-// one (1 360 vs 1 130 cycles per step); its a4 half goes to a third wave
+// state + cost + staging waves (4 x batch <= #SIMDs: one 3-wave workgroup per CU): a cost wave that also stages is the longer
+// one of a pair (1 360 vs 1 130 cycles per step), so its a4 half goes to a third wave
 template <int NCZ, int NCU, bool RU0 = false, bool RXC = false>
 __global__ void __launch_bounds__(192) __attribute__((amdgpu_waves_per_eu(1, 1)))
 k_forward_fused_sc3(RecLayout L, FusedArgs F, int T, int n_alpha, const double *__restrict__ Kin,
@@ -2394,16 +2275,17 @@ int backward_fused_form(const Ctx *c)
     return (f == 1 || f == 5) ? f : (2 * c->d.batch <= c->n_simd ? 5 : 1);
 }
 
-// The wave organisation launch_forward_fused will pick: 1 one wave per trajectory, 2 state / cost + staging pair, 3 the state /
-// cost / staging triple, 4 (the default while 2 x batch <= #SIMDs) the state / cost pair for UNIFORM key-point sets -- the state
-// wave interpolates its own operands, no staging wave -- with the triple (4 x batch <= #SIMDs) or the one-wave general form
-// behind it for per-DoF lists; the device flag decides which of the two runs.  Late round 4, with r_u = 0 / constant-r_x
-// instantiations of the scoring wave and a state wave that issues 7 loads per step instead of 10 (profiles/r04_forward_forms.txt):
-// 1.31 / 1.43 / 1.47 ms at 1 / 64 / 256 trajectories (one wave per trajectory: 1.72).
+// The wave organisation launch_forward_fused will pick: 1 one wave per trajectory, 3 the state / cost / staging triple, 4 (the
+// default while 2 x batch <= #SIMDs) the state / cost pair for UNIFORM key-point sets -- the state wave interpolates its own
+// operands, no staging wave -- with the triple (4 x batch <= #SIMDs) or the one-wave general form behind it for per-DoF lists;
+// the device flag decides which of the two runs.  Late round 4, with r_u = 0 / constant-r_x instantiations of the scoring wave and
+// a state wave that issues 7 loads per step instead of 10 (profiles/r04_forward_forms.txt): 1.31 / 1.43 / 1.47 ms at 1 / 64 / 256
+// trajectories (one wave per trajectory: 1.72).  KPILQR_FUSED_FWD_WAVES = 1 | 3 | 4 forces a form (diagnostic,
+// include/kpilqr.h); any other value is ignored, as in backward_fused_form.
 int forward_fused_form(const Ctx *c)
 {
-    if (c->tune.fused_fwd_waves) return c->tune.fused_fwd_waves;
-    return 2 * c->d.batch <= c->n_simd ? 4 : 1;
+    const int f = c->tune.fused_fwd_waves;
+    return (f == 1 || f == 3 || f == 4) ? f : (2 * c->d.batch <= c->n_simd ? 4 : 1);
 }
 
 // raw: difference the key-point ordered payload inside the sweep (one-wave form only; the caller checks backward_fused_form)
@@ -2415,15 +2297,14 @@ hipError_t launch_backward_fused(Ctx *c, int pd_stride, bool raw)
     const FusedArgs F = fused_args(c);
     // Wave organisation of the backward sweep (backward_fused_form above).  While every wave of the consumer / helper pair can have
     // a SIMD to itself (2 x batch <= #SIMDs) the pair is the fastest form; beyond that two waves take turns on a SIMD and one wave
-    // per trajectory wins (DESIGN.md sections 4.0, 4.4).  KPILQR_FUSED_WAVES forces a form: 1 = one wave, 2 = control/state split,
-    // 3 = producer/consumer pair, 4 = the consumer / side / producer triple, 5 = the consumer / helper pair.
+    // per trajectory wins (DESIGN.md sections 4.0, 4.4).  KPILQR_FUSED_WAVES forces a form: 1 = one wave, 5 = the consumer / helper pair.
     const int form = backward_fused_form(c);
     if (raw && form != 1 && form != 5) return hipErrorInvalidValue;
     c->last_bwd_form = form; c->last_bwd_raw = raw; c->last_bwd_ru0 = form == 1 && c->ru_zero;       // kpilqr_last_launch
     const bool rxc = form == 1 && c->ru_zero && c->rx_const_on;     // (the caller has materialised r_x for every other form)
     c->last_bwd_rxc = rxc;
     c->last_bwd_slopes = form == 1 && c->kps != nullptr && !(raw && c->tune.fused_uni == 0);      // (what the general form walks, if it runs)
-    if (form != 1) return launch_backward_fused_waves(c, pd_stride, raw, form);
+    if (form != 1) return launch_backward_fused_waves(c, pd_stride, raw);
 #define LAUNCH5(NN, MM, RU, RW, UN, RX)                                                                       \
     do {                                                                                                     \
         if (excl)                                                                                            \
@@ -2465,41 +2346,38 @@ hipError_t launch_backward_fused(Ctx *c, int pd_stride, bool raw)
 #endif
 
 #if KP_PART(2)
-// form 5 of the backward sweep, the consumer / helper pair; launch_backward_fused has filled in kpilqr_last_launch's fields
-hipError_t launch_backward_fused_waves(Ctx *c, int pd_stride, bool raw, int form)
+// form 5 of the backward sweep, the consumer / helper pair; launch_backward_fused has filled in kpilqr_last_launch's fields.
+// raw: the raw launch sequence of the pair (the helper differences the payload of uniform sets)
+hipError_t launch_backward_fused_waves(Ctx *c, int pd_stride, bool raw)
 {
     const int n = c->n, m = c->d.m;
     dim3 grid(c->d.batch);
     const FusedArgs F = fused_args(c);
     const int role_shift = c->tune.role_shift;
     dim3 block2(128);
-    // form 5, consumer / helper pair: the raw launch sequence of the pair (the helper differences the payload of uniform sets)
-    if (form == 5) {
-        const bool hru0 = c->ru_zero, hrxc = c->ru_zero && c->rx_const_on;
-        c->last_bwd_ru0 = hru0; c->last_bwd_rxc = hrxc;
-        // per-DoF lists: the helper walks the slope store (made by k_fd_kp_difference / k_kp_slopes for such sets only), uniform
-        // sets the column store with its dividing tracker: two launches, the device flag decides
-        const bool hslp = c->kps != nullptr;
-        c->last_bwd_slopes = hslp;
+    const bool hru0 = c->ru_zero, hrxc = c->ru_zero && c->rx_const_on;
+    c->last_bwd_ru0 = hru0; c->last_bwd_rxc = hrxc;
+    // per-DoF lists: the helper walks the slope store (made by k_fd_kp_difference / k_kp_slopes for such sets only), uniform
+    // sets the column store with its dividing tracker: two launches, the device flag decides
+    const bool hslp = c->kps != nullptr;
+    c->last_bwd_slopes = hslp;
 #define LAUNCHPH2(NN, MM, RW, RU, RX, SL, GUARD) hipLaunchKernelGGL((k_backward_fusedph<NN, MM, RW, RU, RX, SL>), grid, block2, 0, c->stream, c->L, F, c->d.T, role_shift, c->lambda, pd_stride, c->K, c->k, c->delta_J, c->status, c->kp_uniform, GUARD)
 #define LAUNCHPH(NN, MM, RW, SL, GUARD) do { if (hrxc) LAUNCHPH2(NN, MM, RW, true, true, SL, GUARD); else if (hru0) LAUNCHPH2(NN, MM, RW, true, false, SL, GUARD); else LAUNCHPH2(NN, MM, RW, false, false, SL, GUARD); } while (0)
 #define KP_X(NN, MM)                                                                                   \
-        if (n == NN && m == MM) {                                                                      \
-            if (raw) {                                                                                 \
-                LAUNCHPH(NN, MM, true, false, 1);                                                      \
-                hipError_t e_ = launch_fd_kp_difference(c, true);                                      \
-                if (e_ != hipSuccess) return e_;                                                       \
-                if (hslp) LAUNCHPH(NN, MM, false, true, 0); else LAUNCHPH(NN, MM, false, false, 0);    \
-            } else if (hslp) { LAUNCHPH(NN, MM, false, false, 1); LAUNCHPH(NN, MM, false, true, 0); }  \
-            else LAUNCHPH(NN, MM, false, false, -1);                                                   \
-            return hipGetLastError();                                                                  \
-        }
-        KP_T1_SHAPES(KP_X)
+    if (n == NN && m == MM) {                                                                          \
+        if (raw) {                                                                                     \
+            LAUNCHPH(NN, MM, true, false, 1);                                                          \
+            hipError_t e_ = launch_fd_kp_difference(c, true);                                          \
+            if (e_ != hipSuccess) return e_;                                                           \
+            if (hslp) LAUNCHPH(NN, MM, false, true, 0); else LAUNCHPH(NN, MM, false, false, 0);        \
+        } else if (hslp) { LAUNCHPH(NN, MM, false, false, 1); LAUNCHPH(NN, MM, false, true, 0); }      \
+        else LAUNCHPH(NN, MM, false, false, -1);                                                       \
+        return hipGetLastError();                                                                      \
+    }
+    KP_T1_SHAPES(KP_X)
 #undef KP_X
 #undef LAUNCHPH
 #undef LAUNCHPH2
-        return hipErrorInvalidValue;
-    }
     return hipErrorInvalidValue;
 }
 #endif
@@ -2527,7 +2405,7 @@ hipError_t launch_forward_fused(Ctx *c, double *U_alpha_dev)
     // While a trajectory can have three SIMDs of a CU (4 x batch <= #SIMDs) the state / cost / staging triple runs it: 1.58 ms per
     // sweep at B = 1, 1.74 ... 1.76 at B = 128 ... 256 (four tile sets per wave, a time loop without conditions) against 1.80 for
     // one wave per trajectory with its tile requests four steps ahead, which takes over beyond.
-    // KPILQR_FUSED_FWD_WAVES = 1 | 2 | 3 forces a form.
+    // KPILQR_FUSED_FWD_WAVES = 1 | 3 | 4 forces a form.
     int form = forward_fused_form(c);
     const bool src_ru0 = c->ru_zero, src_rxc = c->ru_zero && c->rx_const_on;      // the cost wave of the state / cost groups
     const int ncz = (n + 2 + 3) / 4, ncu = (m + 3) / 4;       // tile chunks of [dx; alpha; 1] and of the controls
@@ -2535,8 +2413,8 @@ hipError_t launch_forward_fused(Ctx *c, double *U_alpha_dev)
     c->last_fwd_form_ragged = 0;
     if (form == 4) {
         dim3 block2(128);
-        // per-DoF lists: the triple, or (KPILQR_FWD_RAGGED_PAIR=1) the state / cost+staging pair, or one wave per trajectory
-        const int behind = 4 * c->d.batch <= c->n_simd ? 3 : c->tune.fwd_ragged_pair ? 2 : 1;
+        // per-DoF lists: the triple, or one wave per trajectory
+        const int behind = 4 * c->d.batch <= c->n_simd ? 3 : 1;
 #define LAUNCHSCU(NCZ, NCU)                                                                                             \
         if (ncz == NCZ && ncu == NCU) {                                                                                 \
             if (src_rxc) hipLaunchKernelGGL((k_forward_fused_scu<NCZ, NCU, true, true>), grid, block2, 0, c->stream, c->L, F, c->d.T, c->d.n_alpha, \
@@ -2551,13 +2429,13 @@ hipError_t launch_forward_fused(Ctx *c, double *U_alpha_dev)
         hipError_t e_ = hipGetLastError();
         if (e_ != hipSuccess) return e_;
         c->last_fwd_form = 3;                                 // kpilqr_last_launch: "pair" on a uniform set ...
-        c->last_fwd_form_ragged = behind == 3 ? 4 : behind == 2 ? 3 : 1;        // ... the triple / pair / w1 otherwise
+        c->last_fwd_form_ragged = behind == 3 ? 4 : 1;        // ... the triple / w1 otherwise
         c->last_fwd_ru0 = c->ru_zero; c->last_fwd_rxc = src_rxc;
         c->last_fwd_slopes = behind == 1 && c->kps != nullptr;
         if (c->kp_known_uniform) return hipSuccess;           // (the host placed the lists and saw them equal: nothing else can run)
         form = behind; only_ragged = 1;
     } else {
-        c->last_fwd_form = form == 3 ? 4 : form == 2 ? 3 : 1;      // kpilqr_last_launch: triple / pair / w1
+        c->last_fwd_form = form == 3 ? 4 : 1;      // kpilqr_last_launch: triple / w1
         c->last_fwd_ru0 = c->ru_zero; c->last_fwd_rxc = src_rxc;
         c->last_fwd_slopes = form == 1 && c->kps != nullptr;
     }
@@ -2576,22 +2454,6 @@ hipError_t launch_forward_fused(Ctx *c, double *U_alpha_dev)
         }
         LAUNCHSC3(4, 2) LAUNCHSC3(2, 1) LAUNCHSC3(4, 1) LAUNCHSC3(3, 1)
 #undef LAUNCHSC3
-        return hipErrorInvalidValue;
-    }
-    if (form == 2) {
-        dim3 block2(128);
-#define LAUNCHSC(NCZ, NCU)                                                                                              \
-        if (ncz == NCZ && ncu == NCU) {                                                                                 \
-            if (src_rxc) hipLaunchKernelGGL((k_forward_fused_sc<NCZ, NCU, true, true>), grid, block2, 0, c->stream, c->L, F, c->d.T, c->d.n_alpha, \
-                               c->K, c->k, c->u_nom, c->ctrl_lim, c->alphas, c->cost_pred, U_alpha_dev, c->kp_uniform, only_ragged); \
-            else if (src_ru0) hipLaunchKernelGGL((k_forward_fused_sc<NCZ, NCU, true, false>), grid, block2, 0, c->stream, c->L, F, c->d.T, c->d.n_alpha, \
-                               c->K, c->k, c->u_nom, c->ctrl_lim, c->alphas, c->cost_pred, U_alpha_dev, c->kp_uniform, only_ragged); \
-            else hipLaunchKernelGGL((k_forward_fused_sc<NCZ, NCU>), grid, block2, 0, c->stream, c->L, F, c->d.T, c->d.n_alpha, \
-                               c->K, c->k, c->u_nom, c->ctrl_lim, c->alphas, c->cost_pred, U_alpha_dev, c->kp_uniform, only_ragged); \
-            return hipGetLastError();                                                                                   \
-        }
-        LAUNCHSC(4, 2) LAUNCHSC(2, 1) LAUNCHSC(4, 1) LAUNCHSC(3, 1)
-#undef LAUNCHSC
         return hipErrorInvalidValue;
     }
 #define LAUNCH4(NCZ, NCU, RU, UNI, RX)                                                                            \

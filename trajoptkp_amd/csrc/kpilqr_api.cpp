@@ -79,7 +79,6 @@ Ctx::Tuning read_tuning_from_env()
 {
     Ctx::Tuning t;
     t.fused_bwd_waves = env_int("KPILQR_FUSED_WAVES", 0);
-    t.fwd_ragged_pair = env_int("KPILQR_FWD_RAGGED_PAIR", 0);
     t.fused_fwd_waves = env_int("KPILQR_FUSED_FWD_WAVES", 0);
     t.role_shift = env_int("KPILQR_ROLE_SHIFT", 9);
     t.tiled_nt_min = env_int("KPILQR_TILED_NT_MIN", 0);
@@ -805,11 +804,7 @@ int kpilqr_upload_fd_slab(kpilqr_ctx *c, const void *slab, int njobs, int nnom, 
 static void fdkp_layout(int n, int entries, kpilqr_fdkp_layout *L)
 {
     L->entry_stride = (size_t)(6 * n + 2) * 8;
-#if KP_RAW_PAIRS
     L->xplus = 0; L->xminus = 8; L->elem_stride = 16; L->mode = (size_t)6 * n * 8;       // (x+, x-) pairs, element by element
-#else
-    L->xplus = 0; L->xminus = (size_t)3 * n * 8; L->elem_stride = 8; L->mode = (size_t)6 * n * 8;
-#endif
     L->bytes = (size_t)entries * L->entry_stride;
 }
 
@@ -985,13 +980,13 @@ static int run_backward(kpilqr_ctx *c, int pd_stride)
         if (rc) return rc;
         rc = ensure_kps(c);
         if (rc) return rc;
-        // Key-point ordered payload, one wave per trajectory or the producer / consumer pair: the sweep (its producer wave)
+        // Key-point ordered payload, one wave per trajectory or the consumer / helper pair: the sweep (its helper wave)
         // differences the payload itself and leaves kpc
         // behind for the forward sweep -- no differencing kernel.  (It may stop at a failed PD check, so it never marks
         // kpc valid: another backward pass on the same payload differences again.)  Otherwise the payload is differenced
         // into kpc first, once, and the sweeps read kpc.
         const int bform = backward_fused_form(c);
-        if (!c->kpc_valid && c->fd_kind == 2 && (bform == 1 || bform == 3 || bform == 5) && c->tune.fused_raw != 0) {
+        if (!c->kpc_valid && c->fd_kind == 2 && (bform == 1 || bform == 5) && c->tune.fused_raw != 0) {
             KP_HIP(c, launch_backward_fused(c, pd_stride, true));
             c->kpc_touched = true;
             // (KPILQR_FUSED_UNI=0, diagnostic: the GENERAL raw sweep has differenced every set inside the sweep -- dividing at its
@@ -1507,7 +1502,7 @@ const char *kpilqr_forward_variant(kpilqr_ctx *c) { return c ? c->fwd_variant : 
 
 // What the last backward (which = 0) / forward (which = 1) launch of this context WAS: "<variant>" for the materialising
 // families; for the fused sweeps "<variant>:<waves>:<columns>:<lists>[:ru0][:rxc][:slopes]" with
-//   waves    w1 one wavefront per trajectory | w2 control / state split | pair | triple
+//   waves    w1 one wavefront per trajectory | pair | triple | pairh
 //   columns  raw: the backward sweep differenced the key-point ordered payload itself | kpc: read from the column store
 //   lists    uni: every DoF of a trajectory has the same key-point list (the straight-line crossing forms ran) | ragged
 // The `lists` token is decided on the device (the host never needs it otherwise): this call reads the flag back, i.e. it
@@ -1528,7 +1523,7 @@ const char *kpilqr_last_launch(kpilqr_ctx *c, int which)
     if (hipSetDevice(c->d.device) != hipSuccess || (c->pipe_dirty && join_pipeline(c) != KPILQR_OK) ||
         hipMemcpyAsync(&uni, c->kp_uniform, sizeof(int), hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
         hipStreamSynchronize(c->stream) != hipSuccess) { out += ":?"; return out.c_str(); }
-    static const char *const wname[6] = {"", "w1", "w2", "pair", "triple", "pairh"};
+    static const char *const wname[6] = {"", "w1", "", "pair", "triple", "pairh"};      // by form number (2 is not used)
     const int ran = (which == 1 && !uni && c->last_fwd_form_ragged) ? c->last_fwd_form_ragged : form;
     out += ":"; out += wname[ran < 6 ? ran : 0];
     // (the raw launch sequence differences inside the sweep for uniform sets only: per-DoF lists take k_fd_kp_difference and

@@ -15,21 +15,6 @@
 #include <cstdlib>
 #include <type_traits>
 #include "mfma_common.h"
-#ifndef KP_COL_STAGE_D
-#define KP_COL_STAGE_D 1            // 0: the column kernel stages Fz, Fu at the top of the step: A/B builds
-#endif
-#ifndef KP_SC_SPREAD
-#define KP_SC_SPREAD 1              // 0: the state / cost forward sweep's requests as blocks behind the products: A/B builds
-#endif
-#ifndef KP_UW_SPREAD
-#define KP_UW_SPREAD 1              // 0: the u-wave kernel's requests as blocks behind the products: A/B builds
-#endif
-#ifndef KP_FT_SPREAD
-#define KP_FT_SPREAD 1              // 0: the one-group forward sweeps' requests as blocks behind the products (three / four tiles, every a6-inside form): A/B builds
-#endif
-#ifndef KP_COL_SPREAD
-#define KP_COL_SPREAD 1             // 0: the column kernel's requests as blocks (top of the step, behind the products): A/B builds
-#endif
 #ifndef KP_NS_HOLD
 #define KP_NS_HOLD 8                // factorised steps behind a Newton-Schulz refresh that gave up before the fast path is tried again
 #endif
@@ -228,9 +213,8 @@ k_backward_tiled_col(RecLayout L, CostSrc CS, int T, const double *__restrict__ 
     // SPREAD: the requests for the next step's tiles go out one by one under the products of phase BC (round 5, late: as blocks of
     // twenty at the top of the step and behind the products they were 1 000 + ~700 exposed cycles of a 21 100-cycle step -- the four
     // waves of a trajectory share one address unit)
-    constexpr bool SPREAD = KP_COL_SPREAD && NCL > 0;
+    constexpr bool SPREAD = NCL > 0;
     static_assert(!SPREAD || NT == 4, "the spread requests deal Fu over the NT row tiles: four registers");
-    constexpr bool STAGE_D = SPREAD && KP_COL_STAGE_D;
     // M = 8 is the catch-all instantiation for any num_ctrl <= 8 (walker 6, hopper / pentabot 3, ...): the m x m system is
     // padded with identity rows to 8 x 8 for the (rare) per-lane LDL' steps; everything else works on tiles anyway.
     constexpr bool PAD = (M == 8);
@@ -396,7 +380,7 @@ k_backward_tiled_col(RecLayout L, CostSrc CS, int T, const double *__restrict__ 
 #else
 #define CYK(i)
 #endif
-    // the step's tiles into LDS.  STAGE_D (with the spread requests): Fz(:,w), Fu(w) of step t-1 are staged in phase D of step t -- bufF
+    // the step's tiles into LDS.  SPREAD: Fz(:,w), Fu(w) of step t-1 are staged in phase D of step t -- bufF
     // and bufFu are free behind the barrier that ends BC, the tiles were requested under BC's first half, and the writes drain
     // under phase D's per-lane factorisation instead of standing (540 cycles) in front of the step's first barrier (drawn residual
     // Jacobians 36.5 -> 35.9 ms on configs[4]; nothing where the refresh applies)
@@ -408,7 +392,7 @@ k_backward_tiled_col(RecLayout L, CostSrc CS, int T, const double *__restrict__ 
         if (w == tn && lane_nn) bufF[(tn * NT + w) * TILE + reg_nn * 64 + lane] = 1.0;
         lds_store(bufFu + w * TILE, lane, pFu);
     };
-    if constexpr (STAGE_D) stage();
+    if constexpr (SPREAD) stage();
     for (int t = T - 1; t >= 0; t--) {
         pd_counter++;
         const bool check_pd = pd_counter >= pd_stride;
@@ -416,7 +400,7 @@ k_backward_tiled_col(RecLayout L, CostSrc CS, int T, const double *__restrict__ 
         __amdgpu_buffer_rsrc_t rn = more ? rsrc_of(t - 1) : __builtin_amdgcn_make_buffer_rsrc((void *)R0, 0, 0, 0x00020000);
         // ---- A: stage Fz(:,w) (+ the homogeneous 1) and Fu(w) ----------------------------------------------
         CYK(10)
-        if constexpr (!STAGE_D) stage();
+        if constexpr (!SPREAD) stage();
         __builtin_amdgcn_sched_barrier(0);
         CYK(9)
         if constexpr (!SPREAD) {
@@ -532,7 +516,7 @@ k_backward_tiled_col(RecLayout L, CostSrc CS, int T, const double *__restrict__ 
         d4 Qp_[NT];
 #pragma unroll
         for (int k = 0; k < NT; k++) Qp_[k] = lds_tile(bufQp + k * TILE, lane);
-        if constexpr (STAGE_D) stage();
+        if constexpr (SPREAD) stage();
 #pragma unroll
         for (int k = 0; k < NT; k++) Quu = Quu + Qp_[k];
         d4 Qr = Quu;
@@ -813,17 +797,12 @@ k_backward_tiled_uw(RecLayout L, int T, const double *__restrict__ rec, const do
 #pragma unroll
                 for (int i = 0; i < NT; i++) {
                     if (r < nck(i)) Qp[i] = MFMA(comp(pFu[i], r), comp(Tu[i], r), Qp[i]);
-                    if constexpr (KP_UW_SPREAD) {   // the next step's Fu, register by register behind its last use (see k_backward_tiled_col)
-                        setc(pFu[i], r, tbld(rn, oFu[i][r]));
-                        if (r < nck(i)) __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                        __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
-                    }
+                    // the next step's Fu, register by register behind its last use (see k_backward_tiled_col)
+                    setc(pFu[i], r, tbld(rn, oFu[i][r]));
+                    if (r < nck(i)) __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+                    __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
                 }
             __builtin_amdgcn_sched_barrier(0);
-            if constexpr (!KP_UW_SPREAD) {
-#pragma unroll
-                for (int k = 0; k < NT; k++) pFu[k] = ld4(rn, oFu[k]);
-            }
             __builtin_amdgcn_sched_barrier(0);
             CYC(7)
             __syncthreads();                                       // (the column waves' Fz, Fu are in LDS: not used here)
@@ -981,42 +960,34 @@ k_backward_tiled_uw(RecLayout L, int T, const double *__restrict__ rec, const do
                     Y[k] = pF[k];
                     if (k == tn && w == tn) Y[k] = Y[k] + nn_one;          // Fz(n,n) = 1
                 }
-                if constexpr (KP_UW_SPREAD) {
-                    // VtY with the next step's requests one by one under the products (see k_backward_tiled_col): Fz(k,w) register r
-                    // behind the products that read it (from Y, its copy), Fu(w) under the first row tile
-                    const d4 Fuw = pFu;
+                // VtY with the next step's requests one by one under the products (see k_backward_tiled_col): Fz(k,w) register r
+                // behind the products that read it (from Y, its copy), Fu(w) under the first row tile
+                const d4 Fuw = pFu;
 #pragma unroll
-                    for (int i = 0; i < NT; i++) Tz[i] = zero;
+                for (int i = 0; i < NT; i++) Tz[i] = zero;
 #pragma unroll
-                    for (int k = 0; k < NT; k++) {
-                        d4 Vk[NT];
+                for (int k = 0; k < NT; k++) {
+                    d4 Vk[NT];
 #pragma unroll
-                        for (int i = 0; i < NT; i++) Vk[i] = lds_tile(bufV + (k * NT + i) * TILE, lane);
+                    for (int i = 0; i < NT; i++) Vk[i] = lds_tile(bufV + (k * NT + i) * TILE, lane);
 #pragma unroll
-                        for (int r = 0; r < 4; r++) {
-                            if (r < nck(k)) {
+                    for (int r = 0; r < 4; r++) {
+                        if (r < nck(k)) {
 #pragma unroll
-                                for (int i = 0; i < NT; i++) Tz[i] = MFMA(comp(Vk[i], r), comp(Y[k], r), Tz[i]);
-                                __builtin_amdgcn_sched_group_barrier(0x008, NT, 0);
-                            }
-                            setc(pF[k], r, tbld(rn, oF[k][r]));
-                            if (k == 0) setc(pFu, r, tbld(rn, oFu[r]));
-                            if (k == 0) __builtin_amdgcn_sched_group_barrier(0x020, 2, 0);
-                            else __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
+                            for (int i = 0; i < NT; i++) Tz[i] = MFMA(comp(Vk[i], r), comp(Y[k], r), Tz[i]);
+                            __builtin_amdgcn_sched_group_barrier(0x008, NT, 0);
                         }
+                        setc(pF[k], r, tbld(rn, oF[k][r]));
+                        if (k == 0) setc(pFu, r, tbld(rn, oFu[r]));
+                        if (k == 0) __builtin_amdgcn_sched_group_barrier(0x020, 2, 0);
+                        else __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
                     }
-#pragma unroll
-                    for (int k = 0; k < NT; k++) lds_store(bufF + (k * NT + w) * TILE, lane, Y[k]);
-                    lds_store(bufFu + w * TILE, lane, Fuw);
-                } else {
-                VtY(Y, Tz);
+                }
 #pragma unroll
                 for (int k = 0; k < NT; k++) lds_store(bufF + (k * NT + w) * TILE, lane, Y[k]);
-                lds_store(bufFu + w * TILE, lane, pFu);
-                }
+                lds_store(bufFu + w * TILE, lane, Fuw);
             }
             __builtin_amdgcn_sched_barrier(0);
-            if constexpr (!KP_UW_SPREAD) request(rn);
             __builtin_amdgcn_sched_barrier(0);
             CYC(7)
             __syncthreads();                                       // every wave's Fz, Fu are in LDS
@@ -1025,11 +996,10 @@ k_backward_tiled_uw(RecLayout L, int T, const double *__restrict__ rec, const do
             d4 Quzw = zero, Qzz[ND];
 #pragma unroll
             for (int d = 0; d < ND; d++) Qzz[d] = zero;
-            if constexpr (KP_UW_SPREAD) {       // the cost tiles start the chains (requested a step ago), their registers are free for the next step's
-                Quzw = pLuz;
+            // the cost tiles start the chains (requested a step ago), their registers are free for the next step's
+            Quzw = pLuz;
 #pragma unroll
-                for (int d = 0; d < ND; d++) Qzz[d] = pL[d];
-            }
+            for (int d = 0; d < ND; d++) Qzz[d] = pL[d];
 #pragma unroll
             for (int k = 0; k < NT; k++) {
                 d4 Fk[ND];
@@ -1042,24 +1012,17 @@ k_backward_tiled_uw(RecLayout L, int T, const double *__restrict__ rec, const do
                         Quzw = MFMA(comp(Fuk, r), comp(Tz[k], r), Quzw);
 #pragma unroll
                         for (int d = 0; d < ND; d++) Qzz[d] = MFMA(comp(Fk[d], r), comp(Tz[k], r), Qzz[d]);
-                        if constexpr (KP_UW_SPREAD) __builtin_amdgcn_sched_group_barrier(0x008, ND + 1, 0);
+                        __builtin_amdgcn_sched_group_barrier(0x008, ND + 1, 0);
                     }
-                    if constexpr (KP_UW_SPREAD) {               // request (k, r): register r of pL[k] (k < ND) and, at k = NT-1, of pLuz
-                        if (k < ND) setc(pL[k], r, tbld(rn, oL[k][r]));
-                        if (k == NT - 1) setc(pLuz, r, tbld(rn, oLuz[r]));
-                        if (k < ND && k == NT - 1) __builtin_amdgcn_sched_group_barrier(0x020, 2, 0);
-                        else if (k < ND || k == NT - 1) __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
-                    }
+                    // request (k, r): register r of pL[k] (k < ND) and, at k = NT-1, of pLuz
+                    if (k < ND) setc(pL[k], r, tbld(rn, oL[k][r]));
+                    if (k == NT - 1) setc(pLuz, r, tbld(rn, oLuz[r]));
+                    if (k < ND && k == NT - 1) __builtin_amdgcn_sched_group_barrier(0x020, 2, 0);
+                    else if (k < ND || k == NT - 1) __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
                 }
-            }
-            if constexpr (!KP_UW_SPREAD) {
-            Quzw = Quzw + pLuz;
-#pragma unroll
-            for (int d = 0; d < ND; d++) Qzz[d] = Qzz[d] + pL[d];
             }
             CYC(8)
             __builtin_amdgcn_sched_barrier(0);
-            if constexpr (!KP_UW_SPREAD) request_cost(rn);         // (issued while the u-wave still refreshes the inverse)
             __builtin_amdgcn_sched_barrier(0);
             CYC(2)
             __syncthreads();                                       // the inverse and the verdict are out
@@ -1294,7 +1257,7 @@ k_forward_tiled(RecLayout L, CostSrc CS, int T, int n_alpha, const double *__res
     // the products instead of in blocks behind them (the four waves of a trajectory share one address unit: a block of twenty
     // requests per wave stood ~1 600 cycles in front of it), registers that hold structural zeros only are not requested, k rides in
     // ONE request (the lanes of row n) and joins the gain operand at its use instead of behind the request
-    constexpr bool FSPREAD = KP_FT_SPREAD && NCL > 0 && (A6 || NT > 2);       // (two tiles, materialised: 3.54 against 3.37 ms on pushing -- stays with the blocks)
+    constexpr bool FSPREAD = NCL > 0 && (A6 || NT > 2);       // (two tiles, materialised: 3.54 against 3.37 ms on pushing -- stays with the blocks)
     const bool k_here = tnz == wi;
     const int okn = (k_here && q == (n & 3) && c < m) ? 8 * c : OOBT;
     double kmask[4];
@@ -1529,7 +1492,7 @@ k_forward_tiled(RecLayout L, CostSrc CS, int T, int n_alpha, const double *__res
 // ---------------------------------------------------------------------------------------------------------------
 // Forward pass, STATE / COST wave groups (round 4; materialised tiles, two row tiles; while the 2 NT waves of a trajectory each
 // find a SIMD: 2 NT x batch <= #SIMDs -- configs[2]: Panda pushing, 64 trajectories, 4 of a CU's SIMDs instead of 2).  Only the
-// state recursion is serial in time (as in fused_mfma.hip's k_forward_fused_sc): state wave i keeps row tile i of Z and runs
+// state recursion is serial in time (as in fused_mfma.hip's k_forward_fused_scu): state wave i keeps row tile i of Z and runs
 //     slice of K dx + alpha k | barrier | sum of the slices, clamp | Z' = A dx + B du | barrier          (4 + 4 NT + 2 MFMAs)
 // and publishes Z_t (a three-slot LDS ring) and dU_t; cost wave i, ONE STEP BEHIND, scores the candidates' row tile i --
 // Wz = Lc Z (4 NT MFMAs), 0.5 Z'Wz, and on the last cost wave the control cost dU'(0.5 l_uu dU + l_u) -- from the published
@@ -1701,45 +1664,31 @@ __device__ __forceinline__ void ft_state_role(double *zring, double *upart, doub
         for (int k = 0; k < NT - 1; k++) Zk[k] = lds_tile(zc + k * TILE, lane);
         Zk[NT - 1] = lds_tile_n<NCL>(zc + (NT - 1) * TILE, lane);
         d4 Zn = zero;
-        if constexpr (KP_SC_SPREAD) {
-            // the next step's gain rows and A tiles, register by register behind the product that read the register (round 5, late:
-            // the waves of a trajectory share one address unit, and a block of thirteen requests stood in front of the barrier)
-            auto comp = [](const d4 &v, int r) { return r == 0 ? v.x : r == 1 ? v.y : r == 2 ? v.z : v.w; };
-            const int soA = tn1 * recB;
-            d4 Us = zero;
+        // the next step's gain rows and A tiles, register by register behind the product that read the register (round 5, late:
+        // the waves of a trajectory share one address unit, and a block of thirteen requests stood in front of the barrier)
+        auto comp = [](const d4 &v, int r) { return r == 0 ? v.x : r == 1 ? v.y : r == 2 ? v.z : v.w; };
+        const int soA = tn1 * recB;
+        d4 Us = zero;
 #pragma unroll
-            for (int r = 0; r < NCW; r++) {
-                Us = MFMA(comp(Yk, r), comp(Zi, r), Us);
-                setc(cur.Ykw, r, tblds(rKt, oKw[r], sK));
-                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
-            }
-            cur.kk = tblds(rkt, okn, sk);
-            lds_store_n<NCU>(upart + wi * TILE, lane, Us);
-#pragma unroll
-            for (int k = 0; k < NT; k++) {
-                d4 Ya = cur.Ya[k];
-                if (k == tnz) { Ya.x += oneT[0]; Ya.y += oneT[1]; Ya.z += oneT[2]; Ya.w += oneT[3]; }
-#pragma unroll
-                for (int r = 0; r < (k < NT - 1 ? 4 : NCL); r++) {
-                    Zn = MFMA(comp(Ya, r), comp(Zk[k], r), Zn);
-                    setc(cur.Ya[k], r, tblds(rRec, oA[k][r], soA));
-                    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                    __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
-                }
-            }
-        } else {
-        lds_store_n<NCU>(upart + wi * TILE, lane, Pc<NCW>(Yk, Zi, zero));      // this wave's slice of K dx + alpha k (rows < num_ctrl)
+        for (int r = 0; r < NCW; r++) {
+            Us = MFMA(comp(Yk, r), comp(Zi, r), Us);
+            setc(cur.Ykw, r, tblds(rKt, oKw[r], sK));
+            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+            __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
+        }
+        cur.kk = tblds(rkt, okn, sk);
+        lds_store_n<NCU>(upart + wi * TILE, lane, Us);
 #pragma unroll
         for (int k = 0; k < NT; k++) {
             d4 Ya = cur.Ya[k];
             if (k == tnz) { Ya.x += oneT[0]; Ya.y += oneT[1]; Ya.z += oneT[2]; Ya.w += oneT[3]; }
-            if (k < NT - 1) Zn = Pc<4>(Ya, Zk[k], Zn); else Zn = Pc<NCL>(Ya, Zk[k], Zn);
-        }
-        __builtin_amdgcn_sched_barrier(0);
-        cur.Ykw = ld4ns<NCW>(rKt, oKw, sK); cur.kk = tblds(rkt, okn, sk);
-        request_A(t + 1);
-        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int r = 0; r < (k < NT - 1 ? 4 : NCL); r++) {
+                Zn = MFMA(comp(Ya, r), comp(Zk[k], r), Zn);
+                setc(cur.Ya[k], r, tblds(rRec, oA[k][r], soA));
+                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+                __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
+            }
         }
         __syncthreads();
         // ---- control law + clamp (every state wave; :876-890) ----------------------------------------------------------
@@ -1860,36 +1809,23 @@ k_forward_tiled_sc(RecLayout L, int T, int n_alpha, const double *__restrict__ r
             d4 Wz = zero;
             d4 Wu = zero;
             const d4 lu = cur.lu;
-            if constexpr (KP_SC_SPREAD) {
-                auto comp = [](const d4 &v, int r) { return r == 0 ? v.x : r == 1 ? v.y : r == 2 ? v.z : v.w; };
+            auto comp = [](const d4 &v, int r) { return r == 0 ? v.x : r == 1 ? v.y : r == 2 ? v.z : v.w; };
 #pragma unroll
-                for (int k = 0; k < NT; k++)
+            for (int k = 0; k < NT; k++)
 #pragma unroll
-                    for (int r = 0; r < (k < NT - 1 ? 4 : NCL); r++) {
-                        Wz = MFMA(comp(cur.Lc[k], r), comp(Zk[k], r), Wz);
-                        setc(cur.Lc[k], r, tblds(rRec, oLc[k][r], so));
-                        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                        __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
-                    }
-#pragma unroll
-                for (int r = 0; r < NCU; r++) {
-                    Wu = MFMA(comp(cur.Luu, r), comp(dU, r), Wu);
-                    setc(cur.Luu, r, tblds(rRec, oLuu[r], so));
-                    setc(cur.lu, r, tblds(rRec, olu[r], so));
+                for (int r = 0; r < (k < NT - 1 ? 4 : NCL); r++) {
+                    Wz = MFMA(comp(cur.Lc[k], r), comp(Zk[k], r), Wz);
+                    setc(cur.Lc[k], r, tblds(rRec, oLc[k][r], so));
                     __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                    __builtin_amdgcn_sched_group_barrier(0x020, 2, 0);
+                    __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
                 }
-            } else {
 #pragma unroll
-            for (int k = 0; k < NT - 1; k++) Wz = Pc<4>(cur.Lc[k], Zk[k], Wz);
-            Wz = Pc<NCL>(cur.Lc[NT - 1], Zk[NT - 1], Wz);
-            Wu = Pc<NCU>(cur.Luu, dU, zero);                                 // (l_uu, l_u: the last cost wave's; zeros elsewhere)
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int k = 0; k < NT - 1; k++) cur.Lc[k] = ld4ns<4>(rRec, oLc[k], so);
-            cur.Lc[NT - 1] = ld4ns<NCL>(rRec, oLc[NT - 1], so);
-            cur.Luu = ld4ns<NCU>(rRec, oLuu, so); cur.lu = ld4ns<NCU>(rRec, olu, so);
-            __builtin_amdgcn_sched_barrier(0);
+            for (int r = 0; r < NCU; r++) {
+                Wu = MFMA(comp(cur.Luu, r), comp(dU, r), Wu);
+                setc(cur.Luu, r, tblds(rRec, oLuu[r], so));
+                setc(cur.lu, r, tblds(rRec, olu[r], so));
+                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+                __builtin_amdgcn_sched_group_barrier(0x020, 2, 0);
             }
             d4 Zi = Zk[0];                                                   // this wave's own row tile (wi is wave-uniform)
 #pragma unroll
@@ -1937,14 +1873,12 @@ static hipError_t launch_ft2(Ctx *c, double *U_alpha_dev)
     // compile-time chunk count of the last row tile: two row tiles materialised -- the interleaved chains with two register sets (pushing
     // 3.52 -> 3.41 ms, walker 3.40 -> 3.19; with three tiles that code was SLOWER, 4.98 -> 5.56 ms on light clutter n=38); everything
     // else -- the requests one by one under the products (round 5: light clutter 5.04 -> 4.61, configs[4] 12.5 -> 9.15 ms)
-    if constexpr (KP_FT_SPREAD || (!A6 && NT == 2)) {
-        const int rows = c->n + 2 - 16 * (NT - 1), ncl = rows >= 16 ? 4 : (rows + 3) / 4;
-        if (c->tune.tiled_uw != 0) switch (ncl > 1 ? ncl : 1) {
-        case 1: return launch_ft3<NT, A6, 1>(c, U_alpha_dev);
-        case 2: return launch_ft3<NT, A6, 2>(c, U_alpha_dev);
-        case 3: return launch_ft3<NT, A6, 3>(c, U_alpha_dev);
-        case 4: return launch_ft3<NT, A6, 4>(c, U_alpha_dev);
-        }
+    const int rows = c->n + 2 - 16 * (NT - 1), ncl = rows >= 16 ? 4 : (rows + 3) / 4;
+    if (c->tune.tiled_uw != 0) switch (ncl > 1 ? ncl : 1) {
+    case 1: return launch_ft3<NT, A6, 1>(c, U_alpha_dev);
+    case 2: return launch_ft3<NT, A6, 2>(c, U_alpha_dev);
+    case 3: return launch_ft3<NT, A6, 3>(c, U_alpha_dev);
+    case 4: return launch_ft3<NT, A6, 4>(c, U_alpha_dev);
     }
     return launch_ft3<NT, A6, 0>(c, U_alpha_dev);
 }

@@ -22,10 +22,6 @@
 #include <cstdlib>
 #include "mfma_common.h"
 
-#ifndef KP_WIDE_SPREAD
-#define KP_WIDE_SPREAD 1            // 0: the wide-control sweeps' requests as one block per step: A/B builds
-#endif
-
 namespace kpilqr {
 
 typedef unsigned int u32x2w __attribute__((ext_vector_type(2)));
@@ -288,7 +284,6 @@ k_backward_tiled_wide(RecLayout L, int T, const double *__restrict__ rec, const 
         // (round 5, late: the ~50 requests of a step go out in groups behind the product groups of phase BC instead of as one block
         // in front of this barrier -- the waves of a trajectory share one address unit)
         const __amdgpu_buffer_rsrc_t rn = more ? rsrc_of(t - 1) : rnone;
-        if constexpr (!KP_WIDE_SPREAD) load_src(rn);                   // single-buffered: requested right behind their last use
         __builtin_amdgcn_sched_barrier(0);
         __syncthreads();
         // ---- BC: Tz(:,w), Tu(w,:), Quz(:,w), Qzz(:,w) ---------------------------------------------------------------------
@@ -301,7 +296,7 @@ k_backward_tiled_wide(RecLayout L, int T, const double *__restrict__ rec, const 
 #pragma unroll
             for (int k = 0; k < NT; k++) acc = WPn(wlds(bufV + (k * NT + i) * WTILE, lane), Fc[k], acc, k < NT - 1 ? 4 : ncl);
             Tz[i] = acc;
-            if constexpr (KP_WIDE_SPREAD) { pF[i] = wld_Fz(rn, S, i, w, q, c); pL[i] = wld_Lzz(rn, S, i, w, q, c); }
+            pF[i] = wld_Fz(rn, S, i, w, q, c); pL[i] = wld_Lzz(rn, S, i, w, q, c);
         }
 #pragma unroll
         for (int j = 0; j < MT; j++) {
@@ -309,7 +304,7 @@ k_backward_tiled_wide(RecLayout L, int T, const double *__restrict__ rec, const 
 #pragma unroll
             for (int k = 0; k < NT; k++) Tu = WPn(wlds(bufV + (k * NT + w) * WTILE, lane), wlds(bufFu + (k * MT + j) * WTILE, lane), Tu, k < NT - 1 ? 4 : ncl);
             wsts(bufTu + (w * MT + j) * WTILE, lane, Tu);
-            if constexpr (KP_WIDE_SPREAD) { pFu[j] = wld_Fu(rn, S, w, j, q, c); pLuz[j] = wld_Luz(rn, S, j, w, q, c); }
+            pFu[j] = wld_Fu(rn, S, w, j, q, c); pLuz[j] = wld_Luz(rn, S, j, w, q, c);
         }
         d4 Quzw[MT];
 #pragma unroll
@@ -319,12 +314,10 @@ k_backward_tiled_wide(RecLayout L, int T, const double *__restrict__ rec, const 
             for (int k = 0; k < NT; k++) acc = WPn(wlds(bufFu + (k * MT + j) * WTILE, lane), Tz[k], acc, k < NT - 1 ? 4 : ncl);
             Quzw[j] = acc;
         }
-        if constexpr (KP_WIDE_SPREAD) {
 #pragma unroll
-            for (int s_ = 0; s_ < (MT * MT + NT - 1) / NT; s_++) {
-                const int tq = w + s_ * NT;
-                pLuu[s_] = (tq < MT * MT) ? wld_Luu(rn, S, tq / MT, tq % MT, q, c) : zero;
-            }
+        for (int s_ = 0; s_ < (MT * MT + NT - 1) / NT; s_++) {
+            const int tq = w + s_ * NT;
+            pLuu[s_] = (tq < MT * MT) ? wld_Luu(rn, S, tq / MT, tq % MT, q, c) : zero;
         }
         d4 Qzz[NT];
 #pragma unroll
@@ -547,7 +540,7 @@ k_forward_tiled_wide(RecLayout L, int T, int n_alpha, const double *__restrict__
     const int ncw = nchunk(wi);
     auto mch = [&](int j) { const int rows = m - 16 * j; return rows >= 16 ? 4 : rows <= 0 ? 0 : (rows + 3) / 4; };
 
-    int oKw[MT][4], okw[MT][4], oA[NT][4], oLc[NT][4], oB[MT][4], oLuu[MT][MT][4], olu[MT][4], oub[MT][4];
+    int oKw[MT][4], oA[NT][4], oLc[NT][4], oB[MT][4], oLuu[MT][MT][4], olu[MT][4], oub[MT][4];
     double oneT[4], lo[MT][4], hi[MT][4];
     const int tnz = n >> 4;
     const int o = 16 * wi + c;
@@ -571,7 +564,6 @@ k_forward_tiled_wide(RecLayout L, int T, int n_alpha, const double *__restrict__
         for (int j = 0; j < MT; j++) {
             const int cu = 16 * j + c, ru = 16 * j + row;               // control index as a column / as a row
             oKw[j][r] = (pw < n && cu < m) ? 8 * (pw * m + cu) : OOBW;
-            okw[j][r] = (pw == n && cu < m) ? 8 * cu : OOBW;
             oB[j][r] = (ru < m && o < n) ? 8 * L.b(o, ru) : OOBW;
             olu[j][r] = (ru < m) ? 8 * (L.off_lu + ru) : OOBW;
             oub[j][r] = (ru < m) ? 8 * ru : OOBW;
@@ -625,8 +617,7 @@ k_forward_tiled_wide(RecLayout L, int T, int n_alpha, const double *__restrict__
         const __amdgpu_buffer_rsrc_t rk = rs_of(kin, m, t, m * 8), ru = rs_of(u_nom, m, t, m * 8);
 #pragma unroll
         for (int j = 0; j < MT; j++) {
-            if constexpr (KP_WIDE_SPREAD) { cur.Ykw[j] = ld4(rK, oKw[j]); kv[j] = wbld(rk, okn[j]); }
-            else cur.Ykw[j] = ld4(rK, oKw[j]) + ld4(rk, okw[j]);
+            cur.Ykw[j] = ld4(rK, oKw[j]); kv[j] = wbld(rk, okn[j]);
             cur.Yb[j] = ld4(rR, oB[j]); cur.lu[j] = ld4(rR, olu[j]); cur.ub[j] = ld4(ru, oub[j]);
 #pragma unroll
             for (int j2 = 0; j2 < MT; j2++) cur.Luu[j][j2] = ld4(rR, oLuu[j][j2]);
@@ -645,14 +636,11 @@ k_forward_tiled_wide(RecLayout L, int T, int n_alpha, const double *__restrict__
         // ---- this wave's slice of K dx + alpha k, both control tiles ---------------------------------------------------------
 #pragma unroll
         for (int j = 0; j < MT; j++) {
-            if constexpr (KP_WIDE_SPREAD) {
-                d4 Yk = cur.Ykw[j];
-                Yk.x = __builtin_fma(kmask[0], kv[j], Yk.x); Yk.y = __builtin_fma(kmask[1], kv[j], Yk.y);
-                Yk.z = __builtin_fma(kmask[2], kv[j], Yk.z); Yk.w = __builtin_fma(kmask[3], kv[j], Yk.w);
-                wsts(upart + (wi * MT + j) * WTILE, lane, WPn(Yk, Zi, zero, ncw));
-                cur.Ykw[j] = ld4(rKn, oKw[j]); kv[j] = wbld(rkn, okn[j]);
-            } else
-            wsts(upart + (wi * MT + j) * WTILE, lane, WPn(cur.Ykw[j], Zi, zero, ncw));
+            d4 Yk = cur.Ykw[j];
+            Yk.x = __builtin_fma(kmask[0], kv[j], Yk.x); Yk.y = __builtin_fma(kmask[1], kv[j], Yk.y);
+            Yk.z = __builtin_fma(kmask[2], kv[j], Yk.z); Yk.w = __builtin_fma(kmask[3], kv[j], Yk.w);
+            wsts(upart + (wi * MT + j) * WTILE, lane, WPn(Yk, Zi, zero, ncw));
+            cur.Ykw[j] = ld4(rKn, oKw[j]); kv[j] = wbld(rkn, okn[j]);
         }
         __syncthreads();
         // ---- control law + clamp (every wave; :876-890) ----------------------------------------------------------------------
@@ -671,7 +659,7 @@ k_forward_tiled_wide(RecLayout L, int T, int n_alpha, const double *__restrict__
             v = u.z; if (v > hi[j][2]) v = hi[j][2]; if (v < lo[j][2]) v = lo[j][2]; u.z = v;
             v = u.w; if (v > hi[j][3]) v = hi[j][3]; if (v < lo[j][3]) v = lo[j][3]; u.w = v;
             U[j] = u; dU[j] = u - cur.ub[j];
-            if constexpr (KP_WIDE_SPREAD) cur.ub[j] = ld4(run, oub[j]);
+            cur.ub[j] = ld4(run, oub[j]);
         }
         if (wi == NT - 1) {                        // control cost and U_alpha by the LAST wave (its row tile is the shortest)
             if (U_alpha && c < n_alpha) {
@@ -691,13 +679,11 @@ k_forward_tiled_wide(RecLayout L, int T, int n_alpha, const double *__restrict__
                 partial += dU[j].x * (0.5 * Wu.x + cur.lu[j].x) + dU[j].y * (0.5 * Wu.y + cur.lu[j].y)
                          + dU[j].z * (0.5 * Wu.z + cur.lu[j].z) + dU[j].w * (0.5 * Wu.w + cur.lu[j].w);
             }
-            if constexpr (KP_WIDE_SPREAD) {
 #pragma unroll
-                for (int j = 0; j < MT; j++) {
-                    cur.lu[j] = ld4(rRn, olu[j]);
+            for (int j = 0; j < MT; j++) {
+                cur.lu[j] = ld4(rRn, olu[j]);
 #pragma unroll
-                    for (int j2 = 0; j2 < MT; j2++) cur.Luu[j][j2] = ld4(rRn, oLuu[j][j2]);
-                }
+                for (int j2 = 0; j2 < MT; j2++) cur.Luu[j][j2] = ld4(rRn, oLuu[j][j2]);
             }
         }
         // ---- state cost rows of this tile, then the linearised dynamics for this tile ----------------------------------------------
@@ -705,7 +691,7 @@ k_forward_tiled_wide(RecLayout L, int T, int n_alpha, const double *__restrict__
 #pragma unroll
         for (int k = 0; k < NT; k++) {
             Wz = WPn(cur.Lc[k], Zk[k], Wz, k < NT - 1 ? 4 : ncl);
-            if constexpr (KP_WIDE_SPREAD) cur.Lc[k] = ld4(rRn, oLc[k]);
+            cur.Lc[k] = ld4(rRn, oLc[k]);
         }
         partial += 0.5 * (Zi.x * Wz.x + Zi.y * Wz.y + Zi.z * Wz.z + Zi.w * Wz.w);
 #pragma unroll
@@ -713,17 +699,12 @@ k_forward_tiled_wide(RecLayout L, int T, int n_alpha, const double *__restrict__
             d4 Ya = cur.Ya[k];
             if (k == tnz) { Ya.x += oneT[0]; Ya.y += oneT[1]; Ya.z += oneT[2]; Ya.w += oneT[3]; }
             Zn = WPn(Ya, Zk[k], Zn, k < NT - 1 ? 4 : ncl);
-            if constexpr (KP_WIDE_SPREAD) cur.Ya[k] = ld4(rRn, oA[k]);
+            cur.Ya[k] = ld4(rRn, oA[k]);
         }
 #pragma unroll
         for (int j = 0; j < MT; j++) {
             Zn = WPn(cur.Yb[j], dU[j], Zn, mch(j));
-            if constexpr (KP_WIDE_SPREAD) cur.Yb[j] = ld4(rRn, oB[j]);
-        }
-        if constexpr (!KP_WIDE_SPREAD) {
-        __builtin_amdgcn_sched_barrier(0);
-        load_all(t + 1);                           // single-buffered: everything of step t has been consumed
-        __builtin_amdgcn_sched_barrier(0);
+            cur.Yb[j] = ld4(rRn, oB[j]);
         }
         Zi = Zn;
         wsts(zn + wi * WTILE, lane, Zn);
