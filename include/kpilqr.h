@@ -338,11 +338,19 @@ int  kpilqr_backward_stats(kpilqr_ctx *ctx, int pd_check_stride, int *hist);
 /* K [batch][T][n][m] (column-major m x n), k [batch][T][m]; either may be NULL. */
 int  kpilqr_download_gains(kpilqr_ctx *ctx, double *K, double *k);
 
-/* iLQR_SVR::LeastImportantDofs, "sampling and summing" branch (src/Optimiser/iLQR_SVR.cpp:952-968), on the gains of
- * the last backward pass: sums [batch][dof] = (sum over t = 0, s, 2s, ... and controls j of
- * |K[t](j,i)| + |K[t](j,i+dof)|) / T.  The SVD branch (:902-950) and the state-vector resize it triggers stay on
- * the host (host/SVR.h; the resize is kpilqr_resize). */
+/* iLQR_SVR::LeastImportantDofs on the gains of the last backward pass, both of the reference's measures, with no download of K.
+ * Asynchronous on the context's stream (sums valid after kpilqr_sync); KPILQR_ERR_ARG for a NULL argument or
+ * sampling_k_interval < 1.  Sums of a trajectory whose last backward pass has status != 0 are undefined.  The state-vector
+ * resize a removal triggers is kpilqr_resize.
+ * "Sampling and summing" branch (src/Optimiser/iLQR_SVR.cpp:952-968): sums [batch][dof] = (sum over t = 0, s, 2s, ... < T
+ * and controls j of |K[t](j,i)| + |K[t](j,i+dof)|) / T. */
 int  kpilqr_dof_importance(kpilqr_ctx *ctx, int sampling_k_interval, double *sums);
+/* Singular-vector branch (:902-950): K[t] = U S V', sums [batch][dof] = (sum over t = 0, s, 2s, ... < T and the min(3, m)
+ * largest singular triplets k of |V(i,k) S_k| + |V(i+dof,k) S_k|) / T, the SVD being host/SVR.cpp's one-sided Jacobi
+ * (ThinSVD).  Bit-identical with host/SVR.cpp's DofImportance when n <= 16 and n * m' <= 128 (m' = m rounded up to a power
+ * of two); otherwise equal to rounding.  KPILQR_ERR_ARG also when (n + 1) * m > 8192 (W of one step
+ * does not fit the 64 KB of LDS of one wavefront).  Staging of up to 256 MB is held by the context.  Detect the entry point by its symbol. */
+int  kpilqr_dof_importance_svd(kpilqr_ctx *ctx, int sampling_k_interval, double *sums);
 
 /* ---- STEP 3: forward pass over the line-search alphas ----------------------------------------
  * Nominal controls U_old [batch][T][m] and ModelTranslator::ReturnControlLimits [2*m] = lo,hi pairs. */

@@ -23,7 +23,7 @@ SYMBOLS = [
     "kpilqr_iterate", "kpilqr_set_AB", "kpilqr_get_AB", "kpilqr_set_cost_derivs",
     "kpilqr_get_cost_derivs", "kpilqr_backward_variant", "kpilqr_forward_variant",
     "kpilqr_upload_states", "kpilqr_generate_keypoints", "kpilqr_get_keypoints",
-    "kpilqr_filter_dynamics", "kpilqr_dof_importance",
+    "kpilqr_filter_dynamics", "kpilqr_dof_importance", "kpilqr_dof_importance_svd",
     "kpilqr_comm_unique_id", "kpilqr_comm_init", "kpilqr_allreduce_linesearch",
     "kpilqr_fd_slab_layout", "kpilqr_upload_fd_slab", "kpilqr_iterate_streamed", "kpilqr_resize",
     "kpilqr_keypoint_error_test", "kpilqr_fd_kp_layout", "kpilqr_upload_fd_kp", "kpilqr_backward_stats",
@@ -122,6 +122,7 @@ def load():
     L.kpilqr_get_keypoints.argtypes = [vp, vp, vp, C.c_int]
     L.kpilqr_filter_dynamics.argtypes = [vp, C.c_char_p, vp, C.c_int]
     L.kpilqr_dof_importance.argtypes = [vp, C.c_int, vp]
+    L.kpilqr_dof_importance_svd.argtypes = [vp, C.c_int, vp]
     L.kpilqr_comm_unique_id.argtypes = [vp]
     L.kpilqr_comm_init.argtypes = [vp, C.c_int, C.c_int, vp]
     L.kpilqr_allreduce_linesearch.argtypes = [vp, vp]

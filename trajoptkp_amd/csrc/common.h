@@ -234,6 +234,13 @@ hipError_t launch_unpack_AB(Ctx *c, double *A, double *B);
 hipError_t launch_pack_cost(Ctx *c, const double *lx, const double *lxx, const double *lu, const double *luu);
 hipError_t launch_unpack_cost(Ctx *c, double *lx, double *lxx, double *lu, double *luu);
 
+// svr.hip: iLQR_SVR's singular-vector DoF importance over the resident gains.  svr_lane_form: the lane-per-step form (bit-identical
+// with host/SVR.cpp) takes (n, m); svr_supported: some form does (the wave-per-step form keeps W in at most 64 KB of LDS).
+bool svr_lane_form(int n, int m);
+bool svr_supported(int n, int m);
+size_t svr_stage_bytes(int batch, int dof, int m, int T, int sampling);     // work buffer of launch_dof_importance_svd
+hipError_t launch_dof_importance_svd(Ctx *c, int sampling, double *work);   // sums [batch][dof] at the head of work
+
 // riccati_generic.hip / forward_generic.hip: any (n, m); LDS-resident, op order of the reference.
 hipError_t launch_backward_generic(Ctx *c, int pd_stride);
 hipError_t launch_forward_generic(Ctx *c, double *U_alpha_dev);

@@ -1074,6 +1074,20 @@ int kpilqr_dof_importance(kpilqr_ctx *c, int sampling_k_interval, double *sums)
     return KPILQR_OK;
 }
 
+// iLQR_SVR::LeastImportantDofs, singular-vector branch (iLQR_SVR.cpp:902-950), over the gains of the last backward pass
+int kpilqr_dof_importance_svd(kpilqr_ctx *c, int sampling_k_interval, double *sums)
+{
+    if (!c || !sums) return KPILQR_ERR_ARG;
+    KP_ENTER(c);
+    if (sampling_k_interval < 1) return set_err(c, KPILQR_ERR_ARG, "sampling_k_interval must be >= 1");
+    if (!svr_supported(c->n, c->d.m)) return set_err(c, KPILQR_ERR_ARG, "kpilqr_dof_importance_svd: n * m too large for the LDS of one wave");
+    int rc = ensure_stage(c, svr_stage_bytes(c->d.batch, c->d.dof, c->d.m, c->d.T, sampling_k_interval));
+    if (rc) return rc;
+    KP_HIP(c, launch_dof_importance_svd(c, sampling_k_interval, c->stage));
+    KP_HIP(c, hipMemcpyAsync(sums, c->stage, (size_t)c->d.batch * c->d.dof * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    return KPILQR_OK;
+}
+
 // ---- STEP 3 -------------------------------------------------------------------------------------
 int kpilqr_upload_nominal(kpilqr_ctx *c, const double *u_nom, const double *ctrl_lim)
 {

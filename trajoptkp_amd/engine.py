@@ -304,6 +304,18 @@ class Engine:
         self.sync()
         return out
 
+    def dof_importance_svd(self, sampling_k_interval=1):
+        """iLQR_SVR::LeastImportantDofs (singular-vector branch) over the last gains -> [batch][dof]."""
+        out = np.zeros((self.batch, self.dof))
+        self._ck(self._L.kpilqr_dof_importance_svd(self._h, int(sampling_k_interval), _ptr(out)))
+        self.sync()
+        return out
+
+    def least_important_dofs(self, threshold, sampling_k_interval=1, svd=False):
+        """iLQR_SVR::LeastImportantDofs: per trajectory, the DoFs whose importance is below threshold (strict)."""
+        sums = self.dof_importance_svd(sampling_k_interval) if svd else self.dof_importance(sampling_k_interval)
+        return [[i for i in range(self.dof) if s[i] < threshold] for s in sums]
+
     # -- STEP 1c --------------------------------------------------------------------------------
     def upload_residuals(self, r=None, r_x=None, r_u=None, w_run=None, w_term=None):
         B, T1, n, m, nr = self.batch, self.T + 1, self.n, self.m, self.nr

@@ -41,6 +41,7 @@ def load_host():
     H.kpilqr_host_run_acrobot_batch.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, vp, C.c_int, vp, C.c_int, vp, vp, vp]
     H.kpilqr_host_run_acrobot_batch2.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, vp, C.c_int, C.c_char_p, vp, C.c_int, vp, vp, vp]
     H.kpilqr_host_dof_importance.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, vp, vp]
+    H.kpilqr_host_acrobot_dof_importance.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int, vp, vp]
     H.kpilqr_host_relocate_records.argtypes = [vp, vp, C.c_size_t, C.c_int, C.c_int, vp, vp, vp]
     H.kpilqr_host_model_info.argtypes = [C.c_char_p, vp, vp, vp]
     H.kpilqr_host_fd_kp_check.argtypes = [C.c_char_p, C.c_int, C.c_int, C.c_int, vp, vp]
@@ -251,3 +252,17 @@ def dof_importance(K, dof, sampling_k_interval=1, svd=False, threshold=0.0):
     sums = np.zeros(dof); rem = np.zeros(dof, np.int32)
     cnt = H.kpilqr_host_dof_importance(_p(Kc), dof, m, T, int(sampling_k_interval), int(svd), float(threshold), _p(sums), _p(rem))
     return sums, rem[:cnt].copy()
+
+
+def acrobot_dof_importance(q0s=None, T=100, min_N=5, iters=3, fused=False, sampling_k_interval=1, svd=True):
+    """DofImportance of the optimiser classes on the device after an acrobot run of iters iterations: q0s None = one iLQR_GPU,
+    else an iLQR_GPU_Batch of the swing-ups from q0s [B][2].  Returns (device [B][dof], host/SVR.cpp on the same gains)."""
+    H = load_host()
+    B = 0 if q0s is None else len(q0s)
+    q = None if q0s is None else np.ascontiguousarray(q0s, np.float64)
+    dev = np.zeros((max(B, 1), 2)); ref = np.zeros((max(B, 1), 2))
+    rc = H.kpilqr_host_acrobot_dof_importance(B, T, min_N, iters, None if q is None else _p(q), int(fused), int(sampling_k_interval),
+                                              int(svd), _p(dev), _p(ref))
+    if rc < 0:
+        raise RuntimeError(f"kpilqr_host_acrobot_dof_importance failed: {rc}")
+    return dev, ref

@@ -1,10 +1,12 @@
 // SVR.h -- the state-vector-reduction pieces of iLQR_SVR that touch this path (src/Optimiser/iLQR_SVR.cpp:897-968):
 // the importance of every DoF measured on the feedback gains of the last backward pass, and the list of DoFs below
 // the threshold.  Two measures, as in the reference:
-//   * "sampling and summing" (:952-968): sum over sampled steps and controls of |K(j, i)| + |K(j, i + dof)| -- this one
-//     also runs on the device over the resident gains (kpilqr_dof_importance);
+//   * "sampling and summing" (:952-968): sum over sampled steps and controls of |K(j, i)| + |K(j, i + dof)|;
 //   * the singular-vector method (:902-950): K[t] = U S V', sum over the three largest singular triplets of
-//     |V(i, k) s_k| + |V(i + dof, k) s_k|.  A handful of small SVDs per optimisation: host work.
+//     |V(i, k) s_k| + |V(i + dof, k) s_k|.
+// Both also run on the device over the resident gains (kpilqr_dof_importance, kpilqr_dof_importance_svd: csrc/svr.hip restates
+// ThinSVD below operation for operation); the host classes' DofImportance calls them.  These functions are the reference the
+// device is tested against, and serve callers that hold the gains on the host.
 // The resize that follows a removal is kpilqr_resize (include/kpilqr.h).
 #pragma once
 #include <vector>

@@ -139,6 +139,49 @@ int kpilqr_host_run_acrobot_batch2(int B, int T, int min_N, int max_iter, int mi
     return 0;
 }
 
+// iLQR_SVR's DoF importance through the optimiser classes, on the gains their contexts hold after an acrobot run of iters
+// iterations: B = 0 one iLQR_GPU from the task's start, B >= 1 an iLQR_GPU_Batch of B swing-ups from q0s [B][2].  dev
+// [max(B,1)][dof]: the class's DofImportance (on the device); host [max(B,1)][dof]: host/SVR.cpp's DofImportance on the same
+// gains (iLQR_GPU: its K; iLQR_GPU_Batch: downloaded from its context).  Returns dof, or < 0.
+int kpilqr_host_acrobot_dof_importance(int B, int T, int min_N, int iters, const double *q0s, int fused, int sampling_k_interval,
+                                       int eigen_vector_method, double *dev, double *host)
+{
+    const bool svd = eigen_vector_method != 0;
+    auto make = [&](double q0, double q1) {
+        auto sim = std::make_shared<AcrobotSimulator>(0.01, 8);
+        auto mt = std::make_shared<AcrobotTranslator>(sim);
+        mt->min_N = min_N;
+        sim->main_data->qpos[0] = q0; sim->main_data->qpos[1] = q1;
+        *sim->master_reset_data = *sim->main_data;
+        return iLQR_GPU_Batch::Problem{mt, sim, std::make_shared<Differentiator>(mt, sim)};
+    };
+    if (B == 0) {
+        auto p = make(3.1415, 0.3);
+        iLQR_GPU opt(p.model_translator, p.MuJoCo_helper, p.differentiator, T);
+        if (!opt.ok()) return -2;
+        opt.SetFused(fused != 0);
+        opt.Optimise(p.MuJoCo_helper->main_data, std::vector<MatrixXd>(T, MatrixXd(1, 1)), iters, iters, T);
+        const std::vector<double> d = opt.DofImportance(sampling_k_interval, svd), h = DofImportance(opt.K, 2, sampling_k_interval, svd);
+        std::copy(d.begin(), d.end(), dev); std::copy(h.begin(), h.end(), host);
+        return 2;
+    }
+    std::vector<iLQR_GPU_Batch::Problem> probs;
+    for (int b = 0; b < B; b++) probs.push_back(make(q0s[2 * b], q0s[2 * b + 1]));
+    iLQR_GPU_Batch opt(probs, T, 0, fused != 0);
+    if (!opt.ok()) return -2;
+    opt.OptimiseAll(std::vector<std::vector<MatrixXd>>(B, std::vector<MatrixXd>(T, MatrixXd(1, 1))), iters, iters);
+    const std::vector<std::vector<double>> d = opt.DofImportance(sampling_k_interval, svd);
+    std::vector<double> Kd((size_t)B * T * 4);
+    if (kpilqr_download_gains(opt.Context(), Kd.data(), nullptr) || kpilqr_sync(opt.Context())) return -3;
+    for (int b = 0; b < B; b++) {
+        std::vector<MatrixXd> Kb(T, MatrixXd(1, 4));
+        for (int t = 0; t < T; t++) std::memcpy(Kb[t].data(), Kd.data() + ((size_t)b * T + t) * 4, sizeof(double) * 4);
+        const std::vector<double> h = DofImportance(Kb, 2, sampling_k_interval, svd);
+        std::copy(d[b].begin(), d[b].end(), dev + (size_t)b * 2); std::copy(h.begin(), h.end(), host + (size_t)b * 2);
+    }
+    return 2;
+}
+
 // relocate_records of the batch shim (iLQR_GPU_Batch.cpp) on caller-made slabs: dst == NULL moves in place inside src
 int kpilqr_host_relocate_records(char *src, char *dst, size_t stride, int B, int dof, const int *old_offs, const int *new_offs, const char *regen)
 {

@@ -409,3 +409,13 @@ void iLQR_GPU::DownloadDerivatives(std::vector<MatrixXd> &A, std::vector<MatrixX
         std::copy(b.begin() + (size_t)t * n * m, b.begin() + (size_t)(t + 1) * n * m, B[t].data());
     }
 }
+
+std::vector<double> iLQR_GPU::DofImportance(int sampling_k_interval, bool eigen_vector_method)
+{
+    std::vector<double> sums(dof, 0.0);
+    int rc = eigen_vector_method ? kpilqr_dof_importance_svd(ctx, sampling_k_interval, sums.data())
+                                 : kpilqr_dof_importance(ctx, sampling_k_interval, sums.data());
+    if (rc) fatal(eigen_vector_method ? "kpilqr_dof_importance_svd" : "kpilqr_dof_importance", rc);
+    if ((rc = kpilqr_sync(ctx))) fatal("kpilqr_sync", rc);
+    return sums;
+}

@@ -19,6 +19,9 @@ public:
 
     // gains of the last backward pass, reference layout (K[t] is m x n, k[t] is m x 1)
     std::vector<MatrixXd> K, k;
+    // iLQR_SVR's DoF importance (host/SVR.h, DofImportance) on the gains of the last backward pass as the device holds them,
+    // either branch, without downloading K: [dof]
+    std::vector<double> DofImportance(int sampling_k_interval, bool eigen_vector_method);
     double delta_J = 0.0;
     // A, B, l_* of the last GenerateDerivatives as the reference exposes them (debug hook of the ABI)
     void DownloadDerivatives(std::vector<MatrixXd> &A, std::vector<MatrixXd> &B);

@@ -151,6 +151,18 @@ void relocate_records(const char *src, char *dst, size_t stride, int B, int dof,
     for (int b = B - 1; b >= 0; b--) if (!regen[b] && new_offs[(size_t)b * dof] > old_offs[(size_t)b * dof]) move(b);
 }
 
+std::vector<std::vector<double>> iLQR_GPU_Batch::DofImportance(int sampling_k_interval, bool eigen_vector_method)
+{
+    std::vector<double> flat((size_t)B * dof, 0.0);
+    int rc = eigen_vector_method ? kpilqr_dof_importance_svd(ctx, sampling_k_interval, flat.data())
+                                 : kpilqr_dof_importance(ctx, sampling_k_interval, flat.data());
+    if (rc) fatal(eigen_vector_method ? "kpilqr_dof_importance_svd" : "kpilqr_dof_importance", rc);
+    if ((rc = kpilqr_sync(ctx))) fatal("kpilqr_sync", rc);
+    std::vector<std::vector<double>> sums(B);
+    for (int b = 0; b < B; b++) sums[b].assign(flat.begin() + (size_t)b * dof, flat.begin() + (size_t)(b + 1) * dof);
+    return sums;
+}
+
 // STEP 1 for the trajectories in `who` (Optimiser::GenerateDerivatives, Optimiser.cpp:80-169): key-points and FD
 // on the host (every trajectory on its own persistent pool, all into ONE pinned slab), then the GPU
 // stages for the whole batch.  Trajectories not in `who` keep their linearisation: on a materialising context their key-point

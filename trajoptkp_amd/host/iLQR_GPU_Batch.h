@@ -35,6 +35,10 @@ public:
     std::vector<int> num_iterations;
     std::vector<double> lambda;
     std::vector<std::vector<MatrixXd>> K, k;
+    // iLQR_SVR's DoF importance (host/SVR.h, DofImportance) of every trajectory on the gains of the last backward pass as the
+    // device holds them, either branch, without downloading K: [B][dof]
+    std::vector<std::vector<double>> DofImportance(int sampling_k_interval, bool eigen_vector_method);
+    kpilqr_ctx *Context() const { return ctx; }
     // line-search statistics of the last iteration, the 8 doubles of the multi-GPU reduction
     // (sum_b J_pred(alpha_1..6), sum_b delta_J, #valid backward passes) -- SURVEY.md section 8e
     double linesearch_stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
