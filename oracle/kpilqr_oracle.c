@@ -471,8 +471,10 @@ int orc_backward(int n, int m, int T,
     double *Q_ux = (double *)malloc(sizeof(double) * nm), *Q_uu_reg = (double *)malloc(sizeof(double) * mm_);
     double *inv = (double *)malloc(sizeof(double) * mm_);
     double *AtV = (double *)malloc(sizeof(double) * nn), *BtV = (double *)malloc(sizeof(double) * nm);
-    double *t1 = (double *)malloc(sizeof(double) * nn), *t2 = (double *)malloc(sizeof(double) * nn);
-    double *t3 = (double *)malloc(sizeof(double) * nn), *t4 = (double *)malloc(sizeof(double) * nn);
+    /* work matrices: n x n, m x m (Q_uu, -Q_uu^-1) and m x n products -- the largest of the three (m > n: under-sized before) */
+    const size_t tw = nn > mm_ ? (nn > nm ? nn : nm) : (mm_ > nm ? mm_ : nm);
+    double *t1 = (double *)malloc(sizeof(double) * tw), *t2 = (double *)malloc(sizeof(double) * tw);
+    double *t3 = (double *)malloc(sizeof(double) * tw), *t4 = (double *)malloc(sizeof(double) * tw);
     int ret = 0;
 
     memcpy(V_x, l_x + (size_t)(T - 1) * n, sizeof(double) * n);        /* :537 */

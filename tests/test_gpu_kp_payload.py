@@ -316,12 +316,14 @@ def test_constant_residual_jacobians_give_the_bytes_of_the_streamed_form(task, T
         assert relerr(ref["K"][b], o["K"]) < 1e-9 and relerr(ref["cost"][b], o["cost_pred"]) < 1e-9
 
 
-@pytest.mark.parametrize("task,T", [("acrobot", 100), ("pentabot", 64), ("panda_reaching", 131)])
+@pytest.mark.parametrize("task,T", [("acrobot", 100), ("pentabot", 64), ("panda_reaching", 131)]
+                         + [pytest.param(synth.shape_task(7, 7, nr), 60, id=f"panda_nr{nr}-60") for nr in (1, 9, 15)])
 def test_residual_row_fetched_in_pairs_ignores_what_lies_behind_it(task, T, waves):
     """Round 5: the one-wave sweeps on uniform key-point sets fetch r_t with two 16-byte requests (residual rows relabelled so that
     a lane's registers hold consecutive residuals).  With an odd residual count (acrobot 5, pentabot 3) the last pair of row t
     reaches one element into row t+1 -- under a zero weight: whatever finite number sits there (here 1e300 in the whole row t = T,
-    which no stage uses) changes no bit of any result."""
+    which no stage uses) changes no bit of any result.  The panda shape at nr = 1, 9, 15: one, three and four residual chunks
+    (RV2B in fused_mfma.hip), 15 the odd count whose last pair comes from the last register."""
     p = synth.make_problem(task=task, T=T, batch=3, min_N=4, config_id=1 if task == "acrobot" else 2)
     assert p["rx_const"] is not None
     q = dict(p); q["r"] = p["r"].copy(); q["r"][:, T, :] = 1.0e300

@@ -59,6 +59,25 @@ TASKS = {
 }
 
 
+def shape_task(dof, m, nr, dt=0.008, lim=None):
+    """A task of any shape (dof, m, nr): the cfg dict of TASKS, to be passed as `task` to make_problem / make_ragged_problem.
+    Weights and limits are deterministic functions of the shape: running weights 1, 0.5, 0.1, 0.05, 0.01, ... (a decade every
+    two residuals), terminal weights 100 times those, control limits 50 (or `lim`, a scalar or one per control).  The selector-row
+    residual Jacobian (rx_const) works for any nr; m > dof is allowed (the extra actuators act on the DoFs again, cyclically)."""
+    w_run = [float(10.0 ** -(i // 2)) * (1.0 if i % 2 == 0 else 0.5) for i in range(nr)]
+    lim = [50.0] * m if lim is None else ([float(lim)] * m if np.isscalar(lim) else [float(x) for x in lim])
+    assert len(lim) == m
+    return dict(dof=int(dof), m=int(m), nr=int(nr), dt=float(dt), lim=lim, w_run=w_run, w_term=[100.0 * w for w in w_run],
+                name=f"shape_{dof}x{m}x{nr}")
+
+
+def _task_cfg(task):
+    """(name, cfg) of a task given by name (TASKS) or as a cfg dict (shape_task)."""
+    if isinstance(task, dict):
+        return task.get("name", f"shape_{task['dof']}x{task['m']}x{task['nr']}"), task
+    return task, TASKS[task]
+
+
 def seed_for(config_id, b):
     return 0x5EED0000 + config_id * 1_000_003 + b
 
@@ -101,7 +120,7 @@ def _dynamics_keypoints(rng, dof, m, dt, kp_times):
         Ak[dof:, :dof] += dt * (-Minv @ np.diag(stiff))
         Ak[dof:, dof:] += dt * (-Minv @ np.diag(damp))
         Bk = np.zeros((n, m))
-        Bk[dof:, :] = dt * Minv[:, :m]
+        Bk[dof:, :] = dt * Minv[:, np.arange(m) % dof]      # (m > dof, shape tasks only: actuators act on the DoFs cyclically)
         A[k] = Ak.T          # column-major: [c, r]
         B[k] = Bk.T
     return A, B
@@ -109,8 +128,9 @@ def _dynamics_keypoints(rng, dof, m, dt, kp_times):
 
 def make_problem(task="panda_reaching", T=3000, batch=1, min_N=5, config_id=2, dense_residuals=False,
                  one_sided_frac=0.0, lam=0.1, eps=1e-6, first_b=0):
-    """Builds one batch of `batch` trajectories.  Returns a dict of numpy arrays in C-ABI layout."""
-    cfg = TASKS[task]
+    """Builds one batch of `batch` trajectories.  Returns a dict of numpy arrays in C-ABI layout.  task: a name of TASKS or a cfg
+    dict (shape_task)."""
+    task, cfg = _task_cfg(task)
     dof, m, nr, dt = cfg["dof"], cfg["m"], cfg["nr"], cfg["dt"]
     n = 2 * dof
     lim = np.asarray(cfg["lim"], dtype=np.float64)
@@ -279,8 +299,8 @@ def make_ragged_problem(task, T, kp_rows, dyn=None, config_id=3, dense_residuals
     every DoF has its own key-point times) and FD jobs only where the reference would compute them: at step t the
     columns of the DoFs listed in keypoints[t] (control column i for i < num_ctrl, velocity column i+dof, position
     column i; Differentiator.cpp:81-428).  dyn: optional list of dense (A [T,n,n], B [T,m,n]) per trajectory (else a
-    random walk over the union of key-point times)."""
-    cfg = TASKS[task]
+    random walk over the union of key-point times).  task: a name of TASKS or a cfg dict (shape_task)."""
+    task, cfg = _task_cfg(task)
     dof, m, nr, dt = cfg["dof"], cfg["m"], cfg["nr"], cfg["dt"]
     n = 2 * dof
     batch = len(kp_rows)
