@@ -62,8 +62,8 @@ def forward_wide_supported(n, m, n_alpha, nt_min=0):    # tiled_wide.hip:724
 
 
 def select_variants(dof, m, nr, T, n_alpha, batch, flags, env=None):
-    """select_variants (kpilqr_api.cpp:304-339): (backward variant, forward variant), or None where kpilqr_create refuses the
-    shape with KPILQR_ERR_ARG (the generic backward sweep's LDS, :334)."""
+    """select_variants (kpilqr_api.cpp:297-332): (backward variant, forward variant), or None where kpilqr_create refuses the
+    shape with KPILQR_ERR_ARG (the generic backward sweep's LDS, :327)."""
     n = 2 * dof
     nt_min = _env(env, "KPILQR_TILED_NT_MIN", 0)
     generic, force_tiled = bool(flags & FLAG_GENERIC), bool(flags & FLAG_TILED)
@@ -76,7 +76,7 @@ def select_variants(dof, m, nr, T, n_alpha, batch, flags, env=None):
     fused = bool(flags & FLAG_FUSED) and not generic and not force_tiled and fused_supported(n, m, nr, dof, T, n_alpha)
     if fused:
         bv = fv = "mfma_f64_t1_fused"
-    elif flags & FLAG_FUSED and bv == fv == "mfma_f64_tiled":           # :328-333
+    elif flags & FLAG_FUSED and bv == fv == "mfma_f64_tiled":           # :321-326
         a6 = _env(env, "KPILQR_TILED_A6", -1)
         if nr <= 16 and (a6 != 0 if a6 >= 0 else (tiled_nt(n, nt_min) == 4 and batch >= 96)):
             bv = fv = "mfma_f64_tiled_a6"
@@ -104,16 +104,16 @@ def dispatch(dof, m, nr, T, n_alpha, batch, n_simd, flags, env=None, rx_const=Fa
     n = 2 * dof
     nt = tiled_nt(n, _env(env, "KPILQR_TILED_NT_MIN", 0))
     uw = _env(env, "KPILQR_TILED_UW", -1)
-    excl = "excl" if batch <= n_simd else "plain"       # riccati_mfma.hip:384, forward_mfma.hip:194, fused_mfma.hip:2296, 2403
+    excl = "excl" if batch <= n_simd else "plain"       # riccati_mfma.hip:384, forward_mfma.hip:193, FusedLaunch::excl, fused_mfma.hip:2283, 2303
     ncz, ncu = (n + 2 + 3) // 4, (m + 3) // 4
     out = dict(variants=(bv, fv), extra=(), launch=(bv, fv))
     if bv == "mfma_f64_t1_fused":
         f = _env(env, "KPILQR_FUSED_WAVES", 0)
-        bform = f if f in (1, 5) else (5 if 2 * batch <= n_simd else 1)           # backward_fused_form, fused_mfma.hip:2272
+        bform = f if f in (1, 5) else (5 if 2 * batch <= n_simd else 1)           # plan_backward_fused, fused_mfma.hip:2272-2276
         f = _env(env, "KPILQR_FUSED_FWD_WAVES", 0)
-        fform = f if f in (1, 3, 4) else (4 if 2 * batch <= n_simd else 1)        # forward_fused_form, :2285
+        fform = f if f in (1, 3, 4) else (4 if 2 * batch <= n_simd else 1)        # plan_forward_fused, :2294-2298
         out["bwd"] = ("fused_bwd", n, m, "w1", excl) if bform == 1 else ("fused_bwd", n, m, "pairh", "-")
-        if fform == 4:                                  # the uniform pair; per-DoF lists run the triple or w1 behind it (:2414-2439)
+        if fform == 4:                                  # the uniform pair; per-DoF lists run the triple or w1 behind it (waves_ragged, :2299)
             behind = 3 if 4 * batch <= n_simd else 1
             fform_ran = 4 if uniform else behind
         else:
@@ -123,12 +123,12 @@ def dispatch(dof, m, nr, T, n_alpha, batch, n_simd, flags, env=None, rx_const=Fa
         rxc = rx_const and ru_zero
         if rxc and bform == 1:
             out["extra"] = (("fused_rv2", n, m, rv2_ncr(nr)),)
-        # kpilqr_last_launch (kpilqr_api.cpp:1524): ":w1:" / ":pairh:" / ":pair:" / ":triple:" (the forward pair reports the form
+        # kpilqr_last_launch (kpilqr_api.cpp:1517): ":w1:" / ":pairh:" / ":pair:" / ":triple:" (the forward pair reports the form
         # that ran on this set)
         out["launch"] = (bv + (":w1:" if bform == 1 else ":pairh:"), fv + ":" + {1: "w1", 3: "triple", 4: "pair"}[fform_ran] + ":")
         return out
     if bv == "mfma_f64_t1":
-        out["bwd"] = ("t1_bwd", n, m, excl)             # launch_backward_mfma, riccati_mfma.hip:380
+        out["bwd"] = ("t1_bwd", n, m, excl)             # launch_backward_mfma, riccati_mfma.hip:390
     elif bv.startswith("mfma_f64_tiled"):
         a6 = bv.endswith("_a6")
         M = 7 if m == 7 else 1 if m == 1 else 8         # launch_backward_tiled, tiled_mfma.hip:1134-1140
@@ -146,7 +146,7 @@ def dispatch(dof, m, nr, T, n_alpha, batch, n_simd, flags, env=None, rx_const=Fa
         out["bwd"] = ("wide_bwd", nt, 2 if m > 16 else 1)   # launch_backward_wide, tiled_wide.hip:513-519
     else:
         out["bwd"] = ("generic_bwd",)
-    if fv == "mfma_f64_t1":                             # launch_forward_mfma, forward_mfma.hip:189-209
+    if fv == "mfma_f64_t1":                             # launch_forward_mfma, forward_mfma.hip:199-204
         out["fwd"] = ("t1_fwd", max(ncz, 2), min(ncu, 2), excl)
     elif fv.startswith("mfma_f64_tiled"):
         a6 = fv.endswith("_a6")
@@ -171,12 +171,12 @@ def _compiled():
     """The instantiations the library compiles, by hand from the launchers (not derived from dispatch)."""
     keys = []
     for n, m in T1_SHAPES:
-        keys += [("t1_bwd", n, m, e) for e in ("excl", "plain")]                       # riccati_mfma.hip:386-397
-        keys += [("fused_bwd", n, m, "w1", e) for e in ("excl", "plain")]              # fused_mfma.hip:2308-2340
-        keys += [("fused_bwd", n, m, "pairh", "-")]                                    # :2351-2382
+        keys += [("t1_bwd", n, m, e) for e in ("excl", "plain")]                       # launch_bm, riccati_mfma.hip:380-395
+        keys += [("fused_bwd", n, m, "w1", e) for e in ("excl", "plain")]              # launch_bf_kernel ... launch_backward_fused, fused_mfma.hip:2308-2352
+        keys += [("fused_bwd", n, m, "pairh", "-")]                                    # launch_bph_kernel ... launch_backward_fused_pair, :2358-2393
         keys += [("fused_rv2", n, m, ncr) for ncr in (1, 2, 3, 4)]                     # :343
-    keys += [("t1_fwd", ncz, ncu, e) for ncz in (2, 3, 4) for ncu in (1, 2) for e in ("excl", "plain")]   # forward_mfma.hip:205-206
-    for ncz, ncu in ((4, 2), (2, 1), (4, 1), (3, 1)):                                  # fused_mfma.hip:2425, 2451, 2481
+    keys += [("t1_fwd", ncz, ncu, e) for ncz in (2, 3, 4) for ncu in (1, 2) for e in ("excl", "plain")]   # launch_fm, forward_mfma.hip:189-203
+    for ncz, ncu in ((4, 2), (2, 1), (4, 1), (3, 1)):                                  # KP_FWD_SHAPES, fused_mfma.hip:2458 (launch_ff_pair, _triple, _w1: 2418-2448)
         keys += [("fused_fwd", ncz, ncu, "w1", e) for e in ("excl", "plain")]
         keys += [("fused_fwd", ncz, ncu, f, "-") for f in ("pair", "triple")]
     for M in (1, 7, 8):                                                                # tiled_mfma.hip:1134-1140
@@ -296,7 +296,7 @@ def cases(n_simd):
 
 
 def generic_max_dof(m):
-    """The largest dof whose generic backward sweep fits the LDS bound (kpilqr_api.cpp:334, generic.hip:93)."""
+    """The largest dof whose generic backward sweep fits the LDS bound (kpilqr_api.cpp:327, generic.hip:93)."""
     dof = 1
     while generic_lds_bytes(2 * (dof + 1), m) <= LDS_MAX:
         dof += 1

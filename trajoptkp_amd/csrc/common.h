@@ -39,6 +39,20 @@ struct RecLayout {
     __host__ __device__ int b(int row, int col) const { return off_B + col * n + row; }
 };
 
+// ---- what one launch of a fused (one-tile) sweep is ------------------------------------------
+// Made by plan_backward_fused / plan_forward_fused (fused_mfma.hip, where the policy is explained) and read by everyone else: the
+// launchers map it to kernels, run_backward / run_forward ask it whether r_x needs its broadcast copy, kpilqr_last_launch prints it.
+enum class Waves : int { none, w1, pair, triple, pairh };      // (kpilqr_last_launch's names; none: not a fused launch)
+struct FusedLaunch {
+    Waves waves = Waves::none;          // wave organisation: one wave per trajectory | state / cost pair | + staging wave | consumer / helper pair
+    Waves waves_ragged = Waves::none;   // forward: what runs behind the uniform pair on per-DoF lists (triple or w1); else = waves
+    bool raw = false;                   // backward: the sweep differences the key-point ordered payload itself
+    bool ru0 = false;                   // r_u = 0: the instantiations without the r_u loads and the Ju product
+    bool rxc = false;                   // constant r_x kept in registers (ru0 instantiations only): nobody reads the r_x buffer
+    bool slopes = false;                // the general (per-DoF list) form walks the slope store
+    bool excl = false;                  // w1: every wave has a SIMD to itself (the _excl twins)
+};
+
 struct Ctx {
     kpilqr_dims d{};
     int n = 0;
@@ -165,12 +179,8 @@ struct Ctx {
 
     const char *bwd_variant = "";
     const char *fwd_variant = "";
-    // what the last backward / forward launch of this context actually was (kpilqr_last_launch): wave organisation
-    // (1 one wave per trajectory, 3 pair, 4 triple, 5 consumer / helper pair; 0: not a fused launch, or none yet), whether the
-    // sweep differenced the raw payload itself, which residual instantiation ran
-    int last_bwd_form = 0, last_fwd_form = 0, last_fwd_form_ragged = 0;      // (_ragged: the form that ran instead on per-DoF lists, if another)
-    bool last_bwd_raw = false, last_bwd_ru0 = false, last_fwd_ru0 = false, last_bwd_rxc = false, last_fwd_rxc = false;
-    bool last_bwd_slopes = false, last_fwd_slopes = false;
+    // what the last backward / forward launch of this context actually was (kpilqr_last_launch); Waves::none: not a fused launch, or none yet
+    FusedLaunch last_bwd, last_fwd;
     std::string launch_desc[2];
 
     // Diagnostic switches, read from the environment ONCE by kpilqr_create; the launchers only
@@ -266,12 +276,12 @@ hipError_t launch_backward_wide(Ctx *c, int pd_stride);
 bool forward_wide_supported(int n, int m, int n_alpha, int nt_min);
 hipError_t launch_forward_wide(Ctx *c, double *U_alpha_dev);
 // fused_mfma.hip: a4 + a6 evaluated inside the sweeps (n+2 <= 16)
-bool fused_supported(int n, int m, int nr, int dof, int T, int stride, int n_alpha);
-int backward_fused_form(const Ctx *c);
-int forward_fused_form(const Ctx *c);
-hipError_t launch_backward_fused(Ctx *c, int pd_stride, bool raw);
-hipError_t launch_backward_fused_waves(Ctx *c, int pd_stride, bool raw);      // form 5 (fused_mfma.hip, part 2)
-hipError_t launch_forward_fused(Ctx *c, double *U_alpha_dev);
+bool fused_supported(int n, int m, int nr, int dof, int T, int n_alpha);
+FusedLaunch plan_backward_fused(const Ctx *c, bool raw);     // raw: the sweep differences the key-point ordered payload itself
+FusedLaunch plan_forward_fused(const Ctx *c);
+hipError_t launch_backward_fused(Ctx *c, const FusedLaunch &p, int pd_stride);
+hipError_t launch_backward_fused_pair(Ctx *c, const FusedLaunch &p, int pd_stride);     // Waves::pairh (fused_mfma.hip, part 2)
+hipError_t launch_forward_fused(Ctx *c, const FusedLaunch &p, double *U_alpha_dev);
 hipError_t launch_backward_fused_stats(Ctx *c, int pd_stride, int *hist_dev);
 
 }  // namespace kpilqr

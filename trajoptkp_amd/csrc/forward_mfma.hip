@@ -186,27 +186,21 @@ bool forward_mfma_supported(int n, int m, int n_alpha)
     return (n + 2 <= 16) && (m <= 8) && (n_alpha <= 16) && n >= 2;
 }
 
+// excl: every wave has a SIMD to itself
+template <int NCZ, int NCU>
+static hipError_t launch_fm(Ctx *c, double *U_alpha_dev)
+{
+    const auto kernel = c->d.batch <= c->n_simd ? k_forward_mfma_excl<NCZ, NCU> : k_forward_mfma<NCZ, NCU>;
+    hipLaunchKernelGGL(kernel, dim3(c->d.batch), dim3(64), 0, c->stream, c->L, c->d.T, c->d.n_alpha, c->rec, c->K, c->k, c->u_nom,
+                       c->ctrl_lim, c->alphas, c->cost_pred, U_alpha_dev);
+    return hipGetLastError();
+}
+
 hipError_t launch_forward_mfma(Ctx *c, double *U_alpha_dev)
 {
-    const int n = c->n, m = c->d.m;
-    const int ncz = (n + 2 + 3) / 4, ncu = (m + 3) / 4;
-    dim3 grid(c->d.batch), block(64);
-    const bool excl = c->d.batch <= c->n_simd;
-#define LAUNCH(NCZ, NCU)                                                                                         \
-    do {                                                                                                         \
-        if (excl)                                                                                                \
-            hipLaunchKernelGGL((k_forward_mfma_excl<NCZ, NCU>), grid, block, 0, c->stream, c->L, c->d.T,         \
-                               c->d.n_alpha, c->rec, c->K, c->k, c->u_nom, c->ctrl_lim, c->alphas, c->cost_pred, \
-                               U_alpha_dev);                                                                     \
-        else                                                                                                     \
-            hipLaunchKernelGGL((k_forward_mfma<NCZ, NCU>), grid, block, 0, c->stream, c->L, c->d.T,              \
-                               c->d.n_alpha, c->rec, c->K, c->k, c->u_nom, c->ctrl_lim, c->alphas, c->cost_pred, \
-                               U_alpha_dev);                                                                     \
-    } while (0)
-    if (ncu <= 1) { if (ncz <= 2) LAUNCH(2, 1); else if (ncz == 3) LAUNCH(3, 1); else LAUNCH(4, 1); }
-    else          { if (ncz <= 2) LAUNCH(2, 2); else if (ncz == 3) LAUNCH(3, 2); else LAUNCH(4, 2); }
-#undef LAUNCH
-    return hipGetLastError();
+    const int ncz = (c->n + 2 + 3) / 4, ncu = (c->d.m + 3) / 4;
+    if (ncu <= 1) return ncz <= 2 ? launch_fm<2, 1>(c, U_alpha_dev) : ncz == 3 ? launch_fm<3, 1>(c, U_alpha_dev) : launch_fm<4, 1>(c, U_alpha_dev);
+    return ncz <= 2 ? launch_fm<2, 2>(c, U_alpha_dev) : ncz == 3 ? launch_fm<3, 2>(c, U_alpha_dev) : launch_fm<4, 2>(c, U_alpha_dev);
 }
 
 }  // namespace kpilqr

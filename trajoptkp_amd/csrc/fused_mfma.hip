@@ -24,7 +24,7 @@
 //     The forward pass scores a candidate with the same model written on the residuals:
 //         l_x'dx + dx'l_xx dx/2 = sum_k w_k Jx_k (2 r_k + Jx_k),   Jx = r_x dx      (likewise for du).
 //
-// Wave organisations (launch_backward_fused / launch_forward_fused pick by batch size):
+// Wave organisations (plan_backward_fused / plan_forward_fused pick by batch size):
 //   backward: one wave per trajectory (batch > #SIMDs/2) | consumer / helper pair;
 //   forward:  one wave -- in a form for uniform key-point sets (no LDS transpose) and a general one, chosen on the device --
 //             | state / cost pair | state / cost / staging triple.
@@ -2245,9 +2245,8 @@ k_forward_fused_sc3(RecLayout L, FusedArgs F, int T, int n_alpha, const double *
 }
 
 #if KP_PART(1)
-bool fused_supported(int n, int m, int nr, int dof, int T, int stride, int n_alpha)
+bool fused_supported(int n, int m, int nr, int dof, int T, int n_alpha)
 {
-    (void)stride;
     // one trajectory's slice of the key-point column store (at most T entries per DoF, 3n doubles each) behind one descriptor
     return kp_t1_shape(n, m) && nr >= 1 && nr <= 16 && m <= dof && n_alpha <= 16 && (long long)T * dof * (6 * n + 2) * 8 < (long long)BIGOFF;
 }
@@ -2262,122 +2261,134 @@ static FusedArgs fused_args(const Ctx *c)
 }
 
 #if KP_PART(1)
-// Which wave organisation launch_backward_fused will pick: 1 one wave per trajectory, 5 the consumer / helper pair (both have RAW
-// instantiations).  While a trajectory can have two SIMDs (2 x batch <= #SIMDs) the pair runs it: the consumer's chain is
+// ---- the plans: WHAT a fused sweep launch is (FusedLaunch, common.h).  The launchers below map a plan to kernels and decide nothing.
+// Backward.  While a trajectory can have two SIMDs (2 x batch <= #SIMDs) the consumer / helper pair runs it: the consumer's chain is
 // Tu | Quu | refresh | gains | V', the helper forms the side products Tz, Quz, Qzz, then a4 + a6 of the next step, and differences
 // the payload of uniform sets.  Beyond that two waves take turns on a SIMD and one wave per trajectory wins.
-// KPILQR_FUSED_WAVES = 1 | 5 forces a form (diagnostic, include/kpilqr.h).  Rounds 2-4 also had a control / state split (2), a
-// producer / consumer pair (3) and a consumer / side / producer triple (4): all measured slower than the helper pair at every
-// batch size (profiles/r04_helper_pair.txt) and were removed in round 5 (DESIGN_HISTORY.md keeps their numbers).
-int backward_fused_form(const Ctx *c)
+// Both have RAW instantiations.  KPILQR_FUSED_WAVES = 1 (one wave) | 5 (the pair) forces one (diagnostic, include/kpilqr.h); any
+// other value is the library's choice.  Rounds 2-4 also had a control / state split, a producer / consumer pair and a consumer /
+// side / producer triple: all measured slower than the helper pair at every batch size (profiles/r04_helper_pair.txt) and were
+// removed in round 5 (DESIGN_HISTORY.md keeps their numbers).
+FusedLaunch plan_backward_fused(const Ctx *c, bool raw)
 {
     const int f = c->tune.fused_bwd_waves;
-    return (f == 1 || f == 5) ? f : (2 * c->d.batch <= c->n_simd ? 5 : 1);
+    FusedLaunch p;
+    p.waves = p.waves_ragged = f == 1 ? Waves::w1 : (f == 5 || 2 * c->d.batch <= c->n_simd) ? Waves::pairh : Waves::w1;
+    p.raw = raw;
+    p.ru0 = c->ru_zero;
+    p.rxc = c->ru_zero && c->rx_const_on;       // (the constant-Jacobian kernels exist with r_u = 0 only)
+    // per-DoF lists walk the slope store (made by k_fd_kp_difference / k_kp_slopes for such sets only) -- but for the GENERAL raw
+    // form of the one-wave sweep (KPILQR_FUSED_UNI=0, diagnostic), which differences every set itself and divides at its crossings
+    p.slopes = c->kps != nullptr && !(p.waves == Waves::w1 && raw && c->tune.fused_uni == 0);
+    p.excl = c->d.batch <= c->n_simd;
+    return p;
 }
 
-// The wave organisation launch_forward_fused will pick: 1 one wave per trajectory, 3 the state / cost / staging triple, 4 (the
-// default while 2 x batch <= #SIMDs) the state / cost pair for UNIFORM key-point sets -- the state wave interpolates its own
-// operands, no staging wave -- with the triple (4 x batch <= #SIMDs) or the one-wave general form behind it for per-DoF lists;
-// the device flag decides which of the two runs.  Late round 4, with r_u = 0 / constant-r_x instantiations of the scoring wave and
-// a state wave that issues 7 loads per step instead of 10 (profiles/r04_forward_forms.txt): 1.31 / 1.43 / 1.47 ms at 1 / 64 / 256
-// trajectories (one wave per trajectory: 1.72).  KPILQR_FUSED_FWD_WAVES = 1 | 3 | 4 forces a form (diagnostic,
-// include/kpilqr.h); any other value is ignored, as in backward_fused_form.
-int forward_fused_form(const Ctx *c)
+// Forward.  While 2 x batch <= #SIMDs the state / cost pair runs UNIFORM key-point sets -- the state wave interpolates its own
+// operands, no staging wave -- with the state / cost / staging triple (4 x batch <= #SIMDs) or the one-wave general form behind it
+// for per-DoF lists; the device flag decides which of the two runs.  Beyond that one wave per trajectory, its tile requests four
+// steps ahead.  Late round 4, with r_u = 0 / constant-r_x instantiations of the scoring wave and a state wave that issues 7 loads
+// per step instead of 10 (profiles/r04_forward_forms.txt): 1.31 / 1.43 / 1.47 ms at 1 / 64 / 256 trajectories (one wave per
+// trajectory: 1.72; the triple alone: 1.58 at B = 1, 1.74 ... 1.76 at B = 128 ... 256).  KPILQR_FUSED_FWD_WAVES = 1 (one wave) |
+// 3 (triple) | 4 (pair) forces one (diagnostic, include/kpilqr.h); any other value is the library's choice.
+FusedLaunch plan_forward_fused(const Ctx *c)
 {
     const int f = c->tune.fused_fwd_waves;
-    return (f == 1 || f == 3 || f == 4) ? f : (2 * c->d.batch <= c->n_simd ? 4 : 1);
+    FusedLaunch p;
+    p.waves = f == 1 ? Waves::w1 : f == 3 ? Waves::triple : (f == 4 || 2 * c->d.batch <= c->n_simd) ? Waves::pair : Waves::w1;
+    p.waves_ragged = p.waves != Waves::pair ? p.waves : 4 * c->d.batch <= c->n_simd ? Waves::triple : Waves::w1;
+    p.ru0 = c->ru_zero;
+    p.rxc = c->ru_zero && c->rx_const_on;       // (every form's cost wave has its constant-Jacobian instantiation, with r_u = 0 only)
+    p.slopes = p.waves_ragged == Waves::w1 && c->kps != nullptr;
+    p.excl = c->d.batch <= c->n_simd;
+    return p;
 }
 
-// raw: difference the key-point ordered payload inside the sweep (one-wave form only; the caller checks backward_fused_form)
-hipError_t launch_backward_fused(Ctx *c, int pd_stride, bool raw)
+// ---- one wave per trajectory, backward
+template <int NN, int MM, bool RU, bool RW, bool UN, bool RX>
+static void launch_bf_kernel(Ctx *c, const FusedLaunch &p, const FusedArgs &F, int pd_stride)
 {
+    const auto kernel = p.excl ? k_backward_fused_excl<NN, MM, RU, RW, UN, RX> : k_backward_fused<NN, MM, RU, RW, UN, RX>;
+    hipLaunchKernelGGL(kernel, dim3(c->d.batch), dim3(64), 0, c->stream, c->L, F, c->d.T, c->lambda, pd_stride, c->K, c->k, c->delta_J,
+                       c->status, c->kp_uniform);
+}
+// rxc: constant residual Jacobians.  The kernels exist with r_u = 0 only, hence RX = RU: nothing is compiled for <RU = false, RX = true>
+template <int NN, int MM, bool RU, bool RW, bool UN>
+static void launch_bf_form(Ctx *c, const FusedLaunch &p, const FusedArgs &F, int pd_stride)
+{
+    if (RU && p.rxc) launch_bf_kernel<NN, MM, RU, RW, UN, RU>(c, p, F, pd_stride);
+    else launch_bf_kernel<NN, MM, RU, RW, UN, false>(c, p, F, pd_stride);
+}
+// The launch sequence: the uniform and the general form back to back, the one whose kind of key-point set is not resident leaves
+// at once.  raw: only UNIFORM sets are differenced inside the sweep; for per-DoF lists a lane's crossing is a divergent branch that
+// every lane of the wave pays for (17 loads, 8 stores on most steps), and the streaming kernel + the plain general sweep are faster
+// (iterative-error lists with a key-point on 99 % of the steps: 8.7 + 2.2 against 11.9 ms) -- k_fd_kp_difference is launched in
+// between and looks at the same device flag.  (KPILQR_FUSED_UNI=0, diagnostic: the general form alone, raw or not, for every set.)
+template <int NN, int MM, bool RU>
+static hipError_t launch_bf_sequence(Ctx *c, const FusedLaunch &p, const FusedArgs &F, int pd_stride)
+{
+    const bool uni = c->tune.fused_uni != 0;
+    if (p.raw && uni) {
+        launch_bf_form<NN, MM, RU, true, true>(c, p, F, pd_stride);
+        const hipError_t e = launch_fd_kp_difference(c, true);     // (per-DoF lists: columns and their slopes)
+        if (e != hipSuccess) return e;
+        launch_bf_form<NN, MM, RU, false, false>(c, p, F, pd_stride);
+    } else if (p.raw) launch_bf_form<NN, MM, RU, true, false>(c, p, F, pd_stride);
+    else {
+        if (uni) launch_bf_form<NN, MM, RU, false, true>(c, p, F, pd_stride);
+        launch_bf_form<NN, MM, RU, false, false>(c, p, F, pd_stride);
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_backward_fused(Ctx *c, const FusedLaunch &p, int pd_stride)
+{
+    if (p.waves == Waves::pairh) return launch_backward_fused_pair(c, p, pd_stride);
     const int n = c->n, m = c->d.m;
-    dim3 grid(c->d.batch), block(64);
-    const bool excl = c->d.batch <= c->n_simd;
     const FusedArgs F = fused_args(c);
-    // Wave organisation of the backward sweep (backward_fused_form above).  While every wave of the consumer / helper pair can have
-    // a SIMD to itself (2 x batch <= #SIMDs) the pair is the fastest form; beyond that two waves take turns on a SIMD and one wave
-    // per trajectory wins (DESIGN.md sections 4.0, 4.4).  KPILQR_FUSED_WAVES forces a form: 1 = one wave, 5 = the consumer / helper pair.
-    const int form = backward_fused_form(c);
-    if (raw && form != 1 && form != 5) return hipErrorInvalidValue;
-    c->last_bwd_form = form; c->last_bwd_raw = raw; c->last_bwd_ru0 = form == 1 && c->ru_zero;       // kpilqr_last_launch
-    const bool rxc = form == 1 && c->ru_zero && c->rx_const_on;     // (the caller has materialised r_x for every other form)
-    c->last_bwd_rxc = rxc;
-    c->last_bwd_slopes = form == 1 && c->kps != nullptr && !(raw && c->tune.fused_uni == 0);      // (what the general form walks, if it runs)
-    if (form != 1) return launch_backward_fused_waves(c, pd_stride, raw);
-#define LAUNCH5(NN, MM, RU, RW, UN, RX)                                                                       \
-    do {                                                                                                     \
-        if (excl)                                                                                            \
-            hipLaunchKernelGGL((k_backward_fused_excl<NN, MM, RU, RW, UN, RX>), grid, block, 0, c->stream, c->L, F, c->d.T,  \
-                               c->lambda, pd_stride, c->K, c->k, c->delta_J, c->status, c->kp_uniform);      \
-        else                                                                                                 \
-            hipLaunchKernelGGL((k_backward_fused<NN, MM, RU, RW, UN, RX>), grid, block, 0, c->stream, c->L, F, c->d.T,   \
-                               c->lambda, pd_stride, c->K, c->k, c->delta_J, c->status, c->kp_uniform);      \
-    } while (0)
-// rxc: constant residual Jacobians (with r_u = 0 only: RU instantiations)
-#define LAUNCH4(NN, MM, RU, RW, UN) do { if (RU && rxc) LAUNCH5(NN, MM, RU, RW, UN, RU); else LAUNCH5(NN, MM, RU, RW, UN, false); } while (0)
-// both forms, back to back: the one whose kind of key-point set is not resident leaves at once.  raw: only UNIFORM sets are
-// differenced inside the sweep; for per-DoF lists a lane's crossing is a divergent branch that every lane of the wave pays for
-// (17 loads, 8 stores on most steps), and the streaming kernel + the plain general sweep are faster (iterative-error lists with
-// a key-point on 99 % of the steps: 8.7 + 2.2 against 11.9 ms) -- k_fd_kp_difference is launched in between and looks at the
-// same device flag.  (KPILQR_FUSED_UNI=0, diagnostic: the general raw form for every set.)
-#define LAUNCH3(NN, MM, RU, RW) do { if (c->tune.fused_uni != 0) LAUNCH4(NN, MM, RU, RW, true); LAUNCH4(NN, MM, RU, RW, false); } while (0)
-#define LAUNCH2(NN, MM, RU)                                                                                             \
-    do {                                                                                                                \
-        if (raw && c->tune.fused_uni != 0) {                                                                            \
-            LAUNCH4(NN, MM, RU, true, true);                                                                            \
-            hipError_t e_ = launch_fd_kp_difference(c, true);     /* (per-DoF lists: columns and their slopes) */       \
-            if (e_ != hipSuccess) return e_;                                                                            \
-            LAUNCH4(NN, MM, RU, false, false);                                                                          \
-        } else if (raw) LAUNCH3(NN, MM, RU, true);                                                                      \
-        else LAUNCH3(NN, MM, RU, false);                                                                                \
-    } while (0)
-#define LAUNCH(NN, MM) do { if (c->ru_zero) LAUNCH2(NN, MM, true); else LAUNCH2(NN, MM, false); } while (0)
-#define KP_X(NN, MM) if (n == NN && m == MM) { LAUNCH(NN, MM); return hipGetLastError(); }
+#define KP_X(NN, MM) if (n == NN && m == MM) return p.ru0 ? launch_bf_sequence<NN, MM, true>(c, p, F, pd_stride) : launch_bf_sequence<NN, MM, false>(c, p, F, pd_stride);
     KP_T1_SHAPES(KP_X)
 #undef KP_X
-#undef LAUNCH
-#undef LAUNCH2
-#undef LAUNCH3
-#undef LAUNCH4
-#undef LAUNCH5
     return hipErrorInvalidValue;
 }
 #endif
 
 #if KP_PART(2)
-// form 5 of the backward sweep, the consumer / helper pair; launch_backward_fused has filled in kpilqr_last_launch's fields.
-// raw: the raw launch sequence of the pair (the helper differences the payload of uniform sets)
-hipError_t launch_backward_fused_waves(Ctx *c, int pd_stride, bool raw)
+// ---- the consumer / helper pair, backward.  guard: which kind of key-point set a launch serves (-1 any, 1 uniform, 0 per-DoF lists)
+template <int NN, int MM, bool RW, bool SL>
+static void launch_bph_kernel(Ctx *c, const FusedLaunch &p, const FusedArgs &F, int pd_stride, int guard)
+{
+    auto kernel = k_backward_fusedph<NN, MM, RW, true, true, SL>;
+    if (!p.rxc) kernel = p.ru0 ? k_backward_fusedph<NN, MM, RW, true, false, SL> : k_backward_fusedph<NN, MM, RW, false, false, SL>;
+    hipLaunchKernelGGL(kernel, dim3(c->d.batch), dim3(128), 0, c->stream, c->L, F, c->d.T, c->tune.role_shift, c->lambda, pd_stride, c->K,
+                       c->k, c->delta_J, c->status, c->kp_uniform, guard);
+}
+// Per-DoF lists: the helper walks the slope store, uniform sets the column store with its dividing tracker: two launches, the
+// device flag decides.  raw: the helper differences the payload of uniform sets; k_fd_kp_difference and the plain sweep behind it
+// serve per-DoF lists.
+template <int NN, int MM>
+static hipError_t launch_bph_sequence(Ctx *c, const FusedLaunch &p, const FusedArgs &F, int pd_stride)
+{
+    if (p.raw) {
+        launch_bph_kernel<NN, MM, true, false>(c, p, F, pd_stride, 1);
+        const hipError_t e = launch_fd_kp_difference(c, true);
+        if (e != hipSuccess) return e;
+        if (p.slopes) launch_bph_kernel<NN, MM, false, true>(c, p, F, pd_stride, 0);
+        else launch_bph_kernel<NN, MM, false, false>(c, p, F, pd_stride, 0);
+    } else if (p.slopes) {
+        launch_bph_kernel<NN, MM, false, false>(c, p, F, pd_stride, 1);
+        launch_bph_kernel<NN, MM, false, true>(c, p, F, pd_stride, 0);
+    } else launch_bph_kernel<NN, MM, false, false>(c, p, F, pd_stride, -1);
+    return hipGetLastError();
+}
+
+hipError_t launch_backward_fused_pair(Ctx *c, const FusedLaunch &p, int pd_stride)
 {
     const int n = c->n, m = c->d.m;
-    dim3 grid(c->d.batch);
     const FusedArgs F = fused_args(c);
-    const int role_shift = c->tune.role_shift;
-    dim3 block2(128);
-    const bool hru0 = c->ru_zero, hrxc = c->ru_zero && c->rx_const_on;
-    c->last_bwd_ru0 = hru0; c->last_bwd_rxc = hrxc;
-    // per-DoF lists: the helper walks the slope store (made by k_fd_kp_difference / k_kp_slopes for such sets only), uniform
-    // sets the column store with its dividing tracker: two launches, the device flag decides
-    const bool hslp = c->kps != nullptr;
-    c->last_bwd_slopes = hslp;
-#define LAUNCHPH2(NN, MM, RW, RU, RX, SL, GUARD) hipLaunchKernelGGL((k_backward_fusedph<NN, MM, RW, RU, RX, SL>), grid, block2, 0, c->stream, c->L, F, c->d.T, role_shift, c->lambda, pd_stride, c->K, c->k, c->delta_J, c->status, c->kp_uniform, GUARD)
-#define LAUNCHPH(NN, MM, RW, SL, GUARD) do { if (hrxc) LAUNCHPH2(NN, MM, RW, true, true, SL, GUARD); else if (hru0) LAUNCHPH2(NN, MM, RW, true, false, SL, GUARD); else LAUNCHPH2(NN, MM, RW, false, false, SL, GUARD); } while (0)
-#define KP_X(NN, MM)                                                                                   \
-    if (n == NN && m == MM) {                                                                          \
-        if (raw) {                                                                                     \
-            LAUNCHPH(NN, MM, true, false, 1);                                                          \
-            hipError_t e_ = launch_fd_kp_difference(c, true);                                          \
-            if (e_ != hipSuccess) return e_;                                                           \
-            if (hslp) LAUNCHPH(NN, MM, false, true, 0); else LAUNCHPH(NN, MM, false, false, 0);        \
-        } else if (hslp) { LAUNCHPH(NN, MM, false, false, 1); LAUNCHPH(NN, MM, false, true, 0); }      \
-        else LAUNCHPH(NN, MM, false, false, -1);                                                       \
-        return hipGetLastError();                                                                      \
-    }
+#define KP_X(NN, MM) if (n == NN && m == MM) return launch_bph_sequence<NN, MM>(c, p, F, pd_stride);
     KP_T1_SHAPES(KP_X)
 #undef KP_X
-#undef LAUNCHPH
-#undef LAUNCHPH2
     return hipErrorInvalidValue;
 }
 #endif
@@ -2396,92 +2407,73 @@ hipError_t launch_backward_fused_stats(Ctx *c, int pd_stride, int *hist_dev)
 
 #endif
 #if KP_PART(3)
-hipError_t launch_forward_fused(Ctx *c, double *U_alpha_dev)
+// ---- forward.  Every kernel takes the same arguments (the triple one more: only_ragged)
+template <class Kernel, class... More>
+static void launch_ff_kernel(Kernel kernel, int block, Ctx *c, const FusedArgs &F, double *U_alpha_dev, More... more)
 {
-    const int n = c->n, m = c->d.m;
-    dim3 grid(c->d.batch), block(64);
-    const bool excl = c->d.batch <= c->n_simd;
+    hipLaunchKernelGGL(kernel, dim3(c->d.batch), dim3(block), 0, c->stream, c->L, F, c->d.T, c->d.n_alpha, c->K, c->k, c->u_nom, c->ctrl_lim,
+                       c->alphas, c->cost_pred, U_alpha_dev, c->kp_uniform, more...);
+}
+// the state / cost pair (uniform sets) and the state / cost / staging triple: the cost wave has the residual instantiations
+template <int NCZ, int NCU>
+static void launch_ff_pair(Ctx *c, const FusedLaunch &p, const FusedArgs &F, double *U_alpha_dev)
+{
+    auto kernel = k_forward_fused_scu<NCZ, NCU, true, true>;
+    if (!p.rxc) kernel = p.ru0 ? k_forward_fused_scu<NCZ, NCU, true, false> : k_forward_fused_scu<NCZ, NCU>;
+    launch_ff_kernel(kernel, 128, c, F, U_alpha_dev);
+}
+template <int NCZ, int NCU>
+static void launch_ff_triple(Ctx *c, const FusedLaunch &p, const FusedArgs &F, double *U_alpha_dev, int only_ragged)
+{
+    auto kernel = k_forward_fused_sc3<NCZ, NCU, true, true>;
+    if (!p.rxc) kernel = p.ru0 ? k_forward_fused_sc3<NCZ, NCU, true, false> : k_forward_fused_sc3<NCZ, NCU>;
+    launch_ff_kernel(kernel, 192, c, F, U_alpha_dev, only_ragged);
+}
+// One wave per trajectory: the uniform and the general form back to back, the one whose kind of key-point set is not resident
+// leaves at once (k_forward_fused); behind the pair the general form alone.  RX = RU as in launch_bf_form.  RU (r_u never
+// uploaded): the instantiation without the r_u loads and the Ju product.  Round-2 history: it measured SLOWER at first (3.76 vs
+// 3.22 ms at B = 1024: the compiler's wait placement left the latency shadow it sat in), and faster once the uniform-key-point
+// form and the per-trajectory descriptors had changed the loop (2.81 vs 3.03 ms).
+template <int NCZ, int NCU, bool RU, bool UNI>
+static void launch_ff_form(Ctx *c, const FusedLaunch &p, const FusedArgs &F, double *U_alpha_dev)
+{
+    if (RU && p.rxc) launch_ff_kernel(p.excl ? k_forward_fused_excl<NCZ, NCU, RU, UNI, RU> : k_forward_fused<NCZ, NCU, RU, UNI, RU>, 64, c, F, U_alpha_dev);
+    else launch_ff_kernel(p.excl ? k_forward_fused_excl<NCZ, NCU, RU, UNI, false> : k_forward_fused<NCZ, NCU, RU, UNI, false>, 64, c, F, U_alpha_dev);
+}
+template <int NCZ, int NCU, bool RU>
+static void launch_ff_w1(Ctx *c, const FusedLaunch &p, const FusedArgs &F, double *U_alpha_dev, bool only_ragged)
+{
+    if (!only_ragged) launch_ff_form<NCZ, NCU, RU, true>(c, p, F, U_alpha_dev);
+    launch_ff_form<NCZ, NCU, RU, false>(c, p, F, U_alpha_dev);
+}
+
+// The launch sequence.  The pair serves uniform sets; what runs behind it (only_ragged) leaves at once on one, and is not launched
+// at all when the host placed the lists and saw them equal.
+hipError_t launch_forward_fused(Ctx *c, const FusedLaunch &p, double *U_alpha_dev)
+{
+    if (!kp_t1_shape(c->n, c->d.m)) return hipErrorInvalidValue;
+    const int ncz = (c->n + 2 + 3) / 4, ncu = (c->d.m + 3) / 4;       // tile chunks of [dx; alpha; 1] and of the controls name the shape
     const FusedArgs F = fused_args(c);
-    // While a trajectory can have three SIMDs of a CU (4 x batch <= #SIMDs) the state / cost / staging triple runs it: 1.58 ms per
-    // sweep at B = 1, 1.74 ... 1.76 at B = 128 ... 256 (four tile sets per wave, a time loop without conditions) against 1.80 for
-    // one wave per trajectory with its tile requests four steps ahead, which takes over beyond.
-    // KPILQR_FUSED_FWD_WAVES = 1 | 3 | 4 forces a form.
-    int form = forward_fused_form(c);
-    const bool src_ru0 = c->ru_zero, src_rxc = c->ru_zero && c->rx_const_on;      // the cost wave of the state / cost groups
-    const int ncz = (n + 2 + 3) / 4, ncu = (m + 3) / 4;       // tile chunks of [dx; alpha; 1] and of the controls
-    int only_ragged = 0;                                      // the general forms behind the uniform pair leave on a uniform set
-    c->last_fwd_form_ragged = 0;
-    if (form == 4) {
-        dim3 block2(128);
-        // per-DoF lists: the triple, or one wave per trajectory
-        const int behind = 4 * c->d.batch <= c->n_simd ? 3 : 1;
-#define LAUNCHSCU(NCZ, NCU)                                                                                             \
-        if (ncz == NCZ && ncu == NCU) {                                                                                 \
-            if (src_rxc) hipLaunchKernelGGL((k_forward_fused_scu<NCZ, NCU, true, true>), grid, block2, 0, c->stream, c->L, F, c->d.T, c->d.n_alpha, \
-                               c->K, c->k, c->u_nom, c->ctrl_lim, c->alphas, c->cost_pred, U_alpha_dev, c->kp_uniform);  \
-            else if (src_ru0) hipLaunchKernelGGL((k_forward_fused_scu<NCZ, NCU, true, false>), grid, block2, 0, c->stream, c->L, F, c->d.T, c->d.n_alpha, \
-                               c->K, c->k, c->u_nom, c->ctrl_lim, c->alphas, c->cost_pred, U_alpha_dev, c->kp_uniform);  \
-            else hipLaunchKernelGGL((k_forward_fused_scu<NCZ, NCU>), grid, block2, 0, c->stream, c->L, F, c->d.T, c->d.n_alpha, \
-                               c->K, c->k, c->u_nom, c->ctrl_lim, c->alphas, c->cost_pred, U_alpha_dev, c->kp_uniform);  \
-        }
-        LAUNCHSCU(4, 2) LAUNCHSCU(2, 1) LAUNCHSCU(4, 1) LAUNCHSCU(3, 1)
-#undef LAUNCHSCU
-        hipError_t e_ = hipGetLastError();
-        if (e_ != hipSuccess) return e_;
-        c->last_fwd_form = 3;                                 // kpilqr_last_launch: "pair" on a uniform set ...
-        c->last_fwd_form_ragged = behind == 3 ? 4 : 1;        // ... the triple / w1 otherwise
-        c->last_fwd_ru0 = c->ru_zero; c->last_fwd_rxc = src_rxc;
-        c->last_fwd_slopes = behind == 1 && c->kps != nullptr;
-        if (c->kp_known_uniform) return hipSuccess;           // (the host placed the lists and saw them equal: nothing else can run)
-        form = behind; only_ragged = 1;
-    } else {
-        c->last_fwd_form = form == 3 ? 4 : 1;      // kpilqr_last_launch: triple / w1
-        c->last_fwd_ru0 = c->ru_zero; c->last_fwd_rxc = src_rxc;
-        c->last_fwd_slopes = form == 1 && c->kps != nullptr;
-    }
-    const bool rxc = form == 1 && c->ru_zero && c->rx_const_on;
-    if (form == 3) {
-        dim3 block3(192);
-#define LAUNCHSC3(NCZ, NCU)                                                                                             \
-        if (ncz == NCZ && ncu == NCU) {                                                                                 \
-            if (src_rxc) hipLaunchKernelGGL((k_forward_fused_sc3<NCZ, NCU, true, true>), grid, block3, 0, c->stream, c->L, F, c->d.T, c->d.n_alpha, \
-                               c->K, c->k, c->u_nom, c->ctrl_lim, c->alphas, c->cost_pred, U_alpha_dev, c->kp_uniform, only_ragged); \
-            else if (src_ru0) hipLaunchKernelGGL((k_forward_fused_sc3<NCZ, NCU, true, false>), grid, block3, 0, c->stream, c->L, F, c->d.T, c->d.n_alpha, \
-                               c->K, c->k, c->u_nom, c->ctrl_lim, c->alphas, c->cost_pred, U_alpha_dev, c->kp_uniform, only_ragged); \
-            else hipLaunchKernelGGL((k_forward_fused_sc3<NCZ, NCU>), grid, block3, 0, c->stream, c->L, F, c->d.T, c->d.n_alpha, \
-                               c->K, c->k, c->u_nom, c->ctrl_lim, c->alphas, c->cost_pred, U_alpha_dev, c->kp_uniform, only_ragged); \
-            return hipGetLastError();                                                                                   \
-        }
-        LAUNCHSC3(4, 2) LAUNCHSC3(2, 1) LAUNCHSC3(4, 1) LAUNCHSC3(3, 1)
-#undef LAUNCHSC3
-        return hipErrorInvalidValue;
-    }
-#define LAUNCH4(NCZ, NCU, RU, UNI, RX)                                                                            \
-    do {                                                                                                          \
-        if (excl)                                                                                                 \
-            hipLaunchKernelGGL((k_forward_fused_excl<NCZ, NCU, RU, UNI, RX>), grid, block, 0, c->stream, c->L, F, c->d.T, \
-                               c->d.n_alpha, c->K, c->k, c->u_nom, c->ctrl_lim, c->alphas, c->cost_pred,  \
-                               U_alpha_dev, c->kp_uniform);                                                       \
-        else                                                                                                      \
-            hipLaunchKernelGGL((k_forward_fused<NCZ, NCU, RU, UNI, RX>), grid, block, 0, c->stream, c->L, F, c->d.T,  \
-                               c->d.n_alpha, c->K, c->k, c->u_nom, c->ctrl_lim, c->alphas, c->cost_pred,  \
-                               U_alpha_dev, c->kp_uniform);                                                       \
-    } while (0)
-#define LAUNCH3(NCZ, NCU, RU, UNI) do { if (RU && rxc) LAUNCH4(NCZ, NCU, RU, UNI, RU); else LAUNCH4(NCZ, NCU, RU, UNI, false); } while (0)
-// both forms, back to back: the one whose kind of key-point set is not resident leaves at once (k_forward_fused)
-#define LAUNCH2(NCZ, NCU, RU) do { if (!only_ragged) LAUNCH3(NCZ, NCU, RU, true); LAUNCH3(NCZ, NCU, RU, false); } while (0)
-// r_u never uploaded (ru_zero): the instantiation without the r_u loads and the Ju product.  Round-2 history: it measured
-// SLOWER at first (3.76 vs 3.22 ms at B = 1024: the compiler's wait placement left the latency shadow it sat in), and
-// faster once the uniform-key-point form and the per-trajectory descriptors had changed the loop (2.81 vs 3.03 ms).
-#define LAUNCH(NCZ, NCU) do { if (c->ru_zero) LAUNCH2(NCZ, NCU, true); else LAUNCH2(NCZ, NCU, false); } while (0)
-#define KP_X(NCZ, NCU) if (ncz == NCZ && ncu == NCU) { LAUNCH(NCZ, NCU); return hipGetLastError(); }
-    KP_X(4, 2) KP_X(2, 1) KP_X(4, 1) KP_X(3, 1)
+    const bool only_ragged = p.waves == Waves::pair;
+#define KP_FWD_SHAPES(X) X(4, 2) X(2, 1) X(4, 1) X(3, 1)
+    if (only_ragged) {
+#define KP_X(NCZ, NCU) if (ncz == NCZ && ncu == NCU) launch_ff_pair<NCZ, NCU>(c, p, F, U_alpha_dev);
+        KP_FWD_SHAPES(KP_X)
 #undef KP_X
-#undef LAUNCH
-#undef LAUNCH2
-#undef LAUNCH3
-#undef LAUNCH4
-    return hipErrorInvalidValue;
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess || c->kp_known_uniform) return e;
+    }
+    if (p.waves_ragged == Waves::triple) {
+#define KP_X(NCZ, NCU) if (ncz == NCZ && ncu == NCU) launch_ff_triple<NCZ, NCU>(c, p, F, U_alpha_dev, only_ragged);
+        KP_FWD_SHAPES(KP_X)
+#undef KP_X
+    } else {
+#define KP_X(NCZ, NCU) if (ncz == NCZ && ncu == NCU) { if (p.ru0) launch_ff_w1<NCZ, NCU, true>(c, p, F, U_alpha_dev, only_ragged); else launch_ff_w1<NCZ, NCU, false>(c, p, F, U_alpha_dev, only_ragged); }
+        KP_FWD_SHAPES(KP_X)
+#undef KP_X
+    }
+#undef KP_FWD_SHAPES
+    return hipGetLastError();
 }
 #endif
 

@@ -283,8 +283,8 @@ static void payload_changed(kpilqr_ctx *c)
     c->rec_synced = false;
 }
 
-// Constant residual Jacobians (kpilqr_upload_residual_jacobians_const): the one-wave fused sweeps keep r_x in registers; every
-// other kernel family streams r_x per step from the context's buffer, which then receives the broadcast copy -- once, on demand.
+// Constant residual Jacobians (kpilqr_upload_residual_jacobians_const): a fused sweep whose plan says rxc keeps r_x in registers;
+// every other sweep streams r_x per step from the context's buffer, which then receives the broadcast copy -- once, on demand.
 static int ensure_rx_buffer(kpilqr_ctx *c)
 {
     if (!c->rx_const_on || c->rx_buf_valid) return KPILQR_OK;
@@ -292,13 +292,6 @@ static int ensure_rx_buffer(kpilqr_ctx *c)
     c->rx_buf_valid = true;
     return KPILQR_OK;
 }
-// whether the sweep about to be launched reads the r_x buffer (every form but the one-wave fused instantiations without r_u)
-static bool backward_reads_rx_buffer(const kpilqr_ctx *c)
-{
-    const int form = c->fused ? backward_fused_form(c) : 0;
-    return !((form == 1 || form == 5) && c->ru_zero);       // (the forms with a constant-Jacobian instantiation)
-}
-static bool forward_reads_rx_buffer(const kpilqr_ctx *c) { return !(c->fused && c->ru_zero); }      // (every fused forward form has its constant-Jacobian instantiation)
 
 // kernel families for c->d (names: kpilqr_backward_variant)
 static int select_variants(kpilqr_ctx *c)
@@ -314,7 +307,7 @@ static int select_variants(kpilqr_ctx *c)
                    : (!generic && forward_tiled_supported(c->n, dims->m, dims->n_alpha, c->tune.tiled_nt_min)) ? "mfma_f64_tiled"
                    : (!generic && forward_wide_supported(c->n, dims->m, dims->n_alpha, c->tune.tiled_nt_min)) ? "mfma_f64_wide" : "generic_lds";
     if ((dims->flags & KPILQR_FLAG_FUSED) && !generic && !force_tiled &&
-        fused_supported(c->n, dims->m, dims->nr, dims->dof, dims->T, c->L.stride, dims->n_alpha)) {
+        fused_supported(c->n, dims->m, dims->nr, dims->dof, dims->T, dims->n_alpha)) {
         c->fused = true;
         c->bwd_variant = c->fwd_variant = "mfma_f64_t1_fused";
     }
@@ -972,7 +965,6 @@ static int check_fused(kpilqr_ctx *c)
 
 static int run_backward(kpilqr_ctx *c, int pd_stride)
 {
-    if (c->rx_const_on && (c->fused || c->tiled_a6) && backward_reads_rx_buffer(c)) { const int rcx = ensure_rx_buffer(c); if (rcx) return rcx; }
     if (c->fused) {
         int rc = check_fused(c);
         if (rc) return rc;
@@ -980,26 +972,27 @@ static int run_backward(kpilqr_ctx *c, int pd_stride)
         if (rc) return rc;
         rc = ensure_kps(c);
         if (rc) return rc;
-        // Key-point ordered payload, one wave per trajectory or the consumer / helper pair: the sweep (its helper wave)
-        // differences the payload itself and leaves kpc
-        // behind for the forward sweep -- no differencing kernel.  (It may stop at a failed PD check, so it never marks
-        // kpc valid: another backward pass on the same payload differences again.)  Otherwise the payload is differenced
-        // into kpc first, once, and the sweeps read kpc.
-        const int bform = backward_fused_form(c);
-        if (!c->kpc_valid && c->fd_kind == 2 && (bform == 1 || bform == 5) && c->tune.fused_raw != 0) {
-            KP_HIP(c, launch_backward_fused(c, pd_stride, true));
+        // Key-point ordered payload: the sweep (one wave per trajectory, or the helper wave of the pair) differences the payload
+        // itself and leaves kpc behind for the forward sweep -- no differencing kernel.  (It may stop at a failed PD check, so it
+        // never marks kpc valid: another backward pass on the same payload differences again.)  Otherwise the payload is
+        // differenced into kpc first, once, and the sweeps read kpc.
+        const FusedLaunch plan = c->last_bwd = plan_backward_fused(c, !c->kpc_valid && c->fd_kind == 2 && c->tune.fused_raw != 0);
+        if (!plan.rxc) { rc = ensure_rx_buffer(c); if (rc) return rc; }       // (the sweep streams r_x: a constant one needs its broadcast copy)
+        if (plan.raw) {
+            KP_HIP(c, launch_backward_fused(c, plan, pd_stride));
             c->kpc_touched = true;
             // (KPILQR_FUSED_UNI=0, diagnostic: the GENERAL raw sweep has differenced every set inside the sweep -- dividing at its
             // crossings -- and left the columns; the forward sweep's general form walks the slope store, made from them here)
-            if (c->tune.fused_uni == 0 && bform == 1 && c->kps) KP_HIP(c, launch_kp_slopes(c, false));
+            if (c->kps && !plan.slopes) KP_HIP(c, launch_kp_slopes(c, false));
             return KPILQR_OK;
         }
         if (!c->kpc_valid) { rc = difference_to_kpc(c); if (rc) return rc; }
         if (c->kpc_valid) { rc = slopes_for_kpc(c); if (rc) return rc; }
-        KP_HIP(c, launch_backward_fused(c, pd_stride, false));
+        KP_HIP(c, launch_backward_fused(c, plan, pd_stride));
         return KPILQR_OK;
     }
-    c->last_bwd_form = 0;
+    c->last_bwd = FusedLaunch{};       // (no plan: not a fused launch, and the tiled a6 sweep streams r_x)
+    if (c->tiled_a6) { const int rc = ensure_rx_buffer(c); if (rc) return rc; }
     if (strcmp(c->bwd_variant, "mfma_f64_t1") == 0) KP_HIP(c, launch_backward_mfma(c, pd_stride));
     else if (strncmp(c->bwd_variant, "mfma_f64_tiled", 14) == 0) KP_HIP(c, launch_backward_tiled(c, pd_stride));
     else if (strcmp(c->bwd_variant, "mfma_f64_wide") == 0) KP_HIP(c, launch_backward_wide(c, pd_stride));
@@ -1112,21 +1105,23 @@ static int ensure_stage(kpilqr_ctx *c, size_t bytes)
 
 static int run_forward(kpilqr_ctx *c, double *U_dev)
 {
-    if (c->rx_const_on && (c->fused || c->tiled_a6) && forward_reads_rx_buffer(c)) { const int rcx = ensure_rx_buffer(c); if (rcx) return rcx; }
     if (c->fused) {
         int rc = check_fused(c);
         if (rc) return rc;
         rc = ensure_kpc(c);
         if (rc) return rc;
-        // kpc: differenced explicitly, or left behind by the raw backward sweep of this payload
-        if (!c->kpc_valid && !c->kpc_touched) { rc = difference_to_kpc(c); if (rc) return rc; }
         rc = ensure_kps(c);
         if (rc) return rc;
+        const FusedLaunch plan = c->last_fwd = plan_forward_fused(c);
+        if (!plan.rxc) { rc = ensure_rx_buffer(c); if (rc) return rc; }       // (as in run_backward)
+        // kpc: differenced explicitly, or left behind by the raw backward sweep of this payload
+        if (!c->kpc_valid && !c->kpc_touched) { rc = difference_to_kpc(c); if (rc) return rc; }
         if (c->kpc_valid) { rc = slopes_for_kpc(c); if (rc) return rc; }       // (behind a raw backward sweep: its launch sequence made them)
-        KP_HIP(c, launch_forward_fused(c, U_dev));
+        KP_HIP(c, launch_forward_fused(c, plan, U_dev));
         return KPILQR_OK;
     }
-    c->last_fwd_form = 0;
+    c->last_fwd = FusedLaunch{};
+    if (c->tiled_a6) { const int rc = ensure_rx_buffer(c); if (rc) return rc; }
     if (strcmp(c->fwd_variant, "mfma_f64_t1") == 0) KP_HIP(c, launch_forward_mfma(c, U_dev));
     else if (strncmp(c->fwd_variant, "mfma_f64_tiled", 14) == 0) KP_HIP(c, launch_forward_tiled(c, U_dev));
     else if (strcmp(c->fwd_variant, "mfma_f64_wide") == 0) KP_HIP(c, launch_forward_wide(c, U_dev));
@@ -1319,7 +1314,7 @@ int kpilqr_iterate_streamed(kpilqr_ctx *c, const kpilqr_stream_io *io, int pd_ch
     if (io->r_x) { c->rx_const_on = false; c->rx_buf_valid = true; }
     // constant residual Jacobians and a kernel family that streams r_x: the broadcast copy is made here, on the context (the
     // chunks' wave organisation is the whole batch's: make_view gives a chunk its share of the SIMDs)
-    if (c->rx_const_on && (!c->fused || backward_reads_rx_buffer(c) || forward_reads_rx_buffer(c))) { rc = ensure_rx_buffer(c); if (rc) return rc; }
+    if (!(c->fused && plan_backward_fused(c, false).rxc && plan_forward_fused(c).rxc)) { rc = ensure_rx_buffer(c); if (rc) return rc; }
     // order the chunk streams behind whatever the caller enqueued on the context's stream so far (key-points, weights ...)
     KP_HIP(c, hipEventRecord(c->pipe_in, c->stream));
     // from here on chunk streams hold work: every exit path, errors included, leaves the pipeline marked for joining, so a
@@ -1390,9 +1385,7 @@ int kpilqr_iterate_streamed(kpilqr_ctx *c, const kpilqr_stream_io *io, int pd_ch
         rc = run_forward(&v, nullptr);
         if (rc) { c->err = v.err; return rc; }
         vflags_valid = v.kpc_valid; vflags_touched = v.kpc_touched; vflags_slopes = v.kps_valid;
-        c->last_bwd_form = v.last_bwd_form; c->last_fwd_form = v.last_fwd_form; c->last_bwd_raw = v.last_bwd_raw; c->last_fwd_form_ragged = v.last_fwd_form_ragged;
-        c->last_bwd_ru0 = v.last_bwd_ru0; c->last_fwd_ru0 = v.last_fwd_ru0; c->last_bwd_rxc = v.last_bwd_rxc; c->last_fwd_rxc = v.last_fwd_rxc;
-        c->last_bwd_slopes = v.last_bwd_slopes; c->last_fwd_slopes = v.last_fwd_slopes;
+        c->last_bwd = v.last_bwd; c->last_fwd = v.last_fwd;
         // ---- D2H of the chunk ------------------------------------------------------------------------------------
         // K, k by a copy kernel: it overlaps with the SDMA uploads of the next chunks (two SDMA directions do not)
         if (k_down) {
@@ -1525,9 +1518,9 @@ const char *kpilqr_last_launch(kpilqr_ctx *c, int which)
 {
     if (!c || which < 0 || which > 1) return "";
     std::string &out = c->launch_desc[which];
-    const int form = which == 0 ? c->last_bwd_form : c->last_fwd_form;
+    const FusedLaunch &p = which == 0 ? c->last_bwd : c->last_fwd;
     out = which == 0 ? c->bwd_variant : c->fwd_variant;
-    if (form == 0) {
+    if (p.waves == Waves::none) {
         if (c->fused) { out += ":none"; return out.c_str(); }
         // the two-tile forward sweep on materialised tiles: one wave per row tile, or state / cost wave groups (small batches)
         if (which == 1 && strcmp(c->fwd_variant, "mfma_f64_tiled") == 0 && forward_tiled_sc_selected(c)) out += ":state_cost_waves";
@@ -1537,16 +1530,15 @@ const char *kpilqr_last_launch(kpilqr_ctx *c, int which)
     if (hipSetDevice(c->d.device) != hipSuccess || (c->pipe_dirty && join_pipeline(c) != KPILQR_OK) ||
         hipMemcpyAsync(&uni, c->kp_uniform, sizeof(int), hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
         hipStreamSynchronize(c->stream) != hipSuccess) { out += ":?"; return out.c_str(); }
-    static const char *const wname[6] = {"", "w1", "", "pair", "triple", "pairh"};      // by form number (2 is not used)
-    const int ran = (which == 1 && !uni && c->last_fwd_form_ragged) ? c->last_fwd_form_ragged : form;
-    out += ":"; out += wname[ran < 6 ? ran : 0];
+    static const char *const wname[] = {"", "w1", "pair", "triple", "pairh"};      // by Waves
+    out += ":"; out += wname[(int)(uni ? p.waves : p.waves_ragged)];
     // (the raw launch sequence differences inside the sweep for uniform sets only: per-DoF lists take k_fd_kp_difference and
     // the plain sweep, launched behind it -- unless KPILQR_FUSED_UNI=0 forces the general raw form, one wave per trajectory)
-    if (which == 0) out += (c->last_bwd_raw && (uni || (c->tune.fused_uni == 0 && form == 1))) ? ":raw" : ":kpc";
+    if (which == 0) out += (p.raw && (uni || (c->tune.fused_uni == 0 && p.waves == Waves::w1))) ? ":raw" : ":kpc";
     out += uni ? ":uni" : ":ragged";
-    if (which == 0 ? c->last_bwd_ru0 : c->last_fwd_ru0) out += ":ru0";
-    if (which == 0 ? c->last_bwd_rxc : c->last_fwd_rxc) out += ":rxc";
-    if (!uni && (which == 0 ? c->last_bwd_slopes : c->last_fwd_slopes)) out += ":slopes";
+    if (p.ru0) out += ":ru0";
+    if (p.rxc) out += ":rxc";
+    if (!uni && p.slopes) out += ":slopes";
     return out.c_str();
 }
 

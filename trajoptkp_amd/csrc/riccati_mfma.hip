@@ -377,24 +377,22 @@ bool backward_mfma_supported(int n, int m)
     return kp_t1_shape(n, m);
 }
 
+// excl: every wave has a SIMD to itself
+template <int NN, int MM>
+static hipError_t launch_bm(Ctx *c, int pd_stride)
+{
+    const auto kernel = c->d.batch <= c->n_simd ? k_backward_mfma_excl<NN, MM> : k_backward_mfma<NN, MM>;
+    hipLaunchKernelGGL(kernel, dim3(c->d.batch), dim3(64), 0, c->stream, c->L, c->d.T, c->rec, c->lambda, pd_stride, c->K, c->k,
+                       c->delta_J, c->status);
+    return hipGetLastError();
+}
+
 hipError_t launch_backward_mfma(Ctx *c, int pd_stride)
 {
     const int n = c->n, m = c->d.m;
-    dim3 grid(c->d.batch), block(64);
-    const bool excl = c->d.batch <= c->n_simd;
-#define LAUNCH(NN, MM)                                                                                    \
-    do {                                                                                                  \
-        if (excl)                                                                                         \
-            hipLaunchKernelGGL((k_backward_mfma_excl<NN, MM>), grid, block, 0, c->stream, c->L, c->d.T,   \
-                               c->rec, c->lambda, pd_stride, c->K, c->k, c->delta_J, c->status);          \
-        else                                                                                              \
-            hipLaunchKernelGGL((k_backward_mfma<NN, MM>), grid, block, 0, c->stream, c->L, c->d.T,        \
-                               c->rec, c->lambda, pd_stride, c->K, c->k, c->delta_J, c->status);          \
-    } while (0)
-#define KP_X(NN, MM) if (n == NN && m == MM) { LAUNCH(NN, MM); return hipGetLastError(); }
+#define KP_X(NN, MM) if (n == NN && m == MM) return launch_bm<NN, MM>(c, pd_stride);
     KP_T1_SHAPES(KP_X)
 #undef KP_X
-#undef LAUNCH
     return hipErrorInvalidValue;
 }
 
