@@ -41,6 +41,9 @@
  *   KPILQR_FUSED_RAW        0: a key-point ordered payload is differenced by k_fd_kp_difference in front of the backward
  *                           sweep instead of inside it (default: inside, for uniform key-point sets).
  *   KPILQR_FUSED_UNI        0: the general (per-DoF list) forms of the one-wave sweeps also for uniform key-point sets.
+ *   KPILQR_FD_INTERP        0: a context with step records differences and interpolates a key-point ordered or column payload
+ *                           in the separate passes (k_fd_kp_difference, k_kpc_to_records, k_interpolate) instead of in one
+ *                           (k_fd_kp_interpolate); same bits either way.  kpilqr_last_launch(ctx, 2) says which ran.
  *   KPILQR_ROLE_SHIFT       wave pairs: block-index bit from which the two roles swap wave slots (default 9; 0 = every
  *                           other block).  Placement probe; no effect on results.
  *   KPILQR_TILED_UW         tiled backward sweep (n + 2 > 16): 1 u-wave form | 0 column-wave form (default by tile count).
@@ -274,6 +277,18 @@ int  kpilqr_iterate_streamed(kpilqr_ctx *ctx, const kpilqr_stream_io *io, int pd
 int  kpilqr_fd_difference(kpilqr_ctx *ctx);
 /* KeypointGenerator::InterpolateDerivatives (src/KeyPointGenerator/KeyPointGenerator.cpp:840-954). */
 int  kpilqr_interpolate(kpilqr_ctx *ctx);
+/* kpilqr_fd_difference followed by kpilqr_interpolate: the resident FD payload -> A, B of every step, i.e. the differencing tail
+ * of Differentiator::DynamicsDerivatives (src/Differentiator/Differentiator.cpp:166-222,441-457) and
+ * KeypointGenerator::InterpolateDerivatives (src/KeyPointGenerator/KeyPointGenerator.cpp:840-954) in one call.  With a key-point
+ * ordered payload (kpilqr_upload_fd_kp) or a column payload (kpilqr_upload_kp_columns) it is ONE pass over the step records that
+ * fetches and differences a segment's endpoints from the payload (k_fd_kp_interpolate): the key-point column store is neither
+ * written nor read, and every record is written once.  With job lists (kpilqr_upload_fd / _slab) it runs the two calls.  The
+ * records hold bit for bit what the two calls leave there, including what they leave alone (steps outside a DoF list's first /
+ * last key-point, B columns of actuators beyond the DoFs, the cost blocks).  On a KPILQR_FLAG_FUSED context the step records are
+ * allocated on demand, as for kpilqr_interpolate.  KPILQR_ERR_STATE before kpilqr_set_keypoints / kpilqr_generate_keypoints.
+ * Asynchronous on the context's stream.  kpilqr_iterate and kpilqr_iterate_streamed linearise the same way on a context with
+ * step records; kpilqr_last_launch(ctx, 2) reports the form.  KPILQR_VERSION is unchanged: detect the entry point by its symbol. */
+int  kpilqr_fd_interpolate(kpilqr_ctx *ctx);
 
 /* Optimiser::FilterDynamicsMatrices (src/Optimiser/Optimiser.cpp:340-406, run from GenerateDerivatives :105-107 when
  * the task sets `filtering`): rows dof..2dof-1 of every A[t], filtered along time in place, after
@@ -400,6 +415,12 @@ const char *kpilqr_forward_variant(kpilqr_ctx *ctx);
  *   rxc      constant residual Jacobians kept in registers (kpilqr_upload_residual_jacobians_const)
  *   slopes   per-DoF lists walked on precomputed segment slopes (a crossing is loads only)
  * The `lists` token is decided on the device; this call reads the flag back and therefore WAITS for the context's stream.
+ * which = 2: the linearisation stage (differencing + interpolation of A, B) of the last kpilqr_fd_interpolate, kpilqr_iterate or
+ * kpilqr_iterate_streamed; does not wait.  "" before any of them (and in a library without kpilqr_fd_interpolate), else
+ *     "fd_kp_interpolate"          key-point ordered payload, one pass
+ *     "kp_columns_interpolate"     column payload, one pass
+ *     "fd_difference+interpolate"  the separate passes (job lists, or KPILQR_FD_INTERP=0)
+ *     "in_sweep"                   KPILQR_FLAG_FUSED context: the sweeps difference and interpolate themselves
  * For logs and tests (a test can assert which kernel form it exercised).  version >= 400. */
 const char *kpilqr_last_launch(kpilqr_ctx *ctx, int which);
 

@@ -28,7 +28,11 @@ SYMBOLS = [
     "kpilqr_fd_slab_layout", "kpilqr_upload_fd_slab", "kpilqr_iterate_streamed", "kpilqr_resize",
     "kpilqr_keypoint_error_test", "kpilqr_fd_kp_layout", "kpilqr_upload_fd_kp", "kpilqr_backward_stats",
     "kpilqr_upload_kp_columns", "kpilqr_upload_residual_jacobians_const", "kpilqr_last_launch",
+    "kpilqr_fd_interpolate",
 ]
+# entry points added without a version bump (include/kpilqr.h: "detect the entry point by its symbol"): bound only when the library
+# has them -- KPILQR_LIB may name an older build of the same major version
+OPTIONAL_SYMBOLS = {"kpilqr_fd_interpolate"}
 
 
 class Dims(C.Structure):
@@ -137,7 +141,11 @@ def load():
     L.kpilqr_upload_kp_columns.argtypes = [vp, vp, C.c_int]
     L.kpilqr_upload_residual_jacobians_const.argtypes = [vp, vp, vp]
     L.kpilqr_last_launch.argtypes = [vp, C.c_int]; L.kpilqr_last_launch.restype = C.c_char_p
+    if hasattr(L, "kpilqr_fd_interpolate"):
+        L.kpilqr_fd_interpolate.argtypes = [vp]
     for s in SYMBOLS:
+        if s in OPTIONAL_SYMBOLS and not hasattr(L, s):
+            continue
         getattr(L, s)          # raises AttributeError if the .so lacks a declared symbol
     # the structs above (FdkpLayout, StreamIO ...) are those of ABI major version ABI_MAJOR: a library of another major version
     # would write past them or read them wrongly (round-4 advisor: kpilqr_fdkp_layout grew a field between 3.x and 4.0)

@@ -81,6 +81,11 @@ struct Ctx {
     double *traj_cost = nullptr;  // [batch]
     int *status = nullptr;        // [batch]
     int2 *segmap = nullptr;       // [batch][dof][T]: (start,end) key-points around t, or (-1,-1)
+    // [batch][dof][T]: CSR entry of the key-point at or before t (the one-pass linearisation fetches a segment's endpoints by
+    // entry), or -1 outside the list.  Built with segmap on a context that has records; on demand on a fused one (segent_valid)
+    int *segent = nullptr;
+    size_t segent_cap = 0;        // bytes
+    bool segent_valid = false;
     int *kp_offsets = nullptr;    // [batch*dof+1]
     int *kp_times = nullptr;      // [kp_total]
     size_t kp_cap = 0;            // capacity of kp_times (ints)
@@ -182,6 +187,7 @@ struct Ctx {
     // what the last backward / forward launch of this context actually was (kpilqr_last_launch); Waves::none: not a fused launch, or none yet
     FusedLaunch last_bwd, last_fwd;
     std::string launch_desc[2];
+    const char *last_linearise = "";   // kpilqr_last_launch(ctx, 2): how the last linearisation (a2 + a4) ran
 
     // Diagnostic switches, read from the environment ONCE by kpilqr_create; the launchers only
     // look here.  0 = let the library choose.
@@ -195,6 +201,7 @@ struct Ctx {
         int tiled_fsc = -1;        // KPILQR_TILED_FSC: -1 auto, 0 | 1: the state / cost wave groups of the two-tile forward sweep
         int fused_uni = -1;        // KPILQR_FUSED_UNI: 0 never take the uniform-key-point form of the one-wave backward sweep (diagnostic)
         int fused_raw = -1;        // KPILQR_FUSED_RAW: 0 never difference inside the backward sweep (diagnostic), else auto
+        int fd_interp = -1;        // KPILQR_FD_INTERP: 0 = never difference and interpolate in one pass (the three-pass sequence runs), else auto
         int pipe_copy = -1;        // KPILQR_PIPE_COPY: chunk pipeline copies by kernel: bit 0 uploads, bit 1 downloads (-1 auto)
     } tune;
 };
@@ -220,7 +227,7 @@ hipError_t launch_kp_slopes(Ctx *c, bool only_if_ragged = true);   // key-point 
 hipError_t launch_build_entry_tables(Ctx *c);            // kp_entry, kp_entry_list from the CSR lists
 hipError_t launch_copy_out(hipStream_t s, double *dst_host, const double *src_dev, size_t count);   // D2H by a kernel
 hipError_t launch_copy_in(hipStream_t s, void *dst_dev, const void *src_host, size_t bytes);        // H2D by a kernel
-hipError_t launch_build_segmap(Ctx *c);
+hipError_t launch_build_segmap(Ctx *c, bool segent_only = false);   // segmap (and segent when allocated); segent_only: segent alone
 // comm.cpp (RCCL opened lazily) and the pack kernel of elementwise.hip
 const char *comm_unique_id(char *id128);
 const char *comm_init(Ctx *c, int nranks, int rank, const char *id128);
@@ -232,6 +239,8 @@ hipError_t launch_generate_keypoints(Ctx *c, int method, int min_N, int max_N, d
                                      const double *X_dev, unsigned long long *mask_dev, int *count_dev);
 hipError_t launch_kp_error_test(Ctx *c, int n_iv, const int *iv_dev, int min_N, double threshold, unsigned char *good_dev);
 hipError_t launch_interpolate(Ctx *c);
+// linearise.hip: key-point ordered payload (fd_kind 2) or column payload (3) -> every step record's [A|B], a2 + a4 in one pass
+hipError_t launch_fd_kp_interpolate(Ctx *c);
 hipError_t launch_filter_dynamics(Ctx *c, int method, const double *coefs_dev, int ncoef);
 hipError_t launch_dof_importance(Ctx *c, int sampling, double *sums_dev);
 hipError_t launch_cost_derivs(Ctx *c);

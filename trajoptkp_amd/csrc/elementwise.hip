@@ -356,9 +356,11 @@ hipError_t launch_build_entry_tables(Ctx *c)
 // Key-point CSR (per trajectory, per DoF: sorted times) -> dense (start,end) map per (b, dof, t):
 // the pair of consecutive key-points strictly around t, or (-1,-1) when t is itself a key-point
 // of that DoF or lies outside the DoF's first/last key-point (the reference leaves those alone).
+// segent (optional, linearise.hip): the CSR ENTRY p of the key-point at or before t -- the segment's endpoints are entries p and
+// p + 1, a key-point step is entry p itself -- or -1 outside the DoF's first/last key-point.  segmap: null when only segent is wanted.
 __global__ void __launch_bounds__(256)
 k_build_segmap(int batch, int dof, int T, const int *__restrict__ offs, const int *__restrict__ times,
-               int2 *__restrict__ segmap)
+               int2 *__restrict__ segmap, int *__restrict__ segent)
 {
     const long long total = (long long)batch * dof * T;
     for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x; idx < total;
@@ -374,11 +376,16 @@ k_build_segmap(int batch, int dof, int T, const int *__restrict__ offs, const in
         }
         const int p = lo - 1;
         int2 r = make_int2(-1, -1);
+        int ent = -1;
         if (p >= lo0 && p + 1 < hi0) {
             const int s = times[p], e = times[p + 1];
             if (s != t) r = make_int2(s, e);
+            ent = p;
+        } else if (p >= lo0 && times[p] == t) {
+            ent = p;                                                 // the list's last key-point
         }
-        segmap[idx] = r;
+        if (segmap) segmap[idx] = r;
+        if (segent) segent[idx] = ent;
     }
 }
 
@@ -398,9 +405,9 @@ k_kp_uniform(int batch, int dof, const int *__restrict__ offs, const int *__rest
     if (!same) atomicAnd(flag, 0);
 }
 
-hipError_t launch_build_segmap(Ctx *c)
+hipError_t launch_build_segmap(Ctx *c, bool segent_only)
 {
-    {
+    if (!segent_only) {
         // (KPILQR_FUSED_UNI=0, diagnostic: every set counts as per-DoF lists, the general forms of the sweeps run)
         const bool never = c->tune.fused_uni == 0;
         hipError_t e = hipMemsetAsync(c->kp_uniform, never ? 0 : 1, sizeof(int), c->stream);        // any non-zero value: uniform until shown otherwise
@@ -411,7 +418,7 @@ hipError_t launch_build_segmap(Ctx *c)
     int blocks = (int)((total + 255) / 256);
     if (blocks > 256 * 32) blocks = 256 * 32;
     hipLaunchKernelGGL(k_build_segmap, dim3(blocks), dim3(256), 0, c->stream, c->d.batch, c->d.dof,
-                       c->d.T, c->kp_offsets, c->kp_times, c->segmap);
+                       c->d.T, c->kp_offsets, c->kp_times, segent_only ? (int2 *)nullptr : c->segmap, c->segent);
     return hipGetLastError();
 }
 

@@ -88,6 +88,7 @@ Ctx::Tuning read_tuning_from_env()
     t.pipe_copy = env_int("KPILQR_PIPE_COPY", -1);
     t.fused_raw = env_int("KPILQR_FUSED_RAW", -1);
     t.fused_uni = env_int("KPILQR_FUSED_UNI", -1);
+    t.fd_interp = env_int("KPILQR_FD_INTERP", -1);
     return t;
 }
 }  // namespace kpilqr
@@ -133,6 +134,17 @@ static int size_buffers(kpilqr_ctx *c)
         }
         // records start zeroed so that padding / never-written columns are defined
         if (w.zero && w.bytes) KP_HIP(c, hipMemsetAsync(*w.p, 0, w.bytes, c->stream));
+    }
+    // the entry map of the one-pass linearisation, beside segmap: with the records (a fused context builds it on demand, ensure_segent)
+    {
+        const size_t need = B * dims->dof * T * sizeof(int);
+        if (c->segent && need > c->segent_cap) { KP_HIP(c, hipFree(c->segent)); c->segent = nullptr; c->segent_cap = 0; }
+        if (!c->fused && !c->segent) {
+            hipError_t e = hipMalloc((void **)&c->segent, need ? need : 8);
+            if (e != hipSuccess) { c->err = std::string("hipMalloc failed: ") + hipGetErrorString(e); return KPILQR_ERR_ALLOC; }
+            c->segent_cap = need;
+        }
+        c->segent_valid = false;
     }
     c->have_rec = !c->fused;
     c->rec_fd_base = c->rec;
@@ -254,10 +266,48 @@ static int records_from_payload(kpilqr_ctx *c)
     return KPILQR_OK;
 }
 
+// segent for the current lists: built with segmap where the context has it allocated, else (a fused context) here
+static int ensure_segent(kpilqr_ctx *c)
+{
+    if (c->segent_valid) return KPILQR_OK;
+    const int rc = grow_dev(c, (void **)&c->segent, &c->segent_cap, (size_t)c->d.batch * c->d.dof * c->d.T * sizeof(int), false);
+    if (rc < 0) return rc;
+    KP_HIP(c, launch_build_segmap(c, true));
+    c->segent_valid = true;
+    return KPILQR_OK;
+}
+
+// The linearisation stage (a2 + a4) of a context that has records: [A|B] of every step from the resident payload.  A key-point
+// ordered or column payload goes through k_fd_kp_interpolate (linearise.hip), one pass that leaves kpc alone -- kpc_valid /
+// kpc_touched / kps_valid keep saying what kpc holds, so a later call that needs the column store differences the payload again;
+// job lists, and everything under KPILQR_FD_INTERP=0, run the sequence difference -> kpc -> records -> k_interpolate.
+static bool linearise_one_pass(const kpilqr_ctx *c)
+{
+    if (c->tune.fd_interp == 0) return false;
+    if (c->fd_kind == 3) return c->kpc_valid;
+    return c->fd_kind == 2;
+}
+
+static int linearise(kpilqr_ctx *c)
+{
+    if (linearise_one_pass(c)) {
+        const int rc = ensure_segent(c);
+        if (rc) return rc;
+        KP_HIP(c, launch_fd_kp_interpolate(c));
+        c->last_linearise = c->fd_kind == 3 ? "kp_columns_interpolate" : "fd_kp_interpolate";
+        return KPILQR_OK;
+    }
+    const int rc = records_from_payload(c);
+    if (rc) return rc;
+    KP_HIP(c, launch_interpolate(c));
+    c->last_linearise = "fd_difference+interpolate";
+    return KPILQR_OK;
+}
+
 // A fused context has no step records until something asks for the materialised sequence (kpilqr_interpolate, get_AB /
 // set_AB, the cost-derivative hooks, the key-point error test, KPILQR_BUF_STEP_RECORDS): then they are allocated, zeroed
 // and given the key-point columns of the resident payload.
-static int ensure_records(kpilqr_ctx *c)
+static int ensure_record_storage(kpilqr_ctx *c)
 {
     if (!c->have_rec) {
         const size_t bytes = (size_t)c->d.batch * c->d.T * c->L.stride * 8;
@@ -268,6 +318,12 @@ static int ensure_records(kpilqr_ctx *c)
         c->have_rec = true;
         c->rec_synced = false;
     }
+    return KPILQR_OK;
+}
+
+static int ensure_records(kpilqr_ctx *c)
+{
+    { const int rc = ensure_record_storage(c); if (rc) return rc; }
     if (!c->rec_synced) {
         const int rc = records_from_payload(c);
         if (rc) return rc;
@@ -410,7 +466,7 @@ void kpilqr_destroy(kpilqr_ctx *c)
     void *ptrs[] = {c->rec, c->K, c->k, c->r, c->r_x, c->r_u, c->w_run, c->w_term, c->u_nom, c->ctrl_lim,
                     c->lambda, c->alphas, c->cost_pred, c->delta_J, c->traj_cost, c->status, c->segmap,
                     c->kp_offsets, c->kp_times, c->X_states, c->kp_thr, c->kp_mask, c->kp_count, c->ls8, c->fd_dev,
-                    c->stage, c->err_flag, c->kp_uniform, c->kpc, c->kp_entry, c->kp_entry_list, c->fdk_dev, c->rx_const, c->kps};
+                    c->stage, c->err_flag, c->kp_uniform, c->kpc, c->kp_entry, c->kp_entry_list, c->fdk_dev, c->rx_const, c->kps, c->segent};
     for (void *p : ptrs) if (p) (void)hipFree(p);
     if (c->err_flag_host) (void)hipHostFree(c->err_flag_host);
     if (c->kp_traj_first_host) free(c->kp_traj_first_host);
@@ -575,6 +631,7 @@ int kpilqr_set_keypoints(kpilqr_ctx *c, const int *kp_offsets, const int *kp_tim
     KP_HIP(c, hipMemcpyAsync(c->kp_offsets, kp_offsets, (nlists + 1) * sizeof(int), hipMemcpyHostToDevice, c->stream));
     KP_HIP(c, hipMemcpyAsync(c->kp_times, kp_times, (size_t)total * sizeof(int), hipMemcpyHostToDevice, c->stream));
     KP_HIP(c, launch_build_segmap(c));
+    c->segent_valid = c->segent != nullptr;
     // pageable host arrays: make the copies complete before returning control (pinned ones are read in place)
     if (!(is_pinned(kp_offsets) && is_pinned(kp_times))) KP_HIP(c, hipStreamSynchronize(c->stream));
     c->have_kp = true;
@@ -637,6 +694,7 @@ int kpilqr_generate_keypoints(kpilqr_ctx *c, const char *method, int min_N, int 
     }
     KP_HIP(c, launch_generate_keypoints(c, mth, min_N, max_N, dt, thresholds ? c->kp_thr : nullptr, c->X_states, c->kp_mask, c->kp_count));
     KP_HIP(c, launch_build_segmap(c));
+    c->segent_valid = c->segent != nullptr;
     c->have_kp = true;
     c->kp_known_uniform = mth == 0 && c->tune.fused_uni != 0;    // set_interval: one list for all DoFs; the other methods place per DoF
     c->kp_canonical = true;      // rows 0 and T-1 are always full and the lists are strictly increasing by construction
@@ -876,6 +934,26 @@ int kpilqr_interpolate(kpilqr_ctx *c)
     if (c->fused) { const int rc = ensure_records(c); if (rc) return rc; }
     KP_HIP(c, launch_interpolate(c));
     return KPILQR_OK;
+}
+
+// kpilqr_fd_difference + kpilqr_interpolate (Differentiator.cpp:166-222,441-457 + KeyPointGenerator.cpp:840-954)
+int kpilqr_fd_interpolate(kpilqr_ctx *c)
+{
+    if (!c) return KPILQR_ERR_ARG;
+    KP_ENTER(c);
+    if (!c->have_kp) return set_err(c, KPILQR_ERR_STATE, "kpilqr_fd_interpolate before kpilqr_set_keypoints");
+    if (c->fused) {
+        // the sweeps of a fused context read the column store: it is differenced as kpilqr_fd_difference does; the records appear on
+        // demand (allocated and zeroed) and are filled in one pass where the payload allows
+        int rc = difference_to_kpc(c);
+        if (rc) return rc;
+        rc = ensure_record_storage(c);
+        if (rc) return rc;
+        rc = linearise(c);
+        if (rc == KPILQR_OK) c->rec_synced = true;
+        return rc;
+    }
+    return linearise(c);
 }
 
 // Optimiser::FilterDynamicsMatrices (Optimiser.cpp:340-406) on the materialised A sequence
@@ -1158,10 +1236,10 @@ int kpilqr_iterate(kpilqr_ctx *c, const double *lambda, int pd_check_stride, con
     if (lambda) KP_HIP(c, hipMemcpyAsync(c->lambda, lambda, (size_t)c->d.batch * 8, hipMemcpyHostToDevice, c->stream));
     if (alphas) KP_HIP(c, hipMemcpyAsync(c->alphas, alphas, (size_t)c->d.n_alpha * 8, hipMemcpyHostToDevice, c->stream));
     if (!c->fused) {              // the fused sweeps difference (or read kpc), interpolate A, B and form l_* themselves
-        { const int rcp = records_from_payload(c); if (rcp) return rcp; }
-        KP_HIP(c, launch_interpolate(c));
+        { const int rcl = linearise(c); if (rcl) return rcl; }
         if (!c->tiled_a6) { const int rcx = ensure_rx_buffer(c); if (rcx) return rcx; KP_HIP(c, launch_cost_derivs(c)); }      // tiled + flag: l_* are formed inside the sweeps
     }
+    else c->last_linearise = "in_sweep";
     int rc = run_backward(c, pd_check_stride);
     if (rc) return rc;
     return run_forward(c, nullptr);
@@ -1193,6 +1271,7 @@ static void make_view(const kpilqr_ctx *c, int b0, int nb, hipStream_t s, kpilqr
     v->r += o * (T + 1) * nr; v->r_x += o * (T + 1) * nr * n; v->r_u += o * (T + 1) * nr * m;
     v->u_nom += o * T * m; v->lambda += o; v->cost_pred += o * na; v->delta_J += o; v->traj_cost += o; v->status += o;
     v->segmap += o * dof * T; v->kp_offsets += o * dof;
+    if (v->segent) v->segent += o * dof * T;
     if (c->kp_traj_first_host) { v->fdk_first = c->kp_traj_first_host[b0]; v->kp_view_entries = c->kp_traj_first_host[b0 + nb] - v->fdk_first; }
     long long share = (long long)c->n_simd * nb / c->d.batch;
     v->n_simd = share < 4 ? 4 : (int)share;
@@ -1295,7 +1374,9 @@ int kpilqr_iterate_streamed(kpilqr_ctx *c, const kpilqr_stream_io *io, int pd_ch
         rc = ensure_kpc(c); if (rc) return rc;
         rc = ensure_entry_tables(c); if (rc) return rc;
     }
+    if (!c->fused && (kslab || kcols) && c->tune.fd_interp != 0) { rc = ensure_segent(c); if (rc) return rc; }
     if (c->fused) {
+        c->last_linearise = "in_sweep";
         // per-DoF lists: a chunk computes the slopes of ITS entries, whose range only the host copy of the lists gives
         if (!c->kp_known_uniform && !c->kp_traj_first_host)
             return set_err(c, KPILQR_ERR_STATE, "kpilqr_iterate_streamed with per-DoF key-point lists: the lists must be known to the host (kpilqr_set_keypoints, or kpilqr_get_keypoints after generating them)");
@@ -1376,8 +1457,16 @@ int kpilqr_iterate_streamed(kpilqr_ctx *c, const kpilqr_stream_io *io, int pd_ch
         if (io->lambda) KP_HIP(c, h2d(v.lambda, io->lambda + o, cnt * 8, s));
         // ---- kernels of the chunk --------------------------------------------------------------------------------
         if (!c->fused) {
-            if (slab || kslab || kcols) { rc = records_from_payload(&v); if (rc) { c->err = v.err; return rc; } }
-            KP_HIP(c, launch_interpolate(&v));
+            // a new key-point ordered / column payload: the chunk's records in one pass; else the payload's key-point columns into
+            // the records (none new: they hold them already) and k_interpolate
+            if ((kslab || kcols) && linearise_one_pass(&v)) {
+                KP_HIP(c, launch_fd_kp_interpolate(&v));
+                c->last_linearise = kcols ? "kp_columns_interpolate" : "fd_kp_interpolate";
+            } else {
+                if (slab || kslab || kcols) { rc = records_from_payload(&v); if (rc) { c->err = v.err; return rc; } }
+                KP_HIP(c, launch_interpolate(&v));
+                c->last_linearise = "fd_difference+interpolate";
+            }
             if (!c->tiled_a6) KP_HIP(c, launch_cost_derivs(&v));
         }
         rc = run_backward(&v, pd_check_stride);
@@ -1514,8 +1603,11 @@ const char *kpilqr_forward_variant(kpilqr_ctx *c) { return c ? c->fwd_variant : 
 //   lists    uni: every DoF of a trajectory has the same key-point list (the straight-line crossing forms ran) | ragged
 // The `lists` token is decided on the device (the host never needs it otherwise): this call reads the flag back, i.e. it
 // waits for the context's stream.
+// which = 2: the linearisation stage (a2 + a4) of the last kpilqr_fd_interpolate / kpilqr_iterate / kpilqr_iterate_streamed:
+//   fd_kp_interpolate | kp_columns_interpolate (one pass, linearise.hip) | fd_difference+interpolate | in_sweep (fused context)
 const char *kpilqr_last_launch(kpilqr_ctx *c, int which)
 {
+    if (c && which == 2) return c->last_linearise;
     if (!c || which < 0 || which > 1) return "";
     std::string &out = c->launch_desc[which];
     const FusedLaunch &p = which == 0 ? c->last_bwd : c->last_fwd;

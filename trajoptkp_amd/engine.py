@@ -116,8 +116,9 @@ class Engine:
 
     def last_launch(self, which="backward"):
         """kpilqr_last_launch: the form the last backward / forward launch actually took, e.g.
-        'mfma_f64_t1_fused:w1:raw:uni:ru0' (waits for the stream)."""
-        return self._L.kpilqr_last_launch(self._h, 0 if which == "backward" else 1).decode()
+        'mfma_f64_t1_fused:w1:raw:uni:ru0' (waits for the stream); which="linearise": the differencing + interpolation stage of
+        the last fd_interpolate / iterate / iterate_streamed, e.g. 'fd_kp_interpolate'."""
+        return self._L.kpilqr_last_launch(self._h, {"backward": 0, "linearise": 2}.get(which, 1)).decode()
 
     def device_array(self, which, shape, typestr="<f8"):
         p, sz = C.c_void_p(), C.c_size_t()
@@ -291,6 +292,13 @@ class Engine:
 
     def interpolate(self):
         self._ck(self._L.kpilqr_interpolate(self._h))
+
+    def fd_interpolate(self):
+        """kpilqr_fd_interpolate: fd_difference + interpolate, one pass over the step records for a key-point ordered or
+        column payload."""
+        if not hasattr(self._L, "kpilqr_fd_interpolate"):
+            raise KpilqrError(_lib.ERR_ARG, "this libkpilqr.so has no kpilqr_fd_interpolate")
+        self._ck(self._L.kpilqr_fd_interpolate(self._h))
 
     def filter_dynamics(self, method, coefs):
         """Optimiser::FilterDynamicsMatrices on the materialised A (after interpolate)."""

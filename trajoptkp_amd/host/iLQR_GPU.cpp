@@ -212,8 +212,10 @@ void iLQR_GPU::GenerateDerivatives()
     rc = kpilqr_upload_fd_slab(ctx, staging.slab, staging.njobs, staging.nnom, eps);
     if (rc) fatal("kpilqr_upload_fd_slab", rc);
     }
-    if ((rc = kpilqr_fd_difference(ctx))) fatal("kpilqr_fd_difference", rc);
-    if (!fused_active && (rc = kpilqr_interpolate(ctx))) fatal("kpilqr_interpolate", rc);
+    // a materialising context: A, B of every step in one call (one pass over the records for a key-point ordered payload); the
+    // fused sweeps interpolate themselves and want the differenced key-point columns only
+    if (fused_active) { if ((rc = kpilqr_fd_difference(ctx))) fatal("kpilqr_fd_difference", rc); }
+    else if ((rc = kpilqr_fd_interpolate(ctx))) fatal("kpilqr_fd_interpolate", rc);
     if (filteringMethod != "none") {                              // Optimiser.cpp:105-107
         if (fused_active) { recreate_ctx = true; std::fprintf(stderr, "iLQR_GPU: filtering set after the context was created; call Resize first\n"); std::exit(1); }
         const bool lp = filteringMethod == "low_pass";

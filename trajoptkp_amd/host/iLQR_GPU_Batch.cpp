@@ -249,8 +249,10 @@ void iLQR_GPU_Batch::GenerateDerivatives(const std::vector<int> &who)
         rc = kpilqr_upload_fd_slab(ctx, staging.slab, staging.njobs, staging.nnom, eps);
         if (rc) fatal("kpilqr_upload_fd_slab", rc);
     }
-    if ((rc = kpilqr_fd_difference(ctx))) fatal("kpilqr_fd_difference", rc);
-    if (!fused_active && (rc = kpilqr_interpolate(ctx))) fatal("kpilqr_interpolate", rc);
+    // a materialising context: A, B of every step in one call (one pass over the records for a key-point ordered payload); the
+    // fused sweeps interpolate themselves and want the differenced key-point columns only
+    if (fused_active) { if ((rc = kpilqr_fd_difference(ctx))) fatal("kpilqr_fd_difference", rc); }
+    else if ((rc = kpilqr_fd_interpolate(ctx))) fatal("kpilqr_fd_interpolate", rc);
     if (const_jacobians) {
         // a task with ONE residual Jacobian (ModelTranslator::ConstantResidualJacobians; Reaching.cpp:43-54): the pair went into
         // const_rx / const_ru when the optimiser was built and goes up once; only the residuals travel per linearisation
