@@ -14,7 +14,7 @@ ENV_KEYS = ("KPILQR_FUSED_WAVES", "KPILQR_FUSED_FWD_WAVES", "KPILQR_TILED_NT_MIN
             "KPILQR_TILED_FSC")
 
 
-def _env(env, key, default):                            # read_tuning_from_env, kpilqr_api.cpp:81-90
+def _env(env, key, default):                            # read_tuning_from_env, kpilqr_api.cpp
     v = (env or {}).get(key)
     return default if v is None or v == "" else int(v)
 
@@ -24,11 +24,11 @@ def _cdiv(a, b):                                        # C's int division (trun
     return q if (a >= 0) == (b > 0) else -q
 
 
-def tiled_nt(n, nt_min=0):                              # tiled_nt, tiled_mfma.hip:648 (wide_nt, tiled_wide.hip:489, is the same)
+def tiled_nt(n, nt_min=0):                              # tiled_nt, tiled_mfma.hip:649 (wide_nt, tiled_wide.hip:488, is the same)
     return max((n + 1 + 15) // 16, 2, nt_min)
 
 
-def backward_col_lds_bytes(nt):                         # tiled_mfma.hip:640
+def backward_col_lds_bytes(nt):                         # tiled_mfma.hip:641
     return 8 * ((2 * nt * nt + 7 * nt) * TILE + max(nt * nt * TPAD, 832))
 
 
@@ -62,8 +62,8 @@ def forward_wide_supported(n, m, n_alpha, nt_min=0):    # tiled_wide.hip:724
 
 
 def select_variants(dof, m, nr, T, n_alpha, batch, flags, env=None):
-    """select_variants (kpilqr_api.cpp:297-332): (backward variant, forward variant), or None where kpilqr_create refuses the
-    shape with KPILQR_ERR_ARG (the generic backward sweep's LDS, :327)."""
+    """select_variants (kpilqr_api.cpp): (backward variant, forward variant), or None where kpilqr_create refuses the
+    shape with KPILQR_ERR_ARG (the generic backward sweep's LDS, its last check)."""
     n = 2 * dof
     nt_min = _env(env, "KPILQR_TILED_NT_MIN", 0)
     generic, force_tiled = bool(flags & FLAG_GENERIC), bool(flags & FLAG_TILED)
@@ -76,7 +76,7 @@ def select_variants(dof, m, nr, T, n_alpha, batch, flags, env=None):
     fused = bool(flags & FLAG_FUSED) and not generic and not force_tiled and fused_supported(n, m, nr, dof, T, n_alpha)
     if fused:
         bv = fv = "mfma_f64_t1_fused"
-    elif flags & FLAG_FUSED and bv == fv == "mfma_f64_tiled":           # :321-326
+    elif flags & FLAG_FUSED and bv == fv == "mfma_f64_tiled":           # (the tiled_a6 choice)
         a6 = _env(env, "KPILQR_TILED_A6", -1)
         if nr <= 16 and (a6 != 0 if a6 >= 0 else (tiled_nt(n, nt_min) == 4 and batch >= 96)):
             bv = fv = "mfma_f64_tiled_a6"
@@ -123,7 +123,7 @@ def dispatch(dof, m, nr, T, n_alpha, batch, n_simd, flags, env=None, rx_const=Fa
         rxc = rx_const and ru_zero
         if rxc and bform == 1:
             out["extra"] = (("fused_rv2", n, m, rv2_ncr(nr)),)
-        # kpilqr_last_launch (kpilqr_api.cpp:1517): ":w1:" / ":pairh:" / ":pair:" / ":triple:" (the forward pair reports the form
+        # kpilqr_last_launch (kpilqr_api.cpp): ":w1:" / ":pairh:" / ":pair:" / ":triple:" (the forward pair reports the form
         # that ran on this set)
         out["launch"] = (bv + (":w1:" if bform == 1 else ":pairh:"), fv + ":" + {1: "w1", 3: "triple", 4: "pair"}[fform_ran] + ":")
         return out
@@ -296,7 +296,7 @@ def cases(n_simd):
 
 
 def generic_max_dof(m):
-    """The largest dof whose generic backward sweep fits the LDS bound (kpilqr_api.cpp:327, generic.hip:93)."""
+    """The largest dof whose generic backward sweep fits the LDS bound (select_variants in kpilqr_api.cpp, generic.hip:93)."""
     dof = 1
     while generic_lds_bytes(2 * (dof + 1), m) <= LDS_MAX:
         dof += 1

@@ -219,6 +219,66 @@ def test_streamed_iteration_with_the_kp_ordered_payload(fused):
             assert np.array_equal(K, ref["K"]) and np.array_equal(cp, ref["cost"])
 
 
+@pytest.mark.parametrize("fused", [True, False])
+@pytest.mark.parametrize("payload", ["fd_kp", "kp_cols"])
+def test_streamed_iterations_with_a_growing_entry_payload(payload, fused):
+    """Consecutive kpilqr_iterate_streamed calls on one context whose key-point lists get denser, so that the key-point ordered
+    slab (fd_kp) or the column store (kp_cols) has to be re-allocated while the chunk streams of the call before are still in
+    flight -- the counterpart of test_streamed_iterations_with_a_changing_slab_layout for the payloads laid out by entry.  Every
+    result is that of the blocking call sequence on a fresh context, bit for bit."""
+    from trajoptkp_amd.engine import rows_to_dof_csr
+    T, batch = 40, 5
+    probs = [synth.make_problem(task="acrobot", T=T, batch=batch, min_N=mn, dense_residuals=True, config_id=cid)
+             for mn, cid in ((8, 2), (3, 3), (1, 4))]
+    dof, n = probs[0]["dof"], probs[0]["n"]
+    entries = [int(rows_to_dof_csr(p["kp_rows"], dof, T)[0][-1]) for p in probs]
+    per_entry = (6 * n + 2) * 8 if payload == "fd_kp" else 3 * n * 8          # kpilqr_fd_kp_layout's entry_stride | [3][n] doubles
+    for a, b in zip(entries, entries[1:]):
+        # more than doubled, which is more than the largest slack any buffer is given (a quarter + 4096 bytes): it must grow
+        assert b * per_entry > 2 * a * per_entry and b * per_entry > a * per_entry + a * per_entry // 4 + 4096, entries
+
+    def payload_of(e, p):
+        xp, xm, mode = synth.kp_ordered_payload(p)
+        return e.fd_kp_slab(xp, xm, mode) if payload == "fd_kp" else e.kp_columns(xp, xm, mode, eps=p["eps"])
+
+    want = []
+    for p in probs:
+        with Engine(p["dof"], p["m"], T, p["nr"], batch=batch, fused=fused) as e:
+            synth.upload(e, p, kp_ordered=True)
+            if payload == "kp_cols":
+                e.upload_kp_columns(payload_of(e, p))
+            e.iterate(p["lam"], 100, orc.alphas(6))
+            K, k = e.gains()
+            want.append((K, k, e.results()))
+    p0 = probs[0]
+    with Engine(p0["dof"], p0["m"], T, p0["nr"], batch=batch, fused=fused) as e:
+        e.upload_residuals(None, None, None, p0["w_run"], p0["w_term"])
+        e.upload_nominal(None, p0["ctrl_lim"])
+        e.set_keypoints_rows(p0["kp_rows"])
+        e.forward_linear(orc.alphas(6), fetch=False)              # alphas resident
+        outs = []
+        for it, p in enumerate(probs):
+            e.set_keypoints_rows(p["kp_rows"])
+            s = payload_of(e, p)
+            assert s["entries"] == entries[it]
+            pin = {}
+            for name in ("r", "r_x", "r_u", "u_nom"):
+                pin[name] = e.pinned(p[name].shape); pin[name][...] = p[name]
+            lam = e.pinned(batch); lam[:] = p["lam"]
+            K = e.pinned(want[it][0].shape); k = e.pinned(want[it][1].shape)
+            cp = e.pinned((batch, 6)); st = e.pinned(batch, np.int32)
+            st[:] = -1
+            e.iterate_streamed(eps=p["eps"], lam=lam, K=K, k=k, cost_pred=cp, status=st, nchunks=3,
+                               **{payload: s}, **pin)             # no wait in between
+            outs.append((K, k, cp, st))
+        e.sync()
+        outs = [tuple(np.array(a) for a in o) for o in outs]       # the pinned buffers are freed with the engine
+    for (K, k, cp, st), (K0, k0, res0) in zip(outs, want):
+        assert np.all(st == 0)
+        assert np.array_equal(K, K0) and np.array_equal(k, k0)
+        assert np.array_equal(cp, res0["cost_pred"]) and np.array_equal(st, res0["status"])
+
+
 def test_backward_stats_histogram():
     """kpilqr_backward_stats: every step of every trajectory is counted once, the gains are those of kpilqr_backward, and a
     small lambda needs more refresh work than a large one."""

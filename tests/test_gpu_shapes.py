@@ -18,7 +18,7 @@ RTOL = 1e-9
 
 
 def _n_simd():
-    # as kpilqr_create does (kpilqr_api.cpp:364): SIMDs = CUs x 4
+    # as kpilqr_create does (kpilqr_api.cpp): SIMDs = CUs x 4
     import torch
     return torch.cuda.get_device_properties(0).multi_processor_count * 4
 

@@ -35,7 +35,7 @@ def test_every_case_maps_to_a_compiled_key_or_a_stated_refusal():
 
 
 def test_generic_lds_bound_for_seven_controls():
-    # kpilqr_api.cpp:327 with generic.hip:93: 19 970 doubles at dof 46 fit in 160 KB, 20 774 at dof 47 do not
+    # select_variants (kpilqr_api.cpp) with generic.hip:93: 19 970 doubles at dof 46 fit in 160 KB, 20 774 at dof 47 do not
     assert S.GENERIC_MAX_DOF_M7 == 46
     assert S.generic_lds_bytes(92, 7) <= 160 * 1024 < S.generic_lds_bytes(94, 7)
     assert S.select_variants(46, 7, 4, 5, 6, 2, 0) == ("generic_lds", "generic_lds")

@@ -53,6 +53,26 @@ struct FusedLaunch {
     bool excl = false;                  // w1: every wave has a SIMD to itself (the _excl twins)
 };
 
+// ---- device memory a context owns ------------------------------------------------------------
+// Pointer and allocated bytes.  Trivially copyable and without a destructor on purpose: a view of a trajectory range
+// (kpilqr_iterate_streamed) is a copy of the context with shifted pointers, and only kpilqr_destroy frees.  Sized by reserve()
+// (kpilqr_api.cpp) and by nothing else; DevBuf<T> converts to T *, which is all the launchers see.
+struct DevMem {
+    void *p = nullptr;
+    size_t cap = 0;               // allocated bytes
+};
+template <class T>
+struct DevBuf : DevMem {
+    operator T *() const { return static_cast<T *>(p); }
+    void shift(size_t count) { p = static_cast<T *>(p) + count; }      // a view: count elements further on
+};
+
+// FD payload resident on the device: job lists (kpilqr_upload_fd / _slab) | one record per key-point entry (kpilqr_upload_fd_kp) |
+// the differenced key-point columns themselves (kpilqr_upload_kp_columns: they live in kpc)
+enum class FdPayload : int { none, jobs, kp_ordered, kp_columns };
+// kernel family of a sweep, chosen per direction by select_variants (names: kpilqr_backward_variant)
+enum class Family : int { generic, t1, tiled, wide, fused };
+
 struct Ctx {
     kpilqr_dims d{};
     int n = 0;
@@ -62,33 +82,31 @@ struct Ctx {
     bool own_stream = false;
     std::string err;
 
-    // device buffers (cap[]: allocated bytes of the dimension-dependent ones, kpilqr_resize re-uses them)
-    size_t cap[18] = {0};
-    double *rec = nullptr;        // [batch][T][stride]
-    int *kp_uniform = nullptr;    // device flag: every trajectory has one key-point list for all its DoFs (k_kp_uniform)
-    double *K = nullptr;          // [batch][T][n*m]
-    double *k = nullptr;          // [batch][T][m]
-    double *r = nullptr;          // [batch][T+1][nr]
-    double *r_x = nullptr;        // [batch][T+1][nr][n]
-    double *r_u = nullptr;        // [batch][T+1][nr][m]
-    double *w_run = nullptr, *w_term = nullptr;   // [nr]
-    double *u_nom = nullptr;      // [batch][T][m]
-    double *ctrl_lim = nullptr;   // [2m]
-    double *lambda = nullptr;     // [batch]
-    double *alphas = nullptr;     // [n_alpha]
-    double *cost_pred = nullptr;  // [batch][n_alpha]
-    double *delta_J = nullptr;    // [batch]
-    double *traj_cost = nullptr;  // [batch]
-    int *status = nullptr;        // [batch]
-    int2 *segmap = nullptr;       // [batch][dof][T]: (start,end) key-points around t, or (-1,-1)
+    // device buffers (every DevBuf member is listed in for_each_buffer below; capacities are remembered, kpilqr_resize re-uses them)
+    bool is_view = false;         // a copy made by make_view: it borrows the context's buffers and never allocates (reserve refuses)
+    DevBuf<double> rec;           // [batch][T][stride]
+    DevBuf<int> kp_uniform;       // device flag: every trajectory has one key-point list for all its DoFs (k_kp_uniform)
+    DevBuf<double> K;             // [batch][T][n*m]
+    DevBuf<double> k;             // [batch][T][m]
+    DevBuf<double> r;             // [batch][T+1][nr]
+    DevBuf<double> r_x;           // [batch][T+1][nr][n]
+    DevBuf<double> r_u;           // [batch][T+1][nr][m]
+    DevBuf<double> w_run, w_term; // [nr]
+    DevBuf<double> u_nom;         // [batch][T][m]
+    DevBuf<double> ctrl_lim;      // [2m]
+    DevBuf<double> lambda;        // [batch]
+    DevBuf<double> alphas;        // [n_alpha]
+    DevBuf<double> cost_pred;     // [batch][n_alpha]
+    DevBuf<double> delta_J;       // [batch]
+    DevBuf<double> traj_cost;     // [batch]
+    DevBuf<int> status;           // [batch]
+    DevBuf<int2> segmap;          // [batch][dof][T]: (start,end) key-points around t, or (-1,-1)
     // [batch][dof][T]: CSR entry of the key-point at or before t (the one-pass linearisation fetches a segment's endpoints by
     // entry), or -1 outside the list.  Built with segmap on a context that has records; on demand on a fused one (segent_valid)
-    int *segent = nullptr;
-    size_t segent_cap = 0;        // bytes
+    DevBuf<int> segent;
     bool segent_valid = false;
-    int *kp_offsets = nullptr;    // [batch*dof+1]
-    int *kp_times = nullptr;      // [kp_total]
-    size_t kp_cap = 0;            // capacity of kp_times (ints)
+    DevBuf<int> kp_offsets;       // [batch*dof+1]
+    DevBuf<int> kp_times;         // [kp_total]
     bool have_kp = false;
     bool kp_canonical = false;   // every DoF list strictly increasing, first 0, last T-1 (what the fused sweeps walk)
     bool fused = false;          // KPILQR_FLAG_FUSED and a supported shape
@@ -97,8 +115,7 @@ struct Ctx {
     // constant residual Jacobians (kpilqr_upload_residual_jacobians_const): ONE r_x [nr][n] for every trajectory and step.
     // rx_const_on: the fused one-wave sweeps keep it in registers and never read the r_x buffer; rx_buf_valid: the r_x buffer
     // holds the broadcast copy (made on demand for every other kernel family, ensure_rx_buffer)
-    double *rx_const = nullptr;
-    size_t rx_const_cap = 0;
+    DevBuf<double> rx_const;
     bool rx_const_on = false, rx_buf_valid = true;
 
     // ---- fused contexts: the key-point column store (no step records) ---------------------------------------------------
@@ -107,52 +124,46 @@ struct Ctx {
     //                       kind 0: position column (A col d), 1: velocity column (A col d + dof), 2: control column (B col d, d < m)
     // i.e. 3n doubles per (trajectory, DoF, key-point) instead of a whole record per (trajectory, step).  The records are
     // allocated on demand when something asks for the materialised sequence (kpilqr_interpolate, get_AB, the error test ...).
-    double *kpc = nullptr;
-    size_t kpc_cap = 0;          // bytes
+    DevBuf<double> kpc;
     bool kpc_valid = false;      // kpc holds ALL differenced columns of the resident FD payload for the current key-points
     bool kpc_touched = false;    // a raw backward sweep has (re)written kpc from the resident payload since it was uploaded
     // slope store beside kpc (k_kp_slopes): kps [entry][3][n][2] = (column value, (column of the list's next key-point - this column) /
     // (time gap)) pairs, slope 0 for a list's last entry.  Read by the general (per-DoF list) forms of the one-wave sweeps; allocated only when the lists may be
     // ragged (kp_known_uniform: the host has seen that every trajectory's DoFs share one list -- then the device flag says the same
     // and only the segment-loop forms run)
-    double *kps = nullptr;
-    size_t kps_cap = 0;
+    DevBuf<double> kps;
     bool kps_valid = false;      // kps holds the slopes of the columns kpc holds (kpc_valid)
     bool kp_known_uniform = false;
     int kp_view_entries = -1;    // a view of a trajectory range: the CSR entries of its trajectories (first: fdk_first); -1: the context
-    int *kp_entry = nullptr;     // [batch*dof][T]: CSR entry of (list, t), or -1        (built with the segment map)
-    int *kp_entry_list = nullptr;// [entries]: list (= b*dof + d) of a CSR entry
-    size_t kp_entry_cap = 0, kp_entry_list_cap = 0;   // ints
+    DevBuf<int> kp_entry;        // [batch*dof][T]: CSR entry of (list, t), or -1        (built with the segment map)
+    DevBuf<int> kp_entry_list;   // [entries]: list (= b*dof + d) of a CSR entry
     bool entry_tables_valid = false;
     bool have_rec = false;       // step records allocated (always on a non-fused context; on demand on a fused one)
     bool rec_synced = false;     // fused context: the records hold the key-point columns of the resident payload
     int kp_total_host = -1;      // number of CSR entries when the host knows it (kpilqr_set_keypoints), else -1
     int *kp_traj_first_host = nullptr;                // [batch+1] first CSR entry of every trajectory (host copy), or null
-    // FD payload resident on the device: 0 none, 1 job lists (kpilqr_upload_fd / _slab), 2 key-point ordered (kpilqr_upload_fd_kp)
-    int fd_kind = 0;
+    FdPayload fd_payload = FdPayload::none;
     // key-point ordered payload: one record per CSR entry, [(x+, x-) pairs of the 3n elements | int32 mode, pad] = fdk_stride() bytes
-    char *fdk_dev = nullptr;
-    size_t fdk_dev_cap = 0;
+    DevBuf<char> fdk_dev;
     size_t fdk_stride() const { return (size_t)(6 * n + 2) * 8; }
     int fdk_entries = 0;         // entries of the resident key-point ordered payload (a view: of its trajectories)
     int fdk_first = 0;           // first entry of a view's trajectories (0 for the context itself)
 
     // nominal states for on-device key-point placement (kpilqr_upload_states), allocated on first use
-    double *X_states = nullptr;   // [batch][T][n]
-    double *kp_thr = nullptr;     // [dof]
-    unsigned long long *kp_mask = nullptr;   // [batch*dof][ceil(T/64)]
-    int *kp_count = nullptr;      // [batch*dof]
+    DevBuf<double> X_states;      // [batch][T][n]
+    DevBuf<double> kp_thr;        // [dof]
+    DevBuf<unsigned long long> kp_mask;      // [batch*dof][ceil(T/64)]
+    DevBuf<int> kp_count;         // [batch*dof]
     bool have_states = false;
 
     // RCCL communicator for the line-search reduction (kpilqr_comm_init), and its 8-double device buffer
     void *comm = nullptr;
     int comm_ranks = 1;
-    double *ls8 = nullptr;
+    DevBuf<double> ls8;
 
     // FD job buffers: ONE device slab (grown on demand) whose layout mirrors the host slab of kpilqr_fd_slab_layout,
     // so that an upload is one hipMemcpyAsync; the pointers below point into it and are recomputed by every upload
-    char *fd_dev = nullptr;
-    size_t fd_dev_cap = 0;                 // bytes
+    DevBuf<char> fd_dev;
     int njobs = 0, nnom = 0;
     int *job_b = nullptr, *job_t = nullptr, *job_col = nullptr, *job_nom = nullptr;
     unsigned char *job_mode = nullptr;
@@ -163,7 +174,7 @@ struct Ctx {
     double *rec_fd_base = nullptr;
     int fd_batch_total = 0;
     // device-side argument checks raise bits here; kpilqr_sync reads it back through the pinned mirror
-    int *err_flag = nullptr;
+    DevBuf<int> err_flag;
     int *err_flag_host = nullptr;          // pinned
 
     // trajectory-chunk pipeline of kpilqr_iterate_streamed: H2D(c+1) | kernels(c) | D2H(c-1) on separate streams
@@ -179,11 +190,19 @@ struct Ctx {
     unsigned long long pipe_sig = 0;       // hash of (njobs, nnom, traj_job_first, traj_nom_first) of the streamed iteration in flight
 
     // staging for debug hooks / U_alpha
-    double *stage = nullptr;
-    size_t stage_cap = 0;   // bytes
+    DevBuf<double> stage;
 
-    const char *bwd_variant = "";
-    const char *fwd_variant = "";
+    // everything the context owns on the device, once: kpilqr_destroy frees by walking this
+    template <class F>
+    void for_each_buffer(F f)
+    {
+        DevMem *const all[] = {&rec, &kp_uniform, &K, &k, &r, &r_x, &r_u, &w_run, &w_term, &u_nom, &ctrl_lim, &lambda, &alphas, &cost_pred,
+                               &delta_J, &traj_cost, &status, &segmap, &segent, &kp_offsets, &kp_times, &rx_const, &kpc, &kps, &kp_entry,
+                               &kp_entry_list, &fdk_dev, &X_states, &kp_thr, &kp_mask, &kp_count, &ls8, &fd_dev, &err_flag, &stage};
+        for (DevMem *b : all) f(*b);
+    }
+
+    Family bwd_family = Family::generic, fwd_family = Family::generic;
     // what the last backward / forward launch of this context actually was (kpilqr_last_launch); Waves::none: not a fused launch, or none yet
     FusedLaunch last_bwd, last_fwd;
     std::string launch_desc[2];
@@ -239,7 +258,7 @@ hipError_t launch_generate_keypoints(Ctx *c, int method, int min_N, int max_N, d
                                      const double *X_dev, unsigned long long *mask_dev, int *count_dev);
 hipError_t launch_kp_error_test(Ctx *c, int n_iv, const int *iv_dev, int min_N, double threshold, unsigned char *good_dev);
 hipError_t launch_interpolate(Ctx *c);
-// linearise.hip: key-point ordered payload (fd_kind 2) or column payload (3) -> every step record's [A|B], a2 + a4 in one pass
+// linearise.hip: key-point ordered payload (FdPayload::kp_ordered) or column payload (kp_columns) -> every step record's [A|B], a2 + a4 in one pass
 hipError_t launch_fd_kp_interpolate(Ctx *c);
 hipError_t launch_filter_dynamics(Ctx *c, int method, const double *coefs_dev, int ncoef);
 hipError_t launch_dof_importance(Ctx *c, int sampling, double *sums_dev);

@@ -51,21 +51,48 @@ static int join_pipeline(kpilqr_ctx *c)
         if ((c)->pipe_dirty) { int rcj_ = join_pipeline(c); if (rcj_) return rcj_; } \
     } while (0)
 
-template <class T>
-static hipError_t dalloc(T **p, size_t count)
+// ---- device memory: every allocation of a context is made here ------------------------------------------------------------
+// What a growing buffer allocates beyond the bytes asked for: need / div + add (div 0: nothing), so that sizes which move a little
+// from one call to the next -- the key-point lists of the adaptive methods -- do not re-allocate every time.
+struct Slack { size_t div, add; };
+static constexpr Slack kExact{0, 0};              // the dimension-sized buffers and the staging area
+static constexpr Slack kQuarter{4, 4096};         // per key-point entry: column store, slope store
+static constexpr Slack kEighth{8, 4096};          // the two FD slabs
+
+static bool would_grow(const DevMem &b, size_t need) { return need > b.cap; }
+
+static hipError_t release(DevMem &b)
 {
-    *p = nullptr;
-    if (count == 0) count = 1;
-    return hipMalloc((void **)p, count * sizeof(T));
+    const hipError_t e = b.p ? hipFree(b.p) : hipSuccess;
+    b = DevMem{};
+    return e;
 }
 
-template <class T>
-static int regrow(kpilqr_ctx *c, T **p, size_t count)
+// Room for `need` bytes in b.  Nothing happens while they fit; otherwise the old allocation is freed -- after a wait for the
+// context's stream: nothing in flight still uses it -- and need + slack bytes are allocated.  Returns 1 when it re-allocated (the
+// old contents are gone), 0 when not, an error code < 0.  zero: the `need` bytes are cleared, grown or not.
+static int reserve(kpilqr_ctx *c, DevMem &b, size_t need, Slack slack, bool zero)
 {
-    if (*p) KP_HIP(c, hipFree(*p));
-    *p = nullptr;
-    KP_HIP(c, dalloc(p, count));
-    return KPILQR_OK;
+    int grown = 0;
+    if (would_grow(b, need)) {
+        if (c->is_view) return set_err(c, KPILQR_ERR_STATE, "a view of a trajectory range never allocates: its context sizes the buffers first");
+        if (b.p) KP_HIP(c, hipStreamSynchronize(c->stream));
+        KP_HIP(c, release(b));
+        const size_t bytes = need + (slack.div ? need / slack.div + slack.add : 0);
+        const hipError_t e = hipMalloc(&b.p, bytes);
+        if (e != hipSuccess) { b.p = nullptr; return set_err(c, KPILQR_ERR_ALLOC, std::string("hipMalloc failed: ") + hipGetErrorString(e)); }
+        b.cap = bytes;
+        grown = 1;
+    }
+    if (zero && need) KP_HIP(c, hipMemsetAsync(b.p, 0, need, c->stream));
+    return grown;
+}
+
+// the staging area of the debug hooks / U_alpha
+static int ensure_stage(kpilqr_ctx *c, size_t bytes)
+{
+    const int rc = reserve(c, c->stage, bytes, kExact, false);
+    return rc < 0 ? rc : KPILQR_OK;
 }
 
 static int env_int(const char *name, int dflt)
@@ -102,49 +129,37 @@ static int size_buffers(kpilqr_ctx *c)
     c->n = 2 * dims->dof;
     c->L = RecLayout(c->n, dims->m);
     const size_t B = dims->batch, T = dims->T, n = c->n, m = dims->m, nr = dims->nr;
-    struct Want { void **p; size_t bytes; size_t *cap; bool zero; };
-    const Want want[] = {
+    const size_t segent_bytes = B * dims->dof * T * sizeof(int);
+    // k_build_segmap writes segent wherever it exists: one a fused context built on demand must not outlive a shape it does not cover
+    if (c->fused && would_grow(c->segent, segent_bytes)) KP_HIP(c, release(c->segent));
+    c->segent_valid = false;
+    struct Row { DevMem *buf; size_t bytes; bool zero; };      // zero: records start zeroed so that padding / never-written columns are defined
+    const Row rows[] = {
         // a fused (one-tile) context keeps key-point columns only (Ctx::kpc); its records appear on demand (ensure_records)
-        {(void **)&c->rec, c->fused ? 0 : B * T * c->L.stride * 8, &c->cap[0], true},
-        {(void **)&c->K, B * T * n * m * 8, &c->cap[1], true},
-        {(void **)&c->k, B * T * m * 8, &c->cap[2], true},
-        {(void **)&c->r, B * (T + 1) * nr * 8, &c->cap[3], true},
-        {(void **)&c->r_x, B * (T + 1) * nr * n * 8, &c->cap[4], true},
-        {(void **)&c->r_u, B * (T + 1) * nr * m * 8, &c->cap[5], true},
-        {(void **)&c->w_run, nr * 8, &c->cap[6], false},
-        {(void **)&c->w_term, nr * 8, &c->cap[7], false},
-        {(void **)&c->u_nom, B * T * m * 8, &c->cap[8], true},
-        {(void **)&c->ctrl_lim, 2 * m * 8, &c->cap[9], false},
-        {(void **)&c->lambda, B * 8, &c->cap[10], false},
-        {(void **)&c->alphas, (size_t)dims->n_alpha * 8, &c->cap[11], false},
-        {(void **)&c->cost_pred, B * dims->n_alpha * 8, &c->cap[12], false},
-        {(void **)&c->delta_J, B * 8, &c->cap[13], false},
-        {(void **)&c->traj_cost, B * 8, &c->cap[14], false},
-        {(void **)&c->status, B * 4, &c->cap[15], true},
-        {(void **)&c->segmap, B * dims->dof * T * sizeof(int2), &c->cap[16], false},
-        {(void **)&c->kp_offsets, (B * dims->dof + 1) * 4, &c->cap[17], false},
+        {&c->rec, c->fused ? 0 : B * T * c->L.stride * 8, true},
+        {&c->K, B * T * n * m * 8, true},
+        {&c->k, B * T * m * 8, true},
+        {&c->r, B * (T + 1) * nr * 8, true},
+        {&c->r_x, B * (T + 1) * nr * n * 8, true},
+        {&c->r_u, B * (T + 1) * nr * m * 8, true},
+        {&c->w_run, nr * 8, false},
+        {&c->w_term, nr * 8, false},
+        {&c->u_nom, B * T * m * 8, true},
+        {&c->ctrl_lim, 2 * m * 8, false},
+        {&c->lambda, B * 8, false},
+        {&c->alphas, (size_t)dims->n_alpha * 8, false},
+        {&c->cost_pred, B * dims->n_alpha * 8, false},
+        {&c->delta_J, B * 8, false},
+        {&c->traj_cost, B * 8, false},
+        {&c->status, B * 4, true},
+        {&c->segmap, B * dims->dof * T * sizeof(int2), false},
+        {&c->kp_offsets, (B * dims->dof + 1) * 4, false},
+        // the entry map of the one-pass linearisation, beside segmap: with the records (a fused context builds it on demand, ensure_segent)
+        {&c->segent, c->fused ? 0 : segent_bytes, false},
     };
-    for (const Want &w : want) {
-        if (w.bytes > *w.cap) {
-            if (*w.p) KP_HIP(c, hipFree(*w.p));
-            *w.p = nullptr; *w.cap = 0;
-            hipError_t e = hipMalloc(w.p, w.bytes ? w.bytes : 8);
-            if (e != hipSuccess) { c->err = std::string("hipMalloc failed: ") + hipGetErrorString(e); return KPILQR_ERR_ALLOC; }
-            *w.cap = w.bytes;
-        }
-        // records start zeroed so that padding / never-written columns are defined
-        if (w.zero && w.bytes) KP_HIP(c, hipMemsetAsync(*w.p, 0, w.bytes, c->stream));
-    }
-    // the entry map of the one-pass linearisation, beside segmap: with the records (a fused context builds it on demand, ensure_segent)
-    {
-        const size_t need = B * dims->dof * T * sizeof(int);
-        if (c->segent && need > c->segent_cap) { KP_HIP(c, hipFree(c->segent)); c->segent = nullptr; c->segent_cap = 0; }
-        if (!c->fused && !c->segent) {
-            hipError_t e = hipMalloc((void **)&c->segent, need ? need : 8);
-            if (e != hipSuccess) { c->err = std::string("hipMalloc failed: ") + hipGetErrorString(e); return KPILQR_ERR_ALLOC; }
-            c->segent_cap = need;
-        }
-        c->segent_valid = false;
+    for (const Row &row : rows) {
+        const int rc = reserve(c, *row.buf, row.bytes, kExact, row.zero);
+        if (rc < 0) return rc;
     }
     c->have_rec = !c->fused;
     c->rec_fd_base = c->rec;
@@ -153,26 +168,17 @@ static int size_buffers(kpilqr_ctx *c)
 }
 
 // ---- fused contexts: key-point column store, entry tables, records on demand ----------------------------------------------
-static int grow_dev(kpilqr_ctx *c, void **p, size_t *cap, size_t bytes, bool zero)
-{
-    if (bytes > *cap) {
-        KP_HIP(c, hipStreamSynchronize(c->stream));              // nothing in flight still uses the old allocation
-        if (*p) KP_HIP(c, hipFree(*p));
-        *p = nullptr; *cap = 0;
-        hipError_t e = hipMalloc(p, bytes ? bytes : 8);
-        if (e != hipSuccess) { c->err = std::string("hipMalloc failed: ") + hipGetErrorString(e); return KPILQR_ERR_ALLOC; }
-        *cap = bytes;
-        if (zero) KP_HIP(c, hipMemsetAsync(*p, 0, bytes, c->stream));
-        return 1;                                                // re-allocated: the old contents are gone
-    }
-    return KPILQR_OK;
-}
-
 // number of CSR entries of the current lists (known to the host since kpilqr_set_keypoints / kpilqr_generate_keypoints,
 // which reads the total back); the capacity of kp_times before any key-points exist
 static size_t kp_entries(const kpilqr_ctx *c)
 {
-    return c->kp_total_host >= 0 ? (size_t)c->kp_total_host : c->kp_cap;
+    return c->kp_total_host >= 0 ? (size_t)c->kp_total_host : c->kp_times.cap / sizeof(int);
+}
+
+// a payload with one record (or three columns) per key-point entry: it is laid out BY the lists
+static bool payload_by_entry(const kpilqr_ctx *c)
+{
+    return c->fd_payload == FdPayload::kp_ordered || c->fd_payload == FdPayload::kp_columns;
 }
 
 // kpc for the current key-points: 3n doubles per CSR entry (a quarter of slack, so that lists whose counts move a little
@@ -180,10 +186,12 @@ static size_t kp_entries(const kpilqr_ctx *c)
 static int ensure_kpc(kpilqr_ctx *c)
 {
     const size_t need = kp_entries(c) * 3 * (size_t)c->n * 8;
-    if (need <= c->kpc_cap) return KPILQR_OK;
-    const int rc = grow_dev(c, (void **)&c->kpc, &c->kpc_cap, need + need / 4 + 4096, true);
+    const int rc = reserve(c, c->kpc, need, kQuarter, false);
     if (rc < 0) return rc;
-    if (rc > 0) c->kpc_valid = c->kpc_touched = c->kps_valid = false;
+    if (rc > 0) {              // a new store starts zeroed, slack included: entries come into use without passing through here
+        KP_HIP(c, hipMemsetAsync(c->kpc, 0, c->kpc.cap, c->stream));
+        c->kpc_valid = c->kpc_touched = c->kps_valid = false;
+    }
     return KPILQR_OK;
 }
 
@@ -192,10 +200,9 @@ static int ensure_kps(kpilqr_ctx *c, bool force = false)
 {
     if (c->kp_known_uniform && !force) return KPILQR_OK;
     const size_t need = kp_entries(c) * 6 * (size_t)c->n * 8;              // (value, slope) pairs
-    if (need <= c->kps_cap) return KPILQR_OK;
-    const int rc = grow_dev(c, (void **)&c->kps, &c->kps_cap, need + need / 4 + 4096, false);
+    const int rc = reserve(c, c->kps, need, kQuarter, false);
     if (rc < 0) return rc;
-    c->kps_valid = false;
+    if (rc > 0) c->kps_valid = false;
     return KPILQR_OK;
 }
 
@@ -213,12 +220,9 @@ static int slopes_for_kpc(kpilqr_ctx *c)
 static int ensure_entry_tables(kpilqr_ctx *c)
 {
     if (c->entry_tables_valid) return KPILQR_OK;
-    int rc = grow_dev(c, (void **)&c->kp_entry, &c->kp_entry_cap, (size_t)c->d.batch * c->d.dof * c->d.T * sizeof(int), false);
+    int rc = reserve(c, c->kp_entry, (size_t)c->d.batch * c->d.dof * c->d.T * sizeof(int), kExact, false);
     if (rc < 0) return rc;
-    {
-        const size_t need = (kp_entries(c) ? kp_entries(c) : 1) * sizeof(int);
-        rc = need <= c->kp_entry_list_cap ? KPILQR_OK : grow_dev(c, (void **)&c->kp_entry_list, &c->kp_entry_list_cap, need + need / 4, false);
-    }
+    rc = reserve(c, c->kp_entry_list, (kp_entries(c) ? kp_entries(c) : 1) * sizeof(int), Slack{4, 0}, false);
     if (rc < 0) return rc;
     KP_HIP(c, launch_build_entry_tables(c));
     c->entry_tables_valid = true;
@@ -228,8 +232,8 @@ static int ensure_entry_tables(kpilqr_ctx *c)
 // The resident FD payload differenced into kpc (explicitly: the raw backward sweep does the same on the fly)
 static int difference_to_kpc(kpilqr_ctx *c)
 {
-    if (c->fd_kind == 0 || !c->have_kp) return KPILQR_OK;
-    if (c->fd_kind == 3) {                       // the columns ARE the payload
+    if (c->fd_payload == FdPayload::none || !c->have_kp) return KPILQR_OK;
+    if (c->fd_payload == FdPayload::kp_columns) {                       // the columns ARE the payload
         if (!c->kpc_valid) return set_err(c, KPILQR_ERR_STATE, "the key-point columns are gone (new key-points): upload them again");
         return KPILQR_OK;
     }
@@ -237,7 +241,7 @@ static int difference_to_kpc(kpilqr_ctx *c)
     if (rc) return rc;
     if (c->fused) { rc = ensure_kps(c); if (rc) return rc; }       // (only the fused sweeps' per-DoF list forms read the slope store)
     c->kps_valid = false;
-    if (c->fd_kind == 1) {
+    if (c->fd_payload == FdPayload::jobs) {
         rc = ensure_entry_tables(c);
         if (rc) return rc;
         KP_HIP(c, launch_fd_difference_kpc(c));
@@ -253,8 +257,8 @@ static int difference_to_kpc(kpilqr_ctx *c)
 // context that has records)
 static int records_from_payload(kpilqr_ctx *c)
 {
-    if (c->fd_kind == 1) { KP_HIP(c, launch_fd_difference(c)); return KPILQR_OK; }
-    if (c->fd_kind == 2 || c->fd_kind == 3) {
+    if (c->fd_payload == FdPayload::jobs) { KP_HIP(c, launch_fd_difference(c)); return KPILQR_OK; }
+    if (payload_by_entry(c)) {
         if (!c->have_kp) return KPILQR_OK;
         int rc = KPILQR_OK;
         if (!c->kpc_valid) rc = difference_to_kpc(c);
@@ -270,7 +274,7 @@ static int records_from_payload(kpilqr_ctx *c)
 static int ensure_segent(kpilqr_ctx *c)
 {
     if (c->segent_valid) return KPILQR_OK;
-    const int rc = grow_dev(c, (void **)&c->segent, &c->segent_cap, (size_t)c->d.batch * c->d.dof * c->d.T * sizeof(int), false);
+    const int rc = reserve(c, c->segent, (size_t)c->d.batch * c->d.dof * c->d.T * sizeof(int), kExact, false);
     if (rc < 0) return rc;
     KP_HIP(c, launch_build_segmap(c, true));
     c->segent_valid = true;
@@ -284,21 +288,22 @@ static int ensure_segent(kpilqr_ctx *c)
 static bool linearise_one_pass(const kpilqr_ctx *c)
 {
     if (c->tune.fd_interp == 0) return false;
-    if (c->fd_kind == 3) return c->kpc_valid;
-    return c->fd_kind == 2;
+    if (c->fd_payload == FdPayload::kp_columns) return c->kpc_valid;
+    return c->fd_payload == FdPayload::kp_ordered;
 }
 
-static int linearise(kpilqr_ctx *c)
+// from_payload = false: the records hold the payload's key-point columns already (a chunk of a streamed iteration that brought
+// no new payload), so k_interpolate alone runs.
+static int linearise(kpilqr_ctx *c, bool from_payload = true)
 {
-    if (linearise_one_pass(c)) {
+    if (from_payload && linearise_one_pass(c)) {
         const int rc = ensure_segent(c);
         if (rc) return rc;
         KP_HIP(c, launch_fd_kp_interpolate(c));
-        c->last_linearise = c->fd_kind == 3 ? "kp_columns_interpolate" : "fd_kp_interpolate";
+        c->last_linearise = c->fd_payload == FdPayload::kp_columns ? "kp_columns_interpolate" : "fd_kp_interpolate";
         return KPILQR_OK;
     }
-    const int rc = records_from_payload(c);
-    if (rc) return rc;
+    if (from_payload) { const int rc = records_from_payload(c); if (rc) return rc; }
     KP_HIP(c, launch_interpolate(c));
     c->last_linearise = "fd_difference+interpolate";
     return KPILQR_OK;
@@ -310,10 +315,8 @@ static int linearise(kpilqr_ctx *c)
 static int ensure_record_storage(kpilqr_ctx *c)
 {
     if (!c->have_rec) {
-        const size_t bytes = (size_t)c->d.batch * c->d.T * c->L.stride * 8;
-        const int rc = grow_dev(c, (void **)&c->rec, &c->cap[0], bytes, false);
+        const int rc = reserve(c, c->rec, (size_t)c->d.batch * c->d.T * c->L.stride * 8, kExact, true);
         if (rc < 0) return rc;
-        KP_HIP(c, hipMemsetAsync(c->rec, 0, bytes, c->stream));
         c->rec_fd_base = c->rec;
         c->have_rec = true;
         c->rec_synced = false;
@@ -339,6 +342,26 @@ static void payload_changed(kpilqr_ctx *c)
     c->rec_synced = false;
 }
 
+// New key-point lists of `total` entries are on the device: everything that was derived from the old ones is stale, and a payload
+// laid out by them is dropped (it has to follow them)
+static void keypoints_changed(kpilqr_ctx *c, int total)
+{
+    c->kp_total_host = total;
+    c->entry_tables_valid = false;
+    if (payload_by_entry(c)) { c->fd_payload = FdPayload::none; c->fdk_entries = 0; }
+    payload_changed(c);
+}
+
+// Host copy of the first CSR entry of every trajectory (kpilqr_iterate_streamed cuts an entry-ordered payload into chunks by it);
+// false: no host memory
+static bool remember_traj_first(kpilqr_ctx *c, const int *kp_offsets)
+{
+    if (!c->kp_traj_first_host) c->kp_traj_first_host = (int *)malloc(sizeof(int) * ((size_t)c->d.batch + 1));
+    if (!c->kp_traj_first_host) return false;
+    for (int b = 0; b <= c->d.batch; b++) c->kp_traj_first_host[b] = kp_offsets[(size_t)b * c->d.dof];
+    return true;
+}
+
 // Constant residual Jacobians (kpilqr_upload_residual_jacobians_const): a fused sweep whose plan says rxc keeps r_x in registers;
 // every other sweep streams r_x per step from the context's buffer, which then receives the broadcast copy -- once, on demand.
 static int ensure_rx_buffer(kpilqr_ctx *c)
@@ -349,23 +372,36 @@ static int ensure_rx_buffer(kpilqr_ctx *c)
     return KPILQR_OK;
 }
 
-// kernel families for c->d (names: kpilqr_backward_variant)
+// what kpilqr_backward_variant / kpilqr_forward_variant call a family (a6: Ctx::tiled_a6)
+static const char *variant_name(Family f, bool a6)
+{
+    switch (f) {
+    case Family::t1: return "mfma_f64_t1";
+    case Family::tiled: return a6 ? "mfma_f64_tiled_a6" : "mfma_f64_tiled";
+    case Family::wide: return "mfma_f64_wide";
+    case Family::fused: return "mfma_f64_t1_fused";
+    case Family::generic: break;
+    }
+    return "generic_lds";
+}
+
+// kernel families for c->d
 static int select_variants(kpilqr_ctx *c)
 {
     const kpilqr_dims *dims = &c->d;
     c->fused = c->tiled_a6 = false;
     const bool generic = (dims->flags & KPILQR_FLAG_GENERIC_KERNELS) != 0;
     const bool force_tiled = (dims->flags & KPILQR_FLAG_TILED_KERNELS) != 0;
-    c->bwd_variant = (!generic && !force_tiled && backward_mfma_supported(c->n, dims->m)) ? "mfma_f64_t1"
-                   : (!generic && backward_tiled_supported(c->n, dims->m, c->tune.tiled_nt_min)) ? "mfma_f64_tiled"
-                   : (!generic && backward_wide_supported(c->n, dims->m, c->tune.tiled_nt_min)) ? "mfma_f64_wide" : "generic_lds";
-    c->fwd_variant = (!generic && !force_tiled && forward_mfma_supported(c->n, dims->m, dims->n_alpha)) ? "mfma_f64_t1"
-                   : (!generic && forward_tiled_supported(c->n, dims->m, dims->n_alpha, c->tune.tiled_nt_min)) ? "mfma_f64_tiled"
-                   : (!generic && forward_wide_supported(c->n, dims->m, dims->n_alpha, c->tune.tiled_nt_min)) ? "mfma_f64_wide" : "generic_lds";
+    c->bwd_family = (!generic && !force_tiled && backward_mfma_supported(c->n, dims->m)) ? Family::t1
+                  : (!generic && backward_tiled_supported(c->n, dims->m, c->tune.tiled_nt_min)) ? Family::tiled
+                  : (!generic && backward_wide_supported(c->n, dims->m, c->tune.tiled_nt_min)) ? Family::wide : Family::generic;
+    c->fwd_family = (!generic && !force_tiled && forward_mfma_supported(c->n, dims->m, dims->n_alpha)) ? Family::t1
+                  : (!generic && forward_tiled_supported(c->n, dims->m, dims->n_alpha, c->tune.tiled_nt_min)) ? Family::tiled
+                  : (!generic && forward_wide_supported(c->n, dims->m, dims->n_alpha, c->tune.tiled_nt_min)) ? Family::wide : Family::generic;
     if ((dims->flags & KPILQR_FLAG_FUSED) && !generic && !force_tiled &&
         fused_supported(c->n, dims->m, dims->nr, dims->dof, dims->T, dims->n_alpha)) {
         c->fused = true;
-        c->bwd_variant = c->fwd_variant = "mfma_f64_t1_fused";
+        c->bwd_family = c->fwd_family = Family::fused;
     }
     // The same flag on a tiled shape (n + 2 > 16): a6 (variant "..._a6"), cost derivatives formed from the residuals inside the
     // sweeps.  It replaces k_cost_derivs (HBM-bound: n^2 doubles written per step) by NT*ceil(nr/4) + 6 MFMAs per wave-step of the
@@ -373,14 +409,10 @@ static int select_variants(kpilqr_ctx *c)
     // (n = 62, B = 128, T = 5000: 74.4 -> 70.6 ms), a loss for two or three tiles at the batches measured.  KPILQR_TILED_A6 = 0 | 1.
     // (a4 inside the tiled sweeps existed in rounds 2-4, parity-green and slower by more than the k_interpolate it removed; removed
     // in round 5: tiled_mfma.hip.)
-    if ((dims->flags & KPILQR_FLAG_FUSED) && !c->fused &&
-        strcmp(c->bwd_variant, "mfma_f64_tiled") == 0 && strcmp(c->fwd_variant, "mfma_f64_tiled") == 0) {
-        const bool want_a6 = dims->nr <= 16 && (c->tune.tiled_a6 >= 0 ? c->tune.tiled_a6 != 0
-                                                : (tiled_tiles(c->n, c->tune.tiled_nt_min) == 4 && dims->batch >= 96));
-        c->tiled_a6 = want_a6;
-        if (want_a6) c->bwd_variant = c->fwd_variant = "mfma_f64_tiled_a6";
-    }
-    if (strcmp(c->bwd_variant, "generic_lds") == 0 && backward_generic_lds_bytes(c->n, dims->m) > 160 * 1024) {
+    if ((dims->flags & KPILQR_FLAG_FUSED) && c->bwd_family == Family::tiled && c->fwd_family == Family::tiled)
+        c->tiled_a6 = dims->nr <= 16 && (c->tune.tiled_a6 >= 0 ? c->tune.tiled_a6 != 0
+                                         : (tiled_tiles(c->n, c->tune.tiled_nt_min) == 4 && dims->batch >= 96));
+    if (c->bwd_family == Family::generic && backward_generic_lds_bytes(c->n, dims->m) > 160 * 1024) {
         c->err = "state dimension too large for the generic backward kernel (LDS)";
         return KPILQR_ERR_ARG;
     }
@@ -431,21 +463,14 @@ int kpilqr_create(const kpilqr_dims *dims, void *stream, kpilqr_ctx **out)
     {
         int rcs = select_variants(c);                        // first: a fused context allocates no step records
         if (rcs == KPILQR_OK) rcs = size_buffers(c);
-        if (rcs != KPILQR_OK) { const std::string msg = c->err; kpilqr_destroy(c); return set_err(nullptr, rcs, msg); }
+        if (rcs >= 0) rcs = reserve(c, c->err_flag, sizeof(int), kExact, true);
+        if (rcs >= 0) rcs = reserve(c, c->kp_uniform, sizeof(int), kExact, true);
+        if (rcs >= 0) {
+            const hipError_t e = hipHostMalloc((void **)&c->err_flag_host, sizeof(int), hipHostMallocDefault);
+            if (e != hipSuccess) rcs = set_err(c, KPILQR_ERR_ALLOC, std::string("hipMalloc failed: ") + hipGetErrorString(e));
+        }
+        if (rcs < 0) { const std::string msg = c->err; kpilqr_destroy(c); return set_err(nullptr, rcs, msg); }
     }
-    hipError_t rc = hipSuccess;
-#define TRY(x) do { if (rc == hipSuccess) rc = (x); } while (0)
-    TRY(dalloc(&c->err_flag, 1));
-    TRY(dalloc(&c->kp_uniform, 1));
-    TRY(hipHostMalloc((void **)&c->err_flag_host, sizeof(int), hipHostMallocDefault));
-#undef TRY
-    if (rc != hipSuccess) {
-        std::string msg = std::string("hipMalloc failed: ") + hipGetErrorString(rc);
-        kpilqr_destroy(c);
-        return set_err(nullptr, KPILQR_ERR_ALLOC, msg);
-    }
-    (void)hipMemsetAsync(c->err_flag, 0, sizeof(int), c->stream);
-    (void)hipMemsetAsync(c->kp_uniform, 0, sizeof(int), c->stream);
     *out = c;
     return KPILQR_OK;
 }
@@ -463,11 +488,7 @@ void kpilqr_destroy(kpilqr_ctx *c)
         if (c->pipe_in) (void)hipEventDestroy(c->pipe_in);
     }
     comm_destroy(c);
-    void *ptrs[] = {c->rec, c->K, c->k, c->r, c->r_x, c->r_u, c->w_run, c->w_term, c->u_nom, c->ctrl_lim,
-                    c->lambda, c->alphas, c->cost_pred, c->delta_J, c->traj_cost, c->status, c->segmap,
-                    c->kp_offsets, c->kp_times, c->X_states, c->kp_thr, c->kp_mask, c->kp_count, c->ls8, c->fd_dev,
-                    c->stage, c->err_flag, c->kp_uniform, c->kpc, c->kp_entry, c->kp_entry_list, c->fdk_dev, c->rx_const, c->kps, c->segent};
-    for (void *p : ptrs) if (p) (void)hipFree(p);
+    c->for_each_buffer([](DevMem &b) { (void)release(b); });
     if (c->err_flag_host) (void)hipHostFree(c->err_flag_host);
     if (c->kp_traj_first_host) free(c->kp_traj_first_host);
     if (c->own_stream) (void)hipStreamDestroy(c->stream);
@@ -504,15 +525,14 @@ int kpilqr_resize(kpilqr_ctx *c, int new_dof, int new_num_ctrl, int new_horizon)
     }
     c->have_kp = c->kp_canonical = c->have_states = c->kp_known_uniform = false;
     c->njobs = c->nnom = 0;
-    c->fd_kind = 0; c->fdk_entries = 0; c->entry_tables_valid = false; c->kp_total_host = -1;
+    c->fd_payload = FdPayload::none; c->fdk_entries = 0; c->entry_tables_valid = false; c->kp_total_host = -1;
     if (c->kp_traj_first_host) { free(c->kp_traj_first_host); c->kp_traj_first_host = nullptr; }
     payload_changed(c);
     c->ru_zero = true;                                   // size_buffers zeroed r_u
     c->rx_const_on = false; c->rx_buf_valid = true;
-    if (c->X_states) { KP_HIP(c, hipFree(c->X_states)); c->X_states = nullptr; }
-    if (c->kp_mask) { KP_HIP(c, hipFree(c->kp_mask)); c->kp_mask = nullptr; }
-    if (c->kp_count) { KP_HIP(c, hipFree(c->kp_count)); c->kp_count = nullptr; }
-    if (c->kp_thr) { KP_HIP(c, hipFree(c->kp_thr)); c->kp_thr = nullptr; }
+    // the key-point placement buffers were sized by the old shape: they are allocated again on first use
+    DevMem *const placement[] = {&c->X_states, &c->kp_mask, &c->kp_count, &c->kp_thr};
+    for (DevMem *b : placement) KP_HIP(c, release(*b));
     return KPILQR_OK;
 }
 
@@ -623,11 +643,7 @@ int kpilqr_set_keypoints(kpilqr_ctx *c, const int *kp_offsets, const int *kp_tim
             uniform = (o[i + 1] - o[i] == len0) && memcmp(kp_times + o[i], kp_times + o[0], sizeof(int) * (size_t)len0) == 0;
     }
     c->kp_known_uniform = uniform && c->tune.fused_uni != 0;     // (KPILQR_FUSED_UNI=0: the general forms run on every set)
-    if ((size_t)total > c->kp_cap) {
-        if (c->kp_times) { KP_HIP(c, hipStreamSynchronize(c->stream)); KP_HIP(c, hipFree(c->kp_times)); c->kp_times = nullptr; }
-        c->kp_cap = (size_t)total + (size_t)total / 4 + 64;
-        KP_HIP(c, dalloc(&c->kp_times, c->kp_cap));
-    }
+    { const int rcg = reserve(c, c->kp_times, (size_t)total * sizeof(int), Slack{4, 64 * sizeof(int)}, false); if (rcg < 0) return rcg; }
     KP_HIP(c, hipMemcpyAsync(c->kp_offsets, kp_offsets, (nlists + 1) * sizeof(int), hipMemcpyHostToDevice, c->stream));
     KP_HIP(c, hipMemcpyAsync(c->kp_times, kp_times, (size_t)total * sizeof(int), hipMemcpyHostToDevice, c->stream));
     KP_HIP(c, launch_build_segmap(c));
@@ -635,19 +651,10 @@ int kpilqr_set_keypoints(kpilqr_ctx *c, const int *kp_offsets, const int *kp_tim
     // pageable host arrays: make the copies complete before returning control (pinned ones are read in place)
     if (!(is_pinned(kp_offsets) && is_pinned(kp_times))) KP_HIP(c, hipStreamSynchronize(c->stream));
     c->have_kp = true;
-    // host copy of the first CSR entry of every trajectory (chunking of a key-point ordered payload), and everything that
-    // was derived from the old lists is stale; a key-point ordered payload is laid out BY the lists: it has to follow them
-    c->kp_total_host = total;
-    if (!c->kp_traj_first_host) c->kp_traj_first_host = (int *)malloc(sizeof(int) * ((size_t)c->d.batch + 1));
-    if (!c->kp_traj_first_host) return set_err(c, KPILQR_ERR_ALLOC, "host allocation failed");
-    for (int b = 0; b <= c->d.batch; b++) c->kp_traj_first_host[b] = kp_offsets[(size_t)b * c->d.dof];
-    c->entry_tables_valid = false;
-    if (c->fd_kind == 2 || c->fd_kind == 3) { c->fd_kind = 0; c->fdk_entries = 0; }
-    payload_changed(c);
+    keypoints_changed(c, total);
+    if (!remember_traj_first(c, kp_offsets)) return set_err(c, KPILQR_ERR_ALLOC, "host allocation failed");
     return KPILQR_OK;
 }
-
-static int ensure_stage(kpilqr_ctx *c, size_t bytes);
 
 // ---- key-point placement on the device ----------------------------------------------------------------
 int kpilqr_upload_states(kpilqr_ctx *c, const double *X)
@@ -655,7 +662,7 @@ int kpilqr_upload_states(kpilqr_ctx *c, const double *X)
     if (!c || !X) return KPILQR_ERR_ARG;
     KP_ENTER(c);
     const size_t count = (size_t)c->d.batch * c->d.T * c->n;
-    if (!c->X_states) KP_HIP(c, hipMalloc((void **)&c->X_states, count * sizeof(double)));
+    { const int rcg = reserve(c, c->X_states, count * sizeof(double), kExact, false); if (rcg < 0) return rcg; }
     KP_HIP(c, hipMemcpyAsync(c->X_states, X, count * sizeof(double), hipMemcpyHostToDevice, c->stream));
     c->have_states = true;
     return KPILQR_OK;
@@ -677,17 +684,14 @@ int kpilqr_generate_keypoints(kpilqr_ctx *c, const char *method, int min_N, int 
     if (mth != 0 && (!thresholds || (mth == 1 && !(dt > 0.0)))) return set_err(c, KPILQR_ERR_ARG, "thresholds (and, for adaptive_jerk, a positive dt) are required");
     if (mth != 0 && !c->have_states) return set_err(c, KPILQR_ERR_STATE, "kpilqr_generate_keypoints before kpilqr_upload_states");
     const size_t nlists = (size_t)c->d.batch * c->d.dof, T = c->d.T, nchunks = (T + 63) / 64;
-    if (!c->kp_thr) KP_HIP(c, hipMalloc((void **)&c->kp_thr, sizeof(double) * c->d.dof));
-    if (!c->kp_mask) KP_HIP(c, hipMalloc((void **)&c->kp_mask, sizeof(unsigned long long) * nlists * nchunks));
-    if (!c->kp_count) KP_HIP(c, hipMalloc((void **)&c->kp_count, sizeof(int) * nlists));
-    if (!c->X_states) KP_HIP(c, hipMalloc((void **)&c->X_states, sizeof(double) * c->d.batch * T * c->n));   // set_interval never reads it
-    if (nlists * T > c->kp_cap) {            // worst case: every step a key-point
-        KP_HIP(c, hipStreamSynchronize(c->stream));
-        if (c->kp_times) KP_HIP(c, hipFree(c->kp_times));
-        c->kp_times = nullptr; c->kp_cap = 0;
-        KP_HIP(c, dalloc(&c->kp_times, nlists * T));
-        c->kp_cap = nlists * T;
-    }
+    const struct { DevMem *buf; size_t bytes; } rows[] = {
+        {&c->kp_thr, sizeof(double) * c->d.dof},
+        {&c->kp_mask, sizeof(unsigned long long) * nlists * nchunks},
+        {&c->kp_count, sizeof(int) * nlists},
+        {&c->X_states, sizeof(double) * c->d.batch * T * c->n},      // set_interval never reads it
+        {&c->kp_times, sizeof(int) * nlists * T},                    // worst case: every step a key-point
+    };
+    for (const auto &row : rows) { const int rcg = reserve(c, *row.buf, row.bytes, kExact, false); if (rcg < 0) return rcg; }
     if (thresholds) {
         KP_HIP(c, hipMemcpyAsync(c->kp_thr, thresholds, sizeof(double) * c->d.dof, hipMemcpyHostToDevice, c->stream));
         KP_HIP(c, hipStreamSynchronize(c->stream));       // the host array may be pageable
@@ -706,12 +710,9 @@ int kpilqr_generate_keypoints(kpilqr_ctx *c, const char *method, int min_N, int 
         KP_HIP(c, hipMemcpyAsync(&total, c->kp_offsets + nlists, sizeof(int), hipMemcpyDeviceToHost, c->stream));
         KP_HIP(c, hipStreamSynchronize(c->stream));
         if (total < 0 || (size_t)total > nlists * T) return set_err(c, KPILQR_ERR_HIP, "kpilqr_generate_keypoints: implausible key-point count read back");
-        c->kp_total_host = total;
+        keypoints_changed(c, total);
     }
     if (c->kp_traj_first_host) { free(c->kp_traj_first_host); c->kp_traj_first_host = nullptr; }
-    c->entry_tables_valid = false;
-    if (c->fd_kind == 2 || c->fd_kind == 3) { c->fd_kind = 0; c->fdk_entries = 0; }
-    payload_changed(c);
     return KPILQR_OK;
 }
 
@@ -725,8 +726,8 @@ int kpilqr_keypoint_error_test(kpilqr_ctx *c, int n_iv, const int *intervals, in
     if (rc) return rc;
     rc = ensure_records(c);                  // a fused context: records on demand, with the resident payload's columns
     if (rc) return rc;
-    int *iv_dev = (int *)c->stage;
-    unsigned char *good_dev = (unsigned char *)c->stage + off;
+    int *iv_dev = (int *)c->stage.p;
+    unsigned char *good_dev = (unsigned char *)c->stage.p + off;
     KP_HIP(c, hipMemcpyAsync(iv_dev, intervals, iv_bytes, hipMemcpyHostToDevice, c->stream));
     KP_HIP(c, launch_kp_error_test(c, n_iv, iv_dev, min_N, threshold, good_dev));
     KP_HIP(c, hipMemcpyAsync(good, good_dev, (size_t)n_iv, hipMemcpyDeviceToHost, c->stream));
@@ -745,8 +746,7 @@ int kpilqr_get_keypoints(kpilqr_ctx *c, int *kp_offsets, int *kp_times, int time
     KP_HIP(c, hipStreamSynchronize(c->stream));
     const int total = kp_offsets[nlists];
     c->kp_total_host = total;
-    if (!c->kp_traj_first_host) c->kp_traj_first_host = (int *)malloc(sizeof(int) * ((size_t)c->d.batch + 1));
-    if (c->kp_traj_first_host) for (int b = 0; b <= c->d.batch; b++) c->kp_traj_first_host[b] = kp_offsets[(size_t)b * c->d.dof];
+    (void)remember_traj_first(c, kp_offsets);          // (without it a streamed entry-ordered payload is refused, nothing else)
     if (kp_times) {
         if (total > times_capacity) return set_err(c, KPILQR_ERR_ARG, "kp_times capacity too small");
         KP_HIP(c, hipMemcpyAsync(kp_times, c->kp_times, (size_t)total * sizeof(int), hipMemcpyDeviceToHost, c->stream));
@@ -783,14 +783,8 @@ int kpilqr_fd_slab_layout(kpilqr_ctx *c, int njobs, int nnom, kpilqr_fd_layout *
 static int fd_bind(kpilqr_ctx *c, int njobs, int nnom, kpilqr_fd_layout *L)
 {
     fd_layout(c->n, njobs, nnom, L);
-    if (L->bytes > c->fd_dev_cap) {
-        KP_HIP(c, hipStreamSynchronize(c->stream));
-        if (c->fd_dev) KP_HIP(c, hipFree(c->fd_dev));
-        c->fd_dev = nullptr; c->fd_dev_cap = 0;
-        const size_t cap = L->bytes + L->bytes / 8 + 4096;
-        KP_HIP(c, hipMalloc((void **)&c->fd_dev, cap));
-        c->fd_dev_cap = cap;
-    }
+    const int rc = reserve(c, c->fd_dev, L->bytes, kEighth, false);
+    if (rc < 0) return rc;
     char *base = c->fd_dev;
     c->xplus = (double *)(base + L->xplus); c->xminus = (double *)(base + L->xminus); c->xnom = (double *)(base + L->xnom);
     c->job_b = (int *)(base + L->job_b); c->job_t = (int *)(base + L->job_t); c->job_col = (int *)(base + L->job_col);
@@ -828,7 +822,7 @@ int kpilqr_upload_fd(kpilqr_ctx *c, int njobs, const int *job_b, const int *job_
     }
     if (nnom) KP_HIP(c, hipMemcpyAsync(c->xnom, xnom, (size_t)nnom * n * sizeof(double), hipMemcpyHostToDevice, c->stream));
     c->njobs = njobs; c->nnom = nnom; c->eps = eps;
-    c->fd_kind = 1; payload_changed(c);
+    c->fd_payload = FdPayload::jobs; payload_changed(c);
     // pageable sources: the caller may free them on return, so wait for the copies; pinned ones are read in place
     if (!(is_pinned(job_b) && is_pinned(job_t) && is_pinned(job_col) && is_pinned(job_mode) && is_pinned(job_nom) &&
           is_pinned(xplus) && is_pinned(xminus) && is_pinned(xnom)))
@@ -846,7 +840,7 @@ int kpilqr_upload_fd_slab(kpilqr_ctx *c, const void *slab, int njobs, int nnom, 
     if (rc) return rc;
     if (njobs) KP_HIP(c, hipMemcpyAsync(c->fd_dev, slab, L.bytes, hipMemcpyHostToDevice, c->stream));   // the one DMA
     c->njobs = njobs; c->nnom = nnom; c->eps = eps;
-    c->fd_kind = 1; payload_changed(c);
+    c->fd_payload = FdPayload::jobs; payload_changed(c);
     if (!is_pinned(slab)) KP_HIP(c, hipStreamSynchronize(c->stream));
     return KPILQR_OK;
 }
@@ -870,9 +864,8 @@ int kpilqr_fd_kp_layout(kpilqr_ctx *c, int entries, kpilqr_fdkp_layout *out)
 static int fdk_bind(kpilqr_ctx *c, int entries, kpilqr_fdkp_layout *L)
 {
     fdkp_layout(c->n, entries, L);
-    const int rc = grow_dev(c, (void **)&c->fdk_dev, &c->fdk_dev_cap, L->bytes + L->bytes / 8 + 4096, false);
-    if (rc < 0) return rc;
-    return KPILQR_OK;
+    const int rc = reserve(c, c->fdk_dev, L->bytes, kEighth, false);
+    return rc < 0 ? rc : KPILQR_OK;
 }
 
 int kpilqr_upload_fd_kp(kpilqr_ctx *c, const void *slab, int entries, double eps)
@@ -889,12 +882,12 @@ int kpilqr_upload_fd_kp(kpilqr_ctx *c, const void *slab, int entries, double eps
     if (rc) return rc;
     if (entries) KP_HIP(c, hipMemcpyAsync(c->fdk_dev, slab, L.bytes, hipMemcpyHostToDevice, c->stream));   // the one DMA
     c->fdk_entries = entries; c->fdk_first = 0; c->eps = eps;
-    c->fd_kind = 2; payload_changed(c);
+    c->fd_payload = FdPayload::kp_ordered; payload_changed(c);
     if (!is_pinned(slab)) KP_HIP(c, hipStreamSynchronize(c->stream));
     return KPILQR_OK;
 }
 
-// The differenced key-point columns as the payload (fd_kind 3): straight into the column store
+// The differenced key-point columns as the payload (FdPayload::kp_columns): straight into the column store
 int kpilqr_upload_kp_columns(kpilqr_ctx *c, const double *columns, int entries)
 {
     if (!c || entries < 0 || (entries > 0 && !columns)) return KPILQR_ERR_ARG;
@@ -905,7 +898,7 @@ int kpilqr_upload_kp_columns(kpilqr_ctx *c, const double *columns, int entries)
     int rc = ensure_kpc(c);
     if (rc) return rc;
     if (entries) KP_HIP(c, hipMemcpyAsync(c->kpc, columns, (size_t)entries * 3 * c->n * 8, hipMemcpyHostToDevice, c->stream));
-    c->fd_kind = 3; c->fdk_entries = entries; c->fdk_first = 0;      // (the entry range, as for the key-point ordered payload)
+    c->fd_payload = FdPayload::kp_columns; c->fdk_entries = entries; c->fdk_first = 0;      // (the entry range, as for the key-point ordered payload)
     payload_changed(c);
     c->kpc_valid = true;
     if (!is_pinned(columns)) KP_HIP(c, hipStreamSynchronize(c->stream));
@@ -996,7 +989,7 @@ int kpilqr_upload_residual_jacobians_const(kpilqr_ctx *c, const double *r_x, con
     if (!c || !r_x) return KPILQR_ERR_ARG;
     KP_ENTER(c);
     const size_t n = c->n, m = c->d.m, nr = c->d.nr, reps = (size_t)c->d.batch * (c->d.T + 1);
-    { const int rcg = grow_dev(c, (void **)&c->rx_const, &c->rx_const_cap, nr * n * 8, false); if (rcg < 0) return rcg; }
+    { const int rcg = reserve(c, c->rx_const, nr * n * 8, kExact, false); if (rcg < 0) return rcg; }
     KP_HIP(c, hipMemcpyAsync(c->rx_const, r_x, nr * n * 8, hipMemcpyHostToDevice, c->stream));
     c->rx_const_on = true; c->rx_buf_valid = false;
     if (r_u) {                                   // dense control residuals: streamed from the (broadcast) buffer like r_x then
@@ -1054,7 +1047,7 @@ static int run_backward(kpilqr_ctx *c, int pd_stride)
         // itself and leaves kpc behind for the forward sweep -- no differencing kernel.  (It may stop at a failed PD check, so it
         // never marks kpc valid: another backward pass on the same payload differences again.)  Otherwise the payload is
         // differenced into kpc first, once, and the sweeps read kpc.
-        const FusedLaunch plan = c->last_bwd = plan_backward_fused(c, !c->kpc_valid && c->fd_kind == 2 && c->tune.fused_raw != 0);
+        const FusedLaunch plan = c->last_bwd = plan_backward_fused(c, !c->kpc_valid && c->fd_payload == FdPayload::kp_ordered && c->tune.fused_raw != 0);
         if (!plan.rxc) { rc = ensure_rx_buffer(c); if (rc) return rc; }       // (the sweep streams r_x: a constant one needs its broadcast copy)
         if (plan.raw) {
             KP_HIP(c, launch_backward_fused(c, plan, pd_stride));
@@ -1071,10 +1064,12 @@ static int run_backward(kpilqr_ctx *c, int pd_stride)
     }
     c->last_bwd = FusedLaunch{};       // (no plan: not a fused launch, and the tiled a6 sweep streams r_x)
     if (c->tiled_a6) { const int rc = ensure_rx_buffer(c); if (rc) return rc; }
-    if (strcmp(c->bwd_variant, "mfma_f64_t1") == 0) KP_HIP(c, launch_backward_mfma(c, pd_stride));
-    else if (strncmp(c->bwd_variant, "mfma_f64_tiled", 14) == 0) KP_HIP(c, launch_backward_tiled(c, pd_stride));
-    else if (strcmp(c->bwd_variant, "mfma_f64_wide") == 0) KP_HIP(c, launch_backward_wide(c, pd_stride));
-    else KP_HIP(c, launch_backward_generic(c, pd_stride));
+    switch (c->bwd_family) {
+    case Family::t1: KP_HIP(c, launch_backward_mfma(c, pd_stride)); break;
+    case Family::tiled: KP_HIP(c, launch_backward_tiled(c, pd_stride)); break;
+    case Family::wide: KP_HIP(c, launch_backward_wide(c, pd_stride)); break;
+    default: KP_HIP(c, launch_backward_generic(c, pd_stride)); break;
+    }
     return KPILQR_OK;
 }
 
@@ -1116,7 +1111,7 @@ int kpilqr_backward_stats(kpilqr_ctx *c, int pd_check_stride, int *hist)
     const size_t bytes = (size_t)c->d.batch * 6 * sizeof(int);
     rc = ensure_stage(c, bytes);
     if (rc) return rc;
-    KP_HIP(c, launch_backward_fused_stats(c, pd_check_stride, (int *)c->stage));
+    KP_HIP(c, launch_backward_fused_stats(c, pd_check_stride, (int *)c->stage.p));
     KP_HIP(c, hipMemcpyAsync(hist, c->stage, bytes, hipMemcpyDeviceToHost, c->stream));
     return sync_and_report(c);
 }
@@ -1170,17 +1165,6 @@ int kpilqr_upload_nominal(kpilqr_ctx *c, const double *u_nom, const double *ctrl
     return KPILQR_OK;
 }
 
-static int ensure_stage(kpilqr_ctx *c, size_t bytes)
-{
-    if (bytes <= c->stage_cap) return KPILQR_OK;
-    KP_HIP(c, hipStreamSynchronize(c->stream));
-    if (c->stage) KP_HIP(c, hipFree(c->stage));
-    c->stage = nullptr; c->stage_cap = 0;
-    KP_HIP(c, hipMalloc((void **)&c->stage, bytes));
-    c->stage_cap = bytes;
-    return KPILQR_OK;
-}
-
 static int run_forward(kpilqr_ctx *c, double *U_dev)
 {
     if (c->fused) {
@@ -1200,10 +1184,12 @@ static int run_forward(kpilqr_ctx *c, double *U_dev)
     }
     c->last_fwd = FusedLaunch{};
     if (c->tiled_a6) { const int rc = ensure_rx_buffer(c); if (rc) return rc; }
-    if (strcmp(c->fwd_variant, "mfma_f64_t1") == 0) KP_HIP(c, launch_forward_mfma(c, U_dev));
-    else if (strncmp(c->fwd_variant, "mfma_f64_tiled", 14) == 0) KP_HIP(c, launch_forward_tiled(c, U_dev));
-    else if (strcmp(c->fwd_variant, "mfma_f64_wide") == 0) KP_HIP(c, launch_forward_wide(c, U_dev));
-    else KP_HIP(c, launch_forward_generic(c, U_dev));
+    switch (c->fwd_family) {
+    case Family::t1: KP_HIP(c, launch_forward_mfma(c, U_dev)); break;
+    case Family::tiled: KP_HIP(c, launch_forward_tiled(c, U_dev)); break;
+    case Family::wide: KP_HIP(c, launch_forward_wide(c, U_dev)); break;
+    default: KP_HIP(c, launch_forward_generic(c, U_dev)); break;
+    }
     return KPILQR_OK;
 }
 
@@ -1264,14 +1250,15 @@ static int pipe_setup(kpilqr_ctx *c)
 static void make_view(const kpilqr_ctx *c, int b0, int nb, hipStream_t s, kpilqr_ctx *v)
 {
     *v = *c;
+    v->is_view = true;             // it borrows the context's buffers: reserve() refuses to grow one through it
     const size_t T = c->d.T, n = c->n, m = c->d.m, nr = c->d.nr, na = c->d.n_alpha, dof = c->d.dof, o = (size_t)b0;
     v->d.batch = nb; v->stream = s; v->own_stream = false;
-    if (v->rec) v->rec += o * T * c->L.stride;
-    v->K += o * T * n * m; v->k += o * T * m;
-    v->r += o * (T + 1) * nr; v->r_x += o * (T + 1) * nr * n; v->r_u += o * (T + 1) * nr * m;
-    v->u_nom += o * T * m; v->lambda += o; v->cost_pred += o * na; v->delta_J += o; v->traj_cost += o; v->status += o;
-    v->segmap += o * dof * T; v->kp_offsets += o * dof;
-    if (v->segent) v->segent += o * dof * T;
+    if (v->rec) v->rec.shift(o * T * c->L.stride);
+    v->K.shift(o * T * n * m); v->k.shift(o * T * m);
+    v->r.shift(o * (T + 1) * nr); v->r_x.shift(o * (T + 1) * nr * n); v->r_u.shift(o * (T + 1) * nr * m);
+    v->u_nom.shift(o * T * m); v->lambda.shift(o); v->cost_pred.shift(o * na); v->delta_J.shift(o); v->traj_cost.shift(o); v->status.shift(o);
+    v->segmap.shift(o * dof * T); v->kp_offsets.shift(o * dof);
+    if (v->segent) v->segent.shift(o * dof * T);
     if (c->kp_traj_first_host) { v->fdk_first = c->kp_traj_first_host[b0]; v->kp_view_entries = c->kp_traj_first_host[b0 + nb] - v->fdk_first; }
     long long share = (long long)c->n_simd * nb / c->d.batch;
     v->n_simd = share < 4 ? 4 : (int)share;
@@ -1339,10 +1326,10 @@ int kpilqr_iterate_streamed(kpilqr_ctx *c, const kpilqr_stream_io *io, int pd_ch
         // are the same; when the layout or the per-trajectory offsets differ from the iteration still in flight, the
         // new uploads could overwrite regions another chunk stream is still differencing -- so the pipeline is joined
         // first (every chunk stream then starts behind everything enqueued so far, through pipe_in below).
-        kpilqr_fd_layout probe;
-        fd_layout(n, io->njobs, io->nnom, &probe);
-        if (c->pipe_dirty && (sig != c->pipe_sig || probe.bytes > c->fd_dev_cap)) { rc = join_pipeline(c); if (rc) return rc; }
-        if (probe.bytes > c->fd_dev_cap)                           // a growth frees the old slab: nothing may still read it
+        fd_layout(n, io->njobs, io->nnom, &L);
+        const bool grows = would_grow(c->fd_dev, L.bytes);
+        if (c->pipe_dirty && (sig != c->pipe_sig || grows)) { rc = join_pipeline(c); if (rc) return rc; }
+        if (grows)                                                 // a growth frees the old slab: nothing may still read it
             for (int i = 0; i < Ctx::kPipeStreams; i++) KP_HIP(c, hipStreamSynchronize(c->pipe_stream[i]));
         rc = fd_bind(c, io->njobs, io->nnom, &L);
         if (rc) return rc;
@@ -1354,9 +1341,8 @@ int kpilqr_iterate_streamed(kpilqr_ctx *c, const kpilqr_stream_io *io, int pd_ch
     if (kslab) {
         // a chunk's payload lands at its trajectories' entry range, which only the key-points decide: same-stream order
         // protects it from the next iteration's uploads (new key-points go through KP_ENTER, which joins the pipeline)
-        kpilqr_fdkp_layout probe;
-        fdkp_layout(n, io->entries, &probe);
-        if (probe.bytes + probe.bytes / 8 + 4096 > c->fdk_dev_cap && c->pipe_ready) {
+        fdkp_layout(n, io->entries, &LK);
+        if (would_grow(c->fdk_dev, LK.bytes)) {                 // as for the job-list slab
             rc = join_pipeline(c); if (rc) return rc;
             for (int i = 0; i < Ctx::kPipeStreams; i++) KP_HIP(c, hipStreamSynchronize(c->pipe_stream[i]));
         }
@@ -1365,12 +1351,13 @@ int kpilqr_iterate_streamed(kpilqr_ctx *c, const kpilqr_stream_io *io, int pd_ch
         c->fdk_entries = io->entries; c->fdk_first = 0; c->eps = io->eps;
     }
     const double *kcols = io->kp_columns;
-    if (slab) c->fd_kind = 1;
-    if (kslab) c->fd_kind = 2;
-    if (kcols) { c->fd_kind = 3; c->fdk_entries = io->entries; c->fdk_first = 0; }
-    if (slab || kslab || kcols) payload_changed(c);
-    // allocations and tables the chunks need are made HERE, on the context: a view never allocates
-    if (c->fused || c->fd_kind == 2 || c->fd_kind == 3) {
+    const bool new_payload = slab || kslab || kcols;
+    if (slab) c->fd_payload = FdPayload::jobs;
+    if (kslab) c->fd_payload = FdPayload::kp_ordered;
+    if (kcols) { c->fd_payload = FdPayload::kp_columns; c->fdk_entries = io->entries; c->fdk_first = 0; }
+    if (new_payload) payload_changed(c);
+    // allocations and tables the chunks need are made HERE, on the context: a view never allocates (reserve refuses)
+    if (c->fused || payload_by_entry(c)) {
         rc = ensure_kpc(c); if (rc) return rc;
         rc = ensure_entry_tables(c); if (rc) return rc;
     }
@@ -1385,7 +1372,7 @@ int kpilqr_iterate_streamed(kpilqr_ctx *c, const kpilqr_stream_io *io, int pd_ch
     // No new payload, but the column store of the resident one is stale (key-points changed since a job-list upload): a chunk
     // view has no jobs (its njobs is 0), so the payload is re-differenced HERE, on the context, for the whole batch -- what
     // kpilqr_iterate would do.  (A key-point ordered payload is dropped by new key-points; the chunks handle a resident one.)
-    if (c->fused && !slab && !kslab && !kcols && !c->kpc_valid && c->fd_kind == 1) {
+    if (c->fused && !new_payload && !c->kpc_valid && c->fd_payload == FdPayload::jobs) {
         rc = difference_to_kpc(c); if (rc) return rc;
     }
     // Per-step Jacobians in this call end the constant mode -- recorded only HERE, behind every check that can still reject the
@@ -1446,7 +1433,7 @@ int kpilqr_iterate_streamed(kpilqr_ctx *c, const kpilqr_stream_io *io, int pd_ch
         } else {
             // no new FD payload: what was differenced before is reused (kpc / the records' key-point columns)
             v.njobs = 0;
-            if ((c->fd_kind == 2 || c->fd_kind == 3) && c->kp_traj_first_host) {
+            if (payload_by_entry(c) && c->kp_traj_first_host) {
                 v.fdk_first = c->kp_traj_first_host[b0]; v.fdk_entries = c->kp_traj_first_host[b1] - v.fdk_first;
             }
         }
@@ -1457,16 +1444,10 @@ int kpilqr_iterate_streamed(kpilqr_ctx *c, const kpilqr_stream_io *io, int pd_ch
         if (io->lambda) KP_HIP(c, h2d(v.lambda, io->lambda + o, cnt * 8, s));
         // ---- kernels of the chunk --------------------------------------------------------------------------------
         if (!c->fused) {
-            // a new key-point ordered / column payload: the chunk's records in one pass; else the payload's key-point columns into
-            // the records (none new: they hold them already) and k_interpolate
-            if ((kslab || kcols) && linearise_one_pass(&v)) {
-                KP_HIP(c, launch_fd_kp_interpolate(&v));
-                c->last_linearise = kcols ? "kp_columns_interpolate" : "fd_kp_interpolate";
-            } else {
-                if (slab || kslab || kcols) { rc = records_from_payload(&v); if (rc) { c->err = v.err; return rc; } }
-                KP_HIP(c, launch_interpolate(&v));
-                c->last_linearise = "fd_difference+interpolate";
-            }
+            // (no new payload: the records hold its key-point columns already)
+            rc = linearise(&v, new_payload);
+            if (rc) { c->err = v.err; return rc; }
+            c->last_linearise = v.last_linearise;
             if (!c->tiled_a6) KP_HIP(c, launch_cost_derivs(&v));
         }
         rc = run_backward(&v, pd_check_stride);
@@ -1513,7 +1494,7 @@ int kpilqr_allreduce_linesearch(kpilqr_ctx *c, double vec8[8])
 {
     if (!c) return KPILQR_ERR_ARG;
     KP_ENTER(c);
-    if (!c->ls8) KP_HIP(c, hipMalloc((void **)&c->ls8, 8 * sizeof(double)));
+    { const int rcg = reserve(c, c->ls8, 8 * sizeof(double), kExact, false); if (rcg < 0) return rcg; }
     KP_HIP(c, launch_pack_linesearch(c, c->ls8));
     if (const char *e = comm_allreduce8(c, c->ls8)) return set_err(c, KPILQR_ERR_HIP, std::string("RCCL: ") + e);
     if (vec8) KP_HIP(c, hipMemcpyAsync(vec8, c->ls8, 8 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
@@ -1521,19 +1502,47 @@ int kpilqr_allreduce_linesearch(kpilqr_ctx *c, double vec8[8])
 }
 
 // ---- debug / oracle hooks -------------------------------------------------------------------------
+// Staging of the reference layout, shared by each set / get pair: the records exist (a fused context materialises them), and the
+// staging area holds the arrays one behind the other -- A | B, or l_x | l_xx | l_u | l_uu
+struct Staged { size_t bytes[4]; double *dev[4]; };
+
+static int stage_arrays(kpilqr_ctx *c, int count, Staged *s)
+{
+    if (c->fused) { const int rc = ensure_records(c); if (rc) return rc; }
+    size_t total = 0;
+    for (int i = 0; i < count; i++) total += s->bytes[i];
+    const int rc = ensure_stage(c, total);
+    if (rc) return rc;
+    size_t off = 0;
+    for (int i = 0; i < count; i++) { s->dev[i] = c->stage + off / 8; off += s->bytes[i]; }
+    return KPILQR_OK;
+}
+
+static int stage_AB(kpilqr_ctx *c, Staged *s)
+{
+    const size_t BT = (size_t)c->d.batch * c->d.T, n = c->n, m = c->d.m;
+    *s = Staged{{BT * n * n * 8, BT * n * m * 8}, {}};
+    return stage_arrays(c, 2, s);
+}
+
+static int stage_cost(kpilqr_ctx *c, Staged *s)
+{
+    const size_t BT = (size_t)c->d.batch * c->d.T, n = c->n, m = c->d.m;
+    *s = Staged{{BT * n * 8, BT * n * n * 8, BT * m * 8, BT * m * m * 8}, {}};
+    return stage_arrays(c, 4, s);
+}
+
 int kpilqr_set_AB(kpilqr_ctx *c, const double *A, const double *B)
 {
     if (!c) return KPILQR_ERR_ARG;
     KP_ENTER(c);
-    if (c->fused) { const int rcr = ensure_records(c); if (rcr) return rcr; }
-    const size_t BT = (size_t)c->d.batch * c->d.T, n = c->n, m = c->d.m;
-    const size_t szA = BT * n * n * 8, szB = BT * n * m * 8;
-    int rc = ensure_stage(c, szA + szB);
+    Staged s;
+    const int rc = stage_AB(c, &s);
     if (rc) return rc;
-    double *dA = c->stage, *dB = (double *)((char *)c->stage + szA);
-    if (A) KP_HIP(c, hipMemcpyAsync(dA, A, szA, hipMemcpyHostToDevice, c->stream));
-    if (B) KP_HIP(c, hipMemcpyAsync(dB, B, szB, hipMemcpyHostToDevice, c->stream));
-    KP_HIP(c, launch_pack_AB(c, A ? dA : nullptr, B ? dB : nullptr));
+    const double *src[2] = {A, B};
+    for (int i = 0; i < 2; i++)
+        if (src[i]) KP_HIP(c, hipMemcpyAsync(s.dev[i], src[i], s.bytes[i], hipMemcpyHostToDevice, c->stream));
+    KP_HIP(c, launch_pack_AB(c, A ? s.dev[0] : nullptr, B ? s.dev[1] : nullptr));
     KP_HIP(c, hipStreamSynchronize(c->stream));
     return KPILQR_OK;
 }
@@ -1542,15 +1551,13 @@ int kpilqr_get_AB(kpilqr_ctx *c, double *A, double *B)
 {
     if (!c) return KPILQR_ERR_ARG;
     KP_ENTER(c);
-    if (c->fused) { const int rcr = ensure_records(c); if (rcr) return rcr; }
-    const size_t BT = (size_t)c->d.batch * c->d.T, n = c->n, m = c->d.m;
-    const size_t szA = BT * n * n * 8, szB = BT * n * m * 8;
-    int rc = ensure_stage(c, szA + szB);
+    Staged s;
+    const int rc = stage_AB(c, &s);
     if (rc) return rc;
-    double *dA = c->stage, *dB = (double *)((char *)c->stage + szA);
-    KP_HIP(c, launch_unpack_AB(c, A ? dA : nullptr, B ? dB : nullptr));
-    if (A) KP_HIP(c, hipMemcpyAsync(A, dA, szA, hipMemcpyDeviceToHost, c->stream));
-    if (B) KP_HIP(c, hipMemcpyAsync(B, dB, szB, hipMemcpyDeviceToHost, c->stream));
+    KP_HIP(c, launch_unpack_AB(c, A ? s.dev[0] : nullptr, B ? s.dev[1] : nullptr));
+    double *dst[2] = {A, B};
+    for (int i = 0; i < 2; i++)
+        if (dst[i]) KP_HIP(c, hipMemcpyAsync(dst[i], s.dev[i], s.bytes[i], hipMemcpyDeviceToHost, c->stream));
     return sync_and_report(c);
 }
 
@@ -1558,18 +1565,13 @@ int kpilqr_set_cost_derivs(kpilqr_ctx *c, const double *l_x, const double *l_xx,
 {
     if (!c) return KPILQR_ERR_ARG;
     KP_ENTER(c);
-    if (c->fused) { const int rcr = ensure_records(c); if (rcr) return rcr; }
-    const size_t BT = (size_t)c->d.batch * c->d.T, n = c->n, m = c->d.m;
-    const size_t s1 = BT * n * 8, s2 = BT * n * n * 8, s3 = BT * m * 8, s4 = BT * m * m * 8;
-    int rc = ensure_stage(c, s1 + s2 + s3 + s4);
+    Staged s;
+    const int rc = stage_cost(c, &s);
     if (rc) return rc;
-    char *base = (char *)c->stage;
-    double *d1 = (double *)base, *d2 = (double *)(base + s1), *d3 = (double *)(base + s1 + s2), *d4 = (double *)(base + s1 + s2 + s3);
-    if (l_x) KP_HIP(c, hipMemcpyAsync(d1, l_x, s1, hipMemcpyHostToDevice, c->stream));
-    if (l_xx) KP_HIP(c, hipMemcpyAsync(d2, l_xx, s2, hipMemcpyHostToDevice, c->stream));
-    if (l_u) KP_HIP(c, hipMemcpyAsync(d3, l_u, s3, hipMemcpyHostToDevice, c->stream));
-    if (l_uu) KP_HIP(c, hipMemcpyAsync(d4, l_uu, s4, hipMemcpyHostToDevice, c->stream));
-    KP_HIP(c, launch_pack_cost(c, l_x ? d1 : nullptr, l_xx ? d2 : nullptr, l_u ? d3 : nullptr, l_uu ? d4 : nullptr));
+    const double *src[4] = {l_x, l_xx, l_u, l_uu};
+    for (int i = 0; i < 4; i++)
+        if (src[i]) KP_HIP(c, hipMemcpyAsync(s.dev[i], src[i], s.bytes[i], hipMemcpyHostToDevice, c->stream));
+    KP_HIP(c, launch_pack_cost(c, l_x ? s.dev[0] : nullptr, l_xx ? s.dev[1] : nullptr, l_u ? s.dev[2] : nullptr, l_uu ? s.dev[3] : nullptr));
     KP_HIP(c, hipStreamSynchronize(c->stream));
     return KPILQR_OK;
 }
@@ -1578,23 +1580,18 @@ int kpilqr_get_cost_derivs(kpilqr_ctx *c, double *l_x, double *l_xx, double *l_u
 {
     if (!c) return KPILQR_ERR_ARG;
     KP_ENTER(c);
-    if (c->fused) { const int rcr = ensure_records(c); if (rcr) return rcr; }
-    const size_t BT = (size_t)c->d.batch * c->d.T, n = c->n, m = c->d.m;
-    const size_t s1 = BT * n * 8, s2 = BT * n * n * 8, s3 = BT * m * 8, s4 = BT * m * m * 8;
-    int rc = ensure_stage(c, s1 + s2 + s3 + s4);
+    Staged s;
+    const int rc = stage_cost(c, &s);
     if (rc) return rc;
-    char *base = (char *)c->stage;
-    double *d1 = (double *)base, *d2 = (double *)(base + s1), *d3 = (double *)(base + s1 + s2), *d4 = (double *)(base + s1 + s2 + s3);
-    KP_HIP(c, launch_unpack_cost(c, l_x ? d1 : nullptr, l_xx ? d2 : nullptr, l_u ? d3 : nullptr, l_uu ? d4 : nullptr));
-    if (l_x) KP_HIP(c, hipMemcpyAsync(l_x, d1, s1, hipMemcpyDeviceToHost, c->stream));
-    if (l_xx) KP_HIP(c, hipMemcpyAsync(l_xx, d2, s2, hipMemcpyDeviceToHost, c->stream));
-    if (l_u) KP_HIP(c, hipMemcpyAsync(l_u, d3, s3, hipMemcpyDeviceToHost, c->stream));
-    if (l_uu) KP_HIP(c, hipMemcpyAsync(l_uu, d4, s4, hipMemcpyDeviceToHost, c->stream));
+    KP_HIP(c, launch_unpack_cost(c, l_x ? s.dev[0] : nullptr, l_xx ? s.dev[1] : nullptr, l_u ? s.dev[2] : nullptr, l_uu ? s.dev[3] : nullptr));
+    double *dst[4] = {l_x, l_xx, l_u, l_uu};
+    for (int i = 0; i < 4; i++)
+        if (dst[i]) KP_HIP(c, hipMemcpyAsync(dst[i], s.dev[i], s.bytes[i], hipMemcpyDeviceToHost, c->stream));
     return sync_and_report(c);
 }
 
-const char *kpilqr_backward_variant(kpilqr_ctx *c) { return c ? c->bwd_variant : ""; }
-const char *kpilqr_forward_variant(kpilqr_ctx *c) { return c ? c->fwd_variant : ""; }
+const char *kpilqr_backward_variant(kpilqr_ctx *c) { return c ? variant_name(c->bwd_family, c->tiled_a6) : ""; }
+const char *kpilqr_forward_variant(kpilqr_ctx *c) { return c ? variant_name(c->fwd_family, c->tiled_a6) : ""; }
 
 // What the last backward (which = 0) / forward (which = 1) launch of this context WAS: "<variant>" for the materialising
 // families; for the fused sweeps "<variant>:<waves>:<columns>:<lists>[:ru0][:rxc][:slopes]" with
@@ -1611,11 +1608,11 @@ const char *kpilqr_last_launch(kpilqr_ctx *c, int which)
     if (!c || which < 0 || which > 1) return "";
     std::string &out = c->launch_desc[which];
     const FusedLaunch &p = which == 0 ? c->last_bwd : c->last_fwd;
-    out = which == 0 ? c->bwd_variant : c->fwd_variant;
+    out = variant_name(which == 0 ? c->bwd_family : c->fwd_family, c->tiled_a6);
     if (p.waves == Waves::none) {
         if (c->fused) { out += ":none"; return out.c_str(); }
         // the two-tile forward sweep on materialised tiles: one wave per row tile, or state / cost wave groups (small batches)
-        if (which == 1 && strcmp(c->fwd_variant, "mfma_f64_tiled") == 0 && forward_tiled_sc_selected(c)) out += ":state_cost_waves";
+        if (which == 1 && c->fwd_family == Family::tiled && !c->tiled_a6 && forward_tiled_sc_selected(c)) out += ":state_cost_waves";
         return out.c_str();
     }
     int uni = 0;

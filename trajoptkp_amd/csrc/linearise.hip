@@ -105,12 +105,12 @@ hipError_t launch_fd_kp_interpolate(Ctx *c)
     int threads = ((ne / 2 + 63) / 64) * 64;
     if (threads > 256) threads = 256;
     const size_t lds = (sizeof(int2) + sizeof(int)) * c->d.dof * LIN_TT;
-    if (c->fd_kind == 3)
+    if (c->fd_payload == FdPayload::kp_columns)
         hipLaunchKernelGGL(k_fd_kp_interpolate<true>, grid, dim3(threads), lds, c->stream, c->L, c->d.dof, c->d.T, c->segmap, c->segent,
-                           (const double2 *)c->kpc, c->eps, c->rec);
+                           (const double2 *)c->kpc.p, c->eps, c->rec);
     else
         hipLaunchKernelGGL(k_fd_kp_interpolate<false>, grid, dim3(threads), lds, c->stream, c->L, c->d.dof, c->d.T, c->segmap, c->segent,
-                           (const double2 *)c->fdk_dev, c->eps, c->rec);
+                           (const double2 *)c->fdk_dev.p, c->eps, c->rec);
     return hipGetLastError();
 }
 
