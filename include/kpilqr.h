@@ -91,6 +91,30 @@ typedef struct {
                                            library may form only the cost derivatives inside the sweeps (variant
                                            "mfma_f64_tiled_a6": four-tile states from ~100 trajectories up); A and B
                                            are then still materialised and kpilqr_iterate skips kpilqr_cost_derivs. */
+#define KPILQR_FLAG_UNION_KEYPOINTS 8   /* Opt-in, together with KPILQR_FLAG_FUSED on a one-tile shape (n+2 <= 16); ignored
+                                           otherwise, the way FUSED is on an unsupported shape.  Per-DoF key-point lists
+                                           (velocity_change, adaptive_jerk, iterative_error) run the general forms of the fused
+                                           sweeps; with this flag kpilqr_backward / kpilqr_forward_linear / kpilqr_iterate give
+                                           every DoF of a trajectory the UNION of that trajectory's key-point times -- a column
+                                           at an inserted time is the interpolant kpilqr_interpolate writes at that step, bit
+                                           for bit -- so the lists are uniform and the segment-loop forms of the sweeps run on a
+                                           union column store (kpilqr_last_launch: "...:union").  The piecewise-linear A(t), B(t)
+                                           are the same functions; re-interpolating between union times instead of between a
+                                           DoF's own key-points changes roundings at the 1e-16 level (K, k, delta_J, predicted
+                                           costs within ~4e-15 relative of the per-DoF forms; the tests hold both to 1e-9 of the
+                                           oracle).  That difference is why kpilqr_get_keypoints, kpilqr_interpolate,
+                                           kpilqr_fd_interpolate and kpilqr_get_AB keep working on the CALLER's lists and keep
+                                           the reference's bits.  Cost: ONE wait for the stream per key-point change (the
+                                           per-trajectory union sizes, 4 * batch bytes, are read back to size the store), the
+                                           differencing and expansion kernels in front of the sweeps, and the union store:
+                                           dof * sum_b |U_b| entries of 3n doubles beside the column store's sum of the list
+                                           lengths (about 6x at lists on 7 % of the steps whose union covers 41 %).  Lists
+                                           the host knows to be uniform (kpilqr_set_keypoints saw equal lists, set_interval)
+                                           allocate and launch nothing of this.  kpilqr_backward_stats and
+                                           kpilqr_iterate_streamed ignore the flag.  The speed of the route rests on the byte
+                                           model of DESIGN.md section 9, not on a measurement (profiles/union_keypoints.txt
+                                           holds the procedure): the flag is off by default.  KPILQR_VERSION is unchanged: detect the
+                                           feature by the symbols kpilqr_get_union_keypoints / kpilqr_get_union_columns. */
 
 enum {
     KPILQR_OK = 0,
@@ -398,6 +422,16 @@ int  kpilqr_get_AB(kpilqr_ctx *ctx, double *A, double *B);
 int  kpilqr_set_cost_derivs(kpilqr_ctx *ctx, const double *l_x, const double *l_xx,
                             const double *l_u, const double *l_uu);
 int  kpilqr_get_cost_derivs(kpilqr_ctx *ctx, double *l_x, double *l_xx, double *l_u, double *l_uu);
+/* The union of KPILQR_FLAG_UNION_KEYPOINTS, read back.  Both calls build it on demand (also for lists known to be uniform, whose
+ * union is the list) and are synchronous; KPILQR_ERR_STATE when the flag is not active on this context (not set, or not a fused
+ * one-tile shape) or there are no key-points yet.
+ * kpilqr_get_union_keypoints: traj_offsets [batch+1] and ONE sorted list of union times per trajectory,
+ * times[traj_offsets[b] .. traj_offsets[b+1]); times may be NULL to query the size.  Returns the total count or an error (< 0).
+ * kpilqr_get_union_columns: the union column store [entry_u][3][n], entry_u = dof * traj_offsets[b] + d * |U_b| + j for
+ * (trajectory b, DoF d, j-th union time), kinds as for kpilqr_upload_kp_columns; needs a resident FD payload
+ * (KPILQR_ERR_STATE without one).  columns may be NULL to query the size.  Returns the number of union entries or an error. */
+int  kpilqr_get_union_keypoints(kpilqr_ctx *ctx, int *traj_offsets /*[batch+1]*/, int *times, int times_capacity);
+int  kpilqr_get_union_columns(kpilqr_ctx *ctx, double *columns, size_t capacity_doubles);
 
 /* Name of the kernel variant the backward / forward pass will launch for these dims
  * ("mfma_f64_t1", "generic_lds", ...): for logs, tests and the bench's roofline line. */
@@ -405,7 +439,7 @@ const char *kpilqr_backward_variant(kpilqr_ctx *ctx);
 const char *kpilqr_forward_variant(kpilqr_ctx *ctx);
 /* What the LAST backward (which = 0) / forward (which = 1) launch of this context was -- the variant above and, for the
  * KPILQR_FLAG_FUSED sweeps, the form the library picked from the batch size, the payload and the key-point lists:
- *     "<variant>:<waves>:<columns>:<lists>[:ru0][:rxc][:slopes]"          e.g. "mfma_f64_t1_fused:w1:raw:uni:ru0"
+ *     "<variant>:<waves>:<columns>:<lists>[:ru0][:rxc][:slopes][:union]"  e.g. "mfma_f64_t1_fused:w1:raw:uni:ru0"
  *   waves    w1 one wavefront per trajectory | pair | triple | pairh (backward: consumer / helper pair)
  *            (forward `pair` on a uniform set: state wave with its own interpolant + scoring wave)
  *   columns  (backward only) raw: the sweep differenced the key-point ordered FD payload itself | kpc: it read the differenced
@@ -414,6 +448,8 @@ const char *kpilqr_forward_variant(kpilqr_ctx *ctx);
  *   ru0      no control residuals (r_u never uploaded): the products with r_u are left out
  *   rxc      constant residual Jacobians kept in registers (kpilqr_upload_residual_jacobians_const)
  *   slopes   per-DoF lists walked on precomputed segment slopes (a crossing is loads only)
+ *   union    always last: the launch ran on the union store of KPILQR_FLAG_UNION_KEYPOINTS (`lists` is then the union's: uni),
+ *            e.g. "mfma_f64_t1_fused:w1:kpc:uni:ru0:rxc:union"
  * The `lists` token is decided on the device; this call reads the flag back and therefore WAITS for the context's stream.
  * which = 2: the linearisation stage (differencing + interpolation of A, B) of the last kpilqr_fd_interpolate, kpilqr_iterate or
  * kpilqr_iterate_streamed; does not wait.  "" before any of them (and in a library without kpilqr_fd_interpolate), else
@@ -421,6 +457,7 @@ const char *kpilqr_forward_variant(kpilqr_ctx *ctx);
  *     "kp_columns_interpolate"     column payload, one pass
  *     "fd_difference+interpolate"  the separate passes (job lists, or KPILQR_FD_INTERP=0)
  *     "in_sweep"                   KPILQR_FLAG_FUSED context: the sweeps difference and interpolate themselves
+ *     "kp_union"                   the same on the union store of KPILQR_FLAG_UNION_KEYPOINTS (kpilqr_iterate with per-DoF lists)
  * For logs and tests (a test can assert which kernel form it exercised).  version >= 400. */
 const char *kpilqr_last_launch(kpilqr_ctx *ctx, int which);
 

@@ -28,11 +28,11 @@ SYMBOLS = [
     "kpilqr_fd_slab_layout", "kpilqr_upload_fd_slab", "kpilqr_iterate_streamed", "kpilqr_resize",
     "kpilqr_keypoint_error_test", "kpilqr_fd_kp_layout", "kpilqr_upload_fd_kp", "kpilqr_backward_stats",
     "kpilqr_upload_kp_columns", "kpilqr_upload_residual_jacobians_const", "kpilqr_last_launch",
-    "kpilqr_fd_interpolate",
+    "kpilqr_fd_interpolate", "kpilqr_get_union_keypoints", "kpilqr_get_union_columns",
 ]
 # entry points added without a version bump (include/kpilqr.h: "detect the entry point by its symbol"): bound only when the library
 # has them -- KPILQR_LIB may name an older build of the same major version
-OPTIONAL_SYMBOLS = {"kpilqr_fd_interpolate"}
+OPTIONAL_SYMBOLS = {"kpilqr_fd_interpolate", "kpilqr_get_union_keypoints", "kpilqr_get_union_columns"}
 
 
 class Dims(C.Structure):
@@ -61,6 +61,7 @@ ABI_MAJOR = 4                  # KPILQR_VERSION / 100 of the include/kpilqr.h th
 FLAG_GENERIC_KERNELS = 1
 FLAG_TILED_KERNELS = 2
 FLAG_FUSED = 4
+FLAG_UNION_KEYPOINTS = 8       # with FLAG_FUSED on a one-tile shape: per-DoF lists re-sampled onto their trajectory's union
 
 BUF_STEP_RECORDS, BUF_K, BUF_k, BUF_RESIDUALS, BUF_R_X, BUF_R_U, BUF_U_NOM, BUF_FD_XPLUS, \
     BUF_FD_XMINUS, BUF_COST_PRED, BUF_DELTA_J, BUF_STATUS = range(12)
@@ -143,6 +144,9 @@ def load():
     L.kpilqr_last_launch.argtypes = [vp, C.c_int]; L.kpilqr_last_launch.restype = C.c_char_p
     if hasattr(L, "kpilqr_fd_interpolate"):
         L.kpilqr_fd_interpolate.argtypes = [vp]
+    if hasattr(L, "kpilqr_get_union_keypoints"):
+        L.kpilqr_get_union_keypoints.argtypes = [vp, vp, vp, C.c_int]
+        L.kpilqr_get_union_columns.argtypes = [vp, vp, C.c_size_t]
     for s in SYMBOLS:
         if s in OPTIONAL_SYMBOLS and not hasattr(L, s):
             continue

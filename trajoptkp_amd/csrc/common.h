@@ -51,6 +51,7 @@ struct FusedLaunch {
     bool rxc = false;                   // constant r_x kept in registers (ru0 instantiations only): nobody reads the r_x buffer
     bool slopes = false;                // the general (per-DoF list) form walks the slope store
     bool excl = false;                  // w1: every wave has a SIMD to itself (the _excl twins)
+    bool uni_on_union = false;          // the launch ran on the union store (KPILQR_FLAG_UNION_KEYPOINTS); only kpilqr_last_launch reads it
 };
 
 // ---- device memory a context owns ------------------------------------------------------------
@@ -149,6 +150,22 @@ struct Ctx {
     int fdk_entries = 0;         // entries of the resident key-point ordered payload (a view: of its trajectories)
     int fdk_first = 0;           // first entry of a view's trajectories (0 for the context itself)
 
+    // ---- KPILQR_FLAG_UNION_KEYPOINTS: per-DoF lists re-sampled onto their trajectory's union (kp_union.hip) ---------------------
+    // Every DoF of trajectory b gets the union U_b of the trajectory's key-point times, so the lists are uniform and the
+    // segment-loop forms of the sweeps run.  The union is stored once per DoF list, as an ordinary CSR the sweeps can read:
+    //   kpu_offsets [batch*dof+1], kpu_offsets[b*dof+d] = dof * kpu_traj_first[b] + d * |U_b|;  kpu_times [dof * sum |U_b|]
+    //   kpu_src [entry_u]: the own-list CSR entry p of the key-point at or before the union time; ~p when the time IS a key-point of the DoF
+    //   kpcu [entry_u][3][n]: the union column store (k_kp_union_expand: copies and k_interpolate's interpolants of kpc)
+    //   kpu_traj_first [batch+1]: union times before trajectory b (first the per-trajectory counts the host reads back and scans)
+    DevBuf<int> kpu_offsets, kpu_times, kpu_src, kpu_traj_first;
+    DevBuf<double> kpcu;
+    DevBuf<int> kpu_uniform;     // the device flag a union view hands to the sweeps: always non-zero
+    bool union_on = false;       // the flag is set and the context is fused (one-tile shape)
+    bool kpu_valid = false;      // the union lists are built for the current key-points
+    bool kpcu_valid = false;     // kpcu is expanded from the current kpc
+    int kpu_total = 0;           // sum over trajectories of |U_b| (entries_u = dof * kpu_total)
+    int *kpu_traj_first_host = nullptr;               // [batch+1] host copy of kpu_traj_first
+
     // nominal states for on-device key-point placement (kpilqr_upload_states), allocated on first use
     DevBuf<double> X_states;      // [batch][T][n]
     DevBuf<double> kp_thr;        // [dof]
@@ -198,7 +215,7 @@ struct Ctx {
     {
         DevMem *const all[] = {&rec, &kp_uniform, &K, &k, &r, &r_x, &r_u, &w_run, &w_term, &u_nom, &ctrl_lim, &lambda, &alphas, &cost_pred,
                                &delta_J, &traj_cost, &status, &segmap, &segent, &kp_offsets, &kp_times, &rx_const, &kpc, &kps, &kp_entry,
-                               &kp_entry_list, &fdk_dev, &X_states, &kp_thr, &kp_mask, &kp_count, &ls8, &fd_dev, &err_flag, &stage};
+                               &kp_entry_list, &fdk_dev, &kpu_offsets, &kpu_times, &kpu_src, &kpu_traj_first, &kpcu, &kpu_uniform, &X_states, &kp_thr, &kp_mask, &kp_count, &ls8, &fd_dev, &err_flag, &stage};
         for (DevMem *b : all) f(*b);
     }
 
@@ -247,6 +264,10 @@ hipError_t launch_build_entry_tables(Ctx *c);            // kp_entry, kp_entry_l
 hipError_t launch_copy_out(hipStream_t s, double *dst_host, const double *src_dev, size_t count);   // D2H by a kernel
 hipError_t launch_copy_in(hipStream_t s, void *dst_dev, const void *src_host, size_t bytes);        // H2D by a kernel
 hipError_t launch_build_segmap(Ctx *c, bool segent_only = false);   // segmap (and segent when allocated); segent_only: segent alone
+// kp_union.hip: the union of a trajectory's per-DoF key-point lists (KPILQR_FLAG_UNION_KEYPOINTS)
+hipError_t launch_kp_union_count(Ctx *c);                // |U_b| of every trajectory -> kpu_traj_first [batch]
+hipError_t launch_kp_union_build(Ctx *c);                // kpu_traj_first (scanned) -> kpu_offsets, kpu_times, kpu_src
+hipError_t launch_kp_union_expand(Ctx *c);               // kpc -> kpcu
 // comm.cpp (RCCL opened lazily) and the pack kernel of elementwise.hip
 const char *comm_unique_id(char *id128);
 const char *comm_init(Ctx *c, int nranks, int rank, const char *id128);

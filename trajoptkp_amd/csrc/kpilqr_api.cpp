@@ -190,7 +190,7 @@ static int ensure_kpc(kpilqr_ctx *c)
     if (rc < 0) return rc;
     if (rc > 0) {              // a new store starts zeroed, slack included: entries come into use without passing through here
         KP_HIP(c, hipMemsetAsync(c->kpc, 0, c->kpc.cap, c->stream));
-        c->kpc_valid = c->kpc_touched = c->kps_valid = false;
+        c->kpc_valid = c->kpc_touched = c->kps_valid = c->kpcu_valid = false;
     }
     return KPILQR_OK;
 }
@@ -230,7 +230,8 @@ static int ensure_entry_tables(kpilqr_ctx *c)
 }
 
 // The resident FD payload differenced into kpc (explicitly: the raw backward sweep does the same on the fly)
-static int difference_to_kpc(kpilqr_ctx *c)
+// want_slopes = false (the union route, whose sweeps never walk a slope store): none is allocated for it
+static int difference_to_kpc(kpilqr_ctx *c, bool want_slopes = true)
 {
     if (c->fd_payload == FdPayload::none || !c->have_kp) return KPILQR_OK;
     if (c->fd_payload == FdPayload::kp_columns) {                       // the columns ARE the payload
@@ -239,7 +240,7 @@ static int difference_to_kpc(kpilqr_ctx *c)
     }
     int rc = ensure_kpc(c);
     if (rc) return rc;
-    if (c->fused) { rc = ensure_kps(c); if (rc) return rc; }       // (only the fused sweeps' per-DoF list forms read the slope store)
+    if (c->fused && want_slopes) { rc = ensure_kps(c); if (rc) return rc; }       // (only the fused sweeps' per-DoF list forms read the slope store)
     c->kps_valid = false;
     if (c->fd_payload == FdPayload::jobs) {
         rc = ensure_entry_tables(c);
@@ -339,6 +340,7 @@ static int ensure_records(kpilqr_ctx *c)
 static void payload_changed(kpilqr_ctx *c)
 {
     c->kpc_valid = c->kpc_touched = c->kps_valid = false;
+    c->kpcu_valid = false;          // (the union columns are expanded from kpc)
     c->rec_synced = false;
 }
 
@@ -348,6 +350,7 @@ static void keypoints_changed(kpilqr_ctx *c, int total)
 {
     c->kp_total_host = total;
     c->entry_tables_valid = false;
+    c->kpu_valid = false;
     if (payload_by_entry(c)) { c->fd_payload = FdPayload::none; c->fdk_entries = 0; }
     payload_changed(c);
 }
@@ -370,6 +373,92 @@ static int ensure_rx_buffer(kpilqr_ctx *c)
     KP_HIP(c, launch_broadcast_rx(c));
     c->rx_buf_valid = true;
     return KPILQR_OK;
+}
+
+// ---- KPILQR_FLAG_UNION_KEYPOINTS: per-DoF lists re-sampled onto their trajectory's union (kp_union.hip) ----------------------
+// The sweeps of this launch take the union route: the flag is active, the lists are (or may be) per-DoF, and the uniform forms are
+// not switched off.  Never through a view: kpilqr_iterate_streamed runs today's per-DoF forms chunk by chunk.
+static bool union_route(const kpilqr_ctx *c)
+{
+    return c->union_on && !c->is_view && !c->kp_known_uniform && c->tune.fused_uni != 0;
+}
+
+// The union lists for the current key-points: the per-trajectory counts are read back (4 * batch bytes, ONE wait for the stream
+// per key-point change), scanned on the host, and the buffers sized from the scan; a second launch writes the lists.
+static int ensure_union(kpilqr_ctx *c)
+{
+    if (c->kpu_valid) return KPILQR_OK;
+    if (!c->kp_canonical)
+        return set_err(c, KPILQR_ERR_STATE, "the key-point union needs canonical key-points (per DoF: strictly increasing, first 0, last T-1)");
+    const size_t B = c->d.batch, dof = c->d.dof;
+    int rc = reserve(c, c->kpu_traj_first, (B + 1) * sizeof(int), kQuarter, false);
+    if (rc < 0) return rc;
+    rc = reserve(c, c->kpu_offsets, (B * dof + 1) * sizeof(int), kQuarter, false);
+    if (rc < 0) return rc;
+    rc = reserve(c, c->kpu_uniform, sizeof(int), kQuarter, false);
+    if (rc < 0) return rc;
+    int *first = (int *)realloc(c->kpu_traj_first_host, sizeof(int) * (B + 1));
+    if (!first) return set_err(c, KPILQR_ERR_ALLOC, "host allocation failed");
+    c->kpu_traj_first_host = first;
+    KP_HIP(c, launch_kp_union_count(c));
+    KP_HIP(c, hipMemcpyAsync(first + 1, c->kpu_traj_first, B * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    KP_HIP(c, hipStreamSynchronize(c->stream));
+    first[0] = 0;
+    for (size_t b = 0; b < B; b++) {
+        const int cnt = first[b + 1];
+        if (cnt < 2 || cnt > c->d.T || (size_t)first[b] + cnt > (size_t)INT32_MAX / dof)
+            return set_err(c, KPILQR_ERR_HIP, "key-point union: implausible count read back");
+        first[b + 1] = first[b] + cnt;
+    }
+    c->kpu_total = first[B];
+    const size_t entries = dof * (size_t)c->kpu_total;
+    rc = reserve(c, c->kpu_times, entries * sizeof(int), kQuarter, false);
+    if (rc < 0) return rc;
+    rc = reserve(c, c->kpu_src, entries * sizeof(int), kQuarter, false);
+    if (rc < 0) return rc;
+    // (the host array lives in the context and is rewritten only behind the wait above: a pageable source is safe)
+    KP_HIP(c, hipMemcpyAsync(c->kpu_traj_first, first, (B + 1) * sizeof(int), hipMemcpyHostToDevice, c->stream));
+    KP_HIP(c, hipMemsetAsync(c->kpu_uniform, 1, sizeof(int), c->stream));          // any non-zero value: uniform
+    KP_HIP(c, launch_kp_union_build(c));
+    c->kpu_valid = true;
+    c->kpcu_valid = false;
+    return KPILQR_OK;
+}
+
+// kpcu expanded from what kpc holds (the caller has differenced the resident payload into it)
+static int ensure_union_columns(kpilqr_ctx *c)
+{
+    int rc = ensure_union(c);
+    if (rc) return rc;
+    if (c->kpcu_valid) return KPILQR_OK;
+    rc = reserve(c, c->kpcu, (size_t)c->d.dof * c->kpu_total * 3 * c->n * 8, kQuarter, false);
+    if (rc < 0) return rc;
+    KP_HIP(c, launch_kp_union_expand(c));
+    c->kpcu_valid = c->kpc_valid;          // (no payload: kpc is whatever it was left as, and is expanded again next time)
+    return KPILQR_OK;
+}
+
+// kpc differenced from the resident payload (never by a raw sweep), the union built and expanded
+static int prepare_union(kpilqr_ctx *c)
+{
+    int rc = ensure_kpc(c);
+    if (rc) return rc;
+    if (!c->kpc_valid) { rc = difference_to_kpc(c, false); if (rc) return rc; }
+    return ensure_union_columns(c);
+}
+
+// The context as the sweeps see it on the union route: a copy like make_view's (it never allocates) whose key-point lists and
+// column store are the union's.  The lists are uniform by construction: only the segment-loop forms are launched, no slope
+// store is needed, and nothing is differenced inside a sweep.  Status, delta_J, gains and costs land in the context's buffers.
+static void make_union_view(const kpilqr_ctx *c, kpilqr_ctx *v)
+{
+    *v = *c;
+    v->is_view = true;
+    v->kp_offsets = c->kpu_offsets; v->kp_times = c->kpu_times; v->kp_uniform = c->kpu_uniform;
+    v->kpc = c->kpcu; v->kpc_valid = true;
+    v->kps = DevBuf<double>{}; v->kps_valid = false;
+    v->kp_known_uniform = true;
+    v->fd_payload = FdPayload::kp_columns;          // (nothing to difference: plan_backward_fused plans raw = false)
 }
 
 // what kpilqr_backward_variant / kpilqr_forward_variant call a family (a6: Ctx::tiled_a6)
@@ -403,6 +492,7 @@ static int select_variants(kpilqr_ctx *c)
         c->fused = true;
         c->bwd_family = c->fwd_family = Family::fused;
     }
+    c->union_on = c->fused && (dims->flags & KPILQR_FLAG_UNION_KEYPOINTS) != 0;      // (ignored on any other shape, as FUSED is)
     // The same flag on a tiled shape (n + 2 > 16): a6 (variant "..._a6"), cost derivatives formed from the residuals inside the
     // sweeps.  It replaces k_cost_derivs (HBM-bound: n^2 doubles written per step) by NT*ceil(nr/4) + 6 MFMAs per wave-step of the
     // latency-bound backward sweep (+9 % at four tiles, whatever the batch): a gain from ~100 trajectories of a four-tile state up
@@ -491,6 +581,7 @@ void kpilqr_destroy(kpilqr_ctx *c)
     c->for_each_buffer([](DevMem &b) { (void)release(b); });
     if (c->err_flag_host) (void)hipHostFree(c->err_flag_host);
     if (c->kp_traj_first_host) free(c->kp_traj_first_host);
+    if (c->kpu_traj_first_host) free(c->kpu_traj_first_host);
     if (c->own_stream) (void)hipStreamDestroy(c->stream);
     delete c;
 }
@@ -528,6 +619,7 @@ int kpilqr_resize(kpilqr_ctx *c, int new_dof, int new_num_ctrl, int new_horizon)
     c->fd_payload = FdPayload::none; c->fdk_entries = 0; c->entry_tables_valid = false; c->kp_total_host = -1;
     if (c->kp_traj_first_host) { free(c->kp_traj_first_host); c->kp_traj_first_host = nullptr; }
     payload_changed(c);
+    c->kpu_valid = false;
     c->ru_zero = true;                                   // size_buffers zeroed r_u
     c->rx_const_on = false; c->rx_buf_valid = true;
     // the key-point placement buffers were sized by the old shape: they are allocated again on first use
@@ -911,7 +1003,7 @@ int kpilqr_fd_difference(kpilqr_ctx *c)
     KP_ENTER(c);
     if (c->fused) {
         // the sweeps read the key-point column store; the records, if something has asked for them, follow
-        int rc = difference_to_kpc(c);
+        int rc = difference_to_kpc(c, !union_route(c));
         if (rc) return rc;
         if (c->have_rec) { rc = records_from_payload(c); if (rc) return rc; c->rec_synced = true; }
         return KPILQR_OK;
@@ -938,7 +1030,7 @@ int kpilqr_fd_interpolate(kpilqr_ctx *c)
     if (c->fused) {
         // the sweeps of a fused context read the column store: it is differenced as kpilqr_fd_difference does; the records appear on
         // demand (allocated and zeroed) and are filled in one pass where the payload allows
-        int rc = difference_to_kpc(c);
+        int rc = difference_to_kpc(c, !union_route(c));
         if (rc) return rc;
         rc = ensure_record_storage(c);
         if (rc) return rc;
@@ -1039,6 +1131,18 @@ static int run_backward(kpilqr_ctx *c, int pd_stride)
     if (c->fused) {
         int rc = check_fused(c);
         if (rc) return rc;
+        if (union_route(c)) {
+            rc = prepare_union(c);
+            if (rc) return rc;
+            kpilqr_ctx v;
+            make_union_view(c, &v);
+            FusedLaunch plan = plan_backward_fused(&v, false);
+            plan.uni_on_union = true;
+            c->last_bwd = plan;
+            if (!plan.rxc) { rc = ensure_rx_buffer(c); if (rc) return rc; }
+            KP_HIP(c, launch_backward_fused(&v, plan, pd_stride));
+            return KPILQR_OK;
+        }
         rc = ensure_kpc(c);
         if (rc) return rc;
         rc = ensure_kps(c);
@@ -1170,6 +1274,18 @@ static int run_forward(kpilqr_ctx *c, double *U_dev)
     if (c->fused) {
         int rc = check_fused(c);
         if (rc) return rc;
+        if (union_route(c)) {
+            rc = prepare_union(c);
+            if (rc) return rc;
+            kpilqr_ctx v;
+            make_union_view(c, &v);
+            FusedLaunch plan = plan_forward_fused(&v);
+            plan.uni_on_union = true;
+            c->last_fwd = plan;
+            if (!plan.rxc) { rc = ensure_rx_buffer(c); if (rc) return rc; }
+            KP_HIP(c, launch_forward_fused(&v, plan, U_dev));
+            return KPILQR_OK;
+        }
         rc = ensure_kpc(c);
         if (rc) return rc;
         rc = ensure_kps(c);
@@ -1225,7 +1341,7 @@ int kpilqr_iterate(kpilqr_ctx *c, const double *lambda, int pd_check_stride, con
         { const int rcl = linearise(c); if (rcl) return rcl; }
         if (!c->tiled_a6) { const int rcx = ensure_rx_buffer(c); if (rcx) return rcx; KP_HIP(c, launch_cost_derivs(c)); }      // tiled + flag: l_* are formed inside the sweeps
     }
-    else c->last_linearise = "in_sweep";
+    else c->last_linearise = union_route(c) ? "kp_union" : "in_sweep";
     int rc = run_backward(c, pd_check_stride);
     if (rc) return rc;
     return run_forward(c, nullptr);
@@ -1590,6 +1706,47 @@ int kpilqr_get_cost_derivs(kpilqr_ctx *c, double *l_x, double *l_xx, double *l_u
     return sync_and_report(c);
 }
 
+// ---- the union of KPILQR_FLAG_UNION_KEYPOINTS, read back (both build it on demand; synchronous) ----------------------------------
+int kpilqr_get_union_keypoints(kpilqr_ctx *c, int *traj_offsets, int *times, int times_capacity)
+{
+    if (!c || !traj_offsets) return KPILQR_ERR_ARG;
+    KP_ENTER(c);
+    if (!c->union_on) return set_err(c, KPILQR_ERR_STATE, "kpilqr_get_union_keypoints: KPILQR_FLAG_UNION_KEYPOINTS is not active on this context");
+    if (!c->have_kp) return set_err(c, KPILQR_ERR_STATE, "no key-points set");
+    const int rc = ensure_union(c);
+    if (rc) return rc;
+    const int B = c->d.batch, dof = c->d.dof, total = c->kpu_total;
+    memcpy(traj_offsets, c->kpu_traj_first_host, sizeof(int) * ((size_t)B + 1));
+    if (times) {
+        if (total > times_capacity) return set_err(c, KPILQR_ERR_ARG, "union times capacity too small");
+        // every DoF list of a trajectory holds the same times: the first one is copied out
+        for (int b = 0; b < B; b++) {
+            const int f0 = traj_offsets[b], cnt = traj_offsets[b + 1] - f0;
+            KP_HIP(c, hipMemcpyAsync(times + f0, c->kpu_times + (size_t)dof * f0, sizeof(int) * (size_t)cnt, hipMemcpyDeviceToHost, c->stream));
+        }
+    }
+    { const int rcs = sync_and_report(c); if (rcs) return rcs; }
+    return total;
+}
+
+int kpilqr_get_union_columns(kpilqr_ctx *c, double *columns, size_t capacity_doubles)
+{
+    if (!c) return KPILQR_ERR_ARG;
+    KP_ENTER(c);
+    if (!c->union_on) return set_err(c, KPILQR_ERR_STATE, "kpilqr_get_union_columns: KPILQR_FLAG_UNION_KEYPOINTS is not active on this context");
+    if (!c->have_kp) return set_err(c, KPILQR_ERR_STATE, "no key-points set");
+    if (c->fd_payload == FdPayload::none) return set_err(c, KPILQR_ERR_STATE, "kpilqr_get_union_columns: no FD payload resident");
+    const int rc = prepare_union(c);
+    if (rc) return rc;
+    const size_t entries = (size_t)c->d.dof * c->kpu_total, count = entries * 3 * c->n;
+    if (columns) {
+        if (count > capacity_doubles) return set_err(c, KPILQR_ERR_ARG, "union columns capacity too small");
+        KP_HIP(c, hipMemcpyAsync(columns, c->kpcu, count * 8, hipMemcpyDeviceToHost, c->stream));
+    }
+    { const int rcs = sync_and_report(c); if (rcs) return rcs; }
+    return (int)entries;
+}
+
 const char *kpilqr_backward_variant(kpilqr_ctx *c) { return c ? variant_name(c->bwd_family, c->tiled_a6) : ""; }
 const char *kpilqr_forward_variant(kpilqr_ctx *c) { return c ? variant_name(c->fwd_family, c->tiled_a6) : ""; }
 
@@ -1598,10 +1755,12 @@ const char *kpilqr_forward_variant(kpilqr_ctx *c) { return c ? variant_name(c->f
 //   waves    w1 one wavefront per trajectory | pair | triple | pairh
 //   columns  raw: the backward sweep differenced the key-point ordered payload itself | kpc: read from the column store
 //   lists    uni: every DoF of a trajectory has the same key-point list (the straight-line crossing forms ran) | ragged
+// and ":union" at the end when the launch ran on the union store of KPILQR_FLAG_UNION_KEYPOINTS (then `lists` is the union's: uni).
 // The `lists` token is decided on the device (the host never needs it otherwise): this call reads the flag back, i.e. it
 // waits for the context's stream.
 // which = 2: the linearisation stage (a2 + a4) of the last kpilqr_fd_interpolate / kpilqr_iterate / kpilqr_iterate_streamed:
-//   fd_kp_interpolate | kp_columns_interpolate (one pass, linearise.hip) | fd_difference+interpolate | in_sweep (fused context)
+//   fd_kp_interpolate | kp_columns_interpolate (one pass, linearise.hip) | fd_difference+interpolate | in_sweep (fused context) |
+//   kp_union (fused context, sweeps on the union store)
 const char *kpilqr_last_launch(kpilqr_ctx *c, int which)
 {
     if (c && which == 2) return c->last_linearise;
@@ -1616,8 +1775,9 @@ const char *kpilqr_last_launch(kpilqr_ctx *c, int which)
         return out.c_str();
     }
     int uni = 0;
+    // (a launch on the union store read the union's flag, not the one of the caller's lists)
     if (hipSetDevice(c->d.device) != hipSuccess || (c->pipe_dirty && join_pipeline(c) != KPILQR_OK) ||
-        hipMemcpyAsync(&uni, c->kp_uniform, sizeof(int), hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+        hipMemcpyAsync(&uni, p.uni_on_union ? c->kpu_uniform : c->kp_uniform, sizeof(int), hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
         hipStreamSynchronize(c->stream) != hipSuccess) { out += ":?"; return out.c_str(); }
     static const char *const wname[] = {"", "w1", "pair", "triple", "pairh"};      // by Waves
     out += ":"; out += wname[(int)(uni ? p.waves : p.waves_ragged)];
@@ -1628,6 +1788,7 @@ const char *kpilqr_last_launch(kpilqr_ctx *c, int which)
     if (p.ru0) out += ":ru0";
     if (p.rxc) out += ":rxc";
     if (!uni && p.slopes) out += ":slopes";
+    if (p.uni_on_union) out += ":union";
     return out.c_str();
 }
 

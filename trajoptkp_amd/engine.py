@@ -58,11 +58,13 @@ class _PinnedBlock:
 
 
 class Engine:
-    def __init__(self, dof, m, T, nr, batch=1, n_alpha=6, device=0, stream=None, generic=False, tiled=False, fused=False):
+    def __init__(self, dof, m, T, nr, batch=1, n_alpha=6, device=0, stream=None, generic=False, tiled=False, fused=False,
+                 union_keypoints=False):
         self._L = _lib.load()
         self.dof, self.n, self.m, self.T, self.nr = dof, 2 * dof, m, T, nr
         self.batch, self.n_alpha, self.device = batch, n_alpha, device
-        d = _lib.Dims(dof, m, T, nr, batch, n_alpha, device, (_lib.FLAG_GENERIC_KERNELS if generic else 0) | (_lib.FLAG_TILED_KERNELS if tiled else 0) | (_lib.FLAG_FUSED if fused else 0))
+        d = _lib.Dims(dof, m, T, nr, batch, n_alpha, device, (_lib.FLAG_GENERIC_KERNELS if generic else 0) | (_lib.FLAG_TILED_KERNELS if tiled else 0) | (_lib.FLAG_FUSED if fused else 0)
+                      | (_lib.FLAG_UNION_KEYPOINTS if union_keypoints else 0))
         h = C.c_void_p()
         rc = self._L.kpilqr_create(C.byref(d), C.c_void_p(stream) if stream else None, C.byref(h))
         if rc != 0:
@@ -161,6 +163,26 @@ class Engine:
         times = np.zeros(max(total, 1), np.int32)
         self._ck(self._L.kpilqr_get_keypoints(self._h, _ptr(offs), _ptr(times), len(times)))
         return offs, times[:total]
+
+    def get_union_keypoints(self):
+        """kpilqr_get_union_keypoints (a context created with union_keypoints=True): -> (traj_offsets [batch+1], times), one
+        sorted list of union times per trajectory."""
+        if not hasattr(self._L, "kpilqr_get_union_keypoints"):
+            raise KpilqrError(_lib.ERR_ARG, "this libkpilqr.so has no kpilqr_get_union_keypoints")
+        offs = np.zeros(self.batch + 1, np.int32)
+        total = self._ck(self._L.kpilqr_get_union_keypoints(self._h, _ptr(offs), None, 0))
+        times = np.zeros(max(total, 1), np.int32)
+        self._ck(self._L.kpilqr_get_union_keypoints(self._h, _ptr(offs), _ptr(times), len(times)))
+        return offs, times[:total]
+
+    def get_union_columns(self):
+        """kpilqr_get_union_columns: the union column store [entry_u][3][n], entry_u = dof * traj_offsets[b] + d * |U_b| + j."""
+        if not hasattr(self._L, "kpilqr_get_union_columns"):
+            raise KpilqrError(_lib.ERR_ARG, "this libkpilqr.so has no kpilqr_get_union_columns")
+        entries = self._ck(self._L.kpilqr_get_union_columns(self._h, None, 0))
+        cols = np.zeros((max(entries, 1), 3, self.n))
+        self._ck(self._L.kpilqr_get_union_columns(self._h, _ptr(cols), cols.size))
+        return cols[:entries]
 
     def keypoint_error_test(self, intervals, min_N, threshold):
         """kpilqr_keypoint_error_test: intervals [n][4] = (trajectory, DoF, start, end) -> bool [n] (True: good)."""
