@@ -747,7 +747,8 @@ __device__ __forceinline__ void backward_fused_body(double *sh, const double *pc
         //      (it gives the PD verdict of :587-595), and whenever the residual is too large to converge fast.
         bool done = false;
         int ns_steps = 0;
-        // (segment-loop forms: the peeled step is the one right below a key-point -- known at compile time)
+        // (segment-loop forms: the peeled step is the one right below a key-point -- known at compile time; which steps are peeled,
+        // the re-seed below and its Xprev = Xinv are mirrored in tests/_refresh.py)
         constexpr bool KINK = UNI && !PC && decltype(may_be_first)::value;
         const bool refreshed = haveX && !check_pd && kp_inverse_refresh_n<NCU, KINK, PC>(Qr, Iu, Xinv, Xprev, m, STATS ? &ns_steps : nullptr);    // Xinv, Xprev: NEGATED inverses
         if constexpr (STATS) { if (refreshed) hcnt[ns_steps < 0 ? 0 : ns_steps > 3 ? 3 : ns_steps]++; }

@@ -71,6 +71,7 @@ __device__ __forceinline__ bool kp_inverse_refresh(const d4 &Qr, const d4 &Iu, d
     if (NCU > 2) rmax = fmax(rmax, fabs(R.z));
     if (NCU > 3) rmax = fmax(rmax, fabs(R.w));
     const double e = (double)m * rmax;
+    // (thresholds and step counts mirrored in tests/_refresh.py, family "plain")
     if (__builtin_amdgcn_ballot_w64(!(e < 0.11)) != 0) return false;
     const int iters = (__builtin_amdgcn_ballot_w64(e >= 1.3e-2) != 0) ? 4
                     : (__builtin_amdgcn_ballot_w64(e >= 1.7e-4) != 0) ? 3
@@ -112,6 +113,7 @@ __device__ __forceinline__ bool kp_inverse_refresh_p(const d4 &Qr, const d4 &Iu,
     if (NCU > 2) rmax = fmax(rmax, fabs(R.z));
     if (NCU > 3) rmax = fmax(rmax, fabs(R.w));
     const double e = (double)m * rmax;
+    // (thresholds and step counts mirrored in tests/_refresh.py, family "p")
     if (__builtin_amdgcn_ballot_w64(!(e < 2.0e-5)) != 0) {
         if (__builtin_amdgcn_ballot_w64(!(e < 0.11)) != 0) return false;
         const int iters = (__builtin_amdgcn_ballot_w64(e >= 1.3e-2) != 0) ? 3 : (__builtin_amdgcn_ballot_w64(e >= 1.7e-4) != 0) ? 2 : 1;
@@ -157,6 +159,7 @@ __device__ __forceinline__ bool kp_inverse_refresh_n(const d4 &Qr, const d4 &Iu,
     if (NCU > 2) rmax = fmax(rmax, fabs(R.z));
     if (NCU > 3) rmax = fmax(rmax, fabs(R.w));
     const double e = (double)m * rmax;
+    // (thresholds, series terms and step counts mirrored in tests/_refresh.py, families "n", "n_kink", "n_ser4")
     if (__builtin_amdgcn_ballot_w64(!(e < (KINK ? 1.7e-4 : 2.0e-5))) != 0) {
         if (__builtin_amdgcn_ballot_w64(!(e < 0.11)) != 0) { if (steps) *steps = -1; return false; }
         if (!KINK && SER4 && KP_SERIES4 && __builtin_amdgcn_ballot_w64(e >= 1.7e-4) == 0) {

@@ -17,6 +17,7 @@
 #include "mfma_common.h"
 #ifndef KP_NS_HOLD
 #define KP_NS_HOLD 8                // factorised steps behind a Newton-Schulz refresh that gave up before the fast path is tried again
+                                    // (the hold of both tiled forms is mirrored in tests/_refresh.py, families "plain", "plain_col")
 #endif
 #ifndef KP_FT_SETS
 #define KP_FT_SETS 2                // register sets of the two-tile forward sweep on materialised tiles (1: rounds 1-3, A/B builds)

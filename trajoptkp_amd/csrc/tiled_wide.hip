@@ -380,6 +380,7 @@ k_backward_tiled_wide(RecLayout L, int T, const double *__restrict__ rec, const 
                 for (int i = 0; i < MT * MT; i++) Xinv[i] = Xn[i];
             };
             const double e = (double)m * residual();
+            // (thresholds and step counts mirrored in tests/_refresh.py, family "wide")
             if (__builtin_amdgcn_ballot_w64(!(e < 0.11)) == 0) {
                 const int iters = (__builtin_amdgcn_ballot_w64(e >= 1.3e-2) != 0) ? 4
                                 : (__builtin_amdgcn_ballot_w64(e >= 1.7e-4) != 0) ? 3
