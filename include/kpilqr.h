@@ -169,6 +169,60 @@ int  kpilqr_device_ptr(kpilqr_ctx *ctx, int which, void **dptr, size_t *bytes);
  * std::vector<std::vector<int>> keypoints, include/KeyPointGenerator.h:85-100).  */
 int  kpilqr_set_keypoints(kpilqr_ctx *ctx, const int *kp_offsets, const int *kp_times);
 
+/* ---- partial re-linearisation: new lists, and a new payload, for SOME trajectories -------------------------------------------
+ * Only trajectories whose last step was accepted regenerate their derivatives (src/Optimiser/iLQR.cpp:419), but a payload laid out
+ * by CSR entry has to follow the lists, and new lists of one trajectory shift the entry offsets of every later one.  These calls
+ * keep what is unchanged on the device: the records of the trajectories that are NOT listed are moved to their new entry offsets
+ * there (an HBM-rate copy, kp_partial.hip), and only the listed trajectories' records cross the link.
+ * `traj` [count] is strictly increasing and within [0, batch) in all four calls; anything else is KPILQR_ERR_ARG.  All four first
+ * order themselves behind a kpilqr_iterate_streamed still in flight.  KPILQR_VERSION is unchanged: detect them by their symbols.
+ *
+ * kpilqr_update_keypoints replaces the per-DoF lists of the listed trajectories -- kp_offsets [count*dof + 1] starts at 0 and
+ * indexes kp_times, trajectories in `traj` order, checked exactly as kpilqr_set_keypoints checks (range, monotone offsets) -- and
+ * keeps everybody else's.  It leaves the context exactly as kpilqr_set_keypoints with the merged lists would (device CSR, segment
+ * maps, canonical / uniform flags, kpilqr_get_keypoints, the union lists invalid), with one exception: a resident payload laid out
+ * by entry SURVIVES -- the slab of kpilqr_upload_fd_kp, or the columns of kpilqr_upload_kp_columns.  The listed trajectories'
+ * entry ranges are then PENDING: until the matching partial upload below arrives, every call that would read the payload returns
+ * KPILQR_ERR_STATE and names what is missing (kpilqr_backward, kpilqr_backward_stats, kpilqr_iterate, kpilqr_iterate_streamed
+ * without a new payload, kpilqr_fd_difference, kpilqr_interpolate, kpilqr_fd_interpolate, kpilqr_get_AB, kpilqr_get_union_columns
+ * and whatever else would difference it), and so does another kpilqr_update_keypoints.  A whole new payload (kpilqr_upload_fd_kp,
+ * kpilqr_upload_kp_columns, kpilqr_upload_fd / _slab, a payload of kpilqr_iterate_streamed) or new lists for everybody
+ * (kpilqr_set_keypoints, kpilqr_generate_keypoints) clear the pending state at any time.  With a job-list payload, or with none,
+ * there is nothing to carry: the call behaves exactly like kpilqr_set_keypoints on the merged lists.  count = 0 is a no-op:
+ * nothing becomes invalid.  A rejected call leaves the context as it was.
+ * Cost.  (1) The context keeps a host mirror of all offsets, 4 * (batch*dof + 1) bytes, filled by kpilqr_set_keypoints; after
+ * kpilqr_generate_keypoints it is read back on the first update, which WAITS for the stream.  The call also waits for its own
+ * copies (the merged offsets are staged in memory it owns), i.e. for the relocation.  (2) The relocation is never in place -- ranges
+ * move both ways -- so the context gets SECOND buffers for the by-entry payload and the list times, reserved the first time an update
+ * has something to carry and swapped with the live ones after the copy: the by-entry payload allocation is DOUBLED once this
+ * route has been used (5.9 GB more at Panda reaching, T = 3000, batch 1024, velocity_change lists).  An update whose new total
+ * exceeds the capacity grows the second buffer first and copies before anything is freed: the kept records are never lost.
+ * Not through a view of kpilqr_iterate_streamed's chunks (never allocates).
+ *
+ * kpilqr_upload_fd_kp_partial / kpilqr_upload_kp_columns_partial complete the payload: the slab (records of kpilqr_fd_kp_layout)
+ * or column array ([entries][3][n]) holds the records of the listed trajectories back to back in `traj` order.  `traj` must be
+ * exactly the pending set and `entries` the sum of their entry counts (else KPILQR_ERR_ARG); eps must match the resident
+ * payload's bit for bit (else KPILQR_ERR_ARG: a context has one eps); the payload kind must be the resident kind (else
+ * KPILQR_ERR_STATE).  One hipMemcpyAsync per run of adjacent listed trajectories, straight into place, no kernel; pinned / pageable
+ * behaviour as kpilqr_upload_fd_kp.  Afterwards the payload is complete and everything derived from it is stale, as after a whole
+ * upload (the column store, slope store, union store and step records are re-derived).
+ *
+ * kpilqr_download_gains_partial writes K [count][T][n][m] and k [count][T][m] of the listed trajectories, compact, in the
+ * per-trajectory layout of kpilqr_download_gains: one copy per array and run of adjacent trajectories, asynchronous; either
+ * pointer may be NULL.
+ *
+ * Out of scope: residuals still go up for the whole batch (kpilqr_upload_residuals); job-list payloads are not carried; the
+ * chunks of kpilqr_iterate_streamed are unchanged; nothing derived from the payload stays valid across an update; and
+ * kpilqr_generate_keypoints places key-points for the whole batch only. */
+int  kpilqr_update_keypoints(kpilqr_ctx *ctx, int count, const int *traj,
+                             const int *kp_offsets /* [count*dof + 1], starts at 0 */, const int *kp_times);
+int  kpilqr_upload_fd_kp_partial(kpilqr_ctx *ctx, int count, const int *traj,
+                                 const void *slab, int entries, double eps);
+int  kpilqr_upload_kp_columns_partial(kpilqr_ctx *ctx, int count, const int *traj,
+                                      const double *columns, int entries);
+int  kpilqr_download_gains_partial(kpilqr_ctx *ctx, int count, const int *traj,
+                                   double *K /* [count][T][n][m] */, double *k /* [count][T][m] */);
+
 /* Key-point placement on the device for the whole batch (optional).
  * X [batch][T][n]: the nominal trajectory states (positions then velocities), as Optimiser::X_old. */
 int  kpilqr_upload_states(kpilqr_ctx *ctx, const double *X);

@@ -29,10 +29,13 @@ SYMBOLS = [
     "kpilqr_keypoint_error_test", "kpilqr_fd_kp_layout", "kpilqr_upload_fd_kp", "kpilqr_backward_stats",
     "kpilqr_upload_kp_columns", "kpilqr_upload_residual_jacobians_const", "kpilqr_last_launch",
     "kpilqr_fd_interpolate", "kpilqr_get_union_keypoints", "kpilqr_get_union_columns",
+    "kpilqr_update_keypoints", "kpilqr_upload_fd_kp_partial", "kpilqr_upload_kp_columns_partial", "kpilqr_download_gains_partial",
 ]
 # entry points added without a version bump (include/kpilqr.h: "detect the entry point by its symbol"): bound only when the library
 # has them -- KPILQR_LIB may name an older build of the same major version
-OPTIONAL_SYMBOLS = {"kpilqr_fd_interpolate", "kpilqr_get_union_keypoints", "kpilqr_get_union_columns"}
+OPTIONAL_SYMBOLS = {"kpilqr_fd_interpolate", "kpilqr_get_union_keypoints", "kpilqr_get_union_columns",
+                    "kpilqr_update_keypoints", "kpilqr_upload_fd_kp_partial", "kpilqr_upload_kp_columns_partial",
+                    "kpilqr_download_gains_partial"}
 
 
 class Dims(C.Structure):
@@ -147,6 +150,11 @@ def load():
     if hasattr(L, "kpilqr_get_union_keypoints"):
         L.kpilqr_get_union_keypoints.argtypes = [vp, vp, vp, C.c_int]
         L.kpilqr_get_union_columns.argtypes = [vp, vp, C.c_size_t]
+    if hasattr(L, "kpilqr_update_keypoints"):
+        L.kpilqr_update_keypoints.argtypes = [vp, C.c_int, vp, vp, vp]
+        L.kpilqr_upload_fd_kp_partial.argtypes = [vp, C.c_int, vp, vp, C.c_int, C.c_double]
+        L.kpilqr_upload_kp_columns_partial.argtypes = [vp, C.c_int, vp, vp, C.c_int]
+        L.kpilqr_download_gains_partial.argtypes = [vp, C.c_int, vp, vp, vp]
     for s in SYMBOLS:
         if s in OPTIONAL_SYMBOLS and not hasattr(L, s):
             continue

@@ -166,6 +166,25 @@ struct Ctx {
     int kpu_total = 0;           // sum over trajectories of |U_b| (entries_u = dof * kpu_total)
     int *kpu_traj_first_host = nullptr;               // [batch+1] host copy of kpu_traj_first
 
+    // ---- kpilqr_update_keypoints: new lists for SOME trajectories, a by-entry payload carried over (kp_partial.hip) --------------
+    // Second buffers of the payload slab, the column store and kp_times: the kept trajectories' records and lists are copied to
+    // their new entry offsets in the second buffer, which is then SWAPPED with the live one (never in place: ranges move both ways).
+    // Reserved the first time an update has something to carry, so the by-entry payload is held twice from then on.
+    DevBuf<char> fdk_alt;
+    DevBuf<double> kpc_alt;
+    DevBuf<int> kp_times_alt;
+    DevBuf<int> kp_upl_times;    // the new lists' times as uploaded
+    DevBuf<int> kp_move;         // [3][batch+1]: first entry before | after | inside kp_upl_times (-1: kept), kp_merge_offsets
+    // host mirrors (malloc): all offsets [batch*dof+1] (valid: filled by kpilqr_set_keypoints, read back once after
+    // kpilqr_generate_keypoints) and per-trajectory flags [batch] (kp_merge.h) from which kp_canonical / kp_known_uniform follow
+    int *kp_offsets_host = nullptr;
+    bool kp_offsets_host_valid = false;
+    unsigned char *kp_flags_host = nullptr;
+    // the trajectories whose entry ranges wait for kpilqr_upload_fd_kp_partial / kpilqr_upload_kp_columns_partial: until then every
+    // call that would read the payload is refused
+    int *kp_pending_host = nullptr;       // [batch]
+    int n_pending = 0, pending_entries = 0;
+
     // nominal states for on-device key-point placement (kpilqr_upload_states), allocated on first use
     DevBuf<double> X_states;      // [batch][T][n]
     DevBuf<double> kp_thr;        // [dof]
@@ -215,7 +234,7 @@ struct Ctx {
     {
         DevMem *const all[] = {&rec, &kp_uniform, &K, &k, &r, &r_x, &r_u, &w_run, &w_term, &u_nom, &ctrl_lim, &lambda, &alphas, &cost_pred,
                                &delta_J, &traj_cost, &status, &segmap, &segent, &kp_offsets, &kp_times, &rx_const, &kpc, &kps, &kp_entry,
-                               &kp_entry_list, &fdk_dev, &kpu_offsets, &kpu_times, &kpu_src, &kpu_traj_first, &kpcu, &kpu_uniform, &X_states, &kp_thr, &kp_mask, &kp_count, &ls8, &fd_dev, &err_flag, &stage};
+                               &kp_entry_list, &fdk_dev, &kpu_offsets, &kpu_times, &kpu_src, &kpu_traj_first, &kpcu, &kpu_uniform, &fdk_alt, &kpc_alt, &kp_times_alt, &kp_upl_times, &kp_move, &X_states, &kp_thr, &kp_mask, &kp_count, &ls8, &fd_dev, &err_flag, &stage};
         for (DevMem *b : all) f(*b);
     }
 
@@ -268,6 +287,12 @@ hipError_t launch_build_segmap(Ctx *c, bool segent_only = false);   // segmap (a
 hipError_t launch_kp_union_count(Ctx *c);                // |U_b| of every trajectory -> kpu_traj_first [batch]
 hipError_t launch_kp_union_build(Ctx *c);                // kpu_traj_first (scanned) -> kpu_offsets, kpu_times, kpu_src
 hipError_t launch_kp_union_expand(Ctx *c);               // kpc -> kpcu
+// kp_partial.hip: kpilqr_update_keypoints -- kept trajectories' records / lists to their new entry offsets in a second buffer
+// (first_old, first_new, upl_first: the three rows of Ctx::kp_move; units: 16-byte units per record)
+hipError_t launch_relocate_entries(Ctx *c, int units, long long longest_kept_entries, const int *first_old, const int *first_new,
+                                   const int *upl_first, const void *src, void *dst);
+hipError_t launch_merge_kp_times(Ctx *c, int longest_entries, const int *first_old, const int *first_new, const int *upl_first,
+                                 const int *old_times, const int *upl_times, int *times);
 // comm.cpp (RCCL opened lazily) and the pack kernel of elementwise.hip
 const char *comm_unique_id(char *id128);
 const char *comm_init(Ctx *c, int nranks, int rank, const char *id128);

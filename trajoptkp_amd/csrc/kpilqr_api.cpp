@@ -5,9 +5,11 @@
 #include <cstdlib>
 #include <cstring>
 #include <new>
+#include <utility>
 #include <vector>
 
 #include "common.h"
+#include "kp_merge.h"
 
 using namespace kpilqr;
 
@@ -94,6 +96,8 @@ static int ensure_stage(kpilqr_ctx *c, size_t bytes)
     const int rc = reserve(c, c->stage, bytes, kExact, false);
     return rc < 0 ? rc : KPILQR_OK;
 }
+
+static int check_complete(kpilqr_ctx *c, const char *who);      // (below: ranges pending since kpilqr_update_keypoints)
 
 static int env_int(const char *name, int dflt)
 {
@@ -234,6 +238,7 @@ static int ensure_entry_tables(kpilqr_ctx *c)
 static int difference_to_kpc(kpilqr_ctx *c, bool want_slopes = true)
 {
     if (c->fd_payload == FdPayload::none || !c->have_kp) return KPILQR_OK;
+    { const int rcp = check_complete(c, "differencing the resident payload"); if (rcp) return rcp; }      // (whoever asks: the entry points check first)
     if (c->fd_payload == FdPayload::kp_columns) {                       // the columns ARE the payload
         if (!c->kpc_valid) return set_err(c, KPILQR_ERR_STATE, "the key-point columns are gone (new key-points): upload them again");
         return KPILQR_OK;
@@ -259,6 +264,7 @@ static int difference_to_kpc(kpilqr_ctx *c, bool want_slopes = true)
 static int records_from_payload(kpilqr_ctx *c)
 {
     if (c->fd_payload == FdPayload::jobs) { KP_HIP(c, launch_fd_difference(c)); return KPILQR_OK; }
+    { const int rcp = check_complete(c, "the records of the resident payload"); if (rcp) return rcp; }
     if (payload_by_entry(c)) {
         if (!c->have_kp) return KPILQR_OK;
         int rc = KPILQR_OK;
@@ -342,6 +348,16 @@ static void payload_changed(kpilqr_ctx *c)
     c->kpc_valid = c->kpc_touched = c->kps_valid = false;
     c->kpcu_valid = false;          // (the union columns are expanded from kpc)
     c->rec_synced = false;
+    c->n_pending = c->pending_entries = 0;      // (a whole payload, new lists for everybody, or the partial upload that was waited for)
+}
+
+// kpilqr_update_keypoints has left entry ranges of the resident payload unwritten: nothing may read it before the partial upload
+static int check_complete(kpilqr_ctx *c, const char *who)
+{
+    if (!c->n_pending) return KPILQR_OK;
+    return set_err(c, KPILQR_ERR_STATE, std::string(who) + ": the payload of " + std::to_string(c->n_pending) + " trajectories (first: " +
+                   std::to_string(c->kp_pending_host[0]) + ", " + std::to_string(c->pending_entries) + " entries) is pending since kpilqr_update_keypoints: "
+                   "kpilqr_upload_fd_kp_partial / kpilqr_upload_kp_columns_partial is missing");
 }
 
 // New key-point lists of `total` entries are on the device: everything that was derived from the old ones is stale, and a payload
@@ -363,6 +379,28 @@ static bool remember_traj_first(kpilqr_ctx *c, const int *kp_offsets)
     if (!c->kp_traj_first_host) return false;
     for (int b = 0; b <= c->d.batch; b++) c->kp_traj_first_host[b] = kp_offsets[(size_t)b * c->d.dof];
     return true;
+}
+
+// Host mirrors behind kpilqr_update_keypoints: the per-trajectory flags [batch] exist from the first key-points on; the offsets
+// are copied here by kpilqr_set_keypoints (offs != null) or marked as to-be-read-back (kpilqr_generate_keypoints).  false: no memory
+static bool remember_lists(kpilqr_ctx *c, const int *offs)
+{
+    const size_t nlists = (size_t)c->d.batch * c->d.dof;
+    if (!c->kp_flags_host) c->kp_flags_host = (unsigned char *)malloc((size_t)c->d.batch);
+    if (!c->kp_offsets_host) c->kp_offsets_host = (int *)malloc(sizeof(int) * (nlists + 1));
+    if (!c->kp_flags_host || !c->kp_offsets_host) return false;
+    if (offs) memcpy(c->kp_offsets_host, offs, sizeof(int) * (nlists + 1));
+    c->kp_offsets_host_valid = offs != nullptr;
+    return true;
+}
+
+static void forget_lists(kpilqr_ctx *c)
+{
+    int **const ints[] = {&c->kp_traj_first_host, &c->kp_offsets_host, &c->kp_pending_host};
+    for (int **p : ints) { free(*p); *p = nullptr; }
+    free(c->kp_flags_host); c->kp_flags_host = nullptr;
+    c->kp_offsets_host_valid = false;
+    c->n_pending = c->pending_entries = 0;
 }
 
 // Constant residual Jacobians (kpilqr_upload_residual_jacobians_const): a fused sweep whose plan says rxc keeps r_x in registers;
@@ -580,7 +618,7 @@ void kpilqr_destroy(kpilqr_ctx *c)
     comm_destroy(c);
     c->for_each_buffer([](DevMem &b) { (void)release(b); });
     if (c->err_flag_host) (void)hipHostFree(c->err_flag_host);
-    if (c->kp_traj_first_host) free(c->kp_traj_first_host);
+    forget_lists(c);
     if (c->kpu_traj_first_host) free(c->kpu_traj_first_host);
     if (c->own_stream) (void)hipStreamDestroy(c->stream);
     delete c;
@@ -617,7 +655,7 @@ int kpilqr_resize(kpilqr_ctx *c, int new_dof, int new_num_ctrl, int new_horizon)
     c->have_kp = c->kp_canonical = c->have_states = c->kp_known_uniform = false;
     c->njobs = c->nnom = 0;
     c->fd_payload = FdPayload::none; c->fdk_entries = 0; c->entry_tables_valid = false; c->kp_total_host = -1;
-    if (c->kp_traj_first_host) { free(c->kp_traj_first_host); c->kp_traj_first_host = nullptr; }
+    forget_lists(c);                                     // (sized by the old batch * dof)
     payload_changed(c);
     c->kpu_valid = false;
     c->ru_zero = true;                                   // size_buffers zeroed r_u
@@ -712,30 +750,17 @@ int kpilqr_set_keypoints(kpilqr_ctx *c, const int *kp_offsets, const int *kp_tim
     if (!c || !kp_offsets || !kp_times) return KPILQR_ERR_ARG;
     KP_ENTER(c);
     const size_t nlists = (size_t)c->d.batch * c->d.dof;
+    if (const char *bad = kp_check_lists(nlists, c->d.T, kp_offsets, kp_times)) return set_err(c, KPILQR_ERR_ARG, bad);
     const int total = kp_offsets[nlists];
-    if (kp_offsets[0] != 0 || total < 0) return set_err(c, KPILQR_ERR_ARG, "kp_offsets must start at 0");
-    for (size_t i = 0; i < nlists; i++)
-        if (kp_offsets[i + 1] < kp_offsets[i]) return set_err(c, KPILQR_ERR_ARG, "kp_offsets not monotone");
-    for (int i = 0; i < total; i++)
-        if (kp_times[i] < 0 || kp_times[i] >= c->d.T) return set_err(c, KPILQR_ERR_ARG, "kp_times out of [0,T)");
-    bool canonical = true;
-    for (size_t i = 0; i < nlists && canonical; i++) {
-        const int a = kp_offsets[i], e = kp_offsets[i + 1];
-        if (e <= a || kp_times[a] != 0 || kp_times[e - 1] != c->d.T - 1) { canonical = false; break; }
-        for (int j = a + 1; j < e; j++) if (kp_times[j] <= kp_times[j - 1]) { canonical = false; break; }
-    }
-    c->kp_canonical = canonical;
-    // every trajectory's DoFs share one list (set_interval): the device flag of k_kp_uniform will say the same, only the
-    // segment-loop forms of the sweeps run and no slope store is needed
-    bool uniform = true;
-    for (int b = 0; b < c->d.batch && uniform; b++) {
-        const int *o = kp_offsets + (size_t)b * c->d.dof;
-        const int len0 = o[1] - o[0];
-        for (int i = 1; i < c->d.dof && uniform; i++)
-            uniform = (o[i + 1] - o[i] == len0) && memcmp(kp_times + o[i], kp_times + o[0], sizeof(int) * (size_t)len0) == 0;
-    }
-    c->kp_known_uniform = uniform && c->tune.fused_uni != 0;     // (KPILQR_FUSED_UNI=0: the general forms run on every set)
     { const int rcg = reserve(c, c->kp_times, (size_t)total * sizeof(int), Slack{4, 64 * sizeof(int)}, false); if (rcg < 0) return rcg; }
+    if (!remember_lists(c, kp_offsets)) return set_err(c, KPILQR_ERR_ALLOC, "host allocation failed");
+    // per trajectory (kpilqr_update_keypoints merges them): canonical lists; every DoF shares one list (set_interval) -- when that
+    // holds for the whole batch the device flag of k_kp_uniform will say the same, only the segment-loop forms of the sweeps run
+    // and no slope store is needed
+    for (int b = 0; b < c->d.batch; b++) c->kp_flags_host[b] = kp_traj_flags(c->d.dof, c->d.T, kp_offsets + (size_t)b * c->d.dof, kp_times);
+    const unsigned char flags = kp_batch_flags(c->d.batch, c->kp_flags_host);
+    c->kp_canonical = (flags & kKpCanonical) != 0;
+    c->kp_known_uniform = (flags & kKpUniform) && c->tune.fused_uni != 0;     // (KPILQR_FUSED_UNI=0: the general forms run on every set)
     KP_HIP(c, hipMemcpyAsync(c->kp_offsets, kp_offsets, (nlists + 1) * sizeof(int), hipMemcpyHostToDevice, c->stream));
     KP_HIP(c, hipMemcpyAsync(c->kp_times, kp_times, (size_t)total * sizeof(int), hipMemcpyHostToDevice, c->stream));
     KP_HIP(c, launch_build_segmap(c));
@@ -745,6 +770,109 @@ int kpilqr_set_keypoints(kpilqr_ctx *c, const int *kp_offsets, const int *kp_tim
     c->have_kp = true;
     keypoints_changed(c, total);
     if (!remember_traj_first(c, kp_offsets)) return set_err(c, KPILQR_ERR_ALLOC, "host allocation failed");
+    return KPILQR_OK;
+}
+
+// ---- new lists for SOME trajectories: a payload laid out by entry follows them on the device (kp_partial.hip) ---------------------
+// The batch offsets as the host knows them: kpilqr_set_keypoints left them; behind kpilqr_generate_keypoints they are read back
+// here, once (a wait for the stream)
+static int ensure_offsets_mirror(kpilqr_ctx *c)
+{
+    if (!c->kp_offsets_host || !c->kp_flags_host) return set_err(c, KPILQR_ERR_STATE, "kpilqr_update_keypoints: the context has no key-point lists yet");
+    if (c->kp_offsets_host_valid) return KPILQR_OK;
+    const size_t nlists = (size_t)c->d.batch * c->d.dof;
+    KP_HIP(c, hipMemcpyAsync(c->kp_offsets_host, c->kp_offsets, (nlists + 1) * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    KP_HIP(c, hipStreamSynchronize(c->stream));
+    bool ok = c->kp_offsets_host[0] == 0 && c->kp_offsets_host[nlists] == c->kp_total_host;
+    for (size_t i = 0; i < nlists && ok; i++) ok = c->kp_offsets_host[i + 1] >= c->kp_offsets_host[i];
+    if (!ok) return set_err(c, KPILQR_ERR_HIP, "kpilqr_update_keypoints: implausible key-point offsets read back");
+    c->kp_offsets_host_valid = true;
+    return KPILQR_OK;
+}
+
+int kpilqr_update_keypoints(kpilqr_ctx *c, int count, const int *traj, const int *kp_offsets, const int *kp_times)
+{
+    if (!c || count < 0 || (count > 0 && (!traj || !kp_offsets || !kp_times))) return KPILQR_ERR_ARG;
+    KP_ENTER(c);
+    if (count == 0) return KPILQR_OK;                    // nobody's lists change: nothing becomes invalid
+    const int B = c->d.batch, dof = c->d.dof;
+    const size_t nlists = (size_t)B * dof, nnew = (size_t)count * dof, B1 = (size_t)B + 1;
+    if (!kp_traj_list_ok(B, count, traj)) return set_err(c, KPILQR_ERR_ARG, "kpilqr_update_keypoints: traj must be strictly increasing and within [0, batch)");
+    if (const char *bad = kp_check_lists(nnew, c->d.T, kp_offsets, kp_times)) return set_err(c, KPILQR_ERR_ARG, bad);
+    if (!c->have_kp) return set_err(c, KPILQR_ERR_STATE, "kpilqr_update_keypoints before kpilqr_set_keypoints / kpilqr_generate_keypoints");
+    if (c->is_view) return set_err(c, KPILQR_ERR_STATE, "a view of a trajectory range never allocates: its context sizes the buffers first");
+    { const int rcp = check_complete(c, "kpilqr_update_keypoints"); if (rcp) return rcp; }
+    int rc = ensure_offsets_mirror(c);
+    if (rc) return rc;
+
+    // ---- the merged CSR and who moves where (kp_merge.h); nothing of the context changes before every buffer is there ------------
+    int *merged = (int *)malloc(sizeof(int) * (nlists + 1)), *mv = (int *)malloc(sizeof(int) * 3 * B1);
+    struct Free { int *a, *b; ~Free() { free(a); free(b); } } guard{merged, mv};
+    if (!merged || !mv) return set_err(c, KPILQR_ERR_ALLOC, "host allocation failed");
+    int *const first_old = mv, *const first_new = mv + B1, *const upl_first = mv + 2 * B1;
+    if (!kp_merge_offsets(B, dof, c->kp_offsets_host, count, traj, kp_offsets, merged, first_old, first_new, upl_first))
+        return set_err(c, KPILQR_ERR_ARG, "kpilqr_update_keypoints: more key-point entries than an int counts");
+    const int total = merged[nlists], new_entries = kp_offsets[nnew];
+    int longest = 0, longest_kept = 0;
+    for (int b = 0; b < B; b++) {
+        if (first_new[b + 1] - first_new[b] > longest) longest = first_new[b + 1] - first_new[b];
+        if (upl_first[b] < 0 && first_old[b + 1] - first_old[b] > longest_kept) longest_kept = first_old[b + 1] - first_old[b];
+    }
+    // a payload laid out by entry survives: the records of everybody who is not listed move to their new offsets.  Job lists carry
+    // their own indices and stay as they are; without a payload there is nothing to carry.
+    const FdPayload kind = c->fd_payload;
+    const bool carry = kind == FdPayload::kp_ordered || (kind == FdPayload::kp_columns && c->kpc_valid);
+    DevMem *live = nullptr, *alt = nullptr;
+    size_t rec_bytes = 0;
+    if (kind == FdPayload::kp_ordered) { live = &c->fdk_dev; alt = &c->fdk_alt; rec_bytes = c->fdk_stride(); }
+    else { live = &c->kpc; alt = &c->kpc_alt; rec_bytes = (size_t)3 * c->n * 8; }
+    // Growth: the destinations are reserved FIRST (what reserve() frees is an old second buffer nobody reads any more), the copies
+    // read the live buffers, and only the swap retires those -- to become the second buffers of the next update
+    rc = reserve(c, c->kp_times_alt, (size_t)total * sizeof(int), Slack{4, 64 * sizeof(int)}, false);
+    if (rc < 0) return rc;
+    rc = reserve(c, c->kp_upl_times, (size_t)new_entries * sizeof(int), kQuarter, false);
+    if (rc < 0) return rc;
+    rc = reserve(c, c->kp_move, 3 * B1 * sizeof(int), kExact, false);
+    if (rc < 0) return rc;
+    if (carry) {
+        rc = reserve(c, *alt, (size_t)total * rec_bytes, kQuarter, false);
+        if (rc < 0) return rc;
+        // (a new column store starts zeroed, slack included, as ensure_kpc's does)
+        if (rc > 0 && kind == FdPayload::kp_columns) KP_HIP(c, hipMemsetAsync(alt->p, 0, alt->cap, c->stream));
+    }
+
+    // ---- enqueue: offsets and the move table up, lists merged, kept records moved, buffers swapped --------------------------------
+    const int *const mv_dev = c->kp_move;
+    KP_HIP(c, hipMemcpyAsync(c->kp_offsets, merged, (nlists + 1) * sizeof(int), hipMemcpyHostToDevice, c->stream));
+    KP_HIP(c, hipMemcpyAsync(c->kp_move, mv, 3 * B1 * sizeof(int), hipMemcpyHostToDevice, c->stream));
+    if (new_entries) KP_HIP(c, hipMemcpyAsync(c->kp_upl_times, kp_times, (size_t)new_entries * sizeof(int), hipMemcpyHostToDevice, c->stream));
+    KP_HIP(c, launch_merge_kp_times(c, longest, mv_dev, mv_dev + B1, mv_dev + 2 * B1, c->kp_times, c->kp_upl_times, c->kp_times_alt));
+    std::swap(c->kp_times, c->kp_times_alt);
+    if (carry) {
+        KP_HIP(c, launch_relocate_entries(c, (int)(rec_bytes / 16), longest_kept, mv_dev, mv_dev + B1, mv_dev + 2 * B1, live->p, alt->p));
+        std::swap(*live, *alt);
+    }
+    KP_HIP(c, launch_build_segmap(c));
+    c->segent_valid = c->segent != nullptr;
+    // the staging arrays above are this call's own: they are read before it returns
+    KP_HIP(c, hipStreamSynchronize(c->stream));
+
+    // ---- the context as kpilqr_set_keypoints(merged lists) leaves it -- except that the payload stays, with ranges pending ---------
+    for (int i = 0; i < count; i++) c->kp_flags_host[traj[i]] = kp_traj_flags(dof, c->d.T, kp_offsets + (size_t)i * dof, kp_times);
+    const unsigned char flags = kp_batch_flags(B, c->kp_flags_host);
+    c->kp_canonical = (flags & kKpCanonical) != 0;
+    c->kp_known_uniform = (flags & kKpUniform) && c->tune.fused_uni != 0;
+    free(c->kp_offsets_host);
+    c->kp_offsets_host = merged; guard.a = nullptr;
+    keypoints_changed(c, total);
+    if (!remember_traj_first(c, merged)) return set_err(c, KPILQR_ERR_ALLOC, "host allocation failed");
+    if (carry) {
+        if (!c->kp_pending_host) c->kp_pending_host = (int *)malloc(sizeof(int) * (size_t)B);
+        if (!c->kp_pending_host) return set_err(c, KPILQR_ERR_ALLOC, "host allocation failed");      // (the payload is dropped: as kpilqr_set_keypoints)
+        c->fd_payload = kind; c->fdk_entries = total; c->fdk_first = 0;
+        memcpy(c->kp_pending_host, traj, sizeof(int) * (size_t)count);
+        c->n_pending = count; c->pending_entries = new_entries;
+    }
     return KPILQR_OK;
 }
 
@@ -805,6 +933,9 @@ int kpilqr_generate_keypoints(kpilqr_ctx *c, const char *method, int min_N, int 
         keypoints_changed(c, total);
     }
     if (c->kp_traj_first_host) { free(c->kp_traj_first_host); c->kp_traj_first_host = nullptr; }
+    // (the lists exist on the device only: kpilqr_update_keypoints reads the offsets back when it first needs them)
+    if (!remember_lists(c, nullptr)) return set_err(c, KPILQR_ERR_ALLOC, "host allocation failed");
+    memset(c->kp_flags_host, kKpCanonical | (mth == 0 ? kKpUniform : 0), (size_t)c->d.batch);
     return KPILQR_OK;
 }
 
@@ -997,10 +1128,68 @@ int kpilqr_upload_kp_columns(kpilqr_ctx *c, const double *columns, int entries)
     return KPILQR_OK;
 }
 
+// ---- the pending ranges of kpilqr_update_keypoints filled in: one copy per run of adjacent trajectories, straight into place --------
+static int check_partial(kpilqr_ctx *c, const char *who, FdPayload kind, int count, const int *traj, int entries)
+{
+    const std::string w(who);
+    if (!payload_by_entry(c)) return set_err(c, KPILQR_ERR_STATE, w + ": no payload laid out by key-point entry is resident");
+    if (c->fd_payload != kind) return set_err(c, KPILQR_ERR_STATE, w + ": the resident payload is of the other kind (key-point ordered records / key-point columns)");
+    if (count != c->n_pending || (count > 0 && memcmp(traj, c->kp_pending_host, sizeof(int) * (size_t)count) != 0))
+        return set_err(c, KPILQR_ERR_ARG, w + ": traj is not the set of trajectories pending since kpilqr_update_keypoints");
+    if (entries != c->pending_entries) return set_err(c, KPILQR_ERR_ARG, w + ": `entries` is not the number of key-point entries of the listed trajectories");
+    return KPILQR_OK;
+}
+
+static int upload_runs(kpilqr_ctx *c, int count, const int *traj, const char *src, char *dst, size_t rec_bytes)
+{
+    const int *first = c->kp_traj_first_host;
+    for (int i = 0; i < count;) {
+        int j = i;
+        while (j + 1 < count && traj[j + 1] == traj[j] + 1) j++;
+        const size_t e0 = (size_t)first[traj[i]], bytes = ((size_t)first[traj[j] + 1] - e0) * rec_bytes;
+        if (bytes) KP_HIP(c, hipMemcpyAsync(dst + e0 * rec_bytes, src, bytes, hipMemcpyHostToDevice, c->stream));
+        src += bytes;
+        i = j + 1;
+    }
+    return KPILQR_OK;
+}
+
+int kpilqr_upload_fd_kp_partial(kpilqr_ctx *c, int count, const int *traj, const void *slab, int entries, double eps)
+{
+    if (!c || count < 0 || entries < 0 || (count > 0 && !traj) || (entries > 0 && !slab)) return KPILQR_ERR_ARG;
+    KP_ENTER(c);
+    if (count == 0 && entries == 0 && !c->n_pending) return KPILQR_OK;
+    int rc = check_partial(c, "kpilqr_upload_fd_kp_partial", FdPayload::kp_ordered, count, traj, entries);
+    if (rc) return rc;
+    if (memcmp(&eps, &c->eps, sizeof(double)) != 0)
+        return set_err(c, KPILQR_ERR_ARG, "kpilqr_upload_fd_kp_partial: eps differs from the resident payload's (a context has one eps)");
+    rc = upload_runs(c, count, traj, (const char *)slab, c->fdk_dev, c->fdk_stride());
+    if (rc) return rc;
+    payload_changed(c);                                  // complete again; whatever was derived from the old one is stale
+    if (!is_pinned(slab)) KP_HIP(c, hipStreamSynchronize(c->stream));
+    return KPILQR_OK;
+}
+
+int kpilqr_upload_kp_columns_partial(kpilqr_ctx *c, int count, const int *traj, const double *columns, int entries)
+{
+    if (!c || count < 0 || entries < 0 || (count > 0 && !traj) || (entries > 0 && !columns)) return KPILQR_ERR_ARG;
+    KP_ENTER(c);
+    if (count == 0 && entries == 0 && !c->n_pending) return KPILQR_OK;
+    int rc = check_partial(c, "kpilqr_upload_kp_columns_partial", FdPayload::kp_columns, count, traj, entries);
+    if (rc) return rc;
+    rc = upload_runs(c, count, traj, (const char *)columns, (char *)c->kpc.p, (size_t)3 * c->n * 8);
+    if (rc) return rc;
+    payload_changed(c);
+    c->kpc_valid = true;                                 // (the columns ARE the payload)
+    if (!is_pinned(columns)) KP_HIP(c, hipStreamSynchronize(c->stream));
+    return KPILQR_OK;
+}
+
 int kpilqr_fd_difference(kpilqr_ctx *c)
 {
     if (!c) return KPILQR_ERR_ARG;
     KP_ENTER(c);
+    { const int rcp = check_complete(c, "kpilqr_fd_difference"); if (rcp) return rcp; }
     if (c->fused) {
         // the sweeps read the key-point column store; the records, if something has asked for them, follow
         int rc = difference_to_kpc(c, !union_route(c));
@@ -1016,6 +1205,7 @@ int kpilqr_interpolate(kpilqr_ctx *c)
     if (!c) return KPILQR_ERR_ARG;
     KP_ENTER(c);
     if (!c->have_kp) return set_err(c, KPILQR_ERR_STATE, "kpilqr_interpolate before kpilqr_set_keypoints");
+    { const int rcp = check_complete(c, "kpilqr_interpolate"); if (rcp) return rcp; }
     if (c->fused) { const int rc = ensure_records(c); if (rc) return rc; }
     KP_HIP(c, launch_interpolate(c));
     return KPILQR_OK;
@@ -1027,6 +1217,7 @@ int kpilqr_fd_interpolate(kpilqr_ctx *c)
     if (!c) return KPILQR_ERR_ARG;
     KP_ENTER(c);
     if (!c->have_kp) return set_err(c, KPILQR_ERR_STATE, "kpilqr_fd_interpolate before kpilqr_set_keypoints");
+    { const int rcp = check_complete(c, "kpilqr_fd_interpolate"); if (rcp) return rcp; }
     if (c->fused) {
         // the sweeps of a fused context read the column store: it is differenced as kpilqr_fd_difference does; the records appear on
         // demand (allocated and zeroed) and are filled in one pass where the payload allows
@@ -1182,6 +1373,7 @@ int kpilqr_backward(kpilqr_ctx *c, const double *lambda, int pd_check_stride, in
     if (!c) return KPILQR_ERR_ARG;
     KP_ENTER(c);
     if (pd_check_stride < 1) return set_err(c, KPILQR_ERR_ARG, "pd_check_stride must be >= 1");
+    { const int rcp = check_complete(c, "kpilqr_backward"); if (rcp) return rcp; }
     if (lambda) KP_HIP(c, hipMemcpyAsync(c->lambda, lambda, (size_t)c->d.batch * 8, hipMemcpyHostToDevice, c->stream));
     int rc = run_backward(c, pd_check_stride);
     if (rc) return rc;
@@ -1200,6 +1392,7 @@ int kpilqr_backward_stats(kpilqr_ctx *c, int pd_check_stride, int *hist)
     KP_ENTER(c);
     if (!c->fused) return set_err(c, KPILQR_ERR_STATE, "kpilqr_backward_stats: fused contexts only");
     if (pd_check_stride < 1) return set_err(c, KPILQR_ERR_ARG, "pd_check_stride must be >= 1");
+    { const int rcp = check_complete(c, "kpilqr_backward_stats"); if (rcp) return rcp; }
     int rc = check_fused(c);
     if (rc) return rc;
     rc = ensure_kpc(c);
@@ -1227,6 +1420,24 @@ int kpilqr_download_gains(kpilqr_ctx *c, double *K, double *k)
     const size_t B = c->d.batch, T = c->d.T, n = c->n, m = c->d.m;
     if (K) KP_HIP(c, hipMemcpyAsync(K, c->K, B * T * n * m * 8, hipMemcpyDeviceToHost, c->stream));
     if (k) KP_HIP(c, hipMemcpyAsync(k, c->k, B * T * m * 8, hipMemcpyDeviceToHost, c->stream));
+    return KPILQR_OK;
+}
+
+// the gains of the listed trajectories, compact: one copy per array and run of adjacent trajectories
+int kpilqr_download_gains_partial(kpilqr_ctx *c, int count, const int *traj, double *K, double *k)
+{
+    if (!c || count < 0 || (count > 0 && !traj)) return KPILQR_ERR_ARG;
+    KP_ENTER(c);
+    if (!kp_traj_list_ok(c->d.batch, count, traj)) return set_err(c, KPILQR_ERR_ARG, "kpilqr_download_gains_partial: traj must be strictly increasing and within [0, batch)");
+    const size_t perK = (size_t)c->d.T * c->n * c->d.m, perk = (size_t)c->d.T * c->d.m;
+    for (int i = 0; i < count;) {
+        int j = i;
+        while (j + 1 < count && traj[j + 1] == traj[j] + 1) j++;
+        const size_t run = (size_t)(j - i + 1), b0 = (size_t)traj[i];
+        if (K) KP_HIP(c, hipMemcpyAsync(K + (size_t)i * perK, c->K + b0 * perK, run * perK * 8, hipMemcpyDeviceToHost, c->stream));
+        if (k) KP_HIP(c, hipMemcpyAsync(k + (size_t)i * perk, c->k + b0 * perk, run * perk * 8, hipMemcpyDeviceToHost, c->stream));
+        i = j + 1;
+    }
     return KPILQR_OK;
 }
 
@@ -1335,6 +1546,7 @@ int kpilqr_iterate(kpilqr_ctx *c, const double *lambda, int pd_check_stride, con
     KP_ENTER(c);
     if (!c->have_kp) return set_err(c, KPILQR_ERR_STATE, "kpilqr_iterate before kpilqr_set_keypoints");
     if (pd_check_stride < 1) return set_err(c, KPILQR_ERR_ARG, "pd_check_stride must be >= 1");
+    { const int rcp = check_complete(c, "kpilqr_iterate"); if (rcp) return rcp; }
     if (lambda) KP_HIP(c, hipMemcpyAsync(c->lambda, lambda, (size_t)c->d.batch * 8, hipMemcpyHostToDevice, c->stream));
     if (alphas) KP_HIP(c, hipMemcpyAsync(c->alphas, alphas, (size_t)c->d.n_alpha * 8, hipMemcpyHostToDevice, c->stream));
     if (!c->fused) {              // the fused sweeps difference (or read kpc), interpolate A, B and form l_* themselves
@@ -1386,6 +1598,11 @@ int kpilqr_iterate_streamed(kpilqr_ctx *c, const kpilqr_stream_io *io, int pd_ch
     KP_HIP(c, hipSetDevice(c->d.device));
     if (!c->have_kp) return set_err(c, KPILQR_ERR_STATE, "kpilqr_iterate_streamed before kpilqr_set_keypoints");
     if (pd_check_stride < 1) return set_err(c, KPILQR_ERR_ARG, "pd_check_stride must be >= 1");
+    // (a whole new payload completes the resident one; without it the pending ranges of kpilqr_update_keypoints would be read)
+    if (!io->fd_slab && !io->fd_kp_slab && !io->kp_columns) {
+        if (c->n_pending) { const int rcj = join_pipeline(c); if (rcj) return rcj; }
+        const int rcp = check_complete(c, "kpilqr_iterate_streamed without a new payload"); if (rcp) return rcp;
+    }
     const int B = c->d.batch;
     if (nchunks < 1) nchunks = Ctx::kPipeStreams;          // 0: one chunk per pipeline stream
     if (nchunks > B) nchunks = B;
@@ -1667,6 +1884,7 @@ int kpilqr_get_AB(kpilqr_ctx *c, double *A, double *B)
 {
     if (!c) return KPILQR_ERR_ARG;
     KP_ENTER(c);
+    { const int rcp = check_complete(c, "kpilqr_get_AB"); if (rcp) return rcp; }
     Staged s;
     const int rc = stage_AB(c, &s);
     if (rc) return rc;
@@ -1736,6 +1954,7 @@ int kpilqr_get_union_columns(kpilqr_ctx *c, double *columns, size_t capacity_dou
     if (!c->union_on) return set_err(c, KPILQR_ERR_STATE, "kpilqr_get_union_columns: KPILQR_FLAG_UNION_KEYPOINTS is not active on this context");
     if (!c->have_kp) return set_err(c, KPILQR_ERR_STATE, "no key-points set");
     if (c->fd_payload == FdPayload::none) return set_err(c, KPILQR_ERR_STATE, "kpilqr_get_union_columns: no FD payload resident");
+    { const int rcp = check_complete(c, "kpilqr_get_union_columns"); if (rcp) return rcp; }
     const int rc = prepare_union(c);
     if (rc) return rc;
     const size_t entries = (size_t)c->d.dof * c->kpu_total, count = entries * 3 * c->n;

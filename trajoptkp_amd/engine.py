@@ -146,6 +146,41 @@ class Engine:
         offs, times = rows_to_dof_csr(per_traj, self.dof, self.T)
         self.set_keypoints(offs, times)
 
+    # -- partial re-linearisation: new lists / payload for SOME trajectories ---------------------------
+    def _partial(self, name):
+        if not hasattr(self._L, name):
+            raise KpilqrError(_lib.ERR_ARG, f"this libkpilqr.so has no {name}")
+        return getattr(self._L, name)
+
+    def update_keypoints(self, traj, kp_offsets, kp_times):
+        """kpilqr_update_keypoints: per-DoF CSR (offsets [len(traj)*dof+1] from 0, times) of the listed trajectories alone; a
+        resident payload laid out by entry survives, their ranges pending until upload_fd_kp_partial / upload_kp_columns_partial."""
+        tr = np.ascontiguousarray(traj, dtype=np.int32).reshape(-1)
+        o = np.ascontiguousarray(kp_offsets, dtype=np.int32)
+        t = np.ascontiguousarray(kp_times, dtype=np.int32)
+        if o.shape != (len(tr) * self.dof + 1,):
+            raise ValueError("kp_offsets must have len(traj)*dof+1 entries")
+        if t.shape != (int(o[-1]),):
+            raise ValueError("kp_times length must equal kp_offsets[-1]")
+        self._ck(self._partial("kpilqr_update_keypoints")(self._h, len(tr), _ptr(tr), _ptr(o), _ptr(t if len(t) else np.zeros(1, np.int32))))
+
+    def update_keypoints_rows(self, traj, per_traj):
+        """per_traj: one (offs[T+1], cols) pair -- the reference's keypoints[t] lists -- per trajectory of `traj`."""
+        if len(per_traj) != len(traj):
+            raise ValueError("one (offs, cols) pair per listed trajectory")
+        offs, times = rows_to_dof_csr(per_traj, self.dof, self.T)
+        self.update_keypoints(traj, offs, times)
+
+    def upload_fd_kp_partial(self, traj, s, eps=1e-6):
+        """kpilqr_upload_fd_kp_partial: s = fd_kp_slab(...) of the listed trajectories' entries, back to back in traj order."""
+        tr = np.ascontiguousarray(traj, dtype=np.int32).reshape(-1)
+        self._ck(self._partial("kpilqr_upload_fd_kp_partial")(self._h, len(tr), _ptr(tr), _ptr(s["slab"]), s["entries"], float(eps)))
+
+    def upload_kp_columns_partial(self, traj, s):
+        """kpilqr_upload_kp_columns_partial: s = kp_columns(...) of the listed trajectories' entries, back to back in traj order."""
+        tr = np.ascontiguousarray(traj, dtype=np.int32).reshape(-1)
+        self._ck(self._partial("kpilqr_upload_kp_columns_partial")(self._h, len(tr), _ptr(tr), _ptr(s["cols"]), s["entries"]))
+
     # -- key-point placement on the device (SURVEY 8f.2) ----------------------------------------------
     def upload_states(self, X):
         X = _f64(X, (self.batch, self.T, self.n))
@@ -393,9 +428,17 @@ class Engine:
         self._ck(self._L.kpilqr_backward_stats(self._h, int(pd_stride), _ptr(h)))
         return h
 
-    def gains(self):
-        K = np.zeros((self.batch, self.T, self.n, self.m)); k = np.zeros((self.batch, self.T, self.m))
-        self._ck(self._L.kpilqr_download_gains(self._h, _ptr(K), _ptr(k)))
+    def gains(self, traj=None, want_K=True, want_k=True):
+        """K, k of the last backward pass; traj: of those trajectories alone (kpilqr_download_gains_partial), compact, in traj
+        order.  An array that is not wanted comes back as None."""
+        nb = self.batch if traj is None else len(traj)
+        K = np.zeros((nb, self.T, self.n, self.m)) if want_K else None
+        k = np.zeros((nb, self.T, self.m)) if want_k else None
+        if traj is None:
+            self._ck(self._L.kpilqr_download_gains(self._h, _ptr(K), _ptr(k)))
+        else:
+            tr = np.ascontiguousarray(traj, dtype=np.int32).reshape(-1)
+            self._ck(self._partial("kpilqr_download_gains_partial")(self._h, len(tr), _ptr(tr), _ptr(K), _ptr(k)))
         self.sync()
         return K, k
 

@@ -108,8 +108,20 @@ int kpilqr_host_run_acrobot_batch(int B, int T, int min_N, int max_iter, int min
 
 // ... with a key-point method by name (NULL: the task's default, set_interval): the adaptive methods give every trajectory its own
 // per-DoF lists, whose counts change from one linearisation to the next
+int kpilqr_host_run_acrobot_batch3(int B, int T, int min_N, int max_iter, int min_iter, double torque_weight, const double *q0s,
+                                   int fused, const char *method, double *cost_history, int cost_cap, int *iterations, double *U_out, double *stats,
+                                   double *traffic, int traffic_cap);
 int kpilqr_host_run_acrobot_batch2(int B, int T, int min_N, int max_iter, int min_iter, double torque_weight, const double *q0s,
                                    int fused, const char *method, double *cost_history, int cost_cap, int *iterations, double *U_out, double *stats)
+{
+    return kpilqr_host_run_acrobot_batch3(B, T, min_N, max_iter, min_iter, torque_weight, q0s, fused, method, cost_history, cost_cap, iterations, U_out, stats, nullptr, 0);
+}
+
+// ... and what crossed the link: traffic [traffic_cap] = FD payload bytes uploaded, gain bytes downloaded, number of linearisations,
+// then the batch's key-point entries at each of them (as many as fit)
+int kpilqr_host_run_acrobot_batch3(int B, int T, int min_N, int max_iter, int min_iter, double torque_weight, const double *q0s,
+                                   int fused, const char *method, double *cost_history, int cost_cap, int *iterations, double *U_out, double *stats,
+                                   double *traffic, int traffic_cap)
 {
     std::vector<iLQR_GPU_Batch::Problem> probs;
     for (int b = 0; b < B; b++) {
@@ -136,6 +148,11 @@ int kpilqr_host_run_acrobot_batch2(int B, int T, int min_N, int max_iter, int mi
         if (U_out) for (int t = 0; t < T; t++) U_out[(size_t)b * T + t] = U[b][t](0);
     }
     if (stats) for (int i = 0; i < 8; i++) stats[i] = opt.linesearch_stats[i];
+    if (traffic && traffic_cap >= 3) {
+        traffic[0] = (double)opt.payload_bytes_uploaded; traffic[1] = (double)opt.gain_bytes_downloaded;
+        traffic[2] = (double)opt.linearisation_entries.size();
+        for (size_t i = 0; i < opt.linearisation_entries.size() && 3 + (int)i < traffic_cap; i++) traffic[3 + i] = opt.linearisation_entries[i];
+    }
     return 0;
 }
 

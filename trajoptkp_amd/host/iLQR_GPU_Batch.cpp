@@ -65,7 +65,8 @@ iLQR_GPU_Batch::~iLQR_GPU_Batch()
     kpilqr_sync(ctx);
     staging.free_all();
     if (kp_slab) kpilqr_host_free(ctx, kp_slab);
-    kp_slab = nullptr;
+    if (kp_part) kpilqr_host_free(ctx, kp_part);
+    kp_slab = kp_part = nullptr;
     double **all[] = {&host_r, &host_rx, &host_ru, &host_unom, &host_K, &host_k};
     for (double **p : all) { if (*p) kpilqr_host_free(ctx, *p); *p = nullptr; }
     kpilqr_destroy(ctx);
@@ -167,7 +168,9 @@ std::vector<std::vector<double>> iLQR_GPU_Batch::DofImportance(int sampling_k_in
 // on the host (every trajectory on its own persistent pool, all into ONE pinned slab), then the GPU
 // stages for the whole batch.  Trajectories not in `who` keep their linearisation: on a materialising context their key-point
 // columns stay in the step records at (b, t); on a fused context -- which holds no records, only the column store indexed by CSR
-// entry -- the host slab is the authoritative copy of every trajectory's payload and the WHOLE batch goes up key-point ordered.
+// entry -- the host slab is the authoritative copy of every trajectory's payload.  The first complete regeneration sends it whole; a
+// partial one sends the records of `who` alone (kpilqr_update_keypoints + kpilqr_upload_fd_kp_partial): the library moves the
+// others' records to their new entry offsets on the device.
 void iLQR_GPU_Batch::GenerateDerivatives(const std::vector<int> &who)
 {
     const int n = 2 * dof, m = num_ctrl;
@@ -200,15 +203,18 @@ void iLQR_GPU_Batch::GenerateDerivatives(const std::vector<int> &who)
     }
     // Fused sweeps take the payload KEY-POINT ORDERED (one record per CSR entry, written in place by the FD workers, no job
     // lists: iLQR_GPU.cpp), ALWAYS: new key-points re-index the device's column store, so the records of the trajectories
-    // that do NOT regenerate (their last step was rejected, iLQR.cpp:419) must go up again too, at their NEW entry offsets --
+    // that do NOT regenerate (their last step was rejected, iLQR.cpp:419) have to sit at their NEW entry offsets --
     // the adaptive methods move the counts of the regenerating trajectories and with them everybody else's offsets.  The
-    // host slab of the previous call holds those records; they are moved to their new places, `who` is filled in place.
+    // host slab of the previous call holds those records; they are moved to their new places, `who` is filled in place.  The
+    // device does the same move on its own copy (kpilqr_update_keypoints), so only the records of `who` cross the link: they
+    // are written into a second pinned slab, back to back in trajectory order, and copied from there into the batch slab.
     // (Round 3 uploaded a job list of `who` alone when the CSR had moved: the others' entries then held stale or zero columns.)
     const bool kp_ordered = fused_active;
     kpilqr_fdkp_layout lay = {};
+    const bool partial = kp_ordered && (int)who.size() != B;
+    std::vector<int> who_offs(1, 0), who_times, who_first;      // the lists of `who` as their own CSR; first packed entry of each
     if (kp_ordered) {
         if ((rc = kpilqr_fd_kp_layout(ctx, offs.back(), &lay))) fatal("kpilqr_fd_kp_layout", rc);
-        const bool partial = (int)who.size() != B;
         if (partial && kp_slab_offs.empty()) fatal("partial regeneration before any complete one", -1);
         std::vector<char> regen(B, 0);
         for (int b : who) regen[b] = 1;
@@ -222,6 +228,21 @@ void iLQR_GPU_Batch::GenerateDerivatives(const std::vector<int> &who)
         } else if (partial && kp_slab_offs != offs) {
             relocate_records(kp_slab, kp_slab, lay.entry_stride, B, dof, kp_slab_offs, offs, regen);
         }
+        if (partial) {
+            for (int b : who) {
+                const Traj &s = S[b];
+                who_first.push_back(who_offs.back());
+                for (int i = 0; i < dof; i++) who_offs.push_back(who_offs.back() + (s.kp_offsets[i + 1] - s.kp_offsets[i]));
+                who_times.insert(who_times.end(), s.kp_times.begin(), s.kp_times.end());
+            }
+            const size_t need = (size_t)who_offs.back() * lay.entry_stride;
+            if (need > kp_part_bytes) {
+                if (kp_part) kpilqr_host_free(ctx, kp_part);
+                kp_part_bytes = need + need / 4 + 4096;
+                kp_part = nullptr;
+                if ((rc = kpilqr_host_alloc(ctx, kp_part_bytes, (void **)&kp_part))) fatal("kpilqr_host_alloc", rc);
+            }
+        }
     } else {
         int tot_jobs = 0, tot_kps = 0;
         for (int b : who) { int j, k_; P[b].differentiator->CountJobs(S[b].kpgen->keypoints, j, k_); tot_jobs += j; tot_kps += k_; }
@@ -229,18 +250,34 @@ void iLQR_GPU_Batch::GenerateDerivatives(const std::vector<int> &who)
         kp_slab_offs.clear();                                  // the job-list payload replaces the records on the device
     }
     // pass 2: FD of every trajectory on its own persistent pool, all into the ONE pinned slab, trajectories in order
-    for (int b : who) {
+    for (size_t w = 0; w < who.size(); w++) {
+        const int b = who[w];
         Traj &s = S[b];
         Differentiator &diff = *P[b].differentiator;
-        if (kp_ordered) diff.DynamicsDerivativesKp(kp_slab, lay.entry_stride, offs[(size_t)b * dof], s.kp_offsets, s.kp_times, s.kpgen->keypoints, eps);
+        if (partial) {
+            diff.DynamicsDerivativesKp(kp_part, lay.entry_stride, who_first[w], s.kp_offsets, s.kp_times, s.kpgen->keypoints, eps);
+            std::memcpy(kp_slab + (size_t)offs[(size_t)b * dof] * lay.entry_stride, kp_part + (size_t)who_first[w] * lay.entry_stride,
+                        (size_t)(who_offs[(w + 1) * dof] - who_offs[w * dof]) * lay.entry_stride);
+        }
+        else if (kp_ordered) diff.DynamicsDerivativesKp(kp_slab, lay.entry_stride, offs[(size_t)b * dof], s.kp_offsets, s.kp_times, s.kpgen->keypoints, eps);
         else diff.DynamicsDerivativesPlanned(staging, b, s.kpgen->keypoints, eps);
         for (int t = 0; t <= T; t++)
             for (int i = 0; i < nr; i++) host_r[((size_t)b * (T + 1) + t) * nr + i] = s.residuals[t](i);
         if (!const_jacobians) diff.ResidualDerivativesAll(host_rx + (size_t)b * (T + 1) * nr * n, host_ru + (size_t)b * (T + 1) * nr * m, T, eps);
     }
-    if ((rc = kpilqr_set_keypoints(ctx, offs.data(), times.data()))) fatal("kpilqr_set_keypoints", rc);
-    if (kp_ordered) {
+    linearisation_entries.push_back(offs.back());
+    if (partial) {
+        // the lists and the records of `who` alone; the library keeps everybody else's and moves their records on the device
+        if (who_times.empty()) who_times.push_back(0);          // (never read: a non-null pointer for lists without entries)
+        if ((rc = kpilqr_update_keypoints(ctx, (int)who.size(), who.data(), who_offs.data(), who_times.data()))) fatal("kpilqr_update_keypoints", rc);
+        if ((rc = kpilqr_upload_fd_kp_partial(ctx, (int)who.size(), who.data(), kp_part, who_offs.back(), eps))) fatal("kpilqr_upload_fd_kp_partial", rc);
+        payload_bytes_uploaded += (size_t)who_offs.back() * lay.entry_stride;
+        kp_slab_offs = offs;
+    } else if ((rc = kpilqr_set_keypoints(ctx, offs.data(), times.data()))) {
+        fatal("kpilqr_set_keypoints", rc);
+    } else if (kp_ordered) {
         if ((rc = kpilqr_upload_fd_kp(ctx, kp_slab, offs.back(), eps))) fatal("kpilqr_upload_fd_kp", rc);
+        payload_bytes_uploaded += lay.bytes;
         kp_slab_offs = offs;
     } else {
         // the slab's array offsets were computed from the PLANNED totals: an under-filled plan would make the device read
@@ -248,6 +285,8 @@ void iLQR_GPU_Batch::GenerateDerivatives(const std::vector<int> &who)
         if (!staging.complete()) { std::fprintf(stderr, "FD staging: %d of %d jobs, %d of %d nominal rows filled\n", staging.njobs, staging.plan_jobs, staging.nnom, staging.plan_noms); std::exit(1); }
         rc = kpilqr_upload_fd_slab(ctx, staging.slab, staging.njobs, staging.nnom, eps);
         if (rc) fatal("kpilqr_upload_fd_slab", rc);
+        kpilqr_fd_layout jl;
+        if (kpilqr_fd_slab_layout(ctx, staging.njobs, staging.nnom, &jl) == KPILQR_OK) payload_bytes_uploaded += jl.bytes;
     }
     // a materialising context: A, B of every step in one call (one pass over the records for a key-point ordered payload); the
     // fused sweeps interpolate themselves and want the differenced key-point columns only
@@ -318,7 +357,11 @@ std::vector<std::vector<MatrixXd>> iLQR_GPU_Batch::OptimiseAll(const std::vector
             for (int t = 0; t < T; t++) for (int i = 0; i < m; i++) host_unom[((size_t)b * T + t) * m + i] = S[b].U_old[t](i);
         if ((rc = kpilqr_upload_nominal(ctx, host_unom, ctrl_lim.data()))) fatal("kpilqr_upload_nominal", rc);
         if ((rc = kpilqr_forward_linear(ctx, alphas.data(), pred.data(), nullptr))) fatal("kpilqr_forward_linear", rc);
-        if ((rc = kpilqr_download_gains(ctx, host_K, host_k))) fatal("kpilqr_download_gains", rc);
+        // K, k only of the trajectories that will use them (active, with a valid backward pass): compact, in trajectory order
+        std::vector<int> fetch, fetch_row(B, -1);
+        for (int b : active) if (valid[b]) { fetch_row[b] = (int)fetch.size(); fetch.push_back(b); }
+        if (!fetch.empty() && (rc = kpilqr_download_gains_partial(ctx, (int)fetch.size(), fetch.data(), host_K, host_k))) fatal("kpilqr_download_gains_partial", rc);
+        gain_bytes_downloaded += fetch.size() * ((size_t)T * n * m + (size_t)T * m) * sizeof(double);
         if ((rc = kpilqr_sync(ctx))) fatal("kpilqr_sync", rc);
         for (double &v : linesearch_stats) v = 0.0;
         for (int b : active) {
@@ -329,9 +372,10 @@ std::vector<std::vector<MatrixXd>> iLQR_GPU_Batch::OptimiseAll(const std::vector
         for (int b : active) {
             Traj &s = S[b];
             if (!valid[b]) { cost_history[b].push_back(s.new_cost); continue; }
+            const size_t row = (size_t)fetch_row[b];
             for (int t = 0; t < T; t++) {
-                for (int c = 0; c < n; c++) for (int r = 0; r < m; r++) K[b][t](r, c) = host_K[(((size_t)b * T + t) * n + c) * m + r];
-                for (int r = 0; r < m; r++) k[b][t](r) = host_k[((size_t)b * T + t) * m + r];
+                for (int c = 0; c < n; c++) for (int r = 0; r < m; r++) K[b][t](r, c) = host_K[((row * T + t) * n + c) * m + r];
+                for (int r = 0; r < m; r++) k[b][t](r) = host_k[(row * T + t) * m + r];
             }
             const int na = (int)alphas.size();
             int best = -1;

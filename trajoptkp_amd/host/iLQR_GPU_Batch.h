@@ -42,6 +42,11 @@ public:
     // line-search statistics of the last iteration, the 8 doubles of the multi-GPU reduction
     // (sum_b J_pred(alpha_1..6), sum_b delta_J, #valid backward passes) -- SURVEY.md section 8e
     double linesearch_stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    // what crossed the link since construction: FD payload bytes up (whole slabs, or the regenerating trajectories' records alone
+    // after a partial regeneration on a fused context), gain bytes down (K, k of the active trajectories with a valid backward
+    // pass); and the batch's key-point entries at every linearisation
+    size_t payload_bytes_uploaded = 0, gain_bytes_downloaded = 0;
+    std::vector<int> linearisation_entries;
     // regularisation / line search constants (include/Optimiser/Optimiser.h:239-242,259,303)
     double max_lambda = 10.0, min_lambda = 0.0001, lambda_factor = 10, epsConverge = 0.02;
     int num_parallel_rollouts = 6;
@@ -73,6 +78,8 @@ private:
     // iterations so that a partial regeneration refills only its trajectories' records while the entry layout stays the same
     char *kp_slab = nullptr;
     size_t kp_slab_bytes = 0;
+    char *kp_part = nullptr;                // pinned: the records of a partial regeneration's trajectories, back to back
+    size_t kp_part_bytes = 0;
     std::vector<int> kp_slab_offs;          // the batch CSR the slab's records were laid out for (empty: no valid slab)
     bool const_jacobians = false, const_jacobians_resident = false;     // the task's ONE residual Jacobian pair: uploaded once
     std::vector<double> const_rx, const_ru;
