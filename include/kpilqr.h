@@ -211,9 +211,9 @@ int  kpilqr_set_keypoints(kpilqr_ctx *ctx, const int *kp_offsets, const int *kp_
  * per-trajectory layout of kpilqr_download_gains: one copy per array and run of adjacent trajectories, asynchronous; either
  * pointer may be NULL.
  *
- * Out of scope: residuals still go up for the whole batch (kpilqr_upload_residuals); job-list payloads are not carried; the
- * chunks of kpilqr_iterate_streamed are unchanged; nothing derived from the payload stays valid across an update; and
- * kpilqr_generate_keypoints places key-points for the whole batch only. */
+ * Out of scope: job-list payloads are not carried; the chunks of kpilqr_iterate_streamed are unchanged; nothing derived from the
+ * payload stays valid across an update; and kpilqr_generate_keypoints places key-points for the whole batch only.  (Residuals,
+ * nominal controls and step records of a subset: the calls further down, "partial re-linearisation, the rest".) */
 int  kpilqr_update_keypoints(kpilqr_ctx *ctx, int count, const int *traj,
                              const int *kp_offsets /* [count*dof + 1], starts at 0 */, const int *kp_times);
 int  kpilqr_upload_fd_kp_partial(kpilqr_ctx *ctx, int count, const int *traj,
@@ -222,6 +222,48 @@ int  kpilqr_upload_kp_columns_partial(kpilqr_ctx *ctx, int count, const int *tra
                                       const double *columns, int entries);
 int  kpilqr_download_gains_partial(kpilqr_ctx *ctx, int count, const int *traj,
                                    double *K /* [count][T][n][m] */, double *k /* [count][T][m] */);
+
+/* ---- partial re-linearisation, the rest: residuals, nominal controls and step records of SOME trajectories -------------------
+ * What else a linearisation of a subset moves and recomputes.  All four calls take (count, traj) with the contract of
+ * kpilqr_update_keypoints: `traj` [count] strictly increasing and within [0, batch), else KPILQR_ERR_ARG and nothing is enqueued or
+ * changed; count = 0 is a no-op returning KPILQR_OK; a NULL context is KPILQR_ERR_ARG; not through a view of
+ * kpilqr_iterate_streamed's chunks (KPILQR_ERR_STATE).  Host arrays are COMPACT: the listed trajectories' rows back to back in `traj`
+ * order.  Copies go out as one hipMemcpyAsync per array and run of adjacent trajectories, straight to their place (as
+ * kpilqr_download_gains_partial): no staging buffer, no scatter kernel.  KPILQR_VERSION is unchanged: detect them by their symbols.
+ *
+ * kpilqr_upload_residuals_partial: r [count][T+1][nr], r_x [count][T+1][nr][n], r_u [count][T+1][nr][m]; NULL = not sent.  Weights
+ * stay with kpilqr_upload_residuals.  Rows of a subset never change the form the sweeps run in, so each of these is refused with
+ * KPILQR_ERR_STATE, changes nothing, and names the whole-batch call to make first:
+ *   r_x  in constant-Jacobian mode (kpilqr_upload_residual_jacobians_const), or before a whole r_x has been uploaded -- every
+ *        other row of the buffer has to mean something;
+ *   r_u  before a whole r_u upload or broadcast: a context that runs the r_u-free sweeps (":ru0") is not flipped by a few rows.
+ * r has no precondition.  Nothing else changes state: payload, key-points, pending ranges and kpilqr_last_launch are untouched.
+ * The odd-residual-count rule of kpilqr_upload_residuals ("all T+1 rows finite") applies to the rows sent.
+ * kpilqr_upload_nominal_partial: u_nom [count][T][m] (NULL = not sent); control limits stay with kpilqr_upload_nominal.
+ *
+ * kpilqr_fd_interpolate_partial / kpilqr_cost_derivs_partial are kpilqr_fd_interpolate / kpilqr_cost_derivs for the listed
+ * trajectories only: in their records the results are bit for bit what the whole-batch call writes there, and no byte of any
+ * other trajectory's records is written.  The caller's contract: the other trajectories' records hold a complete linearisation from
+ * an earlier whole or partial call, and their lists, payload, residuals and weights have not changed since.  ONE launch per stage
+ * for the whole list, however scattered it is (the kernels read the trajectory of a block row from a device copy of the list,
+ * batch ints held by the context, filled by one hipMemcpyAsync; the call waits for the stream only when `traj` is pageable, as
+ * kpilqr_set_keypoints does).  With a job-list payload k_fd_difference runs over the RESIDENT jobs -- those of kept trajectories
+ * rewrite what their records hold; a host that uploads the listed trajectories' jobs alone touches nobody else -- and k_interpolate
+ * over the list.  With KPILQR_FD_INTERP=0 the three-pass sequence runs with its record-writing passes restricted to the list (the
+ * column scatter once per run of adjacent trajectories: a diagnostic path).  kpilqr_fd_interpolate_partial is KPILQR_ERR_STATE
+ * before any key-points exist and while ranges are pending after kpilqr_update_keypoints; kpilqr_cost_derivs_partial makes the
+ * broadcast copy of constant Jacobians as kpilqr_cost_derivs does.  On a KPILQR_FLAG_FUSED context both return KPILQR_ERR_STATE: it
+ * holds no persistent records and its sweeps read the column store.  kpilqr_last_launch(ctx, 2) reports the form with ":subset"
+ * appended ("fd_kp_interpolate:subset", "kp_columns_interpolate:subset", "fd_difference+interpolate:subset").
+ *
+ * Out of scope: the sweeps still run over the whole batch; kpilqr_generate_keypoints and kpilqr_upload_states for a subset; keeping
+ * the column store, slope store and union store of kept trajectories on a KPILQR_FLAG_FUSED context; kpilqr_iterate and
+ * kpilqr_iterate_streamed (whole batch); job-list payloads carried across kpilqr_update_keypoints. */
+int  kpilqr_upload_residuals_partial(kpilqr_ctx *ctx, int count, const int *traj,
+                                     const double *r, const double *r_x, const double *r_u);
+int  kpilqr_upload_nominal_partial(kpilqr_ctx *ctx, int count, const int *traj, const double *u_nom);
+int  kpilqr_fd_interpolate_partial(kpilqr_ctx *ctx, int count, const int *traj);
+int  kpilqr_cost_derivs_partial(kpilqr_ctx *ctx, int count, const int *traj);
 
 /* Key-point placement on the device for the whole batch (optional).
  * X [batch][T][n]: the nominal trajectory states (positions then velocities), as Optimiser::X_old. */
@@ -512,6 +554,7 @@ const char *kpilqr_forward_variant(kpilqr_ctx *ctx);
  *     "fd_difference+interpolate"  the separate passes (job lists, or KPILQR_FD_INTERP=0)
  *     "in_sweep"                   KPILQR_FLAG_FUSED context: the sweeps difference and interpolate themselves
  *     "kp_union"                   the same on the union store of KPILQR_FLAG_UNION_KEYPOINTS (kpilqr_iterate with per-DoF lists)
+ * with ":subset" appended when the last linearisation was a kpilqr_fd_interpolate_partial.
  * For logs and tests (a test can assert which kernel form it exercised).  version >= 400. */
 const char *kpilqr_last_launch(kpilqr_ctx *ctx, int which);
 

@@ -30,12 +30,14 @@ SYMBOLS = [
     "kpilqr_upload_kp_columns", "kpilqr_upload_residual_jacobians_const", "kpilqr_last_launch",
     "kpilqr_fd_interpolate", "kpilqr_get_union_keypoints", "kpilqr_get_union_columns",
     "kpilqr_update_keypoints", "kpilqr_upload_fd_kp_partial", "kpilqr_upload_kp_columns_partial", "kpilqr_download_gains_partial",
+    "kpilqr_upload_residuals_partial", "kpilqr_upload_nominal_partial", "kpilqr_fd_interpolate_partial", "kpilqr_cost_derivs_partial",
 ]
 # entry points added without a version bump (include/kpilqr.h: "detect the entry point by its symbol"): bound only when the library
 # has them -- KPILQR_LIB may name an older build of the same major version
 OPTIONAL_SYMBOLS = {"kpilqr_fd_interpolate", "kpilqr_get_union_keypoints", "kpilqr_get_union_columns",
                     "kpilqr_update_keypoints", "kpilqr_upload_fd_kp_partial", "kpilqr_upload_kp_columns_partial",
-                    "kpilqr_download_gains_partial"}
+                    "kpilqr_download_gains_partial", "kpilqr_upload_residuals_partial", "kpilqr_upload_nominal_partial",
+                    "kpilqr_fd_interpolate_partial", "kpilqr_cost_derivs_partial"}
 
 
 class Dims(C.Structure):
@@ -155,6 +157,11 @@ def load():
         L.kpilqr_upload_fd_kp_partial.argtypes = [vp, C.c_int, vp, vp, C.c_int, C.c_double]
         L.kpilqr_upload_kp_columns_partial.argtypes = [vp, C.c_int, vp, vp, C.c_int]
         L.kpilqr_download_gains_partial.argtypes = [vp, C.c_int, vp, vp, vp]
+    if hasattr(L, "kpilqr_upload_residuals_partial"):
+        L.kpilqr_upload_residuals_partial.argtypes = [vp, C.c_int, vp, vp, vp, vp]
+        L.kpilqr_upload_nominal_partial.argtypes = [vp, C.c_int, vp, vp]
+        L.kpilqr_fd_interpolate_partial.argtypes = [vp, C.c_int, vp]
+        L.kpilqr_cost_derivs_partial.argtypes = [vp, C.c_int, vp]
     for s in SYMBOLS:
         if s in OPTIONAL_SYMBOLS and not hasattr(L, s):
             continue

@@ -101,6 +101,7 @@ struct Ctx {
     DevBuf<double> delta_J;       // [batch]
     DevBuf<double> traj_cost;     // [batch]
     DevBuf<int> status;           // [batch]
+    DevBuf<int> traj_list;        // [batch]: the trajectories of the partial record calls in flight (kpilqr_fd_interpolate_partial ...)
     DevBuf<int2> segmap;          // [batch][dof][T]: (start,end) key-points around t, or (-1,-1)
     // [batch][dof][T]: CSR entry of the key-point at or before t (the one-pass linearisation fetches a segment's endpoints by
     // entry), or -1 outside the list.  Built with segmap on a context that has records; on demand on a fused one (segent_valid)
@@ -118,6 +119,7 @@ struct Ctx {
     // holds the broadcast copy (made on demand for every other kernel family, ensure_rx_buffer)
     DevBuf<double> rx_const;
     bool rx_const_on = false, rx_buf_valid = true;
+    bool rx_whole = false;       // every row of the r_x buffer has been given (a whole upload, the broadcast copy): rows of a subset may replace some
 
     // ---- fused contexts: the key-point column store (no step records) ---------------------------------------------------
     // A fused (one-tile) context does not allocate step records: its sweeps read the differenced key-point columns from
@@ -233,7 +235,7 @@ struct Ctx {
     void for_each_buffer(F f)
     {
         DevMem *const all[] = {&rec, &kp_uniform, &K, &k, &r, &r_x, &r_u, &w_run, &w_term, &u_nom, &ctrl_lim, &lambda, &alphas, &cost_pred,
-                               &delta_J, &traj_cost, &status, &segmap, &segent, &kp_offsets, &kp_times, &rx_const, &kpc, &kps, &kp_entry,
+                               &delta_J, &traj_cost, &status, &traj_list, &segmap, &segent, &kp_offsets, &kp_times, &rx_const, &kpc, &kps, &kp_entry,
                                &kp_entry_list, &fdk_dev, &kpu_offsets, &kpu_times, &kpu_src, &kpu_traj_first, &kpcu, &kpu_uniform, &fdk_alt, &kpc_alt, &kp_times_alt, &kp_upl_times, &kp_move, &X_states, &kp_thr, &kp_mask, &kp_count, &ls8, &fd_dev, &err_flag, &stage};
         for (DevMem *b : all) f(*b);
     }
@@ -303,12 +305,12 @@ hipError_t launch_pack_linesearch(Ctx *c, double *dev8);
 hipError_t launch_generate_keypoints(Ctx *c, int method, int min_N, int max_N, double dt, const double *thr_dev,
                                      const double *X_dev, unsigned long long *mask_dev, int *count_dev);
 hipError_t launch_kp_error_test(Ctx *c, int n_iv, const int *iv_dev, int min_N, double threshold, unsigned char *good_dev);
-hipError_t launch_interpolate(Ctx *c);
+hipError_t launch_interpolate(Ctx *c, const int *traj = nullptr, int count = 0);      // traj (device): those trajectories alone
 // linearise.hip: key-point ordered payload (FdPayload::kp_ordered) or column payload (kp_columns) -> every step record's [A|B], a2 + a4 in one pass
-hipError_t launch_fd_kp_interpolate(Ctx *c);
+hipError_t launch_fd_kp_interpolate(Ctx *c, const int *traj = nullptr, int count = 0);
 hipError_t launch_filter_dynamics(Ctx *c, int method, const double *coefs_dev, int ncoef);
 hipError_t launch_dof_importance(Ctx *c, int sampling, double *sums_dev);
-hipError_t launch_cost_derivs(Ctx *c);
+hipError_t launch_cost_derivs(Ctx *c, const int *traj = nullptr, int count = 0);
 hipError_t launch_broadcast_rx(Ctx *c);                  // rx_const -> r_x [batch][T+1][nr][n]
 hipError_t launch_broadcast(hipStream_t s, const double *src_dev, int len, double *dst_dev, size_t reps);   // dst [reps][len] = src [len]
 hipError_t launch_trajectory_cost(Ctx *c);

@@ -430,12 +430,12 @@ hipError_t launch_build_segmap(Ctx *c, bool segent_only)
 // (KeyPointGenerator.cpp:900,934) -- compiled without FMA contraction.
 #define INTERP_TT 16
 __global__ void __launch_bounds__(256)
-k_interpolate(RecLayout L, int dof, int T, const int2 *__restrict__ segmap, double *__restrict__ rec)
+k_interpolate(RecLayout L, int dof, int T, const int2 *__restrict__ segmap, double *__restrict__ rec, const int *__restrict__ traj)
 {
     extern __shared__ __attribute__((aligned(16))) int2 ssm[];      // [dof][INTERP_TT]
     const int n = L.n, m = L.m;
     const int ne = n * n + n * m;               // even: n = 2*dof
-    const int b = blockIdx.y;
+    const int b = traj ? traj[blockIdx.y] : blockIdx.y;      // a subset (kpilqr_fd_interpolate_partial): block-uniform, a scalar load
     const int t0 = blockIdx.x * INTERP_TT;
     const int nt = min(INTERP_TT, T - t0);
     double *R = rec + (size_t)b * T * L.stride;
@@ -472,14 +472,16 @@ k_interpolate(RecLayout L, int dof, int T, const int2 *__restrict__ segmap, doub
     }
 }
 
-hipError_t launch_interpolate(Ctx *c)
+// traj (device, count trajectories): the listed trajectories alone, one block row each; null: the whole batch
+hipError_t launch_interpolate(Ctx *c, const int *traj, int count)
 {
-    dim3 grid((c->d.T + INTERP_TT - 1) / INTERP_TT, c->d.batch);
+    if (traj && count <= 0) return hipSuccess;
+    dim3 grid((c->d.T + INTERP_TT - 1) / INTERP_TT, traj ? count : c->d.batch);
     const int ne = c->n * c->n + c->n * c->d.m;
     int threads = ((ne / 2 + 63) / 64) * 64;
     if (threads > 256) threads = 256;
     const size_t lds = sizeof(int2) * c->d.dof * INTERP_TT;
-    hipLaunchKernelGGL(k_interpolate, grid, dim3(threads), lds, c->stream, c->L, c->d.dof, c->d.T, c->segmap, c->rec);
+    hipLaunchKernelGGL(k_interpolate, grid, dim3(threads), lds, c->stream, c->L, c->d.dof, c->d.T, c->segmap, c->rec, traj);
     return hipGetLastError();
 }
 
@@ -491,12 +493,13 @@ hipError_t launch_interpolate(Ctx *c)
 __global__ void __launch_bounds__(256)
 k_cost_derivs(RecLayout L, int nr, int T,
               const double *__restrict__ r, const double *__restrict__ r_x, const double *__restrict__ r_u,
-              const double *__restrict__ w_run, const double *__restrict__ w_term, double *__restrict__ rec)
+              const double *__restrict__ w_run, const double *__restrict__ w_term, double *__restrict__ rec,
+              const int *__restrict__ traj)
 {
     extern __shared__ __attribute__((aligned(16))) double sh[];
     const int n = L.n, m = L.m;
     const int per = nr * (1 + n + m);
-    const int b = blockIdx.y;
+    const int b = traj ? traj[blockIdx.y] : blockIdx.y;      // a subset (kpilqr_cost_derivs_partial): block-uniform, a scalar load
     const int t0 = blockIdx.x * COST_TT;
     const int nt = min(COST_TT, T - t0);
     double *sw = sh + COST_TT * per;               // [2][nr]: doubled running / terminal weights (w*2 is exact)
@@ -568,13 +571,14 @@ template <int N, int M>
 __global__ void __launch_bounds__(256)
 k_cost_derivs_rows(RecLayout L, int nr, int T,
                    const double *__restrict__ r, const double *__restrict__ r_x, const double *__restrict__ r_u,
-                   const double *__restrict__ w_run, const double *__restrict__ w_term, double *__restrict__ rec)
+                   const double *__restrict__ w_run, const double *__restrict__ w_term, double *__restrict__ rec,
+                   const int *__restrict__ traj)
 {
     extern __shared__ __attribute__((aligned(16))) double sh[];
     constexpr int ROWS = N + M;
     constexpr int TT = 256 / ROWS;                 // time-steps per block
     const int per = nr * (1 + N + M);
-    const int b = blockIdx.y;
+    const int b = traj ? traj[blockIdx.y] : blockIdx.y;      // (as in k_cost_derivs)
     const int t0 = blockIdx.x * TT;
     const int nt = min(TT, T - t0);
     constexpr int NOUT_ = N * N + N + M * M + M;
@@ -664,10 +668,10 @@ k_cost_derivs_rows(RecLayout L, int nr, int T,
 }
 
 template <int N, int M>
-static hipError_t launch_cost_rows(Ctx *c)
+static hipError_t launch_cost_rows(Ctx *c, const int *traj, int count)
 {
     constexpr int TT = 256 / (N + M);
-    dim3 grid((c->d.T + TT - 1) / TT, c->d.batch);
+    dim3 grid((c->d.T + TT - 1) / TT, traj ? count : c->d.batch);
     const int per = c->d.nr * (1 + N + M), nout = N * N + N + M * M + M;
     const size_t lds = sizeof(double) * (TT * (per > nout ? per : nout) + 2 * c->d.nr);
     if (lds > 64 * 1024) {       // large states stage a few steps of 30 KB outputs: opt in to the CU's full 160 KB
@@ -675,23 +679,25 @@ static hipError_t launch_cost_rows(Ctx *c)
         if (e != hipSuccess) return e;
     }
     hipLaunchKernelGGL((k_cost_derivs_rows<N, M>), grid, dim3(256), lds, c->stream, c->L, c->d.nr, c->d.T, c->r,
-                       c->r_x, c->r_u, c->w_run, c->w_term, c->rec);
+                       c->r_x, c->r_u, c->w_run, c->w_term, c->rec, traj);
     return hipGetLastError();
 }
 
-hipError_t launch_cost_derivs(Ctx *c)
+// traj (device, count trajectories): the listed trajectories alone, one block row each; null: the whole batch
+hipError_t launch_cost_derivs(Ctx *c, const int *traj, int count)
 {
+    if (traj && count <= 0) return hipSuccess;
     const int per_ = c->d.nr * (1 + c->n + c->d.m), nout_ = c->n * c->n + c->n + c->d.m * c->d.m + c->d.m;
     const size_t lds_rows = sizeof(double) * ((256 / (c->n + c->d.m)) * (per_ > nout_ ? per_ : nout_) + 2 * c->d.nr);
     if (lds_rows <= 64 * 1024) {      // (n=62 was tried on the rows kernel with 95 KB of LDS: 20.3 ms vs 16.0 ms generic)
-        if (c->n == 14 && c->d.m == 7) return launch_cost_rows<14, 7>(c);
-        if (c->n == 4 && c->d.m == 1) return launch_cost_rows<4, 1>(c);
-        if (c->n == 20 && c->d.m == 7) return launch_cost_rows<20, 7>(c);
+        if (c->n == 14 && c->d.m == 7) return launch_cost_rows<14, 7>(c, traj, count);
+        if (c->n == 4 && c->d.m == 1) return launch_cost_rows<4, 1>(c, traj, count);
+        if (c->n == 20 && c->d.m == 7) return launch_cost_rows<20, 7>(c, traj, count);
     }
-    dim3 grid((c->d.T + COST_TT - 1) / COST_TT, c->d.batch);
+    dim3 grid((c->d.T + COST_TT - 1) / COST_TT, traj ? count : c->d.batch);
     const size_t lds = sizeof(double) * (COST_TT * c->d.nr * (1 + c->n + c->d.m) + 2 * c->d.nr);
     hipLaunchKernelGGL(k_cost_derivs, grid, dim3(256), lds, c->stream, c->L, c->d.nr, c->d.T, c->r, c->r_x,
-                       c->r_u, c->w_run, c->w_term, c->rec);
+                       c->r_u, c->w_run, c->w_term, c->rec, traj);
     return hipGetLastError();
 }
 

@@ -156,6 +156,7 @@ static int size_buffers(kpilqr_ctx *c)
         {&c->delta_J, B * 8, false},
         {&c->traj_cost, B * 8, false},
         {&c->status, B * 4, true},
+        {&c->traj_list, B * sizeof(int), false},
         {&c->segmap, B * dims->dof * T * sizeof(int2), false},
         {&c->kp_offsets, (B * dims->dof + 1) * 4, false},
         // the entry map of the one-pass linearisation, beside segmap: with the records (a fused context builds it on demand, ensure_segent)
@@ -409,7 +410,7 @@ static int ensure_rx_buffer(kpilqr_ctx *c)
 {
     if (!c->rx_const_on || c->rx_buf_valid) return KPILQR_OK;
     KP_HIP(c, launch_broadcast_rx(c));
-    c->rx_buf_valid = true;
+    c->rx_buf_valid = c->rx_whole = true;
     return KPILQR_OK;
 }
 
@@ -659,7 +660,7 @@ int kpilqr_resize(kpilqr_ctx *c, int new_dof, int new_num_ctrl, int new_horizon)
     payload_changed(c);
     c->kpu_valid = false;
     c->ru_zero = true;                                   // size_buffers zeroed r_u
-    c->rx_const_on = false; c->rx_buf_valid = true;
+    c->rx_const_on = false; c->rx_buf_valid = true; c->rx_whole = false;
     // the key-point placement buffers were sized by the old shape: they are allocated again on first use
     DevMem *const placement[] = {&c->X_states, &c->kp_mask, &c->kp_count, &c->kp_thr};
     for (DevMem *b : placement) KP_HIP(c, release(*b));
@@ -725,7 +726,7 @@ int kpilqr_device_ptr(kpilqr_ctx *c, int which, void **dptr, size_t *bytes)
         // a writable pointer leaves the library: the buffer gets the constant Jacobians' broadcast copy and is what the
         // sweeps read from here on (the constant mode is off, as for r_u below)
         { const int rcx = ensure_rx_buffer(c); if (rcx) return rcx; }
-        c->rx_const_on = false; c->rx_buf_valid = true;
+        c->rx_const_on = false; c->rx_buf_valid = c->rx_whole = true;
         p = c->r_x; sz = B * (T + 1) * nr * n * 8; break;
     case KPILQR_BUF_R_U:
         // a writable pointer leaves the library: from here on r_u may be non-zero without kpilqr_upload_residuals having
@@ -1258,7 +1259,7 @@ int kpilqr_upload_residuals(kpilqr_ctx *c, const double *r, const double *r_x, c
     KP_ENTER(c);
     const size_t B = c->d.batch, T1 = c->d.T + 1, n = c->n, m = c->d.m, nr = c->d.nr;
     if (r) KP_HIP(c, hipMemcpyAsync(c->r, r, B * T1 * nr * 8, hipMemcpyHostToDevice, c->stream));
-    if (r_x) { KP_HIP(c, hipMemcpyAsync(c->r_x, r_x, B * T1 * nr * n * 8, hipMemcpyHostToDevice, c->stream)); c->rx_const_on = false; c->rx_buf_valid = true; }
+    if (r_x) { KP_HIP(c, hipMemcpyAsync(c->r_x, r_x, B * T1 * nr * n * 8, hipMemcpyHostToDevice, c->stream)); c->rx_const_on = false; c->rx_buf_valid = c->rx_whole = true; }
     if (r_u) { KP_HIP(c, hipMemcpyAsync(c->r_u, r_u, B * T1 * nr * m * 8, hipMemcpyHostToDevice, c->stream)); c->ru_zero = false; }
     if (w_run) KP_HIP(c, hipMemcpyAsync(c->w_run, w_run, nr * 8, hipMemcpyHostToDevice, c->stream));
     if (w_term) KP_HIP(c, hipMemcpyAsync(c->w_term, w_term, nr * 8, hipMemcpyHostToDevice, c->stream));
@@ -1477,6 +1478,136 @@ int kpilqr_upload_nominal(kpilqr_ctx *c, const double *u_nom, const double *ctrl
     const size_t B = c->d.batch, T = c->d.T, m = c->d.m;
     if (u_nom) KP_HIP(c, hipMemcpyAsync(c->u_nom, u_nom, B * T * m * 8, hipMemcpyHostToDevice, c->stream));
     if (ctrl_lim) KP_HIP(c, hipMemcpyAsync(c->ctrl_lim, ctrl_lim, 2 * m * 8, hipMemcpyHostToDevice, c->stream));
+    return KPILQR_OK;
+}
+
+// ---- partial re-linearisation, the rest: residuals, nominal controls and step records of SOME trajectories ------------------------
+// The checks every call of the family makes before anything is enqueued or changed (kpilqr_update_keypoints' contract)
+static int check_traj_list(kpilqr_ctx *c, const char *who, int count, const int *traj)
+{
+    if (c->is_view) return set_err(c, KPILQR_ERR_STATE, std::string(who) + ": not through a view of a trajectory range");
+    if (!kp_traj_list_ok(c->d.batch, count, traj)) return set_err(c, KPILQR_ERR_ARG, std::string(who) + ": traj must be strictly increasing and within [0, batch)");
+    return KPILQR_OK;
+}
+
+// `per` doubles per trajectory, compact on the host in traj order: one copy per run of adjacent trajectories, straight to their place
+static int upload_rows(kpilqr_ctx *c, int count, const int *traj, const double *src, double *dst, size_t per)
+{
+    for (int i = 0; i < count;) {
+        int j = i;
+        while (j + 1 < count && traj[j + 1] == traj[j] + 1) j++;
+        KP_HIP(c, hipMemcpyAsync(dst + (size_t)traj[i] * per, src + (size_t)i * per, (size_t)(j - i + 1) * per * 8, hipMemcpyHostToDevice, c->stream));
+        i = j + 1;
+    }
+    return KPILQR_OK;
+}
+
+int kpilqr_upload_residuals_partial(kpilqr_ctx *c, int count, const int *traj, const double *r, const double *r_x, const double *r_u)
+{
+    if (!c || count < 0 || (count > 0 && !traj)) return KPILQR_ERR_ARG;
+    KP_ENTER(c);
+    if (count == 0) return KPILQR_OK;
+    int rc = check_traj_list(c, "kpilqr_upload_residuals_partial", count, traj);
+    if (rc) return rc;
+    // rows of a subset need every other row of the buffer to mean something, and must not flip the form the sweeps run in
+    if (r_x && c->rx_const_on)
+        return set_err(c, KPILQR_ERR_STATE, "kpilqr_upload_residuals_partial: the context holds constant residual Jacobians; a whole r_x through kpilqr_upload_residuals ends that mode first");
+    if (r_x && !(c->rx_buf_valid && c->rx_whole))
+        return set_err(c, KPILQR_ERR_STATE, "kpilqr_upload_residuals_partial: r_x of a subset before a whole r_x: kpilqr_upload_residuals first");
+    if (r_u && c->ru_zero)
+        return set_err(c, KPILQR_ERR_STATE, "kpilqr_upload_residuals_partial: r_u of a subset on a context that runs without control residuals: a whole r_u through kpilqr_upload_residuals first");
+    const size_t T1 = c->d.T + 1, n = c->n, m = c->d.m, nr = c->d.nr;
+    if (r) { rc = upload_rows(c, count, traj, r, c->r, T1 * nr); if (rc) return rc; }
+    if (r_x) { rc = upload_rows(c, count, traj, r_x, c->r_x, T1 * nr * n); if (rc) return rc; }
+    if (r_u) { rc = upload_rows(c, count, traj, r_u, c->r_u, T1 * nr * m); if (rc) return rc; }
+    return KPILQR_OK;
+}
+
+int kpilqr_upload_nominal_partial(kpilqr_ctx *c, int count, const int *traj, const double *u_nom)
+{
+    if (!c || count < 0 || (count > 0 && !traj)) return KPILQR_ERR_ARG;
+    KP_ENTER(c);
+    if (count == 0) return KPILQR_OK;
+    const int rc = check_traj_list(c, "kpilqr_upload_nominal_partial", count, traj);
+    if (rc) return rc;
+    return u_nom ? upload_rows(c, count, traj, u_nom, c->u_nom, (size_t)c->d.T * c->d.m) : KPILQR_OK;
+}
+
+// The key-point columns of the listed trajectories alone written into the records (the middle pass of the three-pass sequence on
+// a payload laid out by entry): a trajectory's entries are one range of the column store, so this is k_kpc_to_records once per run
+// of adjacent trajectories.  Only KPILQR_FD_INTERP=0 comes here -- a diagnostic switch; the product path is the one pass.
+static int kpc_to_records_of(kpilqr_ctx *c, int count, const int *traj)
+{
+    if (!c->kp_traj_first_host) {             // (lists placed on the device: their offsets are read back, once)
+        const int rc = ensure_offsets_mirror(c);
+        if (rc) return rc;
+        if (!remember_traj_first(c, c->kp_offsets_host)) return set_err(c, KPILQR_ERR_ALLOC, "host allocation failed");
+    }
+    const int first = c->fdk_first, entries = c->fdk_entries;
+    hipError_t e = hipSuccess;
+    for (int i = 0; i < count && e == hipSuccess;) {
+        int j = i;
+        while (j + 1 < count && traj[j + 1] == traj[j] + 1) j++;
+        c->fdk_first = c->kp_traj_first_host[traj[i]];
+        c->fdk_entries = c->kp_traj_first_host[traj[j] + 1] - c->fdk_first;
+        e = launch_kpc_to_records(c);
+        i = j + 1;
+    }
+    c->fdk_first = first; c->fdk_entries = entries;
+    KP_HIP(c, e);
+    return KPILQR_OK;
+}
+
+// kpilqr_fd_interpolate for the listed trajectories: [A|B] of their records from the resident payload, nobody else's records written
+int kpilqr_fd_interpolate_partial(kpilqr_ctx *c, int count, const int *traj)
+{
+    if (!c || count < 0 || (count > 0 && !traj)) return KPILQR_ERR_ARG;
+    KP_ENTER(c);
+    if (count == 0) return KPILQR_OK;
+    int rc = check_traj_list(c, "kpilqr_fd_interpolate_partial", count, traj);
+    if (rc) return rc;
+    if (c->fused) return set_err(c, KPILQR_ERR_STATE, "kpilqr_fd_interpolate_partial: a KPILQR_FLAG_FUSED context holds no persistent step records (its sweeps read the column store): kpilqr_fd_difference");
+    if (!c->have_kp) return set_err(c, KPILQR_ERR_STATE, "kpilqr_fd_interpolate_partial before kpilqr_set_keypoints");
+    rc = check_complete(c, "kpilqr_fd_interpolate_partial");
+    if (rc) return rc;
+    KP_HIP(c, hipMemcpyAsync(c->traj_list, traj, (size_t)count * sizeof(int), hipMemcpyHostToDevice, c->stream));
+    if (linearise_one_pass(c)) {
+        rc = ensure_segent(c);
+        if (rc) return rc;
+        KP_HIP(c, launch_fd_kp_interpolate(c, c->traj_list, count));
+        c->last_linearise = c->fd_payload == FdPayload::kp_columns ? "kp_columns_interpolate:subset" : "fd_kp_interpolate:subset";
+    } else {
+        // job lists: the resident jobs are differenced (whoever they belong to: a kept trajectory's jobs rewrite what its records
+        // hold); a payload by entry under KPILQR_FD_INTERP=0: columns -> the listed trajectories' key-point steps; then k_interpolate
+        if (c->fd_payload == FdPayload::jobs) KP_HIP(c, launch_fd_difference(c));
+        else if (payload_by_entry(c)) {
+            if (!c->kpc_valid) { rc = difference_to_kpc(c); if (rc) return rc; }
+            rc = ensure_entry_tables(c);
+            if (rc) return rc;
+            rc = kpc_to_records_of(c, count, traj);
+            if (rc) return rc;
+        }
+        KP_HIP(c, launch_interpolate(c, c->traj_list, count));
+        c->last_linearise = "fd_difference+interpolate:subset";
+    }
+    if (!is_pinned(traj)) KP_HIP(c, hipStreamSynchronize(c->stream));      // (the copy of a pageable list is complete before the caller has it back)
+    return KPILQR_OK;
+}
+
+// kpilqr_cost_derivs for the listed trajectories
+int kpilqr_cost_derivs_partial(kpilqr_ctx *c, int count, const int *traj)
+{
+    if (!c || count < 0 || (count > 0 && !traj)) return KPILQR_ERR_ARG;
+    KP_ENTER(c);
+    if (count == 0) return KPILQR_OK;
+    int rc = check_traj_list(c, "kpilqr_cost_derivs_partial", count, traj);
+    if (rc) return rc;
+    if (c->fused) return set_err(c, KPILQR_ERR_STATE, "kpilqr_cost_derivs_partial: a KPILQR_FLAG_FUSED context holds no persistent step records (its sweeps form the cost derivatives themselves)");
+    rc = ensure_rx_buffer(c);
+    if (rc) return rc;
+    KP_HIP(c, hipMemcpyAsync(c->traj_list, traj, (size_t)count * sizeof(int), hipMemcpyHostToDevice, c->stream));
+    KP_HIP(c, launch_cost_derivs(c, c->traj_list, count));
+    if (!is_pinned(traj)) KP_HIP(c, hipStreamSynchronize(c->stream));
     return KPILQR_OK;
 }
 
@@ -1712,7 +1843,7 @@ int kpilqr_iterate_streamed(kpilqr_ctx *c, const kpilqr_stream_io *io, int pd_ch
     // call (a rejected call must leave the context as it was: round-4 advisor; before, a call refused for an unpinned buffer had
     // already left the constant mode and the next sweep read an r_x buffer that never received the broadcast copy)
     if (io->r_u) c->ru_zero = false;
-    if (io->r_x) { c->rx_const_on = false; c->rx_buf_valid = true; }
+    if (io->r_x) { c->rx_const_on = false; c->rx_buf_valid = c->rx_whole = true; }
     // constant residual Jacobians and a kernel family that streams r_x: the broadcast copy is made here, on the context (the
     // chunks' wave organisation is the whole batch's: make_view gives a chunk its share of the SIMDs)
     if (!(c->fused && plan_backward_fused(c, false).rxc && plan_forward_fused(c).rxc)) { rc = ensure_rx_buffer(c); if (rc) return rc; }

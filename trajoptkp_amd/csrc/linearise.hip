@@ -30,12 +30,12 @@ namespace kpilqr {
 template <bool COLS>
 __global__ void __launch_bounds__(256)
 k_fd_kp_interpolate(RecLayout L, int dof, int T, const int2 *__restrict__ segmap, const int *__restrict__ segent,
-                    const double2 *__restrict__ src, double eps, double *__restrict__ rec)
+                    const double2 *__restrict__ src, double eps, double *__restrict__ rec, const int *__restrict__ traj)
 {
     extern __shared__ __attribute__((aligned(16))) int2 ssm[];      // [dof][LIN_TT] (s, e), then int [dof][LIN_TT] entry
     const int n = L.n, m = L.m;
     const int ne = n * n + n * m;               // even: n = 2*dof
-    const int b = blockIdx.y;
+    const int b = traj ? traj[blockIdx.y] : blockIdx.y;      // a subset (kpilqr_fd_interpolate_partial): block-uniform, a scalar load
     const int t0 = blockIdx.x * LIN_TT;
     const int nt = min(LIN_TT, T - t0);
     int *sen = (int *)(ssm + dof * LIN_TT);
@@ -97,20 +97,21 @@ k_fd_kp_interpolate(RecLayout L, int dof, int T, const int2 *__restrict__ segmap
 // Works on a view of a trajectory range (kpilqr_iterate_streamed): rec, segmap and segent are the view's (shifted), batch its
 // trajectories; segent holds ABSOLUTE CSR entries, so the payload / column store is addressed through its unshifted base and
 // the entries a chunk touches are its own: [fdk_first, fdk_first + fdk_entries).
-hipError_t launch_fd_kp_interpolate(Ctx *c)
+// traj (device, count trajectories): the listed trajectories alone, one block row each; null: the whole batch.
+hipError_t launch_fd_kp_interpolate(Ctx *c, const int *traj, int count)
 {
-    if (c->d.batch <= 0 || c->d.T <= 0) return hipSuccess;
-    dim3 grid((c->d.T + LIN_TT - 1) / LIN_TT, c->d.batch);
+    if (c->d.batch <= 0 || c->d.T <= 0 || (traj && count <= 0)) return hipSuccess;
+    dim3 grid((c->d.T + LIN_TT - 1) / LIN_TT, traj ? count : c->d.batch);
     const int ne = c->n * c->n + c->n * c->d.m;
     int threads = ((ne / 2 + 63) / 64) * 64;
     if (threads > 256) threads = 256;
     const size_t lds = (sizeof(int2) + sizeof(int)) * c->d.dof * LIN_TT;
     if (c->fd_payload == FdPayload::kp_columns)
         hipLaunchKernelGGL(k_fd_kp_interpolate<true>, grid, dim3(threads), lds, c->stream, c->L, c->d.dof, c->d.T, c->segmap, c->segent,
-                           (const double2 *)c->kpc.p, c->eps, c->rec);
+                           (const double2 *)c->kpc.p, c->eps, c->rec, traj);
     else
         hipLaunchKernelGGL(k_fd_kp_interpolate<false>, grid, dim3(threads), lds, c->stream, c->L, c->d.dof, c->d.T, c->segmap, c->segent,
-                           (const double2 *)c->fdk_dev.p, c->eps, c->rec);
+                           (const double2 *)c->fdk_dev.p, c->eps, c->rec, traj);
     return hipGetLastError();
 }
 

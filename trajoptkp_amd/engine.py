@@ -181,6 +181,37 @@ class Engine:
         tr = np.ascontiguousarray(traj, dtype=np.int32).reshape(-1)
         self._ck(self._partial("kpilqr_upload_kp_columns_partial")(self._h, len(tr), _ptr(tr), _ptr(s["cols"]), s["entries"]))
 
+    def _traj(self, traj):
+        return np.ascontiguousarray(traj, dtype=np.int32).reshape(-1)
+
+    def upload_residuals_partial(self, traj, r=None, r_x=None, r_u=None):
+        """kpilqr_upload_residuals_partial: the rows of the listed trajectories alone, compact in traj order -- r [len(traj)][T+1][nr],
+        r_x [..][nr][n], r_u [..][nr][m]; None = not sent."""
+        tr = self._traj(traj)
+        c, T1, n, m, nr = len(tr), self.T + 1, self.n, self.m, self.nr
+        r = None if r is None else _f64(r, (c, T1, nr))
+        r_x = None if r_x is None else _f64(r_x, (c, T1, nr, n))
+        r_u = None if r_u is None else _f64(r_u, (c, T1, nr, m))
+        self._keep += [tr, r, r_x, r_u]
+        self._ck(self._partial("kpilqr_upload_residuals_partial")(self._h, len(tr), _ptr(tr), _ptr(r), _ptr(r_x), _ptr(r_u)))
+
+    def upload_nominal_partial(self, traj, u_nom):
+        """kpilqr_upload_nominal_partial: u_nom [len(traj)][T][m] of the listed trajectories, compact in traj order."""
+        tr = self._traj(traj)
+        u = None if u_nom is None else _f64(u_nom, (len(tr), self.T, self.m))
+        self._keep += [tr, u]
+        self._ck(self._partial("kpilqr_upload_nominal_partial")(self._h, len(tr), _ptr(tr), _ptr(u)))
+
+    def fd_interpolate_partial(self, traj):
+        """kpilqr_fd_interpolate_partial: fd_interpolate for the listed trajectories' step records alone."""
+        tr = self._traj(traj)
+        self._ck(self._partial("kpilqr_fd_interpolate_partial")(self._h, len(tr), _ptr(tr)))
+
+    def cost_derivs_partial(self, traj):
+        """kpilqr_cost_derivs_partial: cost_derivs for the listed trajectories' step records alone."""
+        tr = self._traj(traj)
+        self._ck(self._partial("kpilqr_cost_derivs_partial")(self._h, len(tr), _ptr(tr)))
+
     # -- key-point placement on the device (SURVEY 8f.2) ----------------------------------------------
     def upload_states(self, X):
         X = _f64(X, (self.batch, self.T, self.n))

@@ -119,9 +119,22 @@ int kpilqr_host_run_acrobot_batch2(int B, int T, int min_N, int max_iter, int mi
 
 // ... and what crossed the link: traffic [traffic_cap] = FD payload bytes uploaded, gain bytes downloaded, number of linearisations,
 // then the batch's key-point entries at each of them (as many as fit)
+int kpilqr_host_run_acrobot_batch4(int B, int T, int min_N, int max_iter, int min_iter, double torque_weight, const double *q0s,
+                                   int fused, const char *method, double *cost_history, int cost_cap, int *iterations, double *U_out, double *stats,
+                                   double *traffic, int traffic_cap, double *inputs);
 int kpilqr_host_run_acrobot_batch3(int B, int T, int min_N, int max_iter, int min_iter, double torque_weight, const double *q0s,
                                    int fused, const char *method, double *cost_history, int cost_cap, int *iterations, double *U_out, double *stats,
                                    double *traffic, int traffic_cap)
+{
+    return kpilqr_host_run_acrobot_batch4(B, T, min_N, max_iter, min_iter, torque_weight, q0s, fused, method, cost_history, cost_cap, iterations, U_out, stats,
+                                          traffic, traffic_cap, nullptr);
+}
+
+// ... and the per-iteration inputs: inputs [2] = residual (r, and r_x, r_u unless "+constjac") bytes uploaded, nominal-control bytes
+// uploaded.  "+wholeinputs" in `method`: the shim sends them, and linearises the step records, through the whole-batch calls
+int kpilqr_host_run_acrobot_batch4(int B, int T, int min_N, int max_iter, int min_iter, double torque_weight, const double *q0s,
+                                   int fused, const char *method, double *cost_history, int cost_cap, int *iterations, double *U_out, double *stats,
+                                   double *traffic, int traffic_cap, double *inputs)
 {
     std::vector<iLQR_GPU_Batch::Problem> probs;
     for (int b = 0; b < B; b++) {
@@ -139,6 +152,7 @@ int kpilqr_host_run_acrobot_batch3(int B, int T, int min_N, int max_iter, int mi
     }
     iLQR_GPU_Batch opt(probs, T, 0, fused != 0);
     if (!opt.ok()) return -2;
+    opt.whole_inputs = method && std::string(method).find("+wholeinputs") != std::string::npos;
     std::vector<std::vector<MatrixXd>> U0(B, std::vector<MatrixXd>(T, MatrixXd(1, 1)));
     auto U = opt.OptimiseAll(U0, max_iter, min_iter);
     for (int b = 0; b < B; b++) {
@@ -153,6 +167,7 @@ int kpilqr_host_run_acrobot_batch3(int B, int T, int min_N, int max_iter, int mi
         traffic[2] = (double)opt.linearisation_entries.size();
         for (size_t i = 0; i < opt.linearisation_entries.size() && 3 + (int)i < traffic_cap; i++) traffic[3 + i] = opt.linearisation_entries[i];
     }
+    if (inputs) { inputs[0] = (double)opt.residual_bytes_uploaded; inputs[1] = (double)opt.nominal_bytes_uploaded; }
     return 0;
 }
 

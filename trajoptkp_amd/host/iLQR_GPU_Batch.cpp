@@ -210,6 +210,10 @@ void iLQR_GPU_Batch::GenerateDerivatives(const std::vector<int> &who)
     // are written into a second pinned slab, back to back in trajectory order, and copied from there into the batch slab.
     // (Round 3 uploaded a job list of `who` alone when the CSR had moved: the others' entries then held stale or zero columns.)
     const bool kp_ordered = fused_active;
+    // Residuals (and their Jacobians) of `who` alone once everybody's are resident: written COMPACT -- row w of the pinned arrays
+    // for who[w] -- and sent with kpilqr_upload_residuals_partial.  (The arrays need not keep the others' rows on this route: a whole
+    // upload only ever happens when everybody regenerates, which refills every row.  whole_inputs keeps row b for trajectory b.)
+    const bool part_in = !whole_inputs && inputs_resident && (int)who.size() != B;
     kpilqr_fdkp_layout lay = {};
     const bool partial = kp_ordered && (int)who.size() != B;
     std::vector<int> who_offs(1, 0), who_times, who_first;      // the lists of `who` as their own CSR; first packed entry of each
@@ -261,9 +265,10 @@ void iLQR_GPU_Batch::GenerateDerivatives(const std::vector<int> &who)
         }
         else if (kp_ordered) diff.DynamicsDerivativesKp(kp_slab, lay.entry_stride, offs[(size_t)b * dof], s.kp_offsets, s.kp_times, s.kpgen->keypoints, eps);
         else diff.DynamicsDerivativesPlanned(staging, b, s.kpgen->keypoints, eps);
+        const size_t row = part_in ? w : (size_t)b;
         for (int t = 0; t <= T; t++)
-            for (int i = 0; i < nr; i++) host_r[((size_t)b * (T + 1) + t) * nr + i] = s.residuals[t](i);
-        if (!const_jacobians) diff.ResidualDerivativesAll(host_rx + (size_t)b * (T + 1) * nr * n, host_ru + (size_t)b * (T + 1) * nr * m, T, eps);
+            for (int i = 0; i < nr; i++) host_r[(row * (T + 1) + t) * nr + i] = s.residuals[t](i);
+        if (!const_jacobians) diff.ResidualDerivativesAll(host_rx + row * (T + 1) * nr * n, host_ru + row * (T + 1) * nr * m, T, eps);
     }
     linearisation_entries.push_back(offs.back());
     if (partial) {
@@ -288,22 +293,33 @@ void iLQR_GPU_Batch::GenerateDerivatives(const std::vector<int> &who)
         kpilqr_fd_layout jl;
         if (kpilqr_fd_slab_layout(ctx, staging.njobs, staging.nnom, &jl) == KPILQR_OK) payload_bytes_uploaded += jl.bytes;
     }
-    // a materialising context: A, B of every step in one call (one pass over the records for a key-point ordered payload); the
-    // fused sweeps interpolate themselves and want the differenced key-point columns only
+    // a materialising context: A, B of every step in one call (one pass over the records for a key-point ordered payload) -- of the
+    // records of `who` alone when everybody else's still hold their linearisation (their lists were re-sent unchanged, the resident
+    // jobs are those of `who`); the fused sweeps interpolate themselves and want the differenced key-point columns only
+    const int nwho = (int)who.size();
     if (fused_active) { if ((rc = kpilqr_fd_difference(ctx))) fatal("kpilqr_fd_difference", rc); }
+    else if (part_in) { if ((rc = kpilqr_fd_interpolate_partial(ctx, nwho, who.data()))) fatal("kpilqr_fd_interpolate_partial", rc); }
     else if ((rc = kpilqr_fd_interpolate(ctx))) fatal("kpilqr_fd_interpolate", rc);
-    if (const_jacobians) {
-        // a task with ONE residual Jacobian (ModelTranslator::ConstantResidualJacobians; Reaching.cpp:43-54): the pair went into
-        // const_rx / const_ru when the optimiser was built and goes up once; only the residuals travel per linearisation
-        if (!const_jacobians_resident) {
-            bool ru_zero = true;
-            for (double v : const_ru) ru_zero = ru_zero && v == 0.0;
-            if ((rc = kpilqr_upload_residual_jacobians_const(ctx, const_rx.data(), ru_zero ? nullptr : const_ru.data()))) fatal("kpilqr_upload_residual_jacobians_const", rc);
-            const_jacobians_resident = true;
-        }
-        if ((rc = kpilqr_upload_residuals(ctx, host_r, nullptr, nullptr, w_run.data(), w_term.data()))) fatal("kpilqr_upload_residuals", rc);
-    } else if ((rc = kpilqr_upload_residuals(ctx, host_r, host_rx, host_ru, w_run.data(), w_term.data()))) fatal("kpilqr_upload_residuals", rc);
-    if (!fused_active && (rc = kpilqr_cost_derivs(ctx))) fatal("kpilqr_cost_derivs", rc);
+    // a task with ONE residual Jacobian (ModelTranslator::ConstantResidualJacobians; Reaching.cpp:43-54): the pair went into
+    // const_rx / const_ru when the optimiser was built and goes up once; only the residuals travel per linearisation
+    if (const_jacobians && !const_jacobians_resident) {
+        bool ru_zero = true;
+        for (double v : const_ru) ru_zero = ru_zero && v == 0.0;
+        if ((rc = kpilqr_upload_residual_jacobians_const(ctx, const_rx.data(), ru_zero ? nullptr : const_ru.data()))) fatal("kpilqr_upload_residual_jacobians_const", rc);
+        const_jacobians_resident = true;
+    }
+    const double *jac_x = const_jacobians ? nullptr : host_rx, *jac_u = const_jacobians ? nullptr : host_ru;
+    const size_t traj_bytes = (size_t)(T + 1) * nr * (const_jacobians ? 1 : 1 + n + m) * sizeof(double);
+    if (part_in) {
+        if ((rc = kpilqr_upload_residuals_partial(ctx, nwho, who.data(), host_r, jac_x, jac_u))) fatal("kpilqr_upload_residuals_partial", rc);
+        residual_bytes_uploaded += (size_t)nwho * traj_bytes;
+        if (!fused_active && (rc = kpilqr_cost_derivs_partial(ctx, nwho, who.data()))) fatal("kpilqr_cost_derivs_partial", rc);
+    } else {
+        if ((rc = kpilqr_upload_residuals(ctx, host_r, jac_x, jac_u, w_run.data(), w_term.data()))) fatal("kpilqr_upload_residuals", rc);
+        residual_bytes_uploaded += (size_t)B * traj_bytes;
+        if (!fused_active && (rc = kpilqr_cost_derivs(ctx))) fatal("kpilqr_cost_derivs", rc);
+    }
+    if (nwho == B) inputs_resident = true;
 }
 
 std::vector<std::vector<MatrixXd>> iLQR_GPU_Batch::OptimiseAll(const std::vector<std::vector<MatrixXd>> &initial_controls,
@@ -321,6 +337,7 @@ std::vector<std::vector<MatrixXd>> iLQR_GPU_Batch::OptimiseAll(const std::vector
         s.cost_reduced_last_iter = true; s.done = false; s.lambda_exit = false;
         if (s.kp_offsets.empty()) { s.kp_offsets.assign(dof + 1, 0); }
     }
+    unom_stale.assign(B, 1);                   // (Rollout set every U_old)
     std::vector<double> lam_used(B), pred((size_t)B * alphas.size()), dJ(B);
     std::vector<int> status(B);
     std::vector<std::vector<MatrixXd>> U_try(alphas.size(), std::vector<MatrixXd>(T, MatrixXd(m, 1)));
@@ -353,9 +370,16 @@ std::vector<std::vector<MatrixXd>> iLQR_GPU_Batch::OptimiseAll(const std::vector
             if (!again) break;
         }
         // STEP 3: linearised forward pass over the alphas for the whole batch, then a confirming rollout per trajectory
-        for (int b = 0; b < B; b++)
-            for (int t = 0; t < T; t++) for (int i = 0; i < m; i++) host_unom[((size_t)b * T + t) * m + i] = S[b].U_old[t](i);
-        if ((rc = kpilqr_upload_nominal(ctx, host_unom, ctrl_lim.data()))) fatal("kpilqr_upload_nominal", rc);
+        // U_old changes only where a step was accepted: after the first whole upload the rows that changed go up alone, compact
+        std::vector<int> moved;
+        for (int b = 0; b < B; b++) if (unom_stale[b] || whole_inputs) moved.push_back(b);
+        const bool all_rows = (int)moved.size() == B;
+        for (size_t w = 0; w < moved.size(); w++)
+            for (int t = 0; t < T; t++) for (int i = 0; i < m; i++) host_unom[(w * T + t) * m + i] = S[moved[w]].U_old[t](i);
+        if (all_rows) { if ((rc = kpilqr_upload_nominal(ctx, host_unom, ctrl_lim.data()))) fatal("kpilqr_upload_nominal", rc); }
+        else if ((rc = kpilqr_upload_nominal_partial(ctx, (int)moved.size(), moved.data(), host_unom))) fatal("kpilqr_upload_nominal_partial", rc);
+        nominal_bytes_uploaded += moved.size() * (size_t)T * m * sizeof(double);
+        unom_stale.assign(B, 0);
         if ((rc = kpilqr_forward_linear(ctx, alphas.data(), pred.data(), nullptr))) fatal("kpilqr_forward_linear", rc);
         // K, k only of the trajectories that will use them (active, with a valid backward pass): compact, in trajectory order
         std::vector<int> fetch, fetch_row(B, -1);
@@ -414,6 +438,7 @@ std::vector<std::vector<MatrixXd>> iLQR_GPU_Batch::OptimiseAll(const std::vector
                 }
                 s.old_cost = s.new_cost;
                 s.cost_reduced_last_iter = true;
+                unom_stale[b] = 1;
             } else {
                 s.cost_reduced_last_iter = false;
                 lambda[b] *= lambda_factor; lambda[b] *= lambda_factor;                    // :525-527

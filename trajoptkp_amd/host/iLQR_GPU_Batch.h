@@ -46,6 +46,13 @@ public:
     // after a partial regeneration on a fused context), gain bytes down (K, k of the active trajectories with a valid backward
     // pass); and the batch's key-point entries at every linearisation
     size_t payload_bytes_uploaded = 0, gain_bytes_downloaded = 0;
+    // ... and the per-iteration inputs: r (and r_x, r_u unless the task's Jacobians are constant) up at every linearisation -- the
+    // rows of the regenerating trajectories alone once a complete linearisation is resident -- and U_old up at every iteration, the
+    // rows that changed since the last upload alone.  Weights and control limits are not counted.
+    size_t residual_bytes_uploaded = 0, nominal_bytes_uploaded = 0;
+    // true: residuals, nominal controls and (on a materialising context) the step records go through the whole-batch calls at every
+    // linearisation, as before the partial calls existed -- the A/B of the tests
+    bool whole_inputs = false;
     std::vector<int> linearisation_entries;
     // regularisation / line search constants (include/Optimiser/Optimiser.h:239-242,259,303)
     double max_lambda = 10.0, min_lambda = 0.0001, lambda_factor = 10, epsConverge = 0.02;
@@ -82,6 +89,8 @@ private:
     size_t kp_part_bytes = 0;
     std::vector<int> kp_slab_offs;          // the batch CSR the slab's records were laid out for (empty: no valid slab)
     bool const_jacobians = false, const_jacobians_resident = false;     // the task's ONE residual Jacobian pair: uploaded once
+    bool inputs_resident = false;           // a complete linearisation has happened: every row of r (r_x, r_u) and every record is on the device
+    std::vector<char> unom_stale;           // [B] U_old changed since the device's row was uploaded
     std::vector<double> const_rx, const_ru;
     double *host_r = nullptr, *host_rx = nullptr, *host_ru = nullptr, *host_unom = nullptr, *host_K = nullptr, *host_k = nullptr;
 };
