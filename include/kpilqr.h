@@ -472,6 +472,30 @@ int  kpilqr_backward(kpilqr_ctx *ctx, const double *lambda, int pd_check_stride,
 int  kpilqr_backward_stats(kpilqr_ctx *ctx, int pd_check_stride, int *hist);
 /* K [batch][T][n][m] (column-major m x n), k [batch][T][m]; either may be NULL. */
 int  kpilqr_download_gains(kpilqr_ctx *ctx, double *K, double *k);
+/* K as FP32: half the bytes of the largest download a re-linearising host makes every iteration (K is T*n*m*8 bytes per trajectory,
+ * Panda reaching at T = 3000: 2.35 MB of the 2.52 MB of K and k; 1.18 MB as FP32).  Opt-in: the FP64 calls above are unchanged.
+ * Contract.  Layout, compactness and the `traj` rules are exactly those of kpilqr_download_gains / kpilqr_download_gains_partial:
+ * K32 [batch][T][n][m] (or [count][T][n][m], the listed trajectories back to back in `traj` order), k [batch][T][m] (or
+ * [count][T][m]); `traj` [count] strictly increasing and within [0, batch), else KPILQR_ERR_ARG and nothing is enqueued; count = 0 is
+ * a no-op returning KPILQR_OK; either pointer may be NULL; a NULL context is KPILQR_ERR_ARG; not through a view of
+ * kpilqr_iterate_streamed's chunks (KPILQR_ERR_STATE: a view never allocates).  Asynchronous on the context's stream: outputs are
+ * valid after kpilqr_sync (the call waits for the stream only when `traj` is pageable, as kpilqr_fd_interpolate_partial does, or when
+ * the float buffer has to grow).
+ * Precision.  K32[i] is the IEEE round-to-nearest-even conversion of the FP64 gain K[i], bit for bit what the C cast (float) gives:
+ * at most 2^-24 (6e-8) relative per element, against the 1e-6 the gains are held to; results in the FP32 subnormal range are
+ * produced, not flushed; magnitudes above FLT_MAX become +-inf; NaN stays NaN.  k stays FP64 and is the same copy as in the FP64
+ * calls (7 % of the bytes, and it enters the control unscaled by a small state difference).  The resident FP64 K is never written:
+ * kpilqr_download_gains*, kpilqr_forward_linear, kpilqr_dof_importance* and KPILQR_BUF_K see the same bits before and after.
+ * How.  ONE launch of a streaming kernel (k_gains_f32, gains.hip) gathers the listed trajectories' K -- however scattered the list
+ * is: it reads the trajectory of a block row from the device copy of the list kpilqr_fd_interpolate_partial uses -- and rounds it
+ * into a compact float buffer; then ONE hipMemcpyAsync of that buffer, and the usual copies for k.
+ * Memory cost: the float buffer, count*T*n*m*4 bytes of device memory owned by the context, reserved on demand and kept at the
+ * largest size asked for (whole batch: half the size of K; KPILQR_ERR_ALLOC when it cannot be had).
+ * Out of scope: kpilqr_iterate_streamed (kpilqr_stream_io is a fixed struct of this ABI version: its K stays FP64); FP32 for k, for
+ * any upload, or inside any sweep; an environment switch.  KPILQR_VERSION is unchanged: detect the calls by their symbols. */
+int  kpilqr_download_gains_f32(kpilqr_ctx *ctx, float *K32 /* [batch][T][n][m] */, double *k /* [batch][T][m] */);
+int  kpilqr_download_gains_f32_partial(kpilqr_ctx *ctx, int count, const int *traj,
+                                       float *K32 /* [count][T][n][m] */, double *k /* [count][T][m] */);
 
 /* iLQR_SVR::LeastImportantDofs on the gains of the last backward pass, both of the reference's measures, with no download of K.
  * Asynchronous on the context's stream (sums valid after kpilqr_sync); KPILQR_ERR_ARG for a NULL argument or

@@ -31,13 +31,15 @@ SYMBOLS = [
     "kpilqr_fd_interpolate", "kpilqr_get_union_keypoints", "kpilqr_get_union_columns",
     "kpilqr_update_keypoints", "kpilqr_upload_fd_kp_partial", "kpilqr_upload_kp_columns_partial", "kpilqr_download_gains_partial",
     "kpilqr_upload_residuals_partial", "kpilqr_upload_nominal_partial", "kpilqr_fd_interpolate_partial", "kpilqr_cost_derivs_partial",
+    "kpilqr_download_gains_f32", "kpilqr_download_gains_f32_partial",
 ]
 # entry points added without a version bump (include/kpilqr.h: "detect the entry point by its symbol"): bound only when the library
 # has them -- KPILQR_LIB may name an older build of the same major version
 OPTIONAL_SYMBOLS = {"kpilqr_fd_interpolate", "kpilqr_get_union_keypoints", "kpilqr_get_union_columns",
                     "kpilqr_update_keypoints", "kpilqr_upload_fd_kp_partial", "kpilqr_upload_kp_columns_partial",
                     "kpilqr_download_gains_partial", "kpilqr_upload_residuals_partial", "kpilqr_upload_nominal_partial",
-                    "kpilqr_fd_interpolate_partial", "kpilqr_cost_derivs_partial"}
+                    "kpilqr_fd_interpolate_partial", "kpilqr_cost_derivs_partial",
+                    "kpilqr_download_gains_f32", "kpilqr_download_gains_f32_partial"}
 
 
 class Dims(C.Structure):
@@ -162,6 +164,9 @@ def load():
         L.kpilqr_upload_nominal_partial.argtypes = [vp, C.c_int, vp, vp]
         L.kpilqr_fd_interpolate_partial.argtypes = [vp, C.c_int, vp]
         L.kpilqr_cost_derivs_partial.argtypes = [vp, C.c_int, vp]
+    if hasattr(L, "kpilqr_download_gains_f32"):
+        L.kpilqr_download_gains_f32.argtypes = [vp, vp, vp]
+        L.kpilqr_download_gains_f32_partial.argtypes = [vp, C.c_int, vp, vp, vp]
     for s in SYMBOLS:
         if s in OPTIONAL_SYMBOLS and not hasattr(L, s):
             continue

@@ -89,6 +89,7 @@ struct Ctx {
     DevBuf<int> kp_uniform;       // device flag: every trajectory has one key-point list for all its DoFs (k_kp_uniform)
     DevBuf<double> K;             // [batch][T][n*m]
     DevBuf<double> k;             // [batch][T][m]
+    DevBuf<float> K32;            // [count][T][n*m]: K of the trajectories of the last kpilqr_download_gains_f32[_partial], rounded to FP32 (gains.hip); reserved on demand
     DevBuf<double> r;             // [batch][T+1][nr]
     DevBuf<double> r_x;           // [batch][T+1][nr][n]
     DevBuf<double> r_u;           // [batch][T+1][nr][m]
@@ -235,7 +236,7 @@ struct Ctx {
     void for_each_buffer(F f)
     {
         DevMem *const all[] = {&rec, &kp_uniform, &K, &k, &r, &r_x, &r_u, &w_run, &w_term, &u_nom, &ctrl_lim, &lambda, &alphas, &cost_pred,
-                               &delta_J, &traj_cost, &status, &traj_list, &segmap, &segent, &kp_offsets, &kp_times, &rx_const, &kpc, &kps, &kp_entry,
+                               &delta_J, &traj_cost, &status, &traj_list, &K32, &segmap, &segent, &kp_offsets, &kp_times, &rx_const, &kpc, &kps, &kp_entry,
                                &kp_entry_list, &fdk_dev, &kpu_offsets, &kpu_times, &kpu_src, &kpu_traj_first, &kpcu, &kpu_uniform, &fdk_alt, &kpc_alt, &kp_times_alt, &kp_upl_times, &kp_move, &X_states, &kp_thr, &kp_mask, &kp_count, &ls8, &fd_dev, &err_flag, &stage};
         for (DevMem *b : all) f(*b);
     }
@@ -295,6 +296,8 @@ hipError_t launch_relocate_entries(Ctx *c, int units, long long longest_kept_ent
                                    const int *upl_first, const void *src, void *dst);
 hipError_t launch_merge_kp_times(Ctx *c, int longest_entries, const int *first_old, const int *first_new, const int *upl_first,
                                  const int *old_times, const int *upl_times, int *times);
+// gains.hip: K of `count` trajectories (traj: their indices on the device; nullptr: trajectories 0 .. count-1) -> out [count][T][n][m], FP32
+hipError_t launch_gains_f32(Ctx *c, const int *traj, int count, float *out);
 // comm.cpp (RCCL opened lazily) and the pack kernel of elementwise.hip
 const char *comm_unique_id(char *id128);
 const char *comm_init(Ctx *c, int nranks, int rank, const char *id128);

@@ -1611,6 +1611,49 @@ int kpilqr_cost_derivs_partial(kpilqr_ctx *c, int count, const int *traj)
     return KPILQR_OK;
 }
 
+// ---- K as FP32: half the bytes of the largest per-iteration download ---------------------------------------------------------------
+// K of the rows (traj == nullptr: trajectories 0 .. count-1) is rounded into the context's compact float buffer by ONE launch
+// (gains.hip) and leaves with ONE copy; k stays FP64 and is copied as kpilqr_download_gains[_partial] copies it.  The caller has
+// checked the list: nothing below rejects an argument.
+static int download_gains_f32(kpilqr_ctx *c, int count, const int *traj, float *K32, double *k)
+{
+    const size_t perK = (size_t)c->d.T * c->n * c->d.m, perk = (size_t)c->d.T * c->d.m;
+    if (K32) {
+        const int rc = reserve(c, c->K32, (size_t)count * perK * sizeof(float), kExact, false);
+        if (rc < 0) return rc;
+        if (traj) KP_HIP(c, hipMemcpyAsync(c->traj_list, traj, (size_t)count * sizeof(int), hipMemcpyHostToDevice, c->stream));
+        KP_HIP(c, launch_gains_f32(c, traj ? (const int *)c->traj_list : nullptr, count, c->K32));
+        KP_HIP(c, hipMemcpyAsync(K32, c->K32, (size_t)count * perK * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    }
+    if (k && !traj) KP_HIP(c, hipMemcpyAsync(k, c->k, (size_t)count * perk * 8, hipMemcpyDeviceToHost, c->stream));
+    for (int i = 0; k && traj && i < count;) {
+        int j = i;
+        while (j + 1 < count && traj[j + 1] == traj[j] + 1) j++;
+        KP_HIP(c, hipMemcpyAsync(k + (size_t)i * perk, c->k + (size_t)traj[i] * perk, (size_t)(j - i + 1) * perk * 8, hipMemcpyDeviceToHost, c->stream));
+        i = j + 1;
+    }
+    if (K32 && traj && !is_pinned(traj)) KP_HIP(c, hipStreamSynchronize(c->stream));      // (the copy of a pageable list is complete before the caller has it back)
+    return KPILQR_OK;
+}
+
+int kpilqr_download_gains_f32(kpilqr_ctx *c, float *K32, double *k)
+{
+    if (!c) return KPILQR_ERR_ARG;
+    KP_ENTER(c);
+    if (c->is_view) return set_err(c, KPILQR_ERR_STATE, "kpilqr_download_gains_f32: not through a view of a trajectory range");
+    return download_gains_f32(c, c->d.batch, nullptr, K32, k);
+}
+
+int kpilqr_download_gains_f32_partial(kpilqr_ctx *c, int count, const int *traj, float *K32, double *k)
+{
+    if (!c || count < 0 || (count > 0 && !traj)) return KPILQR_ERR_ARG;
+    KP_ENTER(c);
+    if (count == 0) return KPILQR_OK;
+    const int rc = check_traj_list(c, "kpilqr_download_gains_f32_partial", count, traj);
+    if (rc) return rc;
+    return download_gains_f32(c, count, traj, K32, k);
+}
+
 static int run_forward(kpilqr_ctx *c, double *U_dev)
 {
     if (c->fused) {

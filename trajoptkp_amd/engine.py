@@ -459,17 +459,19 @@ class Engine:
         self._ck(self._L.kpilqr_backward_stats(self._h, int(pd_stride), _ptr(h)))
         return h
 
-    def gains(self, traj=None, want_K=True, want_k=True):
+    def gains(self, traj=None, want_K=True, want_k=True, f32=False):
         """K, k of the last backward pass; traj: of those trajectories alone (kpilqr_download_gains_partial), compact, in traj
-        order.  An array that is not wanted comes back as None."""
+        order.  An array that is not wanted comes back as None.  f32: K crosses the link as FP32 (kpilqr_download_gains_f32[_partial])
+        and comes back as np.float32, the round-to-nearest-even cast of the FP64 gains; k is FP64 either way."""
         nb = self.batch if traj is None else len(traj)
-        K = np.zeros((nb, self.T, self.n, self.m)) if want_K else None
+        K = np.zeros((nb, self.T, self.n, self.m), np.float32 if f32 else np.float64) if want_K else None
         k = np.zeros((nb, self.T, self.m)) if want_k else None
+        sfx = "_f32" if f32 else ""
         if traj is None:
-            self._ck(self._L.kpilqr_download_gains(self._h, _ptr(K), _ptr(k)))
+            self._ck(self._partial("kpilqr_download_gains" + sfx)(self._h, _ptr(K), _ptr(k)))
         else:
             tr = np.ascontiguousarray(traj, dtype=np.int32).reshape(-1)
-            self._ck(self._partial("kpilqr_download_gains_partial")(self._h, len(tr), _ptr(tr), _ptr(K), _ptr(k)))
+            self._ck(self._partial("kpilqr_download_gains" + sfx + "_partial")(self._h, len(tr), _ptr(tr), _ptr(K), _ptr(k)))
         self.sync()
         return K, k
 

@@ -43,6 +43,7 @@ def load_host():
     H.kpilqr_host_run_acrobot_batch3.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, vp, C.c_int, C.c_char_p, vp, C.c_int, vp, vp, vp,
                                                  vp, C.c_int]
     H.kpilqr_host_run_acrobot_batch4.argtypes = H.kpilqr_host_run_acrobot_batch3.argtypes + [vp]
+    H.kpilqr_host_run_acrobot_batch5.argtypes = H.kpilqr_host_run_acrobot_batch4.argtypes + [vp]
     H.kpilqr_host_dof_importance.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, vp, vp]
     H.kpilqr_host_acrobot_dof_importance.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int, vp, vp]
     H.kpilqr_host_relocate_records.argtypes = [vp, vp, C.c_size_t, C.c_int, C.c_int, vp, vp, vp]
@@ -154,22 +155,24 @@ def relocate_records(slab, stride, B, dof, old_offs, new_offs, regen, in_place=T
 def run_acrobot_batch(q0s, T=100, min_N=5, max_iter=6, min_iter=2, torque_weight=-1.0, fused=False, method=None):
     """B acrobot swing-ups from the starts q0s [B][2] through ONE batched context (iLQR_GPU_Batch).  method: key-point
     method by name (None: set_interval), with options after a '+': "+constjac" (the task declares its residual Jacobians constant),
-    "+wholeinputs" (residuals, nominal controls and step records through the whole-batch calls at every linearisation).
+    "+wholeinputs" (residuals, nominal controls and step records through the whole-batch calls at every linearisation),
+    "+f32gains" (K comes down as FP32, kpilqr_download_gains_f32_partial; the default is FP64).
     payload_bytes_uploaded / gain_bytes_downloaded: what the run moved over the link (FD payload up; K, k down);
+    gain_trajectories_fetched: the trajectories whose K, k came down, summed over the iterations;
     residual_bytes_uploaded / nominal_bytes_uploaded: r (and r_x, r_u) and U_old up; keypoint_entries: the batch's key-point entries
     at every linearisation."""
     H = load_host()
     q = np.ascontiguousarray(q0s, np.float64); B = q.shape[0]
     cap = max_iter + 2
     hist = np.zeros((B, cap)); its = np.zeros(B, np.int32); U = np.zeros((B, T)); stats = np.zeros(8)
-    traffic = np.zeros(3 + max_iter + 1); inputs = np.zeros(2)
-    rc = H.kpilqr_host_run_acrobot_batch4(B, T, min_N, max_iter, min_iter, float(torque_weight), _p(q), int(fused),
+    traffic = np.zeros(3 + max_iter + 1); inputs = np.zeros(2); gains = np.zeros(1)
+    rc = H.kpilqr_host_run_acrobot_batch5(B, T, min_N, max_iter, min_iter, float(torque_weight), _p(q), int(fused),
                                           None if method is None else method.encode(), _p(hist), cap, _p(its), _p(U), _p(stats),
-                                          _p(traffic), len(traffic), _p(inputs))
+                                          _p(traffic), len(traffic), _p(inputs), _p(gains))
     if rc < 0:
         raise RuntimeError(f"kpilqr_host_run_acrobot_batch failed: {rc}")
     return dict(iterations=its, cost_history=[hist[b][hist[b] >= 0] for b in range(B)], U=U, stats=stats,
-                payload_bytes_uploaded=int(traffic[0]), gain_bytes_downloaded=int(traffic[1]),
+                payload_bytes_uploaded=int(traffic[0]), gain_bytes_downloaded=int(traffic[1]), gain_trajectories_fetched=int(gains[0]),
                 residual_bytes_uploaded=int(inputs[0]), nominal_bytes_uploaded=int(inputs[1]),
                 keypoint_entries=traffic[3:3 + int(traffic[2])].astype(np.int64))
 

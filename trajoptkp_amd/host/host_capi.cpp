@@ -132,9 +132,22 @@ int kpilqr_host_run_acrobot_batch3(int B, int T, int min_N, int max_iter, int mi
 
 // ... and the per-iteration inputs: inputs [2] = residual (r, and r_x, r_u unless "+constjac") bytes uploaded, nominal-control bytes
 // uploaded.  "+wholeinputs" in `method`: the shim sends them, and linearises the step records, through the whole-batch calls
+int kpilqr_host_run_acrobot_batch5(int B, int T, int min_N, int max_iter, int min_iter, double torque_weight, const double *q0s,
+                                   int fused, const char *method, double *cost_history, int cost_cap, int *iterations, double *U_out, double *stats,
+                                   double *traffic, int traffic_cap, double *inputs, double *gains);
 int kpilqr_host_run_acrobot_batch4(int B, int T, int min_N, int max_iter, int min_iter, double torque_weight, const double *q0s,
                                    int fused, const char *method, double *cost_history, int cost_cap, int *iterations, double *U_out, double *stats,
                                    double *traffic, int traffic_cap, double *inputs)
+{
+    return kpilqr_host_run_acrobot_batch5(B, T, min_N, max_iter, min_iter, torque_weight, q0s, fused, method, cost_history, cost_cap, iterations, U_out, stats,
+                                          traffic, traffic_cap, inputs, nullptr);
+}
+
+// ... and the gain download: gains [1] = trajectories whose K, k came down, summed over the iterations (traffic[1] holds their bytes).
+// "+f32gains" in `method`: K crosses the link as FP32 (iLQR_GPU_Batch::gains_f32)
+int kpilqr_host_run_acrobot_batch5(int B, int T, int min_N, int max_iter, int min_iter, double torque_weight, const double *q0s,
+                                   int fused, const char *method, double *cost_history, int cost_cap, int *iterations, double *U_out, double *stats,
+                                   double *traffic, int traffic_cap, double *inputs, double *gains)
 {
     std::vector<iLQR_GPU_Batch::Problem> probs;
     for (int b = 0; b < B; b++) {
@@ -153,6 +166,7 @@ int kpilqr_host_run_acrobot_batch4(int B, int T, int min_N, int max_iter, int mi
     iLQR_GPU_Batch opt(probs, T, 0, fused != 0);
     if (!opt.ok()) return -2;
     opt.whole_inputs = method && std::string(method).find("+wholeinputs") != std::string::npos;
+    opt.gains_f32 = method && std::string(method).find("+f32gains") != std::string::npos;
     std::vector<std::vector<MatrixXd>> U0(B, std::vector<MatrixXd>(T, MatrixXd(1, 1)));
     auto U = opt.OptimiseAll(U0, max_iter, min_iter);
     for (int b = 0; b < B; b++) {
@@ -168,6 +182,7 @@ int kpilqr_host_run_acrobot_batch4(int B, int T, int min_N, int max_iter, int mi
         for (size_t i = 0; i < opt.linearisation_entries.size() && 3 + (int)i < traffic_cap; i++) traffic[3 + i] = opt.linearisation_entries[i];
     }
     if (inputs) { inputs[0] = (double)opt.residual_bytes_uploaded; inputs[1] = (double)opt.nominal_bytes_uploaded; }
+    if (gains) gains[0] = (double)opt.gain_trajectories_fetched;
     return 0;
 }
 
@@ -416,6 +431,7 @@ int kpilqr_host_optimise(const char *model, int T, int max_iter, int min_iter, c
     if (!ilqr.ok()) return -2;
     if (opt.find("+unfused") != std::string::npos) ilqr.SetFused(false);
     if (opt.find("+pruned") != std::string::npos) ilqr.linesearch_mode = iLQR_GPU::LINESEARCH_PRUNED;
+    ilqr.gains_f32 = opt.find("+f32gains") != std::string::npos;          // K down as FP32 (kpilqr_download_gains_f32)
     const int m = M.mt->current_state_vector.num_ctrl;
     std::vector<MatrixXd> U0(T, MatrixXd(m, 1));
     if (u_init) for (int t = 0; t < T; t++) for (int i = 0; i < m; i++) U0[t](i) = u_init[(size_t)t * m + i];

@@ -34,6 +34,8 @@ void iLQR_GPU::free_pinned()
     staging.free_all();
     double **all[] = {&host_r, &host_rx, &host_ru, &host_unom, &host_K, &host_k};
     for (double **p : all) { if (*p && ctx) kpilqr_host_free(ctx, *p); *p = nullptr; }
+    if (host_K32 && ctx) kpilqr_host_free(ctx, host_K32);
+    host_K32 = nullptr;
     if (kp_slab && ctx) kpilqr_host_free(ctx, kp_slab);
     kp_slab = nullptr; kp_slab_bytes = 0;
     if (kp_cols && ctx) kpilqr_host_free(ctx, kp_cols);
@@ -338,10 +340,16 @@ void iLQR_GPU::Iteration(int iteration_num, bool &converged, bool &lambda_exit)
     if (rc) fatal("kpilqr_upload_nominal", rc);
     std::vector<double> pred(na);
     if ((rc = kpilqr_forward_linear(ctx, alphas.data(), pred.data(), nullptr))) fatal("kpilqr_forward_linear", rc);
-    if ((rc = kpilqr_download_gains(ctx, host_K, host_k))) fatal("kpilqr_download_gains", rc);
+    const size_t K_count = (size_t)T * n * m;
+    if (gains_f32) {
+        if (!host_K32 && (rc = kpilqr_host_alloc(ctx, K_count * sizeof(float), (void **)&host_K32))) fatal("kpilqr_host_alloc", rc);
+        if ((rc = kpilqr_download_gains_f32(ctx, host_K32, host_k))) fatal("kpilqr_download_gains_f32", rc);
+    } else if ((rc = kpilqr_download_gains(ctx, host_K, host_k))) fatal("kpilqr_download_gains", rc);
+    gain_bytes_downloaded += K_count * (gains_f32 ? sizeof(float) : sizeof(double)) + (size_t)T * m * sizeof(double);
     if ((rc = kpilqr_sync(ctx))) fatal("kpilqr_sync", rc);
     for (int t = 0; t < T; t++) {
-        for (int c = 0; c < n; c++) for (int r = 0; r < m; r++) K[t](r, c) = host_K[((size_t)t * n + c) * m + r];
+        if (gains_f32) { for (int c = 0; c < n; c++) for (int r = 0; r < m; r++) K[t](r, c) = (double)host_K32[((size_t)t * n + c) * m + r]; }
+        else for (int c = 0; c < n; c++) for (int r = 0; r < m; r++) K[t](r, c) = host_K[((size_t)t * n + c) * m + r];
         for (int r = 0; r < m; r++) k[t](r) = host_k[(size_t)t * m + r];
     }
     tr.predicted = pred;

@@ -34,6 +34,11 @@ public:
     // Fused sweeps: difference the FD results on the HOST, as the reference does (Differentiator.cpp:166-222,441-457), and
     // upload the key-point columns (kpilqr_upload_kp_columns: half the bytes of x+ / x-, the same gains bit for bit)
     bool host_differencing = false;
+    // K comes down as FP32 (kpilqr_download_gains_f32: half the bytes of the largest per-iteration download) into a pinned float
+    // array and is widened into K[t], which is exact; every element is the round-to-nearest-even cast of the FP64 gain (at most
+    // 6e-8 relative, against the 1e-6 the gains are held to).  k stays FP64.  Off by default: the reference's bits.
+    bool gains_f32 = false;
+    size_t gain_bytes_downloaded = 0;        // K and k bytes that crossed the link since construction
     void SetFused(bool on) { if (on != use_fused) { use_fused = on; recreate_ctx = true; Resize(dof, num_ctrl, horizon_length); } }
     std::string BackwardVariant() const { return ctx ? kpilqr_backward_variant(ctx) : ""; }
     // what the last kernels were (kpilqr_last_launch: "...:rxc" = the constant residual Jacobian in registers)
@@ -84,6 +89,7 @@ private:
     double *kp_cols = nullptr;               // host_differencing: the differenced columns [entries][3][n], pinned
     size_t kp_cols_count = 0;
     double *host_r = nullptr, *host_rx = nullptr, *host_ru = nullptr, *host_unom = nullptr, *host_K = nullptr, *host_k = nullptr;
+    float *host_K32 = nullptr;               // gains_f32: K as it crosses the link, pinned; allocated when the option is first used
     void free_pinned();
     bool fused_active = false, recreate_ctx = false;
     bool const_jacobians = false, const_jacobians_resident = false;      // the task's r_x, r_u hold at every state / are on this context

@@ -67,6 +67,8 @@ iLQR_GPU_Batch::~iLQR_GPU_Batch()
     if (kp_slab) kpilqr_host_free(ctx, kp_slab);
     if (kp_part) kpilqr_host_free(ctx, kp_part);
     kp_slab = kp_part = nullptr;
+    if (host_K32) kpilqr_host_free(ctx, host_K32);
+    host_K32 = nullptr;
     double **all[] = {&host_r, &host_rx, &host_ru, &host_unom, &host_K, &host_k};
     for (double **p : all) { if (*p) kpilqr_host_free(ctx, *p); *p = nullptr; }
     kpilqr_destroy(ctx);
@@ -384,8 +386,12 @@ std::vector<std::vector<MatrixXd>> iLQR_GPU_Batch::OptimiseAll(const std::vector
         // K, k only of the trajectories that will use them (active, with a valid backward pass): compact, in trajectory order
         std::vector<int> fetch, fetch_row(B, -1);
         for (int b : active) if (valid[b]) { fetch_row[b] = (int)fetch.size(); fetch.push_back(b); }
-        if (!fetch.empty() && (rc = kpilqr_download_gains_partial(ctx, (int)fetch.size(), fetch.data(), host_K, host_k))) fatal("kpilqr_download_gains_partial", rc);
-        gain_bytes_downloaded += fetch.size() * ((size_t)T * n * m + (size_t)T * m) * sizeof(double);
+        if (gains_f32) {
+            if (!host_K32 && (rc = kpilqr_host_alloc(ctx, (size_t)B * T * n * m * sizeof(float), (void **)&host_K32))) fatal("kpilqr_host_alloc", rc);
+            if (!fetch.empty() && (rc = kpilqr_download_gains_f32_partial(ctx, (int)fetch.size(), fetch.data(), host_K32, host_k))) fatal("kpilqr_download_gains_f32_partial", rc);
+        } else if (!fetch.empty() && (rc = kpilqr_download_gains_partial(ctx, (int)fetch.size(), fetch.data(), host_K, host_k))) fatal("kpilqr_download_gains_partial", rc);
+        gain_bytes_downloaded += fetch.size() * ((size_t)T * n * m * (gains_f32 ? sizeof(float) : sizeof(double)) + (size_t)T * m * sizeof(double));
+        gain_trajectories_fetched += fetch.size();
         if ((rc = kpilqr_sync(ctx))) fatal("kpilqr_sync", rc);
         for (double &v : linesearch_stats) v = 0.0;
         for (int b : active) {
@@ -398,7 +404,8 @@ std::vector<std::vector<MatrixXd>> iLQR_GPU_Batch::OptimiseAll(const std::vector
             if (!valid[b]) { cost_history[b].push_back(s.new_cost); continue; }
             const size_t row = (size_t)fetch_row[b];
             for (int t = 0; t < T; t++) {
-                for (int c = 0; c < n; c++) for (int r = 0; r < m; r++) K[b][t](r, c) = host_K[((row * T + t) * n + c) * m + r];
+                if (gains_f32) { for (int c = 0; c < n; c++) for (int r = 0; r < m; r++) K[b][t](r, c) = (double)host_K32[((row * T + t) * n + c) * m + r]; }
+                else for (int c = 0; c < n; c++) for (int r = 0; r < m; r++) K[b][t](r, c) = host_K[((row * T + t) * n + c) * m + r];
                 for (int r = 0; r < m; r++) k[b][t](r) = host_k[(row * T + t) * m + r];
             }
             const int na = (int)alphas.size();

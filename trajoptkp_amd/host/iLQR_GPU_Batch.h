@@ -46,6 +46,10 @@ public:
     // after a partial regeneration on a fused context), gain bytes down (K, k of the active trajectories with a valid backward
     // pass); and the batch's key-point entries at every linearisation
     size_t payload_bytes_uploaded = 0, gain_bytes_downloaded = 0;
+    size_t gain_trajectories_fetched = 0;    // trajectories whose K, k came down, summed over the iterations
+    // K comes down as FP32 (kpilqr_download_gains_f32_partial: T*n*m*4 instead of *8 bytes per fetched trajectory) into a pinned float
+    // array and is widened into K[b][t], which is exact; k stays FP64.  Off by default: the FP64 gains, bit for bit as before.
+    bool gains_f32 = false;
     // ... and the per-iteration inputs: r (and r_x, r_u unless the task's Jacobians are constant) up at every linearisation -- the
     // rows of the regenerating trajectories alone once a complete linearisation is resident -- and U_old up at every iteration, the
     // rows that changed since the last upload alone.  Weights and control limits are not counted.
@@ -93,6 +97,7 @@ private:
     std::vector<char> unom_stale;           // [B] U_old changed since the device's row was uploaded
     std::vector<double> const_rx, const_ru;
     double *host_r = nullptr, *host_rx = nullptr, *host_ru = nullptr, *host_unom = nullptr, *host_K = nullptr, *host_k = nullptr;
+    float *host_K32 = nullptr;              // gains_f32: K as it crosses the link, pinned [B][T][n][m]; allocated when the option is first used
 };
 
 // Moves the key-point records of the trajectories that do NOT regenerate (regen[b] == 0) from their entry offsets in the old batch
