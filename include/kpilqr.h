@@ -374,7 +374,9 @@ int  kpilqr_upload_kp_columns(kpilqr_ctx *ctx, const double *columns, int entrie
  * chunk stream is still reading).  All offsets are validated before anything is enqueued. */
 typedef struct {
     const void *fd_slab;                        /* kpilqr_fd_slab_layout(njobs, nnom); NULL: no new FD payload, the
-                                                   key-point columns already on the device are reused                    */
+                                                   resident one is swept again (its key-point columns are reused where
+                                                   they exist; a payload that an ordinary upload call brought since the
+                                                   last sweep is differenced first, on every kind of context)            */
     int njobs, nnom;
     const int *traj_job_first, *traj_nom_first; /* [batch+1]                                                             */
     double eps;

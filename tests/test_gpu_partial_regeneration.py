@@ -10,6 +10,7 @@ import functools
 import numpy as np
 import pytest
 
+from _sequences import _entries_of
 from oracle import oracle as orc
 from trajoptkp_amd import Engine, host, synth
 from trajoptkp_amd.engine import KpilqrError, rows_to_dof_csr
@@ -97,12 +98,6 @@ def _engine(p, ctx, monkeypatch):
         monkeypatch.delenv(k)                 # read once, in kpilqr_create
     assert ("fused" in e.backward_variant) == bool(kw.get("fused"))
     return e
-
-
-def _entries_of(p, traj):
-    o, _ = rows_to_dof_csr(p["kp_rows"], p["dof"], p["T"])
-    dof = p["dof"]
-    return np.concatenate([np.arange(o[b * dof], o[(b + 1) * dof]) for b in traj]) if len(traj) else np.zeros(0, np.int64)
 
 
 def _payload(e, p, form, traj=None, eps=None, full_call=False):

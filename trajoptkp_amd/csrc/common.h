@@ -143,7 +143,10 @@ struct Ctx {
     DevBuf<int> kp_entry_list;   // [entries]: list (= b*dof + d) of a CSR entry
     bool entry_tables_valid = false;
     bool have_rec = false;       // step records allocated (always on a non-fused context; on demand on a fused one)
-    bool rec_synced = false;     // fused context: the records hold the key-point columns of the resident payload
+    bool rec_synced = false;     // a linearising call has written the key-point columns of the resident payload (if any) into the records
+                                 // since it arrived: cleared by payload_changed, a streamed iteration without a new payload writes them
+                                 // first when it is clear.  NOT cleared by calls that overwrite records by hand (set_AB, a record pointer,
+                                 // the A filter): such a sweep interpolates what they wrote
     int kp_total_host = -1;      // number of CSR entries when the host knows it (kpilqr_set_keypoints), else -1
     int *kp_traj_first_host = nullptr;                // [batch+1] first CSR entry of every trajectory (host copy), or null
     FdPayload fd_payload = FdPayload::none;
@@ -279,7 +282,9 @@ Ctx::Tuning read_tuning_from_env();
 // elementwise.hip
 hipError_t launch_fd_difference(Ctx *c);                 // job lists -> step records
 hipError_t launch_fd_difference_kpc(Ctx *c);             // job lists -> key-point column store
-hipError_t launch_fd_kp_difference(Ctx *c, bool only_if_ragged = false);   // key-point ordered payload -> key-point column store (only_if_ragged: leaves at once when the device flag kp_uniform is set)
+// key-point ordered payload -> key-point column store (only_if_ragged: leaves at once when the device flag kp_uniform is set;
+// with_slopes: also the slope store of per-DoF lists, which the caller has sized for the current lists -- ensure_kps)
+hipError_t launch_fd_kp_difference(Ctx *c, bool only_if_ragged = false, bool with_slopes = true);
 hipError_t launch_kpc_to_records(Ctx *c);                // key-point column store -> step records
 hipError_t launch_kp_slopes(Ctx *c, bool only_if_ragged = true);   // key-point column store -> slope store (per-DoF lists only)
 hipError_t launch_build_entry_tables(Ctx *c);            // kp_entry, kp_entry_list from the CSR lists

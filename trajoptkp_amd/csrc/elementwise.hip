@@ -219,7 +219,7 @@ k_fd_kp_difference(int n, long long npairs_total, unsigned long long magic, cons
     }
 }
 
-hipError_t launch_fd_kp_difference(Ctx *c, bool only_if_ragged)
+hipError_t launch_fd_kp_difference(Ctx *c, bool only_if_ragged, bool with_slopes)
 {
     // a view of a trajectory range (kpilqr_iterate_streamed) differences its own entries: [fdk_first, fdk_first + fdk_entries)
     if (c->fdk_entries == 0) return hipSuccess;
@@ -232,7 +232,9 @@ hipError_t launch_fd_kp_difference(Ctx *c, bool only_if_ragged)
     const double2 *rec = (const double2 *)(c->fdk_dev + (size_t)c->fdk_first * c->fdk_stride());
     double2 *kpc = (double2 *)(c->kpc + (size_t)c->fdk_first * 3 * c->n);
     const int *flag = only_if_ragged ? c->kp_uniform : (const int *)nullptr;
-    if (c->kps && !c->kp_known_uniform)         // per-DoF lists possible: their slope store in the same pass
+    // per-DoF lists possible: their slope store in the same pass -- only for a caller that has sized it for the current lists
+    // (with_slopes): a slope store that merely EXISTS may be that of shorter lists
+    if (with_slopes && c->kps && !c->kp_known_uniform)
         hipLaunchKernelGGL(k_fd_kp_difference<true>, dim3(blocks), dim3(256), 0, c->stream, c->n, npairs, magic, rec, c->eps, kpc, flag, c->fdk_entries,
                            c->kp_times + c->fdk_first, (double2 *)(c->kps + (size_t)c->fdk_first * 6 * c->n));
     else

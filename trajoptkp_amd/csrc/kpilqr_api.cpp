@@ -246,15 +246,19 @@ static int difference_to_kpc(kpilqr_ctx *c, bool want_slopes = true)
     }
     int rc = ensure_kpc(c);
     if (rc) return rc;
-    if (c->fused && want_slopes) { rc = ensure_kps(c); if (rc) return rc; }       // (only the fused sweeps' per-DoF list forms read the slope store)
+    // Only the fused sweeps' per-DoF list forms read the slope store, and only then is it sized for the current lists.  Anybody else
+    // (the union route, a context with records) must not have it written: one that exists from earlier, shorter lists would be
+    // written past its end.
+    const bool slopes = c->fused && want_slopes;
+    if (slopes) { rc = ensure_kps(c); if (rc) return rc; }
     c->kps_valid = false;
     if (c->fd_payload == FdPayload::jobs) {
         rc = ensure_entry_tables(c);
         if (rc) return rc;
         KP_HIP(c, launch_fd_difference_kpc(c));
     } else {
-        KP_HIP(c, launch_fd_kp_difference(c));
-        if (c->kps && !c->kp_known_uniform) c->kps_valid = true;         // (the slope store of per-DoF lists is written in the same pass)
+        KP_HIP(c, launch_fd_kp_difference(c, false, slopes));
+        if (slopes && c->kps && !c->kp_known_uniform) c->kps_valid = true;         // (the slope store of per-DoF lists is written in the same pass)
     }
     c->kpc_valid = true;
     return KPILQR_OK;
@@ -1198,7 +1202,9 @@ int kpilqr_fd_difference(kpilqr_ctx *c)
         if (c->have_rec) { rc = records_from_payload(c); if (rc) return rc; c->rec_synced = true; }
         return KPILQR_OK;
     }
-    return records_from_payload(c);
+    const int rc = records_from_payload(c);
+    if (rc == KPILQR_OK) c->rec_synced = true;
+    return rc;
 }
 
 int kpilqr_interpolate(kpilqr_ctx *c)
@@ -1230,7 +1236,9 @@ int kpilqr_fd_interpolate(kpilqr_ctx *c)
         if (rc == KPILQR_OK) c->rec_synced = true;
         return rc;
     }
-    return linearise(c);
+    const int rc = linearise(c);
+    if (rc == KPILQR_OK) c->rec_synced = true;
+    return rc;
 }
 
 // Optimiser::FilterDynamicsMatrices (Optimiser.cpp:340-406) on the materialised A sequence
@@ -1725,6 +1733,7 @@ int kpilqr_iterate(kpilqr_ctx *c, const double *lambda, int pd_check_stride, con
     if (alphas) KP_HIP(c, hipMemcpyAsync(c->alphas, alphas, (size_t)c->d.n_alpha * 8, hipMemcpyHostToDevice, c->stream));
     if (!c->fused) {              // the fused sweeps difference (or read kpc), interpolate A, B and form l_* themselves
         { const int rcl = linearise(c); if (rcl) return rcl; }
+        c->rec_synced = true;
         if (!c->tiled_a6) { const int rcx = ensure_rx_buffer(c); if (rcx) return rcx; KP_HIP(c, launch_cost_derivs(c)); }      // tiled + flag: l_* are formed inside the sweeps
     }
     else c->last_linearise = union_route(c) ? "kp_union" : "in_sweep";
@@ -1882,6 +1891,16 @@ int kpilqr_iterate_streamed(kpilqr_ctx *c, const kpilqr_stream_io *io, int pd_ch
     if (c->fused && !new_payload && !c->kpc_valid && c->fd_payload == FdPayload::jobs) {
         rc = difference_to_kpc(c); if (rc) return rc;
     }
+    // The same on a context with records: without a new payload a chunk runs k_interpolate alone, between the key-point columns its
+    // records hold -- those of the resident payload only if something has written them there since it arrived.  A payload uploaded
+    // by an ordinary call (kpilqr_upload_fd_kp, a partial upload behind kpilqr_update_keypoints ...) and not linearised yet is
+    // written into the records HERE, for the whole batch, behind the chunks of any earlier iteration (rec_synced is cleared by
+    // payload_changed, so this is the first sweep since that upload: the join costs an overlap nobody had).
+    if (!c->fused && !new_payload && !c->rec_synced) {
+        rc = join_pipeline(c); if (rc) return rc;
+        rc = records_from_payload(c); if (rc) return rc;
+        c->rec_synced = true;
+    }
     // Per-step Jacobians in this call end the constant mode -- recorded only HERE, behind every check that can still reject the
     // call (a rejected call must leave the context as it was: round-4 advisor; before, a call refused for an unpinned buffer had
     // already left the constant mode and the next sweep read an r_x buffer that never received the broadcast copy)
@@ -1977,6 +1996,7 @@ int kpilqr_iterate_streamed(kpilqr_ctx *c, const kpilqr_stream_io *io, int pd_ch
         if (io->status) KP_HIP(c, hipMemcpyAsync(io->status + o, v.status, cnt * 4, hipMemcpyDeviceToHost, s));
     }
     c->kpc_valid = vflags_valid; c->kpc_touched = vflags_touched; c->kps_valid = vflags_slopes;      // what every chunk did to its slice of kpc
+    if (!c->fused && new_payload) c->rec_synced = true;      // every chunk has linearised its trajectories from the new payload
     return KPILQR_OK;
 }
 
