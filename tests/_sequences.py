@@ -1,8 +1,8 @@
 """Model-based sequence tests: ONE long-lived context driven through a random sequence of ABI calls while a Python shadow tracks
 what its inputs now are (tests/test_gpu_sequences.py on the GPU, tests/test_sequence_model.py on the CPU, tools/sequence_fuzz.py).
 
-What a context computes depends on the validity flags of Ctx (common.h: kpc_valid, kpc_touched, kps_valid, kpu_valid, kpcu_valid,
-rec_synced, have_rec, segent_valid, entry_tables_valid, kp_known_uniform, kp_canonical, kp_offsets_host_valid, n_pending, rx_const_on,
+What a context computes depends on the validity flags of Ctx (common.h: PayloadDerived -- kpc_valid, kpc_touched, kps_valid, kpcu_valid,
+rec_synced --, ListsDerived -- entry_tables_valid, segent_valid, kpu_valid --, have_rec, kp_known_uniform, kp_canonical, kp_offsets_host_valid, n_pending, rx_const_on,
 rx_buf_valid, rx_whole, ru_zero, fd_payload, pipe_dirty).  A flag left set one call too long makes a sweep read yesterday's
 linearisation; no kernel is wrong then and no single-shot test reaches the state.  Here every observation is compared with the CPU
 oracle on the shadow and with a FRESH context that is given the shadow by the shortest whole-batch route.

@@ -427,6 +427,33 @@ def test_partial_linearisation_end_to_end_on_records(subset):
     _same(got, want, subset)
 
 
+def test_a_whole_linearisation_behind_the_per_run_launches_of_a_subset(monkeypatch):
+    """KPILQR_FD_INTERP=0 on the records context above: kpilqr_fd_interpolate_partial scatters the columns of the `gaps` subset with
+    one k_kpc_to_records launch per run of adjacent trajectories, each over that run's entry range.  The ranges are arguments of the
+    launch: the context's own range is still the whole payload afterwards, so a whole-batch kpilqr_fd_interpolate behind the subset
+    call rewrites EVERY record (they are overwritten with a sentinel in between: key-point columns it skipped would stay the
+    sentinel's, and k_interpolate would spread them) -- bit for bit what a fresh context makes of the merged problem."""
+    task = "panda_pushing"
+    p0, p1 = _pair(task, True)
+    who = SUBSETS["gaps"]
+    pm = _merged(p0, p1, who)
+    with _engine(p0, monkeypatch, {"KPILQR_FD_INTERP": "0"}) as e:
+        e.set_keypoints_rows(p0["kp_rows"])
+        _payload(e, p0, "fd_kp")
+        e.fd_interpolate()
+        e.update_keypoints_rows(who, [p1["kp_rows"][b] for b in who])
+        _payload(e, pm, "fd_kp", who)
+        e.fd_interpolate_partial(who)
+        assert e.last_launch("linearise") == "fd_difference+interpolate:subset"
+        e.set_AB(*_sentinel(p0))
+        e.fd_interpolate()
+        assert e.last_launch("linearise") == "fd_difference+interpolate"
+        A, Bm = e.get_AB()
+    wA, wB, whow = _fresh_AB(task, "fd_kp", "gaps", "0")
+    assert whow == "fd_difference+interpolate" and np.any(wA != 0) and np.any(wB != 0)
+    assert np.array_equal(A, wA) and np.array_equal(Bm, wB)
+
+
 # ---- 6. the batch shim --------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("constjac", [False, True], ids=["jacobians", "constjac"])
 @pytest.mark.parametrize("fused", [True, False], ids=["fused", "records"])

@@ -7,8 +7,10 @@ documented refusals -- while a Python shadow tracks what the inputs now are.  At
      observe call: np.array_equal where both contexts report the same launch strings, 1e-12 where the forms differ (raw / column store
      after an explicit fd_difference, per-DoF / union); on contexts with records also get_AB / get_cost_derivs.
 
-What this holds in place are the validity flags of Ctx (common.h) and the five helpers that set and clear them (kpilqr_api.cpp):
-a flag left set one call too long makes a sweep read yesterday's linearisation, and no single-shot test reaches that state.
+What this holds in place is the validity state of Ctx (common.h: the aggregates PayloadDerived and ListsDerived) and its three
+rules (kpilqr_api.cpp): an event -- payload_changed, keypoints_changed, size_buffers -- resets an aggregate as a whole, the function
+that fills a store marks it, and a streamed call takes the payload-derived state back from its last chunk view.  A flag left set one
+call too long makes a sweep read yesterday's linearisation, and no single-shot test reaches that state.
 tests/test_sequence_model.py shows on the CPU that the sequences are legal, cover every op class and would notice a device that ignored
 everything since the previous observation.  tools/sequence_fuzz.py runs the same code over uncommitted seeds.
 
@@ -88,6 +90,31 @@ REGRESSIONS = {
         dict(op="observe", how="streamed", nchunks=3, payload=None, res=None, gains="all", seed=13),
     ]),
 }
+# ---- reduced sequences that pin how the validity state travels ("Who says what is still valid") ---------------------------
+# The payload-derived state of the LAST chunk view is what the context holds after kpilqr_iterate_streamed: a column payload that
+# arrives in 3 chunks (per-DoF lists: every chunk makes the slopes of its own entries), then kpilqr_iterate on what is resident (the
+# column store has to count as valid: the payload cannot be differenced again), then a streamed call without a payload.
+REGRESSIONS["streamed_column_payload_then_sweeps_on_what_is_resident"] = ("fused", [
+    dict(op="set_keypoints", how="bisect", seed=1), dict(op="upload_payload", kind="fd_kp", seed=2),
+    dict(op="upload_residuals", what="r+rx", seed=3), dict(op="weights", seed=4), dict(op="nominal", seed=5),
+    dict(op="observe", how="iterate", gains="all", seed=6),
+    dict(op="observe", how="streamed", nchunks=3, payload="cols", res=None, gains="all", seed=7),
+    dict(op="observe", how="iterate", gains="all", seed=8),
+    dict(op="observe", how="streamed", nchunks=2, payload=None, res=None, gains="all", seed=9),
+])
+# rec_synced is set by the functions that write the records (records_from_payload, linearise) and cleared by a new payload: the
+# records of a fused context appear on demand behind kpilqr_fd_difference, an ordinary upload makes them stale, kpilqr_get_AB has
+# them written again, and the sweeps see the new payload.  The same calls on a context that always has records.
+_RECORDS_ON_DEMAND = [
+    dict(op="set_keypoints", how="bisect", seed=1), dict(op="upload_payload", kind="fd_kp", seed=2),
+    dict(op="upload_residuals", what="r+rx", seed=3), dict(op="weights", seed=4), dict(op="nominal", seed=5),
+    dict(op="stage", call="fd_difference"), dict(op="stage", call="interpolate"),
+    dict(op="upload_payload", kind="cols", seed=6, same_kp=True),
+    dict(op="stage", call="get_AB"),
+    dict(op="observe", how="iterate", gains="all", seed=7),
+]
+REGRESSIONS["records_on_demand_then_an_ordinary_upload"] = ("fused", _RECORDS_ON_DEMAND)
+REGRESSIONS["records_on_demand_then_an_ordinary_upload_t1"] = ("records_t1", _RECORDS_ON_DEMAND)
 REGRESSIONS["streamed_without_payload_after_an_ordinary_upload_tiled"] = ("records_tiled", REGRESSIONS["streamed_without_payload_after_an_ordinary_upload"][1])
 
 

@@ -4,7 +4,9 @@
 // Random batches of per-DoF lists (canonical, broken, uniform, empty), a random strictly increasing subset with new lists of other
 // lengths: the merged offsets, the move table and the per-trajectory flags are held against a restatement with std::vector, and
 // the move itself is replayed on byte buffers -- what k_relocate_entries / k_merge_kp_times do with the same three arrays -- into
-// allocations of exactly the needed size, so that an index one past a range is a sanitizer report.  Prints the number of trials.
+// allocations of exactly the needed size, so that an index one past a range is a sanitizer report.  The walk over runs of adjacent
+// trajectories (kp_for_each_run: what every call on a subset copies or launches by) is held against a naive restatement on random
+// strictly increasing lists, the empty list, one element, all adjacent and none adjacent included.  Prints the number of trials.
 #include <cstdio>
 #include <cstdlib>
 #include <random>
@@ -55,6 +57,39 @@ static unsigned char flags_of(const Lists &l, int T)
     return f;
 }
 
+// kp_for_each_run on `traj` (an exactly sized heap copy) against the definition: the runs partition the list in order, each is a
+// stretch of consecutive indices, none could be longer, and i is the position of a run's first element; a non-zero result of f
+// stops the walk and comes back.  -> the line of the first failed requirement, 0: fine.
+static int run_walk_fails(const std::vector<int> &list)
+{
+#define RUN_REQUIRE(x) do { if (!(x)) { std::free(traj); return __LINE__; } } while (0)
+    const int count = (int)list.size();
+    int *traj = (int *)std::malloc(sizeof(int) * list.size() + 1);
+    for (int i = 0; i < count; i++) traj[i] = list[i];
+    struct Run { int i, first, len; };
+    std::vector<Run> runs;
+    RUN_REQUIRE(kp_for_each_run(count, traj, [&](int i, int first, int len) { runs.push_back({i, first, len}); return 0; }) == 0);
+    int at = 0;                                                            // position in the list the next run has to start at
+    for (size_t r = 0; r < runs.size(); r++) {
+        RUN_REQUIRE(runs[r].i == at && runs[r].len >= 1 && at + runs[r].len <= count && runs[r].first == list[at]);
+        for (int j = 0; j < runs[r].len; j++) RUN_REQUIRE(list[at + j] == runs[r].first + j);
+        at += runs[r].len;
+        RUN_REQUIRE(at == count || list[at] != list[at - 1] + 1);          // maximal
+    }
+    RUN_REQUIRE(at == count);
+    size_t naive = 0;                                                      // runs = 1 + places where the list jumps
+    for (int i = 0; i < count; i++) naive += i == 0 || list[i] != list[i - 1] + 1;
+    RUN_REQUIRE(runs.size() == naive);
+    for (size_t stop = 0; stop < runs.size(); stop++) {                    // the first non-zero result ends the walk
+        size_t calls = 0;
+        RUN_REQUIRE(kp_for_each_run(count, traj, [&](int, int, int) { return calls++ == stop ? 7 + (int)stop : 0; }) == 7 + (int)stop);
+        RUN_REQUIRE(calls == stop + 1);
+    }
+    std::free(traj);
+    return 0;
+#undef RUN_REQUIRE
+}
+
 #define REQUIRE(x) do { if (!(x)) { std::fprintf(stderr, "trial %d: %s failed (line %d)\n", trial, #x, __LINE__); return 1; } } while (0)
 
 int main()
@@ -76,6 +111,7 @@ int main()
         REQUIRE(kp_check_lists((size_t)B * dof, T, old_offs.data(), old_times.data()) == nullptr);
         REQUIRE(kp_check_lists(traj.size() * dof, T, new_offs.data(), new_times.data()) == nullptr);
         REQUIRE(kp_traj_list_ok(B, (int)traj.size(), traj.data()));
+        REQUIRE(run_walk_fails(traj) == 0);
 
         // exactly sized heap arrays: one element too far is a report
         int *merged = (int *)std::malloc(sizeof(int) * ((size_t)B * dof + 1)), *mv = (int *)std::malloc(sizeof(int) * 3 * ((size_t)B + 1));
@@ -130,6 +166,16 @@ int main()
         }
         std::free(merged); std::free(mv); std::free(rec_old); std::free(rec_new); std::free(times);
     }
-    std::printf("kp_merge_fuzz: %d trials ok\n", trial);
+    // the run walk on longer lists: every density from none adjacent to all adjacent, and the corner cases by hand
+    int walks = 0;
+    for (; walks < 2000; walks++) {
+        const int B = 1 + (int)(rng() % 40), keep = (int)(rng() % 11);      // keep / 10: the chance that an index is listed
+        std::vector<int> traj;
+        for (int b = 0; b < B; b++) if ((int)(rng() % 10) < keep) traj.push_back(b);
+        REQUIRE(kp_traj_list_ok(B, (int)traj.size(), traj.data()) && run_walk_fails(traj) == 0);
+    }
+    const std::vector<int> corner[] = {{}, {0}, {5}, {0, 1, 2, 3, 4}, {3, 4, 5}, {0, 2, 4, 6}, {1, 3}, {0, 1, 3, 4, 5, 9}, {0, 2, 3}};
+    for (const std::vector<int> &traj : corner) { REQUIRE(run_walk_fails(traj) == 0); walks++; }
+    std::printf("kp_merge_fuzz: %d trials ok, %d run walks ok\n", trial, walks);
     return 0;
 }

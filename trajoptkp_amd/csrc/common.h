@@ -74,6 +74,27 @@ enum class FdPayload : int { none, jobs, kp_ordered, kp_columns };
 // kernel family of a sweep, chosen per direction by select_variants (names: kpilqr_backward_variant)
 enum class Family : int { generic, t1, tiled, wide, fused };
 
+// ---- what is still valid ("Who says what is still valid") ---------------------------
+// Two aggregates of Ctx, grouped by what their stores are derived from; an event resets an aggregate AS A WHOLE (= {}), so a flag
+// added here later is cleared by construction.  A flag is set by the function that fills its store and by nobody else.
+// From the resident FD payload and the key-point lists: reset by payload_changed (hence by keypoints_changed), size_buffers.
+struct PayloadDerived {
+    bool kpc_valid = false;      // kpc holds ALL differenced columns of the resident FD payload for the current key-points
+    bool kpc_touched = false;    // a raw backward sweep has (re)written kpc from the resident payload since it was uploaded
+    bool kps_valid = false;      // kps holds the slopes of the columns kpc holds (kpc_valid)
+    bool kpcu_valid = false;     // kpcu is expanded from the current kpc
+    bool rec_synced = false;     // the key-point columns of the resident payload (if any) are in the step records: set by the two functions
+                                 // that write them for the whole batch (records_from_payload, linearise), a streamed iteration without a
+                                 // new payload writes them first when it is clear.  NOT cleared by calls that overwrite records by hand
+                                 // (set_AB, a record pointer, the A filter): such a sweep interpolates what they wrote
+};
+// From the key-point lists alone: reset by keypoints_changed, size_buffers.
+struct ListsDerived {
+    bool entry_tables_valid = false;     // kp_entry, kp_entry_list
+    bool segent_valid = false;           // segent
+    bool kpu_valid = false;              // the union lists (kpu_offsets, kpu_times, kpu_src, kpu_traj_first)
+};
+
 struct Ctx {
     kpilqr_dims d{};
     int n = 0;
@@ -82,6 +103,8 @@ struct Ctx {
     int n_simd = 1024;             // SIMDs on the device (CUs x 4)
     bool own_stream = false;
     std::string err;
+    PayloadDerived pay;
+    ListsDerived lst;
 
     // device buffers (every DevBuf member is listed in for_each_buffer below; capacities are remembered, kpilqr_resize re-uses them)
     bool is_view = false;         // a copy made by make_view: it borrows the context's buffers and never allocates (reserve refuses)
@@ -105,9 +128,8 @@ struct Ctx {
     DevBuf<int> traj_list;        // [batch]: the trajectories of the partial record calls in flight (kpilqr_fd_interpolate_partial ...)
     DevBuf<int2> segmap;          // [batch][dof][T]: (start,end) key-points around t, or (-1,-1)
     // [batch][dof][T]: CSR entry of the key-point at or before t (the one-pass linearisation fetches a segment's endpoints by
-    // entry), or -1 outside the list.  Built with segmap on a context that has records; on demand on a fused one (segent_valid)
+    // entry), or -1 outside the list.  Built with segmap on a context that has records; on demand on a fused one (lst.segent_valid)
     DevBuf<int> segent;
-    bool segent_valid = false;
     DevBuf<int> kp_offsets;       // [batch*dof+1]
     DevBuf<int> kp_times;         // [kp_total]
     bool have_kp = false;
@@ -129,24 +151,16 @@ struct Ctx {
     // i.e. 3n doubles per (trajectory, DoF, key-point) instead of a whole record per (trajectory, step).  The records are
     // allocated on demand when something asks for the materialised sequence (kpilqr_interpolate, get_AB, the error test ...).
     DevBuf<double> kpc;
-    bool kpc_valid = false;      // kpc holds ALL differenced columns of the resident FD payload for the current key-points
-    bool kpc_touched = false;    // a raw backward sweep has (re)written kpc from the resident payload since it was uploaded
     // slope store beside kpc (k_kp_slopes): kps [entry][3][n][2] = (column value, (column of the list's next key-point - this column) /
     // (time gap)) pairs, slope 0 for a list's last entry.  Read by the general (per-DoF list) forms of the one-wave sweeps; allocated only when the lists may be
     // ragged (kp_known_uniform: the host has seen that every trajectory's DoFs share one list -- then the device flag says the same
     // and only the segment-loop forms run)
     DevBuf<double> kps;
-    bool kps_valid = false;      // kps holds the slopes of the columns kpc holds (kpc_valid)
     bool kp_known_uniform = false;
     int kp_view_entries = -1;    // a view of a trajectory range: the CSR entries of its trajectories (first: fdk_first); -1: the context
     DevBuf<int> kp_entry;        // [batch*dof][T]: CSR entry of (list, t), or -1        (built with the segment map)
     DevBuf<int> kp_entry_list;   // [entries]: list (= b*dof + d) of a CSR entry
-    bool entry_tables_valid = false;
     bool have_rec = false;       // step records allocated (always on a non-fused context; on demand on a fused one)
-    bool rec_synced = false;     // a linearising call has written the key-point columns of the resident payload (if any) into the records
-                                 // since it arrived: cleared by payload_changed, a streamed iteration without a new payload writes them
-                                 // first when it is clear.  NOT cleared by calls that overwrite records by hand (set_AB, a record pointer,
-                                 // the A filter): such a sweep interpolates what they wrote
     int kp_total_host = -1;      // number of CSR entries when the host knows it (kpilqr_set_keypoints), else -1
     int *kp_traj_first_host = nullptr;                // [batch+1] first CSR entry of every trajectory (host copy), or null
     FdPayload fd_payload = FdPayload::none;
@@ -167,8 +181,6 @@ struct Ctx {
     DevBuf<double> kpcu;
     DevBuf<int> kpu_uniform;     // the device flag a union view hands to the sweeps: always non-zero
     bool union_on = false;       // the flag is set and the context is fused (one-tile shape)
-    bool kpu_valid = false;      // the union lists are built for the current key-points
-    bool kpcu_valid = false;     // kpcu is expanded from the current kpc
     int kpu_total = 0;           // sum over trajectories of |U_b| (entries_u = dof * kpu_total)
     int *kpu_traj_first_host = nullptr;               // [batch+1] host copy of kpu_traj_first
 
@@ -285,7 +297,7 @@ hipError_t launch_fd_difference_kpc(Ctx *c);             // job lists -> key-poi
 // key-point ordered payload -> key-point column store (only_if_ragged: leaves at once when the device flag kp_uniform is set;
 // with_slopes: also the slope store of per-DoF lists, which the caller has sized for the current lists -- ensure_kps)
 hipError_t launch_fd_kp_difference(Ctx *c, bool only_if_ragged = false, bool with_slopes = true);
-hipError_t launch_kpc_to_records(Ctx *c);                // key-point column store -> step records
+hipError_t launch_kpc_to_records(Ctx *c, int first, int entries);   // key-point column store -> step records, CSR entries [first, first + entries)
 hipError_t launch_kp_slopes(Ctx *c, bool only_if_ragged = true);   // key-point column store -> slope store (per-DoF lists only)
 hipError_t launch_build_entry_tables(Ctx *c);            // kp_entry, kp_entry_list from the CSR lists
 hipError_t launch_copy_out(hipStream_t s, double *dst_host, const double *src_dev, size_t count);   // D2H by a kernel

@@ -314,19 +314,19 @@ k_kpc_to_records(RecLayout L, int dof, int T, long long npairs_total, unsigned l
     }
 }
 
-// entries [e0, e0 + ne) of the context's lists (a view: its own trajectories)
-hipError_t launch_kpc_to_records(Ctx *c)
+// entries [first, first + entries) of the context's lists (the whole payload: c->fdk_first, c->fdk_entries; a view: its own trajectories)
+hipError_t launch_kpc_to_records(Ctx *c, int first, int entries)
 {
-    if (c->fdk_entries == 0) return hipSuccess;
+    if (entries == 0) return hipSuccess;
     const int np = c->n >> 1;
-    const long long npairs = (long long)c->fdk_entries * 3 * np;
+    const long long npairs = (long long)entries * 3 * np;
     const unsigned long long magic = np > 1 ? ~0ULL / (unsigned)np + 1ULL : 0ULL;
     const long long want = (npairs + 1023) / 1024;
     const long long cap = (long long)(c->n_simd / 4) * 64;
     const int blocks = (int)(want < cap ? (want < 1 ? 1 : want) : cap);
-    const size_t o = (size_t)c->fdk_first * 3;
-    hipLaunchKernelGGL(k_kpc_to_records, dim3(blocks), dim3(256), 0, c->stream, c->L, c->d.dof, c->d.T, npairs, magic, c->kp_times + c->fdk_first,
-                       c->kp_entry_list + c->fdk_first, c->kpc + o * c->n, c->rec_fd_base);
+    const size_t o = (size_t)first * 3;
+    hipLaunchKernelGGL(k_kpc_to_records, dim3(blocks), dim3(256), 0, c->stream, c->L, c->d.dof, c->d.T, npairs, magic, c->kp_times + first,
+                       c->kp_entry_list + first, c->kpc + o * c->n, c->rec_fd_base);
     return hipGetLastError();
 }
 

@@ -1,6 +1,7 @@
-// kp_merge.h -- the host arithmetic of kpilqr_update_keypoints: checks of per-DoF key-point lists, their per-trajectory flags, and
-// the merge of a subset's new lists into the batch CSR.  Plain C++ without HIP on purpose: kpilqr_api.cpp uses it, and a
-// stand-alone program can drive it under the host sanitizers (tools/kp_merge_fuzz.cpp).
+// kp_merge.h -- the host arithmetic of kpilqr_update_keypoints and the calls on a subset of the batch: checks of per-DoF key-point
+// lists, their per-trajectory flags, the walk over a subset's runs of adjacent trajectories, and the merge of a subset's new lists
+// into the batch CSR.  Plain C++ without HIP on purpose: kpilqr_api.cpp uses it, and a stand-alone program can drive it under the
+// host sanitizers (tools/kp_merge_fuzz.cpp).
 #pragma once
 
 #include <stddef.h>
@@ -54,6 +55,21 @@ inline bool kp_traj_list_ok(int batch, int count, const int *traj)
     for (int i = 0; i < count; i++)
         if (traj[i] < 0 || traj[i] >= batch || (i > 0 && traj[i] <= traj[i - 1])) return false;
     return true;
+}
+
+// f(i, first, len) for every maximal run traj[i] .. traj[i + len - 1] = first .. first + len - 1 of adjacent trajectories in a
+// strictly increasing list, in order (the calls on a subset copy or launch once per run).  Stops at the first non-zero result of f
+// and returns it; 0: every run was visited.
+template <class F>
+inline int kp_for_each_run(int count, const int *traj, F f)
+{
+    for (int i = 0; i < count;) {
+        int j = i;
+        while (j + 1 < count && traj[j + 1] == traj[j] + 1) j++;
+        if (const int rc = f(i, traj[i], j - i + 1)) return rc;
+        i = j + 1;
+    }
+    return 0;
 }
 
 // The batch CSR with the lists of the `count` trajectories in `traj` replaced: new_offs [count*dof+1] (from 0) are theirs, old_offs

@@ -33,6 +33,13 @@ static bool is_pinned(const void *p)
     return a.type == hipMemoryTypeHost;
 }
 
+// an async copy from (or the launch behind one of) a pageable host array is complete before the caller has the array back
+static int wait_unless_pinned(kpilqr_ctx *c, const void *host)
+{
+    if (!is_pinned(host)) KP_HIP(c, hipStreamSynchronize(c->stream));
+    return KPILQR_OK;
+}
+
 // chunk streams of kpilqr_iterate_streamed -> the context's stream: everything enqueued by a streamed iteration is
 // ordered before whatever the caller enqueues next
 static int join_pipeline(kpilqr_ctx *c)
@@ -136,7 +143,7 @@ static int size_buffers(kpilqr_ctx *c)
     const size_t segent_bytes = B * dims->dof * T * sizeof(int);
     // k_build_segmap writes segent wherever it exists: one a fused context built on demand must not outlive a shape it does not cover
     if (c->fused && would_grow(c->segent, segent_bytes)) KP_HIP(c, release(c->segent));
-    c->segent_valid = false;
+    c->pay = {}; c->lst = {};          // whatever was derived from the old shape's payload and lists
     struct Row { DevMem *buf; size_t bytes; bool zero; };      // zero: records start zeroed so that padding / never-written columns are defined
     const Row rows[] = {
         // a fused (one-tile) context keeps key-point columns only (Ctx::kpc); its records appear on demand (ensure_records)
@@ -195,7 +202,9 @@ static int ensure_kpc(kpilqr_ctx *c)
     if (rc < 0) return rc;
     if (rc > 0) {              // a new store starts zeroed, slack included: entries come into use without passing through here
         KP_HIP(c, hipMemsetAsync(c->kpc, 0, c->kpc.cap, c->stream));
-        c->kpc_valid = c->kpc_touched = c->kps_valid = c->kpcu_valid = false;
+        const bool rec_synced = c->pay.rec_synced;           // (the records are not made from this store's bytes: they keep what they hold)
+        c->pay = {};
+        c->pay.rec_synced = rec_synced;
     }
     return KPILQR_OK;
 }
@@ -207,30 +216,30 @@ static int ensure_kps(kpilqr_ctx *c, bool force = false)
     const size_t need = kp_entries(c) * 6 * (size_t)c->n * 8;              // (value, slope) pairs
     const int rc = reserve(c, c->kps, need, kQuarter, false);
     if (rc < 0) return rc;
-    if (rc > 0) c->kps_valid = false;
+    if (rc > 0) c->pay.kps_valid = false;
     return KPILQR_OK;
 }
 
 // the slopes of the columns kpc holds (per-DoF lists: the general forms of the one-wave sweeps walk them; k_kp_slopes leaves at
-// once when the device says the set is uniform)
-static int slopes_for_kpc(kpilqr_ctx *c)
+// once when the device says the set is uniform).  always: whatever the lists and the flag say (kpilqr_backward_stats' general form)
+static int slopes_for_kpc(kpilqr_ctx *c, bool always = false)
 {
-    if (c->kps_valid || c->kp_known_uniform || !c->kps) return KPILQR_OK;
-    KP_HIP(c, launch_kp_slopes(c, true));
-    c->kps_valid = true;
+    if (!always && (c->pay.kps_valid || c->kp_known_uniform || !c->kps)) return KPILQR_OK;
+    KP_HIP(c, launch_kp_slopes(c, !always));
+    c->pay.kps_valid = true;
     return KPILQR_OK;
 }
 
 // kp_entry [list][t] and kp_entry_list [entry] for the current lists
 static int ensure_entry_tables(kpilqr_ctx *c)
 {
-    if (c->entry_tables_valid) return KPILQR_OK;
+    if (c->lst.entry_tables_valid) return KPILQR_OK;
     int rc = reserve(c, c->kp_entry, (size_t)c->d.batch * c->d.dof * c->d.T * sizeof(int), kExact, false);
     if (rc < 0) return rc;
     rc = reserve(c, c->kp_entry_list, (kp_entries(c) ? kp_entries(c) : 1) * sizeof(int), Slack{4, 0}, false);
     if (rc < 0) return rc;
     KP_HIP(c, launch_build_entry_tables(c));
-    c->entry_tables_valid = true;
+    c->lst.entry_tables_valid = true;
     return KPILQR_OK;
 }
 
@@ -241,7 +250,7 @@ static int difference_to_kpc(kpilqr_ctx *c, bool want_slopes = true)
     if (c->fd_payload == FdPayload::none || !c->have_kp) return KPILQR_OK;
     { const int rcp = check_complete(c, "differencing the resident payload"); if (rcp) return rcp; }      // (whoever asks: the entry points check first)
     if (c->fd_payload == FdPayload::kp_columns) {                       // the columns ARE the payload
-        if (!c->kpc_valid) return set_err(c, KPILQR_ERR_STATE, "the key-point columns are gone (new key-points): upload them again");
+        if (!c->pay.kpc_valid) return set_err(c, KPILQR_ERR_STATE, "the key-point columns are gone (new key-points): upload them again");
         return KPILQR_OK;
     }
     int rc = ensure_kpc(c);
@@ -251,45 +260,47 @@ static int difference_to_kpc(kpilqr_ctx *c, bool want_slopes = true)
     // written past its end.
     const bool slopes = c->fused && want_slopes;
     if (slopes) { rc = ensure_kps(c); if (rc) return rc; }
-    c->kps_valid = false;
+    c->pay.kps_valid = false;
     if (c->fd_payload == FdPayload::jobs) {
         rc = ensure_entry_tables(c);
         if (rc) return rc;
         KP_HIP(c, launch_fd_difference_kpc(c));
     } else {
         KP_HIP(c, launch_fd_kp_difference(c, false, slopes));
-        if (slopes && c->kps && !c->kp_known_uniform) c->kps_valid = true;         // (the slope store of per-DoF lists is written in the same pass)
+        if (slopes && c->kps && !c->kp_known_uniform) c->pay.kps_valid = true;         // (the slope store of per-DoF lists is written in the same pass)
     }
-    c->kpc_valid = true;
+    c->pay.kpc_valid = true;
     return KPILQR_OK;
 }
 
 // The key-point columns of the resident FD payload written into the step records (what kpilqr_fd_difference means on a
-// context that has records)
+// context that has records): the whole batch's (a view: its chunk's), and the one place besides linearise that says so
 static int records_from_payload(kpilqr_ctx *c)
 {
-    if (c->fd_payload == FdPayload::jobs) { KP_HIP(c, launch_fd_difference(c)); return KPILQR_OK; }
-    { const int rcp = check_complete(c, "the records of the resident payload"); if (rcp) return rcp; }
-    if (payload_by_entry(c)) {
-        if (!c->have_kp) return KPILQR_OK;
-        int rc = KPILQR_OK;
-        if (!c->kpc_valid) rc = difference_to_kpc(c);
-        if (rc) return rc;
-        rc = ensure_entry_tables(c);
-        if (rc) return rc;
-        KP_HIP(c, launch_kpc_to_records(c));
+    if (c->fd_payload == FdPayload::jobs) KP_HIP(c, launch_fd_difference(c));
+    else {
+        { const int rcp = check_complete(c, "the records of the resident payload"); if (rcp) return rcp; }
+        if (payload_by_entry(c) && c->have_kp) {
+            int rc = KPILQR_OK;
+            if (!c->pay.kpc_valid) rc = difference_to_kpc(c);
+            if (rc) return rc;
+            rc = ensure_entry_tables(c);
+            if (rc) return rc;
+            KP_HIP(c, launch_kpc_to_records(c, c->fdk_first, c->fdk_entries));
+        }
     }
+    c->pay.rec_synced = true;          // (no payload or no lists: nothing to write)
     return KPILQR_OK;
 }
 
 // segent for the current lists: built with segmap where the context has it allocated, else (a fused context) here
 static int ensure_segent(kpilqr_ctx *c)
 {
-    if (c->segent_valid) return KPILQR_OK;
+    if (c->lst.segent_valid) return KPILQR_OK;
     const int rc = reserve(c, c->segent, (size_t)c->d.batch * c->d.dof * c->d.T * sizeof(int), kExact, false);
     if (rc < 0) return rc;
     KP_HIP(c, launch_build_segmap(c, true));
-    c->segent_valid = true;
+    c->lst.segent_valid = true;
     return KPILQR_OK;
 }
 
@@ -300,12 +311,12 @@ static int ensure_segent(kpilqr_ctx *c)
 static bool linearise_one_pass(const kpilqr_ctx *c)
 {
     if (c->tune.fd_interp == 0) return false;
-    if (c->fd_payload == FdPayload::kp_columns) return c->kpc_valid;
+    if (c->fd_payload == FdPayload::kp_columns) return c->pay.kpc_valid;
     return c->fd_payload == FdPayload::kp_ordered;
 }
 
 // from_payload = false: the records hold the payload's key-point columns already (a chunk of a streamed iteration that brought
-// no new payload), so k_interpolate alone runs.
+// no new payload), so k_interpolate alone runs and rec_synced is left as it is.
 static int linearise(kpilqr_ctx *c, bool from_payload = true)
 {
     if (from_payload && linearise_one_pass(c)) {
@@ -313,6 +324,7 @@ static int linearise(kpilqr_ctx *c, bool from_payload = true)
         if (rc) return rc;
         KP_HIP(c, launch_fd_kp_interpolate(c));
         c->last_linearise = c->fd_payload == FdPayload::kp_columns ? "kp_columns_interpolate" : "fd_kp_interpolate";
+        c->pay.rec_synced = true;
         return KPILQR_OK;
     }
     if (from_payload) { const int rc = records_from_payload(c); if (rc) return rc; }
@@ -331,7 +343,7 @@ static int ensure_record_storage(kpilqr_ctx *c)
         if (rc < 0) return rc;
         c->rec_fd_base = c->rec;
         c->have_rec = true;
-        c->rec_synced = false;
+        c->pay.rec_synced = false;
     }
     return KPILQR_OK;
 }
@@ -339,20 +351,13 @@ static int ensure_record_storage(kpilqr_ctx *c)
 static int ensure_records(kpilqr_ctx *c)
 {
     { const int rc = ensure_record_storage(c); if (rc) return rc; }
-    if (!c->rec_synced) {
-        const int rc = records_from_payload(c);
-        if (rc) return rc;
-        c->rec_synced = true;
-    }
-    return KPILQR_OK;
+    return c->pay.rec_synced ? KPILQR_OK : records_from_payload(c);
 }
 
 // a new FD payload or new key-points: whatever was derived from the old ones is stale
 static void payload_changed(kpilqr_ctx *c)
 {
-    c->kpc_valid = c->kpc_touched = c->kps_valid = false;
-    c->kpcu_valid = false;          // (the union columns are expanded from kpc)
-    c->rec_synced = false;
+    c->pay = {};
     c->n_pending = c->pending_entries = 0;      // (a whole payload, new lists for everybody, or the partial upload that was waited for)
 }
 
@@ -365,15 +370,49 @@ static int check_complete(kpilqr_ctx *c, const char *who)
                    "kpilqr_upload_fd_kp_partial / kpilqr_upload_kp_columns_partial is missing");
 }
 
+// ---- the calls on a subset of the batch (kpilqr_update_keypoints and the _partial family) ----------------------------------------
+// What each of them does first, before anything is enqueued or changed: the argument check, KP_ENTER, and for `traj` [count]
+//   listed          not through a view of a trajectory range; strictly increasing and within [0, batch)
+//   listed_or_view  the list check alone (kpilqr_download_gains_partial reads through a view too; kpilqr_update_keypoints refuses
+//                   one later, in the words of everything that allocates)
+//   pending         nothing: the two payload uploads hold traj against the pending set (check_partial), and for them count = 0 is
+//                   a call like any other while ranges are pending
+// -> 1: go on | KPILQR_OK: nobody is listed, nothing to do | < 0: refused.  (They leave through wait_unless_pinned where a
+// pageable array of the caller's is still being read.)
+enum class Subset : int { listed, listed_or_view, pending };
+static int enter_subset(kpilqr_ctx *c, const char *who, int count, const int *traj, Subset kind = Subset::listed)
+{
+    if (!c || count < 0 || (count > 0 && !traj)) return KPILQR_ERR_ARG;
+    KP_ENTER(c);
+    if (kind == Subset::pending) return 1;
+    if (count == 0) return KPILQR_OK;
+    if (kind == Subset::listed && c->is_view) return set_err(c, KPILQR_ERR_STATE, std::string(who) + ": not through a view of a trajectory range");
+    if (!kp_traj_list_ok(c->d.batch, count, traj)) return set_err(c, KPILQR_ERR_ARG, std::string(who) + ": traj must be strictly increasing and within [0, batch)");
+    return 1;
+}
+
 // New key-point lists of `total` entries are on the device: everything that was derived from the old ones is stale, and a payload
 // laid out by them is dropped (it has to follow them)
 static void keypoints_changed(kpilqr_ctx *c, int total)
 {
     c->kp_total_host = total;
-    c->entry_tables_valid = false;
-    c->kpu_valid = false;
+    c->lst = {};
     if (payload_by_entry(c)) { c->fd_payload = FdPayload::none; c->fdk_entries = 0; }
     payload_changed(c);
+}
+
+// What kpilqr_set_keypoints, kpilqr_update_keypoints and kpilqr_generate_keypoints leave behind once the new lists (`total`
+// entries) are enqueued on the device: the segment map, the event -- keypoints_changed FIRST, it resets the aggregate segent's
+// mark lives in -- and then what is known about the new lists.  uniform: every trajectory's DoFs share one list.
+static int lists_installed(kpilqr_ctx *c, int total, bool canonical, bool uniform)
+{
+    KP_HIP(c, launch_build_segmap(c));
+    keypoints_changed(c, total);
+    c->lst.segent_valid = c->segent != nullptr;          // (k_build_segmap writes segent wherever it exists)
+    c->have_kp = true;
+    c->kp_canonical = canonical;
+    c->kp_known_uniform = uniform && c->tune.fused_uni != 0;      // (KPILQR_FUSED_UNI=0: the general forms run on every set)
+    return KPILQR_OK;
 }
 
 // Host copy of the first CSR entry of every trajectory (kpilqr_iterate_streamed cuts an entry-ordered payload into chunks by it);
@@ -430,7 +469,7 @@ static bool union_route(const kpilqr_ctx *c)
 // per key-point change), scanned on the host, and the buffers sized from the scan; a second launch writes the lists.
 static int ensure_union(kpilqr_ctx *c)
 {
-    if (c->kpu_valid) return KPILQR_OK;
+    if (c->lst.kpu_valid) return KPILQR_OK;
     if (!c->kp_canonical)
         return set_err(c, KPILQR_ERR_STATE, "the key-point union needs canonical key-points (per DoF: strictly increasing, first 0, last T-1)");
     const size_t B = c->d.batch, dof = c->d.dof;
@@ -463,8 +502,8 @@ static int ensure_union(kpilqr_ctx *c)
     KP_HIP(c, hipMemcpyAsync(c->kpu_traj_first, first, (B + 1) * sizeof(int), hipMemcpyHostToDevice, c->stream));
     KP_HIP(c, hipMemsetAsync(c->kpu_uniform, 1, sizeof(int), c->stream));          // any non-zero value: uniform
     KP_HIP(c, launch_kp_union_build(c));
-    c->kpu_valid = true;
-    c->kpcu_valid = false;
+    c->lst.kpu_valid = true;
+    c->pay.kpcu_valid = false;
     return KPILQR_OK;
 }
 
@@ -473,11 +512,11 @@ static int ensure_union_columns(kpilqr_ctx *c)
 {
     int rc = ensure_union(c);
     if (rc) return rc;
-    if (c->kpcu_valid) return KPILQR_OK;
+    if (c->pay.kpcu_valid) return KPILQR_OK;
     rc = reserve(c, c->kpcu, (size_t)c->d.dof * c->kpu_total * 3 * c->n * 8, kQuarter, false);
     if (rc < 0) return rc;
     KP_HIP(c, launch_kp_union_expand(c));
-    c->kpcu_valid = c->kpc_valid;          // (no payload: kpc is whatever it was left as, and is expanded again next time)
+    c->pay.kpcu_valid = c->pay.kpc_valid;          // (no payload: kpc is whatever it was left as, and is expanded again next time)
     return KPILQR_OK;
 }
 
@@ -486,7 +525,7 @@ static int prepare_union(kpilqr_ctx *c)
 {
     int rc = ensure_kpc(c);
     if (rc) return rc;
-    if (!c->kpc_valid) { rc = difference_to_kpc(c, false); if (rc) return rc; }
+    if (!c->pay.kpc_valid) { rc = difference_to_kpc(c, false); if (rc) return rc; }
     return ensure_union_columns(c);
 }
 
@@ -498,8 +537,8 @@ static void make_union_view(const kpilqr_ctx *c, kpilqr_ctx *v)
     *v = *c;
     v->is_view = true;
     v->kp_offsets = c->kpu_offsets; v->kp_times = c->kpu_times; v->kp_uniform = c->kpu_uniform;
-    v->kpc = c->kpcu; v->kpc_valid = true;
-    v->kps = DevBuf<double>{}; v->kps_valid = false;
+    v->kpc = c->kpcu; v->pay.kpc_valid = true;
+    v->kps = DevBuf<double>{}; v->pay.kps_valid = false;
     v->kp_known_uniform = true;
     v->fd_payload = FdPayload::kp_columns;          // (nothing to difference: plan_backward_fused plans raw = false)
 }
@@ -659,10 +698,8 @@ int kpilqr_resize(kpilqr_ctx *c, int new_dof, int new_num_ctrl, int new_horizon)
     }
     c->have_kp = c->kp_canonical = c->have_states = c->kp_known_uniform = false;
     c->njobs = c->nnom = 0;
-    c->fd_payload = FdPayload::none; c->fdk_entries = 0; c->entry_tables_valid = false; c->kp_total_host = -1;
-    forget_lists(c);                                     // (sized by the old batch * dof)
-    payload_changed(c);
-    c->kpu_valid = false;
+    c->fd_payload = FdPayload::none; c->fdk_entries = 0; c->kp_total_host = -1;
+    forget_lists(c);                                     // (sized by the old batch * dof; size_buffers has reset both validity aggregates)
     c->ru_zero = true;                                   // size_buffers zeroed r_u
     c->rx_const_on = false; c->rx_buf_valid = true; c->rx_whole = false;
     // the key-point placement buffers were sized by the old shape: they are allocated again on first use
@@ -764,16 +801,11 @@ int kpilqr_set_keypoints(kpilqr_ctx *c, const int *kp_offsets, const int *kp_tim
     // and no slope store is needed
     for (int b = 0; b < c->d.batch; b++) c->kp_flags_host[b] = kp_traj_flags(c->d.dof, c->d.T, kp_offsets + (size_t)b * c->d.dof, kp_times);
     const unsigned char flags = kp_batch_flags(c->d.batch, c->kp_flags_host);
-    c->kp_canonical = (flags & kKpCanonical) != 0;
-    c->kp_known_uniform = (flags & kKpUniform) && c->tune.fused_uni != 0;     // (KPILQR_FUSED_UNI=0: the general forms run on every set)
     KP_HIP(c, hipMemcpyAsync(c->kp_offsets, kp_offsets, (nlists + 1) * sizeof(int), hipMemcpyHostToDevice, c->stream));
     KP_HIP(c, hipMemcpyAsync(c->kp_times, kp_times, (size_t)total * sizeof(int), hipMemcpyHostToDevice, c->stream));
-    KP_HIP(c, launch_build_segmap(c));
-    c->segent_valid = c->segent != nullptr;
+    { const int rci = lists_installed(c, total, flags & kKpCanonical, flags & kKpUniform); if (rci) return rci; }
     // pageable host arrays: make the copies complete before returning control (pinned ones are read in place)
     if (!(is_pinned(kp_offsets) && is_pinned(kp_times))) KP_HIP(c, hipStreamSynchronize(c->stream));
-    c->have_kp = true;
-    keypoints_changed(c, total);
     if (!remember_traj_first(c, kp_offsets)) return set_err(c, KPILQR_ERR_ALLOC, "host allocation failed");
     return KPILQR_OK;
 }
@@ -797,12 +829,11 @@ static int ensure_offsets_mirror(kpilqr_ctx *c)
 
 int kpilqr_update_keypoints(kpilqr_ctx *c, int count, const int *traj, const int *kp_offsets, const int *kp_times)
 {
-    if (!c || count < 0 || (count > 0 && (!traj || !kp_offsets || !kp_times))) return KPILQR_ERR_ARG;
-    KP_ENTER(c);
-    if (count == 0) return KPILQR_OK;                    // nobody's lists change: nothing becomes invalid
+    if (count > 0 && (!kp_offsets || !kp_times)) return KPILQR_ERR_ARG;
+    // (count = 0: nobody's lists change, nothing becomes invalid; a view is refused below, in the words of everything that allocates)
+    { const int go = enter_subset(c, "kpilqr_update_keypoints", count, traj, Subset::listed_or_view); if (go <= 0) return go; }
     const int B = c->d.batch, dof = c->d.dof;
     const size_t nlists = (size_t)B * dof, nnew = (size_t)count * dof, B1 = (size_t)B + 1;
-    if (!kp_traj_list_ok(B, count, traj)) return set_err(c, KPILQR_ERR_ARG, "kpilqr_update_keypoints: traj must be strictly increasing and within [0, batch)");
     if (const char *bad = kp_check_lists(nnew, c->d.T, kp_offsets, kp_times)) return set_err(c, KPILQR_ERR_ARG, bad);
     if (!c->have_kp) return set_err(c, KPILQR_ERR_STATE, "kpilqr_update_keypoints before kpilqr_set_keypoints / kpilqr_generate_keypoints");
     if (c->is_view) return set_err(c, KPILQR_ERR_STATE, "a view of a trajectory range never allocates: its context sizes the buffers first");
@@ -826,7 +857,7 @@ int kpilqr_update_keypoints(kpilqr_ctx *c, int count, const int *traj, const int
     // a payload laid out by entry survives: the records of everybody who is not listed move to their new offsets.  Job lists carry
     // their own indices and stay as they are; without a payload there is nothing to carry.
     const FdPayload kind = c->fd_payload;
-    const bool carry = kind == FdPayload::kp_ordered || (kind == FdPayload::kp_columns && c->kpc_valid);
+    const bool carry = kind == FdPayload::kp_ordered || (kind == FdPayload::kp_columns && c->pay.kpc_valid);
     DevMem *live = nullptr, *alt = nullptr;
     size_t rec_bytes = 0;
     if (kind == FdPayload::kp_ordered) { live = &c->fdk_dev; alt = &c->fdk_alt; rec_bytes = c->fdk_stride(); }
@@ -857,19 +888,15 @@ int kpilqr_update_keypoints(kpilqr_ctx *c, int count, const int *traj, const int
         KP_HIP(c, launch_relocate_entries(c, (int)(rec_bytes / 16), longest_kept, mv_dev, mv_dev + B1, mv_dev + 2 * B1, live->p, alt->p));
         std::swap(*live, *alt);
     }
-    KP_HIP(c, launch_build_segmap(c));
-    c->segent_valid = c->segent != nullptr;
-    // the staging arrays above are this call's own: they are read before it returns
-    KP_HIP(c, hipStreamSynchronize(c->stream));
-
     // ---- the context as kpilqr_set_keypoints(merged lists) leaves it -- except that the payload stays, with ranges pending ---------
     for (int i = 0; i < count; i++) c->kp_flags_host[traj[i]] = kp_traj_flags(dof, c->d.T, kp_offsets + (size_t)i * dof, kp_times);
     const unsigned char flags = kp_batch_flags(B, c->kp_flags_host);
-    c->kp_canonical = (flags & kKpCanonical) != 0;
-    c->kp_known_uniform = (flags & kKpUniform) && c->tune.fused_uni != 0;
+    rc = lists_installed(c, total, flags & kKpCanonical, flags & kKpUniform);
+    if (rc) return rc;
+    // the staging arrays above are this call's own: they are read before it returns
+    KP_HIP(c, hipStreamSynchronize(c->stream));
     free(c->kp_offsets_host);
     c->kp_offsets_host = merged; guard.a = nullptr;
-    keypoints_changed(c, total);
     if (!remember_traj_first(c, merged)) return set_err(c, KPILQR_ERR_ALLOC, "host allocation failed");
     if (carry) {
         if (!c->kp_pending_host) c->kp_pending_host = (int *)malloc(sizeof(int) * (size_t)B);
@@ -922,11 +949,6 @@ int kpilqr_generate_keypoints(kpilqr_ctx *c, const char *method, int min_N, int 
         KP_HIP(c, hipStreamSynchronize(c->stream));       // the host array may be pageable
     }
     KP_HIP(c, launch_generate_keypoints(c, mth, min_N, max_N, dt, thresholds ? c->kp_thr : nullptr, c->X_states, c->kp_mask, c->kp_count));
-    KP_HIP(c, launch_build_segmap(c));
-    c->segent_valid = c->segent != nullptr;
-    c->have_kp = true;
-    c->kp_known_uniform = mth == 0 && c->tune.fused_uni != 0;    // set_interval: one list for all DoFs; the other methods place per DoF
-    c->kp_canonical = true;      // rows 0 and T-1 are always full and the lists are strictly increasing by construction
     // The lists exist on the device only (kpilqr_get_keypoints brings them to the host), but their TOTAL is read back here --
     // one int: the column store and the entry tables are sized from it (not from the worst case batch * dof * T: 7.2 GB
     // against 1.4 GB at the headline shape), and the `entries` of a key-point ordered upload is checked against it.
@@ -935,7 +957,10 @@ int kpilqr_generate_keypoints(kpilqr_ctx *c, const char *method, int min_N, int 
         KP_HIP(c, hipMemcpyAsync(&total, c->kp_offsets + nlists, sizeof(int), hipMemcpyDeviceToHost, c->stream));
         KP_HIP(c, hipStreamSynchronize(c->stream));
         if (total < 0 || (size_t)total > nlists * T) return set_err(c, KPILQR_ERR_HIP, "kpilqr_generate_keypoints: implausible key-point count read back");
-        keypoints_changed(c, total);
+        // canonical: rows 0 and T-1 are always full and the lists are strictly increasing by construction; set_interval: one list
+        // for all DoFs, the other methods place per DoF
+        const int rci = lists_installed(c, total, true, mth == 0);
+        if (rci) return rci;
     }
     if (c->kp_traj_first_host) { free(c->kp_traj_first_host); c->kp_traj_first_host = nullptr; }
     // (the lists exist on the device only: kpilqr_update_keypoints reads the offsets back when it first needs them)
@@ -1069,8 +1094,7 @@ int kpilqr_upload_fd_slab(kpilqr_ctx *c, const void *slab, int njobs, int nnom, 
     if (njobs) KP_HIP(c, hipMemcpyAsync(c->fd_dev, slab, L.bytes, hipMemcpyHostToDevice, c->stream));   // the one DMA
     c->njobs = njobs; c->nnom = nnom; c->eps = eps;
     c->fd_payload = FdPayload::jobs; payload_changed(c);
-    if (!is_pinned(slab)) KP_HIP(c, hipStreamSynchronize(c->stream));
-    return KPILQR_OK;
+    return wait_unless_pinned(c, slab);
 }
 
 // ---- key-point ordered FD payload ---------------------------------------------------------------------------------------
@@ -1111,8 +1135,7 @@ int kpilqr_upload_fd_kp(kpilqr_ctx *c, const void *slab, int entries, double eps
     if (entries) KP_HIP(c, hipMemcpyAsync(c->fdk_dev, slab, L.bytes, hipMemcpyHostToDevice, c->stream));   // the one DMA
     c->fdk_entries = entries; c->fdk_first = 0; c->eps = eps;
     c->fd_payload = FdPayload::kp_ordered; payload_changed(c);
-    if (!is_pinned(slab)) KP_HIP(c, hipStreamSynchronize(c->stream));
-    return KPILQR_OK;
+    return wait_unless_pinned(c, slab);
 }
 
 // The differenced key-point columns as the payload (FdPayload::kp_columns): straight into the column store
@@ -1128,12 +1151,12 @@ int kpilqr_upload_kp_columns(kpilqr_ctx *c, const double *columns, int entries)
     if (entries) KP_HIP(c, hipMemcpyAsync(c->kpc, columns, (size_t)entries * 3 * c->n * 8, hipMemcpyHostToDevice, c->stream));
     c->fd_payload = FdPayload::kp_columns; c->fdk_entries = entries; c->fdk_first = 0;      // (the entry range, as for the key-point ordered payload)
     payload_changed(c);
-    c->kpc_valid = true;
-    if (!is_pinned(columns)) KP_HIP(c, hipStreamSynchronize(c->stream));
-    return KPILQR_OK;
+    c->pay.kpc_valid = true;
+    return wait_unless_pinned(c, columns);
 }
 
 // ---- the pending ranges of kpilqr_update_keypoints filled in: one copy per run of adjacent trajectories, straight into place --------
+// (entered through enter_subset(..., Subset::pending): `traj` is held against the pending set here, not against the batch)
 static int check_partial(kpilqr_ctx *c, const char *who, FdPayload kind, int count, const int *traj, int entries)
 {
     const std::string w(who);
@@ -1148,21 +1171,18 @@ static int check_partial(kpilqr_ctx *c, const char *who, FdPayload kind, int cou
 static int upload_runs(kpilqr_ctx *c, int count, const int *traj, const char *src, char *dst, size_t rec_bytes)
 {
     const int *first = c->kp_traj_first_host;
-    for (int i = 0; i < count;) {
-        int j = i;
-        while (j + 1 < count && traj[j + 1] == traj[j] + 1) j++;
-        const size_t e0 = (size_t)first[traj[i]], bytes = ((size_t)first[traj[j] + 1] - e0) * rec_bytes;
+    return kp_for_each_run(count, traj, [&](int, int b0, int run) -> int {
+        const size_t e0 = (size_t)first[b0], bytes = ((size_t)first[b0 + run] - e0) * rec_bytes;
         if (bytes) KP_HIP(c, hipMemcpyAsync(dst + e0 * rec_bytes, src, bytes, hipMemcpyHostToDevice, c->stream));
         src += bytes;
-        i = j + 1;
-    }
-    return KPILQR_OK;
+        return KPILQR_OK;
+    });
 }
 
 int kpilqr_upload_fd_kp_partial(kpilqr_ctx *c, int count, const int *traj, const void *slab, int entries, double eps)
 {
-    if (!c || count < 0 || entries < 0 || (count > 0 && !traj) || (entries > 0 && !slab)) return KPILQR_ERR_ARG;
-    KP_ENTER(c);
+    if (entries < 0 || (entries > 0 && !slab)) return KPILQR_ERR_ARG;
+    { const int go = enter_subset(c, "kpilqr_upload_fd_kp_partial", count, traj, Subset::pending); if (go <= 0) return go; }
     if (count == 0 && entries == 0 && !c->n_pending) return KPILQR_OK;
     int rc = check_partial(c, "kpilqr_upload_fd_kp_partial", FdPayload::kp_ordered, count, traj, entries);
     if (rc) return rc;
@@ -1171,23 +1191,21 @@ int kpilqr_upload_fd_kp_partial(kpilqr_ctx *c, int count, const int *traj, const
     rc = upload_runs(c, count, traj, (const char *)slab, c->fdk_dev, c->fdk_stride());
     if (rc) return rc;
     payload_changed(c);                                  // complete again; whatever was derived from the old one is stale
-    if (!is_pinned(slab)) KP_HIP(c, hipStreamSynchronize(c->stream));
-    return KPILQR_OK;
+    return wait_unless_pinned(c, slab);
 }
 
 int kpilqr_upload_kp_columns_partial(kpilqr_ctx *c, int count, const int *traj, const double *columns, int entries)
 {
-    if (!c || count < 0 || entries < 0 || (count > 0 && !traj) || (entries > 0 && !columns)) return KPILQR_ERR_ARG;
-    KP_ENTER(c);
+    if (entries < 0 || (entries > 0 && !columns)) return KPILQR_ERR_ARG;
+    { const int go = enter_subset(c, "kpilqr_upload_kp_columns_partial", count, traj, Subset::pending); if (go <= 0) return go; }
     if (count == 0 && entries == 0 && !c->n_pending) return KPILQR_OK;
     int rc = check_partial(c, "kpilqr_upload_kp_columns_partial", FdPayload::kp_columns, count, traj, entries);
     if (rc) return rc;
     rc = upload_runs(c, count, traj, (const char *)columns, (char *)c->kpc.p, (size_t)3 * c->n * 8);
     if (rc) return rc;
     payload_changed(c);
-    c->kpc_valid = true;                                 // (the columns ARE the payload)
-    if (!is_pinned(columns)) KP_HIP(c, hipStreamSynchronize(c->stream));
-    return KPILQR_OK;
+    c->pay.kpc_valid = true;                                 // (the columns ARE the payload)
+    return wait_unless_pinned(c, columns);
 }
 
 int kpilqr_fd_difference(kpilqr_ctx *c)
@@ -1199,12 +1217,9 @@ int kpilqr_fd_difference(kpilqr_ctx *c)
         // the sweeps read the key-point column store; the records, if something has asked for them, follow
         int rc = difference_to_kpc(c, !union_route(c));
         if (rc) return rc;
-        if (c->have_rec) { rc = records_from_payload(c); if (rc) return rc; c->rec_synced = true; }
-        return KPILQR_OK;
+        return c->have_rec ? records_from_payload(c) : KPILQR_OK;
     }
-    const int rc = records_from_payload(c);
-    if (rc == KPILQR_OK) c->rec_synced = true;
-    return rc;
+    return records_from_payload(c);
 }
 
 int kpilqr_interpolate(kpilqr_ctx *c)
@@ -1232,13 +1247,8 @@ int kpilqr_fd_interpolate(kpilqr_ctx *c)
         if (rc) return rc;
         rc = ensure_record_storage(c);
         if (rc) return rc;
-        rc = linearise(c);
-        if (rc == KPILQR_OK) c->rec_synced = true;
-        return rc;
     }
-    const int rc = linearise(c);
-    if (rc == KPILQR_OK) c->rec_synced = true;
-    return rc;
+    return linearise(c);
 }
 
 // Optimiser::FilterDynamicsMatrices (Optimiser.cpp:340-406) on the materialised A sequence
@@ -1351,18 +1361,18 @@ static int run_backward(kpilqr_ctx *c, int pd_stride)
         // itself and leaves kpc behind for the forward sweep -- no differencing kernel.  (It may stop at a failed PD check, so it
         // never marks kpc valid: another backward pass on the same payload differences again.)  Otherwise the payload is
         // differenced into kpc first, once, and the sweeps read kpc.
-        const FusedLaunch plan = c->last_bwd = plan_backward_fused(c, !c->kpc_valid && c->fd_payload == FdPayload::kp_ordered && c->tune.fused_raw != 0);
+        const FusedLaunch plan = c->last_bwd = plan_backward_fused(c, !c->pay.kpc_valid && c->fd_payload == FdPayload::kp_ordered && c->tune.fused_raw != 0);
         if (!plan.rxc) { rc = ensure_rx_buffer(c); if (rc) return rc; }       // (the sweep streams r_x: a constant one needs its broadcast copy)
         if (plan.raw) {
             KP_HIP(c, launch_backward_fused(c, plan, pd_stride));
-            c->kpc_touched = true;
+            c->pay.kpc_touched = true;
             // (KPILQR_FUSED_UNI=0, diagnostic: the GENERAL raw sweep has differenced every set inside the sweep -- dividing at its
             // crossings -- and left the columns; the forward sweep's general form walks the slope store, made from them here)
             if (c->kps && !plan.slopes) KP_HIP(c, launch_kp_slopes(c, false));
             return KPILQR_OK;
         }
-        if (!c->kpc_valid) { rc = difference_to_kpc(c); if (rc) return rc; }
-        if (c->kpc_valid) { rc = slopes_for_kpc(c); if (rc) return rc; }
+        if (!c->pay.kpc_valid) { rc = difference_to_kpc(c); if (rc) return rc; }
+        if (c->pay.kpc_valid) { rc = slopes_for_kpc(c); if (rc) return rc; }
         KP_HIP(c, launch_backward_fused(c, plan, pd_stride));
         return KPILQR_OK;
     }
@@ -1406,12 +1416,12 @@ int kpilqr_backward_stats(kpilqr_ctx *c, int pd_check_stride, int *hist)
     if (rc) return rc;
     rc = ensure_kpc(c);
     if (rc) return rc;
-    if (!c->kpc_valid) { rc = difference_to_kpc(c); if (rc) return rc; }
+    if (!c->pay.kpc_valid) { rc = difference_to_kpc(c); if (rc) return rc; }
     // (the instrumented sweep is the GENERAL form whatever the lists are: it walks the slope store, made here unconditionally)
     rc = ensure_kps(c, true);
     if (rc) return rc;
-    KP_HIP(c, launch_kp_slopes(c, false));
-    c->kps_valid = true;
+    rc = slopes_for_kpc(c, true);
+    if (rc) return rc;
     rc = ensure_rx_buffer(c);
     if (rc) return rc;
     const size_t bytes = (size_t)c->d.batch * 6 * sizeof(int);
@@ -1435,19 +1445,13 @@ int kpilqr_download_gains(kpilqr_ctx *c, double *K, double *k)
 // the gains of the listed trajectories, compact: one copy per array and run of adjacent trajectories
 int kpilqr_download_gains_partial(kpilqr_ctx *c, int count, const int *traj, double *K, double *k)
 {
-    if (!c || count < 0 || (count > 0 && !traj)) return KPILQR_ERR_ARG;
-    KP_ENTER(c);
-    if (!kp_traj_list_ok(c->d.batch, count, traj)) return set_err(c, KPILQR_ERR_ARG, "kpilqr_download_gains_partial: traj must be strictly increasing and within [0, batch)");
+    { const int go = enter_subset(c, "kpilqr_download_gains_partial", count, traj, Subset::listed_or_view); if (go <= 0) return go; }
     const size_t perK = (size_t)c->d.T * c->n * c->d.m, perk = (size_t)c->d.T * c->d.m;
-    for (int i = 0; i < count;) {
-        int j = i;
-        while (j + 1 < count && traj[j + 1] == traj[j] + 1) j++;
-        const size_t run = (size_t)(j - i + 1), b0 = (size_t)traj[i];
-        if (K) KP_HIP(c, hipMemcpyAsync(K + (size_t)i * perK, c->K + b0 * perK, run * perK * 8, hipMemcpyDeviceToHost, c->stream));
-        if (k) KP_HIP(c, hipMemcpyAsync(k + (size_t)i * perk, c->k + b0 * perk, run * perk * 8, hipMemcpyDeviceToHost, c->stream));
-        i = j + 1;
-    }
-    return KPILQR_OK;
+    return kp_for_each_run(count, traj, [&](int i, int b0, int run) -> int {
+        if (K) KP_HIP(c, hipMemcpyAsync(K + (size_t)i * perK, c->K + (size_t)b0 * perK, (size_t)run * perK * 8, hipMemcpyDeviceToHost, c->stream));
+        if (k) KP_HIP(c, hipMemcpyAsync(k + (size_t)i * perk, c->k + (size_t)b0 * perk, (size_t)run * perk * 8, hipMemcpyDeviceToHost, c->stream));
+        return KPILQR_OK;
+    });
 }
 
 // iLQR_SVR::LeastImportantDofs, summing branch (iLQR_SVR.cpp:952-968), over the gains of the last backward pass
@@ -1490,33 +1494,19 @@ int kpilqr_upload_nominal(kpilqr_ctx *c, const double *u_nom, const double *ctrl
 }
 
 // ---- partial re-linearisation, the rest: residuals, nominal controls and step records of SOME trajectories ------------------------
-// The checks every call of the family makes before anything is enqueued or changed (kpilqr_update_keypoints' contract)
-static int check_traj_list(kpilqr_ctx *c, const char *who, int count, const int *traj)
-{
-    if (c->is_view) return set_err(c, KPILQR_ERR_STATE, std::string(who) + ": not through a view of a trajectory range");
-    if (!kp_traj_list_ok(c->d.batch, count, traj)) return set_err(c, KPILQR_ERR_ARG, std::string(who) + ": traj must be strictly increasing and within [0, batch)");
-    return KPILQR_OK;
-}
-
 // `per` doubles per trajectory, compact on the host in traj order: one copy per run of adjacent trajectories, straight to their place
 static int upload_rows(kpilqr_ctx *c, int count, const int *traj, const double *src, double *dst, size_t per)
 {
-    for (int i = 0; i < count;) {
-        int j = i;
-        while (j + 1 < count && traj[j + 1] == traj[j] + 1) j++;
-        KP_HIP(c, hipMemcpyAsync(dst + (size_t)traj[i] * per, src + (size_t)i * per, (size_t)(j - i + 1) * per * 8, hipMemcpyHostToDevice, c->stream));
-        i = j + 1;
-    }
-    return KPILQR_OK;
+    return kp_for_each_run(count, traj, [&](int i, int b0, int run) -> int {
+        KP_HIP(c, hipMemcpyAsync(dst + (size_t)b0 * per, src + (size_t)i * per, (size_t)run * per * 8, hipMemcpyHostToDevice, c->stream));
+        return KPILQR_OK;
+    });
 }
 
 int kpilqr_upload_residuals_partial(kpilqr_ctx *c, int count, const int *traj, const double *r, const double *r_x, const double *r_u)
 {
-    if (!c || count < 0 || (count > 0 && !traj)) return KPILQR_ERR_ARG;
-    KP_ENTER(c);
-    if (count == 0) return KPILQR_OK;
-    int rc = check_traj_list(c, "kpilqr_upload_residuals_partial", count, traj);
-    if (rc) return rc;
+    int rc = enter_subset(c, "kpilqr_upload_residuals_partial", count, traj);
+    if (rc <= 0) return rc;
     // rows of a subset need every other row of the buffer to mean something, and must not flip the form the sweeps run in
     if (r_x && c->rx_const_on)
         return set_err(c, KPILQR_ERR_STATE, "kpilqr_upload_residuals_partial: the context holds constant residual Jacobians; a whole r_x through kpilqr_upload_residuals ends that mode first");
@@ -1533,11 +1523,8 @@ int kpilqr_upload_residuals_partial(kpilqr_ctx *c, int count, const int *traj, c
 
 int kpilqr_upload_nominal_partial(kpilqr_ctx *c, int count, const int *traj, const double *u_nom)
 {
-    if (!c || count < 0 || (count > 0 && !traj)) return KPILQR_ERR_ARG;
-    KP_ENTER(c);
-    if (count == 0) return KPILQR_OK;
-    const int rc = check_traj_list(c, "kpilqr_upload_nominal_partial", count, traj);
-    if (rc) return rc;
+    const int go = enter_subset(c, "kpilqr_upload_nominal_partial", count, traj);
+    if (go <= 0) return go;
     return u_nom ? upload_rows(c, count, traj, u_nom, c->u_nom, (size_t)c->d.T * c->d.m) : KPILQR_OK;
 }
 
@@ -1551,29 +1538,18 @@ static int kpc_to_records_of(kpilqr_ctx *c, int count, const int *traj)
         if (rc) return rc;
         if (!remember_traj_first(c, c->kp_offsets_host)) return set_err(c, KPILQR_ERR_ALLOC, "host allocation failed");
     }
-    const int first = c->fdk_first, entries = c->fdk_entries;
-    hipError_t e = hipSuccess;
-    for (int i = 0; i < count && e == hipSuccess;) {
-        int j = i;
-        while (j + 1 < count && traj[j + 1] == traj[j] + 1) j++;
-        c->fdk_first = c->kp_traj_first_host[traj[i]];
-        c->fdk_entries = c->kp_traj_first_host[traj[j] + 1] - c->fdk_first;
-        e = launch_kpc_to_records(c);
-        i = j + 1;
-    }
-    c->fdk_first = first; c->fdk_entries = entries;
-    KP_HIP(c, e);
-    return KPILQR_OK;
+    const int *first = c->kp_traj_first_host;
+    return kp_for_each_run(count, traj, [&](int, int b0, int run) -> int {
+        KP_HIP(c, launch_kpc_to_records(c, first[b0], first[b0 + run] - first[b0]));
+        return KPILQR_OK;
+    });
 }
 
 // kpilqr_fd_interpolate for the listed trajectories: [A|B] of their records from the resident payload, nobody else's records written
 int kpilqr_fd_interpolate_partial(kpilqr_ctx *c, int count, const int *traj)
 {
-    if (!c || count < 0 || (count > 0 && !traj)) return KPILQR_ERR_ARG;
-    KP_ENTER(c);
-    if (count == 0) return KPILQR_OK;
-    int rc = check_traj_list(c, "kpilqr_fd_interpolate_partial", count, traj);
-    if (rc) return rc;
+    int rc = enter_subset(c, "kpilqr_fd_interpolate_partial", count, traj);
+    if (rc <= 0) return rc;
     if (c->fused) return set_err(c, KPILQR_ERR_STATE, "kpilqr_fd_interpolate_partial: a KPILQR_FLAG_FUSED context holds no persistent step records (its sweeps read the column store): kpilqr_fd_difference");
     if (!c->have_kp) return set_err(c, KPILQR_ERR_STATE, "kpilqr_fd_interpolate_partial before kpilqr_set_keypoints");
     rc = check_complete(c, "kpilqr_fd_interpolate_partial");
@@ -1589,7 +1565,7 @@ int kpilqr_fd_interpolate_partial(kpilqr_ctx *c, int count, const int *traj)
         // hold); a payload by entry under KPILQR_FD_INTERP=0: columns -> the listed trajectories' key-point steps; then k_interpolate
         if (c->fd_payload == FdPayload::jobs) KP_HIP(c, launch_fd_difference(c));
         else if (payload_by_entry(c)) {
-            if (!c->kpc_valid) { rc = difference_to_kpc(c); if (rc) return rc; }
+            if (!c->pay.kpc_valid) { rc = difference_to_kpc(c); if (rc) return rc; }
             rc = ensure_entry_tables(c);
             if (rc) return rc;
             rc = kpc_to_records_of(c, count, traj);
@@ -1598,25 +1574,20 @@ int kpilqr_fd_interpolate_partial(kpilqr_ctx *c, int count, const int *traj)
         KP_HIP(c, launch_interpolate(c, c->traj_list, count));
         c->last_linearise = "fd_difference+interpolate:subset";
     }
-    if (!is_pinned(traj)) KP_HIP(c, hipStreamSynchronize(c->stream));      // (the copy of a pageable list is complete before the caller has it back)
-    return KPILQR_OK;
+    return wait_unless_pinned(c, traj);
 }
 
 // kpilqr_cost_derivs for the listed trajectories
 int kpilqr_cost_derivs_partial(kpilqr_ctx *c, int count, const int *traj)
 {
-    if (!c || count < 0 || (count > 0 && !traj)) return KPILQR_ERR_ARG;
-    KP_ENTER(c);
-    if (count == 0) return KPILQR_OK;
-    int rc = check_traj_list(c, "kpilqr_cost_derivs_partial", count, traj);
-    if (rc) return rc;
+    int rc = enter_subset(c, "kpilqr_cost_derivs_partial", count, traj);
+    if (rc <= 0) return rc;
     if (c->fused) return set_err(c, KPILQR_ERR_STATE, "kpilqr_cost_derivs_partial: a KPILQR_FLAG_FUSED context holds no persistent step records (its sweeps form the cost derivatives themselves)");
     rc = ensure_rx_buffer(c);
     if (rc) return rc;
     KP_HIP(c, hipMemcpyAsync(c->traj_list, traj, (size_t)count * sizeof(int), hipMemcpyHostToDevice, c->stream));
     KP_HIP(c, launch_cost_derivs(c, c->traj_list, count));
-    if (!is_pinned(traj)) KP_HIP(c, hipStreamSynchronize(c->stream));
-    return KPILQR_OK;
+    return wait_unless_pinned(c, traj);
 }
 
 // ---- K as FP32: half the bytes of the largest per-iteration download ---------------------------------------------------------------
@@ -1634,14 +1605,14 @@ static int download_gains_f32(kpilqr_ctx *c, int count, const int *traj, float *
         KP_HIP(c, hipMemcpyAsync(K32, c->K32, (size_t)count * perK * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     }
     if (k && !traj) KP_HIP(c, hipMemcpyAsync(k, c->k, (size_t)count * perk * 8, hipMemcpyDeviceToHost, c->stream));
-    for (int i = 0; k && traj && i < count;) {
-        int j = i;
-        while (j + 1 < count && traj[j + 1] == traj[j] + 1) j++;
-        KP_HIP(c, hipMemcpyAsync(k + (size_t)i * perk, c->k + (size_t)traj[i] * perk, (size_t)(j - i + 1) * perk * 8, hipMemcpyDeviceToHost, c->stream));
-        i = j + 1;
+    if (k && traj) {
+        const int rc = kp_for_each_run(count, traj, [&](int i, int b0, int run) -> int {
+            KP_HIP(c, hipMemcpyAsync(k + (size_t)i * perk, c->k + (size_t)b0 * perk, (size_t)run * perk * 8, hipMemcpyDeviceToHost, c->stream));
+            return KPILQR_OK;
+        });
+        if (rc) return rc;
     }
-    if (K32 && traj && !is_pinned(traj)) KP_HIP(c, hipStreamSynchronize(c->stream));      // (the copy of a pageable list is complete before the caller has it back)
-    return KPILQR_OK;
+    return K32 ? wait_unless_pinned(c, traj) : KPILQR_OK;      // (traj was copied to the device for the rounding launch; nullptr counts as pinned)
 }
 
 int kpilqr_download_gains_f32(kpilqr_ctx *c, float *K32, double *k)
@@ -1654,11 +1625,8 @@ int kpilqr_download_gains_f32(kpilqr_ctx *c, float *K32, double *k)
 
 int kpilqr_download_gains_f32_partial(kpilqr_ctx *c, int count, const int *traj, float *K32, double *k)
 {
-    if (!c || count < 0 || (count > 0 && !traj)) return KPILQR_ERR_ARG;
-    KP_ENTER(c);
-    if (count == 0) return KPILQR_OK;
-    const int rc = check_traj_list(c, "kpilqr_download_gains_f32_partial", count, traj);
-    if (rc) return rc;
+    const int go = enter_subset(c, "kpilqr_download_gains_f32_partial", count, traj);
+    if (go <= 0) return go;
     return download_gains_f32(c, count, traj, K32, k);
 }
 
@@ -1686,8 +1654,8 @@ static int run_forward(kpilqr_ctx *c, double *U_dev)
         const FusedLaunch plan = c->last_fwd = plan_forward_fused(c);
         if (!plan.rxc) { rc = ensure_rx_buffer(c); if (rc) return rc; }       // (as in run_backward)
         // kpc: differenced explicitly, or left behind by the raw backward sweep of this payload
-        if (!c->kpc_valid && !c->kpc_touched) { rc = difference_to_kpc(c); if (rc) return rc; }
-        if (c->kpc_valid) { rc = slopes_for_kpc(c); if (rc) return rc; }       // (behind a raw backward sweep: its launch sequence made them)
+        if (!c->pay.kpc_valid && !c->pay.kpc_touched) { rc = difference_to_kpc(c); if (rc) return rc; }
+        if (c->pay.kpc_valid) { rc = slopes_for_kpc(c); if (rc) return rc; }       // (behind a raw backward sweep: its launch sequence made them)
         KP_HIP(c, launch_forward_fused(c, plan, U_dev));
         return KPILQR_OK;
     }
@@ -1733,7 +1701,6 @@ int kpilqr_iterate(kpilqr_ctx *c, const double *lambda, int pd_check_stride, con
     if (alphas) KP_HIP(c, hipMemcpyAsync(c->alphas, alphas, (size_t)c->d.n_alpha * 8, hipMemcpyHostToDevice, c->stream));
     if (!c->fused) {              // the fused sweeps difference (or read kpc), interpolate A, B and form l_* themselves
         { const int rcl = linearise(c); if (rcl) return rcl; }
-        c->rec_synced = true;
         if (!c->tiled_a6) { const int rcx = ensure_rx_buffer(c); if (rcx) return rcx; KP_HIP(c, launch_cost_derivs(c)); }      // tiled + flag: l_* are formed inside the sweeps
     }
     else c->last_linearise = union_route(c) ? "kp_union" : "in_sweep";
@@ -1888,7 +1855,7 @@ int kpilqr_iterate_streamed(kpilqr_ctx *c, const kpilqr_stream_io *io, int pd_ch
     // No new payload, but the column store of the resident one is stale (key-points changed since a job-list upload): a chunk
     // view has no jobs (its njobs is 0), so the payload is re-differenced HERE, on the context, for the whole batch -- what
     // kpilqr_iterate would do.  (A key-point ordered payload is dropped by new key-points; the chunks handle a resident one.)
-    if (c->fused && !new_payload && !c->kpc_valid && c->fd_payload == FdPayload::jobs) {
+    if (c->fused && !new_payload && !c->pay.kpc_valid && c->fd_payload == FdPayload::jobs) {
         rc = difference_to_kpc(c); if (rc) return rc;
     }
     // The same on a context with records: without a new payload a chunk runs k_interpolate alone, between the key-point columns its
@@ -1896,10 +1863,9 @@ int kpilqr_iterate_streamed(kpilqr_ctx *c, const kpilqr_stream_io *io, int pd_ch
     // by an ordinary call (kpilqr_upload_fd_kp, a partial upload behind kpilqr_update_keypoints ...) and not linearised yet is
     // written into the records HERE, for the whole batch, behind the chunks of any earlier iteration (rec_synced is cleared by
     // payload_changed, so this is the first sweep since that upload: the join costs an overlap nobody had).
-    if (!c->fused && !new_payload && !c->rec_synced) {
+    if (!c->fused && !new_payload && !c->pay.rec_synced) {
         rc = join_pipeline(c); if (rc) return rc;
         rc = records_from_payload(c); if (rc) return rc;
-        c->rec_synced = true;
     }
     // Per-step Jacobians in this call end the constant mode -- recorded only HERE, behind every check that can still reject the
     // call (a rejected call must leave the context as it was: round-4 advisor; before, a call refused for an unpinned buffer had
@@ -1915,7 +1881,10 @@ int kpilqr_iterate_streamed(kpilqr_ctx *c, const kpilqr_stream_io *io, int pd_ch
     // later kpilqr_sync / kpilqr_destroy waits for the DMAs that read the caller's buffers
     c->pipe_dirty = true;
 
-    bool vflags_valid = c->kpc_valid, vflags_touched = c->kpc_touched, vflags_slopes = c->kps_valid;
+    // What the chunks do to the payload-derived state comes back from the LAST view, whole (every chunk does the same to its slice
+    // of kpc, kps and the records; a view never takes the union route, so kpcu_valid returns as it left).  Nothing of ListsDerived
+    // comes back: a view builds no table -- the context ensured them above.
+    PayloadDerived after = c->pay;
     for (int ch = 0; ch < nchunks; ch++) {
         const int b0 = (int)((long long)B * ch / nchunks), b1 = (int)((long long)B * (ch + 1) / nchunks), nb = b1 - b0;
         if (nb <= 0) continue;
@@ -1923,6 +1892,7 @@ int kpilqr_iterate_streamed(kpilqr_ctx *c, const kpilqr_stream_io *io, int pd_ch
         KP_HIP(c, hipStreamWaitEvent(s, c->pipe_in, 0));
         kpilqr_ctx v;
         make_view(c, b0, nb, s, &v);
+        const auto of_view = [&](int rcv) { if (rcv) c->err = v.err; return rcv; };      // a view's refusal is the context's
         const size_t o = b0, cnt = nb;
         // ---- H2D of the chunk ------------------------------------------------------------------------------------
         if (slab) {
@@ -1955,7 +1925,7 @@ int kpilqr_iterate_streamed(kpilqr_ctx *c, const kpilqr_stream_io *io, int pd_ch
             const size_t E = (size_t)(e1 - e0), eo = (size_t)e0 * 3 * n;
             if (E) KP_HIP(c, h2d(c->kpc + eo, kcols + eo, E * 3 * n * 8, s));
             v.njobs = 0; v.fdk_first = e0; v.fdk_entries = (int)E;
-            v.kpc_valid = true;
+            v.pay.kpc_valid = true;
         } else {
             // no new FD payload: what was differenced before is reused (kpc / the records' key-point columns)
             v.njobs = 0;
@@ -1971,16 +1941,16 @@ int kpilqr_iterate_streamed(kpilqr_ctx *c, const kpilqr_stream_io *io, int pd_ch
         // ---- kernels of the chunk --------------------------------------------------------------------------------
         if (!c->fused) {
             // (no new payload: the records hold its key-point columns already)
-            rc = linearise(&v, new_payload);
-            if (rc) { c->err = v.err; return rc; }
+            rc = of_view(linearise(&v, new_payload));
+            if (rc) return rc;
             c->last_linearise = v.last_linearise;
             if (!c->tiled_a6) KP_HIP(c, launch_cost_derivs(&v));
         }
-        rc = run_backward(&v, pd_check_stride);
-        if (rc) { c->err = v.err; return rc; }
-        rc = run_forward(&v, nullptr);
-        if (rc) { c->err = v.err; return rc; }
-        vflags_valid = v.kpc_valid; vflags_touched = v.kpc_touched; vflags_slopes = v.kps_valid;
+        rc = of_view(run_backward(&v, pd_check_stride));
+        if (rc) return rc;
+        rc = of_view(run_forward(&v, nullptr));
+        if (rc) return rc;
+        after = v.pay;
         c->last_bwd = v.last_bwd; c->last_fwd = v.last_fwd;
         // ---- D2H of the chunk ------------------------------------------------------------------------------------
         // K, k by a copy kernel: it overlaps with the SDMA uploads of the next chunks (two SDMA directions do not)
@@ -1995,8 +1965,7 @@ int kpilqr_iterate_streamed(kpilqr_ctx *c, const kpilqr_stream_io *io, int pd_ch
         if (io->delta_J) KP_HIP(c, hipMemcpyAsync(io->delta_J + o, v.delta_J, cnt * 8, hipMemcpyDeviceToHost, s));
         if (io->status) KP_HIP(c, hipMemcpyAsync(io->status + o, v.status, cnt * 4, hipMemcpyDeviceToHost, s));
     }
-    c->kpc_valid = vflags_valid; c->kpc_touched = vflags_touched; c->kps_valid = vflags_slopes;      // what every chunk did to its slice of kpc
-    if (!c->fused && new_payload) c->rec_synced = true;      // every chunk has linearised its trajectories from the new payload
+    c->pay = after;
     return KPILQR_OK;
 }
 
