@@ -53,7 +53,9 @@
  *   KPILQR_TILED_NT_MIN     run the tiled kernels with at least this many tiles (test coverage of a tile count on a
  *                           small state).
  *   KPILQR_PIPE_COPY        kpilqr_iterate_streamed: bit 0 uploads / bit 1 downloads by copy kernels instead of SDMA
- *                           (default 2).
+ *                           (default 2).  Bit 1 does not reach the K32 and gain_traj downloads of kpilqr_iterate_streamed2:
+ *                           they always leave through the gather kernel (a converted or gathered download through SDMA would
+ *                           need the staging buffer that call avoids).
  * The host-side thread count of the FD pool is a constructor argument of the host classes, not an environment switch. */
 
 #ifdef __cplusplus
@@ -394,6 +396,49 @@ typedef struct {
 } kpilqr_stream_io;
 int  kpilqr_iterate_streamed(kpilqr_ctx *ctx, const kpilqr_stream_io *io, int pd_check_stride, int nchunks);
 
+/* kpilqr_iterate_streamed with two options for the gains it brings down: K as FP32, and the gains of a list of trajectories alone --
+ * what kpilqr_download_gains_f32 and kpilqr_download_gains_partial do for the explicit calls, inside the chunk pipeline.  The struct
+ * carries its own size, so later fields can be appended: struct_size must be sizeof(kpilqr_stream_io2) as the caller compiled it,
+ * else KPILQR_ERR_ARG.  `io` is the struct of kpilqr_iterate_streamed, every field with the meaning it has there; with K32 = NULL and
+ * gain_traj = NULL the call IS kpilqr_iterate_streamed (one implementation, the same copies and launches in the same order).
+ * The list.  gain_traj = NULL: K / K32 / k of the whole batch, as before.  Else gain_traj [gain_count], strictly increasing and within
+ * [0, batch) -- the contract of kpilqr_download_gains_partial -- and the outputs are COMPACT: K (or K32) [gain_count][T][n][m] and
+ * k [gain_count][T][m], the listed trajectories back to back in list order, and nothing beyond gain_count rows is written;
+ * gain_count = 0 with a list: no gains come down.  gain_traj is read during the call only and may be pageable (the library keeps a
+ * copy of its own).  The sweeps run over the whole batch regardless of the list, and cost_pred, delta_J and status stay whole-batch
+ * outputs.  K of a trajectory whose status is non-zero is copied as it is (undefined, see kpilqr_backward).
+ * K32.  out: K as FP32 in the layout of io.K; io.K and K32 are exclusive (io.K must then be NULL).  K32 must be pinned
+ * (kpilqr_host_alloc) and 8-byte aligned.  The values are those of kpilqr_download_gains_f32: the IEEE round-to-nearest-even cast of
+ * the resident FP64 K, bit for bit; FP32 subnormals are produced, not flushed; magnitudes above FLT_MAX become +-inf; NaN stays NaN.
+ * k stays FP64.  The resident FP64 K is only read.
+ * Rejections, all KPILQR_ERR_ARG, all before anything is enqueued or the context is changed (a context in the constant-Jacobian mode
+ * stays in it): io2 = NULL; a wrong struct_size; io.K and K32 both given; K32 not pinned or not 8-byte aligned; gain_count < 0;
+ * gain_count > 0 with gain_traj = NULL; a list that is not strictly increasing or leaves [0, batch).
+ * How.  Chunks are contiguous trajectory ranges and the list increases, so a chunk's share is one slice of the list and one contiguous
+ * range of the compact outputs.  ONE launch per chunk and array of a gather kernel (k_gains_out, gains.hip; 32 workgroups, as the copy
+ * kernel of the FP64 route) reads the chunk's rows of the resident K / k, rounds K when K32 is asked for, and stores straight into the
+ * caller's pinned buffer, on the chunk's own stream: no staging buffer, no second DMA, and it overlaps the uploads of the next chunks
+ * as the FP64 copy kernel does.  A chunk without listed trajectories launches nothing for the gains.  K32 and the outputs of a list
+ * take this route whatever KPILQR_PIPE_COPY says (bit 1 chooses between SDMA and the copy kernel for the FP64 whole-batch downloads
+ * only).  The context keeps a device copy of the list (batch ints) and its mirror: consecutive calls overlap without a wait while
+ * the list equals the one in flight; a different list first orders the call behind the iteration in flight, as differing job
+ * offsets do.
+ * Bytes: Panda reaching, T = 3000: 2.52 MB of gains per trajectory become 1.34 MB with K32, and proportionally fewer with a list;
+ * uploads stay and share the link, so the rate gains less: measured once at B = 1024, three chunks, against the FP64 call in the same
+ * process, 1.10x with K32, 1.22x with K32 of a scattered half of the batch, 1.17x with FP64 K of that half (profiles/streamed_gains.txt).
+ * Out of scope: FP32 for k, for any upload or inside any sweep; uploads or sweeps of a subset inside the chunks;
+ * KPILQR_FLAG_UNION_KEYPOINTS inside the chunks.  KPILQR_VERSION is unchanged: detect the call by its symbol. */
+typedef struct {
+    size_t struct_size;                         /* sizeof(kpilqr_stream_io2) as the caller compiled it                   */
+    kpilqr_stream_io io;                        /* every field with the meaning it has for kpilqr_iterate_streamed       */
+    float *K32;                                 /* out: K as FP32, layout of io.K; io.K must then be NULL                */
+    int gain_count;                             /* with gain_traj: number of listed trajectories (0: no gains come down) */
+    const int *gain_traj;                       /* NULL: K / K32 / k of the whole batch.  Else [gain_count], strictly increasing,
+                                                   within [0, batch): K (or K32) [gain_count][T][n][m] and k [gain_count][T][m]
+                                                   COMPACT, in list order                                                 */
+} kpilqr_stream_io2;
+int  kpilqr_iterate_streamed2(kpilqr_ctx *ctx, const kpilqr_stream_io2 *io2, int pd_check_stride, int nchunks);
+
 /* Differencing tail of Differentiator::DynamicsDerivatives (:166-222,286-321,386-423,441-457):
  * writes the key-point columns of A and B. */
 int  kpilqr_fd_difference(kpilqr_ctx *ctx);
@@ -494,7 +539,8 @@ int  kpilqr_download_gains(kpilqr_ctx *ctx, double *K, double *k);
  * Memory cost: the float buffer, count*T*n*m*4 bytes of device memory owned by the context, reserved on demand and kept at the
  * largest size asked for (whole batch: half the size of K; KPILQR_ERR_ALLOC when it cannot be had).
  * Out of scope: kpilqr_iterate_streamed (kpilqr_stream_io is a fixed struct of this ABI version: its K stays FP64); FP32 for k, for
- * any upload, or inside any sweep; an environment switch.  KPILQR_VERSION is unchanged: detect the calls by their symbols. */
+ * any upload, or inside any sweep; an environment switch.  KPILQR_VERSION is unchanged: detect the calls by their symbols.
+ * (The chunk pipeline has a call of its own that brings K down as FP32: kpilqr_iterate_streamed2, with a struct that can grow.) */
 int  kpilqr_download_gains_f32(kpilqr_ctx *ctx, float *K32 /* [batch][T][n][m] */, double *k /* [batch][T][m] */);
 int  kpilqr_download_gains_f32_partial(kpilqr_ctx *ctx, int count, const int *traj,
                                        float *K32 /* [count][T][n][m] */, double *k /* [count][T][m] */);

@@ -8,6 +8,14 @@ Forms: "serial"  = kpilqr_upload_fd + kpilqr_upload_residuals + kpilqr_iterate +
        "chunks=N" = kpilqr_iterate_streamed over N trajectory chunks (H2D | kernels | D2H overlapped; the FD payload goes up
        key-point ordered, kpilqr_fd_kp_layout), one sync at the end
        of the timed loop ("pipelined") or after every iteration ("per-iteration sync").
+
+  python tools/pcie_inclusive.py gains [batch] [steps] [rounds]
+
+The gain downloads of the chunk pipeline (profiles/streamed_gains.txt): Panda reaching, T = 3000, constant residual Jacobian,
+key-point ordered payload, three chunks, pipelined; four legs alternating in one process --
+  1 FP64 K through kpilqr_iterate_streamed (the reference of every ratio)      2 K32, whole batch (kpilqr_iterate_streamed2)
+  3 K32 of a scattered half of the batch                                         4 FP64 K of the same half
+With KPILQR_LIB naming a library without kpilqr_iterate_streamed2 (a build of an earlier commit) leg 1 alone is timed.
 """
 import sys
 import time
@@ -131,7 +139,65 @@ def measure(B=256, steps=5, T=3000, task="panda_reaching", chunk_list=(4, 8, 16)
     return out
 
 
+def measure_gains(B=256, steps=10, rounds=3, T=3000, nchunks=3, quiet=False):
+    uniq = min(8, B)
+    p = synth.tile_problem(synth.make_problem(task="panda_reaching", T=T, batch=uniq, min_N=5), B // uniq)
+    B = p["batch"]
+    with Engine(p["dof"], p["m"], T, p["nr"], batch=B, fused=True) as e:
+        synth.upload(e, p, kp_ordered=True, rx_const=True)
+        e.iterate(p["lam"], 100, np.array([(i / 6.0) ** 2 for i in range(1, 7)])); e.sync()
+        K0, k0 = e.gains()
+        r = e.pinned(p["r"].shape); r[...] = p["r"]
+        lam = e.pinned(B); lam[:] = p["lam"]
+        slab = e.fd_kp_slab(*synth.kp_ordered_payload(p))
+        half = np.sort(np.random.default_rng(5).permutation(B)[:B // 2]).astype(np.int32)      # scattered: runs of every length
+        H = len(half)
+        K = e.pinned(K0.shape); k = e.pinned(k0.shape); K32 = e.pinned(K0.shape, np.float32)
+        Kh = e.pinned((H,) + K0.shape[1:]); kh = e.pinned((H,) + k0.shape[1:]); K32h = e.pinned((H,) + K0.shape[1:], np.float32)
+        legs = [("1 FP64 K, kpilqr_iterate_streamed", dict(K=K, k=k), K.nbytes + k.nbytes)]
+        if hasattr(e._L, "kpilqr_iterate_streamed2"):
+            legs += [("2 K32, whole batch", dict(K32=K32, k=k), K32.nbytes + k.nbytes),
+                     ("3 K32, scattered half listed", dict(K32=K32h, k=kh, gain_traj=half), K32h.nbytes + kh.nbytes),
+                     ("4 FP64 K, the same half listed", dict(K=Kh, k=kh, gain_traj=half), Kh.nbytes + kh.nbytes)]
+        up = slab["layout"].bytes + r.nbytes
+
+        def run(kw):
+            e.iterate_streamed(fd_kp=slab, eps=p["eps"], r=r, lam=lam, nchunks=nchunks, **kw)
+
+        for _, kw, _ in legs:
+            run(kw); run(kw)
+        e.sync()
+        # (the :rxc sweeps: K in the bits of the staged path, k to 1e-12 -- as in measure())
+        assert np.array_equal(K, K0) and np.max(np.abs(k - k0)) <= 1e-12 * np.max(np.abs(k0))
+        if len(legs) > 1:
+            with np.errstate(under="ignore"):
+                assert np.array_equal(K32, K0.astype(np.float32)) and np.array_equal(K32h, K0[half].astype(np.float32))
+            assert np.array_equal(Kh, K0[half]) and np.array_equal(kh, k[half])
+        times = [[] for _ in legs]
+        for _ in range(rounds):
+            for i, (_, kw, _) in enumerate(legs):
+                t0 = time.perf_counter()
+                for _ in range(steps):
+                    run(kw)
+                e.sync()
+                times[i].append((time.perf_counter() - t0) / steps)
+    rows = []
+    for (label, _, dn), ts in zip(legs, times):
+        dt = float(np.median(ts))
+        rows.append(dict(leg=label, ms_per_iteration=1e3 * dt, ms_rounds=[round(1e3 * t, 3) for t in ts], traj_it_per_s=B / dt,
+                         h2d_GB=up / 1e9, d2h_GB=dn / 1e9, link_GBps=(up + dn) / dt / 1e9, rate_vs_leg1=float(np.median(times[0])) / dt))
+    if not quiet:
+        for r_ in rows:
+            print(f"B={B} {r_['leg']:34s}: {r_['ms_per_iteration']:8.2f} ms (rounds {r_['ms_rounds']}) = {r_['traj_it_per_s']:9.1f} traj-it/s  x{r_['rate_vs_leg1']:.3f}"
+                  f"  (H2D {r_['h2d_GB']:.3f} GB + D2H {r_['d2h_GB']:.3f} GB -> {r_['link_GBps']:.1f} GB/s)", flush=True)
+    return dict(batch=B, T=T, steps=steps, rounds=rounds, nchunks=nchunks, rows=rows)
+
+
 if __name__ == "__main__":
+    if len(sys.argv) > 1 and sys.argv[1] == "gains":
+        a = [int(x) for x in sys.argv[2:]]
+        measure_gains(*a)
+        sys.exit(0)
     B = int(sys.argv[1]) if len(sys.argv) > 1 else 256
     steps = int(sys.argv[2]) if len(sys.argv) > 2 else 5
     chunks = tuple(int(x) for x in sys.argv[3].split(",")) if len(sys.argv) > 3 else (4, 8, 16)

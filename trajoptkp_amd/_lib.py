@@ -31,7 +31,7 @@ SYMBOLS = [
     "kpilqr_fd_interpolate", "kpilqr_get_union_keypoints", "kpilqr_get_union_columns",
     "kpilqr_update_keypoints", "kpilqr_upload_fd_kp_partial", "kpilqr_upload_kp_columns_partial", "kpilqr_download_gains_partial",
     "kpilqr_upload_residuals_partial", "kpilqr_upload_nominal_partial", "kpilqr_fd_interpolate_partial", "kpilqr_cost_derivs_partial",
-    "kpilqr_download_gains_f32", "kpilqr_download_gains_f32_partial",
+    "kpilqr_download_gains_f32", "kpilqr_download_gains_f32_partial", "kpilqr_iterate_streamed2",
 ]
 # entry points added without a version bump (include/kpilqr.h: "detect the entry point by its symbol"): bound only when the library
 # has them -- KPILQR_LIB may name an older build of the same major version
@@ -39,7 +39,7 @@ OPTIONAL_SYMBOLS = {"kpilqr_fd_interpolate", "kpilqr_get_union_keypoints", "kpil
                     "kpilqr_update_keypoints", "kpilqr_upload_fd_kp_partial", "kpilqr_upload_kp_columns_partial",
                     "kpilqr_download_gains_partial", "kpilqr_upload_residuals_partial", "kpilqr_upload_nominal_partial",
                     "kpilqr_fd_interpolate_partial", "kpilqr_cost_derivs_partial",
-                    "kpilqr_download_gains_f32", "kpilqr_download_gains_f32_partial"}
+                    "kpilqr_download_gains_f32", "kpilqr_download_gains_f32_partial", "kpilqr_iterate_streamed2"}
 
 
 class Dims(C.Structure):
@@ -62,6 +62,11 @@ class StreamIO(C.Structure):
                 ("r", C.c_void_p), ("r_x", C.c_void_p), ("r_u", C.c_void_p), ("u_nom", C.c_void_p), ("lam", C.c_void_p),
                 ("K", C.c_void_p), ("k", C.c_void_p), ("cost_pred", C.c_void_p), ("delta_J", C.c_void_p),
                 ("status", C.c_void_p), ("fd_kp_slab", C.c_void_p), ("entries", C.c_int), ("kp_columns", C.c_void_p)]
+
+
+class StreamIO2(C.Structure):
+    """kpilqr_stream_io2: StreamIO with K as FP32 and the gains of a list of trajectories; struct_size = sizeof(StreamIO2)"""
+    _fields_ = [("struct_size", C.c_size_t), ("io", StreamIO), ("K32", C.c_void_p), ("gain_count", C.c_int), ("gain_traj", C.c_void_p)]
 
 
 ABI_MAJOR = 4                  # KPILQR_VERSION / 100 of the include/kpilqr.h this binding mirrors
@@ -167,6 +172,8 @@ def load():
     if hasattr(L, "kpilqr_download_gains_f32"):
         L.kpilqr_download_gains_f32.argtypes = [vp, vp, vp]
         L.kpilqr_download_gains_f32_partial.argtypes = [vp, C.c_int, vp, vp, vp]
+    if hasattr(L, "kpilqr_iterate_streamed2"):
+        L.kpilqr_iterate_streamed2.argtypes = [vp, C.POINTER(StreamIO2), C.c_int, C.c_int]
     for s in SYMBOLS:
         if s in OPTIONAL_SYMBOLS and not hasattr(L, s):
             continue

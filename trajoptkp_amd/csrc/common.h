@@ -242,6 +242,14 @@ struct Ctx {
     bool pipe_ready = false, pipe_dirty = false;
     int pipe_chunks = 0;
     unsigned long long pipe_sig = 0;       // hash of (njobs, nnom, traj_job_first, traj_nom_first) of the streamed iteration in flight
+    // kpilqr_iterate_streamed2 with gain_traj: the list the chunks' gather launches read (gains.hip).  A device copy of its own -- not
+    // traj_list, which the partial calls overwrite on the context's stream while chunks may still be reading -- and its pinned host
+    // mirror: a call whose list equals the mirror uploads nothing and overlaps with the iteration in flight; a different list joins
+    // the pipeline first (the rule of pipe_sig), and pipe_list_up says when the mirror may be overwritten (its upload has left it)
+    DevBuf<int> pipe_list;                 // [batch], reserved by the first call that carries a list
+    int *pipe_list_host = nullptr;         // [batch], pinned
+    int pipe_list_count = -1;              // entries of the list pipe_list holds; -1: none yet
+    hipEvent_t pipe_list_up = nullptr;
 
     // staging for debug hooks / U_alpha
     DevBuf<double> stage;
@@ -252,7 +260,7 @@ struct Ctx {
     {
         DevMem *const all[] = {&rec, &kp_uniform, &K, &k, &r, &r_x, &r_u, &w_run, &w_term, &u_nom, &ctrl_lim, &lambda, &alphas, &cost_pred,
                                &delta_J, &traj_cost, &status, &traj_list, &K32, &segmap, &segent, &kp_offsets, &kp_times, &rx_const, &kpc, &kps, &kp_entry,
-                               &kp_entry_list, &fdk_dev, &kpu_offsets, &kpu_times, &kpu_src, &kpu_traj_first, &kpcu, &kpu_uniform, &fdk_alt, &kpc_alt, &kp_times_alt, &kp_upl_times, &kp_move, &X_states, &kp_thr, &kp_mask, &kp_count, &ls8, &fd_dev, &err_flag, &stage};
+                               &kp_entry_list, &fdk_dev, &kpu_offsets, &kpu_times, &kpu_src, &kpu_traj_first, &kpcu, &kpu_uniform, &fdk_alt, &kpc_alt, &kp_times_alt, &kp_upl_times, &kp_move, &X_states, &kp_thr, &kp_mask, &kp_count, &ls8, &fd_dev, &err_flag, &stage, &pipe_list};
         for (DevMem *b : all) f(*b);
     }
 
@@ -315,6 +323,11 @@ hipError_t launch_merge_kp_times(Ctx *c, int longest_entries, const int *first_o
                                  const int *old_times, const int *upl_times, int *times);
 // gains.hip: K of `count` trajectories (traj: their indices on the device; nullptr: trajectories 0 .. count-1) -> out [count][T][n][m], FP32
 hipError_t launch_gains_f32(Ctx *c, const int *traj, int count, float *out);
+// gains.hip, the chunks of kpilqr_iterate_streamed2: rows of the resident K or k gathered and stored straight into mapped pinned host
+// memory on stream s.  Row i of `count` is trajectory traj[i] (device; nullptr: first + i) of the CONTEXT's buffers (c is never a view);
+// dst [count][row] compact.  K_f32: K rounded to FP32 | K_f64, k_f64: as they are
+enum class GainsForm : int { K_f32, K_f64, k_f64 };
+hipError_t launch_gains_out(const Ctx *c, hipStream_t s, GainsForm form, const int *traj, int first, int count, void *dst_host);
 // comm.cpp (RCCL opened lazily) and the pack kernel of elementwise.hip
 const char *comm_unique_id(char *id128);
 const char *comm_init(Ctx *c, int nranks, int rank, const char *id128);

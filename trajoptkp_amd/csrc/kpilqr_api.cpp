@@ -662,6 +662,8 @@ void kpilqr_destroy(kpilqr_ctx *c)
     comm_destroy(c);
     c->for_each_buffer([](DevMem &b) { (void)release(b); });
     if (c->err_flag_host) (void)hipHostFree(c->err_flag_host);
+    if (c->pipe_list_host) (void)hipHostFree(c->pipe_list_host);
+    if (c->pipe_list_up) (void)hipEventDestroy(c->pipe_list_up);
     forget_lists(c);
     if (c->kpu_traj_first_host) free(c->kpu_traj_first_host);
     if (c->own_stream) (void)hipStreamDestroy(c->stream);
@@ -1742,9 +1744,40 @@ static void make_view(const kpilqr_ctx *c, int b0, int nb, hipStream_t s, kpilqr
     v->n_simd = share < 4 ? 4 : (int)share;
 }
 
-int kpilqr_iterate_streamed(kpilqr_ctx *c, const kpilqr_stream_io *io, int pd_check_stride, int nchunks)
+// What kpilqr_iterate_streamed2 adds to a streamed iteration: K as FP32, and the gains of a list of trajectories alone.
+// kpilqr_iterate_streamed is the same walk with neither (K32 == nullptr, !listed): it enqueues what it always has.
+struct StreamGains {
+    float *K32 = nullptr;          // K rounded to FP32 instead of io->K
+    bool listed = false;           // traj [count] (strictly increasing, within [0, batch)): K / K32 / k of those rows, compact
+    int count = 0;
+    const int *traj = nullptr;
+};
+
+// The list of a streamed iteration on the device, before the chunks are cut: reserved and filled on the CONTEXT (a view never
+// allocates), on the context's stream ahead of pipe_in.  A list equal to the one the device copy holds is not uploaded again, so
+// consecutive calls keep overlapping; a different one first orders the context's stream behind the chunks still reading the old one.
+static int pipe_list_bind(kpilqr_ctx *c, const StreamGains &g)
 {
-    if (!c || !io) return KPILQR_ERR_ARG;
+    if (!g.listed || g.count == 0) return KPILQR_OK;
+    const size_t B = c->d.batch;
+    { const int rc = reserve(c, c->pipe_list, B * sizeof(int), kExact, false); if (rc < 0) return rc; }
+    if (!c->pipe_list_host) {
+        const hipError_t e = hipHostMalloc((void **)&c->pipe_list_host, B * sizeof(int), hipHostMallocDefault);
+        if (e != hipSuccess) { c->pipe_list_host = nullptr; return set_err(c, KPILQR_ERR_ALLOC, std::string("hipHostMalloc failed: ") + hipGetErrorString(e)); }
+    }
+    if (!c->pipe_list_up) KP_HIP(c, hipEventCreateWithFlags(&c->pipe_list_up, hipEventDisableTiming));
+    if (c->pipe_list_count == g.count && memcmp(c->pipe_list_host, g.traj, sizeof(int) * (size_t)g.count) == 0) return KPILQR_OK;
+    { const int rc = join_pipeline(c); if (rc) return rc; }
+    if (c->pipe_list_count >= 0) KP_HIP(c, hipEventSynchronize(c->pipe_list_up));      // the mirror's last upload has read it
+    memcpy(c->pipe_list_host, g.traj, sizeof(int) * (size_t)g.count);
+    c->pipe_list_count = g.count;
+    KP_HIP(c, hipMemcpyAsync(c->pipe_list, c->pipe_list_host, sizeof(int) * (size_t)g.count, hipMemcpyHostToDevice, c->stream));
+    KP_HIP(c, hipEventRecord(c->pipe_list_up, c->stream));
+    return KPILQR_OK;
+}
+
+static int iterate_streamed(kpilqr_ctx *c, const kpilqr_stream_io *io, const StreamGains &g, int pd_check_stride, int nchunks)
+{
     KP_HIP(c, hipSetDevice(c->d.device));
     if (!c->have_kp) return set_err(c, KPILQR_ERR_STATE, "kpilqr_iterate_streamed before kpilqr_set_keypoints");
     if (pd_check_stride < 1) return set_err(c, KPILQR_ERR_ARG, "pd_check_stride must be >= 1");
@@ -1767,6 +1800,12 @@ int kpilqr_iterate_streamed(kpilqr_ctx *c, const kpilqr_stream_io *io, int pd_ch
     }
     const void *hostp[] = {io->kp_columns, io->fd_kp_slab, io->fd_slab, io->r, io->r_x, io->r_u, io->u_nom, io->lambda, io->K, io->k, io->cost_pred, io->delta_J, io->status};
     for (const void *p : hostp) if (!is_pinned(p)) return set_err(c, KPILQR_ERR_ARG, "kpilqr_iterate_streamed: host buffers must be pinned (kpilqr_host_alloc)");
+    if (g.K32) {
+        if (io->K) return set_err(c, KPILQR_ERR_ARG, "kpilqr_iterate_streamed2: io.K and K32 are exclusive");
+        if (!is_pinned(g.K32) || ((size_t)g.K32 & 7)) return set_err(c, KPILQR_ERR_ARG, "kpilqr_iterate_streamed2: K32 must be pinned (kpilqr_host_alloc) and 8-byte aligned");
+    }
+    if (g.listed && !kp_traj_list_ok(B, g.count, g.traj))
+        return set_err(c, KPILQR_ERR_ARG, "kpilqr_iterate_streamed2: gain_traj must be strictly increasing and within [0, batch)");
     if (c->fused) { int rc = check_fused(c); if (rc) return rc; }
     int rc = pipe_setup(c);
     if (rc) return rc;
@@ -1875,6 +1914,10 @@ int kpilqr_iterate_streamed(kpilqr_ctx *c, const kpilqr_stream_io *io, int pd_ch
     // constant residual Jacobians and a kernel family that streams r_x: the broadcast copy is made here, on the context (the
     // chunks' wave organisation is the whole batch's: make_view gives a chunk its share of the SIMDs)
     if (!(c->fused && plan_backward_fused(c, false).rxc && plan_forward_fused(c).rxc)) { rc = ensure_rx_buffer(c); if (rc) return rc; }
+    // the list of the gains that come down: on the device before the chunks, which read their slices of it
+    rc = pipe_list_bind(c, g); if (rc) return rc;
+    const bool gather = g.K32 || g.listed;      // K (and k of a list) leave through gains.hip's gather kernel
+    int li = 0;                                 // first list entry not below the chunk (chunks and list both increase)
     // order the chunk streams behind whatever the caller enqueued on the context's stream so far (key-points, weights ...)
     KP_HIP(c, hipEventRecord(c->pipe_in, c->stream));
     // from here on chunk streams hold work: every exit path, errors included, leaves the pipeline marked for joining, so a
@@ -1954,12 +1997,25 @@ int kpilqr_iterate_streamed(kpilqr_ctx *c, const kpilqr_stream_io *io, int pd_ch
         c->last_bwd = v.last_bwd; c->last_fwd = v.last_fwd;
         // ---- D2H of the chunk ------------------------------------------------------------------------------------
         // K, k by a copy kernel: it overlaps with the SDMA uploads of the next chunks (two SDMA directions do not)
+        if (gather) {
+            // K32 and the rows of a list: gathered (and rounded) by ONE launch per array straight into the pinned destination, whatever
+            // KPILQR_PIPE_COPY says (through SDMA they would need a staging buffer).  The chunk's share of a list is one slice of it,
+            // [i0, li), and one contiguous range of the compact outputs; without a list it is the chunk's own rows.
+            int i0 = b0, rows = nb;
+            if (g.listed) { i0 = li; while (li < g.count && g.traj[li] < b1) li++; rows = li - i0; }
+            const int *tl = g.listed ? (const int *)c->pipe_list + i0 : nullptr;
+            const size_t perK = (size_t)T * n * m, perk = (size_t)T * m;
+            if (g.K32) KP_HIP(c, launch_gains_out(c, s, GainsForm::K_f32, tl, b0, rows, g.K32 + (size_t)i0 * perK));
+            else if (io->K) KP_HIP(c, launch_gains_out(c, s, GainsForm::K_f64, tl, b0, rows, io->K + (size_t)i0 * perK));
+            if (io->k && g.listed) KP_HIP(c, launch_gains_out(c, s, GainsForm::k_f64, tl, b0, rows, io->k + (size_t)i0 * perk));
+        }
+        const bool k_whole = io->k && !g.listed;      // k of the whole batch: the copy it always was, beside K32 too
         if (k_down) {
-            if (io->K) KP_HIP(c, launch_copy_out(s, io->K + o * T * n * m, v.K, cnt * T * n * m));
-            if (io->k) KP_HIP(c, launch_copy_out(s, io->k + o * T * m, v.k, cnt * T * m));
+            if (io->K && !gather) KP_HIP(c, launch_copy_out(s, io->K + o * T * n * m, v.K, cnt * T * n * m));
+            if (k_whole) KP_HIP(c, launch_copy_out(s, io->k + o * T * m, v.k, cnt * T * m));
         } else {
-            if (io->K) KP_HIP(c, hipMemcpyAsync(io->K + o * T * n * m, v.K, cnt * T * n * m * 8, hipMemcpyDeviceToHost, s));
-            if (io->k) KP_HIP(c, hipMemcpyAsync(io->k + o * T * m, v.k, cnt * T * m * 8, hipMemcpyDeviceToHost, s));
+            if (io->K && !gather) KP_HIP(c, hipMemcpyAsync(io->K + o * T * n * m, v.K, cnt * T * n * m * 8, hipMemcpyDeviceToHost, s));
+            if (k_whole) KP_HIP(c, hipMemcpyAsync(io->k + o * T * m, v.k, cnt * T * m * 8, hipMemcpyDeviceToHost, s));
         }
         if (io->cost_pred) KP_HIP(c, hipMemcpyAsync(io->cost_pred + o * na, v.cost_pred, cnt * na * 8, hipMemcpyDeviceToHost, s));
         if (io->delta_J) KP_HIP(c, hipMemcpyAsync(io->delta_J + o, v.delta_J, cnt * 8, hipMemcpyDeviceToHost, s));
@@ -1967,6 +2023,23 @@ int kpilqr_iterate_streamed(kpilqr_ctx *c, const kpilqr_stream_io *io, int pd_ch
     }
     c->pay = after;
     return KPILQR_OK;
+}
+
+int kpilqr_iterate_streamed(kpilqr_ctx *c, const kpilqr_stream_io *io, int pd_check_stride, int nchunks)
+{
+    if (!c || !io) return KPILQR_ERR_ARG;
+    return iterate_streamed(c, io, StreamGains{}, pd_check_stride, nchunks);
+}
+
+int kpilqr_iterate_streamed2(kpilqr_ctx *c, const kpilqr_stream_io2 *io2, int pd_check_stride, int nchunks)
+{
+    if (!c || !io2) return KPILQR_ERR_ARG;
+    if (io2->struct_size != sizeof(kpilqr_stream_io2)) return set_err(c, KPILQR_ERR_ARG, "kpilqr_iterate_streamed2: struct_size is not sizeof(kpilqr_stream_io2) of this library");
+    if (io2->gain_count < 0 || (io2->gain_count > 0 && !io2->gain_traj)) return set_err(c, KPILQR_ERR_ARG, "kpilqr_iterate_streamed2: gain_count < 0, or listed trajectories without gain_traj");
+    StreamGains g;
+    g.K32 = io2->K32;
+    g.listed = io2->gain_traj != nullptr; g.count = io2->gain_count; g.traj = io2->gain_traj;
+    return iterate_streamed(c, &io2->io, g, pd_check_stride, nchunks);
 }
 
 // ---- multi-GPU: the line-search cost reduction -----------------------------------------------------------

@@ -358,9 +358,25 @@ class Engine:
         self._ck(self._L.kpilqr_upload_fd_slab(self._h, _ptr(s["slab"]), s["njobs"], s["nnom"], float(eps)))
 
     def iterate_streamed(self, fd=None, fd_kp=None, kp_cols=None, eps=1e-6, r=None, r_x=None, r_u=None, u_nom=None, lam=None, K=None, k=None,
-                         cost_pred=None, delta_J=None, status=None, pd_stride=100, nchunks=0):
-        """kpilqr_iterate_streamed: every array must come from self.pinned(); asynchronous (sync() to wait)."""
-        io = _lib.StreamIO()
+                         cost_pred=None, delta_J=None, status=None, pd_stride=100, nchunks=0, K32=None, gain_traj=None):
+        """kpilqr_iterate_streamed: every array must come from self.pinned(); asynchronous (sync() to wait).
+        K32 (np.float32, pinned; instead of K): K comes down rounded to FP32.  gain_traj (any int sequence, strictly increasing): K / K32
+        / k of those trajectories alone, compact in list order ([]: no gains come down).  Either one takes kpilqr_iterate_streamed2;
+        with neither the call is the one it always was."""
+        io2 = None
+        if K32 is not None or gain_traj is not None:
+            io2 = _lib.StreamIO2()
+            io2.struct_size = C.sizeof(_lib.StreamIO2)
+            if K32 is not None:
+                if K32.dtype != np.float32:
+                    raise ValueError("K32 must be a float32 array")
+                io2.K32 = K32.ctypes.data
+            if gain_traj is not None:
+                tr = self._traj(gain_traj)
+                io2.gain_count = len(tr)
+                tr = tr if len(tr) else np.zeros(1, np.int32)          # an empty list is still a list: a non-NULL pointer
+                io2.gain_traj = tr.ctypes.data                         # (read during the call only)
+        io = _lib.StreamIO() if io2 is None else io2.io
         if fd is not None:
             io.fd_slab = fd["slab"].ctypes.data; io.njobs = fd["njobs"]; io.nnom = fd["nnom"]
             io.traj_job_first = fd["traj_job_first"].ctypes.data; io.traj_nom_first = fd["traj_nom_first"].ctypes.data
@@ -373,7 +389,10 @@ class Engine:
                         ("cost_pred", cost_pred), ("delta_J", delta_J), ("status", status)):
             if a is not None:
                 setattr(io, name, a.ctypes.data)
-        self._ck(self._L.kpilqr_iterate_streamed(self._h, C.byref(io), int(pd_stride), int(nchunks)))
+        if io2 is None:
+            self._ck(self._L.kpilqr_iterate_streamed(self._h, C.byref(io), int(pd_stride), int(nchunks)))
+        else:
+            self._ck(self._partial("kpilqr_iterate_streamed2")(self._h, C.byref(io2), int(pd_stride), int(nchunks)))
 
     def fd_difference(self):
         self._ck(self._L.kpilqr_fd_difference(self._h))
