@@ -507,15 +507,59 @@ int  kpilqr_trajectory_cost(kpilqr_ctx *ctx, double *cost /*[batch]*/);
  * (results stay on the device, KPILQR_BUF_STATUS / KPILQR_BUF_DELTA_J).  A trajectory with status != 0 has stopped at that
  * step (the reference returns false there and retries at a larger lambda, iLQR.cpp:435-442): its gains below that step, its
  * delta_J and the outputs of a kpilqr_forward_linear that follows are UNDEFINED for that trajectory until a backward pass
- * succeeds (on a fused context its key-point columns may be differenced only down to that step). */
+ * succeeds (on a fused context its key-point columns may be differenced only down to that step).  With a schedule set by
+ * kpilqr_set_lambda_retry (below) the call retries such a trajectory itself, at a raised lambda. */
 int  kpilqr_backward(kpilqr_ctx *ctx, const double *lambda, int pd_check_stride,
                      int *status, double *delta_J);
+/* ---- Lambda retry: the failure side of the reference's lambda schedule behind the ABI ----------------------------------------
+ * The reference retries a backward pass whose Q_uu + lambda I failed the Cholesky test at lambda * lambdaFactor and gives up above
+ * maxLambda (src/Optimiser/iLQR.cpp:435-442, UpdateLambda :636-657).  Without a schedule that loop is the caller's: backward, sync,
+ * look at status, backward again for the whole batch.  With one, every call that runs a backward sweep -- kpilqr_backward,
+ * kpilqr_iterate, kpilqr_iterate_streamed and kpilqr_iterate_streamed2 (per chunk) -- runs it on the device, per trajectory:
+ *     sweep at lambda; status == 0: settled.  Otherwise lambda' = lambda * factor (ONE IEEE multiply); lambda' > max_lambda: give
+ *     up; otherwise, while fewer than max_attempts sweeps have run in this call, sweep again at lambda'.
+ * Opt-in: set once on the context, like key-points, weights, limits and alphas (kpilqr_stream_io / _io2 are unchanged); NULL turns it
+ * off, the default.  Without a schedule no copy, launch or result differs from a library without these calls.
+ * After the call, per trajectory: the RESIDENT lambda is the lambda of its last sweep (lambda_used; a later call with lambda = NULL
+ * starts from it), attempts is the number of sweeps it ran, and status, delta_J, K, k and the key-point columns a raw sweep leaves
+ * behind are those of its last sweep.  A settled trajectory is never swept again within the call: its outputs are the bits of its
+ * successful sweep.  One that gave up or ran out of attempts has the failing step of its last sweep in status and everything else
+ * undefined, as above.  The success side of UpdateLambda (/ factor, the min_lambda clamp) stays with the caller, who derives its
+ * state from (status, lambda_used, attempts):
+ *     status == 0                                             valid backward pass at lambda_used; next lambda = max(lambda_used / factor, min_lambda)
+ *     status != 0 and lambda_used * factor >  max_lambda      lambda exit (the reference clamps lambda to maxLambda and stops)
+ *     status != 0 and lambda_used * factor <= max_lambda      out of attempts: call again -- with lambda = NULL the call starts at the resident
+ *                                                             lambda_used (that sweep fails again) and carries on up the schedule; a
+ *                                                             caller that passes lambda_used * factor saves the repeated sweep
+ * (lambda_used * factor computed by the caller in double is the value the device compared.)
+ * How.  Every backward kernel has a gated twin that takes `gate` [batch] and leaves at its first statement where gate[b] == 0;
+ * between two attempts ONE small kernel (k_lambda_retry, lambda_retry.hip) reads status, advances lambda, counts the attempt and
+ * writes the gate.  The first attempt launches the kernels without the gate: it is the launch of a context without a schedule
+ * (behind one small kernel that sets every trajectory's count to 1).  The number of attempts launched is the
+ * longest run the schedule allows from the lambdas the caller passed (for the streamed calls: a chunk's own slice of io.lambda),
+ * computed on the host with the same multiply and capped by max_attempts; with lambda = NULL it is max_attempts.  What runs before
+ * the sweep (column store, slopes, broadcast Jacobians) runs once; a retried raw sweep differences its payload again.
+ * kpilqr_set_lambda_retry: KPILQR_ERR_ARG -- before anything changes -- for a struct_size that is not this library's, a factor that is
+ * not finite and > 1, a max_lambda that is not finite and > 0, max_attempts outside 1 .. 64; enqueues nothing.  kpilqr_resize keeps
+ * the schedule.  kpilqr_backward_stats ignores it (one instrumented sweep).
+ * kpilqr_download_lambda_retry: lambda_used [batch], attempts [batch] of the last backward pass under the schedule; either may be
+ * NULL.  Asynchronous on the context's stream, behind a streamed iteration in flight; valid after kpilqr_sync.  KPILQR_ERR_STATE
+ * while no schedule is set or before any backward sweep ran under it.
+ * KPILQR_VERSION is unchanged: detect the calls by their symbols. */
+typedef struct {
+    size_t struct_size;   /* sizeof(kpilqr_lambda_retry) as compiled, else KPILQR_ERR_ARG */
+    double factor;        /* lambdaFactor (10): finite and > 1 */
+    double max_lambda;    /* maxLambda (10): finite and > 0 */
+    int    max_attempts;  /* sweeps per trajectory and call, the first included: 1 .. 64 */
+} kpilqr_lambda_retry;
+int  kpilqr_set_lambda_retry(kpilqr_ctx *ctx, const kpilqr_lambda_retry *sched /* NULL: off */);
+int  kpilqr_download_lambda_retry(kpilqr_ctx *ctx, double *lambda_used /*[batch]*/, int *attempts /*[batch]*/);
 /* Diagnostic: the backward pass of a KPILQR_FLAG_FUSED context with counters.  The explicit inverse the reference forms at
  * every step (iLQR.cpp:597-600) is carried along the sweep and refreshed on the matrix core; how much work a step needs is
  * data dependent (and a launch lasts as long as its slowest wavefront).  hist [batch][6] = steps whose inverse came from:
  * [0] the third-order refresh alone, [1..3] that plus 1 / 2 / 3 second-order steps, [4] the LDL' factorisation (first step,
  * every pd_check_stride-th step, re-seeds), [5] Eigen's pivoted LDLT restated (indefinite Q_uu + lambda I on an unchecked
- * step).  K, k, delta_J, status as kpilqr_backward; lambda as last given.  Synchronous. */
+ * step).  K, k, delta_J, status as kpilqr_backward; lambda as last given.  Synchronous.  Ignores kpilqr_set_lambda_retry: one sweep. */
 int  kpilqr_backward_stats(kpilqr_ctx *ctx, int pd_check_stride, int *hist);
 /* K [batch][T][n][m] (column-major m x n), k [batch][T][m]; either may be NULL. */
 int  kpilqr_download_gains(kpilqr_ctx *ctx, double *K, double *k);

@@ -16,6 +16,8 @@ UNITS = [("riccati_mfma.hip", MFMAF), ("forward_mfma.hip", MFMAF), ("tiled_mfma.
 
 # (pattern on the demangled name, reason it is not dispatched by tests/test_gpu_shapes.py)
 REASONS = [
+    (r"k_backward_\w+_retry\b|k_backward_tiled_(col|uw|wide)<.*, true>$", "lambda retry twin (kpilqr_set_lambda_retry): runs the attempts behind the first of a "
+                                                                       "backward pass under a schedule; tests/test_gpu_lambda_retry.py dispatches one per family"),
     (r"k_backward_fused_stats<", "diagnostic entry point only (kpilqr_backward_stats, the refresh histogram)"),
     (r"k_(backward|forward)_fused<", "plain form (batch > n_simd) in a residual / payload mode other than the headline's (constant r_x, "
                                      "key-point ordered payload): test_batch_boundaries runs the plain form in that mode only"),

@@ -32,6 +32,7 @@ SYMBOLS = [
     "kpilqr_update_keypoints", "kpilqr_upload_fd_kp_partial", "kpilqr_upload_kp_columns_partial", "kpilqr_download_gains_partial",
     "kpilqr_upload_residuals_partial", "kpilqr_upload_nominal_partial", "kpilqr_fd_interpolate_partial", "kpilqr_cost_derivs_partial",
     "kpilqr_download_gains_f32", "kpilqr_download_gains_f32_partial", "kpilqr_iterate_streamed2",
+    "kpilqr_set_lambda_retry", "kpilqr_download_lambda_retry",
 ]
 # entry points added without a version bump (include/kpilqr.h: "detect the entry point by its symbol"): bound only when the library
 # has them -- KPILQR_LIB may name an older build of the same major version
@@ -39,7 +40,8 @@ OPTIONAL_SYMBOLS = {"kpilqr_fd_interpolate", "kpilqr_get_union_keypoints", "kpil
                     "kpilqr_update_keypoints", "kpilqr_upload_fd_kp_partial", "kpilqr_upload_kp_columns_partial",
                     "kpilqr_download_gains_partial", "kpilqr_upload_residuals_partial", "kpilqr_upload_nominal_partial",
                     "kpilqr_fd_interpolate_partial", "kpilqr_cost_derivs_partial",
-                    "kpilqr_download_gains_f32", "kpilqr_download_gains_f32_partial", "kpilqr_iterate_streamed2"}
+                    "kpilqr_download_gains_f32", "kpilqr_download_gains_f32_partial", "kpilqr_iterate_streamed2",
+                    "kpilqr_set_lambda_retry", "kpilqr_download_lambda_retry"}
 
 
 class Dims(C.Structure):
@@ -67,6 +69,11 @@ class StreamIO(C.Structure):
 class StreamIO2(C.Structure):
     """kpilqr_stream_io2: StreamIO with K as FP32 and the gains of a list of trajectories; struct_size = sizeof(StreamIO2)"""
     _fields_ = [("struct_size", C.c_size_t), ("io", StreamIO), ("K32", C.c_void_p), ("gain_count", C.c_int), ("gain_traj", C.c_void_p)]
+
+
+class LambdaRetry(C.Structure):
+    """kpilqr_lambda_retry: the failure side of the lambda schedule, run on the device; struct_size = sizeof(LambdaRetry)"""
+    _fields_ = [("struct_size", C.c_size_t), ("factor", C.c_double), ("max_lambda", C.c_double), ("max_attempts", C.c_int)]
 
 
 ABI_MAJOR = 4                  # KPILQR_VERSION / 100 of the include/kpilqr.h this binding mirrors
@@ -174,6 +181,9 @@ def load():
         L.kpilqr_download_gains_f32_partial.argtypes = [vp, C.c_int, vp, vp, vp]
     if hasattr(L, "kpilqr_iterate_streamed2"):
         L.kpilqr_iterate_streamed2.argtypes = [vp, C.POINTER(StreamIO2), C.c_int, C.c_int]
+    if hasattr(L, "kpilqr_set_lambda_retry"):
+        L.kpilqr_set_lambda_retry.argtypes = [vp, C.POINTER(LambdaRetry)]
+        L.kpilqr_download_lambda_retry.argtypes = [vp, vp, vp]
     for s in SYMBOLS:
         if s in OPTIONAL_SYMBOLS and not hasattr(L, s):
             continue

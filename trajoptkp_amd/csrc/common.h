@@ -125,6 +125,10 @@ struct Ctx {
     DevBuf<double> delta_J;       // [batch]
     DevBuf<double> traj_cost;     // [batch]
     DevBuf<int> status;           // [batch]
+    // kpilqr_set_lambda_retry (lambda_retry.hip): sweeps each trajectory has run in the last backward pass under the schedule, and whether
+    // the next attempt of the call in flight sweeps it again (1) or it is settled / has given up (0)
+    DevBuf<int> attempts;         // [batch]
+    DevBuf<int> gate;             // [batch]
     DevBuf<int> traj_list;        // [batch]: the trajectories of the partial record calls in flight (kpilqr_fd_interpolate_partial ...)
     DevBuf<int2> segmap;          // [batch][dof][T]: (start,end) key-points around t, or (-1,-1)
     // [batch][dof][T]: CSR entry of the key-point at or before t (the one-pass linearisation fetches a segment's endpoints by
@@ -259,10 +263,20 @@ struct Ctx {
     void for_each_buffer(F f)
     {
         DevMem *const all[] = {&rec, &kp_uniform, &K, &k, &r, &r_x, &r_u, &w_run, &w_term, &u_nom, &ctrl_lim, &lambda, &alphas, &cost_pred,
-                               &delta_J, &traj_cost, &status, &traj_list, &K32, &segmap, &segent, &kp_offsets, &kp_times, &rx_const, &kpc, &kps, &kp_entry,
+                               &delta_J, &traj_cost, &status, &attempts, &gate, &traj_list, &K32, &segmap, &segent, &kp_offsets, &kp_times, &rx_const, &kpc, &kps, &kp_entry,
                                &kp_entry_list, &fdk_dev, &kpu_offsets, &kpu_times, &kpu_src, &kpu_traj_first, &kpcu, &kpu_uniform, &fdk_alt, &kpc_alt, &kp_times_alt, &kp_upl_times, &kp_move, &X_states, &kp_thr, &kp_mask, &kp_count, &ls8, &fd_dev, &err_flag, &stage, &pipe_list};
         for (DevMem *b : all) f(*b);
     }
+
+    // The lambda retry schedule (kpilqr_set_lambda_retry; kept by kpilqr_resize).  retry_attempts: the attempts the backward pass about
+    // to run launches, set by the entry point from the lambdas its caller passed.  bwd_gate: what the backward launchers look at -- nullptr
+    // (the kernels of a context without a schedule) on the first attempt, `gate` on the attempts behind k_lambda_retry, which
+    // launch the kernels' _retry twins.
+    kpilqr_lambda_retry retry{};
+    bool retry_on = false;
+    bool retry_ran = false;       // a backward pass has run under the schedule since it was set: attempts holds its counts
+    int retry_attempts = 1;
+    const int *bwd_gate = nullptr;
 
     Family bwd_family = Family::generic, fwd_family = Family::generic;
     // what the last backward / forward launch of this context actually was (kpilqr_last_launch); Waves::none: not a fused launch, or none yet
@@ -328,6 +342,9 @@ hipError_t launch_gains_f32(Ctx *c, const int *traj, int count, float *out);
 // dst [count][row] compact.  K_f32: K rounded to FP32 | K_f64, k_f64: as they are
 enum class GainsForm : int { K_f32, K_f64, k_f64 };
 hipError_t launch_gains_out(const Ctx *c, hipStream_t s, GainsForm form, const int *traj, int first, int count, void *dst_host);
+// lambda_retry.hip: attempts = 1, gate = 1 for every trajectory | between two attempts: status -> lambda, attempts, gate
+hipError_t launch_lambda_retry_begin(Ctx *c);
+hipError_t launch_lambda_retry(Ctx *c);
 // comm.cpp (RCCL opened lazily) and the pack kernel of elementwise.hip
 const char *comm_unique_id(char *id128);
 const char *comm_init(Ctx *c, int nranks, int rank, const char *id128);

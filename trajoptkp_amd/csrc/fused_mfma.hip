@@ -995,7 +995,31 @@ k_backward_fused_excl(RecLayout L, FusedArgs F, int T, const double *__restrict_
     if ((*kp_uniform != 0) != UNI) return;
     backward_fused_body<N, M, false, RU0, RAW, UNI, false, RXC>(sh, nullptr, nullptr, L, F, T, lambda, pd_stride, Kout, kout, delta_J, status);
 }
-
+// The lambda retry twins of the two (kpilqr_set_lambda_retry, lambda_retry.hip): the attempts behind the first of a backward pass under a
+// schedule.  A wave whose trajectory is settled or has given up (gate[b] == 0) leaves before anything else; the first attempt, and
+// every launch without a schedule, is one of the two kernels above, unchanged.
+template <int N, int M, bool RU0, bool RAW, bool UNI, bool RXC = false>
+__global__ void __launch_bounds__(64)
+k_backward_fused_retry(RecLayout L, FusedArgs F, int T, const double *__restrict__ lambda,
+                       int pd_stride, double *__restrict__ Kout, double *__restrict__ kout,
+                       double *__restrict__ delta_J, int *__restrict__ status, const int *__restrict__ kp_uniform, const int *__restrict__ gate)
+{
+    __shared__ __attribute__((aligned(16))) double sh[FLDS_TOTAL];
+    if (gate[KP_BLOCK_TRAJ] == 0) return;
+    if ((*kp_uniform != 0) != UNI) return;
+    backward_fused_body<N, M, false, RU0, RAW, UNI, false, RXC>(sh, nullptr, nullptr, L, F, T, lambda, pd_stride, Kout, kout, delta_J, status);
+}
+template <int N, int M, bool RU0, bool RAW, bool UNI, bool RXC = false>
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1)))
+k_backward_fused_excl_retry(RecLayout L, FusedArgs F, int T, const double *__restrict__ lambda,
+                            int pd_stride, double *__restrict__ Kout, double *__restrict__ kout,
+                            double *__restrict__ delta_J, int *__restrict__ status, const int *__restrict__ kp_uniform, const int *__restrict__ gate)
+{
+    __shared__ __attribute__((aligned(16))) double sh[FLDS_TOTAL];
+    if (gate[KP_BLOCK_TRAJ] == 0) return;
+    if ((*kp_uniform != 0) != UNI) return;
+    backward_fused_body<N, M, false, RU0, RAW, UNI, false, RXC>(sh, nullptr, nullptr, L, F, T, lambda, pd_stride, Kout, kout, delta_J, status);
+}
 
 // ---------------------------------------------------------------------------------------------------------
 // Column trackers of the helper wave (consumer / helper pair below): a4 walking DOWN in time, NV values per lane.
@@ -1395,6 +1419,25 @@ k_backward_fusedph(RecLayout L, FusedArgs F, int T, int role_shift, const double
                    double *__restrict__ delta_J, int *__restrict__ status, const int *__restrict__ kp_uniform, int guard)
 {
     __shared__ __attribute__((aligned(16))) double sh[FPC_TOTAL];
+    if (guard >= 0 && (*kp_uniform != 0) != (guard != 0)) return;
+    const bool consumer = ((__builtin_amdgcn_readfirstlane(threadIdx.x >> 6) ^ (blockIdx.x >> role_shift)) & 1) == 0;
+    if (consumer)
+        backward_fused_body<N, M, true, RU0>(sh, sh + FPC_RING, (int *)(sh + FPC_FLAG), L, F, T, lambda, pd_stride, Kout, kout,
+                                                   delta_J, status);
+    else
+        fusedpc_producer<N, M, RAWP, RU0, RXC, SLP>(sh + FPC_RING, (int *)(sh + FPC_FLAG), L, F, T, sh);
+}
+// ... and its lambda retry twin (see k_backward_fused_retry): consumer and helper of a settled trajectory, or of one that gave up, leave
+// together, before the role split and before either touches the ring or its flags -- nobody is left waiting for a partner
+template <int N, int M, bool RAWP, bool RU0, bool RXC, bool SLP = false>
+__global__ void __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(1, 1)))
+k_backward_fusedph_retry(RecLayout L, FusedArgs F, int T, int role_shift, const double *__restrict__ lambda,
+                         int pd_stride, double *__restrict__ Kout, double *__restrict__ kout,
+                         double *__restrict__ delta_J, int *__restrict__ status, const int *__restrict__ kp_uniform, int guard,
+                         const int *__restrict__ gate)
+{
+    __shared__ __attribute__((aligned(16))) double sh[FPC_TOTAL];
+    if (gate[KP_BLOCK_TRAJ] == 0) return;
     if (guard >= 0 && (*kp_uniform != 0) != (guard != 0)) return;
     const bool consumer = ((__builtin_amdgcn_readfirstlane(threadIdx.x >> 6) ^ (blockIdx.x >> role_shift)) & 1) == 0;
     if (consumer)
@@ -2309,6 +2352,12 @@ FusedLaunch plan_forward_fused(const Ctx *c)
 template <int NN, int MM, bool RU, bool RW, bool UN, bool RX>
 static void launch_bf_kernel(Ctx *c, const FusedLaunch &p, const FusedArgs &F, int pd_stride)
 {
+    if (c->bwd_gate) {
+        const auto twin = p.excl ? k_backward_fused_excl_retry<NN, MM, RU, RW, UN, RX> : k_backward_fused_retry<NN, MM, RU, RW, UN, RX>;
+        hipLaunchKernelGGL(twin, dim3(c->d.batch), dim3(64), 0, c->stream, c->L, F, c->d.T, c->lambda, pd_stride, c->K, c->k, c->delta_J,
+                           c->status, c->kp_uniform, c->bwd_gate);
+        return;
+    }
     const auto kernel = p.excl ? k_backward_fused_excl<NN, MM, RU, RW, UN, RX> : k_backward_fused<NN, MM, RU, RW, UN, RX>;
     hipLaunchKernelGGL(kernel, dim3(c->d.batch), dim3(64), 0, c->stream, c->L, F, c->d.T, c->lambda, pd_stride, c->K, c->k, c->delta_J,
                        c->status, c->kp_uniform);
@@ -2359,6 +2408,13 @@ hipError_t launch_backward_fused(Ctx *c, const FusedLaunch &p, int pd_stride)
 template <int NN, int MM, bool RW, bool SL>
 static void launch_bph_kernel(Ctx *c, const FusedLaunch &p, const FusedArgs &F, int pd_stride, int guard)
 {
+    if (c->bwd_gate) {
+        auto twin = k_backward_fusedph_retry<NN, MM, RW, true, true, SL>;
+        if (!p.rxc) twin = p.ru0 ? k_backward_fusedph_retry<NN, MM, RW, true, false, SL> : k_backward_fusedph_retry<NN, MM, RW, false, false, SL>;
+        hipLaunchKernelGGL(twin, dim3(c->d.batch), dim3(128), 0, c->stream, c->L, F, c->d.T, c->tune.role_shift, c->lambda, pd_stride, c->K,
+                           c->k, c->delta_J, c->status, c->kp_uniform, guard, c->bwd_gate);
+        return;
+    }
     auto kernel = k_backward_fusedph<NN, MM, RW, true, true, SL>;
     if (!p.rxc) kernel = p.ru0 ? k_backward_fusedph<NN, MM, RW, true, false, SL> : k_backward_fusedph<NN, MM, RW, false, false, SL>;
     hipLaunchKernelGGL(kernel, dim3(c->d.batch), dim3(128), 0, c->stream, c->L, F, c->d.T, c->tune.role_shift, c->lambda, pd_stride, c->K,

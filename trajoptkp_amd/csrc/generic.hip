@@ -98,10 +98,10 @@ size_t backward_generic_lds_bytes(int n, int m)
     return d * sizeof(double);
 }
 
-__global__ void __launch_bounds__(64)
-k_backward_generic(RecLayout L, int T, const double *__restrict__ rec, const double *__restrict__ lambda,
-                   int pd_stride, double *__restrict__ Kout, double *__restrict__ kout,
-                   double *__restrict__ delta_J, int *__restrict__ status)
+__device__ __forceinline__ void
+backward_generic_body(RecLayout L, int T, const double *__restrict__ rec, const double *__restrict__ lambda,
+                      int pd_stride, double *__restrict__ Kout, double *__restrict__ kout,
+                      double *__restrict__ delta_J, int *__restrict__ status)
 {
     extern __shared__ __attribute__((aligned(16))) double sh[];
     const int n = L.n, m = L.m, tid = threadIdx.x, NT = blockDim.x;
@@ -262,14 +262,40 @@ k_backward_generic(RecLayout L, int T, const double *__restrict__ rec, const dou
     if (tid == 0) { delta_J[b] = dJ; status[b] = fail; }
 }
 
+// The kernel and its lambda retry twin (kpilqr_set_lambda_retry, lambda_retry.hip).  The twin runs the attempts BEHIND the first of a
+// backward pass under a schedule: its first statement looks at gate[b] -- b the block's trajectory, a scalar load and a branch uniform
+// over the block, before any LDS write, barrier or role split -- and the whole block leaves where the trajectory is settled or has
+// given up.  The first attempt, and every launch without a schedule, is the kernel without the gate: the same instructions as in a
+// library without the schedule (profiles/lambda_retry.txt has the register counts of both).
+__global__ void __launch_bounds__(64)
+k_backward_generic(RecLayout L, int T, const double *__restrict__ rec, const double *__restrict__ lambda,
+                   int pd_stride, double *__restrict__ Kout, double *__restrict__ kout,
+                   double *__restrict__ delta_J, int *__restrict__ status)
+{
+    backward_generic_body(L, T, rec, lambda, pd_stride, Kout, kout, delta_J, status);
+}
+__global__ void __launch_bounds__(64)
+k_backward_generic_retry(RecLayout L, int T, const double *__restrict__ rec, const double *__restrict__ lambda,
+                         int pd_stride, double *__restrict__ Kout, double *__restrict__ kout,
+                         double *__restrict__ delta_J, int *__restrict__ status, const int *__restrict__ gate)
+{
+    if (gate[blockIdx.x] == 0) return;
+    backward_generic_body(L, T, rec, lambda, pd_stride, Kout, kout, delta_J, status);
+}
+
 hipError_t launch_backward_generic(Ctx *c, int pd_stride)
 {
     const size_t lds = backward_generic_lds_bytes(c->n, c->d.m);
     if (lds > 160 * 1024) return hipErrorInvalidValue;
-    hipError_t e = hipFuncSetAttribute((const void *)k_backward_generic, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    const void *kernel = c->bwd_gate ? (const void *)k_backward_generic_retry : (const void *)k_backward_generic;
+    hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_backward_generic, dim3(c->d.batch), dim3(64), lds, c->stream, c->L, c->d.T, c->rec,
-                       c->lambda, pd_stride, c->K, c->k, c->delta_J, c->status);
+    if (c->bwd_gate)
+        hipLaunchKernelGGL(k_backward_generic_retry, dim3(c->d.batch), dim3(64), lds, c->stream, c->L, c->d.T, c->rec,
+                           c->lambda, pd_stride, c->K, c->k, c->delta_J, c->status, c->bwd_gate);
+    else
+        hipLaunchKernelGGL(k_backward_generic, dim3(c->d.batch), dim3(64), lds, c->stream, c->L, c->d.T, c->rec,
+                           c->lambda, pd_stride, c->K, c->k, c->delta_J, c->status);
     return hipGetLastError();
 }
 

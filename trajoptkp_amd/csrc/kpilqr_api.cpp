@@ -163,6 +163,8 @@ static int size_buffers(kpilqr_ctx *c)
         {&c->delta_J, B * 8, false},
         {&c->traj_cost, B * 8, false},
         {&c->status, B * 4, true},
+        {&c->attempts, B * 4, true},
+        {&c->gate, B * 4, true},
         {&c->traj_list, B * sizeof(int), false},
         {&c->segmap, B * dims->dof * T * sizeof(int2), false},
         {&c->kp_offsets, (B * dims->dof + 1) * 4, false},
@@ -702,6 +704,7 @@ int kpilqr_resize(kpilqr_ctx *c, int new_dof, int new_num_ctrl, int new_horizon)
     c->njobs = c->nnom = 0;
     c->fd_payload = FdPayload::none; c->fdk_entries = 0; c->kp_total_host = -1;
     forget_lists(c);                                     // (sized by the old batch * dof; size_buffers has reset both validity aggregates)
+    c->retry_ran = false;                                // (the lambda retry schedule itself stays; lambda and the counts are forgotten)
     c->ru_zero = true;                                   // size_buffers zeroed r_u
     c->rx_const_on = false; c->rx_buf_valid = true; c->rx_whole = false;
     // the key-point placement buffers were sized by the old shape: they are allocated again on first use
@@ -1338,6 +1341,49 @@ static int check_fused(kpilqr_ctx *c)
     return KPILQR_OK;
 }
 
+// ---- the lambda retry schedule (kpilqr_set_lambda_retry) --------------------------------------------------------------------
+// How many attempts a backward pass launches: the longest run of lambda values the schedule allows from the lambdas the caller passed
+// (for positive lambdas: from the smallest), the host loop's multiply and comparison, capped by max_attempts.  Without the caller's
+// lambdas (the resident ones are used) max_attempts.  Later attempts than a trajectory needs leave at the gate.
+static int retry_attempts_for(const kpilqr_ctx *c, const double *lambda, size_t count)
+{
+    if (!c->retry_on) return 1;
+    const kpilqr_lambda_retry &s = c->retry;
+    if (!lambda) return s.max_attempts;
+    int most = 1;
+    for (size_t b = 0; b < count && most < s.max_attempts; b++) {
+        int a = 1;
+        for (double l = lambda[b]; a < s.max_attempts; a++) {
+            l = l * s.factor;
+            if (l > s.max_lambda) break;
+        }
+        if (a > most) most = a;
+    }
+    return most;
+}
+
+// The sweep launch of one backward pass -- `launch`, a launcher's whole launch sequence on lc (the context, a chunk view, or the union
+// view made from c) -- and under a schedule its repetitions: k_lambda_retry between two attempts advances lambda where a PD check
+// failed and writes the gate the next attempt's kernels look at first.  The first attempt has no gate: it is the launch of a context
+// without a schedule.  What runs before the sweeps (column store, slopes, broadcast Jacobians) has run once, in run_backward.
+extern "C++" template <class Launch>
+static int sweep_attempts(kpilqr_ctx *c, kpilqr_ctx *lc, Launch launch)
+{
+    lc->bwd_gate = nullptr;
+    if (!c->retry_on) { KP_HIP(c, launch()); return KPILQR_OK; }
+    KP_HIP(c, launch_lambda_retry_begin(c));
+    KP_HIP(c, launch());
+    for (int a = 1; a < c->retry_attempts; a++) {
+        KP_HIP(c, launch_lambda_retry(c));
+        lc->bwd_gate = c->gate;
+        const hipError_t e = launch();
+        lc->bwd_gate = nullptr;
+        KP_HIP(c, e);
+    }
+    c->retry_ran = true;
+    return KPILQR_OK;
+}
+
 static int run_backward(kpilqr_ctx *c, int pd_stride)
 {
     if (c->fused) {
@@ -1352,8 +1398,7 @@ static int run_backward(kpilqr_ctx *c, int pd_stride)
             plan.uni_on_union = true;
             c->last_bwd = plan;
             if (!plan.rxc) { rc = ensure_rx_buffer(c); if (rc) return rc; }
-            KP_HIP(c, launch_backward_fused(&v, plan, pd_stride));
-            return KPILQR_OK;
+            return sweep_attempts(c, &v, [&] { return launch_backward_fused(&v, plan, pd_stride); });
         }
         rc = ensure_kpc(c);
         if (rc) return rc;
@@ -1366,7 +1411,9 @@ static int run_backward(kpilqr_ctx *c, int pd_stride)
         const FusedLaunch plan = c->last_bwd = plan_backward_fused(c, !c->pay.kpc_valid && c->fd_payload == FdPayload::kp_ordered && c->tune.fused_raw != 0);
         if (!plan.rxc) { rc = ensure_rx_buffer(c); if (rc) return rc; }       // (the sweep streams r_x: a constant one needs its broadcast copy)
         if (plan.raw) {
-            KP_HIP(c, launch_backward_fused(c, plan, pd_stride));
+            // (a retried raw sweep differences its trajectory's payload again, as it does after a retry by the host)
+            rc = sweep_attempts(c, c, [&] { return launch_backward_fused(c, plan, pd_stride); });
+            if (rc) return rc;
             c->pay.kpc_touched = true;
             // (KPILQR_FUSED_UNI=0, diagnostic: the GENERAL raw sweep has differenced every set inside the sweep -- dividing at its
             // crossings -- and left the columns; the forward sweep's general form walks the slope store, made from them here)
@@ -1375,18 +1422,18 @@ static int run_backward(kpilqr_ctx *c, int pd_stride)
         }
         if (!c->pay.kpc_valid) { rc = difference_to_kpc(c); if (rc) return rc; }
         if (c->pay.kpc_valid) { rc = slopes_for_kpc(c); if (rc) return rc; }
-        KP_HIP(c, launch_backward_fused(c, plan, pd_stride));
-        return KPILQR_OK;
+        return sweep_attempts(c, c, [&] { return launch_backward_fused(c, plan, pd_stride); });
     }
     c->last_bwd = FusedLaunch{};       // (no plan: not a fused launch, and the tiled a6 sweep streams r_x)
     if (c->tiled_a6) { const int rc = ensure_rx_buffer(c); if (rc) return rc; }
-    switch (c->bwd_family) {
-    case Family::t1: KP_HIP(c, launch_backward_mfma(c, pd_stride)); break;
-    case Family::tiled: KP_HIP(c, launch_backward_tiled(c, pd_stride)); break;
-    case Family::wide: KP_HIP(c, launch_backward_wide(c, pd_stride)); break;
-    default: KP_HIP(c, launch_backward_generic(c, pd_stride)); break;
-    }
-    return KPILQR_OK;
+    return sweep_attempts(c, c, [&] {
+        switch (c->bwd_family) {
+        case Family::t1: return launch_backward_mfma(c, pd_stride);
+        case Family::tiled: return launch_backward_tiled(c, pd_stride);
+        case Family::wide: return launch_backward_wide(c, pd_stride);
+        default: return launch_backward_generic(c, pd_stride);
+        }
+    });
 }
 
 int kpilqr_backward(kpilqr_ctx *c, const double *lambda, int pd_check_stride, int *status, double *delta_J)
@@ -1396,6 +1443,7 @@ int kpilqr_backward(kpilqr_ctx *c, const double *lambda, int pd_check_stride, in
     if (pd_check_stride < 1) return set_err(c, KPILQR_ERR_ARG, "pd_check_stride must be >= 1");
     { const int rcp = check_complete(c, "kpilqr_backward"); if (rcp) return rcp; }
     if (lambda) KP_HIP(c, hipMemcpyAsync(c->lambda, lambda, (size_t)c->d.batch * 8, hipMemcpyHostToDevice, c->stream));
+    c->retry_attempts = retry_attempts_for(c, lambda, c->d.batch);
     int rc = run_backward(c, pd_check_stride);
     if (rc) return rc;
     if (status) KP_HIP(c, hipMemcpyAsync(status, c->status, (size_t)c->d.batch * 4, hipMemcpyDeviceToHost, c->stream));
@@ -1406,7 +1454,8 @@ int kpilqr_backward(kpilqr_ctx *c, const double *lambda, int pd_check_stride, in
 // Diagnostic (bench's lambda sweep): the backward pass of a fused context in its instrumented form.  hist [batch][6] = number
 // of steps whose (Quu + lambda I)^-1 came from: the third-order Newton-Schulz refresh alone, that plus 1 / 2 / 3 second-order
 // steps, the LDL' factorisation (first step, checked steps, re-seeds), the pivoted slow path.  Gains, delta_J and status
-// are written as by kpilqr_backward.  Uses the lambda already resident.  Synchronous.
+// are written as by kpilqr_backward.  Uses the lambda already resident.  Synchronous.  One sweep whatever kpilqr_set_lambda_retry says:
+// the instrumented kernel has no gate, and the histogram is that of ONE sweep.
 int kpilqr_backward_stats(kpilqr_ctx *c, int pd_check_stride, int *hist)
 {
     if (!c || !hist) return KPILQR_ERR_ARG;
@@ -1432,6 +1481,42 @@ int kpilqr_backward_stats(kpilqr_ctx *c, int pd_check_stride, int *hist)
     KP_HIP(c, launch_backward_fused_stats(c, pd_check_stride, (int *)c->stage.p));
     KP_HIP(c, hipMemcpyAsync(hist, c->stage, bytes, hipMemcpyDeviceToHost, c->stream));
     return sync_and_report(c);
+}
+
+// The lambda retry schedule (include/kpilqr.h, "Lambda retry").  Everything is checked before the context changes; nothing is enqueued.
+int kpilqr_set_lambda_retry(kpilqr_ctx *c, const kpilqr_lambda_retry *sched)
+{
+    if (!c) return KPILQR_ERR_ARG;
+    if (c->is_view) return set_err(c, KPILQR_ERR_ARG, "kpilqr_set_lambda_retry: not through a view of a trajectory range");
+    if (sched) {
+        if (sched->struct_size != sizeof(kpilqr_lambda_retry))
+            return set_err(c, KPILQR_ERR_ARG, "kpilqr_set_lambda_retry: struct_size is not sizeof(kpilqr_lambda_retry) of this library");
+        // (written so that a NaN fails each test)
+        if (!(sched->factor > 1.0) || !(sched->factor <= 1.7976931348623157e308))
+            return set_err(c, KPILQR_ERR_ARG, "kpilqr_set_lambda_retry: factor must be finite and > 1");
+        if (!(sched->max_lambda > 0.0) || !(sched->max_lambda <= 1.7976931348623157e308))
+            return set_err(c, KPILQR_ERR_ARG, "kpilqr_set_lambda_retry: max_lambda must be finite and > 0");
+        if (sched->max_attempts < 1 || sched->max_attempts > 64)
+            return set_err(c, KPILQR_ERR_ARG, "kpilqr_set_lambda_retry: max_attempts must be in 1 .. 64");
+    }
+    // (a streamed iteration in flight has enqueued its attempts already: the new schedule holds from the next call on)
+    c->retry_on = sched != nullptr;
+    c->retry = sched ? *sched : kpilqr_lambda_retry{};
+    c->retry_ran = false;
+    c->retry_attempts = 1;
+    return KPILQR_OK;
+}
+
+int kpilqr_download_lambda_retry(kpilqr_ctx *c, double *lambda_used, int *attempts)
+{
+    if (!c) return KPILQR_ERR_ARG;
+    if (c->is_view) return set_err(c, KPILQR_ERR_ARG, "kpilqr_download_lambda_retry: not through a view of a trajectory range");
+    if (!c->retry_on) return set_err(c, KPILQR_ERR_STATE, "kpilqr_download_lambda_retry: no schedule is set (kpilqr_set_lambda_retry)");
+    if (!c->retry_ran) return set_err(c, KPILQR_ERR_STATE, "kpilqr_download_lambda_retry: no backward sweep has run under the schedule yet");
+    KP_ENTER(c);              // (behind the chunks of a streamed iteration in flight)
+    if (lambda_used) KP_HIP(c, hipMemcpyAsync(lambda_used, c->lambda, (size_t)c->d.batch * 8, hipMemcpyDeviceToHost, c->stream));
+    if (attempts) KP_HIP(c, hipMemcpyAsync(attempts, c->attempts, (size_t)c->d.batch * 4, hipMemcpyDeviceToHost, c->stream));
+    return KPILQR_OK;
 }
 
 int kpilqr_download_gains(kpilqr_ctx *c, double *K, double *k)
@@ -1706,6 +1791,7 @@ int kpilqr_iterate(kpilqr_ctx *c, const double *lambda, int pd_check_stride, con
         if (!c->tiled_a6) { const int rcx = ensure_rx_buffer(c); if (rcx) return rcx; KP_HIP(c, launch_cost_derivs(c)); }      // tiled + flag: l_* are formed inside the sweeps
     }
     else c->last_linearise = union_route(c) ? "kp_union" : "in_sweep";
+    c->retry_attempts = retry_attempts_for(c, lambda, c->d.batch);
     int rc = run_backward(c, pd_check_stride);
     if (rc) return rc;
     return run_forward(c, nullptr);
@@ -1737,6 +1823,7 @@ static void make_view(const kpilqr_ctx *c, int b0, int nb, hipStream_t s, kpilqr
     v->K.shift(o * T * n * m); v->k.shift(o * T * m);
     v->r.shift(o * (T + 1) * nr); v->r_x.shift(o * (T + 1) * nr * n); v->r_u.shift(o * (T + 1) * nr * m);
     v->u_nom.shift(o * T * m); v->lambda.shift(o); v->cost_pred.shift(o * na); v->delta_J.shift(o); v->traj_cost.shift(o); v->status.shift(o);
+    v->attempts.shift(o); v->gate.shift(o);
     v->segmap.shift(o * dof * T); v->kp_offsets.shift(o * dof);
     if (v->segent) v->segent.shift(o * dof * T);
     if (c->kp_traj_first_host) { v->fdk_first = c->kp_traj_first_host[b0]; v->kp_view_entries = c->kp_traj_first_host[b0 + nb] - v->fdk_first; }
@@ -1989,8 +2076,10 @@ static int iterate_streamed(kpilqr_ctx *c, const kpilqr_stream_io *io, const Str
             c->last_linearise = v.last_linearise;
             if (!c->tiled_a6) KP_HIP(c, launch_cost_derivs(&v));
         }
+        v.retry_attempts = retry_attempts_for(c, io->lambda ? io->lambda + o : nullptr, cnt);      // (the chunk's own lambdas decide its attempts)
         rc = of_view(run_backward(&v, pd_check_stride));
         if (rc) return rc;
+        c->retry_ran = v.retry_ran;
         rc = of_view(run_forward(&v, nullptr));
         if (rc) return rc;
         after = v.pay;

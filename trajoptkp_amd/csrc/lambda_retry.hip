@@ -1,0 +1,69 @@
+// lambda_retry.hip -- kpilqr_set_lambda_retry: the device side of retrying a backward sweep whose PD check failed at a raised lambda
+// (the failure branch of iLQR.cpp:435-442 with UpdateLambda, :636-657), without the host.
+//
+// The sweeps themselves do not change: every backward kernel reads lambda[b] once at its top and writes status[b] once at its end.
+// Between two attempts of a call k_lambda_retry looks at the status each trajectory's last sweep left, advances lambda[b] where
+// the schedule allows another sweep and writes gate[b]; the next attempt's kernels leave at their first statement where gate[b] is 0,
+// so a settled trajectory keeps the bits of its successful sweep and one that gave up keeps its failing status.
+//
+//   status == 0                        -> settled:  gate 0
+//   lambda * factor >  max_lambda      -> gives up: gate 0, lambda stays the lambda of the last sweep
+//   otherwise                          -> lambda := lambda * factor, attempts += 1, gate 1
+//
+// lambda * factor is ONE IEEE multiply (the Makefile builds this file without FMA contraction; there is nothing to contract), the
+// comparison is the host loop's: what the caller computes from (status, lambda_used) is what ran here.  One thread per trajectory,
+// plain vector loads and stores; a chunk of a streamed iteration runs it on its own slice (the pointers of a view are shifted).
+#include "common.h"
+
+namespace kpilqr {
+
+#define KPLR_THREADS 256
+
+// before the first attempt of a call: every trajectory is about to run its first sweep
+__global__ void __launch_bounds__(KPLR_THREADS)
+k_lambda_retry_begin(int batch, int *__restrict__ attempts, int *__restrict__ gate)
+{
+    const int b = blockIdx.x * KPLR_THREADS + threadIdx.x;
+    if (b >= batch) return;
+    attempts[b] = 1;
+    gate[b] = 1;
+}
+
+// between two attempts.  A trajectory whose gate is already 0 did not run the last attempt: its status is an earlier sweep's and
+// it stays out.
+__global__ void __launch_bounds__(KPLR_THREADS)
+k_lambda_retry(int batch, double factor, double max_lambda, const int *__restrict__ status, double *__restrict__ lambda,
+               int *__restrict__ attempts, int *__restrict__ gate)
+{
+    const int b = blockIdx.x * KPLR_THREADS + threadIdx.x;
+    if (b >= batch) return;
+    if (gate[b] == 0) return;
+    int again = 0;
+    if (status[b] != 0) {
+        const double next = lambda[b] * factor;
+        if (!(next > max_lambda)) {
+            lambda[b] = next;
+            attempts[b] += 1;
+            again = 1;
+        }
+    }
+    gate[b] = again;
+}
+
+hipError_t launch_lambda_retry_begin(Ctx *c)
+{
+    if (c->d.batch <= 0) return hipSuccess;
+    hipLaunchKernelGGL(k_lambda_retry_begin, dim3((c->d.batch + KPLR_THREADS - 1) / KPLR_THREADS), dim3(KPLR_THREADS), 0, c->stream, c->d.batch,
+                       (int *)c->attempts, (int *)c->gate);
+    return hipGetLastError();
+}
+
+hipError_t launch_lambda_retry(Ctx *c)
+{
+    if (c->d.batch <= 0) return hipSuccess;
+    hipLaunchKernelGGL(k_lambda_retry, dim3((c->d.batch + KPLR_THREADS - 1) / KPLR_THREADS), dim3(KPLR_THREADS), 0, c->stream, c->d.batch,
+                       c->retry.factor, c->retry.max_lambda, (const int *)c->status, (double *)c->lambda, (int *)c->attempts, (int *)c->gate);
+    return hipGetLastError();
+}
+
+}  // namespace kpilqr

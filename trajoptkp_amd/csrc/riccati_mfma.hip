@@ -372,6 +372,29 @@ k_backward_mfma_excl(RecLayout L, int T, const double *__restrict__ rec, const d
     backward_body<N, M, ABL>(L, T, rec, lambda, pd_stride, Kout, kout, delta_J, status);
 }
 
+// The lambda retry twins (kpilqr_set_lambda_retry, lambda_retry.hip): the attempts behind the first of a backward pass under a schedule.
+// A wave whose trajectory is settled or has given up leaves at once; the first attempt, and every launch without a schedule, is one
+// of the two kernels above, unchanged.
+template <int N, int M>
+__global__ void __launch_bounds__(64)
+k_backward_mfma_retry(RecLayout L, int T, const double *__restrict__ rec, const double *__restrict__ lambda,
+                      int pd_stride, double *__restrict__ Kout, double *__restrict__ kout,
+                      double *__restrict__ delta_J, int *__restrict__ status, const int *__restrict__ gate)
+{
+    if (gate[blockIdx.x] == 0) return;
+    backward_body<N, M, 0>(L, T, rec, lambda, pd_stride, Kout, kout, delta_J, status);
+}
+
+template <int N, int M>
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1)))
+k_backward_mfma_excl_retry(RecLayout L, int T, const double *__restrict__ rec, const double *__restrict__ lambda,
+                           int pd_stride, double *__restrict__ Kout, double *__restrict__ kout,
+                           double *__restrict__ delta_J, int *__restrict__ status, const int *__restrict__ gate)
+{
+    if (gate[blockIdx.x] == 0) return;
+    backward_body<N, M, 0>(L, T, rec, lambda, pd_stride, Kout, kout, delta_J, status);
+}
+
 bool backward_mfma_supported(int n, int m)
 {
     return kp_t1_shape(n, m);
@@ -381,6 +404,12 @@ bool backward_mfma_supported(int n, int m)
 template <int NN, int MM>
 static hipError_t launch_bm(Ctx *c, int pd_stride)
 {
+    if (c->bwd_gate) {
+        const auto twin = c->d.batch <= c->n_simd ? k_backward_mfma_excl_retry<NN, MM> : k_backward_mfma_retry<NN, MM>;
+        hipLaunchKernelGGL(twin, dim3(c->d.batch), dim3(64), 0, c->stream, c->L, c->d.T, c->rec, c->lambda, pd_stride, c->K, c->k,
+                           c->delta_J, c->status, c->bwd_gate);
+        return hipGetLastError();
+    }
     const auto kernel = c->d.batch <= c->n_simd ? k_backward_mfma_excl<NN, MM> : k_backward_mfma<NN, MM>;
     hipLaunchKernelGGL(kernel, dim3(c->d.batch), dim3(64), 0, c->stream, c->L, c->d.T, c->rec, c->lambda, pd_stride, c->K, c->k,
                        c->delta_J, c->status);

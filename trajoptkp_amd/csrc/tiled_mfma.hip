@@ -202,12 +202,18 @@ __device__ __forceinline__ d4 ld_Ru(__amdgpu_buffer_rsrc_t rs, int m, int nr, in
 // against 12.5 ms, for 5.0 ms of k_interpolate saved.  Removed in round 5.)
 // NCL > 0: the chunk count of the last row tile at compile time (see k_backward_tiled_uw) and the products of phase BC as
 // interleaved chains; NCL = 0: run-time count, one chain after the other.
-template <int M, int NT, bool A6, int NCL = 0>
+// GATED: the kernel's lambda retry twin (kpilqr_set_lambda_retry, lambda_retry.hip), which runs the attempts BEHIND the first of a
+// backward pass under a schedule.  Its first statement looks at gate[b] -- b the block's trajectory: a scalar load and a branch uniform
+// over the block, before any LDS write or barrier -- and the whole block leaves where the trajectory is settled or has
+// given up.  GATED = false is the kernel of the first attempt and of every launch without a schedule: `gate` is not read, and the
+// instructions are those of a library without the schedule (profiles/lambda_retry.txt has the register counts of both).
+template <int M, int NT, bool A6, int NCL = 0, bool GATED = false>
 __global__ void __launch_bounds__(64 * NT)
 k_backward_tiled_col(RecLayout L, CostSrc CS, int T, const double *__restrict__ rec, const double *__restrict__ lambda,
                      int pd_stride, double *__restrict__ Kout, double *__restrict__ kout,
-                     double *__restrict__ delta_J, int *__restrict__ status)
+                     double *__restrict__ delta_J, int *__restrict__ status, const int *__restrict__ gate)
 {
+    if constexpr (GATED) { if (gate[KP_TILED_TRAJ] == 0) return; }
     extern __shared__ __attribute__((aligned(16))) double sh[];
     constexpr int NCU = (M + 3) / 4;
     constexpr int NZZ = NT * NT;
@@ -680,12 +686,14 @@ bool backward_tiled_supported(int n, int m, int nt_min)
 // step -- starts at the first barrier and not behind the column waves' staging.
 // NCL = 4-row chunks of the last row tile that hold rows of z (compile-time here: a run-time count puts every chunk of the last
 // tile behind its own branch, and the basic blocks that leaves keep the scheduler from interleaving independent MFMA chains).
-template <int M, int NT, int NCL>
+// GATED: as in k_backward_tiled_col; the u-wave leaves with the column waves.
+template <int M, int NT, int NCL, bool GATED = false>
 __global__ void __launch_bounds__(64 * (NT + 1))
 k_backward_tiled_uw(RecLayout L, int T, const double *__restrict__ rec, const double *__restrict__ lambda,
                     int pd_stride, double *__restrict__ Kout, double *__restrict__ kout,
-                    double *__restrict__ delta_J, int *__restrict__ status)
+                    double *__restrict__ delta_J, int *__restrict__ status, const int *__restrict__ gate)
 {
+    if constexpr (GATED) { if (gate[KP_TILED_TRAJ] == 0) return; }
     extern __shared__ __attribute__((aligned(16))) double sh[];
     constexpr int NCU = (M + 3) / 4;
     constexpr int NZZ = NT * NT;
@@ -1078,10 +1086,11 @@ template <int M, int NT, int NCL>
 static hipError_t launch_bt_uw2(Ctx *c, int pd_stride)
 {
     const size_t ldc = backward_col_lds_bytes(NT);
-    hipError_t e = hipFuncSetAttribute((const void *)k_backward_tiled_uw<M, NT, NCL>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldc);
+    const auto kernel = c->bwd_gate ? k_backward_tiled_uw<M, NT, NCL, true> : k_backward_tiled_uw<M, NT, NCL, false>;
+    hipError_t e = hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldc);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((k_backward_tiled_uw<M, NT, NCL>), dim3(c->d.batch), dim3(64 * (NT + 1)), ldc, c->stream, c->L, c->d.T, c->rec,
-                       c->lambda, pd_stride, c->K, c->k, c->delta_J, c->status);
+    hipLaunchKernelGGL(kernel, dim3(c->d.batch), dim3(64 * (NT + 1)), ldc, c->stream, c->L, c->d.T, c->rec,
+                       c->lambda, pd_stride, c->K, c->k, c->delta_J, c->status, c->bwd_gate);
     return hipGetLastError();
 }
 template <int M, int NT>
@@ -1103,11 +1112,12 @@ template <int M, int NT, bool A6, int NCL>
 static hipError_t launch_bt3(Ctx *c, int pd_stride)
 {
     const size_t ldc = backward_col_lds_bytes(NT);
-    hipError_t e = hipFuncSetAttribute((const void *)k_backward_tiled_col<M, NT, A6, NCL>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldc);
+    const auto kernel = c->bwd_gate ? k_backward_tiled_col<M, NT, A6, NCL, true> : k_backward_tiled_col<M, NT, A6, NCL, false>;
+    hipError_t e = hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldc);
     if (e != hipSuccess) return e;
     const CostSrc CS = {c->r, c->r_x, c->r_u, c->w_run, c->w_term, c->d.nr};
-    hipLaunchKernelGGL((k_backward_tiled_col<M, NT, A6, NCL>), dim3(c->d.batch), dim3(64 * NT), ldc, c->stream, c->L, CS, c->d.T, c->rec,
-                       c->lambda, pd_stride, c->K, c->k, c->delta_J, c->status);
+    hipLaunchKernelGGL(kernel, dim3(c->d.batch), dim3(64 * NT), ldc, c->stream, c->L, CS, c->d.T, c->rec,
+                       c->lambda, pd_stride, c->K, c->k, c->delta_J, c->status, c->bwd_gate);
     return hipGetLastError();
 }
 template <int M, int NT, bool A6>

@@ -196,12 +196,18 @@ template <int NT, int MT> struct WideLds {
     static constexpr int Total = DenseInF ? Flags + 8 : Dense + DenseSz;
 };
 
-template <int NT, int MT>
+// GATED: the kernel's lambda retry twin (kpilqr_set_lambda_retry, lambda_retry.hip), which runs the attempts BEHIND the first of a
+// backward pass under a schedule.  Its first statement looks at gate[b] -- b the block's trajectory: a scalar load and a branch uniform
+// over the block, before any LDS write or barrier -- and the whole block leaves where the trajectory is settled or has
+// given up.  GATED = false is the kernel of the first attempt and of every launch without a schedule: `gate` is not read, and the
+// instructions are those of a library without the schedule (profiles/lambda_retry.txt has the register counts of both).
+template <int NT, int MT, bool GATED = false>
 __global__ void __launch_bounds__(64 * NT)
 k_backward_tiled_wide(RecLayout L, int T, const double *__restrict__ rec, const double *__restrict__ lambda,
                       int pd_stride, double *__restrict__ Kout, double *__restrict__ kout,
-                      double *__restrict__ delta_J, int *__restrict__ status)
+                      double *__restrict__ delta_J, int *__restrict__ status, const int *__restrict__ gate)
 {
+    if constexpr (GATED) { if (gate[blockIdx.x] == 0) return; }
     extern __shared__ __attribute__((aligned(16))) double sh[];
     using M_ = WideLds<NT, MT>;
     const int n = L.n, m = L.m, nz = n + 1;
@@ -504,10 +510,11 @@ template <int NT, int MT>
 static hipError_t launch_bw(Ctx *c, int pd_stride)
 {
     const size_t lds = sizeof(double) * (size_t)WideLds<NT, MT>::Total;
-    hipError_t e = hipFuncSetAttribute((const void *)k_backward_tiled_wide<NT, MT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    const auto kernel = c->bwd_gate ? k_backward_tiled_wide<NT, MT, true> : k_backward_tiled_wide<NT, MT, false>;
+    hipError_t e = hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((k_backward_tiled_wide<NT, MT>), dim3(c->d.batch), dim3(64 * NT), lds, c->stream, c->L, c->d.T, c->rec, c->lambda,
-                       pd_stride, c->K, c->k, c->delta_J, c->status);
+    hipLaunchKernelGGL(kernel, dim3(c->d.batch), dim3(64 * NT), lds, c->stream, c->L, c->d.T, c->rec, c->lambda,
+                       pd_stride, c->K, c->k, c->delta_J, c->status, c->bwd_gate);
     return hipGetLastError();
 }
 

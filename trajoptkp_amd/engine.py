@@ -472,6 +472,25 @@ class Engine:
         self.sync()
         return status, dJ
 
+    def set_lambda_retry(self, factor=10.0, max_lambda=10.0, max_attempts=6):
+        """kpilqr_set_lambda_retry: every later backward / iterate / iterate_streamed retries a trajectory whose PD check failed at
+        lambda * factor on the device, until it settles, lambda * factor > max_lambda, or max_attempts sweeps have run (the first
+        included).  set_lambda_retry(None): off, the default."""
+        fn = self._partial("kpilqr_set_lambda_retry")
+        if factor is None:
+            self._ck(fn(self._h, None))
+            return
+        s = _lib.LambdaRetry(C.sizeof(_lib.LambdaRetry), float(factor), float(max_lambda), int(max_attempts))
+        self._ck(fn(self._h, C.byref(s)))
+
+    def lambda_retry(self):
+        """kpilqr_download_lambda_retry -> (lambda_used [batch], attempts [batch]) of the last backward pass under the schedule: the
+        lambda of every trajectory's last sweep (resident: lam=None continues from it) and the number of sweeps it ran."""
+        lam = np.zeros(self.batch); att = np.zeros(self.batch, np.int32)
+        self._ck(self._partial("kpilqr_download_lambda_retry")(self._h, _ptr(lam), _ptr(att)))
+        self.sync()
+        return lam, att
+
     def backward_stats(self, pd_stride=100):
         """kpilqr_backward_stats: the instrumented backward sweep of a fused context -> hist [batch][6] (see include/kpilqr.h)."""
         h = np.zeros((self.batch, 6), np.int32)

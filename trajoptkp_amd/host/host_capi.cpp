@@ -145,10 +145,26 @@ int kpilqr_host_run_acrobot_batch4(int B, int T, int min_N, int max_iter, int mi
 
 // ... and the gain download: gains [1] = trajectories whose K, k came down, summed over the iterations (traffic[1] holds their bytes).
 // "+f32gains" in `method`: K crosses the link as FP32 (iLQR_GPU_Batch::gains_f32)
+int kpilqr_host_run_acrobot_batch6(int B, int T, int min_N, int max_iter, int min_iter, double torque_weight, const double *q0s,
+                                   int fused, const char *method, double *cost_history, int cost_cap, int *iterations, double *U_out, double *stats,
+                                   double *traffic, int traffic_cap, double *inputs, double *gains, double *retry);
 int kpilqr_host_run_acrobot_batch5(int B, int T, int min_N, int max_iter, int min_iter, double torque_weight, const double *q0s,
                                    int fused, const char *method, double *cost_history, int cost_cap, int *iterations, double *U_out, double *stats,
                                    double *traffic, int traffic_cap, double *inputs, double *gains)
 {
+    return kpilqr_host_run_acrobot_batch6(B, T, min_N, max_iter, min_iter, torque_weight, q0s, fused, method, cost_history, cost_cap, iterations, U_out, stats,
+                                          traffic, traffic_cap, inputs, gains, nullptr);
+}
+
+// ... and STEP 2's PD retry: retry [2 + B] = calls of kpilqr_backward, sweeps repeated at a raised lambda (summed over trajectories and
+// iterations), then every trajectory's final lambda.  "+devretry" in `method`: the retry runs on the device (iLQR_GPU_Batch::
+// device_lambda_retry).  "+signedtorque": torque_weight is taken as given, sign included (without it a negative value means "the
+// task's default"): a negative weight makes Q_uu + lambda I fail its PD check at small lambda, which is what exercises the retry.
+int kpilqr_host_run_acrobot_batch6(int B, int T, int min_N, int max_iter, int min_iter, double torque_weight, const double *q0s,
+                                   int fused, const char *method, double *cost_history, int cost_cap, int *iterations, double *U_out, double *stats,
+                                   double *traffic, int traffic_cap, double *inputs, double *gains, double *retry)
+{
+    const bool signed_torque = method && std::string(method).find("+signedtorque") != std::string::npos;
     std::vector<iLQR_GPU_Batch::Problem> probs;
     for (int b = 0; b < B; b++) {
         auto sim = std::make_shared<AcrobotSimulator>(0.01, 8);
@@ -158,7 +174,7 @@ int kpilqr_host_run_acrobot_batch5(int B, int T, int min_N, int max_iter, int mi
         mt->constant_residual_jacobians = mspec.find("+constjac") != std::string::npos;
         if (mspec.find('+') != std::string::npos) mspec = mspec.substr(0, mspec.find('+'));
         if (!mspec.empty()) mt->keypoint_method = mspec;
-        if (torque_weight >= 0) { mt->residual_list[4].weight = torque_weight; mt->residual_list[4].weight_terminal = torque_weight; }
+        if (torque_weight >= 0 || signed_torque) { mt->residual_list[4].weight = torque_weight; mt->residual_list[4].weight_terminal = torque_weight; }
         sim->main_data->qpos[0] = q0s[2 * b]; sim->main_data->qpos[1] = q0s[2 * b + 1];
         *sim->master_reset_data = *sim->main_data;
         probs.push_back({mt, sim, std::make_shared<Differentiator>(mt, sim)});
@@ -167,6 +183,7 @@ int kpilqr_host_run_acrobot_batch5(int B, int T, int min_N, int max_iter, int mi
     if (!opt.ok()) return -2;
     opt.whole_inputs = method && std::string(method).find("+wholeinputs") != std::string::npos;
     opt.gains_f32 = method && std::string(method).find("+f32gains") != std::string::npos;
+    opt.device_lambda_retry = method && std::string(method).find("+devretry") != std::string::npos;
     std::vector<std::vector<MatrixXd>> U0(B, std::vector<MatrixXd>(T, MatrixXd(1, 1)));
     auto U = opt.OptimiseAll(U0, max_iter, min_iter);
     for (int b = 0; b < B; b++) {
@@ -183,6 +200,10 @@ int kpilqr_host_run_acrobot_batch5(int B, int T, int min_N, int max_iter, int mi
     }
     if (inputs) { inputs[0] = (double)opt.residual_bytes_uploaded; inputs[1] = (double)opt.nominal_bytes_uploaded; }
     if (gains) gains[0] = (double)opt.gain_trajectories_fetched;
+    if (retry) {
+        retry[0] = (double)opt.backward_sweeps; retry[1] = (double)opt.lambda_retries;
+        for (int b = 0; b < B; b++) retry[2 + b] = opt.lambda[b];
+    }
     return 0;
 }
 

@@ -341,7 +341,13 @@ std::vector<std::vector<MatrixXd>> iLQR_GPU_Batch::OptimiseAll(const std::vector
     }
     unom_stale.assign(B, 1);                   // (Rollout set every U_old)
     std::vector<double> lam_used(B), pred((size_t)B * alphas.size()), dJ(B);
-    std::vector<int> status(B);
+    std::vector<int> status(B), attempts(B, 1);
+    std::vector<double> lam_dev(B);
+    if (device_lambda_retry) {   // the failure side of the lambda schedule (:435-442, :636-657) on the device instead of the host loop below
+        kpilqr_lambda_retry sched;
+        sched.struct_size = sizeof(sched); sched.factor = lambda_factor; sched.max_lambda = max_lambda; sched.max_attempts = 64;
+        if ((rc = kpilqr_set_lambda_retry(ctx, &sched))) fatal("kpilqr_set_lambda_retry", rc);
+    }
     std::vector<std::vector<MatrixXd>> U_try(alphas.size(), std::vector<MatrixXd>(T, MatrixXd(m, 1)));
     for (int it = 0; it < max_iterations; it++) {
         std::vector<int> active, regen;
@@ -355,10 +361,18 @@ std::vector<std::vector<MatrixXd>> iLQR_GPU_Batch::OptimiseAll(const std::vector
         for (int b = 0; b < B; b++) { lam_used[b] = lambda[b]; if (S[b].done) settled[b] = 1; }
         for (;;) {
             if ((rc = kpilqr_backward(ctx, lam_used.data(), 100, status.data(), dJ.data())) < 0) fatal("kpilqr_backward", rc);
+            backward_sweeps++;
+            if (device_lambda_retry && (rc = kpilqr_download_lambda_retry(ctx, lam_dev.data(), attempts.data()))) fatal("kpilqr_download_lambda_retry", rc);
             if ((rc = kpilqr_sync(ctx))) fatal("kpilqr_sync", rc);
             bool again = false;
             for (int b : active) {
                 if (settled[b]) continue;
+                if (device_lambda_retry) {
+                    // the device has run the failing branch below attempts - 1 times already, with the same multiply: status is that
+                    // of the sweep at lam_dev[b], where the host loop would stand now
+                    lambda_retries += (size_t)(attempts[b] - 1);
+                    lam_used[b] = lambda[b] = lam_dev[b];
+                }
                 const bool ok = status[b] == 0;
                 // UpdateLambda (:636-657)
                 if (!ok) lambda[b] *= lambda_factor; else lambda[b] /= lambda_factor;
@@ -367,7 +381,7 @@ std::vector<std::vector<MatrixXd>> iLQR_GPU_Batch::OptimiseAll(const std::vector
                 if (lambda[b] < min_lambda) lambda[b] = min_lambda;
                 if (ok) { valid[b] = 1; settled[b] = 1; S[b].delta_J = dJ[b]; }     // lam_used[b] stays: reruns reproduce it
                 else if (lambda_exit) { settled[b] = 1; S[b].lambda_exit = true; S[b].done = true; }
-                else { lam_used[b] = lambda[b]; again = true; }
+                else { lam_used[b] = lambda[b]; again = true; lambda_retries++; }
             }
             if (!again) break;
         }

@@ -58,6 +58,13 @@ public:
     // linearisation, as before the partial calls existed -- the A/B of the tests
     bool whole_inputs = false;
     std::vector<int> linearisation_entries;
+    // STEP 2's PD retry on the device (kpilqr_set_lambda_retry with lambda_factor, max_lambda and the ABI's largest attempt count): one
+    // kpilqr_backward, one kpilqr_download_lambda_retry and one sync per iteration instead of a sync and a whole-batch sweep per
+    // retry; lambda[b], valid, lambda_exit and delta_J are rebuilt from (status, lambda_used, attempts) by the code of the host loop.
+    // Off by default: the host loop, call for call as before (kpilqr_set_lambda_retry is only ever called with the option on).
+    bool device_lambda_retry = false;
+    // calls of kpilqr_backward, and sweeps a trajectory repeated at a raised lambda (on either route), since construction
+    size_t backward_sweeps = 0, lambda_retries = 0;
     // regularisation / line search constants (include/Optimiser/Optimiser.h:239-242,259,303)
     double max_lambda = 10.0, min_lambda = 0.0001, lambda_factor = 10, epsConverge = 0.02;
     int num_parallel_rollouts = 6;
