@@ -489,7 +489,10 @@ int  kpilqr_upload_residuals(kpilqr_ctx *ctx, const double *r, const double *r_x
  * the constant mode).  The sweeps that keep the matrix in registers (kpilqr_last_launch: "...:rxc") also keep the constant
  * block l_xx = r_x' W r_x as a resident tile and add l_x = r_x' W r to it with ONE matrix product per step instead of four
  * (version >= 410): the same numbers in another accumulation order -- gains identical, k / delta_J / costs within ~1e-15
- * relative of the per-step form (tests hold 1e-12).  A call that is rejected (bad argument, unpinned buffer) leaves the mode
+ * relative of the per-step form (tests hold 1e-12).  The uniform one-wave backward sweep at n = 14, m = 7 forms Q_uu, Q_ux and
+ * Q_xx from two matrix products on packed tiles instead of three ("...:w1:...:uni"): Q_uu and Q_ux keep their bits for a given value
+ * function, V' moves at rounding level, so K, k, delta_J and the costs agree with the general form and with earlier versions to
+ * ~1e-15 relative, not bit for bit; the two payload kinds still give each other's bits.  A call that is rejected (bad argument, unpinned buffer) leaves the mode
  * as it was.  version >= 400. */
 int  kpilqr_upload_residual_jacobians_const(kpilqr_ctx *ctx, const double *r_x, const double *r_u);
 /* ModelTranslator::CostDerivativesFromResiduals (src/ModelTranslator/ModelTranslator.cpp:552-583)

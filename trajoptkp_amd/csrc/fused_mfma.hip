@@ -477,10 +477,11 @@ __device__ __forceinline__ void backward_fused_body(double *sh, const double *pc
     // (element (n, n), the constant of the value function, is dropped by the sweep anyway).  The terminal step (V = Lzz under the
     // terminal weights, :537-539) keeps the full product.  31.4 matrix instructions per step instead of 34.4, and a chain of four at
     // the top of the step becomes one.  The accumulation order differs from the per-step form's: results agree to ~1e-15, not bit for bit.
+    // (PACKQ, below: the same one product writes v into COLUMN n of the tile instead, see the step.)
     constexpr bool CXX = RXC && !PC;
     d4 Cxx = {0.0, 0.0, 0.0, 0.0}, RxW = Cxx;
-    const double en2 = (c == n) ? 2.0 : 0.0;
-    (void)Cxx; (void)RxW; (void)en2;
+    const double en2 = (c == n) ? 2.0 : 0.0, en1 = (c == n) ? 1.0 : 0.0;
+    (void)Cxx; (void)RxW; (void)en2; (void)en1;
     if constexpr (RXC) {                           // the one r_x of the task: in registers for the whole sweep
         __amdgpu_buffer_rsrc_t rRx = frsrc(F.rx_const, nr * n * 8);
         cur.Rx.x = fbld(rRx, oRx[0]); cur.Rx.y = fbld(rRx, oRx[1]); cur.Rx.z = fbld(rRx, oRx[2]); cur.Rx.w = fbld(rRx, oRx[3]);
@@ -499,6 +500,34 @@ __device__ __forceinline__ void backward_fused_body(double *sh, const double *pc
         cr.a = shift(co2.a, kd * KpU * strideR); cr.al = shift(co2.al, kd * KpU * strideR);      // (the payload's elements are 16 bytes)
         cr.b = shift(co2.b, kd * KpU * strideR); cr.bl = shift(co2.bl, kd * KpU * strideR);
     }
+    // PACKQ (the uniform one-wave sweep at (14,7); n + 1 > 8, m <= 8): the tracker holds the two PACKED operand tiles of the step
+    //     slot a: Y1 = [ Fz cols 0..7 | Fu in cols 8..8+m-1 | 0 ]        slot b: Pk = [ Fu | 0 (cols m..7) | Fz cols 8..n ]
+    // -- lanes 8 .. 8+m-1 walk B column c - 8 (the list of DoF c - 8) in slot a and their own A column in slot b, which sat idle
+    // in them; the per-lane offsets ride in the same load instructions, so a crossing issues no more requests.  The
+    // duplicated B columns are not stored to kpc (cs).  See the products in `step`.
+    constexpr bool PACKQ = UNI && !PC && N == 14 && M == 7;
+    static_assert(!PACKQ || (N + 1 > 8 && M <= 8 && (M + 3) / 4 <= 2), "packed Q tiles: split row 8");
+    ColOffsN cs = cu;                                          // raw sweep: where a differenced column goes in kpc
+    (void)cs;
+    if constexpr (PACKQ) {
+        if (c >= 8) {
+            constexpr int NF4 = 4 * (N / 4);
+            const bool dup = c < 8 + m;
+            const int jb = (c - 8) * KpU;
+            const int b0 = 8 * (2 * N + q), bl0 = (NF4 + q < N) ? 8 * (2 * N + NF4 + q) : BIGOFF;
+            ColOffsN bu, br;
+            bu.a = dup ? b0 + jb * strideB : BIGOFF; bu.al = dup ? shift(bl0, jb * strideB) : BIGOFF;
+            bu.b = cu.a; bu.bl = cu.al;
+            br.a = dup ? 2 * b0 + jb * strideR : BIGOFF; br.al = dup ? shift(dbl_off(bl0), jb * strideR) : BIGOFF;
+            br.b = cr.a; br.bl = cr.al;
+            cs.a = BIGOFF; cs.al = BIGOFF; cs.b = cu.a; cs.bl = cu.al;
+            cu = bu; cr = br;
+        }
+    }
+    const bool lo8 = c < 8;
+    const double dbl8 = lo8 ? 1.0 : 2.0;
+    const u64 mask_hi8 = lo8 ? 0ull : ~0ull;
+    (void)lo8; (void)dbl8; (void)mask_hi8;
     int up = KpU - 1;                                          // UNI: position (in every list) of the current segment's start
     int us = T, unb = T - 1, unb_v = T - 1;                    // UNI: its time, and the time of the next start (uniform; unb_v: as loaded)
     (void)up; (void)us; (void)unb; (void)unb_v; (void)cu; (void)cr;
@@ -586,6 +615,8 @@ __device__ __forceinline__ void backward_fused_body(double *sh, const double *pc
         const unsigned long long cyc_s0 = __builtin_readcyclecounter();
 #endif
         d4 Fz, Fu, Lzz, LU;
+        d4 Y1 = zero;                                  // PACKQ: the packed tile of slot a
+        (void)Y1;
         const bool term = decltype(may_be_first)::value && (t == T - 1);
         bool cross = false;                            // general form: this lane has crossed the start of its segment
         (void)cross;
@@ -646,6 +677,8 @@ __device__ __forceinline__ void backward_fused_body(double *sh, const double *pc
         Fz.z = lerp_nc(sv[2], dt, av[2]); Fz.w = lerp_nc(sv[3], dt, av[3]);
         Fu.x = lerp_nc(sv[4], dt, av[4]); Fu.y = lerp_nc(sv[5], dt, av[5]);
         Fu.z = lerp_nc(sv[6], dt, av[6]); Fu.w = lerp_nc(sv[7], dt, av[7]);
+        Y1 = Fz;                                        // PACKQ: slot a is Y1, slot b (Fu) is Pk; Fz is the per-lane pick
+        if constexpr (PACKQ) { Fz.x = lo8 ? Y1.x : Fu.x; Fz.y = lo8 ? Y1.y : Fu.y; Fz.z = lo8 ? Y1.z : Fu.z; Fz.w = lo8 ? Y1.w : Fu.w; }
         // ---- a6: Lzz, l_uu, l_u from the residuals --------------------------------------------------------
         if constexpr (CXX) {
             if (term) {                                 // (compile-time false away from a sweep's first step)
@@ -656,7 +689,13 @@ __device__ __forceinline__ void backward_fused_body(double *sh, const double *pc
             } else {
                 double p = RxW.x * cur.R1.x;
                 p = __builtin_fma(RxW.y, cur.R1.y, p); p = __builtin_fma(RxW.z, cur.R1.z, p); p = __builtin_fma(RxW.w, cur.R1.w, p);
-                Lzz = MFMA(en2, p, Cxx);
+                if constexpr (PACKQ) {
+                    // packed Q products (below): of row n the merged Qzz tile keeps columns 8.. only, so v goes into COLUMN n instead
+                    // (p as the first operand: D(i, n) = sum_q p(i, q)) -- once in rows 0..7, which are doubled with their block, twice in
+                    // rows 8..; ((2 v) + 0)/2 is exact either way.  Still one product, up here off the Riccati chain.
+                    Lzz = MFMA(p * dbl8, en1, Cxx);
+                }
+                else Lzz = MFMA(en2, p, Cxx);
             }
         } else {
         d4 Rz;
@@ -696,7 +735,7 @@ __device__ __forceinline__ void backward_fused_body(double *sh, const double *pc
         if constexpr (RAW && UNI) {
             // the differenced column of the crossing above (it is the segment's start value now): like the gains it leaves
             // behind the wait for this step's tiles -- in front of it, the wait sat out the stores' acknowledgement
-            if (kst_pos >= 0) { store_col_n<N>(rT, cu, kst_pos * strideB, sv); kst_pos = -1; }
+            if (kst_pos >= 0) { store_col_n<N>(rT, cs, kst_pos * strideB, sv); kst_pos = -1; }
         }
         // (unconditional: a request behind `if (t > 0)` costs a scalar branch per step and makes the compiler's later waits
         // conservative -- in the general form its wait for the crossing's columns drained the tiles; 4.76 -> 4.70 ms in the
@@ -721,17 +760,37 @@ __device__ __forceinline__ void backward_fused_body(double *sh, const double *pc
         // (one wave per trajectory: the regularisation rides in the accumulator's initial value, Qr = (l_uu + lambda I) + Fu'Tu -- nothing
         // downstream wants the un-regularised Quu: V' and delta_J are written on Qr, G and lambda below -- so the adds leave the chain
         // behind the product: 4.15 -> 4.10 ms at B=1024.  The consumer wave of the pair measured 1 % SLOWER with it and keeps the adds.)
-        d4 Tu = PS<NCZ>(V, Fu, zero);
-        d4 Qr = PS<NCZ>(Fu, Tu, PC ? Luu : Luu + LamI);          // Quu (+ lambda I)
+        d4 Qr, Quz, Qzz;
+        if constexpr (PACKQ) {
+            // Quu, Quz and every needed entry of Qzz from TWO products on the packed tiles instead of three (16 matrix instructions
+            // instead of 20): Fu' Tu fills 7 x 7 and Fu' Tz 7 x 15 of a 16 x 16 output, and Qzz is symmetric like the V' it enters.
+            //     T2 = V' Pk = [Tu | 0 | Tz cols 8..n]
+            //     D2 = Pk' T2: rows / cols < m are Quu, rows / cols 8..n are Qzz[8:, 8:], the rest is never read
+            //     D1 = Y1' Tz: rows 0..7 are Qzz[0:8, :], rows 8..8+m-1 are Quz
+            // The split row 8 is a register pair: (.x, .y) <-> (.z, .w) is a renaming.  The accumulators start from the cost terms of
+            // the blocks that are read.  Qr = D2 goes to the refresh as it is: column 7 of Pk is zero, columns 8.. of Qr only make
+            // rows >= 8 of the residual, which NCU = 2 never reads, and the LDL' path reads elements (i, j) < m.
+            const d4 T2 = PS<NCZ>(V, Fu, zero);          // (first: the per-lane pick of Fz lands under it)
+            const d4 Tz = PS<NCZ>(V, Fz, zero);
+            const d4 i2 = {Luu.x + LamI.x, Luu.y + LamI.y, Lzz.z, Lzz.w};
+            const d4 i1 = {Lzz.x, Lzz.y, Luz.x, Luz.y};
+            const d4 D2 = PS<NCZ>(Fu, T2, i2);
+            const d4 D1 = PS<NCZ>(Y1, Tz, i1);
+            Qr = D2;
+            Quz.x = D1.z; Quz.y = D1.w; Quz.z = 0.0; Quz.w = 0.0;
+            Qzz.x = D1.x; Qzz.y = D1.y; Qzz.z = D2.z; Qzz.w = D2.w;          // (merged behind the gains, below)
+        } else {
+        const d4 Tu = PS<NCZ>(V, Fu, zero);
+        Qr = PS<NCZ>(Fu, Tu, PC ? Luu : Luu + LamI);          // Quu (+ lambda I)
         if constexpr (PC) { Qr.x += LamI.x; Qr.y += LamI.y; Qr.z += LamI.z; Qr.w += LamI.w; }
         // ---- Tz, Quz, Qzz --------------------------------------------------------------- :570-579
-        d4 Quz, Qzz;
         if constexpr (PC) {
             Quz = zero; Qzz = zero;                   // the helper wave forms them meanwhile: read behind the refresh
         } else {
             d4 Tz = PS<NCZ>(V, Fz, zero);
             Quz = PS<NCZ>(Fu, Tz, Luz);
             Qzz = PS<NCZ>(Fz, Tz, Lzz);
+        }
         }
 #ifdef KP_CYC
         asm volatile("" :: "v"(Qr.x), "v"(Quz.x), "v"(Qzz.x));
@@ -839,6 +898,13 @@ __device__ __forceinline__ void backward_fused_body(double *sh, const double *pc
         if (NCU > 3) dJ = __builtin_fma(Kp.w, Kp.w, dJ);
         // V' = Qzz + K'Quu K + K'Quz + Quz'K (:606-607) with K = -X, (Quu + lambda I) X = Quz:
         //    = Qzz - X'(Quz + lambda X) = Qzz + K'(Quz - lambda K)   -- one product; G = (Quu + 2 lambda I)K' is never formed
+        if constexpr (PACKQ) {
+            // merged tile for V' = Qm + K'G: the block rows 8..n x cols 0..7 is never computed, its mirror image counts twice (exact)
+            // -- (acc + acc')/2 below gives every entry of V what it was, up to the summation order of that block.  Down here, off the
+            // chain Quu -> inverse -> gains, while the gains' product lands.
+            Qzz.x *= dbl8; Qzz.y *= dbl8;
+            Qzz.z = bits_and(Qzz.z, mask_hi8); Qzz.w = bits_and(Qzz.w, mask_hi8);
+        }
         d4 G;
         G.x = __builtin_fma(-lam, Kp.x, Quz.x); G.y = __builtin_fma(-lam, Kp.y, Quz.y);
         G.z = __builtin_fma(-lam, Kp.z, Quz.z); G.w = __builtin_fma(-lam, Kp.w, Quz.w);
@@ -897,7 +963,12 @@ __device__ __forceinline__ void backward_fused_body(double *sh, const double *pc
 #pragma unroll
                     for (int i = 0; i < 8; i++) pv[i] = fdiv(pv[i] - pm[i], eps2, rinv2);
                 } else {
-                    const bool oa = (pmode & bitA) != 0, ob = (pmode & 4) != 0;
+                    bool oa = (pmode & bitA) != 0, ob = (pmode & 4) != 0;
+                    if constexpr (PACKQ) {
+                        // lanes 8 ..: slot a is the control column of DoF c - 8 (its mode word sits in lane c - 8), slot b the lane's A column
+                        const int m8 = __shfl(pmode, (lane - 8) & 63);
+                        if (!lo8) { ob = oa; oa = (m8 & 4) != 0; }
+                    }
                     const double dA = oa ? 0.5 * eps2 : eps2, rA = oa ? 2.0 * rinv2 : rinv2;     // exact halves / doubles
                     const double dB = ob ? 0.5 * eps2 : eps2, rB = ob ? 2.0 * rinv2 : rinv2;
 #pragma unroll
@@ -913,7 +984,7 @@ __device__ __forceinline__ void backward_fused_body(double *sh, const double *pc
             for (int i = 0; i < 8; i++) { av[i] = fdiv(sv[i] - pv[i], den, rinv); sv[i] = pv[i]; }
             if (c == n) {                                          // Fz(n,n) = 1 rides in the idle lane's constant start value
 #pragma unroll
-                for (int r = 0; r < 4; r++) if (4 * r + q == n) { sv[r] = 1.0; av[r] = 0.0; }
+                for (int r = 0; r < 4; r++) if (4 * r + q == n) { sv[(PACKQ ? 4 : 0) + r] = 1.0; av[(PACKQ ? 4 : 0) + r] = 0.0; }
             }
             const int t_hi = us - 1;
             us = unb;
