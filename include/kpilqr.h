@@ -360,6 +360,47 @@ int  kpilqr_upload_fd_kp(kpilqr_ctx *ctx, const void *slab, int entries, double 
  * kpilqr_upload_fd_kp.  Refers to the CURRENT key-points like the FD payloads; replaces them. */
 int  kpilqr_upload_kp_columns(kpilqr_ctx *ctx, const double *columns, int entries);
 
+/* The key-point columns as FP32: half the bytes of the largest upload a host that differences itself makes every iteration (3n
+ * doubles per entry; Panda reaching at T = 3000, key-points every 5 steps, 4 200 entries: 1.41 MB per trajectory, 0.71 MB as FP32;
+ * the x+ / x- payload is 2.89 MB).  Opt-in: kpilqr_upload_kp_columns / _partial are unchanged.
+ * Contract.  Layout, entry order, kinds, the `entries` rule, the `traj` rules and the "refers to the CURRENT key-points, replaces the
+ * payload" semantics are exactly those of kpilqr_upload_kp_columns / kpilqr_upload_kp_columns_partial: columns32 [entries][3][n] in
+ * CSR entry order, or the listed (= pending) trajectories' entries back to back in `traj` order; kind-2 slots of DoFs >= num_ctrl
+ * are present and ignored.  Rejections are theirs too, before anything is enqueued or the context changes: a NULL context or
+ * pointer, a negative count or `entries` (KPILQR_ERR_ARG), a call before key-points (KPILQR_ERR_STATE), `entries` that is not
+ * kp_offsets[batch*dof] -- or not the pending trajectories' sum --, a `traj` that is not the pending set (KPILQR_ERR_ARG), a resident
+ * payload of the other kind (KPILQR_ERR_STATE); not through a view of kpilqr_iterate_streamed's chunks (KPILQR_ERR_STATE: a view
+ * never allocates).  Pinned / pageable behaviour as kpilqr_upload_fd_kp: the call waits for the stream only when columns32 is
+ * pageable, or when the staging buffer has to grow.
+ * Encoding (the CALLER's side).  A column of A is a unit vector plus O(dt): a plain (float) cast of it spends FP32's 24 bits on the
+ * 1 and moves the gains by up to 2.8e-6 (profiles/columns_f32.txt), past the 1e-6 they are held to.  So the unit entry is REMOVED
+ * before the cast -- the subtraction in double --; for an entry of DoF d, r = 0 .. n-1:
+ *     columns32[e][0][r] = (float)(A(r, d)       - (r == d ? 1 : 0))
+ *     columns32[e][1][r] = (float)(A(r, d + dof) - (r == d + dof ? 1 : 0))
+ *     columns32[e][2][r] = (float) B(r, d)
+ * With that the gains move by at most 2.8e-7 on the measured workloads (same profile), a small multiple of what
+ * kpilqr_download_gains_f32 costs.
+ * Decoding (the LIBRARY's side).  kpc[e][k][r] = (double)columns32[e][k][r], an exact widening, followed by ONE IEEE addition of
+ * 1.0 at the unit row of kinds 0 and 1 (r == d, r == d + dof) and nowhere else.  FP32 subnormals widen exactly, NaN stays NaN,
+ * +-inf stays +-inf, -0 stays -0 off the unit rows.  The column store then holds, bit for bit, what kpilqr_upload_kp_columns
+ * would hold if it were given those decoded doubles, and the context ends in the state that call leaves (payload kind, validity
+ * flags, what a later kpilqr_update_keypoints relocates, what kpilqr_fd_interpolate and the raw and non-raw sweeps read): nothing
+ * downstream knows the difference.
+ * How.  ONE hipMemcpyAsync of the floats into a staging buffer the context owns, then ONE launch of a streaming kernel
+ * (k_kp_columns_f32, columns_f32.hip: a block row per (trajectory, DoF) list of the device CSR, 8-byte loads, 16-byte stores) on the
+ * context's stream.  The partial call widens only the pending trajectories' entry ranges -- those kpilqr_upload_kp_columns_partial
+ * copies into -- however scattered the list is: the kernel reads where each of them starts from the table kpilqr_update_keypoints
+ * left on the device.  kpilqr_last_launch is unchanged (it describes the sweeps and the linearisation).
+ * Memory cost: the staging buffer, entries*3n*4 bytes of device memory, reserved on demand and kept at the largest size asked for
+ * (half the size of the column store; KPILQR_ERR_ALLOC when it cannot be had).  A context that never makes these calls allocates
+ * and launches nothing for them.
+ * Out of scope: the chunk pipeline (kpilqr_stream_io and kpilqr_stream_io2 are fixed structs: a streamed FP32 column route needs a
+ * call of its own); FP32 for the x+ / x- payloads, residuals, residual Jacobians, nominal controls, or inside any sweep; the batch
+ * shim (it uploads x+ / x-); an environment switch.  KPILQR_VERSION is unchanged: detect the calls by their symbols. */
+int  kpilqr_upload_kp_columns_f32(kpilqr_ctx *ctx, const float *columns32 /* [entries][3][n] */, int entries);
+int  kpilqr_upload_kp_columns_f32_partial(kpilqr_ctx *ctx, int count, const int *traj,
+                                          const float *columns32 /* the listed trajectories' entries, back to back */, int entries);
+
 /* One whole iteration for the batch, PIPELINED over chunks of trajectories: chunk c's uploads, its kernels and its
  * downloads run on their own stream, so H2D(c+1), kernels(c) and D2H(c-1) overlap (and so do consecutive calls: nothing
  * here waits for the previous iteration).  Every host pointer must be pinned (kpilqr_host_alloc); NULL inputs keep what

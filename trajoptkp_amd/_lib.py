@@ -33,6 +33,7 @@ SYMBOLS = [
     "kpilqr_upload_residuals_partial", "kpilqr_upload_nominal_partial", "kpilqr_fd_interpolate_partial", "kpilqr_cost_derivs_partial",
     "kpilqr_download_gains_f32", "kpilqr_download_gains_f32_partial", "kpilqr_iterate_streamed2",
     "kpilqr_set_lambda_retry", "kpilqr_download_lambda_retry",
+    "kpilqr_upload_kp_columns_f32", "kpilqr_upload_kp_columns_f32_partial",
 ]
 # entry points added without a version bump (include/kpilqr.h: "detect the entry point by its symbol"): bound only when the library
 # has them -- KPILQR_LIB may name an older build of the same major version
@@ -41,7 +42,8 @@ OPTIONAL_SYMBOLS = {"kpilqr_fd_interpolate", "kpilqr_get_union_keypoints", "kpil
                     "kpilqr_download_gains_partial", "kpilqr_upload_residuals_partial", "kpilqr_upload_nominal_partial",
                     "kpilqr_fd_interpolate_partial", "kpilqr_cost_derivs_partial",
                     "kpilqr_download_gains_f32", "kpilqr_download_gains_f32_partial", "kpilqr_iterate_streamed2",
-                    "kpilqr_set_lambda_retry", "kpilqr_download_lambda_retry"}
+                    "kpilqr_set_lambda_retry", "kpilqr_download_lambda_retry",
+                    "kpilqr_upload_kp_columns_f32", "kpilqr_upload_kp_columns_f32_partial"}
 
 
 class Dims(C.Structure):
@@ -184,6 +186,9 @@ def load():
     if hasattr(L, "kpilqr_set_lambda_retry"):
         L.kpilqr_set_lambda_retry.argtypes = [vp, C.POINTER(LambdaRetry)]
         L.kpilqr_download_lambda_retry.argtypes = [vp, vp, vp]
+    if hasattr(L, "kpilqr_upload_kp_columns_f32"):
+        L.kpilqr_upload_kp_columns_f32.argtypes = [vp, vp, C.c_int]
+        L.kpilqr_upload_kp_columns_f32_partial.argtypes = [vp, C.c_int, vp, vp, C.c_int]
     for s in SYMBOLS:
         if s in OPTIONAL_SYMBOLS and not hasattr(L, s):
             continue

@@ -155,6 +155,7 @@ struct Ctx {
     // i.e. 3n doubles per (trajectory, DoF, key-point) instead of a whole record per (trajectory, step).  The records are
     // allocated on demand when something asks for the materialised sequence (kpilqr_interpolate, get_AB, the error test ...).
     DevBuf<double> kpc;
+    DevBuf<float> kpc32;          // [entries][3][n]: the encoded floats of the last kpilqr_upload_kp_columns_f32[_partial] on their way into kpc (columns_f32.hip); reserved on demand
     // slope store beside kpc (k_kp_slopes): kps [entry][3][n][2] = (column value, (column of the list's next key-point - this column) /
     // (time gap)) pairs, slope 0 for a list's last entry.  Read by the general (per-DoF list) forms of the one-wave sweeps; allocated only when the lists may be
     // ragged (kp_known_uniform: the host has seen that every trajectory's DoFs share one list -- then the device flag says the same
@@ -263,7 +264,7 @@ struct Ctx {
     void for_each_buffer(F f)
     {
         DevMem *const all[] = {&rec, &kp_uniform, &K, &k, &r, &r_x, &r_u, &w_run, &w_term, &u_nom, &ctrl_lim, &lambda, &alphas, &cost_pred,
-                               &delta_J, &traj_cost, &status, &attempts, &gate, &traj_list, &K32, &segmap, &segent, &kp_offsets, &kp_times, &rx_const, &kpc, &kps, &kp_entry,
+                               &delta_J, &traj_cost, &status, &attempts, &gate, &traj_list, &K32, &segmap, &segent, &kp_offsets, &kp_times, &rx_const, &kpc, &kpc32, &kps, &kp_entry,
                                &kp_entry_list, &fdk_dev, &kpu_offsets, &kpu_times, &kpu_src, &kpu_traj_first, &kpcu, &kpu_uniform, &fdk_alt, &kpc_alt, &kp_times_alt, &kp_upl_times, &kp_move, &X_states, &kp_thr, &kp_mask, &kp_count, &ls8, &fd_dev, &err_flag, &stage, &pipe_list};
         for (DevMem *b : all) f(*b);
     }
@@ -342,6 +343,9 @@ hipError_t launch_gains_f32(Ctx *c, const int *traj, int count, float *out);
 // dst [count][row] compact.  K_f32: K rounded to FP32 | K_f64, k_f64: as they are
 enum class GainsForm : int { K_f32, K_f64, k_f64 };
 hipError_t launch_gains_out(const Ctx *c, hipStream_t s, GainsForm form, const int *traj, int first, int count, void *dst_host);
+// columns_f32.hip: the encoded FP32 key-point columns in src (device) decoded into the column store.  upl_first == nullptr: src holds
+// every entry; else upl_first [batch] (device, the third row of Ctx::kp_move): first entry of a listed trajectory inside src, -1: not listed
+hipError_t launch_kp_columns_f32(Ctx *c, const float *src, const int *upl_first);
 // lambda_retry.hip: attempts = 1, gate = 1 for every trajectory | between two attempts: status -> lambda, attempts, gate
 hipError_t launch_lambda_retry_begin(Ctx *c);
 hipError_t launch_lambda_retry(Ctx *c);

@@ -1213,6 +1213,66 @@ int kpilqr_upload_kp_columns_partial(kpilqr_ctx *c, int count, const int *traj, 
     return wait_unless_pinned(c, columns);
 }
 
+// ---- the key-point columns as FP32: half the bytes of the largest upload ---------------------------------------------------------------
+// The encoded floats (include/kpilqr.h: A's unit entry removed before the cast) go with ONE copy into the staging buffer the context
+// owns -- reserved on demand and kept at the largest size asked for, as the float buffer of the gains is -- and ONE launch
+// (columns_f32.hip) widens them into the column store, adding the unit entry back.  The callers have checked everything.
+static int reserve_columns_f32(kpilqr_ctx *c, int entries)
+{
+    const int rc = reserve(c, c->kpc32, (size_t)entries * 3 * c->n * sizeof(float), kExact, false);
+    return rc < 0 ? rc : KPILQR_OK;
+}
+
+static int widen_columns_f32(kpilqr_ctx *c, const float *columns32, int entries, const int *upl_first)
+{
+    if (!entries) return KPILQR_OK;
+    KP_HIP(c, hipMemcpyAsync(c->kpc32, columns32, (size_t)entries * 3 * c->n * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    KP_HIP(c, launch_kp_columns_f32(c, c->kpc32, upl_first));
+    return KPILQR_OK;
+}
+
+int kpilqr_upload_kp_columns_f32(kpilqr_ctx *c, const float *columns32, int entries)
+{
+    if (!c || entries < 0 || (entries > 0 && !columns32)) return KPILQR_ERR_ARG;
+    KP_ENTER(c);
+    if (!c->have_kp) return set_err(c, KPILQR_ERR_STATE, "kpilqr_upload_kp_columns_f32 before the key-points it is ordered by (kpilqr_set_keypoints / kpilqr_generate_keypoints)");
+    if (entries != c->kp_total_host)
+        return set_err(c, KPILQR_ERR_ARG, "kpilqr_upload_kp_columns_f32: `entries` is not the number of key-point entries (kp_offsets[batch*dof])");
+    if (c->is_view) return set_err(c, KPILQR_ERR_STATE, "kpilqr_upload_kp_columns_f32: not through a view of a trajectory range");
+    // both buffers before anything is enqueued or the context changes: the staging buffer first (it alone may fail for a context
+    // whose column store is already there)
+    int rc = reserve_columns_f32(c, entries);
+    if (rc) return rc;
+    rc = ensure_kpc(c);
+    if (rc) return rc;
+    rc = widen_columns_f32(c, columns32, entries, nullptr);
+    if (rc) return rc;
+    c->fd_payload = FdPayload::kp_columns; c->fdk_entries = entries; c->fdk_first = 0;      // (the state kpilqr_upload_kp_columns leaves)
+    payload_changed(c);
+    c->pay.kpc_valid = true;
+    return wait_unless_pinned(c, columns32);
+}
+
+int kpilqr_upload_kp_columns_f32_partial(kpilqr_ctx *c, int count, const int *traj, const float *columns32, int entries)
+{
+    if (entries < 0 || (entries > 0 && !columns32)) return KPILQR_ERR_ARG;
+    { const int go = enter_subset(c, "kpilqr_upload_kp_columns_f32_partial", count, traj, Subset::pending); if (go <= 0) return go; }
+    if (count == 0 && entries == 0 && !c->n_pending) return KPILQR_OK;
+    int rc = check_partial(c, "kpilqr_upload_kp_columns_f32_partial", FdPayload::kp_columns, count, traj, entries);
+    if (rc) return rc;
+    if (c->is_view) return set_err(c, KPILQR_ERR_STATE, "kpilqr_upload_kp_columns_f32_partial: not through a view of a trajectory range");
+    // The pending trajectories' entries inside `columns32` are the third row of the move table kpilqr_update_keypoints left on the
+    // device (check_partial has held traj to exactly that call's list, and nothing else writes the table): the launch reads them
+    // there, so a scattered list costs no copy per run
+    rc = reserve_columns_f32(c, entries);
+    if (rc) return rc;
+    rc = widen_columns_f32(c, columns32, entries, (const int *)c->kp_move + 2 * ((size_t)c->d.batch + 1));
+    if (rc) return rc;
+    payload_changed(c);
+    c->pay.kpc_valid = true;                                 // (the columns ARE the payload)
+    return wait_unless_pinned(c, columns32);
+}
+
 int kpilqr_fd_difference(kpilqr_ctx *c)
 {
     if (!c) return KPILQR_ERR_ARG;

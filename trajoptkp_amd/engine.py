@@ -354,6 +354,23 @@ class Engine:
     def upload_kp_columns(self, s):
         self._ck(self._L.kpilqr_upload_kp_columns(self._h, _ptr(s["cols"]), s["entries"]))
 
+    def upload_kp_columns_f32(self, columns32, traj=None):
+        """kpilqr_upload_kp_columns_f32[_partial]: the key-point columns as FP32, ENCODED as include/kpilqr.h says (A's unit entry
+        removed before the cast: synth.kp_columns_f32) -- float32 [entries][3][n] in CSR entry order, or with traj (the trajectories
+        pending since update_keypoints) their entries back to back.  The library widens them into the FP64 column store."""
+        c32 = np.asarray(columns32)
+        if c32.dtype != np.float32:
+            raise ValueError("columns32 must be a float32 array (no silent rounding here: the encoding is the caller's)")
+        c32 = np.ascontiguousarray(c32)
+        if c32.size % (3 * self.n):
+            raise ValueError(f"columns32 must hold whole entries of 3 * {self.n} floats")
+        ent = c32.size // (3 * self.n)
+        if traj is None:
+            self._ck(self._partial("kpilqr_upload_kp_columns_f32")(self._h, _ptr(c32) if ent else None, ent))
+        else:
+            tr = self._traj(traj)
+            self._ck(self._partial("kpilqr_upload_kp_columns_f32_partial")(self._h, len(tr), _ptr(tr), _ptr(c32) if ent else None, ent))
+
     def upload_fd_slab(self, s, eps=1e-6):
         self._ck(self._L.kpilqr_upload_fd_slab(self._h, _ptr(s["slab"]), s["njobs"], s["nnom"], float(eps)))
 

@@ -51,7 +51,7 @@ int kpilqr_host_run_acrobot(int T, int min_N, int max_iter, int min_iter, const 
                             double torque_weight /* <0: task default 100 */,
                             double *cost_history, int cost_cap, double *U_out, double *K0_out, double *timings_ms)
 {
-    // keypoint_method_name may carry options after a '+': "set_interval+unfused", "set_interval+analytic"
+    // keypoint_method_name may carry options after a '+': "set_interval+unfused", "set_interval+analytic", "set_interval+fused+columns+f32cols"
     std::string spec = keypoint_method_name ? keypoint_method_name : "";
     const std::string keypoint_method_full = spec;
     const bool unfused = spec.find("+unfused") != std::string::npos, fused = spec.find("+fused") != std::string::npos, analytic = spec.find("+analytic") != std::string::npos;
@@ -80,6 +80,10 @@ int kpilqr_host_run_acrobot(int T, int min_N, int max_iter, int min_iter, const 
     if (unfused) opt.SetFused(false);
     if (fused) opt.SetFused(true);
     opt.host_differencing = keypoint_method_full.find("+columns") != std::string::npos;
+    // "+f32cols" (with "+columns"): the columns go up as FP32 (kpilqr_upload_kp_columns_f32); "+hostf32cols": rounded alike, decoded
+    // on the host and uploaded as FP64 -- the run "+f32cols" must reproduce
+    opt.kp_columns_f32 = keypoint_method_full.find("+f32cols") != std::string::npos;
+    opt.kp_columns_f32_on_host = keypoint_method_full.find("+hostf32cols") != std::string::npos;
     if (lowpass || fir) { opt.filteringMethod = lowpass ? "low_pass" : "FIR"; opt.SetFused(false); }
     std::vector<MatrixXd> U0(T, MatrixXd(1, 1));
     std::vector<MatrixXd> U = opt.Optimise(sim->main_data, U0, max_iter, min_iter, T);
@@ -87,10 +91,10 @@ int kpilqr_host_run_acrobot(int T, int min_N, int max_iter, int min_iter, const 
     for (int i = 0; i < nh && i < cost_cap; i++) cost_history[i] = opt.cost_history[i];
     if (U_out) for (int t = 0; t < T; t++) U_out[t] = U[t](0);
     if (K0_out) for (int c = 0; c < 4; c++) K0_out[c] = opt.K[0](0, c);
-    if (timings_ms) {         // [8]: four times, then how the residual Jacobians travelled and whether the last backward sweep kept them in registers
+    if (timings_ms) {         // [8]: four times, then how the residual Jacobians travelled, whether the last backward sweep kept them in registers, and the FD payload bytes uploaded
         timings_ms[0] = opt.avg_time_get_derivs_ms; timings_ms[1] = opt.avg_time_backwards_pass_ms; timings_ms[2] = opt.avg_time_forwards_pass_ms; timings_ms[3] = opt.opt_time_ms;
         timings_ms[4] = opt.constant_jacobian_uploads; timings_ms[5] = opt.per_step_jacobian_uploads;
-        timings_ms[6] = opt.LastLaunch(0).find(":rxc") != std::string::npos ? 1.0 : 0.0; timings_ms[7] = 0.0;
+        timings_ms[6] = opt.LastLaunch(0).find(":rxc") != std::string::npos ? 1.0 : 0.0; timings_ms[7] = (double)opt.payload_bytes_uploaded;
     }
     return opt.num_iterations;
 }

@@ -40,6 +40,8 @@ void iLQR_GPU::free_pinned()
     kp_slab = nullptr; kp_slab_bytes = 0;
     if (kp_cols && ctx) kpilqr_host_free(ctx, kp_cols);
     kp_cols = nullptr; kp_cols_count = 0;
+    if (kp_cols32 && ctx) kpilqr_host_free(ctx, kp_cols32);
+    kp_cols32 = nullptr; kp_cols32_count = 0;
 }
 
 iLQR_GPU::~iLQR_GPU()
@@ -180,25 +182,49 @@ void iLQR_GPU::GenerateDerivatives()
             // a2 on the host: (x+ - x-) / (2 eps), or / eps for a one-sided job (bit `kind` of the entry's mode word), then the
             // columns go up as they are
             const size_t per = (size_t)3 * n, want = (size_t)entries * per;
-            if (want > kp_cols_count) {
+            if (!kp_columns_f32 && want > kp_cols_count) {
                 if (kp_cols) kpilqr_host_free(ctx, kp_cols);
                 kp_cols_count = want + want / 4 + 64;
                 if ((rc = kpilqr_host_alloc(ctx, kp_cols_count * sizeof(double), (void **)&kp_cols))) fatal("kpilqr_host_alloc", rc);
             }
-            for (int e = 0; e < entries; e++) {
+            // kp_columns_f32: the columns cross the link as FP32, encoded as include/kpilqr.h says -- A's unit entry (row d of the
+            // position column, row d + dof of the velocity column) removed in double before the cast -- into a pinned float buffer;
+            // kp_columns_f32_on_host: the same rounding, decoded here and uploaded as FP64 (what the library's decoding must reproduce)
+            const bool round32 = kp_columns_f32 || kp_columns_f32_on_host;
+            if (kp_columns_f32 && want > kp_cols32_count) {
+                if (kp_cols32) kpilqr_host_free(ctx, kp_cols32);
+                kp_cols32_count = want + want / 4 + 64;
+                if ((rc = kpilqr_host_alloc(ctx, kp_cols32_count * sizeof(float), (void **)&kp_cols32))) fatal("kpilqr_host_alloc", rc);
+            }
+            for (int d = 0; d < dof; d++)
+            for (int e = offs[d]; e < offs[d + 1]; e++) {
                 const char *rec = kp_slab + (size_t)e * lay.entry_stride;
                 const char *xp = rec + lay.xplus, *xm = rec + lay.xminus;
                 const int mode = *(const int *)(rec + lay.mode);
                 for (int kind = 0; kind < 3; kind++) {
                     const double den = ((mode >> kind) & 1) ? eps : 2 * eps;
+                    const int unit_row = kind == 0 ? d : kind == 1 ? d + dof : -1;
                     for (int r = 0; r < n; r++) {
-                        const size_t el = ((size_t)kind * n + r) * lay.elem_stride;
-                        kp_cols[(size_t)e * per + (size_t)kind * n + r] = (*(const double *)(xp + el) - *(const double *)(xm + el)) / den;
+                        const size_t el = ((size_t)kind * n + r) * lay.elem_stride, at = (size_t)e * per + (size_t)kind * n + r;
+                        const double v = (*(const double *)(xp + el) - *(const double *)(xm + el)) / den;
+                        if (!round32) { kp_cols[at] = v; continue; }
+                        const float enc = (float)(r == unit_row ? v - 1.0 : v);
+                        if (kp_columns_f32) kp_cols32[at] = enc;
+                        else kp_cols[at] = r == unit_row ? (double)enc + 1.0 : (double)enc;
                     }
                 }
             }
-            if ((rc = kpilqr_upload_kp_columns(ctx, kp_cols, entries))) fatal("kpilqr_upload_kp_columns", rc);
-        } else if ((rc = kpilqr_upload_fd_kp(ctx, kp_slab, entries, eps))) fatal("kpilqr_upload_fd_kp", rc);
+            if (kp_columns_f32) {
+                if ((rc = kpilqr_upload_kp_columns_f32(ctx, kp_cols32, entries))) fatal("kpilqr_upload_kp_columns_f32", rc);
+                payload_bytes_uploaded += want * sizeof(float);
+            } else {
+                if ((rc = kpilqr_upload_kp_columns(ctx, kp_cols, entries))) fatal("kpilqr_upload_kp_columns", rc);
+                payload_bytes_uploaded += want * sizeof(double);
+            }
+        } else {
+            if ((rc = kpilqr_upload_fd_kp(ctx, kp_slab, entries, eps))) fatal("kpilqr_upload_fd_kp", rc);
+            payload_bytes_uploaded += lay.bytes;
+        }
     } else {
     // FD at the key-points on the persistent pool, straight into ONE pinned slab (jobs, nominal rows):
     // the upload is a single DMA and nothing on the host walks the jobs afterwards
@@ -213,6 +239,7 @@ void iLQR_GPU::GenerateDerivatives()
     if (!staging.complete()) { std::fprintf(stderr, "FD staging: %d of %d jobs, %d of %d nominal rows filled\n", staging.njobs, staging.plan_jobs, staging.nnom, staging.plan_noms); std::exit(1); }
     rc = kpilqr_upload_fd_slab(ctx, staging.slab, staging.njobs, staging.nnom, eps);
     if (rc) fatal("kpilqr_upload_fd_slab", rc);
+    { kpilqr_fd_layout jl; if (kpilqr_fd_slab_layout(ctx, staging.njobs, staging.nnom, &jl) == KPILQR_OK) payload_bytes_uploaded += jl.bytes; }
     }
     // a materialising context: A, B of every step in one call (one pass over the records for a key-point ordered payload); the
     // fused sweeps interpolate themselves and want the differenced key-point columns only

@@ -34,6 +34,15 @@ public:
     // Fused sweeps: difference the FD results on the HOST, as the reference does (Differentiator.cpp:166-222,441-457), and
     // upload the key-point columns (kpilqr_upload_kp_columns: half the bytes of x+ / x-, the same gains bit for bit)
     bool host_differencing = false;
+    // With host_differencing: the columns cross the link as FP32 (kpilqr_upload_kp_columns_f32: half the bytes again), written by the
+    // FD loop into a pinned float buffer in the encoding of include/kpilqr.h -- A's unit entry removed, in double, before the cast,
+    // so that FP32's 24 bits go to the O(dt) part of a column: the gains move by a few 1e-8 to 1e-7 (profiles/columns_f32.txt).
+    // Off by default: the reference's bits.  Without host_differencing it means nothing.
+    bool kp_columns_f32 = false;
+    // The same rounding, but decoded on the host and uploaded as FP64 through kpilqr_upload_kp_columns: what the FP32 route must
+    // reproduce bit for bit (tests; telling a precision question from a transport one)
+    bool kp_columns_f32_on_host = false;
+    size_t payload_bytes_uploaded = 0;       // FD payload bytes (x+ / x- records, job slabs or columns) that crossed the link since construction
     // K comes down as FP32 (kpilqr_download_gains_f32: half the bytes of the largest per-iteration download) into a pinned float
     // array and is widened into K[t], which is exact; every element is the round-to-nearest-even cast of the FP64 gain (at most
     // 6e-8 relative, against the 1e-6 the gains are held to).  k stays FP64.  Off by default: the reference's bits.
@@ -88,6 +97,8 @@ private:
     size_t kp_slab_bytes = 0;
     double *kp_cols = nullptr;               // host_differencing: the differenced columns [entries][3][n], pinned
     size_t kp_cols_count = 0;
+    float *kp_cols32 = nullptr;              // kp_columns_f32: the encoded columns as they cross the link, pinned; allocated when the option is first used
+    size_t kp_cols32_count = 0;
     double *host_r = nullptr, *host_rx = nullptr, *host_ru = nullptr, *host_unom = nullptr, *host_K = nullptr, *host_k = nullptr;
     float *host_K32 = nullptr;               // gains_f32: K as it crosses the link, pinned; allocated when the option is first used
     void free_pinned();

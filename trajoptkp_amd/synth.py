@@ -424,6 +424,48 @@ def kp_ordered_payload(p):
     return xp, xm, mode
 
 
+def kp_columns(p):
+    """The key-point columns of a problem differenced on the host, float64 [entries][3][n] in CSR entry order (IEEE quotients:
+    what Engine.kp_columns forms from kp_ordered_payload, without an Engine) -- the payload of kpilqr_upload_kp_columns."""
+    xp, xm, mode = kp_ordered_payload(p)
+    den = np.where((mode.astype(np.int32)[:, None] >> np.arange(3)[None, :]) & 1, float(p["eps"]), 2.0 * float(p["eps"]))
+    return (xp - xm) / den[:, :, None]
+
+
+def kp_entry_dofs(p):
+    """The DoF of every CSR entry of a problem's key-point lists, [entries]."""
+    from .engine import rows_to_dof_csr
+    offs, _ = rows_to_dof_csr(p["kp_rows"], p["dof"], p["T"])
+    return np.repeat(np.arange(p["batch"] * p["dof"]) % p["dof"], np.diff(offs))
+
+
+def _kp_unit_rows(dofs, dof):
+    """Index arrays of the unit elements of the columns of A inside [entries][3][n]: (e, 0, d) and (e, 1, d + dof)."""
+    e = np.arange(len(dofs))
+    return (np.concatenate([e, e]), np.concatenate([np.zeros_like(e), np.ones_like(e)]), np.concatenate([dofs, dofs + dof]))
+
+
+def encode_kp_columns_f32(cols, dofs, dof):
+    """The caller's side of kpilqr_upload_kp_columns_f32 (include/kpilqr.h): float32 [entries][3][n] with the unit entry of A's
+    columns removed, in double, before the cast.  cols: float64 [entries][3][n]; dofs [entries]: the DoF of every entry."""
+    c = np.array(cols, dtype=np.float64)
+    c[_kp_unit_rows(np.asarray(dofs), dof)] -= 1.0
+    with np.errstate(over="ignore"):
+        return c.astype(np.float32)
+
+
+def decode_kp_columns_f32(columns32, dofs, dof):
+    """The library's side restated: the exact widening, then ONE addition of 1.0 at the unit rows of kinds 0 and 1."""
+    c = np.asarray(columns32, dtype=np.float32).astype(np.float64)
+    c[_kp_unit_rows(np.asarray(dofs), dof)] += 1.0
+    return c
+
+
+def kp_columns_f32(p):
+    """The encoded FP32 key-point columns of a problem: the payload of kpilqr_upload_kp_columns_f32 / Engine.upload_kp_columns_f32."""
+    return encode_kp_columns_f32(kp_columns(p), kp_entry_dofs(p), p["dof"])
+
+
 def upload(engine, p, keypoints=True, kp_ordered=False, rx_const=False):
     """Push a problem dict into an Engine (everything the GPU path needs to run one iteration).  kp_ordered: the FD
     payload goes up key-point ordered (kpilqr_upload_fd_kp) instead of as job lists.  rx_const: a problem whose residual
