@@ -27,12 +27,12 @@ def _case_id(c):
             + ("-rxc" if c["rx_const"] else "") + ("" if c["uniform"] else "-ragged") + (f"-{env}" if env else ""))
 
 
-def _problem(c, batch=None, config_id=4):
+def _problem(c, batch=None, config_id=4, min_N=4):
     task = synth.shape_task(c["dof"], c["m"], c["nr"])
     batch = c["batch"] if batch is None else batch
     dense = False if c["rx_const"] else True
     if c["uniform"]:
-        return synth.make_problem(task=task, T=c["T"], batch=batch, min_N=4, dense_residuals=dense, one_sided_frac=0.1,
+        return synth.make_problem(task=task, T=c["T"], batch=batch, min_N=min_N, dense_residuals=dense, one_sided_frac=0.1,
                                   config_id=config_id)
     # per-DoF lists that differ whatever the seed: DoF 0 has key-points at the ends only, the last one splits every interval
     rng = np.random.default_rng(1000 * c["dof"] + c["m"])
@@ -50,7 +50,7 @@ def _set_env(c, monkeypatch):
 def _engine(c, p):
     """The context of case c for problem p (the environment of the case is read at creation: _set_env first)."""
     return Engine(p["dof"], p["m"], p["T"], p["nr"], batch=p["batch"], n_alpha=c["n_alpha"], fused=bool(c["flags"] & S.FLAG_FUSED),
-                  tiled=bool(c["flags"] & S.FLAG_TILED))
+                  tiled=bool(c["flags"] & S.FLAG_TILED), generic=bool(c["flags"] & S.FLAG_GENERIC))
 
 
 def _backward(e, c, p, kp_ordered=False, pd=100):

@@ -64,6 +64,19 @@ def dispatched(path):
     return counts
 
 
+def horizon_residues(n_simd=1024):
+    """Per time loop of tests/_horizons.py: its step group and the residues T mod group, and the horizons below one group, that the
+    cases of tests/_shapes.py and of tests/_horizons.py run it at."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import _horizons as HZ, _shapes as S
+    lines = []
+    for loop, g in sorted(HZ.GROUPS.items()):
+        for name, cs in (("_shapes", [c for c in S.cases(n_simd) if c["why"] != "refused"]), ("_horizons", HZ.cases())):
+            Ts = sorted({c["T"] for c in cs if loop in HZ.loops_of(c, n_simd)})
+            lines.append(f"# loop {loop} (group {g}) {name}: residues {sorted({T % g for T in Ts if T >= g})}, below a group {[T for T in Ts if T < g]}")
+    return lines
+
+
 def main():
     args = [a for a in sys.argv[1:] if not a.startswith("--")]
     before = dispatched(sys.argv[sys.argv.index("--before") + 1]) if "--before" in sys.argv else None
@@ -89,6 +102,7 @@ def main():
     print(f"# {len(syms)} sweep kernels compiled, {n_hit} dispatched by tests/test_gpu_shapes.py"
           + (f", {n_new} of them (NEW) by no other test of the GPU suite" if before is not None else "") + f"; {bad} unexplained")
     print("\n".join(lines))
+    print("\n".join(horizon_residues()))
     return 1 if bad else 0
 
 
