@@ -480,6 +480,46 @@ typedef struct {
 } kpilqr_stream_io2;
 int  kpilqr_iterate_streamed2(kpilqr_ctx *ctx, const kpilqr_stream_io2 *io2, int pd_check_stride, int nchunks);
 
+/* kpilqr_iterate_streamed2 taking the key-point columns as FP32 inside the chunks -- what kpilqr_upload_kp_columns_f32 does for the
+ * explicit call, in the chunk pipeline: a host that differences itself sends half the bytes of its largest upload and keeps the
+ * overlap.  struct_size must be sizeof(kpilqr_stream_io3) as the caller compiled it, and io2.struct_size sizeof(kpilqr_stream_io2),
+ * else KPILQR_ERR_ARG.  `io2` is the struct of kpilqr_iterate_streamed2, every field with the meaning it has there (K32 and gain_traj
+ * combine freely with kp_columns32); with kp_columns32 = NULL the call IS kpilqr_iterate_streamed2 (one implementation, the same
+ * copies and launches in the same order).
+ * The payload.  kp_columns32 is a fourth payload kind beside io.fd_slab, io.fd_kp_slab and io.kp_columns: one payload per iteration,
+ * at most one of the four may be given.  [io2.io.entries][3][n] floats in CSR entry order, io2.io.entries = kp_offsets[batch*dof] as
+ * for io.kp_columns, the lists known to the host as for io.kp_columns (kpilqr_set_keypoints, or kpilqr_get_keypoints after generating
+ * them; else KPILQR_ERR_STATE).  kp_columns32 must be pinned (kpilqr_host_alloc) and is read until the iteration has completed.
+ * Encoding and decoding are, word for word, those of kpilqr_upload_kp_columns_f32: the caller removes A's unit entry before the
+ * cast, the library widens exactly and adds 1.0 at the unit rows of kinds 0 and 1 and nowhere else; kind-2 slots of DoFs >= num_ctrl
+ * are present and ignored.  After the call the context is in the state an iteration with io.kp_columns fed the decoded doubles
+ * leaves (payload kind, validity flags, what a later kpilqr_update_keypoints relocates), and K, k, cost_pred, delta_J and status
+ * are that iteration's bit for bit: nothing downstream knows the difference.
+ * Rejections, all KPILQR_ERR_ARG, all before anything is enqueued or the context is changed (a context in the constant-Jacobian mode
+ * stays in it): ctx = NULL or io3 = NULL; a wrong struct_size, outer or inner; kp_columns32 not pinned; kp_columns32 given together
+ * with another payload; io2.io.entries that is not the number of key-point entries.  The refusals of kpilqr_iterate_streamed2 keep
+ * their codes.
+ * How.  Per chunk, on the chunk's own stream: ONE upload of the chunk's entries*3n floats into its range of the staging buffer of
+ * kpilqr_upload_kp_columns_f32 (by SDMA or by the copy kernel, as KPILQR_PIPE_COPY bit 0 says for every other upload), then ONE
+ * launch of k_kp_columns_f32 over the chunk's lists (columns_f32.hip), which decodes that range into the chunk's range of the
+ * column store; a chunk without entries copies and launches nothing.  The staging buffer is the context's, entries*3n*4 bytes,
+ * reserved before the chunks are cut (KPILQR_ERR_ALLOC when it cannot be had) and kept; a call that has to grow it first orders
+ * itself behind the iteration in flight.  Consecutive calls with unchanged key-points overlap without a wait: a chunk's range of the
+ * staging buffer follows from the key-points alone, so same-stream order protects it from the next call's upload.  The explicit
+ * kpilqr_upload_kp_columns_f32 / _partial share the buffer and order themselves behind a streamed iteration in flight.
+ * Bytes: Panda reaching, T = 3000, key-points every 5 steps: 1.41 MB of columns per trajectory become 0.71 MB; residuals, nominal
+ * controls and the downloads stay and share the link (profiles/streamed_columns_f32.txt holds the byte model and what was measured).
+ * Out of scope: uploads or sweeps of a subset inside the chunks; KPILQR_FLAG_UNION_KEYPOINTS inside the chunks; FP32 for x+ / x-,
+ * residuals, residual Jacobians, u_nom or k, or inside any sweep; the host classes (they do not use the streamed route); any change
+ * to kpilqr_stream_io or kpilqr_stream_io2; an environment switch.  KPILQR_VERSION is unchanged: detect the call by its symbol. */
+typedef struct {
+    size_t struct_size;                         /* sizeof(kpilqr_stream_io3) as the caller compiled it                   */
+    kpilqr_stream_io2 io2;                      /* every field as for kpilqr_iterate_streamed2; io2.struct_size = sizeof(kpilqr_stream_io2) */
+    const float *kp_columns32;                  /* the ENCODED key-point columns of kpilqr_upload_kp_columns_f32,
+                                                   [io2.io.entries][3][n], pinned; NULL: the call is kpilqr_iterate_streamed2 */
+} kpilqr_stream_io3;
+int  kpilqr_iterate_streamed3(kpilqr_ctx *ctx, const kpilqr_stream_io3 *io3, int pd_check_stride, int nchunks);
+
 /* Differencing tail of Differentiator::DynamicsDerivatives (:166-222,286-321,386-423,441-457):
  * writes the key-point columns of A and B. */
 int  kpilqr_fd_difference(kpilqr_ctx *ctx);

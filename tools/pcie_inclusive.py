@@ -16,6 +16,15 @@ key-point ordered payload, three chunks, pipelined; four legs alternating in one
   1 FP64 K through kpilqr_iterate_streamed (the reference of every ratio)      2 K32, whole batch (kpilqr_iterate_streamed2)
   3 K32 of a scattered half of the batch                                         4 FP64 K of the same half
 With KPILQR_LIB naming a library without kpilqr_iterate_streamed2 (a build of an earlier commit) leg 1 alone is timed.
+
+  python tools/pcie_inclusive.py columns [batch] [steps] [rounds]
+
+The key-point columns of a host that differences itself, through the chunk pipeline (profiles/streamed_columns_f32.txt): the same
+workload, residuals and nominal controls uploaded every iteration, three chunks, pipelined; legs alternating in one process --
+  1 FP64 columns through kpilqr_iterate_streamed (kp_cols; the reference of every ratio)
+  2 FP32 columns through kpilqr_iterate_streamed3        3 FP32 columns and K32
+  0 the key-point ordered x+ / x- payload through kpilqr_iterate_streamed, for scale (what bench.py's pcie_inclusive measures)
+With KPILQR_LIB naming a library without kpilqr_iterate_streamed3, legs 0 and 1 alone are timed.
 """
 import sys
 import time
@@ -193,7 +202,83 @@ def measure_gains(B=256, steps=10, rounds=3, T=3000, nchunks=3, quiet=False):
     return dict(batch=B, T=T, steps=steps, rounds=rounds, nchunks=nchunks, rows=rows)
 
 
+def measure_columns(B=256, steps=10, rounds=3, T=3000, nchunks=3, quiet=False):
+    uniq = min(8, B)
+    p = synth.tile_problem(synth.make_problem(task="panda_reaching", T=T, batch=uniq, min_N=5), B // uniq)
+    B = p["batch"]
+    with Engine(p["dof"], p["m"], T, p["nr"], batch=B, fused=True) as e:
+        synth.upload(e, p, kp_ordered=True, rx_const=True)
+        alphas = np.array([(i / 6.0) ** 2 for i in range(1, 7)])
+        r = e.pinned(p["r"].shape); r[...] = p["r"]
+        u_nom = e.pinned(p["u_nom"].shape); u_nom[...] = p["u_nom"]
+        lam = e.pinned(B); lam[:] = p["lam"]
+        payload = synth.kp_ordered_payload(p)
+        slab = e.fd_kp_slab(*payload)
+        cols = e.kp_columns(*payload, eps=p["eps"])
+        E, n = cols["entries"], p["n"]
+        dofs = synth.kp_entry_dofs(p)
+        c32 = e.pinned(E * 3 * n, np.float32)
+        c32[...] = synth.encode_kp_columns_f32(cols["cols"][:E * 3 * n].reshape(E, 3, n), dofs, p["dof"]).reshape(-1)
+        # the yardsticks of the two payloads: the staged path on the FP64 columns, and on the numpy-decoded FP32 ones
+        e.upload_kp_columns(cols); e.iterate(p["lam"], 100, alphas); e.sync()
+        K0, k0 = e.gains()
+        dec = dict(cols=np.ascontiguousarray(synth.decode_kp_columns_f32(np.asarray(c32).reshape(E, 3, n), dofs, p["dof"]).reshape(-1)), entries=E)
+        e.upload_kp_columns(dec); e.iterate(p["lam"], 100, alphas); e.sync()
+        K1, k1 = e.gains()
+        K = e.pinned(K0.shape); k = e.pinned(k0.shape); K32 = e.pinned(K0.shape, np.float32)
+        same_up = r.nbytes + u_nom.nbytes + lam.nbytes
+        col64, col32 = E * 3 * n * 8, E * 3 * n * 4
+        legs = [("0 x+ / x- key-point ordered, FP64 K", e.iterate_streamed, dict(fd_kp=slab, K=K, k=k), slab["layout"].bytes, K.nbytes + k.nbytes),
+                ("1 FP64 columns, kpilqr_iterate_streamed", e.iterate_streamed, dict(kp_cols=cols, K=K, k=k), col64, K.nbytes + k.nbytes)]
+        if hasattr(e._L, "kpilqr_iterate_streamed3"):
+            legs += [("2 FP32 columns, kpilqr_iterate_streamed3", e.iterate_streamed3, dict(kp_cols32=c32, K=K, k=k), col32, K.nbytes + k.nbytes),
+                     ("3 FP32 columns and K32", e.iterate_streamed3, dict(kp_cols32=c32, K32=K32, k=k), col32, K32.nbytes + k.nbytes)]
+
+        def run(fn, kw):
+            fn(eps=p["eps"], r=r, u_nom=u_nom, lam=lam, nchunks=nchunks, **kw)
+
+        def close(k_got, k_want):      # (the :rxc sweeps: K in the bits of the staged path, k to 1e-12 -- as in measure())
+            return np.max(np.abs(k_got - k_want)) <= 1e-12 * np.max(np.abs(k_want))
+
+        for label, fn, kw, _, _ in legs:
+            K[...] = 0; K32[...] = 0
+            run(fn, kw); run(fn, kw)
+            e.sync()
+            if label[0] in "01":
+                assert np.array_equal(K, K0) and close(k, k0), label
+            elif label[0] == "2":
+                assert np.array_equal(K, K1) and close(k, k1), label
+            else:
+                with np.errstate(under="ignore"):
+                    assert np.array_equal(K32, K1.astype(np.float32)) and close(k, k1), label
+        times = [[] for _ in legs]
+        for _ in range(rounds):
+            for i, (_, fn, kw, _, _) in enumerate(legs):
+                t0 = time.perf_counter()
+                for _ in range(steps):
+                    run(fn, kw)
+                e.sync()
+                times[i].append((time.perf_counter() - t0) / steps)
+        moved = float(np.max(np.abs(K1 - K0)) / np.max(np.abs(K0)))
+    rows = []
+    for (label, _, _, up, dn), ts in zip(legs, times):
+        dt = float(np.median(ts))
+        rows.append(dict(leg=label, ms_per_iteration=1e3 * dt, ms_rounds=[round(1e3 * t, 3) for t in ts], traj_it_per_s=B / dt,
+                         h2d_MB_per_traj=(up + same_up) / B / 1e6, d2h_MB_per_traj=dn / B / 1e6, link_GBps=(up + same_up + dn) / dt / 1e9,
+                         rate_vs_leg1=float(np.median(times[1])) / dt))
+    if not quiet:
+        for r_ in rows:
+            print(f"B={B} {r_['leg']:42s}: {r_['ms_per_iteration']:8.2f} ms (rounds {r_['ms_rounds']}) = {r_['traj_it_per_s']:9.1f} traj-it/s  x{r_['rate_vs_leg1']:.3f}"
+                  f"  (H2D {r_['h2d_MB_per_traj']:.3f} MB + D2H {r_['d2h_MB_per_traj']:.3f} MB per trajectory -> {r_['link_GBps']:.1f} GB/s)", flush=True)
+        print(f"B={B} the FP32 transport moves K by {moved:.2e} relative (max |dK| / max |K|, staged path on both payloads)", flush=True)
+    return dict(batch=B, T=T, steps=steps, rounds=rounds, nchunks=nchunks, rows=rows, K_moved_by_f32_columns=moved)
+
+
 if __name__ == "__main__":
+    if len(sys.argv) > 1 and sys.argv[1] == "columns":
+        a = [int(x) for x in sys.argv[2:]]
+        measure_columns(*a)
+        sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "gains":
         a = [int(x) for x in sys.argv[2:]]
         measure_gains(*a)

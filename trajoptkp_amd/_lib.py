@@ -33,7 +33,7 @@ SYMBOLS = [
     "kpilqr_upload_residuals_partial", "kpilqr_upload_nominal_partial", "kpilqr_fd_interpolate_partial", "kpilqr_cost_derivs_partial",
     "kpilqr_download_gains_f32", "kpilqr_download_gains_f32_partial", "kpilqr_iterate_streamed2",
     "kpilqr_set_lambda_retry", "kpilqr_download_lambda_retry",
-    "kpilqr_upload_kp_columns_f32", "kpilqr_upload_kp_columns_f32_partial",
+    "kpilqr_upload_kp_columns_f32", "kpilqr_upload_kp_columns_f32_partial", "kpilqr_iterate_streamed3",
 ]
 # entry points added without a version bump (include/kpilqr.h: "detect the entry point by its symbol"): bound only when the library
 # has them -- KPILQR_LIB may name an older build of the same major version
@@ -43,7 +43,7 @@ OPTIONAL_SYMBOLS = {"kpilqr_fd_interpolate", "kpilqr_get_union_keypoints", "kpil
                     "kpilqr_fd_interpolate_partial", "kpilqr_cost_derivs_partial",
                     "kpilqr_download_gains_f32", "kpilqr_download_gains_f32_partial", "kpilqr_iterate_streamed2",
                     "kpilqr_set_lambda_retry", "kpilqr_download_lambda_retry",
-                    "kpilqr_upload_kp_columns_f32", "kpilqr_upload_kp_columns_f32_partial"}
+                    "kpilqr_upload_kp_columns_f32", "kpilqr_upload_kp_columns_f32_partial", "kpilqr_iterate_streamed3"}
 
 
 class Dims(C.Structure):
@@ -71,6 +71,11 @@ class StreamIO(C.Structure):
 class StreamIO2(C.Structure):
     """kpilqr_stream_io2: StreamIO with K as FP32 and the gains of a list of trajectories; struct_size = sizeof(StreamIO2)"""
     _fields_ = [("struct_size", C.c_size_t), ("io", StreamIO), ("K32", C.c_void_p), ("gain_count", C.c_int), ("gain_traj", C.c_void_p)]
+
+
+class StreamIO3(C.Structure):
+    """kpilqr_stream_io3: StreamIO2 with the key-point columns as ENCODED FP32 for a payload; struct_size = sizeof(StreamIO3)"""
+    _fields_ = [("struct_size", C.c_size_t), ("io2", StreamIO2), ("kp_columns32", C.c_void_p)]
 
 
 class LambdaRetry(C.Structure):
@@ -189,6 +194,8 @@ def load():
     if hasattr(L, "kpilqr_upload_kp_columns_f32"):
         L.kpilqr_upload_kp_columns_f32.argtypes = [vp, vp, C.c_int]
         L.kpilqr_upload_kp_columns_f32_partial.argtypes = [vp, C.c_int, vp, vp, C.c_int]
+    if hasattr(L, "kpilqr_iterate_streamed3"):
+        L.kpilqr_iterate_streamed3.argtypes = [vp, C.POINTER(StreamIO3), C.c_int, C.c_int]
     for s in SYMBOLS:
         if s in OPTIONAL_SYMBOLS and not hasattr(L, s):
             continue

@@ -25,16 +25,16 @@ namespace kpilqr {
 #define KPC32_THREADS 256
 #define KPC32_ITERS 8                                 // pairs a lane decodes per slice: a block's slice is 16 KB in, 32 KB out
 
-// Block (x, y): slices x, x + gridDim.x, ... of lists y, y + gridDim.y, ... of the nlists = batch*dof lists.  ppe = 3n/2 pairs per
-// entry.  upl_first == nullptr: the staging buffer holds every entry, in store order.  Else (the partial call) upl_first [batch] is the
+// Block (x, y): slices x, x + gridDim.x, ... of lists l0 + y, l0 + y + gridDim.y, ... of the lists [l0, l1) (the whole batch: 0,
+// batch*dof; a chunk of a streamed iteration: its trajectories' lists).  ppe = 3n/2 pairs per entry.  upl_first == nullptr: the staging buffer holds every entry, in store order.  Else (the partial call) upl_first [batch] is the
 // third row of Ctx::kp_move as kpilqr_update_keypoints left it: the first entry of trajectory b INSIDE the compact staging buffer,
 // or -1 for a trajectory that is not listed, whose lists are left alone.  Every offset is uniform over the block.
 __global__ void __launch_bounds__(KPC32_THREADS)
-k_kp_columns_f32(int nlists, int dof, int ppe, const int *__restrict__ kp_offsets, const int *__restrict__ upl_first,
+k_kp_columns_f32(int l0, int l1, int dof, int ppe, const int *__restrict__ kp_offsets, const int *__restrict__ upl_first,
                  const float2 *__restrict__ src, double2 *__restrict__ kpc)
 {
     constexpr int slice = KPC32_THREADS * KPC32_ITERS;
-    for (int l = blockIdx.y; l < nlists; l += gridDim.y) {
+    for (int l = l0 + (int)blockIdx.y; l < l1; l += gridDim.y) {
         const int b = l / dof, d = l - b * dof;
         const int e0 = kp_offsets[l];
         long long s0 = e0;                                          // first entry of the list inside the staging buffer
@@ -66,6 +66,19 @@ k_kp_columns_f32(int nlists, int dof, int ppe, const int *__restrict__ kp_offset
     }
 }
 
+// The lists [l0, l1) of the device CSR on stream s; src and upl_first as the kernel reads them.  (l1 - l0 > 0, ppe > 0)
+static hipError_t launch_lists(Ctx *c, hipStream_t s, int l0, int l1, const float *src, const int *upl_first_dev)
+{
+    const int ppe = 3 * c->n / 2, nlists = l1 - l0;
+    constexpr long long slice = (long long)KPC32_THREADS * KPC32_ITERS;
+    // a canonical list has at most T entries; its slices are walked by up to 16 blocks (Panda, T = 3000, key-points every 5 steps: 7 slices)
+    const long long want = ((long long)c->d.T * ppe + slice - 1) / slice;
+    const dim3 grid((unsigned)(want > 16 ? 16 : want), (unsigned)(nlists < 65535 ? nlists : 65535));
+    hipLaunchKernelGGL(k_kp_columns_f32, grid, dim3(KPC32_THREADS), 0, s, l0, l1, c->d.dof, ppe, (const int *)c->kp_offsets,
+                       upl_first_dev, (const float2 *)src, (double2 *)(double *)c->kpc);
+    return hipGetLastError();
+}
+
 // src (device): the encoded floats -- of every entry (upl_first_dev == nullptr), or of the listed trajectories' entries back to back
 // (upl_first_dev [batch]: their first entries inside src, -1 for everybody else) -> the column store, at the lists' own ranges
 hipError_t launch_kp_columns_f32(Ctx *c, const float *src, const int *upl_first_dev)
@@ -74,13 +87,19 @@ hipError_t launch_kp_columns_f32(Ctx *c, const float *src, const int *upl_first_
     const int ppe = 3 * c->n / 2;
     if (nlists <= 0 || ppe == 0) return hipSuccess;
     if (nlists > INT32_MAX) return hipErrorInvalidValue;
-    constexpr long long slice = (long long)KPC32_THREADS * KPC32_ITERS;
-    // a canonical list has at most T entries; its slices are walked by up to 16 blocks (Panda, T = 3000, key-points every 5 steps: 7 slices)
-    const long long want = ((long long)c->d.T * ppe + slice - 1) / slice;
-    const dim3 grid((unsigned)(want > 16 ? 16 : want), (unsigned)(nlists < 65535 ? nlists : 65535));
-    hipLaunchKernelGGL(k_kp_columns_f32, grid, dim3(KPC32_THREADS), 0, c->stream, (int)nlists, c->d.dof, ppe, (const int *)c->kp_offsets,
-                       upl_first_dev, (const float2 *)src, (double2 *)(double *)c->kpc);
-    return hipGetLastError();
+    return launch_lists(c, c->stream, 0, (int)nlists, src, upl_first_dev);
+}
+
+// A chunk of a streamed iteration (kpilqr_iterate_streamed3): the lists [l0, l1) = [b0*dof, b1*dof) of the chunk's trajectories, decoded
+// from `staging` -- the CONTEXT's staging buffer, in store order: the chunk's floats sit at its first entry * 3n, where its one
+// upload put them -- into the same entries of the column store, on the chunk's stream s.  c is the context, never a view: its
+// tables and pointers are the absolute ones.
+hipError_t launch_kp_columns_f32_range(Ctx *c, hipStream_t s, int l0, int l1, const float *staging)
+{
+    const long long nlists = (long long)c->d.batch * c->d.dof;
+    if (l0 < 0 || l1 < l0 || l1 > nlists) return hipErrorInvalidValue;
+    if (l1 == l0 || c->n == 0) return hipSuccess;
+    return launch_lists(c, s, l0, l1, staging, nullptr);
 }
 
 }  // namespace kpilqr

@@ -155,7 +155,7 @@ struct Ctx {
     // i.e. 3n doubles per (trajectory, DoF, key-point) instead of a whole record per (trajectory, step).  The records are
     // allocated on demand when something asks for the materialised sequence (kpilqr_interpolate, get_AB, the error test ...).
     DevBuf<double> kpc;
-    DevBuf<float> kpc32;          // [entries][3][n]: the encoded floats of the last kpilqr_upload_kp_columns_f32[_partial] on their way into kpc (columns_f32.hip); reserved on demand
+    DevBuf<float> kpc32;          // [entries][3][n]: the encoded floats of the last kpilqr_upload_kp_columns_f32[_partial] or kp_columns32 of kpilqr_iterate_streamed3 on their way into kpc (columns_f32.hip); reserved on demand
     // slope store beside kpc (k_kp_slopes): kps [entry][3][n][2] = (column value, (column of the list's next key-point - this column) /
     // (time gap)) pairs, slope 0 for a list's last entry.  Read by the general (per-DoF list) forms of the one-wave sweeps; allocated only when the lists may be
     // ragged (kp_known_uniform: the host has seen that every trajectory's DoFs share one list -- then the device flag says the same
@@ -346,6 +346,9 @@ hipError_t launch_gains_out(const Ctx *c, hipStream_t s, GainsForm form, const i
 // columns_f32.hip: the encoded FP32 key-point columns in src (device) decoded into the column store.  upl_first == nullptr: src holds
 // every entry; else upl_first [batch] (device, the third row of Ctx::kp_move): first entry of a listed trajectory inside src, -1: not listed
 hipError_t launch_kp_columns_f32(Ctx *c, const float *src, const int *upl_first);
+// the same for a chunk of kpilqr_iterate_streamed3: the lists [l0, l1) = [b0*dof, b1*dof) of the CONTEXT's device CSR (c is never a view),
+// decoded on stream s from `staging` (Ctx::kpc32, in store order: a list's floats sit at its first entry * 3n) into the column store
+hipError_t launch_kp_columns_f32_range(Ctx *c, hipStream_t s, int l0, int l1, const float *staging);
 // lambda_retry.hip: attempts = 1, gate = 1 for every trajectory | between two attempts: status -> lambda, attempts, gate
 hipError_t launch_lambda_retry_begin(Ctx *c);
 hipError_t launch_lambda_retry(Ctx *c);

@@ -1923,13 +1923,15 @@ static int pipe_list_bind(kpilqr_ctx *c, const StreamGains &g)
     return KPILQR_OK;
 }
 
-static int iterate_streamed(kpilqr_ctx *c, const kpilqr_stream_io *io, const StreamGains &g, int pd_check_stride, int nchunks)
+// kcols32: what kpilqr_iterate_streamed3 adds -- the ENCODED FP32 key-point columns (kpilqr_upload_kp_columns_f32) as a fourth payload
+// kind; nullptr: the walk of the two earlier calls, which enqueues what it always has.
+static int iterate_streamed(kpilqr_ctx *c, const kpilqr_stream_io *io, const StreamGains &g, int pd_check_stride, int nchunks, const float *kcols32 = nullptr)
 {
     KP_HIP(c, hipSetDevice(c->d.device));
     if (!c->have_kp) return set_err(c, KPILQR_ERR_STATE, "kpilqr_iterate_streamed before kpilqr_set_keypoints");
     if (pd_check_stride < 1) return set_err(c, KPILQR_ERR_ARG, "pd_check_stride must be >= 1");
     // (a whole new payload completes the resident one; without it the pending ranges of kpilqr_update_keypoints would be read)
-    if (!io->fd_slab && !io->fd_kp_slab && !io->kp_columns) {
+    if (!io->fd_slab && !io->fd_kp_slab && !io->kp_columns && !kcols32) {
         if (c->n_pending) { const int rcj = join_pipeline(c); if (rcj) return rcj; }
         const int rcp = check_complete(c, "kpilqr_iterate_streamed without a new payload"); if (rcp) return rcp;
     }
@@ -1938,14 +1940,14 @@ static int iterate_streamed(kpilqr_ctx *c, const kpilqr_stream_io *io, const Str
     if (nchunks > B) nchunks = B;
     if (io->fd_slab && (io->njobs < 1 || !io->traj_job_first || (io->nnom > 0 && !io->traj_nom_first)))
         return set_err(c, KPILQR_ERR_ARG, "streamed FD payload needs the per-trajectory job / nominal-row offsets");
-    if ((io->fd_slab != nullptr) + (io->fd_kp_slab != nullptr) + (io->kp_columns != nullptr) > 1)
-        return set_err(c, KPILQR_ERR_ARG, "one FD payload per iteration: job lists OR key-point ordered OR key-point columns");
-    if (io->fd_kp_slab || io->kp_columns) {
+    if ((io->fd_slab != nullptr) + (io->fd_kp_slab != nullptr) + (io->kp_columns != nullptr) + (kcols32 != nullptr) > 1)
+        return set_err(c, KPILQR_ERR_ARG, "one FD payload per iteration: job lists OR key-point ordered OR key-point columns (FP64 OR FP32)");
+    if (io->fd_kp_slab || io->kp_columns || kcols32) {
         if (!c->kp_traj_first_host || c->kp_total_host < 0)
             return set_err(c, KPILQR_ERR_STATE, "streamed key-point ordered payload: the lists must be known to the host (kpilqr_set_keypoints, or kpilqr_get_keypoints after generating them)");
-        if (io->entries != c->kp_total_host) return set_err(c, KPILQR_ERR_ARG, "fd_kp_slab / kp_columns: `entries` is not the number of key-point entries");
+        if (io->entries != c->kp_total_host) return set_err(c, KPILQR_ERR_ARG, "fd_kp_slab / kp_columns / kp_columns32: `entries` is not the number of key-point entries");
     }
-    const void *hostp[] = {io->kp_columns, io->fd_kp_slab, io->fd_slab, io->r, io->r_x, io->r_u, io->u_nom, io->lambda, io->K, io->k, io->cost_pred, io->delta_J, io->status};
+    const void *hostp[] = {kcols32, io->kp_columns, io->fd_kp_slab, io->fd_slab, io->r, io->r_x, io->r_u, io->u_nom, io->lambda, io->K, io->k, io->cost_pred, io->delta_J, io->status};
     for (const void *p : hostp) if (!is_pinned(p)) return set_err(c, KPILQR_ERR_ARG, "kpilqr_iterate_streamed: host buffers must be pinned (kpilqr_host_alloc)");
     if (g.K32) {
         if (io->K) return set_err(c, KPILQR_ERR_ARG, "kpilqr_iterate_streamed2: io.K and K32 are exclusive");
@@ -2019,18 +2021,30 @@ static int iterate_streamed(kpilqr_ctx *c, const kpilqr_stream_io *io, const Str
         if (rc) return rc;
         c->fdk_entries = io->entries; c->fdk_first = 0; c->eps = io->eps;
     }
+    if (kcols32) {
+        // The staging buffer the chunks upload into (shared with kpilqr_upload_kp_columns_f32[_partial], which join the pipeline on
+        // entry): a chunk's floats land at its trajectories' entry range, which only the key-points decide, so same-stream order
+        // protects it from the next iteration's upload as it does the key-point ordered slab.  A growth frees the old buffer, which nothing
+        // may still read: as for the slabs
+        if (would_grow(c->kpc32, (size_t)io->entries * 3 * n * sizeof(float))) {
+            rc = join_pipeline(c); if (rc) return rc;
+            for (int i = 0; i < Ctx::kPipeStreams; i++) KP_HIP(c, hipStreamSynchronize(c->pipe_stream[i]));
+        }
+        rc = reserve_columns_f32(c, io->entries);
+        if (rc) return rc;
+    }
     const double *kcols = io->kp_columns;
-    const bool new_payload = slab || kslab || kcols;
+    const bool new_payload = slab || kslab || kcols || kcols32;
     if (slab) c->fd_payload = FdPayload::jobs;
     if (kslab) c->fd_payload = FdPayload::kp_ordered;
-    if (kcols) { c->fd_payload = FdPayload::kp_columns; c->fdk_entries = io->entries; c->fdk_first = 0; }
+    if (kcols || kcols32) { c->fd_payload = FdPayload::kp_columns; c->fdk_entries = io->entries; c->fdk_first = 0; }
     if (new_payload) payload_changed(c);
     // allocations and tables the chunks need are made HERE, on the context: a view never allocates (reserve refuses)
     if (c->fused || payload_by_entry(c)) {
         rc = ensure_kpc(c); if (rc) return rc;
         rc = ensure_entry_tables(c); if (rc) return rc;
     }
-    if (!c->fused && (kslab || kcols) && c->tune.fd_interp != 0) { rc = ensure_segent(c); if (rc) return rc; }
+    if (!c->fused && (kslab || kcols || kcols32) && c->tune.fd_interp != 0) { rc = ensure_segent(c); if (rc) return rc; }
     if (c->fused) {
         c->last_linearise = "in_sweep";
         // per-DoF lists: a chunk computes the slopes of ITS entries, whose range only the host copy of the lists gives
@@ -2116,6 +2130,17 @@ static int iterate_streamed(kpilqr_ctx *c, const kpilqr_stream_io *io, const Str
             if (E) KP_HIP(c, h2d(c->kpc + eo, kcols + eo, E * 3 * n * 8, s));
             v.njobs = 0; v.fdk_first = e0; v.fdk_entries = (int)E;
             v.pay.kpc_valid = true;
+        } else if (kcols32) {
+            // the chunk's encoded floats into its range of the staging buffer, widened from there into its range of the column store:
+            // ONE copy, ONE launch (columns_f32.hip; the context's absolute tables), then the view is the FP64 columns' view
+            const int e0 = c->kp_traj_first_host[b0], e1 = c->kp_traj_first_host[b1];
+            const size_t E = (size_t)(e1 - e0), eo = (size_t)e0 * 3 * n;
+            if (E) {
+                KP_HIP(c, h2d(c->kpc32 + eo, kcols32 + eo, E * 3 * n * sizeof(float), s));
+                KP_HIP(c, launch_kp_columns_f32_range(c, s, b0 * c->d.dof, b1 * c->d.dof, c->kpc32));
+            }
+            v.njobs = 0; v.fdk_first = e0; v.fdk_entries = (int)E;
+            v.pay.kpc_valid = true;
         } else {
             // no new FD payload: what was differenced before is reused (kpc / the records' key-point columns)
             v.njobs = 0;
@@ -2180,15 +2205,32 @@ int kpilqr_iterate_streamed(kpilqr_ctx *c, const kpilqr_stream_io *io, int pd_ch
     return iterate_streamed(c, io, StreamGains{}, pd_check_stride, nchunks);
 }
 
+// the checks and the options of a kpilqr_stream_io2, for the two calls that carry one
+static int stream_gains_of(kpilqr_ctx *c, const kpilqr_stream_io2 *io2, StreamGains *g)
+{
+    if (io2->struct_size != sizeof(kpilqr_stream_io2)) return set_err(c, KPILQR_ERR_ARG, "kpilqr_iterate_streamed2: struct_size is not sizeof(kpilqr_stream_io2) of this library");
+    if (io2->gain_count < 0 || (io2->gain_count > 0 && !io2->gain_traj)) return set_err(c, KPILQR_ERR_ARG, "kpilqr_iterate_streamed2: gain_count < 0, or listed trajectories without gain_traj");
+    g->K32 = io2->K32;
+    g->listed = io2->gain_traj != nullptr; g->count = io2->gain_count; g->traj = io2->gain_traj;
+    return KPILQR_OK;
+}
+
 int kpilqr_iterate_streamed2(kpilqr_ctx *c, const kpilqr_stream_io2 *io2, int pd_check_stride, int nchunks)
 {
     if (!c || !io2) return KPILQR_ERR_ARG;
-    if (io2->struct_size != sizeof(kpilqr_stream_io2)) return set_err(c, KPILQR_ERR_ARG, "kpilqr_iterate_streamed2: struct_size is not sizeof(kpilqr_stream_io2) of this library");
-    if (io2->gain_count < 0 || (io2->gain_count > 0 && !io2->gain_traj)) return set_err(c, KPILQR_ERR_ARG, "kpilqr_iterate_streamed2: gain_count < 0, or listed trajectories without gain_traj");
     StreamGains g;
-    g.K32 = io2->K32;
-    g.listed = io2->gain_traj != nullptr; g.count = io2->gain_count; g.traj = io2->gain_traj;
+    if (const int rc = stream_gains_of(c, io2, &g)) return rc;
     return iterate_streamed(c, &io2->io, g, pd_check_stride, nchunks);
+}
+
+// kpilqr_iterate_streamed2 with the key-point columns as ENCODED FP32 for a payload: with kp_columns32 == NULL it IS that call
+int kpilqr_iterate_streamed3(kpilqr_ctx *c, const kpilqr_stream_io3 *io3, int pd_check_stride, int nchunks)
+{
+    if (!c || !io3) return KPILQR_ERR_ARG;
+    if (io3->struct_size != sizeof(kpilqr_stream_io3)) return set_err(c, KPILQR_ERR_ARG, "kpilqr_iterate_streamed3: struct_size is not sizeof(kpilqr_stream_io3) of this library");
+    StreamGains g;
+    if (const int rc = stream_gains_of(c, &io3->io2, &g)) return rc;
+    return iterate_streamed(c, &io3->io2.io, g, pd_check_stride, nchunks, io3->kp_columns32);
 }
 
 // ---- multi-GPU: the line-search cost reduction -----------------------------------------------------------

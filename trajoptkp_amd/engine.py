@@ -380,9 +380,30 @@ class Engine:
         K32 (np.float32, pinned; instead of K): K comes down rounded to FP32.  gain_traj (any int sequence, strictly increasing): K / K32
         / k of those trajectories alone, compact in list order ([]: no gains come down).  Either one takes kpilqr_iterate_streamed2;
         with neither the call is the one it always was."""
-        io2 = None
-        if K32 is not None or gain_traj is not None:
-            io2 = _lib.StreamIO2()
+        self._iterate_streamed(fd, fd_kp, kp_cols, eps, r, r_x, r_u, u_nom, lam, K, k, cost_pred, delta_J, status, pd_stride, nchunks,
+                               K32, gain_traj, None)
+
+    def iterate_streamed3(self, fd=None, fd_kp=None, kp_cols=None, eps=1e-6, r=None, r_x=None, r_u=None, u_nom=None, lam=None, K=None, k=None,
+                          cost_pred=None, delta_J=None, status=None, pd_stride=100, nchunks=0, K32=None, gain_traj=None, kp_cols32=None):
+        """kpilqr_iterate_streamed3: iterate_streamed with kp_cols32 -- the key-point columns as FP32, ENCODED as include/kpilqr.h says
+        (synth.kp_columns_f32), a pinned float32 array [entries][3][n] -- for the payload, instead of fd / fd_kp / kp_cols.  Always takes
+        the new entry point (with kp_cols32=None that call is kpilqr_iterate_streamed2)."""
+        if kp_cols32 is not None:
+            if kp_cols32.dtype != np.float32:
+                raise ValueError("kp_cols32 must be a float32 array (no silent rounding here: the encoding is the caller's)")
+            if kp_cols32.size % (3 * self.n):
+                raise ValueError(f"kp_cols32 must hold whole entries of 3 * {self.n} floats")
+        io3 = _lib.StreamIO3()
+        io3.struct_size = C.sizeof(_lib.StreamIO3)
+        self._iterate_streamed(fd, fd_kp, kp_cols, eps, r, r_x, r_u, u_nom, lam, K, k, cost_pred, delta_J, status, pd_stride, nchunks,
+                               K32, gain_traj, io3, kp_cols32)
+
+    def _iterate_streamed(self, fd, fd_kp, kp_cols, eps, r, r_x, r_u, u_nom, lam, K, k, cost_pred, delta_J, status, pd_stride, nchunks,
+                          K32, gain_traj, io3, kp_cols32=None):
+        io2 = None if io3 is None else io3.io2
+        if io2 is not None or K32 is not None or gain_traj is not None:
+            if io2 is None:
+                io2 = _lib.StreamIO2()
             io2.struct_size = C.sizeof(_lib.StreamIO2)
             if K32 is not None:
                 if K32.dtype != np.float32:
@@ -401,12 +422,16 @@ class Engine:
             io.fd_kp_slab = fd_kp["slab"].ctypes.data; io.entries = fd_kp["entries"]
         if kp_cols is not None:
             io.kp_columns = kp_cols["cols"].ctypes.data; io.entries = kp_cols["entries"]
+        if kp_cols32 is not None:
+            io3.kp_columns32 = kp_cols32.ctypes.data; io.entries = kp_cols32.size // (3 * self.n)
         io.eps = float(eps)
         for name, a in (("r", r), ("r_x", r_x), ("r_u", r_u), ("u_nom", u_nom), ("lam", lam), ("K", K), ("k", k),
                         ("cost_pred", cost_pred), ("delta_J", delta_J), ("status", status)):
             if a is not None:
                 setattr(io, name, a.ctypes.data)
-        if io2 is None:
+        if io3 is not None:
+            self._ck(self._partial("kpilqr_iterate_streamed3")(self._h, C.byref(io3), int(pd_stride), int(nchunks)))
+        elif io2 is None:
             self._ck(self._L.kpilqr_iterate_streamed(self._h, C.byref(io), int(pd_stride), int(nchunks)))
         else:
             self._ck(self._partial("kpilqr_iterate_streamed2")(self._h, C.byref(io2), int(pd_stride), int(nchunks)))
