@@ -467,8 +467,8 @@ int  kpilqr_iterate_streamed(kpilqr_ctx *ctx, const kpilqr_stream_io *io, int pd
  * Bytes: Panda reaching, T = 3000: 2.52 MB of gains per trajectory become 1.34 MB with K32, and proportionally fewer with a list;
  * uploads stay and share the link, so the rate gains less: measured once at B = 1024, three chunks, against the FP64 call in the same
  * process, 1.10x with K32, 1.22x with K32 of a scattered half of the batch, 1.17x with FP64 K of that half (profiles/streamed_gains.txt).
- * Out of scope: FP32 for k, for any upload or inside any sweep; uploads or sweeps of a subset inside the chunks;
- * KPILQR_FLAG_UNION_KEYPOINTS inside the chunks.  KPILQR_VERSION is unchanged: detect the call by its symbol. */
+ * Out of scope: FP32 for k, for any upload or inside any sweep; uploads or sweeps of a subset inside the chunks
+ * (kpilqr_iterate_streamed4 has since added the uploads); KPILQR_FLAG_UNION_KEYPOINTS inside the chunks.  KPILQR_VERSION is unchanged: detect the call by its symbol. */
 typedef struct {
     size_t struct_size;                         /* sizeof(kpilqr_stream_io2) as the caller compiled it                   */
     kpilqr_stream_io io;                        /* every field with the meaning it has for kpilqr_iterate_streamed       */
@@ -511,7 +511,8 @@ int  kpilqr_iterate_streamed2(kpilqr_ctx *ctx, const kpilqr_stream_io2 *io2, int
  * controls and the downloads stay and share the link (profiles/streamed_columns_f32.txt holds the byte model and what was measured).
  * Out of scope: uploads or sweeps of a subset inside the chunks; KPILQR_FLAG_UNION_KEYPOINTS inside the chunks; FP32 for x+ / x-,
  * residuals, residual Jacobians, u_nom or k, or inside any sweep; the host classes (they do not use the streamed route); any change
- * to kpilqr_stream_io or kpilqr_stream_io2; an environment switch.  KPILQR_VERSION is unchanged: detect the call by its symbol. */
+ * to kpilqr_stream_io or kpilqr_stream_io2; an environment switch.  KPILQR_VERSION is unchanged: detect the call by its symbol.
+ * (Uploads of a subset inside the chunks have since arrived as kpilqr_iterate_streamed4, below; its sweeps still cover every trajectory.) */
 typedef struct {
     size_t struct_size;                         /* sizeof(kpilqr_stream_io3) as the caller compiled it                   */
     kpilqr_stream_io2 io2;                      /* every field as for kpilqr_iterate_streamed2; io2.struct_size = sizeof(kpilqr_stream_io2) */
@@ -519,6 +520,69 @@ typedef struct {
                                                    [io2.io.entries][3][n], pinned; NULL: the call is kpilqr_iterate_streamed2 */
 } kpilqr_stream_io3;
 int  kpilqr_iterate_streamed3(kpilqr_ctx *ctx, const kpilqr_stream_io3 *io3, int pd_check_stride, int nchunks);
+
+/* kpilqr_iterate_streamed3 uploading the inputs of a LISTED SUBSET of the batch inside the chunks -- what kpilqr_update_keypoints,
+ * kpilqr_upload_*_partial do for the explicit calls, in the chunk pipeline: a host that re-linearises only the trajectories whose
+ * last step was accepted (src/Optimiser/iLQR.cpp:419) sends their inputs alone and keeps the overlap; everybody else repeats the
+ * backward pass at a new lambda on the derivatives that are resident.  struct_size must be sizeof(kpilqr_stream_io4) as the caller
+ * compiled it, io3.struct_size sizeof(kpilqr_stream_io3) and io3.io2.struct_size sizeof(kpilqr_stream_io2), else KPILQR_ERR_ARG.
+ * `io3` is the struct of kpilqr_iterate_streamed3, every field with the meaning it has there; with upload_traj = NULL the call IS
+ * kpilqr_iterate_streamed3 (one implementation, the same copies and launches in the same order; upload_count is then ignored
+ * unless it is > 0, which is refused).
+ * The list.  upload_traj [upload_count] is strictly increasing and within [0, batch) (the rules of kpilqr_download_gains_partial and
+ * gain_traj); it is read during the call only and may be pageable; it is independent of gain_traj.
+ * Compact inputs.  io.r [count][T+1][nr], io.r_x [count][T+1][nr][n], io.r_u [count][T+1][nr][m], io.u_nom [count][T][m]: the listed
+ * trajectories' rows back to back in list order; a NULL pointer keeps what is resident; all pinned as before.  The payload: at most
+ * one of io.fd_kp_slab, io.kp_columns, io3.kp_columns32 may be given; it holds the records / columns / encoded floats of the listed
+ * trajectories' CSR entries back to back in list order, io.entries is the sum of their entry counts under the CURRENT lists, the
+ * lists must be known to the host as for the by-entry payloads of the older calls, and the encoding of kp_columns32 is unchanged.
+ * io.lambda stays [batch]: lambda changes for everybody.  All outputs keep their meaning, whole batch or gain_traj.
+ * upload_count = 0 with a list: no input but lambda is copied; the sweeps and downloads run on what is resident.
+ * Results and state afterwards are those of a kpilqr_iterate_streamed3 given whole-batch arrays that hold the resident bytes with the
+ * listed rows / entries replaced: K, k, cost_pred, delta_J and status bit for bit, and the same payload kind, validity flags, what
+ * a later kpilqr_update_keypoints relocates, and kpilqr_last_launch strings.  The sweeps, and on a context with records the
+ * linearisation, still run over every trajectory of every chunk.
+ * Changed key-points.  The caller first calls kpilqr_update_keypoints for the trajectories whose lists changed (an ordinary call: it
+ * orders itself behind the pipeline), which leaves their ranges pending.  A streamed4 call whose payload list contains every
+ * pending trajectory completes them -- a superset is fine -- and after it nothing is pending.  A list that misses a pending
+ * trajectory is KPILQR_ERR_STATE naming it.
+ * Rejections, all before anything is enqueued or the context is changed (a context in the constant-Jacobian mode stays in it).
+ * KPILQR_ERR_ARG: ctx = NULL or io4 = NULL; a wrong struct_size, outer or inner; upload_count < 0; upload_count > 0 with a NULL list;
+ * a list that is not strictly increasing or leaves the range; io.fd_slab together with a list (job lists carry their own
+ * trajectory indices: out of scope); io.entries that is not the listed sum; io.eps that differs from the resident key-point
+ * ordered payload's (a context has one eps, as for kpilqr_upload_fd_kp_partial).  KPILQR_ERR_STATE: a payload with a list while the
+ * context holds no complete resident payload of the same kind for the trajectories not listed (kp_columns32 counts as the column
+ * kind); r_x with a list in the constant-Jacobian mode, or before a whole r_x upload; r_u with a list before a whole r_u upload or
+ * broadcast -- the refusals of kpilqr_upload_residuals_partial, in its words.  Every refusal of the older calls keeps its code.
+ * How.  Per chunk and per array that is given, on the chunk's own stream: ONE upload of the chunk's compact slice -- the list
+ * increases and chunks are contiguous ranges, so a chunk's share is one slice of the list and one contiguous range of each compact
+ * input -- into a device staging region (by SDMA or by the copy kernel, as KPILQR_PIPE_COPY bit 0 says for every other upload), then
+ * ONE launch of k_rows_in (rows_in.hip) that moves the rows device-to-device from staging to their trajectories' places; for the
+ * by-entry payloads a row is the trajectory's entry range.  kp_columns32: one upload of the slice's floats, then k_kp_columns_f32
+ * decoding straight into the listed trajectories' ranges of the column store, no FP64 intermediate.  A chunk without listed
+ * trajectories copies and launches nothing for the inputs beyond lambda.
+ * Overlap.  Two consecutive calls with DIFFERENT lists overlap like calls with equal lists: a staging region is addressed by the
+ * chunk (its first trajectory), not by the list, so same-stream order protects it; the list's pinned mirror and device copy are a
+ * ring of four, and a slot is written again behind the chunks that read it four calls earlier, never behind the iteration in flight.
+ * Memory: staging as large as the whole-batch form of each input kind that was ever given with a list (r, r_x, r_u, u_nom, the
+ * by-entry payload; kp_columns32 uses the staging buffer of kpilqr_upload_kp_columns_f32), reserved on the context before the
+ * chunks are cut (KPILQR_ERR_ALLOC when it cannot be had) and kept, plus 8 ints per trajectory for the ring; a call that has to grow
+ * a region first orders itself behind the iteration in flight.  A context that never passes a list allocates and launches nothing
+ * new.
+ * Bytes (a model): with a fraction f of the batch listed the upload of an iteration shrinks to f of itself plus lambda; the gains
+ * still come down for everybody.  Panda reaching, T = 3000: 1.41 MB (columns) or 2.89 MB (x+-) of payload, 0.34 MB of r and 0.17 MB
+ * of u_nom per trajectory, 4.7 MB of r_x with per-step Jacobians -- none of which crosses the link for a kept trajectory
+ * (profiles/streamed_subset_uploads.txt).
+ * Out of scope: sweeps or linearisation of a subset; job-list payloads (io.fd_slab) with a list; KPILQR_FLAG_UNION_KEYPOINTS inside
+ * the chunks; the host classes and the batch shim (they do not use the streamed route); any change to kpilqr_stream_io, _io2 or
+ * _io3; an environment switch.  KPILQR_VERSION is unchanged: detect the call by its symbol. */
+typedef struct {
+    size_t struct_size;                         /* sizeof(kpilqr_stream_io4) as the caller compiled it                   */
+    kpilqr_stream_io3 io3;                      /* every field as for kpilqr_iterate_streamed3 (inner struct_sizes checked as there) */
+    int upload_count;                           /* with upload_traj: number of listed trajectories                       */
+    const int *upload_traj;                     /* NULL: whole-batch inputs, the call IS kpilqr_iterate_streamed3        */
+} kpilqr_stream_io4;
+int  kpilqr_iterate_streamed4(kpilqr_ctx *ctx, const kpilqr_stream_io4 *io4, int pd_check_stride, int nchunks);
 
 /* Differencing tail of Differentiator::DynamicsDerivatives (:166-222,286-321,386-423,441-457):
  * writes the key-point columns of A and B. */

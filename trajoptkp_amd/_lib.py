@@ -33,7 +33,7 @@ SYMBOLS = [
     "kpilqr_upload_residuals_partial", "kpilqr_upload_nominal_partial", "kpilqr_fd_interpolate_partial", "kpilqr_cost_derivs_partial",
     "kpilqr_download_gains_f32", "kpilqr_download_gains_f32_partial", "kpilqr_iterate_streamed2",
     "kpilqr_set_lambda_retry", "kpilqr_download_lambda_retry",
-    "kpilqr_upload_kp_columns_f32", "kpilqr_upload_kp_columns_f32_partial", "kpilqr_iterate_streamed3",
+    "kpilqr_upload_kp_columns_f32", "kpilqr_upload_kp_columns_f32_partial", "kpilqr_iterate_streamed3", "kpilqr_iterate_streamed4",
 ]
 # entry points added without a version bump (include/kpilqr.h: "detect the entry point by its symbol"): bound only when the library
 # has them -- KPILQR_LIB may name an older build of the same major version
@@ -43,7 +43,8 @@ OPTIONAL_SYMBOLS = {"kpilqr_fd_interpolate", "kpilqr_get_union_keypoints", "kpil
                     "kpilqr_fd_interpolate_partial", "kpilqr_cost_derivs_partial",
                     "kpilqr_download_gains_f32", "kpilqr_download_gains_f32_partial", "kpilqr_iterate_streamed2",
                     "kpilqr_set_lambda_retry", "kpilqr_download_lambda_retry",
-                    "kpilqr_upload_kp_columns_f32", "kpilqr_upload_kp_columns_f32_partial", "kpilqr_iterate_streamed3"}
+                    "kpilqr_upload_kp_columns_f32", "kpilqr_upload_kp_columns_f32_partial", "kpilqr_iterate_streamed3",
+                    "kpilqr_iterate_streamed4"}
 
 
 class Dims(C.Structure):
@@ -76,6 +77,11 @@ class StreamIO2(C.Structure):
 class StreamIO3(C.Structure):
     """kpilqr_stream_io3: StreamIO2 with the key-point columns as ENCODED FP32 for a payload; struct_size = sizeof(StreamIO3)"""
     _fields_ = [("struct_size", C.c_size_t), ("io2", StreamIO2), ("kp_columns32", C.c_void_p)]
+
+
+class StreamIO4(C.Structure):
+    """kpilqr_stream_io4: StreamIO3 with the list of trajectories whose inputs come up; struct_size = sizeof(StreamIO4)"""
+    _fields_ = [("struct_size", C.c_size_t), ("io3", StreamIO3), ("upload_count", C.c_int), ("upload_traj", C.c_void_p)]
 
 
 class LambdaRetry(C.Structure):
@@ -196,6 +202,8 @@ def load():
         L.kpilqr_upload_kp_columns_f32_partial.argtypes = [vp, C.c_int, vp, vp, C.c_int]
     if hasattr(L, "kpilqr_iterate_streamed3"):
         L.kpilqr_iterate_streamed3.argtypes = [vp, C.POINTER(StreamIO3), C.c_int, C.c_int]
+    if hasattr(L, "kpilqr_iterate_streamed4"):
+        L.kpilqr_iterate_streamed4.argtypes = [vp, C.POINTER(StreamIO4), C.c_int, C.c_int]
     for s in SYMBOLS:
         if s in OPTIONAL_SYMBOLS and not hasattr(L, s):
             continue

@@ -94,12 +94,15 @@ hipError_t launch_kp_columns_f32(Ctx *c, const float *src, const int *upl_first_
 // from `staging` -- the CONTEXT's staging buffer, in store order: the chunk's floats sit at its first entry * 3n, where its one
 // upload put them -- into the same entries of the column store, on the chunk's stream s.  c is the context, never a view: its
 // tables and pointers are the absolute ones.
-hipError_t launch_kp_columns_f32_range(Ctx *c, hipStream_t s, int l0, int l1, const float *staging)
+// upl_first_dev != nullptr (kpilqr_iterate_streamed4 with upload_traj): the staging buffer holds the entries of the chunk's LISTED
+// trajectories alone, back to back from the chunk's first entry on; upl_first_dev [batch] is the first entry of trajectory b inside
+// the staging buffer, -1 for a trajectory that is not listed, whose lists are left alone -- the table of the partial explicit call.
+hipError_t launch_kp_columns_f32_range(Ctx *c, hipStream_t s, int l0, int l1, const float *staging, const int *upl_first_dev)
 {
     const long long nlists = (long long)c->d.batch * c->d.dof;
     if (l0 < 0 || l1 < l0 || l1 > nlists) return hipErrorInvalidValue;
     if (l1 == l0 || c->n == 0) return hipSuccess;
-    return launch_lists(c, s, l0, l1, staging, nullptr);
+    return launch_lists(c, s, l0, l1, staging, upl_first_dev);
 }
 
 }  // namespace kpilqr

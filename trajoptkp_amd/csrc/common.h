@@ -255,6 +255,24 @@ struct Ctx {
     int *pipe_list_host = nullptr;         // [batch], pinned
     int pipe_list_count = -1;              // entries of the list pipe_list holds; -1: none yet
     hipEvent_t pipe_list_up = nullptr;
+    // kpilqr_iterate_streamed4 with upload_traj (rows_in.hip).  rows_stage: one staging region per input kind, as large as the
+    // whole-batch form of that input, reserved by the first call that gives the kind with a list and kept; a chunk uploads its compact
+    // slice to where its first trajectory's rows (entries) would sit, so same-stream order protects the region from the next call's upload
+    // whatever that call's list is.  (The FP32 columns stage in kpc32.)  The list changes with every iteration, so its device copy and
+    // pinned mirror are a RING: slot rows_next holds [2][batch] ints -- the list | per trajectory the first entry of its payload inside
+    // the staging region, -1: not listed.  A slot is written again kRowsRing calls later: the host then waits for the slot's own
+    // upload (rows_up, long done), and the context's stream waits for the chunks that read the slot (rows_read), never for the
+    // iteration in flight.
+    enum RowsKind : int { kRowsR, kRowsRx, kRowsRu, kRowsUnom, kRowsPayload, kRowsKinds };
+    DevBuf<char> rows_stage[kRowsKinds];
+    static constexpr int kRowsRing = 4;
+    DevBuf<int> rows_list;                 // [kRowsRing][2][batch]
+    int *rows_list_host = nullptr;         // [kRowsRing][2][batch], pinned
+    hipEvent_t rows_up[kRowsRing] = {};
+    hipEvent_t rows_read[kRowsRing][kPipeStreams] = {};
+    bool rows_read_set[kRowsRing][kPipeStreams] = {};
+    int rows_next = 0;
+    size_t rows_pay_rec = 0;               // bytes per entry of the payload last staged in rows_stage[kRowsPayload] (records | FP64 columns)
 
     // staging for debug hooks / U_alpha
     DevBuf<double> stage;
@@ -265,7 +283,8 @@ struct Ctx {
     {
         DevMem *const all[] = {&rec, &kp_uniform, &K, &k, &r, &r_x, &r_u, &w_run, &w_term, &u_nom, &ctrl_lim, &lambda, &alphas, &cost_pred,
                                &delta_J, &traj_cost, &status, &attempts, &gate, &traj_list, &K32, &segmap, &segent, &kp_offsets, &kp_times, &rx_const, &kpc, &kpc32, &kps, &kp_entry,
-                               &kp_entry_list, &fdk_dev, &kpu_offsets, &kpu_times, &kpu_src, &kpu_traj_first, &kpcu, &kpu_uniform, &fdk_alt, &kpc_alt, &kp_times_alt, &kp_upl_times, &kp_move, &X_states, &kp_thr, &kp_mask, &kp_count, &ls8, &fd_dev, &err_flag, &stage, &pipe_list};
+                               &kp_entry_list, &fdk_dev, &kpu_offsets, &kpu_times, &kpu_src, &kpu_traj_first, &kpcu, &kpu_uniform, &fdk_alt, &kpc_alt, &kp_times_alt, &kp_upl_times, &kp_move, &X_states, &kp_thr, &kp_mask, &kp_count, &ls8, &fd_dev, &err_flag, &stage, &pipe_list,
+                               &rows_stage[0], &rows_stage[1], &rows_stage[2], &rows_stage[3], &rows_stage[4], &rows_list};
         for (DevMem *b : all) f(*b);
     }
 
@@ -348,7 +367,17 @@ hipError_t launch_gains_out(const Ctx *c, hipStream_t s, GainsForm form, const i
 hipError_t launch_kp_columns_f32(Ctx *c, const float *src, const int *upl_first);
 // the same for a chunk of kpilqr_iterate_streamed3: the lists [l0, l1) = [b0*dof, b1*dof) of the CONTEXT's device CSR (c is never a view),
 // decoded on stream s from `staging` (Ctx::kpc32, in store order: a list's floats sit at its first entry * 3n) into the column store
-hipError_t launch_kp_columns_f32_range(Ctx *c, hipStream_t s, int l0, int l1, const float *staging);
+// upl_first != nullptr (a chunk of kpilqr_iterate_streamed4 with upload_traj): staging holds the chunk's LISTED trajectories' entries alone;
+// upl_first [batch] (device): first entry of trajectory b inside staging, -1: not listed, its lists are left alone
+hipError_t launch_kp_columns_f32_range(Ctx *c, hipStream_t s, int l0, int l1, const float *staging, const int *upl_first = nullptr);
+// rows_in.hip, the chunks of kpilqr_iterate_streamed4 with upload_traj: rows of a chunk's staging region moved to their trajectories'
+// places on stream s.  Row i of `count` is trajectory traj[i] (device).  Fixed rows of `units` doubles: staging + i*units -> dst + traj[i]*units
+hipError_t launch_rows_in(hipStream_t s, const int *traj, int count, long long units, const double *staging, double *dst);
+// rows by key-point entry (records of the key-point ordered payload, FP64 columns; rec_bytes per entry, a multiple of 16): the entry
+// range of trajectory traj[i] in the CONTEXT's device CSR (c is never a view), read from entry src_first[traj[i]] of staging
+// (src_first [batch], device) and written to the trajectory's own range of dst
+hipError_t launch_rows_in_entries(const Ctx *c, hipStream_t s, const int *traj, int count, const int *src_first, size_t rec_bytes,
+                                  const void *staging, void *dst);
 // lambda_retry.hip: attempts = 1, gate = 1 for every trajectory | between two attempts: status -> lambda, attempts, gate
 hipError_t launch_lambda_retry_begin(Ctx *c);
 hipError_t launch_lambda_retry(Ctx *c);

@@ -666,6 +666,11 @@ void kpilqr_destroy(kpilqr_ctx *c)
     if (c->err_flag_host) (void)hipHostFree(c->err_flag_host);
     if (c->pipe_list_host) (void)hipHostFree(c->pipe_list_host);
     if (c->pipe_list_up) (void)hipEventDestroy(c->pipe_list_up);
+    if (c->rows_list_host) (void)hipHostFree(c->rows_list_host);
+    for (int i = 0; i < Ctx::kRowsRing; i++) {
+        if (c->rows_up[i]) (void)hipEventDestroy(c->rows_up[i]);
+        for (hipEvent_t e : c->rows_read[i]) if (e) (void)hipEventDestroy(e);
+    }
     forget_lists(c);
     if (c->kpu_traj_first_host) free(c->kpu_traj_first_host);
     if (c->own_stream) (void)hipStreamDestroy(c->stream);
@@ -1923,9 +1928,97 @@ static int pipe_list_bind(kpilqr_ctx *c, const StreamGains &g)
     return KPILQR_OK;
 }
 
+// What kpilqr_iterate_streamed4 adds: the inputs (payload, r, r_x, r_u, u_nom) of a list of trajectories alone, compact in list order.
+// !listed: the walk of the three earlier calls, which enqueues what it always has.
+struct StreamRows {
+    bool listed = false;           // traj [count] (strictly increasing, within [0, batch)); read during the call only
+    int count = 0;
+    const int *traj = nullptr;
+};
+
+// The checks of a streamed iteration whose inputs follow a list (kpilqr_iterate_streamed4 with upload_traj), all before anything is
+// enqueued or the context changes.  The list itself has been checked, and with a by-entry payload the host knows the lists.
+static int check_stream_rows(kpilqr_ctx *c, const kpilqr_stream_io *io, const StreamRows &u, const float *kcols32)
+{
+    const std::string w("kpilqr_iterate_streamed4");
+    if (io->fd_slab) return set_err(c, KPILQR_ERR_ARG, w + ": io.fd_slab with upload_traj (job lists carry their own trajectory indices: out of scope)");
+    if (io->fd_kp_slab || io->kp_columns || kcols32) {
+        long long sum = 0;
+        for (int i = 0; i < u.count; i++) sum += c->kp_traj_first_host[u.traj[i] + 1] - c->kp_traj_first_host[u.traj[i]];
+        if (io->entries != sum) return set_err(c, KPILQR_ERR_ARG, w + ": `entries` is not the number of key-point entries of the listed trajectories");
+        // the trajectories that are not listed keep their payload: it has to be there, whole, and of the kind that arrives
+        const FdPayload kind = io->fd_kp_slab ? FdPayload::kp_ordered : FdPayload::kp_columns;
+        const bool resident = c->fd_payload == kind && (kind == FdPayload::kp_ordered || c->pay.kpc_valid || c->n_pending > 0);
+        if (!resident)
+            return set_err(c, KPILQR_ERR_STATE, w + ": a payload with upload_traj, but the context holds no complete resident payload of the same kind "
+                                                    "(key-point ordered records / key-point columns) for the trajectories that are not listed");
+        if (io->fd_kp_slab && memcmp(&io->eps, &c->eps, sizeof(double)) != 0)
+            return set_err(c, KPILQR_ERR_ARG, w + ": eps differs from the resident payload's (a context has one eps)");
+        // ranges pending since kpilqr_update_keypoints: the list has to bring every one of them (both lists increase)
+        for (int p = 0, i = 0; p < c->n_pending; p++) {
+            const int b = c->kp_pending_host[p];
+            while (i < u.count && u.traj[i] < b) i++;
+            if (i == u.count || u.traj[i] != b)
+                return set_err(c, KPILQR_ERR_STATE, w + ": the payload of trajectory " + std::to_string(b) + " is pending since kpilqr_update_keypoints "
+                                                        "and upload_traj does not list it");
+        }
+    }
+    // (the refusals of kpilqr_upload_residuals_partial, in its words)
+    if (io->r_x && c->rx_const_on)
+        return set_err(c, KPILQR_ERR_STATE, w + ": the context holds constant residual Jacobians; a whole r_x through kpilqr_upload_residuals ends that mode first");
+    if (io->r_x && !(c->rx_buf_valid && c->rx_whole))
+        return set_err(c, KPILQR_ERR_STATE, w + ": r_x of a subset before a whole r_x: kpilqr_upload_residuals first");
+    if (io->r_u && c->ru_zero)
+        return set_err(c, KPILQR_ERR_STATE, w + ": r_u of a subset on a context that runs without control residuals: a whole r_u through kpilqr_upload_residuals first");
+    return KPILQR_OK;
+}
+
+// The ring slot of a listed call, before the chunks are cut: the list and, per trajectory, the first entry of its payload inside the
+// staging region (-1: not listed) into the slot's pinned mirror, uploaded on the context's stream ahead of pipe_in.  The slot was
+// last used kRowsRing calls ago: the wait for its upload is over long since, and the context's stream is ordered behind the chunks
+// that read its device copy -- no wait concerns the iteration in flight.  -> *slot_out
+static int rows_list_bind(kpilqr_ctx *c, const StreamRows &u, int nchunks, bool by_entry, int *slot_out)
+{
+    const int B = c->d.batch, slot = c->rows_next;
+    const size_t per_slot = 2 * (size_t)B;
+    if (!c->rows_list_host) {
+        { const int rc = reserve(c, c->rows_list, Ctx::kRowsRing * per_slot * sizeof(int), kExact, false); if (rc < 0) return rc; }
+        const hipError_t e = hipHostMalloc((void **)&c->rows_list_host, Ctx::kRowsRing * per_slot * sizeof(int), hipHostMallocDefault);
+        if (e != hipSuccess) { c->rows_list_host = nullptr; return set_err(c, KPILQR_ERR_ALLOC, std::string("hipHostMalloc failed: ") + hipGetErrorString(e)); }
+    }
+    if (!c->rows_up[slot]) {
+        KP_HIP(c, hipEventCreateWithFlags(&c->rows_up[slot], hipEventDisableTiming));
+        for (int i = 0; i < Ctx::kPipeStreams; i++) KP_HIP(c, hipEventCreateWithFlags(&c->rows_read[slot][i], hipEventDisableTiming));
+    } else {
+        KP_HIP(c, hipEventSynchronize(c->rows_up[slot]));
+    }
+    for (int i = 0; i < Ctx::kPipeStreams; i++)
+        if (c->rows_read_set[slot][i]) { KP_HIP(c, hipStreamWaitEvent(c->stream, c->rows_read[slot][i], 0)); c->rows_read_set[slot][i] = false; }
+    int *const list = c->rows_list_host + slot * per_slot, *const first = list + B;
+    memcpy(list, u.traj, sizeof(int) * (size_t)u.count);
+    for (int b = 0; b < B; b++) first[b] = -1;
+    if (by_entry) {
+        // a chunk's listed entries sit back to back from the chunk's own first entry on
+        for (int ch = 0, i = 0; ch < nchunks; ch++) {
+            const int b0 = (int)((long long)B * ch / nchunks), b1 = (int)((long long)B * (ch + 1) / nchunks);
+            int at = c->kp_traj_first_host[b0];
+            for (; i < u.count && u.traj[i] < b1; i++) {
+                first[u.traj[i]] = at;
+                at += c->kp_traj_first_host[u.traj[i] + 1] - c->kp_traj_first_host[u.traj[i]];
+            }
+        }
+    }
+    KP_HIP(c, hipMemcpyAsync((int *)c->rows_list + slot * per_slot, list, per_slot * sizeof(int), hipMemcpyHostToDevice, c->stream));
+    KP_HIP(c, hipEventRecord(c->rows_up[slot], c->stream));
+    c->rows_next = (slot + 1) % Ctx::kRowsRing;
+    *slot_out = slot;
+    return KPILQR_OK;
+}
+
 // kcols32: what kpilqr_iterate_streamed3 adds -- the ENCODED FP32 key-point columns (kpilqr_upload_kp_columns_f32) as a fourth payload
-// kind; nullptr: the walk of the two earlier calls, which enqueues what it always has.
-static int iterate_streamed(kpilqr_ctx *c, const kpilqr_stream_io *io, const StreamGains &g, int pd_check_stride, int nchunks, const float *kcols32 = nullptr)
+// kind; nullptr: the walk of the two earlier calls, which enqueues what it always has.  u: what kpilqr_iterate_streamed4 adds.
+static int iterate_streamed(kpilqr_ctx *c, const kpilqr_stream_io *io, const StreamGains &g, int pd_check_stride, int nchunks, const float *kcols32 = nullptr,
+                            const StreamRows &u = StreamRows{})
 {
     KP_HIP(c, hipSetDevice(c->d.device));
     if (!c->have_kp) return set_err(c, KPILQR_ERR_STATE, "kpilqr_iterate_streamed before kpilqr_set_keypoints");
@@ -1938,6 +2031,8 @@ static int iterate_streamed(kpilqr_ctx *c, const kpilqr_stream_io *io, const Str
     const int B = c->d.batch;
     if (nchunks < 1) nchunks = Ctx::kPipeStreams;          // 0: one chunk per pipeline stream
     if (nchunks > B) nchunks = B;
+    if (u.listed && !kp_traj_list_ok(B, u.count, u.traj))
+        return set_err(c, KPILQR_ERR_ARG, "kpilqr_iterate_streamed4: upload_traj must be strictly increasing and within [0, batch)");
     if (io->fd_slab && (io->njobs < 1 || !io->traj_job_first || (io->nnom > 0 && !io->traj_nom_first)))
         return set_err(c, KPILQR_ERR_ARG, "streamed FD payload needs the per-trajectory job / nominal-row offsets");
     if ((io->fd_slab != nullptr) + (io->fd_kp_slab != nullptr) + (io->kp_columns != nullptr) + (kcols32 != nullptr) > 1)
@@ -1945,8 +2040,11 @@ static int iterate_streamed(kpilqr_ctx *c, const kpilqr_stream_io *io, const Str
     if (io->fd_kp_slab || io->kp_columns || kcols32) {
         if (!c->kp_traj_first_host || c->kp_total_host < 0)
             return set_err(c, KPILQR_ERR_STATE, "streamed key-point ordered payload: the lists must be known to the host (kpilqr_set_keypoints, or kpilqr_get_keypoints after generating them)");
-        if (io->entries != c->kp_total_host) return set_err(c, KPILQR_ERR_ARG, "fd_kp_slab / kp_columns / kp_columns32: `entries` is not the number of key-point entries");
+        if (!u.listed && io->entries != c->kp_total_host) return set_err(c, KPILQR_ERR_ARG, "fd_kp_slab / kp_columns / kp_columns32: `entries` is not the number of key-point entries");
     }
+    if (u.listed) { const int rcu = check_stream_rows(c, io, u, kcols32); if (rcu) return rcu; }
+    // entries of the payload as it will be resident: with a list the kept trajectories' stay beside the ones that arrive
+    const int pay_entries = u.listed ? c->kp_total_host : io->entries;
     const void *hostp[] = {kcols32, io->kp_columns, io->fd_kp_slab, io->fd_slab, io->r, io->r_x, io->r_u, io->u_nom, io->lambda, io->K, io->k, io->cost_pred, io->delta_J, io->status};
     for (const void *p : hostp) if (!is_pinned(p)) return set_err(c, KPILQR_ERR_ARG, "kpilqr_iterate_streamed: host buffers must be pinned (kpilqr_host_alloc)");
     if (g.K32) {
@@ -2012,32 +2110,57 @@ static int iterate_streamed(kpilqr_ctx *c, const kpilqr_stream_io *io, const Str
     if (kslab) {
         // a chunk's payload lands at its trajectories' entry range, which only the key-points decide: same-stream order
         // protects it from the next iteration's uploads (new key-points go through KP_ENTER, which joins the pipeline)
-        fdkp_layout(n, io->entries, &LK);
+        fdkp_layout(n, pay_entries, &LK);
         if (would_grow(c->fdk_dev, LK.bytes)) {                 // as for the job-list slab
             rc = join_pipeline(c); if (rc) return rc;
             for (int i = 0; i < Ctx::kPipeStreams; i++) KP_HIP(c, hipStreamSynchronize(c->pipe_stream[i]));
         }
-        rc = fdk_bind(c, io->entries, &LK);
+        rc = fdk_bind(c, pay_entries, &LK);
         if (rc) return rc;
-        c->fdk_entries = io->entries; c->fdk_first = 0; c->eps = io->eps;
+        c->fdk_entries = pay_entries; c->fdk_first = 0; c->eps = io->eps;
     }
     if (kcols32) {
         // The staging buffer the chunks upload into (shared with kpilqr_upload_kp_columns_f32[_partial], which join the pipeline on
         // entry): a chunk's floats land at its trajectories' entry range, which only the key-points decide, so same-stream order
         // protects it from the next iteration's upload as it does the key-point ordered slab.  A growth frees the old buffer, which nothing
         // may still read: as for the slabs
-        if (would_grow(c->kpc32, (size_t)io->entries * 3 * n * sizeof(float))) {
+        if (would_grow(c->kpc32, (size_t)pay_entries * 3 * n * sizeof(float))) {
             rc = join_pipeline(c); if (rc) return rc;
             for (int i = 0; i < Ctx::kPipeStreams; i++) KP_HIP(c, hipStreamSynchronize(c->pipe_stream[i]));
         }
-        rc = reserve_columns_f32(c, io->entries);
+        rc = reserve_columns_f32(c, pay_entries);
         if (rc) return rc;
+    }
+    // Inputs of a list: the staging regions the chunks upload their compact slices into, one per input kind that is given, as large
+    // as the whole-batch form of that input -- a chunk's slice lands where its first trajectory's rows (entries) would, which the
+    // chunk alone decides, so same-stream order protects it from the next call's upload whatever that call lists.  Reserved here, on
+    // the context, and kept; a growth frees the old region, which nothing may still read: as for the slabs.  (kp_columns32 stages
+    // in kpc32, above.)
+    const size_t T1 = (size_t)T + 1;
+    const size_t rows_per[Ctx::kRowsKinds] = {T1 * nr, T1 * nr * n, T1 * nr * m, (size_t)T * m, 0};      // doubles per trajectory
+    const double *const rows_src[Ctx::kRowsKinds] = {io->r, io->r_x, io->r_u, io->u_nom, nullptr};
+    const size_t pay_rec = kslab ? LK.entry_stride : (size_t)3 * n * 8;                                   // bytes per entry of a staged payload
+    const bool stage_pay = u.listed && (kslab || io->kp_columns);
+    if (u.listed && u.count > 0) {
+        size_t need[Ctx::kRowsKinds];
+        for (int kd = 0; kd < Ctx::kRowsPayload; kd++) need[kd] = rows_src[kd] ? (size_t)B * rows_per[kd] * 8 : 0;
+        need[Ctx::kRowsPayload] = stage_pay ? (size_t)pay_entries * pay_rec : 0;
+        bool grows = false;
+        for (int kd = 0; kd < Ctx::kRowsKinds; kd++) grows = grows || would_grow(c->rows_stage[kd], need[kd]);
+        if (grows) {
+            rc = join_pipeline(c); if (rc) return rc;
+            for (int i = 0; i < Ctx::kPipeStreams; i++) KP_HIP(c, hipStreamSynchronize(c->pipe_stream[i]));
+        }
+        for (int kd = 0; kd < Ctx::kRowsKinds; kd++) { rc = reserve(c, c->rows_stage[kd], need[kd], kExact, false); if (rc < 0) return rc; }
+        // the payload region is cut by entry * record size: records behind columns (or the other way round) would cut it elsewhere,
+        // and a chunk's upload could land in a range another chunk stream is still reading -- the rule of pipe_sig
+        if (stage_pay && c->rows_pay_rec != pay_rec) { rc = join_pipeline(c); if (rc) return rc; c->rows_pay_rec = pay_rec; }
     }
     const double *kcols = io->kp_columns;
     const bool new_payload = slab || kslab || kcols || kcols32;
     if (slab) c->fd_payload = FdPayload::jobs;
     if (kslab) c->fd_payload = FdPayload::kp_ordered;
-    if (kcols || kcols32) { c->fd_payload = FdPayload::kp_columns; c->fdk_entries = io->entries; c->fdk_first = 0; }
+    if (kcols || kcols32) { c->fd_payload = FdPayload::kp_columns; c->fdk_entries = pay_entries; c->fdk_first = 0; }
     if (new_payload) payload_changed(c);
     // allocations and tables the chunks need are made HERE, on the context: a view never allocates (reserve refuses)
     if (c->fused || payload_by_entry(c)) {
@@ -2077,6 +2200,11 @@ static int iterate_streamed(kpilqr_ctx *c, const kpilqr_stream_io *io, const Str
     if (!(c->fused && plan_backward_fused(c, false).rxc && plan_forward_fused(c).rxc)) { rc = ensure_rx_buffer(c); if (rc) return rc; }
     // the list of the gains that come down: on the device before the chunks, which read their slices of it
     rc = pipe_list_bind(c, g); if (rc) return rc;
+    // the list of the inputs that come up, in its ring slot (an empty list reads none)
+    int uslot = 0, ui = 0;                      // ui: first entry of upload_traj not below the chunk
+    size_t upe = 0;                             // payload entries of the listed trajectories below the chunk
+    if (u.listed && u.count > 0) { rc = rows_list_bind(c, u, nchunks, new_payload, &uslot); if (rc) return rc; }
+    const int *const ulist = u.listed && u.count > 0 ? (const int *)c->rows_list + (size_t)uslot * 2 * B : nullptr, *const ufirst = ulist ? ulist + B : nullptr;
     const bool gather = g.K32 || g.listed;      // K (and k of a list) leave through gains.hip's gather kernel
     int li = 0;                                 // first list entry not below the chunk (chunks and list both increase)
     // order the chunk streams behind whatever the caller enqueued on the context's stream so far (key-points, weights ...)
@@ -2099,7 +2227,32 @@ static int iterate_streamed(kpilqr_ctx *c, const kpilqr_stream_io *io, const Str
         const auto of_view = [&](int rcv) { if (rcv) c->err = v.err; return rcv; };      // a view's refusal is the context's
         const size_t o = b0, cnt = nb;
         // ---- H2D of the chunk ------------------------------------------------------------------------------------
-        if (slab) {
+        // inputs of a list: the chunk's share is the slice [ui0, ui) of the list -- `rows` rows of every compact input from row ui0
+        // on, and, of a by-entry payload, `lE` entries from entry upe0 on
+        const int ui0 = ui;
+        const size_t upe0 = upe;
+        if (u.listed) {
+            for (; ui < u.count && u.traj[ui] < b1; ui++)
+                if (new_payload) upe += (size_t)(c->kp_traj_first_host[u.traj[ui] + 1] - c->kp_traj_first_host[u.traj[ui]]);
+        }
+        const int rows = ui - ui0;
+        const size_t lE = upe - upe0;
+        if (u.listed && new_payload) {
+            // ONE upload of the chunk's compact slice to where the chunk's first entry would sit in the staging region, ONE launch that
+            // moves (kp_columns32: decodes) the listed trajectories' entry ranges from there into place; the view is the whole chunk's
+            const int e0 = c->kp_traj_first_host[b0], e1 = c->kp_traj_first_host[b1];
+            if (lE && kcols32) {
+                KP_HIP(c, h2d(c->kpc32 + (size_t)e0 * 3 * n, kcols32 + upe0 * 3 * n, lE * 3 * n * sizeof(float), s));
+                KP_HIP(c, launch_kp_columns_f32_range(c, s, b0 * c->d.dof, b1 * c->d.dof, c->kpc32, ufirst));
+            } else if (lE) {
+                char *const stg = c->rows_stage[Ctx::kRowsPayload];
+                const char *const src = kslab ? kslab : (const char *)io->kp_columns;
+                KP_HIP(c, h2d(stg + (size_t)e0 * pay_rec, src + upe0 * pay_rec, lE * pay_rec, s));
+                KP_HIP(c, launch_rows_in_entries(c, s, ulist + ui0, rows, ufirst, pay_rec, stg, kslab ? (void *)c->fdk_dev.p : (void *)c->kpc.p));
+            }
+            v.njobs = 0; v.fdk_first = e0; v.fdk_entries = e1 - e0;
+            if (!kslab) v.pay.kpc_valid = true;
+        } else if (slab) {
             const int j0 = io->traj_job_first[b0], j1 = io->traj_job_first[b1];
             const size_t J = (size_t)(j1 - j0), jo = (size_t)j0;
             if (J) {
@@ -2148,10 +2301,28 @@ static int iterate_streamed(kpilqr_ctx *c, const kpilqr_stream_io *io, const Str
                 v.fdk_first = c->kp_traj_first_host[b0]; v.fdk_entries = c->kp_traj_first_host[b1] - v.fdk_first;
             }
         }
-        if (io->r) KP_HIP(c, h2d(v.r, io->r + o * (T + 1) * nr, cnt * (T + 1) * nr * 8, s));
-        if (io->r_x) KP_HIP(c, h2d(v.r_x, io->r_x + o * (T + 1) * nr * n, cnt * (T + 1) * nr * n * 8, s));
-        if (io->r_u) KP_HIP(c, h2d(v.r_u, io->r_u + o * (T + 1) * nr * m, cnt * (T + 1) * nr * m * 8, s));
-        if (io->u_nom) KP_HIP(c, h2d(v.u_nom, io->u_nom + o * T * m, cnt * T * m * 8, s));
+        if (u.listed) {
+            // per array that is given: ONE upload of the chunk's rows into its staging region (at the chunk's first trajectory), ONE
+            // launch of k_rows_in (rows_in.hip) to the listed trajectories' places in the CONTEXT's buffer
+            double *const rows_dst[Ctx::kRowsPayload] = {c->r, c->r_x, c->r_u, c->u_nom};
+            for (int kd = 0; kd < Ctx::kRowsPayload && rows; kd++) {
+                if (!rows_src[kd]) continue;
+                const size_t per = rows_per[kd];
+                double *const stg = (double *)c->rows_stage[kd].p + o * per;
+                KP_HIP(c, h2d(stg, rows_src[kd] + (size_t)ui0 * per, (size_t)rows * per * 8, s));
+                KP_HIP(c, launch_rows_in(s, ulist + ui0, rows, (long long)per, stg, rows_dst[kd]));
+            }
+            // (the slot of the list may be written again once this stream has passed here)
+            if (rows) {
+                KP_HIP(c, hipEventRecord(c->rows_read[uslot][ch % Ctx::kPipeStreams], s));
+                c->rows_read_set[uslot][ch % Ctx::kPipeStreams] = true;
+            }
+        } else {
+            if (io->r) KP_HIP(c, h2d(v.r, io->r + o * (T + 1) * nr, cnt * (T + 1) * nr * 8, s));
+            if (io->r_x) KP_HIP(c, h2d(v.r_x, io->r_x + o * (T + 1) * nr * n, cnt * (T + 1) * nr * n * 8, s));
+            if (io->r_u) KP_HIP(c, h2d(v.r_u, io->r_u + o * (T + 1) * nr * m, cnt * (T + 1) * nr * m * 8, s));
+            if (io->u_nom) KP_HIP(c, h2d(v.u_nom, io->u_nom + o * T * m, cnt * T * m * 8, s));
+        }
         if (io->lambda) KP_HIP(c, h2d(v.lambda, io->lambda + o, cnt * 8, s));
         // ---- kernels of the chunk --------------------------------------------------------------------------------
         if (!c->fused) {
@@ -2231,6 +2402,22 @@ int kpilqr_iterate_streamed3(kpilqr_ctx *c, const kpilqr_stream_io3 *io3, int pd
     StreamGains g;
     if (const int rc = stream_gains_of(c, &io3->io2, &g)) return rc;
     return iterate_streamed(c, &io3->io2.io, g, pd_check_stride, nchunks, io3->kp_columns32);
+}
+
+// kpilqr_iterate_streamed3 taking the inputs of a list of trajectories alone: with upload_traj == NULL it IS that call
+int kpilqr_iterate_streamed4(kpilqr_ctx *c, const kpilqr_stream_io4 *io4, int pd_check_stride, int nchunks)
+{
+    if (!c || !io4) return KPILQR_ERR_ARG;
+    if (io4->struct_size != sizeof(kpilqr_stream_io4)) return set_err(c, KPILQR_ERR_ARG, "kpilqr_iterate_streamed4: struct_size is not sizeof(kpilqr_stream_io4) of this library");
+    const kpilqr_stream_io3 *io3 = &io4->io3;
+    if (io3->struct_size != sizeof(kpilqr_stream_io3)) return set_err(c, KPILQR_ERR_ARG, "kpilqr_iterate_streamed3: struct_size is not sizeof(kpilqr_stream_io3) of this library");
+    if (io4->upload_count < 0 || (io4->upload_count > 0 && !io4->upload_traj))
+        return set_err(c, KPILQR_ERR_ARG, "kpilqr_iterate_streamed4: upload_count < 0, or listed trajectories without upload_traj");
+    StreamGains g;
+    if (const int rc = stream_gains_of(c, &io3->io2, &g)) return rc;
+    StreamRows u;
+    u.listed = io4->upload_traj != nullptr; u.count = u.listed ? io4->upload_count : 0; u.traj = io4->upload_traj;
+    return iterate_streamed(c, &io3->io2.io, g, pd_check_stride, nchunks, io3->kp_columns32, u);
 }
 
 // ---- multi-GPU: the line-search cost reduction -----------------------------------------------------------

@@ -398,8 +398,32 @@ class Engine:
         self._iterate_streamed(fd, fd_kp, kp_cols, eps, r, r_x, r_u, u_nom, lam, K, k, cost_pred, delta_J, status, pd_stride, nchunks,
                                K32, gain_traj, io3, kp_cols32)
 
+    def iterate_streamed4(self, fd=None, fd_kp=None, kp_cols=None, eps=1e-6, r=None, r_x=None, r_u=None, u_nom=None, lam=None, K=None, k=None,
+                          cost_pred=None, delta_J=None, status=None, pd_stride=100, nchunks=0, K32=None, gain_traj=None, kp_cols32=None,
+                          upload_traj=None):
+        """kpilqr_iterate_streamed4: iterate_streamed3 with upload_traj (any int sequence, strictly increasing; [] is a list too) -- the
+        inputs of those trajectories alone: r, r_x, r_u, u_nom hold their rows and fd_kp / kp_cols / kp_cols32 their entries, back to
+        back in list order; lam stays [batch].  Everybody else keeps what is resident.  Always takes the new entry point (with
+        upload_traj=None that call is kpilqr_iterate_streamed3)."""
+        if kp_cols32 is not None:
+            if kp_cols32.dtype != np.float32:
+                raise ValueError("kp_cols32 must be a float32 array (no silent rounding here: the encoding is the caller's)")
+            if kp_cols32.size % (3 * self.n):
+                raise ValueError(f"kp_cols32 must hold whole entries of 3 * {self.n} floats")
+        io4 = _lib.StreamIO4()
+        io4.struct_size = C.sizeof(_lib.StreamIO4)
+        io4.io3.struct_size = C.sizeof(_lib.StreamIO3)
+        tr = None
+        if upload_traj is not None:
+            tr = self._traj(upload_traj)
+            io4.upload_count = len(tr)
+            tr = tr if len(tr) else np.zeros(1, np.int32)              # an empty list is still a list: a non-NULL pointer
+            io4.upload_traj = tr.ctypes.data                           # (read during the call only: tr lives until it returns)
+        self._iterate_streamed(fd, fd_kp, kp_cols, eps, r, r_x, r_u, u_nom, lam, K, k, cost_pred, delta_J, status, pd_stride, nchunks,
+                               K32, gain_traj, io4.io3, kp_cols32, io4)
+
     def _iterate_streamed(self, fd, fd_kp, kp_cols, eps, r, r_x, r_u, u_nom, lam, K, k, cost_pred, delta_J, status, pd_stride, nchunks,
-                          K32, gain_traj, io3, kp_cols32=None):
+                          K32, gain_traj, io3, kp_cols32=None, io4=None):
         io2 = None if io3 is None else io3.io2
         if io2 is not None or K32 is not None or gain_traj is not None:
             if io2 is None:
@@ -429,7 +453,9 @@ class Engine:
                         ("cost_pred", cost_pred), ("delta_J", delta_J), ("status", status)):
             if a is not None:
                 setattr(io, name, a.ctypes.data)
-        if io3 is not None:
+        if io4 is not None:
+            self._ck(self._partial("kpilqr_iterate_streamed4")(self._h, C.byref(io4), int(pd_stride), int(nchunks)))
+        elif io3 is not None:
             self._ck(self._partial("kpilqr_iterate_streamed3")(self._h, C.byref(io3), int(pd_stride), int(nchunks)))
         elif io2 is None:
             self._ck(self._L.kpilqr_iterate_streamed(self._h, C.byref(io), int(pd_stride), int(nchunks)))
