@@ -260,7 +260,8 @@ int  kpilqr_download_gains_partial(kpilqr_ctx *ctx, int count, const int *traj,
  *
  * Out of scope: the sweeps still run over the whole batch; kpilqr_generate_keypoints and kpilqr_upload_states for a subset; keeping
  * the column store, slope store and union store of kept trajectories on a KPILQR_FLAG_FUSED context; kpilqr_iterate and
- * kpilqr_iterate_streamed (whole batch); job-list payloads carried across kpilqr_update_keypoints. */
+ * kpilqr_iterate_streamed (whole batch); job-list payloads carried across kpilqr_update_keypoints.
+ * (since: kpilqr_backward_partial, kpilqr_forward_linear_partial and kpilqr_iterate_partial sweep a listed subset -- "Sweeps of a subset".) */
 int  kpilqr_upload_residuals_partial(kpilqr_ctx *ctx, int count, const int *traj,
                                      const double *r, const double *r_x, const double *r_u);
 int  kpilqr_upload_nominal_partial(kpilqr_ctx *ctx, int count, const int *traj, const double *u_nom);
@@ -468,7 +469,8 @@ int  kpilqr_iterate_streamed(kpilqr_ctx *ctx, const kpilqr_stream_io *io, int pd
  * uploads stay and share the link, so the rate gains less: measured once at B = 1024, three chunks, against the FP64 call in the same
  * process, 1.10x with K32, 1.22x with K32 of a scattered half of the batch, 1.17x with FP64 K of that half (profiles/streamed_gains.txt).
  * Out of scope: FP32 for k, for any upload or inside any sweep; uploads or sweeps of a subset inside the chunks
- * (kpilqr_iterate_streamed4 has since added the uploads); KPILQR_FLAG_UNION_KEYPOINTS inside the chunks.  KPILQR_VERSION is unchanged: detect the call by its symbol. */
+ * (kpilqr_iterate_streamed4 has since added the uploads); KPILQR_FLAG_UNION_KEYPOINTS inside the chunks.  KPILQR_VERSION is unchanged: detect the call by its symbol.
+ * (since: the explicit calls sweep a listed subset -- "Sweeps of a subset"; the chunks still sweep every trajectory.) */
 typedef struct {
     size_t struct_size;                         /* sizeof(kpilqr_stream_io2) as the caller compiled it                   */
     kpilqr_stream_io io;                        /* every field with the meaning it has for kpilqr_iterate_streamed       */
@@ -512,7 +514,8 @@ int  kpilqr_iterate_streamed2(kpilqr_ctx *ctx, const kpilqr_stream_io2 *io2, int
  * Out of scope: uploads or sweeps of a subset inside the chunks; KPILQR_FLAG_UNION_KEYPOINTS inside the chunks; FP32 for x+ / x-,
  * residuals, residual Jacobians, u_nom or k, or inside any sweep; the host classes (they do not use the streamed route); any change
  * to kpilqr_stream_io or kpilqr_stream_io2; an environment switch.  KPILQR_VERSION is unchanged: detect the call by its symbol.
- * (Uploads of a subset inside the chunks have since arrived as kpilqr_iterate_streamed4, below; its sweeps still cover every trajectory.) */
+ * (Uploads of a subset inside the chunks have since arrived as kpilqr_iterate_streamed4, below; its sweeps still cover every trajectory.)
+ * (since: the explicit calls sweep a listed subset -- "Sweeps of a subset"; the chunks still sweep every trajectory.) */
 typedef struct {
     size_t struct_size;                         /* sizeof(kpilqr_stream_io3) as the caller compiled it                   */
     kpilqr_stream_io2 io2;                      /* every field as for kpilqr_iterate_streamed2; io2.struct_size = sizeof(kpilqr_stream_io2) */
@@ -575,7 +578,8 @@ int  kpilqr_iterate_streamed3(kpilqr_ctx *ctx, const kpilqr_stream_io3 *io3, int
  * (profiles/streamed_subset_uploads.txt).
  * Out of scope: sweeps or linearisation of a subset; job-list payloads (io.fd_slab) with a list; KPILQR_FLAG_UNION_KEYPOINTS inside
  * the chunks; the host classes and the batch shim (they do not use the streamed route); any change to kpilqr_stream_io, _io2 or
- * _io3; an environment switch.  KPILQR_VERSION is unchanged: detect the call by its symbol. */
+ * _io3; an environment switch.  KPILQR_VERSION is unchanged: detect the call by its symbol.
+ * (since: the explicit calls sweep a listed subset -- "Sweeps of a subset"; the chunks still sweep every trajectory.) */
 typedef struct {
     size_t struct_size;                         /* sizeof(kpilqr_stream_io4) as the caller compiled it                   */
     kpilqr_stream_io3 io3;                      /* every field as for kpilqr_iterate_streamed3 (inner struct_sizes checked as there) */
@@ -762,6 +766,55 @@ int  kpilqr_forward_linear(kpilqr_ctx *ctx, const double *alphas, double *cost_p
 
 /* ---- one whole iteration (STEP 1b + 1c + 2 + 3) enqueued back to back ------------------------ */
 int  kpilqr_iterate(kpilqr_ctx *ctx, const double *lambda, int pd_check_stride, const double *alphas);
+
+/* ---- Sweeps of a subset: STEP 2, STEP 3 and the whole iteration over a LIST of trajectories ------------------------------------
+ * kpilqr_backward / kpilqr_forward_linear / kpilqr_iterate for the listed trajectories alone: finished trajectories are not swept
+ * again, a retry sweeps the trajectories that failed.  (count, traj) has the contract of the _partial family: `traj` [count] strictly
+ * increasing and within [0, batch), else KPILQR_ERR_ARG and nothing is enqueued or changed; count = 0 is a no-op returning KPILQR_OK;
+ * count < 0, count > 0 with a NULL list and a NULL context are KPILQR_ERR_ARG; not through a view of kpilqr_iterate_streamed's chunks
+ * (KPILQR_ERR_STATE); each call orders itself behind a streamed iteration in flight and waits for the stream only when `traj` is
+ * pageable.  pd_check_stride < 1 is KPILQR_ERR_ARG.
+ * Compact layouts.  Host arrays are COMPACT: the listed trajectories' rows back to back in `traj` order -- lambda [count] (NULL: the
+ * resident lambdas), status [count], delta_J [count], cost_pred [count][n_alpha], U_alpha [count][n_alpha][T][m]; each may be NULL.
+ * Per listed trajectory K, k, status, delta_J, cost_pred, the resident lambda and U_alpha are bit for bit what a context holding
+ * exactly the listed trajectories (batch = count, the same inputs, flags and environment) produces.  (A sweep that fails its PD
+ * check stops at the failing step, as in kpilqr_backward: status says so, and the gains of the steps it did not reach keep what they held.)
+ * No byte of an unlisted trajectory is written: its K, k, status, delta_J, cost_pred, lambda, attempts and step records keep what
+ * they hold.
+ * Form.  What only arranges waves follows `count`, as it follows the batch in the whole-batch calls: the wave pairs / triple / one
+ * wave per trajectory of the fused sweeps, their exclusive-SIMD twins, the default of KPILQR_TILED_FSC.  What decides which stores
+ * exist or are valid stays the context's: the a6 form of the tiled sweeps, ru0, rxc, the device flag for uniform lists.  The diagnostic
+ * environment switches force forms as they do for the whole batch.  kpilqr_last_launch(ctx, 0 | 1) reports the form that ran with
+ * ":subset" appended last.
+ * Fused contexts: a subset sweep reads the column store and never differences inside the sweep.  A column store that is not valid
+ * is differenced for the WHOLE batch first (the launch of kpilqr_fd_difference, with the slopes per-DoF lists need) and is then valid
+ * for everybody.  KPILQR_FLAG_UNION_KEYPOINTS is ignored, as kpilqr_backward_stats ignores it.  Before any key-points exist, and while
+ * ranges are pending after kpilqr_update_keypoints, the calls return KPILQR_ERR_STATE.
+ * Contexts with records: the caller's contract is that of kpilqr_fd_interpolate_partial -- the listed trajectories' records hold a
+ * complete linearisation.  kpilqr_iterate_partial runs kpilqr_fd_interpolate_partial, kpilqr_cost_derivs_partial (not where the tiled
+ * sweeps form the cost derivatives themselves), the backward and the forward sweep; on a fused context the two sweeps only.  It sets
+ * kpilqr_last_launch(ctx, 2) as kpilqr_iterate does, with ":subset" appended.
+ * Lambda retry.  kpilqr_set_lambda_retry composes: the schedule runs per LISTED trajectory; an unlisted trajectory is never armed,
+ * whatever status an earlier sweep left it; the attempts launched follow the compact lambdas (lambda = NULL: max_attempts).
+ * kpilqr_download_lambda_retry stays a whole-batch read of what is resident.
+ * How, and what it costs.  ONE launch per sweep kernel with `count` workgroups: workgroup i reads its trajectory from the device copy
+ * of the list (the one kpilqr_fd_interpolate_partial uses), a scalar load.  The backward sweeps run through the lambda retry twins of
+ * their kernels, which take the list beside the gate; the forward sweeps through listed twins of theirs; the kernels of the
+ * whole-batch calls are unchanged.  lambda, status, delta_J and cost_pred cross with ONE copy each and one small placing or gathering
+ * launch (rows_in.hip), however scattered the list is, through a staging buffer of count * (20 + 8 n_alpha) bytes reserved by the first
+ * such call; U_alpha, a debug output, goes as one copy per run of adjacent trajectories out of a whole-batch staging area.  A context
+ * that never makes these calls allocates and launches nothing for them.
+ * Out of scope: the chunk pipeline (a streamed iteration sweeps the whole batch); differencing inside a listed sweep; keeping the
+ * column store, slope store or union store of kept trajectories across kpilqr_update_keypoints; kpilqr_backward_stats,
+ * kpilqr_generate_keypoints and kpilqr_upload_states for a subset; an environment switch.  kpilqr_allreduce_linesearch sums whatever
+ * cost_pred and status are resident, the rows an earlier sweep left for unlisted trajectories included.
+ * KPILQR_VERSION is unchanged: detect the calls by their symbols. */
+int  kpilqr_backward_partial(kpilqr_ctx *ctx, int count, const int *traj, const double *lambda /* [count] or NULL */,
+                             int pd_check_stride, int *status /* [count] */, double *delta_J /* [count] */);
+int  kpilqr_forward_linear_partial(kpilqr_ctx *ctx, int count, const int *traj, const double *alphas,
+                                   double *cost_pred /* [count][n_alpha] */, double *U_alpha /* [count][n_alpha][T][m] or NULL */);
+int  kpilqr_iterate_partial(kpilqr_ctx *ctx, int count, const int *traj, const double *lambda /* [count] or NULL */,
+                            int pd_check_stride, const double *alphas);
 
 /* ---- several GPUs: trajectories are sharded, one context (and one process or thread) per GPU; the only collective
  * is the line-search cost reduction named by the design: one all-reduce of 8 doubles per iteration over RCCL/xGMI,

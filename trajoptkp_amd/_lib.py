@@ -34,6 +34,7 @@ SYMBOLS = [
     "kpilqr_download_gains_f32", "kpilqr_download_gains_f32_partial", "kpilqr_iterate_streamed2",
     "kpilqr_set_lambda_retry", "kpilqr_download_lambda_retry",
     "kpilqr_upload_kp_columns_f32", "kpilqr_upload_kp_columns_f32_partial", "kpilqr_iterate_streamed3", "kpilqr_iterate_streamed4",
+    "kpilqr_backward_partial", "kpilqr_forward_linear_partial", "kpilqr_iterate_partial",
 ]
 # entry points added without a version bump (include/kpilqr.h: "detect the entry point by its symbol"): bound only when the library
 # has them -- KPILQR_LIB may name an older build of the same major version
@@ -44,7 +45,8 @@ OPTIONAL_SYMBOLS = {"kpilqr_fd_interpolate", "kpilqr_get_union_keypoints", "kpil
                     "kpilqr_download_gains_f32", "kpilqr_download_gains_f32_partial", "kpilqr_iterate_streamed2",
                     "kpilqr_set_lambda_retry", "kpilqr_download_lambda_retry",
                     "kpilqr_upload_kp_columns_f32", "kpilqr_upload_kp_columns_f32_partial", "kpilqr_iterate_streamed3",
-                    "kpilqr_iterate_streamed4"}
+                    "kpilqr_iterate_streamed4",
+                    "kpilqr_backward_partial", "kpilqr_forward_linear_partial", "kpilqr_iterate_partial"}
 
 
 class Dims(C.Structure):
@@ -204,6 +206,10 @@ def load():
         L.kpilqr_iterate_streamed3.argtypes = [vp, C.POINTER(StreamIO3), C.c_int, C.c_int]
     if hasattr(L, "kpilqr_iterate_streamed4"):
         L.kpilqr_iterate_streamed4.argtypes = [vp, C.POINTER(StreamIO4), C.c_int, C.c_int]
+    if hasattr(L, "kpilqr_backward_partial"):
+        L.kpilqr_backward_partial.argtypes = [vp, C.c_int, vp, vp, C.c_int, vp, vp]
+        L.kpilqr_forward_linear_partial.argtypes = [vp, C.c_int, vp, vp, vp, vp]
+        L.kpilqr_iterate_partial.argtypes = [vp, C.c_int, vp, vp, C.c_int, vp]
     for s in SYMBOLS:
         if s in OPTIONAL_SYMBOLS and not hasattr(L, s):
             continue

@@ -276,6 +276,9 @@ struct Ctx {
 
     // staging for debug hooks / U_alpha
     DevBuf<double> stage;
+    // the compact host arrays of the listed sweeps (kpilqr_backward_partial, kpilqr_forward_linear_partial) on their way in and out:
+    // [lambda | delta_J | cost_pred | status] of `count` rows; reserved by the first such call, never by anybody else
+    DevBuf<char> sweep_stage;
 
     // everything the context owns on the device, once: kpilqr_destroy frees by walking this
     template <class F>
@@ -283,7 +286,7 @@ struct Ctx {
     {
         DevMem *const all[] = {&rec, &kp_uniform, &K, &k, &r, &r_x, &r_u, &w_run, &w_term, &u_nom, &ctrl_lim, &lambda, &alphas, &cost_pred,
                                &delta_J, &traj_cost, &status, &attempts, &gate, &traj_list, &K32, &segmap, &segent, &kp_offsets, &kp_times, &rx_const, &kpc, &kpc32, &kps, &kp_entry,
-                               &kp_entry_list, &fdk_dev, &kpu_offsets, &kpu_times, &kpu_src, &kpu_traj_first, &kpcu, &kpu_uniform, &fdk_alt, &kpc_alt, &kp_times_alt, &kp_upl_times, &kp_move, &X_states, &kp_thr, &kp_mask, &kp_count, &ls8, &fd_dev, &err_flag, &stage, &pipe_list,
+                               &kp_entry_list, &fdk_dev, &kpu_offsets, &kpu_times, &kpu_src, &kpu_traj_first, &kpcu, &kpu_uniform, &fdk_alt, &kpc_alt, &kp_times_alt, &kp_upl_times, &kp_move, &X_states, &kp_thr, &kp_mask, &kp_count, &ls8, &fd_dev, &err_flag, &stage, &sweep_stage, &pipe_list,
                                &rows_stage[0], &rows_stage[1], &rows_stage[2], &rows_stage[3], &rows_stage[4], &rows_list};
         for (DevMem *b : all) f(*b);
     }
@@ -297,10 +300,16 @@ struct Ctx {
     bool retry_ran = false;       // a backward pass has run under the schedule since it was set: attempts holds its counts
     int retry_attempts = 1;
     const int *bwd_gate = nullptr;
+    // A listed launch (kpilqr_backward_partial / kpilqr_forward_linear_partial): the device copy of the list (traj_list) in a copy of
+    // the context whose d.batch is the list's length -- the launch width, by which the launchers choose their forms -- and whose
+    // per-trajectory pointers stay the context's: block i sweeps trajectory sweep_list[i].  nullptr: every block sweeps its own index.
+    // The backward launchers run a listed launch through the retry twins, so it always comes with bwd_gate.
+    const int *sweep_list = nullptr;
 
     Family bwd_family = Family::generic, fwd_family = Family::generic;
     // what the last backward / forward launch of this context actually was (kpilqr_last_launch); Waves::none: not a fused launch, or none yet
     FusedLaunch last_bwd, last_fwd;
+    int last_width[2] = {-1, -1};      // trajectories of the last backward / forward launch when it was a listed one (its launch width), -1: the whole batch
     std::string launch_desc[2];
     const char *last_linearise = "";   // kpilqr_last_launch(ctx, 2): how the last linearisation (a2 + a4) ran
 
@@ -322,6 +331,10 @@ struct Ctx {
 };
 
 Ctx::Tuning read_tuning_from_env();
+
+// The trajectory a block of a sweep works on: its own index, but in a listed launch (Ctx::sweep_list) entry blockIdx.x of the list --
+// a scalar load off a kernel argument indexed by the block, so the index stays wave-uniform for the descriptors built from it.
+__device__ __forceinline__ int kp_block_traj(const int *__restrict__ list, int own) { return list ? list[blockIdx.x] : own; }
 
 #define KP_HIP(ctx, call)                                                        \
     do {                                                                         \
@@ -379,8 +392,13 @@ hipError_t launch_rows_in(hipStream_t s, const int *traj, int count, long long u
 hipError_t launch_rows_in_entries(const Ctx *c, hipStream_t s, const int *traj, int count, const int *src_first, size_t rec_bytes,
                                   const void *staging, void *dst);
 // lambda_retry.hip: attempts = 1, gate = 1 for every trajectory | between two attempts: status -> lambda, attempts, gate
+// (a listed launch, Ctx::sweep_list: thread i works on trajectory sweep_list[i] and nobody touches an unlisted trajectory's words)
 hipError_t launch_lambda_retry_begin(Ctx *c);
 hipError_t launch_lambda_retry(Ctx *c);
+hipError_t launch_gate_arm(Ctx *c);                      // gate = 1 for the listed trajectories: a listed sweep without a schedule
+// rows_in.hip, the mirror image of launch_rows_in for the small per-trajectory outputs of the listed sweeps (status, delta_J, cost_pred):
+// `count` rows of `words` 4-byte words, row traj[i] (device) of src -> row i of staging
+hipError_t launch_rows_out(hipStream_t s, const int *traj, int count, int words, const void *src, void *staging);
 // comm.cpp (RCCL opened lazily) and the pack kernel of elementwise.hip
 const char *comm_unique_id(char *id128);
 const char *comm_init(Ctx *c, int nranks, int rank, const char *id128);

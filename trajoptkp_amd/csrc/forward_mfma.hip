@@ -51,11 +51,11 @@ __device__ __forceinline__ void forward_body(RecLayout L, int T, int n_alpha, co
                const double *__restrict__ Kin, const double *__restrict__ kin,
                const double *__restrict__ u_nom, const double *__restrict__ ctrl_lim,
                const double *__restrict__ alphas, double *__restrict__ cost_pred,
-               double *__restrict__ U_alpha)
+               double *__restrict__ U_alpha, const int btraj = blockIdx.x)
 {
     const int n = L.n, m = L.m;
     const int lane = threadIdx.x, c = lane & 15, q = lane >> 4;
-    const int b = blockIdx.x;
+    const int b = btraj;
 
     // per-lane source BYTE offsets; OOB = structural zero
     int oK[4], ok_[4], oA[4], oB[4], oLc[4], oLuu[4], olu[4], oub[4];
@@ -180,6 +180,27 @@ k_forward_mfma_excl(RecLayout L, int T, int n_alpha, const double *__restrict__ 
 {
     forward_body<NCZ, NCU>(L, T, n_alpha, rec, Kin, kin, u_nom, ctrl_lim, alphas, cost_pred, U_alpha);
 }
+// The listed twins of the two (kpilqr_forward_linear_partial): block i sweeps trajectory list[i] -- a scalar load off a kernel
+// argument, so the index the per-step descriptors are built from stays wave-uniform.  The same body; the two kernels above are the
+// launches of every whole-batch call, unchanged.
+template <int NCZ, int NCU>
+__global__ void __launch_bounds__(64)
+k_forward_mfma_listed(RecLayout L, int T, int n_alpha, const double *__restrict__ rec, const double *__restrict__ Kin,
+                      const double *__restrict__ kin, const double *__restrict__ u_nom, const double *__restrict__ ctrl_lim,
+                      const double *__restrict__ alphas, double *__restrict__ cost_pred, double *__restrict__ U_alpha,
+                      const int *__restrict__ list)
+{
+    forward_body<NCZ, NCU>(L, T, n_alpha, rec, Kin, kin, u_nom, ctrl_lim, alphas, cost_pred, U_alpha, list[blockIdx.x]);
+}
+template <int NCZ, int NCU>
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1)))
+k_forward_mfma_excl_listed(RecLayout L, int T, int n_alpha, const double *__restrict__ rec, const double *__restrict__ Kin,
+                           const double *__restrict__ kin, const double *__restrict__ u_nom, const double *__restrict__ ctrl_lim,
+                           const double *__restrict__ alphas, double *__restrict__ cost_pred, double *__restrict__ U_alpha,
+                           const int *__restrict__ list)
+{
+    forward_body<NCZ, NCU>(L, T, n_alpha, rec, Kin, kin, u_nom, ctrl_lim, alphas, cost_pred, U_alpha, list[blockIdx.x]);
+}
 
 bool forward_mfma_supported(int n, int m, int n_alpha)
 {
@@ -190,6 +211,12 @@ bool forward_mfma_supported(int n, int m, int n_alpha)
 template <int NCZ, int NCU>
 static hipError_t launch_fm(Ctx *c, double *U_alpha_dev)
 {
+    if (c->sweep_list) {
+        const auto twin = c->d.batch <= c->n_simd ? k_forward_mfma_excl_listed<NCZ, NCU> : k_forward_mfma_listed<NCZ, NCU>;
+        hipLaunchKernelGGL(twin, dim3(c->d.batch), dim3(64), 0, c->stream, c->L, c->d.T, c->d.n_alpha, c->rec, c->K, c->k, c->u_nom,
+                           c->ctrl_lim, c->alphas, c->cost_pred, U_alpha_dev, c->sweep_list);
+        return hipGetLastError();
+    }
     const auto kernel = c->d.batch <= c->n_simd ? k_forward_mfma_excl<NCZ, NCU> : k_forward_mfma<NCZ, NCU>;
     hipLaunchKernelGGL(kernel, dim3(c->d.batch), dim3(64), 0, c->stream, c->L, c->d.T, c->d.n_alpha, c->rec, c->K, c->k, c->u_nom,
                        c->ctrl_lim, c->alphas, c->cost_pred, U_alpha_dev);

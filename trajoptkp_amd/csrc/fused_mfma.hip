@@ -320,7 +320,7 @@ __device__ __forceinline__ void lds_store4(double *t, int lane, const d4 &v);
 template <int N, int M, bool PC, bool RU0 = false, bool RAW = false, bool UNI = false, bool STATS = false, bool RXC = false>
 __device__ __forceinline__ void backward_fused_body(double *sh, const double *pcbuf, int *sflag, RecLayout L, FusedArgs F, int T,
                 const double *__restrict__ lambda, int pd_stride, double *__restrict__ Kout, double *__restrict__ kout,
-                double *__restrict__ delta_J, int *__restrict__ status, int *__restrict__ hist = nullptr)
+                double *__restrict__ delta_J, int *__restrict__ status, int *__restrict__ hist = nullptr, const int btraj = KP_BLOCK_TRAJ)
 {
     int hcnt[6] = {0, 0, 0, 0, 0, 0};
     (void)hcnt;
@@ -334,7 +334,7 @@ __device__ __forceinline__ void backward_fused_body(double *sh, const double *pc
     // top of the step.)
     auto wsync = [&]() { __builtin_amdgcn_wave_barrier(); };
     const int lane = threadIdx.x & 63, c = lane & 15, q = lane >> 4;
-    const int b = KP_BLOCK_TRAJ;
+    const int b = btraj;                  // (the block's own index but in a listed launch: see k_backward_fused_retry)
     const double lam = lambda[b];
     // (probe builds, -DKP_PROBE_BWD=bits: 1 residual loads, 2 key-point stores, 4 gain stores go to one of eight trajectories)
     const int bR = (KP_PROBE_BWD & 1) ? (int)(blockIdx.x & 7) : b, bP = (KP_PROBE_BWD & 2) ? (int)(blockIdx.x & 7) : b, bS = (KP_PROBE_BWD & 4) ? (int)(blockIdx.x & 7) : b;
@@ -1069,27 +1069,34 @@ k_backward_fused_excl(RecLayout L, FusedArgs F, int T, const double *__restrict_
 // The lambda retry twins of the two (kpilqr_set_lambda_retry, lambda_retry.hip): the attempts behind the first of a backward pass under a
 // schedule.  A wave whose trajectory is settled or has given up (gate[b] == 0) leaves before anything else; the first attempt, and
 // every launch without a schedule, is one of the two kernels above, unchanged.
+// The twins also run the sweeps of a listed subset (kpilqr_backward_partial): `list` (device, nullptr: every block sweeps its own index)
+// names the trajectory of block i, gate and every per-trajectory address follow it, and the caller has armed the gate of the listed
+// trajectories.  list[blockIdx.x] is a scalar load off a kernel argument: the index stays wave-uniform, as the descriptors need it.
 template <int N, int M, bool RU0, bool RAW, bool UNI, bool RXC = false>
 __global__ void __launch_bounds__(64)
 k_backward_fused_retry(RecLayout L, FusedArgs F, int T, const double *__restrict__ lambda,
                        int pd_stride, double *__restrict__ Kout, double *__restrict__ kout,
-                       double *__restrict__ delta_J, int *__restrict__ status, const int *__restrict__ kp_uniform, const int *__restrict__ gate)
+                       double *__restrict__ delta_J, int *__restrict__ status, const int *__restrict__ kp_uniform, const int *__restrict__ gate,
+                       const int *__restrict__ list)
 {
     __shared__ __attribute__((aligned(16))) double sh[FLDS_TOTAL];
-    if (gate[KP_BLOCK_TRAJ] == 0) return;
+    const int b = kp_block_traj(list, KP_BLOCK_TRAJ);
+    if (gate[b] == 0) return;
     if ((*kp_uniform != 0) != UNI) return;
-    backward_fused_body<N, M, false, RU0, RAW, UNI, false, RXC>(sh, nullptr, nullptr, L, F, T, lambda, pd_stride, Kout, kout, delta_J, status);
+    backward_fused_body<N, M, false, RU0, RAW, UNI, false, RXC>(sh, nullptr, nullptr, L, F, T, lambda, pd_stride, Kout, kout, delta_J, status, nullptr, b);
 }
 template <int N, int M, bool RU0, bool RAW, bool UNI, bool RXC = false>
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1)))
 k_backward_fused_excl_retry(RecLayout L, FusedArgs F, int T, const double *__restrict__ lambda,
                             int pd_stride, double *__restrict__ Kout, double *__restrict__ kout,
-                            double *__restrict__ delta_J, int *__restrict__ status, const int *__restrict__ kp_uniform, const int *__restrict__ gate)
+                            double *__restrict__ delta_J, int *__restrict__ status, const int *__restrict__ kp_uniform, const int *__restrict__ gate,
+                            const int *__restrict__ list)
 {
     __shared__ __attribute__((aligned(16))) double sh[FLDS_TOTAL];
-    if (gate[KP_BLOCK_TRAJ] == 0) return;
+    const int b = kp_block_traj(list, KP_BLOCK_TRAJ);
+    if (gate[b] == 0) return;
     if ((*kp_uniform != 0) != UNI) return;
-    backward_fused_body<N, M, false, RU0, RAW, UNI, false, RXC>(sh, nullptr, nullptr, L, F, T, lambda, pd_stride, Kout, kout, delta_J, status);
+    backward_fused_body<N, M, false, RU0, RAW, UNI, false, RXC>(sh, nullptr, nullptr, L, F, T, lambda, pd_stride, Kout, kout, delta_J, status, nullptr, b);
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -1319,13 +1326,13 @@ struct DownTrackerRaw {
 // registers (see backward_fused_body).
 // SLP (differenced column store): per-DoF lists walked on the slope store (DownTrackerSlp).
 template <int N, int M, bool RAWP = false, bool RU0 = false, bool RXC = false, bool SLP = false>
-__device__ __forceinline__ void fusedpc_producer(double *pcbuf, int *sflag, RecLayout L, FusedArgs F, int T, const double *sh = nullptr)
+__device__ __forceinline__ void fusedpc_producer(double *pcbuf, int *sflag, RecLayout L, FusedArgs F, int T, const double *sh = nullptr, const int btraj = KP_BLOCK_TRAJ)
 {
     static_assert(!SLP || !RAWP, "the slope store serves the helper on a differenced column store");
     static_assert(!RXC || RU0, "RXC comes with RU0");
     constexpr int n = N, m = M;
     const int lane = threadIdx.x & 63, c = lane & 15, q = lane >> 4;
-    const int b = KP_BLOCK_TRAJ;
+    const int b = btraj;
     const int nr = F.nr, ncr = (nr + 3) >> 2;
     const int strideB = 3 * L.n * 8;                               // bytes of one key-point entry of kpc: three columns
     typename std::conditional<RAWP, DownTrackerRaw, typename std::conditional<SLP, DownTrackerSlp, DownTracker<8>>::type>::type tr;       // A rows then B rows of column c
@@ -1505,17 +1512,18 @@ __global__ void __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(1, 1))
 k_backward_fusedph_retry(RecLayout L, FusedArgs F, int T, int role_shift, const double *__restrict__ lambda,
                          int pd_stride, double *__restrict__ Kout, double *__restrict__ kout,
                          double *__restrict__ delta_J, int *__restrict__ status, const int *__restrict__ kp_uniform, int guard,
-                         const int *__restrict__ gate)
+                         const int *__restrict__ gate, const int *__restrict__ list)
 {
     __shared__ __attribute__((aligned(16))) double sh[FPC_TOTAL];
-    if (gate[KP_BLOCK_TRAJ] == 0) return;
+    const int b = kp_block_traj(list, KP_BLOCK_TRAJ);     // (a listed subset: see k_backward_fused_retry; the role placement stays on the block index)
+    if (gate[b] == 0) return;
     if (guard >= 0 && (*kp_uniform != 0) != (guard != 0)) return;
     const bool consumer = ((__builtin_amdgcn_readfirstlane(threadIdx.x >> 6) ^ (blockIdx.x >> role_shift)) & 1) == 0;
     if (consumer)
         backward_fused_body<N, M, true, RU0>(sh, sh + FPC_RING, (int *)(sh + FPC_FLAG), L, F, T, lambda, pd_stride, Kout, kout,
-                                                   delta_J, status);
+                                                   delta_J, status, nullptr, b);
     else
-        fusedpc_producer<N, M, RAWP, RU0, RXC, SLP>(sh + FPC_RING, (int *)(sh + FPC_FLAG), L, F, T, sh);
+        fusedpc_producer<N, M, RAWP, RU0, RXC, SLP>(sh + FPC_RING, (int *)(sh + FPC_FLAG), L, F, T, sh, b);
 }
 // ---------------------------------------------------------------------------------------------------------
 // Forward pass.  The column tracker walks UP in time; its tiles (row = A row, col = A column) are turned into
@@ -1550,7 +1558,7 @@ __device__ __forceinline__ void fwd_tail(StepF &step, int t, int T)
 template <int NCZ, int NCU, bool RU0 = false, bool UNI = false, bool RXC = false>
 __device__ __forceinline__ void forward_fused_body(RecLayout L, FusedArgs F, int T, int n_alpha, const double *__restrict__ Kin, const double *__restrict__ kin,
                const double *__restrict__ u_nom, const double *__restrict__ ctrl_lim,
-               const double *__restrict__ alphas, double *__restrict__ cost_pred, double *__restrict__ U_alpha)
+               const double *__restrict__ alphas, double *__restrict__ cost_pred, double *__restrict__ U_alpha, const int btraj = KP_BLOCK_TRAJ)
 {
     __shared__ __attribute__((aligned(16))) double shA[16 * 17], shB[16 * 17];
     // The chunk counts name the shape (KP_T1_SHAPES: (14,7) -> <4,2>, (4,1) -> <2,1>, (12,3) -> <4,1>, (10,3) -> <3,1>; the
@@ -1559,7 +1567,7 @@ __device__ __forceinline__ void forward_fused_body(RecLayout L, FusedArgs F, int
     constexpr int n = (NCZ == 4 && NCU == 2) ? 14 : (NCZ == 2) ? 4 : (NCZ == 4) ? 12 : 10;
     constexpr int m = (NCZ == 4 && NCU == 2) ? 7 : (NCZ == 2) ? 1 : 3;
     const int lane = threadIdx.x, c = lane & 15, q = lane >> 4;
-    const int b = KP_BLOCK_TRAJ;
+    const int b = btraj;
     const int nr = F.nr;
     constexpr int strideB = 3 * n * 8;                             // bytes of one key-point entry of kpc: three columns
     constexpr int ncx = (n + 3) >> 2;
@@ -1985,6 +1993,29 @@ k_forward_fused_excl(RecLayout L, FusedArgs F, int T, int n_alpha, const double 
     if ((*kp_uniform != 0) != UNI) return;
     forward_fused_body<NCZ, NCU, RU0, UNI, RXC>(L, F, T, n_alpha, Kin, kin, u_nom, ctrl_lim, alphas, cost_pred, U_alpha);
 }
+// The listed twins of the two (kpilqr_forward_linear_partial): block i sweeps trajectory list[i] -- a scalar load off a kernel
+// argument, so the index the per-trajectory descriptors are built from stays wave-uniform.  The same body; the two kernels above
+// are the launches of every whole-batch call, unchanged.
+template <int NCZ, int NCU, bool RU0, bool UNI, bool RXC = false>
+__global__ void __launch_bounds__(64)
+k_forward_fused_listed(RecLayout L, FusedArgs F, int T, int n_alpha, const double *__restrict__ Kin,
+                       const double *__restrict__ kin, const double *__restrict__ u_nom, const double *__restrict__ ctrl_lim,
+                       const double *__restrict__ alphas, double *__restrict__ cost_pred, double *__restrict__ U_alpha,
+                       const int *__restrict__ kp_uniform, const int *__restrict__ list)
+{
+    if ((*kp_uniform != 0) != UNI) return;
+    forward_fused_body<NCZ, NCU, RU0, UNI, RXC>(L, F, T, n_alpha, Kin, kin, u_nom, ctrl_lim, alphas, cost_pred, U_alpha, list[blockIdx.x]);
+}
+template <int NCZ, int NCU, bool RU0, bool UNI, bool RXC = false>
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1)))
+k_forward_fused_excl_listed(RecLayout L, FusedArgs F, int T, int n_alpha, const double *__restrict__ Kin,
+                            const double *__restrict__ kin, const double *__restrict__ u_nom, const double *__restrict__ ctrl_lim,
+                            const double *__restrict__ alphas, double *__restrict__ cost_pred, double *__restrict__ U_alpha,
+                            const int *__restrict__ kp_uniform, const int *__restrict__ list)
+{
+    if ((*kp_uniform != 0) != UNI) return;
+    forward_fused_body<NCZ, NCU, RU0, UNI, RXC>(L, F, T, n_alpha, Kin, kin, u_nom, ctrl_lim, alphas, cost_pred, U_alpha, list[blockIdx.x]);
+}
 
 // ---------------------------------------------------------------------------------------------------------
 // Forward pass, STATE / COST wave pair per trajectory (small batches: every wave has a SIMD to itself).  Only the state
@@ -2005,11 +2036,11 @@ k_forward_fused_excl(RecLayout L, FusedArgs F, int T, int n_alpha, const double 
 template <int NCZ, int NCU, bool RU0 = false, bool UNI = false>
 __device__ __forceinline__ void forward_sc_state(double *sh, RecLayout L, int T, int n_alpha, const double *__restrict__ Kin,
                const double *__restrict__ kin, const double *__restrict__ u_nom, const double *__restrict__ ctrl_lim,
-               const double *__restrict__ alphas, double *__restrict__ U_alpha, const FusedArgs *Fp = nullptr)
+               const double *__restrict__ alphas, double *__restrict__ U_alpha, const FusedArgs *Fp = nullptr, const int btraj = blockIdx.x)
 {
     const int n = L.n, m = L.m;
     const int lane = threadIdx.x & 63, c = lane & 15, q = lane >> 4;
-    const int b = blockIdx.x;
+    const int b = btraj;
     int oK[4], oub[4];
     double lo[NCU], hi[NCU], kmask[4];
     // k rides in row n of the gain operand: ONE load (the lanes of that row), added into the register that holds the row
@@ -2182,11 +2213,11 @@ __device__ __forceinline__ void forward_sc_state(double *sh, RecLayout L, int T,
 // ROLE 1: score only (the cost wave); 2: stage the A, B columns only (third wave of the triple)
 // RU0: r_u = 0 (no r_u tiles, no Ju product); RXC (with RU0): ONE constant r_x, its transposed tile in registers (forward_fused_body)
 template <int NCZ, int NCU, int ROLE, bool RU0 = false, bool RXC = false>
-__device__ __forceinline__ void forward_sc_cost(double *sh, RecLayout L, FusedArgs F, int T, int n_alpha, double *__restrict__ cost_pred)
+__device__ __forceinline__ void forward_sc_cost(double *sh, RecLayout L, FusedArgs F, int T, int n_alpha, double *__restrict__ cost_pred, const int btraj = blockIdx.x)
 {
     const int n = L.n, m = L.m;
     const int lane = threadIdx.x & 63, c = lane & 15, q = lane >> 4;
-    const int b = blockIdx.x;
+    const int b = btraj;
     const int nr = F.nr;
     const int strideB = 3 * L.n * 8;                               // bytes of one key-point entry of kpc: three columns
     const int ncx = (n + 3) >> 2;
@@ -2358,6 +2389,36 @@ k_forward_fused_sc3(RecLayout L, FusedArgs F, int T, int n_alpha, const double *
     else if (role == 1) forward_sc_cost<NCZ, NCU, 1, RU0, RXC>(sh, L, F, T, n_alpha, cost_pred);
     else forward_sc_cost<NCZ, NCU, 2>(sh, L, F, T, n_alpha, cost_pred);
 }
+// The listed twins of the pair and the triple (see k_forward_fused_listed): every wave of block i works on trajectory list[i]
+template <int NCZ, int NCU, bool RU0 = false, bool RXC = false>
+__global__ void __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(1, 1)))
+k_forward_fused_scu_listed(RecLayout L, FusedArgs F, int T, int n_alpha, const double *__restrict__ Kin,
+                           const double *__restrict__ kin, const double *__restrict__ u_nom, const double *__restrict__ ctrl_lim,
+                           const double *__restrict__ alphas, double *__restrict__ cost_pred, double *__restrict__ U_alpha,
+                           const int *__restrict__ kp_uniform, const int *__restrict__ list)
+{
+    __shared__ __attribute__((aligned(16))) double sh[FSC_TOTAL];
+    if (*kp_uniform == 0) return;
+    const int b = list[blockIdx.x];
+    const bool state = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6) == 0;
+    if (state) forward_sc_state<NCZ, NCU, RU0, true>(sh, L, T, n_alpha, Kin, kin, u_nom, ctrl_lim, alphas, U_alpha, &F, b);
+    else       forward_sc_cost<NCZ, NCU, 1, RU0, RXC>(sh, L, F, T, n_alpha, cost_pred, b);
+}
+template <int NCZ, int NCU, bool RU0 = false, bool RXC = false>
+__global__ void __launch_bounds__(192) __attribute__((amdgpu_waves_per_eu(1, 1)))
+k_forward_fused_sc3_listed(RecLayout L, FusedArgs F, int T, int n_alpha, const double *__restrict__ Kin,
+                           const double *__restrict__ kin, const double *__restrict__ u_nom, const double *__restrict__ ctrl_lim,
+                           const double *__restrict__ alphas, double *__restrict__ cost_pred, double *__restrict__ U_alpha,
+                           const int *__restrict__ kp_uniform, int only_ragged, const int *__restrict__ list)
+{
+    __shared__ __attribute__((aligned(16))) double sh[FSC_TOTAL];
+    if (only_ragged && *kp_uniform != 0) return;
+    const int b = list[blockIdx.x];
+    const int role = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    if (role == 0) forward_sc_state<NCZ, NCU, RU0>(sh, L, T, n_alpha, Kin, kin, u_nom, ctrl_lim, alphas, U_alpha, nullptr, b);
+    else if (role == 1) forward_sc_cost<NCZ, NCU, 1, RU0, RXC>(sh, L, F, T, n_alpha, cost_pred, b);
+    else forward_sc_cost<NCZ, NCU, 2>(sh, L, F, T, n_alpha, cost_pred, b);
+}
 
 #if KP_PART(1)
 bool fused_supported(int n, int m, int nr, int dof, int T, int n_alpha)
@@ -2426,7 +2487,7 @@ static void launch_bf_kernel(Ctx *c, const FusedLaunch &p, const FusedArgs &F, i
     if (c->bwd_gate) {
         const auto twin = p.excl ? k_backward_fused_excl_retry<NN, MM, RU, RW, UN, RX> : k_backward_fused_retry<NN, MM, RU, RW, UN, RX>;
         hipLaunchKernelGGL(twin, dim3(c->d.batch), dim3(64), 0, c->stream, c->L, F, c->d.T, c->lambda, pd_stride, c->K, c->k, c->delta_J,
-                           c->status, c->kp_uniform, c->bwd_gate);
+                           c->status, c->kp_uniform, c->bwd_gate, c->sweep_list);
         return;
     }
     const auto kernel = p.excl ? k_backward_fused_excl<NN, MM, RU, RW, UN, RX> : k_backward_fused<NN, MM, RU, RW, UN, RX>;
@@ -2483,7 +2544,7 @@ static void launch_bph_kernel(Ctx *c, const FusedLaunch &p, const FusedArgs &F, 
         auto twin = k_backward_fusedph_retry<NN, MM, RW, true, true, SL>;
         if (!p.rxc) twin = p.ru0 ? k_backward_fusedph_retry<NN, MM, RW, true, false, SL> : k_backward_fusedph_retry<NN, MM, RW, false, false, SL>;
         hipLaunchKernelGGL(twin, dim3(c->d.batch), dim3(128), 0, c->stream, c->L, F, c->d.T, c->tune.role_shift, c->lambda, pd_stride, c->K,
-                           c->k, c->delta_J, c->status, c->kp_uniform, guard, c->bwd_gate);
+                           c->k, c->delta_J, c->status, c->kp_uniform, guard, c->bwd_gate, c->sweep_list);
         return;
     }
     auto kernel = k_backward_fusedph<NN, MM, RW, true, true, SL>;
@@ -2546,6 +2607,12 @@ static void launch_ff_kernel(Kernel kernel, int block, Ctx *c, const FusedArgs &
 template <int NCZ, int NCU>
 static void launch_ff_pair(Ctx *c, const FusedLaunch &p, const FusedArgs &F, double *U_alpha_dev)
 {
+    if (c->sweep_list) {           // a listed subset (kpilqr_forward_linear_partial): the listed twin of the same form
+        auto twin = k_forward_fused_scu_listed<NCZ, NCU, true, true>;
+        if (!p.rxc) twin = p.ru0 ? k_forward_fused_scu_listed<NCZ, NCU, true, false> : k_forward_fused_scu_listed<NCZ, NCU>;
+        launch_ff_kernel(twin, 128, c, F, U_alpha_dev, c->sweep_list);
+        return;
+    }
     auto kernel = k_forward_fused_scu<NCZ, NCU, true, true>;
     if (!p.rxc) kernel = p.ru0 ? k_forward_fused_scu<NCZ, NCU, true, false> : k_forward_fused_scu<NCZ, NCU>;
     launch_ff_kernel(kernel, 128, c, F, U_alpha_dev);
@@ -2553,6 +2620,12 @@ static void launch_ff_pair(Ctx *c, const FusedLaunch &p, const FusedArgs &F, dou
 template <int NCZ, int NCU>
 static void launch_ff_triple(Ctx *c, const FusedLaunch &p, const FusedArgs &F, double *U_alpha_dev, int only_ragged)
 {
+    if (c->sweep_list) {
+        auto twin = k_forward_fused_sc3_listed<NCZ, NCU, true, true>;
+        if (!p.rxc) twin = p.ru0 ? k_forward_fused_sc3_listed<NCZ, NCU, true, false> : k_forward_fused_sc3_listed<NCZ, NCU>;
+        launch_ff_kernel(twin, 192, c, F, U_alpha_dev, only_ragged, c->sweep_list);
+        return;
+    }
     auto kernel = k_forward_fused_sc3<NCZ, NCU, true, true>;
     if (!p.rxc) kernel = p.ru0 ? k_forward_fused_sc3<NCZ, NCU, true, false> : k_forward_fused_sc3<NCZ, NCU>;
     launch_ff_kernel(kernel, 192, c, F, U_alpha_dev, only_ragged);
@@ -2565,6 +2638,11 @@ static void launch_ff_triple(Ctx *c, const FusedLaunch &p, const FusedArgs &F, d
 template <int NCZ, int NCU, bool RU, bool UNI>
 static void launch_ff_form(Ctx *c, const FusedLaunch &p, const FusedArgs &F, double *U_alpha_dev)
 {
+    if (c->sweep_list) {
+        if (RU && p.rxc) launch_ff_kernel(p.excl ? k_forward_fused_excl_listed<NCZ, NCU, RU, UNI, RU> : k_forward_fused_listed<NCZ, NCU, RU, UNI, RU>, 64, c, F, U_alpha_dev, c->sweep_list);
+        else launch_ff_kernel(p.excl ? k_forward_fused_excl_listed<NCZ, NCU, RU, UNI, false> : k_forward_fused_listed<NCZ, NCU, RU, UNI, false>, 64, c, F, U_alpha_dev, c->sweep_list);
+        return;
+    }
     if (RU && p.rxc) launch_ff_kernel(p.excl ? k_forward_fused_excl<NCZ, NCU, RU, UNI, RU> : k_forward_fused<NCZ, NCU, RU, UNI, RU>, 64, c, F, U_alpha_dev);
     else launch_ff_kernel(p.excl ? k_forward_fused_excl<NCZ, NCU, RU, UNI, false> : k_forward_fused<NCZ, NCU, RU, UNI, false>, 64, c, F, U_alpha_dev);
 }

@@ -101,11 +101,11 @@ size_t backward_generic_lds_bytes(int n, int m)
 __device__ __forceinline__ void
 backward_generic_body(RecLayout L, int T, const double *__restrict__ rec, const double *__restrict__ lambda,
                       int pd_stride, double *__restrict__ Kout, double *__restrict__ kout,
-                      double *__restrict__ delta_J, int *__restrict__ status)
+                      double *__restrict__ delta_J, int *__restrict__ status, const int btraj = blockIdx.x)
 {
     extern __shared__ __attribute__((aligned(16))) double sh[];
     const int n = L.n, m = L.m, tid = threadIdx.x, NT = blockDim.x;
-    const int b = blockIdx.x;
+    const int b = btraj;
     double *Vxx = sh, *AtV = Vxx + n * n, *BtV = AtV + n * n, *Qux = BtV + m * n, *Kt = Qux + m * n,
            *G = Kt + m * n, *Quu = G + m * n, *Qreg = Quu + m * m, *inv = Qreg + m * m, *wa = inv + m * m,
            *wx = wa + m * m, *Vx = wx + m * m, *Qx = Vx + n, *Qu = Qx + n, *kt = Qu + m, *g = kt + m,
@@ -267,6 +267,8 @@ backward_generic_body(RecLayout L, int T, const double *__restrict__ rec, const 
 // over the block, before any LDS write, barrier or role split -- and the whole block leaves where the trajectory is settled or has
 // given up.  The first attempt, and every launch without a schedule, is the kernel without the gate: the same instructions as in a
 // library without the schedule (profiles/lambda_retry.txt has the register counts of both).
+// The twin also runs the sweep of a listed subset (kpilqr_backward_partial): `list` (device, nullptr: every block sweeps its own
+// index) names the trajectory of block i, and the caller has armed the gate of the listed trajectories.
 __global__ void __launch_bounds__(64)
 k_backward_generic(RecLayout L, int T, const double *__restrict__ rec, const double *__restrict__ lambda,
                    int pd_stride, double *__restrict__ Kout, double *__restrict__ kout,
@@ -277,10 +279,11 @@ k_backward_generic(RecLayout L, int T, const double *__restrict__ rec, const dou
 __global__ void __launch_bounds__(64)
 k_backward_generic_retry(RecLayout L, int T, const double *__restrict__ rec, const double *__restrict__ lambda,
                          int pd_stride, double *__restrict__ Kout, double *__restrict__ kout,
-                         double *__restrict__ delta_J, int *__restrict__ status, const int *__restrict__ gate)
+                         double *__restrict__ delta_J, int *__restrict__ status, const int *__restrict__ gate, const int *__restrict__ list)
 {
-    if (gate[blockIdx.x] == 0) return;
-    backward_generic_body(L, T, rec, lambda, pd_stride, Kout, kout, delta_J, status);
+    const int b = kp_block_traj(list, blockIdx.x);
+    if (gate[b] == 0) return;
+    backward_generic_body(L, T, rec, lambda, pd_stride, Kout, kout, delta_J, status, b);
 }
 
 hipError_t launch_backward_generic(Ctx *c, int pd_stride)
@@ -292,7 +295,7 @@ hipError_t launch_backward_generic(Ctx *c, int pd_stride)
     if (e != hipSuccess) return e;
     if (c->bwd_gate)
         hipLaunchKernelGGL(k_backward_generic_retry, dim3(c->d.batch), dim3(64), lds, c->stream, c->L, c->d.T, c->rec,
-                           c->lambda, pd_stride, c->K, c->k, c->delta_J, c->status, c->bwd_gate);
+                           c->lambda, pd_stride, c->K, c->k, c->delta_J, c->status, c->bwd_gate, c->sweep_list);
     else
         hipLaunchKernelGGL(k_backward_generic, dim3(c->d.batch), dim3(64), lds, c->stream, c->L, c->d.T, c->rec,
                            c->lambda, pd_stride, c->K, c->k, c->delta_J, c->status);
@@ -301,16 +304,16 @@ hipError_t launch_backward_generic(Ctx *c, int pd_stride)
 
 // ---------------------------------------------------------------------------------------------
 // a8, generic: one wavefront per (trajectory, alpha).
-__global__ void __launch_bounds__(64)
-k_forward_generic(RecLayout L, int T, int n_alpha, const double *__restrict__ rec,
-                  const double *__restrict__ Kin, const double *__restrict__ kin,
-                  const double *__restrict__ u_nom, const double *__restrict__ ctrl_lim,
-                  const double *__restrict__ alphas, double *__restrict__ cost_pred,
-                  double *__restrict__ U_alpha)
+__device__ __forceinline__ void
+forward_generic_body(RecLayout L, int T, int n_alpha, const double *__restrict__ rec,
+                     const double *__restrict__ Kin, const double *__restrict__ kin,
+                     const double *__restrict__ u_nom, const double *__restrict__ ctrl_lim,
+                     const double *__restrict__ alphas, double *__restrict__ cost_pred,
+                     double *__restrict__ U_alpha, const int b)
 {
     extern __shared__ __attribute__((aligned(16))) double sh[];
     const int n = L.n, m = L.m, tid = threadIdx.x, NT = blockDim.x;
-    const int b = blockIdx.x, a = blockIdx.y;
+    const int a = blockIdx.y;
     double *dx = sh, *dxn = dx + n, *tv = dxn + n, *du = tv + n, *fb = du + m, *tu = fb + m;
     const double alpha = alphas[a];
     for (int i = tid; i < n; i += NT) dx[i] = 0.0;
@@ -367,10 +370,35 @@ k_forward_generic(RecLayout L, int T, int n_alpha, const double *__restrict__ re
     }
     if (tid == 0) cost_pred[(size_t)b * n_alpha + a] = cost;
 }
+// The kernel and its listed twin (kpilqr_forward_linear_partial): block (i, a) of the twin works on trajectory list[i]
+__global__ void __launch_bounds__(64)
+k_forward_generic(RecLayout L, int T, int n_alpha, const double *__restrict__ rec,
+                  const double *__restrict__ Kin, const double *__restrict__ kin,
+                  const double *__restrict__ u_nom, const double *__restrict__ ctrl_lim,
+                  const double *__restrict__ alphas, double *__restrict__ cost_pred,
+                  double *__restrict__ U_alpha)
+{
+    forward_generic_body(L, T, n_alpha, rec, Kin, kin, u_nom, ctrl_lim, alphas, cost_pred, U_alpha, blockIdx.x);
+}
+__global__ void __launch_bounds__(64)
+k_forward_generic_listed(RecLayout L, int T, int n_alpha, const double *__restrict__ rec,
+                         const double *__restrict__ Kin, const double *__restrict__ kin,
+                         const double *__restrict__ u_nom, const double *__restrict__ ctrl_lim,
+                         const double *__restrict__ alphas, double *__restrict__ cost_pred,
+                         double *__restrict__ U_alpha, const int *__restrict__ list)
+{
+    forward_generic_body(L, T, n_alpha, rec, Kin, kin, u_nom, ctrl_lim, alphas, cost_pred, U_alpha, list[blockIdx.x]);
+}
 
 hipError_t launch_forward_generic(Ctx *c, double *U_alpha_dev)
 {
     const size_t lds = sizeof(double) * (3 * c->n + 3 * c->d.m);
+    if (c->sweep_list) {
+        hipLaunchKernelGGL(k_forward_generic_listed, dim3(c->d.batch, c->d.n_alpha), dim3(64), lds, c->stream, c->L, c->d.T,
+                           c->d.n_alpha, c->rec, c->K, c->k, c->u_nom, c->ctrl_lim, c->alphas, c->cost_pred,
+                           U_alpha_dev, c->sweep_list);
+        return hipGetLastError();
+    }
     hipLaunchKernelGGL(k_forward_generic, dim3(c->d.batch, c->d.n_alpha), dim3(64), lds, c->stream, c->L, c->d.T,
                        c->d.n_alpha, c->rec, c->K, c->k, c->u_nom, c->ctrl_lim, c->alphas, c->cost_pred,
                        U_alpha_dev);

@@ -1434,15 +1434,24 @@ static int retry_attempts_for(const kpilqr_ctx *c, const double *lambda, size_t 
 extern "C++" template <class Launch>
 static int sweep_attempts(kpilqr_ctx *c, kpilqr_ctx *lc, Launch launch)
 {
-    lc->bwd_gate = nullptr;
-    if (!c->retry_on) { KP_HIP(c, launch()); return KPILQR_OK; }
-    KP_HIP(c, launch_lambda_retry_begin(c));
+    // A listed launch (lc: make_list_view) runs through the retry twins from its first attempt on -- they take the list beside the
+    // gate -- with the gate armed for the listed trajectories alone; the schedule's two kernels walk the list, not the batch.
+    const bool listed = lc->sweep_list != nullptr;
+    const int *const first_gate = listed ? (const int *)c->gate : nullptr;
+    kpilqr_ctx *const rc = listed ? lc : c;
+    lc->bwd_gate = first_gate;
+    if (!c->retry_on) {
+        if (listed) KP_HIP(c, launch_gate_arm(lc));
+        KP_HIP(c, launch());
+        return KPILQR_OK;
+    }
+    KP_HIP(c, launch_lambda_retry_begin(rc));
     KP_HIP(c, launch());
     for (int a = 1; a < c->retry_attempts; a++) {
-        KP_HIP(c, launch_lambda_retry(c));
+        KP_HIP(c, launch_lambda_retry(rc));
         lc->bwd_gate = c->gate;
         const hipError_t e = launch();
-        lc->bwd_gate = nullptr;
+        lc->bwd_gate = first_gate;
         KP_HIP(c, e);
     }
     c->retry_ran = true;
@@ -1451,6 +1460,7 @@ static int sweep_attempts(kpilqr_ctx *c, kpilqr_ctx *lc, Launch launch)
 
 static int run_backward(kpilqr_ctx *c, int pd_stride)
 {
+    c->last_width[0] = -1;
     if (c->fused) {
         int rc = check_fused(c);
         if (rc) return rc;
@@ -1784,6 +1794,7 @@ int kpilqr_download_gains_f32_partial(kpilqr_ctx *c, int count, const int *traj,
 
 static int run_forward(kpilqr_ctx *c, double *U_dev)
 {
+    c->last_width[1] = -1;
     if (c->fused) {
         int rc = check_fused(c);
         if (rc) return rc;
@@ -1860,6 +1871,207 @@ int kpilqr_iterate(kpilqr_ctx *c, const double *lambda, int pd_check_stride, con
     int rc = run_backward(c, pd_check_stride);
     if (rc) return rc;
     return run_forward(c, nullptr);
+}
+
+// ---- the sweeps over a listed subset of the batch (include/kpilqr.h, "Sweeps of a subset") ---------------------------------------------
+// A copy of the context for the launchers, as make_view's: d.batch is the list's length -- the launch width, by which the launchers and
+// the fused plans choose what only arranges waves -- sweep_list the device copy of the list; every per-trajectory pointer stays the
+// context's, block i finds its trajectory through the list.  n_simd stays the chip's: a listed launch has it to itself.  Made AFTER
+// everything that may allocate: it borrows the pointers.
+static void make_list_view(const kpilqr_ctx *c, int count, kpilqr_ctx *v)
+{
+    *v = *c;
+    v->is_view = true;
+    v->own_stream = false;
+    v->d.batch = count;
+    v->sweep_list = c->traj_list;
+}
+
+// the compact staging regions of a listed call with `count` rows, inside sweep_stage
+struct SweepStage { double *lambda, *delta_J, *cost_pred; int *status; };
+static int sweep_stage_of(kpilqr_ctx *c, int count, SweepStage *s)
+{
+    const size_t na = c->d.n_alpha, n8 = (size_t)count * 8;
+    const int rc = reserve(c, c->sweep_stage, n8 * (2 + na) + (size_t)count * 4, kExact, false);
+    if (rc < 0) return rc;
+    char *p = c->sweep_stage;
+    s->lambda = (double *)p; s->delta_J = (double *)(p + n8); s->cost_pred = (double *)(p + 2 * n8); s->status = (int *)(p + n8 * (2 + na));
+    return KPILQR_OK;
+}
+
+// everything a listed sweep refuses, before anything is enqueued or changed; -> 1: go on, as enter_subset
+static int enter_sweep_subset(kpilqr_ctx *c, const char *who, int count, const int *traj, bool backward, int pd_check_stride)
+{
+    const int go = enter_subset(c, who, count, traj);
+    if (go <= 0) return go;
+    if (backward && pd_check_stride < 1) return set_err(c, KPILQR_ERR_ARG, "pd_check_stride must be >= 1");
+    { const int rcp = check_complete(c, who); if (rcp) return rcp; }
+    if (c->fused) { const int rcf = check_fused(c); if (rcf) return rcf; }
+    return 1;
+}
+
+// Fused contexts: a listed sweep reads the column store and never differences inside the sweep; a store that is not valid is
+// differenced for the whole batch first (kpilqr_fd_difference's launch, with the slopes per-DoF lists need) and is then valid for everybody.
+static int columns_for_listed_sweep(kpilqr_ctx *c)
+{
+    int rc = ensure_kpc(c);
+    if (rc) return rc;
+    rc = ensure_kps(c);
+    if (rc) return rc;
+    if (!c->pay.kpc_valid) { rc = difference_to_kpc(c); if (rc) return rc; }
+    if (c->pay.kpc_valid) { rc = slopes_for_kpc(c); if (rc) return rc; }
+    return KPILQR_OK;
+}
+
+// the list is on the device (traj_list) and checked
+static int run_backward_listed(kpilqr_ctx *c, int count, int pd_stride)
+{
+    kpilqr_ctx v;
+    if (c->fused) {
+        int rc = columns_for_listed_sweep(c);
+        if (rc) return rc;
+        make_list_view(c, count, &v);
+        const FusedLaunch plan = c->last_bwd = plan_backward_fused(&v, false);
+        if (!plan.rxc) { rc = ensure_rx_buffer(c); if (rc) return rc; make_list_view(c, count, &v); }
+        c->last_width[0] = count;
+        return sweep_attempts(c, &v, [&] { return launch_backward_fused(&v, plan, pd_stride); });
+    }
+    c->last_bwd = FusedLaunch{};
+    if (c->tiled_a6) { const int rc = ensure_rx_buffer(c); if (rc) return rc; }
+    make_list_view(c, count, &v);
+    c->last_width[0] = count;
+    return sweep_attempts(c, &v, [&] {
+        switch (c->bwd_family) {
+        case Family::t1: return launch_backward_mfma(&v, pd_stride);
+        case Family::tiled: return launch_backward_tiled(&v, pd_stride);
+        case Family::wide: return launch_backward_wide(&v, pd_stride);
+        default: return launch_backward_generic(&v, pd_stride);
+        }
+    });
+}
+
+static int run_forward_listed(kpilqr_ctx *c, int count, double *U_dev)
+{
+    kpilqr_ctx v;
+    if (c->fused) {
+        int rc = columns_for_listed_sweep(c);
+        if (rc) return rc;
+        make_list_view(c, count, &v);
+        const FusedLaunch plan = c->last_fwd = plan_forward_fused(&v);
+        if (!plan.rxc) { rc = ensure_rx_buffer(c); if (rc) return rc; make_list_view(c, count, &v); }
+        c->last_width[1] = count;
+        KP_HIP(c, launch_forward_fused(&v, plan, U_dev));
+        return KPILQR_OK;
+    }
+    c->last_fwd = FusedLaunch{};
+    if (c->tiled_a6) { const int rc = ensure_rx_buffer(c); if (rc) return rc; }
+    make_list_view(c, count, &v);
+    c->last_width[1] = count;
+    switch (c->fwd_family) {
+    case Family::t1: KP_HIP(c, launch_forward_mfma(&v, U_dev)); break;
+    case Family::tiled: KP_HIP(c, launch_forward_tiled(&v, U_dev)); break;
+    case Family::wide: KP_HIP(c, launch_forward_wide(&v, U_dev)); break;
+    default: KP_HIP(c, launch_forward_generic(&v, U_dev)); break;
+    }
+    return KPILQR_OK;
+}
+
+// the list and the compact lambdas to the device; the lambdas placed by ONE launch
+static int listed_inputs(kpilqr_ctx *c, int count, const int *traj, const double *lambda, const SweepStage &st)
+{
+    KP_HIP(c, hipMemcpyAsync(c->traj_list, traj, (size_t)count * sizeof(int), hipMemcpyHostToDevice, c->stream));
+    if (lambda) {
+        KP_HIP(c, hipMemcpyAsync(st.lambda, lambda, (size_t)count * 8, hipMemcpyHostToDevice, c->stream));
+        KP_HIP(c, launch_rows_in(c->stream, c->traj_list, count, 1, st.lambda, c->lambda));
+    }
+    return KPILQR_OK;
+}
+
+static int backward_listed(kpilqr_ctx *c, int count, const int *traj, const double *lambda, int pd_check_stride, int *status, double *delta_J)
+{
+    SweepStage st;
+    int rc = sweep_stage_of(c, count, &st);
+    if (rc) return rc;
+    rc = listed_inputs(c, count, traj, lambda, st);
+    if (rc) return rc;
+    c->retry_attempts = retry_attempts_for(c, lambda, (size_t)count);
+    rc = run_backward_listed(c, count, pd_check_stride);
+    if (rc) return rc;
+    if (status) {
+        KP_HIP(c, launch_rows_out(c->stream, c->traj_list, count, 1, (const int *)c->status, st.status));
+        KP_HIP(c, hipMemcpyAsync(status, st.status, (size_t)count * 4, hipMemcpyDeviceToHost, c->stream));
+    }
+    if (delta_J) {
+        KP_HIP(c, launch_rows_out(c->stream, c->traj_list, count, 2, (const double *)c->delta_J, st.delta_J));
+        KP_HIP(c, hipMemcpyAsync(delta_J, st.delta_J, (size_t)count * 8, hipMemcpyDeviceToHost, c->stream));
+    }
+    return KPILQR_OK;
+}
+
+static int forward_listed(kpilqr_ctx *c, int count, const int *traj, bool list_resident, const double *alphas, double *cost_pred, double *U_alpha)
+{
+    const size_t B = c->d.batch, T = c->d.T, m = c->d.m, na = c->d.n_alpha;
+    SweepStage st;
+    int rc = sweep_stage_of(c, count, &st);
+    if (rc) return rc;
+    if (!list_resident) KP_HIP(c, hipMemcpyAsync(c->traj_list, traj, (size_t)count * sizeof(int), hipMemcpyHostToDevice, c->stream));
+    if (alphas) KP_HIP(c, hipMemcpyAsync(c->alphas, alphas, na * 8, hipMemcpyHostToDevice, c->stream));
+    double *U_dev = nullptr;
+    if (U_alpha) {              // (debug output: the sweep writes a trajectory's controls at its own place of a whole-batch staging area)
+        rc = ensure_stage(c, B * na * T * m * 8);
+        if (rc) return rc;
+        U_dev = c->stage;
+    }
+    rc = run_forward_listed(c, count, U_dev);
+    if (rc) return rc;
+    if (cost_pred) {
+        KP_HIP(c, launch_rows_out(c->stream, c->traj_list, count, 2 * (int)na, (const double *)c->cost_pred, st.cost_pred));
+        KP_HIP(c, hipMemcpyAsync(cost_pred, st.cost_pred, (size_t)count * na * 8, hipMemcpyDeviceToHost, c->stream));
+    }
+    if (U_alpha) {
+        const size_t per = na * T * m;
+        rc = kp_for_each_run(count, traj, [&](int i, int b0, int run) -> int {
+            KP_HIP(c, hipMemcpyAsync(U_alpha + (size_t)i * per, U_dev + (size_t)b0 * per, (size_t)run * per * 8, hipMemcpyDeviceToHost, c->stream));
+            return KPILQR_OK;
+        });
+        if (rc) return rc;
+    }
+    return KPILQR_OK;
+}
+
+int kpilqr_backward_partial(kpilqr_ctx *c, int count, const int *traj, const double *lambda, int pd_check_stride, int *status, double *delta_J)
+{
+    const int go = enter_sweep_subset(c, "kpilqr_backward_partial", count, traj, true, pd_check_stride);
+    if (go <= 0) return go;
+    const int rc = backward_listed(c, count, traj, lambda, pd_check_stride, status, delta_J);
+    return rc ? rc : wait_unless_pinned(c, traj);
+}
+
+int kpilqr_forward_linear_partial(kpilqr_ctx *c, int count, const int *traj, const double *alphas, double *cost_pred, double *U_alpha)
+{
+    const int go = enter_sweep_subset(c, "kpilqr_forward_linear_partial", count, traj, false, 1);
+    if (go <= 0) return go;
+    const int rc = forward_listed(c, count, traj, false, alphas, cost_pred, U_alpha);
+    return rc ? rc : wait_unless_pinned(c, traj);
+}
+
+// kpilqr_iterate for the listed trajectories.  A context with records: kpilqr_fd_interpolate_partial, kpilqr_cost_derivs_partial (not
+// where the tiled sweeps form the cost derivatives themselves), then the two sweeps; a fused context: the two sweeps.
+int kpilqr_iterate_partial(kpilqr_ctx *c, int count, const int *traj, const double *lambda, int pd_check_stride, const double *alphas)
+{
+    const int go = enter_sweep_subset(c, "kpilqr_iterate_partial", count, traj, true, pd_check_stride);
+    if (go <= 0) return go;
+    if (!c->have_kp) return set_err(c, KPILQR_ERR_STATE, "kpilqr_iterate_partial before kpilqr_set_keypoints");
+    if (!c->fused) {
+        int rcl = kpilqr_fd_interpolate_partial(c, count, traj);
+        if (rcl) return rcl;
+        if (!c->tiled_a6) { rcl = kpilqr_cost_derivs_partial(c, count, traj); if (rcl) return rcl; }
+    }
+    else c->last_linearise = "in_sweep:subset";
+    int rc = backward_listed(c, count, traj, lambda, pd_check_stride, nullptr, nullptr);
+    if (rc) return rc;
+    rc = forward_listed(c, count, traj, true, alphas, nullptr, nullptr);
+    return rc ? rc : wait_unless_pinned(c, traj);
 }
 
 // ---- whole iteration, pipelined over chunks of trajectories ------------------------------------------------------------
@@ -2594,6 +2806,8 @@ const char *kpilqr_forward_variant(kpilqr_ctx *c) { return c ? variant_name(c->f
 // which = 2: the linearisation stage (a2 + a4) of the last kpilqr_fd_interpolate / kpilqr_iterate / kpilqr_iterate_streamed:
 //   fd_kp_interpolate | kp_columns_interpolate (one pass, linearise.hip) | fd_difference+interpolate | in_sweep (fused context) |
 //   kp_union (fused context, sweeps on the union store)
+// ":subset" comes last where the launch was a listed one (kpilqr_backward_partial, kpilqr_forward_linear_partial, kpilqr_iterate_partial):
+// the tokens before it are the form the list's length chose.
 const char *kpilqr_last_launch(kpilqr_ctx *c, int which)
 {
     if (c && which == 2) return c->last_linearise;
@@ -2604,7 +2818,11 @@ const char *kpilqr_last_launch(kpilqr_ctx *c, int which)
     if (p.waves == Waves::none) {
         if (c->fused) { out += ":none"; return out.c_str(); }
         // the two-tile forward sweep on materialised tiles: one wave per row tile, or state / cost wave groups (small batches)
-        if (which == 1 && c->fwd_family == Family::tiled && !c->tiled_a6 && forward_tiled_sc_selected(c)) out += ":state_cost_waves";
+        // (a listed launch chose by its own width)
+        Ctx w = *c;
+        if (c->last_width[which] >= 0) w.d.batch = c->last_width[which];
+        if (which == 1 && c->fwd_family == Family::tiled && !c->tiled_a6 && forward_tiled_sc_selected(&w)) out += ":state_cost_waves";
+        if (c->last_width[which] >= 0) out += ":subset";
         return out.c_str();
     }
     int uni = 0;
@@ -2622,6 +2840,7 @@ const char *kpilqr_last_launch(kpilqr_ctx *c, int which)
     if (p.rxc) out += ":rxc";
     if (!uni && p.slopes) out += ":slopes";
     if (p.uni_on_union) out += ":union";
+    if (c->last_width[which] >= 0) out += ":subset";
     return out.c_str();
 }
 

@@ -50,9 +50,54 @@ k_lambda_retry(int batch, double factor, double max_lambda, const int *__restric
     gate[b] = again;
 }
 
+// The same two for a listed launch (kpilqr_backward_partial; Ctx::sweep_list, d.batch entries): thread i works on trajectory list[i],
+// so an unlisted trajectory -- whose status may well be non-zero from an earlier sweep -- is never armed, and no word of its
+// lambda, attempts or gate is written.  The listed sweeps look at the gates of listed trajectories only.
+__global__ void __launch_bounds__(KPLR_THREADS)
+k_lambda_retry_begin_listed(int count, const int *__restrict__ list, int *__restrict__ attempts, int *__restrict__ gate)
+{
+    const int i = blockIdx.x * KPLR_THREADS + threadIdx.x;
+    if (i >= count) return;
+    const int b = list[i];
+    if (attempts) attempts[b] = 1;           // (nullptr: no schedule, the gate alone is armed -- launch_gate_arm)
+    gate[b] = 1;
+}
+__global__ void __launch_bounds__(KPLR_THREADS)
+k_lambda_retry_listed(int count, const int *__restrict__ list, double factor, double max_lambda, const int *__restrict__ status,
+                      double *__restrict__ lambda, int *__restrict__ attempts, int *__restrict__ gate)
+{
+    const int i = blockIdx.x * KPLR_THREADS + threadIdx.x;
+    if (i >= count) return;
+    const int b = list[i];
+    if (gate[b] == 0) return;
+    int again = 0;
+    if (status[b] != 0) {
+        const double next = lambda[b] * factor;
+        if (!(next > max_lambda)) {
+            lambda[b] = next;
+            attempts[b] += 1;
+            again = 1;
+        }
+    }
+    gate[b] = again;
+}
+
+hipError_t launch_gate_arm(Ctx *c)
+{
+    if (c->d.batch <= 0 || !c->sweep_list) return hipSuccess;
+    hipLaunchKernelGGL(k_lambda_retry_begin_listed, dim3((c->d.batch + KPLR_THREADS - 1) / KPLR_THREADS), dim3(KPLR_THREADS), 0, c->stream,
+                       c->d.batch, c->sweep_list, (int *)nullptr, (int *)c->gate);
+    return hipGetLastError();
+}
+
 hipError_t launch_lambda_retry_begin(Ctx *c)
 {
     if (c->d.batch <= 0) return hipSuccess;
+    if (c->sweep_list) {
+        hipLaunchKernelGGL(k_lambda_retry_begin_listed, dim3((c->d.batch + KPLR_THREADS - 1) / KPLR_THREADS), dim3(KPLR_THREADS), 0, c->stream,
+                           c->d.batch, c->sweep_list, (int *)c->attempts, (int *)c->gate);
+        return hipGetLastError();
+    }
     hipLaunchKernelGGL(k_lambda_retry_begin, dim3((c->d.batch + KPLR_THREADS - 1) / KPLR_THREADS), dim3(KPLR_THREADS), 0, c->stream, c->d.batch,
                        (int *)c->attempts, (int *)c->gate);
     return hipGetLastError();
@@ -61,6 +106,12 @@ hipError_t launch_lambda_retry_begin(Ctx *c)
 hipError_t launch_lambda_retry(Ctx *c)
 {
     if (c->d.batch <= 0) return hipSuccess;
+    if (c->sweep_list) {
+        hipLaunchKernelGGL(k_lambda_retry_listed, dim3((c->d.batch + KPLR_THREADS - 1) / KPLR_THREADS), dim3(KPLR_THREADS), 0, c->stream,
+                           c->d.batch, c->sweep_list, c->retry.factor, c->retry.max_lambda, (const int *)c->status, (double *)c->lambda,
+                           (int *)c->attempts, (int *)c->gate);
+        return hipGetLastError();
+    }
     hipLaunchKernelGGL(k_lambda_retry, dim3((c->d.batch + KPLR_THREADS - 1) / KPLR_THREADS), dim3(KPLR_THREADS), 0, c->stream, c->d.batch,
                        c->retry.factor, c->retry.max_lambda, (const int *)c->status, (double *)c->lambda, (int *)c->attempts, (int *)c->gate);
     return hipGetLastError();

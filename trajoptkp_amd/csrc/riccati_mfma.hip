@@ -121,14 +121,14 @@ template <int R> __device__ __forceinline__ void set_reg(d4 &v, double x) { if (
 template <int N, int M, int ABL>
 __device__ __forceinline__ void backward_body(RecLayout L, int T, const double *__restrict__ rec, const double *__restrict__ lambda,
                 int pd_stride, double *__restrict__ Kout, double *__restrict__ kout,
-                double *__restrict__ delta_J, int *__restrict__ status)
+                double *__restrict__ delta_J, int *__restrict__ status, const int btraj = blockIdx.x)
 {
     constexpr int NCZ = (N + 1 + 3) / 4;      // row chunks covering z = [dx; 1]
     constexpr int NCU = (M + 3) / 4;          // row chunks covering u
     constexpr int n = N, m = M;
     __shared__ __attribute__((aligned(16))) double sh[LDS_TOTAL];
     const int lane = threadIdx.x, c = lane & 15, q = lane >> 4;
-    const int b = blockIdx.x;
+    const int b = btraj;                      // (the block's own index but in a listed launch: see k_backward_mfma_retry)
     const double lam = lambda[b];
 
     TileOffs o;
@@ -374,25 +374,29 @@ k_backward_mfma_excl(RecLayout L, int T, const double *__restrict__ rec, const d
 
 // The lambda retry twins (kpilqr_set_lambda_retry, lambda_retry.hip): the attempts behind the first of a backward pass under a schedule.
 // A wave whose trajectory is settled or has given up leaves at once; the first attempt, and every launch without a schedule, is one
-// of the two kernels above, unchanged.
+// of the two kernels above, unchanged.  The twins also run the sweeps of a listed subset (kpilqr_backward_partial): `list` (device,
+// nullptr: every block sweeps its own index) names the trajectory of block i -- a scalar load off a kernel argument, wave-uniform --
+// and the caller has armed the gate of the listed trajectories.
 template <int N, int M>
 __global__ void __launch_bounds__(64)
 k_backward_mfma_retry(RecLayout L, int T, const double *__restrict__ rec, const double *__restrict__ lambda,
                       int pd_stride, double *__restrict__ Kout, double *__restrict__ kout,
-                      double *__restrict__ delta_J, int *__restrict__ status, const int *__restrict__ gate)
+                      double *__restrict__ delta_J, int *__restrict__ status, const int *__restrict__ gate, const int *__restrict__ list)
 {
-    if (gate[blockIdx.x] == 0) return;
-    backward_body<N, M, 0>(L, T, rec, lambda, pd_stride, Kout, kout, delta_J, status);
+    const int b = kp_block_traj(list, blockIdx.x);
+    if (gate[b] == 0) return;
+    backward_body<N, M, 0>(L, T, rec, lambda, pd_stride, Kout, kout, delta_J, status, b);
 }
 
 template <int N, int M>
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1)))
 k_backward_mfma_excl_retry(RecLayout L, int T, const double *__restrict__ rec, const double *__restrict__ lambda,
                            int pd_stride, double *__restrict__ Kout, double *__restrict__ kout,
-                           double *__restrict__ delta_J, int *__restrict__ status, const int *__restrict__ gate)
+                           double *__restrict__ delta_J, int *__restrict__ status, const int *__restrict__ gate, const int *__restrict__ list)
 {
-    if (gate[blockIdx.x] == 0) return;
-    backward_body<N, M, 0>(L, T, rec, lambda, pd_stride, Kout, kout, delta_J, status);
+    const int b = kp_block_traj(list, blockIdx.x);
+    if (gate[b] == 0) return;
+    backward_body<N, M, 0>(L, T, rec, lambda, pd_stride, Kout, kout, delta_J, status, b);
 }
 
 bool backward_mfma_supported(int n, int m)
@@ -407,7 +411,7 @@ static hipError_t launch_bm(Ctx *c, int pd_stride)
     if (c->bwd_gate) {
         const auto twin = c->d.batch <= c->n_simd ? k_backward_mfma_excl_retry<NN, MM> : k_backward_mfma_retry<NN, MM>;
         hipLaunchKernelGGL(twin, dim3(c->d.batch), dim3(64), 0, c->stream, c->L, c->d.T, c->rec, c->lambda, pd_stride, c->K, c->k,
-                           c->delta_J, c->status, c->bwd_gate);
+                           c->delta_J, c->status, c->bwd_gate, c->sweep_list);
         return hipGetLastError();
     }
     const auto kernel = c->d.batch <= c->n_simd ? k_backward_mfma_excl<NN, MM> : k_backward_mfma<NN, MM>;

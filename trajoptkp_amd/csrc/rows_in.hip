@@ -67,6 +67,28 @@ k_rows_in_entries(int count, const int *__restrict__ traj, int dof, long long up
     }
 }
 
+// The mirror image for the listed sweeps (kpilqr_backward_partial, kpilqr_forward_linear_partial): the listed trajectories' rows of a small
+// per-trajectory output (status: one int; delta_J: one double; cost_pred: n_alpha doubles) gathered into a compact staging array that
+// leaves with ONE copy, however scattered the list is.  Rows of a few 4-byte words: one thread per word, a pure copy.
+__global__ void __launch_bounds__(KPR_THREADS)
+k_rows_out(int count, const int *__restrict__ traj, int words, const unsigned *__restrict__ src, unsigned *__restrict__ dst)
+{
+    const long long total = (long long)count * words;
+    for (long long g = (long long)blockIdx.x * KPR_THREADS + threadIdx.x; g < total; g += (long long)gridDim.x * KPR_THREADS) {
+        const long long i = g / words, p = g - i * words;
+        dst[g] = src[(long long)traj[i] * words + p];
+    }
+}
+
+hipError_t launch_rows_out(hipStream_t s, const int *traj_dev, int count, int words, const void *src, void *staging)
+{
+    if (count <= 0 || words <= 0) return hipSuccess;
+    const long long total = (long long)count * words;
+    const int blocks = (int)((total + KPR_THREADS - 1) / KPR_THREADS < 32 ? (total + KPR_THREADS - 1) / KPR_THREADS : 32);
+    hipLaunchKernelGGL(k_rows_out, dim3(blocks), dim3(KPR_THREADS), 0, s, count, traj_dev, words, (const unsigned *)src, (unsigned *)staging);
+    return hipGetLastError();
+}
+
 // `count` rows of `units` doubles: row i of `staging` (device) -> row traj[i] (traj on the device) of dst, on stream s
 hipError_t launch_rows_in(hipStream_t s, const int *traj_dev, int count, long long units, const double *staging, double *dst)
 {

@@ -207,13 +207,16 @@ __device__ __forceinline__ d4 ld_Ru(__amdgpu_buffer_rsrc_t rs, int m, int nr, in
 // over the block, before any LDS write or barrier -- and the whole block leaves where the trajectory is settled or has
 // given up.  GATED = false is the kernel of the first attempt and of every launch without a schedule: `gate` is not read, and the
 // instructions are those of a library without the schedule (profiles/lambda_retry.txt has the register counts of both).
+// The GATED twin also runs the sweep of a listed subset (kpilqr_backward_partial): `list` (device, nullptr: every block sweeps its own
+// index; never read with GATED = false) names the trajectory of block i -- a scalar load off a kernel argument, uniform over the
+// block -- and the caller has armed the gate of the listed trajectories.
 template <int M, int NT, bool A6, int NCL = 0, bool GATED = false>
 __global__ void __launch_bounds__(64 * NT)
 k_backward_tiled_col(RecLayout L, CostSrc CS, int T, const double *__restrict__ rec, const double *__restrict__ lambda,
                      int pd_stride, double *__restrict__ Kout, double *__restrict__ kout,
-                     double *__restrict__ delta_J, int *__restrict__ status, const int *__restrict__ gate)
+                     double *__restrict__ delta_J, int *__restrict__ status, const int *__restrict__ gate, const int *__restrict__ list)
 {
-    if constexpr (GATED) { if (gate[KP_TILED_TRAJ] == 0) return; }
+    if constexpr (GATED) { if (gate[kp_block_traj(list, KP_TILED_TRAJ)] == 0) return; }
     extern __shared__ __attribute__((aligned(16))) double sh[];
     constexpr int NCU = (M + 3) / 4;
     constexpr int NZZ = NT * NT;
@@ -228,7 +231,7 @@ k_backward_tiled_col(RecLayout L, CostSrc CS, int T, const double *__restrict__ 
     const int n = L.n, m = PAD ? L.m : M, nz = n + 1;
     const int lane = threadIdx.x & 63, c = lane & 15, q = lane >> 4;
     const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);    // this wave's column tile (wave-uniform)
-    const int b = KP_TILED_TRAJ;
+    const int b = GATED ? kp_block_traj(list, KP_TILED_TRAJ) : KP_TILED_TRAJ;
     const double lam = lambda[b];
     double *bufV = sh;                               // V' (NT x NT tiles, tile (i,j) at i*NT+j)
     double *bufF = bufV + NZZ * TILE;                // Fz
@@ -691,9 +694,9 @@ template <int M, int NT, int NCL, bool GATED = false>
 __global__ void __launch_bounds__(64 * (NT + 1))
 k_backward_tiled_uw(RecLayout L, int T, const double *__restrict__ rec, const double *__restrict__ lambda,
                     int pd_stride, double *__restrict__ Kout, double *__restrict__ kout,
-                    double *__restrict__ delta_J, int *__restrict__ status, const int *__restrict__ gate)
+                    double *__restrict__ delta_J, int *__restrict__ status, const int *__restrict__ gate, const int *__restrict__ list)
 {
-    if constexpr (GATED) { if (gate[KP_TILED_TRAJ] == 0) return; }
+    if constexpr (GATED) { if (gate[kp_block_traj(list, KP_TILED_TRAJ)] == 0) return; }
     extern __shared__ __attribute__((aligned(16))) double sh[];
     constexpr int NCU = (M + 3) / 4;
     constexpr int NZZ = NT * NT;
@@ -702,7 +705,7 @@ k_backward_tiled_uw(RecLayout L, int T, const double *__restrict__ rec, const do
     const int lane = threadIdx.x & 63, c = lane & 15, q = lane >> 4;
     const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);    // column tile of this wave; NT: the u-wave
     const bool uw = (w == NT);
-    const int b = KP_TILED_TRAJ;
+    const int b = GATED ? kp_block_traj(list, KP_TILED_TRAJ) : KP_TILED_TRAJ;
     const double lam = lambda[b];
     double *bufV = sh;
     double *bufF = bufV + NZZ * TILE;
@@ -1090,7 +1093,7 @@ static hipError_t launch_bt_uw2(Ctx *c, int pd_stride)
     hipError_t e = hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldc);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(kernel, dim3(c->d.batch), dim3(64 * (NT + 1)), ldc, c->stream, c->L, c->d.T, c->rec,
-                       c->lambda, pd_stride, c->K, c->k, c->delta_J, c->status, c->bwd_gate);
+                       c->lambda, pd_stride, c->K, c->k, c->delta_J, c->status, c->bwd_gate, c->sweep_list);
     return hipGetLastError();
 }
 template <int M, int NT>
@@ -1117,7 +1120,7 @@ static hipError_t launch_bt3(Ctx *c, int pd_stride)
     if (e != hipSuccess) return e;
     const CostSrc CS = {c->r, c->r_x, c->r_u, c->w_run, c->w_term, c->d.nr};
     hipLaunchKernelGGL(kernel, dim3(c->d.batch), dim3(64 * NT), ldc, c->stream, c->L, CS, c->d.T, c->rec,
-                       c->lambda, pd_stride, c->K, c->k, c->delta_J, c->status, c->bwd_gate);
+                       c->lambda, pd_stride, c->K, c->k, c->delta_J, c->status, c->bwd_gate, c->sweep_list);
     return hipGetLastError();
 }
 template <int M, int NT, bool A6>
@@ -1158,11 +1161,14 @@ hipError_t launch_backward_tiled(Ctx *c, int pd_stride)
 // Z tiles are exchanged through a double-buffered LDS image with ONE s_barrier per time-step.
 // NCL > 0: chunk count of the last row tile at compile time, the two accumulation chains of a step (state cost rows Lc Z, next
 // state Ya Z) issued interleaved; NCL = 0: run-time count, one chain after the other (see k_backward_tiled_uw).
-template <int NT, bool A6, int NCL = 0>
+// LISTED: the kernel's twin for a listed subset (kpilqr_forward_linear_partial): block i sweeps trajectory list[i] -- a scalar load
+// off a kernel argument, uniform over the block.  LISTED = false is the kernel of every whole-batch call: `list` is not read.
+template <int NT, bool A6, int NCL = 0, bool LISTED = false>
 __global__ void __launch_bounds__(64 * NT)
 k_forward_tiled(RecLayout L, CostSrc CS, int T, int n_alpha, const double *__restrict__ rec, const double *__restrict__ Kin,
                 const double *__restrict__ kin, const double *__restrict__ u_nom, const double *__restrict__ ctrl_lim,
-                const double *__restrict__ alphas, double *__restrict__ cost_pred, double *__restrict__ U_alpha)
+                const double *__restrict__ alphas, double *__restrict__ cost_pred, double *__restrict__ U_alpha,
+                const int *__restrict__ list)
 {
     extern __shared__ __attribute__((aligned(16))) double fsh[];
     double (*zbuf)[NT * TILE] = (double (*)[NT * TILE])fsh;                 // [2][NT * TILE]
@@ -1172,7 +1178,7 @@ k_forward_tiled(RecLayout L, CostSrc CS, int T, int n_alpha, const double *__res
     const int n = L.n, m = L.m, nz2 = n + 2;
     const int lane = threadIdx.x & 63, c = lane & 15, q = lane >> 4;
     const int wi = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // this wave's row tile (wave-uniform)
-    const int b = KP_TILED_TRAJ;
+    const int b = LISTED ? list[blockIdx.x] : KP_TILED_TRAJ;
     const int ncu = (m + 3) >> 2;
     auto nchunk = [&](int kt) { const int rows = nz2 - 16 * kt; return rows >= 16 ? 4 : (rows + 3) / 4; };
     const int ncl = nchunk(NT - 1);
@@ -1739,11 +1745,13 @@ __device__ __forceinline__ void ft_state_role(double *zring, double *upart, doub
     __syncthreads(); __syncthreads();                                    // the tick in which the cost waves score step T-1
 }
 
-template <int NT, int NCL, int NCU>
+// LISTED: as in k_forward_tiled
+template <int NT, int NCL, int NCU, bool LISTED = false>
 __global__ void __launch_bounds__(128 * NT)
 k_forward_tiled_sc(RecLayout L, int T, int n_alpha, const double *__restrict__ rec, const double *__restrict__ Kin,
                    const double *__restrict__ kin, const double *__restrict__ u_nom, const double *__restrict__ ctrl_lim,
-                   const double *__restrict__ alphas, double *__restrict__ cost_pred, double *__restrict__ U_alpha)
+                   const double *__restrict__ alphas, double *__restrict__ cost_pred, double *__restrict__ U_alpha,
+                   const int *__restrict__ list)
 {
     static_assert(NT == 2, "the role dispatch below is written for two row tiles");
     extern __shared__ __attribute__((aligned(16))) double fsh[];
@@ -1756,7 +1764,7 @@ k_forward_tiled_sc(RecLayout L, int T, int n_alpha, const double *__restrict__ r
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const bool is_state = wv < NT;
     const int wi = is_state ? wv : wv - NT;                                  // this wave's row tile (wave-uniform)
-    const int b = KP_TILED_TRAJ;
+    const int b = LISTED ? list[blockIdx.x] : KP_TILED_TRAJ;
     // a tile whose every register is dead (m > 4 NCU cannot happen: the launcher picks NCU from m) keeps the LDS images clean:
     // the slots read with fewer registers than a tile has are the ones written with as few
     if (is_state) {
@@ -1870,12 +1878,13 @@ static hipError_t launch_ft3(Ctx *c, double *U_alpha_dev)
 {
     const CostSrc CS = {c->r, c->r_x, c->r_u, c->w_run, c->w_term, c->d.nr};
     const size_t lds = sizeof(double) * ((size_t)(3 + (A6 ? 1 : 0)) * NT * TILE + NT * 64);
+    const auto kernel = c->sweep_list ? k_forward_tiled<NT, A6, NCL, true> : k_forward_tiled<NT, A6, NCL, false>;
     if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute((const void *)k_forward_tiled<NT, A6, NCL>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        hipError_t e = hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return e;
     }
-    hipLaunchKernelGGL((k_forward_tiled<NT, A6, NCL>), dim3(c->d.batch), dim3(64 * NT), lds, c->stream, c->L, CS, c->d.T,
-                       c->d.n_alpha, c->rec, c->K, c->k, c->u_nom, c->ctrl_lim, c->alphas, c->cost_pred, U_alpha_dev);
+    hipLaunchKernelGGL(kernel, dim3(c->d.batch), dim3(64 * NT), lds, c->stream, c->L, CS, c->d.T,
+                       c->d.n_alpha, c->rec, c->K, c->k, c->u_nom, c->ctrl_lim, c->alphas, c->cost_pred, U_alpha_dev, c->sweep_list);
     return hipGetLastError();
 }
 template <int NT, bool A6>
@@ -1898,8 +1907,9 @@ static hipError_t launch_ft_sc2(Ctx *c, double *U_alpha_dev)
 {
     const size_t lds = sizeof(double) * ((size_t)(4 * NT + 2) * TILE + NT * 64);
     // the LDS images are read with the register counts they are written with; what lies beyond is never read -- but start clean
-    hipLaunchKernelGGL((k_forward_tiled_sc<NT, NCL, NCU>), dim3(c->d.batch), dim3(128 * NT), lds, c->stream, c->L, c->d.T, c->d.n_alpha, c->rec, c->K, c->k,
-                       c->u_nom, c->ctrl_lim, c->alphas, c->cost_pred, U_alpha_dev);
+    const auto kernel = c->sweep_list ? k_forward_tiled_sc<NT, NCL, NCU, true> : k_forward_tiled_sc<NT, NCL, NCU, false>;
+    hipLaunchKernelGGL(kernel, dim3(c->d.batch), dim3(128 * NT), lds, c->stream, c->L, c->d.T, c->d.n_alpha, c->rec, c->K, c->k,
+                       c->u_nom, c->ctrl_lim, c->alphas, c->cost_pred, U_alpha_dev, c->sweep_list);
     return hipGetLastError();
 }
 template <int NT>

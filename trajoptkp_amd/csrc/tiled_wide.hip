@@ -205,15 +205,15 @@ template <int NT, int MT, bool GATED = false>
 __global__ void __launch_bounds__(64 * NT)
 k_backward_tiled_wide(RecLayout L, int T, const double *__restrict__ rec, const double *__restrict__ lambda,
                       int pd_stride, double *__restrict__ Kout, double *__restrict__ kout,
-                      double *__restrict__ delta_J, int *__restrict__ status, const int *__restrict__ gate)
+                      double *__restrict__ delta_J, int *__restrict__ status, const int *__restrict__ gate, const int *__restrict__ list)
 {
-    if constexpr (GATED) { if (gate[blockIdx.x] == 0) return; }
+    if constexpr (GATED) { if (gate[kp_block_traj(list, blockIdx.x)] == 0) return; }
     extern __shared__ __attribute__((aligned(16))) double sh[];
     using M_ = WideLds<NT, MT>;
     const int n = L.n, m = L.m, nz = n + 1;
     const int lane = threadIdx.x & 63, c = lane & 15, q = lane >> 4;
     const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int b = blockIdx.x;
+    const int b = GATED ? kp_block_traj(list, blockIdx.x) : (int)blockIdx.x;      // (GATED: also the sweep of a listed subset, see k_backward_tiled_col)
     const double lam = lambda[b];
     double *bufV = sh + M_::V, *bufF = sh + M_::F, *bufT = sh + M_::T, *bufFu = sh + M_::Fu, *bufX = sh + M_::X;
     double *bufTu = bufT, *bufQ = bufTu + NT * MT * WTILE, *bufInv = bufQ + MT * MT * WTILE;      // alias the scratch of phases E / F
@@ -514,7 +514,7 @@ static hipError_t launch_bw(Ctx *c, int pd_stride)
     hipError_t e = hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(kernel, dim3(c->d.batch), dim3(64 * NT), lds, c->stream, c->L, c->d.T, c->rec, c->lambda,
-                       pd_stride, c->K, c->k, c->delta_J, c->status, c->bwd_gate);
+                       pd_stride, c->K, c->k, c->delta_J, c->status, c->bwd_gate, c->sweep_list);
     return hipGetLastError();
 }
 
@@ -529,11 +529,14 @@ hipError_t launch_backward_wide(Ctx *c, int pd_stride)
 // ---------------------------------------------------------------------------------------------------------------------------
 // Forward pass for 16 < num_ctrl <= 32: k_forward_tiled's plain form with the control block over two tiles.  Wave wi owns row
 // tile wi of Z+ and of Lc Z and forms its slice of the control law for BOTH control tiles; every wave clamps the same U.
-template <int NT, int MT>
+// LISTED: the kernel's twin for a listed subset (kpilqr_forward_linear_partial), block i sweeps trajectory list[i]; LISTED = false is
+// the kernel of every whole-batch call and never reads `list` (see k_forward_tiled)
+template <int NT, int MT, bool LISTED = false>
 __global__ void __launch_bounds__(64 * NT)
 k_forward_tiled_wide(RecLayout L, int T, int n_alpha, const double *__restrict__ rec, const double *__restrict__ Kin,
                      const double *__restrict__ kin, const double *__restrict__ u_nom, const double *__restrict__ ctrl_lim,
-                     const double *__restrict__ alphas, double *__restrict__ cost_pred, double *__restrict__ U_alpha)
+                     const double *__restrict__ alphas, double *__restrict__ cost_pred, double *__restrict__ U_alpha,
+                     const int *__restrict__ list)
 {
     extern __shared__ __attribute__((aligned(16))) double fsh[];
     double (*zbuf)[NT * WTILE] = (double (*)[NT * WTILE])fsh;               // [2][NT * TILE]
@@ -542,7 +545,7 @@ k_forward_tiled_wide(RecLayout L, int T, int n_alpha, const double *__restrict__
     const int n = L.n, m = L.m, nz2 = n + 2;
     const int lane = threadIdx.x & 63, c = lane & 15, q = lane >> 4;
     const int wi = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int b = blockIdx.x;
+    const int b = LISTED ? list[blockIdx.x] : (int)blockIdx.x;
     auto nchunk = [&](int kt) { const int rows = nz2 - 16 * kt; return rows >= 16 ? 4 : (rows + 3) / 4; };
     const int ncl = nchunk(NT - 1);
     const int ncw = nchunk(wi);
@@ -739,12 +742,13 @@ template <int NT>
 static hipError_t launch_fw(Ctx *c, double *U_alpha_dev)
 {
     const size_t lds = sizeof(double) * ((size_t)(2 * NT + NT * 2) * WTILE + NT * 64);
+    const auto kernel = c->sweep_list ? k_forward_tiled_wide<NT, 2, true> : k_forward_tiled_wide<NT, 2, false>;
     if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute((const void *)k_forward_tiled_wide<NT, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        hipError_t e = hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return e;
     }
-    hipLaunchKernelGGL((k_forward_tiled_wide<NT, 2>), dim3(c->d.batch), dim3(64 * NT), lds, c->stream, c->L, c->d.T, c->d.n_alpha, c->rec,
-                       c->K, c->k, c->u_nom, c->ctrl_lim, c->alphas, c->cost_pred, U_alpha_dev);
+    hipLaunchKernelGGL(kernel, dim3(c->d.batch), dim3(64 * NT), lds, c->stream, c->L, c->d.T, c->d.n_alpha, c->rec,
+                       c->K, c->k, c->u_nom, c->ctrl_lim, c->alphas, c->cost_pred, U_alpha_dev, c->sweep_list);
     return hipGetLastError();
 }
 

@@ -623,6 +623,41 @@ class Engine:
         self._keep += [lam, a]
         self._ck(self._L.kpilqr_iterate(self._h, _ptr(lam), pd_stride, _ptr(a)))
 
+    # -- the sweeps over a listed subset of the batch: compact arrays in traj order, nobody else's outputs written ------------------
+    def backward_partial(self, traj, lam=None, pd_stride=100, fetch=True):
+        """kpilqr_backward_partial: the backward sweep of the listed trajectories alone.  lam: one value or [len(traj)] (None: the
+        resident lambdas) -> (status [len(traj)], delta_J [len(traj)])."""
+        tr = self._traj(traj)
+        if lam is not None:
+            lam = _f64(np.broadcast_to(np.asarray(lam, dtype=np.float64), (len(tr),)))
+        fn = self._partial("kpilqr_backward_partial")
+        if not fetch:
+            self._ck(fn(self._h, len(tr), _ptr(tr), _ptr(lam), int(pd_stride), None, None))
+            self.sync()                 # (lam and tr are read during the call only once the stream has them)
+            return None
+        status = np.zeros(len(tr), np.int32); dJ = np.zeros(len(tr))
+        self._ck(fn(self._h, len(tr), _ptr(tr), _ptr(lam), int(pd_stride), _ptr(status), _ptr(dJ)))
+        self.sync()
+        return status, dJ
+
+    def forward_linear_partial(self, traj, alphas, want_U=False):
+        """kpilqr_forward_linear_partial -> cost_pred [len(traj)][n_alpha] (and U_alpha [len(traj)][n_alpha][T][m] with want_U)."""
+        tr = self._traj(traj)
+        a = None if alphas is None else _f64(alphas, (self.n_alpha,))
+        cost = np.zeros((len(tr), self.n_alpha))
+        U = np.zeros((len(tr), self.n_alpha, self.T, self.m)) if want_U else None
+        self._ck(self._partial("kpilqr_forward_linear_partial")(self._h, len(tr), _ptr(tr), _ptr(a), _ptr(cost), _ptr(U)))
+        self.sync()
+        return (cost, U) if want_U else cost
+
+    def iterate_partial(self, traj, lam=None, pd_stride=100, alphas=None):
+        """kpilqr_iterate_partial: the whole iteration for the listed trajectories alone (results(): their rows are new)."""
+        tr = self._traj(traj)
+        lam = None if lam is None else _f64(np.broadcast_to(np.asarray(lam, dtype=np.float64), (len(tr),)))
+        a = None if alphas is None else _f64(alphas, (self.n_alpha,))
+        self._ck(self._partial("kpilqr_iterate_partial")(self._h, len(tr), _ptr(tr), _ptr(lam), int(pd_stride), _ptr(a)))
+        self.sync()
+
     def results(self):
         """Device-resident outputs of the last backward/forward: status, delta_J, cost_pred."""
         import ctypes

@@ -45,6 +45,7 @@ def load_host():
     H.kpilqr_host_run_acrobot_batch4.argtypes = H.kpilqr_host_run_acrobot_batch3.argtypes + [vp]
     H.kpilqr_host_run_acrobot_batch5.argtypes = H.kpilqr_host_run_acrobot_batch4.argtypes + [vp]
     H.kpilqr_host_run_acrobot_batch6.argtypes = H.kpilqr_host_run_acrobot_batch5.argtypes + [vp]
+    H.kpilqr_host_run_acrobot_batch7.argtypes = H.kpilqr_host_run_acrobot_batch6.argtypes + [vp]
     H.kpilqr_host_dof_importance.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, vp, vp]
     H.kpilqr_host_acrobot_dof_importance.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int, vp, vp]
     H.kpilqr_host_relocate_records.argtypes = [vp, vp, C.c_size_t, C.c_int, C.c_int, vp, vp, vp]
@@ -165,7 +166,10 @@ def run_acrobot_batch(q0s, T=100, min_N=5, max_iter=6, min_iter=2, torque_weight
     "+wholeinputs" (residuals, nominal controls and step records through the whole-batch calls at every linearisation),
     "+f32gains" (K comes down as FP32, kpilqr_download_gains_f32_partial; the default is FP64), "+devretry" (STEP 2's PD retry runs
     on the device, kpilqr_set_lambda_retry; the default is the host loop), "+signedtorque" (torque_weight is taken as given, sign
-    included: a negative weight makes PD checks fail at small lambda; without it a negative value means the task's default).
+    included: a negative weight makes PD checks fail at small lambda; without it a negative value means the task's default),
+    "+activesweeps" (STEP 2 sweeps the active trajectories that are not settled, STEP 3 those with a valid backward pass:
+    kpilqr_backward_partial / kpilqr_forward_linear_partial; the default sweeps the whole batch every time).
+    backward_trajectories_swept / forward_trajectories_swept: trajectories swept by STEP 2 / STEP 3, summed over the calls.
     backward_sweeps: calls of kpilqr_backward; lambda_retries: sweeps repeated at a raised lambda, summed over trajectories and
     iterations; final_lambda [B]; cost_history_raw [B][max_iter + 2]: the histories as written, -1 behind their ends.
     payload_bytes_uploaded / gain_bytes_downloaded: what the run moved over the link (FD payload up; K, k down);
@@ -176,17 +180,18 @@ def run_acrobot_batch(q0s, T=100, min_N=5, max_iter=6, min_iter=2, torque_weight
     q = np.ascontiguousarray(q0s, np.float64); B = q.shape[0]
     cap = max_iter + 2
     hist = np.zeros((B, cap)); its = np.zeros(B, np.int32); U = np.zeros((B, T)); stats = np.zeros(8)
-    traffic = np.zeros(3 + max_iter + 1); inputs = np.zeros(2); gains = np.zeros(1); retry = np.zeros(2 + B)
-    rc = H.kpilqr_host_run_acrobot_batch6(B, T, min_N, max_iter, min_iter, float(torque_weight), _p(q), int(fused),
+    traffic = np.zeros(3 + max_iter + 1); inputs = np.zeros(2); gains = np.zeros(1); retry = np.zeros(2 + B); swept = np.zeros(2)
+    rc = H.kpilqr_host_run_acrobot_batch7(B, T, min_N, max_iter, min_iter, float(torque_weight), _p(q), int(fused),
                                           None if method is None else method.encode(), _p(hist), cap, _p(its), _p(U), _p(stats),
-                                          _p(traffic), len(traffic), _p(inputs), _p(gains), _p(retry))
+                                          _p(traffic), len(traffic), _p(inputs), _p(gains), _p(retry), _p(swept))
     if rc < 0:
         raise RuntimeError(f"kpilqr_host_run_acrobot_batch failed: {rc}")
     return dict(iterations=its, cost_history=[hist[b][hist[b] >= 0] for b in range(B)], U=U, stats=stats,
                 payload_bytes_uploaded=int(traffic[0]), gain_bytes_downloaded=int(traffic[1]), gain_trajectories_fetched=int(gains[0]),
                 residual_bytes_uploaded=int(inputs[0]), nominal_bytes_uploaded=int(inputs[1]),
                 keypoint_entries=traffic[3:3 + int(traffic[2])].astype(np.int64),
-                backward_sweeps=int(retry[0]), lambda_retries=int(retry[1]), final_lambda=retry[2:].copy(), cost_history_raw=hist)
+                backward_sweeps=int(retry[0]), lambda_retries=int(retry[1]),
+                backward_trajectories_swept=int(swept[0]), forward_trajectories_swept=int(swept[1]), final_lambda=retry[2:].copy(), cost_history_raw=hist)
 
 
 # ---- stand-in models by name ("acrobot", "floating_body"): primitives for the oracle's restatement of the host FD loops ----

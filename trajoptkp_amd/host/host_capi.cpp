@@ -164,9 +164,23 @@ int kpilqr_host_run_acrobot_batch5(int B, int T, int min_N, int max_iter, int mi
 // iterations), then every trajectory's final lambda.  "+devretry" in `method`: the retry runs on the device (iLQR_GPU_Batch::
 // device_lambda_retry).  "+signedtorque": torque_weight is taken as given, sign included (without it a negative value means "the
 // task's default"): a negative weight makes Q_uu + lambda I fail its PD check at small lambda, which is what exercises the retry.
+int kpilqr_host_run_acrobot_batch7(int B, int T, int min_N, int max_iter, int min_iter, double torque_weight, const double *q0s,
+                                   int fused, const char *method, double *cost_history, int cost_cap, int *iterations, double *U_out, double *stats,
+                                   double *traffic, int traffic_cap, double *inputs, double *gains, double *retry, double *swept);
 int kpilqr_host_run_acrobot_batch6(int B, int T, int min_N, int max_iter, int min_iter, double torque_weight, const double *q0s,
                                    int fused, const char *method, double *cost_history, int cost_cap, int *iterations, double *U_out, double *stats,
                                    double *traffic, int traffic_cap, double *inputs, double *gains, double *retry)
+{
+    return kpilqr_host_run_acrobot_batch7(B, T, min_N, max_iter, min_iter, torque_weight, q0s, fused, method, cost_history, cost_cap, iterations, U_out, stats,
+                                          traffic, traffic_cap, inputs, gains, retry, nullptr);
+}
+
+// ... and the sweeps: swept [2] = trajectories swept by STEP 2 and by STEP 3, summed over the calls.  "+activesweeps" in `method`:
+// STEP 2 sweeps the active trajectories that are not settled, STEP 3 those with a valid backward pass (iLQR_GPU_Batch::active_sweeps);
+// it combines with "+devretry" and "+f32gains"
+int kpilqr_host_run_acrobot_batch7(int B, int T, int min_N, int max_iter, int min_iter, double torque_weight, const double *q0s,
+                                   int fused, const char *method, double *cost_history, int cost_cap, int *iterations, double *U_out, double *stats,
+                                   double *traffic, int traffic_cap, double *inputs, double *gains, double *retry, double *swept)
 {
     const bool signed_torque = method && std::string(method).find("+signedtorque") != std::string::npos;
     std::vector<iLQR_GPU_Batch::Problem> probs;
@@ -188,6 +202,7 @@ int kpilqr_host_run_acrobot_batch6(int B, int T, int min_N, int max_iter, int mi
     opt.whole_inputs = method && std::string(method).find("+wholeinputs") != std::string::npos;
     opt.gains_f32 = method && std::string(method).find("+f32gains") != std::string::npos;
     opt.device_lambda_retry = method && std::string(method).find("+devretry") != std::string::npos;
+    opt.active_sweeps = method && std::string(method).find("+activesweeps") != std::string::npos;
     std::vector<std::vector<MatrixXd>> U0(B, std::vector<MatrixXd>(T, MatrixXd(1, 1)));
     auto U = opt.OptimiseAll(U0, max_iter, min_iter);
     for (int b = 0; b < B; b++) {
@@ -208,6 +223,7 @@ int kpilqr_host_run_acrobot_batch6(int B, int T, int min_N, int max_iter, int mi
         retry[0] = (double)opt.backward_sweeps; retry[1] = (double)opt.lambda_retries;
         for (int b = 0; b < B; b++) retry[2 + b] = opt.lambda[b];
     }
+    if (swept) { swept[0] = (double)opt.backward_trajectories_swept; swept[1] = (double)opt.forward_trajectories_swept; }
     return 0;
 }
 

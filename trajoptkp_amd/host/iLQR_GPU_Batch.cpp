@@ -359,11 +359,24 @@ std::vector<std::vector<MatrixXd>> iLQR_GPU_Batch::OptimiseAll(const std::vector
         // STEP 2 (:435-442): backward pass with the PD retry, lambda per trajectory
         std::vector<char> valid(B, 0), settled(B, 0);
         for (int b = 0; b < B; b++) { lam_used[b] = lambda[b]; if (S[b].done) settled[b] = 1; }
+        std::vector<int> sweep, st_c;
+        std::vector<double> lam_c, dJ_c;
         for (;;) {
-            if ((rc = kpilqr_backward(ctx, lam_used.data(), 100, status.data(), dJ.data())) < 0) fatal("kpilqr_backward", rc);
+            if (active_sweeps) {
+                // the trajectories this attempt is for, compact: at first every active one, then those whose last sweep failed
+                sweep.clear(); lam_c.clear();
+                for (int b : active) if (!settled[b]) { sweep.push_back(b); lam_c.push_back(lam_used[b]); }
+                st_c.assign(sweep.size(), 0); dJ_c.assign(sweep.size(), 0.0);
+                if ((rc = kpilqr_backward_partial(ctx, (int)sweep.size(), sweep.data(), lam_c.data(), 100, st_c.data(), dJ_c.data())) < 0) fatal("kpilqr_backward_partial", rc);
+                backward_trajectories_swept += sweep.size();
+            } else {
+                if ((rc = kpilqr_backward(ctx, lam_used.data(), 100, status.data(), dJ.data())) < 0) fatal("kpilqr_backward", rc);
+                backward_trajectories_swept += (size_t)B;
+            }
             backward_sweeps++;
             if (device_lambda_retry && (rc = kpilqr_download_lambda_retry(ctx, lam_dev.data(), attempts.data()))) fatal("kpilqr_download_lambda_retry", rc);
             if ((rc = kpilqr_sync(ctx))) fatal("kpilqr_sync", rc);
+            if (active_sweeps) for (size_t w = 0; w < sweep.size(); w++) { status[sweep[w]] = st_c[w]; dJ[sweep[w]] = dJ_c[w]; }
             bool again = false;
             for (int b : active) {
                 if (settled[b]) continue;
@@ -396,10 +409,18 @@ std::vector<std::vector<MatrixXd>> iLQR_GPU_Batch::OptimiseAll(const std::vector
         else if ((rc = kpilqr_upload_nominal_partial(ctx, (int)moved.size(), moved.data(), host_unom))) fatal("kpilqr_upload_nominal_partial", rc);
         nominal_bytes_uploaded += moved.size() * (size_t)T * m * sizeof(double);
         unom_stale.assign(B, 0);
-        if ((rc = kpilqr_forward_linear(ctx, alphas.data(), pred.data(), nullptr))) fatal("kpilqr_forward_linear", rc);
         // K, k only of the trajectories that will use them (active, with a valid backward pass): compact, in trajectory order
         std::vector<int> fetch, fetch_row(B, -1);
         for (int b : active) if (valid[b]) { fetch_row[b] = (int)fetch.size(); fetch.push_back(b); }
+        std::vector<double> pred_c;
+        if (active_sweeps) {           // ... and the forward sweep of those trajectories alone, their predictions compact
+            pred_c.assign(fetch.size() * alphas.size(), 0.0);
+            if ((rc = kpilqr_forward_linear_partial(ctx, (int)fetch.size(), fetch.data(), alphas.data(), pred_c.data(), nullptr))) fatal("kpilqr_forward_linear_partial", rc);
+            forward_trajectories_swept += fetch.size();
+        } else {
+            if ((rc = kpilqr_forward_linear(ctx, alphas.data(), pred.data(), nullptr))) fatal("kpilqr_forward_linear", rc);
+            forward_trajectories_swept += (size_t)B;
+        }
         if (gains_f32) {
             if (!host_K32 && (rc = kpilqr_host_alloc(ctx, (size_t)B * T * n * m * sizeof(float), (void **)&host_K32))) fatal("kpilqr_host_alloc", rc);
             if (!fetch.empty() && (rc = kpilqr_download_gains_f32_partial(ctx, (int)fetch.size(), fetch.data(), host_K32, host_k))) fatal("kpilqr_download_gains_f32_partial", rc);
@@ -407,6 +428,9 @@ std::vector<std::vector<MatrixXd>> iLQR_GPU_Batch::OptimiseAll(const std::vector
         gain_bytes_downloaded += fetch.size() * ((size_t)T * n * m * (gains_f32 ? sizeof(float) : sizeof(double)) + (size_t)T * m * sizeof(double));
         gain_trajectories_fetched += fetch.size();
         if ((rc = kpilqr_sync(ctx))) fatal("kpilqr_sync", rc);
+        if (active_sweeps)
+            for (size_t w = 0; w < fetch.size(); w++)
+                for (size_t a = 0; a < alphas.size(); a++) pred[(size_t)fetch[w] * alphas.size() + a] = pred_c[w * alphas.size() + a];
         for (double &v : linesearch_stats) v = 0.0;
         for (int b : active) {
             if (!valid[b]) continue;

@@ -65,6 +65,12 @@ public:
     bool device_lambda_retry = false;
     // calls of kpilqr_backward, and sweeps a trajectory repeated at a raised lambda (on either route), since construction
     size_t backward_sweeps = 0, lambda_retries = 0;
+    // STEP 2 and STEP 3 over the trajectories that need them (kpilqr_backward_partial, kpilqr_forward_linear_partial): STEP 2 sweeps
+    // `active` minus the settled trajectories -- so each host retry sweeps only the trajectories that failed -- and STEP 3 the
+    // trajectories with a valid backward pass.  Off by default: the whole-batch calls, call for call as before.
+    bool active_sweeps = false;
+    // trajectories swept, summed over the calls: batch per call on the default route, the list's length with active_sweeps
+    size_t backward_trajectories_swept = 0, forward_trajectories_swept = 0;
     // regularisation / line search constants (include/Optimiser/Optimiser.h:239-242,259,303)
     double max_lambda = 10.0, min_lambda = 0.0001, lambda_factor = 10, epsConverge = 0.02;
     int num_parallel_rollouts = 6;
