@@ -138,6 +138,59 @@ def test_streamed_offsets_are_validated_before_anything_is_enqueued():
         assert np.array_equal(K1, K0)
 
 
+def test_a_refused_streamed_call_leaves_the_iteration_in_flight_alone():
+    """include/kpilqr.h: every refusal of kpilqr_iterate_streamed comes before anything is enqueued or the context is changed.  A
+    job-list iteration is in flight on 3 chunks when a 2-chunk call with a non-monotone traj_job_first is refused: the iteration in
+    flight, and a valid 3-chunk call behind the refusal, give bit for bit what the same call gives on a fresh context."""
+    p = synth.make_problem(task="panda_reaching", T=60, batch=4, min_N=5)
+    alphas = orc.alphas(6)
+
+    def context():
+        e = Engine(p["dof"], p["m"], p["T"], p["nr"], batch=4, fused=True)
+        synth.upload(e, p)
+        e.iterate(p["lam"], 100, alphas)                          # alphas resident
+        s = e.fd_slab(p["job_b"], p["job_t"], p["job_col"], p["job_mode"], p["xplus"], p["xminus"], p["job_nom"], p["xnom"])
+        pin = {}
+        for name in ("r", "r_x", "r_u", "u_nom"):
+            pin[name] = e.pinned(p[name].shape); pin[name][...] = p[name]
+        pin["lam"] = e.pinned(4); pin["lam"][:] = p["lam"]
+        return e, s, pin
+
+    with Engine(p["dof"], p["m"], p["T"], p["nr"], batch=4, fused=True) as e:
+        shapes = [a.shape for a in e.gains()]
+
+    def outputs(e):                                               # (kpilqr_host_alloc joins the pipeline: allocated before the calls)
+        out = dict(K=e.pinned(shapes[0]), k=e.pinned(shapes[1]), cost_pred=e.pinned((4, 6)), status=e.pinned(4, np.int32))
+        for a in out.values():
+            a[...] = -1
+        return out
+
+    e, s, pin = context()
+    with e:
+        want = outputs(e)
+        e.iterate_streamed(fd=s, eps=p["eps"], nchunks=3, **pin, **want)
+        e.sync()
+        want = {name: np.array(a) for name, a in want.items()}
+    assert np.all(want["status"] == 0)
+    e, s, pin = context()
+    with e:
+        first, refused, second = outputs(e), outputs(e), outputs(e)
+        bad = dict(s, traj_job_first=e.pinned(5, np.int32))
+        bad["traj_job_first"][:] = s["traj_job_first"]
+        bad["traj_job_first"][2] = int(s["traj_job_first"][1]) - 1        # the middle entry, below its predecessor
+        e.iterate_streamed(fd=s, eps=p["eps"], nchunks=3, **pin, **first)              # in flight: no wait
+        with pytest.raises(KpilqrError) as ei:
+            e.iterate_streamed(fd=bad, eps=p["eps"], nchunks=2, **pin, **refused)
+        assert ei.value.code == -1 and "traj_job_first not monotone in [0, njobs]" in str(ei.value)
+        e.sync()
+        for name, a in first.items():
+            assert np.array_equal(a, want[name]), name
+        e.iterate_streamed(fd=s, eps=p["eps"], nchunks=3, **pin, **second)
+        e.sync()
+        for name, a in second.items():
+            assert np.array_equal(a, want[name]), name
+
+
 # ---- the C ABI's collective with two ranks -----------------------------------------------------------------------------
 _RANK_SCRIPT = r"""
 import json, os, sys, time

@@ -2087,19 +2087,32 @@ static int pipe_setup(kpilqr_ctx *c)
     return KPILQR_OK;
 }
 
+// doubles per trajectory of the arrays a chunk moves: the one place that spells them (views, staging regions, uploads, downloads)
+struct RowSizes { size_t r, r_x, r_u, u_nom, K, k; };
+static RowSizes row_sizes(const kpilqr_ctx *c)
+{
+    const size_t T = c->d.T, n = c->n, m = c->d.m, nr = c->d.nr;
+    return {(T + 1) * nr, (T + 1) * nr * n, (T + 1) * nr * m, T * m, T * n * m, T * m};
+}
+
+// first trajectory of chunk ch of nchunks (ch == nchunks: the batch's end)
+static int chunk_first(int B, int ch, int nchunks) { return (int)((long long)B * ch / nchunks); }
+
 // A view of trajectories [b0, b0+nb) of context c on stream s: every per-trajectory pointer shifted, so the ordinary
 // launchers run unchanged on the chunk.  n_simd is the chunk's SHARE of the chip: the launchers pick their wave
-// organisation (wave pairs / triples per trajectory) as if the whole batch were in flight, which it is.
+// organisation (wave pairs / triples per trajectory) as if the whole batch were in flight, which it is.  Where the host knows the
+// lists the view carries its trajectories' entry range, [fdk_first, fdk_first + kp_view_entries): the one place that reads it.
 static void make_view(const kpilqr_ctx *c, int b0, int nb, hipStream_t s, kpilqr_ctx *v)
 {
     *v = *c;
     v->is_view = true;             // it borrows the context's buffers: reserve() refuses to grow one through it
-    const size_t T = c->d.T, n = c->n, m = c->d.m, nr = c->d.nr, na = c->d.n_alpha, dof = c->d.dof, o = (size_t)b0;
+    const size_t T = c->d.T, na = c->d.n_alpha, dof = c->d.dof, o = (size_t)b0;
+    const RowSizes per = row_sizes(c);
     v->d.batch = nb; v->stream = s; v->own_stream = false;
     if (v->rec) v->rec.shift(o * T * c->L.stride);
-    v->K.shift(o * T * n * m); v->k.shift(o * T * m);
-    v->r.shift(o * (T + 1) * nr); v->r_x.shift(o * (T + 1) * nr * n); v->r_u.shift(o * (T + 1) * nr * m);
-    v->u_nom.shift(o * T * m); v->lambda.shift(o); v->cost_pred.shift(o * na); v->delta_J.shift(o); v->traj_cost.shift(o); v->status.shift(o);
+    v->K.shift(o * per.K); v->k.shift(o * per.k);
+    v->r.shift(o * per.r); v->r_x.shift(o * per.r_x); v->r_u.shift(o * per.r_u);
+    v->u_nom.shift(o * per.u_nom); v->lambda.shift(o); v->cost_pred.shift(o * na); v->delta_J.shift(o); v->traj_cost.shift(o); v->status.shift(o);
     v->attempts.shift(o); v->gate.shift(o);
     v->segmap.shift(o * dof * T); v->kp_offsets.shift(o * dof);
     if (v->segent) v->segent.shift(o * dof * T);
@@ -2108,19 +2121,52 @@ static void make_view(const kpilqr_ctx *c, int b0, int nb, hipStream_t s, kpilqr
     v->n_simd = share < 4 ? 4 : (int)share;
 }
 
-// What kpilqr_iterate_streamed2 adds to a streamed iteration: K as FP32, and the gains of a list of trajectories alone.
-// kpilqr_iterate_streamed is the same walk with neither (K32 == nullptr, !listed): it enqueues what it always has.
-struct StreamGains {
-    float *K32 = nullptr;          // K rounded to FP32 instead of io->K
-    bool listed = false;           // traj [count] (strictly increasing, within [0, batch)): K / K32 / k of those rows, compact
-    int count = 0;
+// A list of trajectories (strictly increasing, within [0, batch)) that a streamed iteration follows, and the walk over it: chunks and
+// list both increase, so a chunk's share is the slice the cursor passes on its way to the chunk's end.
+struct StreamList {
+    bool listed = false;
+    int count = 0, pos = 0;        // pos: first entry no chunk has taken yet
     const int *traj = nullptr;
+    void slice_below(int b1, int *i0, int *i1) { *i0 = pos; while (pos < count && traj[pos] < b1) pos++; *i1 = pos; }
+};
+
+// The FD payload a streamed iteration brings, decided once (at the "one FD payload per iteration" refusal of stream_check)
+enum class StreamPayload { none, jobs, kp_ordered, columns, columns_f32 };
+
+// A streamed iteration, resolved: what the four entry points ask for (they fill the first group), what stream_check decides about the
+// payload, and where stream_prepare found the device side of it.  The three kinds by key-point entry (kp_ordered, columns,
+// columns_f32) differ in the fields below and in nothing else: a chunk copies ONE contiguous range of `rec` bytes per entry from
+// `src` to `land` at its own first entry, and one launch may follow (stream_chunk_payload).
+struct StreamCall {
+    const kpilqr_stream_io *io = nullptr;
+    int pd_check_stride = 0, nchunks = 0;
+    float *K32 = nullptr;              // kpilqr_iterate_streamed2: K rounded to FP32 instead of io->K
+    StreamList gains;                  // kpilqr_iterate_streamed2: K / K32 / k of those rows alone, compact
+    const float *kcols32 = nullptr;    // kpilqr_iterate_streamed3: the ENCODED FP32 key-point columns (kpilqr_upload_kp_columns_f32) for a payload
+    StreamList rows;                   // kpilqr_iterate_streamed4: the inputs (payload, r, r_x, r_u, u_nom) of those trajectories alone, compact; read during the call only
+    // stream_check
+    StreamPayload kind = StreamPayload::none;
+    const char *src = nullptr;         // by entry: the host source ...
+    size_t rec = 0;                    // ... and its bytes per entry (the record stride | 3n doubles | 3n floats)
+    // stream_prepare
+    kpilqr_fd_layout L{};              // jobs: the slab's layout
+    char *land = nullptr;              // by entry: device base a chunk's range is copied to (fdk_dev | kpc | kpc32; FP64 of a list: rows_stage[kRowsPayload])
+    void *place = nullptr;             // FP64 of a list: where launch_rows_in_entries moves the listed ranges from `land` (fdk_dev | kpc)
+    const int *ulist = nullptr, *ufirst = nullptr;      // rows: the list and the per-trajectory first entries on the device (its ring slot)
+    int uslot = 0;
+    bool k_up = false, k_down = false; // copies by kernel (KPILQR_PIPE_COPY)
+    StreamCall(const kpilqr_stream_io *io_, int stride, int chunks) : io(io_), pd_check_stride(stride), nchunks(chunks) {}
+    bool by_entry() const { return kind != StreamPayload::none && kind != StreamPayload::jobs; }
+    hipError_t h2d(void *dst, const void *from, size_t bytes, hipStream_t s) const      // a chunk's inputs: by SDMA, or by the copy kernel
+    {
+        return k_up ? launch_copy_in(s, dst, from, bytes) : hipMemcpyAsync(dst, from, bytes, hipMemcpyHostToDevice, s);
+    }
 };
 
 // The list of a streamed iteration on the device, before the chunks are cut: reserved and filled on the CONTEXT (a view never
 // allocates), on the context's stream ahead of pipe_in.  A list equal to the one the device copy holds is not uploaded again, so
 // consecutive calls keep overlapping; a different one first orders the context's stream behind the chunks still reading the old one.
-static int pipe_list_bind(kpilqr_ctx *c, const StreamGains &g)
+static int pipe_list_bind(kpilqr_ctx *c, const StreamList &g)
 {
     if (!g.listed || g.count == 0) return KPILQR_OK;
     const size_t B = c->d.batch;
@@ -2140,48 +2186,15 @@ static int pipe_list_bind(kpilqr_ctx *c, const StreamGains &g)
     return KPILQR_OK;
 }
 
-// What kpilqr_iterate_streamed4 adds: the inputs (payload, r, r_x, r_u, u_nom) of a list of trajectories alone, compact in list order.
-// !listed: the walk of the three earlier calls, which enqueues what it always has.
-struct StreamRows {
-    bool listed = false;           // traj [count] (strictly increasing, within [0, batch)); read during the call only
-    int count = 0;
-    const int *traj = nullptr;
-};
-
-// The checks of a streamed iteration whose inputs follow a list (kpilqr_iterate_streamed4 with upload_traj), all before anything is
-// enqueued or the context changes.  The list itself has been checked, and with a by-entry payload the host knows the lists.
-static int check_stream_rows(kpilqr_ctx *c, const kpilqr_stream_io *io, const StreamRows &u, const float *kcols32)
+// A buffer that grows is freed: nothing in flight may still read it.  If one of `needs` (buffer, bytes) would grow, the pipeline is
+// joined and the host waits for every chunk stream; the caller's reserve() then waits for the context's stream, as always.
+static int quiesce_for_growth(kpilqr_ctx *c, std::initializer_list<std::pair<const DevMem *, size_t>> needs)
 {
-    const std::string w("kpilqr_iterate_streamed4");
-    if (io->fd_slab) return set_err(c, KPILQR_ERR_ARG, w + ": io.fd_slab with upload_traj (job lists carry their own trajectory indices: out of scope)");
-    if (io->fd_kp_slab || io->kp_columns || kcols32) {
-        long long sum = 0;
-        for (int i = 0; i < u.count; i++) sum += c->kp_traj_first_host[u.traj[i] + 1] - c->kp_traj_first_host[u.traj[i]];
-        if (io->entries != sum) return set_err(c, KPILQR_ERR_ARG, w + ": `entries` is not the number of key-point entries of the listed trajectories");
-        // the trajectories that are not listed keep their payload: it has to be there, whole, and of the kind that arrives
-        const FdPayload kind = io->fd_kp_slab ? FdPayload::kp_ordered : FdPayload::kp_columns;
-        const bool resident = c->fd_payload == kind && (kind == FdPayload::kp_ordered || c->pay.kpc_valid || c->n_pending > 0);
-        if (!resident)
-            return set_err(c, KPILQR_ERR_STATE, w + ": a payload with upload_traj, but the context holds no complete resident payload of the same kind "
-                                                    "(key-point ordered records / key-point columns) for the trajectories that are not listed");
-        if (io->fd_kp_slab && memcmp(&io->eps, &c->eps, sizeof(double)) != 0)
-            return set_err(c, KPILQR_ERR_ARG, w + ": eps differs from the resident payload's (a context has one eps)");
-        // ranges pending since kpilqr_update_keypoints: the list has to bring every one of them (both lists increase)
-        for (int p = 0, i = 0; p < c->n_pending; p++) {
-            const int b = c->kp_pending_host[p];
-            while (i < u.count && u.traj[i] < b) i++;
-            if (i == u.count || u.traj[i] != b)
-                return set_err(c, KPILQR_ERR_STATE, w + ": the payload of trajectory " + std::to_string(b) + " is pending since kpilqr_update_keypoints "
-                                                        "and upload_traj does not list it");
-        }
-    }
-    // (the refusals of kpilqr_upload_residuals_partial, in its words)
-    if (io->r_x && c->rx_const_on)
-        return set_err(c, KPILQR_ERR_STATE, w + ": the context holds constant residual Jacobians; a whole r_x through kpilqr_upload_residuals ends that mode first");
-    if (io->r_x && !(c->rx_buf_valid && c->rx_whole))
-        return set_err(c, KPILQR_ERR_STATE, w + ": r_x of a subset before a whole r_x: kpilqr_upload_residuals first");
-    if (io->r_u && c->ru_zero)
-        return set_err(c, KPILQR_ERR_STATE, w + ": r_u of a subset on a context that runs without control residuals: a whole r_u through kpilqr_upload_residuals first");
+    bool grows = false;
+    for (const auto &nd : needs) grows = grows || would_grow(*nd.first, nd.second);
+    if (!grows) return KPILQR_OK;
+    { const int rc = join_pipeline(c); if (rc) return rc; }
+    for (int i = 0; i < Ctx::kPipeStreams; i++) KP_HIP(c, hipStreamSynchronize(c->pipe_stream[i]));
     return KPILQR_OK;
 }
 
@@ -2189,7 +2202,7 @@ static int check_stream_rows(kpilqr_ctx *c, const kpilqr_stream_io *io, const St
 // staging region (-1: not listed) into the slot's pinned mirror, uploaded on the context's stream ahead of pipe_in.  The slot was
 // last used kRowsRing calls ago: the wait for its upload is over long since, and the context's stream is ordered behind the chunks
 // that read its device copy -- no wait concerns the iteration in flight.  -> *slot_out
-static int rows_list_bind(kpilqr_ctx *c, const StreamRows &u, int nchunks, bool by_entry, int *slot_out)
+static int rows_list_bind(kpilqr_ctx *c, const StreamList &u, int nchunks, bool by_entry, int *slot_out)
 {
     const int B = c->d.batch, slot = c->rows_next;
     const size_t per_slot = 2 * (size_t)B;
@@ -2212,8 +2225,8 @@ static int rows_list_bind(kpilqr_ctx *c, const StreamRows &u, int nchunks, bool 
     if (by_entry) {
         // a chunk's listed entries sit back to back from the chunk's own first entry on
         for (int ch = 0, i = 0; ch < nchunks; ch++) {
-            const int b0 = (int)((long long)B * ch / nchunks), b1 = (int)((long long)B * (ch + 1) / nchunks);
-            int at = c->kp_traj_first_host[b0];
+            const int b1 = chunk_first(B, ch + 1, nchunks);
+            int at = c->kp_traj_first_host[chunk_first(B, ch, nchunks)];
             for (; i < u.count && u.traj[i] < b1; i++) {
                 first[u.traj[i]] = at;
                 at += c->kp_traj_first_host[u.traj[i] + 1] - c->kp_traj_first_host[u.traj[i]];
@@ -2227,119 +2240,142 @@ static int rows_list_bind(kpilqr_ctx *c, const StreamRows &u, int nchunks, bool 
     return KPILQR_OK;
 }
 
-// kcols32: what kpilqr_iterate_streamed3 adds -- the ENCODED FP32 key-point columns (kpilqr_upload_kp_columns_f32) as a fourth payload
-// kind; nullptr: the walk of the two earlier calls, which enqueues what it always has.  u: what kpilqr_iterate_streamed4 adds.
-static int iterate_streamed(kpilqr_ctx *c, const kpilqr_stream_io *io, const StreamGains &g, int pd_check_stride, int nchunks, const float *kcols32 = nullptr,
-                            const StreamRows &u = StreamRows{})
+// Phase 1 of a streamed iteration -- EVERY refusal, before a single operation is enqueued or the context is changed: nothing here
+// writes to *c but set_err (and the join ahead of check_complete, which orders streams and changes no derived state).  It decides the
+// payload's kind, and for job lists returns in *sig the FNV-1a hash of what decides where a chunk's payload lands.
+static int stream_check(kpilqr_ctx *c, StreamCall *call, unsigned long long *sig)
 {
-    KP_HIP(c, hipSetDevice(c->d.device));
+    const kpilqr_stream_io *io = call->io;
+    const StreamList &u = call->rows, &g = call->gains;
+    const float *kcols32 = call->kcols32;
     if (!c->have_kp) return set_err(c, KPILQR_ERR_STATE, "kpilqr_iterate_streamed before kpilqr_set_keypoints");
-    if (pd_check_stride < 1) return set_err(c, KPILQR_ERR_ARG, "pd_check_stride must be >= 1");
+    if (call->pd_check_stride < 1) return set_err(c, KPILQR_ERR_ARG, "pd_check_stride must be >= 1");
     // (a whole new payload completes the resident one; without it the pending ranges of kpilqr_update_keypoints would be read)
     if (!io->fd_slab && !io->fd_kp_slab && !io->kp_columns && !kcols32) {
         if (c->n_pending) { const int rcj = join_pipeline(c); if (rcj) return rcj; }
         const int rcp = check_complete(c, "kpilqr_iterate_streamed without a new payload"); if (rcp) return rcp;
     }
     const int B = c->d.batch;
-    if (nchunks < 1) nchunks = Ctx::kPipeStreams;          // 0: one chunk per pipeline stream
-    if (nchunks > B) nchunks = B;
     if (u.listed && !kp_traj_list_ok(B, u.count, u.traj))
         return set_err(c, KPILQR_ERR_ARG, "kpilqr_iterate_streamed4: upload_traj must be strictly increasing and within [0, batch)");
     if (io->fd_slab && (io->njobs < 1 || !io->traj_job_first || (io->nnom > 0 && !io->traj_nom_first)))
         return set_err(c, KPILQR_ERR_ARG, "streamed FD payload needs the per-trajectory job / nominal-row offsets");
     if ((io->fd_slab != nullptr) + (io->fd_kp_slab != nullptr) + (io->kp_columns != nullptr) + (kcols32 != nullptr) > 1)
         return set_err(c, KPILQR_ERR_ARG, "one FD payload per iteration: job lists OR key-point ordered OR key-point columns (FP64 OR FP32)");
-    if (io->fd_kp_slab || io->kp_columns || kcols32) {
+    const size_t n3 = (size_t)3 * c->n;
+    kpilqr_fdkp_layout LK{};
+    fdkp_layout(c->n, 0, &LK);
+    if (io->fd_slab) call->kind = StreamPayload::jobs;
+    if (io->fd_kp_slab) { call->kind = StreamPayload::kp_ordered; call->src = (const char *)io->fd_kp_slab; call->rec = LK.entry_stride; }
+    if (io->kp_columns) { call->kind = StreamPayload::columns; call->src = (const char *)io->kp_columns; call->rec = n3 * sizeof(double); }
+    if (kcols32) { call->kind = StreamPayload::columns_f32; call->src = (const char *)kcols32; call->rec = n3 * sizeof(float); }
+    if (call->by_entry()) {
         if (!c->kp_traj_first_host || c->kp_total_host < 0)
             return set_err(c, KPILQR_ERR_STATE, "streamed key-point ordered payload: the lists must be known to the host (kpilqr_set_keypoints, or kpilqr_get_keypoints after generating them)");
         if (!u.listed && io->entries != c->kp_total_host) return set_err(c, KPILQR_ERR_ARG, "fd_kp_slab / kp_columns / kp_columns32: `entries` is not the number of key-point entries");
     }
-    if (u.listed) { const int rcu = check_stream_rows(c, io, u, kcols32); if (rcu) return rcu; }
-    // entries of the payload as it will be resident: with a list the kept trajectories' stay beside the ones that arrive
-    const int pay_entries = u.listed ? c->kp_total_host : io->entries;
+    // inputs that follow a list (kpilqr_iterate_streamed4 with upload_traj): the list itself has been checked, and with a by-entry
+    // payload the host knows the lists
+    static const std::string w("kpilqr_iterate_streamed4");
+    if (u.listed && io->fd_slab) return set_err(c, KPILQR_ERR_ARG, w + ": io.fd_slab with upload_traj (job lists carry their own trajectory indices: out of scope)");
+    if (u.listed && call->by_entry()) {
+        long long sum = 0;
+        for (int i = 0; i < u.count; i++) sum += c->kp_traj_first_host[u.traj[i] + 1] - c->kp_traj_first_host[u.traj[i]];
+        if (io->entries != sum) return set_err(c, KPILQR_ERR_ARG, w + ": `entries` is not the number of key-point entries of the listed trajectories");
+        // the trajectories that are not listed keep their payload: it has to be there, whole, and of the kind that arrives
+        const FdPayload kind = io->fd_kp_slab ? FdPayload::kp_ordered : FdPayload::kp_columns;
+        const bool resident = c->fd_payload == kind && (kind == FdPayload::kp_ordered || c->pay.kpc_valid || c->n_pending > 0);
+        if (!resident)
+            return set_err(c, KPILQR_ERR_STATE, w + ": a payload with upload_traj, but the context holds no complete resident payload of the same kind "
+                                                    "(key-point ordered records / key-point columns) for the trajectories that are not listed");
+        if (io->fd_kp_slab && memcmp(&io->eps, &c->eps, sizeof(double)) != 0)
+            return set_err(c, KPILQR_ERR_ARG, w + ": eps differs from the resident payload's (a context has one eps)");
+        // ranges pending since kpilqr_update_keypoints: the list has to bring every one of them (both lists increase)
+        for (int p = 0, i = 0; p < c->n_pending; p++) {
+            const int b = c->kp_pending_host[p];
+            while (i < u.count && u.traj[i] < b) i++;
+            if (i == u.count || u.traj[i] != b)
+                return set_err(c, KPILQR_ERR_STATE, w + ": the payload of trajectory " + std::to_string(b) + " is pending since kpilqr_update_keypoints "
+                                                        "and upload_traj does not list it");
+        }
+    }
+    // (the refusals of kpilqr_upload_residuals_partial, in its words)
+    if (u.listed && io->r_x && c->rx_const_on)
+        return set_err(c, KPILQR_ERR_STATE, w + ": the context holds constant residual Jacobians; a whole r_x through kpilqr_upload_residuals ends that mode first");
+    if (u.listed && io->r_x && !(c->rx_buf_valid && c->rx_whole))
+        return set_err(c, KPILQR_ERR_STATE, w + ": r_x of a subset before a whole r_x: kpilqr_upload_residuals first");
+    if (u.listed && io->r_u && c->ru_zero)
+        return set_err(c, KPILQR_ERR_STATE, w + ": r_u of a subset on a context that runs without control residuals: a whole r_u through kpilqr_upload_residuals first");
     const void *hostp[] = {kcols32, io->kp_columns, io->fd_kp_slab, io->fd_slab, io->r, io->r_x, io->r_u, io->u_nom, io->lambda, io->K, io->k, io->cost_pred, io->delta_J, io->status};
     for (const void *p : hostp) if (!is_pinned(p)) return set_err(c, KPILQR_ERR_ARG, "kpilqr_iterate_streamed: host buffers must be pinned (kpilqr_host_alloc)");
-    if (g.K32) {
+    if (call->K32) {
         if (io->K) return set_err(c, KPILQR_ERR_ARG, "kpilqr_iterate_streamed2: io.K and K32 are exclusive");
-        if (!is_pinned(g.K32) || ((size_t)g.K32 & 7)) return set_err(c, KPILQR_ERR_ARG, "kpilqr_iterate_streamed2: K32 must be pinned (kpilqr_host_alloc) and 8-byte aligned");
+        if (!is_pinned(call->K32) || ((size_t)call->K32 & 7)) return set_err(c, KPILQR_ERR_ARG, "kpilqr_iterate_streamed2: K32 must be pinned (kpilqr_host_alloc) and 8-byte aligned");
     }
     if (g.listed && !kp_traj_list_ok(B, g.count, g.traj))
         return set_err(c, KPILQR_ERR_ARG, "kpilqr_iterate_streamed2: gain_traj must be strictly increasing and within [0, batch)");
-    if (c->fused) { int rc = check_fused(c); if (rc) return rc; }
-    int rc = pipe_setup(c);
-    if (rc) return rc;
-    // the chunk -> stream map must not change while earlier chunks are still in flight (same-stream order is what
-    // protects a chunk's device buffers from the next iteration's uploads)
-    if (c->pipe_dirty && c->pipe_chunks != nchunks) { rc = join_pipeline(c); if (rc) return rc; }
-    c->pipe_chunks = nchunks;
-
-    const int n = c->n, m = c->d.m, nr = c->d.nr, T = c->d.T, na = c->d.n_alpha;
-    // uploads by SDMA, downloads by a copy kernel: the only pairing whose two directions overlap inside this pipeline
-    // (KPILQR_PIPE_COPY: bit 0 uploads by kernel, bit 1 downloads by kernel; profiles/r02_pcie_inclusive.txt)
-    const int pipe_copy = c->tune.pipe_copy >= 0 ? c->tune.pipe_copy : 2;
-    const bool k_up = pipe_copy & 1, k_down = pipe_copy & 2;
-    auto h2d = [&](void *dst, const void *src, size_t bytes, hipStream_t st) -> hipError_t {
-        return k_up ? launch_copy_in(st, dst, src, bytes) : hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, st);
-    };
-    kpilqr_fd_layout L{};
-    const char *slab = (const char *)io->fd_slab;
-    if (slab) {
-        // ---- validate EVERYTHING before a single operation is enqueued or the context is changed --------------------
-        if (io->traj_job_first[0] != 0 || io->traj_job_first[B] != io->njobs)
-            return set_err(c, KPILQR_ERR_ARG, "traj_job_first must run from 0 to njobs");
-        unsigned long long sig = 1469598103934665603ULL;           // FNV-1a over what decides where a chunk's payload lands
-        auto mix = [&](unsigned long long v) { sig = (sig ^ v) * 1099511628211ULL; };
-        mix((unsigned)io->njobs); mix((unsigned)io->nnom);
-        for (int b = 0; b <= B; b++) {
-            const int j = io->traj_job_first[b];
-            if (j < 0 || j > io->njobs || (b > 0 && j < io->traj_job_first[b - 1]))
-                return set_err(c, KPILQR_ERR_ARG, "traj_job_first not monotone in [0, njobs]");
-            mix((unsigned)j);
-            if (io->nnom > 0) {
-                const int q = io->traj_nom_first[b];
-                if (q < 0 || q > io->nnom || (b > 0 && q < io->traj_nom_first[b - 1]))
-                    return set_err(c, KPILQR_ERR_ARG, "traj_nom_first not monotone in [0, nnom]");
-                mix((unsigned)q);
-            }
+    if (c->fused) { const int rc = check_fused(c); if (rc) return rc; }
+    if (!io->fd_slab) return KPILQR_OK;
+    // the job lists' offsets, last: the one walk over the batch
+    if (io->traj_job_first[0] != 0 || io->traj_job_first[B] != io->njobs)
+        return set_err(c, KPILQR_ERR_ARG, "traj_job_first must run from 0 to njobs");
+    unsigned long long h = 1469598103934665603ULL;
+    auto mix = [&](unsigned long long v) { h = (h ^ v) * 1099511628211ULL; };
+    mix((unsigned)io->njobs); mix((unsigned)io->nnom);
+    for (int b = 0; b <= B; b++) {
+        const int j = io->traj_job_first[b];
+        if (j < 0 || j > io->njobs || (b > 0 && j < io->traj_job_first[b - 1]))
+            return set_err(c, KPILQR_ERR_ARG, "traj_job_first not monotone in [0, njobs]");
+        mix((unsigned)j);
+        if (io->nnom > 0) {
+            const int q = io->traj_nom_first[b];
+            if (q < 0 || q > io->nnom || (b > 0 && q < io->traj_nom_first[b - 1]))
+                return set_err(c, KPILQR_ERR_ARG, "traj_nom_first not monotone in [0, nnom]");
+            mix((unsigned)q);
         }
+    }
+    *sig = h;
+    return KPILQR_OK;
+}
+
+// The buffers the chunks upload into, sized on the context before a chunk is cut (a view never allocates), and what the context
+// records about the payload that lands in them.  pay_entries: entries of the payload as it will be resident.
+static int stream_reserve(kpilqr_ctx *c, StreamCall *call, unsigned long long sig, int pay_entries)
+{
+    const kpilqr_stream_io *io = call->io;
+    const int n = c->n, B = c->d.batch;
+    int rc;
+    if (call->kind == StreamPayload::jobs) {
         // The device slab is laid out from (njobs, nnom) and a chunk's payload lands at its trajectories' job / nominal
         // ranges.  Same-stream order protects a chunk's ranges from the NEXT iteration's uploads only while those ranges
         // are the same; when the layout or the per-trajectory offsets differ from the iteration still in flight, the
         // new uploads could overwrite regions another chunk stream is still differencing -- so the pipeline is joined
         // first (every chunk stream then starts behind everything enqueued so far, through pipe_in below).
+        kpilqr_fd_layout &L = call->L;
         fd_layout(n, io->njobs, io->nnom, &L);
-        const bool grows = would_grow(c->fd_dev, L.bytes);
-        if (c->pipe_dirty && (sig != c->pipe_sig || grows)) { rc = join_pipeline(c); if (rc) return rc; }
-        if (grows)                                                 // a growth frees the old slab: nothing may still read it
-            for (int i = 0; i < Ctx::kPipeStreams; i++) KP_HIP(c, hipStreamSynchronize(c->pipe_stream[i]));
+        if (c->pipe_dirty && sig != c->pipe_sig) { rc = join_pipeline(c); if (rc) return rc; }
+        rc = quiesce_for_growth(c, {{&c->fd_dev, L.bytes}}); if (rc) return rc;
         rc = fd_bind(c, io->njobs, io->nnom, &L);
         if (rc) return rc;
         c->pipe_sig = sig;
         c->njobs = io->njobs; c->nnom = io->nnom; c->eps = io->eps;
     }
-    kpilqr_fdkp_layout LK{};
-    const char *kslab = (const char *)io->fd_kp_slab;
-    if (kslab) {
+    if (call->kind == StreamPayload::kp_ordered) {
         // a chunk's payload lands at its trajectories' entry range, which only the key-points decide: same-stream order
         // protects it from the next iteration's uploads (new key-points go through KP_ENTER, which joins the pipeline)
+        kpilqr_fdkp_layout LK{};
         fdkp_layout(n, pay_entries, &LK);
-        if (would_grow(c->fdk_dev, LK.bytes)) {                 // as for the job-list slab
-            rc = join_pipeline(c); if (rc) return rc;
-            for (int i = 0; i < Ctx::kPipeStreams; i++) KP_HIP(c, hipStreamSynchronize(c->pipe_stream[i]));
-        }
+        rc = quiesce_for_growth(c, {{&c->fdk_dev, LK.bytes}}); if (rc) return rc;      // as for the job-list slab
         rc = fdk_bind(c, pay_entries, &LK);
         if (rc) return rc;
         c->fdk_entries = pay_entries; c->fdk_first = 0; c->eps = io->eps;
     }
-    if (kcols32) {
+    if (call->kind == StreamPayload::columns_f32) {
         // The staging buffer the chunks upload into (shared with kpilqr_upload_kp_columns_f32[_partial], which join the pipeline on
         // entry): a chunk's floats land at its trajectories' entry range, which only the key-points decide, so same-stream order
         // protects it from the next iteration's upload as it does the key-point ordered slab.  A growth frees the old buffer, which nothing
         // may still read: as for the slabs
-        if (would_grow(c->kpc32, (size_t)pay_entries * 3 * n * sizeof(float))) {
-            rc = join_pipeline(c); if (rc) return rc;
-            for (int i = 0; i < Ctx::kPipeStreams; i++) KP_HIP(c, hipStreamSynchronize(c->pipe_stream[i]));
-        }
+        rc = quiesce_for_growth(c, {{&c->kpc32, (size_t)pay_entries * call->rec}}); if (rc) return rc;
         rc = reserve_columns_f32(c, pay_entries);
         if (rc) return rc;
     }
@@ -2348,38 +2384,55 @@ static int iterate_streamed(kpilqr_ctx *c, const kpilqr_stream_io *io, const Str
     // chunk alone decides, so same-stream order protects it from the next call's upload whatever that call lists.  Reserved here, on
     // the context, and kept; a growth frees the old region, which nothing may still read: as for the slabs.  (kp_columns32 stages
     // in kpc32, above.)
-    const size_t T1 = (size_t)T + 1;
-    const size_t rows_per[Ctx::kRowsKinds] = {T1 * nr, T1 * nr * n, T1 * nr * m, (size_t)T * m, 0};      // doubles per trajectory
-    const double *const rows_src[Ctx::kRowsKinds] = {io->r, io->r_x, io->r_u, io->u_nom, nullptr};
-    const size_t pay_rec = kslab ? LK.entry_stride : (size_t)3 * n * 8;                                   // bytes per entry of a staged payload
-    const bool stage_pay = u.listed && (kslab || io->kp_columns);
+    const StreamList &u = call->rows;
+    const bool stage_pay = u.listed && (call->kind == StreamPayload::kp_ordered || call->kind == StreamPayload::columns);
     if (u.listed && u.count > 0) {
-        size_t need[Ctx::kRowsKinds];
-        for (int kd = 0; kd < Ctx::kRowsPayload; kd++) need[kd] = rows_src[kd] ? (size_t)B * rows_per[kd] * 8 : 0;
-        need[Ctx::kRowsPayload] = stage_pay ? (size_t)pay_entries * pay_rec : 0;
-        bool grows = false;
-        for (int kd = 0; kd < Ctx::kRowsKinds; kd++) grows = grows || would_grow(c->rows_stage[kd], need[kd]);
-        if (grows) {
-            rc = join_pipeline(c); if (rc) return rc;
-            for (int i = 0; i < Ctx::kPipeStreams; i++) KP_HIP(c, hipStreamSynchronize(c->pipe_stream[i]));
-        }
-        for (int kd = 0; kd < Ctx::kRowsKinds; kd++) { rc = reserve(c, c->rows_stage[kd], need[kd], kExact, false); if (rc < 0) return rc; }
+        const RowSizes per = row_sizes(c);
+        const size_t all = (size_t)B * sizeof(double);
+        const size_t need[Ctx::kRowsKinds] = {io->r ? all * per.r : 0, io->r_x ? all * per.r_x : 0, io->r_u ? all * per.r_u : 0, io->u_nom ? all * per.u_nom : 0,
+                                              stage_pay ? (size_t)pay_entries * call->rec : 0};
+        DevBuf<char> *const stg = c->rows_stage;
+        rc = quiesce_for_growth(c, {{&stg[0], need[0]}, {&stg[1], need[1]}, {&stg[2], need[2]}, {&stg[3], need[3]}, {&stg[4], need[4]}}); if (rc) return rc;
+        for (int kd = 0; kd < Ctx::kRowsKinds; kd++) { rc = reserve(c, stg[kd], need[kd], kExact, false); if (rc < 0) return rc; }
         // the payload region is cut by entry * record size: records behind columns (or the other way round) would cut it elsewhere,
         // and a chunk's upload could land in a range another chunk stream is still reading -- the rule of pipe_sig
-        if (stage_pay && c->rows_pay_rec != pay_rec) { rc = join_pipeline(c); if (rc) return rc; c->rows_pay_rec = pay_rec; }
+        if (stage_pay && c->rows_pay_rec != call->rec) { rc = join_pipeline(c); if (rc) return rc; c->rows_pay_rec = call->rec; }
     }
-    const double *kcols = io->kp_columns;
-    const bool new_payload = slab || kslab || kcols || kcols32;
-    if (slab) c->fd_payload = FdPayload::jobs;
-    if (kslab) c->fd_payload = FdPayload::kp_ordered;
-    if (kcols || kcols32) { c->fd_payload = FdPayload::kp_columns; c->fdk_entries = pay_entries; c->fdk_first = 0; }
-    if (new_payload) payload_changed(c);
+    if (call->kind == StreamPayload::jobs) c->fd_payload = FdPayload::jobs;
+    if (call->kind == StreamPayload::kp_ordered) c->fd_payload = FdPayload::kp_ordered;
+    if (call->kind == StreamPayload::columns || call->kind == StreamPayload::columns_f32) { c->fd_payload = FdPayload::kp_columns; c->fdk_entries = pay_entries; c->fdk_first = 0; }
+    if (call->kind != StreamPayload::none) payload_changed(c);
+    return KPILQR_OK;
+}
+
+// Phase 2 -- everything a streamed iteration does ONCE, on the context, before the chunks are cut.  Nothing here touches a chunk
+// stream except through quiesce_for_growth and join_pipeline.
+static int stream_prepare(kpilqr_ctx *c, StreamCall *call, unsigned long long sig)
+{
+    const kpilqr_stream_io *io = call->io;
+    const int B = c->d.batch;
+    int rc = pipe_setup(c);
+    if (rc) return rc;
+    if (call->nchunks < 1) call->nchunks = Ctx::kPipeStreams;          // 0: one chunk per pipeline stream
+    if (call->nchunks > B) call->nchunks = B;
+    // the chunk -> stream map must not change while earlier chunks are still in flight (same-stream order is what
+    // protects a chunk's device buffers from the next iteration's uploads)
+    if (c->pipe_dirty && c->pipe_chunks != call->nchunks) { rc = join_pipeline(c); if (rc) return rc; }
+    c->pipe_chunks = call->nchunks;
+    // uploads by SDMA, downloads by a copy kernel: the only pairing whose two directions overlap inside this pipeline
+    // (KPILQR_PIPE_COPY: bit 0 uploads by kernel, bit 1 downloads by kernel; profiles/r02_pcie_inclusive.txt)
+    const int pipe_copy = c->tune.pipe_copy >= 0 ? c->tune.pipe_copy : 2;
+    call->k_up = pipe_copy & 1; call->k_down = pipe_copy & 2;
+    // entries of the payload as it will be resident: with a list the kept trajectories' stay beside the ones that arrive
+    rc = stream_reserve(c, call, sig, call->rows.listed ? c->kp_total_host : io->entries);
+    if (rc) return rc;
+    const bool new_payload = call->kind != StreamPayload::none, by_entry = call->by_entry();
     // allocations and tables the chunks need are made HERE, on the context: a view never allocates (reserve refuses)
     if (c->fused || payload_by_entry(c)) {
         rc = ensure_kpc(c); if (rc) return rc;
         rc = ensure_entry_tables(c); if (rc) return rc;
     }
-    if (!c->fused && (kslab || kcols || kcols32) && c->tune.fd_interp != 0) { rc = ensure_segent(c); if (rc) return rc; }
+    if (!c->fused && by_entry && c->tune.fd_interp != 0) { rc = ensure_segent(c); if (rc) return rc; }
     if (c->fused) {
         c->last_linearise = "in_sweep";
         // per-DoF lists: a chunk computes the slopes of ITS entries, whose range only the host copy of the lists gives
@@ -2411,172 +2464,210 @@ static int iterate_streamed(kpilqr_ctx *c, const kpilqr_stream_io *io, const Str
     // chunks' wave organisation is the whole batch's: make_view gives a chunk its share of the SIMDs)
     if (!(c->fused && plan_backward_fused(c, false).rxc && plan_forward_fused(c).rxc)) { rc = ensure_rx_buffer(c); if (rc) return rc; }
     // the list of the gains that come down: on the device before the chunks, which read their slices of it
-    rc = pipe_list_bind(c, g); if (rc) return rc;
+    rc = pipe_list_bind(c, call->gains); if (rc) return rc;
     // the list of the inputs that come up, in its ring slot (an empty list reads none)
-    int uslot = 0, ui = 0;                      // ui: first entry of upload_traj not below the chunk
-    size_t upe = 0;                             // payload entries of the listed trajectories below the chunk
-    if (u.listed && u.count > 0) { rc = rows_list_bind(c, u, nchunks, new_payload, &uslot); if (rc) return rc; }
-    const int *const ulist = u.listed && u.count > 0 ? (const int *)c->rows_list + (size_t)uslot * 2 * B : nullptr, *const ufirst = ulist ? ulist + B : nullptr;
-    const bool gather = g.K32 || g.listed;      // K (and k of a list) leave through gains.hip's gather kernel
-    int li = 0;                                 // first list entry not below the chunk (chunks and list both increase)
+    const StreamList &u = call->rows;
+    if (u.listed && u.count > 0) {
+        rc = rows_list_bind(c, u, call->nchunks, new_payload, &call->uslot); if (rc) return rc;
+        call->ulist = (const int *)c->rows_list + (size_t)call->uslot * 2 * B; call->ufirst = call->ulist + B;
+    }
+    // where a chunk's range of a by-entry payload lands, now that every buffer is there
+    char *const stage = c->rows_stage[Ctx::kRowsPayload];
+    if (call->kind == StreamPayload::kp_ordered) { call->place = c->fdk_dev.p; call->land = u.listed ? stage : (char *)c->fdk_dev.p; }
+    if (call->kind == StreamPayload::columns) { call->place = c->kpc.p; call->land = u.listed ? stage : (char *)c->kpc.p; }
+    if (call->kind == StreamPayload::columns_f32) call->land = (char *)c->kpc32.p;
     // order the chunk streams behind whatever the caller enqueued on the context's stream so far (key-points, weights ...)
     KP_HIP(c, hipEventRecord(c->pipe_in, c->stream));
     // from here on chunk streams hold work: every exit path, errors included, leaves the pipeline marked for joining, so a
     // later kpilqr_sync / kpilqr_destroy waits for the DMAs that read the caller's buffers
     c->pipe_dirty = true;
+    return KPILQR_OK;
+}
 
+// One chunk of a streamed iteration: trajectories [b0, b1) as the view v on stream s, and its slices of the upload list
+struct StreamChunk {
+    int ch = 0, b0 = 0, b1 = 0;
+    hipStream_t s = nullptr;
+    kpilqr_ctx v;
+    int u0 = 0, urows = 0;             // inputs of a list: rows [u0, u0 + urows) of every compact input ...
+    size_t uent0 = 0, uents = 0;       // ... and, of a by-entry payload, `uents` entries from entry uent0 on
+};
+
+// The chunk's FD payload: uploaded, and the view told what it holds
+static int stream_chunk_payload(kpilqr_ctx *c, const StreamCall &call, StreamChunk &k)
+{
+    const kpilqr_stream_io *io = call.io;
+    kpilqr_ctx &v = k.v;
+    hipStream_t s = k.s;
+    const int n = c->n;
+    if (call.kind == StreamPayload::jobs) {
+        const kpilqr_fd_layout &L = call.L;
+        const char *slab = (const char *)io->fd_slab;
+        const int j0 = io->traj_job_first[k.b0], j1 = io->traj_job_first[k.b1];
+        const size_t J = (size_t)(j1 - j0), jo = (size_t)j0;
+        if (J) {
+            KP_HIP(c, call.h2d(c->xplus + jo * n, slab + L.xplus + jo * n * 8, J * n * 8, s));
+            KP_HIP(c, call.h2d(c->xminus + jo * n, slab + L.xminus + jo * n * 8, J * n * 8, s));
+            KP_HIP(c, call.h2d(c->job_b + jo, slab + L.job_b + jo * 4, J * 4, s));
+            KP_HIP(c, call.h2d(c->job_t + jo, slab + L.job_t + jo * 4, J * 4, s));
+            KP_HIP(c, call.h2d(c->job_col + jo, slab + L.job_col + jo * 4, J * 4, s));
+            KP_HIP(c, call.h2d(c->job_nom + jo, slab + L.job_nom + jo * 4, J * 4, s));
+            KP_HIP(c, call.h2d(c->job_mode + jo, slab + L.job_mode + jo, J, s));
+        }
+        if (io->nnom > 0) {
+            const int q0 = io->traj_nom_first[k.b0], q1 = io->traj_nom_first[k.b1];
+            if (q1 > q0) KP_HIP(c, call.h2d(c->xnom + (size_t)q0 * n, slab + L.xnom + (size_t)q0 * n * 8, (size_t)(q1 - q0) * n * 8, s));
+        }
+        // the chunk's jobs: a contiguous range of the job arrays
+        v.job_b = c->job_b + jo; v.job_t = c->job_t + jo; v.job_col = c->job_col + jo; v.job_nom = c->job_nom + jo;
+        v.job_mode = c->job_mode + jo; v.xplus = c->xplus + jo * n; v.xminus = c->xminus + jo * n; v.njobs = (int)J;
+    } else if (call.by_entry()) {
+        // ONE copy of ONE contiguous range to where the chunk's first entry sits in `land`: the chunk's own entries (the view's range)
+        // straight into place, or with a list its compact slice into the staging region; then at most ONE launch: FP32 columns are
+        // widened into the column store (columns_f32.hip; the context's absolute tables; with a list, of the listed trajectories
+        // alone), FP64 payloads of a list moved to the listed trajectories' entry ranges.  The view is the whole chunk's either way.
+        const bool listed = call.rows.listed;
+        const size_t rec = call.rec, e0 = (size_t)v.fdk_first, first = listed ? k.uent0 : e0, count = listed ? k.uents : (size_t)v.kp_view_entries;
+        if (count) {
+            KP_HIP(c, call.h2d(call.land + e0 * rec, call.src + first * rec, count * rec, s));
+            if (call.kind == StreamPayload::columns_f32) KP_HIP(c, launch_kp_columns_f32_range(c, s, k.b0 * c->d.dof, k.b1 * c->d.dof, c->kpc32, call.ufirst));
+            else if (listed) KP_HIP(c, launch_rows_in_entries(c, s, call.ulist + k.u0, k.urows, call.ufirst, rec, call.land, call.place));
+        }
+        v.njobs = 0; v.fdk_entries = v.kp_view_entries;      // the chunk's entries
+        if (call.kind != StreamPayload::kp_ordered) v.pay.kpc_valid = true;
+    } else {
+        // no new FD payload: what was differenced before is reused (kpc / the records' key-point columns)
+        v.njobs = 0;
+        if (payload_by_entry(c) && c->kp_traj_first_host) v.fdk_entries = v.kp_view_entries;
+    }
+    return KPILQR_OK;
+}
+
+// The chunk's rows of r, r_x, r_u, u_nom (those that are given) and its lambdas
+static int stream_chunk_rows(kpilqr_ctx *c, const StreamCall &call, StreamChunk &k)
+{
+    const kpilqr_stream_io *io = call.io;
+    const RowSizes sz = row_sizes(c);
+    const size_t o = k.b0, cnt = k.b1 - k.b0;
+    const double *const src[Ctx::kRowsPayload] = {io->r, io->r_x, io->r_u, io->u_nom};
+    double *const dst[Ctx::kRowsPayload] = {c->r, c->r_x, c->r_u, c->u_nom};
+    const size_t pers[Ctx::kRowsPayload] = {sz.r, sz.r_x, sz.r_u, sz.u_nom};
+    for (int kd = 0; kd < Ctx::kRowsPayload; kd++) {
+        const size_t per = pers[kd];
+        if (!src[kd]) continue;
+        if (!call.rows.listed) {
+            KP_HIP(c, call.h2d(dst[kd] + o * per, src[kd] + o * per, cnt * per * 8, k.s));
+        } else if (k.urows) {
+            // of a list: ONE upload of the chunk's rows into its staging region (at the chunk's first trajectory), ONE launch of
+            // k_rows_in (rows_in.hip) to the listed trajectories' places in the CONTEXT's buffer
+            double *const stg = (double *)c->rows_stage[kd].p + o * per;
+            KP_HIP(c, call.h2d(stg, src[kd] + (size_t)k.u0 * per, (size_t)k.urows * per * 8, k.s));
+            KP_HIP(c, launch_rows_in(k.s, call.ulist + k.u0, k.urows, (long long)per, stg, dst[kd]));
+        }
+    }
+    // (the slot of the list may be written again once this stream has passed here)
+    if (k.urows) {
+        KP_HIP(c, hipEventRecord(c->rows_read[call.uslot][k.ch % Ctx::kPipeStreams], k.s));
+        c->rows_read_set[call.uslot][k.ch % Ctx::kPipeStreams] = true;
+    }
+    if (io->lambda) KP_HIP(c, call.h2d(k.v.lambda, io->lambda + o, cnt * 8, k.s));
+    return KPILQR_OK;
+}
+
+// The chunk's kernels: the ordinary launchers on the view
+static int stream_chunk_sweeps(kpilqr_ctx *c, const StreamCall &call, StreamChunk &k)
+{
+    const kpilqr_stream_io *io = call.io;
+    kpilqr_ctx &v = k.v;
+    const size_t o = k.b0, cnt = k.b1 - k.b0;
+    const auto of_view = [&](int rcv) { if (rcv) c->err = v.err; return rcv; };      // a view's refusal is the context's
+    int rc;
+    if (!c->fused) {
+        // (no new payload: the records hold its key-point columns already)
+        rc = of_view(linearise(&v, call.kind != StreamPayload::none));
+        if (rc) return rc;
+        c->last_linearise = v.last_linearise;
+        if (!c->tiled_a6) KP_HIP(c, launch_cost_derivs(&v));
+    }
+    v.retry_attempts = retry_attempts_for(c, io->lambda ? io->lambda + o : nullptr, cnt);      // (the chunk's own lambdas decide its attempts)
+    rc = of_view(run_backward(&v, call.pd_check_stride));
+    if (rc) return rc;
+    c->retry_ran = v.retry_ran;
+    rc = of_view(run_forward(&v, nullptr));
+    if (rc) return rc;
+    c->last_bwd = v.last_bwd; c->last_fwd = v.last_fwd;
+    return KPILQR_OK;
+}
+
+// The chunk's outputs.  K, k by a copy kernel: it overlaps with the SDMA uploads of the next chunks (two SDMA directions do not)
+static int stream_chunk_down(kpilqr_ctx *c, StreamCall &call, StreamChunk &k)
+{
+    const kpilqr_stream_io *io = call.io;
+    const kpilqr_ctx &v = k.v;
+    hipStream_t s = k.s;
+    StreamList &g = call.gains;
+    const RowSizes per = row_sizes(c);
+    const size_t na = c->d.n_alpha, o = k.b0, cnt = k.b1 - k.b0;
+    const bool gather = call.K32 || g.listed;      // K (and k of a list) leave through gains.hip's gather kernel
+    if (gather) {
+        // K32 and the rows of a list: gathered (and rounded) by ONE launch per array straight into the pinned destination, whatever
+        // KPILQR_PIPE_COPY says (through SDMA they would need a staging buffer).  The chunk's share of a list is one slice of it,
+        // [i0, i1), and one contiguous range of the compact outputs; without a list it is the chunk's own rows.
+        int i0 = k.b0, i1 = k.b1;
+        if (g.listed) g.slice_below(k.b1, &i0, &i1);
+        const int *tl = g.listed ? (const int *)c->pipe_list + i0 : nullptr;
+        if (call.K32) KP_HIP(c, launch_gains_out(c, s, GainsForm::K_f32, tl, k.b0, i1 - i0, call.K32 + (size_t)i0 * per.K));
+        else if (io->K) KP_HIP(c, launch_gains_out(c, s, GainsForm::K_f64, tl, k.b0, i1 - i0, io->K + (size_t)i0 * per.K));
+        if (io->k && g.listed) KP_HIP(c, launch_gains_out(c, s, GainsForm::k_f64, tl, k.b0, i1 - i0, io->k + (size_t)i0 * per.k));
+    }
+    // K and k of the whole batch (k: the copy it always was, beside K32 too), by the copy kernel unless KPILQR_PIPE_COPY says SDMA
+    const auto d2h = [&](double *dst, const double *src, size_t count) {
+        return call.k_down ? launch_copy_out(s, dst, src, count) : hipMemcpyAsync(dst, src, count * 8, hipMemcpyDeviceToHost, s);
+    };
+    if (io->K && !gather) KP_HIP(c, d2h(io->K + o * per.K, v.K, cnt * per.K));
+    if (io->k && !g.listed) KP_HIP(c, d2h(io->k + o * per.k, v.k, cnt * per.k));
+    if (io->cost_pred) KP_HIP(c, hipMemcpyAsync(io->cost_pred + o * na, v.cost_pred, cnt * na * 8, hipMemcpyDeviceToHost, s));
+    if (io->delta_J) KP_HIP(c, hipMemcpyAsync(io->delta_J + o, v.delta_J, cnt * 8, hipMemcpyDeviceToHost, s));
+    if (io->status) KP_HIP(c, hipMemcpyAsync(io->status + o, v.status, cnt * 4, hipMemcpyDeviceToHost, s));
+    return KPILQR_OK;
+}
+
+// A streamed iteration in three phases: every refusal (stream_check), everything done once on the context (stream_prepare), then
+// per chunk the payload, the rows, the sweeps and the downloads, each chunk on its own stream.
+static int iterate_streamed(kpilqr_ctx *c, StreamCall call)
+{
+    KP_HIP(c, hipSetDevice(c->d.device));
+    unsigned long long sig = 0;
+    int rc = stream_check(c, &call, &sig);
+    if (rc) return rc;
+    rc = stream_prepare(c, &call, sig);
+    if (rc) return rc;
     // What the chunks do to the payload-derived state comes back from the LAST view, whole (every chunk does the same to its slice
     // of kpc, kps and the records; a view never takes the union route, so kpcu_valid returns as it left).  Nothing of ListsDerived
     // comes back: a view builds no table -- the context ensured them above.
     PayloadDerived after = c->pay;
-    for (int ch = 0; ch < nchunks; ch++) {
-        const int b0 = (int)((long long)B * ch / nchunks), b1 = (int)((long long)B * (ch + 1) / nchunks), nb = b1 - b0;
-        if (nb <= 0) continue;
-        hipStream_t s = c->pipe_stream[ch % Ctx::kPipeStreams];
-        KP_HIP(c, hipStreamWaitEvent(s, c->pipe_in, 0));
-        kpilqr_ctx v;
-        make_view(c, b0, nb, s, &v);
-        const auto of_view = [&](int rcv) { if (rcv) c->err = v.err; return rcv; };      // a view's refusal is the context's
-        const size_t o = b0, cnt = nb;
-        // ---- H2D of the chunk ------------------------------------------------------------------------------------
-        // inputs of a list: the chunk's share is the slice [ui0, ui) of the list -- `rows` rows of every compact input from row ui0
-        // on, and, of a by-entry payload, `lE` entries from entry upe0 on
-        const int ui0 = ui;
-        const size_t upe0 = upe;
-        if (u.listed) {
-            for (; ui < u.count && u.traj[ui] < b1; ui++)
-                if (new_payload) upe += (size_t)(c->kp_traj_first_host[u.traj[ui] + 1] - c->kp_traj_first_host[u.traj[ui]]);
-        }
-        const int rows = ui - ui0;
-        const size_t lE = upe - upe0;
-        if (u.listed && new_payload) {
-            // ONE upload of the chunk's compact slice to where the chunk's first entry would sit in the staging region, ONE launch that
-            // moves (kp_columns32: decodes) the listed trajectories' entry ranges from there into place; the view is the whole chunk's
-            const int e0 = c->kp_traj_first_host[b0], e1 = c->kp_traj_first_host[b1];
-            if (lE && kcols32) {
-                KP_HIP(c, h2d(c->kpc32 + (size_t)e0 * 3 * n, kcols32 + upe0 * 3 * n, lE * 3 * n * sizeof(float), s));
-                KP_HIP(c, launch_kp_columns_f32_range(c, s, b0 * c->d.dof, b1 * c->d.dof, c->kpc32, ufirst));
-            } else if (lE) {
-                char *const stg = c->rows_stage[Ctx::kRowsPayload];
-                const char *const src = kslab ? kslab : (const char *)io->kp_columns;
-                KP_HIP(c, h2d(stg + (size_t)e0 * pay_rec, src + upe0 * pay_rec, lE * pay_rec, s));
-                KP_HIP(c, launch_rows_in_entries(c, s, ulist + ui0, rows, ufirst, pay_rec, stg, kslab ? (void *)c->fdk_dev.p : (void *)c->kpc.p));
-            }
-            v.njobs = 0; v.fdk_first = e0; v.fdk_entries = e1 - e0;
-            if (!kslab) v.pay.kpc_valid = true;
-        } else if (slab) {
-            const int j0 = io->traj_job_first[b0], j1 = io->traj_job_first[b1];
-            const size_t J = (size_t)(j1 - j0), jo = (size_t)j0;
-            if (J) {
-                KP_HIP(c, h2d(c->xplus + jo * n, slab + L.xplus + jo * n * 8, J * n * 8, s));
-                KP_HIP(c, h2d(c->xminus + jo * n, slab + L.xminus + jo * n * 8, J * n * 8, s));
-                KP_HIP(c, h2d(c->job_b + jo, slab + L.job_b + jo * 4, J * 4, s));
-                KP_HIP(c, h2d(c->job_t + jo, slab + L.job_t + jo * 4, J * 4, s));
-                KP_HIP(c, h2d(c->job_col + jo, slab + L.job_col + jo * 4, J * 4, s));
-                KP_HIP(c, h2d(c->job_nom + jo, slab + L.job_nom + jo * 4, J * 4, s));
-                KP_HIP(c, h2d(c->job_mode + jo, slab + L.job_mode + jo, J, s));
-            }
-            if (io->nnom > 0) {
-                const int q0 = io->traj_nom_first[b0], q1 = io->traj_nom_first[b1];
-                if (q1 > q0) KP_HIP(c, h2d(c->xnom + (size_t)q0 * n, slab + L.xnom + (size_t)q0 * n * 8, (size_t)(q1 - q0) * n * 8, s));
-            }
-            // the chunk's jobs: a contiguous range of the job arrays
-            v.job_b = c->job_b + jo; v.job_t = c->job_t + jo; v.job_col = c->job_col + jo; v.job_nom = c->job_nom + jo;
-            v.job_mode = c->job_mode + jo; v.xplus = c->xplus + jo * n; v.xminus = c->xminus + jo * n; v.njobs = (int)J;
-        } else if (kslab) {
-            const int e0 = c->kp_traj_first_host[b0], e1 = c->kp_traj_first_host[b1];
-            const size_t E = (size_t)(e1 - e0), eo = (size_t)e0;
-            if (E) KP_HIP(c, h2d(c->fdk_dev + eo * LK.entry_stride, kslab + eo * LK.entry_stride, E * LK.entry_stride, s));   // the chunk: ONE range
-            v.fdk_first = e0; v.fdk_entries = (int)E;      // the chunk's entries
-        } else if (kcols) {
-            // the chunk's columns, straight into its range of the column store
-            const int e0 = c->kp_traj_first_host[b0], e1 = c->kp_traj_first_host[b1];
-            const size_t E = (size_t)(e1 - e0), eo = (size_t)e0 * 3 * n;
-            if (E) KP_HIP(c, h2d(c->kpc + eo, kcols + eo, E * 3 * n * 8, s));
-            v.njobs = 0; v.fdk_first = e0; v.fdk_entries = (int)E;
-            v.pay.kpc_valid = true;
-        } else if (kcols32) {
-            // the chunk's encoded floats into its range of the staging buffer, widened from there into its range of the column store:
-            // ONE copy, ONE launch (columns_f32.hip; the context's absolute tables), then the view is the FP64 columns' view
-            const int e0 = c->kp_traj_first_host[b0], e1 = c->kp_traj_first_host[b1];
-            const size_t E = (size_t)(e1 - e0), eo = (size_t)e0 * 3 * n;
-            if (E) {
-                KP_HIP(c, h2d(c->kpc32 + eo, kcols32 + eo, E * 3 * n * sizeof(float), s));
-                KP_HIP(c, launch_kp_columns_f32_range(c, s, b0 * c->d.dof, b1 * c->d.dof, c->kpc32));
-            }
-            v.njobs = 0; v.fdk_first = e0; v.fdk_entries = (int)E;
-            v.pay.kpc_valid = true;
-        } else {
-            // no new FD payload: what was differenced before is reused (kpc / the records' key-point columns)
-            v.njobs = 0;
-            if (payload_by_entry(c) && c->kp_traj_first_host) {
-                v.fdk_first = c->kp_traj_first_host[b0]; v.fdk_entries = c->kp_traj_first_host[b1] - v.fdk_first;
-            }
-        }
-        if (u.listed) {
-            // per array that is given: ONE upload of the chunk's rows into its staging region (at the chunk's first trajectory), ONE
-            // launch of k_rows_in (rows_in.hip) to the listed trajectories' places in the CONTEXT's buffer
-            double *const rows_dst[Ctx::kRowsPayload] = {c->r, c->r_x, c->r_u, c->u_nom};
-            for (int kd = 0; kd < Ctx::kRowsPayload && rows; kd++) {
-                if (!rows_src[kd]) continue;
-                const size_t per = rows_per[kd];
-                double *const stg = (double *)c->rows_stage[kd].p + o * per;
-                KP_HIP(c, h2d(stg, rows_src[kd] + (size_t)ui0 * per, (size_t)rows * per * 8, s));
-                KP_HIP(c, launch_rows_in(s, ulist + ui0, rows, (long long)per, stg, rows_dst[kd]));
-            }
-            // (the slot of the list may be written again once this stream has passed here)
-            if (rows) {
-                KP_HIP(c, hipEventRecord(c->rows_read[uslot][ch % Ctx::kPipeStreams], s));
-                c->rows_read_set[uslot][ch % Ctx::kPipeStreams] = true;
-            }
-        } else {
-            if (io->r) KP_HIP(c, h2d(v.r, io->r + o * (T + 1) * nr, cnt * (T + 1) * nr * 8, s));
-            if (io->r_x) KP_HIP(c, h2d(v.r_x, io->r_x + o * (T + 1) * nr * n, cnt * (T + 1) * nr * n * 8, s));
-            if (io->r_u) KP_HIP(c, h2d(v.r_u, io->r_u + o * (T + 1) * nr * m, cnt * (T + 1) * nr * m * 8, s));
-            if (io->u_nom) KP_HIP(c, h2d(v.u_nom, io->u_nom + o * T * m, cnt * T * m * 8, s));
-        }
-        if (io->lambda) KP_HIP(c, h2d(v.lambda, io->lambda + o, cnt * 8, s));
-        // ---- kernels of the chunk --------------------------------------------------------------------------------
-        if (!c->fused) {
-            // (no new payload: the records hold its key-point columns already)
-            rc = of_view(linearise(&v, new_payload));
-            if (rc) return rc;
-            c->last_linearise = v.last_linearise;
-            if (!c->tiled_a6) KP_HIP(c, launch_cost_derivs(&v));
-        }
-        v.retry_attempts = retry_attempts_for(c, io->lambda ? io->lambda + o : nullptr, cnt);      // (the chunk's own lambdas decide its attempts)
-        rc = of_view(run_backward(&v, pd_check_stride));
-        if (rc) return rc;
-        c->retry_ran = v.retry_ran;
-        rc = of_view(run_forward(&v, nullptr));
-        if (rc) return rc;
-        after = v.pay;
-        c->last_bwd = v.last_bwd; c->last_fwd = v.last_fwd;
-        // ---- D2H of the chunk ------------------------------------------------------------------------------------
-        // K, k by a copy kernel: it overlaps with the SDMA uploads of the next chunks (two SDMA directions do not)
-        if (gather) {
-            // K32 and the rows of a list: gathered (and rounded) by ONE launch per array straight into the pinned destination, whatever
-            // KPILQR_PIPE_COPY says (through SDMA they would need a staging buffer).  The chunk's share of a list is one slice of it,
-            // [i0, li), and one contiguous range of the compact outputs; without a list it is the chunk's own rows.
-            int i0 = b0, rows = nb;
-            if (g.listed) { i0 = li; while (li < g.count && g.traj[li] < b1) li++; rows = li - i0; }
-            const int *tl = g.listed ? (const int *)c->pipe_list + i0 : nullptr;
-            const size_t perK = (size_t)T * n * m, perk = (size_t)T * m;
-            if (g.K32) KP_HIP(c, launch_gains_out(c, s, GainsForm::K_f32, tl, b0, rows, g.K32 + (size_t)i0 * perK));
-            else if (io->K) KP_HIP(c, launch_gains_out(c, s, GainsForm::K_f64, tl, b0, rows, io->K + (size_t)i0 * perK));
-            if (io->k && g.listed) KP_HIP(c, launch_gains_out(c, s, GainsForm::k_f64, tl, b0, rows, io->k + (size_t)i0 * perk));
-        }
-        const bool k_whole = io->k && !g.listed;      // k of the whole batch: the copy it always was, beside K32 too
-        if (k_down) {
-            if (io->K && !gather) KP_HIP(c, launch_copy_out(s, io->K + o * T * n * m, v.K, cnt * T * n * m));
-            if (k_whole) KP_HIP(c, launch_copy_out(s, io->k + o * T * m, v.k, cnt * T * m));
-        } else {
-            if (io->K && !gather) KP_HIP(c, hipMemcpyAsync(io->K + o * T * n * m, v.K, cnt * T * n * m * 8, hipMemcpyDeviceToHost, s));
-            if (k_whole) KP_HIP(c, hipMemcpyAsync(io->k + o * T * m, v.k, cnt * T * m * 8, hipMemcpyDeviceToHost, s));
-        }
-        if (io->cost_pred) KP_HIP(c, hipMemcpyAsync(io->cost_pred + o * na, v.cost_pred, cnt * na * 8, hipMemcpyDeviceToHost, s));
-        if (io->delta_J) KP_HIP(c, hipMemcpyAsync(io->delta_J + o, v.delta_J, cnt * 8, hipMemcpyDeviceToHost, s));
-        if (io->status) KP_HIP(c, hipMemcpyAsync(io->status + o, v.status, cnt * 4, hipMemcpyDeviceToHost, s));
+    const int B = c->d.batch;
+    StreamList &u = call.rows;
+    StreamChunk k;
+    size_t uent = 0;                            // payload entries of the listed trajectories below the chunk
+    for (k.ch = 0; k.ch < call.nchunks; k.ch++) {
+        k.b0 = chunk_first(B, k.ch, call.nchunks); k.b1 = chunk_first(B, k.ch + 1, call.nchunks);
+        if (k.b1 <= k.b0) continue;
+        k.s = c->pipe_stream[k.ch % Ctx::kPipeStreams];
+        KP_HIP(c, hipStreamWaitEvent(k.s, c->pipe_in, 0));
+        make_view(c, k.b0, k.b1 - k.b0, k.s, &k.v);
+        // inputs of a list: the chunk's share is one slice of the list, and of a by-entry payload the entries of that slice
+        int u1 = 0;
+        if (u.listed) u.slice_below(k.b1, &k.u0, &u1);
+        k.urows = u1 - k.u0; k.uent0 = uent;
+        if (call.by_entry())
+            for (int i = k.u0; i < u1; i++) uent += (size_t)(c->kp_traj_first_host[u.traj[i] + 1] - c->kp_traj_first_host[u.traj[i]]);
+        k.uents = uent - k.uent0;
+        rc = stream_chunk_payload(c, call, k); if (rc) return rc;
+        rc = stream_chunk_rows(c, call, k); if (rc) return rc;
+        rc = stream_chunk_sweeps(c, call, k); if (rc) return rc;
+        after = k.v.pay;
+        rc = stream_chunk_down(c, call, k); if (rc) return rc;
     }
     c->pay = after;
     return KPILQR_OK;
@@ -2585,25 +2676,25 @@ static int iterate_streamed(kpilqr_ctx *c, const kpilqr_stream_io *io, const Str
 int kpilqr_iterate_streamed(kpilqr_ctx *c, const kpilqr_stream_io *io, int pd_check_stride, int nchunks)
 {
     if (!c || !io) return KPILQR_ERR_ARG;
-    return iterate_streamed(c, io, StreamGains{}, pd_check_stride, nchunks);
+    return iterate_streamed(c, StreamCall(io, pd_check_stride, nchunks));
 }
 
-// the checks and the options of a kpilqr_stream_io2, for the two calls that carry one
-static int stream_gains_of(kpilqr_ctx *c, const kpilqr_stream_io2 *io2, StreamGains *g)
+// the checks and the options of a kpilqr_stream_io2, for the three calls that carry one
+static int stream_gains_of(kpilqr_ctx *c, const kpilqr_stream_io2 *io2, StreamCall *call)
 {
     if (io2->struct_size != sizeof(kpilqr_stream_io2)) return set_err(c, KPILQR_ERR_ARG, "kpilqr_iterate_streamed2: struct_size is not sizeof(kpilqr_stream_io2) of this library");
     if (io2->gain_count < 0 || (io2->gain_count > 0 && !io2->gain_traj)) return set_err(c, KPILQR_ERR_ARG, "kpilqr_iterate_streamed2: gain_count < 0, or listed trajectories without gain_traj");
-    g->K32 = io2->K32;
-    g->listed = io2->gain_traj != nullptr; g->count = io2->gain_count; g->traj = io2->gain_traj;
+    call->K32 = io2->K32;
+    call->gains.listed = io2->gain_traj != nullptr; call->gains.count = io2->gain_count; call->gains.traj = io2->gain_traj;
     return KPILQR_OK;
 }
 
 int kpilqr_iterate_streamed2(kpilqr_ctx *c, const kpilqr_stream_io2 *io2, int pd_check_stride, int nchunks)
 {
     if (!c || !io2) return KPILQR_ERR_ARG;
-    StreamGains g;
-    if (const int rc = stream_gains_of(c, io2, &g)) return rc;
-    return iterate_streamed(c, &io2->io, g, pd_check_stride, nchunks);
+    StreamCall call(&io2->io, pd_check_stride, nchunks);
+    if (const int rc = stream_gains_of(c, io2, &call)) return rc;
+    return iterate_streamed(c, call);
 }
 
 // kpilqr_iterate_streamed2 with the key-point columns as ENCODED FP32 for a payload: with kp_columns32 == NULL it IS that call
@@ -2611,9 +2702,10 @@ int kpilqr_iterate_streamed3(kpilqr_ctx *c, const kpilqr_stream_io3 *io3, int pd
 {
     if (!c || !io3) return KPILQR_ERR_ARG;
     if (io3->struct_size != sizeof(kpilqr_stream_io3)) return set_err(c, KPILQR_ERR_ARG, "kpilqr_iterate_streamed3: struct_size is not sizeof(kpilqr_stream_io3) of this library");
-    StreamGains g;
-    if (const int rc = stream_gains_of(c, &io3->io2, &g)) return rc;
-    return iterate_streamed(c, &io3->io2.io, g, pd_check_stride, nchunks, io3->kp_columns32);
+    StreamCall call(&io3->io2.io, pd_check_stride, nchunks);
+    if (const int rc = stream_gains_of(c, &io3->io2, &call)) return rc;
+    call.kcols32 = io3->kp_columns32;
+    return iterate_streamed(c, call);
 }
 
 // kpilqr_iterate_streamed3 taking the inputs of a list of trajectories alone: with upload_traj == NULL it IS that call
@@ -2625,11 +2717,11 @@ int kpilqr_iterate_streamed4(kpilqr_ctx *c, const kpilqr_stream_io4 *io4, int pd
     if (io3->struct_size != sizeof(kpilqr_stream_io3)) return set_err(c, KPILQR_ERR_ARG, "kpilqr_iterate_streamed3: struct_size is not sizeof(kpilqr_stream_io3) of this library");
     if (io4->upload_count < 0 || (io4->upload_count > 0 && !io4->upload_traj))
         return set_err(c, KPILQR_ERR_ARG, "kpilqr_iterate_streamed4: upload_count < 0, or listed trajectories without upload_traj");
-    StreamGains g;
-    if (const int rc = stream_gains_of(c, &io3->io2, &g)) return rc;
-    StreamRows u;
-    u.listed = io4->upload_traj != nullptr; u.count = u.listed ? io4->upload_count : 0; u.traj = io4->upload_traj;
-    return iterate_streamed(c, &io3->io2.io, g, pd_check_stride, nchunks, io3->kp_columns32, u);
+    StreamCall call(&io3->io2.io, pd_check_stride, nchunks);
+    if (const int rc = stream_gains_of(c, &io3->io2, &call)) return rc;
+    call.kcols32 = io3->kp_columns32;
+    call.rows.listed = io4->upload_traj != nullptr; call.rows.count = call.rows.listed ? io4->upload_count : 0; call.rows.traj = io4->upload_traj;
+    return iterate_streamed(c, call);
 }
 
 // ---- multi-GPU: the line-search cost reduction -----------------------------------------------------------
