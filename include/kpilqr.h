@@ -872,6 +872,14 @@ const char *kpilqr_forward_variant(kpilqr_ctx *ctx);
  *     "in_sweep"                   KPILQR_FLAG_FUSED context: the sweeps difference and interpolate themselves
  *     "kp_union"                   the same on the union store of KPILQR_FLAG_UNION_KEYPOINTS (kpilqr_iterate with per-DoF lists)
  * with ":subset" appended when the last linearisation was a kpilqr_fd_interpolate_partial.
+ * which = 3: how the last forward launch scored its steps (kpilqr_forward_linear[_partial], kpilqr_iterate[_partial] or the chunks of
+ * kpilqr_iterate_streamed*); waits like which = 1.  "" before any forward launch and after a forward call that was refused before it
+ * launched anything, else
+ *     "pair2"   one residual-Jacobian product scores TWO steps: the one-wave sweep on uniform lists with the constant Jacobian
+ *               ("...:w1:uni:ru0:rxc") and n_alpha <= 8 -- the candidates then fill at most half of the matrix tile's columns
+ *     "step"    every step has its own product: every other launch
+ *     "?"       the device's word on the key-point lists could not be read back (which = 1 then ends in ":?")
+ *   A library older than this answer returns "" for which = 3 at all times; KPILQR_VERSION is unchanged.
  * For logs and tests (a test can assert which kernel form it exercised).  version >= 400. */
 const char *kpilqr_last_launch(kpilqr_ctx *ctx, int which);
 

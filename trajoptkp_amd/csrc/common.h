@@ -51,6 +51,9 @@ struct FusedLaunch {
     bool rxc = false;                   // constant r_x kept in registers (ru0 instantiations only): nobody reads the r_x buffer
     bool slopes = false;                // the general (per-DoF list) form walks the slope store
     bool excl = false;                  // w1: every wave has a SIMD to itself (the _excl twins)
+    bool pair2 = false;                 // forward, w1 on uniform lists with rxc: one scoring product per two steps (n_alpha <= 8)
+    bool fwd_ran = false;               // last_fwd only: the forward call that left this record launched its sweep (set behind the launch,
+                                        // also on the empty record of a launch that is not fused); kpilqr_last_launch(ctx, 3) is "" without it
     bool uni_on_union = false;          // the launch ran on the union store (KPILQR_FLAG_UNION_KEYPOINTS); only kpilqr_last_launch reads it
 };
 

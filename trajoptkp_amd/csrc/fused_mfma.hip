@@ -1530,24 +1530,28 @@ k_backward_fusedph_retry(RecLayout L, FusedArgs F, int T, int role_shift, const 
 // the Y operands (row = contraction index) through a padded LDS transpose, off the Z dependency chain.
 // The time loop of the forward sweep by register set: NS consecutive steps with compile-time set indices, and what is left
 // below a full group at the end (MODE 1 ends in the final step, mode 3, at t = T-1; MODE 0 has no final step of its own).
-template <int K, int NS, int MODE, class StepF>
+// The role tag of a step (paired scoring, see PAIR2 in forward_fused_body): 0 the step scores itself with its own r_x product
+// (every form but the paired one), 1 the even member of a pair (no scoring: its Z stays live), 2 the odd member (ONE product
+// scores both), 3 a step of the paired form that scores itself (the step in front of the final one when it has no partner, and
+// the final step).  P2: the sets pair up as (0, 1), (2, 3).
+template <int K, int NS, int MODE, bool P2 = false, class StepF>
 __device__ __forceinline__ void fwd_steps(StepF &step, int t)
 {
-    step(t, std::integral_constant<int, MODE>{}, std::integral_constant<int, K>{});
-    if constexpr (K + 1 < NS) fwd_steps<K + 1, NS, MODE>(step, t + 1);
+    step(t, std::integral_constant<int, MODE>{}, std::integral_constant<int, K>{}, std::integral_constant<int, P2 ? 1 + (K & 1) : 0>{});
+    if constexpr (K + 1 < NS) fwd_steps<K + 1, NS, MODE, P2>(step, t + 1);
 }
 template <int K, int NS, int MODE, class StepF>
 __device__ __forceinline__ void fwd_tail(StepF &step, int t, int T)
 {
     if constexpr (MODE == 0) {
         if (t < T) {
-            step(t, std::integral_constant<int, 0>{}, std::integral_constant<int, K>{});
+            step(t, std::integral_constant<int, 0>{}, std::integral_constant<int, K>{}, std::integral_constant<int, 0>{});
             if constexpr (K + 1 < NS) fwd_tail<K + 1, NS, 0>(step, t + 1, T);
         }
     } else {
-        if (K + 1 == NS || t == T - 1) step(T - 1, std::integral_constant<int, 3>{}, std::integral_constant<int, K>{});
+        if (K + 1 == NS || t == T - 1) step(T - 1, std::integral_constant<int, 3>{}, std::integral_constant<int, K>{}, std::integral_constant<int, 0>{});
         else {
-            step(t, std::integral_constant<int, MODE>{}, std::integral_constant<int, K>{});
+            step(t, std::integral_constant<int, MODE>{}, std::integral_constant<int, K>{}, std::integral_constant<int, 0>{});
             if constexpr (K + 1 < NS) fwd_tail<K + 1, NS, MODE>(step, t + 1, T);
         }
     }
@@ -1555,7 +1559,8 @@ __device__ __forceinline__ void fwd_tail(StepF &step, int t, int T)
 
 // RXC: one r_x [nr][n] for every trajectory and step (see backward_fused_body): its transposed tile stays in registers, the
 // sweep issues no r_x loads (4 of a step's 15) and the four tile sets shrink by a tile each.
-template <int NCZ, int NCU, bool RU0 = false, bool UNI = false, bool RXC = false>
+// PAIR2 (with RXC, RU0, UNI; n_alpha <= 8, FusedLaunch::pair2): ONE scoring product per two steps, see P2 below.
+template <int NCZ, int NCU, bool RU0 = false, bool UNI = false, bool RXC = false, bool PAIR2 = false>
 __device__ __forceinline__ void forward_fused_body(RecLayout L, FusedArgs F, int T, int n_alpha, const double *__restrict__ Kin, const double *__restrict__ kin,
                const double *__restrict__ u_nom, const double *__restrict__ ctrl_lim,
                const double *__restrict__ alphas, double *__restrict__ cost_pred, double *__restrict__ U_alpha, const int btraj = KP_BLOCK_TRAJ)
@@ -1589,6 +1594,19 @@ __device__ __forceinline__ void forward_fused_body(RecLayout L, FusedArgs F, int
     const int cs = sig(c);                                                  // the residual in column c of the RxT operand
     const int oR2[2] = {(2 * q < nr) ? 16 * q : OOBF, (8 + 2 * q < nr) ? 64 + 16 * q : OOBF};
     (void)oR2;
+    // P2 (paired scoring): the r_x product sits off the state chain, its first operand is the same resident tile at every step and
+    // column c of its result depends on column c of Z alone -- and the candidates fill n_alpha <= 8 of the tile's 16 columns.  So the
+    // running steps pair up by register set, (0, 1) and (2, 3): the even member (step t) issues no scoring product and keeps its Z;
+    // the odd member (step t+1) moves columns 0..7 of Z_t into columns 8..15 of its own Z -- a masked row shift, two 32-bit moves
+    // per register, behind the last product of the state chain that reads the tile, so the chain never sees them -- and ONE product
+    // scores both: lanes c < 8 accumulate step t+1, lanes c >= 8 step t, folded behind the sweep.  r arrives once per pair, with the
+    // same two 16-byte requests: lanes c < 8 read the row above (a per-lane byte offset of one row).  The over-read of an odd
+    // residual count (see RV2 below) then reaches one element past row t+1: pairs end at step T-2, so it stays inside the T + 1 rows.
+    // The final step (terminal weights, its own tile) and a step T-2 left without a partner score themselves as before.
+    constexpr bool P2 = PAIR2 && RXC && RU0 && UNI;
+    static_assert(!P2 || (KP_FWD_SETS & 1) == 0, "paired scoring pairs the register sets");
+    const int oR2p[2] = {oR2[0] == OOBF ? OOBF : oR2[0] + (c < 8 ? nr * 8 : 0), oR2[1] == OOBF ? OOBF : oR2[1] + (c < 8 ? nr * 8 : 0)};
+    (void)oR2p;
 #pragma unroll
     for (int r = 0; r < 4; r++) {
         const int row = 4 * r + q;
@@ -1646,7 +1664,8 @@ __device__ __forceinline__ void forward_fused_body(RecLayout L, FusedArgs F, int
             s.RuT.x = fbld(rRu, oRuT[0]); s.RuT.y = NCU > 1 ? fbld(rRu, oRuT[1]) : 0.0;
             s.RuT.z = NCU > 2 ? fbld(rRu, oRuT[2]) : 0.0; s.RuT.w = NCU > 3 ? fbld(rRu, oRuT[3]) : 0.0;
         }
-        if constexpr (RV2) {
+        if constexpr (P2) {             // (r belongs to the pair: requested behind the tiles, below)
+        } else if constexpr (RV2) {
             // (descriptor one element longer: the last pair of an odd residual count reaches into the next step's row -- the array has
             // T + 1 rows, the weights beyond nr are zero)
             __amdgpu_buffer_rsrc_t rR2 = frsrc(rb + (size_t)t * nr, nr * 8 + 8);
@@ -1731,6 +1750,18 @@ __device__ __forceinline__ void forward_fused_body(RecLayout L, FusedArgs F, int
     (void)RxTc;
 #pragma unroll
     for (int k = 0; k < NS; k++) load_tiles(k < T ? k : T - 1, S[k]);
+    if constexpr (P2) {
+        // r of the pairs (k, k + 1), kept in the even set: rows k and k + 1 of the T + 1, one element more for the over-read of an
+        // odd residual count; a pair that does not exist at this horizon fetches the last one that could (never used)
+#pragma unroll
+        for (int k = 0; k < NS; k += 2) {
+            const int tk = k + 2 < T ? k : (T > 2 ? T - 2 : 0), rows = T + 1 - tk;
+            __amdgpu_buffer_rsrc_t rRp = frsrc(rb + (size_t)tk * nr, rows > 2 ? 2 * nr * 8 + 8 : rows * nr * 8);
+            double r0, r1, r2, r3;
+            fbld2s(rRp, oR2p[0], 0, r0, r1); fbld2s(rRp, oR2p[1], 0, r2, r3);
+            S[k].rv.x = r0; S[k].rv.y = r1; S[k].rv.z = r2; S[k].rv.w = r3;
+        }
+    }
 
     // One wavefront per workgroup: LDS accesses of the wave execute in order, so the write -> transposed read
     // pairs below need no barrier.  The Y operands of step t+1 are produced during step t (off the Z chain).
@@ -1802,9 +1833,14 @@ __device__ __forceinline__ void forward_fused_body(RecLayout L, FusedArgs F, int
     // join of paths that each issued it ends in register copies at the join, and a copy waits for the load (a form with the
     // crossing step peeled into straight-line code had `s_waitcnt vmcnt(0)` plus 16 moves at the end of every segment).
     // PAR: the parity of t (which register set the step works on)
-    auto step = [&](int t, auto mode_tag, auto par_tag) __attribute__((always_inline)) {
+    d4 Zev = zero, rvE = zero, rvF = zero;          // P2: Z of a pair's even member; r of the two steps that score themselves (T-2, T-1)
+    (void)Zev; (void)rvE; (void)rvF;
+    auto step = [&](int t, auto mode_tag, auto par_tag, auto role_tag) __attribute__((always_inline)) {
         constexpr int MODE = decltype(mode_tag)::value;
-        Tiles &cur = S[decltype(par_tag)::value];
+        constexpr int PAR = decltype(par_tag)::value;
+        constexpr int ROLE = P2 ? decltype(role_tag)::value : 0;      // (see fwd_steps)
+        static_assert(!P2 || (ROLE >= 1 && ROLE <= 3 && (MODE != 3 || ROLE == 3)), "a step of the paired form has a role");
+        Tiles &cur = S[PAR];
         const bool more = MODE == 3 ? false : MODE != 0 ? true : t + 1 < T;
         const int tn = MODE == 3 ? t : (t + NS < T ? t + NS : T - 1);       // (behind the last steps: a valid address, never used)
         const int sK = tn * m * n * 8, sk = tn * m * 8, sRx = tn * nr * n * 8, sRu = tn * nr * m * 8, sR = tn * nr * 8;
@@ -1850,7 +1886,26 @@ __device__ __forceinline__ void forward_fused_body(RecLayout L, FusedArgs F, int
         Zn = PS<NCU>(Yb, dU, Zn);                      // + B du: the next state
         d4 Ju = zero;                                  // RU0: r_u = 0, the control residual term vanishes
         if constexpr (!RU0) Ju = PS<NCU>(cur.RuT, dU, zero);
-        const d4 Jx = PS<ncx>(RXC ? ((SQW && MODE == 3) ? RxTt : RxTc) : cur.RxT, Z, zero);     // (SQW: sqrt(w) Jx; terminal weights at the final step)
+        d4 Jx = zero;
+        if constexpr (ROLE == 1) Zev = Z;                  // scored by the odd member
+        else {
+            if constexpr (ROLE == 2) {
+                // columns 8..15 of Z <- columns 0..7 of the even member's Z (row_shr:8 under bank mask 0xc: lanes 8..15 of every row of
+                // 16 take the value 8 lanes below, lanes 0..7 keep theirs).  Every product of the state chain that reads Z has been
+                // issued above; Z is replaced right below, so the chain never carries these columns.
+                auto put = [](double dst, double src) {
+                    const u32x2f d = __builtin_bit_cast(u32x2f, dst), s = __builtin_bit_cast(u32x2f, src);
+                    const u32x2f o = {(unsigned)__builtin_amdgcn_update_dpp((int)d.x, (int)s.x, 0x118, 0xf, 0xc, false),
+                                      (unsigned)__builtin_amdgcn_update_dpp((int)d.y, (int)s.y, 0x118, 0xf, 0xc, false)};
+                    return __builtin_bit_cast(double, o);
+                };
+                Z.x = put(Z.x, Zev.x);
+                if constexpr (ncx > 1) Z.y = put(Z.y, Zev.y);
+                if constexpr (ncx > 2) Z.z = put(Z.z, Zev.z);
+                if constexpr (ncx > 3) Z.w = put(Z.w, Zev.w);
+            }
+            Jx = PS<ncx>(RXC ? ((SQW && MODE == 3) ? RxTt : RxTc) : cur.RxT, Z, zero);     // (SQW: sqrt(w) Jx; terminal weights at the final step)
+        }
         Z = Zn;
         __builtin_amdgcn_sched_barrier(0);
         if constexpr (!RXC) { cur.RxT.x = fblds(rRx, oRxT[0], sRx); cur.RxT.y = fblds(rRx, oRxT[1], sRx); cur.RxT.z = fblds(rRx, oRxT[2], sRx); cur.RxT.w = fblds(rRx, oRxT[3], sRx); }
@@ -1906,6 +1961,28 @@ __device__ __forceinline__ void forward_fused_body(RecLayout L, FusedArgs F, int
 #pragma unroll
             for (int r = 0; r < 4; r++) wcur[r] = wterm[r];
         }
+        if constexpr (ROLE == 1) {                 // nothing to score, nothing to request: r belongs to the pair
+        } else if constexpr (ROLE == 3) {          // scores itself, signs on the spot; r came with the requests in front of the last group
+            if constexpr (MODE == 3)
+                partial += sgterm[0] * (Jx.x * __builtin_fma(s2term[0], rvF.x, Jx.x)) + sgterm[1] * (Jx.y * __builtin_fma(s2term[1], rvF.y, Jx.y))
+                         + sgterm[2] * (Jx.z * __builtin_fma(s2term[2], rvF.z, Jx.z)) + sgterm[3] * (Jx.w * __builtin_fma(s2term[3], rvF.w, Jx.w));
+            else
+                partial += sgrun[0] * (Jx.x * __builtin_fma(s2run[0], rvE.x, Jx.x)) + sgrun[1] * (Jx.y * __builtin_fma(s2run[1], rvE.y, Jx.y))
+                         + sgrun[2] * (Jx.z * __builtin_fma(s2run[2], rvE.z, Jx.z)) + sgrun[3] * (Jx.w * __builtin_fma(s2run[3], rvE.w, Jx.w));
+        } else if constexpr (ROLE == 2) {          // lanes c < 8: this step; lanes c >= 8: the even member, with the r of its own row
+            const d4 rp = S[PAR & ~1].rv;
+            acc4[0] = __builtin_fma(Jx.x, __builtin_fma(s2run[0], rp.x, Jx.x), acc4[0]);
+            acc4[1] = __builtin_fma(Jx.y, __builtin_fma(s2run[1], rp.y, Jx.y), acc4[1]);
+            acc4[2] = __builtin_fma(Jx.z, __builtin_fma(s2run[2], rp.z, Jx.z), acc4[2]);
+            acc4[3] = __builtin_fma(Jx.w, __builtin_fma(s2run[3], rp.w, Jx.w), acc4[3]);
+            __builtin_amdgcn_sched_barrier(0);
+            // the pair NS steps on: rows t - 1 + NS and t + NS (behind the last pair: rows T-2, T-1, never used)
+            const int sRp = (t + NS < T ? t - 1 + NS : T - 2) * nr * 8;
+            double r0, r1, r2, r3;
+            fbld2s(rR, oR2p[0], sRp, r0, r1); fbld2s(rR, oR2p[1], sRp, r2, r3);
+            S[PAR & ~1].rv.x = r0; S[PAR & ~1].rv.y = r1; S[PAR & ~1].rv.z = r2; S[PAR & ~1].rv.w = r3;
+            __builtin_amdgcn_sched_barrier(0);
+        } else {
         const d4 r2 = cur.rv + cur.rv;
         if constexpr (SQW) {
             if constexpr (MODE == 3) {         // the final step: terminal weights, their signs applied on the spot
@@ -1934,6 +2011,7 @@ __device__ __forceinline__ void forward_fused_body(RecLayout L, FusedArgs F, int
         cur.rv.x = fblds(rR, oR[0], sR); cur.rv.y = fblds(rR, oR[1], sR); cur.rv.z = fblds(rR, oR[2], sR); cur.rv.w = fblds(rR, oR[3], sR);
         }
         __builtin_amdgcn_sched_barrier(0);
+        }
     };
     if constexpr (UNI) {
         // Segments from the bottom: segment p = steps k_p .. k_p+1 - 1; the last key-point T-1 is a segment of its own (the
@@ -1957,13 +2035,46 @@ __device__ __forceinline__ void forward_fused_body(RecLayout L, FusedArgs F, int
             }
         }
         int t = 0;
-        for (; t + NS < T; t += NS) fwd_steps<0, NS, 1>(step, t);         // (the crossing inside a step moves up, uks, uke on)
+        for (; t + NS < T; t += NS) fwd_steps<0, NS, 1, P2>(step, t);     // (the crossing inside a step moves up, uks, uke on)
+        if constexpr (P2) {
+            // What is left, 1..NS steps: pairs while two running steps remain, then step T-2 by itself if it has no partner, then the
+            // final step.  The r of those two is requested here, in front of every branch, in all lanes.  Each step runs on the set
+            // its tiles were requested into (set = steps past t), as (step: MODE, set, role):
+            //   left = 1:                                                                T-1: 3, 0, 3
+            //   left = 2:  t: 1, 0, 3 (T-2, no partner)                                  T-1: 3, 1, 3
+            //   left = 3:  t: 1, 0, 1   t+1: 1, 1, 2 (T-2)                               T-1: 3, 2, 3
+            //   left = 4:  t: 1, 0, 1   t+1: 1, 1, 2   t+2: 1, 2, 3 (T-2, no partner)    T-1: 3, 3, 3
+            {
+                const int sE = (T > 1 ? T - 2 : 0) * nr * 8, sF = (T - 1) * nr * 8;
+                double r0, r1, r2, r3;
+                fbld2s(rR, oR2[0], sE, r0, r1); fbld2s(rR, oR2[1], sE, r2, r3);
+                rvE.x = r0; rvE.y = r1; rvE.z = r2; rvE.w = r3;
+                fbld2s(rR, oR2[0], sF, r0, r1); fbld2s(rR, oR2[1], sF, r2, r3);
+                rvF.x = r0; rvF.y = r1; rvF.z = r2; rvF.w = r3;
+            }
+            using I0 = std::integral_constant<int, 0>; using I1 = std::integral_constant<int, 1>;
+            using I2 = std::integral_constant<int, 2>; using I3 = std::integral_constant<int, 3>;
+            static_assert(NS == 4, "the remainder below is written for four register sets");
+            const int left = T - t;
+            if (left >= 3) {
+                step(t, I1{}, I0{}, I1{});
+                step(t + 1, I1{}, I1{}, I2{});
+                if (left == 4) { step(t + 2, I1{}, I2{}, I3{}); step(T - 1, I3{}, I3{}, I3{}); }
+                else step(T - 1, I3{}, I2{}, I3{});
+            } else if (left == 2) { step(t, I1{}, I0{}, I3{}); step(T - 1, I3{}, I1{}, I3{}); }
+            else step(T - 1, I3{}, I0{}, I3{});
+        } else
         fwd_tail<0, NS, 1>(step, t, T);
     } else {
         int t = 0;
         for (; t + NS <= T; t += NS) fwd_steps<0, NS, 0>(step, t);
         fwd_tail<0, NS, 0>(step, t, T);
     }
+    if constexpr (P2) {                // the even members sit in lanes c >= 8 of the pair sums (and of nothing else)
+        double pairs = sgrun[0] * acc4[0] + sgrun[1] * acc4[1] + sgrun[2] * acc4[2] + sgrun[3] * acc4[3];
+        pairs += __shfl_xor(pairs, 8);
+        partial += pairs;
+    } else
     if constexpr (SQW) partial += sgrun[0] * acc4[0] + sgrun[1] * acc4[1] + sgrun[2] * acc4[2] + sgrun[3] * acc4[3];
     partial += __shfl_xor(partial, 16);
     partial += __shfl_xor(partial, 32);
@@ -1973,7 +2084,7 @@ __device__ __forceinline__ void forward_fused_body(RecLayout L, FusedArgs F, int
 // The one-wave forward sweep comes in two forms, launched back to back: UNI for key-point sets in which every DoF of a
 // trajectory has the same list (the device flag of k_kp_uniform says so), the general form otherwise.  Each looks at the
 // flag first and leaves if the set is not its kind, so the host never has to know.
-template <int NCZ, int NCU, bool RU0, bool UNI, bool RXC = false>
+template <int NCZ, int NCU, bool RU0, bool UNI, bool RXC = false, bool PAIR2 = false>
 __global__ void __launch_bounds__(64)
 k_forward_fused(RecLayout L, FusedArgs F, int T, int n_alpha, const double *__restrict__ Kin,
                 const double *__restrict__ kin, const double *__restrict__ u_nom, const double *__restrict__ ctrl_lim,
@@ -1981,9 +2092,9 @@ k_forward_fused(RecLayout L, FusedArgs F, int T, int n_alpha, const double *__re
                 const int *__restrict__ kp_uniform)
 {
     if ((*kp_uniform != 0) != UNI) return;
-    forward_fused_body<NCZ, NCU, RU0, UNI, RXC>(L, F, T, n_alpha, Kin, kin, u_nom, ctrl_lim, alphas, cost_pred, U_alpha);
+    forward_fused_body<NCZ, NCU, RU0, UNI, RXC, PAIR2>(L, F, T, n_alpha, Kin, kin, u_nom, ctrl_lim, alphas, cost_pred, U_alpha);
 }
-template <int NCZ, int NCU, bool RU0, bool UNI, bool RXC = false>
+template <int NCZ, int NCU, bool RU0, bool UNI, bool RXC = false, bool PAIR2 = false>
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1)))
 k_forward_fused_excl(RecLayout L, FusedArgs F, int T, int n_alpha, const double *__restrict__ Kin,
                      const double *__restrict__ kin, const double *__restrict__ u_nom, const double *__restrict__ ctrl_lim,
@@ -1991,12 +2102,12 @@ k_forward_fused_excl(RecLayout L, FusedArgs F, int T, int n_alpha, const double 
                      const int *__restrict__ kp_uniform)
 {
     if ((*kp_uniform != 0) != UNI) return;
-    forward_fused_body<NCZ, NCU, RU0, UNI, RXC>(L, F, T, n_alpha, Kin, kin, u_nom, ctrl_lim, alphas, cost_pred, U_alpha);
+    forward_fused_body<NCZ, NCU, RU0, UNI, RXC, PAIR2>(L, F, T, n_alpha, Kin, kin, u_nom, ctrl_lim, alphas, cost_pred, U_alpha);
 }
 // The listed twins of the two (kpilqr_forward_linear_partial): block i sweeps trajectory list[i] -- a scalar load off a kernel
 // argument, so the index the per-trajectory descriptors are built from stays wave-uniform.  The same body; the two kernels above
 // are the launches of every whole-batch call, unchanged.
-template <int NCZ, int NCU, bool RU0, bool UNI, bool RXC = false>
+template <int NCZ, int NCU, bool RU0, bool UNI, bool RXC = false, bool PAIR2 = false>
 __global__ void __launch_bounds__(64)
 k_forward_fused_listed(RecLayout L, FusedArgs F, int T, int n_alpha, const double *__restrict__ Kin,
                        const double *__restrict__ kin, const double *__restrict__ u_nom, const double *__restrict__ ctrl_lim,
@@ -2004,9 +2115,9 @@ k_forward_fused_listed(RecLayout L, FusedArgs F, int T, int n_alpha, const doubl
                        const int *__restrict__ kp_uniform, const int *__restrict__ list)
 {
     if ((*kp_uniform != 0) != UNI) return;
-    forward_fused_body<NCZ, NCU, RU0, UNI, RXC>(L, F, T, n_alpha, Kin, kin, u_nom, ctrl_lim, alphas, cost_pred, U_alpha, list[blockIdx.x]);
+    forward_fused_body<NCZ, NCU, RU0, UNI, RXC, PAIR2>(L, F, T, n_alpha, Kin, kin, u_nom, ctrl_lim, alphas, cost_pred, U_alpha, list[blockIdx.x]);
 }
-template <int NCZ, int NCU, bool RU0, bool UNI, bool RXC = false>
+template <int NCZ, int NCU, bool RU0, bool UNI, bool RXC = false, bool PAIR2 = false>
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1)))
 k_forward_fused_excl_listed(RecLayout L, FusedArgs F, int T, int n_alpha, const double *__restrict__ Kin,
                             const double *__restrict__ kin, const double *__restrict__ u_nom, const double *__restrict__ ctrl_lim,
@@ -2014,7 +2125,7 @@ k_forward_fused_excl_listed(RecLayout L, FusedArgs F, int T, int n_alpha, const 
                             const int *__restrict__ kp_uniform, const int *__restrict__ list)
 {
     if ((*kp_uniform != 0) != UNI) return;
-    forward_fused_body<NCZ, NCU, RU0, UNI, RXC>(L, F, T, n_alpha, Kin, kin, u_nom, ctrl_lim, alphas, cost_pred, U_alpha, list[blockIdx.x]);
+    forward_fused_body<NCZ, NCU, RU0, UNI, RXC, PAIR2>(L, F, T, n_alpha, Kin, kin, u_nom, ctrl_lim, alphas, cost_pred, U_alpha, list[blockIdx.x]);
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -2477,6 +2588,9 @@ FusedLaunch plan_forward_fused(const Ctx *c)
     p.rxc = c->ru_zero && c->rx_const_on;       // (every form's cost wave has its constant-Jacobian instantiation, with r_u = 0 only)
     p.slopes = p.waves_ragged == Waves::w1 && c->kps != nullptr;
     p.excl = c->d.batch <= c->n_simd;
+    // the uniform one-wave form with the constant Jacobian scores two steps per r_x product while the candidates fill at most half
+    // of the tile's columns (forward_fused_body, P2)
+    p.pair2 = p.waves == Waves::w1 && p.rxc && c->d.n_alpha <= 8;
     return p;
 }
 
@@ -2638,6 +2752,14 @@ static void launch_ff_triple(Ctx *c, const FusedLaunch &p, const FusedArgs &F, d
 template <int NCZ, int NCU, bool RU, bool UNI>
 static void launch_ff_form(Ctx *c, const FusedLaunch &p, const FusedArgs &F, double *U_alpha_dev)
 {
+    // paired scoring (FusedLaunch::pair2): the uniform constant-Jacobian form with ONE scoring product per two steps
+    if constexpr (RU && UNI) {
+        if (p.rxc && p.pair2) {
+            if (c->sweep_list) launch_ff_kernel(p.excl ? k_forward_fused_excl_listed<NCZ, NCU, true, true, true, true> : k_forward_fused_listed<NCZ, NCU, true, true, true, true>, 64, c, F, U_alpha_dev, c->sweep_list);
+            else launch_ff_kernel(p.excl ? k_forward_fused_excl<NCZ, NCU, true, true, true, true> : k_forward_fused<NCZ, NCU, true, true, true, true>, 64, c, F, U_alpha_dev);
+            return;
+        }
+    }
     if (c->sweep_list) {
         if (RU && p.rxc) launch_ff_kernel(p.excl ? k_forward_fused_excl_listed<NCZ, NCU, RU, UNI, RU> : k_forward_fused_listed<NCZ, NCU, RU, UNI, RU>, 64, c, F, U_alpha_dev, c->sweep_list);
         else launch_ff_kernel(p.excl ? k_forward_fused_excl_listed<NCZ, NCU, RU, UNI, false> : k_forward_fused_listed<NCZ, NCU, RU, UNI, false>, 64, c, F, U_alpha_dev, c->sweep_list);

@@ -1808,6 +1808,7 @@ static int run_forward(kpilqr_ctx *c, double *U_dev)
             c->last_fwd = plan;
             if (!plan.rxc) { rc = ensure_rx_buffer(c); if (rc) return rc; }
             KP_HIP(c, launch_forward_fused(&v, plan, U_dev));
+            c->last_fwd.fwd_ran = true;
             return KPILQR_OK;
         }
         rc = ensure_kpc(c);
@@ -1820,6 +1821,7 @@ static int run_forward(kpilqr_ctx *c, double *U_dev)
         if (!c->pay.kpc_valid && !c->pay.kpc_touched) { rc = difference_to_kpc(c); if (rc) return rc; }
         if (c->pay.kpc_valid) { rc = slopes_for_kpc(c); if (rc) return rc; }       // (behind a raw backward sweep: its launch sequence made them)
         KP_HIP(c, launch_forward_fused(c, plan, U_dev));
+        c->last_fwd.fwd_ran = true;
         return KPILQR_OK;
     }
     c->last_fwd = FusedLaunch{};
@@ -1830,6 +1832,7 @@ static int run_forward(kpilqr_ctx *c, double *U_dev)
     case Family::wide: KP_HIP(c, launch_forward_wide(c, U_dev)); break;
     default: KP_HIP(c, launch_forward_generic(c, U_dev)); break;
     }
+    c->last_fwd.fwd_ran = true;
     return KPILQR_OK;
 }
 
@@ -1961,6 +1964,7 @@ static int run_forward_listed(kpilqr_ctx *c, int count, double *U_dev)
         if (!plan.rxc) { rc = ensure_rx_buffer(c); if (rc) return rc; make_list_view(c, count, &v); }
         c->last_width[1] = count;
         KP_HIP(c, launch_forward_fused(&v, plan, U_dev));
+        c->last_fwd.fwd_ran = true;
         return KPILQR_OK;
     }
     c->last_fwd = FusedLaunch{};
@@ -1973,6 +1977,7 @@ static int run_forward_listed(kpilqr_ctx *c, int count, double *U_dev)
     case Family::wide: KP_HIP(c, launch_forward_wide(&v, U_dev)); break;
     default: KP_HIP(c, launch_forward_generic(&v, U_dev)); break;
     }
+    c->last_fwd.fwd_ran = true;
     return KPILQR_OK;
 }
 
@@ -2900,9 +2905,24 @@ const char *kpilqr_forward_variant(kpilqr_ctx *c) { return c ? variant_name(c->f
 //   kp_union (fused context, sweeps on the union store)
 // ":subset" comes last where the launch was a listed one (kpilqr_backward_partial, kpilqr_forward_linear_partial, kpilqr_iterate_partial):
 // the tokens before it are the form the list's length chose.
+// which = 3: how the last forward launch scored its steps: "pair2" one r_x product per two steps (the uniform one-wave form with the
+// constant Jacobian and n_alpha <= 8: FusedLaunch::pair2; uniform lists are the device's word, so this waits like which = 1) |
+// "step" every step its own, i.e. every other launch; "" while the last forward call has launched nothing (none yet, or it was refused
+// before its launch: FusedLaunch::fwd_ran, which travels with last_fwd -- a streamed iteration's chunk views hand it back with the plan);
+// "?" where the flag cannot be read back (which = 1 then ends in ":?").
 const char *kpilqr_last_launch(kpilqr_ctx *c, int which)
 {
     if (c && which == 2) return c->last_linearise;
+    if (c && which == 3) {
+        const FusedLaunch &p = c->last_fwd;
+        if (!p.fwd_ran) return "";
+        if (!p.pair2) return "step";
+        int uni = 0;
+        if (hipSetDevice(c->d.device) != hipSuccess || (c->pipe_dirty && join_pipeline(c) != KPILQR_OK) ||
+            hipMemcpyAsync(&uni, p.uni_on_union ? c->kpu_uniform : c->kp_uniform, sizeof(int), hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+            hipStreamSynchronize(c->stream) != hipSuccess) return "?";
+        return uni ? "pair2" : "step";
+    }
     if (!c || which < 0 || which > 1) return "";
     std::string &out = c->launch_desc[which];
     const FusedLaunch &p = which == 0 ? c->last_bwd : c->last_fwd;

@@ -119,8 +119,9 @@ class Engine:
     def last_launch(self, which="backward"):
         """kpilqr_last_launch: the form the last backward / forward launch actually took, e.g.
         'mfma_f64_t1_fused:w1:raw:uni:ru0' (waits for the stream); which="linearise": the differencing + interpolation stage of
-        the last fd_interpolate / iterate / iterate_streamed, e.g. 'fd_kp_interpolate'."""
-        return self._L.kpilqr_last_launch(self._h, {"backward": 0, "linearise": 2}.get(which, 1)).decode()
+        the last fd_interpolate / iterate / iterate_streamed, e.g. 'fd_kp_interpolate'; which="forward_scoring": 'pair2' (one
+        residual-Jacobian product per two steps) or 'step' for the last forward launch, '' before any."""
+        return self._L.kpilqr_last_launch(self._h, {"backward": 0, "linearise": 2, "forward_scoring": 3}.get(which, 1)).decode()
 
     def device_array(self, which, shape, typestr="<f8"):
         p, sz = C.c_void_p(), C.c_size_t()
