@@ -206,7 +206,7 @@ def _full_batch_parity(*argv):
 
 def test_headline_dispatch_one_wave_raw_uniform_at_batch_1024():
     """The bench's kernels at the size where they are the library's DEFAULT (round-3 verdict, Weak 2): 1024 distinct seeds,
-    key-point ordered payload, default environment -> `k_backward_fused_excl<14,7,RU0,RAW,UNI>` ("...:w1:raw:uni:ru0", read back
+    key-point ordered payload, default environment -> `k_backward_fused<14,7,RU0,RAW,UNI,RXC,EXCL>` ("...:w1:raw:uni:ru0", read back
     through kpilqr_last_launch and asserted by the tool), 64 trajectories spread over the batch against the oracle at 1e-9
     (iLQR.cpp:535-634 with the differencing of Differentiator.cpp:166-222,441-457 inside), and ALL 1024 trajectories' K, k,
     delta_J, costs bit-identical with the `KPILQR_FUSED_RAW=0` leg (differencing kernel + plain sweep) and within 1e-12 of the

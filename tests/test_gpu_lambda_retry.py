@@ -1,4 +1,4 @@
-"""GPU tests of the lambda retry schedule (kpilqr_set_lambda_retry, csrc/lambda_retry.hip and the _retry twins of every backward
+"""GPU tests of the lambda retry schedule (kpilqr_set_lambda_retry, csrc/lambda_retry.hip and the GATED twins of every backward
 kernel): a backward pass whose PD check fails is swept again at lambda * factor on the device, per trajectory, until it settles, the
 schedule gives up, or the attempts run out.
 

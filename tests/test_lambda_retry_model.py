@@ -136,22 +136,36 @@ def test_header_documents_the_contract():
         assert word in doc, word
 
 
-def test_built_library_holds_a_gated_twin_of_every_backward_kernel():
-    """The device code of libkpilqr.so has, for every backward kernel instantiation that a backward pass launches, its lambda retry
-    twin (a k_backward_*_retry kernel, or the GATED = true instantiation of a tiled kernel): as many twins as kernels, family by family."""
+def _sweep_instantiations(direction, suffix):
+    """The k_<direction>_* kernels in the device code of libkpilqr.so, split by their LAST template argument -- GATED of every backward
+    kernel, LISTED of every forward one -- into two sets of (name, all other arguments, EXCL among them).
+    generic.hip's kernels are no templates and keep the name suffix: k_backward_generic_retry is k_backward_generic<true> here."""
     out = subprocess.run(["strings", "-n", "12", _lib.LIB_PATH], capture_output=True, text=True, check=True).stdout
-    syms = set(re.findall(r"_ZN6kpilqr\d+k_backward_\w+", out))
+    syms = set(re.findall(r"_ZN6kpilqr\d+k_%s_\w+" % direction, out))
     names = subprocess.run(["c++filt"], input="\n".join(sorted(syms)), capture_output=True, text=True, check=True).stdout.split("\n")
-    kernels = {re.sub(r"^void ", "", n.split("(")[0]) for n in names if "k_backward_" in n and "_stats" not in n}
-    assert len(kernels) > 100, len(kernels)
-    plain, twins = set(), set()
+    kernels = {re.sub(r"^void ", "", n.split("(")[0]) for n in names if "k_%s_" % direction in n and "_stats" not in n}
+    off, on = set(), set()
     for k in kernels:
         base, args = k.split("<", 1) if "<" in k else (k, ">")
         args = [a.strip() for a in args.rstrip(">").split(",")] if args != ">" else []
-        if base.startswith("kpilqr::k_backward_tiled_"):
-            (twins if args[-1] == "true" else plain).add((base, tuple(args[:-1])))
-        elif base.endswith("_retry"):
-            twins.add((base[:-len("_retry")], tuple(args)))
-        else:
-            plain.add((base, tuple(a for a in args if not (base.startswith("kpilqr::k_backward_mfma") and len(args) == 3 and a is args[2]))))
+        if not args:
+            assert "_generic" in base, k
+            base, args = re.sub(suffix + "$", "", base), ["true" if base.endswith(suffix) else "false"]
+        assert args[-1] in ("true", "false"), k
+        (on if args[-1] == "true" else off).add((base, tuple(args[:-1])))
+    return kernels, off, on
+
+
+def test_built_library_holds_a_gated_twin_of_every_backward_kernel():
+    """The device code of libkpilqr.so has, for every backward kernel instantiation that a backward pass launches, its lambda retry
+    twin (the GATED = true instantiation of the same kernel, every other argument equal): as many twins as kernels, family by family."""
+    kernels, plain, twins = _sweep_instantiations("backward", "_retry")
+    assert len(kernels) > 100, len(kernels)
     assert plain == twins, (sorted(plain - twins)[:5], sorted(twins - plain)[:5])
+
+
+def test_built_library_holds_a_listed_twin_of_every_forward_kernel():
+    """... and for every forward kernel instantiation its LISTED = true partner (kpilqr_forward_linear_partial), and the other way round."""
+    kernels, whole, listed = _sweep_instantiations("forward", "_listed")
+    assert len(kernels) > 100, len(kernels)
+    assert whole == listed, (sorted(whole - listed)[:5], sorted(listed - whole)[:5])

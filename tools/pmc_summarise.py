@@ -23,10 +23,10 @@ KEYS = {"k_backward_fused": "backward_fused", "k_forward_fused": "forward_fused"
 def key_of(name):
     # the one-wave forward sweep is launched in two forms (uniform key-point sets / general), one of which returns at
     # once: only the uniform form runs the bench workload (set_interval key-points)
-    if re.search(r"k_forward_fused(_excl)?<\d+, \d+, (true|false), false(, (true|false))*>", name):      # (<NCZ, NCU, RU0, UNI[, RXC[, PAIR2]]>)
+    if re.search(r"k_forward_fused<\d+, \d+, (true|false), false(, (true|false)){4}>", name):      # (<NCZ, NCU, RU0, UNI, RXC, PAIR2, EXCL, LISTED>)
         return None
-    # the same for the one-wave backward sweep since round 3 (<N, M, RU0, RAW, UNI[, RXC]>: UNI = false leaves at once here)
-    if re.search(r"k_backward_fused(_excl)?<\d+, \d+, (true|false), (true|false), false(, (true|false))?>", name):
+    # the same for the one-wave backward sweep since round 3 (<N, M, RU0, RAW, UNI, RXC, EXCL, GATED>: UNI = false leaves at once here)
+    if re.search(r"k_backward_fused<\d+, \d+, (true|false), (true|false), false(, (true|false)){3}>", name):
         return None
     for k, v in KEYS.items():
         if k in name:

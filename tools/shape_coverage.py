@@ -15,13 +15,17 @@ UNITS = [("riccati_mfma.hip", MFMAF), ("forward_mfma.hip", MFMAF), ("tiled_mfma.
          ("generic.hip", ["-ffp-contract=off"])] + [("fused_mfma.hip", MFMAF + [f"-DKP_FUSED_PART={i}"]) for i in (1, 2, 3)]
 
 # (pattern on the demangled name, reason it is not dispatched by tests/test_gpu_shapes.py)
+# The trailing template flags of the sweep kernels are ..., EXCL, GATED backward and ..., EXCL, LISTED forward (the
+# pair, triple and tiled kernels have no EXCL; generic.hip keeps the name suffixes _retry / _listed).  First match wins.
 REASONS = [
-    (r"k_backward_\w+_retry\b|k_backward_tiled_(col|uw|wide)<.*, true>$", "lambda retry twin (kpilqr_set_lambda_retry): runs the attempts behind the first of a "
-                                                                       "backward pass under a schedule; tests/test_gpu_lambda_retry.py dispatches one per family"),
+    (r"k_backward_\w+<.*, true>$|k_backward_generic_retry\b", "GATED instantiation, the lambda retry twin (kpilqr_set_lambda_retry): runs the attempts behind the "
+                                                             "first of a backward pass under a schedule; tests/test_gpu_lambda_retry.py dispatches one per family"),
+    (r"k_forward_\w+<.*, true>$|k_forward_generic_listed\b", "LISTED instantiation (kpilqr_forward_linear_partial): sweeps a listed subset of the batch; "
+                                                            "tests/test_gpu_partial_sweeps.py dispatches one per family"),
     (r"k_backward_fused_stats<", "diagnostic entry point only (kpilqr_backward_stats, the refresh histogram)"),
-    (r"k_(backward|forward)_fused<", "plain form (batch > n_simd) in a residual / payload mode other than the headline's (constant r_x, "
-                                     "key-point ordered payload): test_batch_boundaries runs the plain form in that mode only"),
-    (r"k_(backward_fused_excl|backward_fusedph|forward_fused_excl|forward_fused_sc3|forward_fused_scu)<",
+    (r"k_(backward|forward)_fused<.*, false, false>$", "plain form (EXCL = false: batch > n_simd) in a residual / payload mode other than the headline's (constant r_x, "
+                                                       "key-point ordered payload): test_batch_boundaries runs the plain form in that mode only"),
+    (r"k_(backward_fused|backward_fusedph|forward_fused|forward_fused_sc3|forward_fused_scu)<",
      "a residual / payload mode of the fused sweeps (template flags RU / RW / UN / RX / SL), not a shape: the shape cases run "
      "dense r_u or a constant r_x, never r_u = 0 with per-step r_x"),
 ]

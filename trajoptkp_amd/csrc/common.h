@@ -6,6 +6,7 @@
 #include <stddef.h>
 #include <stdint.h>
 #include <string>
+#include <type_traits>
 
 #include "../../include/kpilqr.h"
 
@@ -50,7 +51,7 @@ struct FusedLaunch {
     bool ru0 = false;                   // r_u = 0: the instantiations without the r_u loads and the Ju product
     bool rxc = false;                   // constant r_x kept in registers (ru0 instantiations only): nobody reads the r_x buffer
     bool slopes = false;                // the general (per-DoF list) form walks the slope store
-    bool excl = false;                  // w1: every wave has a SIMD to itself (the _excl twins)
+    bool excl = false;                  // w1: every wave has a SIMD to itself (EXCL instantiations)
     bool pair2 = false;                 // forward, w1 on uniform lists with rxc: one scoring product per two steps (n_alpha <= 8)
     bool fwd_ran = false;               // last_fwd only: the forward call that left this record launched its sweep (set behind the launch,
                                         // also on the empty record of a launch that is not fused); kpilqr_last_launch(ctx, 3) is "" without it
@@ -296,8 +297,8 @@ struct Ctx {
 
     // The lambda retry schedule (kpilqr_set_lambda_retry; kept by kpilqr_resize).  retry_attempts: the attempts the backward pass about
     // to run launches, set by the entry point from the lambdas its caller passed.  bwd_gate: what the backward launchers look at -- nullptr
-    // (the kernels of a context without a schedule) on the first attempt, `gate` on the attempts behind k_lambda_retry, which
-    // launch the kernels' _retry twins.
+    // (GATED = false: the kernels of a context without a schedule) on the first attempt, `gate` on the attempts behind k_lambda_retry,
+    // which launch the kernels' GATED instantiations.
     kpilqr_lambda_retry retry{};
     bool retry_on = false;
     bool retry_ran = false;       // a backward pass has run under the schedule since it was set: attempts holds its counts
@@ -306,7 +307,7 @@ struct Ctx {
     // A listed launch (kpilqr_backward_partial / kpilqr_forward_linear_partial): the device copy of the list (traj_list) in a copy of
     // the context whose d.batch is the list's length -- the launch width, by which the launchers choose their forms -- and whose
     // per-trajectory pointers stay the context's: block i sweeps trajectory sweep_list[i].  nullptr: every block sweeps its own index.
-    // The backward launchers run a listed launch through the retry twins, so it always comes with bwd_gate.
+    // The backward launchers run a listed launch through the GATED instantiations, so it always comes with bwd_gate.
     const int *sweep_list = nullptr;
 
     Family bwd_family = Family::generic, fwd_family = Family::generic;
@@ -338,6 +339,16 @@ Ctx::Tuning read_tuning_from_env();
 // The trajectory a block of a sweep works on: its own index, but in a listed launch (Ctx::sweep_list) entry blockIdx.x of the list --
 // a scalar load off a kernel argument indexed by the block, so the index stays wave-uniform for the descriptors built from it.
 __device__ __forceinline__ int kp_block_traj(const int *__restrict__ list, int own) { return list ? list[blockIdx.x] : own; }
+
+// The sweep kernels' trailing template flags (backward `..., bool EXCL, bool GATED`, forward `..., bool EXCL,
+// bool LISTED`) from the two runtime conditions that decide them: f is a generic lambda that names its instantiation with the two
+// std::bool_constant it is given and launches it -- one launch, one argument list, whatever the flags.
+template <class F>
+inline auto kp_with_flags(bool first, bool second, F &&f)
+{
+    if (first) return second ? f(std::true_type{}, std::true_type{}) : f(std::true_type{}, std::false_type{});
+    return second ? f(std::false_type{}, std::true_type{}) : f(std::false_type{}, std::false_type{});
+}
 
 #define KP_HIP(ctx, call)                                                        \
     do {                                                                         \

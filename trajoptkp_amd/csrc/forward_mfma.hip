@@ -163,43 +163,18 @@ __device__ __forceinline__ void forward_body(RecLayout L, int T, int n_alpha, co
     if (q == 0 && c < n_alpha) cost_pred[(size_t)b * n_alpha + c] = partial;
 }
 
-// Shared / exclusive-SIMD entry points (see riccati_mfma.hip: one wave per SIMD when the batch fits).
-template <int NCZ, int NCU>
-__global__ void __launch_bounds__(64)
+// One entry point, shared or exclusive-SIMD (EXCL, see riccati_mfma.hip: one wave per SIMD when the batch fits).  LISTED
+// (kpilqr_forward_linear_partial): block i sweeps trajectory list[i] -- a scalar load off a kernel argument, so the index the
+// per-step descriptors are built from stays wave-uniform.  LISTED = false, the launch of every whole-batch call, never reads `list`.
+template <int NCZ, int NCU, bool EXCL, bool LISTED>
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, EXCL ? 1 : 0)))
 k_forward_mfma(RecLayout L, int T, int n_alpha, const double *__restrict__ rec, const double *__restrict__ Kin,
                const double *__restrict__ kin, const double *__restrict__ u_nom, const double *__restrict__ ctrl_lim,
-               const double *__restrict__ alphas, double *__restrict__ cost_pred, double *__restrict__ U_alpha)
+               const double *__restrict__ alphas, double *__restrict__ cost_pred, double *__restrict__ U_alpha,
+               const int *__restrict__ list)
 {
-    forward_body<NCZ, NCU>(L, T, n_alpha, rec, Kin, kin, u_nom, ctrl_lim, alphas, cost_pred, U_alpha);
-}
-template <int NCZ, int NCU>
-__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1)))
-k_forward_mfma_excl(RecLayout L, int T, int n_alpha, const double *__restrict__ rec, const double *__restrict__ Kin,
-                    const double *__restrict__ kin, const double *__restrict__ u_nom, const double *__restrict__ ctrl_lim,
-                    const double *__restrict__ alphas, double *__restrict__ cost_pred, double *__restrict__ U_alpha)
-{
-    forward_body<NCZ, NCU>(L, T, n_alpha, rec, Kin, kin, u_nom, ctrl_lim, alphas, cost_pred, U_alpha);
-}
-// The listed twins of the two (kpilqr_forward_linear_partial): block i sweeps trajectory list[i] -- a scalar load off a kernel
-// argument, so the index the per-step descriptors are built from stays wave-uniform.  The same body; the two kernels above are the
-// launches of every whole-batch call, unchanged.
-template <int NCZ, int NCU>
-__global__ void __launch_bounds__(64)
-k_forward_mfma_listed(RecLayout L, int T, int n_alpha, const double *__restrict__ rec, const double *__restrict__ Kin,
-                      const double *__restrict__ kin, const double *__restrict__ u_nom, const double *__restrict__ ctrl_lim,
-                      const double *__restrict__ alphas, double *__restrict__ cost_pred, double *__restrict__ U_alpha,
-                      const int *__restrict__ list)
-{
-    forward_body<NCZ, NCU>(L, T, n_alpha, rec, Kin, kin, u_nom, ctrl_lim, alphas, cost_pred, U_alpha, list[blockIdx.x]);
-}
-template <int NCZ, int NCU>
-__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1)))
-k_forward_mfma_excl_listed(RecLayout L, int T, int n_alpha, const double *__restrict__ rec, const double *__restrict__ Kin,
-                           const double *__restrict__ kin, const double *__restrict__ u_nom, const double *__restrict__ ctrl_lim,
-                           const double *__restrict__ alphas, double *__restrict__ cost_pred, double *__restrict__ U_alpha,
-                           const int *__restrict__ list)
-{
-    forward_body<NCZ, NCU>(L, T, n_alpha, rec, Kin, kin, u_nom, ctrl_lim, alphas, cost_pred, U_alpha, list[blockIdx.x]);
+    const int b = LISTED ? list[blockIdx.x] : (int)blockIdx.x;
+    forward_body<NCZ, NCU>(L, T, n_alpha, rec, Kin, kin, u_nom, ctrl_lim, alphas, cost_pred, U_alpha, b);
 }
 
 bool forward_mfma_supported(int n, int m, int n_alpha)
@@ -211,16 +186,11 @@ bool forward_mfma_supported(int n, int m, int n_alpha)
 template <int NCZ, int NCU>
 static hipError_t launch_fm(Ctx *c, double *U_alpha_dev)
 {
-    if (c->sweep_list) {
-        const auto twin = c->d.batch <= c->n_simd ? k_forward_mfma_excl_listed<NCZ, NCU> : k_forward_mfma_listed<NCZ, NCU>;
-        hipLaunchKernelGGL(twin, dim3(c->d.batch), dim3(64), 0, c->stream, c->L, c->d.T, c->d.n_alpha, c->rec, c->K, c->k, c->u_nom,
-                           c->ctrl_lim, c->alphas, c->cost_pred, U_alpha_dev, c->sweep_list);
+    return kp_with_flags(c->d.batch <= c->n_simd, c->sweep_list != nullptr, [&](auto excl, auto listed) {
+        hipLaunchKernelGGL((k_forward_mfma<NCZ, NCU, excl(), listed()>), dim3(c->d.batch), dim3(64), 0, c->stream, c->L, c->d.T,
+                           c->d.n_alpha, c->rec, c->K, c->k, c->u_nom, c->ctrl_lim, c->alphas, c->cost_pred, U_alpha_dev, c->sweep_list);
         return hipGetLastError();
-    }
-    const auto kernel = c->d.batch <= c->n_simd ? k_forward_mfma_excl<NCZ, NCU> : k_forward_mfma<NCZ, NCU>;
-    hipLaunchKernelGGL(kernel, dim3(c->d.batch), dim3(64), 0, c->stream, c->L, c->d.T, c->d.n_alpha, c->rec, c->K, c->k, c->u_nom,
-                       c->ctrl_lim, c->alphas, c->cost_pred, U_alpha_dev);
-    return hipGetLastError();
+    });
 }
 
 hipError_t launch_forward_mfma(Ctx *c, double *U_alpha_dev)

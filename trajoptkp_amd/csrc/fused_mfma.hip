@@ -334,7 +334,7 @@ __device__ __forceinline__ void backward_fused_body(double *sh, const double *pc
     // top of the step.)
     auto wsync = [&]() { __builtin_amdgcn_wave_barrier(); };
     const int lane = threadIdx.x & 63, c = lane & 15, q = lane >> 4;
-    const int b = btraj;                  // (the block's own index but in a listed launch: see k_backward_fused_retry)
+    const int b = btraj;                  // (the block's own index but in a listed launch: see k_backward_fused)
     const double lam = lambda[b];
     // (probe builds, -DKP_PROBE_BWD=bits: 1 residual loads, 2 key-point stores, 4 gain stores go to one of eight trajectories)
     const int bR = (KP_PROBE_BWD & 1) ? (int)(blockIdx.x & 7) : b, bP = (KP_PROBE_BWD & 2) ? (int)(blockIdx.x & 7) : b, bS = (KP_PROBE_BWD & 4) ? (int)(blockIdx.x & 7) : b;
@@ -1046,55 +1046,23 @@ k_backward_fused_stats(RecLayout L, FusedArgs F, int T, const double *__restrict
 // The one-wave backward sweep comes in two forms, launched back to back like the forward sweep's: UNI for key-point sets in
 // which every DoF of a trajectory has the same list, the general form otherwise; each looks at the device flag first and
 // leaves if the set is not its kind.
-template <int N, int M, bool RU0, bool RAW, bool UNI, bool RXC = false>
-__global__ void __launch_bounds__(64)
-k_backward_fused(RecLayout L, FusedArgs F, int T, const double *__restrict__ lambda,
-                 int pd_stride, double *__restrict__ Kout, double *__restrict__ kout,
-                 double *__restrict__ delta_J, int *__restrict__ status, const int *__restrict__ kp_uniform)
-{
-    __shared__ __attribute__((aligned(16))) double sh[FLDS_TOTAL];
-    if ((*kp_uniform != 0) != UNI) return;
-    backward_fused_body<N, M, false, RU0, RAW, UNI, false, RXC>(sh, nullptr, nullptr, L, F, T, lambda, pd_stride, Kout, kout, delta_J, status);
-}
-template <int N, int M, bool RU0, bool RAW, bool UNI, bool RXC = false>
-__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1)))
-k_backward_fused_excl(RecLayout L, FusedArgs F, int T, const double *__restrict__ lambda,
-                      int pd_stride, double *__restrict__ Kout, double *__restrict__ kout,
-                      double *__restrict__ delta_J, int *__restrict__ status, const int *__restrict__ kp_uniform)
-{
-    __shared__ __attribute__((aligned(16))) double sh[FLDS_TOTAL];
-    if ((*kp_uniform != 0) != UNI) return;
-    backward_fused_body<N, M, false, RU0, RAW, UNI, false, RXC>(sh, nullptr, nullptr, L, F, T, lambda, pd_stride, Kout, kout, delta_J, status);
-}
-// The lambda retry twins of the two (kpilqr_set_lambda_retry, lambda_retry.hip): the attempts behind the first of a backward pass under a
-// schedule.  A wave whose trajectory is settled or has given up (gate[b] == 0) leaves before anything else; the first attempt, and
-// every launch without a schedule, is one of the two kernels above, unchanged.
-// The twins also run the sweeps of a listed subset (kpilqr_backward_partial): `list` (device, nullptr: every block sweeps its own index)
+// EXCL, GATED: the trailing flags of every backward sweep kernel (riccati_mfma.hip says why a wave wants a SIMD to
+// itself).  GATED runs the attempts behind the first of a backward pass under a lambda retry schedule (kpilqr_set_lambda_retry,
+// lambda_retry.hip): a wave whose trajectory is settled or has given up (gate[b] == 0) leaves before anything else; the first
+// attempt, and every launch without a schedule, is GATED = false, which reads neither `gate` nor `list`.
+// GATED also runs the sweeps of a listed subset (kpilqr_backward_partial): `list` (device, nullptr: every block sweeps its own index)
 // names the trajectory of block i, gate and every per-trajectory address follow it, and the caller has armed the gate of the listed
 // trajectories.  list[blockIdx.x] is a scalar load off a kernel argument: the index stays wave-uniform, as the descriptors need it.
-template <int N, int M, bool RU0, bool RAW, bool UNI, bool RXC = false>
-__global__ void __launch_bounds__(64)
-k_backward_fused_retry(RecLayout L, FusedArgs F, int T, const double *__restrict__ lambda,
-                       int pd_stride, double *__restrict__ Kout, double *__restrict__ kout,
-                       double *__restrict__ delta_J, int *__restrict__ status, const int *__restrict__ kp_uniform, const int *__restrict__ gate,
-                       const int *__restrict__ list)
+template <int N, int M, bool RU0, bool RAW, bool UNI, bool RXC, bool EXCL, bool GATED>
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, EXCL ? 1 : 0)))
+k_backward_fused(RecLayout L, FusedArgs F, int T, const double *__restrict__ lambda,
+                 int pd_stride, double *__restrict__ Kout, double *__restrict__ kout,
+                 double *__restrict__ delta_J, int *__restrict__ status, const int *__restrict__ kp_uniform, const int *__restrict__ gate,
+                 const int *__restrict__ list)
 {
     __shared__ __attribute__((aligned(16))) double sh[FLDS_TOTAL];
-    const int b = kp_block_traj(list, KP_BLOCK_TRAJ);
-    if (gate[b] == 0) return;
-    if ((*kp_uniform != 0) != UNI) return;
-    backward_fused_body<N, M, false, RU0, RAW, UNI, false, RXC>(sh, nullptr, nullptr, L, F, T, lambda, pd_stride, Kout, kout, delta_J, status, nullptr, b);
-}
-template <int N, int M, bool RU0, bool RAW, bool UNI, bool RXC = false>
-__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1)))
-k_backward_fused_excl_retry(RecLayout L, FusedArgs F, int T, const double *__restrict__ lambda,
-                            int pd_stride, double *__restrict__ Kout, double *__restrict__ kout,
-                            double *__restrict__ delta_J, int *__restrict__ status, const int *__restrict__ kp_uniform, const int *__restrict__ gate,
-                            const int *__restrict__ list)
-{
-    __shared__ __attribute__((aligned(16))) double sh[FLDS_TOTAL];
-    const int b = kp_block_traj(list, KP_BLOCK_TRAJ);
-    if (gate[b] == 0) return;
+    const int b = GATED ? kp_block_traj(list, KP_BLOCK_TRAJ) : KP_BLOCK_TRAJ;
+    if constexpr (GATED) { if (gate[b] == 0) return; }
     if ((*kp_uniform != 0) != UNI) return;
     backward_fused_body<N, M, false, RU0, RAW, UNI, false, RXC>(sh, nullptr, nullptr, L, F, T, lambda, pd_stride, Kout, kout, delta_J, status, nullptr, b);
 }
@@ -1489,34 +1457,19 @@ __device__ __forceinline__ void fusedpc_producer(double *pcbuf, int *sflag, RecL
 #define FPC_TOTAL (FPC_FLAG + 2)
 // guard: -1 run, 1 run only when the device flag says the key-point set is uniform, 0 only when it is not (the raw helper is
 // launched for uniform sets; per-DoF lists go through k_fd_kp_difference and the plain / slope-store helper, launched behind it)
-// Consumer / helper pair (2 x batch <= #SIMDs: a SIMD each)
-template <int N, int M, bool RAWP, bool RU0, bool RXC, bool SLP = false>
+// Consumer / helper pair (2 x batch <= #SIMDs: a SIMD each, so always exclusive: no EXCL flag).  GATED (see k_backward_fused): consumer
+// and helper of a settled trajectory, or of one that gave up, leave together, before the role split and before either touches the
+// ring or its flags -- nobody is left waiting for a partner.  In a listed subset the role placement stays on the block index.
+template <int N, int M, bool RAWP, bool RU0, bool RXC, bool SLP, bool GATED>
 __global__ void __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(1, 1)))
 k_backward_fusedph(RecLayout L, FusedArgs F, int T, int role_shift, const double *__restrict__ lambda,
                    int pd_stride, double *__restrict__ Kout, double *__restrict__ kout,
-                   double *__restrict__ delta_J, int *__restrict__ status, const int *__restrict__ kp_uniform, int guard)
+                   double *__restrict__ delta_J, int *__restrict__ status, const int *__restrict__ kp_uniform, int guard,
+                   const int *__restrict__ gate, const int *__restrict__ list)
 {
     __shared__ __attribute__((aligned(16))) double sh[FPC_TOTAL];
-    if (guard >= 0 && (*kp_uniform != 0) != (guard != 0)) return;
-    const bool consumer = ((__builtin_amdgcn_readfirstlane(threadIdx.x >> 6) ^ (blockIdx.x >> role_shift)) & 1) == 0;
-    if (consumer)
-        backward_fused_body<N, M, true, RU0>(sh, sh + FPC_RING, (int *)(sh + FPC_FLAG), L, F, T, lambda, pd_stride, Kout, kout,
-                                                   delta_J, status);
-    else
-        fusedpc_producer<N, M, RAWP, RU0, RXC, SLP>(sh + FPC_RING, (int *)(sh + FPC_FLAG), L, F, T, sh);
-}
-// ... and its lambda retry twin (see k_backward_fused_retry): consumer and helper of a settled trajectory, or of one that gave up, leave
-// together, before the role split and before either touches the ring or its flags -- nobody is left waiting for a partner
-template <int N, int M, bool RAWP, bool RU0, bool RXC, bool SLP = false>
-__global__ void __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(1, 1)))
-k_backward_fusedph_retry(RecLayout L, FusedArgs F, int T, int role_shift, const double *__restrict__ lambda,
-                         int pd_stride, double *__restrict__ Kout, double *__restrict__ kout,
-                         double *__restrict__ delta_J, int *__restrict__ status, const int *__restrict__ kp_uniform, int guard,
-                         const int *__restrict__ gate, const int *__restrict__ list)
-{
-    __shared__ __attribute__((aligned(16))) double sh[FPC_TOTAL];
-    const int b = kp_block_traj(list, KP_BLOCK_TRAJ);     // (a listed subset: see k_backward_fused_retry; the role placement stays on the block index)
-    if (gate[b] == 0) return;
+    const int b = GATED ? kp_block_traj(list, KP_BLOCK_TRAJ) : KP_BLOCK_TRAJ;
+    if constexpr (GATED) { if (gate[b] == 0) return; }
     if (guard >= 0 && (*kp_uniform != 0) != (guard != 0)) return;
     const bool consumer = ((__builtin_amdgcn_readfirstlane(threadIdx.x >> 6) ^ (blockIdx.x >> role_shift)) & 1) == 0;
     if (consumer)
@@ -2084,48 +2037,20 @@ __device__ __forceinline__ void forward_fused_body(RecLayout L, FusedArgs F, int
 // The one-wave forward sweep comes in two forms, launched back to back: UNI for key-point sets in which every DoF of a
 // trajectory has the same list (the device flag of k_kp_uniform says so), the general form otherwise.  Each looks at the
 // flag first and leaves if the set is not its kind, so the host never has to know.
-template <int NCZ, int NCU, bool RU0, bool UNI, bool RXC = false, bool PAIR2 = false>
-__global__ void __launch_bounds__(64)
+// EXCL, LISTED: the trailing flags of every forward sweep kernel.  LISTED (kpilqr_forward_linear_partial): block
+// i sweeps trajectory list[i] -- a scalar load off a kernel argument, so the index the per-trajectory descriptors are built from stays
+// wave-uniform.  LISTED = false, the launch of every whole-batch call, never reads `list`.  (The index is formed in the call of the
+// body, where the body's default argument forms the block's own: in front of it, the compiler orders the entry block differently.)
+template <int NCZ, int NCU, bool RU0, bool UNI, bool RXC, bool PAIR2, bool EXCL, bool LISTED>
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, EXCL ? 1 : 0)))
 k_forward_fused(RecLayout L, FusedArgs F, int T, int n_alpha, const double *__restrict__ Kin,
                 const double *__restrict__ kin, const double *__restrict__ u_nom, const double *__restrict__ ctrl_lim,
                 const double *__restrict__ alphas, double *__restrict__ cost_pred, double *__restrict__ U_alpha,
-                const int *__restrict__ kp_uniform)
+                const int *__restrict__ kp_uniform, const int *__restrict__ list)
 {
     if ((*kp_uniform != 0) != UNI) return;
-    forward_fused_body<NCZ, NCU, RU0, UNI, RXC, PAIR2>(L, F, T, n_alpha, Kin, kin, u_nom, ctrl_lim, alphas, cost_pred, U_alpha);
-}
-template <int NCZ, int NCU, bool RU0, bool UNI, bool RXC = false, bool PAIR2 = false>
-__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1)))
-k_forward_fused_excl(RecLayout L, FusedArgs F, int T, int n_alpha, const double *__restrict__ Kin,
-                     const double *__restrict__ kin, const double *__restrict__ u_nom, const double *__restrict__ ctrl_lim,
-                     const double *__restrict__ alphas, double *__restrict__ cost_pred, double *__restrict__ U_alpha,
-                     const int *__restrict__ kp_uniform)
-{
-    if ((*kp_uniform != 0) != UNI) return;
-    forward_fused_body<NCZ, NCU, RU0, UNI, RXC, PAIR2>(L, F, T, n_alpha, Kin, kin, u_nom, ctrl_lim, alphas, cost_pred, U_alpha);
-}
-// The listed twins of the two (kpilqr_forward_linear_partial): block i sweeps trajectory list[i] -- a scalar load off a kernel
-// argument, so the index the per-trajectory descriptors are built from stays wave-uniform.  The same body; the two kernels above
-// are the launches of every whole-batch call, unchanged.
-template <int NCZ, int NCU, bool RU0, bool UNI, bool RXC = false, bool PAIR2 = false>
-__global__ void __launch_bounds__(64)
-k_forward_fused_listed(RecLayout L, FusedArgs F, int T, int n_alpha, const double *__restrict__ Kin,
-                       const double *__restrict__ kin, const double *__restrict__ u_nom, const double *__restrict__ ctrl_lim,
-                       const double *__restrict__ alphas, double *__restrict__ cost_pred, double *__restrict__ U_alpha,
-                       const int *__restrict__ kp_uniform, const int *__restrict__ list)
-{
-    if ((*kp_uniform != 0) != UNI) return;
-    forward_fused_body<NCZ, NCU, RU0, UNI, RXC, PAIR2>(L, F, T, n_alpha, Kin, kin, u_nom, ctrl_lim, alphas, cost_pred, U_alpha, list[blockIdx.x]);
-}
-template <int NCZ, int NCU, bool RU0, bool UNI, bool RXC = false, bool PAIR2 = false>
-__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1)))
-k_forward_fused_excl_listed(RecLayout L, FusedArgs F, int T, int n_alpha, const double *__restrict__ Kin,
-                            const double *__restrict__ kin, const double *__restrict__ u_nom, const double *__restrict__ ctrl_lim,
-                            const double *__restrict__ alphas, double *__restrict__ cost_pred, double *__restrict__ U_alpha,
-                            const int *__restrict__ kp_uniform, const int *__restrict__ list)
-{
-    if ((*kp_uniform != 0) != UNI) return;
-    forward_fused_body<NCZ, NCU, RU0, UNI, RXC, PAIR2>(L, F, T, n_alpha, Kin, kin, u_nom, ctrl_lim, alphas, cost_pred, U_alpha, list[blockIdx.x]);
+    forward_fused_body<NCZ, NCU, RU0, UNI, RXC, PAIR2>(L, F, T, n_alpha, Kin, kin, u_nom, ctrl_lim, alphas, cost_pred, U_alpha,
+                                                       LISTED ? list[blockIdx.x] : KP_BLOCK_TRAJ);
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -2470,65 +2395,38 @@ __device__ __forceinline__ void forward_sc_cost(double *sh, RecLayout L, FusedAr
 
 // UNIFORM key-point sets: state wave (with its own a4) + scoring wave -- no staging wave, whatever the batch up to #SIMDs / 2.
 // Leaves at once if the device flag says the set is not uniform (the general forms are launched behind it and look at the same flag).
-template <int NCZ, int NCU, bool RU0 = false, bool RXC = false>
+// LISTED (see k_forward_fused; always exclusive, so no EXCL flag): every wave of block i works on trajectory list[i].
+template <int NCZ, int NCU, bool RU0, bool RXC, bool LISTED>
 __global__ void __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(1, 1)))
 k_forward_fused_scu(RecLayout L, FusedArgs F, int T, int n_alpha, const double *__restrict__ Kin,
                     const double *__restrict__ kin, const double *__restrict__ u_nom, const double *__restrict__ ctrl_lim,
                     const double *__restrict__ alphas, double *__restrict__ cost_pred, double *__restrict__ U_alpha,
-                    const int *__restrict__ kp_uniform)
+                    const int *__restrict__ kp_uniform, const int *__restrict__ list)
 {
     __shared__ __attribute__((aligned(16))) double sh[FSC_TOTAL];
     if (*kp_uniform == 0) return;
+    const int listed = LISTED ? list[blockIdx.x] : 0;       // (one load in front of the role split; the block's own index is read by the role that uses it)
     const bool state = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6) == 0;
-    if (state) forward_sc_state<NCZ, NCU, RU0, true>(sh, L, T, n_alpha, Kin, kin, u_nom, ctrl_lim, alphas, U_alpha, &F);
-    else       forward_sc_cost<NCZ, NCU, 1, RU0, RXC>(sh, L, F, T, n_alpha, cost_pred);
+    if (state) forward_sc_state<NCZ, NCU, RU0, true>(sh, L, T, n_alpha, Kin, kin, u_nom, ctrl_lim, alphas, U_alpha, &F, LISTED ? listed : (int)blockIdx.x);
+    else       forward_sc_cost<NCZ, NCU, 1, RU0, RXC>(sh, L, F, T, n_alpha, cost_pred, LISTED ? listed : (int)blockIdx.x);
 }
 
 // state + cost + staging waves (4 x batch <= #SIMDs: one 3-wave workgroup per CU): a cost wave that also stages is the longer
 // one of a pair (1 360 vs 1 130 cycles per step), so its a4 half goes to a third wave
-template <int NCZ, int NCU, bool RU0 = false, bool RXC = false>
+template <int NCZ, int NCU, bool RU0, bool RXC, bool LISTED>
 __global__ void __launch_bounds__(192) __attribute__((amdgpu_waves_per_eu(1, 1)))
 k_forward_fused_sc3(RecLayout L, FusedArgs F, int T, int n_alpha, const double *__restrict__ Kin,
                     const double *__restrict__ kin, const double *__restrict__ u_nom, const double *__restrict__ ctrl_lim,
                     const double *__restrict__ alphas, double *__restrict__ cost_pred, double *__restrict__ U_alpha,
-                    const int *__restrict__ kp_uniform, int only_ragged)
+                    const int *__restrict__ kp_uniform, int only_ragged, const int *__restrict__ list)
 {
     __shared__ __attribute__((aligned(16))) double sh[FSC_TOTAL];
     if (only_ragged && *kp_uniform != 0) return;       // (launched behind k_forward_fused_scu, which has run the uniform set)
+    const int listed = LISTED ? list[blockIdx.x] : 0;       // (as in k_forward_fused_scu)
     const int role = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    if (role == 0) forward_sc_state<NCZ, NCU, RU0>(sh, L, T, n_alpha, Kin, kin, u_nom, ctrl_lim, alphas, U_alpha);
-    else if (role == 1) forward_sc_cost<NCZ, NCU, 1, RU0, RXC>(sh, L, F, T, n_alpha, cost_pred);
-    else forward_sc_cost<NCZ, NCU, 2>(sh, L, F, T, n_alpha, cost_pred);
-}
-// The listed twins of the pair and the triple (see k_forward_fused_listed): every wave of block i works on trajectory list[i]
-template <int NCZ, int NCU, bool RU0 = false, bool RXC = false>
-__global__ void __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(1, 1)))
-k_forward_fused_scu_listed(RecLayout L, FusedArgs F, int T, int n_alpha, const double *__restrict__ Kin,
-                           const double *__restrict__ kin, const double *__restrict__ u_nom, const double *__restrict__ ctrl_lim,
-                           const double *__restrict__ alphas, double *__restrict__ cost_pred, double *__restrict__ U_alpha,
-                           const int *__restrict__ kp_uniform, const int *__restrict__ list)
-{
-    __shared__ __attribute__((aligned(16))) double sh[FSC_TOTAL];
-    if (*kp_uniform == 0) return;
-    const int b = list[blockIdx.x];
-    const bool state = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6) == 0;
-    if (state) forward_sc_state<NCZ, NCU, RU0, true>(sh, L, T, n_alpha, Kin, kin, u_nom, ctrl_lim, alphas, U_alpha, &F, b);
-    else       forward_sc_cost<NCZ, NCU, 1, RU0, RXC>(sh, L, F, T, n_alpha, cost_pred, b);
-}
-template <int NCZ, int NCU, bool RU0 = false, bool RXC = false>
-__global__ void __launch_bounds__(192) __attribute__((amdgpu_waves_per_eu(1, 1)))
-k_forward_fused_sc3_listed(RecLayout L, FusedArgs F, int T, int n_alpha, const double *__restrict__ Kin,
-                           const double *__restrict__ kin, const double *__restrict__ u_nom, const double *__restrict__ ctrl_lim,
-                           const double *__restrict__ alphas, double *__restrict__ cost_pred, double *__restrict__ U_alpha,
-                           const int *__restrict__ kp_uniform, int only_ragged, const int *__restrict__ list)
-{
-    __shared__ __attribute__((aligned(16))) double sh[FSC_TOTAL];
-    if (only_ragged && *kp_uniform != 0) return;
-    const int b = list[blockIdx.x];
-    const int role = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    if (role == 0) forward_sc_state<NCZ, NCU, RU0>(sh, L, T, n_alpha, Kin, kin, u_nom, ctrl_lim, alphas, U_alpha, nullptr, b);
-    else if (role == 1) forward_sc_cost<NCZ, NCU, 1, RU0, RXC>(sh, L, F, T, n_alpha, cost_pred, b);
-    else forward_sc_cost<NCZ, NCU, 2>(sh, L, F, T, n_alpha, cost_pred, b);
+    if (role == 0) forward_sc_state<NCZ, NCU, RU0>(sh, L, T, n_alpha, Kin, kin, u_nom, ctrl_lim, alphas, U_alpha, nullptr, LISTED ? listed : (int)blockIdx.x);
+    else if (role == 1) forward_sc_cost<NCZ, NCU, 1, RU0, RXC>(sh, L, F, T, n_alpha, cost_pred, LISTED ? listed : (int)blockIdx.x);
+    else forward_sc_cost<NCZ, NCU, 2>(sh, L, F, T, n_alpha, cost_pred, LISTED ? listed : (int)blockIdx.x);
 }
 
 #if KP_PART(1)
@@ -2598,15 +2496,10 @@ FusedLaunch plan_forward_fused(const Ctx *c)
 template <int NN, int MM, bool RU, bool RW, bool UN, bool RX>
 static void launch_bf_kernel(Ctx *c, const FusedLaunch &p, const FusedArgs &F, int pd_stride)
 {
-    if (c->bwd_gate) {
-        const auto twin = p.excl ? k_backward_fused_excl_retry<NN, MM, RU, RW, UN, RX> : k_backward_fused_retry<NN, MM, RU, RW, UN, RX>;
-        hipLaunchKernelGGL(twin, dim3(c->d.batch), dim3(64), 0, c->stream, c->L, F, c->d.T, c->lambda, pd_stride, c->K, c->k, c->delta_J,
-                           c->status, c->kp_uniform, c->bwd_gate, c->sweep_list);
-        return;
-    }
-    const auto kernel = p.excl ? k_backward_fused_excl<NN, MM, RU, RW, UN, RX> : k_backward_fused<NN, MM, RU, RW, UN, RX>;
-    hipLaunchKernelGGL(kernel, dim3(c->d.batch), dim3(64), 0, c->stream, c->L, F, c->d.T, c->lambda, pd_stride, c->K, c->k, c->delta_J,
-                       c->status, c->kp_uniform);
+    kp_with_flags(p.excl, c->bwd_gate != nullptr, [&](auto excl, auto gated) {
+        hipLaunchKernelGGL((k_backward_fused<NN, MM, RU, RW, UN, RX, excl(), gated()>), dim3(c->d.batch), dim3(64), 0, c->stream, c->L, F,
+                           c->d.T, c->lambda, pd_stride, c->K, c->k, c->delta_J, c->status, c->kp_uniform, c->bwd_gate, c->sweep_list);
+    });
 }
 // rxc: constant residual Jacobians.  The kernels exist with r_u = 0 only, hence RX = RU: nothing is compiled for <RU = false, RX = true>
 template <int NN, int MM, bool RU, bool RW, bool UN>
@@ -2654,17 +2547,14 @@ hipError_t launch_backward_fused(Ctx *c, const FusedLaunch &p, int pd_stride)
 template <int NN, int MM, bool RW, bool SL>
 static void launch_bph_kernel(Ctx *c, const FusedLaunch &p, const FusedArgs &F, int pd_stride, int guard)
 {
-    if (c->bwd_gate) {
-        auto twin = k_backward_fusedph_retry<NN, MM, RW, true, true, SL>;
-        if (!p.rxc) twin = p.ru0 ? k_backward_fusedph_retry<NN, MM, RW, true, false, SL> : k_backward_fusedph_retry<NN, MM, RW, false, false, SL>;
-        hipLaunchKernelGGL(twin, dim3(c->d.batch), dim3(128), 0, c->stream, c->L, F, c->d.T, c->tune.role_shift, c->lambda, pd_stride, c->K,
-                           c->k, c->delta_J, c->status, c->kp_uniform, guard, c->bwd_gate, c->sweep_list);
-        return;
-    }
-    auto kernel = k_backward_fusedph<NN, MM, RW, true, true, SL>;
-    if (!p.rxc) kernel = p.ru0 ? k_backward_fusedph<NN, MM, RW, true, false, SL> : k_backward_fusedph<NN, MM, RW, false, false, SL>;
-    hipLaunchKernelGGL(kernel, dim3(c->d.batch), dim3(128), 0, c->stream, c->L, F, c->d.T, c->tune.role_shift, c->lambda, pd_stride, c->K,
-                       c->k, c->delta_J, c->status, c->kp_uniform, guard);
+    const auto pick = [&](auto gated) {
+        auto kernel = k_backward_fusedph<NN, MM, RW, true, true, SL, gated()>;
+        if (!p.rxc) kernel = p.ru0 ? k_backward_fusedph<NN, MM, RW, true, false, SL, gated()> : k_backward_fusedph<NN, MM, RW, false, false, SL, gated()>;
+        return kernel;
+    };
+    hipLaunchKernelGGL(c->bwd_gate ? pick(std::true_type{}) : pick(std::false_type{}), dim3(c->d.batch), dim3(128), 0, c->stream, c->L, F,
+                       c->d.T, c->tune.role_shift, c->lambda, pd_stride, c->K, c->k, c->delta_J, c->status, c->kp_uniform, guard, c->bwd_gate,
+                       c->sweep_list);
 }
 // Per-DoF lists: the helper walks the slope store, uniform sets the column store with its dividing tracker: two launches, the
 // device flag decides.  raw: the helper differences the payload of uniform sets; k_fd_kp_difference and the plain sweep behind it
@@ -2710,39 +2600,34 @@ hipError_t launch_backward_fused_stats(Ctx *c, int pd_stride, int *hist_dev)
 
 #endif
 #if KP_PART(3)
-// ---- forward.  Every kernel takes the same arguments (the triple one more: only_ragged)
+// ---- forward.  Every kernel takes the same arguments (the triple one more in front of the list: only_ragged)
 template <class Kernel, class... More>
 static void launch_ff_kernel(Kernel kernel, int block, Ctx *c, const FusedArgs &F, double *U_alpha_dev, More... more)
 {
     hipLaunchKernelGGL(kernel, dim3(c->d.batch), dim3(block), 0, c->stream, c->L, F, c->d.T, c->d.n_alpha, c->K, c->k, c->u_nom, c->ctrl_lim,
-                       c->alphas, c->cost_pred, U_alpha_dev, c->kp_uniform, more...);
+                       c->alphas, c->cost_pred, U_alpha_dev, c->kp_uniform, more..., c->sweep_list);
 }
-// the state / cost pair (uniform sets) and the state / cost / staging triple: the cost wave has the residual instantiations
+// the state / cost pair (uniform sets) and the state / cost / staging triple: the cost wave has the residual instantiations;
+// a listed subset (kpilqr_forward_linear_partial) runs the LISTED instantiation of the same form
 template <int NCZ, int NCU>
 static void launch_ff_pair(Ctx *c, const FusedLaunch &p, const FusedArgs &F, double *U_alpha_dev)
 {
-    if (c->sweep_list) {           // a listed subset (kpilqr_forward_linear_partial): the listed twin of the same form
-        auto twin = k_forward_fused_scu_listed<NCZ, NCU, true, true>;
-        if (!p.rxc) twin = p.ru0 ? k_forward_fused_scu_listed<NCZ, NCU, true, false> : k_forward_fused_scu_listed<NCZ, NCU>;
-        launch_ff_kernel(twin, 128, c, F, U_alpha_dev, c->sweep_list);
-        return;
-    }
-    auto kernel = k_forward_fused_scu<NCZ, NCU, true, true>;
-    if (!p.rxc) kernel = p.ru0 ? k_forward_fused_scu<NCZ, NCU, true, false> : k_forward_fused_scu<NCZ, NCU>;
-    launch_ff_kernel(kernel, 128, c, F, U_alpha_dev);
+    const auto pick = [&](auto listed) {
+        auto kernel = k_forward_fused_scu<NCZ, NCU, true, true, listed()>;
+        if (!p.rxc) kernel = p.ru0 ? k_forward_fused_scu<NCZ, NCU, true, false, listed()> : k_forward_fused_scu<NCZ, NCU, false, false, listed()>;
+        return kernel;
+    };
+    launch_ff_kernel(c->sweep_list ? pick(std::true_type{}) : pick(std::false_type{}), 128, c, F, U_alpha_dev);
 }
 template <int NCZ, int NCU>
 static void launch_ff_triple(Ctx *c, const FusedLaunch &p, const FusedArgs &F, double *U_alpha_dev, int only_ragged)
 {
-    if (c->sweep_list) {
-        auto twin = k_forward_fused_sc3_listed<NCZ, NCU, true, true>;
-        if (!p.rxc) twin = p.ru0 ? k_forward_fused_sc3_listed<NCZ, NCU, true, false> : k_forward_fused_sc3_listed<NCZ, NCU>;
-        launch_ff_kernel(twin, 192, c, F, U_alpha_dev, only_ragged, c->sweep_list);
-        return;
-    }
-    auto kernel = k_forward_fused_sc3<NCZ, NCU, true, true>;
-    if (!p.rxc) kernel = p.ru0 ? k_forward_fused_sc3<NCZ, NCU, true, false> : k_forward_fused_sc3<NCZ, NCU>;
-    launch_ff_kernel(kernel, 192, c, F, U_alpha_dev, only_ragged);
+    const auto pick = [&](auto listed) {
+        auto kernel = k_forward_fused_sc3<NCZ, NCU, true, true, listed()>;
+        if (!p.rxc) kernel = p.ru0 ? k_forward_fused_sc3<NCZ, NCU, true, false, listed()> : k_forward_fused_sc3<NCZ, NCU, false, false, listed()>;
+        return kernel;
+    };
+    launch_ff_kernel(c->sweep_list ? pick(std::true_type{}) : pick(std::false_type{}), 192, c, F, U_alpha_dev, only_ragged);
 }
 // One wave per trajectory: the uniform and the general form back to back, the one whose kind of key-point set is not resident
 // leaves at once (k_forward_fused); behind the pair the general form alone.  RX = RU as in launch_bf_form.  RU (r_u never
@@ -2752,21 +2637,17 @@ static void launch_ff_triple(Ctx *c, const FusedLaunch &p, const FusedArgs &F, d
 template <int NCZ, int NCU, bool RU, bool UNI>
 static void launch_ff_form(Ctx *c, const FusedLaunch &p, const FusedArgs &F, double *U_alpha_dev)
 {
-    // paired scoring (FusedLaunch::pair2): the uniform constant-Jacobian form with ONE scoring product per two steps
-    if constexpr (RU && UNI) {
-        if (p.rxc && p.pair2) {
-            if (c->sweep_list) launch_ff_kernel(p.excl ? k_forward_fused_excl_listed<NCZ, NCU, true, true, true, true> : k_forward_fused_listed<NCZ, NCU, true, true, true, true>, 64, c, F, U_alpha_dev, c->sweep_list);
-            else launch_ff_kernel(p.excl ? k_forward_fused_excl<NCZ, NCU, true, true, true, true> : k_forward_fused<NCZ, NCU, true, true, true, true>, 64, c, F, U_alpha_dev);
-            return;
+    kp_with_flags(p.excl, c->sweep_list != nullptr, [&](auto excl, auto listed) {
+        // paired scoring (FusedLaunch::pair2): the uniform constant-Jacobian form with ONE scoring product per two steps
+        if constexpr (RU && UNI) {
+            if (p.rxc && p.pair2) {
+                launch_ff_kernel(k_forward_fused<NCZ, NCU, true, true, true, true, excl(), listed()>, 64, c, F, U_alpha_dev);
+                return;
+            }
         }
-    }
-    if (c->sweep_list) {
-        if (RU && p.rxc) launch_ff_kernel(p.excl ? k_forward_fused_excl_listed<NCZ, NCU, RU, UNI, RU> : k_forward_fused_listed<NCZ, NCU, RU, UNI, RU>, 64, c, F, U_alpha_dev, c->sweep_list);
-        else launch_ff_kernel(p.excl ? k_forward_fused_excl_listed<NCZ, NCU, RU, UNI, false> : k_forward_fused_listed<NCZ, NCU, RU, UNI, false>, 64, c, F, U_alpha_dev, c->sweep_list);
-        return;
-    }
-    if (RU && p.rxc) launch_ff_kernel(p.excl ? k_forward_fused_excl<NCZ, NCU, RU, UNI, RU> : k_forward_fused<NCZ, NCU, RU, UNI, RU>, 64, c, F, U_alpha_dev);
-    else launch_ff_kernel(p.excl ? k_forward_fused_excl<NCZ, NCU, RU, UNI, false> : k_forward_fused<NCZ, NCU, RU, UNI, false>, 64, c, F, U_alpha_dev);
+        if (RU && p.rxc) launch_ff_kernel(k_forward_fused<NCZ, NCU, RU, UNI, RU, false, excl(), listed()>, 64, c, F, U_alpha_dev);
+        else launch_ff_kernel(k_forward_fused<NCZ, NCU, RU, UNI, false, false, excl(), listed()>, 64, c, F, U_alpha_dev);
+    });
 }
 template <int NCZ, int NCU, bool RU>
 static void launch_ff_w1(Ctx *c, const FusedLaunch &p, const FusedArgs &F, double *U_alpha_dev, bool only_ragged)

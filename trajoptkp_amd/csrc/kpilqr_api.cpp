@@ -1434,8 +1434,8 @@ static int retry_attempts_for(const kpilqr_ctx *c, const double *lambda, size_t 
 extern "C++" template <class Launch>
 static int sweep_attempts(kpilqr_ctx *c, kpilqr_ctx *lc, Launch launch)
 {
-    // A listed launch (lc: make_list_view) runs through the retry twins from its first attempt on -- they take the list beside the
-    // gate -- with the gate armed for the listed trajectories alone; the schedule's two kernels walk the list, not the batch.
+    // A listed launch (lc: make_list_view) runs through the GATED instantiations from its first attempt on -- they are the ones that read
+    // the list beside the gate -- with the gate armed for the listed trajectories alone; the schedule's two kernels walk the list, not the batch.
     const bool listed = lc->sweep_list != nullptr;
     const int *const first_gate = listed ? (const int *)c->gate : nullptr;
     kpilqr_ctx *const rc = listed ? lc : c;
@@ -1456,6 +1456,17 @@ static int sweep_attempts(kpilqr_ctx *c, kpilqr_ctx *lc, Launch launch)
     }
     c->retry_ran = true;
     return KPILQR_OK;
+}
+
+// the sweep of a context that is not fused, on lc (the context, or a list view of it): one launcher per family
+static hipError_t launch_backward_family(Ctx *lc, int pd_stride)
+{
+    switch (lc->bwd_family) {
+    case Family::t1: return launch_backward_mfma(lc, pd_stride);
+    case Family::tiled: return launch_backward_tiled(lc, pd_stride);
+    case Family::wide: return launch_backward_wide(lc, pd_stride);
+    default: return launch_backward_generic(lc, pd_stride);
+    }
 }
 
 static int run_backward(kpilqr_ctx *c, int pd_stride)
@@ -1501,14 +1512,7 @@ static int run_backward(kpilqr_ctx *c, int pd_stride)
     }
     c->last_bwd = FusedLaunch{};       // (no plan: not a fused launch, and the tiled a6 sweep streams r_x)
     if (c->tiled_a6) { const int rc = ensure_rx_buffer(c); if (rc) return rc; }
-    return sweep_attempts(c, c, [&] {
-        switch (c->bwd_family) {
-        case Family::t1: return launch_backward_mfma(c, pd_stride);
-        case Family::tiled: return launch_backward_tiled(c, pd_stride);
-        case Family::wide: return launch_backward_wide(c, pd_stride);
-        default: return launch_backward_generic(c, pd_stride);
-        }
-    });
+    return sweep_attempts(c, c, [&] { return launch_backward_family(c, pd_stride); });
 }
 
 int kpilqr_backward(kpilqr_ctx *c, const double *lambda, int pd_check_stride, int *status, double *delta_J)
@@ -1792,6 +1796,17 @@ int kpilqr_download_gains_f32_partial(kpilqr_ctx *c, int count, const int *traj,
     return download_gains_f32(c, count, traj, K32, k);
 }
 
+// as launch_backward_family
+static hipError_t launch_forward_family(Ctx *lc, double *U_dev)
+{
+    switch (lc->fwd_family) {
+    case Family::t1: return launch_forward_mfma(lc, U_dev);
+    case Family::tiled: return launch_forward_tiled(lc, U_dev);
+    case Family::wide: return launch_forward_wide(lc, U_dev);
+    default: return launch_forward_generic(lc, U_dev);
+    }
+}
+
 static int run_forward(kpilqr_ctx *c, double *U_dev)
 {
     c->last_width[1] = -1;
@@ -1826,12 +1841,7 @@ static int run_forward(kpilqr_ctx *c, double *U_dev)
     }
     c->last_fwd = FusedLaunch{};
     if (c->tiled_a6) { const int rc = ensure_rx_buffer(c); if (rc) return rc; }
-    switch (c->fwd_family) {
-    case Family::t1: KP_HIP(c, launch_forward_mfma(c, U_dev)); break;
-    case Family::tiled: KP_HIP(c, launch_forward_tiled(c, U_dev)); break;
-    case Family::wide: KP_HIP(c, launch_forward_wide(c, U_dev)); break;
-    default: KP_HIP(c, launch_forward_generic(c, U_dev)); break;
-    }
+    KP_HIP(c, launch_forward_family(c, U_dev));
     c->last_fwd.fwd_ran = true;
     return KPILQR_OK;
 }
@@ -1943,14 +1953,7 @@ static int run_backward_listed(kpilqr_ctx *c, int count, int pd_stride)
     if (c->tiled_a6) { const int rc = ensure_rx_buffer(c); if (rc) return rc; }
     make_list_view(c, count, &v);
     c->last_width[0] = count;
-    return sweep_attempts(c, &v, [&] {
-        switch (c->bwd_family) {
-        case Family::t1: return launch_backward_mfma(&v, pd_stride);
-        case Family::tiled: return launch_backward_tiled(&v, pd_stride);
-        case Family::wide: return launch_backward_wide(&v, pd_stride);
-        default: return launch_backward_generic(&v, pd_stride);
-        }
-    });
+    return sweep_attempts(c, &v, [&] { return launch_backward_family(&v, pd_stride); });
 }
 
 static int run_forward_listed(kpilqr_ctx *c, int count, double *U_dev)
@@ -1971,12 +1974,7 @@ static int run_forward_listed(kpilqr_ctx *c, int count, double *U_dev)
     if (c->tiled_a6) { const int rc = ensure_rx_buffer(c); if (rc) return rc; }
     make_list_view(c, count, &v);
     c->last_width[1] = count;
-    switch (c->fwd_family) {
-    case Family::t1: KP_HIP(c, launch_forward_mfma(&v, U_dev)); break;
-    case Family::tiled: KP_HIP(c, launch_forward_tiled(&v, U_dev)); break;
-    case Family::wide: KP_HIP(c, launch_forward_wide(&v, U_dev)); break;
-    default: KP_HIP(c, launch_forward_generic(&v, U_dev)); break;
-    }
+    KP_HIP(c, launch_forward_family(&v, U_dev));
     c->last_fwd.fwd_ran = true;
     return KPILQR_OK;
 }

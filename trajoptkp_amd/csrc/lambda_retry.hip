@@ -19,24 +19,31 @@ namespace kpilqr {
 
 #define KPLR_THREADS 256
 
-// before the first attempt of a call: every trajectory is about to run its first sweep
+// Both kernels take (count, list): thread i works on trajectory list[i], or on trajectory i where list is nullptr (the whole batch).
+// In a listed launch (kpilqr_backward_partial; Ctx::sweep_list, d.batch entries) an unlisted trajectory -- whose status may well be
+// non-zero from an earlier sweep -- is therefore never armed, and no word of its lambda, attempts or gate is written.  The listed
+// sweeps look at the gates of listed trajectories only.
+
+// before the first attempt of a call: every trajectory (of the list) is about to run its first sweep
 __global__ void __launch_bounds__(KPLR_THREADS)
-k_lambda_retry_begin(int batch, int *__restrict__ attempts, int *__restrict__ gate)
+k_lambda_retry_begin(int count, const int *__restrict__ list, int *__restrict__ attempts, int *__restrict__ gate)
 {
-    const int b = blockIdx.x * KPLR_THREADS + threadIdx.x;
-    if (b >= batch) return;
-    attempts[b] = 1;
+    const int i = blockIdx.x * KPLR_THREADS + threadIdx.x;
+    if (i >= count) return;
+    const int b = list ? list[i] : i;
+    if (attempts) attempts[b] = 1;           // (nullptr: no schedule, the gate alone is armed -- launch_gate_arm)
     gate[b] = 1;
 }
 
 // between two attempts.  A trajectory whose gate is already 0 did not run the last attempt: its status is an earlier sweep's and
 // it stays out.
 __global__ void __launch_bounds__(KPLR_THREADS)
-k_lambda_retry(int batch, double factor, double max_lambda, const int *__restrict__ status, double *__restrict__ lambda,
-               int *__restrict__ attempts, int *__restrict__ gate)
+k_lambda_retry(int count, const int *__restrict__ list, double factor, double max_lambda, const int *__restrict__ status,
+               double *__restrict__ lambda, int *__restrict__ attempts, int *__restrict__ gate)
 {
-    const int b = blockIdx.x * KPLR_THREADS + threadIdx.x;
-    if (b >= batch) return;
+    const int i = blockIdx.x * KPLR_THREADS + threadIdx.x;
+    if (i >= count) return;
+    const int b = list ? list[i] : i;
     if (gate[b] == 0) return;
     int again = 0;
     if (status[b] != 0) {
@@ -50,70 +57,31 @@ k_lambda_retry(int batch, double factor, double max_lambda, const int *__restric
     gate[b] = again;
 }
 
-// The same two for a listed launch (kpilqr_backward_partial; Ctx::sweep_list, d.batch entries): thread i works on trajectory list[i],
-// so an unlisted trajectory -- whose status may well be non-zero from an earlier sweep -- is never armed, and no word of its
-// lambda, attempts or gate is written.  The listed sweeps look at the gates of listed trajectories only.
-__global__ void __launch_bounds__(KPLR_THREADS)
-k_lambda_retry_begin_listed(int count, const int *__restrict__ list, int *__restrict__ attempts, int *__restrict__ gate)
+static hipError_t launch_begin(Ctx *c, int *attempts)
 {
-    const int i = blockIdx.x * KPLR_THREADS + threadIdx.x;
-    if (i >= count) return;
-    const int b = list[i];
-    if (attempts) attempts[b] = 1;           // (nullptr: no schedule, the gate alone is armed -- launch_gate_arm)
-    gate[b] = 1;
-}
-__global__ void __launch_bounds__(KPLR_THREADS)
-k_lambda_retry_listed(int count, const int *__restrict__ list, double factor, double max_lambda, const int *__restrict__ status,
-                      double *__restrict__ lambda, int *__restrict__ attempts, int *__restrict__ gate)
-{
-    const int i = blockIdx.x * KPLR_THREADS + threadIdx.x;
-    if (i >= count) return;
-    const int b = list[i];
-    if (gate[b] == 0) return;
-    int again = 0;
-    if (status[b] != 0) {
-        const double next = lambda[b] * factor;
-        if (!(next > max_lambda)) {
-            lambda[b] = next;
-            attempts[b] += 1;
-            again = 1;
-        }
-    }
-    gate[b] = again;
+    hipLaunchKernelGGL(k_lambda_retry_begin, dim3((c->d.batch + KPLR_THREADS - 1) / KPLR_THREADS), dim3(KPLR_THREADS), 0, c->stream, c->d.batch,
+                       c->sweep_list, attempts, (int *)c->gate);
+    return hipGetLastError();
 }
 
 hipError_t launch_gate_arm(Ctx *c)
 {
     if (c->d.batch <= 0 || !c->sweep_list) return hipSuccess;
-    hipLaunchKernelGGL(k_lambda_retry_begin_listed, dim3((c->d.batch + KPLR_THREADS - 1) / KPLR_THREADS), dim3(KPLR_THREADS), 0, c->stream,
-                       c->d.batch, c->sweep_list, (int *)nullptr, (int *)c->gate);
-    return hipGetLastError();
+    return launch_begin(c, nullptr);
 }
 
 hipError_t launch_lambda_retry_begin(Ctx *c)
 {
     if (c->d.batch <= 0) return hipSuccess;
-    if (c->sweep_list) {
-        hipLaunchKernelGGL(k_lambda_retry_begin_listed, dim3((c->d.batch + KPLR_THREADS - 1) / KPLR_THREADS), dim3(KPLR_THREADS), 0, c->stream,
-                           c->d.batch, c->sweep_list, (int *)c->attempts, (int *)c->gate);
-        return hipGetLastError();
-    }
-    hipLaunchKernelGGL(k_lambda_retry_begin, dim3((c->d.batch + KPLR_THREADS - 1) / KPLR_THREADS), dim3(KPLR_THREADS), 0, c->stream, c->d.batch,
-                       (int *)c->attempts, (int *)c->gate);
-    return hipGetLastError();
+    return launch_begin(c, (int *)c->attempts);
 }
 
 hipError_t launch_lambda_retry(Ctx *c)
 {
     if (c->d.batch <= 0) return hipSuccess;
-    if (c->sweep_list) {
-        hipLaunchKernelGGL(k_lambda_retry_listed, dim3((c->d.batch + KPLR_THREADS - 1) / KPLR_THREADS), dim3(KPLR_THREADS), 0, c->stream,
-                           c->d.batch, c->sweep_list, c->retry.factor, c->retry.max_lambda, (const int *)c->status, (double *)c->lambda,
-                           (int *)c->attempts, (int *)c->gate);
-        return hipGetLastError();
-    }
     hipLaunchKernelGGL(k_lambda_retry, dim3((c->d.batch + KPLR_THREADS - 1) / KPLR_THREADS), dim3(KPLR_THREADS), 0, c->stream, c->d.batch,
-                       c->retry.factor, c->retry.max_lambda, (const int *)c->status, (double *)c->lambda, (int *)c->attempts, (int *)c->gate);
+                       c->sweep_list, c->retry.factor, c->retry.max_lambda, (const int *)c->status, (double *)c->lambda, (int *)c->attempts,
+                       (int *)c->gate);
     return hipGetLastError();
 }
 

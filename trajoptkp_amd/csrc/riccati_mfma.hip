@@ -128,7 +128,7 @@ __device__ __forceinline__ void backward_body(RecLayout L, int T, const double *
     constexpr int n = N, m = M;
     __shared__ __attribute__((aligned(16))) double sh[LDS_TOTAL];
     const int lane = threadIdx.x, c = lane & 15, q = lane >> 4;
-    const int b = btraj;                      // (the block's own index but in a listed launch: see k_backward_mfma_retry)
+    const int b = btraj;                      // (the block's own index but in a listed launch: see k_backward_mfma)
     const double lam = lambda[b];
 
     TileOffs o;
@@ -349,54 +349,25 @@ __device__ __forceinline__ void backward_body(RecLayout L, int T, const double *
     if (lane == 0) status[b] = fail;
 }
 
-// Two entry points over the same body.  One wavefront owns a SIMD's FP64 pipe for the whole horizon,
-// so when the batch fits the chip (<= 1 wave per SIMD) the "exclusive" form declares at most one wave
-// per SIMD: the hardware dispatcher can then never stack two trajectories on one SIMD while others
-// sit idle (it did, after kernels of a different shape: 8.5 ms instead of 6.2 ms at B=1024, T=3000).
-// Larger batches use the shared form (two co-resident waves per SIMD hide each other's latencies).
-template <int N, int M, int ABL = 0>
-__global__ void __launch_bounds__(64)
+// One entry point over the body, in four instantiations (the convention of every sweep kernel: DESIGN.md section 4).
+// EXCL: one wavefront owns a SIMD's FP64 pipe for the whole horizon, so when the batch fits the chip (<= 1 wave per SIMD) the
+// "exclusive" form declares at most one wave per SIMD: the hardware dispatcher can then never stack two trajectories on one SIMD
+// while others sit idle (it did, after kernels of a different shape: 8.5 ms instead of 6.2 ms at B=1024, T=3000).  Larger batches
+// use the shared form (two co-resident waves per SIMD hide each other's latencies).
+// GATED: the attempts behind the first of a backward pass under a lambda retry schedule (kpilqr_set_lambda_retry, lambda_retry.hip).
+// A wave whose trajectory is settled or has given up leaves at once; the first attempt, and every launch without a schedule, is
+// GATED = false and reads neither `gate` nor `list`.  GATED also runs the sweeps of a listed subset (kpilqr_backward_partial): `list`
+// (device, nullptr: every block sweeps its own index) names the trajectory of block i -- a scalar load off a kernel argument,
+// wave-uniform -- and the caller has armed the gate of the listed trajectories.
+template <int N, int M, int ABL = 0, bool EXCL = false, bool GATED = false>
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, EXCL ? 1 : 0)))
 k_backward_mfma(RecLayout L, int T, const double *__restrict__ rec, const double *__restrict__ lambda,
                 int pd_stride, double *__restrict__ Kout, double *__restrict__ kout,
-                double *__restrict__ delta_J, int *__restrict__ status)
+                double *__restrict__ delta_J, int *__restrict__ status, const int *__restrict__ gate, const int *__restrict__ list)
 {
-    backward_body<N, M, ABL>(L, T, rec, lambda, pd_stride, Kout, kout, delta_J, status);
-}
-
-template <int N, int M, int ABL = 0>
-__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1)))
-k_backward_mfma_excl(RecLayout L, int T, const double *__restrict__ rec, const double *__restrict__ lambda,
-                     int pd_stride, double *__restrict__ Kout, double *__restrict__ kout,
-                     double *__restrict__ delta_J, int *__restrict__ status)
-{
-    backward_body<N, M, ABL>(L, T, rec, lambda, pd_stride, Kout, kout, delta_J, status);
-}
-
-// The lambda retry twins (kpilqr_set_lambda_retry, lambda_retry.hip): the attempts behind the first of a backward pass under a schedule.
-// A wave whose trajectory is settled or has given up leaves at once; the first attempt, and every launch without a schedule, is one
-// of the two kernels above, unchanged.  The twins also run the sweeps of a listed subset (kpilqr_backward_partial): `list` (device,
-// nullptr: every block sweeps its own index) names the trajectory of block i -- a scalar load off a kernel argument, wave-uniform --
-// and the caller has armed the gate of the listed trajectories.
-template <int N, int M>
-__global__ void __launch_bounds__(64)
-k_backward_mfma_retry(RecLayout L, int T, const double *__restrict__ rec, const double *__restrict__ lambda,
-                      int pd_stride, double *__restrict__ Kout, double *__restrict__ kout,
-                      double *__restrict__ delta_J, int *__restrict__ status, const int *__restrict__ gate, const int *__restrict__ list)
-{
-    const int b = kp_block_traj(list, blockIdx.x);
-    if (gate[b] == 0) return;
-    backward_body<N, M, 0>(L, T, rec, lambda, pd_stride, Kout, kout, delta_J, status, b);
-}
-
-template <int N, int M>
-__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1)))
-k_backward_mfma_excl_retry(RecLayout L, int T, const double *__restrict__ rec, const double *__restrict__ lambda,
-                           int pd_stride, double *__restrict__ Kout, double *__restrict__ kout,
-                           double *__restrict__ delta_J, int *__restrict__ status, const int *__restrict__ gate, const int *__restrict__ list)
-{
-    const int b = kp_block_traj(list, blockIdx.x);
-    if (gate[b] == 0) return;
-    backward_body<N, M, 0>(L, T, rec, lambda, pd_stride, Kout, kout, delta_J, status, b);
+    const int b = GATED ? kp_block_traj(list, blockIdx.x) : (int)blockIdx.x;
+    if constexpr (GATED) { if (gate[b] == 0) return; }
+    backward_body<N, M, ABL>(L, T, rec, lambda, pd_stride, Kout, kout, delta_J, status, b);
 }
 
 bool backward_mfma_supported(int n, int m)
@@ -408,16 +379,11 @@ bool backward_mfma_supported(int n, int m)
 template <int NN, int MM>
 static hipError_t launch_bm(Ctx *c, int pd_stride)
 {
-    if (c->bwd_gate) {
-        const auto twin = c->d.batch <= c->n_simd ? k_backward_mfma_excl_retry<NN, MM> : k_backward_mfma_retry<NN, MM>;
-        hipLaunchKernelGGL(twin, dim3(c->d.batch), dim3(64), 0, c->stream, c->L, c->d.T, c->rec, c->lambda, pd_stride, c->K, c->k,
-                           c->delta_J, c->status, c->bwd_gate, c->sweep_list);
+    return kp_with_flags(c->d.batch <= c->n_simd, c->bwd_gate != nullptr, [&](auto excl, auto gated) {
+        hipLaunchKernelGGL((k_backward_mfma<NN, MM, 0, excl(), gated()>), dim3(c->d.batch), dim3(64), 0, c->stream, c->L, c->d.T, c->rec,
+                           c->lambda, pd_stride, c->K, c->k, c->delta_J, c->status, c->bwd_gate, c->sweep_list);
         return hipGetLastError();
-    }
-    const auto kernel = c->d.batch <= c->n_simd ? k_backward_mfma_excl<NN, MM> : k_backward_mfma<NN, MM>;
-    hipLaunchKernelGGL(kernel, dim3(c->d.batch), dim3(64), 0, c->stream, c->L, c->d.T, c->rec, c->lambda, pd_stride, c->K, c->k,
-                       c->delta_J, c->status);
-    return hipGetLastError();
+    });
 }
 
 hipError_t launch_backward_mfma(Ctx *c, int pd_stride)
