@@ -296,6 +296,80 @@ template <int R> __device__ __forceinline__ void fset_reg(d4 &v, double x) { if 
 #define FPC_SIDE_QZZ (FPC_SIDE_QUZ + 256)
 __device__ __forceinline__ d4 lds_tile4(const double *t, int lane);
 __device__ __forceinline__ void lds_store4(double *t, int lane, const d4 &v);
+// Quu + lambda I is not PD on an unchecked step: the pivoted inverse (one lane, kp_slow_ldlt_inverse) times Quz, as gains with their
+// sign -- the tail of the inlined factorisation block of backward_fused_body, for the form whose factorisation is out of line.
+template <int M>
+__device__ __forceinline__ d4 kp_pivoted_gains(double *sh, int m_rt, int lane)
+{
+    constexpr int m = M;
+    const int c = lane & 15, q = lane >> 4;
+    double *wa = sh + FLDS_SLOW, *wx = wa + 256, *wt = wx + 256;
+    int *tr = (int *)(wt + 16);
+    if (lane == 0) kp_slow_ldlt_inverse(m_rt, sh + FLDS_Q, FMS, wa, wx, wt, tr);
+    __builtin_amdgcn_wave_barrier();
+    double x[M];
+#pragma unroll
+    for (int i = 0; i < M; i++) {
+        double sacc = 0.0;
+#pragma unroll
+        for (int p = 0; p < M; p++) sacc += (-wx[i + p * m]) * sh[FLDS_Z + c * FMZ + p];
+        x[i] = -sacc;
+    }
+    __builtin_amdgcn_wave_barrier();
+    double xr[4] = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+    for (int i = 0; i < M; i++)
+        if (q == (i & 3)) xr[i >> 2] = x[i];
+    d4 Kp;
+    Kp.x = -xr[0]; Kp.y = -xr[1]; Kp.z = -xr[2]; Kp.w = -xr[3];
+    return Kp;
+}
+
+// The factorisation path of a step of the uniform one-wave sweep (the first step, checked steps, re-seeds: 1 % of the steps at the
+// bench's pd_stride), OUT OF LINE: inlined, its ~100 live registers (Lm[M][M], rd, x, y) met the refreshed path at the join in front of
+// the gains product, and the allocator parked Quz / Qr of EVERY refreshed step in AGPRs to make room for a branch that step does not
+// take.  noinline like kp_slow_ldlt_inverse: what the rare path needs is saved and restored around the call, on the rare path.
+// In: the LDS image of the step, Qr = Quu + lambda I at FLDS_Q and Quz' at FLDS_Z (written by the caller, wave barrier behind it).
+// Out, in registers (2 NCU doubles and a word: a by-value aggregate of up to 16 registers comes back in VGPRs, a larger one through
+// scratch): the lane's rows of the gains column with its sign, of the NEGATED inverse column, and the verdict.  A LEAF: the pivoted
+// slow path stays with the caller (a call in here would have the return address saved in scratch).  The statements are the inlined
+// block's, one for one: same arithmetic in the same order, same bits.
+enum { KP_FACTOR_NOT_PD = 0, KP_FACTOR_SEEDED = 1, KP_FACTOR_INDEFINITE = 2 };   // checked step failed (:587-595) | LDL', Xinv seeded | unchecked, not PD: pivot
+template <int NCU> struct FactorOut { double Kp[NCU], Xinv[NCU]; int verdict; };
+template <int M>
+__device__ static __attribute__((noinline)) FactorOut<(M + 3) / 4> kp_factor_path(const double *sh, int lane, bool check_pd)
+{
+    constexpr int m = M, NCU = (M + 3) / 4;
+    static_assert(2 * 2 * NCU + 1 <= 16, "FactorOut must come back in registers");
+    const int c = lane & 15, q = lane >> 4;
+    FactorOut<NCU> o;
+#pragma unroll
+    for (int r = 0; r < NCU; r++) { o.Kp[r] = 0.0; o.Xinv[r] = 0.0; }
+    // ---- unpivoted LDL' of Quu + lambda I, redundantly in every lane ----
+    double Lm[M][M], rd[M];
+    const bool pos = kp_ldl_factor<M>([&](int i, int j) { return sh[FLDS_Q + i * FMS + j]; }, Lm, rd);
+    o.verdict = pos ? KP_FACTOR_SEEDED : check_pd ? KP_FACTOR_NOT_PD : KP_FACTOR_INDEFINITE;
+    if (!pos) return o;
+    double x[M];
+#pragma unroll
+    for (int i = 0; i < M; i++) x[i] = sh[FLDS_Z + c * FMZ + i];
+    kp_ldl_solve<M>(Lm, rd, x);
+    // seed the fast path: column c of the inverse in lane c (c < m), as a tile
+    double y[M];
+#pragma unroll
+    for (int i = 0; i < M; i++) y[i] = (i == c) ? 1.0 : 0.0;
+    kp_ldl_solve<M>(Lm, rd, y);
+    double yr[NCU], xr[NCU];
+#pragma unroll
+    for (int r = 0; r < NCU; r++) { yr[r] = 0.0; xr[r] = 0.0; }
+#pragma unroll
+    for (int i = 0; i < M; i++)
+        if (q == (i & 3)) { yr[i >> 2] = (c < m) ? y[i] : 0.0; xr[i >> 2] = x[i]; }
+#pragma unroll
+    for (int r = 0; r < NCU; r++) { o.Xinv[r] = -yr[r]; o.Kp[r] = -xr[r]; }       // the running inverse is kept negated
+    return o;
+}
+
 // RU0: the context's r_u buffer was never written (a task without control residuals: r_u = 0, e.g. reaching,
 // src/ModelTranslator/Reaching.cpp:43-54), so [l_uu | l_u] = Ru' W [Ru | r] is exactly zero: the product and the r_u loads
 // are left out (4 of the step's 40 MFMAs).
@@ -835,6 +909,26 @@ __device__ __forceinline__ void backward_fused_body(double *sh, const double *pc
             if (NCU > 2) sh[FLDS_Z + c * FMZ + 8 + q] = Quz.z;
             if (NCU > 3) sh[FLDS_Z + c * FMZ + 12 + q] = Quz.w;
             wsync();
+            if constexpr (UNI && !PC) {                // out of line: the refreshed path keeps its registers (kp_factor_path)
+                const FactorOut<NCU> fo = kp_factor_path<M>(sh, lane, check_pd);
+                // every lane factorises the same broadcast image: one verdict.  Inlined, the compiler saw that (loads at a uniform
+                // address); a value back from a call is per-lane to it, and through haveX every branch of the step became an EXEC-mask
+                // region (4.61 against 4.00 ms).  Said here instead.
+                const int verdict = __builtin_amdgcn_readfirstlane(fo.verdict);
+                if (verdict == KP_FACTOR_NOT_PD) { fail = t + 1; return false; }
+                if (check_pd) pd_counter = 0;
+                haveX = verdict == KP_FACTOR_SEEDED;
+                if (haveX) {
+                    double kr[4] = {-0.0, -0.0, -0.0, -0.0}, yr[4] = {-0.0, -0.0, -0.0, -0.0};     // (rows behind NCU: as the negated zeros of the inlined form)
+#pragma unroll
+                    for (int r = 0; r < NCU; r++) { kr[r] = fo.Kp[r]; yr[r] = fo.Xinv[r]; }
+                    Kp.x = kr[0]; Kp.y = kr[1]; Kp.z = kr[2]; Kp.w = kr[3];
+                    Xinv.x = yr[0]; Xinv.y = yr[1]; Xinv.z = yr[2]; Xinv.w = yr[3];
+                    Xprev = Xinv;
+                } else {
+                    Kp = kp_pivoted_gains<M>(sh, L.m, lane);
+                }
+            } else {
             // ---- unpivoted LDL' of Quu + lambda I, redundantly in every lane ----
             double Lm[M][M], rd[M];
             const bool pos = kp_ldl_factor<M>([&](int i, int j) { return sh[FLDS_Q + i * FMS + j]; }, Lm, rd);
@@ -885,6 +979,7 @@ __device__ __forceinline__ void backward_fused_body(double *sh, const double *pc
             for (int i = 0; i < M; i++)
                 if (q == (i & 3)) xr[i >> 2] = x[i];
             Kp.x = -xr[0]; Kp.y = -xr[1]; Kp.z = -xr[2]; Kp.w = -xr[3];
+            }
         }
         if constexpr (!PC) { Kst = Kp; tst = t; }
         else store_gains(t, Kp);
