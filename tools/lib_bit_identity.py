@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""lib_bit_identity.py LIB_A LIB_B [--batch 1024] [--T 3000]: do two builds of libkpilqr.so compute the same BITS?  (GPU box)
+"""lib_bit_identity.py LIB_A LIB_B [--batch 1024] [--T 3000] [--max-rel]: do two builds of libkpilqr.so compute the same BITS?  (GPU box)
 
 For a change that is meant to move no arithmetic (register and control-flow work in a sweep).  Each library runs in a process of its
 own (KPILQR_LIB is read when the package is imported) on the same workload -- bench.py's distinct seeds, Panda reaching, key-points
@@ -10,19 +10,24 @@ every 5 steps, from KPILQR_WORKLOAD_CACHE if set -- one backward sweep at the be
 and leaves SHA-256 digests of the bytes of K, k, delta_J, status and cost_pred of the WHOLE batch (K alone is 2.4 GB at the headline:
 only digests leave the process) together with the form the library launched.  Equal digests are equal arrays, bit for bit -- the
 comparison is stricter than np.array_equal only in that it tells -0.0 from 0.0 and one NaN payload from another.
-Exit status 1 if any digest differs."""
+Exit status 1 if any digest differs.
+
+--max-rel (for a change that re-orders a sum; use a batch whose arrays fit beside each other, e.g. --batch 64): the arrays are KEPT
+(.npy in a temporary directory) and the worst relative difference of every array, max |A - B| / max |A|, is printed beside the digests;
+status must still be equal.  Exit status 1 if a status differs or a figure is not finite."""
 import argparse
 import hashlib
 import json
 import os
 import subprocess
 import sys
+import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = ("K", "k", "delta_J", "status", "cost_pred")
 
 
-def child(batch, T):
+def child(batch, T, keep=None):
     sys.path.insert(0, ROOT)
     import numpy as np
     import bench
@@ -39,6 +44,8 @@ def child(batch, T):
             cost = eng.forward_linear(np.array([(i / 6.0) ** 2 for i in range(1, 7)]))
         arrays = dict(zip(NAMES, (K, k, np.asarray(dJ, np.float64), np.asarray(st, np.int32), np.asarray(cost, np.float64))))
         out[leg] = {"backward": launched, "valid": int((np.asarray(st) == 0).sum()), **{n: digest(a) for n, a in arrays.items()}}
+        if keep:
+            for n, a in arrays.items(): np.save(os.path.join(keep, "%s_%s.npy" % (leg, n)), a)
         del K, k
     print("DIGESTS " + json.dumps(out))
 
@@ -49,12 +56,19 @@ def main():
     ap.add_argument("--batch", type=int, default=1024)
     ap.add_argument("--T", type=int, default=3000)
     ap.add_argument("--child", action="store_true")
+    ap.add_argument("--max-rel", action="store_true")
+    ap.add_argument("--keep", default=None)
     args = ap.parse_args()
-    if args.child: return child(args.batch, args.T)
+    if args.child: return child(args.batch, args.T, args.keep)
     if len(args.libs) != 2: sys.exit(__doc__)
     got = []
-    for lib in args.libs:
-        r = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", "--batch", str(args.batch), "--T", str(args.T)],
+    tmp = tempfile.TemporaryDirectory() if args.max_rel else None
+    for i, lib in enumerate(args.libs):
+        keep = []
+        if tmp:
+            os.mkdir(os.path.join(tmp.name, "AB"[i]))
+            keep = ["--keep", os.path.join(tmp.name, "AB"[i])]
+        r = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", "--batch", str(args.batch), "--T", str(args.T)] + keep,
                            env=dict(os.environ, KPILQR_LIB=os.path.abspath(lib)), capture_output=True, text=True)
         line = next((l for l in r.stdout.splitlines() if l.startswith("DIGESTS ")), None)
         if r.returncode or line is None:
@@ -69,6 +83,21 @@ def main():
         print("  %-8s A %s | B %s; valid backward passes %d | %d" % (leg, a["backward"], b["backward"], a["valid"], b["valid"]))
         for n in NAMES: print("    %-9s %s  %s" % (n, a[n][:16], "identical" if a[n] == b[n] else "DIFFERS (B: %s)" % b[n][:16]))
     print("verdict: " + ("every array of every leg is bit-identical" if not bad else "%d arrays or forms differ" % bad))
+    if tmp:
+        import numpy as np
+        worst, ok = 0.0, True
+        for leg in got[0]:
+            for n in NAMES:
+                a, b = (np.load(os.path.join(tmp.name, d, "%s_%s.npy" % (leg, n))) for d in "AB")
+                if n == "status":
+                    ok = ok and bool(np.array_equal(a, b))
+                    print("  %-8s %-9s %s" % (leg, n, "equal" if np.array_equal(a, b) else "DIFFERS"))
+                    continue
+                rel = float(np.max(np.abs(a - b)) / max(float(np.max(np.abs(a))), 1e-300))
+                worst, ok = max(worst, rel), ok and bool(np.isfinite(rel))
+                print("  %-8s %-9s max |A - B| / max |A| = %.3e" % (leg, n, rel))
+        print("worst relative difference %.3e" % worst)
+        return 0 if ok else 1
     return 1 if bad else 0
 
 

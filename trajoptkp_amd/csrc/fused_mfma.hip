@@ -401,6 +401,19 @@ __device__ __forceinline__ void backward_fused_body(double *sh, const double *pc
     constexpr int NCZ = (N + 1 + 3) / 4;
     constexpr int NCU = (M + 3) / 4;
     constexpr int n = N, m = M;
+    // HEADS (uniform one-wave sweeps): the rows behind 4 NCU of the running inverses and of the gains are not state -- Xh, Xq, Ksh are
+    // the NCU live registers of Xinv, Xprev, Kst, and N0t is the tile whose head takes the extrapolated first guess of every step
+    // (kp_inverse_refresh_heads); its zero tail is written here, once (opaque to the compiler, which would otherwise rebuild the tile
+    // from a literal zero on every step).
+    constexpr bool HEADS = UNI && !PC;
+    double Xh[NCU], Xq[NCU], Ksh[NCU];
+    double N0t[2] = {0.0, 0.0};
+#pragma unroll
+    for (int r = 0; r < NCU; r++) { Xh[r] = 0.0; Xq[r] = 0.0; Ksh[r] = 0.0; }
+    // (Declared up here, in front of everything else: further down, beside the running inverse, these dead locals of the other forms
+    // changed the order of the set-up code of the wave pairs' consumer -- two register pairs swapped in kernels that are not touched.
+    // The tail is made opaque below, behind the set-up: see there.)
+    (void)Xh; (void)Xq; (void)Ksh; (void)N0t;
     // one wavefront per workgroup (or the consumer wave of a group): its LDS operations execute in order, so a write ->
     // transposed read pair needs the compiler's ordering only (4.94 -> 4.87 ms against __syncthreads() in the one-wave forms).
     // (Tried: the transposed half requested at the end of a step and averaged in front of the next step's first Riccati
@@ -599,9 +612,16 @@ __device__ __forceinline__ void backward_fused_body(double *sh, const double *pc
         }
     }
     const bool lo8 = c < 8;
-    const double dbl8 = lo8 ? 1.0 : 2.0;
-    const u64 mask_hi8 = lo8 ? 0ull : ~0ull;
-    (void)lo8; (void)dbl8; (void)mask_hi8;
+    (void)lo8;
+    // PACKQ, the merge: the cost block Lzz joins the merged tile of V' = Qm + K'G by FMAs on per-lane constants instead of riding in the
+    // initial values of the D products, and the tile is formed HALVED, so that V = acc + acc' below needs no 0.5:
+    //     Qm/2 = f o D + L/2,     f = 1/2 in the blocks (rows, cols) < 8 and >= 8, 1 in rows < 8 x cols >= 8 (it stands for its never
+    //     computed mirror image too), 0 in that mirror image; L/2 is the whole symmetric cost block halved (its two halves add up).
+    // The 0 factor needs a finite D there: that block of D2 is a product of the same finite operands as the blocks that are read.
+    // Halving is exact (a power of two; V' of a sweep is nowhere near 2^-1021, where the halves of normal numbers stop being exact).
+    const double f_lo = lo8 ? 0.5 : 1.0, f_hi = lo8 ? 0.0 : 0.5;
+    const d4 Cxxh = {0.5 * Cxx.x, 0.5 * Cxx.y, 0.5 * Cxx.z, 0.5 * Cxx.w};
+    (void)f_lo; (void)f_hi; (void)Cxxh;
     int up = KpU - 1;                                          // UNI: position (in every list) of the current segment's start
     int us = T, unb = T - 1, unb_v = T - 1;                    // UNI: its time, and the time of the next start (uniform; unb_v: as loaded)
     (void)up; (void)us; (void)unb; (void)unb_v; (void)cu; (void)cr;
@@ -644,9 +664,15 @@ __device__ __forceinline__ void backward_fused_body(double *sh, const double *pc
     } else {
         __syncthreads();                               // the producer has published step T-1
     }
+    // HEADS: the tail of the first-guess tile becomes opaque HERE, behind the set-up.  In front of it (beside the declarations) the
+    // statement made the compiler treat the set-up's descriptors (E0, rT) as per-lane values in the job-list (kpc) forms: a
+    // readfirstlane loop around every crossing's loads (tools/isa_lint.py: waterfall loops).
+    if constexpr (HEADS) asm volatile("" : "+v"(N0t[0]), "+v"(N0t[1]));
     const d4 zero = {0.0, 0.0, 0.0, 0.0};
     d4 V = zero, accp = zero;                                  // accp (PC): V' of the step before, not yet symmetrised
     (void)accp;
+    // (PACKQ: behind the terminal step W2 holds HALF the running weights -- the cost block of the merge is formed halved -- and the
+    // [l_uu | l_u] product of a sweep with control residuals doubles it back, exactly.  Every other form: the running weights.)
     d4 W2 = {w2term[0], w2term[1], w2term[2], w2term[3]};     // terminal weights at t = T-1, running after
     int pd_counter = 0, fail = 0;
     double dJ = 0.0;
@@ -689,6 +715,8 @@ __device__ __forceinline__ void backward_fused_body(double *sh, const double *pc
         const unsigned long long cyc_s0 = __builtin_readcyclecounter();
 #endif
         d4 Fz, Fu, Lzz, LU;
+        d4 Lh = zero;                                  // PACKQ: Lzz / 2
+        (void)Lh;
         d4 Y1 = zero;                                  // PACKQ: the packed tile of slot a
         (void)Y1;
         const bool term = decltype(may_be_first)::value && (t == T - 1);
@@ -765,9 +793,11 @@ __device__ __forceinline__ void backward_fused_body(double *sh, const double *pc
                 p = __builtin_fma(RxW.y, cur.R1.y, p); p = __builtin_fma(RxW.z, cur.R1.z, p); p = __builtin_fma(RxW.w, cur.R1.w, p);
                 if constexpr (PACKQ) {
                     // packed Q products (below): of row n the merged Qzz tile keeps columns 8.. only, so v goes into COLUMN n instead
-                    // (p as the first operand: D(i, n) = sum_q p(i, q)) -- once in rows 0..7, which are doubled with their block, twice in
-                    // rows 8..; ((2 v) + 0)/2 is exact either way.  Still one product, up here off the Riccati chain.
-                    Lzz = MFMA(p * dbl8, en1, Cxx);
+                    // (p as the first operand: D(i, n) = sum_q p(i, q)), once, on the halved constant block: (L/2)(i, n) = v(i),
+                    // (L/2)(n, i) = 0, and their sum is l_x.  Still one product, up here off the Riccati chain.  (Tried: the product behind
+                    // the merge, C = the merged tile, so that only the lane sums live across the top of the step -- it lost:
+                    // it sits in the chain in front of the refresh, profiles/inner_step_moves_ab.txt.)
+                    Lzz = MFMA(p, en1, Cxxh);
                 }
                 else Lzz = MFMA(en2, p, Cxx);
             }
@@ -777,17 +807,29 @@ __device__ __forceinline__ void backward_fused_body(double *sh, const double *pc
         Rz.z = bits_or(cur.Rx.z, cur.R1.z); Rz.w = bits_or(cur.Rx.w, cur.R1.w);
         Lzz = PR(Rz, Rz * W2, zero, ncr);
         }
+        if constexpr (PACKQ) {
+            // the halved cost block of the merge.  A sweep's first step wants Lzz whole as well (V = Lzz): halved there, by four
+            // multiplies on that one step; below it the tile is formed halved (Cxxh; W2 holds the halved running weights).
+            if (term) { Lh.x = 0.5 * Lzz.x; Lh.y = 0.5 * Lzz.y; Lh.z = 0.5 * Lzz.z; Lh.w = 0.5 * Lzz.w; }
+            else Lh = Lzz;
+        }
         if constexpr (RU0) {
             LU = zero;
         } else {
             d4 Rur;
             Rur.x = bits_or(cur.Ru.x, cur.R1.x); Rur.y = bits_or(cur.Ru.y, cur.R1.y);
             Rur.z = bits_or(cur.Ru.z, cur.R1.z); Rur.w = bits_or(cur.Ru.w, cur.R1.w);
-            LU = PR(cur.Ru, Rur * W2, zero, ncr);
+            if (PACKQ && !term) LU = PR(cur.Ru, Rur * (W2 + W2), zero, ncr);      // ([l_uu | l_u] under the whole running weights)
+            else LU = PR(cur.Ru, Rur * W2, zero, ncr);
         }
         __builtin_amdgcn_sched_barrier(0);
         // the step above, IN FRONT of the requests.  (The test is false only at the first step; compiling it out of the loops'
         // call sites was measured and is 0.04 ms SLOWER at B=1024 -- the scheduler's placement of the stores changes.)
+        if constexpr (HEADS) {
+            d4 Ka = zero;
+            Ka.x = Ksh[0]; if constexpr (NCU > 1) Ka.y = Ksh[1];
+            if (tst >= 0) store_gains(tst, Ka);
+        } else
         if (tst >= 0) store_gains(tst, Kst);
         if constexpr (!UNI) {
             if (cross) {                               // late_cross: the memory operations of the crossing at the top of this step
@@ -826,6 +868,7 @@ __device__ __forceinline__ void backward_fused_body(double *sh, const double *pc
         if (term) {                                     // V_x = l_x[T-1]; V_xx = l_xx[T-1]   (iLQR.cpp:537-539)
             V = Lzz;
             W2.x = w2run[0]; W2.y = w2run[1]; W2.z = w2run[2]; W2.w = w2run[3];
+            if constexpr (PACKQ) { W2.x *= 0.5; W2.y *= 0.5; W2.z *= 0.5; W2.w *= 0.5; }       // (Lzz / 2 of the steps below: see Lh)
         }
         pd_counter++;
         const bool check_pd = pd_counter >= pd_stride;
@@ -846,13 +889,18 @@ __device__ __forceinline__ void backward_fused_body(double *sh, const double *pc
             // rows >= 8 of the residual, which NCU = 2 never reads, and the LDL' path reads elements (i, j) < m.
             const d4 T2 = PS<NCZ>(V, Fu, zero);          // (first: the per-lane pick of Fz lands under it)
             const d4 Tz = PS<NCZ>(V, Fz, zero);
-            const d4 i2 = {Luu.x + LamI.x, Luu.y + LamI.y, Lzz.z, Lzz.w};
-            const d4 i1 = {Lzz.x, Lzz.y, Luz.x, Luz.y};
+            // Lzz enters nothing but V' (Luz, Luu are rows < m of the u-block): it joins at the merge, and the accumulators start from
+            // what the gains need -- without control residuals the resident lambda I (its rows 8.. are zero: m <= 8) and literal zero:
+            // no register is moved to assemble a C operand
+            d4 i2 = LamI, i1 = zero;
+            if constexpr (!RU0) { i2.x = Luu.x + LamI.x; i2.y = Luu.y + LamI.y; i1.z = Luz.x; i1.w = Luz.y; }
             const d4 D2 = PS<NCZ>(Fu, T2, i2);
             const d4 D1 = PS<NCZ>(Y1, Tz, i1);
             Qr = D2;
             Quz.x = D1.z; Quz.y = D1.w; Quz.z = 0.0; Quz.w = 0.0;
-            Qzz.x = D1.x; Qzz.y = D1.y; Qzz.z = D2.z; Qzz.w = D2.w;          // (merged behind the gains, below)
+            // the merge (f_lo, f_hi above): four FMAs on constants, Qm / 2
+            Qzz.x = __builtin_fma(D1.x, f_lo, Lh.x); Qzz.y = __builtin_fma(D1.y, f_lo, Lh.y);
+            Qzz.z = __builtin_fma(D2.z, f_hi, Lh.z); Qzz.w = __builtin_fma(D2.w, f_hi, Lh.w);
         } else {
         const d4 Tu = PS<NCZ>(V, Fu, zero);
         Qr = PS<NCZ>(Fu, Tu, PC ? Luu : Luu + LamI);          // Quu (+ lambda I)
@@ -883,7 +931,9 @@ __device__ __forceinline__ void backward_fused_body(double *sh, const double *pc
         // (segment-loop forms: the peeled step is the one right below a key-point -- known at compile time; which steps are peeled,
         // the re-seed below and its Xprev = Xinv are mirrored in tests/_refresh.py)
         constexpr bool KINK = UNI && !PC && decltype(may_be_first)::value;
-        const bool refreshed = haveX && !check_pd && kp_inverse_refresh_n<NCU, KINK, PC>(Qr, Iu, Xinv, Xprev, m, STATS ? &ns_steps : nullptr);    // Xinv, Xprev: NEGATED inverses
+        bool refreshed;                                 // Xinv, Xprev (HEADS: Xh, Xq): NEGATED inverses
+        if constexpr (HEADS) refreshed = haveX && !check_pd && kp_inverse_refresh_heads<NCU, KINK>(Qr, Iu, N0t, Xh, Xq, m, STATS ? &ns_steps : nullptr);
+        else refreshed = haveX && !check_pd && kp_inverse_refresh_n<NCU, KINK, PC>(Qr, Iu, Xinv, Xprev, m, STATS ? &ns_steps : nullptr);
         if constexpr (STATS) { if (refreshed) hcnt[ns_steps < 0 ? 0 : ns_steps > 3 ? 3 : ns_steps]++; }
         if constexpr (PC) {                           // mid-step barrier of the pair: Quz, Qzz are published
             __syncthreads();
@@ -896,7 +946,9 @@ __device__ __forceinline__ void backward_fused_body(double *sh, const double *pc
 #endif
         d4 Kp = zero;                                 // the gains -X
         if (refreshed) {
-            Kp = PS<NCU>(Xinv, Quz, zero);               // -(Quu + lambda I)^-1 Quz: the gains, with their sign
+            d4 Xa = Xinv;
+            if constexpr (HEADS) { Xa = zero; Xa.x = Xh[0]; if constexpr (NCU > 1) Xa.y = Xh[1]; }     // (the product reads the NCU heads)
+            Kp = PS<NCU>(Xa, Quz, zero);                 // -(Quu + lambda I)^-1 Quz: the gains, with their sign
             done = true;
         }
         if (!done) {
@@ -923,8 +975,13 @@ __device__ __forceinline__ void backward_fused_body(double *sh, const double *pc
 #pragma unroll
                     for (int r = 0; r < NCU; r++) { kr[r] = fo.Kp[r]; yr[r] = fo.Xinv[r]; }
                     Kp.x = kr[0]; Kp.y = kr[1]; Kp.z = kr[2]; Kp.w = kr[3];
+                    if constexpr (HEADS) {
+#pragma unroll
+                        for (int r = 0; r < NCU; r++) { Xh[r] = fo.Xinv[r]; Xq[r] = fo.Xinv[r]; }      // re-seed: heads only
+                    } else {
                     Xinv.x = yr[0]; Xinv.y = yr[1]; Xinv.z = yr[2]; Xinv.w = yr[3];
                     Xprev = Xinv;
+                    }
                 } else {
                     Kp = kp_pivoted_gains<M>(sh, L.m, lane);
                 }
@@ -981,7 +1038,8 @@ __device__ __forceinline__ void backward_fused_body(double *sh, const double *pc
             Kp.x = -xr[0]; Kp.y = -xr[1]; Kp.z = -xr[2]; Kp.w = -xr[3];
             }
         }
-        if constexpr (!PC) { Kst = Kp; tst = t; }
+        if constexpr (HEADS) { Ksh[0] = Kp.x; if constexpr (NCU > 1) Ksh[1] = Kp.y; tst = t; }
+        else if constexpr (!PC) { Kst = Kp; tst = t; }
         else store_gains(t, Kp);
         // delta_J += k'Q_u + k'Q_uu k = -lambda k'k (:612-613): lanes of column n keep the squares of their rows,
         // the four row groups are added once after the sweep
@@ -993,16 +1051,16 @@ __device__ __forceinline__ void backward_fused_body(double *sh, const double *pc
         if (NCU > 3) dJ = __builtin_fma(Kp.w, Kp.w, dJ);
         // V' = Qzz + K'Quu K + K'Quz + Quz'K (:606-607) with K = -X, (Quu + lambda I) X = Quz:
         //    = Qzz - X'(Quz + lambda X) = Qzz + K'(Quz - lambda K)   -- one product; G = (Quu + 2 lambda I)K' is never formed
-        if constexpr (PACKQ) {
-            // merged tile for V' = Qm + K'G: the block rows 8..n x cols 0..7 is never computed, its mirror image counts twice (exact)
-            // -- (acc + acc')/2 below gives every entry of V what it was, up to the summation order of that block.  Down here, off the
-            // chain Quu -> inverse -> gains, while the gains' product lands.
-            Qzz.x *= dbl8; Qzz.y *= dbl8;
-            Qzz.z = bits_and(Qzz.z, mask_hi8); Qzz.w = bits_and(Qzz.w, mask_hi8);
-        }
+        // (PACKQ: Qzz is the merged tile Qm / 2 -- the block rows 8..n x cols 0..7 is never computed, its mirror image counts twice -- and
+        // acc + acc' below gives every entry of V what it was, up to the summation order)
         d4 G;
+        if constexpr (PACKQ) {                           // G / 2 for the halved tile: NCU = 2 registers enter the product
+            G.x = __builtin_fma(-0.5 * lam, Kp.x, 0.5 * Quz.x); G.y = __builtin_fma(-0.5 * lam, Kp.y, 0.5 * Quz.y);
+            G.z = 0.0; G.w = 0.0;
+        } else {
         G.x = __builtin_fma(-lam, Kp.x, Quz.x); G.y = __builtin_fma(-lam, Kp.y, Quz.y);
         G.z = __builtin_fma(-lam, Kp.z, Quz.z); G.w = __builtin_fma(-lam, Kp.w, Quz.w);
+        }
         d4 acc = PS<NCU>(Kp, G, Qzz);
 #ifdef KP_CYC
         asm volatile("" :: "v"(acc.x));
@@ -1017,10 +1075,17 @@ __device__ __forceinline__ void backward_fused_body(double *sh, const double *pc
             accp = acc;                                // symmetrised at the top of the next step, by this wave and by the helper wave
         } else {
             wsync();
+            if constexpr (PACKQ) {                     // acc is V' / 2
+                V.x = acc.x + sh[FLDS_V + c * FVS + q];
+                V.y = acc.y + sh[FLDS_V + c * FVS + 4 + q];
+                V.z = acc.z + sh[FLDS_V + c * FVS + 8 + q];
+                V.w = acc.w + sh[FLDS_V + c * FVS + 12 + q];
+            } else {
             V.x = 0.5 * (acc.x + sh[FLDS_V + c * FVS + q]);
             V.y = 0.5 * (acc.y + sh[FLDS_V + c * FVS + 4 + q]);
             V.z = 0.5 * (acc.z + sh[FLDS_V + c * FVS + 8 + q]);
             V.w = 0.5 * (acc.w + sh[FLDS_V + c * FVS + 12 + q]);
+            }
             if (lane_nn) fset_reg<REG_NN>(V, 0.0);
         }
         if (PC) __syncthreads();                       // end of step: the ring slot is free, the next one is full
@@ -1111,6 +1176,7 @@ __device__ __forceinline__ void backward_fused_body(double *sh, const double *pc
         if (step(T - 1, std::true_type{}))
             for (int t = T - 2; t >= 0; t--) if (!step(t, std::false_type{})) break;
     }
+    if constexpr (HEADS) { Kst.x = Ksh[0]; if constexpr (NCU > 1) Kst.y = Ksh[1]; }      // (heads of the last completed step)
     if constexpr (!PC) { if (tst >= 0) store_gains(tst, Kst); }      // the last completed step
     dJ *= -lam;
     dJ += __shfl_xor(dJ, 16);

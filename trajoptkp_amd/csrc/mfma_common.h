@@ -186,6 +186,47 @@ __device__ __forceinline__ bool kp_inverse_refresh_n(const d4 &Qr, const d4 &Iu,
     return true;
 }
 
+// kp_inverse_refresh_n for the uniform one-wave sweeps, with the state a sweep really carries: rows behind 4 NCU of the m x m inverse
+// are structural zeros, so the running inverse and the one before it are their NCU live registers (Nh, Np) and the first guess is
+// written into the head of N0, a tile that lives across the steps for nothing else and whose tail the caller zeroed once.  N0 is the
+// accumulator input of the series products, which write elsewhere: its tail is never written.  Same products and FMAs in the same
+// order as kp_inverse_refresh_n: same bits in the heads (the tails never entered a head: row i of a product is row i of its inputs).
+template <int NCU, bool KINK>
+__device__ __forceinline__ bool kp_inverse_refresh_heads(const d4 &Qr, const d4 &Iu, double (&Nt)[2], double (&Nh)[NCU], double (&Np)[NCU], int m, int *steps = nullptr)
+{
+    static_assert(NCU <= 2, "heads: one or two live registers");
+    if (steps) *steps = 0;
+    d4 N0;
+    N0.x = __builtin_fma(2.0, Nh[0], -Np[0]);
+    if constexpr (NCU > 1) N0.y = __builtin_fma(2.0, Nh[1], -Np[1]); else N0.y = Nt[0];
+    N0.z = Nt[0]; N0.w = Nt[1];
+    // (no instruction: the tile stays ONE value carried from step to step in the compiler's eyes.  Left to see that every step overwrites
+    // the head, it keeps the tile of the set-up aside and copies all of it in front of every series.)
+    d4 R = kp_P<NCU>(Qr, N0, Iu);                     // I + Q N0
+    d4 Y = kp_P<NCU>(N0, R, N0);
+    Y = kp_P<NCU>(Y, R, N0);
+    if constexpr (KINK) Y = kp_P<NCU>(Y, R, N0);      // N0 (I + R + R^2 + R^3)
+    asm volatile("" :: "v"(N0));                      // (see above: N0 outlives the series)
+    double rmax = fabs(R.x);
+    if constexpr (NCU > 1) rmax = fmax(rmax, fabs(R.y));
+    const double e = (double)m * rmax;
+    // (thresholds, series terms and step counts: kp_inverse_refresh_n's, families "n" and "n_kink" of tests/_refresh.py)
+    if (__builtin_amdgcn_ballot_w64(!(e < (KINK ? 1.7e-4 : 2.0e-5))) != 0) {
+        if (__builtin_amdgcn_ballot_w64(!(e < 0.11)) != 0) { if (steps) *steps = -1; return false; }
+        const int iters = KINK ? ((__builtin_amdgcn_ballot_w64(e >= 1.3e-2) != 0) ? 2 : 1)
+                               : (__builtin_amdgcn_ballot_w64(e >= 1.3e-2) != 0) ? 3 : (__builtin_amdgcn_ballot_w64(e >= 1.7e-4) != 0) ? 2 : 1;
+        if (steps) *steps = iters;
+        R = kp_P<NCU>(Qr, Y, Iu); Y = kp_P<NCU>(Y, R, Y);
+        if (iters > 1) {
+            R = kp_P<NCU>(Qr, Y, Iu); Y = kp_P<NCU>(Y, R, Y);
+            if (iters > 2) { R = kp_P<NCU>(Qr, Y, Iu); Y = kp_P<NCU>(Y, R, Y); }
+        }
+    }
+    Np[0] = Nh[0]; Nh[0] = Y.x;
+    if constexpr (NCU > 1) { Np[1] = Nh[1]; Nh[1] = Y.y; }
+    return true;
+}
+
 // Unpivoted LDL' of an m x m SPD matrix, done redundantly by every lane from a broadcast image (`qel(i,j)` returns
 // element (i,j)): L (unit lower, strictly lower part stored) and the reciprocals of D.  Returns false when a pivot is
 // not positive -- the callers then report the PD failure (checked steps) or take the pivoted slow path.
