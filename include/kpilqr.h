@@ -215,7 +215,8 @@ int  kpilqr_set_keypoints(kpilqr_ctx *ctx, const int *kp_offsets, const int *kp_
  *
  * Out of scope: job-list payloads are not carried; the chunks of kpilqr_iterate_streamed are unchanged; nothing derived from the
  * payload stays valid across an update; and kpilqr_generate_keypoints places key-points for the whole batch only.  (Residuals,
- * nominal controls and step records of a subset: the calls further down, "partial re-linearisation, the rest".) */
+ * nominal controls and step records of a subset: the calls further down, "partial re-linearisation, the rest".)
+ * (since: kpilqr_generate_keypoints_partial places key-points for a listed subset -- "Key-point placement for a subset".) */
 int  kpilqr_update_keypoints(kpilqr_ctx *ctx, int count, const int *traj,
                              const int *kp_offsets /* [count*dof + 1], starts at 0 */, const int *kp_times);
 int  kpilqr_upload_fd_kp_partial(kpilqr_ctx *ctx, int count, const int *traj,
@@ -261,7 +262,8 @@ int  kpilqr_download_gains_partial(kpilqr_ctx *ctx, int count, const int *traj,
  * Out of scope: the sweeps still run over the whole batch; kpilqr_generate_keypoints and kpilqr_upload_states for a subset; keeping
  * the column store, slope store and union store of kept trajectories on a KPILQR_FLAG_FUSED context; kpilqr_iterate and
  * kpilqr_iterate_streamed (whole batch); job-list payloads carried across kpilqr_update_keypoints.
- * (since: kpilqr_backward_partial, kpilqr_forward_linear_partial and kpilqr_iterate_partial sweep a listed subset -- "Sweeps of a subset".) */
+ * (since: kpilqr_backward_partial, kpilqr_forward_linear_partial and kpilqr_iterate_partial sweep a listed subset -- "Sweeps of a subset".)
+ * (since: kpilqr_upload_states_partial and kpilqr_generate_keypoints_partial -- "Key-point placement for a subset".) */
 int  kpilqr_upload_residuals_partial(kpilqr_ctx *ctx, int count, const int *traj,
                                      const double *r, const double *r_x, const double *r_u);
 int  kpilqr_upload_nominal_partial(kpilqr_ctx *ctx, int count, const int *traj, const double *u_nom);
@@ -290,6 +292,54 @@ int  kpilqr_keypoint_error_test(kpilqr_ctx *ctx, int n, const int *intervals, in
 /* Reads the current per-DoF lists back (the host FD loop needs them): kp_offsets [batch*dof+1]; kp_times may be
  * NULL to query the size.  Returns the total number of entries (>= 0) or an error (< 0).  Synchronous. */
 int  kpilqr_get_keypoints(kpilqr_ctx *ctx, int *kp_offsets, int *kp_times, int times_capacity);
+
+/* ---- Key-point placement for a subset: states, placement and the new lists of a LIST of trajectories --------------------------
+ * Device placement and partial re-linearisation together: the trajectories whose step was accepted get new states and new lists
+ * placed on the device, and the by-entry payload of everybody else stays resident.  (count, traj) has the contract of the _partial
+ * family in all three calls: `traj` [count] strictly increasing and within [0, batch), else KPILQR_ERR_ARG and nothing is enqueued
+ * or changed; count = 0 is a no-op returning KPILQR_OK; a NULL context is KPILQR_ERR_ARG; not through a view of
+ * kpilqr_iterate_streamed's chunks (KPILQR_ERR_STATE, never allocates); each call orders itself behind a streamed iteration in
+ * flight.  KPILQR_VERSION is unchanged: detect the calls by their symbols.
+ *
+ * kpilqr_upload_states_partial: X [count][T][n], the listed trajectories' states COMPACT in `traj` order.  The rows go straight to
+ * their place in the states buffer (allocated on first use, as kpilqr_upload_states allocates it), one hipMemcpyAsync per run of
+ * adjacent trajectories: no staging buffer, no kernel.  The context keeps one host byte per trajectory that says whether its states
+ * were ever given: a whole kpilqr_upload_states sets all of them, kpilqr_resize clears them.
+ *
+ * kpilqr_generate_keypoints_partial takes the methods, argument checks and dof <= 64 bound of kpilqr_generate_keypoints
+ * ("iterative_error" is refused with the same message) and leaves the context exactly as kpilqr_update_keypoints(count, traj, lists)
+ * would, where `lists` are bit for bit what kpilqr_generate_keypoints with the same arguments and states places for the listed
+ * trajectories: the CSR merged, kept trajectories' times and by-entry payload moved to their new offsets in the second buffers, the
+ * listed ranges PENDING until kpilqr_upload_fd_kp_partial / kpilqr_upload_kp_columns[_f32]_partial fills them, the union lists
+ * invalid, the host mirror of the offsets valid.  The listed trajectories' flags are what the whole-batch placement sets: canonical,
+ * and uniform only for set_interval.  KPILQR_ERR_STATE: before any key-points exist; while ranges are pending after an earlier
+ * update; for a method other than set_interval when a listed trajectory never had states uploaded (the message names the first
+ * such trajectory).  A rejected call leaves the context as it was.
+ * How, and what it costs.  The placement kernel runs with `count` workgroups: workgroup i reads the states of trajectory traj[i]
+ * off the device copy of the list (the one kpilqr_fd_interpolate_partial uses), a scalar load, and writes bitmask and count rows i,
+ * compact.  The call then WAITS for ONE read-back of the count*dof counts -- the whole-batch call waits for its total -- so every
+ * size is known exactly and no worst-case count*dof*T reservation of list times is made; the compact offsets go back up, the
+ * bitmasks are expanded into the buffer kpilqr_update_keypoints uploads its caller's times to, and from there the two calls are one
+ * function: costs, second buffers and the final wait of kpilqr_update_keypoints apply as written there.  With a job-list payload,
+ * or with none, there is nothing to carry.
+ *
+ * kpilqr_get_keypoints_partial reads the listed trajectories' lists back COMPACT (the host FD loop needs them before it can fill the
+ * listed trajectories' records): kp_offsets [count*dof + 1] re-based to 0, kp_times with one copy per run of adjacent trajectories.
+ * Returns the number of entries of the listed trajectories (>= 0) or an error (< 0).  Synchronous, like kpilqr_get_keypoints.
+ * kp_times = NULL queries the size and does not touch the device when the offsets mirror is valid (always after
+ * kpilqr_set_keypoints, kpilqr_update_keypoints and kpilqr_generate_keypoints_partial; behind kpilqr_generate_keypoints the first
+ * call reads the offsets back, once).  A times_capacity that is too small is KPILQR_ERR_ARG.  It works on any lists, not only
+ * device-placed ones, and it is allowed while ranges are pending: it reads lists, not payload.
+ *
+ * Out of scope: the host shims (they place key-points on the host); the chunks of kpilqr_iterate_streamed;
+ * kpilqr_keypoint_error_test for a subset; job-list payloads carried across the update; an environment switch. */
+int  kpilqr_upload_states_partial(kpilqr_ctx *ctx, int count, const int *traj,
+                                  const double *X /* [count][T][n], compact, traj order */);
+int  kpilqr_generate_keypoints_partial(kpilqr_ctx *ctx, int count, const int *traj, const char *method,
+                                       int min_N, int max_N, const double *thresholds, double dt);
+int  kpilqr_get_keypoints_partial(kpilqr_ctx *ctx, int count, const int *traj,
+                                  int *kp_offsets /* [count*dof + 1], starts at 0 */,
+                                  int *kp_times /* or NULL */, int times_capacity);
 
 /* Host FD results, one job per perturbed column (Differentiator::DynamicsDerivatives,
  * src/Differentiator/Differentiator.cpp:81-428 stays on the host and fills these):
@@ -808,6 +858,7 @@ int  kpilqr_iterate(kpilqr_ctx *ctx, const double *lambda, int pd_check_stride, 
  * column store, slope store or union store of kept trajectories across kpilqr_update_keypoints; kpilqr_backward_stats,
  * kpilqr_generate_keypoints and kpilqr_upload_states for a subset; an environment switch.  kpilqr_allreduce_linesearch sums whatever
  * cost_pred and status are resident, the rows an earlier sweep left for unlisted trajectories included.
+ * (since: kpilqr_upload_states_partial and kpilqr_generate_keypoints_partial -- "Key-point placement for a subset".)
  * KPILQR_VERSION is unchanged: detect the calls by their symbols. */
 int  kpilqr_backward_partial(kpilqr_ctx *ctx, int count, const int *traj, const double *lambda /* [count] or NULL */,
                              int pd_check_stride, int *status /* [count] */, double *delta_J /* [count] */);

@@ -6,7 +6,9 @@
 // the move itself is replayed on byte buffers -- what k_relocate_entries / k_merge_kp_times do with the same three arrays -- into
 // allocations of exactly the needed size, so that an index one past a range is a sanitizer report.  The walk over runs of adjacent
 // trajectories (kp_for_each_run: what every call on a subset copies or launches by) is held against a naive restatement on random
-// strictly increasing lists, the empty list, one element, all adjacent and none adjacent included.  Prints the number of trials.
+// strictly increasing lists, the empty list, one element, all adjacent and none adjacent included.  The offsets
+// kpilqr_generate_keypoints_partial forms from the per-list counts it reads back (kp_offsets_from_counts) are held against the new
+// lists' own offsets in every trial, with a count the kernel cannot write and the edge of an int.  Prints the number of trials.
 #include <cstdio>
 #include <cstdlib>
 #include <random>
@@ -113,8 +115,26 @@ int main()
         REQUIRE(kp_traj_list_ok(B, (int)traj.size(), traj.data()));
         REQUIRE(run_walk_fails(traj) == 0);
 
+        // kpilqr_generate_keypoints_partial: the new lists' offsets from the per-list counts the device reports (exactly sized arrays)
+        {
+            const size_t nnew = traj.size() * dof;
+            int *counts = (int *)std::malloc(sizeof(int) * nnew + 1), *offs = (int *)std::malloc(sizeof(int) * (nnew + 1));
+            bool fits = true;                                               // (a list in any order may repeat a time: more than T entries)
+            for (size_t i = 0; i < nnew; i++) { counts[i] = new_offs[i + 1] - new_offs[i]; fits = fits && counts[i] <= T; }
+            REQUIRE(kp_offsets_from_counts(nnew, T, counts, offs) == (fits ? 0 : 1));
+            for (size_t i = 0; fits && i <= nnew; i++) REQUIRE(offs[i] == new_offs[i]);
+            if (nnew && fits) {                                                     // a count the kernel cannot have written
+                const size_t at = rng() % nnew;
+                const int was = counts[at];
+                counts[at] = rng() % 2 ? -1 : T + 1;
+                REQUIRE(kp_offsets_from_counts(nnew, T, counts, offs) == 1);
+                counts[at] = was;
+            }
+            std::free(counts); std::free(offs);
+        }
+
         // exactly sized heap arrays: one element too far is a report
-        int *merged = (int *)std::malloc(sizeof(int) * ((size_t)B * dof + 1)), *mv = (int *)std::malloc(sizeof(int) * 3 * ((size_t)B + 1));
+        int *merged =(int *)std::malloc(sizeof(int) * ((size_t)B * dof + 1)), *mv = (int *)std::malloc(sizeof(int) * 3 * ((size_t)B + 1));
         int *first_old = mv, *first_new = mv + B + 1, *upl_first = mv + 2 * (B + 1);
         REQUIRE(kp_merge_offsets(B, dof, old_offs.data(), (int)traj.size(), traj.data(), new_offs.data(), merged, first_old, first_new, upl_first));
         for (size_t i = 0; i < want_offs.size(); i++) REQUIRE(merged[i] == want_offs[i]);
@@ -176,6 +196,15 @@ int main()
     }
     const std::vector<int> corner[] = {{}, {0}, {5}, {0, 1, 2, 3, 4}, {3, 4, 5}, {0, 2, 4, 6}, {1, 3}, {0, 1, 3, 4, 5, 9}, {0, 2, 3}};
     for (const std::vector<int> &traj : corner) { REQUIRE(run_walk_fails(traj) == 0); walks++; }
+    // counts -> offsets at the edge of an int: the largest total that fits, and one entry more (the sum is formed in 64 bits)
+    {
+        const int T = INT32_MAX / 4 + 1;                                    // 4 T = 2^31 > INT32_MAX >= 4 T - 1
+        int counts[4] = {T, T, T, T - 1}, offs[5];
+        REQUIRE(kp_offsets_from_counts(4, T, counts, offs) == 0 && offs[4] == INT32_MAX && offs[3] == 3 * (int64_t)T);
+        counts[3] = T;
+        REQUIRE(kp_offsets_from_counts(4, T, counts, offs) == 2);
+        REQUIRE(kp_offsets_from_counts(0, T, counts, offs) == 0 && offs[0] == 0);
+    }
     std::printf("kp_merge_fuzz: %d trials ok, %d run walks ok\n", trial, walks);
     return 0;
 }

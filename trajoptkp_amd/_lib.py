@@ -35,6 +35,7 @@ SYMBOLS = [
     "kpilqr_set_lambda_retry", "kpilqr_download_lambda_retry",
     "kpilqr_upload_kp_columns_f32", "kpilqr_upload_kp_columns_f32_partial", "kpilqr_iterate_streamed3", "kpilqr_iterate_streamed4",
     "kpilqr_backward_partial", "kpilqr_forward_linear_partial", "kpilqr_iterate_partial",
+    "kpilqr_upload_states_partial", "kpilqr_generate_keypoints_partial", "kpilqr_get_keypoints_partial",
 ]
 # entry points added without a version bump (include/kpilqr.h: "detect the entry point by its symbol"): bound only when the library
 # has them -- KPILQR_LIB may name an older build of the same major version
@@ -46,7 +47,8 @@ OPTIONAL_SYMBOLS = {"kpilqr_fd_interpolate", "kpilqr_get_union_keypoints", "kpil
                     "kpilqr_set_lambda_retry", "kpilqr_download_lambda_retry",
                     "kpilqr_upload_kp_columns_f32", "kpilqr_upload_kp_columns_f32_partial", "kpilqr_iterate_streamed3",
                     "kpilqr_iterate_streamed4",
-                    "kpilqr_backward_partial", "kpilqr_forward_linear_partial", "kpilqr_iterate_partial"}
+                    "kpilqr_backward_partial", "kpilqr_forward_linear_partial", "kpilqr_iterate_partial",
+                    "kpilqr_upload_states_partial", "kpilqr_generate_keypoints_partial", "kpilqr_get_keypoints_partial"}
 
 
 class Dims(C.Structure):
@@ -210,6 +212,10 @@ def load():
         L.kpilqr_backward_partial.argtypes = [vp, C.c_int, vp, vp, C.c_int, vp, vp]
         L.kpilqr_forward_linear_partial.argtypes = [vp, C.c_int, vp, vp, vp, vp]
         L.kpilqr_iterate_partial.argtypes = [vp, C.c_int, vp, vp, C.c_int, vp]
+    if hasattr(L, "kpilqr_generate_keypoints_partial"):
+        L.kpilqr_upload_states_partial.argtypes = [vp, C.c_int, vp, vp]
+        L.kpilqr_generate_keypoints_partial.argtypes = [vp, C.c_int, vp, C.c_char_p, C.c_int, C.c_int, vp, C.c_double]
+        L.kpilqr_get_keypoints_partial.argtypes = [vp, C.c_int, vp, vp, vp, C.c_int]
     for s in SYMBOLS:
         if s in OPTIONAL_SYMBOLS and not hasattr(L, s):
             continue

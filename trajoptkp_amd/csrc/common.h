@@ -216,8 +216,11 @@ struct Ctx {
     DevBuf<double> X_states;      // [batch][T][n]
     DevBuf<double> kp_thr;        // [dof]
     DevBuf<unsigned long long> kp_mask;      // [batch*dof][ceil(T/64)]
-    DevBuf<int> kp_count;         // [batch*dof]
+    DevBuf<int> kp_count;         // [batch*dof]; kpilqr_generate_keypoints_partial: [2*batch*dof + 1], the compact counts | at batch*dof their scan
     bool have_states = false;
+    // one host byte per trajectory (malloc, on first use): its states were given since create / resize -- by a whole
+    // kpilqr_upload_states (everybody) or by kpilqr_upload_states_partial.  kpilqr_generate_keypoints_partial looks here.
+    unsigned char *states_given_host = nullptr;      // [batch]
 
     // RCCL communicator for the line-search reduction (kpilqr_comm_init), and its 8-double device buffer
     void *comm = nullptr;
@@ -422,6 +425,11 @@ hipError_t launch_pack_linesearch(Ctx *c, double *dev8);
 // keypoints.hip
 hipError_t launch_generate_keypoints(Ctx *c, int method, int min_N, int max_N, double dt, const double *thr_dev,
                                      const double *X_dev, unsigned long long *mask_dev, int *count_dev);
+// the placement of a listed subset (kpilqr_generate_keypoints_partial): pass 1 over list_dev [count] (device) into COMPACT mask /
+// count rows, and -- once the host has scanned the counts -- pass 3 from those rows into times_dev by offsets_dev [count*dof + 1]
+hipError_t launch_kp_flags_listed(Ctx *c, int count, const int *list_dev, int method, int min_N, int max_N, double dt,
+                                  const double *thr_dev, const double *X_dev, unsigned long long *mask_dev, int *count_dev);
+hipError_t launch_kp_fill_listed(Ctx *c, int count, const unsigned long long *mask_dev, const int *offsets_dev, int *times_dev);
 hipError_t launch_kp_error_test(Ctx *c, int n_iv, const int *iv_dev, int min_N, double threshold, unsigned char *good_dev);
 hipError_t launch_interpolate(Ctx *c, const int *traj = nullptr, int count = 0);      // traj (device): those trajectories alone
 // linearise.hip: key-point ordered payload (FdPayload::kp_ordered) or column payload (kp_columns) -> every step record's [A|B], a2 + a4 in one pass

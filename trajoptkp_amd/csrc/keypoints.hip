@@ -10,6 +10,10 @@
 // Pass 1 writes a 64-step bitmask per list and chunk plus the list's count, pass 2 is an exclusive scan of
 // the counts (kp_offsets), pass 3 expands the bitmasks into kp_times.  Duplicate entries the reference emits
 // for the last row (velocity_change, :724-727) collapse: a DoF is a key-point at a step or it is not.
+//
+// A listed subset (kpilqr_generate_keypoints_partial) runs pass 1 and pass 3 over COMPACT rows: block i of k_kp_flags places
+// trajectory list[i] and writes bitmask and count rows i; the host scans the counts it reads back (kp_merge.h), and k_kp_fill
+// expands the compact rows into the new lists' times.  Pass 2 belongs to the whole-batch call alone.
 #include "common.h"
 
 namespace kpilqr {
@@ -17,13 +21,18 @@ namespace kpilqr {
 #define KP_CHUNK 64
 
 // method: 0 set_interval, 1 adaptive_jerk, 2 velocity_change, 3 adaptive_accel
+// LISTED (kpilqr_generate_keypoints_partial): block i reads the states of trajectory list[i] -- a scalar load off a kernel argument
+// indexed by the block, so the trajectory stays wave-uniform -- and writes rows i of mask and count.  LISTED = false, the launch of
+// the whole-batch call, never reads `list`: block i places trajectory i.
+template <bool LISTED>
 __global__ void __launch_bounds__(64)
 k_kp_flags(int method, int dof, int T, int min_N, int max_N, double dt, const double *__restrict__ thr,
-           const double *__restrict__ X, unsigned long long *__restrict__ mask, int *__restrict__ count)
+           const double *__restrict__ X, const int *__restrict__ list, unsigned long long *__restrict__ mask, int *__restrict__ count)
 {
     extern __shared__ __attribute__((aligned(16))) double sx[];      // [(KP_CHUNK + 2)][dof] velocities
     const int n = 2 * dof;
-    const int b = blockIdx.x, j = threadIdx.x;
+    const int row_out = blockIdx.x, j = threadIdx.x;                  // (mask and count rows are the launch's own: compact in a listed one)
+    const int b = LISTED ? list[blockIdx.x] : (int)blockIdx.x;
     const int nchunks = (T + KP_CHUNK - 1) / KP_CHUNK;
     const double *Xb = X + (size_t)b * T * n;
     const double th = (j < dof && thr) ? thr[j] : 0.0;
@@ -94,10 +103,10 @@ k_kp_flags(int method, int dof, int T, int min_N, int max_N, double dt, const do
                 }
                 if (key) { w |= 1ull << tt; cnt++; }
             }
-            mask[((size_t)b * dof + j) * nchunks + ch] = w;
+            mask[((size_t)row_out * dof + j) * nchunks + ch] = w;
         }
     }
-    if (j < dof) count[(size_t)b * dof + j] = cnt;
+    if (j < dof) count[(size_t)row_out * dof + j] = cnt;
 }
 
 // exclusive scan of counts[0..nlists) -> offsets[0..nlists]; one workgroup
@@ -145,11 +154,30 @@ hipError_t launch_generate_keypoints(Ctx *c, int method, int min_N, int max_N, d
     const int dof = c->d.dof, T = c->d.T, nlists = c->d.batch * dof;
     const int nchunks = (T + KP_CHUNK - 1) / KP_CHUNK;
     const size_t lds = sizeof(double) * (size_t)(KP_CHUNK + 3) * dof;
-    hipLaunchKernelGGL(k_kp_flags, dim3(c->d.batch), dim3(64), lds, c->stream, method, dof, T, min_N, max_N, dt, thr_dev,
-                       X_dev, mask_dev, count_dev);
+    hipLaunchKernelGGL(k_kp_flags<false>, dim3(c->d.batch), dim3(64), lds, c->stream, method, dof, T, min_N, max_N, dt, thr_dev,
+                       X_dev, (const int *)nullptr, mask_dev, count_dev);
     hipLaunchKernelGGL(k_kp_scan, dim3(1), dim3(1024), 0, c->stream, nlists, count_dev, c->kp_offsets);
     hipLaunchKernelGGL(k_kp_fill, dim3((nlists + 255) / 256), dim3(256), 0, c->stream, nlists, nchunks, mask_dev,
                        c->kp_offsets, c->kp_times);
+    return hipGetLastError();
+}
+
+// Pass 1 for the `count` trajectories of list_dev (device): mask_dev [count*dof][nchunks] and count_dev [count*dof], compact
+hipError_t launch_kp_flags_listed(Ctx *c, int count, const int *list_dev, int method, int min_N, int max_N, double dt,
+                                  const double *thr_dev, const double *X_dev, unsigned long long *mask_dev, int *count_dev)
+{
+    const int dof = c->d.dof, T = c->d.T;
+    const size_t lds = sizeof(double) * (size_t)(KP_CHUNK + 3) * dof;
+    hipLaunchKernelGGL(k_kp_flags<true>, dim3(count), dim3(64), lds, c->stream, method, dof, T, min_N, max_N, dt, thr_dev, X_dev,
+                       list_dev, mask_dev, count_dev);
+    return hipGetLastError();
+}
+
+// Pass 3 for the same rows: offsets_dev [count*dof + 1] (from 0, the host's scan of the counts) index times_dev
+hipError_t launch_kp_fill_listed(Ctx *c, int count, const unsigned long long *mask_dev, const int *offsets_dev, int *times_dev)
+{
+    const int nlists = count * c->d.dof, nchunks = (c->d.T + KP_CHUNK - 1) / KP_CHUNK;
+    hipLaunchKernelGGL(k_kp_fill, dim3((nlists + 255) / 256), dim3(256), 0, c->stream, nlists, nchunks, mask_dev, offsets_dev, times_dev);
     return hipGetLastError();
 }
 

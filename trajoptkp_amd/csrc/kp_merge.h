@@ -72,6 +72,22 @@ inline int kp_for_each_run(int count, const int *traj, F f)
     return 0;
 }
 
+// kpilqr_generate_keypoints_partial: the counts [nlists] the placement kernel wrote for the listed trajectories' DoF lists, compact
+// -> offs [nlists + 1] from 0, the new lists' own CSR (what kp_merge_offsets takes as new_offs).  0: done | 1: a count outside
+// [0, T], which is not something the kernel writes | 2: more entries than an int counts.  offs is not to be used unless 0.
+inline int kp_offsets_from_counts(size_t nlists, int T, const int *counts, int *offs)
+{
+    int64_t at = 0;
+    for (size_t i = 0; i < nlists; i++) {
+        if (counts[i] < 0 || counts[i] > T) return 1;
+        offs[i] = (int)at;
+        at += counts[i];
+        if (at > INT32_MAX) return 2;
+    }
+    offs[nlists] = (int)at;
+    return 0;
+}
+
 // The batch CSR with the lists of the `count` trajectories in `traj` replaced: new_offs [count*dof+1] (from 0) are theirs, old_offs
 // [batch*dof+1] everybody's so far.  Writes merged [batch*dof+1] and, per trajectory, its first entry before (old_first [batch+1])
 // and after (new_first [batch+1]) and where its times come from: upl_first [batch+1] = first entry inside the new lists' times for

@@ -77,6 +77,9 @@ static hipError_t release(DevMem &b)
     return e;
 }
 
+// how everything that allocates refuses a view of kpilqr_iterate_streamed's chunks
+static const char *const kViewNeverAllocates = "a view of a trajectory range never allocates: its context sizes the buffers first";
+
 // Room for `need` bytes in b.  Nothing happens while they fit; otherwise the old allocation is freed -- after a wait for the
 // context's stream: nothing in flight still uses it -- and need + slack bytes are allocated.  Returns 1 when it re-allocated (the
 // old contents are gone), 0 when not, an error code < 0.  zero: the `need` bytes are cleared, grown or not.
@@ -84,7 +87,7 @@ static int reserve(kpilqr_ctx *c, DevMem &b, size_t need, Slack slack, bool zero
 {
     int grown = 0;
     if (would_grow(b, need)) {
-        if (c->is_view) return set_err(c, KPILQR_ERR_STATE, "a view of a trajectory range never allocates: its context sizes the buffers first");
+        if (c->is_view) return set_err(c, KPILQR_ERR_STATE, kViewNeverAllocates);
         if (b.p) KP_HIP(c, hipStreamSynchronize(c->stream));
         KP_HIP(c, release(b));
         const size_t bytes = need + (slack.div ? need / slack.div + slack.add : 0);
@@ -672,6 +675,7 @@ void kpilqr_destroy(kpilqr_ctx *c)
         for (hipEvent_t e : c->rows_read[i]) if (e) (void)hipEventDestroy(e);
     }
     forget_lists(c);
+    free(c->states_given_host);
     if (c->kpu_traj_first_host) free(c->kpu_traj_first_host);
     if (c->own_stream) (void)hipStreamDestroy(c->stream);
     delete c;
@@ -706,6 +710,7 @@ int kpilqr_resize(kpilqr_ctx *c, int new_dof, int new_num_ctrl, int new_horizon)
         return set_err(c, rc, msg);
     }
     c->have_kp = c->kp_canonical = c->have_states = c->kp_known_uniform = false;
+    free(c->states_given_host); c->states_given_host = nullptr;      // (nobody's states are given any more)
     c->njobs = c->nnom = 0;
     c->fd_payload = FdPayload::none; c->fdk_entries = 0; c->kp_total_host = -1;
     forget_lists(c);                                     // (sized by the old batch * dof; size_buffers has reset both validity aggregates)
@@ -837,27 +842,25 @@ static int ensure_offsets_mirror(kpilqr_ctx *c)
     return KPILQR_OK;
 }
 
-int kpilqr_update_keypoints(kpilqr_ctx *c, int count, const int *traj, const int *kp_offsets, const int *kp_times)
+// What kpilqr_update_keypoints and kpilqr_generate_keypoints_partial share once the new lists of the `count` trajectories in `traj`
+// are known (kp_offsets [count*dof + 1] from 0, on the host) and the context's offsets mirror is valid: the merge, the second
+// buffers, the enqueue and the bookkeeping.  The two callers differ in where the new lists' TIMES are: kp_times != nullptr is the
+// caller's host array, which goes up into kp_upl_times here and from which the listed trajectories' flags are taken; nullptr says
+// that kp_upl_times (reserved by the caller for kp_offsets[count*dof] entries) already holds them on the device, placed there by
+// k_kp_fill on the context's stream, and placed_flags is every listed trajectory's flag byte.
+static int install_subset_lists(kpilqr_ctx *c, const char *who, int count, const int *traj, const int *kp_offsets, const int *kp_times,
+                                unsigned char placed_flags)
 {
-    if (count > 0 && (!kp_offsets || !kp_times)) return KPILQR_ERR_ARG;
-    // (count = 0: nobody's lists change, nothing becomes invalid; a view is refused below, in the words of everything that allocates)
-    { const int go = enter_subset(c, "kpilqr_update_keypoints", count, traj, Subset::listed_or_view); if (go <= 0) return go; }
     const int B = c->d.batch, dof = c->d.dof;
     const size_t nlists = (size_t)B * dof, nnew = (size_t)count * dof, B1 = (size_t)B + 1;
-    if (const char *bad = kp_check_lists(nnew, c->d.T, kp_offsets, kp_times)) return set_err(c, KPILQR_ERR_ARG, bad);
-    if (!c->have_kp) return set_err(c, KPILQR_ERR_STATE, "kpilqr_update_keypoints before kpilqr_set_keypoints / kpilqr_generate_keypoints");
-    if (c->is_view) return set_err(c, KPILQR_ERR_STATE, "a view of a trajectory range never allocates: its context sizes the buffers first");
-    { const int rcp = check_complete(c, "kpilqr_update_keypoints"); if (rcp) return rcp; }
-    int rc = ensure_offsets_mirror(c);
-    if (rc) return rc;
-
+    int rc;
     // ---- the merged CSR and who moves where (kp_merge.h); nothing of the context changes before every buffer is there ------------
     int *merged = (int *)malloc(sizeof(int) * (nlists + 1)), *mv = (int *)malloc(sizeof(int) * 3 * B1);
     struct Free { int *a, *b; ~Free() { free(a); free(b); } } guard{merged, mv};
     if (!merged || !mv) return set_err(c, KPILQR_ERR_ALLOC, "host allocation failed");
     int *const first_old = mv, *const first_new = mv + B1, *const upl_first = mv + 2 * B1;
     if (!kp_merge_offsets(B, dof, c->kp_offsets_host, count, traj, kp_offsets, merged, first_old, first_new, upl_first))
-        return set_err(c, KPILQR_ERR_ARG, "kpilqr_update_keypoints: more key-point entries than an int counts");
+        return set_err(c, KPILQR_ERR_ARG, std::string(who) + ": more key-point entries than an int counts");
     const int total = merged[nlists], new_entries = kp_offsets[nnew];
     int longest = 0, longest_kept = 0;
     for (int b = 0; b < B; b++) {
@@ -891,7 +894,7 @@ int kpilqr_update_keypoints(kpilqr_ctx *c, int count, const int *traj, const int
     const int *const mv_dev = c->kp_move;
     KP_HIP(c, hipMemcpyAsync(c->kp_offsets, merged, (nlists + 1) * sizeof(int), hipMemcpyHostToDevice, c->stream));
     KP_HIP(c, hipMemcpyAsync(c->kp_move, mv, 3 * B1 * sizeof(int), hipMemcpyHostToDevice, c->stream));
-    if (new_entries) KP_HIP(c, hipMemcpyAsync(c->kp_upl_times, kp_times, (size_t)new_entries * sizeof(int), hipMemcpyHostToDevice, c->stream));
+    if (new_entries && kp_times) KP_HIP(c, hipMemcpyAsync(c->kp_upl_times, kp_times, (size_t)new_entries * sizeof(int), hipMemcpyHostToDevice, c->stream));
     KP_HIP(c, launch_merge_kp_times(c, longest, mv_dev, mv_dev + B1, mv_dev + 2 * B1, c->kp_times, c->kp_upl_times, c->kp_times_alt));
     std::swap(c->kp_times, c->kp_times_alt);
     if (carry) {
@@ -899,7 +902,7 @@ int kpilqr_update_keypoints(kpilqr_ctx *c, int count, const int *traj, const int
         std::swap(*live, *alt);
     }
     // ---- the context as kpilqr_set_keypoints(merged lists) leaves it -- except that the payload stays, with ranges pending ---------
-    for (int i = 0; i < count; i++) c->kp_flags_host[traj[i]] = kp_traj_flags(dof, c->d.T, kp_offsets + (size_t)i * dof, kp_times);
+    for (int i = 0; i < count; i++) c->kp_flags_host[traj[i]] = kp_times ? kp_traj_flags(dof, c->d.T, kp_offsets + (size_t)i * dof, kp_times) : placed_flags;
     const unsigned char flags = kp_batch_flags(B, c->kp_flags_host);
     rc = lists_installed(c, total, flags & kKpCanonical, flags & kKpUniform);
     if (rc) return rc;
@@ -918,6 +921,20 @@ int kpilqr_update_keypoints(kpilqr_ctx *c, int count, const int *traj, const int
     return KPILQR_OK;
 }
 
+int kpilqr_update_keypoints(kpilqr_ctx *c, int count, const int *traj, const int *kp_offsets, const int *kp_times)
+{
+    if (count > 0 && (!kp_offsets || !kp_times)) return KPILQR_ERR_ARG;
+    // (count = 0: nobody's lists change, nothing becomes invalid; a view is refused below, in the words of everything that allocates)
+    { const int go = enter_subset(c, "kpilqr_update_keypoints", count, traj, Subset::listed_or_view); if (go <= 0) return go; }
+    if (const char *bad = kp_check_lists((size_t)count * c->d.dof, c->d.T, kp_offsets, kp_times)) return set_err(c, KPILQR_ERR_ARG, bad);
+    if (!c->have_kp) return set_err(c, KPILQR_ERR_STATE, "kpilqr_update_keypoints before kpilqr_set_keypoints / kpilqr_generate_keypoints");
+    if (c->is_view) return set_err(c, KPILQR_ERR_STATE, kViewNeverAllocates);
+    { const int rcp = check_complete(c, "kpilqr_update_keypoints"); if (rcp) return rcp; }
+    const int rc = ensure_offsets_mirror(c);
+    if (rc) return rc;
+    return install_subset_lists(c, "kpilqr_update_keypoints", count, traj, kp_offsets, kp_times, 0);
+}
+
 // ---- key-point placement on the device ----------------------------------------------------------------
 int kpilqr_upload_states(kpilqr_ctx *c, const double *X)
 {
@@ -927,6 +944,23 @@ int kpilqr_upload_states(kpilqr_ctx *c, const double *X)
     { const int rcg = reserve(c, c->X_states, count * sizeof(double), kExact, false); if (rcg < 0) return rcg; }
     KP_HIP(c, hipMemcpyAsync(c->X_states, X, count * sizeof(double), hipMemcpyHostToDevice, c->stream));
     c->have_states = true;
+    if (c->states_given_host) memset(c->states_given_host, 1, (size_t)c->d.batch);      // (no array yet: have_states says the same to whoever makes it)
+    return KPILQR_OK;
+}
+
+// The placement arguments of kpilqr_generate_keypoints and kpilqr_generate_keypoints_partial -> the kernel's method number in *mth
+// (0 set_interval, 1 adaptive_jerk, 2 velocity_change, 3 adaptive_accel), or KPILQR_ERR_ARG with the message
+static int placement_args(kpilqr_ctx *c, const char *method, int min_N, int max_N, const double *thresholds, double dt, int *mth)
+{
+    if (strcmp(method, "set_interval") == 0) *mth = 0;
+    else if (strcmp(method, "adaptive_jerk") == 0) *mth = 1;
+    else if (strcmp(method, "velocity_change") == 0) *mth = 2;
+    else if (strcmp(method, "adaptive_accel") == 0) *mth = 3;
+    else return set_err(c, KPILQR_ERR_ARG, "kpilqr_generate_keypoints: method must be set_interval, adaptive_jerk, adaptive_accel or velocity_change "
+                                           "(iterative_error interleaves host finite differences and stays on the host)");
+    if (min_N < 1 || max_N < 1) return set_err(c, KPILQR_ERR_ARG, "min_N and max_N must be >= 1");
+    if (c->d.dof > 64) return set_err(c, KPILQR_ERR_ARG, "on-device key-point placement supports dof <= 64");
+    if (*mth != 0 && (!thresholds || (*mth == 1 && !(dt > 0.0)))) return set_err(c, KPILQR_ERR_ARG, "thresholds (and, for adaptive_jerk, a positive dt) are required");
     return KPILQR_OK;
 }
 
@@ -935,15 +969,7 @@ int kpilqr_generate_keypoints(kpilqr_ctx *c, const char *method, int min_N, int 
     if (!c || !method) return KPILQR_ERR_ARG;
     KP_ENTER(c);
     int mth = -1;
-    if (strcmp(method, "set_interval") == 0) mth = 0;
-    else if (strcmp(method, "adaptive_jerk") == 0) mth = 1;
-    else if (strcmp(method, "velocity_change") == 0) mth = 2;
-    else if (strcmp(method, "adaptive_accel") == 0) mth = 3;
-    else return set_err(c, KPILQR_ERR_ARG, "kpilqr_generate_keypoints: method must be set_interval, adaptive_jerk, adaptive_accel or velocity_change "
-                                           "(iterative_error interleaves host finite differences and stays on the host)");
-    if (min_N < 1 || max_N < 1) return set_err(c, KPILQR_ERR_ARG, "min_N and max_N must be >= 1");
-    if (c->d.dof > 64) return set_err(c, KPILQR_ERR_ARG, "on-device key-point placement supports dof <= 64");
-    if (mth != 0 && (!thresholds || (mth == 1 && !(dt > 0.0)))) return set_err(c, KPILQR_ERR_ARG, "thresholds (and, for adaptive_jerk, a positive dt) are required");
+    { const int rca = placement_args(c, method, min_N, max_N, thresholds, dt, &mth); if (rca) return rca; }
     if (mth != 0 && !c->have_states) return set_err(c, KPILQR_ERR_STATE, "kpilqr_generate_keypoints before kpilqr_upload_states");
     const size_t nlists = (size_t)c->d.batch * c->d.dof, T = c->d.T, nchunks = (T + 63) / 64;
     const struct { DevMem *buf; size_t bytes; } rows[] = {
@@ -1754,6 +1780,123 @@ int kpilqr_cost_derivs_partial(kpilqr_ctx *c, int count, const int *traj)
     KP_HIP(c, hipMemcpyAsync(c->traj_list, traj, (size_t)count * sizeof(int), hipMemcpyHostToDevice, c->stream));
     KP_HIP(c, launch_cost_derivs(c, c->traj_list, count));
     return wait_unless_pinned(c, traj);
+}
+
+// ---- key-point placement on the device for a listed subset: states, placement, and the new lists read back compact -------------------
+// All three enter like kpilqr_update_keypoints: the list check of the _partial family, and a view refused in the words of
+// everything that allocates.  -> 1: go on | KPILQR_OK: nobody is listed | < 0: refused
+static int enter_placement_subset(kpilqr_ctx *c, const char *who, int count, const int *traj)
+{
+    const int go = enter_subset(c, who, count, traj, Subset::listed_or_view);
+    if (go <= 0) return go;
+    if (c->is_view) return set_err(c, KPILQR_ERR_STATE, kViewNeverAllocates);
+    return 1;
+}
+
+int kpilqr_upload_states_partial(kpilqr_ctx *c, int count, const int *traj, const double *X)
+{
+    if (count > 0 && !X) return KPILQR_ERR_ARG;
+    { const int go = enter_placement_subset(c, "kpilqr_upload_states_partial", count, traj); if (go <= 0) return go; }
+    const size_t B = c->d.batch, per = (size_t)c->d.T * c->n;
+    { const int rcg = reserve(c, c->X_states, B * per * sizeof(double), kExact, false); if (rcg < 0) return rcg; }
+    if (!c->states_given_host) {
+        c->states_given_host = (unsigned char *)malloc(B);
+        if (!c->states_given_host) return set_err(c, KPILQR_ERR_ALLOC, "host allocation failed");
+        memset(c->states_given_host, c->have_states ? 1 : 0, B);
+    }
+    const int rc = upload_rows(c, count, traj, X, c->X_states, per);
+    if (rc) return rc;
+    for (int i = 0; i < count; i++) c->states_given_host[traj[i]] = 1;
+    return KPILQR_OK;
+}
+
+int kpilqr_generate_keypoints_partial(kpilqr_ctx *c, int count, const int *traj, const char *method, int min_N, int max_N,
+                                      const double *thresholds, double dt)
+{
+    static const char who[] = "kpilqr_generate_keypoints_partial";
+    if (!c || !method) return KPILQR_ERR_ARG;
+    { const int go = enter_placement_subset(c, who, count, traj); if (go <= 0) return go; }
+    int mth = -1;
+    int rc = placement_args(c, method, min_N, max_N, thresholds, dt, &mth);
+    if (rc) return rc;
+    if (!c->have_kp) return set_err(c, KPILQR_ERR_STATE, std::string(who) + " before kpilqr_set_keypoints / kpilqr_generate_keypoints");
+    rc = check_complete(c, who);
+    if (rc) return rc;
+    if (mth != 0 && !c->have_states)
+        for (int i = 0; i < count; i++)
+            if (!c->states_given_host || !c->states_given_host[traj[i]])
+                return set_err(c, KPILQR_ERR_STATE, std::string(who) + ": the states of trajectory " + std::to_string(traj[i]) +
+                               " were never uploaded (kpilqr_upload_states / kpilqr_upload_states_partial)");
+    rc = ensure_offsets_mirror(c);
+    if (rc) return rc;
+
+    // ---- pass 1 over the list, and its counts read back: from here the host knows every size exactly -----------------------------
+    const size_t dof = c->d.dof, nlists = (size_t)c->d.batch * dof, nnew = (size_t)count * dof, T = c->d.T, nchunks = (T + 63) / 64;
+    const struct { DevMem *buf; size_t bytes; } rows[] = {                // (the whole-batch call's sizes: the two share the buffers)
+        {&c->kp_thr, sizeof(double) * dof},
+        {&c->kp_mask, sizeof(unsigned long long) * nlists * nchunks},
+        {&c->kp_count, sizeof(int) * (2 * nlists + 1)},                   // the compact counts | at nlists: their scan, nnew + 1 offsets
+        {&c->X_states, sizeof(double) * c->d.batch * T * c->n},           // set_interval never looks at what it stages from here
+    };
+    for (const auto &row : rows) { const int rcg = reserve(c, *row.buf, row.bytes, kExact, false); if (rcg < 0) return rcg; }
+    int *const counts = (int *)malloc(sizeof(int) * (2 * nnew + 1));
+    if (!counts) return set_err(c, KPILQR_ERR_ALLOC, "host allocation failed");
+    int *const offs = counts + nnew;
+    // (the two arrays are this call's own: whatever was enqueued has read them before they go)
+    struct Free { kpilqr_ctx *c; int *p; ~Free() { (void)hipStreamSynchronize(c->stream); free(p); } } guard{c, counts};
+    if (thresholds) KP_HIP(c, hipMemcpyAsync(c->kp_thr, thresholds, sizeof(double) * dof, hipMemcpyHostToDevice, c->stream));
+    KP_HIP(c, hipMemcpyAsync(c->traj_list, traj, (size_t)count * sizeof(int), hipMemcpyHostToDevice, c->stream));
+    KP_HIP(c, launch_kp_flags_listed(c, count, c->traj_list, mth, min_N, max_N, dt, thresholds ? c->kp_thr : nullptr, c->X_states, c->kp_mask, c->kp_count));
+    KP_HIP(c, hipMemcpyAsync(counts, c->kp_count, nnew * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    KP_HIP(c, hipStreamSynchronize(c->stream));          // (thresholds and traj, which may be pageable, have been read too)
+    const int bad = kp_offsets_from_counts(nnew, (int)T, counts, offs);
+    if (bad == 1) return set_err(c, KPILQR_ERR_HIP, std::string(who) + ": implausible key-point counts read back");
+    if (bad) return set_err(c, KPILQR_ERR_ARG, std::string(who) + ": more key-point entries than an int counts");
+
+    // ---- pass 3: the bitmasks expanded into the new lists' times, where kpilqr_update_keypoints uploads its caller's -----------
+    const int new_entries = offs[nnew];
+    { const int rcg = reserve(c, c->kp_upl_times, (size_t)new_entries * sizeof(int), kQuarter, false); if (rcg < 0) return rcg; }
+    int *const offs_dev = c->kp_count + nlists;
+    KP_HIP(c, hipMemcpyAsync(offs_dev, offs, (nnew + 1) * sizeof(int), hipMemcpyHostToDevice, c->stream));
+    KP_HIP(c, launch_kp_fill_listed(c, count, c->kp_mask, offs_dev, c->kp_upl_times));
+    // canonical: rows 0 and T-1 are always full and the lists strictly increasing by construction; set_interval: one list for all DoFs
+    return install_subset_lists(c, who, count, traj, offs, nullptr, (unsigned char)(kKpCanonical | (mth == 0 ? kKpUniform : 0)));
+}
+
+int kpilqr_get_keypoints_partial(kpilqr_ctx *c, int count, const int *traj, int *kp_offsets, int *kp_times, int times_capacity)
+{
+    if (!c || !kp_offsets) return KPILQR_ERR_ARG;
+    {
+        const int go = enter_placement_subset(c, "kpilqr_get_keypoints_partial", count, traj);
+        if (go < 0) return go;
+        if (go == 0) { kp_offsets[0] = 0; return 0; }
+    }
+    if (!c->have_kp) return set_err(c, KPILQR_ERR_STATE, "no key-points set");
+    // (ranges may be pending: this reads lists, not payload, and that is when the host needs them.  The mirror answers the size
+    // query without the device; behind kpilqr_generate_keypoints it is read back here, once)
+    { const int rc = ensure_offsets_mirror(c); if (rc) return rc; }
+    const int dof = c->d.dof, *const o = c->kp_offsets_host;
+    int at = 0;
+    for (int i = 0; i < count; i++)
+        for (int d = 0; d < dof; d++) {
+            const size_t l = (size_t)traj[i] * dof + d;
+            kp_offsets[(size_t)i * dof + d] = at;
+            at += o[l + 1] - o[l];
+        }
+    kp_offsets[(size_t)count * dof] = at;
+    if (kp_times) {
+        if (at > times_capacity) return set_err(c, KPILQR_ERR_ARG, "kp_times capacity too small");
+        int *dst = kp_times;
+        const int rc = kp_for_each_run(count, traj, [&](int, int b0, int run) -> int {
+            const int e0 = o[(size_t)b0 * dof], len = o[(size_t)(b0 + run) * dof] - e0;
+            if (len) KP_HIP(c, hipMemcpyAsync(dst, c->kp_times + e0, (size_t)len * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+            dst += len;
+            return KPILQR_OK;
+        });
+        if (rc) return rc;
+        KP_HIP(c, hipStreamSynchronize(c->stream));
+    }
+    return at;
 }
 
 // ---- K as FP32: half the bytes of the largest per-iteration download ---------------------------------------------------------------

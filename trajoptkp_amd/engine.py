@@ -231,6 +231,32 @@ class Engine:
         self._ck(self._L.kpilqr_get_keypoints(self._h, _ptr(offs), _ptr(times), len(times)))
         return offs, times[:total]
 
+    # -- key-point placement on the device for a listed subset of the batch ------------------------------
+    def upload_states_partial(self, traj, X):
+        """kpilqr_upload_states_partial: X [len(traj)][T][n], the listed trajectories' states, compact in traj order."""
+        tr = self._traj(traj)
+        X = _f64(X, (len(tr), self.T, self.n))
+        self._keep += [tr, X]
+        self._ck(self._partial("kpilqr_upload_states_partial")(self._h, len(tr), _ptr(tr), _ptr(X)))
+
+    def generate_keypoints_partial(self, traj, method, min_N, max_N=1, thresholds=None, dt=0.0):
+        """kpilqr_generate_keypoints_partial: generate_keypoints for the listed trajectories alone; the context is left as
+        update_keypoints with those lists leaves it (a by-entry payload survives, the listed ranges pending)."""
+        tr = self._traj(traj)
+        th = None if thresholds is None else _f64(thresholds, (self.dof,))
+        self._ck(self._partial("kpilqr_generate_keypoints_partial")(self._h, len(tr), _ptr(tr), method.encode(), int(min_N), int(max_N),
+                                                                   _ptr(th), float(dt)))
+
+    def get_keypoints_partial(self, traj):
+        """-> (offsets [len(traj)*dof+1] from 0, times): the per-DoF CSR of the listed trajectories alone, compact in traj order."""
+        tr = self._traj(traj)
+        fn = self._partial("kpilqr_get_keypoints_partial")
+        offs = np.zeros(len(tr) * self.dof + 1, np.int32)
+        total = self._ck(fn(self._h, len(tr), _ptr(tr), _ptr(offs), None, 0))
+        times = np.zeros(max(total, 1), np.int32)
+        self._ck(fn(self._h, len(tr), _ptr(tr), _ptr(offs), _ptr(times), len(times)))
+        return offs, times[:total]
+
     def get_union_keypoints(self):
         """kpilqr_get_union_keypoints (a context created with union_keypoints=True): -> (traj_offsets [batch+1], times), one
         sorted list of union times per trajectory."""
