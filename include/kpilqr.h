@@ -520,7 +520,8 @@ int  kpilqr_iterate_streamed(kpilqr_ctx *ctx, const kpilqr_stream_io *io, int pd
  * process, 1.10x with K32, 1.22x with K32 of a scattered half of the batch, 1.17x with FP64 K of that half (profiles/streamed_gains.txt).
  * Out of scope: FP32 for k, for any upload or inside any sweep; uploads or sweeps of a subset inside the chunks
  * (kpilqr_iterate_streamed4 has since added the uploads); KPILQR_FLAG_UNION_KEYPOINTS inside the chunks.  KPILQR_VERSION is unchanged: detect the call by its symbol.
- * (since: the explicit calls sweep a listed subset -- "Sweeps of a subset"; the chunks still sweep every trajectory.) */
+ * (since: the explicit calls sweep a listed subset -- "Sweeps of a subset"; the chunks still sweep every trajectory.)
+ * (since: kpilqr_iterate_streamed5, below, linearises and sweeps a listed subset inside the chunks.) */
 typedef struct {
     size_t struct_size;                         /* sizeof(kpilqr_stream_io2) as the caller compiled it                   */
     kpilqr_stream_io io;                        /* every field with the meaning it has for kpilqr_iterate_streamed       */
@@ -565,7 +566,8 @@ int  kpilqr_iterate_streamed2(kpilqr_ctx *ctx, const kpilqr_stream_io2 *io2, int
  * residuals, residual Jacobians, u_nom or k, or inside any sweep; the host classes (they do not use the streamed route); any change
  * to kpilqr_stream_io or kpilqr_stream_io2; an environment switch.  KPILQR_VERSION is unchanged: detect the call by its symbol.
  * (Uploads of a subset inside the chunks have since arrived as kpilqr_iterate_streamed4, below; its sweeps still cover every trajectory.)
- * (since: the explicit calls sweep a listed subset -- "Sweeps of a subset"; the chunks still sweep every trajectory.) */
+ * (since: the explicit calls sweep a listed subset -- "Sweeps of a subset"; the chunks still sweep every trajectory.)
+ * (since: kpilqr_iterate_streamed5, below, linearises and sweeps a listed subset inside the chunks.) */
 typedef struct {
     size_t struct_size;                         /* sizeof(kpilqr_stream_io3) as the caller compiled it                   */
     kpilqr_stream_io2 io2;                      /* every field as for kpilqr_iterate_streamed2; io2.struct_size = sizeof(kpilqr_stream_io2) */
@@ -629,7 +631,8 @@ int  kpilqr_iterate_streamed3(kpilqr_ctx *ctx, const kpilqr_stream_io3 *io3, int
  * Out of scope: sweeps or linearisation of a subset; job-list payloads (io.fd_slab) with a list; KPILQR_FLAG_UNION_KEYPOINTS inside
  * the chunks; the host classes and the batch shim (they do not use the streamed route); any change to kpilqr_stream_io, _io2 or
  * _io3; an environment switch.  KPILQR_VERSION is unchanged: detect the call by its symbol.
- * (since: the explicit calls sweep a listed subset -- "Sweeps of a subset"; the chunks still sweep every trajectory.) */
+ * (since: the explicit calls sweep a listed subset -- "Sweeps of a subset"; the chunks still sweep every trajectory.)
+ * (since: kpilqr_iterate_streamed5, below, linearises and sweeps a listed subset inside the chunks.) */
 typedef struct {
     size_t struct_size;                         /* sizeof(kpilqr_stream_io4) as the caller compiled it                   */
     kpilqr_stream_io3 io3;                      /* every field as for kpilqr_iterate_streamed3 (inner struct_sizes checked as there) */
@@ -637,6 +640,62 @@ typedef struct {
     const int *upload_traj;                     /* NULL: whole-batch inputs, the call IS kpilqr_iterate_streamed3        */
 } kpilqr_stream_io4;
 int  kpilqr_iterate_streamed4(kpilqr_ctx *ctx, const kpilqr_stream_io4 *io4, int pd_check_stride, int nchunks);
+
+/* kpilqr_iterate_streamed4 linearising and SWEEPING a LISTED SUBSET of the batch inside the chunks -- what kpilqr_iterate_partial does
+ * for the explicit calls, in the chunk pipeline: the reference's loop does not sweep a finished trajectory again and a retry sweeps
+ * only those that failed (src/Optimiser/iLQR.cpp:419, :435-442); a host with that active set keeps the overlap and pays for the
+ * active trajectories alone.  struct_size must be sizeof(kpilqr_stream_io5) as the caller compiled it and the inner struct_sizes as
+ * for kpilqr_iterate_streamed4, else KPILQR_ERR_ARG.  `io4` is the struct of kpilqr_iterate_streamed4, every field with the meaning it
+ * has there unless said otherwise below; with sweep_traj = NULL the call IS kpilqr_iterate_streamed4 (one implementation, the same
+ * copies and launches in the same order; sweep_count is then ignored unless it is > 0, which is refused).
+ * The list.  sweep_traj [sweep_count] is strictly increasing and within [0, batch) (the rules of upload_traj and gain_traj); it is
+ * read during the call only and may be pageable.
+ * Semantics with a list.  Per chunk, the listed trajectories of that chunk are handled as kpilqr_iterate_partial handles them: on a
+ * context with records the launches of kpilqr_fd_interpolate_partial and kpilqr_cost_derivs_partial (the latter not where the tiled
+ * sweeps form the cost derivatives themselves), then the backward and the forward sweep, all for the listed alone.  No byte of an
+ * unlisted trajectory's K, k, status, delta_J, cost_pred, lambda, attempts or step records is written.
+ * Compact small arrays.  io.lambda [sweep_count] in list order, placed by one k_rows_in launch per chunk (NULL keeps the resident
+ * lambdas); io.cost_pred [sweep_count][n_alpha], io.delta_J and io.status [sweep_count]: nothing beyond sweep_count rows is written.
+ * K / K32 / k keep following gain_traj exactly as before -- without it the whole batch's resident gains -- and gain_traj is
+ * independent of sweep_traj.
+ * Uploads.  Inputs come with an upload_traj, which must be a subset of sweep_traj (a re-linearised trajectory is an active one): r,
+ * r_x, r_u, u_nom or a payload without upload_traj, or an upload_traj entry missing from sweep_traj (the error names it), is
+ * KPILQR_ERR_ARG, as is io.fd_slab.  The pending-range rule of kpilqr_iterate_streamed4 after kpilqr_update_keypoints is unchanged.
+ * sweep_count = 0 with a list: nothing is swept and nothing is uploaded; the gains of gain_traj still come down.
+ * State afterwards: that of kpilqr_update_keypoints' completion where ranges were pending, kpilqr_upload_*_partial for upload_traj,
+ * then kpilqr_iterate_partial for sweep_traj with the compact lambdas -- payload kind, validity flags, what a later
+ * kpilqr_update_keypoints relocates.  kpilqr_last_launch(ctx, 0|1|2) reports the forms with ":subset" last, on every kind of context.
+ * Fused contexts.  As in the explicit listed sweeps, a listed sweep reads the column store and never differences inside the sweep.
+ * The column and slope stores are reserved on the context before the chunks are cut.  Where a chunk's range of the column store is
+ * not valid (a raw fd_kp payload, in this call or resident) the chunk runs the differencing and slope launches over its own entry
+ * range on its own stream, whoever is listed in it; the store is then valid for everybody.  KPILQR_FLAG_UNION_KEYPOINTS is ignored.
+ * Form.  What only arranges waves follows the length of the chunk's slice of the list on the chunk's share of the SIMDs, as it
+ * follows the chunk's width without a list; what decides which stores exist stays the context's.
+ * Lambda retry composes as in kpilqr_iterate_partial, per chunk: the schedule arms listed trajectories only, and the number of
+ * attempts launched follows the chunk's slice of the compact lambdas (io.lambda = NULL: max_attempts).
+ * Rejections, all before anything is enqueued or the context is changed (a context in the constant-Jacobian mode stays in it):
+ * KPILQR_ERR_ARG for ctx = NULL or io5 = NULL, a wrong outer or inner struct_size, sweep_count < 0, sweep_count > 0 with a NULL list,
+ * a list out of order or out of range, pd_check_stride < 1 and the cases above; KPILQR_ERR_STATE before any key-points exist.  Every
+ * refusal of the older calls keeps its code.
+ * How.  Everything on the chunk's own stream.  Chunks and list both increase, so a chunk's share is one slice of the list.  The view
+ * the launchers get holds the context's unshifted per-trajectory pointers, the slice of the device copy of the list, the slice length
+ * as its batch, the chunk's stream and its share of the SIMDs.  A chunk without listed trajectories launches nothing but its share of
+ * the gain download.  The compact outputs leave by one gathering launch per chunk and array (k_rows_out, rows_in.hip) straight into
+ * the caller's pinned buffer -- the route of k_gains_out: no staging buffer, no second DMA.  The list's pinned mirror and device copy
+ * are a ring of four as for upload_traj: two consecutive calls with different sweep lists overlap without a wait.  Memory: 4 ints
+ * per trajectory on the device and as many pinned for that ring, reserved by the first call with a non-empty sweep list; a context that never passes one allocates and
+ * launches nothing new.
+ * Out of scope: differencing inside a listed sweep, or proportional to the list; job-list payloads with any list;
+ * KPILQR_FLAG_UNION_KEYPOINTS in the chunks; the host classes and the batch shim; any change to kpilqr_stream_io ... _io4; an
+ * environment switch.  KPILQR_VERSION is unchanged: detect the call by its symbol.  (profiles/streamed_subset_sweeps.txt holds the
+ * byte and launch model and says what was measured.) */
+typedef struct {
+    size_t struct_size;                         /* sizeof(kpilqr_stream_io5) as the caller compiled it                   */
+    kpilqr_stream_io4 io4;                      /* every field as for kpilqr_iterate_streamed4 (inner struct_sizes checked as there) */
+    int sweep_count;                            /* with sweep_traj: number of listed trajectories                        */
+    const int *sweep_traj;                      /* NULL: every trajectory is swept, the call IS kpilqr_iterate_streamed4 */
+} kpilqr_stream_io5;
+int  kpilqr_iterate_streamed5(kpilqr_ctx *ctx, const kpilqr_stream_io5 *io5, int pd_check_stride, int nchunks);
 
 /* Differencing tail of Differentiator::DynamicsDerivatives (:166-222,286-321,386-423,441-457):
  * writes the key-point columns of A and B. */

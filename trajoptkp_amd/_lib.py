@@ -34,6 +34,7 @@ SYMBOLS = [
     "kpilqr_download_gains_f32", "kpilqr_download_gains_f32_partial", "kpilqr_iterate_streamed2",
     "kpilqr_set_lambda_retry", "kpilqr_download_lambda_retry",
     "kpilqr_upload_kp_columns_f32", "kpilqr_upload_kp_columns_f32_partial", "kpilqr_iterate_streamed3", "kpilqr_iterate_streamed4",
+    "kpilqr_iterate_streamed5",
     "kpilqr_backward_partial", "kpilqr_forward_linear_partial", "kpilqr_iterate_partial",
     "kpilqr_upload_states_partial", "kpilqr_generate_keypoints_partial", "kpilqr_get_keypoints_partial",
 ]
@@ -46,7 +47,7 @@ OPTIONAL_SYMBOLS = {"kpilqr_fd_interpolate", "kpilqr_get_union_keypoints", "kpil
                     "kpilqr_download_gains_f32", "kpilqr_download_gains_f32_partial", "kpilqr_iterate_streamed2",
                     "kpilqr_set_lambda_retry", "kpilqr_download_lambda_retry",
                     "kpilqr_upload_kp_columns_f32", "kpilqr_upload_kp_columns_f32_partial", "kpilqr_iterate_streamed3",
-                    "kpilqr_iterate_streamed4",
+                    "kpilqr_iterate_streamed4", "kpilqr_iterate_streamed5",
                     "kpilqr_backward_partial", "kpilqr_forward_linear_partial", "kpilqr_iterate_partial",
                     "kpilqr_upload_states_partial", "kpilqr_generate_keypoints_partial", "kpilqr_get_keypoints_partial"}
 
@@ -86,6 +87,11 @@ class StreamIO3(C.Structure):
 class StreamIO4(C.Structure):
     """kpilqr_stream_io4: StreamIO3 with the list of trajectories whose inputs come up; struct_size = sizeof(StreamIO4)"""
     _fields_ = [("struct_size", C.c_size_t), ("io3", StreamIO3), ("upload_count", C.c_int), ("upload_traj", C.c_void_p)]
+
+
+class StreamIO5(C.Structure):
+    """kpilqr_stream_io5: StreamIO4 with the list of trajectories that are linearised and swept; struct_size = sizeof(StreamIO5)"""
+    _fields_ = [("struct_size", C.c_size_t), ("io4", StreamIO4), ("sweep_count", C.c_int), ("sweep_traj", C.c_void_p)]
 
 
 class LambdaRetry(C.Structure):
@@ -208,6 +214,8 @@ def load():
         L.kpilqr_iterate_streamed3.argtypes = [vp, C.POINTER(StreamIO3), C.c_int, C.c_int]
     if hasattr(L, "kpilqr_iterate_streamed4"):
         L.kpilqr_iterate_streamed4.argtypes = [vp, C.POINTER(StreamIO4), C.c_int, C.c_int]
+    if hasattr(L, "kpilqr_iterate_streamed5"):
+        L.kpilqr_iterate_streamed5.argtypes = [vp, C.POINTER(StreamIO5), C.c_int, C.c_int]
     if hasattr(L, "kpilqr_backward_partial"):
         L.kpilqr_backward_partial.argtypes = [vp, C.c_int, vp, vp, C.c_int, vp, vp]
         L.kpilqr_forward_linear_partial.argtypes = [vp, C.c_int, vp, vp, vp, vp]

@@ -280,6 +280,15 @@ struct Ctx {
     bool rows_read_set[kRowsRing][kPipeStreams] = {};
     int rows_next = 0;
     size_t rows_pay_rec = 0;               // bytes per entry of the payload last staged in rows_stage[kRowsPayload] (records | FP64 columns)
+    // kpilqr_iterate_streamed5 with sweep_traj: the list the chunks' LISTED sweep launches, k_rows_in (the compact lambdas) and
+    // k_rows_out (the compact small outputs) read.  The same ring scheme, [kRowsRing][batch] ints, reserved by the first call that
+    // carries a non-empty sweep list and by nobody else.
+    DevBuf<int> sweep_ring;                // [kRowsRing][batch]
+    int *sweep_ring_host = nullptr;        // [kRowsRing][batch], pinned
+    hipEvent_t sweep_up[kRowsRing] = {};
+    hipEvent_t sweep_read[kRowsRing][kPipeStreams] = {};
+    bool sweep_read_set[kRowsRing][kPipeStreams] = {};
+    int sweep_next = 0;
 
     // staging for debug hooks / U_alpha
     DevBuf<double> stage;
@@ -294,7 +303,7 @@ struct Ctx {
         DevMem *const all[] = {&rec, &kp_uniform, &K, &k, &r, &r_x, &r_u, &w_run, &w_term, &u_nom, &ctrl_lim, &lambda, &alphas, &cost_pred,
                                &delta_J, &traj_cost, &status, &attempts, &gate, &traj_list, &K32, &segmap, &segent, &kp_offsets, &kp_times, &rx_const, &kpc, &kpc32, &kps, &kp_entry,
                                &kp_entry_list, &fdk_dev, &kpu_offsets, &kpu_times, &kpu_src, &kpu_traj_first, &kpcu, &kpu_uniform, &fdk_alt, &kpc_alt, &kp_times_alt, &kp_upl_times, &kp_move, &X_states, &kp_thr, &kp_mask, &kp_count, &ls8, &fd_dev, &err_flag, &stage, &sweep_stage, &pipe_list,
-                               &rows_stage[0], &rows_stage[1], &rows_stage[2], &rows_stage[3], &rows_stage[4], &rows_list};
+                               &rows_stage[0], &rows_stage[1], &rows_stage[2], &rows_stage[3], &rows_stage[4], &rows_list, &sweep_ring};
         for (DevMem *b : all) f(*b);
     }
 
@@ -414,7 +423,9 @@ hipError_t launch_lambda_retry_begin(Ctx *c);
 hipError_t launch_lambda_retry(Ctx *c);
 hipError_t launch_gate_arm(Ctx *c);                      // gate = 1 for the listed trajectories: a listed sweep without a schedule
 // rows_in.hip, the mirror image of launch_rows_in for the small per-trajectory outputs of the listed sweeps (status, delta_J, cost_pred):
-// `count` rows of `words` 4-byte words, row traj[i] (device) of src -> row i of staging
+// `count` rows of `words` 4-byte words, row traj[i] (device) of src -> row i of staging.  The chunks of kpilqr_iterate_streamed5 pass
+// the caller's mapped pinned rows for `staging` (the route of launch_gains_out: no staging buffer, no second DMA), and to
+// launch_rows_in, for their few compact lambdas, the caller's pinned rows as its source.
 hipError_t launch_rows_out(hipStream_t s, const int *traj, int count, int words, const void *src, void *staging);
 // comm.cpp (RCCL opened lazily) and the pack kernel of elementwise.hip
 const char *comm_unique_id(char *id128);

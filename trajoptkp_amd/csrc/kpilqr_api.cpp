@@ -674,6 +674,11 @@ void kpilqr_destroy(kpilqr_ctx *c)
         if (c->rows_up[i]) (void)hipEventDestroy(c->rows_up[i]);
         for (hipEvent_t e : c->rows_read[i]) if (e) (void)hipEventDestroy(e);
     }
+    if (c->sweep_ring_host) (void)hipHostFree(c->sweep_ring_host);
+    for (int i = 0; i < Ctx::kRowsRing; i++) {
+        if (c->sweep_up[i]) (void)hipEventDestroy(c->sweep_up[i]);
+        for (hipEvent_t e : c->sweep_read[i]) if (e) (void)hipEventDestroy(e);
+    }
     forget_lists(c);
     free(c->states_given_host);
     if (c->kpu_traj_first_host) free(c->kpu_traj_first_host);
@@ -2079,47 +2084,57 @@ static int columns_for_listed_sweep(kpilqr_ctx *c)
     return KPILQR_OK;
 }
 
+// The launches of a listed backward / forward sweep on the list view v -- of the context (make_list_view) or of a chunk of a streamed
+// iteration (make_chunk_list_view) -- behind everything that may allocate; c, the context, records what ran.
+static int launch_backward_listed(kpilqr_ctx *c, kpilqr_ctx *v, int pd_stride)
+{
+    c->last_width[0] = v->d.batch;
+    if (c->fused) {
+        const FusedLaunch plan = c->last_bwd = plan_backward_fused(v, false);
+        return sweep_attempts(c, v, [&] { return launch_backward_fused(v, plan, pd_stride); });
+    }
+    c->last_bwd = FusedLaunch{};
+    return sweep_attempts(c, v, [&] { return launch_backward_family(v, pd_stride); });
+}
+
+static int launch_forward_listed(kpilqr_ctx *c, kpilqr_ctx *v, double *U_dev)
+{
+    c->last_width[1] = v->d.batch;
+    if (c->fused) {
+        const FusedLaunch plan = c->last_fwd = plan_forward_fused(v);
+        KP_HIP(c, launch_forward_fused(v, plan, U_dev));
+    } else {
+        c->last_fwd = FusedLaunch{};
+        KP_HIP(c, launch_forward_family(v, U_dev));
+    }
+    c->last_fwd.fwd_ran = true;
+    return KPILQR_OK;
+}
+
+// the broadcast copy of constant residual Jacobians, where a listed sweep streams r_x (a plan's rxc does not depend on the launch width)
+static int rx_buffer_for_listed_sweep(kpilqr_ctx *c, bool backward)
+{
+    const bool streams_rx = c->fused ? !(backward ? plan_backward_fused(c, false) : plan_forward_fused(c)).rxc : c->tiled_a6;
+    return streams_rx ? ensure_rx_buffer(c) : KPILQR_OK;
+}
+
 // the list is on the device (traj_list) and checked
 static int run_backward_listed(kpilqr_ctx *c, int count, int pd_stride)
 {
+    if (c->fused) { const int rc = columns_for_listed_sweep(c); if (rc) return rc; }
+    { const int rc = rx_buffer_for_listed_sweep(c, true); if (rc) return rc; }
     kpilqr_ctx v;
-    if (c->fused) {
-        int rc = columns_for_listed_sweep(c);
-        if (rc) return rc;
-        make_list_view(c, count, &v);
-        const FusedLaunch plan = c->last_bwd = plan_backward_fused(&v, false);
-        if (!plan.rxc) { rc = ensure_rx_buffer(c); if (rc) return rc; make_list_view(c, count, &v); }
-        c->last_width[0] = count;
-        return sweep_attempts(c, &v, [&] { return launch_backward_fused(&v, plan, pd_stride); });
-    }
-    c->last_bwd = FusedLaunch{};
-    if (c->tiled_a6) { const int rc = ensure_rx_buffer(c); if (rc) return rc; }
     make_list_view(c, count, &v);
-    c->last_width[0] = count;
-    return sweep_attempts(c, &v, [&] { return launch_backward_family(&v, pd_stride); });
+    return launch_backward_listed(c, &v, pd_stride);
 }
 
 static int run_forward_listed(kpilqr_ctx *c, int count, double *U_dev)
 {
+    if (c->fused) { const int rc = columns_for_listed_sweep(c); if (rc) return rc; }
+    { const int rc = rx_buffer_for_listed_sweep(c, false); if (rc) return rc; }
     kpilqr_ctx v;
-    if (c->fused) {
-        int rc = columns_for_listed_sweep(c);
-        if (rc) return rc;
-        make_list_view(c, count, &v);
-        const FusedLaunch plan = c->last_fwd = plan_forward_fused(&v);
-        if (!plan.rxc) { rc = ensure_rx_buffer(c); if (rc) return rc; make_list_view(c, count, &v); }
-        c->last_width[1] = count;
-        KP_HIP(c, launch_forward_fused(&v, plan, U_dev));
-        c->last_fwd.fwd_ran = true;
-        return KPILQR_OK;
-    }
-    c->last_fwd = FusedLaunch{};
-    if (c->tiled_a6) { const int rc = ensure_rx_buffer(c); if (rc) return rc; }
     make_list_view(c, count, &v);
-    c->last_width[1] = count;
-    KP_HIP(c, launch_forward_family(&v, U_dev));
-    c->last_fwd.fwd_ran = true;
-    return KPILQR_OK;
+    return launch_forward_listed(c, &v, U_dev);
 }
 
 // the list and the compact lambdas to the device; the lambdas placed by ONE launch
@@ -2279,7 +2294,7 @@ struct StreamList {
 // The FD payload a streamed iteration brings, decided once (at the "one FD payload per iteration" refusal of stream_check)
 enum class StreamPayload { none, jobs, kp_ordered, columns, columns_f32 };
 
-// A streamed iteration, resolved: what the four entry points ask for (they fill the first group), what stream_check decides about the
+// A streamed iteration, resolved: what the five entry points ask for (they fill the first group), what stream_check decides about the
 // payload, and where stream_prepare found the device side of it.  The three kinds by key-point entry (kp_ordered, columns,
 // columns_f32) differ in the fields below and in nothing else: a chunk copies ONE contiguous range of `rec` bytes per entry from
 // `src` to `land` at its own first entry, and one launch may follow (stream_chunk_payload).
@@ -2290,6 +2305,7 @@ struct StreamCall {
     StreamList gains;                  // kpilqr_iterate_streamed2: K / K32 / k of those rows alone, compact
     const float *kcols32 = nullptr;    // kpilqr_iterate_streamed3: the ENCODED FP32 key-point columns (kpilqr_upload_kp_columns_f32) for a payload
     StreamList rows;                   // kpilqr_iterate_streamed4: the inputs (payload, r, r_x, r_u, u_nom) of those trajectories alone, compact; read during the call only
+    StreamList sweep;                  // kpilqr_iterate_streamed5: the linearisation and the sweeps of those trajectories alone; lambda, cost_pred, delta_J, status compact
     // stream_check
     StreamPayload kind = StreamPayload::none;
     const char *src = nullptr;         // by entry: the host source ...
@@ -2300,6 +2316,8 @@ struct StreamCall {
     void *place = nullptr;             // FP64 of a list: where launch_rows_in_entries moves the listed ranges from `land` (fdk_dev | kpc)
     const int *ulist = nullptr, *ufirst = nullptr;      // rows: the list and the per-trajectory first entries on the device (its ring slot)
     int uslot = 0;
+    const int *slist = nullptr;        // sweep: the list on the device (its ring slot)
+    int sslot = 0;
     bool k_up = false, k_down = false; // copies by kernel (KPILQR_PIPE_COPY)
     StreamCall(const kpilqr_stream_io *io_, int stride, int chunks) : io(io_), pd_check_stride(stride), nchunks(chunks) {}
     bool by_entry() const { return kind != StreamPayload::none && kind != StreamPayload::jobs; }
@@ -2386,6 +2404,33 @@ static int rows_list_bind(kpilqr_ctx *c, const StreamList &u, int nchunks, bool 
     return KPILQR_OK;
 }
 
+// The same for the sweep list of kpilqr_iterate_streamed5: the list alone, [batch] ints per slot of its own ring.  -> *slot_out
+static int sweep_list_bind(kpilqr_ctx *c, const StreamList &w, int *slot_out)
+{
+    const int slot = c->sweep_next;
+    const size_t per_slot = (size_t)c->d.batch;
+    if (!c->sweep_ring_host) {
+        { const int rc = reserve(c, c->sweep_ring, Ctx::kRowsRing * per_slot * sizeof(int), kExact, false); if (rc < 0) return rc; }
+        const hipError_t e = hipHostMalloc((void **)&c->sweep_ring_host, Ctx::kRowsRing * per_slot * sizeof(int), hipHostMallocDefault);
+        if (e != hipSuccess) { c->sweep_ring_host = nullptr; return set_err(c, KPILQR_ERR_ALLOC, std::string("hipHostMalloc failed: ") + hipGetErrorString(e)); }
+    }
+    if (!c->sweep_up[slot]) {
+        KP_HIP(c, hipEventCreateWithFlags(&c->sweep_up[slot], hipEventDisableTiming));
+        for (int i = 0; i < Ctx::kPipeStreams; i++) KP_HIP(c, hipEventCreateWithFlags(&c->sweep_read[slot][i], hipEventDisableTiming));
+    } else {
+        KP_HIP(c, hipEventSynchronize(c->sweep_up[slot]));
+    }
+    for (int i = 0; i < Ctx::kPipeStreams; i++)
+        if (c->sweep_read_set[slot][i]) { KP_HIP(c, hipStreamWaitEvent(c->stream, c->sweep_read[slot][i], 0)); c->sweep_read_set[slot][i] = false; }
+    int *const list = c->sweep_ring_host + slot * per_slot;
+    memcpy(list, w.traj, sizeof(int) * (size_t)w.count);
+    KP_HIP(c, hipMemcpyAsync((int *)c->sweep_ring + slot * per_slot, list, sizeof(int) * (size_t)w.count, hipMemcpyHostToDevice, c->stream));
+    KP_HIP(c, hipEventRecord(c->sweep_up[slot], c->stream));
+    c->sweep_next = (slot + 1) % Ctx::kRowsRing;
+    *slot_out = slot;
+    return KPILQR_OK;
+}
+
 // Phase 1 of a streamed iteration -- EVERY refusal, before a single operation is enqueued or the context is changed: nothing here
 // writes to *c but set_err (and the join ahead of check_complete, which orders streams and changes no derived state).  It decides the
 // payload's kind, and for job lists returns in *sig the FNV-1a hash of what decides where a chunk's payload lands.
@@ -2443,6 +2488,21 @@ static int stream_check(kpilqr_ctx *c, StreamCall *call, unsigned long long *sig
             if (i == u.count || u.traj[i] != b)
                 return set_err(c, KPILQR_ERR_STATE, w + ": the payload of trajectory " + std::to_string(b) + " is pending since kpilqr_update_keypoints "
                                                         "and upload_traj does not list it");
+        }
+    }
+    // sweeps that follow a list (kpilqr_iterate_streamed5 with sweep_traj): a re-linearised trajectory is an active one, so whatever
+    // comes up comes with an upload list inside the sweep list (both lists increase)
+    const StreamList &sw = call->sweep;
+    if (sw.listed) {
+        static const std::string w5("kpilqr_iterate_streamed5");
+        if (!kp_traj_list_ok(B, sw.count, sw.traj)) return set_err(c, KPILQR_ERR_ARG, w5 + ": sweep_traj must be strictly increasing and within [0, batch)");
+        if (io->fd_slab) return set_err(c, KPILQR_ERR_ARG, w5 + ": io.fd_slab with sweep_traj (job lists carry their own trajectory indices: out of scope)");
+        if (!u.listed && (call->kind != StreamPayload::none || io->r || io->r_x || io->r_u || io->u_nom))
+            return set_err(c, KPILQR_ERR_ARG, w5 + ": inputs with sweep_traj come with an upload_traj inside it");
+        for (int i = 0, j = 0; i < u.count; i++) {
+            while (j < sw.count && sw.traj[j] < u.traj[i]) j++;
+            if (j == sw.count || sw.traj[j] != u.traj[i])
+                return set_err(c, KPILQR_ERR_ARG, w5 + ": upload_traj lists trajectory " + std::to_string(u.traj[i]) + ", which sweep_traj does not (a re-linearised trajectory is an active one)");
         }
     }
     // (the refusals of kpilqr_upload_residuals_partial, in its words)
@@ -2579,8 +2639,15 @@ static int stream_prepare(kpilqr_ctx *c, StreamCall *call, unsigned long long si
         rc = ensure_entry_tables(c); if (rc) return rc;
     }
     if (!c->fused && by_entry && c->tune.fd_interp != 0) { rc = ensure_segent(c); if (rc) return rc; }
+    const StreamList &sw = call->sweep;
+    // a listed chunk reads, or differences, its own entry range of a payload laid out by the lists: the host has to know them
+    if (sw.listed && payload_by_entry(c) && !c->kp_traj_first_host) {
+        rc = ensure_offsets_mirror(c); if (rc) return rc;
+        if (!remember_traj_first(c, c->kp_offsets_host)) return set_err(c, KPILQR_ERR_ALLOC, "host allocation failed");
+    }
     if (c->fused) {
-        c->last_linearise = "in_sweep";
+        if (!sw.listed) c->last_linearise = "in_sweep";
+        else if (sw.count > 0) c->last_linearise = "in_sweep:subset";
         // per-DoF lists: a chunk computes the slopes of ITS entries, whose range only the host copy of the lists gives
         if (!c->kp_known_uniform && !c->kp_traj_first_host)
             return set_err(c, KPILQR_ERR_STATE, "kpilqr_iterate_streamed with per-DoF key-point lists: the lists must be known to the host (kpilqr_set_keypoints, or kpilqr_get_keypoints after generating them)");
@@ -2597,9 +2664,16 @@ static int stream_prepare(kpilqr_ctx *c, StreamCall *call, unsigned long long si
     // by an ordinary call (kpilqr_upload_fd_kp, a partial upload behind kpilqr_update_keypoints ...) and not linearised yet is
     // written into the records HERE, for the whole batch, behind the chunks of any earlier iteration (rec_synced is cleared by
     // payload_changed, so this is the first sweep since that upload: the join costs an overlap nobody had).
-    if (!c->fused && !new_payload && !c->pay.rec_synced) {
+    if (!c->fused && !new_payload && !c->pay.rec_synced && !sw.listed) {
         rc = join_pipeline(c); if (rc) return rc;
         rc = records_from_payload(c); if (rc) return rc;
+    }
+    // A sweep list on a context with records: the chunks linearise their listed trajectories as kpilqr_fd_interpolate_partial does,
+    // from the resident payload, and nobody else's records are written.  Resident job lists are differenced HERE, once (a chunk view
+    // has no jobs), whoever they belong to -- that call's rule -- behind the chunks of any earlier iteration.
+    if (!c->fused && sw.listed && sw.count > 0 && c->fd_payload == FdPayload::jobs) {
+        rc = join_pipeline(c); if (rc) return rc;
+        KP_HIP(c, launch_fd_difference(c));
     }
     // Per-step Jacobians in this call end the constant mode -- recorded only HERE, behind every check that can still reject the
     // call (a rejected call must leave the context as it was: round-4 advisor; before, a call refused for an unpinned buffer had
@@ -2617,6 +2691,11 @@ static int stream_prepare(kpilqr_ctx *c, StreamCall *call, unsigned long long si
         rc = rows_list_bind(c, u, call->nchunks, new_payload, &call->uslot); if (rc) return rc;
         call->ulist = (const int *)c->rows_list + (size_t)call->uslot * 2 * B; call->ufirst = call->ulist + B;
     }
+    // the list of the trajectories that are swept, in a slot of its own ring (an empty list launches nothing that reads one)
+    if (sw.listed && sw.count > 0) {
+        rc = sweep_list_bind(c, sw, &call->sslot); if (rc) return rc;
+        call->slist = (const int *)c->sweep_ring + (size_t)call->sslot * B;
+    }
     // where a chunk's range of a by-entry payload lands, now that every buffer is there
     char *const stage = c->rows_stage[Ctx::kRowsPayload];
     if (call->kind == StreamPayload::kp_ordered) { call->place = c->fdk_dev.p; call->land = u.listed ? stage : (char *)c->fdk_dev.p; }
@@ -2630,13 +2709,14 @@ static int stream_prepare(kpilqr_ctx *c, StreamCall *call, unsigned long long si
     return KPILQR_OK;
 }
 
-// One chunk of a streamed iteration: trajectories [b0, b1) as the view v on stream s, and its slices of the upload list
+// One chunk of a streamed iteration: trajectories [b0, b1) as the view v on stream s, and its slices of the upload and sweep lists
 struct StreamChunk {
     int ch = 0, b0 = 0, b1 = 0;
     hipStream_t s = nullptr;
     kpilqr_ctx v;
     int u0 = 0, urows = 0;             // inputs of a list: rows [u0, u0 + urows) of every compact input ...
     size_t uent0 = 0, uents = 0;       // ... and, of a by-entry payload, `uents` entries from entry uent0 on
+    int s0 = 0, srows = 0;             // sweeps of a list: entries [s0, s0 + srows) of the sweep list, and of every compact small array
 };
 
 // The chunk's FD payload: uploaded, and the view told what it holds
@@ -2716,13 +2796,68 @@ static int stream_chunk_rows(kpilqr_ctx *c, const StreamCall &call, StreamChunk 
         KP_HIP(c, hipEventRecord(c->rows_read[call.uslot][k.ch % Ctx::kPipeStreams], k.s));
         c->rows_read_set[call.uslot][k.ch % Ctx::kPipeStreams] = true;
     }
-    if (io->lambda) KP_HIP(c, call.h2d(k.v.lambda, io->lambda + o, cnt * 8, k.s));
+    // the lambdas: the chunk's own, or with a sweep list its slice of the compact ones, placed by ONE launch of k_rows_in that reads the
+    // caller's pinned rows itself (a few doubles: no staging region, no ring)
+    if (io->lambda && !call.sweep.listed) KP_HIP(c, call.h2d(k.v.lambda, io->lambda + o, cnt * 8, k.s));
+    if (io->lambda && call.sweep.listed) KP_HIP(c, launch_rows_in(k.s, call.slist + k.s0, k.srows, 1, io->lambda + k.s0, c->lambda));
     return KPILQR_OK;
+}
+
+// A chunk's list view: make_view and make_list_view combined.  The context's unshifted per-trajectory pointers and whole payload,
+// block i of a launch finds its trajectory through `list` -- the chunk's slice of the device copy of the sweep list, `count` long:
+// the launch width -- on the chunk's stream and the chunk's share of the SIMDs; what the chunk did to the payload-derived state so far.
+static void make_chunk_list_view(const kpilqr_ctx *c, const kpilqr_ctx &chunk, const int *list, int count, kpilqr_ctx *v)
+{
+    *v = *c;
+    v->is_view = true;
+    v->own_stream = false;
+    v->stream = chunk.stream;
+    v->n_simd = chunk.n_simd;
+    v->pay = chunk.pay;
+    v->d.batch = count;
+    v->sweep_list = list;
+}
+
+// The chunk's kernels with a sweep list: what kpilqr_iterate_partial launches for the chunk's slice of the list, on the chunk's stream
+static int stream_chunk_sweeps_listed(kpilqr_ctx *c, const StreamCall &call, StreamChunk &k)
+{
+    const kpilqr_stream_io *io = call.io;
+    kpilqr_ctx &v = k.v;
+    const auto of = [&](const kpilqr_ctx &w, int rcv) { if (rcv) c->err = w.err; return rcv; };      // a view's refusal is the context's
+    int rc;
+    // The chunk's entry range of the column store, where the listed launches read it: a listed sweep never differences inside the
+    // sweep (columns_for_listed_sweep), and under KPILQR_FD_INTERP=0 the records' key-point steps are written from it.  A range
+    // that is not valid is differenced here, whoever is listed: every chunk leaves its range valid, so the store is for the context.
+    const bool one_pass = !c->fused && linearise_one_pass(&v);
+    if (c->fused) rc = of(v, columns_for_listed_sweep(&v));
+    else rc = (!one_pass && payload_by_entry(&v) && !v.pay.kpc_valid) ? of(v, difference_to_kpc(&v)) : KPILQR_OK;
+    if (rc) return rc;
+    if (!k.srows) return KPILQR_OK;
+    const int *const list = call.slist + k.s0;
+    kpilqr_ctx lv;
+    make_chunk_list_view(c, v, list, k.srows, &lv);
+    if (!c->fused) {
+        // kpilqr_fd_interpolate_partial's launches, then kpilqr_cost_derivs_partial's
+        if (one_pass) {
+            KP_HIP(c, launch_fd_kp_interpolate(&lv, list, k.srows));
+            c->last_linearise = c->fd_payload == FdPayload::kp_columns ? "kp_columns_interpolate:subset" : "fd_kp_interpolate:subset";
+        } else {
+            if (payload_by_entry(c)) { rc = of(lv, kpc_to_records_of(&lv, k.srows, call.sweep.traj + k.s0)); if (rc) return rc; }
+            KP_HIP(c, launch_interpolate(&lv, list, k.srows));
+            c->last_linearise = "fd_difference+interpolate:subset";
+        }
+        if (!c->tiled_a6) KP_HIP(c, launch_cost_derivs(&lv, list, k.srows));
+    }
+    c->retry_attempts = retry_attempts_for(c, io->lambda ? io->lambda + k.s0 : nullptr, (size_t)k.srows);      // (the slice's own lambdas decide its attempts)
+    rc = launch_backward_listed(c, &lv, call.pd_check_stride);
+    if (rc) return rc;
+    return launch_forward_listed(c, &lv, nullptr);
 }
 
 // The chunk's kernels: the ordinary launchers on the view
 static int stream_chunk_sweeps(kpilqr_ctx *c, const StreamCall &call, StreamChunk &k)
 {
+    if (call.sweep.listed) return stream_chunk_sweeps_listed(c, call, k);
     const kpilqr_stream_io *io = call.io;
     kpilqr_ctx &v = k.v;
     const size_t o = k.b0, cnt = k.b1 - k.b0;
@@ -2742,6 +2877,7 @@ static int stream_chunk_sweeps(kpilqr_ctx *c, const StreamCall &call, StreamChun
     rc = of_view(run_forward(&v, nullptr));
     if (rc) return rc;
     c->last_bwd = v.last_bwd; c->last_fwd = v.last_fwd;
+    c->last_width[0] = c->last_width[1] = -1;      // (whole chunks: not a listed launch, whatever ran before)
     return KPILQR_OK;
 }
 
@@ -2772,6 +2908,20 @@ static int stream_chunk_down(kpilqr_ctx *c, StreamCall &call, StreamChunk &k)
     };
     if (io->K && !gather) KP_HIP(c, d2h(io->K + o * per.K, v.K, cnt * per.K));
     if (io->k && !g.listed) KP_HIP(c, d2h(io->k + o * per.k, v.k, cnt * per.k));
+    if (call.sweep.listed) {
+        // the small outputs of a sweep list: the chunk's slice of the compact arrays, gathered by ONE launch per array straight into
+        // the caller's pinned rows (the route of k_gains_out: no staging buffer, no second DMA)
+        if (!k.srows) return KPILQR_OK;
+        const int *const list = call.slist + k.s0;
+        const size_t i0 = (size_t)k.s0;
+        if (io->cost_pred) KP_HIP(c, launch_rows_out(s, list, k.srows, 2 * (int)na, (const double *)c->cost_pred, io->cost_pred + i0 * na));
+        if (io->delta_J) KP_HIP(c, launch_rows_out(s, list, k.srows, 2, (const double *)c->delta_J, io->delta_J + i0));
+        if (io->status) KP_HIP(c, launch_rows_out(s, list, k.srows, 1, (const int *)c->status, io->status + i0));
+        // (the slot of the sweep list may be written again once this stream has passed here)
+        KP_HIP(c, hipEventRecord(c->sweep_read[call.sslot][k.ch % Ctx::kPipeStreams], s));
+        c->sweep_read_set[call.sslot][k.ch % Ctx::kPipeStreams] = true;
+        return KPILQR_OK;
+    }
     if (io->cost_pred) KP_HIP(c, hipMemcpyAsync(io->cost_pred + o * na, v.cost_pred, cnt * na * 8, hipMemcpyDeviceToHost, s));
     if (io->delta_J) KP_HIP(c, hipMemcpyAsync(io->delta_J + o, v.delta_J, cnt * 8, hipMemcpyDeviceToHost, s));
     if (io->status) KP_HIP(c, hipMemcpyAsync(io->status + o, v.status, cnt * 4, hipMemcpyDeviceToHost, s));
@@ -2809,6 +2959,9 @@ static int iterate_streamed(kpilqr_ctx *c, StreamCall call)
         if (call.by_entry())
             for (int i = k.u0; i < u1; i++) uent += (size_t)(c->kp_traj_first_host[u.traj[i] + 1] - c->kp_traj_first_host[u.traj[i]]);
         k.uents = uent - k.uent0;
+        int s1 = 0;
+        if (call.sweep.listed) call.sweep.slice_below(k.b1, &k.s0, &s1);
+        k.srows = s1 - k.s0;
         rc = stream_chunk_payload(c, call, k); if (rc) return rc;
         rc = stream_chunk_rows(c, call, k); if (rc) return rc;
         rc = stream_chunk_sweeps(c, call, k); if (rc) return rc;
@@ -2855,18 +3008,38 @@ int kpilqr_iterate_streamed3(kpilqr_ctx *c, const kpilqr_stream_io3 *io3, int pd
 }
 
 // kpilqr_iterate_streamed3 taking the inputs of a list of trajectories alone: with upload_traj == NULL it IS that call
-int kpilqr_iterate_streamed4(kpilqr_ctx *c, const kpilqr_stream_io4 *io4, int pd_check_stride, int nchunks)
+// the checks and the options of a kpilqr_stream_io4, for the two calls that carry one (call->io is &io4->io3.io2.io)
+static int stream_rows_of(kpilqr_ctx *c, const kpilqr_stream_io4 *io4, StreamCall *call)
 {
-    if (!c || !io4) return KPILQR_ERR_ARG;
     if (io4->struct_size != sizeof(kpilqr_stream_io4)) return set_err(c, KPILQR_ERR_ARG, "kpilqr_iterate_streamed4: struct_size is not sizeof(kpilqr_stream_io4) of this library");
     const kpilqr_stream_io3 *io3 = &io4->io3;
     if (io3->struct_size != sizeof(kpilqr_stream_io3)) return set_err(c, KPILQR_ERR_ARG, "kpilqr_iterate_streamed3: struct_size is not sizeof(kpilqr_stream_io3) of this library");
     if (io4->upload_count < 0 || (io4->upload_count > 0 && !io4->upload_traj))
         return set_err(c, KPILQR_ERR_ARG, "kpilqr_iterate_streamed4: upload_count < 0, or listed trajectories without upload_traj");
-    StreamCall call(&io3->io2.io, pd_check_stride, nchunks);
-    if (const int rc = stream_gains_of(c, &io3->io2, &call)) return rc;
-    call.kcols32 = io3->kp_columns32;
-    call.rows.listed = io4->upload_traj != nullptr; call.rows.count = call.rows.listed ? io4->upload_count : 0; call.rows.traj = io4->upload_traj;
+    if (const int rc = stream_gains_of(c, &io3->io2, call)) return rc;
+    call->kcols32 = io3->kp_columns32;
+    call->rows.listed = io4->upload_traj != nullptr; call->rows.count = call->rows.listed ? io4->upload_count : 0; call->rows.traj = io4->upload_traj;
+    return KPILQR_OK;
+}
+
+int kpilqr_iterate_streamed4(kpilqr_ctx *c, const kpilqr_stream_io4 *io4, int pd_check_stride, int nchunks)
+{
+    if (!c || !io4) return KPILQR_ERR_ARG;
+    StreamCall call(&io4->io3.io2.io, pd_check_stride, nchunks);
+    if (const int rc = stream_rows_of(c, io4, &call)) return rc;
+    return iterate_streamed(c, call);
+}
+
+// kpilqr_iterate_streamed4 linearising and sweeping a list of trajectories alone: with sweep_traj == NULL it IS that call
+int kpilqr_iterate_streamed5(kpilqr_ctx *c, const kpilqr_stream_io5 *io5, int pd_check_stride, int nchunks)
+{
+    if (!c || !io5) return KPILQR_ERR_ARG;
+    if (io5->struct_size != sizeof(kpilqr_stream_io5)) return set_err(c, KPILQR_ERR_ARG, "kpilqr_iterate_streamed5: struct_size is not sizeof(kpilqr_stream_io5) of this library");
+    StreamCall call(&io5->io4.io3.io2.io, pd_check_stride, nchunks);
+    if (const int rc = stream_rows_of(c, &io5->io4, &call)) return rc;
+    if (io5->sweep_count < 0 || (io5->sweep_count > 0 && !io5->sweep_traj))
+        return set_err(c, KPILQR_ERR_ARG, "kpilqr_iterate_streamed5: sweep_count < 0, or listed trajectories without sweep_traj");
+    call.sweep.listed = io5->sweep_traj != nullptr; call.sweep.count = call.sweep.listed ? io5->sweep_count : 0; call.sweep.traj = io5->sweep_traj;
     return iterate_streamed(c, call);
 }
 

@@ -70,6 +70,7 @@ k_rows_in_entries(int count, const int *__restrict__ traj, int dof, long long up
 // The mirror image for the listed sweeps (kpilqr_backward_partial, kpilqr_forward_linear_partial): the listed trajectories' rows of a small
 // per-trajectory output (status: one int; delta_J: one double; cost_pred: n_alpha doubles) gathered into a compact staging array that
 // leaves with ONE copy, however scattered the list is.  Rows of a few 4-byte words: one thread per word, a pure copy.
+// (A chunk of kpilqr_iterate_streamed5 hands it its slice of the caller's mapped pinned array for dst: plain stores through the pointer.)
 __global__ void __launch_bounds__(KPR_THREADS)
 k_rows_out(int count, const int *__restrict__ traj, int words, const unsigned *__restrict__ src, unsigned *__restrict__ dst)
 {

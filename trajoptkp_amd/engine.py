@@ -449,8 +449,38 @@ class Engine:
         self._iterate_streamed(fd, fd_kp, kp_cols, eps, r, r_x, r_u, u_nom, lam, K, k, cost_pred, delta_J, status, pd_stride, nchunks,
                                K32, gain_traj, io4.io3, kp_cols32, io4)
 
+    def iterate_streamed5(self, fd=None, fd_kp=None, kp_cols=None, eps=1e-6, r=None, r_x=None, r_u=None, u_nom=None, lam=None, K=None, k=None,
+                          cost_pred=None, delta_J=None, status=None, pd_stride=100, nchunks=0, K32=None, gain_traj=None, kp_cols32=None,
+                          upload_traj=None, sweep_traj=None):
+        """kpilqr_iterate_streamed5: iterate_streamed4 with sweep_traj (any int sequence, strictly increasing; [] is a list too) -- the
+        linearisation and the sweeps of those trajectories alone, as iterate_partial runs them.  lam, cost_pred, delta_J and status are
+        then compact, [len(sweep_traj)] rows in list order; upload_traj must lie inside sweep_traj; K / K32 / k keep following
+        gain_traj.  Always takes the new entry point (with sweep_traj=None that call is kpilqr_iterate_streamed4)."""
+        if kp_cols32 is not None:
+            if kp_cols32.dtype != np.float32:
+                raise ValueError("kp_cols32 must be a float32 array (no silent rounding here: the encoding is the caller's)")
+            if kp_cols32.size % (3 * self.n):
+                raise ValueError(f"kp_cols32 must hold whole entries of 3 * {self.n} floats")
+        io5 = _lib.StreamIO5()
+        io5.struct_size = C.sizeof(_lib.StreamIO5)
+        io4 = io5.io4
+        io4.struct_size = C.sizeof(_lib.StreamIO4)
+        io4.io3.struct_size = C.sizeof(_lib.StreamIO3)
+        lists = []                                                     # (read during the call only: they live until it returns)
+        for name, given in (("upload", upload_traj), ("sweep", sweep_traj)):
+            if given is None:
+                continue
+            tr = self._traj(given)
+            where = io4 if name == "upload" else io5
+            setattr(where, name + "_count", len(tr))
+            tr = tr if len(tr) else np.zeros(1, np.int32)              # an empty list is still a list: a non-NULL pointer
+            setattr(where, name + "_traj", tr.ctypes.data)
+            lists.append(tr)
+        self._iterate_streamed(fd, fd_kp, kp_cols, eps, r, r_x, r_u, u_nom, lam, K, k, cost_pred, delta_J, status, pd_stride, nchunks,
+                               K32, gain_traj, io4.io3, kp_cols32, io4, io5)
+
     def _iterate_streamed(self, fd, fd_kp, kp_cols, eps, r, r_x, r_u, u_nom, lam, K, k, cost_pred, delta_J, status, pd_stride, nchunks,
-                          K32, gain_traj, io3, kp_cols32=None, io4=None):
+                          K32, gain_traj, io3, kp_cols32=None, io4=None, io5=None):
         io2 = None if io3 is None else io3.io2
         if io2 is not None or K32 is not None or gain_traj is not None:
             if io2 is None:
@@ -480,7 +510,9 @@ class Engine:
                         ("cost_pred", cost_pred), ("delta_J", delta_J), ("status", status)):
             if a is not None:
                 setattr(io, name, a.ctypes.data)
-        if io4 is not None:
+        if io5 is not None:
+            self._ck(self._partial("kpilqr_iterate_streamed5")(self._h, C.byref(io5), int(pd_stride), int(nchunks)))
+        elif io4 is not None:
             self._ck(self._partial("kpilqr_iterate_streamed4")(self._h, C.byref(io4), int(pd_stride), int(nchunks)))
         elif io3 is not None:
             self._ck(self._partial("kpilqr_iterate_streamed3")(self._h, C.byref(io3), int(pd_stride), int(nchunks)))
