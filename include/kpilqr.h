@@ -117,6 +117,68 @@ typedef struct {
                                            model of DESIGN.md section 9, not on a measurement (profiles/union_keypoints.txt
                                            holds the procedure): the flag is off by default.  KPILQR_VERSION is unchanged: detect the
                                            feature by the symbols kpilqr_get_union_keypoints / kpilqr_get_union_columns. */
+#define KPILQR_FLAG_EMBED_SHAPE    16   /* Embedded shapes.  Opt-in, together with KPILQR_FLAG_FUSED; ignored, the way FUSED is on an
+                                           unsupported shape, when the shape has sweep kernels of its own ((dof, m) = (7,7), (2,1),
+                                           (6,3), (5,3)), when GENERIC or TILED kernels are forced, and when no carrier exists.
+                                           Contract.  A one-tile model of any other shape -- a 6-DoF arm (6,6), a 3-link (3,3), a
+                                           pendulum (1,1) ... -- runs the fused sweeps of its CARRIER: the compiled shape (dof', m')
+                                           with the smallest n' = 2 dof', then the smallest m', such that dof <= dof' and m <= m';
+                                           it needs m <= dof, 1 <= nr <= 16, n_alpha <= 16 and a payload of the carrier's shape within
+                                           the sweeps' 2^30-byte offsets.  The caller's problem is zero-embedded at this boundary by
+                                           streaming kernels (embed.hip): state row i goes to row i (i < dof) or i + dof' - dof
+                                           (velocities), controls are a prefix; padded states get zero A columns and rows, zero B rows
+                                           and zero r_x columns, padded controls zero B columns.  The padded block of V then stays
+                                           exactly 0, the padded block of Q_uu + lambda I is lambda I, the padded rows of K and k are
+                                           exactly 0 and the real block sees only additions of exact zeros: K, k, delta_J, status and the
+                                           predicted costs are those of the caller's own problem (the CPU oracle gives identical bits
+                                           for both; the device results are bit for bit those of a context created at the carrier's
+                                           shape and fed the zero-padded problem).  Every array of the calls in scope keeps the
+                                           CALLER's shape: kpilqr_set_keypoints (batch * dof lists, canonical as ever; the padded DoFs
+                                           get copies of the trajectory's list 0, so uniform lists stay uniform), kpilqr_fd_kp_layout
+                                           (the caller's n) + kpilqr_upload_fd_kp and kpilqr_upload_kp_columns (`entries` = the
+                                           caller's kp_offsets[batch*dof]), kpilqr_upload_residuals,
+                                           kpilqr_upload_residual_jacobians_const (padded on the host: ":rxc" / ":ru0" as on the
+                                           carrier), kpilqr_upload_nominal (padded control limits: (-1, 1)), kpilqr_backward,
+                                           kpilqr_forward_linear, kpilqr_iterate, kpilqr_download_gains, kpilqr_download_gains_f32, kpilqr_set_lambda_retry /
+                                           kpilqr_download_lambda_retry, kpilqr_trajectory_cost, kpilqr_allreduce_linesearch, kpilqr_comm_*,
+                                           kpilqr_sync, kpilqr_host_alloc / kpilqr_host_free, kpilqr_strerror, kpilqr_device_ptr of the shape-free
+                                           buffers (residuals, cost_pred, delta_J, status).  kpilqr_get_dims reports the caller's dims,
+                                           kpilqr_get_carrier_dims the carrier's; the variant strings are "mfma_f64_t1_fused" and
+                                           kpilqr_last_launch(ctx, 0 | 1) ends in ":emb<n'>x<m'>", e.g. ":emb14x7".
+                                           The lambda rule.  With padded controls (m' > m) a lambda[b] <= 0 or NaN that the host can see
+                                           is refused by kpilqr_backward and kpilqr_iterate with KPILQR_ERR_ARG before anything is
+                                           enqueued: the padded block of Q_uu + lambda I is lambda I, so lambda = 0 would fail the first
+                                           PD check of every trajectory.  lambda = NULL (the resident lambdas) is accepted; with
+                                           m' == m (e.g. (1,1) in (2,1)) lambda = 0 is legal.
+                                           Costs.  The sweeps do the carrier's work ((14,7)'s for a (6,6) arm); every by-shape upload is
+                                           ONE hipMemcpyAsync into a staging buffer the context owns (as large as the largest such
+                                           transfer, kept) and ONE launch; the gains leave through ONE gathering launch per array and
+                                           ONE copy in the caller's compact layout; device buffers have the carrier's size.  Measured
+                                           once (profiles/embedded_shapes.txt; T = 3000, uniform lists, constant Jacobian): kpilqr_iterate
+                                           at (6,6) 4.17 against 7.52 ms of the tiled kernels at B = 64 and 5.19 against 24.03 ms at
+                                           B = 1024, at (3,2) 3.47 against 6.22 and 4.12 against 18.07 ms; the gain download 0.44 .. 0.77
+                                           of the plain download of the carrier's arrays; the embedding launches add 2.5 .. 6.9 % to
+                                           the payload upload and the gain download.  It won at every size measured; per-DoF lists and
+                                           shapes much smaller than their carrier have not been timed: the flag is off by default.
+                                           Out of scope on an embedded context -- each of these returns KPILQR_ERR_STATE, names itself,
+                                           says "not on an embedded context", enqueues nothing and leaves the context as it was:
+                                           kpilqr_resize; kpilqr_update_keypoints, kpilqr_upload_fd_kp_partial,
+                                           kpilqr_upload_kp_columns_partial, kpilqr_upload_kp_columns_f32,
+                                           kpilqr_upload_kp_columns_f32_partial, kpilqr_download_gains_partial,
+                                           kpilqr_download_gains_f32_partial, kpilqr_upload_residuals_partial,
+                                           kpilqr_upload_nominal_partial, kpilqr_fd_interpolate_partial, kpilqr_cost_derivs_partial,
+                                           kpilqr_backward_partial, kpilqr_forward_linear_partial, kpilqr_iterate_partial;
+                                           kpilqr_iterate_streamed, kpilqr_iterate_streamed2, kpilqr_iterate_streamed3,
+                                           kpilqr_iterate_streamed4, kpilqr_iterate_streamed5; kpilqr_upload_fd, kpilqr_fd_slab_layout,
+                                           kpilqr_upload_fd_slab; kpilqr_upload_states, kpilqr_upload_states_partial,
+                                           kpilqr_generate_keypoints, kpilqr_generate_keypoints_partial, kpilqr_keypoint_error_test,
+                                           kpilqr_get_keypoints, kpilqr_get_keypoints_partial; kpilqr_fd_difference, kpilqr_interpolate,
+                                           kpilqr_fd_interpolate, kpilqr_cost_derivs, kpilqr_set_AB, kpilqr_get_AB,
+                                           kpilqr_set_cost_derivs, kpilqr_get_cost_derivs; kpilqr_filter_dynamics, kpilqr_dof_importance,
+                                           kpilqr_dof_importance_svd, kpilqr_backward_stats; kpilqr_get_union_keypoints,
+                                           kpilqr_get_union_columns (KPILQR_FLAG_UNION_KEYPOINTS is ignored); kpilqr_device_ptr of a
+                                           shape-dependent buffer.  No environment switch.  KPILQR_VERSION is unchanged: detect the
+                                           feature by the symbol kpilqr_get_carrier_dims. */
 
 enum {
     KPILQR_OK = 0,
@@ -150,7 +212,10 @@ int  kpilqr_create(const kpilqr_dims *dims, void *stream, kpilqr_ctx **out);
 void kpilqr_destroy(kpilqr_ctx *ctx);
 int  kpilqr_version(void);
 const char *kpilqr_strerror(kpilqr_ctx *ctx);       /* last error text of this context (or global) */
-int  kpilqr_get_dims(kpilqr_ctx *ctx, kpilqr_dims *out);
+int  kpilqr_get_dims(kpilqr_ctx *ctx, kpilqr_dims *out);   /* the caller's dims, also on an embedded context */
+/* KPILQR_FLAG_EMBED_SHAPE: the dims of the carrier shape the sweeps of an embedded context run at (dof', m'; everything else as
+ * kpilqr_get_dims).  KPILQR_ERR_STATE on a context that is not embedded (flag not set, or ignored for its shape). */
+int  kpilqr_get_carrier_dims(kpilqr_ctx *ctx, kpilqr_dims *out);
 /* iLQR_SVR::Resize (src/Optimiser/iLQR_SVR.cpp:38-193): the state-vector reduction changes dof (and possibly num_ctrl,
  * horizon) between optimisations.  Re-sizes the context IN PLACE: device allocations are kept and only grown when the new
  * sizes do not fit; kernel families are re-selected; everything uploaded before is forgotten.  Synchronous. */

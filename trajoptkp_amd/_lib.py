@@ -37,6 +37,7 @@ SYMBOLS = [
     "kpilqr_iterate_streamed5",
     "kpilqr_backward_partial", "kpilqr_forward_linear_partial", "kpilqr_iterate_partial",
     "kpilqr_upload_states_partial", "kpilqr_generate_keypoints_partial", "kpilqr_get_keypoints_partial",
+    "kpilqr_get_carrier_dims",
 ]
 # entry points added without a version bump (include/kpilqr.h: "detect the entry point by its symbol"): bound only when the library
 # has them -- KPILQR_LIB may name an older build of the same major version
@@ -49,7 +50,8 @@ OPTIONAL_SYMBOLS = {"kpilqr_fd_interpolate", "kpilqr_get_union_keypoints", "kpil
                     "kpilqr_upload_kp_columns_f32", "kpilqr_upload_kp_columns_f32_partial", "kpilqr_iterate_streamed3",
                     "kpilqr_iterate_streamed4", "kpilqr_iterate_streamed5",
                     "kpilqr_backward_partial", "kpilqr_forward_linear_partial", "kpilqr_iterate_partial",
-                    "kpilqr_upload_states_partial", "kpilqr_generate_keypoints_partial", "kpilqr_get_keypoints_partial"}
+                    "kpilqr_upload_states_partial", "kpilqr_generate_keypoints_partial", "kpilqr_get_keypoints_partial",
+                    "kpilqr_get_carrier_dims"}
 
 
 class Dims(C.Structure):
@@ -104,6 +106,7 @@ FLAG_GENERIC_KERNELS = 1
 FLAG_TILED_KERNELS = 2
 FLAG_FUSED = 4
 FLAG_UNION_KEYPOINTS = 8       # with FLAG_FUSED on a one-tile shape: per-DoF lists re-sampled onto their trajectory's union
+FLAG_EMBED_SHAPE = 16          # with FLAG_FUSED: a one-tile shape without kernels of its own runs zero-embedded in a compiled shape
 
 BUF_STEP_RECORDS, BUF_K, BUF_k, BUF_RESIDUALS, BUF_R_X, BUF_R_U, BUF_U_NOM, BUF_FD_XPLUS, \
     BUF_FD_XMINUS, BUF_COST_PRED, BUF_DELTA_J, BUF_STATUS = range(12)
@@ -186,6 +189,8 @@ def load():
     L.kpilqr_last_launch.argtypes = [vp, C.c_int]; L.kpilqr_last_launch.restype = C.c_char_p
     if hasattr(L, "kpilqr_fd_interpolate"):
         L.kpilqr_fd_interpolate.argtypes = [vp]
+    if hasattr(L, "kpilqr_get_carrier_dims"):
+        L.kpilqr_get_carrier_dims.argtypes = [vp, C.POINTER(Dims)]
     if hasattr(L, "kpilqr_get_union_keypoints"):
         L.kpilqr_get_union_keypoints.argtypes = [vp, vp, vp, C.c_int]
         L.kpilqr_get_union_columns.argtypes = [vp, vp, C.c_size_t]

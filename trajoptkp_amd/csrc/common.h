@@ -99,6 +99,17 @@ struct ListsDerived {
     bool kpu_valid = false;              // the union lists (kpu_offsets, kpu_times, kpu_src, kpu_traj_first)
 };
 
+// ---- KPILQR_FLAG_EMBED_SHAPE: a one-tile shape without kernels of its own, zero-embedded into a compiled shape (its "carrier") --
+// The context's own dims (Ctx::d, n, L, families, every launcher argument) are the CARRIER's; this holds the caller's and is looked at
+// by the entry points of kpilqr_api.cpp and by the launchers of embed.hip alone -- no sweep kernel, launcher or launch plan sees it.
+// State rows (and r_x columns) of the caller map to the carrier as i < dof -> i, i >= dof -> i + shift(carrier dof); controls are a
+// prefix.  Padded states have zero A rows / columns, zero B rows and zero r_x columns, padded controls zero B columns.
+struct Embed {
+    bool on = false;
+    int dof = 0, m = 0;           // the caller's
+    int shift(int carrier_dof) const { return carrier_dof - dof; }
+};
+
 struct Ctx {
     kpilqr_dims d{};
     int n = 0;
@@ -290,6 +301,16 @@ struct Ctx {
     bool sweep_read_set[kRowsRing][kPipeStreams] = {};
     int sweep_next = 0;
 
+    // ---- KPILQR_FLAG_EMBED_SHAPE (embed.hip) -------------------------------------------------------------------------------------
+    // emb_stage: what crosses the link in the CALLER's shape, on its way in (payload, r_x, r_u, u_nom: one copy, then one embedding
+    // launch) or out (K, k, U_alpha gathered by one launch, then one copy); reserved on demand, kept at the largest size asked for.
+    // emb_offsets: the caller's CSR offsets [batch*dof + 1] on the device for the payload kernels; emb_offsets_host: their mirror.
+    Embed embed;
+    DevBuf<char> emb_stage;
+    DevBuf<int> emb_offsets;
+    int *emb_offsets_host = nullptr;      // [batch*dof + 1] (malloc), valid while have_kp
+    int emb_entries = 0;                  // the caller's kp_offsets[batch*dof]
+
     // staging for debug hooks / U_alpha
     DevBuf<double> stage;
     // the compact host arrays of the listed sweeps (kpilqr_backward_partial, kpilqr_forward_linear_partial) on their way in and out:
@@ -303,7 +324,7 @@ struct Ctx {
         DevMem *const all[] = {&rec, &kp_uniform, &K, &k, &r, &r_x, &r_u, &w_run, &w_term, &u_nom, &ctrl_lim, &lambda, &alphas, &cost_pred,
                                &delta_J, &traj_cost, &status, &attempts, &gate, &traj_list, &K32, &segmap, &segent, &kp_offsets, &kp_times, &rx_const, &kpc, &kpc32, &kps, &kp_entry,
                                &kp_entry_list, &fdk_dev, &kpu_offsets, &kpu_times, &kpu_src, &kpu_traj_first, &kpcu, &kpu_uniform, &fdk_alt, &kpc_alt, &kp_times_alt, &kp_upl_times, &kp_move, &X_states, &kp_thr, &kp_mask, &kp_count, &ls8, &fd_dev, &err_flag, &stage, &sweep_stage, &pipe_list,
-                               &rows_stage[0], &rows_stage[1], &rows_stage[2], &rows_stage[3], &rows_stage[4], &rows_list, &sweep_ring};
+                               &rows_stage[0], &rows_stage[1], &rows_stage[2], &rows_stage[3], &rows_stage[4], &rows_list, &sweep_ring, &emb_stage, &emb_offsets};
         for (DevMem *b : all) f(*b);
     }
 
@@ -427,6 +448,19 @@ hipError_t launch_gate_arm(Ctx *c);                      // gate = 1 for the lis
 // the caller's mapped pinned rows for `staging` (the route of launch_gains_out: no staging buffer, no second DMA), and to
 // launch_rows_in, for their few compact lambdas, the caller's pinned rows as its source.
 hipError_t launch_rows_out(hipStream_t s, const int *traj, int count, int words, const void *src, void *staging);
+// embed.hip (KPILQR_FLAG_EMBED_SHAPE; c->d is the carrier's shape, c->embed the caller's).  src / dst are device pointers.
+// the caller's key-point ordered payload (records of 6n + 2 doubles by the caller's CSR, c->emb_offsets) -> the carrier's records in
+// c->fdk_dev by the carrier's CSR (c->kp_offsets), every byte of every carrier record written
+hipError_t launch_embed_fd_kp(Ctx *c, const void *src);
+// the caller's key-point columns [entries][3][n] -> the carrier's column store c->kpc [entries'][3][n'], every element written
+hipError_t launch_embed_kp_columns(Ctx *c, const double *src);
+// rows of a matrix sequence: src [rows][cols] -> columns j < split at j, j >= split at j + shift of dst [rows][dst_cols]; nothing
+// else of dst is written (its padding was zeroed with the buffer)
+hipError_t launch_embed_rows(Ctx *c, long long rows, int cols, int dst_cols, int split, int shift, const double *src, double *dst);
+// the inverse for the outputs: dst [count][rows][n][m] compact (FP64, or FP32 by the cast of k_gains_f32 when as_f32) gathered from
+// src [count][rows][n'][m'], row i < split at i, i >= split at i + shift
+hipError_t launch_extract_gains(Ctx *c, int count, long long rows, int n, int m, int src_n, int src_m, int split, int shift,
+                                const double *src, void *dst, bool as_f32);
 // comm.cpp (RCCL opened lazily) and the pack kernel of elementwise.hip
 const char *comm_unique_id(char *id128);
 const char *comm_init(Ctx *c, int nranks, int rank, const char *id128);

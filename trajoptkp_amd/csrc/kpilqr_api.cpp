@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "common.h"
+#include "mfma_common.h"      // (host side only: kp_t1_shape, kp_t1_carrier)
 #include "kp_merge.h"
 
 using namespace kpilqr;
@@ -108,6 +109,39 @@ static int ensure_stage(kpilqr_ctx *c, size_t bytes)
 }
 
 static int check_complete(kpilqr_ctx *c, const char *who);      // (below: ranges pending since kpilqr_update_keypoints)
+
+// ---- KPILQR_FLAG_EMBED_SHAPE: the caller's shape at the ABI boundary (include/kpilqr.h, "Embedded shapes"; embed.hip) --------------
+// c->d, c->n are the carrier's on an embedded context; these are what the caller's arrays are laid out by.
+static int caller_dof(const kpilqr_ctx *c) { return c->embed.on ? c->embed.dof : c->d.dof; }
+static int caller_n(const kpilqr_ctx *c) { return 2 * caller_dof(c); }
+static int caller_m(const kpilqr_ctx *c) { return c->embed.on ? c->embed.m : c->d.m; }
+
+// every entry point that is out of scope on an embedded context: refused first, before anything is enqueued or changed
+static int refuse_embedded(kpilqr_ctx *c, const char *who)
+{
+    return set_err(c, KPILQR_ERR_STATE, std::string(who) + ": not on an embedded context (KPILQR_FLAG_EMBED_SHAPE: the call is out of scope there)");
+}
+#define KP_NOT_EMBEDDED(c, who) do { if ((c) && (c)->embed.on) return refuse_embedded((c), who); } while (0)
+
+// the staging buffer of everything that crosses the link in the caller's shape; grows (after a stream sync) only when it has to
+static int ensure_emb_stage(kpilqr_ctx *c, size_t bytes)
+{
+    const int rc = reserve(c, c->emb_stage, bytes, kEighth, false);
+    return rc < 0 ? rc : KPILQR_OK;
+}
+
+// On an embedded context with padded controls (m' > m) the padded block of Q_uu + lambda I is lambda I: a lambda the host can see
+// to be <= 0 (or NaN) would fail the first PD check of every trajectory for no reason of the caller's problem.  Refused before anything
+// is enqueued; lambda = NULL (the resident lambdas) is accepted.
+static int check_embedded_lambda(kpilqr_ctx *c, const char *who, const double *lambda)
+{
+    if (!c->embed.on || !lambda || c->d.m == c->embed.m) return KPILQR_OK;
+    for (int b = 0; b < c->d.batch; b++)
+        if (!(lambda[b] > 0.0))
+            return set_err(c, KPILQR_ERR_ARG, std::string(who) + ": lambda[" + std::to_string(b) + "] is not > 0 on an embedded context with padded controls "
+                           "(the padded block of Q_uu + lambda I is lambda I, which must be positive definite)");
+    return KPILQR_OK;
+}
 
 static int env_int(const char *name, int dflt)
 {
@@ -579,7 +613,7 @@ static int select_variants(kpilqr_ctx *c)
         c->fused = true;
         c->bwd_family = c->fwd_family = Family::fused;
     }
-    c->union_on = c->fused && (dims->flags & KPILQR_FLAG_UNION_KEYPOINTS) != 0;      // (ignored on any other shape, as FUSED is)
+    c->union_on = c->fused && (dims->flags & KPILQR_FLAG_UNION_KEYPOINTS) != 0 && !c->embed.on;      // (ignored on any other shape, as FUSED is, and on an embedded context)
     // The same flag on a tiled shape (n + 2 > 16): a6 (variant "..._a6"), cost derivatives formed from the residuals inside the
     // sweeps.  It replaces k_cost_derivs (HBM-bound: n^2 doubles written per step) by NT*ceil(nr/4) + 6 MFMAs per wave-step of the
     // latency-bound backward sweep (+9 % at four tiles, whatever the batch): a gain from ~100 trajectories of a four-tile state up
@@ -594,6 +628,25 @@ static int select_variants(kpilqr_ctx *c)
         return KPILQR_ERR_ARG;
     }
     return KPILQR_OK;
+}
+
+// KPILQR_FLAG_EMBED_SHAPE: decided once, in kpilqr_create, before the families are selected.  The flag is ignored -- the way FUSED is on
+// an unsupported shape -- without FUSED, with GENERIC or TILED forced, on a shape that has its own instantiation, and where no
+// carrier exists (kp_t1_carrier; the fused sweeps' own bounds evaluated with the carrier's dims).  Otherwise the context's dims
+// become the carrier's and c->embed keeps the caller's.
+static void choose_embedding(kpilqr_ctx *c)
+{
+    const kpilqr_dims d = c->d;
+    if (!(d.flags & KPILQR_FLAG_EMBED_SHAPE) || !(d.flags & KPILQR_FLAG_FUSED)) return;
+    if (d.flags & (KPILQR_FLAG_GENERIC_KERNELS | KPILQR_FLAG_TILED_KERNELS)) return;
+    if (kp_t1_shape(2 * d.dof, d.m)) return;
+    int cdof = 0, cm = 0;
+    if (!kp_t1_carrier(d.dof, d.m, &cdof, &cm)) return;
+    if (!fused_supported(2 * cdof, cm, d.nr, cdof, d.T, d.n_alpha)) return;
+    c->embed.on = true; c->embed.dof = d.dof; c->embed.m = d.m;
+    c->d.dof = cdof; c->d.m = cm;
+    c->n = 2 * cdof;
+    c->L = RecLayout(c->n, cm);
 }
 
 extern "C" {
@@ -623,6 +676,7 @@ int kpilqr_create(const kpilqr_dims *dims, void *stream, kpilqr_ctx **out)
     c->d = *dims;
     c->n = 2 * dims->dof;
     c->L = RecLayout(c->n, dims->m);
+    choose_embedding(c);                        // (from here on c->d may be a carrier's shape; `dims` stays the caller's)
     {
         hipDeviceProp_t prop;
         if (hipGetDeviceProperties(&prop, dims->device) == hipSuccess && prop.multiProcessorCount > 0)
@@ -681,6 +735,7 @@ void kpilqr_destroy(kpilqr_ctx *c)
     }
     forget_lists(c);
     free(c->states_given_host);
+    free(c->emb_offsets_host);
     if (c->kpu_traj_first_host) free(c->kpu_traj_first_host);
     if (c->own_stream) (void)hipStreamDestroy(c->stream);
     delete c;
@@ -690,6 +745,16 @@ int kpilqr_get_dims(kpilqr_ctx *c, kpilqr_dims *out)
 {
     if (!c || !out) return KPILQR_ERR_ARG;
     *out = c->d;
+    out->dof = caller_dof(c); out->m = caller_m(c);      // (an embedded context reports the caller's shape here)
+    return KPILQR_OK;
+}
+
+// the shape the sweeps of an embedded context run at (KPILQR_FLAG_EMBED_SHAPE); KPILQR_ERR_STATE on a context that is not embedded
+int kpilqr_get_carrier_dims(kpilqr_ctx *c, kpilqr_dims *out)
+{
+    if (!c || !out) return KPILQR_ERR_ARG;
+    if (!c->embed.on) return set_err(c, KPILQR_ERR_STATE, "kpilqr_get_carrier_dims: the context is not embedded (KPILQR_FLAG_EMBED_SHAPE not set, or ignored for this shape)");
+    *out = c->d;
     return KPILQR_OK;
 }
 
@@ -698,6 +763,7 @@ int kpilqr_get_dims(kpilqr_ctx *c, kpilqr_dims *out)
 // controls, weights, limits, alphas, lambda) is forgotten, the kernel families are re-selected.
 int kpilqr_resize(kpilqr_ctx *c, int new_dof, int new_num_ctrl, int new_horizon)
 {
+    KP_NOT_EMBEDDED(c, "kpilqr_resize");
     if (!c) return KPILQR_ERR_ARG;
     KP_ENTER(c);
     if (new_dof < 1 || new_num_ctrl < 1 || new_horizon < 2) return set_err(c, KPILQR_ERR_ARG, "dims out of range");
@@ -776,6 +842,9 @@ int kpilqr_device_ptr(kpilqr_ctx *c, int which, void **dptr, size_t *bytes)
 {
     if (!c || !dptr) return KPILQR_ERR_ARG;
     KP_ENTER(c);
+    // (an embedded context: the buffers laid out by the carrier's shape stay inside; the shape-free ones are the caller's as they are)
+    if (c->embed.on && which != KPILQR_BUF_RESIDUALS && which != KPILQR_BUF_COST_PRED && which != KPILQR_BUF_DELTA_J && which != KPILQR_BUF_STATUS)
+        return refuse_embedded(c, "kpilqr_device_ptr of a shape-dependent buffer");
     const size_t B = c->d.batch, T = c->d.T, n = c->n, m = c->d.m, nr = c->d.nr;
     void *p = nullptr; size_t sz = 0;
     switch (which) {
@@ -807,10 +876,48 @@ int kpilqr_device_ptr(kpilqr_ctx *c, int which, void **dptr, size_t *bytes)
 }
 
 // ---- STEP 1b ------------------------------------------------------------------------------------
+static int install_lists(kpilqr_ctx *c, const int *kp_offsets, const int *kp_times);
+
+// kpilqr_set_keypoints on an embedded context: the caller's lists are checked as they are, expanded on the host to the carrier's CSR
+// (batch * dof' lists: the caller's lists d < dof, then dof' - dof COPIES of the trajectory's list 0 -- a trajectory whose lists
+// are all equal stays uniform, so the segment-loop forms of the sweeps keep running) and installed through the one path.  The
+// caller's offsets stay behind as a host mirror and a device copy: the payload kernels of embed.hip read records by them.
+static int install_embedded_lists(kpilqr_ctx *c, const int *kp_offsets, const int *kp_times)
+{
+    const int B = c->d.batch, dof = c->embed.dof, cdof = c->d.dof;
+    const size_t nlists = (size_t)B * dof;
+    if (const char *bad = kp_check_lists(nlists, c->d.T, kp_offsets, kp_times)) return set_err(c, KPILQR_ERR_ARG, bad);
+    std::vector<int> offs, times;
+    offs.reserve((size_t)B * cdof + 1);
+    offs.push_back(0);
+    for (int b = 0; b < B; b++)
+        for (int d = 0; d < cdof; d++) {
+            const size_t l = (size_t)b * dof + (d < dof ? d : 0);
+            times.insert(times.end(), kp_times + kp_offsets[l], kp_times + kp_offsets[l + 1]);
+            if (times.size() > (size_t)INT32_MAX) return set_err(c, KPILQR_ERR_ARG, "kpilqr_set_keypoints: the expanded lists of the carrier shape exceed 2^31 entries");
+            offs.push_back((int)times.size());
+        }
+    if (times.empty()) times.push_back(0);               // (a pointer to hand on; no entry is read)
+    { const int rcg = reserve(c, c->emb_offsets, (nlists + 1) * sizeof(int), kExact, false); if (rcg < 0) return rcg; }
+    if (!c->emb_offsets_host) c->emb_offsets_host = (int *)malloc(sizeof(int) * (nlists + 1));
+    if (!c->emb_offsets_host) return set_err(c, KPILQR_ERR_ALLOC, "host allocation failed");
+    // (the expanded arrays are pageable: the install path waits for their copies before it returns)
+    { const int rc = install_lists(c, offs.data(), times.data()); if (rc) return rc; }
+    memcpy(c->emb_offsets_host, kp_offsets, sizeof(int) * (nlists + 1));
+    c->emb_entries = kp_offsets[nlists];
+    KP_HIP(c, hipMemcpyAsync(c->emb_offsets, c->emb_offsets_host, (nlists + 1) * sizeof(int), hipMemcpyHostToDevice, c->stream));
+    return KPILQR_OK;
+}
+
 int kpilqr_set_keypoints(kpilqr_ctx *c, const int *kp_offsets, const int *kp_times)
 {
     if (!c || !kp_offsets || !kp_times) return KPILQR_ERR_ARG;
     KP_ENTER(c);
+    return c->embed.on ? install_embedded_lists(c, kp_offsets, kp_times) : install_lists(c, kp_offsets, kp_times);
+}
+
+static int install_lists(kpilqr_ctx *c, const int *kp_offsets, const int *kp_times)
+{
     const size_t nlists = (size_t)c->d.batch * c->d.dof;
     if (const char *bad = kp_check_lists(nlists, c->d.T, kp_offsets, kp_times)) return set_err(c, KPILQR_ERR_ARG, bad);
     const int total = kp_offsets[nlists];
@@ -928,6 +1035,7 @@ static int install_subset_lists(kpilqr_ctx *c, const char *who, int count, const
 
 int kpilqr_update_keypoints(kpilqr_ctx *c, int count, const int *traj, const int *kp_offsets, const int *kp_times)
 {
+    KP_NOT_EMBEDDED(c, "kpilqr_update_keypoints");
     if (count > 0 && (!kp_offsets || !kp_times)) return KPILQR_ERR_ARG;
     // (count = 0: nobody's lists change, nothing becomes invalid; a view is refused below, in the words of everything that allocates)
     { const int go = enter_subset(c, "kpilqr_update_keypoints", count, traj, Subset::listed_or_view); if (go <= 0) return go; }
@@ -943,6 +1051,7 @@ int kpilqr_update_keypoints(kpilqr_ctx *c, int count, const int *traj, const int
 // ---- key-point placement on the device ----------------------------------------------------------------
 int kpilqr_upload_states(kpilqr_ctx *c, const double *X)
 {
+    KP_NOT_EMBEDDED(c, "kpilqr_upload_states");
     if (!c || !X) return KPILQR_ERR_ARG;
     KP_ENTER(c);
     const size_t count = (size_t)c->d.batch * c->d.T * c->n;
@@ -971,6 +1080,7 @@ static int placement_args(kpilqr_ctx *c, const char *method, int min_N, int max_
 
 int kpilqr_generate_keypoints(kpilqr_ctx *c, const char *method, int min_N, int max_N, const double *thresholds, double dt)
 {
+    KP_NOT_EMBEDDED(c, "kpilqr_generate_keypoints");
     if (!c || !method) return KPILQR_ERR_ARG;
     KP_ENTER(c);
     int mth = -1;
@@ -1012,6 +1122,7 @@ int kpilqr_generate_keypoints(kpilqr_ctx *c, const char *method, int min_N, int 
 
 int kpilqr_keypoint_error_test(kpilqr_ctx *c, int n_iv, const int *intervals, int min_N, double threshold, unsigned char *good)
 {
+    KP_NOT_EMBEDDED(c, "kpilqr_keypoint_error_test");
     if (!c || n_iv < 0 || (n_iv > 0 && (!intervals || !good))) return KPILQR_ERR_ARG;
     KP_ENTER(c);
     if (n_iv == 0) return KPILQR_OK;
@@ -1032,6 +1143,7 @@ int kpilqr_keypoint_error_test(kpilqr_ctx *c, int n_iv, const int *intervals, in
 
 int kpilqr_get_keypoints(kpilqr_ctx *c, int *kp_offsets, int *kp_times, int times_capacity)
 {
+    KP_NOT_EMBEDDED(c, "kpilqr_get_keypoints");
     if (!c || !kp_offsets) return KPILQR_ERR_ARG;
     KP_ENTER(c);
     if (!c->have_kp) return set_err(c, KPILQR_ERR_STATE, "no key-points set");
@@ -1068,6 +1180,7 @@ static void fd_layout(int n, int njobs, int nnom, kpilqr_fd_layout *L)
 
 int kpilqr_fd_slab_layout(kpilqr_ctx *c, int njobs, int nnom, kpilqr_fd_layout *out)
 {
+    KP_NOT_EMBEDDED(c, "kpilqr_fd_slab_layout");
     if (!c || !out || njobs < 0 || nnom < 0) return KPILQR_ERR_ARG;
     fd_layout(c->n, njobs, nnom, out);
     return KPILQR_OK;
@@ -1091,6 +1204,7 @@ int kpilqr_upload_fd(kpilqr_ctx *c, int njobs, const int *job_b, const int *job_
                      const unsigned char *job_mode, const int *job_nom, const double *xplus,
                      const double *xminus, int nnom, const double *xnom, double eps)
 {
+    KP_NOT_EMBEDDED(c, "kpilqr_upload_fd");
     if (!c || njobs < 0 || nnom < 0) return KPILQR_ERR_ARG;
     KP_ENTER(c);
     if (njobs > 0 && (!job_b || !job_t || !job_col || !job_mode || !xplus || !xminus))
@@ -1126,6 +1240,7 @@ int kpilqr_upload_fd(kpilqr_ctx *c, int njobs, const int *job_b, const int *job_
 
 int kpilqr_upload_fd_slab(kpilqr_ctx *c, const void *slab, int njobs, int nnom, double eps)
 {
+    KP_NOT_EMBEDDED(c, "kpilqr_upload_fd_slab");
     if (!c || njobs < 0 || nnom < 0 || (njobs > 0 && !slab)) return KPILQR_ERR_ARG;
     KP_ENTER(c);
     if (!(eps > 0.0)) return set_err(c, KPILQR_ERR_ARG, "eps must be positive");
@@ -1149,7 +1264,7 @@ static void fdkp_layout(int n, int entries, kpilqr_fdkp_layout *L)
 int kpilqr_fd_kp_layout(kpilqr_ctx *c, int entries, kpilqr_fdkp_layout *out)
 {
     if (!c || !out || entries < 0) return KPILQR_ERR_ARG;
-    fdkp_layout(c->n, entries, out);
+    fdkp_layout(caller_n(c), entries, out);          // (an embedded context: the caller's records)
     return KPILQR_OK;
 }
 
@@ -1168,12 +1283,27 @@ int kpilqr_upload_fd_kp(kpilqr_ctx *c, const void *slab, int entries, double eps
     if (!(eps > 0.0)) return set_err(c, KPILQR_ERR_ARG, "eps must be positive");
     if (!c->have_kp) return set_err(c, KPILQR_ERR_STATE, "kpilqr_upload_fd_kp before the key-points it is ordered by (kpilqr_set_keypoints / kpilqr_generate_keypoints)");
     // (the sweeps index the slab by the device CSR, not by `entries`: a smaller slab would be read past its end)
-    if (entries != c->kp_total_host)
+    if (entries != (c->embed.on ? c->emb_entries : c->kp_total_host))
         return set_err(c, KPILQR_ERR_ARG, "kpilqr_upload_fd_kp: `entries` is not the number of key-point entries (kp_offsets[batch*dof])");
     kpilqr_fdkp_layout L;
-    int rc = fdk_bind(c, entries, &L);
-    if (rc) return rc;
-    if (entries) KP_HIP(c, hipMemcpyAsync(c->fdk_dev, slab, L.bytes, hipMemcpyHostToDevice, c->stream));   // the one DMA
+    int rc = KPILQR_OK;
+    if (c->embed.on) {
+        // the caller's records into the staging buffer with the one DMA, then one launch that writes every byte of the carrier's
+        // records (embed.hip); the context is then what this call leaves on a context of the carrier's shape
+        kpilqr_fdkp_layout own;
+        fdkp_layout(caller_n(c), entries, &own);
+        rc = ensure_emb_stage(c, own.bytes);
+        if (rc) return rc;
+        rc = fdk_bind(c, c->kp_total_host, &L);
+        if (rc) return rc;
+        if (entries) KP_HIP(c, hipMemcpyAsync(c->emb_stage, slab, own.bytes, hipMemcpyHostToDevice, c->stream));
+        if (c->kp_total_host) KP_HIP(c, launch_embed_fd_kp(c, c->emb_stage));
+        entries = c->kp_total_host;
+    } else {
+        rc = fdk_bind(c, entries, &L);
+        if (rc) return rc;
+        if (entries) KP_HIP(c, hipMemcpyAsync(c->fdk_dev, slab, L.bytes, hipMemcpyHostToDevice, c->stream));   // the one DMA
+    }
     c->fdk_entries = entries; c->fdk_first = 0; c->eps = eps;
     c->fd_payload = FdPayload::kp_ordered; payload_changed(c);
     return wait_unless_pinned(c, slab);
@@ -1185,11 +1315,23 @@ int kpilqr_upload_kp_columns(kpilqr_ctx *c, const double *columns, int entries)
     if (!c || entries < 0 || (entries > 0 && !columns)) return KPILQR_ERR_ARG;
     KP_ENTER(c);
     if (!c->have_kp) return set_err(c, KPILQR_ERR_STATE, "kpilqr_upload_kp_columns before the key-points it is ordered by (kpilqr_set_keypoints / kpilqr_generate_keypoints)");
-    if (entries != c->kp_total_host)
+    if (entries != (c->embed.on ? c->emb_entries : c->kp_total_host))
         return set_err(c, KPILQR_ERR_ARG, "kpilqr_upload_kp_columns: `entries` is not the number of key-point entries (kp_offsets[batch*dof])");
-    int rc = ensure_kpc(c);
-    if (rc) return rc;
-    if (entries) KP_HIP(c, hipMemcpyAsync(c->kpc, columns, (size_t)entries * 3 * c->n * 8, hipMemcpyHostToDevice, c->stream));
+    int rc = KPILQR_OK;
+    if (c->embed.on) {              // as kpilqr_upload_fd_kp: one DMA into the staging buffer, one launch straight into the column store
+        const size_t own = (size_t)entries * 3 * caller_n(c) * 8;
+        rc = ensure_emb_stage(c, own);
+        if (rc) return rc;
+        rc = ensure_kpc(c);
+        if (rc) return rc;
+        if (entries) KP_HIP(c, hipMemcpyAsync(c->emb_stage, columns, own, hipMemcpyHostToDevice, c->stream));
+        if (c->kp_total_host) KP_HIP(c, launch_embed_kp_columns(c, (const double *)c->emb_stage.p));
+        entries = c->kp_total_host;
+    } else {
+        rc = ensure_kpc(c);
+        if (rc) return rc;
+        if (entries) KP_HIP(c, hipMemcpyAsync(c->kpc, columns, (size_t)entries * 3 * c->n * 8, hipMemcpyHostToDevice, c->stream));
+    }
     c->fd_payload = FdPayload::kp_columns; c->fdk_entries = entries; c->fdk_first = 0;      // (the entry range, as for the key-point ordered payload)
     payload_changed(c);
     c->pay.kpc_valid = true;
@@ -1222,6 +1364,7 @@ static int upload_runs(kpilqr_ctx *c, int count, const int *traj, const char *sr
 
 int kpilqr_upload_fd_kp_partial(kpilqr_ctx *c, int count, const int *traj, const void *slab, int entries, double eps)
 {
+    KP_NOT_EMBEDDED(c, "kpilqr_upload_fd_kp_partial");
     if (entries < 0 || (entries > 0 && !slab)) return KPILQR_ERR_ARG;
     { const int go = enter_subset(c, "kpilqr_upload_fd_kp_partial", count, traj, Subset::pending); if (go <= 0) return go; }
     if (count == 0 && entries == 0 && !c->n_pending) return KPILQR_OK;
@@ -1237,6 +1380,7 @@ int kpilqr_upload_fd_kp_partial(kpilqr_ctx *c, int count, const int *traj, const
 
 int kpilqr_upload_kp_columns_partial(kpilqr_ctx *c, int count, const int *traj, const double *columns, int entries)
 {
+    KP_NOT_EMBEDDED(c, "kpilqr_upload_kp_columns_partial");
     if (entries < 0 || (entries > 0 && !columns)) return KPILQR_ERR_ARG;
     { const int go = enter_subset(c, "kpilqr_upload_kp_columns_partial", count, traj, Subset::pending); if (go <= 0) return go; }
     if (count == 0 && entries == 0 && !c->n_pending) return KPILQR_OK;
@@ -1269,6 +1413,7 @@ static int widen_columns_f32(kpilqr_ctx *c, const float *columns32, int entries,
 
 int kpilqr_upload_kp_columns_f32(kpilqr_ctx *c, const float *columns32, int entries)
 {
+    KP_NOT_EMBEDDED(c, "kpilqr_upload_kp_columns_f32");
     if (!c || entries < 0 || (entries > 0 && !columns32)) return KPILQR_ERR_ARG;
     KP_ENTER(c);
     if (!c->have_kp) return set_err(c, KPILQR_ERR_STATE, "kpilqr_upload_kp_columns_f32 before the key-points it is ordered by (kpilqr_set_keypoints / kpilqr_generate_keypoints)");
@@ -1291,6 +1436,7 @@ int kpilqr_upload_kp_columns_f32(kpilqr_ctx *c, const float *columns32, int entr
 
 int kpilqr_upload_kp_columns_f32_partial(kpilqr_ctx *c, int count, const int *traj, const float *columns32, int entries)
 {
+    KP_NOT_EMBEDDED(c, "kpilqr_upload_kp_columns_f32_partial");
     if (entries < 0 || (entries > 0 && !columns32)) return KPILQR_ERR_ARG;
     { const int go = enter_subset(c, "kpilqr_upload_kp_columns_f32_partial", count, traj, Subset::pending); if (go <= 0) return go; }
     if (count == 0 && entries == 0 && !c->n_pending) return KPILQR_OK;
@@ -1311,6 +1457,7 @@ int kpilqr_upload_kp_columns_f32_partial(kpilqr_ctx *c, int count, const int *tr
 
 int kpilqr_fd_difference(kpilqr_ctx *c)
 {
+    KP_NOT_EMBEDDED(c, "kpilqr_fd_difference");
     if (!c) return KPILQR_ERR_ARG;
     KP_ENTER(c);
     { const int rcp = check_complete(c, "kpilqr_fd_difference"); if (rcp) return rcp; }
@@ -1325,6 +1472,7 @@ int kpilqr_fd_difference(kpilqr_ctx *c)
 
 int kpilqr_interpolate(kpilqr_ctx *c)
 {
+    KP_NOT_EMBEDDED(c, "kpilqr_interpolate");
     if (!c) return KPILQR_ERR_ARG;
     KP_ENTER(c);
     if (!c->have_kp) return set_err(c, KPILQR_ERR_STATE, "kpilqr_interpolate before kpilqr_set_keypoints");
@@ -1337,6 +1485,7 @@ int kpilqr_interpolate(kpilqr_ctx *c)
 // kpilqr_fd_difference + kpilqr_interpolate (Differentiator.cpp:166-222,441-457 + KeyPointGenerator.cpp:840-954)
 int kpilqr_fd_interpolate(kpilqr_ctx *c)
 {
+    KP_NOT_EMBEDDED(c, "kpilqr_fd_interpolate");
     if (!c) return KPILQR_ERR_ARG;
     KP_ENTER(c);
     if (!c->have_kp) return set_err(c, KPILQR_ERR_STATE, "kpilqr_fd_interpolate before kpilqr_set_keypoints");
@@ -1355,6 +1504,7 @@ int kpilqr_fd_interpolate(kpilqr_ctx *c)
 // Optimiser::FilterDynamicsMatrices (Optimiser.cpp:340-406) on the materialised A sequence
 int kpilqr_filter_dynamics(kpilqr_ctx *c, const char *method, const double *coefs, int ncoef)
 {
+    KP_NOT_EMBEDDED(c, "kpilqr_filter_dynamics");
     if (!c || !method || !coefs) return KPILQR_ERR_ARG;
     KP_ENTER(c);
     int mth = strcmp(method, "low_pass") == 0 ? 0 : strcmp(method, "FIR") == 0 ? 1 : -1;
@@ -1377,6 +1527,27 @@ int kpilqr_upload_residuals(kpilqr_ctx *c, const double *r, const double *r_x, c
     if (!c) return KPILQR_ERR_ARG;
     KP_ENTER(c);
     const size_t B = c->d.batch, T1 = c->d.T + 1, n = c->n, m = c->d.m, nr = c->d.nr;
+    if (c->embed.on) {
+        // r, w_run, w_term are shape-free; r_x and r_u cross in the caller's pitch into the staging buffer and one launch each places
+        // their columns (embed.hip): the padding of the buffers was zeroed with them and is never written
+        const size_t rows = B * T1 * nr, on = caller_n(c), om = caller_m(c);
+        { const int rcs = ensure_emb_stage(c, rows * ((r_x ? on : 0) + (r_u ? om : 0)) * 8); if (rcs) return rcs; }
+        double *const sx = (double *)c->emb_stage.p, *const su = sx + (r_x ? rows * on : 0);
+        if (r) KP_HIP(c, hipMemcpyAsync(c->r, r, rows * 8, hipMemcpyHostToDevice, c->stream));
+        if (r_x) {
+            KP_HIP(c, hipMemcpyAsync(sx, r_x, rows * on * 8, hipMemcpyHostToDevice, c->stream));
+            KP_HIP(c, launch_embed_rows(c, (long long)rows, (int)on, (int)n, c->embed.dof, c->embed.shift(c->d.dof), sx, c->r_x));
+            c->rx_const_on = false; c->rx_buf_valid = c->rx_whole = true;
+        }
+        if (r_u) {
+            KP_HIP(c, hipMemcpyAsync(su, r_u, rows * om * 8, hipMemcpyHostToDevice, c->stream));
+            KP_HIP(c, launch_embed_rows(c, (long long)rows, (int)om, (int)m, (int)om, 0, su, c->r_u));
+            c->ru_zero = false;
+        }
+        if (w_run) KP_HIP(c, hipMemcpyAsync(c->w_run, w_run, nr * 8, hipMemcpyHostToDevice, c->stream));
+        if (w_term) KP_HIP(c, hipMemcpyAsync(c->w_term, w_term, nr * 8, hipMemcpyHostToDevice, c->stream));
+        return KPILQR_OK;
+    }
     if (r) KP_HIP(c, hipMemcpyAsync(c->r, r, B * T1 * nr * 8, hipMemcpyHostToDevice, c->stream));
     if (r_x) { KP_HIP(c, hipMemcpyAsync(c->r_x, r_x, B * T1 * nr * n * 8, hipMemcpyHostToDevice, c->stream)); c->rx_const_on = false; c->rx_buf_valid = c->rx_whole = true; }
     if (r_u) { KP_HIP(c, hipMemcpyAsync(c->r_u, r_u, B * T1 * nr * m * 8, hipMemcpyHostToDevice, c->stream)); c->ru_zero = false; }
@@ -1392,6 +1563,22 @@ int kpilqr_upload_residual_jacobians_const(kpilqr_ctx *c, const double *r_x, con
     if (!c || !r_x) return KPILQR_ERR_ARG;
     KP_ENTER(c);
     const size_t n = c->n, m = c->d.m, nr = c->d.nr, reps = (size_t)c->d.batch * (c->d.T + 1);
+    // an embedded context: the one small matrix (and r_u's) padded on the host to the carrier's pitch; from here on the call is the
+    // one a context of the carrier's shape gets, so rxc / ru0 are selected as there (the padded arrays are pageable: the call waits)
+    std::vector<double> px, pu;
+    if (c->embed.on) {
+        const size_t on = caller_n(c), om = caller_m(c), dof = c->embed.dof, shift = c->embed.shift(c->d.dof);
+        px.assign(nr * n, 0.0);
+        for (size_t i = 0; i < nr; i++)
+            for (size_t j = 0; j < on; j++) px[i * n + (j < dof ? j : j + shift)] = r_x[i * on + j];
+        r_x = px.data();
+        if (r_u) {
+            pu.assign(nr * m, 0.0);
+            for (size_t i = 0; i < nr; i++)
+                for (size_t j = 0; j < om; j++) pu[i * m + j] = r_u[i * om + j];
+            r_u = pu.data();
+        }
+    }
     { const int rcg = reserve(c, c->rx_const, nr * n * 8, kExact, false); if (rcg < 0) return rcg; }
     KP_HIP(c, hipMemcpyAsync(c->rx_const, r_x, nr * n * 8, hipMemcpyHostToDevice, c->stream));
     c->rx_const_on = true; c->rx_buf_valid = false;
@@ -1411,6 +1598,7 @@ int kpilqr_upload_residual_jacobians_const(kpilqr_ctx *c, const double *r_x, con
 
 int kpilqr_cost_derivs(kpilqr_ctx *c)
 {
+    KP_NOT_EMBEDDED(c, "kpilqr_cost_derivs");
     if (!c) return KPILQR_ERR_ARG;
     KP_ENTER(c);
     { const int rcx = ensure_rx_buffer(c); if (rcx) return rcx; }
@@ -1552,6 +1740,7 @@ int kpilqr_backward(kpilqr_ctx *c, const double *lambda, int pd_check_stride, in
     KP_ENTER(c);
     if (pd_check_stride < 1) return set_err(c, KPILQR_ERR_ARG, "pd_check_stride must be >= 1");
     { const int rcp = check_complete(c, "kpilqr_backward"); if (rcp) return rcp; }
+    { const int rcl = check_embedded_lambda(c, "kpilqr_backward", lambda); if (rcl) return rcl; }
     if (lambda) KP_HIP(c, hipMemcpyAsync(c->lambda, lambda, (size_t)c->d.batch * 8, hipMemcpyHostToDevice, c->stream));
     c->retry_attempts = retry_attempts_for(c, lambda, c->d.batch);
     int rc = run_backward(c, pd_check_stride);
@@ -1568,6 +1757,7 @@ int kpilqr_backward(kpilqr_ctx *c, const double *lambda, int pd_check_stride, in
 // the instrumented kernel has no gate, and the histogram is that of ONE sweep.
 int kpilqr_backward_stats(kpilqr_ctx *c, int pd_check_stride, int *hist)
 {
+    KP_NOT_EMBEDDED(c, "kpilqr_backward_stats");
     if (!c || !hist) return KPILQR_ERR_ARG;
     KP_ENTER(c);
     if (!c->fused) return set_err(c, KPILQR_ERR_STATE, "kpilqr_backward_stats: fused contexts only");
@@ -1629,10 +1819,30 @@ int kpilqr_download_lambda_retry(kpilqr_ctx *c, double *lambda_used, int *attemp
     return KPILQR_OK;
 }
 
+// The gains of an embedded context: ONE launch per array gathers the real block of the carrier's K [b][T][n'][m'] (k: [b][T][m'])
+// into the compact staging buffer in the caller's shape -- K as FP32 by the cast of k_gains_f32 when asked -- and ONE copy per array
+// takes it to the host: no strided copies of 8 m-byte rows.
+static int download_embedded_gains(kpilqr_ctx *c, void *K, bool K_f32, double *k)
+{
+    const size_t B = c->d.batch, T = c->d.T, on = caller_n(c), om = caller_m(c);
+    const size_t bytesK = K ? B * T * on * om * (K_f32 ? 4 : 8) : 0, offk = (bytesK + 15) & ~(size_t)15, bytesk = k ? B * T * om * 8 : 0;
+    { const int rcs = ensure_emb_stage(c, offk + bytesk); if (rcs) return rcs; }
+    if (K) {
+        KP_HIP(c, launch_extract_gains(c, (int)B, (long long)T, (int)on, (int)om, c->n, c->d.m, c->embed.dof, c->embed.shift(c->d.dof), c->K, c->emb_stage.p, K_f32));
+        KP_HIP(c, hipMemcpyAsync(K, c->emb_stage.p, bytesK, hipMemcpyDeviceToHost, c->stream));
+    }
+    if (k) {
+        KP_HIP(c, launch_extract_gains(c, (int)B, (long long)T, 1, (int)om, 1, c->d.m, 1, 0, c->k, (char *)c->emb_stage.p + offk, false));
+        KP_HIP(c, hipMemcpyAsync(k, (char *)c->emb_stage.p + offk, bytesk, hipMemcpyDeviceToHost, c->stream));
+    }
+    return KPILQR_OK;
+}
+
 int kpilqr_download_gains(kpilqr_ctx *c, double *K, double *k)
 {
     if (!c) return KPILQR_ERR_ARG;
     KP_ENTER(c);
+    if (c->embed.on) return download_embedded_gains(c, K, false, k);
     const size_t B = c->d.batch, T = c->d.T, n = c->n, m = c->d.m;
     if (K) KP_HIP(c, hipMemcpyAsync(K, c->K, B * T * n * m * 8, hipMemcpyDeviceToHost, c->stream));
     if (k) KP_HIP(c, hipMemcpyAsync(k, c->k, B * T * m * 8, hipMemcpyDeviceToHost, c->stream));
@@ -1642,6 +1852,7 @@ int kpilqr_download_gains(kpilqr_ctx *c, double *K, double *k)
 // the gains of the listed trajectories, compact: one copy per array and run of adjacent trajectories
 int kpilqr_download_gains_partial(kpilqr_ctx *c, int count, const int *traj, double *K, double *k)
 {
+    KP_NOT_EMBEDDED(c, "kpilqr_download_gains_partial");
     { const int go = enter_subset(c, "kpilqr_download_gains_partial", count, traj, Subset::listed_or_view); if (go <= 0) return go; }
     const size_t perK = (size_t)c->d.T * c->n * c->d.m, perk = (size_t)c->d.T * c->d.m;
     return kp_for_each_run(count, traj, [&](int i, int b0, int run) -> int {
@@ -1654,6 +1865,7 @@ int kpilqr_download_gains_partial(kpilqr_ctx *c, int count, const int *traj, dou
 // iLQR_SVR::LeastImportantDofs, summing branch (iLQR_SVR.cpp:952-968), over the gains of the last backward pass
 int kpilqr_dof_importance(kpilqr_ctx *c, int sampling_k_interval, double *sums)
 {
+    KP_NOT_EMBEDDED(c, "kpilqr_dof_importance");
     if (!c || !sums) return KPILQR_ERR_ARG;
     KP_ENTER(c);
     if (sampling_k_interval < 1) return set_err(c, KPILQR_ERR_ARG, "sampling_k_interval must be >= 1");
@@ -1668,6 +1880,7 @@ int kpilqr_dof_importance(kpilqr_ctx *c, int sampling_k_interval, double *sums)
 // iLQR_SVR::LeastImportantDofs, singular-vector branch (iLQR_SVR.cpp:902-950), over the gains of the last backward pass
 int kpilqr_dof_importance_svd(kpilqr_ctx *c, int sampling_k_interval, double *sums)
 {
+    KP_NOT_EMBEDDED(c, "kpilqr_dof_importance_svd");
     if (!c || !sums) return KPILQR_ERR_ARG;
     KP_ENTER(c);
     if (sampling_k_interval < 1) return set_err(c, KPILQR_ERR_ARG, "sampling_k_interval must be >= 1");
@@ -1685,6 +1898,23 @@ int kpilqr_upload_nominal(kpilqr_ctx *c, const double *u_nom, const double *ctrl
     if (!c) return KPILQR_ERR_ARG;
     KP_ENTER(c);
     const size_t B = c->d.batch, T = c->d.T, m = c->d.m;
+    if (c->embed.on) {
+        // u_nom to the carrier's pitch through the staging buffer and k_embed_rows (the padded controls stay +0); the limits of the
+        // padded controls are (-1, 1), set on the host (2 m' doubles from a temporary: the call waits for that copy)
+        const size_t om = caller_m(c);
+        if (u_nom) {
+            { const int rcs = ensure_emb_stage(c, B * T * om * 8); if (rcs) return rcs; }
+            KP_HIP(c, hipMemcpyAsync(c->emb_stage, u_nom, B * T * om * 8, hipMemcpyHostToDevice, c->stream));
+            KP_HIP(c, launch_embed_rows(c, (long long)(B * T), (int)om, (int)m, (int)om, 0, (const double *)c->emb_stage.p, c->u_nom));
+        }
+        if (ctrl_lim) {
+            std::vector<double> lim(2 * m);
+            for (size_t j = 0; j < m; j++) { lim[2 * j] = j < om ? ctrl_lim[2 * j] : -1.0; lim[2 * j + 1] = j < om ? ctrl_lim[2 * j + 1] : 1.0; }
+            KP_HIP(c, hipMemcpyAsync(c->ctrl_lim, lim.data(), 2 * m * 8, hipMemcpyHostToDevice, c->stream));
+            KP_HIP(c, hipStreamSynchronize(c->stream));
+        }
+        return KPILQR_OK;
+    }
     if (u_nom) KP_HIP(c, hipMemcpyAsync(c->u_nom, u_nom, B * T * m * 8, hipMemcpyHostToDevice, c->stream));
     if (ctrl_lim) KP_HIP(c, hipMemcpyAsync(c->ctrl_lim, ctrl_lim, 2 * m * 8, hipMemcpyHostToDevice, c->stream));
     return KPILQR_OK;
@@ -1702,6 +1932,7 @@ static int upload_rows(kpilqr_ctx *c, int count, const int *traj, const double *
 
 int kpilqr_upload_residuals_partial(kpilqr_ctx *c, int count, const int *traj, const double *r, const double *r_x, const double *r_u)
 {
+    KP_NOT_EMBEDDED(c, "kpilqr_upload_residuals_partial");
     int rc = enter_subset(c, "kpilqr_upload_residuals_partial", count, traj);
     if (rc <= 0) return rc;
     // rows of a subset need every other row of the buffer to mean something, and must not flip the form the sweeps run in
@@ -1720,6 +1951,7 @@ int kpilqr_upload_residuals_partial(kpilqr_ctx *c, int count, const int *traj, c
 
 int kpilqr_upload_nominal_partial(kpilqr_ctx *c, int count, const int *traj, const double *u_nom)
 {
+    KP_NOT_EMBEDDED(c, "kpilqr_upload_nominal_partial");
     const int go = enter_subset(c, "kpilqr_upload_nominal_partial", count, traj);
     if (go <= 0) return go;
     return u_nom ? upload_rows(c, count, traj, u_nom, c->u_nom, (size_t)c->d.T * c->d.m) : KPILQR_OK;
@@ -1745,6 +1977,7 @@ static int kpc_to_records_of(kpilqr_ctx *c, int count, const int *traj)
 // kpilqr_fd_interpolate for the listed trajectories: [A|B] of their records from the resident payload, nobody else's records written
 int kpilqr_fd_interpolate_partial(kpilqr_ctx *c, int count, const int *traj)
 {
+    KP_NOT_EMBEDDED(c, "kpilqr_fd_interpolate_partial");
     int rc = enter_subset(c, "kpilqr_fd_interpolate_partial", count, traj);
     if (rc <= 0) return rc;
     if (c->fused) return set_err(c, KPILQR_ERR_STATE, "kpilqr_fd_interpolate_partial: a KPILQR_FLAG_FUSED context holds no persistent step records (its sweeps read the column store): kpilqr_fd_difference");
@@ -1777,6 +2010,7 @@ int kpilqr_fd_interpolate_partial(kpilqr_ctx *c, int count, const int *traj)
 // kpilqr_cost_derivs for the listed trajectories
 int kpilqr_cost_derivs_partial(kpilqr_ctx *c, int count, const int *traj)
 {
+    KP_NOT_EMBEDDED(c, "kpilqr_cost_derivs_partial");
     int rc = enter_subset(c, "kpilqr_cost_derivs_partial", count, traj);
     if (rc <= 0) return rc;
     if (c->fused) return set_err(c, KPILQR_ERR_STATE, "kpilqr_cost_derivs_partial: a KPILQR_FLAG_FUSED context holds no persistent step records (its sweeps form the cost derivatives themselves)");
@@ -1800,6 +2034,7 @@ static int enter_placement_subset(kpilqr_ctx *c, const char *who, int count, con
 
 int kpilqr_upload_states_partial(kpilqr_ctx *c, int count, const int *traj, const double *X)
 {
+    KP_NOT_EMBEDDED(c, "kpilqr_upload_states_partial");
     if (count > 0 && !X) return KPILQR_ERR_ARG;
     { const int go = enter_placement_subset(c, "kpilqr_upload_states_partial", count, traj); if (go <= 0) return go; }
     const size_t B = c->d.batch, per = (size_t)c->d.T * c->n;
@@ -1818,6 +2053,7 @@ int kpilqr_upload_states_partial(kpilqr_ctx *c, int count, const int *traj, cons
 int kpilqr_generate_keypoints_partial(kpilqr_ctx *c, int count, const int *traj, const char *method, int min_N, int max_N,
                                       const double *thresholds, double dt)
 {
+    KP_NOT_EMBEDDED(c, "kpilqr_generate_keypoints_partial");
     static const char who[] = "kpilqr_generate_keypoints_partial";
     if (!c || !method) return KPILQR_ERR_ARG;
     { const int go = enter_placement_subset(c, who, count, traj); if (go <= 0) return go; }
@@ -1870,6 +2106,7 @@ int kpilqr_generate_keypoints_partial(kpilqr_ctx *c, int count, const int *traj,
 
 int kpilqr_get_keypoints_partial(kpilqr_ctx *c, int count, const int *traj, int *kp_offsets, int *kp_times, int times_capacity)
 {
+    KP_NOT_EMBEDDED(c, "kpilqr_get_keypoints_partial");
     if (!c || !kp_offsets) return KPILQR_ERR_ARG;
     {
         const int go = enter_placement_subset(c, "kpilqr_get_keypoints_partial", count, traj);
@@ -1934,11 +2171,13 @@ int kpilqr_download_gains_f32(kpilqr_ctx *c, float *K32, double *k)
     if (!c) return KPILQR_ERR_ARG;
     KP_ENTER(c);
     if (c->is_view) return set_err(c, KPILQR_ERR_STATE, "kpilqr_download_gains_f32: not through a view of a trajectory range");
+    if (c->embed.on) return download_embedded_gains(c, K32, true, k);
     return download_gains_f32(c, c->d.batch, nullptr, K32, k);
 }
 
 int kpilqr_download_gains_f32_partial(kpilqr_ctx *c, int count, const int *traj, float *K32, double *k)
 {
+    KP_NOT_EMBEDDED(c, "kpilqr_download_gains_f32_partial");
     const int go = enter_subset(c, "kpilqr_download_gains_f32_partial", count, traj);
     if (go <= 0) return go;
     return download_gains_f32(c, count, traj, K32, k);
@@ -2009,6 +2248,13 @@ int kpilqr_forward_linear(kpilqr_ctx *c, const double *alphas, double *cost_pred
     int rc = run_forward(c, U_dev);
     if (rc) return rc;
     if (cost_pred) KP_HIP(c, hipMemcpyAsync(cost_pred, c->cost_pred, B * na * 8, hipMemcpyDeviceToHost, c->stream));
+    if (U_alpha && c->embed.on) {          // the controls of the real block, compact, by the launch that extracts k
+        const size_t om = caller_m(c);
+        { const int rcs = ensure_emb_stage(c, B * na * T * om * 8); if (rcs) return rcs; }
+        KP_HIP(c, launch_extract_gains(c, (int)B, (long long)(na * T), 1, (int)om, 1, (int)m, 1, 0, U_dev, c->emb_stage.p, false));
+        KP_HIP(c, hipMemcpyAsync(U_alpha, c->emb_stage.p, B * na * T * om * 8, hipMemcpyDeviceToHost, c->stream));
+        return KPILQR_OK;
+    }
     if (U_alpha) KP_HIP(c, hipMemcpyAsync(U_alpha, U_dev, B * na * T * m * 8, hipMemcpyDeviceToHost, c->stream));
     return KPILQR_OK;
 }
@@ -2021,6 +2267,7 @@ int kpilqr_iterate(kpilqr_ctx *c, const double *lambda, int pd_check_stride, con
     if (!c->have_kp) return set_err(c, KPILQR_ERR_STATE, "kpilqr_iterate before kpilqr_set_keypoints");
     if (pd_check_stride < 1) return set_err(c, KPILQR_ERR_ARG, "pd_check_stride must be >= 1");
     { const int rcp = check_complete(c, "kpilqr_iterate"); if (rcp) return rcp; }
+    { const int rcl = check_embedded_lambda(c, "kpilqr_iterate", lambda); if (rcl) return rcl; }
     if (lambda) KP_HIP(c, hipMemcpyAsync(c->lambda, lambda, (size_t)c->d.batch * 8, hipMemcpyHostToDevice, c->stream));
     if (alphas) KP_HIP(c, hipMemcpyAsync(c->alphas, alphas, (size_t)c->d.n_alpha * 8, hipMemcpyHostToDevice, c->stream));
     if (!c->fused) {              // the fused sweeps difference (or read kpc), interpolate A, B and form l_* themselves
@@ -2202,6 +2449,7 @@ static int forward_listed(kpilqr_ctx *c, int count, const int *traj, bool list_r
 
 int kpilqr_backward_partial(kpilqr_ctx *c, int count, const int *traj, const double *lambda, int pd_check_stride, int *status, double *delta_J)
 {
+    KP_NOT_EMBEDDED(c, "kpilqr_backward_partial");
     const int go = enter_sweep_subset(c, "kpilqr_backward_partial", count, traj, true, pd_check_stride);
     if (go <= 0) return go;
     const int rc = backward_listed(c, count, traj, lambda, pd_check_stride, status, delta_J);
@@ -2210,6 +2458,7 @@ int kpilqr_backward_partial(kpilqr_ctx *c, int count, const int *traj, const dou
 
 int kpilqr_forward_linear_partial(kpilqr_ctx *c, int count, const int *traj, const double *alphas, double *cost_pred, double *U_alpha)
 {
+    KP_NOT_EMBEDDED(c, "kpilqr_forward_linear_partial");
     const int go = enter_sweep_subset(c, "kpilqr_forward_linear_partial", count, traj, false, 1);
     if (go <= 0) return go;
     const int rc = forward_listed(c, count, traj, false, alphas, cost_pred, U_alpha);
@@ -2220,6 +2469,7 @@ int kpilqr_forward_linear_partial(kpilqr_ctx *c, int count, const int *traj, con
 // where the tiled sweeps form the cost derivatives themselves), then the two sweeps; a fused context: the two sweeps.
 int kpilqr_iterate_partial(kpilqr_ctx *c, int count, const int *traj, const double *lambda, int pd_check_stride, const double *alphas)
 {
+    KP_NOT_EMBEDDED(c, "kpilqr_iterate_partial");
     const int go = enter_sweep_subset(c, "kpilqr_iterate_partial", count, traj, true, pd_check_stride);
     if (go <= 0) return go;
     if (!c->have_kp) return set_err(c, KPILQR_ERR_STATE, "kpilqr_iterate_partial before kpilqr_set_keypoints");
@@ -2974,6 +3224,7 @@ static int iterate_streamed(kpilqr_ctx *c, StreamCall call)
 
 int kpilqr_iterate_streamed(kpilqr_ctx *c, const kpilqr_stream_io *io, int pd_check_stride, int nchunks)
 {
+    KP_NOT_EMBEDDED(c, "kpilqr_iterate_streamed");
     if (!c || !io) return KPILQR_ERR_ARG;
     return iterate_streamed(c, StreamCall(io, pd_check_stride, nchunks));
 }
@@ -2990,6 +3241,7 @@ static int stream_gains_of(kpilqr_ctx *c, const kpilqr_stream_io2 *io2, StreamCa
 
 int kpilqr_iterate_streamed2(kpilqr_ctx *c, const kpilqr_stream_io2 *io2, int pd_check_stride, int nchunks)
 {
+    KP_NOT_EMBEDDED(c, "kpilqr_iterate_streamed2");
     if (!c || !io2) return KPILQR_ERR_ARG;
     StreamCall call(&io2->io, pd_check_stride, nchunks);
     if (const int rc = stream_gains_of(c, io2, &call)) return rc;
@@ -2999,6 +3251,7 @@ int kpilqr_iterate_streamed2(kpilqr_ctx *c, const kpilqr_stream_io2 *io2, int pd
 // kpilqr_iterate_streamed2 with the key-point columns as ENCODED FP32 for a payload: with kp_columns32 == NULL it IS that call
 int kpilqr_iterate_streamed3(kpilqr_ctx *c, const kpilqr_stream_io3 *io3, int pd_check_stride, int nchunks)
 {
+    KP_NOT_EMBEDDED(c, "kpilqr_iterate_streamed3");
     if (!c || !io3) return KPILQR_ERR_ARG;
     if (io3->struct_size != sizeof(kpilqr_stream_io3)) return set_err(c, KPILQR_ERR_ARG, "kpilqr_iterate_streamed3: struct_size is not sizeof(kpilqr_stream_io3) of this library");
     StreamCall call(&io3->io2.io, pd_check_stride, nchunks);
@@ -3024,6 +3277,7 @@ static int stream_rows_of(kpilqr_ctx *c, const kpilqr_stream_io4 *io4, StreamCal
 
 int kpilqr_iterate_streamed4(kpilqr_ctx *c, const kpilqr_stream_io4 *io4, int pd_check_stride, int nchunks)
 {
+    KP_NOT_EMBEDDED(c, "kpilqr_iterate_streamed4");
     if (!c || !io4) return KPILQR_ERR_ARG;
     StreamCall call(&io4->io3.io2.io, pd_check_stride, nchunks);
     if (const int rc = stream_rows_of(c, io4, &call)) return rc;
@@ -3033,6 +3287,7 @@ int kpilqr_iterate_streamed4(kpilqr_ctx *c, const kpilqr_stream_io4 *io4, int pd
 // kpilqr_iterate_streamed4 linearising and sweeping a list of trajectories alone: with sweep_traj == NULL it IS that call
 int kpilqr_iterate_streamed5(kpilqr_ctx *c, const kpilqr_stream_io5 *io5, int pd_check_stride, int nchunks)
 {
+    KP_NOT_EMBEDDED(c, "kpilqr_iterate_streamed5");
     if (!c || !io5) return KPILQR_ERR_ARG;
     if (io5->struct_size != sizeof(kpilqr_stream_io5)) return set_err(c, KPILQR_ERR_ARG, "kpilqr_iterate_streamed5: struct_size is not sizeof(kpilqr_stream_io5) of this library");
     StreamCall call(&io5->io4.io3.io2.io, pd_check_stride, nchunks);
@@ -3104,6 +3359,7 @@ static int stage_cost(kpilqr_ctx *c, Staged *s)
 
 int kpilqr_set_AB(kpilqr_ctx *c, const double *A, const double *B)
 {
+    KP_NOT_EMBEDDED(c, "kpilqr_set_AB");
     if (!c) return KPILQR_ERR_ARG;
     KP_ENTER(c);
     Staged s;
@@ -3119,6 +3375,7 @@ int kpilqr_set_AB(kpilqr_ctx *c, const double *A, const double *B)
 
 int kpilqr_get_AB(kpilqr_ctx *c, double *A, double *B)
 {
+    KP_NOT_EMBEDDED(c, "kpilqr_get_AB");
     if (!c) return KPILQR_ERR_ARG;
     KP_ENTER(c);
     { const int rcp = check_complete(c, "kpilqr_get_AB"); if (rcp) return rcp; }
@@ -3134,6 +3391,7 @@ int kpilqr_get_AB(kpilqr_ctx *c, double *A, double *B)
 
 int kpilqr_set_cost_derivs(kpilqr_ctx *c, const double *l_x, const double *l_xx, const double *l_u, const double *l_uu)
 {
+    KP_NOT_EMBEDDED(c, "kpilqr_set_cost_derivs");
     if (!c) return KPILQR_ERR_ARG;
     KP_ENTER(c);
     Staged s;
@@ -3149,6 +3407,7 @@ int kpilqr_set_cost_derivs(kpilqr_ctx *c, const double *l_x, const double *l_xx,
 
 int kpilqr_get_cost_derivs(kpilqr_ctx *c, double *l_x, double *l_xx, double *l_u, double *l_uu)
 {
+    KP_NOT_EMBEDDED(c, "kpilqr_get_cost_derivs");
     if (!c) return KPILQR_ERR_ARG;
     KP_ENTER(c);
     Staged s;
@@ -3164,6 +3423,7 @@ int kpilqr_get_cost_derivs(kpilqr_ctx *c, double *l_x, double *l_xx, double *l_u
 // ---- the union of KPILQR_FLAG_UNION_KEYPOINTS, read back (both build it on demand; synchronous) ----------------------------------
 int kpilqr_get_union_keypoints(kpilqr_ctx *c, int *traj_offsets, int *times, int times_capacity)
 {
+    KP_NOT_EMBEDDED(c, "kpilqr_get_union_keypoints");
     if (!c || !traj_offsets) return KPILQR_ERR_ARG;
     KP_ENTER(c);
     if (!c->union_on) return set_err(c, KPILQR_ERR_STATE, "kpilqr_get_union_keypoints: KPILQR_FLAG_UNION_KEYPOINTS is not active on this context");
@@ -3186,6 +3446,7 @@ int kpilqr_get_union_keypoints(kpilqr_ctx *c, int *traj_offsets, int *times, int
 
 int kpilqr_get_union_columns(kpilqr_ctx *c, double *columns, size_t capacity_doubles)
 {
+    KP_NOT_EMBEDDED(c, "kpilqr_get_union_columns");
     if (!c) return KPILQR_ERR_ARG;
     KP_ENTER(c);
     if (!c->union_on) return set_err(c, KPILQR_ERR_STATE, "kpilqr_get_union_columns: KPILQR_FLAG_UNION_KEYPOINTS is not active on this context");
@@ -3267,6 +3528,7 @@ const char *kpilqr_last_launch(kpilqr_ctx *c, int which)
     if (!uni && p.slopes) out += ":slopes";
     if (p.uni_on_union) out += ":union";
     if (c->last_width[which] >= 0) out += ":subset";
+    if (c->embed.on) out += ":emb" + std::to_string(c->n) + "x" + std::to_string(c->d.m);      // (always last: the carrier's n' x m')
     return out.c_str();
 }
 

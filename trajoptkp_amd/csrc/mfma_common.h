@@ -45,6 +45,20 @@ static inline bool kp_t1_shape(int n, int m)
 #undef KP_X
     return false;
 }
+// KPILQR_FLAG_EMBED_SHAPE: the carrier of a caller's (dof, m) -- the compiled shape with the smallest n', then the smallest m', that
+// contains it (dof <= dof', m <= m'); the caller's problem is zero-embedded into it at the ABI boundary (embed.hip).  A shape of the
+// table is its own carrier.  false: none contains it (or m > dof, which no fused sweep takes).
+static inline bool kp_t1_carrier(int dof, int m, int *carrier_dof, int *carrier_m)
+{
+    int bn = 0, bm = 0;
+    if (dof < 1 || m < 1 || m > dof) return false;
+#define KP_X(NN, MM) if (2 * dof <= NN && m <= MM && (!bn || NN < bn || (NN == bn && MM < bm))) { bn = NN; bm = MM; }
+    KP_T1_SHAPES(KP_X)
+#undef KP_X
+    if (!bn) return false;
+    *carrier_dof = bn / 2; *carrier_m = bm;
+    return true;
+}
 
 template <int NC>
 __device__ __forceinline__ d4 kp_P(const d4 &Y, const d4 &X, d4 acc)

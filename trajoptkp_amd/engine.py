@@ -59,12 +59,12 @@ class _PinnedBlock:
 
 class Engine:
     def __init__(self, dof, m, T, nr, batch=1, n_alpha=6, device=0, stream=None, generic=False, tiled=False, fused=False,
-                 union_keypoints=False):
+                 union_keypoints=False, embed=False):
         self._L = _lib.load()
         self.dof, self.n, self.m, self.T, self.nr = dof, 2 * dof, m, T, nr
         self.batch, self.n_alpha, self.device = batch, n_alpha, device
         d = _lib.Dims(dof, m, T, nr, batch, n_alpha, device, (_lib.FLAG_GENERIC_KERNELS if generic else 0) | (_lib.FLAG_TILED_KERNELS if tiled else 0) | (_lib.FLAG_FUSED if fused else 0)
-                      | (_lib.FLAG_UNION_KEYPOINTS if union_keypoints else 0))
+                      | (_lib.FLAG_UNION_KEYPOINTS if union_keypoints else 0) | (_lib.FLAG_EMBED_SHAPE if embed else 0))
         h = C.c_void_p()
         rc = self._L.kpilqr_create(C.byref(d), C.c_void_p(stream) if stream else None, C.byref(h))
         if rc != 0:
@@ -107,6 +107,14 @@ class Engine:
         self._ck(self._L.kpilqr_resize(self._h, int(dof), int(m), int(T)))
         self.dof, self.n, self.m, self.T = int(dof), 2 * int(dof), int(m), int(T)
         self._keep.clear()
+
+    def carrier_dims(self):
+        """kpilqr_get_carrier_dims: (dof', m') of the compiled shape an embedded context (embed=True) runs its sweeps at; raises
+        KpilqrError (ERR_STATE) on a context that is not embedded -- flag not given, or ignored for this shape.  Every array of this
+        class keeps the caller's (dof, m) either way."""
+        d = _lib.Dims()
+        self._ck(self._partial("kpilqr_get_carrier_dims")(self._h, C.byref(d)))
+        return d.dof, d.m
 
     @property
     def backward_variant(self):
