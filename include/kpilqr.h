@@ -166,6 +166,7 @@ typedef struct {
                                            kpilqr_upload_kp_columns_partial, kpilqr_upload_kp_columns_f32,
                                            kpilqr_upload_kp_columns_f32_partial, kpilqr_download_gains_partial,
                                            kpilqr_download_gains_f32_partial, kpilqr_upload_residuals_partial,
+                                           kpilqr_upload_residual_jacobians_f32, kpilqr_upload_residual_jacobians_f32_partial,
                                            kpilqr_upload_nominal_partial, kpilqr_fd_interpolate_partial, kpilqr_cost_derivs_partial,
                                            kpilqr_backward_partial, kpilqr_forward_linear_partial, kpilqr_iterate_partial;
                                            kpilqr_iterate_streamed, kpilqr_iterate_streamed2, kpilqr_iterate_streamed3,
@@ -516,6 +517,52 @@ int  kpilqr_upload_kp_columns(kpilqr_ctx *ctx, const double *columns, int entrie
 int  kpilqr_upload_kp_columns_f32(kpilqr_ctx *ctx, const float *columns32 /* [entries][3][n] */, int entries);
 int  kpilqr_upload_kp_columns_f32_partial(kpilqr_ctx *ctx, int count, const int *traj,
                                           const float *columns32 /* the listed trajectories' entries, back to back */, int entries);
+
+/* The per-step residual Jacobians as FP32: half the bytes of the largest upload of a task whose residuals are not affine in the
+ * state (such a task cannot use kpilqr_upload_residual_jacobians_const and sends r_x and r_u every time it linearises; Panda at
+ * T = 3000, nr = 14: 4.71 + 2.35 = 7.06 MB per trajectory, 3.53 MB as FP32, against 1.9 MB for everything else that crosses the
+ * link once the FP32 columns and the FP32 gains are on).  Opt-in: kpilqr_upload_residuals / _partial are unchanged, and a context
+ * that never makes these calls allocates, copies and launches nothing for them.  (This is the transport the column paragraph
+ * above lists as out of scope; it has since arrived here.)
+ * Contract.  r_x32 [batch][T+1][nr][n] and r_u32 [batch][T+1][nr][m] -- for the partial call the listed trajectories' rows, compact
+ * in `traj` order: [count][T+1][nr][n], [count][T+1][nr][m] -- in the layout of kpilqr_upload_residuals; NULL = not sent.  After
+ * either call the context is, bit for bit and flag for flag, what kpilqr_upload_residuals(ctx, NULL, rx, ru, NULL, NULL) -- or
+ * kpilqr_upload_residuals_partial(ctx, count, traj, NULL, rx, ru) -- leaves when rx[i] = (double)r_x32[i] and ru[i] =
+ * (double)r_u32[i]: the r_x / r_u buffers, the end of constant-Jacobian mode behind a whole r_x32, which rows of r_x have been
+ * given, r_u counted as non-zero once r_u32 is given, and with them what the fused sweeps, kpilqr_cost_derivs[_partial] and
+ * kpilqr_last_launch (:ru0, :rxc) then do: nothing downstream knows the difference.  r, w_run and w_term stay with
+ * kpilqr_upload_residuals: r is small and stays FP64.  Both pointers NULL is KPILQR_OK with nothing enqueued.
+ * Encoding (the CALLER's side).  A plain (float) cast, round to nearest even: r_x has no unit entry that would eat the mantissa, so
+ * nothing is removed or added (unlike the key-point columns above).  The library widens: dst = (double)src, an exact widening and
+ * nothing else.  FP32 subnormals widen to their value, +-inf stays +-inf, -0 stays -0, NaN stays NaN.
+ * What it costs in accuracy.  2^-24 (6e-8) relative per element of r_x and r_u.  On the numpy restatement of the pipeline
+ * (oracle/crosscheck.py; panda T = 37 .. 3000, acrobot, pushing; dense and smooth residuals, lambda 1e-4 .. 10) K and k move by at
+ * most 1.1e-7 and 8.0e-8: the 1e-6 bar the gains are held to is held for K and k, about ten times inside it.  It is NOT promised
+ * for the clamped controls of a problem whose l_xx is rank-deficient (hopper, nr = 4 < n = 12, random Jacobians: U moved by 4.3e-6).
+ * Refusals, each before anything is enqueued or changed: a NULL context (KPILQR_ERR_ARG); for the partial call the `traj` rules of
+ * the _partial family (count < 0, a NULL list with count > 0, a list that is not strictly increasing or not within [0, batch):
+ * KPILQR_ERR_ARG; count = 0: KPILQR_OK, nothing to do) and the three refusals of kpilqr_upload_residuals_partial, with its code
+ * (KPILQR_ERR_STATE) and in its words: r_x32 while the context holds constant residual Jacobians; r_x32 of a subset before a whole
+ * r_x; r_u32 of a subset on a context that runs without control residuals (:ru0).  Not through a view of
+ * kpilqr_iterate_streamed's chunks (KPILQR_ERR_STATE: a view never allocates); not on an embedded context
+ * (KPILQR_FLAG_EMBED_SHAPE: KPILQR_ERR_STATE, as listed there).
+ * How.  ONE hipMemcpyAsync per array into a staging buffer the context owns, then ONE launch per array of a streaming kernel
+ * (k_widen_rows, residuals_f32.hip: a block row per trajectory; 8-byte loads and 16-byte stores where a trajectory's element count
+ * is even -- r_x always --, single elements where it is odd) on the context's stream.  The partial call makes no copy per run of a
+ * scattered list: the kernel reads the list from its device copy and places the rows.  Pinned / pageable behaviour as
+ * kpilqr_upload_kp_columns_f32: the call waits for the stream only when an array is pageable, or when the staging buffer has to
+ * grow.  The calls order themselves behind a kpilqr_iterate_streamed still in flight.
+ * Memory cost: the staging buffer, 4 bytes x (elements of r_x32 + r_u32) of the call -- 3.5 MB per trajectory at the headline shape
+ * with both arrays --, reserved before anything is enqueued, grown on demand, kept at the largest size asked for and freed by
+ * kpilqr_destroy (KPILQR_ERR_ALLOC when it cannot be had: the context is unchanged).
+ * Out of scope: FP32 residual Jacobians inside the chunks of kpilqr_iterate_streamed* (a change of its own, as it was for the
+ * columns); embedded contexts; r itself; a bounded staging arena; an environment switch.  KPILQR_VERSION is unchanged: detect the
+ * calls by their symbols. */
+int  kpilqr_upload_residual_jacobians_f32(kpilqr_ctx *ctx, const float *r_x32 /* [batch][T+1][nr][n] or NULL */,
+                                          const float *r_u32 /* [batch][T+1][nr][m] or NULL */);
+int  kpilqr_upload_residual_jacobians_f32_partial(kpilqr_ctx *ctx, int count, const int *traj,
+                                                  const float *r_x32 /* [count][T+1][nr][n] or NULL */,
+                                                  const float *r_u32 /* [count][T+1][nr][m] or NULL */);
 
 /* One whole iteration for the batch, PIPELINED over chunks of trajectories: chunk c's uploads, its kernels and its
  * downloads run on their own stream, so H2D(c+1), kernels(c) and D2H(c-1) overlap (and so do consecutive calls: nothing

@@ -38,6 +38,7 @@ SYMBOLS = [
     "kpilqr_backward_partial", "kpilqr_forward_linear_partial", "kpilqr_iterate_partial",
     "kpilqr_upload_states_partial", "kpilqr_generate_keypoints_partial", "kpilqr_get_keypoints_partial",
     "kpilqr_get_carrier_dims",
+    "kpilqr_upload_residual_jacobians_f32", "kpilqr_upload_residual_jacobians_f32_partial",
 ]
 # entry points added without a version bump (include/kpilqr.h: "detect the entry point by its symbol"): bound only when the library
 # has them -- KPILQR_LIB may name an older build of the same major version
@@ -51,7 +52,8 @@ OPTIONAL_SYMBOLS = {"kpilqr_fd_interpolate", "kpilqr_get_union_keypoints", "kpil
                     "kpilqr_iterate_streamed4", "kpilqr_iterate_streamed5",
                     "kpilqr_backward_partial", "kpilqr_forward_linear_partial", "kpilqr_iterate_partial",
                     "kpilqr_upload_states_partial", "kpilqr_generate_keypoints_partial", "kpilqr_get_keypoints_partial",
-                    "kpilqr_get_carrier_dims"}
+                    "kpilqr_get_carrier_dims",
+                    "kpilqr_upload_residual_jacobians_f32", "kpilqr_upload_residual_jacobians_f32_partial"}
 
 
 class Dims(C.Structure):
@@ -215,6 +217,9 @@ def load():
     if hasattr(L, "kpilqr_upload_kp_columns_f32"):
         L.kpilqr_upload_kp_columns_f32.argtypes = [vp, vp, C.c_int]
         L.kpilqr_upload_kp_columns_f32_partial.argtypes = [vp, C.c_int, vp, vp, C.c_int]
+    if hasattr(L, "kpilqr_upload_residual_jacobians_f32"):
+        L.kpilqr_upload_residual_jacobians_f32.argtypes = [vp, vp, vp]
+        L.kpilqr_upload_residual_jacobians_f32_partial.argtypes = [vp, C.c_int, vp, vp, vp]
     if hasattr(L, "kpilqr_iterate_streamed3"):
         L.kpilqr_iterate_streamed3.argtypes = [vp, C.POINTER(StreamIO3), C.c_int, C.c_int]
     if hasattr(L, "kpilqr_iterate_streamed4"):

@@ -131,6 +131,7 @@ struct Ctx {
     DevBuf<double> r;             // [batch][T+1][nr]
     DevBuf<double> r_x;           // [batch][T+1][nr][n]
     DevBuf<double> r_u;           // [batch][T+1][nr][m]
+    DevBuf<float> rj32;           // [r_x32 | r_u32]: the floats of the last kpilqr_upload_residual_jacobians_f32[_partial] on their way into r_x / r_u (residuals_f32.hip); reserved on demand
     DevBuf<double> w_run, w_term; // [nr]
     DevBuf<double> u_nom;         // [batch][T][m]
     DevBuf<double> ctrl_lim;      // [2m]
@@ -322,7 +323,7 @@ struct Ctx {
     void for_each_buffer(F f)
     {
         DevMem *const all[] = {&rec, &kp_uniform, &K, &k, &r, &r_x, &r_u, &w_run, &w_term, &u_nom, &ctrl_lim, &lambda, &alphas, &cost_pred,
-                               &delta_J, &traj_cost, &status, &attempts, &gate, &traj_list, &K32, &segmap, &segent, &kp_offsets, &kp_times, &rx_const, &kpc, &kpc32, &kps, &kp_entry,
+                               &delta_J, &traj_cost, &status, &attempts, &gate, &traj_list, &K32, &segmap, &segent, &kp_offsets, &kp_times, &rx_const, &rj32, &kpc, &kpc32, &kps, &kp_entry,
                                &kp_entry_list, &fdk_dev, &kpu_offsets, &kpu_times, &kpu_src, &kpu_traj_first, &kpcu, &kpu_uniform, &fdk_alt, &kpc_alt, &kp_times_alt, &kp_upl_times, &kp_move, &X_states, &kp_thr, &kp_mask, &kp_count, &ls8, &fd_dev, &err_flag, &stage, &sweep_stage, &pipe_list,
                                &rows_stage[0], &rows_stage[1], &rows_stage[2], &rows_stage[3], &rows_stage[4], &rows_list, &sweep_ring, &emb_stage, &emb_offsets};
         for (DevMem *b : all) f(*b);
@@ -430,6 +431,9 @@ hipError_t launch_kp_columns_f32(Ctx *c, const float *src, const int *upl_first)
 // upl_first != nullptr (a chunk of kpilqr_iterate_streamed4 with upload_traj): staging holds the chunk's LISTED trajectories' entries alone;
 // upl_first [batch] (device): first entry of trajectory b inside staging, -1: not listed, its lists are left alone
 hipError_t launch_kp_columns_f32_range(Ctx *c, hipStream_t s, int l0, int l1, const float *staging, const int *upl_first = nullptr);
+// residuals_f32.hip: `count` trajectories of `per` floats each, compact in src (device; 8-byte aligned when per is even), widened into
+// rows traj[i] (device; nullptr: rows 0 .. count-1) of dst, `per` doubles per trajectory, on the context's stream
+hipError_t launch_widen_rows(Ctx *c, const int *traj, int count, long long per, const float *src, double *dst);
 // rows_in.hip, the chunks of kpilqr_iterate_streamed4 with upload_traj: rows of a chunk's staging region moved to their trajectories'
 // places on stream s.  Row i of `count` is trajectory traj[i] (device).  Fixed rows of `units` doubles: staging + i*units -> dst + traj[i]*units
 hipError_t launch_rows_in(hipStream_t s, const int *traj, int count, long long units, const double *staging, double *dst);

@@ -1949,6 +1949,71 @@ int kpilqr_upload_residuals_partial(kpilqr_ctx *c, int count, const int *traj, c
     return KPILQR_OK;
 }
 
+// ---- the per-step residual Jacobians as FP32: half the bytes of the largest upload of a task whose residuals are not affine ---------
+// The floats (include/kpilqr.h: a plain cast, nothing is encoded) go with ONE copy per array into the staging buffer the context owns
+// -- [r_x32 | r_u32], reserved on demand and kept at the largest size asked for, as the staging buffer of the FP32 columns is -- and
+// ONE launch per array (residuals_f32.hip) widens them into r_x / r_u, at the listed trajectories' rows for the partial call: the
+// kernel places the rows, so a scattered list costs no copy per run.  The callers have checked everything; `rows` trajectories are
+// compact in the caller's arrays, list == nullptr: they are trajectories 0 .. rows-1.
+static int widen_residual_jacobians_f32(kpilqr_ctx *c, int rows, const int *list, const float *r_x32, const float *r_u32)
+{
+    const size_t T1 = c->d.T + 1, nr = c->d.nr, perx = T1 * nr * c->n, peru = T1 * nr * c->d.m;
+    const size_t nx = r_x32 ? (size_t)rows * perx : 0, nu = r_u32 ? (size_t)rows * peru : 0;
+    // the staging buffer before anything is enqueued or the context changes (KPILQR_ERR_ALLOC leaves the context as it was)
+    { const int rcs = reserve(c, c->rj32, (nx + nu) * sizeof(float), kExact, false); if (rcs < 0) return rcs; }
+    if (!(nx + nu)) return KPILQR_OK;
+    const int *list_dev = nullptr;
+    if (list) {
+        KP_HIP(c, hipMemcpyAsync(c->traj_list, list, (size_t)rows * sizeof(int), hipMemcpyHostToDevice, c->stream));
+        list_dev = c->traj_list;
+    }
+    float *const sx = c->rj32, *const su = sx + nx;           // (nx is even: r_u32's floats start on a pair)
+    if (nx) {
+        KP_HIP(c, hipMemcpyAsync(sx, r_x32, nx * sizeof(float), hipMemcpyHostToDevice, c->stream));
+        KP_HIP(c, launch_widen_rows(c, list_dev, rows, (long long)perx, sx, c->r_x));
+    }
+    if (nu) {
+        KP_HIP(c, hipMemcpyAsync(su, r_u32, nu * sizeof(float), hipMemcpyHostToDevice, c->stream));
+        KP_HIP(c, launch_widen_rows(c, list_dev, rows, (long long)peru, su, c->r_u));
+    }
+    return KPILQR_OK;
+}
+
+int kpilqr_upload_residual_jacobians_f32(kpilqr_ctx *c, const float *r_x32, const float *r_u32)
+{
+    KP_NOT_EMBEDDED(c, "kpilqr_upload_residual_jacobians_f32");
+    if (!c) return KPILQR_ERR_ARG;
+    KP_ENTER(c);
+    if (c->is_view) return set_err(c, KPILQR_ERR_STATE, "kpilqr_upload_residual_jacobians_f32: not through a view of a trajectory range");
+    if (!r_x32 && !r_u32) return KPILQR_OK;
+    const int rc = widen_residual_jacobians_f32(c, c->d.batch, nullptr, r_x32, r_u32);
+    if (rc) return rc;
+    // (the state kpilqr_upload_residuals leaves)
+    if (r_x32) { c->rx_const_on = false; c->rx_buf_valid = c->rx_whole = true; }
+    if (r_u32) c->ru_zero = false;
+    if (!(is_pinned(r_x32) && is_pinned(r_u32))) KP_HIP(c, hipStreamSynchronize(c->stream));
+    return KPILQR_OK;
+}
+
+int kpilqr_upload_residual_jacobians_f32_partial(kpilqr_ctx *c, int count, const int *traj, const float *r_x32, const float *r_u32)
+{
+    KP_NOT_EMBEDDED(c, "kpilqr_upload_residual_jacobians_f32_partial");
+    int rc = enter_subset(c, "kpilqr_upload_residual_jacobians_f32_partial", count, traj);        // (refuses a view, as every listed call)
+    if (rc <= 0) return rc;
+    // (the refusals of kpilqr_upload_residuals_partial, in its words)
+    if (r_x32 && c->rx_const_on)
+        return set_err(c, KPILQR_ERR_STATE, "kpilqr_upload_residual_jacobians_f32_partial: the context holds constant residual Jacobians; a whole r_x through kpilqr_upload_residuals ends that mode first");
+    if (r_x32 && !(c->rx_buf_valid && c->rx_whole))
+        return set_err(c, KPILQR_ERR_STATE, "kpilqr_upload_residual_jacobians_f32_partial: r_x of a subset before a whole r_x: kpilqr_upload_residuals first");
+    if (r_u32 && c->ru_zero)
+        return set_err(c, KPILQR_ERR_STATE, "kpilqr_upload_residual_jacobians_f32_partial: r_u of a subset on a context that runs without control residuals: a whole r_u through kpilqr_upload_residuals first");
+    if (!r_x32 && !r_u32) return KPILQR_OK;
+    rc = widen_residual_jacobians_f32(c, count, traj, r_x32, r_u32);
+    if (rc) return rc;
+    if (!(is_pinned(r_x32) && is_pinned(r_u32))) KP_HIP(c, hipStreamSynchronize(c->stream));
+    return KPILQR_OK;
+}
+
 int kpilqr_upload_nominal_partial(kpilqr_ctx *c, int count, const int *traj, const double *u_nom)
 {
     KP_NOT_EMBEDDED(c, "kpilqr_upload_nominal_partial");

@@ -585,6 +585,29 @@ class Engine:
         self._keep += [r_x, r_u]
         self._ck(self._L.kpilqr_upload_residual_jacobians_const(self._h, _ptr(r_x), _ptr(r_u)))
 
+    def upload_residual_jacobians_f32(self, r_x32=None, r_u32=None, traj=None):
+        """kpilqr_upload_residual_jacobians_f32[_partial]: the per-step residual Jacobians as FP32 -- float32 r_x32 [batch][T+1][nr][n],
+        r_u32 [batch][T+1][nr][m], or with traj the listed trajectories' rows, compact in traj order; None = not sent.  The library
+        widens them exactly into the FP64 buffers (synth.residual_jacobians_f32 makes the cast, which is the caller's)."""
+        tr = None if traj is None else self._traj(traj)
+        rows = self.batch if tr is None else len(tr)
+
+        def f32(a, cols, name):
+            if a is None:
+                return None
+            a = np.asarray(a)
+            if a.dtype != np.float32:
+                raise ValueError(f"{name} must be a float32 array (no silent rounding here: the cast is the caller's)")
+            if a.shape != (rows, self.T + 1, self.nr, cols):
+                raise ValueError(f"{name} must have shape {(rows, self.T + 1, self.nr, cols)}, not {a.shape}")
+            return np.ascontiguousarray(a)
+        r_x32, r_u32 = f32(r_x32, self.n, "r_x32"), f32(r_u32, self.m, "r_u32")
+        self._keep += [tr, r_x32, r_u32]
+        if tr is None:
+            self._ck(self._partial("kpilqr_upload_residual_jacobians_f32")(self._h, _ptr(r_x32), _ptr(r_u32)))
+        else:
+            self._ck(self._partial("kpilqr_upload_residual_jacobians_f32_partial")(self._h, len(tr), _ptr(tr), _ptr(r_x32), _ptr(r_u32)))
+
     def cost_derivs(self):
         self._ck(self._L.kpilqr_cost_derivs(self._h))
 

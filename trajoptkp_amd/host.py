@@ -32,6 +32,8 @@ def load_host():
     H.kpilqr_host_keypoints.restype = C.c_int
     H.kpilqr_host_run_acrobot.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_double, vp, C.c_int, vp, vp, vp]
     H.kpilqr_host_run_acrobot.restype = C.c_int
+    H.kpilqr_host_run_acrobot2.argtypes = H.kpilqr_host_run_acrobot.argtypes + [vp]
+    H.kpilqr_host_run_acrobot2.restype = C.c_int
     H.kpilqr_host_fd_bench.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp]
     H.kpilqr_host_fd_bench.restype = C.c_int
     H.kpilqr_host_save_trajec.argtypes = [C.c_char_p, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]
@@ -81,16 +83,19 @@ def run_acrobot(T=100, min_N=5, max_iter=5, min_iter=2, method="set_interval", t
     "+analytic", "+constjac", "+low_pass" / "+FIR", "+q0=a,b", "+columns" (the FD results are differenced on the host and the
     key-point columns uploaded), and with it "+f32cols" (the columns cross the link as FP32, kpilqr_upload_kp_columns_f32; the default
     is FP64) or "+hostf32cols" (rounded alike but decoded on the host and uploaded as FP64: the run "+f32cols" must reproduce).
-    payload_bytes_uploaded: the FD payload bytes the run moved up the link."""
+    "+f32resjac": the per-step residual Jacobians cross the link as FP32 (kpilqr_upload_residual_jacobians_f32; the default is FP64),
+    "+hostf32resjac": rounded alike but widened on the host and uploaded as FP64 (the run "+f32resjac" must reproduce); "+constjac"
+    ignores both.  payload_bytes_uploaded: the FD payload bytes the run moved up the link; residual_bytes_uploaded: r, r_x and r_u."""
     H = load_host()
-    hist = np.zeros(max_iter + 2); U = np.zeros(T); K0 = np.zeros(4); tm = np.zeros(8)
-    it = H.kpilqr_host_run_acrobot(T, min_N, max_iter, min_iter, method.encode(), float(torque_weight), _p(hist), len(hist), _p(U), _p(K0), _p(tm))
+    hist = np.zeros(max_iter + 2); U = np.zeros(T); K0 = np.zeros(4); tm = np.zeros(8); inputs = np.zeros(1)
+    it = H.kpilqr_host_run_acrobot2(T, min_N, max_iter, min_iter, method.encode(), float(torque_weight), _p(hist), len(hist), _p(U), _p(K0), _p(tm),
+                                    _p(inputs))
     if it < 0:
         raise RuntimeError(f"kpilqr_host_run_acrobot failed: {it}")
     return dict(iterations=it, cost_history=hist[:it + 1].copy(), U=U, K0=K0,
                 timings_ms=dict(derivs=tm[0], backward=tm[1], forward=tm[2], total=tm[3]),
                 constant_jacobian_uploads=int(tm[4]), per_step_jacobian_uploads=int(tm[5]), last_backward_rxc=bool(tm[6]),
-                payload_bytes_uploaded=int(tm[7]))
+                payload_bytes_uploaded=int(tm[7]), residual_bytes_uploaded=int(inputs[0]))
 
 
 def fd_kp_check(model, T, min_N, stagger, u):
@@ -167,6 +172,8 @@ def run_acrobot_batch(q0s, T=100, min_N=5, max_iter=6, min_iter=2, torque_weight
     "+f32gains" (K comes down as FP32, kpilqr_download_gains_f32_partial; the default is FP64), "+devretry" (STEP 2's PD retry runs
     on the device, kpilqr_set_lambda_retry; the default is the host loop), "+signedtorque" (torque_weight is taken as given, sign
     included: a negative weight makes PD checks fail at small lambda; without it a negative value means the task's default),
+    "+f32resjac" (the per-step residual Jacobians cross the link as FP32, kpilqr_upload_residual_jacobians_f32[_partial]; the default is
+    FP64) or "+hostf32resjac" (rounded alike, widened on the host, uploaded as FP64: the run "+f32resjac" must reproduce),
     "+activesweeps" (STEP 2 sweeps the active trajectories that are not settled, STEP 3 those with a valid backward pass:
     kpilqr_backward_partial / kpilqr_forward_linear_partial; the default sweeps the whole batch every time).
     backward_trajectories_swept / forward_trajectories_swept: trajectories swept by STEP 2 / STEP 3, summed over the calls.

@@ -47,9 +47,18 @@ int kpilqr_host_keypoints(const char *method, int dof, int T, int min_N, int max
 // from the hanging-ish start [3.1415, 0.3] (acrobot.yaml:16).  Runs Optimise(max_iter, min_iter) on the
 // GPU engine; writes cost_history (initial cost first) and the final controls.  Returns iterations run,
 // or <0 on error.
+int kpilqr_host_run_acrobot2(int T, int min_N, int max_iter, int min_iter, const char *keypoint_method_name, double torque_weight,
+                             double *cost_history, int cost_cap, double *U_out, double *K0_out, double *timings_ms, double *inputs);
 int kpilqr_host_run_acrobot(int T, int min_N, int max_iter, int min_iter, const char *keypoint_method_name,
                             double torque_weight /* <0: task default 100 */,
                             double *cost_history, int cost_cap, double *U_out, double *K0_out, double *timings_ms)
+{
+    return kpilqr_host_run_acrobot2(T, min_N, max_iter, min_iter, keypoint_method_name, torque_weight, cost_history, cost_cap, U_out, K0_out, timings_ms, nullptr);
+}
+
+// ... and the per-linearisation inputs: inputs [1] = residual (r, and r_x, r_u unless "+constjac") bytes uploaded
+int kpilqr_host_run_acrobot2(int T, int min_N, int max_iter, int min_iter, const char *keypoint_method_name, double torque_weight,
+                             double *cost_history, int cost_cap, double *U_out, double *K0_out, double *timings_ms, double *inputs)
 {
     // keypoint_method_name may carry options after a '+': "set_interval+unfused", "set_interval+analytic", "set_interval+fused+columns+f32cols"
     std::string spec = keypoint_method_name ? keypoint_method_name : "";
@@ -84,6 +93,10 @@ int kpilqr_host_run_acrobot(int T, int min_N, int max_iter, int min_iter, const 
     // on the host and uploaded as FP64 -- the run "+f32cols" must reproduce
     opt.kp_columns_f32 = keypoint_method_full.find("+f32cols") != std::string::npos;
     opt.kp_columns_f32_on_host = keypoint_method_full.find("+hostf32cols") != std::string::npos;
+    // "+f32resjac": the per-step residual Jacobians go up as FP32 (kpilqr_upload_residual_jacobians_f32); "+hostf32resjac": rounded
+    // alike, widened on the host and uploaded as FP64 -- the run "+f32resjac" must reproduce
+    opt.residual_jacobians_f32 = keypoint_method_full.find("+f32resjac") != std::string::npos;
+    opt.residual_jacobians_f32_on_host = keypoint_method_full.find("+hostf32resjac") != std::string::npos;
     if (lowpass || fir) { opt.filteringMethod = lowpass ? "low_pass" : "FIR"; opt.SetFused(false); }
     std::vector<MatrixXd> U0(T, MatrixXd(1, 1));
     std::vector<MatrixXd> U = opt.Optimise(sim->main_data, U0, max_iter, min_iter, T);
@@ -96,6 +109,7 @@ int kpilqr_host_run_acrobot(int T, int min_N, int max_iter, int min_iter, const 
         timings_ms[4] = opt.constant_jacobian_uploads; timings_ms[5] = opt.per_step_jacobian_uploads;
         timings_ms[6] = opt.LastLaunch(0).find(":rxc") != std::string::npos ? 1.0 : 0.0; timings_ms[7] = (double)opt.payload_bytes_uploaded;
     }
+    if (inputs) inputs[0] = (double)opt.residual_bytes_uploaded;
     return opt.num_iterations;
 }
 
@@ -203,6 +217,9 @@ int kpilqr_host_run_acrobot_batch7(int B, int T, int min_N, int max_iter, int mi
     opt.gains_f32 = method && std::string(method).find("+f32gains") != std::string::npos;
     opt.device_lambda_retry = method && std::string(method).find("+devretry") != std::string::npos;
     opt.active_sweeps = method && std::string(method).find("+activesweeps") != std::string::npos;
+    // "+f32resjac" / "+hostf32resjac": iLQR_GPU_Batch::residual_jacobians_f32 / residual_jacobians_f32_on_host
+    opt.residual_jacobians_f32 = method && std::string(method).find("+f32resjac") != std::string::npos;
+    opt.residual_jacobians_f32_on_host = method && std::string(method).find("+hostf32resjac") != std::string::npos;
     std::vector<std::vector<MatrixXd>> U0(B, std::vector<MatrixXd>(T, MatrixXd(1, 1)));
     auto U = opt.OptimiseAll(U0, max_iter, min_iter);
     for (int b = 0; b < B; b++) {

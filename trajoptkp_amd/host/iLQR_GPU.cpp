@@ -36,6 +36,8 @@ void iLQR_GPU::free_pinned()
     for (double **p : all) { if (*p && ctx) kpilqr_host_free(ctx, *p); *p = nullptr; }
     if (host_K32 && ctx) kpilqr_host_free(ctx, host_K32);
     host_K32 = nullptr;
+    float **all32[] = {&host_rx32, &host_ru32};
+    for (float **p : all32) { if (*p && ctx) kpilqr_host_free(ctx, *p); *p = nullptr; }
     if (kp_slab && ctx) kpilqr_host_free(ctx, kp_slab);
     kp_slab = nullptr; kp_slab_bytes = 0;
     if (kp_cols && ctx) kpilqr_host_free(ctx, kp_cols);
@@ -267,10 +269,28 @@ void iLQR_GPU::GenerateDerivatives()
         rc = kpilqr_upload_residuals(ctx, host_r, nullptr, nullptr, w_run.data(), w_term.data());
     } else {
         activeDifferentiator->ResidualDerivativesAll(host_rx, host_ru, T, eps);
-        rc = kpilqr_upload_residuals(ctx, host_r, host_rx, host_ru, w_run.data(), w_term.data());
+        const size_t nx = (size_t)(T + 1) * nr * n, nu = (size_t)(T + 1) * nr * num_ctrl;
+        if (residual_jacobians_f32) {
+            // the Jacobians cross the link as FP32 -- a plain cast into pinned float buffers, the library widens --; r and the weights as ever
+            if (!host_rx32 && (rc = kpilqr_host_alloc(ctx, std::max<size_t>(nx, 1) * sizeof(float), (void **)&host_rx32))) fatal("kpilqr_host_alloc", rc);
+            if (!host_ru32 && (rc = kpilqr_host_alloc(ctx, std::max<size_t>(nu, 1) * sizeof(float), (void **)&host_ru32))) fatal("kpilqr_host_alloc", rc);
+            for (size_t i = 0; i < nx; i++) host_rx32[i] = (float)host_rx[i];
+            for (size_t i = 0; i < nu; i++) host_ru32[i] = (float)host_ru[i];
+            if ((rc = kpilqr_upload_residuals(ctx, host_r, nullptr, nullptr, w_run.data(), w_term.data()))) fatal("kpilqr_upload_residuals", rc);
+            if ((rc = kpilqr_upload_residual_jacobians_f32(ctx, host_rx32, host_ru32))) fatal("kpilqr_upload_residual_jacobians_f32", rc);
+            residual_bytes_uploaded += (nx + nu) * sizeof(float);
+        } else {
+            if (residual_jacobians_f32_on_host) {         // rounded alike, widened here: the doubles the library's widening must leave
+                for (size_t i = 0; i < nx; i++) host_rx[i] = (double)(float)host_rx[i];
+                for (size_t i = 0; i < nu; i++) host_ru[i] = (double)(float)host_ru[i];
+            }
+            rc = kpilqr_upload_residuals(ctx, host_r, host_rx, host_ru, w_run.data(), w_term.data());
+            residual_bytes_uploaded += (nx + nu) * sizeof(double);
+        }
         per_step_jacobian_uploads++;
     }
     if (rc) fatal("kpilqr_upload_residuals", rc);
+    residual_bytes_uploaded += (size_t)(T + 1) * nr * sizeof(double);
     if (!fused_active && (rc = kpilqr_cost_derivs(ctx))) fatal("kpilqr_cost_derivs", rc);
     double pct = 0.0;
     for (int i = 0; i < sv.dof; i++) pct += keypoint_generator->last_percentages[i];

@@ -42,6 +42,16 @@ public:
     // The same rounding, but decoded on the host and uploaded as FP64 through kpilqr_upload_kp_columns: what the FP32 route must
     // reproduce bit for bit (tests; telling a precision question from a transport one)
     bool kp_columns_f32_on_host = false;
+    // The per-step residual Jacobians cross the link as FP32 (kpilqr_upload_residual_jacobians_f32: half the bytes of the largest
+    // upload of a task whose residuals are not affine): what ResidualDerivativesAll produced is cast -- a plain cast, nothing is
+    // encoded -- into pinned float buffers and the library widens it; r and the weights go up as before.  K and k move by 1e-7 at
+    // most on the measured problems (include/kpilqr.h).  Off by default: the reference's bits.  A task with
+    // ConstantResidualJacobians ignores both options.
+    bool residual_jacobians_f32 = false;
+    // The same rounding, but widened on the host and uploaded as FP64 through kpilqr_upload_residuals: what the FP32 route must
+    // reproduce bit for bit (tests; telling a precision question from a transport one)
+    bool residual_jacobians_f32_on_host = false;
+    size_t residual_bytes_uploaded = 0;      // r, r_x and r_u bytes that crossed the link since construction (the constant pair not counted)
     size_t payload_bytes_uploaded = 0;       // FD payload bytes (x+ / x- records, job slabs or columns) that crossed the link since construction
     // K comes down as FP32 (kpilqr_download_gains_f32: half the bytes of the largest per-iteration download) into a pinned float
     // array and is widened into K[t], which is exact; every element is the round-to-nearest-even cast of the FP64 gain (at most
@@ -100,6 +110,7 @@ private:
     float *kp_cols32 = nullptr;              // kp_columns_f32: the encoded columns as they cross the link, pinned; allocated when the option is first used
     size_t kp_cols32_count = 0;
     double *host_r = nullptr, *host_rx = nullptr, *host_ru = nullptr, *host_unom = nullptr, *host_K = nullptr, *host_k = nullptr;
+    float *host_rx32 = nullptr, *host_ru32 = nullptr;      // residual_jacobians_f32: r_x, r_u as they cross the link, pinned; allocated when the option is first used
     float *host_K32 = nullptr;               // gains_f32: K as it crosses the link, pinned; allocated when the option is first used
     void free_pinned();
     bool fused_active = false, recreate_ctx = false;

@@ -69,6 +69,8 @@ iLQR_GPU_Batch::~iLQR_GPU_Batch()
     kp_slab = kp_part = nullptr;
     if (host_K32) kpilqr_host_free(ctx, host_K32);
     host_K32 = nullptr;
+    float **all32[] = {&host_rx32, &host_ru32};
+    for (float **p : all32) { if (*p) kpilqr_host_free(ctx, *p); *p = nullptr; }
     double **all[] = {&host_r, &host_rx, &host_ru, &host_unom, &host_K, &host_k};
     for (double **p : all) { if (*p) kpilqr_host_free(ctx, *p); *p = nullptr; }
     kpilqr_destroy(ctx);
@@ -310,14 +312,30 @@ void iLQR_GPU_Batch::GenerateDerivatives(const std::vector<int> &who)
         if ((rc = kpilqr_upload_residual_jacobians_const(ctx, const_rx.data(), ru_zero ? nullptr : const_ru.data()))) fatal("kpilqr_upload_residual_jacobians_const", rc);
         const_jacobians_resident = true;
     }
-    const double *jac_x = const_jacobians ? nullptr : host_rx, *jac_u = const_jacobians ? nullptr : host_ru;
-    const size_t traj_bytes = (size_t)(T + 1) * nr * (const_jacobians ? 1 : 1 + n + m) * sizeof(double);
+    // residual_jacobians_f32: the rows just written (compact rows of `who`, or everybody's) are cast into pinned float buffers and
+    // cross the link as FP32 behind r, which goes up as ever; residual_jacobians_f32_on_host rounds alike, widens here and sends FP64
+    const bool jac32 = residual_jacobians_f32 && !const_jacobians;
+    const size_t perx = (size_t)(T + 1) * nr * n, peru = (size_t)(T + 1) * nr * m, rows = part_in ? (size_t)nwho : (size_t)B;
+    if (jac32) {
+        if (!host_rx32 && (rc = kpilqr_host_alloc(ctx, std::max<size_t>((size_t)B * perx, 1) * sizeof(float), (void **)&host_rx32))) fatal("kpilqr_host_alloc", rc);
+        if (!host_ru32 && (rc = kpilqr_host_alloc(ctx, std::max<size_t>((size_t)B * peru, 1) * sizeof(float), (void **)&host_ru32))) fatal("kpilqr_host_alloc", rc);
+        for (size_t i = 0; i < rows * perx; i++) host_rx32[i] = (float)host_rx[i];
+        for (size_t i = 0; i < rows * peru; i++) host_ru32[i] = (float)host_ru[i];
+    } else if (residual_jacobians_f32_on_host && !const_jacobians) {
+        for (size_t i = 0; i < rows * perx; i++) host_rx[i] = (double)(float)host_rx[i];
+        for (size_t i = 0; i < rows * peru; i++) host_ru[i] = (double)(float)host_ru[i];
+    }
+    const double *jac_x = const_jacobians || jac32 ? nullptr : host_rx, *jac_u = const_jacobians || jac32 ? nullptr : host_ru;
+    const size_t traj_bytes = (size_t)(T + 1) * nr * sizeof(double)
+                            + (const_jacobians ? 0 : (perx + peru) * (jac32 ? sizeof(float) : sizeof(double)));
     if (part_in) {
         if ((rc = kpilqr_upload_residuals_partial(ctx, nwho, who.data(), host_r, jac_x, jac_u))) fatal("kpilqr_upload_residuals_partial", rc);
+        if (jac32 && (rc = kpilqr_upload_residual_jacobians_f32_partial(ctx, nwho, who.data(), host_rx32, host_ru32))) fatal("kpilqr_upload_residual_jacobians_f32_partial", rc);
         residual_bytes_uploaded += (size_t)nwho * traj_bytes;
         if (!fused_active && (rc = kpilqr_cost_derivs_partial(ctx, nwho, who.data()))) fatal("kpilqr_cost_derivs_partial", rc);
     } else {
         if ((rc = kpilqr_upload_residuals(ctx, host_r, jac_x, jac_u, w_run.data(), w_term.data()))) fatal("kpilqr_upload_residuals", rc);
+        if (jac32 && (rc = kpilqr_upload_residual_jacobians_f32(ctx, host_rx32, host_ru32))) fatal("kpilqr_upload_residual_jacobians_f32", rc);
         residual_bytes_uploaded += (size_t)B * traj_bytes;
         if (!fused_active && (rc = kpilqr_cost_derivs(ctx))) fatal("kpilqr_cost_derivs", rc);
     }

@@ -54,6 +54,12 @@ public:
     // rows of the regenerating trajectories alone once a complete linearisation is resident -- and U_old up at every iteration, the
     // rows that changed since the last upload alone.  Weights and control limits are not counted.
     size_t residual_bytes_uploaded = 0, nominal_bytes_uploaded = 0;
+    // The per-step residual Jacobians cross the link as FP32 (kpilqr_upload_residual_jacobians_f32, or its _partial form where a subset
+    // re-linearises): what ResidualDerivativesAll produced is cast -- a plain cast -- into pinned float buffers and the library widens
+    // it; r goes up as before.  residual_bytes_uploaded counts the floats as 4 bytes.  Off by default: the FP64 Jacobians, bit for bit
+    // as before.  residual_jacobians_f32_on_host: rounded alike, widened on the host and uploaded as FP64 -- the run the FP32 route
+    // must reproduce bit for bit.  A task with ConstantResidualJacobians ignores both.
+    bool residual_jacobians_f32 = false, residual_jacobians_f32_on_host = false;
     // true: residuals, nominal controls and (on a materialising context) the step records go through the whole-batch calls at every
     // linearisation, as before the partial calls existed -- the A/B of the tests
     bool whole_inputs = false;
@@ -110,6 +116,7 @@ private:
     std::vector<char> unom_stale;           // [B] U_old changed since the device's row was uploaded
     std::vector<double> const_rx, const_ru;
     double *host_r = nullptr, *host_rx = nullptr, *host_ru = nullptr, *host_unom = nullptr, *host_K = nullptr, *host_k = nullptr;
+    float *host_rx32 = nullptr, *host_ru32 = nullptr;      // residual_jacobians_f32: r_x, r_u as they cross the link, pinned [B][T+1][nr][n | m]; allocated when the option is first used
     float *host_K32 = nullptr;              // gains_f32: K as it crosses the link, pinned [B][T][n][m]; allocated when the option is first used
 };
 

@@ -466,6 +466,13 @@ def kp_columns_f32(p):
     return encode_kp_columns_f32(kp_columns(p), kp_entry_dofs(p), p["dof"])
 
 
+def residual_jacobians_f32(p):
+    """(r_x32, r_u32): the per-step residual Jacobians of a problem as FP32 -- a plain round-to-nearest-even cast, nothing is encoded
+    (include/kpilqr.h) --, the payload of kpilqr_upload_residual_jacobians_f32 / Engine.upload_residual_jacobians_f32.  The library
+    widens them exactly: what it then holds is r_x32.astype(np.float64), r_u32.astype(np.float64)."""
+    return np.ascontiguousarray(p["r_x"], dtype=np.float32), np.ascontiguousarray(p["r_u"], dtype=np.float32)
+
+
 def upload(engine, p, keypoints=True, kp_ordered=False, rx_const=False):
     """Push a problem dict into an Engine (everything the GPU path needs to run one iteration).  kp_ordered: the FD
     payload goes up key-point ordered (kpilqr_upload_fd_kp) instead of as job lists.  rx_const: a problem whose residual
