@@ -18,14 +18,14 @@ CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
 
 # loop -> steps per group (register sets of the time loop, ring slots, steps per block)
 GROUPS = {
-    "ric_t1": 2,                # KP_RIC_SETS, riccati_mfma.hip:85: preload :167-170, request :219, pair loop and tail :335-344
-    "fwd_t1": 2,                # Tiles S[2], forward_mfma.hip:117: preload :118-119, request :126, pair loop and odd step :158-159
-    "fused_fwd_uni": 4,         # KP_FWD_SETS, fused_mfma.hip:53: NS :1691, preload :1725, request :1801, fwd_steps / fwd_tail :1952-1953
-    "fused_fwd_gen": 4,         # min(KP_FWD_SETS_GEN, 4), fused_mfma.hip:1691 (per-DoF lists, r_u streamed): loop :1956-1957
-    "fused_fwd_gen_ru0": 6,     # KP_FWD_SETS_GEN, fused_mfma.hip:56 (per-DoF lists, r_u = 0): loop :1956-1957
-    "fused_fsc": 4,             # KP_FSC_SETS, fused_mfma.hip:60: state wave :2169-2179 (t + 4 <= T), cost wave :2309-2323 (t + 3 <= T)
-    "fused_ring": 2,            # the 2 FPC_BUF slots of the consumer / helper ring, fused_mfma.hip:1481 (slot t & 1, :624, :1425)
-    "tiled_fwd": 2,             # KP_FT_SETS, tiled_mfma.hip:23: NS :1266, preload :1280, request :1307, pair loop :1484-1485
+    "ric_t1": 2,                # KP_RIC_SETS, riccati_mfma.hip:61: preload :133-136, request :186, pair loop and tail :302-311
+    "fwd_t1": 2,                # Tiles S[2], forward_mfma.hip:92: preload :93-94, request :101, pair loop and odd step :133-134
+    "fused_fwd_uni": 4,         # KP_FWD_SETS, fused_mfma.hip:50: NS :1620, preload :1654, request :1730, fwd_steps / fwd_tail :1881-1882
+    "fused_fwd_gen": 4,         # min(KP_FWD_SETS_GEN, 4), fused_mfma.hip:1620 (per-DoF lists, r_u streamed): loop :1885-1886
+    "fused_fwd_gen_ru0": 6,     # KP_FWD_SETS_GEN, fused_mfma.hip:53 (per-DoF lists, r_u = 0): loop :1885-1886
+    "fused_fsc": 4,             # KP_FSC_SETS, fused_mfma.hip:57: state wave :2098-2108 (t + 4 <= T), cost wave :2238-2252 (t + 3 <= T)
+    "fused_ring": 2,            # the 2 FPC_BUF slots of the consumer / helper ring, fused_mfma.hip:1410 (slot t & 1, :564, :1354)
+    "tiled_fwd": 2,             # KP_FT_SETS, tiled_mfma.hip:23: NS :1179, preload :1193, request :1220, pair loop :1397-1398
     "interp": 16,               # INTERP_TT, elementwise.hip:433: steps per block (:441-442)
     "cost": 4,                  # COST_TT, elementwise.hip:494: steps per block (:505-506)
 }
@@ -55,7 +55,7 @@ W1 = {"KPILQR_FUSED_WAVES": "1", "KPILQR_FUSED_FWD_WAVES": "1"}
 
 
 def parsed_groups(csrc=CSRC):
-    """GROUPS as the sources have it (fused_fwd_gen: the expression of fused_mfma.hip:1691 on the parsed define)."""
+    """GROUPS as the sources have it (fused_fwd_gen: the expression of fused_mfma.hip:1620 on the parsed define)."""
     out = {}
     for loop, (name, pat) in _SOURCES.items():
         found = re.findall(pat, open(os.path.join(csrc, name)).read(), re.M)
@@ -85,7 +85,7 @@ def loops_of(c, n_simd):
             out.add("fused_fsc")
         else:                                           # (r_u = 0 exactly where the case's r_x is the task's constant: _shape_run._problem)
             out.add("fused_fwd_uni" if c["uniform"] else "fused_fwd_gen_ru0" if c["rx_const"] else "fused_fwd_gen")
-    if fwd[0] == "tiled_fwd" and fwd[2] == "-" and fwd[3] > 0:      # NS = KP_FT_SETS where NCL > 0 && !A6, tiled_mfma.hip:1266
+    if fwd[0] == "tiled_fwd" and fwd[2] == "-" and fwd[3] > 0:      # NS = KP_FT_SETS where NCL > 0 && !A6, tiled_mfma.hip:1179
         out.add("tiled_fwd")
     if "fused" not in d["variants"][0]:                  # _shape_run._backward: the materialising stages
         out.add("interp")
@@ -102,7 +102,7 @@ def _forms():
         f[f"fused_w1_d{dof}"] = (dof, m, nr, FLAG_FUSED, W1, True, True, H, "mfma_f64_t1_fused")
         f[f"t1_d{dof}"] = (dof, m, 4, 0, {}, False, True, H, "mfma_f64_t1")
         # per-DoF lists: the general one-wave forward with four sets behind the pair backward, the triple behind the pair
-        # forward (what "4" runs on a per-DoF set at 4 x batch <= #SIMDs, plan_forward_fused, fused_mfma.hip:2413-2414) ...
+        # forward (what "4" runs on a per-DoF set at 4 x batch <= #SIMDs, plan_forward_fused, fused_mfma.hip:2342-2343) ...
         f[f"fused_ragged_stream_d{dof}"] = (dof, m, 4, FLAG_FUSED, {"KPILQR_FUSED_WAVES": "5", "KPILQR_FUSED_FWD_WAVES": "1"}, False, False,
                                             H_RAGGED, "mfma_f64_t1_fused")
         f[f"fused_ragged_rxc_d{dof}"] = (dof, m, 4, FLAG_FUSED, {"KPILQR_FUSED_WAVES": "0", "KPILQR_FUSED_FWD_WAVES": "4"}, True, False,

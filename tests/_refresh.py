@@ -6,15 +6,15 @@ Every sweep carries the explicit inverse X of Q = Quu + lambda I from step to st
 many is read off e = m max|I - Q X0|, X0 the first guess.  File:line citations are to trajoptkp_amd/csrc.
 
   family    kernel                                   first guess   series          bins (label: e below)
-  plain     kp_inverse_refresh, mfma_common.h:65     X             X (I + R)       series 3e-8 | +1 1.7e-4 | +2 1.3e-2 | +3 0.11
-            (tiled col / u-wave / a6, tiled_mfma.hip:531, 831; KP_NS_HOLD = 8, :19)
-  plain_col the same in the col and a6 forms: a give-up on an indefinite step leaves the whole hold behind it (tiled_mfma.hip:566)
-  wide      tiled_wide.hip:350-391                   as plain, no hold
-  p         kp_inverse_refresh_p, :99                2 X - Xprev   X0 (I + R + R^2)   series 2e-5 | +1 1.7e-4 | +2 1.3e-2 | +3 0.11
-            (one-tile materialising, riccati_mfma.hip:233)
-  n         kp_inverse_refresh_n<.,0,0>, :143        as p (on the negated inverse; fused one-wave general form, fused_mfma.hip:752)
+  plain     kp_inverse_refresh, mfma_common.h:203    X             X (I + R)       series 3e-8 | +1 1.7e-4 | +2 1.3e-2 | +3 0.11
+            (tiled col / u-wave / a6, tiled_mfma.hip:444, 744; KP_NS_HOLD = 8, :19)
+  plain_col the same in the col and a6 forms: a give-up on an indefinite step leaves the whole hold behind it (tiled_mfma.hip:479)
+  wide      tiled_wide.hip:275-316                   as plain, no hold
+  p         kp_inverse_refresh_p, :238               2 X - Xprev   X0 (I + R + R^2)   series 2e-5 | +1 1.7e-4 | +2 1.3e-2 | +3 0.11
+            (one-tile materialising, riccati_mfma.hip:200)
+  n         kp_inverse_refresh_n<.,0,0>, :283        as p (on the negated inverse; fused one-wave general form, fused_mfma.hip:692)
   n_kink    the same; KINK on the peeled steps       2 X - Xprev   ... + R^3       series 1.7e-4 | +1 1.3e-2 | +2 0.11
-            (fused one-wave uniform form: the step right below a key-point, fused_mfma.hip:751, 933)
+            (fused one-wave uniform form: the step right below a key-point, fused_mfma.hip:691, 873)
   n_ser4    kp_inverse_refresh_n<.,0,1>              as p, but     ser4 (one more term) for 2e-5 <= e < 1.7e-4 (consumer wave of pairh)
 
 Beyond 0.11 the refresh gives up and the step factorises (ldl_giveup); so do the first step (ldl_first: no inverse yet, also
@@ -25,8 +25,8 @@ import functools
 
 import numpy as np
 
-GIVE_UP = 0.11                                          # mfma_common.h:74, 116, 161; tiled_wide.hip:383
-T_SER_PLAIN, T_SER, T_1, T_2 = 3.0e-8, 2.0e-5, 1.7e-4, 1.3e-2   # mfma_common.h:75-77 | :115, 160 | :76, 117, 160, 162, 172 | :75, 117, 171
+GIVE_UP = 0.11                                          # mfma_common.h:213, 256, 302; tiled_wide.hip:315
+T_SER_PLAIN, T_SER, T_1, T_2 = 3.0e-8, 2.0e-5, 1.7e-4, 1.3e-2   # mfma_common.h:214-216 | :255, 301 | :215, 257, 301, 303, 313 | :214, 257, 312
 KP_NS_HOLD = 8                                          # tiled_mfma.hip:19
 # Every achieved e keeps this factor from every threshold.  (1.25 was asked for, next to targets 5 .. 25 % under the top of a bin
 # and one at 0.12: those are 1.05 and 1.09 from a threshold, and 22 % under the top a second-order step fewer leaves 2e-13, under
@@ -85,7 +85,7 @@ LABEL_ONLY = ("keep_xprev", "hold_short")
 
 
 def peeled_steps(kp_times, T):
-    """The steps the uniform segment-loop forms peel (may_be_first, fused_mfma.hip:584, 933): the first step of every segment
+    """The steps the uniform segment-loop forms peel (may_be_first, fused_mfma.hip:524, 873): the first step of every segment
     [k_p, k_p+1), k_Kp := T, taken from the top: T - 1 and the step right below every key-point but the first."""
     kp = sorted(int(x) for x in kp_times)
     return {T - 1} | {k - 1 for k in kp[1:]}
@@ -164,7 +164,7 @@ class RefreshModel:
             if Y is not None:
                 self.Xprev, self.X = self.X, Y
                 return Y, label, e
-            if self.family in HOLD:                     # the give-up step and KP_NS_HOLD more factorise (tiled_mfma.hip:829-832; :540, 566)
+            if self.family in HOLD:                     # the give-up step and KP_NS_HOLD more factorise (tiled_mfma.hip:742-745; :453, 479)
                 self.hold = KP_NS_HOLD - (1 if self.mut == "hold_short" else 0)
         sym = np.tril(Q) + np.tril(Q, -1).T             # the factorisations read the lower triangle
         pos = bool(np.all(np.linalg.eigvalsh(sym) > 0.0))

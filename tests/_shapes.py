@@ -6,9 +6,9 @@ instantiation, the smallest and the largest problem that reaches it.  tests/test
 File:line citations are to trajoptkp_amd/csrc.  n = 2 dof; T1_SHAPES are the (n, m) pairs of the one-tile kernels."""
 
 FLAG_GENERIC, FLAG_TILED, FLAG_FUSED = 1, 2, 4          # include/kpilqr.h:75-77
-T1_SHAPES = ((14, 7), (4, 1), (12, 3), (10, 3))        # KP_T1_SHAPES, mfma_common.h:40
-BIGOFF = 0x40000000                                     # fused_mfma.hip:47
-TILE, TPAD = 256, 272                                   # tiled_mfma.hip:36-37
+T1_SHAPES = ((14, 7), (4, 1), (12, 3), (10, 3))        # KP_T1_SHAPES, mfma_common.h:174
+BIGOFF = 0x40000000                                     # fused_mfma.hip:44
+TILE, TPAD = 256, 272                                   # KP_TILE, KP_TPAD, mfma_common.h:20-21
 LDS_MAX = 160 * 1024                                    # the LDS bound of the tiled and generic backward sweeps
 ENV_KEYS = ("KPILQR_FUSED_WAVES", "KPILQR_FUSED_FWD_WAVES", "KPILQR_TILED_NT_MIN", "KPILQR_TILED_A6", "KPILQR_TILED_UW",
             "KPILQR_TILED_FSC")
@@ -24,11 +24,11 @@ def _cdiv(a, b):                                        # C's int division (trun
     return q if (a >= 0) == (b > 0) else -q
 
 
-def tiled_nt(n, nt_min=0):                              # tiled_nt, tiled_mfma.hip:649 (wide_nt, tiled_wide.hip:488, is the same)
+def tiled_nt(n, nt_min=0):                              # tiled_nt, tiled_mfma.hip:562 (wide_nt, tiled_wide.hip:413, is the same)
     return max((n + 1 + 15) // 16, 2, nt_min)
 
 
-def backward_col_lds_bytes(nt):                         # tiled_mfma.hip:641
+def backward_col_lds_bytes(nt):                         # tiled_mfma.hip:554
     return 8 * ((2 * nt * nt + 7 * nt) * TILE + max(nt * nt * TPAD, 832))
 
 
@@ -36,28 +36,28 @@ def generic_lds_bytes(n, m):                            # backward_generic_lds_b
     return 8 * (2 * n * n + 4 * m * n + 5 * m * m + 2 * n + 4 * m + m + 2)
 
 
-def fused_supported(n, m, nr, dof, T, n_alpha):         # fused_mfma.hip:2248
+def fused_supported(n, m, nr, dof, T, n_alpha):         # fused_mfma.hip:2177
     return (n, m) in T1_SHAPES and 1 <= nr <= 16 and m <= dof and n_alpha <= 16 and T * dof * (6 * n + 2) * 8 < BIGOFF
 
 
-def backward_tiled_supported(n, m, nt_min=0):           # tiled_mfma.hip:659
+def backward_tiled_supported(n, m, nt_min=0):           # tiled_mfma.hip:572
     nt = tiled_nt(n, nt_min)
     return 2 <= nt <= 4 and 1 <= m <= 8 and backward_col_lds_bytes(nt) <= LDS_MAX
 
 
-def forward_t1_supported(n, m, n_alpha):                # forward_mfma_supported, forward_mfma.hip:184
+def forward_t1_supported(n, m, n_alpha):                # forward_mfma_supported, forward_mfma.hip:159
     return n + 2 <= 16 and m <= 8 and n_alpha <= 16 and n >= 2
 
 
-def forward_tiled_supported(n, m, n_alpha, nt_min=0):   # tiled_mfma.hip:1851
+def forward_tiled_supported(n, m, n_alpha, nt_min=0):   # tiled_mfma.hip:1734
     return 2 <= tiled_nt(n, nt_min) <= 4 and m <= 16 and n_alpha <= 16
 
 
-def backward_wide_supported(n, m, nt_min=0):            # tiled_wide.hip:496
+def backward_wide_supported(n, m, nt_min=0):            # tiled_wide.hip:421
     return 2 <= tiled_nt(n, nt_min) <= 4 and 8 < m <= 32
 
 
-def forward_wide_supported(n, m, n_alpha, nt_min=0):    # tiled_wide.hip:724
+def forward_wide_supported(n, m, n_alpha, nt_min=0):    # tiled_wide.hip:649
     return 2 <= tiled_nt(n, nt_min) <= 4 and 16 < m <= 32 and n_alpha <= 16
 
 
@@ -67,7 +67,7 @@ def select_variants(dof, m, nr, T, n_alpha, batch, flags, env=None):
     n = 2 * dof
     nt_min = _env(env, "KPILQR_TILED_NT_MIN", 0)
     generic, force_tiled = bool(flags & FLAG_GENERIC), bool(flags & FLAG_TILED)
-    bv = ("mfma_f64_t1" if not generic and not force_tiled and (n, m) in T1_SHAPES            # riccati_mfma.hip:375
+    bv = ("mfma_f64_t1" if not generic and not force_tiled and (n, m) in T1_SHAPES            # riccati_mfma.hip:342
           else "mfma_f64_tiled" if not generic and backward_tiled_supported(n, m, nt_min)
           else "mfma_f64_wide" if not generic and backward_wide_supported(n, m, nt_min) else "generic_lds")
     fv = ("mfma_f64_t1" if not generic and not force_tiled and forward_t1_supported(n, m, n_alpha)
@@ -87,7 +87,7 @@ def select_variants(dof, m, nr, T, n_alpha, batch, flags, env=None):
 
 def rv2_ncr(nr):
     """4-row chunks of the relabelled residual rows of the one-wave fused sweeps with a constant r_x and r_u = 0 (RV2B,
-    fused_mfma.hip:343; RV2 in the forward sweep, :1459-1482): registers 0, 1 of a lane hold residuals 0 .. 7, 2, 3 hold 8 .. 15."""
+    fused_mfma.hip:283; RV2 in the forward sweep, :1388-1411): registers 0, 1 of a lane hold residuals 0 .. 7, 2, 3 hold 8 .. 15."""
     return 4 if nr > 9 else 3 if nr > 8 else 2 if nr > 1 else 1
 
 
@@ -104,16 +104,16 @@ def dispatch(dof, m, nr, T, n_alpha, batch, n_simd, flags, env=None, rx_const=Fa
     n = 2 * dof
     nt = tiled_nt(n, _env(env, "KPILQR_TILED_NT_MIN", 0))
     uw = _env(env, "KPILQR_TILED_UW", -1)
-    excl = "excl" if batch <= n_simd else "plain"       # riccati_mfma.hip:384, forward_mfma.hip:193, FusedLaunch::excl, fused_mfma.hip:2283, 2303
+    excl = "excl" if batch <= n_simd else "plain"       # riccati_mfma.hip:351, forward_mfma.hip:168, FusedLaunch::excl, fused_mfma.hip:2212, 2232
     ncz, ncu = (n + 2 + 3) // 4, (m + 3) // 4
     out = dict(variants=(bv, fv), extra=(), launch=(bv, fv))
     if bv == "mfma_f64_t1_fused":
         f = _env(env, "KPILQR_FUSED_WAVES", 0)
-        bform = f if f in (1, 5) else (5 if 2 * batch <= n_simd else 1)           # plan_backward_fused, fused_mfma.hip:2272-2276
+        bform = f if f in (1, 5) else (5 if 2 * batch <= n_simd else 1)           # plan_backward_fused, fused_mfma.hip:2201-2205
         f = _env(env, "KPILQR_FUSED_FWD_WAVES", 0)
-        fform = f if f in (1, 3, 4) else (4 if 2 * batch <= n_simd else 1)        # plan_forward_fused, :2294-2298
+        fform = f if f in (1, 3, 4) else (4 if 2 * batch <= n_simd else 1)        # plan_forward_fused, :2223-2227
         out["bwd"] = ("fused_bwd", n, m, "w1", excl) if bform == 1 else ("fused_bwd", n, m, "pairh", "-")
-        if fform == 4:                                  # the uniform pair; per-DoF lists run the triple or w1 behind it (waves_ragged, :2299)
+        if fform == 4:                                  # the uniform pair; per-DoF lists run the triple or w1 behind it (waves_ragged, :2228)
             behind = 3 if 4 * batch <= n_simd else 1
             fform_ran = 4 if uniform else behind
         else:
@@ -128,40 +128,40 @@ def dispatch(dof, m, nr, T, n_alpha, batch, n_simd, flags, env=None, rx_const=Fa
         out["launch"] = (bv + (":w1:" if bform == 1 else ":pairh:"), fv + ":" + {1: "w1", 3: "triple", 4: "pair"}[fform_ran] + ":")
         return out
     if bv == "mfma_f64_t1":
-        out["bwd"] = ("t1_bwd", n, m, excl)             # launch_backward_mfma, riccati_mfma.hip:390
+        out["bwd"] = ("t1_bwd", n, m, excl)             # launch_backward_mfma, riccati_mfma.hip:357
     elif bv.startswith("mfma_f64_tiled"):
         a6 = bv.endswith("_a6")
-        M = 7 if m == 7 else 1 if m == 1 else 8         # launch_backward_tiled, tiled_mfma.hip:1134-1140
-        if nt <= 3 and not a6 and uw != 0:              # launch_bt, :1128-1131
-            rows = n + 1 - 16 * (nt - 1)                # launch_bt_uw, :1087-1097
+        M = 7 if m == 7 else 1 if m == 1 else 8         # launch_backward_tiled, tiled_mfma.hip:1047-1053
+        if nt <= 3 and not a6 and uw != 0:              # launch_bt, :1041-1044
+            rows = n + 1 - 16 * (nt - 1)                # launch_bt_uw, :1000-1010
             ncl = 4 if rows >= 16 else max(_cdiv(rows + 3, 4), 1)
             out["bwd"] = ("tiled_bwd", M, nt, ncl, "uw")
         else:
             ncl = 0
-            if nt == 4 and uw != 0:                     # launch_bt2, :1112-1124
+            if nt == 4 and uw != 0:                     # launch_bt2, :1025-1037
                 rows = n + 1 - 16 * (nt - 1)
                 ncl = 4 if rows >= 16 else _cdiv(rows + 3, 4)
             out["bwd"] = ("tiled_bwd", M, nt, ncl, "a6" if a6 else "col")
     elif bv == "mfma_f64_wide":
-        out["bwd"] = ("wide_bwd", nt, 2 if m > 16 else 1)   # launch_backward_wide, tiled_wide.hip:513-519
+        out["bwd"] = ("wide_bwd", nt, 2 if m > 16 else 1)   # launch_backward_wide, tiled_wide.hip:438-444
     else:
         out["bwd"] = ("generic_bwd",)
-    if fv == "mfma_f64_t1":                             # launch_forward_mfma, forward_mfma.hip:199-204
+    if fv == "mfma_f64_t1":                             # launch_forward_mfma, forward_mfma.hip:174-204
         out["fwd"] = ("t1_fwd", max(ncz, 2), min(ncu, 2), excl)
     elif fv.startswith("mfma_f64_tiled"):
         a6 = fv.endswith("_a6")
         fsc = _env(env, "KPILQR_TILED_FSC", -1)
-        sc = nt == 2 and not a6 and m <= 8 and (fsc != 0 if fsc >= 0 else 2 * nt * batch <= n_simd)   # tiled_mfma.hip:1907-1913
+        sc = nt == 2 and not a6 and m <= 8 and (fsc != 0 if fsc >= 0 else 2 * nt * batch <= n_simd)   # tiled_mfma.hip:1790-1796
         rows = n + 2 - 16 * (nt - 1)
-        if sc:                                          # launch_ft_sc, :1888-1896
+        if sc:                                          # launch_ft_sc, :1771-1779
             ncl = 4 if rows >= 16 else 1 if rows < 1 else _cdiv(rows + 3, 4)
             out["fwd"] = ("tiled_fwd_sc", ncl, ncu)
             out["launch"] = (out["launch"][0], fv + ":state_cost_waves")
-        else:                                           # launch_ft2, :1868-1881
+        else:                                           # launch_ft2, :1751-1764
             ncl = (4 if rows >= 16 else max(_cdiv(rows + 3, 4), 1)) if uw != 0 else 0
             out["fwd"] = ("tiled_fwd", nt, "a6" if a6 else "-", ncl)
     elif fv == "mfma_f64_wide":
-        out["fwd"] = ("wide_fwd", nt)                   # launch_forward_wide, tiled_wide.hip:743-750
+        out["fwd"] = ("wide_fwd", nt)                   # launch_forward_wide, tiled_wide.hip:668-675
     else:
         out["fwd"] = ("generic_fwd",)
     return out
@@ -171,22 +171,22 @@ def _compiled():
     """The instantiations the library compiles, by hand from the launchers (not derived from dispatch)."""
     keys = []
     for n, m in T1_SHAPES:
-        keys += [("t1_bwd", n, m, e) for e in ("excl", "plain")]                       # launch_bm, riccati_mfma.hip:380-395
-        keys += [("fused_bwd", n, m, "w1", e) for e in ("excl", "plain")]              # launch_bf_kernel ... launch_backward_fused, fused_mfma.hip:2308-2352
-        keys += [("fused_bwd", n, m, "pairh", "-")]                                    # launch_bph_kernel ... launch_backward_fused_pair, :2358-2393
-        keys += [("fused_rv2", n, m, ncr) for ncr in (1, 2, 3, 4)]                     # :343
-    keys += [("t1_fwd", ncz, ncu, e) for ncz in (2, 3, 4) for ncu in (1, 2) for e in ("excl", "plain")]   # launch_fm, forward_mfma.hip:189-203
-    for ncz, ncu in ((4, 2), (2, 1), (4, 1), (3, 1)):                                  # KP_FWD_SHAPES, fused_mfma.hip:2458 (launch_ff_pair, _triple, _w1: 2418-2448)
+        keys += [("t1_bwd", n, m, e) for e in ("excl", "plain")]                       # launch_bm, riccati_mfma.hip:347-362
+        keys += [("fused_bwd", n, m, "w1", e) for e in ("excl", "plain")]              # launch_bf_kernel ... launch_backward_fused, fused_mfma.hip:2237-2281
+        keys += [("fused_bwd", n, m, "pairh", "-")]                                    # launch_bph_kernel ... launch_backward_fused_pair, :2287-2322
+        keys += [("fused_rv2", n, m, ncr) for ncr in (1, 2, 3, 4)]                     # :283
+    keys += [("t1_fwd", ncz, ncu, e) for ncz in (2, 3, 4) for ncu in (1, 2) for e in ("excl", "plain")]   # launch_fm, forward_mfma.hip:164-178
+    for ncz, ncu in ((4, 2), (2, 1), (4, 1), (3, 1)):                                  # KP_FWD_SHAPES, fused_mfma.hip:2387 (launch_ff_pair, _triple, _w1: 2418-2448)
         keys += [("fused_fwd", ncz, ncu, "w1", e) for e in ("excl", "plain")]
         keys += [("fused_fwd", ncz, ncu, f, "-") for f in ("pair", "triple")]
-    for M in (1, 7, 8):                                                                # tiled_mfma.hip:1134-1140
-        keys += [("tiled_bwd", M, nt, ncl, "uw") for nt in (2, 3) for ncl in (1, 2, 3, 4)]          # :1090-1095
-        keys += [("tiled_bwd", M, 4, ncl, f) for ncl in (1, 2, 3, 4) for f in ("col", "a6")]      # :1118-1123
-        keys += [("tiled_bwd", M, nt, 0, f) for nt in (2, 3, 4) for f in ("col", "a6")]           # :1124
-    keys += [("tiled_fwd", nt, a6, ncl) for nt in (2, 3, 4) for a6 in ("-", "a6") for ncl in (0, 1, 2, 3, 4)]   # :1877-1882
-    keys += [("tiled_fwd_sc", ncl, ncu) for ncu in (1, 2) for ncl in (1, 2, 3, 4)]                       # KP_SC, :1893
-    keys += [("wide_bwd", nt, mt) for nt in (2, 3, 4) for mt in (1, 2)]                                  # tiled_wide.hip:516-517
-    keys += [("wide_fwd", nt) for nt in (2, 3, 4)]                                                       # tiled_wide.hip:746-748
+    for M in (1, 7, 8):                                                                # tiled_mfma.hip:1047-1053
+        keys += [("tiled_bwd", M, nt, ncl, "uw") for nt in (2, 3) for ncl in (1, 2, 3, 4)]          # :1003-1008
+        keys += [("tiled_bwd", M, 4, ncl, f) for ncl in (1, 2, 3, 4) for f in ("col", "a6")]      # :1031-1036
+        keys += [("tiled_bwd", M, nt, 0, f) for nt in (2, 3, 4) for f in ("col", "a6")]           # :1037
+    keys += [("tiled_fwd", nt, a6, ncl) for nt in (2, 3, 4) for a6 in ("-", "a6") for ncl in (0, 1, 2, 3, 4)]   # :1760-1765
+    keys += [("tiled_fwd_sc", ncl, ncu) for ncu in (1, 2) for ncl in (1, 2, 3, 4)]                       # KP_SC, :1776
+    keys += [("wide_bwd", nt, mt) for nt in (2, 3, 4) for mt in (1, 2)]                                  # tiled_wide.hip:441-442
+    keys += [("wide_fwd", nt) for nt in (2, 3, 4)]                                                       # tiled_wide.hip:671-673
     keys += [("generic_bwd",), ("generic_fwd",)]
     return keys
 

@@ -21,31 +21,6 @@
 
 namespace kpilqr {
 
-#define MFMA(a, b, c) __builtin_amdgcn_mfma_f64_16x16x4f64((a), (b), (c), 0, 0, 0)
-
-template <int NC>
-__device__ __forceinline__ d4 PF(const d4 &Y, const d4 &X, d4 acc)
-{
-    acc = MFMA(Y.x, X.x, acc);
-    if (NC > 1) acc = MFMA(Y.y, X.y, acc);
-    if (NC > 2) acc = MFMA(Y.z, X.z, acc);
-    if (NC > 3) acc = MFMA(Y.w, X.w, acc);
-    return acc;
-}
-
-// Bounds-checked buffer loads: a lane whose tile element is a structural zero carries an out-of-range
-// offset and gets 0 from the hardware (no select on the loaded value -> the loads of step t+1 stay in
-// flight behind the whole of step t; see riccati_mfma.hip).
-#define OOB 0x7ffffff0
-__device__ __forceinline__ double bld(__amdgpu_buffer_rsrc_t r, int byte_off)
-{
-    return __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(r, byte_off, 0, 0));
-}
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t rsrc(const double *p, int bytes)
-{
-    return __builtin_amdgcn_make_buffer_rsrc((void *)p, 0, bytes, 0x00020000);
-}
-
 template <int NCZ, int NCU>
 __device__ __forceinline__ void forward_body(RecLayout L, int T, int n_alpha, const double *__restrict__ rec,
                const double *__restrict__ Kin, const double *__restrict__ kin,
@@ -57,23 +32,23 @@ __device__ __forceinline__ void forward_body(RecLayout L, int T, int n_alpha, co
     const int lane = threadIdx.x, c = lane & 15, q = lane >> 4;
     const int b = btraj;
 
-    // per-lane source BYTE offsets; OOB = structural zero
+    // per-lane source BYTE offsets; KP_OOB = structural zero
     int oK[4], ok_[4], oA[4], oB[4], oLc[4], oLuu[4], olu[4], oub[4];
     double oneA[4], lo[4], hi[4];
 #pragma unroll
     for (int r = 0; r < 4; r++) {
         const int row = 4 * r + q;
-        oK[r] = (row < n && c < m) ? 8 * (row * m + c) : OOB;            // K(i=c, p=row) at c + row*m
-        ok_[r] = (row == n && c < m) ? 8 * c : OOB;                      // k(i=c)
-        oA[r] = (row < n && c < n) ? 8 * L.a(c, row) : OOB;  // A(i=c, p=row)
+        oK[r] = (row < n && c < m) ? 8 * (row * m + c) : KP_OOB;            // K(i=c, p=row) at c + row*m
+        ok_[r] = (row == n && c < m) ? 8 * c : KP_OOB;                      // k(i=c)
+        oA[r] = (row < n && c < n) ? 8 * L.a(c, row) : KP_OOB;  // A(i=c, p=row)
         oneA[r] = ((row == n && c == n) || (row == n + 1 && c == n + 1)) ? 1.0 : 0.0;
-        oB[r] = (row < m && c < n) ? 8 * L.b(c, row) : OOB;  // B(i=c, p=row)
+        oB[r] = (row < m && c < n) ? 8 * L.b(c, row) : KP_OOB;  // B(i=c, p=row)
         oLc[r] = (row < n && c < n) ? 8 * (L.off_lxx + row * n + c)
                : (row == n + 1 && c < n) ? 8 * (L.off_lx + c)
-               : (c == n + 1 && row < n) ? 8 * (L.off_lx + row) : OOB;
-        oLuu[r] = (row < m && c < m) ? 8 * (L.off_luu + row * m + c) : OOB;
-        olu[r] = (row < m) ? 8 * (L.off_lu + row) : OOB;
-        oub[r] = (row < m) ? 8 * row : OOB;
+               : (c == n + 1 && row < n) ? 8 * (L.off_lx + row) : KP_OOB;
+        oLuu[r] = (row < m && c < m) ? 8 * (L.off_luu + row * m + c) : KP_OOB;
+        olu[r] = (row < m) ? 8 * (L.off_lu + row) : KP_OOB;
+        oub[r] = (row < m) ? 8 * row : KP_OOB;
         lo[r] = (row < m) ? ctrl_lim[2 * row] : -1.0e300;
         hi[r] = (row < m) ? ctrl_lim[2 * row + 1] : 1.0e300;
     }
@@ -94,22 +69,22 @@ __device__ __forceinline__ void forward_body(RecLayout L, int T, int n_alpha, co
     struct Tiles { d4 YkK, Ykk, Ya, Yb, Lc, Luu, lu, ub; };
     const int rec_bytes = L.rec * 8;
     auto load_tiles = [&](int t, Tiles &s) {
-        __amdgpu_buffer_rsrc_t rR = rsrc(rec + ((size_t)b * T + t) * L.stride, rec_bytes);
-        __amdgpu_buffer_rsrc_t rK = rsrc(Kin + ((size_t)b * T + t) * m * n, m * n * 8);
-        __amdgpu_buffer_rsrc_t rk = rsrc(kin + ((size_t)b * T + t) * m, m * 8);
-        __amdgpu_buffer_rsrc_t ru = rsrc(u_nom + ((size_t)b * T + t) * m, m * 8);
-        s.YkK.x = bld(rK, oK[0]); s.YkK.y = bld(rK, oK[1]); s.YkK.z = bld(rK, oK[2]); s.YkK.w = bld(rK, oK[3]);
-        s.Ykk.x = bld(rk, ok_[0]); s.Ykk.y = bld(rk, ok_[1]); s.Ykk.z = bld(rk, ok_[2]); s.Ykk.w = bld(rk, ok_[3]);
-        s.Ya.x = bld(rR, oA[0]); s.Ya.y = bld(rR, oA[1]); s.Ya.z = bld(rR, oA[2]); s.Ya.w = bld(rR, oA[3]);
-        s.Yb.x = bld(rR, oB[0]); s.Yb.y = NCU > 1 ? bld(rR, oB[1]) : 0.0;
-        s.Yb.z = NCU > 2 ? bld(rR, oB[2]) : 0.0; s.Yb.w = NCU > 3 ? bld(rR, oB[3]) : 0.0;
-        s.Lc.x = bld(rR, oLc[0]); s.Lc.y = bld(rR, oLc[1]); s.Lc.z = bld(rR, oLc[2]); s.Lc.w = bld(rR, oLc[3]);
-        s.Luu.x = bld(rR, oLuu[0]); s.Luu.y = NCU > 1 ? bld(rR, oLuu[1]) : 0.0;
-        s.Luu.z = NCU > 2 ? bld(rR, oLuu[2]) : 0.0; s.Luu.w = NCU > 3 ? bld(rR, oLuu[3]) : 0.0;
-        s.lu.x = bld(rR, olu[0]); s.lu.y = NCU > 1 ? bld(rR, olu[1]) : 0.0;
-        s.lu.z = NCU > 2 ? bld(rR, olu[2]) : 0.0; s.lu.w = NCU > 3 ? bld(rR, olu[3]) : 0.0;
-        s.ub.x = bld(ru, oub[0]); s.ub.y = NCU > 1 ? bld(ru, oub[1]) : 0.0;
-        s.ub.z = NCU > 2 ? bld(ru, oub[2]) : 0.0; s.ub.w = NCU > 3 ? bld(ru, oub[3]) : 0.0;
+        __amdgpu_buffer_rsrc_t rR = kp_rsrc(rec + ((size_t)b * T + t) * L.stride, rec_bytes);
+        __amdgpu_buffer_rsrc_t rK = kp_rsrc(Kin + ((size_t)b * T + t) * m * n, m * n * 8);
+        __amdgpu_buffer_rsrc_t rk = kp_rsrc(kin + ((size_t)b * T + t) * m, m * 8);
+        __amdgpu_buffer_rsrc_t ru = kp_rsrc(u_nom + ((size_t)b * T + t) * m, m * 8);
+        s.YkK.x = kp_bld(rK, oK[0]); s.YkK.y = kp_bld(rK, oK[1]); s.YkK.z = kp_bld(rK, oK[2]); s.YkK.w = kp_bld(rK, oK[3]);
+        s.Ykk.x = kp_bld(rk, ok_[0]); s.Ykk.y = kp_bld(rk, ok_[1]); s.Ykk.z = kp_bld(rk, ok_[2]); s.Ykk.w = kp_bld(rk, ok_[3]);
+        s.Ya.x = kp_bld(rR, oA[0]); s.Ya.y = kp_bld(rR, oA[1]); s.Ya.z = kp_bld(rR, oA[2]); s.Ya.w = kp_bld(rR, oA[3]);
+        s.Yb.x = kp_bld(rR, oB[0]); s.Yb.y = NCU > 1 ? kp_bld(rR, oB[1]) : 0.0;
+        s.Yb.z = NCU > 2 ? kp_bld(rR, oB[2]) : 0.0; s.Yb.w = NCU > 3 ? kp_bld(rR, oB[3]) : 0.0;
+        s.Lc.x = kp_bld(rR, oLc[0]); s.Lc.y = kp_bld(rR, oLc[1]); s.Lc.z = kp_bld(rR, oLc[2]); s.Lc.w = kp_bld(rR, oLc[3]);
+        s.Luu.x = kp_bld(rR, oLuu[0]); s.Luu.y = NCU > 1 ? kp_bld(rR, oLuu[1]) : 0.0;
+        s.Luu.z = NCU > 2 ? kp_bld(rR, oLuu[2]) : 0.0; s.Luu.w = NCU > 3 ? kp_bld(rR, oLuu[3]) : 0.0;
+        s.lu.x = kp_bld(rR, olu[0]); s.lu.y = NCU > 1 ? kp_bld(rR, olu[1]) : 0.0;
+        s.lu.z = NCU > 2 ? kp_bld(rR, olu[2]) : 0.0; s.lu.w = NCU > 3 ? kp_bld(rR, olu[3]) : 0.0;
+        s.ub.x = kp_bld(ru, oub[0]); s.ub.y = NCU > 1 ? kp_bld(ru, oub[1]) : 0.0;
+        s.ub.z = NCU > 2 ? kp_bld(ru, oub[2]) : 0.0; s.ub.w = NCU > 3 ? kp_bld(ru, oub[3]) : 0.0;
     };
     // Two tile sets (even / odd steps), each re-requested for step t+2 as soon as step t has taken its copy; the time loop is a
     // body of two steps without conditions (a request behind `if (t + 1 < T)` makes the waits that follow conservative), the
@@ -129,8 +104,8 @@ __device__ __forceinline__ void forward_body(RecLayout L, int T, int n_alpha, co
         // Order of the step: every product is a dependent MFMA chain whose result is usable ~100 cycles after its last
         // issue, so an independent chain follows each one before its consumer:
         //   U chain | A dx chain | clamp (U ready) | B du | l_uu du | Lc Z | cost
-        d4 U = PF<NCZ>(Yk, Z, ub);        // u_nom + K dx + alpha k
-        d4 Zn = PF<NCZ>(Ya, Z, zero);     // A dx (does not need the controls)
+        d4 U = kp_P<NCZ>(Yk, Z, ub);        // u_nom + K dx + alpha k
+        d4 Zn = kp_P<NCZ>(Ya, Z, zero);     // A dx (does not need the controls)
         d4 dU;
         {
             double u;
@@ -139,9 +114,9 @@ __device__ __forceinline__ void forward_body(RecLayout L, int T, int n_alpha, co
             u = U.z; if (u > hi[2]) u = hi[2]; if (u < lo[2]) u = lo[2]; U.z = u; dU.z = u - ub.z;
             u = U.w; if (u > hi[3]) u = hi[3]; if (u < lo[3]) u = lo[3]; U.w = u; dU.w = u - ub.w;
         }
-        Zn = PF<NCU>(Yb, dU, Zn);         // + B du: the next state
-        d4 Wu = PF<NCU>(Luu, dU, zero);
-        d4 Wz = PF<NCZ>(Lc, Z, zero);
+        Zn = kp_P<NCU>(Yb, dU, Zn);         // + B du: the next state
+        d4 Wu = kp_P<NCU>(Luu, dU, zero);
+        d4 Wz = kp_P<NCZ>(Lc, Z, zero);
         if (U_alpha && c < n_alpha) {
             double *Ua = U_alpha + (((size_t)b * n_alpha + c) * T + t) * m;
             const double uv[4] = {U.x, U.y, U.z, U.w};

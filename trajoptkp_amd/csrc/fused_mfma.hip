@@ -36,10 +36,7 @@
 
 namespace kpilqr {
 
-typedef unsigned int u32x2f __attribute__((ext_vector_type(2)));
 typedef unsigned long long u64;
-#define MFMA(a, b, c) __builtin_amdgcn_mfma_f64_16x16x4f64((a), (b), (c), 0, 0, 0)
-#define OOBF 0x7ffffff0
 #define BIGT 0x3fffffff
 // An offset no trajectory's slice of kpc reaches (fused_supported keeps a slice below 1 GB): a lane / register / entry with
 // nothing to load adds it instead of selecting -- BIGOFF and BIGOFF + BIGOFF are both out of range of the descriptor and do
@@ -74,45 +71,6 @@ typedef unsigned long long u64;
 #else
 #define KP_BLOCK_TRAJ ((int)blockIdx.x)
 #endif
-template <int NC>
-__device__ __forceinline__ d4 PS(const d4 &Y, const d4 &X, d4 acc)
-{
-    acc = MFMA(Y.x, X.x, acc);
-    if (NC > 1) acc = MFMA(Y.y, X.y, acc);
-    if (NC > 2) acc = MFMA(Y.z, X.z, acc);
-    if (NC > 3) acc = MFMA(Y.w, X.w, acc);
-    return acc;
-}
-__device__ __forceinline__ d4 PR(const d4 &Y, const d4 &X, d4 acc, int nc)      // nc wave-uniform
-{
-    acc = MFMA(Y.x, X.x, acc);
-    if (nc > 1) acc = MFMA(Y.y, X.y, acc);
-    if (nc > 2) acc = MFMA(Y.z, X.z, acc);
-    if (nc > 3) acc = MFMA(Y.w, X.w, acc);
-    return acc;
-}
-__device__ __forceinline__ double fbld(__amdgpu_buffer_rsrc_t r, int byte_off)
-{
-    return __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(r, byte_off, 0, 0));
-}
-// the same with a wave-uniform byte offset in the instruction's scalar operand: ONE descriptor per array and trajectory,
-// the step selected by an SGPR, instead of a descriptor rebuilt (64-bit address arithmetic, ~8 SALU) per array and step
-__device__ __forceinline__ double fblds(__amdgpu_buffer_rsrc_t r, int byte_off, int soff)
-{
-    return __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(r, byte_off, soff, 0));
-}
-// two consecutive doubles with one request (16-byte aligned)
-typedef unsigned int u32x4f __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ void fbld2s(__amdgpu_buffer_rsrc_t r, int byte_off, int soff, double &a, double &b)
-{
-    const u32x4f v = __builtin_amdgcn_raw_buffer_load_b128(r, byte_off, soff, 0);
-    const u32x2f lo = {v.x, v.y}, hi = {v.z, v.w};
-    a = __builtin_bit_cast(double, lo); b = __builtin_bit_cast(double, hi);
-}
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t frsrc(const void *p, int bytes)
-{
-    return __builtin_amdgcn_make_buffer_rsrc((void *)p, 0, bytes, 0x00020000);
-}
 // correctly rounded a/den for a normal-range quotient: one residual correction on top of a ~1 ulp reciprocal
 // (the hardware division expansion without its scaling / fix-up tail; den is a small positive integer)
 __device__ __forceinline__ double fdiv(double a, double den, double rinv)
@@ -181,28 +139,21 @@ __device__ __forceinline__ void load_col(__amdgpu_buffer_rsrc_t rT, const ColOff
     const int base = ((unsigned)tk < (unsigned)T) ? tk * strideB : BIGOFF;
 #pragma unroll
     for (int r = 0; r < 4; r++) {
-        col[r] = fbld(rT, base + o.a[r]);
-        col[4 + r] = fbld(rT, base + o.b[r]);
+        col[r] = kp_bld(rT, base + o.a[r]);
+        col[4 + r] = kp_bld(rT, base + o.b[r]);
     }
 }
 
 // (value, slope) pairs of the slope store kps [entry][3][n][2] (k_kp_slopes): ONE 16-byte load per element gives a segment's start
 // value and its slope to the next key-point.  Offsets are those of kpc doubled.
-typedef unsigned int u32x4f __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ void fbld2(__amdgpu_buffer_rsrc_t r, int byte_off, double &v, double &a)
-{
-    const u32x4f x = __builtin_amdgcn_raw_buffer_load_b128(r, byte_off, 0, 0);
-    v = __builtin_bit_cast(double, u32x2f{x.x, x.y});
-    a = __builtin_bit_cast(double, u32x2f{x.z, x.w});
-}
 __device__ __forceinline__ int dbl_off(int o) { return o == BIGOFF ? BIGOFF : 2 * o; }
 __device__ __forceinline__ void load_col2(__amdgpu_buffer_rsrc_t rS, const ColOffs &o, int tk, int T, int strideB2, double *col, double *slp)
 {
     const int base = ((unsigned)tk < (unsigned)T) ? tk * strideB2 : BIGOFF;
 #pragma unroll
     for (int r = 0; r < 4; r++) {
-        fbld2(rS, base + dbl_off(o.a[r]), col[r], slp[r]);
-        fbld2(rS, base + dbl_off(o.b[r]), col[4 + r], slp[4 + r]);
+        kp_bld2(rS, base + dbl_off(o.a[r]), col[r], slp[r]);
+        kp_bld2(rS, base + dbl_off(o.b[r]), col[4 + r], slp[4 + r]);
     }
 }
 
@@ -227,8 +178,8 @@ __device__ __forceinline__ void load_col_n(__amdgpu_buffer_rsrc_t rT, const ColO
     const int va = base + o.a, vb = base + o.b;
 #pragma unroll
     for (int r = 0; r < 4; r++) {
-        col[r] = r < NF ? fbld(rT, va + 32 * r) : (r == NF && (N & 3)) ? fbld(rT, base + o.al) : 0.0;
-        col[4 + r] = r < NF ? fbld(rT, vb + 32 * r) : (r == NF && (N & 3)) ? fbld(rT, base + o.bl) : 0.0;
+        col[r] = r < NF ? kp_bld(rT, va + 32 * r) : (r == NF && (N & 3)) ? kp_bld(rT, base + o.al) : 0.0;
+        col[4 + r] = r < NF ? kp_bld(rT, vb + 32 * r) : (r == NF && (N & 3)) ? kp_bld(rT, base + o.bl) : 0.0;
     }
 }
 // (value, slope) pairs from the slope store, column layout (o2: col_offsets_n's offsets doubled)
@@ -239,8 +190,8 @@ __device__ __forceinline__ void load_col2_n(__amdgpu_buffer_rsrc_t rS, const Col
     const int va = base2 + o2.a, vb = base2 + o2.b;
 #pragma unroll
     for (int r = 0; r < 4; r++) {
-        if (r < NF) { fbld2(rS, va + 64 * r, col[r], slp[r]); fbld2(rS, vb + 64 * r, col[4 + r], slp[4 + r]); }
-        else if (r == NF && (N & 3)) { fbld2(rS, base2 + o2.al, col[r], slp[r]); fbld2(rS, base2 + o2.bl, col[4 + r], slp[4 + r]); }
+        if (r < NF) { kp_bld2(rS, va + 64 * r, col[r], slp[r]); kp_bld2(rS, vb + 64 * r, col[4 + r], slp[4 + r]); }
+        else if (r == NF && (N & 3)) { kp_bld2(rS, base2 + o2.al, col[r], slp[r]); kp_bld2(rS, base2 + o2.bl, col[4 + r], slp[4 + r]); }
         else { col[r] = 0.0; slp[r] = 0.0; col[4 + r] = 0.0; slp[4 + r] = 0.0; }
     }
 }
@@ -252,11 +203,11 @@ __device__ __forceinline__ void store_col_n(__amdgpu_buffer_rsrc_t rT, const Col
 #pragma unroll
     for (int r = 0; r < 4; r++) {
         if (r < NF) {
-            __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2f, col[r]), rT, va + 32 * r, 0, 0);
-            __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2f, col[4 + r]), rT, vb + 32 * r, 0, 0);
+            kp_bst(col[r], rT, va + 32 * r);
+            kp_bst(col[4 + r], rT, vb + 32 * r);
         } else if (r == NF && (N & 3)) {
-            __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2f, col[r]), rT, base + o.al, 0, 0);
-            __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2f, col[4 + r]), rT, base + o.bl, 0, 0);
+            kp_bst(col[r], rT, base + o.al);
+            kp_bst(col[4 + r], rT, base + o.bl);
         }
     }
 }
@@ -274,17 +225,8 @@ __device__ __forceinline__ KArgF kernarg_fused()
     return (KArgF)(ka + 40);
 }
 
-// LDS map of the backward kernel (doubles) -- as riccati_mfma.hip
-#define FMS 16
-#define FMZ 17
-#define FVS 17
-#define FLDS_Q 0
-#define FLDS_Z (FLDS_Q + 16 * FMS)
-#define FLDS_V (FLDS_Z + 16 * FMZ)
-#define FLDS_SLOW (FLDS_V + 16 * FVS)
-#define FLDS_TOTAL (FLDS_SLOW + 2 * 256 + 16 + 16)
-
-template <int R> __device__ __forceinline__ void fset_reg(d4 &v, double x) { if (R == 0) v.x = x; else if (R == 1) v.y = x; else if (R == 2) v.z = x; else v.w = x; }
+// LDS of the backward kernel (doubles): the one-tile map of mfma_common.h
+#define FLDS_TOTAL (KP_LDS_SLOW + 2 * 256 + 16 + 16)
 
 // PC = false: one wavefront per trajectory does everything.  PC = true: this is the CONSUMER wave of the consumer / helper pair;
 // the step's tiles Fu, [l_uu | l_u] (and Lzz of the terminal step) come from the LDS ring filled by the helper wave
@@ -294,8 +236,6 @@ template <int R> __device__ __forceinline__ void fset_reg(d4 &v, double x) { if 
 // behind the two ring slots (offsets from the ring base): the helper wave's Quz and Qzz
 #define FPC_SIDE_QUZ (2 * FPC_BUF)
 #define FPC_SIDE_QZZ (FPC_SIDE_QUZ + 256)
-__device__ __forceinline__ d4 lds_tile4(const double *t, int lane);
-__device__ __forceinline__ void lds_store4(double *t, int lane, const d4 &v);
 // Quu + lambda I is not PD on an unchecked step: the pivoted inverse (one lane, kp_slow_ldlt_inverse) times Quz, as gains with their
 // sign -- the tail of the inlined factorisation block of backward_fused_body, for the form whose factorisation is out of line.
 template <int M>
@@ -303,16 +243,16 @@ __device__ __forceinline__ d4 kp_pivoted_gains(double *sh, int m_rt, int lane)
 {
     constexpr int m = M;
     const int c = lane & 15, q = lane >> 4;
-    double *wa = sh + FLDS_SLOW, *wx = wa + 256, *wt = wx + 256;
+    double *wa = sh + KP_LDS_SLOW, *wx = wa + 256, *wt = wx + 256;
     int *tr = (int *)(wt + 16);
-    if (lane == 0) kp_slow_ldlt_inverse(m_rt, sh + FLDS_Q, FMS, wa, wx, wt, tr);
+    if (lane == 0) kp_slow_ldlt_inverse(m_rt, sh + KP_LDS_Q, KP_MS, wa, wx, wt, tr);
     __builtin_amdgcn_wave_barrier();
     double x[M];
 #pragma unroll
     for (int i = 0; i < M; i++) {
         double sacc = 0.0;
 #pragma unroll
-        for (int p = 0; p < M; p++) sacc += (-wx[i + p * m]) * sh[FLDS_Z + c * FMZ + p];
+        for (int p = 0; p < M; p++) sacc += (-wx[i + p * m]) * sh[KP_LDS_Z + c * KP_MZ + p];
         x[i] = -sacc;
     }
     __builtin_amdgcn_wave_barrier();
@@ -329,7 +269,7 @@ __device__ __forceinline__ d4 kp_pivoted_gains(double *sh, int m_rt, int lane)
 // bench's pd_stride), OUT OF LINE: inlined, its ~100 live registers (Lm[M][M], rd, x, y) met the refreshed path at the join in front of
 // the gains product, and the allocator parked Quz / Qr of EVERY refreshed step in AGPRs to make room for a branch that step does not
 // take.  noinline like kp_slow_ldlt_inverse: what the rare path needs is saved and restored around the call, on the rare path.
-// In: the LDS image of the step, Qr = Quu + lambda I at FLDS_Q and Quz' at FLDS_Z (written by the caller, wave barrier behind it).
+// In: the LDS image of the step, Qr = Quu + lambda I at KP_LDS_Q and Quz' at KP_LDS_Z (written by the caller, wave barrier behind it).
 // Out, in registers (2 NCU doubles and a word: a by-value aggregate of up to 16 registers comes back in VGPRs, a larger one through
 // scratch): the lane's rows of the gains column with its sign, of the NEGATED inverse column, and the verdict.  A LEAF: the pivoted
 // slow path stays with the caller (a call in here would have the return address saved in scratch).  The statements are the inlined
@@ -347,12 +287,12 @@ __device__ static __attribute__((noinline)) FactorOut<(M + 3) / 4> kp_factor_pat
     for (int r = 0; r < NCU; r++) { o.Kp[r] = 0.0; o.Xinv[r] = 0.0; }
     // ---- unpivoted LDL' of Quu + lambda I, redundantly in every lane ----
     double Lm[M][M], rd[M];
-    const bool pos = kp_ldl_factor<M>([&](int i, int j) { return sh[FLDS_Q + i * FMS + j]; }, Lm, rd);
+    const bool pos = kp_ldl_factor<M>([&](int i, int j) { return sh[KP_LDS_Q + i * KP_MS + j]; }, Lm, rd);
     o.verdict = pos ? KP_FACTOR_SEEDED : check_pd ? KP_FACTOR_NOT_PD : KP_FACTOR_INDEFINITE;
     if (!pos) return o;
     double x[M];
 #pragma unroll
-    for (int i = 0; i < M; i++) x[i] = sh[FLDS_Z + c * FMZ + i];
+    for (int i = 0; i < M; i++) x[i] = sh[KP_LDS_Z + c * KP_MZ + i];
     kp_ldl_solve<M>(Lm, rd, x);
     // seed the fast path: column c of the inverse in lane c (c < m), as a tile
     double y[M];
@@ -439,12 +379,12 @@ __device__ __forceinline__ void backward_fused_body(double *sh, const double *pc
     // -- registers (0, 1) and (2, 3) of a lane are consecutive residuals, so r_t arrives with two 16-byte requests instead of four
     // 8-byte ones (see RV2 in forward_fused_body).  The rows are the contraction index of every product they enter (Cxx, r_x' W r, the
     // terminal step's Rz' W Rz): a relabelling, with the weights relabelled alike.
-    const int oR12[2] = {(2 * q < nr) ? 16 * q : OOBF, (8 + 2 * q < nr) ? 64 + 16 * q : OOBF};
+    const int oR12[2] = {(2 * q < nr) ? 16 * q : KP_OOB, (8 + 2 * q < nr) ? 64 + 16 * q : KP_OOB};
     (void)oR12;
 #pragma unroll
     for (int r = 0; r < 4; r++) {
         const int kr = RV2B ? 8 * (r >> 1) + 2 * q + (r & 1) : 4 * r + q;     // the residual in row 4r + q
-        oRx[r] = (kr < nr && c < n) ? 8 * (kr * n + c) : OOBF;        // Rz(k, c) = r_x[k][c]
+        oRx[r] = (kr < nr && c < n) ? 8 * (kr * n + c) : KP_OOB;        // Rz(k, c) = r_x[k][c]
         w2run[r] = (kr < nr) ? 2.0 * F.w_run[kr] : 0.0;
         w2term[r] = (kr < nr) ? 2.0 * F.w_term[kr] : 0.0;
     }
@@ -452,10 +392,10 @@ __device__ __forceinline__ void backward_fused_body(double *sh, const double *pc
     for (int r = 0; r < 4; r++) {
         const int row = 4 * r + q;
         // (RXC one-wave sweeps: r[k] in EVERY column -- the lanes of column c form their part of (r_x' W r)(c) from it, see CXX below)
-        oR1[r] = (row < nr && (c == n || (RXC && !PC))) ? 8 * row : OOBF;               //            ... | r[k] in column n
-        oRu[r] = (row < nr && c < m) ? 8 * (row * m + c) : OOBF;      // Ru(k=row, c) = r_u[k][c]
-        oKst[r] = (row < m && c < n) ? 8 * (row + c * m) : OOBF;
-        okst[r] = (row < m && c == n) ? 8 * row : OOBF;
+        oR1[r] = (row < nr && (c == n || (RXC && !PC))) ? 8 * row : KP_OOB;               //            ... | r[k] in column n
+        oRu[r] = (row < nr && c < m) ? 8 * (row * m + c) : KP_OOB;      // Ru(k=row, c) = r_u[k][c]
+        oKst[r] = (row < m && c < n) ? 8 * (row + c * m) : KP_OOB;
+        okst[r] = (row < m && c == n) ? 8 * row : KP_OOB;
         lam2d[r] = (row == c && row < m) ? 2.0 * lam : 0.0;
     }
     const d4 LamI = {0.5 * lam2d[0], 0.5 * lam2d[1], 0.5 * lam2d[2], 0.5 * lam2d[3]};     // lambda on the diagonal of the u-block
@@ -465,7 +405,7 @@ __device__ __forceinline__ void backward_fused_body(double *sh, const double *pc
 
     // this trajectory's key-point entries [E0, E0 + NE): one descriptor over its slice of kpc (and of the raw payload)
     const int E0 = F.kp_offsets[(size_t)bP * F.dof], NE = F.kp_offsets[(size_t)(bP + 1) * F.dof] - E0;
-    __amdgpu_buffer_rsrc_t rT = frsrc(F.kpc + (size_t)E0 * 3 * n, NE * strideB);
+    __amdgpu_buffer_rsrc_t rT = kp_rsrc(F.kpc + (size_t)E0 * 3 * n, NE * strideB);
     const double *rb = F.r + (size_t)bR * (T + 1) * nr;
     const double *rxb = F.r_x + (size_t)bR * (T + 1) * nr * n;
     const double *rub = F.r_u + (size_t)bR * (T + 1) * nr * m;
@@ -476,25 +416,25 @@ __device__ __forceinline__ void backward_fused_body(double *sh, const double *pc
     // instructions per step, 4.84 -> 4.77 ms).  `t` only says whether there IS a step t (the general form asks once more at the bottom).
     const double *pRx = rxb + (size_t)(T - 1) * nr * n, *pR = rb + (size_t)(T - 1) * nr, *pRu = rub + (size_t)(T - 1) * nr * m;
     auto load_res = [&](int t, ResTiles &s) {
-        __amdgpu_buffer_rsrc_t rR = frsrc(pR, nr * 8);
-        __amdgpu_buffer_rsrc_t rR2 = frsrc(pR, nr * 8 + 8);
+        __amdgpu_buffer_rsrc_t rR = kp_rsrc(pR, nr * 8);
+        __amdgpu_buffer_rsrc_t rR2 = kp_rsrc(pR, nr * 8 + 8);
         (void)rR2;
-        __amdgpu_buffer_rsrc_t rRu = frsrc(pRu, nr * m * 8);
+        __amdgpu_buffer_rsrc_t rRu = kp_rsrc(pRu, nr * m * 8);
         if constexpr (!RXC) {
-            __amdgpu_buffer_rsrc_t rRx = frsrc(pRx, nr * n * 8);
-            s.Rx.x = fbld(rRx, oRx[0]); s.Rx.y = fbld(rRx, oRx[1]); s.Rx.z = fbld(rRx, oRx[2]); s.Rx.w = fbld(rRx, oRx[3]);
+            __amdgpu_buffer_rsrc_t rRx = kp_rsrc(pRx, nr * n * 8);
+            s.Rx.x = kp_bld(rRx, oRx[0]); s.Rx.y = kp_bld(rRx, oRx[1]); s.Rx.z = kp_bld(rRx, oRx[2]); s.Rx.w = kp_bld(rRx, oRx[3]);
             if (t > 0) pRx -= nr * n;
         }
         if (t > 0) { pR -= nr; pRu -= nr * m; }       // (behind step 0: stay on it)
         if constexpr (RV2B) {
             // (descriptor one element longer: the last pair of an odd residual count reaches into the next row -- the array has T + 1)
             double r0, r1, r2, r3;
-            fbld2s(rR2, oR12[0], 0, r0, r1); fbld2s(rR2, oR12[1], 0, r2, r3);
+            kp_bld2s(rR2, oR12[0], 0, r0, r1); kp_bld2s(rR2, oR12[1], 0, r2, r3);
             s.R1.x = r0; s.R1.y = r1; s.R1.z = r2; s.R1.w = r3;
         } else {
-        s.R1.x = fbld(rR, oR1[0]); s.R1.y = fbld(rR, oR1[1]); s.R1.z = fbld(rR, oR1[2]); s.R1.w = fbld(rR, oR1[3]);
+        s.R1.x = kp_bld(rR, oR1[0]); s.R1.y = kp_bld(rR, oR1[1]); s.R1.z = kp_bld(rR, oR1[2]); s.R1.w = kp_bld(rR, oR1[3]);
         }
-        if constexpr (!RU0) { s.Ru.x = fbld(rRu, oRu[0]); s.Ru.y = fbld(rRu, oRu[1]); s.Ru.z = fbld(rRu, oRu[2]); s.Ru.w = fbld(rRu, oRu[3]); }
+        if constexpr (!RU0) { s.Ru.x = kp_bld(rRu, oRu[0]); s.Ru.y = kp_bld(rRu, oRu[1]); s.Ru.z = kp_bld(rRu, oRu[2]); s.Ru.w = kp_bld(rRu, oRu[3]); }
     };
 
     // ---- column tracker, walking DOWN in time ----------------------------------------------------------
@@ -522,7 +462,7 @@ __device__ __forceinline__ void backward_fused_body(double *sh, const double *pc
     co2.a = dbl_off(co.a); co2.al = dbl_off(co.al); co2.b = dbl_off(co.b); co2.bl = dbl_off(co.bl);
     auto ebase2 = [&](int e_rel) { return ((unsigned)e_rel < (unsigned)NE) ? e_rel * (2 * strideB) : BIGOFF; };
     (void)co2;
-    if constexpr (SLP) rP = frsrc(F.kps + (size_t)E0 * 6 * n, NE * 2 * strideB);
+    if constexpr (SLP) rP = kp_rsrc(F.kps + (size_t)E0 * 6 * n, NE * 2 * strideB);
     const int bitA = (c < F.dof) ? 1 : 2;                         // mode bit of this lane's A column (position / velocity job)
     auto ebase = [&](int e_rel) { return ((unsigned)e_rel < (unsigned)NE) ? e_rel * strideB : BIGOFF; };
     auto load_raw = [&](int e_rel, double *xp_, double *xm_, int &mo) {
@@ -570,11 +510,11 @@ __device__ __forceinline__ void backward_fused_body(double *sh, const double *pc
     const double en2 = (c == n) ? 2.0 : 0.0, en1 = (c == n) ? 1.0 : 0.0;
     (void)Cxx; (void)RxW; (void)en2; (void)en1;
     if constexpr (RXC) {                           // the one r_x of the task: in registers for the whole sweep
-        __amdgpu_buffer_rsrc_t rRx = frsrc(F.rx_const, nr * n * 8);
-        cur.Rx.x = fbld(rRx, oRx[0]); cur.Rx.y = fbld(rRx, oRx[1]); cur.Rx.z = fbld(rRx, oRx[2]); cur.Rx.w = fbld(rRx, oRx[3]);
+        __amdgpu_buffer_rsrc_t rRx = kp_rsrc(F.rx_const, nr * n * 8);
+        cur.Rx.x = kp_bld(rRx, oRx[0]); cur.Rx.y = kp_bld(rRx, oRx[1]); cur.Rx.z = kp_bld(rRx, oRx[2]); cur.Rx.w = kp_bld(rRx, oRx[3]);
         if constexpr (CXX) {
             RxW.x = cur.Rx.x * w2run[0]; RxW.y = cur.Rx.y * w2run[1]; RxW.z = cur.Rx.z * w2run[2]; RxW.w = cur.Rx.w * w2run[3];
-            Cxx = PR(cur.Rx, RxW, Cxx, ncr);
+            Cxx = kp_Pn(cur.Rx, RxW, Cxx, ncr);
         }
     }
     // UNI: lane offsets of the lane's own DoF list (kd * KpU entries into the slice), the position in the soffset operand
@@ -628,7 +568,7 @@ __device__ __forceinline__ void backward_fused_body(double *sh, const double *pc
     if constexpr (!PC && UNI) {
         // both columns of the first crossing are the last key-point's (slope 0 over the virtual segment [T-1, T])
         if constexpr (RAW) {
-            rP = frsrc(F.fdk + (size_t)E0 * strideR, NE * strideR);
+            rP = kp_rsrc(F.fdk + (size_t)E0 * strideR, NE * strideR);
             load_col2_n<N>(rP, cr, up * strideR, pv, pm);
             pmode = __builtin_amdgcn_raw_buffer_load_b32(rP, up * strideR + kd * KpU * strideR + ((c < n) ? offMode : BIGOFF), 0, 0);
 #pragma unroll
@@ -644,7 +584,7 @@ __device__ __forceinline__ void backward_fused_body(double *sh, const double *pc
     } else if constexpr (!PC) {
         const int e_s = has ? idx - E0 : -1, e_nb = (has && idx - 1 >= lo) ? idx - 1 - E0 : -1;
         if constexpr (RAW) {
-            rP = frsrc(F.fdk + (size_t)E0 * strideR, NE * strideR);
+            rP = kp_rsrc(F.fdk + (size_t)E0 * strideR, NE * strideR);
             int mo0;
             load_raw(e_s, sv, pm, mo0);
             difference(sv, pm, mo0, e_s);
@@ -693,14 +633,14 @@ __device__ __forceinline__ void backward_fused_body(double *sh, const double *pc
     double *pK = Kout + ((size_t)bS * T + T - 1) * m * n, *pk = kout + ((size_t)bS * T + T - 1) * m;
     auto store_gains = [&](int t, const d4 &Kp) {
         (void)t;                                       // the steps are stored in order, T-1 first
-        __amdgpu_buffer_rsrc_t rK = frsrc(pK, m * n * 8);
-        __amdgpu_buffer_rsrc_t rk = frsrc(pk, m * 8);
+        __amdgpu_buffer_rsrc_t rK = kp_rsrc(pK, m * n * 8);
+        __amdgpu_buffer_rsrc_t rk = kp_rsrc(pk, m * 8);
         pK -= m * n; pk -= m;
         const double kv[4] = {Kp.x, Kp.y, Kp.z, Kp.w};
 #pragma unroll
         for (int r = 0; r < NCU; r++) {
-            __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2f, kv[r]), rK, oKst[r], 0, 0);
-            __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2f, kv[r]), rk, okst[r], 0, 0);
+            kp_bst(kv[r], rK, oKst[r]);
+            kp_bst(kv[r], rk, okst[r]);
         }
     };
     // one step of the sweep; false: the PD check of this step failed (the sweep ends)
@@ -724,19 +664,19 @@ __device__ __forceinline__ void backward_fused_body(double *sh, const double *pc
         (void)cross;
         if constexpr (PC) {
             const double *tb = pcbuf + (t & 1) * FPC_BUF;
-            Fu = lds_tile4(tb + 256, lane);
-            if constexpr (RU0) LU = zero; else LU = lds_tile4(tb + 768, lane);
+            Fu = kp_lds_tile(tb + 256, lane);
+            if constexpr (RU0) LU = zero; else LU = kp_lds_tile(tb + 768, lane);
             // Fz, Lzz are the helper wave's operands; only V = Lzz of the last step is ours
             Fz = zero; Lzz = zero;
-            if (term) Lzz = lds_tile4(tb + 512, lane);
+            if (term) Lzz = kp_lds_tile(tb + 512, lane);
             else {
                 // (V' + V'')/2 of the step before: its transposed half is read here, behind the barrier that ended that
                 // step, together with this step's tiles -- no write / wait / read round trip at the end of a step
-                V.x = 0.5 * (accp.x + sh[FLDS_V + c * FVS + q]);
-                V.y = 0.5 * (accp.y + sh[FLDS_V + c * FVS + 4 + q]);
-                V.z = 0.5 * (accp.z + sh[FLDS_V + c * FVS + 8 + q]);
-                V.w = 0.5 * (accp.w + sh[FLDS_V + c * FVS + 12 + q]);
-                if (lane_nn) fset_reg<REG_NN>(V, 0.0);
+                V.x = 0.5 * (accp.x + sh[KP_LDS_V + c * KP_VS + q]);
+                V.y = 0.5 * (accp.y + sh[KP_LDS_V + c * KP_VS + 4 + q]);
+                V.z = 0.5 * (accp.z + sh[KP_LDS_V + c * KP_VS + 8 + q]);
+                V.w = 0.5 * (accp.w + sh[KP_LDS_V + c * KP_VS + 12 + q]);
+                if (lane_nn) kp_set_reg<REG_NN>(V, 0.0);
             }
         } else {
         // ---- a4: this step's A and B columns --------------------------------------------------------------
@@ -787,7 +727,7 @@ __device__ __forceinline__ void backward_fused_body(double *sh, const double *pc
                 d4 Rz;
                 Rz.x = bits_or(cur.Rx.x, bits_and(cur.R1.x, mask_n)); Rz.y = bits_or(cur.Rx.y, bits_and(cur.R1.y, mask_n));
                 Rz.z = bits_or(cur.Rx.z, bits_and(cur.R1.z, mask_n)); Rz.w = bits_or(cur.Rx.w, bits_and(cur.R1.w, mask_n));
-                Lzz = PR(Rz, Rz * W2, zero, ncr);
+                Lzz = kp_Pn(Rz, Rz * W2, zero, ncr);
             } else {
                 double p = RxW.x * cur.R1.x;
                 p = __builtin_fma(RxW.y, cur.R1.y, p); p = __builtin_fma(RxW.z, cur.R1.z, p); p = __builtin_fma(RxW.w, cur.R1.w, p);
@@ -797,15 +737,15 @@ __device__ __forceinline__ void backward_fused_body(double *sh, const double *pc
                     // (L/2)(n, i) = 0, and their sum is l_x.  Still one product, up here off the Riccati chain.  (Tried: the product behind
                     // the merge, C = the merged tile, so that only the lane sums live across the top of the step -- it lost:
                     // it sits in the chain in front of the refresh, profiles/inner_step_moves_ab.txt.)
-                    Lzz = MFMA(p, en1, Cxxh);
+                    Lzz = KP_MFMA(p, en1, Cxxh);
                 }
-                else Lzz = MFMA(en2, p, Cxx);
+                else Lzz = KP_MFMA(en2, p, Cxx);
             }
         } else {
         d4 Rz;
         Rz.x = bits_or(cur.Rx.x, cur.R1.x); Rz.y = bits_or(cur.Rx.y, cur.R1.y);
         Rz.z = bits_or(cur.Rx.z, cur.R1.z); Rz.w = bits_or(cur.Rx.w, cur.R1.w);
-        Lzz = PR(Rz, Rz * W2, zero, ncr);
+        Lzz = kp_Pn(Rz, Rz * W2, zero, ncr);
         }
         if constexpr (PACKQ) {
             // the halved cost block of the merge.  A sweep's first step wants Lzz whole as well (V = Lzz): halved there, by four
@@ -819,8 +759,8 @@ __device__ __forceinline__ void backward_fused_body(double *sh, const double *pc
             d4 Rur;
             Rur.x = bits_or(cur.Ru.x, cur.R1.x); Rur.y = bits_or(cur.Ru.y, cur.R1.y);
             Rur.z = bits_or(cur.Ru.z, cur.R1.z); Rur.w = bits_or(cur.Ru.w, cur.R1.w);
-            if (PACKQ && !term) LU = PR(cur.Ru, Rur * (W2 + W2), zero, ncr);      // ([l_uu | l_u] under the whole running weights)
-            else LU = PR(cur.Ru, Rur * W2, zero, ncr);
+            if (PACKQ && !term) LU = kp_Pn(cur.Ru, Rur * (W2 + W2), zero, ncr);      // ([l_uu | l_u] under the whole running weights)
+            else LU = kp_Pn(cur.Ru, Rur * W2, zero, ncr);
         }
         __builtin_amdgcn_sched_barrier(0);
         // the step above, IN FRONT of the requests.  (The test is false only at the first step; compiling it out of the loops'
@@ -834,16 +774,16 @@ __device__ __forceinline__ void backward_fused_body(double *sh, const double *pc
         if constexpr (!UNI) {
             if (cross) {                               // late_cross: the memory operations of the crossing at the top of this step
                 const KArgF Fk = kernarg_fused();      // crossing-only scalars, from the kernel-argument segment
-                rT = frsrc(Fk->kpc + (size_t)E0 * 3 * n, NE * strideB);
+                rT = kp_rsrc(Fk->kpc + (size_t)E0 * 3 * n, NE * strideB);
                 if constexpr (RAW) {
-                    rP = frsrc(Fk->fdk + (size_t)E0 * strideR, NE * strideR);
+                    rP = kp_rsrc(Fk->fdk + (size_t)E0 * strideR, NE * strideR);
                     store_col_n<N>(rT, co, ebase(idx - E0), sv);          // the column that has just become the start value
                 }
                 nb = (idx - 1 >= lo) ? Fk->kp_times[idx - 1] : -1;
                 const int e_nb = (idx - 1 >= lo) ? idx - 1 - E0 : -1;
                 if constexpr (RAW) load_raw(e_nb, pv, pm, pmode);
                 else {
-                    rP = frsrc(Fk->kps + (size_t)E0 * 6 * n, NE * 2 * strideB);
+                    rP = kp_rsrc(Fk->kps + (size_t)E0 * 6 * n, NE * 2 * strideB);
                     load_col2_n<N>(rP, co2, ebase2(e_nb), pv, pm);             // start column AND slope of the next segment: one load each
                 }
             }
@@ -887,31 +827,31 @@ __device__ __forceinline__ void backward_fused_body(double *sh, const double *pc
             // The split row 8 is a register pair: (.x, .y) <-> (.z, .w) is a renaming.  The accumulators start from the cost terms of
             // the blocks that are read.  Qr = D2 goes to the refresh as it is: column 7 of Pk is zero, columns 8.. of Qr only make
             // rows >= 8 of the residual, which NCU = 2 never reads, and the LDL' path reads elements (i, j) < m.
-            const d4 T2 = PS<NCZ>(V, Fu, zero);          // (first: the per-lane pick of Fz lands under it)
-            const d4 Tz = PS<NCZ>(V, Fz, zero);
+            const d4 T2 = kp_P<NCZ>(V, Fu, zero);          // (first: the per-lane pick of Fz lands under it)
+            const d4 Tz = kp_P<NCZ>(V, Fz, zero);
             // Lzz enters nothing but V' (Luz, Luu are rows < m of the u-block): it joins at the merge, and the accumulators start from
             // what the gains need -- without control residuals the resident lambda I (its rows 8.. are zero: m <= 8) and literal zero:
             // no register is moved to assemble a C operand
             d4 i2 = LamI, i1 = zero;
             if constexpr (!RU0) { i2.x = Luu.x + LamI.x; i2.y = Luu.y + LamI.y; i1.z = Luz.x; i1.w = Luz.y; }
-            const d4 D2 = PS<NCZ>(Fu, T2, i2);
-            const d4 D1 = PS<NCZ>(Y1, Tz, i1);
+            const d4 D2 = kp_P<NCZ>(Fu, T2, i2);
+            const d4 D1 = kp_P<NCZ>(Y1, Tz, i1);
             Qr = D2;
             Quz.x = D1.z; Quz.y = D1.w; Quz.z = 0.0; Quz.w = 0.0;
             // the merge (f_lo, f_hi above): four FMAs on constants, Qm / 2
             Qzz.x = __builtin_fma(D1.x, f_lo, Lh.x); Qzz.y = __builtin_fma(D1.y, f_lo, Lh.y);
             Qzz.z = __builtin_fma(D2.z, f_hi, Lh.z); Qzz.w = __builtin_fma(D2.w, f_hi, Lh.w);
         } else {
-        const d4 Tu = PS<NCZ>(V, Fu, zero);
-        Qr = PS<NCZ>(Fu, Tu, PC ? Luu : Luu + LamI);          // Quu (+ lambda I)
+        const d4 Tu = kp_P<NCZ>(V, Fu, zero);
+        Qr = kp_P<NCZ>(Fu, Tu, PC ? Luu : Luu + LamI);          // Quu (+ lambda I)
         if constexpr (PC) { Qr.x += LamI.x; Qr.y += LamI.y; Qr.z += LamI.z; Qr.w += LamI.w; }
         // ---- Tz, Quz, Qzz --------------------------------------------------------------- :570-579
         if constexpr (PC) {
             Quz = zero; Qzz = zero;                   // the helper wave forms them meanwhile: read behind the refresh
         } else {
-            d4 Tz = PS<NCZ>(V, Fz, zero);
-            Quz = PS<NCZ>(Fu, Tz, Luz);
-            Qzz = PS<NCZ>(Fz, Tz, Lzz);
+            d4 Tz = kp_P<NCZ>(V, Fz, zero);
+            Quz = kp_P<NCZ>(Fu, Tz, Luz);
+            Qzz = kp_P<NCZ>(Fz, Tz, Lzz);
         }
         }
 #ifdef KP_CYC
@@ -937,7 +877,7 @@ __device__ __forceinline__ void backward_fused_body(double *sh, const double *pc
         if constexpr (STATS) { if (refreshed) hcnt[ns_steps < 0 ? 0 : ns_steps > 3 ? 3 : ns_steps]++; }
         if constexpr (PC) {                           // mid-step barrier of the pair: Quz, Qzz are published
             __syncthreads();
-            Quz = lds_tile4(pcbuf + FPC_SIDE_QUZ, lane); Qzz = lds_tile4(pcbuf + FPC_SIDE_QZZ, lane);
+            Quz = kp_lds_tile(pcbuf + FPC_SIDE_QUZ, lane); Qzz = kp_lds_tile(pcbuf + FPC_SIDE_QZZ, lane);
         }
 #ifdef KP_CYC
         asm volatile("" :: "v"(Xinv.x));
@@ -948,18 +888,18 @@ __device__ __forceinline__ void backward_fused_body(double *sh, const double *pc
         if (refreshed) {
             d4 Xa = Xinv;
             if constexpr (HEADS) { Xa = zero; Xa.x = Xh[0]; if constexpr (NCU > 1) Xa.y = Xh[1]; }     // (the product reads the NCU heads)
-            Kp = PS<NCU>(Xa, Quz, zero);                 // -(Quu + lambda I)^-1 Quz: the gains, with their sign
+            Kp = kp_P<NCU>(Xa, Quz, zero);                 // -(Quu + lambda I)^-1 Quz: the gains, with their sign
             done = true;
         }
         if (!done) {
-            sh[FLDS_Q + q * FMS + c] = Qr.x;
-            if (NCU > 1) sh[FLDS_Q + (4 + q) * FMS + c] = Qr.y;
-            if (NCU > 2) sh[FLDS_Q + (8 + q) * FMS + c] = Qr.z;
-            if (NCU > 3) sh[FLDS_Q + (12 + q) * FMS + c] = Qr.w;
-            sh[FLDS_Z + c * FMZ + q] = Quz.x;
-            if (NCU > 1) sh[FLDS_Z + c * FMZ + 4 + q] = Quz.y;
-            if (NCU > 2) sh[FLDS_Z + c * FMZ + 8 + q] = Quz.z;
-            if (NCU > 3) sh[FLDS_Z + c * FMZ + 12 + q] = Quz.w;
+            sh[KP_LDS_Q + q * KP_MS + c] = Qr.x;
+            if (NCU > 1) sh[KP_LDS_Q + (4 + q) * KP_MS + c] = Qr.y;
+            if (NCU > 2) sh[KP_LDS_Q + (8 + q) * KP_MS + c] = Qr.z;
+            if (NCU > 3) sh[KP_LDS_Q + (12 + q) * KP_MS + c] = Qr.w;
+            sh[KP_LDS_Z + c * KP_MZ + q] = Quz.x;
+            if (NCU > 1) sh[KP_LDS_Z + c * KP_MZ + 4 + q] = Quz.y;
+            if (NCU > 2) sh[KP_LDS_Z + c * KP_MZ + 8 + q] = Quz.z;
+            if (NCU > 3) sh[KP_LDS_Z + c * KP_MZ + 12 + q] = Quz.w;
             wsync();
             if constexpr (UNI && !PC) {                // out of line: the refreshed path keeps its registers (kp_factor_path)
                 const FactorOut<NCU> fo = kp_factor_path<M>(sh, lane, check_pd);
@@ -988,7 +928,7 @@ __device__ __forceinline__ void backward_fused_body(double *sh, const double *pc
             } else {
             // ---- unpivoted LDL' of Quu + lambda I, redundantly in every lane ----
             double Lm[M][M], rd[M];
-            const bool pos = kp_ldl_factor<M>([&](int i, int j) { return sh[FLDS_Q + i * FMS + j]; }, Lm, rd);
+            const bool pos = kp_ldl_factor<M>([&](int i, int j) { return sh[KP_LDS_Q + i * KP_MS + j]; }, Lm, rd);
             if (check_pd) {                       // CheckMatrixPD every pd_stride steps   :587-595
                 if (!pos) {
                     fail = t + 1;
@@ -1000,7 +940,7 @@ __device__ __forceinline__ void backward_fused_body(double *sh, const double *pc
             double x[M];
             if (pos) {
 #pragma unroll
-                for (int i = 0; i < M; i++) x[i] = sh[FLDS_Z + c * FMZ + i];
+                for (int i = 0; i < M; i++) x[i] = sh[KP_LDS_Z + c * KP_MZ + i];
                 kp_ldl_solve<M>(Lm, rd, x);
                 // seed the fast path: column c of the inverse in lane c (c < m), as a tile
                 double y[M];
@@ -1017,15 +957,15 @@ __device__ __forceinline__ void backward_fused_body(double *sh, const double *pc
                 if constexpr (STATS) hcnt[4]++;
             } else {
                 if constexpr (STATS) hcnt[5]++;
-                double *wa = sh + FLDS_SLOW, *wx = wa + 256, *wt = wx + 256;
+                double *wa = sh + KP_LDS_SLOW, *wx = wa + 256, *wt = wx + 256;
                 int *tr = (int *)(wt + 16);
-                if (lane == 0) kp_slow_ldlt_inverse(L.m, sh + FLDS_Q, FMS, wa, wx, wt, tr);
+                if (lane == 0) kp_slow_ldlt_inverse(L.m, sh + KP_LDS_Q, KP_MS, wa, wx, wt, tr);
                 wsync();
 #pragma unroll
                 for (int i = 0; i < M; i++) {
                     double sacc = 0.0;
 #pragma unroll
-                    for (int p = 0; p < M; p++) sacc += (-wx[i + p * m]) * sh[FLDS_Z + c * FMZ + p];
+                    for (int p = 0; p < M; p++) sacc += (-wx[i + p * m]) * sh[KP_LDS_Z + c * KP_MZ + p];
                     x[i] = -sacc;
                 }
                 wsync();
@@ -1061,32 +1001,32 @@ __device__ __forceinline__ void backward_fused_body(double *sh, const double *pc
         G.x = __builtin_fma(-lam, Kp.x, Quz.x); G.y = __builtin_fma(-lam, Kp.y, Quz.y);
         G.z = __builtin_fma(-lam, Kp.z, Quz.z); G.w = __builtin_fma(-lam, Kp.w, Quz.w);
         }
-        d4 acc = PS<NCU>(Kp, G, Qzz);
+        d4 acc = kp_P<NCU>(Kp, G, Qzz);
 #ifdef KP_CYC
         asm volatile("" :: "v"(acc.x));
         const unsigned long long cyc_s3 = __builtin_readcyclecounter();
         cyc_d += cyc_s3 - cyc_s2;
 #endif
-        sh[FLDS_V + (q) * FVS + c] = acc.x;
-        sh[FLDS_V + (4 + q) * FVS + c] = acc.y;
-        sh[FLDS_V + (8 + q) * FVS + c] = acc.z;
-        sh[FLDS_V + (12 + q) * FVS + c] = acc.w;
+        sh[KP_LDS_V + (q) * KP_VS + c] = acc.x;
+        sh[KP_LDS_V + (4 + q) * KP_VS + c] = acc.y;
+        sh[KP_LDS_V + (8 + q) * KP_VS + c] = acc.z;
+        sh[KP_LDS_V + (12 + q) * KP_VS + c] = acc.w;
         if constexpr (PC) {
             accp = acc;                                // symmetrised at the top of the next step, by this wave and by the helper wave
         } else {
             wsync();
             if constexpr (PACKQ) {                     // acc is V' / 2
-                V.x = acc.x + sh[FLDS_V + c * FVS + q];
-                V.y = acc.y + sh[FLDS_V + c * FVS + 4 + q];
-                V.z = acc.z + sh[FLDS_V + c * FVS + 8 + q];
-                V.w = acc.w + sh[FLDS_V + c * FVS + 12 + q];
+                V.x = acc.x + sh[KP_LDS_V + c * KP_VS + q];
+                V.y = acc.y + sh[KP_LDS_V + c * KP_VS + 4 + q];
+                V.z = acc.z + sh[KP_LDS_V + c * KP_VS + 8 + q];
+                V.w = acc.w + sh[KP_LDS_V + c * KP_VS + 12 + q];
             } else {
-            V.x = 0.5 * (acc.x + sh[FLDS_V + c * FVS + q]);
-            V.y = 0.5 * (acc.y + sh[FLDS_V + c * FVS + 4 + q]);
-            V.z = 0.5 * (acc.z + sh[FLDS_V + c * FVS + 8 + q]);
-            V.w = 0.5 * (acc.w + sh[FLDS_V + c * FVS + 12 + q]);
+            V.x = 0.5 * (acc.x + sh[KP_LDS_V + c * KP_VS + q]);
+            V.y = 0.5 * (acc.y + sh[KP_LDS_V + c * KP_VS + 4 + q]);
+            V.z = 0.5 * (acc.z + sh[KP_LDS_V + c * KP_VS + 8 + q]);
+            V.w = 0.5 * (acc.w + sh[KP_LDS_V + c * KP_VS + 12 + q]);
             }
-            if (lane_nn) fset_reg<REG_NN>(V, 0.0);
+            if (lane_nn) kp_set_reg<REG_NN>(V, 0.0);
         }
         if (PC) __syncthreads();                       // end of step: the ring slot is free, the next one is full
         else wsync();
@@ -1110,8 +1050,8 @@ __device__ __forceinline__ void backward_fused_body(double *sh, const double *pc
             const unsigned long long cyc0 = __builtin_readcyclecounter();
 #endif
             const KArgF Fk = kernarg_fused();                      // crossing-only scalars, from the kernel-argument segment
-            rT = frsrc(Fk->kpc + (size_t)E0 * 3 * n, NE * strideB);
-            if constexpr (RAW) { rP = frsrc(Fk->fdk + (size_t)E0 * strideR, NE * strideR); eps2 = Fk->eps2; rinv2 = Fk->rinv_2eps; }
+            rT = kp_rsrc(Fk->kpc + (size_t)E0 * 3 * n, NE * strideB);
+            if constexpr (RAW) { rP = kp_rsrc(Fk->fdk + (size_t)E0 * strideR, NE * strideR); eps2 = Fk->eps2; rinv2 = Fk->rinv_2eps; }
             // the time of the new segment's start was requested a crossing ago, BEHIND that crossing's column loads: memory
             // operations return in order, and the wait for the residual tiles of the peeled step ("all but the youngest
             // loads") would otherwise have to sit out this load's latency too (measured: +840 cycles on every peeled step)
@@ -1235,21 +1175,10 @@ __device__ __forceinline__ void load_vals(__amdgpu_buffer_rsrc_t rT, const int *
 {
     const int base = ((unsigned)tk < (unsigned)T) ? tk * strideB : BIGOFF;
 #pragma unroll
-    for (int r = 0; r < NV; r++) out[r] = fbld(rT, base + offs[r]);
+    for (int r = 0; r < NV; r++) out[r] = kp_bld(rT, base + offs[r]);
 }
 
-
-__device__ __forceinline__ d4 lds_tile4(const double *t, int lane)
-{
-    d4 v; v.x = t[lane]; v.y = t[64 + lane]; v.z = t[128 + lane]; v.w = t[192 + lane];
-    return v;
-}
-__device__ __forceinline__ void lds_store4(double *t, int lane, const d4 &v)
-{
-    t[lane] = v.x; t[64 + lane] = v.y; t[128 + lane] = v.z; t[192 + lane] = v.w;
-}
-
-// Column tracker walking down for NV values per lane (a4), shared by the two roles.
+// Column tracker walking down for NV values per lane (a4), shared by the two roles.  (The list walk -- lo, idx, s, nb, nb2 -- is repeated in the two trackers below on purpose: profiles/mfma_primitives_isa.txt, 3.)
 template <int NV>
 struct DownTracker {
     int offs[NV];
@@ -1317,7 +1246,7 @@ struct DownTrackerSlp {
     {
         const int base = ((unsigned)e_rel < (unsigned)NE) ? e_rel * stride2 : BIGOFF;
 #pragma unroll
-        for (int r = 0; r < NV; r++) fbld2(rS, base + dbl_off(offs[r]), v[r], a[r]);
+        for (int r = 0; r < NV; r++) kp_bld2(rS, base + dbl_off(offs[r]), v[r], a[r]);
     }
     __device__ __forceinline__ void init(__amdgpu_buffer_rsrc_t rS, const int *kp_offsets, const int *kp_times, bool has, size_t list, int E0_, int NE_, int stride2)
     {
@@ -1367,7 +1296,7 @@ struct DownTrackerRaw {
     {
         const int base = ((unsigned)e_rel < (unsigned)NE) ? e_rel * strideR : BIGOFF;
 #pragma unroll
-        for (int r = 0; r < NV; r++) fbld2(rP, base + dbl_off(offs[r]), xp[r], xm[r]);      // (x+, x-) of an element: one 16-byte load
+        for (int r = 0; r < NV; r++) kp_bld2(rP, base + dbl_off(offs[r]), xp[r], xm[r]);      // (x+, x-) of an element: one 16-byte load
         mo = __builtin_amdgcn_raw_buffer_load_b32(rP, base + (has ? offMode : BIGOFF), 0, 0);
     }
     __device__ __forceinline__ void diff(double *xp, const double *xm, int mo, double eps2, double rinv2) const
@@ -1382,7 +1311,7 @@ struct DownTrackerRaw {
     {
         const int base = ((unsigned)e_rel < (unsigned)NE) ? e_rel * strideB : BIGOFF;
 #pragma unroll
-        for (int r = 0; r < NV; r++) __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2f, x[r]), rT, base + offs[r], 0, 0);
+        for (int r = 0; r < NV; r++) kp_bst(x[r], rT, base + offs[r]);
     }
     __device__ __forceinline__ void init(__amdgpu_buffer_rsrc_t rT, __amdgpu_buffer_rsrc_t rP, const int *kp_offsets, const int *kp_times, bool has_,
                                          size_t list, int E0_, int NE_, int n, bool pos_col, double eps2, double rinv2)
@@ -1474,9 +1403,9 @@ __device__ __forceinline__ void fusedpc_producer(double *pcbuf, int *sflag, RecL
             const int row = 4 * r + q;
             tr.offs[r] = (row < n && c < n) ? 8 * ((c < F.dof ? 0 : n) + row) : BIGOFF;
             tr.offs[4 + r] = (row < n && c < m) ? 8 * (2 * n + row) : BIGOFF;
-            oRx[r] = (row < nr && c < n) ? 8 * (row * n + c) : OOBF;
-            oR1[r] = (row < nr && (c == n || RXC)) ? 8 * row : OOBF;      // (RXC: r[k] in every column, see CXX in backward_fused_body)
-            oRu[r] = (row < nr && c < m) ? 8 * (row * m + c) : OOBF;
+            oRx[r] = (row < nr && c < n) ? 8 * (row * n + c) : KP_OOB;
+            oR1[r] = (row < nr && (c == n || RXC)) ? 8 * row : KP_OOB;      // (RXC: r[k] in every column, see CXX in backward_fused_body)
+            oRu[r] = (row < nr && c < m) ? 8 * (row * m + c) : KP_OOB;
             wr[r] = (row < nr) ? 2.0 * F.w_run[row] : 0.0;
             wt[r] = (row < nr) ? 2.0 * F.w_term[row] : 0.0;
         }
@@ -1485,7 +1414,7 @@ __device__ __forceinline__ void fusedpc_producer(double *pcbuf, int *sflag, RecL
     }
     const d4 zero = {0.0, 0.0, 0.0, 0.0};
     const int E0 = F.kp_offsets[(size_t)b * F.dof], NE = F.kp_offsets[(size_t)(b + 1) * F.dof] - E0;      // this trajectory's key-point entries
-    __amdgpu_buffer_rsrc_t rT = frsrc(F.kpc + (size_t)E0 * 3 * L.n, NE * strideB);
+    __amdgpu_buffer_rsrc_t rT = kp_rsrc(F.kpc + (size_t)E0 * 3 * L.n, NE * strideB);
     const double *rb = F.r + (size_t)b * (T + 1) * nr;
     const double *rxb = F.r_x + (size_t)b * (T + 1) * nr * n;
     const double *rub = F.r_u + (size_t)b * (T + 1) * nr * m;
@@ -1496,13 +1425,13 @@ __device__ __forceinline__ void fusedpc_producer(double *pcbuf, int *sflag, RecL
     (void)pRx; (void)pR1; (void)pRu;
     auto load_res = [&](int t) {
         const bool ok = t >= 0;
-        __amdgpu_buffer_rsrc_t rA = frsrc(pRx, ok ? nr * n * 8 : 0);
-        __amdgpu_buffer_rsrc_t rR = frsrc(pR1, ok ? nr * 8 : 0);
-        __amdgpu_buffer_rsrc_t rU = frsrc(pRu, ok ? nr * m * 8 : 0);
+        __amdgpu_buffer_rsrc_t rA = kp_rsrc(pRx, ok ? nr * n * 8 : 0);
+        __amdgpu_buffer_rsrc_t rR = kp_rsrc(pR1, ok ? nr * 8 : 0);
+        __amdgpu_buffer_rsrc_t rU = kp_rsrc(pRu, ok ? nr * m * 8 : 0);
         if (t > 0) { pRx -= nr * n; pR1 -= nr; pRu -= nr * m; }
-        if constexpr (!RXC) { Rx.x = fbld(rA, oRx[0]); Rx.y = fbld(rA, oRx[1]); Rx.z = fbld(rA, oRx[2]); Rx.w = fbld(rA, oRx[3]); }
-        R1.x = fbld(rR, oR1[0]); R1.y = fbld(rR, oR1[1]); R1.z = fbld(rR, oR1[2]); R1.w = fbld(rR, oR1[3]);
-        if constexpr (!RU0) { Ru.x = fbld(rU, oRu[0]); Ru.y = fbld(rU, oRu[1]); Ru.z = fbld(rU, oRu[2]); Ru.w = fbld(rU, oRu[3]); }
+        if constexpr (!RXC) { Rx.x = kp_bld(rA, oRx[0]); Rx.y = kp_bld(rA, oRx[1]); Rx.z = kp_bld(rA, oRx[2]); Rx.w = kp_bld(rA, oRx[3]); }
+        R1.x = kp_bld(rR, oR1[0]); R1.y = kp_bld(rR, oR1[1]); R1.z = kp_bld(rR, oR1[2]); R1.w = kp_bld(rR, oR1[3]);
+        if constexpr (!RU0) { Ru.x = kp_bld(rU, oRu[0]); Ru.y = kp_bld(rU, oRu[1]); Ru.z = kp_bld(rU, oRu[2]); Ru.w = kp_bld(rU, oRu[3]); }
     };
     // CXX: the constant block r_x' W r_x as a resident tile, Lzz~ = Cxx + 2 e_n (r_x' W r)' by ONE product (backward_fused_body)
     constexpr bool CXX = RXC;
@@ -1511,21 +1440,21 @@ __device__ __forceinline__ void fusedpc_producer(double *pcbuf, int *sflag, RecL
     const u64 mask_r1 = (c == n) ? ~0ull : 0ull;
     (void)Cxx; (void)RxW; (void)en2; (void)mask_r1;
     if constexpr (RXC) {                           // the one r_x of the task: in registers for the whole sweep
-        __amdgpu_buffer_rsrc_t rA = frsrc(F.rx_const, nr * n * 8);
-        Rx.x = fbld(rA, oRx[0]); Rx.y = fbld(rA, oRx[1]); Rx.z = fbld(rA, oRx[2]); Rx.w = fbld(rA, oRx[3]);
-        if constexpr (CXX) { RxW = Rx * Wr; Cxx = PR(Rx, RxW, zero, ncr); }
+        __amdgpu_buffer_rsrc_t rA = kp_rsrc(F.rx_const, nr * n * 8);
+        Rx.x = kp_bld(rA, oRx[0]); Rx.y = kp_bld(rA, oRx[1]); Rx.z = kp_bld(rA, oRx[2]); Rx.w = kp_bld(rA, oRx[3]);
+        if constexpr (CXX) { RxW = Rx * Wr; Cxx = kp_Pn(Rx, RxW, zero, ncr); }
     }
     if constexpr (RU0) {                           // [l_uu | l_u] = 0: both ring slots once (the consumer does not read them either)
         Ru = zero;
-        lds_store4(pcbuf + 768, lane, zero); lds_store4(pcbuf + FPC_BUF + 768, lane, zero);
+        kp_lds_store(pcbuf + 768, lane, zero); kp_lds_store(pcbuf + FPC_BUF + 768, lane, zero);
     }
     const int kd = (c < F.dof) ? c : c - F.dof;
     __amdgpu_buffer_rsrc_t rP = rT;
     if constexpr (RAWP) {
-        rP = frsrc(F.fdk + (size_t)E0 * (6 * n + 2) * 8, NE * (6 * n + 2) * 8);
+        rP = kp_rsrc(F.fdk + (size_t)E0 * (6 * n + 2) * 8, NE * (6 * n + 2) * 8);
         tr.init(rT, rP, F.kp_offsets, F.kp_times, c < n, (size_t)b * F.dof + kd, E0, NE, n, c < F.dof, F.eps2, F.rinv_2eps);
     } else if constexpr (SLP) {
-        rP = frsrc(F.kps + (size_t)E0 * 6 * L.n, NE * 2 * strideB);              // the trajectory's slice of the slope store
+        rP = kp_rsrc(F.kps + (size_t)E0 * 6 * L.n, NE * 2 * strideB);              // the trajectory's slice of the slope store
         tr.init(rP, F.kp_offsets, F.kp_times, c < n, (size_t)b * F.dof + kd, E0, NE, 2 * strideB);
     } else {
         tr.init(rT, F.kp_offsets, F.kp_times, c < n, (size_t)b * F.dof + kd, E0, NE, strideB);
@@ -1542,7 +1471,7 @@ __device__ __forceinline__ void fusedpc_producer(double *pcbuf, int *sflag, RecL
         if constexpr (CXX && !decltype(terminal)::value) {
             double p = RxW.x * R1.x;
             p = __builtin_fma(RxW.y, R1.y, p); p = __builtin_fma(RxW.z, R1.z, p); p = __builtin_fma(RxW.w, R1.w, p);
-            Lzz = MFMA(en2, p, Cxx);
+            Lzz = KP_MFMA(en2, p, Cxx);
         } else {
             if constexpr (CXX) {
                 Rz.x = bits_or(Rx.x, bits_and(R1.x, mask_r1)); Rz.y = bits_or(Rx.y, bits_and(R1.y, mask_r1));
@@ -1550,21 +1479,21 @@ __device__ __forceinline__ void fusedpc_producer(double *pcbuf, int *sflag, RecL
             } else {
                 Rz.x = bits_or(Rx.x, R1.x); Rz.y = bits_or(Rx.y, R1.y); Rz.z = bits_or(Rx.z, R1.z); Rz.w = bits_or(Rx.w, R1.w);
             }
-            Lzz = PR(Rz, Rz * W2, zero, ncr);
+            Lzz = kp_Pn(Rz, Rz * W2, zero, ncr);
         }
         d4 LU = zero;
         if constexpr (!RU0) {
             Rur.x = bits_or(Ru.x, R1.x); Rur.y = bits_or(Ru.y, R1.y); Rur.z = bits_or(Ru.z, R1.z); Rur.w = bits_or(Ru.w, R1.w);
-            LU = PR(Ru, Rur * W2, zero, ncr);
+            LU = kp_Pn(Ru, Rur * W2, zero, ncr);
         }
         load_res(t - 1);
         double *tb = pcbuf + (t & 1) * FPC_BUF;
         // (Fz is the side products' operand only: it stays in this wave's registers)
-        lds_store4(tb + 256, lane, Fu);
+        kp_lds_store(tb + 256, lane, Fu);
         // (Lzz: the consumer of the pair reads it at the terminal step only, V = Lzz(T-1); the side products take it
         // from registers here)
-        if (t == T - 1) lds_store4(tb + 512, lane, Lzz);
-        if constexpr (!RU0) lds_store4(tb + 768, lane, LU);
+        if (t == T - 1) kp_lds_store(tb + 512, lane, Lzz);
+        if constexpr (!RU0) kp_lds_store(tb + 768, lane, LU);
         hFz = Fz; hFu = Fu; hLzz = Lzz; hLU = LU;
     };
     load_res(T - 1);
@@ -1579,19 +1508,19 @@ __device__ __forceinline__ void fusedpc_producer(double *pcbuf, int *sflag, RecL
     auto side = [&](int t) __attribute__((always_inline)) {
         d4 V = hLzz;                                   // V_xx = l_xx[T-1]   (iLQR.cpp:537-539)
         if (t < T - 1) {                               // (V' + V'')/2 from the consumer's unsymmetrised image, as the consumer forms it
-            V.x = 0.5 * (sh[FLDS_V + (q) * FVS + c] + sh[FLDS_V + c * FVS + q]);
-            V.y = 0.5 * (sh[FLDS_V + (4 + q) * FVS + c] + sh[FLDS_V + c * FVS + 4 + q]);
-            V.z = 0.5 * (sh[FLDS_V + (8 + q) * FVS + c] + sh[FLDS_V + c * FVS + 8 + q]);
-            V.w = 0.5 * (sh[FLDS_V + (12 + q) * FVS + c] + sh[FLDS_V + c * FVS + 12 + q]);
-            if (lane_nn) fset_reg<REG_NN>(V, 0.0);
+            V.x = 0.5 * (sh[KP_LDS_V + (q) * KP_VS + c] + sh[KP_LDS_V + c * KP_VS + q]);
+            V.y = 0.5 * (sh[KP_LDS_V + (4 + q) * KP_VS + c] + sh[KP_LDS_V + c * KP_VS + 4 + q]);
+            V.z = 0.5 * (sh[KP_LDS_V + (8 + q) * KP_VS + c] + sh[KP_LDS_V + c * KP_VS + 8 + q]);
+            V.w = 0.5 * (sh[KP_LDS_V + (12 + q) * KP_VS + c] + sh[KP_LDS_V + c * KP_VS + 12 + q]);
+            if (lane_nn) kp_set_reg<REG_NN>(V, 0.0);
         }
         d4 Luz;
         Luz.x = bits_and(hLU.x, mask_n); Luz.y = bits_and(hLU.y, mask_n); Luz.z = bits_and(hLU.z, mask_n); Luz.w = bits_and(hLU.w, mask_n);
-        const d4 Tz = PS<NCZ>(V, hFz, zero);
-        const d4 Quz = PS<NCZ>(hFu, Tz, Luz);
-        const d4 Qzz = PS<NCZ>(hFz, Tz, hLzz);
-        lds_store4(pcbuf + FPC_SIDE_QUZ, lane, Quz);
-        lds_store4(pcbuf + FPC_SIDE_QZZ, lane, Qzz);
+        const d4 Tz = kp_P<NCZ>(V, hFz, zero);
+        const d4 Quz = kp_P<NCZ>(hFu, Tz, Luz);
+        const d4 Qzz = kp_P<NCZ>(hFz, Tz, hLzz);
+        kp_lds_store(pcbuf + FPC_SIDE_QUZ, lane, Quz);
+        kp_lds_store(pcbuf + FPC_SIDE_QZZ, lane, Qzz);
     };
     for (int t = T - 1; t > 0; t--) {
         side(t);
@@ -1706,7 +1635,7 @@ __device__ __forceinline__ void forward_fused_body(RecLayout L, FusedArgs F, int
     constexpr bool RV2 = UNI;        // (the per-DoF list form measured 1.3 % SLOWER with it: 2.31 against 2.28 ms)
     auto sig = [](int i) { return RV2 ? 8 * (i >> 3) + 2 * (i & 3) + ((i >> 2) & 1) : i; };
     const int cs = sig(c);                                                  // the residual in column c of the RxT operand
-    const int oR2[2] = {(2 * q < nr) ? 16 * q : OOBF, (8 + 2 * q < nr) ? 64 + 16 * q : OOBF};
+    const int oR2[2] = {(2 * q < nr) ? 16 * q : KP_OOB, (8 + 2 * q < nr) ? 64 + 16 * q : KP_OOB};
     (void)oR2;
     // P2 (paired scoring): the r_x product sits off the state chain, its first operand is the same resident tile at every step and
     // column c of its result depends on column c of Z alone -- and the candidates fill n_alpha <= 8 of the tile's 16 columns.  So the
@@ -1719,7 +1648,7 @@ __device__ __forceinline__ void forward_fused_body(RecLayout L, FusedArgs F, int
     // The final step (terminal weights, its own tile) and a step T-2 left without a partner score themselves as before.
     constexpr bool P2 = PAIR2 && RXC && RU0 && UNI;
     static_assert(!P2 || (KP_FWD_SETS & 1) == 0, "paired scoring pairs the register sets");
-    const int oR2p[2] = {oR2[0] == OOBF ? OOBF : oR2[0] + (c < 8 ? nr * 8 : 0), oR2[1] == OOBF ? OOBF : oR2[1] + (c < 8 ? nr * 8 : 0)};
+    const int oR2p[2] = {oR2[0] == KP_OOB ? KP_OOB : oR2[0] + (c < 8 ? nr * 8 : 0), oR2[1] == KP_OOB ? KP_OOB : oR2[1] + (c < 8 ? nr * 8 : 0)};
     (void)oR2p;
 #pragma unroll
     for (int r = 0; r < 4; r++) {
@@ -1731,11 +1660,11 @@ __device__ __forceinline__ void forward_fused_body(RecLayout L, FusedArgs F, int
             co.a[r] = (row < n && c < n) ? 8 * ((d * KpU * 3 + (row < F.dof ? 0 : 1)) * n + c) : BIGOFF;
             co.b[r] = (row < m && c < n) ? 8 * ((row * KpU * 3 + 2) * n + c) : BIGOFF;
         }
-        oK[r] = (row < n && c < m) ? 8 * (row * m + c) : OOBF;
-        oRxT[r] = (row < n && cs < nr) ? 8 * (cs * n + row) : OOBF;   // RxT(p=row, k=c) = r_x[k][p]   (RV2: residual sig(c) in column c)
-        oRuT[r] = (row < m && cs < nr) ? 8 * (cs * m + row) : OOBF;   // RuT(p=row, k=c) = r_u[k][p]
-        oR[r] = (row < nr) ? 8 * row : OOBF;                          // r[k=row] (rows of Jx / Ju; RV2: oR2)
-        oub[r] = (row < m) ? 8 * row : OOBF;
+        oK[r] = (row < n && c < m) ? 8 * (row * m + c) : KP_OOB;
+        oRxT[r] = (row < n && cs < nr) ? 8 * (cs * n + row) : KP_OOB;   // RxT(p=row, k=c) = r_x[k][p]   (RV2: residual sig(c) in column c)
+        oRuT[r] = (row < m && cs < nr) ? 8 * (cs * m + row) : KP_OOB;   // RuT(p=row, k=c) = r_u[k][p]
+        oR[r] = (row < nr) ? 8 * row : KP_OOB;                          // r[k=row] (rows of Jx / Ju; RV2: oR2)
+        oub[r] = (row < m) ? 8 * row : KP_OOB;
         if (r < NCU) {
             lo[r] = (row < m) ? ctrl_lim[2 * row] : -1.0e300;
             hi[r] = (row < m) ? ctrl_lim[2 * row + 1] : 1.0e300;
@@ -1743,7 +1672,7 @@ __device__ __forceinline__ void forward_fused_body(RecLayout L, FusedArgs F, int
         wcur[r] = (sig(row) < nr) ? F.w_run[sig(row)] : 0.0;
     }
     constexpr int rn = n >> 2;                                              // the register of row n (k)
-    const int okn = (q == (n & 3) && c < m) ? 8 * c : OOBF;
+    const int okn = (q == (n & 3) && c < m) ? 8 * c : KP_OOB;
     const double my_alpha = (c < n_alpha) ? alphas[c] : 0.0;
     d4 Z;
     {
@@ -1758,39 +1687,39 @@ __device__ __forceinline__ void forward_fused_body(RecLayout L, FusedArgs F, int
     const d4 zero = {0.0, 0.0, 0.0, 0.0};
     double partial = 0.0;
 
-    __amdgpu_buffer_rsrc_t rT = frsrc(F.kpc + (size_t)E0 * 3 * L.n, NE * strideB);
+    __amdgpu_buffer_rsrc_t rT = kp_rsrc(F.kpc + (size_t)E0 * 3 * L.n, NE * strideB);
     const double *rb = F.r + (size_t)b * (T + 1) * nr;
     const double *rxb = F.r_x + (size_t)b * (T + 1) * nr * n;
     const double *rub = F.r_u + (size_t)b * (T + 1) * nr * m;
 
     struct Tiles { d4 YkK, RxT, RuT, rv, ub; double kk; };      // kk: this lane's element of k (row n of Yk lives in ONE register)
     auto load_tiles = [&](int t, Tiles &s) {
-        __amdgpu_buffer_rsrc_t rK = frsrc(Kin + ((size_t)b * T + t) * m * n, m * n * 8);
-        __amdgpu_buffer_rsrc_t rk = frsrc(kin + ((size_t)b * T + t) * m, m * 8);
-        __amdgpu_buffer_rsrc_t ru = frsrc(u_nom + ((size_t)b * T + t) * m, m * 8);
-        __amdgpu_buffer_rsrc_t rRx = frsrc(rxb + (size_t)t * nr * n, nr * n * 8);
-        __amdgpu_buffer_rsrc_t rRu = frsrc(rub + (size_t)t * nr * m, nr * m * 8);
-        __amdgpu_buffer_rsrc_t rR = frsrc(rb + (size_t)t * nr, nr * 8);
-        s.YkK.x = fbld(rK, oK[0]); s.YkK.y = fbld(rK, oK[1]); s.YkK.z = fbld(rK, oK[2]); s.YkK.w = fbld(rK, oK[3]);
-        s.kk = fbld(rk, okn);
-        if constexpr (!RXC) { s.RxT.x = fbld(rRx, oRxT[0]); s.RxT.y = fbld(rRx, oRxT[1]); s.RxT.z = fbld(rRx, oRxT[2]); s.RxT.w = fbld(rRx, oRxT[3]); }
+        __amdgpu_buffer_rsrc_t rK = kp_rsrc(Kin + ((size_t)b * T + t) * m * n, m * n * 8);
+        __amdgpu_buffer_rsrc_t rk = kp_rsrc(kin + ((size_t)b * T + t) * m, m * 8);
+        __amdgpu_buffer_rsrc_t ru = kp_rsrc(u_nom + ((size_t)b * T + t) * m, m * 8);
+        __amdgpu_buffer_rsrc_t rRx = kp_rsrc(rxb + (size_t)t * nr * n, nr * n * 8);
+        __amdgpu_buffer_rsrc_t rRu = kp_rsrc(rub + (size_t)t * nr * m, nr * m * 8);
+        __amdgpu_buffer_rsrc_t rR = kp_rsrc(rb + (size_t)t * nr, nr * 8);
+        s.YkK.x = kp_bld(rK, oK[0]); s.YkK.y = kp_bld(rK, oK[1]); s.YkK.z = kp_bld(rK, oK[2]); s.YkK.w = kp_bld(rK, oK[3]);
+        s.kk = kp_bld(rk, okn);
+        if constexpr (!RXC) { s.RxT.x = kp_bld(rRx, oRxT[0]); s.RxT.y = kp_bld(rRx, oRxT[1]); s.RxT.z = kp_bld(rRx, oRxT[2]); s.RxT.w = kp_bld(rRx, oRxT[3]); }
         if constexpr (!RU0) {
-            s.RuT.x = fbld(rRu, oRuT[0]); s.RuT.y = NCU > 1 ? fbld(rRu, oRuT[1]) : 0.0;
-            s.RuT.z = NCU > 2 ? fbld(rRu, oRuT[2]) : 0.0; s.RuT.w = NCU > 3 ? fbld(rRu, oRuT[3]) : 0.0;
+            s.RuT.x = kp_bld(rRu, oRuT[0]); s.RuT.y = NCU > 1 ? kp_bld(rRu, oRuT[1]) : 0.0;
+            s.RuT.z = NCU > 2 ? kp_bld(rRu, oRuT[2]) : 0.0; s.RuT.w = NCU > 3 ? kp_bld(rRu, oRuT[3]) : 0.0;
         }
         if constexpr (P2) {             // (r belongs to the pair: requested behind the tiles, below)
         } else if constexpr (RV2) {
             // (descriptor one element longer: the last pair of an odd residual count reaches into the next step's row -- the array has
             // T + 1 rows, the weights beyond nr are zero)
-            __amdgpu_buffer_rsrc_t rR2 = frsrc(rb + (size_t)t * nr, nr * 8 + 8);
+            __amdgpu_buffer_rsrc_t rR2 = kp_rsrc(rb + (size_t)t * nr, nr * 8 + 8);
             double r0, r1, r2, r3;
-            fbld2s(rR2, oR2[0], 0, r0, r1); fbld2s(rR2, oR2[1], 0, r2, r3);
+            kp_bld2s(rR2, oR2[0], 0, r0, r1); kp_bld2s(rR2, oR2[1], 0, r2, r3);
             s.rv.x = r0; s.rv.y = r1; s.rv.z = r2; s.rv.w = r3;
         } else {
-        s.rv.x = fbld(rR, oR[0]); s.rv.y = fbld(rR, oR[1]); s.rv.z = fbld(rR, oR[2]); s.rv.w = fbld(rR, oR[3]);
+        s.rv.x = kp_bld(rR, oR[0]); s.rv.y = kp_bld(rR, oR[1]); s.rv.z = kp_bld(rR, oR[2]); s.rv.w = kp_bld(rR, oR[3]);
         }
-        s.ub.x = fbld(ru, oub[0]); s.ub.y = NCU > 1 ? fbld(ru, oub[1]) : 0.0;
-        s.ub.z = NCU > 2 ? fbld(ru, oub[2]) : 0.0; s.ub.w = NCU > 3 ? fbld(ru, oub[3]) : 0.0;
+        s.ub.x = kp_bld(ru, oub[0]); s.ub.y = NCU > 1 ? kp_bld(ru, oub[1]) : 0.0;
+        s.ub.z = NCU > 2 ? kp_bld(ru, oub[2]) : 0.0; s.ub.w = NCU > 3 ? kp_bld(ru, oub[3]) : 0.0;
     };
 
     // ---- column tracker, walking UP in time --------------------------------------------------------------
@@ -1816,7 +1745,7 @@ __device__ __forceinline__ void forward_fused_body(RecLayout L, FusedArgs F, int
 #pragma unroll
     for (int i = 0; i < 8; i++) av[i] = 0.0;
     if constexpr (!UNI) {
-        rS = frsrc(F.kps + (size_t)E0 * 6 * L.n, NE * 2 * strideB);
+        rS = kp_rsrc(F.kps + (size_t)E0 * 6 * L.n, NE * 2 * strideB);
         load_col2(rS, co, has ? idx - E0 : -1, NE, 2 * strideB, sv, av);
         load_col2(rS, co, (has && idx + 1 < khi) ? idx + 1 - E0 : -1, NE, 2 * strideB, ev, ea);
     }
@@ -1845,8 +1774,8 @@ __device__ __forceinline__ void forward_fused_body(RecLayout L, FusedArgs F, int
     double acc4[4] = {0.0, 0.0, 0.0, 0.0};
     (void)s2run; (void)s2term; (void)RxTt; (void)sgrun; (void)sgterm; (void)acc4;
     if constexpr (RXC) {
-        __amdgpu_buffer_rsrc_t rRxc = frsrc(F.rx_const, nr * n * 8);
-        RxTc.x = fbld(rRxc, oRxT[0]); RxTc.y = fbld(rRxc, oRxT[1]); RxTc.z = fbld(rRxc, oRxT[2]); RxTc.w = fbld(rRxc, oRxT[3]);
+        __amdgpu_buffer_rsrc_t rRxc = kp_rsrc(F.rx_const, nr * n * 8);
+        RxTc.x = kp_bld(rRxc, oRxT[0]); RxTc.y = kp_bld(rRxc, oRxT[1]); RxTc.z = kp_bld(rRxc, oRxT[2]); RxTc.w = kp_bld(rRxc, oRxT[3]);
         if constexpr (SQW) {
             // lane (c, q) of the operand tile holds r_x[k = c][p = 4r + q]: column c is residual c
             const double swr = (cs < nr) ? __builtin_sqrt(fabs(F.w_run[cs])) : 0.0, swt = (cs < nr) ? __builtin_sqrt(fabs(F.w_term[cs])) : 0.0;
@@ -1870,9 +1799,9 @@ __device__ __forceinline__ void forward_fused_body(RecLayout L, FusedArgs F, int
 #pragma unroll
         for (int k = 0; k < NS; k += 2) {
             const int tk = k + 2 < T ? k : (T > 2 ? T - 2 : 0), rows = T + 1 - tk;
-            __amdgpu_buffer_rsrc_t rRp = frsrc(rb + (size_t)tk * nr, rows > 2 ? 2 * nr * 8 + 8 : rows * nr * 8);
+            __amdgpu_buffer_rsrc_t rRp = kp_rsrc(rb + (size_t)tk * nr, rows > 2 ? 2 * nr * 8 + 8 : rows * nr * 8);
             double r0, r1, r2, r3;
-            fbld2s(rRp, oR2p[0], 0, r0, r1); fbld2s(rRp, oR2p[1], 0, r2, r3);
+            kp_bld2s(rRp, oR2p[0], 0, r0, r1); kp_bld2s(rRp, oR2p[1], 0, r2, r3);
             S[k].rv.x = r0; S[k].rv.y = r1; S[k].rv.z = r2; S[k].rv.w = r3;
         }
     }
@@ -1932,9 +1861,9 @@ __device__ __forceinline__ void forward_fused_body(RecLayout L, FusedArgs F, int
 
     // one descriptor per array for the whole trajectory; the step (t+1, or t again behind the last one: never used) goes
     // into the loads' scalar offset
-    const __amdgpu_buffer_rsrc_t rK = frsrc(Kin + (size_t)b * T * m * n, T * m * n * 8), rk = frsrc(kin + (size_t)b * T * m, T * m * 8),
-                                 ru = frsrc(u_nom + (size_t)b * T * m, T * m * 8), rRx = frsrc(rxb, (T + 1) * nr * n * 8),
-                                 rRu = frsrc(rub, (T + 1) * nr * m * 8), rR = frsrc(rb, (T + 1) * nr * 8);
+    const __amdgpu_buffer_rsrc_t rK = kp_rsrc(Kin + (size_t)b * T * m * n, T * m * n * 8), rk = kp_rsrc(kin + (size_t)b * T * m, T * m * 8),
+                                 ru = kp_rsrc(u_nom + (size_t)b * T * m, T * m * 8), rRx = kp_rsrc(rxb, (T + 1) * nr * n * 8),
+                                 rRu = kp_rsrc(rub, (T + 1) * nr * m * 8), rR = kp_rsrc(rb, (T + 1) * nr * 8);
     // UNI: the uniform tracker of the segment loop below (positions and times are wave-uniform scalars)
     int up = 0, uks = 0, uke = 0, ukn_v = 0;            // segment's start position, its start / end time, the time after that (as loaded)
     double ev2[8];                                       // the column after the next one (requested a segment ahead)
@@ -1969,12 +1898,12 @@ __device__ __forceinline__ void forward_fused_body(RecLayout L, FusedArgs F, int
         // controls -- as the accumulator's initial value the tile had to be assembled first: seven moves per step -- and the clamp is
         // v_min / v_max: 1.74 -> 1.68 ms.  (The general form measured 3 % SLOWER with the same change and keeps the old code.)
         constexpr bool TRIM = UNI;
-        d4 U = PS<NCZ>(Yk, Z, TRIM ? zero : ub);       // (u_nom +) K dx + alpha k   (:879)
+        d4 U = kp_P<NCZ>(Yk, Z, TRIM ? zero : ub);       // (u_nom +) K dx + alpha k   (:879)
         __builtin_amdgcn_sched_barrier(0);
-        cur.YkK.x = fblds(rK, oK[0], sK); cur.YkK.y = fblds(rK, oK[1], sK); cur.YkK.z = fblds(rK, oK[2], sK); cur.YkK.w = fblds(rK, oK[3], sK);
-        cur.kk = fblds(rk, okn, sk);
+        cur.YkK.x = kp_blds(rK, oK[0], sK); cur.YkK.y = kp_blds(rK, oK[1], sK); cur.YkK.z = kp_blds(rK, oK[2], sK); cur.YkK.w = kp_blds(rK, oK[3], sK);
+        cur.kk = kp_blds(rk, okn, sk);
         __builtin_amdgcn_sched_barrier(0);
-        d4 Zn = PS<NCZ>(Ya, Z, zero);                  // A dx (does not need the controls)
+        d4 Zn = kp_P<NCZ>(Ya, Z, zero);                  // A dx (does not need the controls)
         __builtin_amdgcn_sched_barrier(0);
         d4 dU;
         {
@@ -1994,12 +1923,12 @@ __device__ __forceinline__ void forward_fused_body(RecLayout L, FusedArgs F, int
             }
         }
         __builtin_amdgcn_sched_barrier(0);
-        cur.ub.x = fblds(ru, oub[0], sk); cur.ub.y = NCU > 1 ? fblds(ru, oub[1], sk) : 0.0;
-        cur.ub.z = NCU > 2 ? fblds(ru, oub[2], sk) : 0.0; cur.ub.w = NCU > 3 ? fblds(ru, oub[3], sk) : 0.0;
+        cur.ub.x = kp_blds(ru, oub[0], sk); cur.ub.y = NCU > 1 ? kp_blds(ru, oub[1], sk) : 0.0;
+        cur.ub.z = NCU > 2 ? kp_blds(ru, oub[2], sk) : 0.0; cur.ub.w = NCU > 3 ? kp_blds(ru, oub[3], sk) : 0.0;
         __builtin_amdgcn_sched_barrier(0);
-        Zn = PS<NCU>(Yb, dU, Zn);                      // + B du: the next state
+        Zn = kp_P<NCU>(Yb, dU, Zn);                      // + B du: the next state
         d4 Ju = zero;                                  // RU0: r_u = 0, the control residual term vanishes
-        if constexpr (!RU0) Ju = PS<NCU>(cur.RuT, dU, zero);
+        if constexpr (!RU0) Ju = kp_P<NCU>(cur.RuT, dU, zero);
         d4 Jx = zero;
         if constexpr (ROLE == 1) Zev = Z;                  // scored by the odd member
         else {
@@ -2008,8 +1937,8 @@ __device__ __forceinline__ void forward_fused_body(RecLayout L, FusedArgs F, int
                 // 16 take the value 8 lanes below, lanes 0..7 keep theirs).  Every product of the state chain that reads Z has been
                 // issued above; Z is replaced right below, so the chain never carries these columns.
                 auto put = [](double dst, double src) {
-                    const u32x2f d = __builtin_bit_cast(u32x2f, dst), s = __builtin_bit_cast(u32x2f, src);
-                    const u32x2f o = {(unsigned)__builtin_amdgcn_update_dpp((int)d.x, (int)s.x, 0x118, 0xf, 0xc, false),
+                    const u32x2 d = __builtin_bit_cast(u32x2, dst), s = __builtin_bit_cast(u32x2, src);
+                    const u32x2 o = {(unsigned)__builtin_amdgcn_update_dpp((int)d.x, (int)s.x, 0x118, 0xf, 0xc, false),
                                       (unsigned)__builtin_amdgcn_update_dpp((int)d.y, (int)s.y, 0x118, 0xf, 0xc, false)};
                     return __builtin_bit_cast(double, o);
                 };
@@ -2018,14 +1947,14 @@ __device__ __forceinline__ void forward_fused_body(RecLayout L, FusedArgs F, int
                 if constexpr (ncx > 2) Z.z = put(Z.z, Zev.z);
                 if constexpr (ncx > 3) Z.w = put(Z.w, Zev.w);
             }
-            Jx = PS<ncx>(RXC ? ((SQW && MODE == 3) ? RxTt : RxTc) : cur.RxT, Z, zero);     // (SQW: sqrt(w) Jx; terminal weights at the final step)
+            Jx = kp_P<ncx>(RXC ? ((SQW && MODE == 3) ? RxTt : RxTc) : cur.RxT, Z, zero);     // (SQW: sqrt(w) Jx; terminal weights at the final step)
         }
         Z = Zn;
         __builtin_amdgcn_sched_barrier(0);
-        if constexpr (!RXC) { cur.RxT.x = fblds(rRx, oRxT[0], sRx); cur.RxT.y = fblds(rRx, oRxT[1], sRx); cur.RxT.z = fblds(rRx, oRxT[2], sRx); cur.RxT.w = fblds(rRx, oRxT[3], sRx); }
+        if constexpr (!RXC) { cur.RxT.x = kp_blds(rRx, oRxT[0], sRx); cur.RxT.y = kp_blds(rRx, oRxT[1], sRx); cur.RxT.z = kp_blds(rRx, oRxT[2], sRx); cur.RxT.w = kp_blds(rRx, oRxT[3], sRx); }
         if constexpr (!RU0) {
-            cur.RuT.x = fblds(rRu, oRuT[0], sRu); cur.RuT.y = NCU > 1 ? fblds(rRu, oRuT[1], sRu) : 0.0;
-            cur.RuT.z = NCU > 2 ? fblds(rRu, oRuT[2], sRu) : 0.0; cur.RuT.w = NCU > 3 ? fblds(rRu, oRuT[3], sRu) : 0.0;
+            cur.RuT.x = kp_blds(rRu, oRuT[0], sRu); cur.RuT.y = NCU > 1 ? kp_blds(rRu, oRuT[1], sRu) : 0.0;
+            cur.RuT.z = NCU > 2 ? kp_blds(rRu, oRuT[2], sRu) : 0.0; cur.RuT.w = NCU > 3 ? kp_blds(rRu, oRuT[3], sRu) : 0.0;
         }
         if (!UNI && more) fetch_Y(Ya, Yb);             // Y operands of step t+1 (staged during step t-1 ... see below)
         __builtin_amdgcn_sched_barrier(0);
@@ -2093,7 +2022,7 @@ __device__ __forceinline__ void forward_fused_body(RecLayout L, FusedArgs F, int
             // the pair NS steps on: rows t - 1 + NS and t + NS (behind the last pair: rows T-2, T-1, never used)
             const int sRp = (t + NS < T ? t - 1 + NS : T - 2) * nr * 8;
             double r0, r1, r2, r3;
-            fbld2s(rR, oR2p[0], sRp, r0, r1); fbld2s(rR, oR2p[1], sRp, r2, r3);
+            kp_bld2s(rR, oR2p[0], sRp, r0, r1); kp_bld2s(rR, oR2p[1], sRp, r2, r3);
             S[PAR & ~1].rv.x = r0; S[PAR & ~1].rv.y = r1; S[PAR & ~1].rv.z = r2; S[PAR & ~1].rv.w = r3;
             __builtin_amdgcn_sched_barrier(0);
         } else {
@@ -2119,10 +2048,10 @@ __device__ __forceinline__ void forward_fused_body(RecLayout L, FusedArgs F, int
         __builtin_amdgcn_sched_barrier(0);
         if constexpr (RV2) {
             double r0, r1, r2, r3;
-            fbld2s(rR, oR2[0], sR, r0, r1); fbld2s(rR, oR2[1], sR, r2, r3);
+            kp_bld2s(rR, oR2[0], sR, r0, r1); kp_bld2s(rR, oR2[1], sR, r2, r3);
             cur.rv.x = r0; cur.rv.y = r1; cur.rv.z = r2; cur.rv.w = r3;
         } else {
-        cur.rv.x = fblds(rR, oR[0], sR); cur.rv.y = fblds(rR, oR[1], sR); cur.rv.z = fblds(rR, oR[2], sR); cur.rv.w = fblds(rR, oR[3], sR);
+        cur.rv.x = kp_blds(rR, oR[0], sR); cur.rv.y = kp_blds(rR, oR[1], sR); cur.rv.z = kp_blds(rR, oR[2], sR); cur.rv.w = kp_blds(rR, oR[3], sR);
         }
         __builtin_amdgcn_sched_barrier(0);
         }
@@ -2161,9 +2090,9 @@ __device__ __forceinline__ void forward_fused_body(RecLayout L, FusedArgs F, int
             {
                 const int sE = (T > 1 ? T - 2 : 0) * nr * 8, sF = (T - 1) * nr * 8;
                 double r0, r1, r2, r3;
-                fbld2s(rR, oR2[0], sE, r0, r1); fbld2s(rR, oR2[1], sE, r2, r3);
+                kp_bld2s(rR, oR2[0], sE, r0, r1); kp_bld2s(rR, oR2[1], sE, r2, r3);
                 rvE.x = r0; rvE.y = r1; rvE.z = r2; rvE.w = r3;
-                fbld2s(rR, oR2[0], sF, r0, r1); fbld2s(rR, oR2[1], sF, r2, r3);
+                kp_bld2s(rR, oR2[0], sF, r0, r1); kp_bld2s(rR, oR2[1], sF, r2, r3);
                 rvF.x = r0; rvF.y = r1; rvF.z = r2; rvF.w = r3;
             }
             using I0 = std::integral_constant<int, 0>; using I1 = std::integral_constant<int, 1>;
@@ -2241,13 +2170,13 @@ __device__ __forceinline__ void forward_sc_state(double *sh, RecLayout L, int T,
     int oK[4], oub[4];
     double lo[NCU], hi[NCU], kmask[4];
     // k rides in row n of the gain operand: ONE load (the lanes of that row), added into the register that holds the row
-    const int okn = (q == (n & 3) && c < m) ? 8 * c : OOBF;
+    const int okn = (q == (n & 3) && c < m) ? 8 * c : KP_OOB;
 #pragma unroll
     for (int r = 0; r < 4; r++) {
         const int row = 4 * r + q;
-        oK[r] = (row < n && c < m) ? 8 * (row * m + c) : OOBF;
+        oK[r] = (row < n && c < m) ? 8 * (row * m + c) : KP_OOB;
         kmask[r] = (r == (n >> 2)) ? 1.0 : 0.0;
-        oub[r] = (row < m) ? 8 * row : OOBF;
+        oub[r] = (row < m) ? 8 * row : KP_OOB;
         if (r < NCU) {
             lo[r] = (row < m) ? ctrl_lim[2 * row] : -1.0e300;
             hi[r] = (row < m) ? ctrl_lim[2 * row + 1] : 1.0e300;
@@ -2271,15 +2200,15 @@ __device__ __forceinline__ void forward_sc_state(double *sh, RecLayout L, int T,
     struct STiles { d4 YkK, ub; double kk; };
     // one descriptor per array for the whole trajectory, the step in the loads' scalar offset (behind the last step: step T-1
     // again, never used) -- as in forward_fused_body
-    const __amdgpu_buffer_rsrc_t rK = frsrc(Kin + (size_t)b * T * m * n, T * m * n * 8), rk = frsrc(kin + (size_t)b * T * m, T * m * 8),
-                                 ru = frsrc(u_nom + (size_t)b * T * m, T * m * 8);
+    const __amdgpu_buffer_rsrc_t rK = kp_rsrc(Kin + (size_t)b * T * m * n, T * m * n * 8), rk = kp_rsrc(kin + (size_t)b * T * m, T * m * 8),
+                                 ru = kp_rsrc(u_nom + (size_t)b * T * m, T * m * 8);
     auto request = [&](int t, STiles &s_) {
         const int tn = t < T ? t : T - 1;
         const int sK = tn * m * n * 8, sk = tn * m * 8;
-        s_.YkK.x = fblds(rK, oK[0], sK); s_.YkK.y = fblds(rK, oK[1], sK); s_.YkK.z = fblds(rK, oK[2], sK); s_.YkK.w = fblds(rK, oK[3], sK);
-        s_.kk = fblds(rk, okn, sk);
-        s_.ub.x = fblds(ru, oub[0], sk); s_.ub.y = NCU > 1 ? fblds(ru, oub[1], sk) : 0.0;
-        s_.ub.z = NCU > 2 ? fblds(ru, oub[2], sk) : 0.0; s_.ub.w = NCU > 3 ? fblds(ru, oub[3], sk) : 0.0;
+        s_.YkK.x = kp_blds(rK, oK[0], sK); s_.YkK.y = kp_blds(rK, oK[1], sK); s_.YkK.z = kp_blds(rK, oK[2], sK); s_.YkK.w = kp_blds(rK, oK[3], sK);
+        s_.kk = kp_blds(rk, okn, sk);
+        s_.ub.x = kp_blds(ru, oub[0], sk); s_.ub.y = NCU > 1 ? kp_blds(ru, oub[1], sk) : 0.0;
+        s_.ub.z = NCU > 2 ? kp_blds(ru, oub[2], sk) : 0.0; s_.ub.w = NCU > 3 ? kp_blds(ru, oub[3], sk) : 0.0;
     };
     // ---- UNI: the segment tracker (forward_fused_body) ----
     ColOffs co;
@@ -2295,7 +2224,7 @@ __device__ __forceinline__ void forward_sc_state(double *sh, RecLayout L, int T,
         const FusedArgs &F = *Fp;
         E0 = F.kp_offsets[(size_t)b * F.dof]; NE = F.kp_offsets[(size_t)(b + 1) * F.dof] - E0;
         KpU = F.kp_offsets[(size_t)b * F.dof + 1] - E0;
-        rT = frsrc(F.kpc + (size_t)E0 * 3 * n, NE * strideB);
+        rT = kp_rsrc(F.kpc + (size_t)E0 * 3 * n, NE * strideB);
 #pragma unroll
         for (int r = 0; r < 4; r++) {
             // the Y operands themselves: Ya(p = row, o = c) = A(o, p), Yb(p, o) = B(o, p) -- element c of column `row`, whose
@@ -2368,11 +2297,11 @@ __device__ __forceinline__ void forward_sc_state(double *sh, RecLayout L, int T,
             Yk.z = __builtin_fma(kmask[2], kk, Yk.z); Yk.w = __builtin_fma(kmask[3], kk, Yk.w);
         }
         const d4 ub = s_.ub;
-        d4 U = PS<NCZ>(Yk, Z, ub);                     // u_nom + K dx + alpha k   (:879)
+        d4 U = kp_P<NCZ>(Yk, Z, ub);                     // u_nom + K dx + alpha k   (:879)
         __builtin_amdgcn_sched_barrier(0);
         request(t + KP_FSC_SETS, s_);
         __builtin_amdgcn_sched_barrier(0);
-        d4 Zn = PS<NCZ>(Ya, Z, zero);                  // A dx
+        d4 Zn = kp_P<NCZ>(Ya, Z, zero);                  // A dx
         d4 dU = zero;
         {
             double u;                                  // clamp (:883-889)
@@ -2382,9 +2311,9 @@ __device__ __forceinline__ void forward_sc_state(double *sh, RecLayout L, int T,
             if (NCU > 3) { u = U.w; if (u > hi[3]) u = hi[3]; if (u < lo[3]) u = lo[3]; U.w = u; dU.w = u - ub.w; }
         }
         double *zs = sh + FSC_ZS + (t & 1) * 512;
-        lds_store4(zs, lane, Z);                       // the state this step started from, and its control change
-        if constexpr (!RU0) lds_store4(zs + 256, lane, dU);
-        Z = PS<NCU>(Yb, dU, Zn);                       // + B du: the next state
+        kp_lds_store(zs, lane, Z);                       // the state this step started from, and its control change
+        if constexpr (!RU0) kp_lds_store(zs + 256, lane, dU);
+        Z = kp_P<NCU>(Yb, dU, Zn);                       // + B du: the next state
         if (U_alpha && c < n_alpha) {
             double *Ua = U_alpha + (((size_t)b * n_alpha + c) * T + t) * m;
             const double uv[4] = {U.x, U.y, U.z, U.w};
@@ -2425,9 +2354,9 @@ __device__ __forceinline__ void forward_sc_cost(double *sh, RecLayout L, FusedAr
 #pragma unroll
     for (int r = 0; r < 4; r++) {
         const int row = 4 * r + q;
-        oRxT[r] = (row < n && c < nr) ? 8 * (c * n + row) : OOBF;     // RxT(p=row, k=c) = r_x[k][p]
-        oRuT[r] = (row < m && c < nr) ? 8 * (c * m + row) : OOBF;     // RuT(p=row, k=c) = r_u[k][p]
-        oR[r] = (row < nr) ? 8 * row : OOBF;
+        oRxT[r] = (row < n && c < nr) ? 8 * (c * n + row) : KP_OOB;     // RxT(p=row, k=c) = r_x[k][p]
+        oRuT[r] = (row < m && c < nr) ? 8 * (c * m + row) : KP_OOB;     // RuT(p=row, k=c) = r_u[k][p]
+        oR[r] = (row < nr) ? 8 * row : KP_OOB;
         wcur[r] = (row < nr) ? F.w_run[row] : 0.0;
         wterm[r] = (row < nr) ? F.w_term[row] : 0.0;   // in registers from the start: a load inside the time loop makes the
                                                        // compiler drain every outstanding prefetch (vmcnt(0)) each step here
@@ -2435,29 +2364,29 @@ __device__ __forceinline__ void forward_sc_cost(double *sh, RecLayout L, FusedAr
     const d4 zero = {0.0, 0.0, 0.0, 0.0};
     double partial = 0.0;
     const int E0 = F.kp_offsets[(size_t)b * F.dof], NE = F.kp_offsets[(size_t)(b + 1) * F.dof] - E0;      // this trajectory's key-point entries
-    __amdgpu_buffer_rsrc_t rT = frsrc(F.kpc + (size_t)E0 * 3 * L.n, NE * strideB);
+    __amdgpu_buffer_rsrc_t rT = kp_rsrc(F.kpc + (size_t)E0 * 3 * L.n, NE * strideB);
     const double *rb = F.r + (size_t)b * (T + 1) * nr;
     const double *rxb = F.r_x + (size_t)b * (T + 1) * nr * n;
     const double *rub = F.r_u + (size_t)b * (T + 1) * nr * m;
     struct CTiles { d4 RxT, RuT, rv; };
-    const __amdgpu_buffer_rsrc_t rNone = frsrc(rb, 0);
+    const __amdgpu_buffer_rsrc_t rNone = kp_rsrc(rb, 0);
     d4 RxTc = {0.0, 0.0, 0.0, 0.0};
     if constexpr (RXC) {
-        __amdgpu_buffer_rsrc_t rRxc = frsrc(F.rx_const, nr * n * 8);
-        RxTc.x = fbld(rRxc, oRxT[0]); RxTc.y = fbld(rRxc, oRxT[1]); RxTc.z = fbld(rRxc, oRxT[2]); RxTc.w = fbld(rRxc, oRxT[3]);
+        __amdgpu_buffer_rsrc_t rRxc = kp_rsrc(F.rx_const, nr * n * 8);
+        RxTc.x = kp_bld(rRxc, oRxT[0]); RxTc.y = kp_bld(rRxc, oRxT[1]); RxTc.z = kp_bld(rRxc, oRxT[2]); RxTc.w = kp_bld(rRxc, oRxT[3]);
     }
     (void)RxTc;
     auto request = [&](int t, CTiles &s_) {
         const bool ok = t < T;
-        __amdgpu_buffer_rsrc_t rRx = ok ? frsrc(rxb + (size_t)t * nr * n, nr * n * 8) : rNone;
-        __amdgpu_buffer_rsrc_t rRu = ok ? frsrc(rub + (size_t)t * nr * m, nr * m * 8) : rNone;
-        __amdgpu_buffer_rsrc_t rR = ok ? frsrc(rb + (size_t)t * nr, nr * 8) : rNone;
-        if constexpr (!RXC) { s_.RxT.x = fbld(rRx, oRxT[0]); s_.RxT.y = fbld(rRx, oRxT[1]); s_.RxT.z = fbld(rRx, oRxT[2]); s_.RxT.w = fbld(rRx, oRxT[3]); }
+        __amdgpu_buffer_rsrc_t rRx = ok ? kp_rsrc(rxb + (size_t)t * nr * n, nr * n * 8) : rNone;
+        __amdgpu_buffer_rsrc_t rRu = ok ? kp_rsrc(rub + (size_t)t * nr * m, nr * m * 8) : rNone;
+        __amdgpu_buffer_rsrc_t rR = ok ? kp_rsrc(rb + (size_t)t * nr, nr * 8) : rNone;
+        if constexpr (!RXC) { s_.RxT.x = kp_bld(rRx, oRxT[0]); s_.RxT.y = kp_bld(rRx, oRxT[1]); s_.RxT.z = kp_bld(rRx, oRxT[2]); s_.RxT.w = kp_bld(rRx, oRxT[3]); }
         if constexpr (!RU0) {
-            s_.RuT.x = fbld(rRu, oRuT[0]); s_.RuT.y = NCU > 1 ? fbld(rRu, oRuT[1]) : 0.0;
-            s_.RuT.z = NCU > 2 ? fbld(rRu, oRuT[2]) : 0.0; s_.RuT.w = NCU > 3 ? fbld(rRu, oRuT[3]) : 0.0;
+            s_.RuT.x = kp_bld(rRu, oRuT[0]); s_.RuT.y = NCU > 1 ? kp_bld(rRu, oRuT[1]) : 0.0;
+            s_.RuT.z = NCU > 2 ? kp_bld(rRu, oRuT[2]) : 0.0; s_.RuT.w = NCU > 3 ? kp_bld(rRu, oRuT[3]) : 0.0;
         }
-        s_.rv.x = fbld(rR, oR[0]); s_.rv.y = fbld(rR, oR[1]); s_.rv.z = fbld(rR, oR[2]); s_.rv.w = fbld(rR, oR[3]);
+        s_.rv.x = kp_bld(rR, oR[0]); s_.rv.y = kp_bld(rR, oR[1]); s_.rv.z = kp_bld(rR, oR[2]); s_.rv.w = kp_bld(rR, oR[3]);
     };
     // ---- column tracker, walking UP in time (as in forward_fused_body) ----
     const int kd = (c < F.dof) ? c : c - F.dof;
@@ -2509,10 +2438,10 @@ __device__ __forceinline__ void forward_sc_cost(double *sh, RecLayout L, FusedAr
         if (ROLE == 1 && t >= 1) {
             const int tt = t - 1;
             const double *zs = sh + FSC_ZS + (tt & 1) * 512;
-            const d4 Zt = lds_tile4(zs, lane);
+            const d4 Zt = kp_lds_tile(zs, lane);
             d4 Ju = zero;                              // RU0: the control residual term vanishes (and nobody reads the dU slot)
-            if constexpr (!RU0) { const d4 dU = lds_tile4(zs + 256, lane); Ju = PS<NCU>(s_.RuT, dU, zero); }
-            const d4 Jx = PR(RXC ? RxTc : s_.RxT, Zt, zero, ncx);
+            if constexpr (!RU0) { const d4 dU = kp_lds_tile(zs + 256, lane); Ju = kp_P<NCU>(s_.RuT, dU, zero); }
+            const d4 Jx = kp_Pn(RXC ? RxTc : s_.RxT, Zt, zero, ncx);
             const d4 r2 = s_.rv + s_.rv;
             __builtin_amdgcn_sched_barrier(0);
             request(tt + KP_FSC_SETS, s_);

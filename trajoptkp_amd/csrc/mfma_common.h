@@ -1,27 +1,163 @@
 // mfma_common.h -- device helpers shared by the FP64 MFMA kernels (riccati_mfma.hip, forward_mfma.hip,
-// tiled_mfma.hip, fused_mfma.hip): the tile type and primitive, bounds-checked buffer loads, a ~1 ulp reciprocal,
-// and the slow path of the backward pass (Eigen's pivoted LDLT + explicit inverse).
+// tiled_mfma.hip, tiled_wide.hip, fused_mfma.hip): the primitive layer (tile type, matrix instruction, bounds-checked
+// buffer accesses, LDS tile images, record tile sources, the one-tile LDS map), a ~1 ulp reciprocal, the running
+// inverse, and the slow path of the backward pass (Eigen's pivoted LDLT + explicit inverse).
 #pragma once
 #include "common.h"
 
 namespace kpilqr {
 
+// ---- the primitive layer: the one copy of what every sweep unit is written in ---------------------------------------------
 typedef double d4 __attribute__((ext_vector_type(4)));
 typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
+typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 // D = A*B + C on the FP64 matrix core, 16x16 output, 4 rows of the contraction per instruction.
 #define KP_MFMA(a, b, c) __builtin_amdgcn_mfma_f64_16x16x4f64((a), (b), (c), 0, 0, 0)
 // byte offset that lies outside every buffer descriptor used here: the load returns 0, the store is dropped
 #define KP_OOB 0x7ffffff0
+// LDS tile image: 256 doubles, register r of lane l at [r*64 + l]; 16 x 17 padded row-major tile (transposed reads without bank conflicts)
+#define KP_TILE 256
+#define KP_TPAD 272
 
+// Bounds-checked buffer accesses: a lane whose tile element is a structural zero carries an out-of-range offset and gets 0
+// from the hardware (no select on the loaded value, so nothing consumes it until the product that needs it).
 __device__ __forceinline__ double kp_bld(__amdgpu_buffer_rsrc_t r, int byte_off)
 {
     return __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(r, byte_off, 0, 0));
+}
+// the same with a wave-uniform byte offset in the instruction's scalar operand: ONE descriptor per array and trajectory,
+// the step selected by an SGPR, instead of a descriptor rebuilt (64-bit address arithmetic, ~8 SALU) per array and step
+__device__ __forceinline__ double kp_blds(__amdgpu_buffer_rsrc_t r, int byte_off, int soff)
+{
+    return __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(r, byte_off, soff, 0));
+}
+// two consecutive doubles with one request (16-byte aligned)
+__device__ __forceinline__ void kp_bld2s(__amdgpu_buffer_rsrc_t r, int byte_off, int soff, double &a, double &b)
+{
+    const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(r, byte_off, soff, 0);
+    const u32x2 lo = {v.x, v.y}, hi = {v.z, v.w};
+    a = __builtin_bit_cast(double, lo); b = __builtin_bit_cast(double, hi);
+}
+__device__ __forceinline__ void kp_bld2(__amdgpu_buffer_rsrc_t r, int byte_off, double &a, double &b) { kp_bld2s(r, byte_off, 0, a, b); }
+__device__ __forceinline__ void kp_bst(double x, __amdgpu_buffer_rsrc_t r, int byte_off)
+{
+    __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, x), r, byte_off, 0, 0);
 }
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t kp_rsrc(const void *p, int bytes)
 {
     return __builtin_amdgcn_make_buffer_rsrc((void *)p, 0, bytes, 0x00020000);
 }
+
+// acc + Y'X over NC 4-row chunks: the one primitive of these kernels (tiles in the accumulator layout are their own
+// transpose as the A operand and the next B operand as they are).
+template <int NC>
+__device__ __forceinline__ d4 kp_P(const d4 &Y, const d4 &X, d4 acc)
+{
+    acc = KP_MFMA(Y.x, X.x, acc);
+    if (NC > 1) acc = KP_MFMA(Y.y, X.y, acc);
+    if (NC > 2) acc = KP_MFMA(Y.z, X.z, acc);
+    if (NC > 3) acc = KP_MFMA(Y.w, X.w, acc);
+    return acc;
+}
+// the same over `nc` chunks known at run time (nc is wave-uniform)
+__device__ __forceinline__ d4 kp_Pn(const d4 &Y, const d4 &X, d4 acc, int nc)
+{
+    acc = KP_MFMA(Y.x, X.x, acc);
+    if (nc > 1) acc = KP_MFMA(Y.y, X.y, acc);
+    if (nc > 2) acc = KP_MFMA(Y.z, X.z, acc);
+    if (nc > 3) acc = KP_MFMA(Y.w, X.w, acc);
+    return acc;
+}
+
+// A tile between registers and its LDS image; <NC>: the first NC registers only (the others read as 0)
+__device__ __forceinline__ d4 kp_lds_tile(const double *t, int lane)
+{
+    d4 v; v.x = t[lane]; v.y = t[64 + lane]; v.z = t[128 + lane]; v.w = t[192 + lane];
+    return v;
+}
+__device__ __forceinline__ void kp_lds_store(double *t, int lane, const d4 &v)
+{
+    t[lane] = v.x; t[64 + lane] = v.y; t[128 + lane] = v.z; t[192 + lane] = v.w;
+}
+template <int NC> __device__ __forceinline__ d4 kp_lds_tile(const double *t, int lane)
+{
+    d4 v = {0.0, 0.0, 0.0, 0.0};
+    v.x = t[lane];
+    if constexpr (NC > 1) v.y = t[64 + lane];
+    if constexpr (NC > 2) v.z = t[128 + lane];
+    if constexpr (NC > 3) v.w = t[192 + lane];
+    return v;
+}
+template <int NC> __device__ __forceinline__ void kp_lds_store(double *t, int lane, const d4 &v)
+{
+    t[lane] = v.x;
+    if constexpr (NC > 1) t[64 + lane] = v.y;
+    if constexpr (NC > 2) t[128 + lane] = v.z;
+    if constexpr (NC > 3) t[192 + lane] = v.w;
+}
+
+// register R of a tile, R at compile time / r at run time
+template <int R> __device__ __forceinline__ void kp_set_reg(d4 &v, double x) { if (R == 0) v.x = x; else if (R == 1) v.y = x; else if (R == 2) v.z = x; else v.w = x; }
+__device__ __forceinline__ void kp_set_reg(d4 &v, int r, double x)
+{
+    if (r == 0) v.x = x; else if (r == 1) v.y = x; else if (r == 2) v.z = x; else v.w = x;
+}
+
+// LDS map (doubles) of the one-tile backward sweeps.  KP_MS: row stride of the Quu image; KP_MZ: column stride of the Quz image
+// (odd -> conflict-free column reads); KP_VS: row stride of the transpose image; behind KP_LDS_SLOW the work area of the slow path.
+#define KP_MS 16
+#define KP_MZ 17
+#define KP_VS 17
+#define KP_LDS_Q 0
+#define KP_LDS_Z (KP_LDS_Q + 16 * KP_MS)
+#define KP_LDS_V (KP_LDS_Z + 16 * KP_MZ)
+#define KP_LDS_SLOW (KP_LDS_V + 16 * KP_VS)
+
+// Tiles of a step record for the tiled sweeps (bounds-checked: structural zeros come back as 0).  Register r of a tile in the
+// accumulator layout: element (16 ti + 4 r + q, 16 tj + c); the *1 loaders fetch one register, so that a sweep can spread its
+// requests under its products.  A control index spans the control tiles tj = 0, 1 (tiled_mfma.hip, m <= 8: tile 0 only).
+struct KpTileSrc { int n, m; int off_A, off_B, off_lxx, off_lx, off_luu, off_lu; };
+
+__device__ __forceinline__ double kp_ld_Lzz1(__amdgpu_buffer_rsrc_t rs, const KpTileSrc &S, int ti, int tj, int r, int q, int c)
+{
+    const int row = 16 * ti + 4 * r + q, col = 16 * tj + c, n = S.n;
+    const int off = (row < n && col < n) ? 8 * (S.off_lxx + row * n + col)
+                  : (col == n && row < n) ? 8 * (S.off_lx + row)
+                  : (row == n && col < n) ? 8 * (S.off_lx + col) : KP_OOB;
+    return kp_bld(rs, off);
+}
+__device__ __forceinline__ double kp_ld_Fz1(__amdgpu_buffer_rsrc_t rs, const KpTileSrc &S, int ti, int tj, int r, int q, int c)
+{
+    const int row = 16 * ti + 4 * r + q, col = 16 * tj + c, n = S.n;
+    return kp_bld(rs, (row < n && col < n) ? 8 * (S.off_A + col * n + row) : KP_OOB);
+}
+// B(row tile ti, control tile tj)
+__device__ __forceinline__ double kp_ld_Fu1(__amdgpu_buffer_rsrc_t rs, const KpTileSrc &S, int ti, int tj, int r, int q, int c)
+{
+    const int row = 16 * ti + 4 * r + q, col = 16 * tj + c;
+    return kp_bld(rs, (row < S.n && col < S.m) ? 8 * (S.off_B + col * S.n + row) : KP_OOB);
+}
+// Luz(control tile tj, state tile tw): l_u in column n
+__device__ __forceinline__ double kp_ld_Luz1(__amdgpu_buffer_rsrc_t rs, const KpTileSrc &S, int tj, int tw, int r, int q, int c)
+{
+    const int row = 16 * tj + 4 * r + q, col = 16 * tw + c;
+    return kp_bld(rs, (row < S.m && col == S.n) ? 8 * (S.off_lu + row) : KP_OOB);
+}
+__device__ __forceinline__ double kp_ld_Luu1(__amdgpu_buffer_rsrc_t rs, const KpTileSrc &S, int ta, int tb, int r, int q, int c)
+{
+    const int row = 16 * ta + 4 * r + q, col = 16 * tb + c;
+    return kp_bld(rs, (row < S.m && col < S.m) ? 8 * (S.off_luu + row * S.m + col) : KP_OOB);
+}
+#define KP_X(NAME) \
+__device__ __forceinline__ d4 kp_ld_##NAME(__amdgpu_buffer_rsrc_t rs, const KpTileSrc &S, int ti, int tj, int q, int c) \
+{ \
+    d4 o = {kp_ld_##NAME##1(rs, S, ti, tj, 0, q, c), kp_ld_##NAME##1(rs, S, ti, tj, 1, q, c), kp_ld_##NAME##1(rs, S, ti, tj, 2, q, c), kp_ld_##NAME##1(rs, S, ti, tj, 3, q, c)}; \
+    return o; \
+}
+KP_X(Lzz) KP_X(Fz) KP_X(Fu) KP_X(Luz) KP_X(Luu)
+#undef KP_X
+
 // 1/x to ~1 ulp: v_rcp_f64 seed + two Newton steps (the pivots are O(lambda)..O(1): no scaling needed; a
 // non-positive or non-finite pivot is caught by the callers' `pos` test and takes the slow path).
 __device__ __forceinline__ double kp_rcp(double x)
@@ -32,8 +168,6 @@ __device__ __forceinline__ double kp_rcp(double x)
     return r;
 }
 
-// acc + Y'X over NC 4-row chunks: the one primitive of these kernels (tiles in the accumulator layout are their own
-// transpose as the A operand and the next B operand as they are).
 // One-tile shapes (n + 1 <= 16) that have their own backward / fused kernel instantiations: Panda reaching and push_soft
 // (14,7), Acrobot and piston (4,1), hopper and floating cube (12,3), pentabot (10,3) -- the joint / actuator counts of the
 // reference's TaskConfigs.  Everything else goes to the tiled kernels (any n + 2 <= 64, num_ctrl <= 8).
@@ -58,16 +192,6 @@ static inline bool kp_t1_carrier(int dof, int m, int *carrier_dof, int *carrier_
     if (!bn) return false;
     *carrier_dof = bn / 2; *carrier_m = bm;
     return true;
-}
-
-template <int NC>
-__device__ __forceinline__ d4 kp_P(const d4 &Y, const d4 &X, d4 acc)
-{
-    acc = KP_MFMA(Y.x, X.x, acc);
-    if (NC > 1) acc = KP_MFMA(Y.y, X.y, acc);
-    if (NC > 2) acc = KP_MFMA(Y.z, X.z, acc);
-    if (NC > 3) acc = KP_MFMA(Y.w, X.w, acc);
-    return acc;
 }
 
 // Running inverse of Q = Quu + lambda I (m x m, rows/cols < 4*NCU of a tile): Newton-Schulz steps

@@ -33,30 +33,6 @@
 
 namespace kpilqr {
 
-#define MFMA KP_MFMA
-
-// acc + Y' X over NC row-chunks (rows 0 .. 4*NC-1 of Y and X).
-template <int NC>
-__device__ __forceinline__ d4 P(const d4 &Y, const d4 &X, d4 acc)
-{
-    acc = MFMA(Y.x, X.x, acc);
-    if (NC > 1) acc = MFMA(Y.y, X.y, acc);
-    if (NC > 2) acc = MFMA(Y.z, X.z, acc);
-    if (NC > 3) acc = MFMA(Y.w, X.w, acc);
-    return acc;
-}
-
-// Step-record loads go through a buffer descriptor that covers exactly ONE record: lanes whose tile
-// element is a structural zero carry an out-of-range offset and the hardware returns 0 for them
-// without touching memory.  No select on the loaded value means nothing consumes it until the MFMA
-// that needs it, so the loads of step t-1 stay in flight behind the whole of step t.
-#define OOB 0x7ffffff0
-
-__device__ __forceinline__ double bld(__amdgpu_buffer_rsrc_t r, int byte_off)
-{
-    return __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(r, byte_off, 0, 0));
-}
-
 // Pull one whole step record into this XCD's L2 a few steps before its tile loads are issued: one
 // LDS-DMA dword per 64-byte sector (the data lands in a scratch LDS row nobody reads).  It costs no
 // VGPR, and it takes the page-table walk and the HBM fetch of that record off the critical path --
@@ -92,32 +68,22 @@ struct StepTiles { d4 Fz, Fu, Lzz, Luz, Luu; };
 template <int NCU>
 __device__ __forceinline__ void load_step(const double *R, int rec_bytes, const TileOffs &o, StepTiles &s)
 {
-    __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc((void *)R, 0, rec_bytes, 0x00020000);
-    s.Fz.x = bld(r, o.fz[0]); s.Fz.y = bld(r, o.fz[1]); s.Fz.z = bld(r, o.fz[2]); s.Fz.w = bld(r, o.fz[3]);
-    s.Fu.x = bld(r, o.fu[0]); s.Fu.y = bld(r, o.fu[1]); s.Fu.z = bld(r, o.fu[2]); s.Fu.w = bld(r, o.fu[3]);
-    s.Lzz.x = bld(r, o.lzz[0]); s.Lzz.y = bld(r, o.lzz[1]); s.Lzz.z = bld(r, o.lzz[2]); s.Lzz.w = bld(r, o.lzz[3]);
-    s.Luz.x = bld(r, o.luz[0]); s.Luu.x = bld(r, o.luu[0]);
-    s.Luz.y = NCU > 1 ? bld(r, o.luz[1]) : 0.0; s.Luu.y = NCU > 1 ? bld(r, o.luu[1]) : 0.0;
-    s.Luz.z = NCU > 2 ? bld(r, o.luz[2]) : 0.0; s.Luu.z = NCU > 2 ? bld(r, o.luu[2]) : 0.0;
-    s.Luz.w = NCU > 3 ? bld(r, o.luz[3]) : 0.0; s.Luu.w = NCU > 3 ? bld(r, o.luu[3]) : 0.0;
+    __amdgpu_buffer_rsrc_t r = kp_rsrc(R, rec_bytes);
+    s.Fz.x = kp_bld(r, o.fz[0]); s.Fz.y = kp_bld(r, o.fz[1]); s.Fz.z = kp_bld(r, o.fz[2]); s.Fz.w = kp_bld(r, o.fz[3]);
+    s.Fu.x = kp_bld(r, o.fu[0]); s.Fu.y = kp_bld(r, o.fu[1]); s.Fu.z = kp_bld(r, o.fu[2]); s.Fu.w = kp_bld(r, o.fu[3]);
+    s.Lzz.x = kp_bld(r, o.lzz[0]); s.Lzz.y = kp_bld(r, o.lzz[1]); s.Lzz.z = kp_bld(r, o.lzz[2]); s.Lzz.w = kp_bld(r, o.lzz[3]);
+    s.Luz.x = kp_bld(r, o.luz[0]); s.Luu.x = kp_bld(r, o.luu[0]);
+    s.Luz.y = NCU > 1 ? kp_bld(r, o.luz[1]) : 0.0; s.Luu.y = NCU > 1 ? kp_bld(r, o.luu[1]) : 0.0;
+    s.Luz.z = NCU > 2 ? kp_bld(r, o.luz[2]) : 0.0; s.Luu.z = NCU > 2 ? kp_bld(r, o.luu[2]) : 0.0;
+    s.Luz.w = NCU > 3 ? kp_bld(r, o.luz[3]) : 0.0; s.Luu.w = NCU > 3 ? kp_bld(r, o.luu[3]) : 0.0;
 }
 
-// LDS map (doubles).  MS: row stride of the Quu image; MZ: column stride of the Quz image (odd ->
-// conflict-free column reads); VS: row stride of the transpose image.
-#define MS 16
-#define MZ 17
-#define VS 17
-#define LDS_Q 0
-#define LDS_Z (LDS_Q + 16 * MS)
-#define LDS_V (LDS_Z + 16 * MZ)
-#define LDS_SLOW (LDS_V + 16 * VS)
-#define LDS_PF (LDS_SLOW + 2 * 256 + 16 + 16)
+// behind the one-tile LDS map (mfma_common.h): the scratch row of the L2 prefetch
+#define LDS_PF (KP_LDS_SLOW + 2 * 256 + 16 + 16)
 #define LDS_TOTAL (LDS_PF + 32)
 
 // ABL: ablation switches for tools/ablate_backward.cpp only (0 in the product): 1 = always load the
 // same record (no HBM streaming), 4 = skip the K/k stores, 8 = skip the symmetrisation transpose.
-template <int R> __device__ __forceinline__ void set_reg(d4 &v, double x) { if (R == 0) v.x = x; else if (R == 1) v.y = x; else if (R == 2) v.z = x; else v.w = x; }
-
 template <int N, int M, int ABL>
 __device__ __forceinline__ void backward_body(RecLayout L, int T, const double *__restrict__ rec, const double *__restrict__ lambda,
                 int pd_stride, double *__restrict__ Kout, double *__restrict__ kout,
@@ -136,23 +102,23 @@ __device__ __forceinline__ void backward_body(RecLayout L, int T, const double *
 #pragma unroll
     for (int r = 0; r < 4; r++) {
         const int row = 4 * r + q;
-        o.fz[r] = (row < n && c < n) ? 8 * L.a(row, c) : OOB;
+        o.fz[r] = (row < n && c < n) ? 8 * L.a(row, c) : KP_OOB;
         one[r] = (row == n && c == n) ? 1.0 : 0.0;
-        o.fu[r] = (row < n && c < m) ? 8 * L.b(row, c) : OOB;
+        o.fu[r] = (row < n && c < m) ? 8 * L.b(row, c) : KP_OOB;
         o.lzz[r] = (row < n && c < n) ? 8 * (L.off_lxx + row * n + c)
                  : (c == n && row < n) ? 8 * (L.off_lx + row)
-                 : (row == n && c < n) ? 8 * (L.off_lx + c) : OOB;
-        o.luz[r] = (row < m && c == n) ? 8 * (L.off_lu + row) : OOB;
-        o.luu[r] = (row < m && c < m) ? 8 * (L.off_luu + row * m + c) : OOB;
+                 : (row == n && c < n) ? 8 * (L.off_lx + c) : KP_OOB;
+        o.luz[r] = (row < m && c == n) ? 8 * (L.off_lu + row) : KP_OOB;
+        o.luu[r] = (row < m && c < m) ? 8 * (L.off_luu + row * m + c) : KP_OOB;
     }
     const int rec_bytes = L.rec * 8;
-    int oKst[4], okst[4];      // byte offsets of this lane's K / k elements, OOB where it owns none
+    int oKst[4], okst[4];      // byte offsets of this lane's K / k elements, KP_OOB where it owns none
     double lam2d[4];           // 2*lambda on the diagonal of the u-block
 #pragma unroll
     for (int r = 0; r < 4; r++) {
         const int row = 4 * r + q;
-        oKst[r] = (row < m && c < n) ? 8 * (row + c * m) : OOB;
-        okst[r] = (row < m && c == n) ? 8 * row : OOB;
+        oKst[r] = (row < m && c < n) ? 8 * (row + c * m) : KP_OOB;
+        okst[r] = (row < m && c == n) ? 8 * row : KP_OOB;
         lam2d[r] = (row == c && row < m) ? 2.0 * lam : 0.0;
     }
     // element (n,n) of a tile lives in lane (c = n, q = n & 3), register n >> 2
@@ -185,6 +151,7 @@ __device__ __forceinline__ void backward_body(RecLayout L, int T, const double *
     auto store_gains = [&](int t_, const d4 &Kp) {
         const int t = __builtin_amdgcn_readfirstlane(t_);
         if (!(ABL & 4)) {
+            // (the two descriptors stay spelled out: through kp_rsrc the <4, 1> kernels come out with other instructions)
             // K (m x n column-major) and k out through bounds-checked buffer stores (lanes that own no
             // element carry an out-of-range offset and are dropped): straight-line code.
             __amdgpu_buffer_rsrc_t rK = __builtin_amdgcn_make_buffer_rsrc((void *)(Kout + ((size_t)b * T + t) * m * n), 0, m * n * 8, 0x00020000);
@@ -192,8 +159,8 @@ __device__ __forceinline__ void backward_body(RecLayout L, int T, const double *
             const double kv[4] = {Kp.x, Kp.y, Kp.z, Kp.w};
 #pragma unroll
             for (int r = 0; r < NCU; r++) {
-                __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, kv[r]), rK, oKst[r], 0, 0);
-                __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, kv[r]), rk, okst[r], 0, 0);
+                kp_bst(kv[r], rK, oKst[r]);
+                kp_bst(kv[r], rk, okst[r]);
             }
         }
     };
@@ -204,12 +171,12 @@ __device__ __forceinline__ void backward_body(RecLayout L, int T, const double *
         Fz.x += one[0]; Fz.y += one[1]; Fz.z += one[2]; Fz.w += one[3];
 
         // ---- Tu = V' Fu ; Quu = l_uu + Fu' Tu --------------------------------------- :577
-        d4 Tu = P<NCZ>(V, cur.Fu, zero);
-        d4 Quu = P<NCZ>(cur.Fu, Tu, cur.Luu);
+        d4 Tu = kp_P<NCZ>(V, cur.Fu, zero);
+        d4 Quu = kp_P<NCZ>(cur.Fu, Tu, cur.Luu);
         // ---- Tz, Quz, Qzz --------------------------------------------------------------- :570-579
-        d4 Tz = P<NCZ>(V, Fz, zero);
-        d4 Quz = P<NCZ>(cur.Fu, Tz, cur.Luz);
-        d4 Qzz = P<NCZ>(Fz, Tz, cur.Lzz);
+        d4 Tz = kp_P<NCZ>(V, Fz, zero);
+        d4 Quz = kp_P<NCZ>(cur.Fu, Tz, cur.Luz);
+        d4 Qzz = kp_P<NCZ>(Fz, Tz, cur.Lzz);
         // the tiles are used up: the gains of the step above go out, then this set is requested for step t-2
         // (behind step 1 the request repeats step 0's record: never used, but no condition around the loads)
         __builtin_amdgcn_sched_barrier(0);
@@ -231,26 +198,26 @@ __device__ __forceinline__ void backward_body(RecLayout L, int T, const double *
         d4 Xp = zero;
         bool done = false;
         if (haveX && !check_pd && kp_inverse_refresh_p<NCU>(Qr, Iu, Xinv, Xprev, m)) {
-            Xp = P<NCU>(Xinv, Quz, zero);                                  // Xinv' Quz = (Quu + lambda I)^-1 Quz
+            Xp = kp_P<NCU>(Xinv, Quz, zero);                                  // Xinv' Quz = (Quu + lambda I)^-1 Quz
             done = true;
         }
         if (!done) {
-            // Quu + lambda I -> LDS image (row-major, stride MS) and Quz (column-major, stride MZ) for the per-lane solve
-            sh[LDS_Q + q * MS + c] = Qr.x;
-            if (NCU > 1) sh[LDS_Q + (4 + q) * MS + c] = Qr.y;
-            if (NCU > 2) sh[LDS_Q + (8 + q) * MS + c] = Qr.z;
-            if (NCU > 3) sh[LDS_Q + (12 + q) * MS + c] = Qr.w;
-            sh[LDS_Z + c * MZ + q] = Quz.x;
-            if (NCU > 1) sh[LDS_Z + c * MZ + 4 + q] = Quz.y;
-            if (NCU > 2) sh[LDS_Z + c * MZ + 8 + q] = Quz.z;
-            if (NCU > 3) sh[LDS_Z + c * MZ + 12 + q] = Quz.w;
+            // Quu + lambda I -> LDS image (row-major, stride KP_MS) and Quz (column-major, stride KP_MZ) for the per-lane solve
+            sh[KP_LDS_Q + q * KP_MS + c] = Qr.x;
+            if (NCU > 1) sh[KP_LDS_Q + (4 + q) * KP_MS + c] = Qr.y;
+            if (NCU > 2) sh[KP_LDS_Q + (8 + q) * KP_MS + c] = Qr.z;
+            if (NCU > 3) sh[KP_LDS_Q + (12 + q) * KP_MS + c] = Qr.w;
+            sh[KP_LDS_Z + c * KP_MZ + q] = Quz.x;
+            if (NCU > 1) sh[KP_LDS_Z + c * KP_MZ + 4 + q] = Quz.y;
+            if (NCU > 2) sh[KP_LDS_Z + c * KP_MZ + 8 + q] = Quz.z;
+            if (NCU > 3) sh[KP_LDS_Z + c * KP_MZ + 12 + q] = Quz.w;
             __syncthreads();
             // ---- unpivoted LDL' of Quu + lambda I, redundantly in every lane (lower triangle) ----
             double Lm[M][M], rd[M];
             // (every lane factorises the same image; the ballot tells the compiler that the verdict -- and with it `fail` and the
             // exit of the time loop -- is wave-uniform: with a per-lane verdict the buffer descriptors of the step became
             // 'divergent' and every load was wrapped in a readfirstlane loop)
-            const bool pos = __builtin_amdgcn_ballot_w64(!kp_ldl_factor<M>([&](int i, int j) { return sh[LDS_Q + i * MS + j]; }, Lm, rd)) == 0;
+            const bool pos = __builtin_amdgcn_ballot_w64(!kp_ldl_factor<M>([&](int i, int j) { return sh[KP_LDS_Q + i * KP_MS + j]; }, Lm, rd)) == 0;
             if (check_pd) {                       // CheckMatrixPD every pd_stride steps   :587-595
                 if (!pos) { if (!fail) fail = t + 1; return; }
                 pd_counter = 0;
@@ -259,7 +226,7 @@ __device__ __forceinline__ void backward_body(RecLayout L, int T, const double *
             double x[M];
             if (pos) {
 #pragma unroll
-                for (int i = 0; i < M; i++) x[i] = sh[LDS_Z + c * MZ + i];
+                for (int i = 0; i < M; i++) x[i] = sh[KP_LDS_Z + c * KP_MZ + i];
                 kp_ldl_solve<M>(Lm, rd, x);
                 // seed the fast path: column c of the inverse in lane c (c < m), as a tile
                 double y[M];
@@ -276,15 +243,15 @@ __device__ __forceinline__ void backward_body(RecLayout L, int T, const double *
             } else {
                 // Q_uu + lambda I is not PD and this is not a checked step: follow Eigen's pivoted
                 // LDLT + explicit inverse exactly (iLQR.cpp:597-604).
-                double *wa = sh + LDS_SLOW, *wx = wa + 256, *wt = wx + 256;
+                double *wa = sh + KP_LDS_SLOW, *wx = wa + 256, *wt = wx + 256;
                 int *tr = (int *)(wt + 16);
-                if (lane == 0) kp_slow_ldlt_inverse(L.m, sh + LDS_Q, MS, wa, wx, wt, tr);
+                if (lane == 0) kp_slow_ldlt_inverse(L.m, sh + KP_LDS_Q, KP_MS, wa, wx, wt, tr);
                 __syncthreads();
 #pragma unroll
                 for (int i = 0; i < M; i++) {
                     double sacc = 0.0;
 #pragma unroll
-                    for (int p = 0; p < M; p++) sacc += (-wx[i + p * m]) * sh[LDS_Z + c * MZ + p];
+                    for (int p = 0; p < M; p++) sacc += (-wx[i + p * m]) * sh[KP_LDS_Z + c * KP_MZ + p];
                     x[i] = -sacc;
                 }
                 __syncthreads();
@@ -313,20 +280,20 @@ __device__ __forceinline__ void backward_body(RecLayout L, int T, const double *
         d4 G;
         G.x = -__builtin_fma(lam, Xp.x, Quz.x); G.y = -__builtin_fma(lam, Xp.y, Quz.y);
         G.z = -__builtin_fma(lam, Xp.z, Quz.z); G.w = -__builtin_fma(lam, Xp.w, Quz.w);
-        d4 acc = P<NCU>(Xp, G, Qzz);
+        d4 acc = kp_P<NCU>(Xp, G, Qzz);
 
         // ---- V' = (V' + V'')/2 through an LDS transpose   (:610) -----------------------------------
         if (ABL & 8) { V = acc; return; }
-        sh[LDS_V + (q) * VS + c] = acc.x;
-        sh[LDS_V + (4 + q) * VS + c] = acc.y;
-        sh[LDS_V + (8 + q) * VS + c] = acc.z;
-        sh[LDS_V + (12 + q) * VS + c] = acc.w;
+        sh[KP_LDS_V + (q) * KP_VS + c] = acc.x;
+        sh[KP_LDS_V + (4 + q) * KP_VS + c] = acc.y;
+        sh[KP_LDS_V + (8 + q) * KP_VS + c] = acc.z;
+        sh[KP_LDS_V + (12 + q) * KP_VS + c] = acc.w;
         __syncthreads();
-        V.x = 0.5 * (acc.x + sh[LDS_V + c * VS + q]);
-        V.y = 0.5 * (acc.y + sh[LDS_V + c * VS + 4 + q]);
-        V.z = 0.5 * (acc.z + sh[LDS_V + c * VS + 8 + q]);
-        V.w = 0.5 * (acc.w + sh[LDS_V + c * VS + 12 + q]);
-        if (lane_nn) set_reg<REG_NN>(V, 0.0);      // element (n,n) carries nothing: keep it at zero
+        V.x = 0.5 * (acc.x + sh[KP_LDS_V + c * KP_VS + q]);
+        V.y = 0.5 * (acc.y + sh[KP_LDS_V + c * KP_VS + 4 + q]);
+        V.z = 0.5 * (acc.z + sh[KP_LDS_V + c * KP_VS + 8 + q]);
+        V.w = 0.5 * (acc.w + sh[KP_LDS_V + c * KP_VS + 12 + q]);
+        if (lane_nn) kp_set_reg<REG_NN>(V, 0.0);      // element (n,n) carries nothing: keep it at zero
         __syncthreads();
     };
     // (one exit per pair, at its end: an exit between the two steps makes the compiler carry the tile sets through copies at

@@ -31,34 +31,6 @@
 #endif
 namespace kpilqr {
 
-typedef unsigned int u32x2t __attribute__((ext_vector_type(2)));
-#define MFMA(a, b, c) __builtin_amdgcn_mfma_f64_16x16x4f64((a), (b), (c), 0, 0, 0)
-#define OOBT 0x7ffffff0
-#define TILE 256
-#define TPAD 272                                     // 16 x 17: padded row-major tile (transposed reads without bank conflicts)
-
-__device__ __forceinline__ double tbld(__amdgpu_buffer_rsrc_t r, int byte_off)
-{
-    return __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(r, byte_off, 0, 0));
-}
-__device__ __forceinline__ d4 lds_tile(const double *t, int lane)
-{
-    d4 v; v.x = t[lane]; v.y = t[64 + lane]; v.z = t[128 + lane]; v.w = t[192 + lane];
-    return v;
-}
-__device__ __forceinline__ void lds_store(double *t, int lane, const d4 &v)
-{
-    t[lane] = v.x; t[64 + lane] = v.y; t[128 + lane] = v.z; t[192 + lane] = v.w;
-}
-// acc += Y'X over `nc` 4-row chunks (nc is wave-uniform)
-__device__ __forceinline__ d4 Pn(const d4 &Y, const d4 &X, d4 acc, int nc)
-{
-    acc = MFMA(Y.x, X.x, acc);
-    if (nc > 1) acc = MFMA(Y.y, X.y, acc);
-    if (nc > 2) acc = MFMA(Y.z, X.z, acc);
-    if (nc > 3) acc = MFMA(Y.w, X.w, acc);
-    return acc;
-}
 // k-th tile of a contraction over NT row tiles: every tile but the last is full (4 chunks, straight-line code so
 // the LDS reads of the following tiles are issued ahead of the MFMAs); only the last tile is cut to the chunks
 // that hold rows of z (ncl, wave-uniform).
@@ -66,76 +38,15 @@ template <int NT>
 __device__ __forceinline__ d4 Pk(int k, const d4 &Y, const d4 &X, d4 acc, int ncl)
 {
     if (k < NT - 1) {
-        acc = MFMA(Y.x, X.x, acc); acc = MFMA(Y.y, X.y, acc); acc = MFMA(Y.z, X.z, acc); acc = MFMA(Y.w, X.w, acc);
+        acc = KP_MFMA(Y.x, X.x, acc); acc = KP_MFMA(Y.y, X.y, acc); acc = KP_MFMA(Y.z, X.z, acc); acc = KP_MFMA(Y.w, X.w, acc);
         return acc;
     }
-    return Pn(Y, X, acc, ncl);
+    return kp_Pn(Y, X, acc, ncl);
 }
 
 // ---------------------------------------------------------------------------------------------
-// Backward pass.  z = [dx; 1] has nz = n+1 entries covered by NT row tiles.
-// Tile loaders (bounds-checked: structural zeros come back as 0).
-struct TileSrc { int n, m; int off_A, off_B, off_lxx, off_lx, off_luu, off_lu; };
-
-// (register r of a tile in the accumulator layout: element (16 ti + 4 r + q, 16 tj + c); the *1 loaders fetch one register, so that
-// a sweep can spread its requests under its products)
-__device__ __forceinline__ double ld_Lzz1(__amdgpu_buffer_rsrc_t rs, const TileSrc &S, int ti, int tj, int r, int q, int c)
-{
-    const int row = 16 * ti + 4 * r + q, col = 16 * tj + c, n = S.n;
-    const int off = (row < n && col < n) ? 8 * (S.off_lxx + row * n + col)
-                  : (col == n && row < n) ? 8 * (S.off_lx + row)
-                  : (row == n && col < n) ? 8 * (S.off_lx + col) : OOBT;
-    return tbld(rs, off);
-}
-__device__ __forceinline__ double ld_Fz1(__amdgpu_buffer_rsrc_t rs, const TileSrc &S, int ti, int tj, int r, int q, int c)
-{
-    const int row = 16 * ti + 4 * r + q, col = 16 * tj + c, n = S.n;
-    return tbld(rs, (row < n && col < n) ? 8 * (S.off_A + col * n + row) : OOBT);
-}
-__device__ __forceinline__ double ld_Fu1(__amdgpu_buffer_rsrc_t rs, const TileSrc &S, int ti, int r, int q, int c)
-{
-    const int row = 16 * ti + 4 * r + q;
-    return tbld(rs, (row < S.n && c < S.m) ? 8 * (S.off_B + c * S.n + row) : OOBT);
-}
-__device__ __forceinline__ double ld_Luz1(__amdgpu_buffer_rsrc_t rs, const TileSrc &S, int tj, int r, int q, int c)
-{
-    const int row = 4 * r + q, col = 16 * tj + c;
-    return tbld(rs, (row < S.m && col == S.n) ? 8 * (S.off_lu + row) : OOBT);
-}
-__device__ __forceinline__ double ld_Luu1(__amdgpu_buffer_rsrc_t rs, const TileSrc &S, int r, int q, int c)
-{
-    const int row = 4 * r + q;
-    return tbld(rs, (row < S.m && c < S.m) ? 8 * (S.off_luu + row * S.m + c) : OOBT);
-}
-__device__ __forceinline__ d4 ld_Lzz(__amdgpu_buffer_rsrc_t rs, const TileSrc &S, int ti, int tj, int q, int c)
-{
-    d4 o = {ld_Lzz1(rs, S, ti, tj, 0, q, c), ld_Lzz1(rs, S, ti, tj, 1, q, c), ld_Lzz1(rs, S, ti, tj, 2, q, c), ld_Lzz1(rs, S, ti, tj, 3, q, c)};
-    return o;
-}
-__device__ __forceinline__ d4 ld_Fz(__amdgpu_buffer_rsrc_t rs, const TileSrc &S, int ti, int tj, int q, int c)
-{
-    d4 o = {ld_Fz1(rs, S, ti, tj, 0, q, c), ld_Fz1(rs, S, ti, tj, 1, q, c), ld_Fz1(rs, S, ti, tj, 2, q, c), ld_Fz1(rs, S, ti, tj, 3, q, c)};
-    return o;
-}
-__device__ __forceinline__ d4 ld_Fu(__amdgpu_buffer_rsrc_t rs, const TileSrc &S, int ti, int q, int c)
-{
-    d4 o = {ld_Fu1(rs, S, ti, 0, q, c), ld_Fu1(rs, S, ti, 1, q, c), ld_Fu1(rs, S, ti, 2, q, c), ld_Fu1(rs, S, ti, 3, q, c)};
-    return o;
-}
-__device__ __forceinline__ d4 ld_Luz(__amdgpu_buffer_rsrc_t rs, const TileSrc &S, int tj, int q, int c)
-{
-    d4 o = {ld_Luz1(rs, S, tj, 0, q, c), ld_Luz1(rs, S, tj, 1, q, c), ld_Luz1(rs, S, tj, 2, q, c), ld_Luz1(rs, S, tj, 3, q, c)};
-    return o;
-}
-__device__ __forceinline__ d4 ld_Luu(__amdgpu_buffer_rsrc_t rs, const TileSrc &S, int q, int c)
-{
-    d4 o = {ld_Luu1(rs, S, 0, q, c), ld_Luu1(rs, S, 1, q, c), ld_Luu1(rs, S, 2, q, c), ld_Luu1(rs, S, 3, q, c)};
-    return o;
-}
-__device__ __forceinline__ void setc(d4 &v, int r, double x)
-{
-    if (r == 0) v.x = x; else if (r == 1) v.y = x; else if (r == 2) v.z = x; else v.w = x;
-}
+// Backward pass.  z = [dx; 1] has nz = n+1 entries covered by NT row tiles; the record tiles come through the loaders of
+// mfma_common.h (kp_ld_*, control tile 0).
 
 // a6 inside the sweeps (KPILQR_FLAG_FUSED on a tiled shape): the cost tiles are formed from the residuals and their
 // Jacobians instead of being read from the records -- Lzz(k,w) = Rz_k' W Rz_w with Rz = [r_x | r] (one column tile each),
@@ -147,19 +58,19 @@ struct CostSrc { const double *r, *r_x, *r_u, *w_run, *w_term; int nr; };
 __device__ __forceinline__ double ld_Rx1(__amdgpu_buffer_rsrc_t rs, int n, int nr, int tj, int r, int q, int c)
 {
     const int res = 4 * r + q, col = 16 * tj + c;
-    return tbld(rs, (res < nr && col < n) ? 8 * (res * n + col) : OOBT);
+    return kp_bld(rs, (res < nr && col < n) ? 8 * (res * n + col) : KP_OOB);
 }
 // r [nr] in column `cn` of a tile (the homogeneous column n lives in tile n>>4 at column n&15)
 __device__ __forceinline__ double ld_R11(__amdgpu_buffer_rsrc_t rs, int nr, int cn, int r, int q, int c)
 {
     const int res = 4 * r + q;
-    return tbld(rs, (res < nr && c == cn) ? 8 * res : OOBT);
+    return kp_bld(rs, (res < nr && c == cn) ? 8 * res : KP_OOB);
 }
 // element (res, c) of r_u [nr][m]
 __device__ __forceinline__ double ld_Ru1(__amdgpu_buffer_rsrc_t rs, int m, int nr, int r, int q, int c)
 {
     const int res = 4 * r + q;
-    return tbld(rs, (res < nr && c < m) ? 8 * (res * m + c) : OOBT);
+    return kp_bld(rs, (res < nr && c < m) ? 8 * (res * m + c) : KP_OOB);
 }
 __device__ __forceinline__ d4 ld_Rx(__amdgpu_buffer_rsrc_t rs, int n, int nr, int tj, int q, int c)
 {
@@ -234,14 +145,14 @@ k_backward_tiled_col(RecLayout L, CostSrc CS, int T, const double *__restrict__ 
     const int b = GATED ? kp_block_traj(list, KP_TILED_TRAJ) : KP_TILED_TRAJ;
     const double lam = lambda[b];
     double *bufV = sh;                               // V' (NT x NT tiles, tile (i,j) at i*NT+j)
-    double *bufF = bufV + NZZ * TILE;                // Fz
-    double *bufT = bufF + NZZ * TILE;                // unsymmetrised V' for the transpose: row-major tiles, row stride 17
-    double *bufFu = bufT + NZZ * TPAD;               // NT
-    double *bufQuz = bufFu + NT * TILE;              // NT
-    double *bufX = bufQuz + NT * TILE;               // NT
-    double *bufG = bufX + NT * TILE;                 // NT
-    double *bufQp = bufG + NT * TILE;                // NT: per-wave partials of Fu'Tu
-    double *sQ = bufQp + NT * TILE + w * TILE;       // NT: this wave's image of Quu + lambda I
+    double *bufF = bufV + NZZ * KP_TILE;                // Fz
+    double *bufT = bufF + NZZ * KP_TILE;                // unsymmetrised V' for the transpose: row-major tiles, row stride 17
+    double *bufFu = bufT + NZZ * KP_TPAD;               // NT
+    double *bufQuz = bufFu + NT * KP_TILE;              // NT
+    double *bufX = bufQuz + NT * KP_TILE;               // NT
+    double *bufG = bufX + NT * KP_TILE;                 // NT
+    double *bufQp = bufG + NT * KP_TILE;                // NT: per-wave partials of Fu'Tu
+    double *sQ = bufQp + NT * KP_TILE + w * KP_TILE;       // NT: this wave's image of Quu + lambda I
     double *sRow = bufT;                             // slow-path work area (phase D: bufT is free outside phase EF)
     // tiles this wave owns: ((w + d) mod NT, w), d < ND (see the header); `red`: the antipodal tile of a wave w >= NT/2 is formed
     // (same code in every wave) and dropped into a dummy area
@@ -250,12 +161,12 @@ k_backward_tiled_col(RecLayout L, CostSrc CS, int T, const double *__restrict__ 
 #pragma unroll
     for (int d = 0; d < ND; d++) ti[d] = (w + d) % NT;
     const bool red_last = (NT % 2 == 0) && w >= NT / 2;
-    double *scr = bufT + w * TPAD;                   // private padded scratch tile for the wave-local transposes
-    double *dummy = bufT + NT * TPAD;                // two tiles nobody reads
+    double *scr = bufT + w * KP_TPAD;                   // private padded scratch tile for the wave-local transposes
+    double *dummy = bufT + NT * KP_TPAD;                // two tiles nobody reads
     auto nchunk = [&](int kt) { const int rows = nz - 16 * kt; return rows >= 16 ? 4 : (rows + 3) / 4; };
     const int ncl = nchunk(NT - 1);
     const int ncw = (w < NT - 1) ? 4 : ncl;          // chunks of row tile w
-    TileSrc S = {n, m, L.off_A, L.off_B, L.off_lxx, L.off_lx, L.off_luu, L.off_lu};
+    KpTileSrc S = {n, m, L.off_A, L.off_B, L.off_lxx, L.off_lx, L.off_luu, L.off_lu};
 
     const double *R0 = rec + (size_t)b * T * L.stride;
     const int rec_bytes = L.rec * 8; (void)rec_bytes;
@@ -273,7 +184,7 @@ k_backward_tiled_col(RecLayout L, CostSrc CS, int T, const double *__restrict__ 
     // source tiles of the current step (column w): Fz(k,w), Lzz(k,w), Fu(w), Luz(w), Luu -- with A6 the cost tiles are
     // formed from residual tiles instead: pL[k] holds Rx_k (r_x rows, column tile k), pLuz the r column, pLuu Ru
     d4 pF[NT], pL[ND], pFu, pLuz, pLuu;
-    auto rsrc_of = [&](int t) { return __builtin_amdgcn_make_buffer_rsrc((void *)(R0 + (size_t)t * L.stride), 0, rec_bytes, 0x00020000); };
+    auto rsrc_of = [&](int t) { return kp_rsrc(R0 + (size_t)t * L.stride, rec_bytes); };
     const int nr = CS.nr, ncr = (nr + 3) >> 2;
     const double *rb = CS.r + (size_t)b * (T + 1) * nr, *rxb = CS.r_x + (size_t)b * (T + 1) * nr * n,
                  *rub = CS.r_u + (size_t)b * (T + 1) * nr * m;
@@ -289,6 +200,8 @@ k_backward_tiled_col(RecLayout L, CostSrc CS, int T, const double *__restrict__ 
         W2run.x = a[0]; W2run.y = a[1]; W2run.z = a[2]; W2run.w = a[3];
         W2term.x = e[0]; W2term.y = e[1]; W2term.z = e[2]; W2term.w = e[3];
     }
+    // (the descriptors of the a6 sources stay spelled out, here and in cost_rsrc: through kp_rsrc the NT = 4 spread kernels of M = 7, 8
+    // come out with other instructions)
     auto load_cost = [&](int t, bool ok) {            // the cost sources of step t (zero-size descriptors when !ok)
         if (A6) {
             const size_t tt = ok ? t : 0;
@@ -300,15 +213,15 @@ k_backward_tiled_col(RecLayout L, CostSrc CS, int T, const double *__restrict__ 
             pLuz = ld_R1(rR, nr, cn, q, c);
             pLuu = ld_Ru(rU, m, nr, q, c);
         } else {
-            __amdgpu_buffer_rsrc_t rs = ok ? rsrc_of(t) : __builtin_amdgcn_make_buffer_rsrc((void *)R0, 0, 0, 0x00020000);
+            __amdgpu_buffer_rsrc_t rs = ok ? rsrc_of(t) : kp_rsrc(R0, 0);
 #pragma unroll
-            for (int d = 0; d < ND; d++) pL[d] = ld_Lzz(rs, S, ti[d], w, q, c);
-            pLuz = ld_Luz(rs, S, w, q, c); pLuu = ld_Luu(rs, S, q, c);
+            for (int d = 0; d < ND; d++) pL[d] = kp_ld_Lzz(rs, S, ti[d], w, q, c);
+            pLuz = kp_ld_Luz(rs, S, 0, w, q, c); pLuu = kp_ld_Luu(rs, S, 0, 0, q, c);
         }
     };
     // SPREAD: the same requests one register at a time -- request (k, r) of the Qzz loop: register r of pL[k] (k < ND) and, at the
     // last k, of pLuz and pLuu; `rc`: the descriptors of the step (cost_rsrc)
-    __amdgpu_buffer_rsrc_t rc0 = __builtin_amdgcn_make_buffer_rsrc((void *)R0, 0, 0, 0x00020000), rc1 = rc0, rc2 = rc0;
+    __amdgpu_buffer_rsrc_t rc0 = kp_rsrc(R0, 0), rc1 = rc0, rc2 = rc0;
     auto cost_rsrc = [&](int t, bool ok) {
         if (A6) {
             const size_t tt = ok ? t : 0;
@@ -316,16 +229,16 @@ k_backward_tiled_col(RecLayout L, CostSrc CS, int T, const double *__restrict__ 
             rc1 = __builtin_amdgcn_make_buffer_rsrc((void *)(rb + tt * nr), 0, ok ? nr * 8 : 0, 0x00020000);
             rc2 = __builtin_amdgcn_make_buffer_rsrc((void *)(rub + tt * nr * m), 0, ok ? nr * m * 8 : 0, 0x00020000);
         } else {
-            rc0 = ok ? rsrc_of(t) : __builtin_amdgcn_make_buffer_rsrc((void *)R0, 0, 0, 0x00020000);
+            rc0 = ok ? rsrc_of(t) : kp_rsrc(R0, 0);
         }
     };
     auto cost_req = [&](int k, int r) {
         if (A6) {
-            if (k < ND) setc(pL[k], r, ld_Rx1(rc0, n, nr, ti[k], r, q, c));
-            if (k == NT - 1) { setc(pLuz, r, ld_R11(rc1, nr, cn, r, q, c)); setc(pLuu, r, ld_Ru1(rc2, m, nr, r, q, c)); }
+            if (k < ND) kp_set_reg(pL[k], r, ld_Rx1(rc0, n, nr, ti[k], r, q, c));
+            if (k == NT - 1) { kp_set_reg(pLuz, r, ld_R11(rc1, nr, cn, r, q, c)); kp_set_reg(pLuu, r, ld_Ru1(rc2, m, nr, r, q, c)); }
         } else {
-            if (k < ND) setc(pL[k], r, ld_Lzz1(rc0, S, ti[k], w, r, q, c));
-            if (k == NT - 1) { setc(pLuz, r, ld_Luz1(rc0, S, w, r, q, c)); setc(pLuu, r, ld_Luu1(rc0, S, r, q, c)); }
+            if (k < ND) kp_set_reg(pL[k], r, kp_ld_Lzz1(rc0, S, ti[k], w, r, q, c));
+            if (k == NT - 1) { kp_set_reg(pLuz, r, kp_ld_Luz1(rc0, S, 0, w, r, q, c)); kp_set_reg(pLuu, r, kp_ld_Luu1(rc0, S, 0, 0, r, q, c)); }
         }
     };
     (void)rc1; (void)rc2;
@@ -339,10 +252,10 @@ k_backward_tiled_col(RecLayout L, CostSrc CS, int T, const double *__restrict__ 
             for (int d = 0; d < ND; d++) {
                 d4 Rzk = pL[d];
                 if (ti[d] == tn) Rzk = Rzk + pLuz;
-                cL[d] = Pn(Rzk, WRz, zero, ncr);
+                cL[d] = kp_Pn(Rzk, WRz, zero, ncr);
             }
-            cLuz = (w == tn) ? Pn(pLuu, pLuz * W2, zero, ncr) : zero;     // l_u in column n
-            cLuu = (w == 0) ? Pn(pLuu, pLuu * W2, zero, ncr) : zero;
+            cLuz = (w == tn) ? kp_Pn(pLuu, pLuz * W2, zero, ncr) : zero;     // l_u in column n
+            cLuu = (w == 0) ? kp_Pn(pLuu, pLuu * W2, zero, ncr) : zero;
         } else {
 #pragma unroll
             for (int d = 0; d < ND; d++) cL[d] = pL[d];
@@ -351,8 +264,8 @@ k_backward_tiled_col(RecLayout L, CostSrc CS, int T, const double *__restrict__ 
     };
     __amdgpu_buffer_rsrc_t rs = rsrc_of(T - 1);
 #pragma unroll
-    for (int k = 0; k < NT; k++) pF[k] = ld_Fz(rs, S, k, w, q, c);
-    pFu = ld_Fu(rs, S, w, q, c);
+    for (int k = 0; k < NT; k++) pF[k] = kp_ld_Fz(rs, S, k, w, q, c);
+    pFu = kp_ld_Fu(rs, S, w, 0, q, c);
     load_cost(T - 1, true);
     // V' <- Lzz(T-1)   (iLQR.cpp:537-539), terminal weights (Optimiser.cpp:208-211)
     // an owned tile of V' goes out as tile (i,w) and, transposed through the private scratch tile (same-wave LDS accesses are
@@ -366,11 +279,11 @@ k_backward_tiled_col(RecLayout L, CostSrc CS, int T, const double *__restrict__ 
         if (d == 0) {
             d4 na = average ? 0.5 * (acc + at) : acc;
             if (average && w == tn) na = na * nn_keep;
-            lds_store(bufV + (w * NT + w) * TILE, lane, na);
+            kp_lds_store(bufV + (w * NT + w) * KP_TILE, lane, na);
         } else {
             const bool red = red_last && d == NT / 2;
-            lds_store(red ? dummy : bufV + (ti[d] * NT + w) * TILE, lane, acc);
-            lds_store(red ? dummy + TILE : bufV + (w * NT + ti[d]) * TILE, lane, at);
+            kp_lds_store(red ? dummy : bufV + (ti[d] * NT + w) * KP_TILE, lane, acc);
+            kp_lds_store(red ? dummy + KP_TILE : bufV + (w * NT + ti[d]) * KP_TILE, lane, at);
         }
     };
     form_cost(W2term);
@@ -396,18 +309,18 @@ k_backward_tiled_col(RecLayout L, CostSrc CS, int T, const double *__restrict__ 
     // Jacobians 36.5 -> 35.9 ms on configs[4]; nothing where the refresh applies)
     auto stage = [&]() {
 #pragma unroll
-        for (int k = 0; k < NT; k++) lds_store(bufF + (k * NT + w) * TILE, lane, pF[k]);
+        for (int k = 0; k < NT; k++) kp_lds_store(bufF + (k * NT + w) * KP_TILE, lane, pF[k]);
         // Fz(n,n) = 1: the loaded element is a structural zero, ONE lane of the wave that owns column n overwrites it (round 5: the
         // add-and-select over every tile of the column was 80 VALU instructions per step)
-        if (w == tn && lane_nn) bufF[(tn * NT + w) * TILE + reg_nn * 64 + lane] = 1.0;
-        lds_store(bufFu + w * TILE, lane, pFu);
+        if (w == tn && lane_nn) bufF[(tn * NT + w) * KP_TILE + reg_nn * 64 + lane] = 1.0;
+        kp_lds_store(bufFu + w * KP_TILE, lane, pFu);
     };
     if constexpr (SPREAD) stage();
     for (int t = T - 1; t >= 0; t--) {
         pd_counter++;
         const bool check_pd = pd_counter >= pd_stride;
         const bool more = t > 0;
-        __amdgpu_buffer_rsrc_t rn = more ? rsrc_of(t - 1) : __builtin_amdgcn_make_buffer_rsrc((void *)R0, 0, 0, 0x00020000);
+        __amdgpu_buffer_rsrc_t rn = more ? rsrc_of(t - 1) : kp_rsrc(R0, 0);
         // ---- A: stage Fz(:,w) (+ the homogeneous 1) and Fu(w) ----------------------------------------------
         CYK(10)
         if constexpr (!SPREAD) stage();
@@ -415,8 +328,8 @@ k_backward_tiled_col(RecLayout L, CostSrc CS, int T, const double *__restrict__ 
         CYK(9)
         if constexpr (!SPREAD) {
 #pragma unroll
-            for (int k = 0; k < NT; k++) pF[k] = ld_Fz(rn, S, k, w, q, c);
-            pFu = ld_Fu(rn, S, w, q, c);
+            for (int k = 0; k < NT; k++) pF[k] = kp_ld_Fz(rn, S, k, w, q, c);
+            pFu = kp_ld_Fu(rn, S, w, 0, q, c);
         }
         __builtin_amdgcn_sched_barrier(0);
         CYK(0)
@@ -428,7 +341,7 @@ k_backward_tiled_col(RecLayout L, CostSrc CS, int T, const double *__restrict__ 
         d4 Fc[NT], Tz[NT], Qzz[ND];
         d4 Quzw = cLuz;                                                     // Quz(w): also kept in registers for the fast path
 #pragma unroll
-        for (int k = 0; k < NT; k++) Fc[k] = lds_tile(bufF + (k * NT + w) * TILE, lane);
+        for (int k = 0; k < NT; k++) Fc[k] = kp_lds_tile(bufF + (k * NT + w) * KP_TILE, lane);
         if constexpr (NCL > 0) {
             // independent accumulation chains issued interleaved (back-to-back MFMAs of ONE chain issue every ~80 cycles, of
             // different chains every 64): Tz(0..NT-1,w) with Tu(w); then Quz(w) with Qzz(0..NT-1,w)
@@ -441,16 +354,16 @@ k_backward_tiled_col(RecLayout L, CostSrc CS, int T, const double *__restrict__ 
             for (int k = 0; k < NT; k++) {
                 d4 Vk[NT];
 #pragma unroll
-                for (int i = 0; i < NT; i++) Vk[i] = lds_tile(bufV + (k * NT + i) * TILE, lane);
-                const d4 Vw = lds_tile(bufV + (k * NT + w) * TILE, lane), Fuk = lds_tile(bufFu + k * TILE, lane);
+                for (int i = 0; i < NT; i++) Vk[i] = kp_lds_tile(bufV + (k * NT + i) * KP_TILE, lane);
+                const d4 Vw = kp_lds_tile(bufV + (k * NT + w) * KP_TILE, lane), Fuk = kp_lds_tile(bufFu + k * KP_TILE, lane);
 #pragma unroll
                 for (int r = 0; r < nck(k); r++) {
 #pragma unroll
-                    for (int i = 0; i < NT; i++) Tz[i] = MFMA(comp(Vk[i], r), comp(Fc[k], r), Tz[i]);
-                    Tu = MFMA(comp(Vw, r), comp(Fuk, r), Tu);
+                    for (int i = 0; i < NT; i++) Tz[i] = KP_MFMA(comp(Vk[i], r), comp(Fc[k], r), Tz[i]);
+                    Tu = KP_MFMA(comp(Vw, r), comp(Fuk, r), Tu);
                     if constexpr (SPREAD) {         // the next step's Fz(k,w), Fu(w): one request under every group of products
-                        setc(pF[k], r, ld_Fz1(rn, S, k, w, r, q, c));
-                        if (r == 0) setc(pFu, k, ld_Fu1(rn, S, w, k, q, c));
+                        kp_set_reg(pF[k], r, kp_ld_Fz1(rn, S, k, w, r, q, c));
+                        if (r == 0) kp_set_reg(pFu, k, kp_ld_Fu1(rn, S, w, 0, k, q, c));
                         __builtin_amdgcn_sched_group_barrier(0x008, NT + 1, 0);
                         if (r == 0) __builtin_amdgcn_sched_group_barrier(0x020, 2, 0);
                         else __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
@@ -458,23 +371,23 @@ k_backward_tiled_col(RecLayout L, CostSrc CS, int T, const double *__restrict__ 
                 }
                 if constexpr (SPREAD) {
 #pragma unroll
-                    for (int r = nck(k); r < 4; r++) setc(pF[k], r, 0.0);       // (chunks of the last row tile that hold no rows of z)
+                    for (int r = nck(k); r < 4; r++) kp_set_reg(pF[k], r, 0.0);       // (chunks of the last row tile that hold no rows of z)
                 }
             }
-            lds_store(bufQp + w * TILE, lane, Pn(lds_tile(bufFu + w * TILE, lane), Tu, (A6 && w == 0) ? cLuu : zero, ncw));
+            kp_lds_store(bufQp + w * KP_TILE, lane, kp_Pn(kp_lds_tile(bufFu + w * KP_TILE, lane), Tu, (A6 && w == 0) ? cLuu : zero, ncw));
 #pragma unroll
             for (int d = 0; d < ND; d++) Qzz[d] = cL[d];
 #pragma unroll
             for (int k = 0; k < NT; k++) {
                 d4 Fk[ND];
 #pragma unroll
-                for (int d = 0; d < ND; d++) Fk[d] = lds_tile(bufF + (k * NT + ti[d]) * TILE, lane);
-                const d4 Fuk = lds_tile(bufFu + k * TILE, lane);
+                for (int d = 0; d < ND; d++) Fk[d] = kp_lds_tile(bufF + (k * NT + ti[d]) * KP_TILE, lane);
+                const d4 Fuk = kp_lds_tile(bufFu + k * KP_TILE, lane);
 #pragma unroll
                 for (int r = 0; r < nck(k); r++) {
-                    Quzw = MFMA(comp(Fuk, r), comp(Tz[k], r), Quzw);
+                    Quzw = KP_MFMA(comp(Fuk, r), comp(Tz[k], r), Quzw);
 #pragma unroll
-                    for (int d = 0; d < ND; d++) Qzz[d] = MFMA(comp(Fk[d], r), comp(Tz[k], r), Qzz[d]);
+                    for (int d = 0; d < ND; d++) Qzz[d] = KP_MFMA(comp(Fk[d], r), comp(Tz[k], r), Qzz[d]);
                     if constexpr (SPREAD) {         // the next step's cost sources (this step's were consumed by form_cost above)
                         cost_req(k, r);
                         __builtin_amdgcn_sched_group_barrier(0x008, ND + 1, 0);
@@ -487,30 +400,30 @@ k_backward_tiled_col(RecLayout L, CostSrc CS, int T, const double *__restrict__ 
                     for (int r = nck(k); r < 4; r++) cost_req(k, r);
                 }
             }
-            lds_store(bufQuz + w * TILE, lane, Quzw);
+            kp_lds_store(bufQuz + w * KP_TILE, lane, Quzw);
         } else {
 #pragma unroll
         for (int i = 0; i < NT; i++) {
             d4 acc = zero;
 #pragma unroll
-            for (int k = 0; k < NT; k++) acc = Pk<NT>(k, lds_tile(bufV + (k * NT + i) * TILE, lane), Fc[k], acc, ncl);
+            for (int k = 0; k < NT; k++) acc = Pk<NT>(k, kp_lds_tile(bufV + (k * NT + i) * KP_TILE, lane), Fc[k], acc, ncl);
             Tz[i] = acc;
         }
         {
             d4 Tu = zero;
 #pragma unroll
-            for (int k = 0; k < NT; k++) Tu = Pk<NT>(k, lds_tile(bufV + (k * NT + w) * TILE, lane), lds_tile(bufFu + k * TILE, lane), Tu, ncl);
+            for (int k = 0; k < NT; k++) Tu = Pk<NT>(k, kp_lds_tile(bufV + (k * NT + w) * KP_TILE, lane), kp_lds_tile(bufFu + k * KP_TILE, lane), Tu, ncl);
             // A6: l_uu rides in wave 0's partial (the other waves never form it)
-            lds_store(bufQp + w * TILE, lane, Pn(lds_tile(bufFu + w * TILE, lane), Tu, (A6 && w == 0) ? cLuu : zero, ncw));
+            kp_lds_store(bufQp + w * KP_TILE, lane, kp_Pn(kp_lds_tile(bufFu + w * KP_TILE, lane), Tu, (A6 && w == 0) ? cLuu : zero, ncw));
         }
 #pragma unroll
-        for (int k = 0; k < NT; k++) Quzw = Pk<NT>(k, lds_tile(bufFu + k * TILE, lane), Tz[k], Quzw, ncl);
-        lds_store(bufQuz + w * TILE, lane, Quzw);
+        for (int k = 0; k < NT; k++) Quzw = Pk<NT>(k, kp_lds_tile(bufFu + k * KP_TILE, lane), Tz[k], Quzw, ncl);
+        kp_lds_store(bufQuz + w * KP_TILE, lane, Quzw);
 #pragma unroll
         for (int d = 0; d < ND; d++) {
             d4 acc = cL[d];
 #pragma unroll
-            for (int k = 0; k < NT; k++) acc = Pk<NT>(k, lds_tile(bufF + (k * NT + ti[d]) * TILE, lane), Tz[k], acc, ncl);
+            for (int k = 0; k < NT; k++) acc = Pk<NT>(k, kp_lds_tile(bufF + (k * NT + ti[d]) * KP_TILE, lane), Tz[k], acc, ncl);
             Qzz[d] = acc;
         }
         }
@@ -525,7 +438,7 @@ k_backward_tiled_col(RecLayout L, CostSrc CS, int T, const double *__restrict__ 
         d4 Quu = A6 ? zero : Luu_t;
         d4 Qp_[NT];
 #pragma unroll
-        for (int k = 0; k < NT; k++) Qp_[k] = lds_tile(bufQp + k * TILE, lane);
+        for (int k = 0; k < NT; k++) Qp_[k] = kp_lds_tile(bufQp + k * KP_TILE, lane);
         if constexpr (SPREAD) stage();
 #pragma unroll
         for (int k = 0; k < NT; k++) Quu = Quu + Qp_[k];
@@ -539,7 +452,7 @@ k_backward_tiled_col(RecLayout L, CostSrc CS, int T, const double *__restrict__ 
         bool done = false;
         const bool tried = haveX && !check_pd;
         if (tried && kp_inverse_refresh<NCU>(Qr, Iu, Xinv, m)) {
-            X = Pn(Xinv, Quzw, zero, NCU);
+            X = kp_Pn(Xinv, Quzw, zero, NCU);
             done = true;
         }
         if (!done) {
@@ -548,7 +461,7 @@ k_backward_tiled_col(RecLayout L, CostSrc CS, int T, const double *__restrict__ 
             // nor tried (round 5: ~750 of a step's 3 600 cycles in phase D on the independently drawn residual Jacobians; data on
             // which the refresh converges never gets here).  Block-uniform like every decision of this phase.
             if (tried) ns_hold = KP_NS_HOLD;
-            lds_store(sQ, lane, Qr);                  // this wave's private image (same-wave LDS accesses are ordered)
+            kp_lds_store(sQ, lane, Qr);                  // this wave's private image (same-wave LDS accesses are ordered)
             auto qel = [&](int i, int j) {
                 if (PAD && (i >= m || j >= m)) return (i == j) ? 1.0 : 0.0;
                 return sQ[(i >> 2) * 64 + j + 16 * (i & 3)];
@@ -567,7 +480,7 @@ k_backward_tiled_col(RecLayout L, CostSrc CS, int T, const double *__restrict__ 
                 }
                 __syncthreads();
             }
-            const double *zt = bufQuz + w * TILE;
+            const double *zt = bufQuz + w * KP_TILE;
             double x[M];
 #pragma unroll
             for (int i = 0; i < M; i++) x[i] = zt[(i >> 2) * 64 + c + 16 * (i & 3)];
@@ -611,16 +524,16 @@ k_backward_tiled_col(RecLayout L, CostSrc CS, int T, const double *__restrict__ 
         d4 Gw;
         {
             const int col = 16 * w + c;
-            lds_store(bufX + w * TILE, lane, X);
-            __amdgpu_buffer_rsrc_t rK = __builtin_amdgcn_make_buffer_rsrc((void *)(Kout + ((size_t)b * T + t) * m * n), 0, m * n * 8, 0x00020000);
-            __amdgpu_buffer_rsrc_t rk = __builtin_amdgcn_make_buffer_rsrc((void *)(kout + ((size_t)b * T + t) * m), 0, m * 8, 0x00020000);
+            kp_lds_store(bufX + w * KP_TILE, lane, X);
+            __amdgpu_buffer_rsrc_t rK = kp_rsrc(Kout + ((size_t)b * T + t) * m * n, m * n * 8);
+            __amdgpu_buffer_rsrc_t rk = kp_rsrc(kout + ((size_t)b * T + t) * m, m * 8);
             const double xv[4] = {X.x, X.y, X.z, X.w};
 #pragma unroll
             for (int r = 0; r < NCU; r++) {
                 const int row = 4 * r + q;
                 const double kv = -xv[r];
-                __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2t, kv), rK, (row < m && col < n) ? 8 * (row + col * m) : OOBT, 0, 0);
-                __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2t, kv), rk, (row < m && col == n) ? 8 * row : OOBT, 0, 0);
+                kp_bst(kv, rK, (row < m && col < n) ? 8 * (row + col * m) : KP_OOB);
+                kp_bst(kv, rk, (row < m && col == n) ? 8 * row : KP_OOB);
             }
             if (col == n) {                           // delta_J -= lambda k'k: lane-local squares, reduced after the sweep
 #pragma unroll
@@ -635,7 +548,7 @@ k_backward_tiled_col(RecLayout L, CostSrc CS, int T, const double *__restrict__ 
         CYK(5)
         // ---- EF: V'(i,w) = Qzz(i,w) + X_i' G_w for the owned tiles, out as tile (i,w) and transposed as tile (w,i) ----------------
 #pragma unroll
-        for (int d = 0; d < ND; d++) publish_V(d, Pn(lds_tile(bufX + ti[d] * TILE, lane), Gw, Qzz[d], NCU), true);
+        for (int d = 0; d < ND; d++) publish_V(d, kp_Pn(kp_lds_tile(bufX + ti[d] * KP_TILE, lane), Gw, Qzz[d], NCU), true);
         CYK(8)
     }
 #ifdef KP_CYC_COL
@@ -650,8 +563,8 @@ k_backward_tiled_col(RecLayout L, CostSrc CS, int T, const double *__restrict__ 
 
 size_t backward_col_lds_bytes(int nt)
 {
-    const size_t tpad = (size_t)nt * nt * TPAD;     // bufT, which also hosts the slow-path work area (832 doubles)
-    return sizeof(double) * ((size_t)(2 * nt * nt + 7 * nt) * TILE + (tpad > 832 ? tpad : 832));
+    const size_t tpad = (size_t)nt * nt * KP_TPAD;     // bufT, which also hosts the slow-path work area (832 doubles)
+    return sizeof(double) * ((size_t)(2 * nt * nt + 7 * nt) * KP_TILE + (tpad > 832 ? tpad : 832));
 }
 
 size_t backward_tiled_lds_bytes(int nt) { return backward_col_lds_bytes(nt); }
@@ -708,17 +621,17 @@ k_backward_tiled_uw(RecLayout L, int T, const double *__restrict__ rec, const do
     const int b = GATED ? kp_block_traj(list, KP_TILED_TRAJ) : KP_TILED_TRAJ;
     const double lam = lambda[b];
     double *bufV = sh;
-    double *bufF = bufV + NZZ * TILE;
-    double *bufT = bufF + NZZ * TILE;
-    double *bufFu = bufT + NZZ * TPAD;
-    double *bufQuz = bufFu + NT * TILE;              // (unused here: Quz(w) stays in its wave)
-    double *bufX = bufQuz + NT * TILE;
-    double *bufG = bufX + NT * TILE;
-    double *sQ = bufG + NT * TILE;                   // the u-wave's image of Quu + lambda I
-    double *bufXi = sQ + TILE;                       // the inverse, u-wave -> column waves
-    int *sFlag = (int *)(bufXi + TILE);              // PD verdict of the step (0 | t+1)
+    double *bufF = bufV + NZZ * KP_TILE;
+    double *bufT = bufF + NZZ * KP_TILE;
+    double *bufFu = bufT + NZZ * KP_TPAD;
+    double *bufQuz = bufFu + NT * KP_TILE;              // (unused here: Quz(w) stays in its wave)
+    double *bufX = bufQuz + NT * KP_TILE;
+    double *bufG = bufX + NT * KP_TILE;
+    double *sQ = bufG + NT * KP_TILE;                   // the u-wave's image of Quu + lambda I
+    double *bufXi = sQ + KP_TILE;                       // the inverse, u-wave -> column waves
+    int *sFlag = (int *)(bufXi + KP_TILE);              // PD verdict of the step (0 | t+1)
     double *sRow = bufT;                             // slow-path work area of the u-wave (phase BC: bufT is free between F and E)
-    TileSrc S = {n, m, L.off_A, L.off_B, L.off_lxx, L.off_lx, L.off_luu, L.off_lu};
+    KpTileSrc S = {n, m, L.off_A, L.off_B, L.off_lxx, L.off_lx, L.off_luu, L.off_lu};
     auto nck = [](int kt) { return kt < NT - 1 ? 4 : NCL; };        // chunks of row tile kt
     auto comp = [](const d4 &v, int r) { return r == 0 ? v.x : r == 1 ? v.y : r == 2 ? v.z : v.w; };
 
@@ -735,8 +648,8 @@ k_backward_tiled_uw(RecLayout L, int T, const double *__restrict__ rec, const do
     double lam2d[4];
 #pragma unroll
     for (int r = 0; r < 4; r++) lam2d[r] = (4 * r + q == c && c < m) ? 2.0 * lam : 0.0;
-    auto rsrc_of = [&](int t) { return __builtin_amdgcn_make_buffer_rsrc((void *)(R0 + (size_t)t * L.stride), 0, rec_bytes, 0x00020000); };
-    auto ld4 = [&](__amdgpu_buffer_rsrc_t rs, const int (&o)[4]) { d4 v = {tbld(rs, o[0]), tbld(rs, o[1]), tbld(rs, o[2]), tbld(rs, o[3])}; return v; };
+    auto rsrc_of = [&](int t) { return kp_rsrc(R0 + (size_t)t * L.stride, rec_bytes); };
+    auto ld4 = [&](__amdgpu_buffer_rsrc_t rs, const int (&o)[4]) { d4 v = {kp_bld(rs, o[0]), kp_bld(rs, o[1]), kp_bld(rs, o[2]), kp_bld(rs, o[3])}; return v; };
     // V'(i,k)' Y(k) summed over the row tiles k, for every output tile i: NT independent accumulation chains issued interleaved.
     // (More, shallower chains -- one per (k,i), halves of Fu'Tu, split products in the refresh -- measured no gain: at one FP64 MFMA
     // per 64 cycles the u-wave's 18 products are issue-bound, not chain-bound; nor did a third-order refresh, with or without the
@@ -748,11 +661,11 @@ k_backward_tiled_uw(RecLayout L, int T, const double *__restrict__ rec, const do
         for (int k = 0; k < NT; k++) {
             d4 Vk[NT];
 #pragma unroll
-            for (int i = 0; i < NT; i++) Vk[i] = lds_tile(bufV + (k * NT + i) * TILE, lane);
+            for (int i = 0; i < NT; i++) Vk[i] = kp_lds_tile(bufV + (k * NT + i) * KP_TILE, lane);
 #pragma unroll
             for (int r = 0; r < nck(k); r++)
 #pragma unroll
-                for (int i = 0; i < NT; i++) Tq[i] = MFMA(comp(Vk[i], r), comp(Y[k], r), Tq[i]);
+                for (int i = 0; i < NT; i++) Tq[i] = KP_MFMA(comp(Vk[i], r), comp(Y[k], r), Tq[i]);
         }
     };
     int pd_counter = 0, fail = 0, ns_hold = 0;
@@ -777,9 +690,9 @@ k_backward_tiled_uw(RecLayout L, int T, const double *__restrict__ rec, const do
 #pragma unroll
             for (int k = 0; k < NT; k++) {
                 const int row = 16 * k + 4 * r + q;
-                oFu[k][r] = (row < n && c < m) ? 8 * (S.off_B + c * n + row) : OOBT;
+                oFu[k][r] = (row < n && c < m) ? 8 * (S.off_B + c * n + row) : KP_OOB;
             }
-            oLuu[r] = (rowu < m && c < m) ? 8 * (S.off_luu + rowu * m + c) : OOBT;
+            oLuu[r] = (rowu < m && c < m) ? 8 * (S.off_luu + rowu * m + c) : KP_OOB;
         }
         d4 pFu[NT], pLuu;
         {
@@ -795,7 +708,7 @@ k_backward_tiled_uw(RecLayout L, int T, const double *__restrict__ rec, const do
         for (int t = T - 1; t >= 0; t--) {
             pd_counter++;
             const bool check_pd = pd_counter >= pd_stride;
-            __amdgpu_buffer_rsrc_t rn = t > 0 ? rsrc_of(t - 1) : __builtin_amdgcn_make_buffer_rsrc((void *)R0, 0, 0, 0x00020000);
+            __amdgpu_buffer_rsrc_t rn = t > 0 ? rsrc_of(t - 1) : kp_rsrc(R0, 0);
             CYC(0)
             __syncthreads();                                       // V' of the step above is complete
             CYC(1)
@@ -808,9 +721,9 @@ k_backward_tiled_uw(RecLayout L, int T, const double *__restrict__ rec, const do
             for (int r = 0; r < 4; r++)
 #pragma unroll
                 for (int i = 0; i < NT; i++) {
-                    if (r < nck(i)) Qp[i] = MFMA(comp(pFu[i], r), comp(Tu[i], r), Qp[i]);
+                    if (r < nck(i)) Qp[i] = KP_MFMA(comp(pFu[i], r), comp(Tu[i], r), Qp[i]);
                     // the next step's Fu, register by register behind its last use (see k_backward_tiled_col)
-                    setc(pFu[i], r, tbld(rn, oFu[i][r]));
+                    kp_set_reg(pFu[i], r, kp_bld(rn, oFu[i][r]));
                     if (r < nck(i)) __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
                     __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
                 }
@@ -843,7 +756,7 @@ k_backward_tiled_uw(RecLayout L, int T, const double *__restrict__ rec, const do
             const bool refreshed = tried && kp_inverse_refresh<NCU>(Qr, Iu, Xinv, m);
             if (tried && !refreshed) ns_hold = KP_NS_HOLD;
             if (!refreshed) {
-                lds_store(sQ, lane, Qr);
+                kp_lds_store(sQ, lane, Qr);
                 auto qel = [&](int i, int j) {
                     if (PAD && (i >= m || j >= m)) return (i == j) ? 1.0 : 0.0;
                     return sQ[(i >> 2) * 64 + j + 16 * (i & 3)];
@@ -880,7 +793,7 @@ k_backward_tiled_uw(RecLayout L, int T, const double *__restrict__ rec, const do
                 Xinv.x = yr[0]; Xinv.y = yr[1]; Xinv.z = yr[2]; Xinv.w = yr[3];
             }
             CYC(8)
-            lds_store(bufXi, lane, Xinv);
+            kp_lds_store(bufXi, lane, Xinv);
             if (lane == 0) sFlag[0] = fail;
             CYC(2)
             __syncthreads();                                       // the inverse and the verdict are out
@@ -900,7 +813,7 @@ k_backward_tiled_uw(RecLayout L, int T, const double *__restrict__ rec, const do
 #pragma unroll
         for (int d = 0; d < ND; d++) ti[d] = (w + d) % NT;
         const bool red_last = (NT % 2 == 0) && w >= NT / 2;
-        double *scr = bufT + w * TPAD, *dummy = bufT + NT * TPAD;
+        double *scr = bufT + w * KP_TPAD, *dummy = bufT + NT * KP_TPAD;
         d4 pF[NT], pL[ND], pFu, pLuz;
         int oF[NT][4], oL[ND][4], oFu[4], oLuz[4];
 #pragma unroll
@@ -909,16 +822,16 @@ k_backward_tiled_uw(RecLayout L, int T, const double *__restrict__ rec, const do
 #pragma unroll
             for (int k = 0; k < NT; k++) {
                 const int row = 16 * k + 4 * r + q;
-                oF[k][r] = (row < n && col < n) ? 8 * (S.off_A + col * n + row) : OOBT;
+                oF[k][r] = (row < n && col < n) ? 8 * (S.off_A + col * n + row) : KP_OOB;
             }
 #pragma unroll
             for (int d = 0; d < ND; d++) {
                 const int row = 16 * ti[d] + 4 * r + q;
                 oL[d][r] = (row < n && col < n) ? 8 * (S.off_lxx + row * n + col)
-                         : (col == n && row < n) ? 8 * (S.off_lx + row) : (row == n && col < n) ? 8 * (S.off_lx + col) : OOBT;
+                         : (col == n && row < n) ? 8 * (S.off_lx + row) : (row == n && col < n) ? 8 * (S.off_lx + col) : KP_OOB;
             }
-            oFu[r] = (rowb < n && c < m) ? 8 * (S.off_B + c * n + rowb) : OOBT;
-            oLuz[r] = (rowu < m && col == n) ? 8 * (S.off_lu + rowu) : OOBT;
+            oFu[r] = (rowb < n && c < m) ? 8 * (S.off_B + c * n + rowb) : KP_OOB;
+            oLuz[r] = (rowu < m && col == n) ? 8 * (S.off_lu + rowu) : KP_OOB;
         }
         auto request = [&](__amdgpu_buffer_rsrc_t rs) {
 #pragma unroll
@@ -945,11 +858,11 @@ k_backward_tiled_uw(RecLayout L, int T, const double *__restrict__ rec, const do
             if (d == 0) {
                 d4 na = average ? 0.5 * (acc + at) : acc;
                 if (average && w == tn) na = na * nn_keep;
-                lds_store(bufV + (w * NT + w) * TILE, lane, na);
+                kp_lds_store(bufV + (w * NT + w) * KP_TILE, lane, na);
             } else {
                 const bool red = red_last && d == NT / 2;
-                lds_store(red ? dummy : bufV + (ti[d] * NT + w) * TILE, lane, acc);
-                lds_store(red ? dummy + TILE : bufV + (w * NT + ti[d]) * TILE, lane, at);
+                kp_lds_store(red ? dummy : bufV + (ti[d] * NT + w) * KP_TILE, lane, acc);
+                kp_lds_store(red ? dummy + KP_TILE : bufV + (w * NT + ti[d]) * KP_TILE, lane, at);
             }
         };
         // V' <- Lzz(T-1)   (iLQR.cpp:537-539)
@@ -959,7 +872,7 @@ k_backward_tiled_uw(RecLayout L, int T, const double *__restrict__ rec, const do
         for (int t = T - 1; t >= 0; t--) {
             pd_counter++;
             const bool check_pd = pd_counter >= pd_stride;
-            __amdgpu_buffer_rsrc_t rn = t > 0 ? rsrc_of(t - 1) : __builtin_amdgcn_make_buffer_rsrc((void *)R0, 0, 0, 0x00020000);
+            __amdgpu_buffer_rsrc_t rn = t > 0 ? rsrc_of(t - 1) : kp_rsrc(R0, 0);
             CYC(0)
             __syncthreads();                                       // V' of the step above is complete
             CYC(1)
@@ -981,23 +894,23 @@ k_backward_tiled_uw(RecLayout L, int T, const double *__restrict__ rec, const do
                 for (int k = 0; k < NT; k++) {
                     d4 Vk[NT];
 #pragma unroll
-                    for (int i = 0; i < NT; i++) Vk[i] = lds_tile(bufV + (k * NT + i) * TILE, lane);
+                    for (int i = 0; i < NT; i++) Vk[i] = kp_lds_tile(bufV + (k * NT + i) * KP_TILE, lane);
 #pragma unroll
                     for (int r = 0; r < 4; r++) {
                         if (r < nck(k)) {
 #pragma unroll
-                            for (int i = 0; i < NT; i++) Tz[i] = MFMA(comp(Vk[i], r), comp(Y[k], r), Tz[i]);
+                            for (int i = 0; i < NT; i++) Tz[i] = KP_MFMA(comp(Vk[i], r), comp(Y[k], r), Tz[i]);
                             __builtin_amdgcn_sched_group_barrier(0x008, NT, 0);
                         }
-                        setc(pF[k], r, tbld(rn, oF[k][r]));
-                        if (k == 0) setc(pFu, r, tbld(rn, oFu[r]));
+                        kp_set_reg(pF[k], r, kp_bld(rn, oF[k][r]));
+                        if (k == 0) kp_set_reg(pFu, r, kp_bld(rn, oFu[r]));
                         if (k == 0) __builtin_amdgcn_sched_group_barrier(0x020, 2, 0);
                         else __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
                     }
                 }
 #pragma unroll
-                for (int k = 0; k < NT; k++) lds_store(bufF + (k * NT + w) * TILE, lane, Y[k]);
-                lds_store(bufFu + w * TILE, lane, Fuw);
+                for (int k = 0; k < NT; k++) kp_lds_store(bufF + (k * NT + w) * KP_TILE, lane, Y[k]);
+                kp_lds_store(bufFu + w * KP_TILE, lane, Fuw);
             }
             __builtin_amdgcn_sched_barrier(0);
             __builtin_amdgcn_sched_barrier(0);
@@ -1015,20 +928,20 @@ k_backward_tiled_uw(RecLayout L, int T, const double *__restrict__ rec, const do
 #pragma unroll
             for (int k = 0; k < NT; k++) {
                 d4 Fk[ND];
-                const d4 Fuk = lds_tile(bufFu + k * TILE, lane);
+                const d4 Fuk = kp_lds_tile(bufFu + k * KP_TILE, lane);
 #pragma unroll
-                for (int d = 0; d < ND; d++) Fk[d] = lds_tile(bufF + (k * NT + ti[d]) * TILE, lane);
+                for (int d = 0; d < ND; d++) Fk[d] = kp_lds_tile(bufF + (k * NT + ti[d]) * KP_TILE, lane);
 #pragma unroll
                 for (int r = 0; r < 4; r++) {
                     if (r < nck(k)) {
-                        Quzw = MFMA(comp(Fuk, r), comp(Tz[k], r), Quzw);
+                        Quzw = KP_MFMA(comp(Fuk, r), comp(Tz[k], r), Quzw);
 #pragma unroll
-                        for (int d = 0; d < ND; d++) Qzz[d] = MFMA(comp(Fk[d], r), comp(Tz[k], r), Qzz[d]);
+                        for (int d = 0; d < ND; d++) Qzz[d] = KP_MFMA(comp(Fk[d], r), comp(Tz[k], r), Qzz[d]);
                         __builtin_amdgcn_sched_group_barrier(0x008, ND + 1, 0);
                     }
                     // request (k, r): register r of pL[k] (k < ND) and, at k = NT-1, of pLuz
-                    if (k < ND) setc(pL[k], r, tbld(rn, oL[k][r]));
-                    if (k == NT - 1) setc(pLuz, r, tbld(rn, oLuz[r]));
+                    if (k < ND) kp_set_reg(pL[k], r, kp_bld(rn, oL[k][r]));
+                    if (k == NT - 1) kp_set_reg(pLuz, r, kp_bld(rn, oLuz[r]));
                     if (k < ND && k == NT - 1) __builtin_amdgcn_sched_group_barrier(0x020, 2, 0);
                     else if (k < ND || k == NT - 1) __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
                 }
@@ -1043,19 +956,19 @@ k_backward_tiled_uw(RecLayout L, int T, const double *__restrict__ rec, const do
             fail = sFlag[0];
             if (fail) break;
             if (check_pd) pd_counter = 0;
-            const d4 X = Pn(lds_tile(bufXi, lane), Quzw, zero, NCU);
+            const d4 X = kp_Pn(kp_lds_tile(bufXi, lane), Quzw, zero, NCU);
             const int col = 16 * w + c;
-            lds_store(bufX + w * TILE, lane, X);
-            __amdgpu_buffer_rsrc_t rK = __builtin_amdgcn_make_buffer_rsrc((void *)pK, 0, m * n * 8, 0x00020000);
-            __amdgpu_buffer_rsrc_t rk = __builtin_amdgcn_make_buffer_rsrc((void *)pk, 0, m * 8, 0x00020000);
+            kp_lds_store(bufX + w * KP_TILE, lane, X);
+            __amdgpu_buffer_rsrc_t rK = kp_rsrc(pK, m * n * 8);
+            __amdgpu_buffer_rsrc_t rk = kp_rsrc(pk, m * 8);
             pK -= (size_t)m * n * 8; pk -= (size_t)m * 8;
             const double xv[4] = {X.x, X.y, X.z, X.w};
 #pragma unroll
             for (int r = 0; r < NCU; r++) {
                 const int row = 4 * r + q;
                 const double kv = -xv[r];
-                __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2t, kv), rK, (row < m && col < n) ? 8 * (row + col * m) : OOBT, 0, 0);
-                __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2t, kv), rk, (row < m && col == n) ? 8 * row : OOBT, 0, 0);
+                kp_bst(kv, rK, (row < m && col < n) ? 8 * (row + col * m) : KP_OOB);
+                kp_bst(kv, rk, (row < m && col == n) ? 8 * row : KP_OOB);
             }
             if (col == n) {                           // delta_J -= lambda k'k: lane-local squares, reduced after the sweep
 #pragma unroll
@@ -1069,7 +982,7 @@ k_backward_tiled_uw(RecLayout L, int T, const double *__restrict__ rec, const do
             __syncthreads();
             // ---- EF: V'(i,w) = Qzz(i,w) + X_i' G_w for the owned tiles, out as tile (i,w) and transposed as tile (w,i) ------------
 #pragma unroll
-            for (int d = 0; d < ND; d++) publish_V(d, Pn(lds_tile(bufX + ti[d] * TILE, lane), Gw, Qzz[d], NCU), true);
+            for (int d = 0; d < ND; d++) publish_V(d, kp_Pn(kp_lds_tile(bufX + ti[d] * KP_TILE, lane), Gw, Qzz[d], NCU), true);
             CYC(5)
         }
     }
@@ -1171,10 +1084,10 @@ k_forward_tiled(RecLayout L, CostSrc CS, int T, int n_alpha, const double *__res
                 const int *__restrict__ list)
 {
     extern __shared__ __attribute__((aligned(16))) double fsh[];
-    double (*zbuf)[NT * TILE] = (double (*)[NT * TILE])fsh;                 // [2][NT * TILE]
-    double *upart = fsh + 2 * NT * TILE;                                     // per-wave partials of K dx + alpha k
-    double *red = upart + NT * TILE;                                         // [NT * 64]
-    double *jpart = red + NT * 64;                                           // A6: per-wave partials of r_x dx  [NT * TILE]
+    double (*zbuf)[NT * KP_TILE] = (double (*)[NT * KP_TILE])fsh;                 // [2][NT * KP_TILE]
+    double *upart = fsh + 2 * NT * KP_TILE;                                     // per-wave partials of K dx + alpha k
+    double *red = upart + NT * KP_TILE;                                         // [NT * 64]
+    double *jpart = red + NT * 64;                                           // A6: per-wave partials of r_x dx  [NT * KP_TILE]
     const int n = L.n, m = L.m, nz2 = n + 2;
     const int lane = threadIdx.x & 63, c = lane & 15, q = lane >> 4;
     const int wi = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // this wave's row tile (wave-uniform)
@@ -1184,7 +1097,7 @@ k_forward_tiled(RecLayout L, CostSrc CS, int T, int n_alpha, const double *__res
     const int ncl = nchunk(NT - 1);
     const int ncw = nchunk(wi);
 
-    // per-lane source byte offsets (OOBT = structural zero); p = contraction (state) index, o = output index
+    // per-lane source byte offsets (KP_OOB = structural zero); p = contraction (state) index, o = output index
     int oKw[4], okw[4], oA[NT][4], oLc[NT][4], oB[4], oLuu[4], olu[4], oub[4];
     double oneT[4], lo[4], hi[4];                    // identity entries of Ya: rows n, n+1 live in row tile tnz only
     const int tnz = n >> 4;
@@ -1194,10 +1107,10 @@ k_forward_tiled(RecLayout L, CostSrc CS, int T, int n_alpha, const double *__res
 #pragma unroll
         for (int r = 0; r < 4; r++) {
             const int pp = 16 * k + 4 * r + q;
-            oA[k][r] = (pp < n && o < n) ? 8 * L.a(o, pp) : OOBT;
+            oA[k][r] = (pp < n && o < n) ? 8 * L.a(o, pp) : KP_OOB;
             oLc[k][r] = (pp < n && o < n) ? 8 * (L.off_lxx + pp * n + o)
                       : (pp == n + 1 && o < n) ? 8 * (L.off_lx + o)
-                      : (o == n + 1 && pp < n) ? 8 * (L.off_lx + pp) : OOBT;
+                      : (o == n + 1 && pp < n) ? 8 * (L.off_lx + pp) : KP_OOB;
         }
 #pragma unroll
     for (int r = 0; r < 4; r++) {
@@ -1205,12 +1118,12 @@ k_forward_tiled(RecLayout L, CostSrc CS, int T, int n_alpha, const double *__res
         const int pt = 16 * tnz + row;
         oneT[r] = ((pt == n && o == n) || (pt == n + 1 && o == n + 1)) ? 1.0 : 0.0;
         const int pw = 16 * wi + row;                                   // this wave's slice of the state index
-        oKw[r] = (pw < n && c < m) ? 8 * (pw * m + c) : OOBT;
-        okw[r] = (pw == n && c < m) ? 8 * c : OOBT;
-        oB[r] = (row < m && o < n) ? 8 * L.b(o, row) : OOBT;
-        oLuu[r] = (row < m && c < m) ? 8 * (L.off_luu + row * m + c) : OOBT;
-        olu[r] = (row < m) ? 8 * (L.off_lu + row) : OOBT;
-        oub[r] = (row < m) ? 8 * row : OOBT;
+        oKw[r] = (pw < n && c < m) ? 8 * (pw * m + c) : KP_OOB;
+        okw[r] = (pw == n && c < m) ? 8 * c : KP_OOB;
+        oB[r] = (row < m && o < n) ? 8 * L.b(o, row) : KP_OOB;
+        oLuu[r] = (row < m && c < m) ? 8 * (L.off_luu + row * m + c) : KP_OOB;
+        olu[r] = (row < m) ? 8 * (L.off_lu + row) : KP_OOB;
+        oub[r] = (row < m) ? 8 * row : KP_OOB;
         lo[r] = (row < m) ? ctrl_lim[2 * row] : -1.0e300;
         hi[r] = (row < m) ? ctrl_lim[2 * row + 1] : 1.0e300;
     }
@@ -1224,9 +1137,9 @@ k_forward_tiled(RecLayout L, CostSrc CS, int T, int n_alpha, const double *__res
     for (int r = 0; r < 4; r++) {
         const int row = 4 * r + q;
         const int pw = 16 * wi + row;
-        oRxT[r] = (A6 && pw < n && c < nr) ? 8 * (c * n + pw) : OOBT;          // RxT(p = pw, k = c) = r_x[k][p]
-        oRuT[r] = (A6 && row < m && c < nr) ? 8 * (c * m + row) : OOBT;        // RuT(p = row, k = c) = r_u[k][p]
-        oRr[r] = (A6 && row < nr) ? 8 * row : OOBT;
+        oRxT[r] = (A6 && pw < n && c < nr) ? 8 * (c * n + pw) : KP_OOB;          // RxT(p = pw, k = c) = r_x[k][p]
+        oRuT[r] = (A6 && row < m && c < nr) ? 8 * (c * m + row) : KP_OOB;        // RuT(p = row, k = c) = r_u[k][p]
+        oRr[r] = (A6 && row < nr) ? 8 * row : KP_OOB;
         wrun[r] = (A6 && row < nr) ? CS.w_run[row] : 0.0;
         wterm[r] = (A6 && row < nr) ? CS.w_term[row] : 0.0;
     }
@@ -1242,7 +1155,7 @@ k_forward_tiled(RecLayout L, CostSrc CS, int T, int n_alpha, const double *__res
             zr[r] = (row == n) ? my_alpha : (row == n + 1) ? 1.0 : 0.0;
         }
         Zi.x = zr[0]; Zi.y = zr[1]; Zi.z = zr[2]; Zi.w = zr[3];
-        lds_store(zbuf[0] + wi * TILE, lane, Zi);
+        kp_lds_store(zbuf[0] + wi * KP_TILE, lane, Zi);
     }
     const d4 zero = {0.0, 0.0, 0.0, 0.0};
     double partial = 0.0;
@@ -1250,16 +1163,16 @@ k_forward_tiled(RecLayout L, CostSrc CS, int T, int n_alpha, const double *__res
     struct Tiles { d4 Ykw, Ya[NT], Lc[NT], Yb, Luu, lu, ub; double kv; };        // A6: Lc[0] = RxT (own slice), Luu = RuT, lu = r; kv: k' (FSPREAD)
     const int rec_bytes = L.rec * 8; (void)rec_bytes;
     auto ld4 = [&](__amdgpu_buffer_rsrc_t rs, const int *off) -> d4 {
-        d4 v; v.x = tbld(rs, off[0]); v.y = tbld(rs, off[1]); v.z = tbld(rs, off[2]); v.w = tbld(rs, off[3]);
+        d4 v; v.x = kp_bld(rs, off[0]); v.y = kp_bld(rs, off[1]); v.z = kp_bld(rs, off[2]); v.w = kp_bld(rs, off[3]);
         return v;
     };
     auto rs_of = [&](const double *base, size_t step_elems, int t, int bytes) {
         const bool ok = t < T;
-        return __builtin_amdgcn_make_buffer_rsrc((void *)(base + ((size_t)b * T + (ok ? t : 0)) * step_elems), 0, ok ? bytes : 0, 0x00020000);
+        return kp_rsrc(base + ((size_t)b * T + (ok ? t : 0)) * step_elems, ok ? bytes : 0);
     };
     auto rs_res = [&](const double *base_b, size_t step_elems, int t, int bytes) {        // residual arrays: base already at trajectory b
         const bool ok = t < T;
-        return __builtin_amdgcn_make_buffer_rsrc((void *)(base_b + (size_t)(ok ? t : 0) * step_elems), 0, ok ? bytes : 0, 0x00020000);
+        return kp_rsrc(base_b + (size_t)(ok ? t : 0) * step_elems, ok ? bytes : 0);
     };
     // Single-buffered tiles: each group is re-requested for step t+1 right behind its last use in step t.
     // Every wave forms only ITS slice of the control law, P([K' ; k'] rows of tile wi, Z_wi) (4 MFMAs instead of
@@ -1276,7 +1189,7 @@ k_forward_tiled(RecLayout L, CostSrc CS, int T, int n_alpha, const double *__res
     // ONE request (the lanes of row n) and joins the gain operand at its use instead of behind the request
     constexpr bool FSPREAD = NCL > 0 && (A6 || NT > 2);       // (two tiles, materialised: 3.54 against 3.37 ms on pushing -- stays with the blocks)
     const bool k_here = tnz == wi;
-    const int okn = (k_here && q == (n & 3) && c < m) ? 8 * c : OOBT;
+    const int okn = (k_here && q == (n & 3) && c < m) ? 8 * c : KP_OOB;
     double kmask[4];
 #pragma unroll
     for (int r = 0; r < 4; r++) kmask[r] = (r == ((n & 15) >> 2)) ? 1.0 : 0.0;
@@ -1288,7 +1201,7 @@ k_forward_tiled(RecLayout L, CostSrc CS, int T, int n_alpha, const double *__res
         __amdgpu_buffer_rsrc_t rR = rs_of(rec, L.stride, s0, rec_bytes), rK = rs_of(Kin, (size_t)m * n, s0, m * n * 8);
         __amdgpu_buffer_rsrc_t rk = rs_of(kin, m, s0, m * 8), ru = rs_of(u_nom, m, s0, m * 8);
         cur.kv = 0.0;
-        if constexpr (FSPREAD) { cur.Ykw = ld4(rK, oKw); cur.kv = tbld(rk, okn); }
+        if constexpr (FSPREAD) { cur.Ykw = ld4(rK, oKw); cur.kv = kp_bld(rk, okn); }
         else cur.Ykw = ld4(rK, oKw) + ld4(rk, okw);
 #pragma unroll
         for (int k = 0; k < NT; k++) { cur.Ya[k] = ld4(rR, oA[k]); if (!A6) cur.Lc[k] = ld4(rR, oLc[k]); }
@@ -1329,18 +1242,18 @@ k_forward_tiled(RecLayout L, CostSrc CS, int T, int n_alpha, const double *__res
 #pragma unroll
             for (int r = 0; r < 4; r++) {
                 if (r < ncw) {                                // (wave-uniform: only the last row tile is short)
-                    Us = MFMA(comp(Yk, r), comp(Zi, r), Us);
-                    if (A6) Js = MFMA(comp(cur.Lc[0], r), comp(Zi, r), Js);
+                    Us = KP_MFMA(comp(Yk, r), comp(Zi, r), Us);
+                    if (A6) Js = KP_MFMA(comp(cur.Lc[0], r), comp(Zi, r), Js);
                 }
-                setc(cur.Ykw, r, tbld(rK, oKw[r]));
-                if (A6) setc(cur.Lc[0], r, tbld(rX, oRxT[r]));
+                kp_set_reg(cur.Ykw, r, kp_bld(rK, oKw[r]));
+                if (A6) kp_set_reg(cur.Lc[0], r, kp_bld(rX, oRxT[r]));
             }
-            cur.kv = tbld(rk, okn);
-            lds_store(upart + wi * TILE, lane, Us);
-            if (A6) lds_store(jpart + wi * TILE, lane, Js);
+            cur.kv = kp_bld(rk, okn);
+            kp_lds_store(upart + wi * KP_TILE, lane, Us);
+            if (A6) kp_lds_store(jpart + wi * KP_TILE, lane, Js);
         } else {
-        lds_store(upart + wi * TILE, lane, Pn(cur.Ykw, Zi, zero, ncw));
-        if (A6) lds_store(jpart + wi * TILE, lane, Pn(cur.Lc[0], Zi, zero, ncw));        // this wave's slice of r_x dx
+        kp_lds_store(upart + wi * KP_TILE, lane, kp_Pn(cur.Ykw, Zi, zero, ncw));
+        if (A6) kp_lds_store(jpart + wi * KP_TILE, lane, kp_Pn(cur.Lc[0], Zi, zero, ncw));        // this wave's slice of r_x dx
         __builtin_amdgcn_sched_barrier(0);
         cur.Ykw = ld4(rK, oKw) + ld4(rk, okw);
         if (A6) cur.Lc[0] = ld4(rs_res(rxb, (size_t)nr * n, tq, nr * n * 8), oRxT);
@@ -1353,10 +1266,10 @@ k_forward_tiled(RecLayout L, CostSrc CS, int T, int n_alpha, const double *__res
         const d4 ub = cur.ub;
         d4 U = ub;
 #pragma unroll
-        for (int k = 0; k < NT; k++) U = U + lds_tile(upart + k * TILE, lane);
+        for (int k = 0; k < NT; k++) U = U + kp_lds_tile(upart + k * KP_TILE, lane);
         d4 Zk[NT];
 #pragma unroll
-        for (int k = 0; k < NT; k++) Zk[k] = lds_tile(zc + k * TILE, lane);
+        for (int k = 0; k < NT; k++) Zk[k] = kp_lds_tile(zc + k * KP_TILE, lane);
         __builtin_amdgcn_sched_barrier(0);
         cur.ub = ld4(ru, oub);
         __builtin_amdgcn_sched_barrier(0);
@@ -1378,8 +1291,8 @@ k_forward_tiled(RecLayout L, CostSrc CS, int T, int n_alpha, const double *__res
             if (A6) {
                 d4 Jx = zero;
 #pragma unroll
-                for (int k = 0; k < NT; k++) Jx = Jx + lds_tile(jpart + k * TILE, lane);
-                const d4 Ju = Pn(cur.Luu, dU, zero, ncu);
+                for (int k = 0; k < NT; k++) Jx = Jx + kp_lds_tile(jpart + k * KP_TILE, lane);
+                const d4 Ju = kp_Pn(cur.Luu, dU, zero, ncu);
                 const d4 r2 = cur.lu + cur.lu;
                 const bool last = (t == T - 1);                        // terminal weights (Optimiser.cpp:209-211)
                 const double w0 = last ? wterm[0] : wrun[0], w1 = last ? wterm[1] : wrun[1];
@@ -1391,7 +1304,7 @@ k_forward_tiled(RecLayout L, CostSrc CS, int T, int n_alpha, const double *__res
                 cur.lu = ld4(rs_res(rb, nr, tq, nr * 8), oRr);
                 __builtin_amdgcn_sched_barrier(0);
             } else {
-            const d4 Wu = Pn(cur.Luu, dU, zero, ncu);
+            const d4 Wu = kp_Pn(cur.Luu, dU, zero, ncu);
             partial += dU.x * (0.5 * Wu.x + cur.lu.x) + dU.y * (0.5 * Wu.y + cur.lu.y)
                      + dU.z * (0.5 * Wu.z + cur.lu.z) + dU.w * (0.5 * Wu.w + cur.lu.w);
             __builtin_amdgcn_sched_barrier(0);
@@ -1411,24 +1324,24 @@ k_forward_tiled(RecLayout L, CostSrc CS, int T, int n_alpha, const double *__res
                 if (k == tnz) { Ya.x += oneT[0]; Ya.y += oneT[1]; Ya.z += oneT[2]; Ya.w += oneT[3]; }
 #pragma unroll
                 for (int r = 0; r < nck(k); r++) {
-                    Zn = MFMA(comp(Ya, r), comp(Zk[k], r), Zn);
-                    if (!A6) Wz = MFMA(comp(cur.Lc[k], r), comp(Zk[k], r), Wz);
-                    setc(cur.Ya[k], r, tbld(rR, oA[k][r]));
-                    if (!A6) setc(cur.Lc[k], r, tbld(rR, oLc[k][r]));
+                    Zn = KP_MFMA(comp(Ya, r), comp(Zk[k], r), Zn);
+                    if (!A6) Wz = KP_MFMA(comp(cur.Lc[k], r), comp(Zk[k], r), Wz);
+                    kp_set_reg(cur.Ya[k], r, kp_bld(rR, oA[k][r]));
+                    if (!A6) kp_set_reg(cur.Lc[k], r, kp_bld(rR, oLc[k][r]));
                     __builtin_amdgcn_sched_group_barrier(0x008, A6 ? 1 : 2, 0);
                     __builtin_amdgcn_sched_group_barrier(0x020, A6 ? 1 : 2, 0);
                 }
 #pragma unroll
                 for (int r = nck(k); r < 4; r++) {            // (chunks of the last row tile that hold no rows of z: structural zeros)
-                    setc(cur.Ya[k], r, 0.0);
-                    if (!A6) setc(cur.Lc[k], r, 0.0);
+                    kp_set_reg(cur.Ya[k], r, 0.0);
+                    if (!A6) kp_set_reg(cur.Lc[k], r, 0.0);
                 }
             }
 #pragma unroll
             for (int r = 0; r < 4; r++)
             {
-                if (r < ncu) Zn = MFMA(comp(cur.Yb, r), comp(dU, r), Zn);
-                setc(cur.Yb, r, tbld(rR, oB[r]));
+                if (r < ncu) Zn = KP_MFMA(comp(cur.Yb, r), comp(dU, r), Zn);
+                kp_set_reg(cur.Yb, r, kp_bld(rR, oB[r]));
             }
             if (!A6) partial += 0.5 * (Zi.x * Wz.x + Zi.y * Wz.y + Zi.z * Wz.z + Zi.w * Wz.w);
         } else if constexpr (NCL > 0 && !A6) {
@@ -1440,11 +1353,11 @@ k_forward_tiled(RecLayout L, CostSrc CS, int T, int n_alpha, const double *__res
                 if (k == tnz) { Ya.x += oneT[0]; Ya.y += oneT[1]; Ya.z += oneT[2]; Ya.w += oneT[3]; }
 #pragma unroll
                 for (int r = 0; r < nck(k); r++) {
-                    Zn = MFMA(comp(Ya, r), comp(Zk[k], r), Zn);
-                    Wz = MFMA(comp(cur.Lc[k], r), comp(Zk[k], r), Wz);
+                    Zn = KP_MFMA(comp(Ya, r), comp(Zk[k], r), Zn);
+                    Wz = KP_MFMA(comp(cur.Lc[k], r), comp(Zk[k], r), Wz);
                 }
             }
-            Zn = Pn(cur.Yb, dU, Zn, ncu);
+            Zn = kp_Pn(cur.Yb, dU, Zn, ncu);
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int k = 0; k < NT; k++) cur.Lc[k] = ld4(rR, oLc[k]);
@@ -1466,7 +1379,7 @@ k_forward_tiled(RecLayout L, CostSrc CS, int T, int n_alpha, const double *__res
             if (k == tnz) { Ya.x += oneT[0]; Ya.y += oneT[1]; Ya.z += oneT[2]; Ya.w += oneT[3]; }
             Zn = Pk<NT>(k, Ya, Zk[k], Zn, ncl);
         }
-        Zn = Pn(cur.Yb, dU, Zn, ncu);
+        Zn = kp_Pn(cur.Yb, dU, Zn, ncu);
         }
         __builtin_amdgcn_sched_barrier(0);
         if constexpr (!FSPREAD) {
@@ -1477,7 +1390,7 @@ k_forward_tiled(RecLayout L, CostSrc CS, int T, int n_alpha, const double *__res
         __builtin_amdgcn_sched_barrier(0);
         CYF(3)
         Zi = Zn;
-        lds_store(zn + wi * TILE, lane, Zn);
+        kp_lds_store(zn + wi * KP_TILE, lane, Zn);
         CYF(4)
         __syncthreads();
         CYF(5)
@@ -1522,52 +1435,22 @@ k_forward_tiled(RecLayout L, CostSrc CS, int T, int n_alpha, const double *__res
 // register that holds structural zeros only -- rows beyond n + 2 in the last tile, rows beyond num_ctrl of a control operand -- is
 // not loaded, not stored, not clamped (an out-of-range buffer load moves no data but still costs its ~30 cycles of issue on a lone
 // wave; 24 -> 15 loads per state wave and step at n = 20, m = 7).
-template <int NC> __device__ __forceinline__ d4 Pc(const d4 &Y, const d4 &X, d4 acc)
-{
-    acc = MFMA(Y.x, X.x, acc);
-    if constexpr (NC > 1) acc = MFMA(Y.y, X.y, acc);
-    if constexpr (NC > 2) acc = MFMA(Y.z, X.z, acc);
-    if constexpr (NC > 3) acc = MFMA(Y.w, X.w, acc);
-    return acc;
-}
-template <int NC> __device__ __forceinline__ d4 lds_tile_n(const double *t, int lane)
-{
-    d4 v = {0.0, 0.0, 0.0, 0.0};
-    v.x = t[lane];
-    if constexpr (NC > 1) v.y = t[64 + lane];
-    if constexpr (NC > 2) v.z = t[128 + lane];
-    if constexpr (NC > 3) v.w = t[192 + lane];
-    return v;
-}
-template <int NC> __device__ __forceinline__ void lds_store_n(double *t, int lane, const d4 &v)
-{
-    t[lane] = v.x;
-    if constexpr (NC > 1) t[64 + lane] = v.y;
-    if constexpr (NC > 2) t[128 + lane] = v.z;
-    if constexpr (NC > 3) t[192 + lane] = v.w;
-}
 template <int NC> __device__ __forceinline__ d4 ld4n(__amdgpu_buffer_rsrc_t rs, const int *off)
 {
     d4 v = {0.0, 0.0, 0.0, 0.0};
-    v.x = tbld(rs, off[0]);
-    if constexpr (NC > 1) v.y = tbld(rs, off[1]);
-    if constexpr (NC > 2) v.z = tbld(rs, off[2]);
-    if constexpr (NC > 3) v.w = tbld(rs, off[3]);
+    v.x = kp_bld(rs, off[0]);
+    if constexpr (NC > 1) v.y = kp_bld(rs, off[1]);
+    if constexpr (NC > 2) v.z = kp_bld(rs, off[2]);
+    if constexpr (NC > 3) v.w = kp_bld(rs, off[3]);
     return v;
-}
-// the same with a wave-uniform byte offset in the loads' scalar operand: ONE descriptor per array and trajectory, the step selected
-// by an SGPR, instead of a descriptor rebuilt (64-bit address arithmetic) per array and step
-__device__ __forceinline__ double tblds(__amdgpu_buffer_rsrc_t r, int byte_off, int soff)
-{
-    return __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(r, byte_off, soff, 0));
 }
 template <int NC> __device__ __forceinline__ d4 ld4ns(__amdgpu_buffer_rsrc_t rs, const int *off, int soff)
 {
     d4 v = {0.0, 0.0, 0.0, 0.0};
-    v.x = tblds(rs, off[0], soff);
-    if constexpr (NC > 1) v.y = tblds(rs, off[1], soff);
-    if constexpr (NC > 2) v.z = tblds(rs, off[2], soff);
-    if constexpr (NC > 3) v.w = tblds(rs, off[3], soff);
+    v.x = kp_blds(rs, off[0], soff);
+    if constexpr (NC > 1) v.y = kp_blds(rs, off[1], soff);
+    if constexpr (NC > 2) v.z = kp_blds(rs, off[2], soff);
+    if constexpr (NC > 3) v.w = kp_blds(rs, off[3], soff);
     return v;
 }
 
@@ -1587,7 +1470,7 @@ __device__ __forceinline__ void ft_state_role(double *zring, double *upart, doub
     const int rec_bytes = L.rec * 8; (void)rec_bytes;
     auto rs_of = [&](const double *base, size_t step_elems, int t, int bytes) {
         const bool ok = t < T;
-        return __builtin_amdgcn_make_buffer_rsrc((void *)(base + ((size_t)b * T + (ok ? t : 0)) * step_elems), 0, ok ? bytes : 0, 0x00020000);
+        return kp_rsrc(base + ((size_t)b * T + (ok ? t : 0)) * step_elems, ok ? bytes : 0);
     };
     int oKw[4], oA[NT][4], oB[4], oub[4];
     double oneT[4], lo[NCU], hi[NCU];
@@ -1596,7 +1479,7 @@ __device__ __forceinline__ void ft_state_role(double *zring, double *upart, doub
 #pragma unroll
         for (int r = 0; r < 4; r++) {
             const int pp = 16 * k + 4 * r + q;
-            oA[k][r] = (pp < n && o < n) ? 8 * L.a(o, pp) : OOBT;
+            oA[k][r] = (pp < n && o < n) ? 8 * L.a(o, pp) : KP_OOB;
         }
 #pragma unroll
     for (int r = 0; r < 4; r++) {
@@ -1604,9 +1487,9 @@ __device__ __forceinline__ void ft_state_role(double *zring, double *upart, doub
         const int pt = 16 * tnz + row;
         oneT[r] = ((pt == n && o == n) || (pt == n + 1 && o == n + 1)) ? 1.0 : 0.0;
         const int pw = 16 * wi + row;
-        oKw[r] = (pw < n && c < m) ? 8 * (pw * m + c) : OOBT;
-        oB[r] = (row < m && o < n) ? 8 * L.b(o, row) : OOBT;
-        oub[r] = (row < m) ? 8 * row : OOBT;
+        oKw[r] = (pw < n && c < m) ? 8 * (pw * m + c) : KP_OOB;
+        oB[r] = (row < m && o < n) ? 8 * L.b(o, row) : KP_OOB;
+        oub[r] = (row < m) ? 8 * row : KP_OOB;
         if (r < NCU) {
             lo[r] = (row < m) ? ctrl_lim[2 * row] : -1.0e300;
             hi[r] = (row < m) ? ctrl_lim[2 * row + 1] : 1.0e300;
@@ -1615,7 +1498,7 @@ __device__ __forceinline__ void ft_state_role(double *zring, double *upart, doub
     // k rides in row n of the gain operand: ONE load (the lanes of that row), added into the register that holds the row
     const bool k_here = tnz == wi;
     const int rk = (n & 15) >> 2;
-    const int okn = (k_here && q == (n & 3) && c < m) ? 8 * c : OOBT;
+    const int okn = (k_here && q == (n & 3) && c < m) ? 8 * c : KP_OOB;
     double kmask[4];                                                     // 1 in the register that holds row n (no branch in the loop)
 #pragma unroll
     for (int r = 0; r < 4; r++) kmask[r] = (r == rk) ? 1.0 : 0.0;
@@ -1629,16 +1512,16 @@ __device__ __forceinline__ void ft_state_role(double *zring, double *upart, doub
             zr[r] = (row == n) ? my_alpha : (row == n + 1) ? 1.0 : 0.0;
         }
         Zi.x = zr[0]; Zi.y = zr[1]; Zi.z = zr[2]; Zi.w = zr[3];
-        lds_store(zring + wi * TILE, lane, Zi);
+        kp_lds_store(zring + wi * KP_TILE, lane, Zi);
     }
     struct STiles { d4 Ykw, Ya[NT], Yb, ub; double kk; } cur;
     // one descriptor per array for the whole trajectory; the step goes into the loads' scalar offset (behind the last step: step
     // T-1 again, never used)
     (void)rs_of;
-    const __amdgpu_buffer_rsrc_t rRec = __builtin_amdgcn_make_buffer_rsrc((void *)(rec + (size_t)b * T * L.stride), 0, (int)((size_t)T * L.stride * 8 < 0x7fffff00u ? (size_t)T * L.stride * 8 : 0x7fffff00u), 0x00020000);
-    const __amdgpu_buffer_rsrc_t rKt = __builtin_amdgcn_make_buffer_rsrc((void *)(Kin + (size_t)b * T * m * n), 0, T * m * n * 8, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rkt = __builtin_amdgcn_make_buffer_rsrc((void *)(kin + (size_t)b * T * m), 0, T * m * 8, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rut = __builtin_amdgcn_make_buffer_rsrc((void *)(u_nom + (size_t)b * T * m), 0, T * m * 8, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rRec = kp_rsrc(rec + (size_t)b * T * L.stride, (int)((size_t)T * L.stride * 8 < 0x7fffff00u ? (size_t)T * L.stride * 8 : 0x7fffff00u));
+    const __amdgpu_buffer_rsrc_t rKt = kp_rsrc(Kin + (size_t)b * T * m * n, T * m * n * 8);
+    const __amdgpu_buffer_rsrc_t rkt = kp_rsrc(kin + (size_t)b * T * m, T * m * 8);
+    const __amdgpu_buffer_rsrc_t rut = kp_rsrc(u_nom + (size_t)b * T * m, T * m * 8);
     const int recB = L.stride * 8;
     auto request_A = [&](int t) {
         const int so = (t < T ? t : T - 1) * recB;
@@ -1651,7 +1534,7 @@ __device__ __forceinline__ void ft_state_role(double *zring, double *upart, doub
         cur.Yb = ld4ns<NCU>(rRec, oB, so);
     };
     {
-        cur.Ykw = ld4ns<NCW>(rKt, oKw, 0); cur.kk = tblds(rkt, okn, 0);
+        cur.Ykw = ld4ns<NCW>(rKt, oKw, 0); cur.kk = kp_blds(rkt, okn, 0);
         request_A(0); request_B(0);
         cur.ub = ld4ns<NCU>(rut, oub, 0);
     }
@@ -1660,9 +1543,9 @@ __device__ __forceinline__ void ft_state_role(double *zring, double *upart, doub
     for (int t = 0; t < T; t++) {
         const int tn1 = t + 1 < T ? t + 1 : T - 1;
         const int sK = tn1 * m * n * 8, sk = tn1 * m * 8;
-        const double *zc = zring + slot * NT * TILE;
+        const double *zc = zring + slot * NT * KP_TILE;
         const int nslot = slot == 2 ? 0 : slot + 1;
-        double *zn = zring + nslot * NT * TILE;
+        double *zn = zring + nslot * NT * KP_TILE;
         d4 Yk = cur.Ykw;
         {
             const double kk = cur.kk;
@@ -1678,8 +1561,8 @@ __device__ __forceinline__ void ft_state_role(double *zring, double *upart, doub
         // 2.92 ms on pushing, 2.78 against 2.67 on walker -- instruction placement, as so often in these sweeps)
         d4 Zk[NT];
 #pragma unroll
-        for (int k = 0; k < NT - 1; k++) Zk[k] = lds_tile(zc + k * TILE, lane);
-        Zk[NT - 1] = lds_tile_n<NCL>(zc + (NT - 1) * TILE, lane);
+        for (int k = 0; k < NT - 1; k++) Zk[k] = kp_lds_tile(zc + k * KP_TILE, lane);
+        Zk[NT - 1] = kp_lds_tile<NCL>(zc + (NT - 1) * KP_TILE, lane);
         d4 Zn = zero;
         // the next step's gain rows and A tiles, register by register behind the product that read the register (round 5, late:
         // the waves of a trajectory share one address unit, and a block of thirteen requests stood in front of the barrier)
@@ -1688,21 +1571,21 @@ __device__ __forceinline__ void ft_state_role(double *zring, double *upart, doub
         d4 Us = zero;
 #pragma unroll
         for (int r = 0; r < NCW; r++) {
-            Us = MFMA(comp(Yk, r), comp(Zi, r), Us);
-            setc(cur.Ykw, r, tblds(rKt, oKw[r], sK));
+            Us = KP_MFMA(comp(Yk, r), comp(Zi, r), Us);
+            kp_set_reg(cur.Ykw, r, kp_blds(rKt, oKw[r], sK));
             __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
             __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
         }
-        cur.kk = tblds(rkt, okn, sk);
-        lds_store_n<NCU>(upart + wi * TILE, lane, Us);
+        cur.kk = kp_blds(rkt, okn, sk);
+        kp_lds_store<NCU>(upart + wi * KP_TILE, lane, Us);
 #pragma unroll
         for (int k = 0; k < NT; k++) {
             d4 Ya = cur.Ya[k];
             if (k == tnz) { Ya.x += oneT[0]; Ya.y += oneT[1]; Ya.z += oneT[2]; Ya.w += oneT[3]; }
 #pragma unroll
             for (int r = 0; r < (k < NT - 1 ? 4 : NCL); r++) {
-                Zn = MFMA(comp(Ya, r), comp(Zk[k], r), Zn);
-                setc(cur.Ya[k], r, tblds(rRec, oA[k][r], soA));
+                Zn = KP_MFMA(comp(Ya, r), comp(Zk[k], r), Zn);
+                kp_set_reg(cur.Ya[k], r, kp_blds(rRec, oA[k][r], soA));
                 __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
                 __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
             }
@@ -1712,7 +1595,7 @@ __device__ __forceinline__ void ft_state_role(double *zring, double *upart, doub
         const d4 ub = cur.ub;
         d4 U = ub;
 #pragma unroll
-        for (int k = 0; k < NT; k++) U = U + lds_tile_n<NCU>(upart + k * TILE, lane);
+        for (int k = 0; k < NT; k++) U = U + kp_lds_tile<NCU>(upart + k * KP_TILE, lane);
         __builtin_amdgcn_sched_barrier(0);
         cur.ub = ld4ns<NCU>(rut, oub, sk);
         __builtin_amdgcn_sched_barrier(0);
@@ -1724,11 +1607,11 @@ __device__ __forceinline__ void ft_state_role(double *zring, double *upart, doub
             if constexpr (NCU > 2) { u = U.z; if (u > hi[2]) u = hi[2]; if (u < lo[2]) u = lo[2]; U.z = u; dU.z = u - ub.z; }
             if constexpr (NCU > 3) { u = U.w; if (u > hi[3]) u = hi[3]; if (u < lo[3]) u = lo[3]; U.w = u; dU.w = u - ub.w; }
         }
-        Zn = Pc<NCU>(cur.Yb, dU, Zn);
+        Zn = kp_P<NCU>(cur.Yb, dU, Zn);
         __builtin_amdgcn_sched_barrier(0);
         request_B(t + 1);
         __builtin_amdgcn_sched_barrier(0);
-        if constexpr (WI == 0) lds_store_n<NCU>(dubuf + (t & 1) * TILE, lane, dU);        // for the control cost, one tick later
+        if constexpr (WI == 0) kp_lds_store<NCU>(dubuf + (t & 1) * KP_TILE, lane, dU);        // for the control cost, one tick later
         if constexpr (WI == NT - 1) {
             if (U_alpha && c < n_alpha) {
                 double *Ua = U_alpha + (((size_t)b * n_alpha + c) * T + t) * m;
@@ -1738,7 +1621,7 @@ __device__ __forceinline__ void ft_state_role(double *zring, double *upart, doub
             }
         }
         Zi = Zn;
-        lds_store_n<NCW>(zn + wi * TILE, lane, Zn);
+        kp_lds_store<NCW>(zn + wi * KP_TILE, lane, Zn);
         slot = nslot;
         __syncthreads();
     }
@@ -1755,10 +1638,10 @@ k_forward_tiled_sc(RecLayout L, int T, int n_alpha, const double *__restrict__ r
 {
     static_assert(NT == 2, "the role dispatch below is written for two row tiles");
     extern __shared__ __attribute__((aligned(16))) double fsh[];
-    double *zring = fsh;                                                     // [3][NT * TILE]: Z_t in slot t mod 3
-    double *upart = zring + 3 * NT * TILE;                                   // per-wave partials of K dx + alpha k
-    double *dubuf = upart + NT * TILE;                                       // [2][TILE]: dU_t in slot t & 1
-    double *red = dubuf + 2 * TILE;                                          // [NT * 64]
+    double *zring = fsh;                                                     // [3][NT * KP_TILE]: Z_t in slot t mod 3
+    double *upart = zring + 3 * NT * KP_TILE;                                   // per-wave partials of K dx + alpha k
+    double *dubuf = upart + NT * KP_TILE;                                       // [2][KP_TILE]: dU_t in slot t & 1
+    double *red = dubuf + 2 * KP_TILE;                                          // [NT * 64]
     const int n = L.n, m = L.m;
     const int lane = threadIdx.x & 63, c = lane & 15, q = lane >> 4;
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -1776,12 +1659,12 @@ k_forward_tiled_sc(RecLayout L, int T, int n_alpha, const double *__restrict__ r
         const d4 zero = {0.0, 0.0, 0.0, 0.0};
         const int rec_bytes = L.rec * 8;
         auto ld4 = [&](__amdgpu_buffer_rsrc_t rs, const int *off) -> d4 {
-            d4 v; v.x = tbld(rs, off[0]); v.y = tbld(rs, off[1]); v.z = tbld(rs, off[2]); v.w = tbld(rs, off[3]);
+            d4 v; v.x = kp_bld(rs, off[0]); v.y = kp_bld(rs, off[1]); v.z = kp_bld(rs, off[2]); v.w = kp_bld(rs, off[3]);
             return v;
         };
         auto rs_of = [&](const double *base, size_t step_elems, int t, int bytes) {
             const bool ok = t < T;
-            return __builtin_amdgcn_make_buffer_rsrc((void *)(base + ((size_t)b * T + (ok ? t : 0)) * step_elems), 0, ok ? bytes : 0, 0x00020000);
+            return kp_rsrc(base + ((size_t)b * T + (ok ? t : 0)) * step_elems, ok ? bytes : 0);
         };
         int oLc[NT][4], oLuu[4], olu[4];
 #pragma unroll
@@ -1791,16 +1674,16 @@ k_forward_tiled_sc(RecLayout L, int T, int n_alpha, const double *__restrict__ r
                 const int pp = 16 * k + 4 * r + q;
                 oLc[k][r] = (pp < n && o < n) ? 8 * (L.off_lxx + pp * n + o)
                           : (pp == n + 1 && o < n) ? 8 * (L.off_lx + o)
-                          : (o == n + 1 && pp < n) ? 8 * (L.off_lx + pp) : OOBT;
+                          : (o == n + 1 && pp < n) ? 8 * (L.off_lx + pp) : KP_OOB;
             }
 #pragma unroll
         for (int r = 0; r < 4; r++) {
             const int row = 4 * r + q;
-            oLuu[r] = (wi == NT - 1 && row < m && c < m) ? 8 * (L.off_luu + row * m + c) : OOBT;
-            olu[r] = (wi == NT - 1 && row < m) ? 8 * (L.off_lu + row) : OOBT;
+            oLuu[r] = (wi == NT - 1 && row < m && c < m) ? 8 * (L.off_luu + row * m + c) : KP_OOB;
+            olu[r] = (wi == NT - 1 && row < m) ? 8 * (L.off_lu + row) : KP_OOB;
         }
         struct CTiles { d4 Lc[NT], Luu, lu; } cur;
-        const __amdgpu_buffer_rsrc_t rRec = __builtin_amdgcn_make_buffer_rsrc((void *)(rec + (size_t)b * T * L.stride), 0, (int)((size_t)T * L.stride * 8 < 0x7fffff00u ? (size_t)T * L.stride * 8 : 0x7fffff00u), 0x00020000);
+        const __amdgpu_buffer_rsrc_t rRec = kp_rsrc(rec + (size_t)b * T * L.stride, (int)((size_t)T * L.stride * 8 < 0x7fffff00u ? (size_t)T * L.stride * 8 : 0x7fffff00u));
         const int recB = L.stride * 8;
         {
             __amdgpu_buffer_rsrc_t rR = rs_of(rec, L.stride, 0, rec_bytes);
@@ -1818,13 +1701,13 @@ k_forward_tiled_sc(RecLayout L, int T, int n_alpha, const double *__restrict__ r
             // nothing of this wave's work must stand in front of it; the scoring runs under the state waves' long phase
             __syncthreads();
             const int so = (t + 1 < T ? t + 1 : T - 1) * recB;
-            const double *zc = zring + slot * NT * TILE;
+            const double *zc = zring + slot * NT * KP_TILE;
             slot = slot == 2 ? 0 : slot + 1;
             d4 Zk[NT];
 #pragma unroll
-            for (int k = 0; k < NT - 1; k++) Zk[k] = lds_tile(zc + k * TILE, lane);
-            Zk[NT - 1] = lds_tile_n<NCL>(zc + (NT - 1) * TILE, lane);
-            const d4 dU = lds_tile_n<NCU>(dubuf + (t & 1) * TILE, lane);
+            for (int k = 0; k < NT - 1; k++) Zk[k] = kp_lds_tile(zc + k * KP_TILE, lane);
+            Zk[NT - 1] = kp_lds_tile<NCL>(zc + (NT - 1) * KP_TILE, lane);
+            const d4 dU = kp_lds_tile<NCU>(dubuf + (t & 1) * KP_TILE, lane);
             d4 Wz = zero;
             d4 Wu = zero;
             const d4 lu = cur.lu;
@@ -1833,16 +1716,16 @@ k_forward_tiled_sc(RecLayout L, int T, int n_alpha, const double *__restrict__ r
             for (int k = 0; k < NT; k++)
 #pragma unroll
                 for (int r = 0; r < (k < NT - 1 ? 4 : NCL); r++) {
-                    Wz = MFMA(comp(cur.Lc[k], r), comp(Zk[k], r), Wz);
-                    setc(cur.Lc[k], r, tblds(rRec, oLc[k][r], so));
+                    Wz = KP_MFMA(comp(cur.Lc[k], r), comp(Zk[k], r), Wz);
+                    kp_set_reg(cur.Lc[k], r, kp_blds(rRec, oLc[k][r], so));
                     __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
                     __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
                 }
 #pragma unroll
             for (int r = 0; r < NCU; r++) {
-                Wu = MFMA(comp(cur.Luu, r), comp(dU, r), Wu);
-                setc(cur.Luu, r, tblds(rRec, oLuu[r], so));
-                setc(cur.lu, r, tblds(rRec, olu[r], so));
+                Wu = KP_MFMA(comp(cur.Luu, r), comp(dU, r), Wu);
+                kp_set_reg(cur.Luu, r, kp_blds(rRec, oLuu[r], so));
+                kp_set_reg(cur.lu, r, kp_blds(rRec, olu[r], so));
                 __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
                 __builtin_amdgcn_sched_group_barrier(0x020, 2, 0);
             }
@@ -1877,7 +1760,7 @@ template <int NT, bool A6, int NCL>
 static hipError_t launch_ft3(Ctx *c, double *U_alpha_dev)
 {
     const CostSrc CS = {c->r, c->r_x, c->r_u, c->w_run, c->w_term, c->d.nr};
-    const size_t lds = sizeof(double) * ((size_t)(3 + (A6 ? 1 : 0)) * NT * TILE + NT * 64);
+    const size_t lds = sizeof(double) * ((size_t)(3 + (A6 ? 1 : 0)) * NT * KP_TILE + NT * 64);
     const auto kernel = c->sweep_list ? k_forward_tiled<NT, A6, NCL, true> : k_forward_tiled<NT, A6, NCL, false>;
     if (lds > 64 * 1024) {
         hipError_t e = hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -1905,7 +1788,7 @@ static hipError_t launch_ft2(Ctx *c, double *U_alpha_dev)
 template <int NT, int NCL, int NCU>
 static hipError_t launch_ft_sc2(Ctx *c, double *U_alpha_dev)
 {
-    const size_t lds = sizeof(double) * ((size_t)(4 * NT + 2) * TILE + NT * 64);
+    const size_t lds = sizeof(double) * ((size_t)(4 * NT + 2) * KP_TILE + NT * 64);
     // the LDS images are read with the register counts they are written with; what lies beyond is never read -- but start clean
     const auto kernel = c->sweep_list ? k_forward_tiled_sc<NT, NCL, NCU, true> : k_forward_tiled_sc<NT, NCL, NCU, false>;
     hipLaunchKernelGGL(kernel, dim3(c->d.batch), dim3(128 * NT), lds, c->stream, c->L, c->d.T, c->d.n_alpha, c->rec, c->K, c->k,

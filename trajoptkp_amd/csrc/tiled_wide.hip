@@ -24,38 +24,12 @@
 
 namespace kpilqr {
 
-typedef unsigned int u32x2w __attribute__((ext_vector_type(2)));
-#define WMFMA(a, b, c) __builtin_amdgcn_mfma_f64_16x16x4f64((a), (b), (c), 0, 0, 0)
-#define OOBW 0x7ffffff0
-#define WTILE 256
-#define WTPAD 272                                    // 16 x 17: padded row-major tile
 #define WDS 33                                       // row stride of the dense m x m images (m <= 32)
 
-__device__ __forceinline__ double wbld(__amdgpu_buffer_rsrc_t r, int byte_off)
-{
-    return __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(r, byte_off, 0, 0));
-}
-__device__ __forceinline__ d4 wlds(const double *t, int lane)
-{
-    d4 v; v.x = t[lane]; v.y = t[64 + lane]; v.z = t[128 + lane]; v.w = t[192 + lane];
-    return v;
-}
-__device__ __forceinline__ void wsts(double *t, int lane, const d4 &v)
-{
-    t[lane] = v.x; t[64 + lane] = v.y; t[128 + lane] = v.z; t[192 + lane] = v.w;
-}
-__device__ __forceinline__ d4 WPn(const d4 &Y, const d4 &X, d4 acc, int nc)       // acc + Y'X over nc 4-row chunks (wave-uniform)
-{
-    acc = WMFMA(Y.x, X.x, acc);
-    if (nc > 1) acc = WMFMA(Y.y, X.y, acc);
-    if (nc > 2) acc = WMFMA(Y.z, X.z, acc);
-    if (nc > 3) acc = WMFMA(Y.w, X.w, acc);
-    return acc;
-}
 // LDS address of element (i, j) of an MT x MT (or any) grid of accumulator-layout tiles, tile (a, b) at (a * MTc + b) * 256
 __device__ __forceinline__ int wtile_addr(int i, int j, int MTc)
 {
-    return ((i >> 4) * MTc + (j >> 4)) * WTILE + ((i & 15) >> 2) * 64 + (j & 15) + 16 * (i & 3);
+    return ((i >> 4) * MTc + (j >> 4)) * KP_TILE + ((i & 15) >> 2) * 64 + (j & 15) + 16 * (i & 3);
 }
 __device__ __forceinline__ void wave_lds_sync()
 {
@@ -114,84 +88,35 @@ __device__ static __attribute__((noinline)) bool coop_ldl_inverse(const double *
     return true;
 }
 
-struct WideSrc { int n, m; int off_A, off_B, off_lxx, off_lx, off_luu, off_lu; };
-
-__device__ __forceinline__ d4 wld_Lzz(__amdgpu_buffer_rsrc_t rs, const WideSrc &S, int ti, int tj, int q, int c)
-{
-    double v[4];
-#pragma unroll
-    for (int r = 0; r < 4; r++) {
-        const int row = 16 * ti + 4 * r + q, col = 16 * tj + c, n = S.n;
-        const int off = (row < n && col < n) ? 8 * (S.off_lxx + row * n + col)
-                      : (col == n && row < n) ? 8 * (S.off_lx + row)
-                      : (row == n && col < n) ? 8 * (S.off_lx + col) : OOBW;
-        v[r] = wbld(rs, off);
-    }
-    d4 o = {v[0], v[1], v[2], v[3]};
-    return o;
+// The record tiles (kp_ld_*1, mfma_common.h), four registers at a time.  (Written as a loop: with kp_ld_*'s initialiser list the
+// backward kernels come out with other instructions.)
+#define KP_X(NAME) \
+__device__ __forceinline__ d4 wld_##NAME(__amdgpu_buffer_rsrc_t rs, const KpTileSrc &S, int ti, int tj, int q, int c) \
+{ \
+    double v[4]; \
+    _Pragma("unroll") \
+    for (int r = 0; r < 4; r++) v[r] = kp_ld_##NAME##1(rs, S, ti, tj, r, q, c); \
+    d4 o = {v[0], v[1], v[2], v[3]}; \
+    return o; \
 }
-__device__ __forceinline__ d4 wld_Fz(__amdgpu_buffer_rsrc_t rs, const WideSrc &S, int ti, int tj, int q, int c)
-{
-    double v[4];
-#pragma unroll
-    for (int r = 0; r < 4; r++) {
-        const int row = 16 * ti + 4 * r + q, col = 16 * tj + c, n = S.n;
-        v[r] = wbld(rs, (row < n && col < n) ? 8 * (S.off_A + col * n + row) : OOBW);
-    }
-    d4 o = {v[0], v[1], v[2], v[3]};
-    return o;
-}
-// B(row tile ti, control tile tj): element (16 ti + 4r+q, 16 tj + c)
-__device__ __forceinline__ d4 wld_Fu(__amdgpu_buffer_rsrc_t rs, const WideSrc &S, int ti, int tj, int q, int c)
-{
-    double v[4];
-#pragma unroll
-    for (int r = 0; r < 4; r++) {
-        const int row = 16 * ti + 4 * r + q, col = 16 * tj + c;
-        v[r] = wbld(rs, (row < S.n && col < S.m) ? 8 * (S.off_B + col * S.n + row) : OOBW);
-    }
-    d4 o = {v[0], v[1], v[2], v[3]};
-    return o;
-}
-// Luz(control tile tj, state tile tw): l_u in column n
-__device__ __forceinline__ d4 wld_Luz(__amdgpu_buffer_rsrc_t rs, const WideSrc &S, int tj, int tw, int q, int c)
-{
-    double v[4];
-#pragma unroll
-    for (int r = 0; r < 4; r++) {
-        const int row = 16 * tj + 4 * r + q, col = 16 * tw + c;
-        v[r] = wbld(rs, (row < S.m && col == S.n) ? 8 * (S.off_lu + row) : OOBW);
-    }
-    d4 o = {v[0], v[1], v[2], v[3]};
-    return o;
-}
-__device__ __forceinline__ d4 wld_Luu(__amdgpu_buffer_rsrc_t rs, const WideSrc &S, int ta, int tb, int q, int c)
-{
-    double v[4];
-#pragma unroll
-    for (int r = 0; r < 4; r++) {
-        const int row = 16 * ta + 4 * r + q, col = 16 * tb + c;
-        v[r] = wbld(rs, (row < S.m && col < S.m) ? 8 * (S.off_luu + row * S.m + col) : OOBW);
-    }
-    d4 o = {v[0], v[1], v[2], v[3]};
-    return o;
-}
+KP_X(Lzz) KP_X(Fz) KP_X(Fu) KP_X(Luz) KP_X(Luu)
+#undef KP_X
 
 // LDS map (doubles) of the backward kernel
 template <int NT, int MT> struct WideLds {
     static constexpr int NZZ = NT * NT;
     static constexpr int V = 0;
-    static constexpr int F = V + NZZ * WTILE;
-    static constexpr int TneedA = NZZ * WTPAD;                                   // the transposing scratch of phases E / F
-    static constexpr int TneedB = (NT * MT + 2 * MT * MT) * WTILE;               // Tu, Quu + lambda I, inverse tiles (phases BC .. D)
+    static constexpr int F = V + NZZ * KP_TILE;
+    static constexpr int TneedA = NZZ * KP_TPAD;                                   // the transposing scratch of phases E / F
+    static constexpr int TneedB = (NT * MT + 2 * MT * MT) * KP_TILE;               // Tu, Quu + lambda I, inverse tiles (phases BC .. D)
     static constexpr int Tsz = TneedA > TneedB ? TneedA : TneedB;
-    static constexpr int T = F + NZZ * WTILE;
+    static constexpr int T = F + NZZ * KP_TILE;
     static constexpr int Fu = T + Tsz;
-    static constexpr int X = Fu + NT * MT * WTILE;
-    static constexpr int Flags = X + MT * NT * WTILE;
+    static constexpr int X = Fu + NT * MT * KP_TILE;
+    static constexpr int Flags = X + MT * NT * KP_TILE;
     // dense work images of the factorisation / slow path: A [32][33], a [32*32], x [32*32], temp [32], tr [32 ints]
     static constexpr int DenseSz = 32 * WDS + 2 * 1024 + 64;
-    static constexpr bool DenseInF = NZZ * WTILE >= DenseSz;                     // four state tiles: Fz is free in phase D
+    static constexpr bool DenseInF = NZZ * KP_TILE >= DenseSz;                     // four state tiles: Fz is free in phase D
     static constexpr int Dense = DenseInF ? F : Flags + 8;
     static constexpr int Total = DenseInF ? Flags + 8 : Dense + DenseSz;
 };
@@ -216,13 +141,13 @@ k_backward_tiled_wide(RecLayout L, int T, const double *__restrict__ rec, const 
     const int b = GATED ? kp_block_traj(list, blockIdx.x) : (int)blockIdx.x;      // (GATED: also the sweep of a listed subset, see k_backward_tiled_col)
     const double lam = lambda[b];
     double *bufV = sh + M_::V, *bufF = sh + M_::F, *bufT = sh + M_::T, *bufFu = sh + M_::Fu, *bufX = sh + M_::X;
-    double *bufTu = bufT, *bufQ = bufTu + NT * MT * WTILE, *bufInv = bufQ + MT * MT * WTILE;      // alias the scratch of phases E / F
+    double *bufTu = bufT, *bufQ = bufTu + NT * MT * KP_TILE, *bufInv = bufQ + MT * MT * KP_TILE;      // alias the scratch of phases E / F
     int *flags = (int *)(sh + M_::Flags);
     double *dense = sh + M_::Dense;
     auto nchunk = [&](int kt) { const int rows = nz - 16 * kt; return rows >= 16 ? 4 : (rows + 3) / 4; };
     const int ncl = nchunk(NT - 1);
     auto mch = [&](int j) { const int rows = m - 16 * j; return rows >= 16 ? 4 : rows <= 0 ? 0 : (rows + 3) / 4; };
-    WideSrc S = {n, m, L.off_A, L.off_B, L.off_lxx, L.off_lx, L.off_luu, L.off_lu};
+    KpTileSrc S = {n, m, L.off_A, L.off_B, L.off_lxx, L.off_lx, L.off_luu, L.off_lu};
     const double *R0 = rec + (size_t)b * T * L.stride;
     const int rec_bytes = L.rec * 8;
     const d4 zero = {0.0, 0.0, 0.0, 0.0};
@@ -240,8 +165,8 @@ k_backward_tiled_wide(RecLayout L, int T, const double *__restrict__ rec, const 
         e.z = (8 + q == c && 16 * a + c < m) ? 1.0 : 0.0; e.w = (12 + q == c && 16 * a + c < m) ? 1.0 : 0.0;
         return e;
     };
-    auto rsrc_of = [&](int t) { return __builtin_amdgcn_make_buffer_rsrc((void *)(R0 + (size_t)t * L.stride), 0, rec_bytes, 0x00020000); };
-    const __amdgpu_buffer_rsrc_t rnone = __builtin_amdgcn_make_buffer_rsrc((void *)R0, 0, 0, 0x00020000);
+    auto rsrc_of = [&](int t) { return kp_rsrc(R0 + (size_t)t * L.stride, rec_bytes); };
+    const __amdgpu_buffer_rsrc_t rnone = kp_rsrc(R0, 0);
 
     // source tiles of the current step: Fz(k,w), Lzz(k,w), Fu(w,j), Luz(j,w); Luu(j1,j2) of the Quu tiles this wave forms
     d4 pF[NT], pL[NT], pFu[MT], pLuz[MT], pLuu[(MT * MT + NT - 1) / NT];
@@ -259,7 +184,7 @@ k_backward_tiled_wide(RecLayout L, int T, const double *__restrict__ rec, const 
     load_src(rsrc_of(T - 1));
     // V' <- Lzz(T-1)   (iLQR.cpp:537-539)
 #pragma unroll
-    for (int k = 0; k < NT; k++) wsts(bufV + (k * NT + w) * WTILE, lane, pL[k]);
+    for (int k = 0; k < NT; k++) kp_lds_store(bufV + (k * NT + w) * KP_TILE, lane, pL[k]);
     if (threadIdx.x == 0) flags[0] = 0;
 
     int pd_counter = 0, fail = 0;
@@ -279,11 +204,11 @@ k_backward_tiled_wide(RecLayout L, int T, const double *__restrict__ rec, const 
         for (int k = 0; k < NT; k++) {
             d4 f = pF[k];
             if (k == tn && w == tn) f = f + nn_one;                    // Fz(n,n) = 1
-            wsts(bufF + (k * NT + w) * WTILE, lane, f);
+            kp_lds_store(bufF + (k * NT + w) * KP_TILE, lane, f);
             cL[k] = pL[k];
         }
 #pragma unroll
-        for (int j = 0; j < MT; j++) { wsts(bufFu + (w * MT + j) * WTILE, lane, pFu[j]); cLuz[j] = pLuz[j]; }
+        for (int j = 0; j < MT; j++) { kp_lds_store(bufFu + (w * MT + j) * KP_TILE, lane, pFu[j]); cLuz[j] = pLuz[j]; }
 #pragma unroll
         for (int s_ = 0; s_ < (MT * MT + NT - 1) / NT; s_++) cLuu[s_] = pLuu[s_];
         __builtin_amdgcn_sched_barrier(0);
@@ -295,12 +220,12 @@ k_backward_tiled_wide(RecLayout L, int T, const double *__restrict__ rec, const 
         // ---- BC: Tz(:,w), Tu(w,:), Quz(:,w), Qzz(:,w) ---------------------------------------------------------------------
         d4 Fc[NT], Tz[NT];
 #pragma unroll
-        for (int k = 0; k < NT; k++) Fc[k] = wlds(bufF + (k * NT + w) * WTILE, lane);
+        for (int k = 0; k < NT; k++) Fc[k] = kp_lds_tile(bufF + (k * NT + w) * KP_TILE, lane);
 #pragma unroll
         for (int i = 0; i < NT; i++) {
             d4 acc = zero;
 #pragma unroll
-            for (int k = 0; k < NT; k++) acc = WPn(wlds(bufV + (k * NT + i) * WTILE, lane), Fc[k], acc, k < NT - 1 ? 4 : ncl);
+            for (int k = 0; k < NT; k++) acc = kp_Pn(kp_lds_tile(bufV + (k * NT + i) * KP_TILE, lane), Fc[k], acc, k < NT - 1 ? 4 : ncl);
             Tz[i] = acc;
             pF[i] = wld_Fz(rn, S, i, w, q, c); pL[i] = wld_Lzz(rn, S, i, w, q, c);
         }
@@ -308,8 +233,8 @@ k_backward_tiled_wide(RecLayout L, int T, const double *__restrict__ rec, const 
         for (int j = 0; j < MT; j++) {
             d4 Tu = zero;
 #pragma unroll
-            for (int k = 0; k < NT; k++) Tu = WPn(wlds(bufV + (k * NT + w) * WTILE, lane), wlds(bufFu + (k * MT + j) * WTILE, lane), Tu, k < NT - 1 ? 4 : ncl);
-            wsts(bufTu + (w * MT + j) * WTILE, lane, Tu);
+            for (int k = 0; k < NT; k++) Tu = kp_Pn(kp_lds_tile(bufV + (k * NT + w) * KP_TILE, lane), kp_lds_tile(bufFu + (k * MT + j) * KP_TILE, lane), Tu, k < NT - 1 ? 4 : ncl);
+            kp_lds_store(bufTu + (w * MT + j) * KP_TILE, lane, Tu);
             pFu[j] = wld_Fu(rn, S, w, j, q, c); pLuz[j] = wld_Luz(rn, S, j, w, q, c);
         }
         d4 Quzw[MT];
@@ -317,7 +242,7 @@ k_backward_tiled_wide(RecLayout L, int T, const double *__restrict__ rec, const 
         for (int j = 0; j < MT; j++) {
             d4 acc = cLuz[j];
 #pragma unroll
-            for (int k = 0; k < NT; k++) acc = WPn(wlds(bufFu + (k * MT + j) * WTILE, lane), Tz[k], acc, k < NT - 1 ? 4 : ncl);
+            for (int k = 0; k < NT; k++) acc = kp_Pn(kp_lds_tile(bufFu + (k * MT + j) * KP_TILE, lane), Tz[k], acc, k < NT - 1 ? 4 : ncl);
             Quzw[j] = acc;
         }
 #pragma unroll
@@ -330,7 +255,7 @@ k_backward_tiled_wide(RecLayout L, int T, const double *__restrict__ rec, const 
         for (int i = 0; i < NT; i++) {
             d4 acc = cL[i];
 #pragma unroll
-            for (int k = 0; k < NT; k++) acc = WPn(wlds(bufF + (k * NT + i) * WTILE, lane), Tz[k], acc, k < NT - 1 ? 4 : ncl);
+            for (int k = 0; k < NT; k++) acc = kp_Pn(kp_lds_tile(bufF + (k * NT + i) * KP_TILE, lane), Tz[k], acc, k < NT - 1 ? 4 : ncl);
             Qzz[i] = acc;
         }
         __syncthreads();
@@ -342,16 +267,16 @@ k_backward_tiled_wide(RecLayout L, int T, const double *__restrict__ rec, const 
                 const int j1 = tq / MT, j2 = tq % MT;
                 d4 acc = cLuu[s_];
 #pragma unroll
-                for (int k = 0; k < NT; k++) acc = WPn(wlds(bufFu + (k * MT + j1) * WTILE, lane), wlds(bufTu + (k * MT + j2) * WTILE, lane), acc, k < NT - 1 ? 4 : ncl);
+                for (int k = 0; k < NT; k++) acc = kp_Pn(kp_lds_tile(bufFu + (k * MT + j1) * KP_TILE, lane), kp_lds_tile(bufTu + (k * MT + j2) * KP_TILE, lane), acc, k < NT - 1 ? 4 : ncl);
                 if (j1 == j2) acc = acc + lam * eye(j1);
-                wsts(bufQ + tq * WTILE, lane, acc);
+                kp_lds_store(bufQ + tq * KP_TILE, lane, acc);
             }
         }
         __syncthreads();
         // ---- D2: (Quu + lambda I)^-1 by every wave (identical inputs: block-uniform decisions), X, K, k, G ----------------------
         d4 Qr[MT * MT];
 #pragma unroll
-        for (int i = 0; i < MT * MT; i++) Qr[i] = wlds(bufQ + i * WTILE, lane);
+        for (int i = 0; i < MT * MT; i++) Qr[i] = kp_lds_tile(bufQ + i * KP_TILE, lane);
         bool done = false;
         if (haveX && !check_pd) {
             // Newton-Schulz: R = I - Q X, X <- X + X R; the count chosen from the measured residual (kp_inverse_refresh)
@@ -364,7 +289,7 @@ k_backward_tiled_wide(RecLayout L, int T, const double *__restrict__ rec, const 
                     for (int bb = 0; bb < MT; bb++) {
                         d4 acc = zero;
 #pragma unroll
-                        for (int j = 0; j < MT; j++) acc = WPn(Qr[j * MT + a], Xinv[j * MT + bb], acc, mch(j));
+                        for (int j = 0; j < MT; j++) acc = kp_Pn(Qr[j * MT + a], Xinv[j * MT + bb], acc, mch(j));
                         d4 r_ = (a == bb ? eye(a) : zero) - acc;
                         R[a * MT + bb] = r_;
                         rmax = fmax(rmax, fmax(fmax(fabs(r_.x), fabs(r_.y)), fmax(fabs(r_.z), fabs(r_.w))));
@@ -379,7 +304,7 @@ k_backward_tiled_wide(RecLayout L, int T, const double *__restrict__ rec, const 
                     for (int bb = 0; bb < MT; bb++) {
                         d4 acc = Xinv[a * MT + bb];
 #pragma unroll
-                        for (int j = 0; j < MT; j++) acc = WPn(Xinv[j * MT + a], R[j * MT + bb], acc, mch(j));
+                        for (int j = 0; j < MT; j++) acc = kp_Pn(Xinv[j * MT + a], R[j * MT + bb], acc, mch(j));
                         Xn[a * MT + bb] = acc;
                     }
 #pragma unroll
@@ -420,7 +345,7 @@ k_backward_tiled_wide(RecLayout L, int T, const double *__restrict__ rec, const 
                 __syncthreads();
             }
 #pragma unroll
-            for (int i = 0; i < MT * MT; i++) Xinv[i] = wlds(bufInv + i * WTILE, lane);
+            for (int i = 0; i < MT * MT; i++) Xinv[i] = kp_lds_tile(bufInv + i * KP_TILE, lane);
             if (pos) {
                 // entries outside the m x m block of the image were never written by the cooperative inverse: mask them
 #pragma unroll
@@ -440,13 +365,13 @@ k_backward_tiled_wide(RecLayout L, int T, const double *__restrict__ rec, const 
         for (int j = 0; j < MT; j++) {
             d4 acc = zero;
 #pragma unroll
-            for (int j2 = 0; j2 < MT; j2++) acc = WPn(Xinv[j2 * MT + j], Quzw[j2], acc, mch(j2));
+            for (int j2 = 0; j2 < MT; j2++) acc = kp_Pn(Xinv[j2 * MT + j], Quzw[j2], acc, mch(j2));
             X[j] = acc;
         }
         {
             const int col = 16 * w + c;
-            __amdgpu_buffer_rsrc_t rK = __builtin_amdgcn_make_buffer_rsrc((void *)(Kout + ((size_t)b * T + t) * m * n), 0, m * n * 8, 0x00020000);
-            __amdgpu_buffer_rsrc_t rk = __builtin_amdgcn_make_buffer_rsrc((void *)(kout + ((size_t)b * T + t) * m), 0, m * 8, 0x00020000);
+            __amdgpu_buffer_rsrc_t rK = kp_rsrc(Kout + ((size_t)b * T + t) * m * n, m * n * 8);
+            __amdgpu_buffer_rsrc_t rk = kp_rsrc(kout + ((size_t)b * T + t) * m, m * 8);
 #pragma unroll
             for (int j = 0; j < MT; j++) {
                 const double xv[4] = {X[j].x, X[j].y, X[j].z, X[j].w};
@@ -454,14 +379,14 @@ k_backward_tiled_wide(RecLayout L, int T, const double *__restrict__ rec, const 
                 for (int r = 0; r < 4; r++) {
                     const int row = 16 * j + 4 * r + q;
                     const double kv = -xv[r];
-                    __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2w, kv), rK, (row < m && col < n) ? 8 * (row + col * m) : OOBW, 0, 0);
-                    __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2w, kv), rk, (row < m && col == n) ? 8 * row : OOBW, 0, 0);
+                    kp_bst(kv, rK, (row < m && col < n) ? 8 * (row + col * m) : KP_OOB);
+                    kp_bst(kv, rk, (row < m && col == n) ? 8 * row : KP_OOB);
                     if (col == n) dJ -= lam * (xv[r] * xv[r]);               // delta_J -= lambda k'k (:612-613)
                 }
                 // G = (Quu + 2 lambda I) K' = -(Quz + lambda X) because (Quu + lambda I) X = Quz
                 G[j].x = -__builtin_fma(lam, X[j].x, Quzw[j].x); G[j].y = -__builtin_fma(lam, X[j].y, Quzw[j].y);
                 G[j].z = -__builtin_fma(lam, X[j].z, Quzw[j].z); G[j].w = -__builtin_fma(lam, X[j].w, Quzw[j].w);
-                wsts(bufX + (j * NT + w) * WTILE, lane, X[j]);
+                kp_lds_store(bufX + (j * NT + w) * KP_TILE, lane, X[j]);
             }
         }
         __syncthreads();
@@ -469,20 +394,20 @@ k_backward_tiled_wide(RecLayout L, int T, const double *__restrict__ rec, const 
 #pragma unroll
         for (int i = 0; i < NT; i++) {
 #pragma unroll
-            for (int j = 0; j < MT; j++) Qzz[i] = WPn(wlds(bufX + (j * NT + i) * WTILE, lane), G[j], Qzz[i], mch(j));
-            double *pw = bufT + (i * NT + w) * WTPAD + q * 17 + c;
+            for (int j = 0; j < MT; j++) Qzz[i] = kp_Pn(kp_lds_tile(bufX + (j * NT + i) * KP_TILE, lane), G[j], Qzz[i], mch(j));
+            double *pw = bufT + (i * NT + w) * KP_TPAD + q * 17 + c;
             pw[0] = Qzz[i].x; pw[4 * 17] = Qzz[i].y; pw[8 * 17] = Qzz[i].z; pw[12 * 17] = Qzz[i].w;
         }
         __syncthreads();
         // ---- F: V'(i,w) = (acc(i,w) + acc(w,i)')/2   (:610) ---------------------------------------------------------------------
 #pragma unroll
         for (int i = 0; i < NT; i++) {
-            const double *pt = bufT + (w * NT + i) * WTPAD + c * 17 + q;
+            const double *pt = bufT + (w * NT + i) * KP_TPAD + c * 17 + q;
             d4 at;
             at.x = pt[0]; at.y = pt[4]; at.z = pt[8]; at.w = pt[12];
             d4 na = 0.5 * (Qzz[i] + at);
             if (i == tn && w == tn) na = na * nn_keep;
-            wsts(bufV + (i * NT + w) * WTILE, lane, na);
+            kp_lds_store(bufV + (i * NT + w) * KP_TILE, lane, na);
         }
         __syncthreads();                                   // bufT is Tu / Quu / inverse again in the next step's phase BC
     }
@@ -539,9 +464,9 @@ k_forward_tiled_wide(RecLayout L, int T, int n_alpha, const double *__restrict__
                      const int *__restrict__ list)
 {
     extern __shared__ __attribute__((aligned(16))) double fsh[];
-    double (*zbuf)[NT * WTILE] = (double (*)[NT * WTILE])fsh;               // [2][NT * TILE]
-    double *upart = fsh + 2 * NT * WTILE;                                    // [NT][MT] tiles: per-wave partials of K dx + alpha k
-    double *red = upart + NT * MT * WTILE;                                   // [NT * 64]
+    double (*zbuf)[NT * KP_TILE] = (double (*)[NT * KP_TILE])fsh;               // [2][NT * TILE]
+    double *upart = fsh + 2 * NT * KP_TILE;                                    // [NT][MT] tiles: per-wave partials of K dx + alpha k
+    double *red = upart + NT * MT * KP_TILE;                                   // [NT * 64]
     const int n = L.n, m = L.m, nz2 = n + 2;
     const int lane = threadIdx.x & 63, c = lane & 15, q = lane >> 4;
     const int wi = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -560,10 +485,10 @@ k_forward_tiled_wide(RecLayout L, int T, int n_alpha, const double *__restrict__
 #pragma unroll
         for (int r = 0; r < 4; r++) {
             const int pp = 16 * k + 4 * r + q;
-            oA[k][r] = (pp < n && o < n) ? 8 * L.a(o, pp) : OOBW;
+            oA[k][r] = (pp < n && o < n) ? 8 * L.a(o, pp) : KP_OOB;
             oLc[k][r] = (pp < n && o < n) ? 8 * (L.off_lxx + pp * n + o)
                       : (pp == n + 1 && o < n) ? 8 * (L.off_lx + o)
-                      : (o == n + 1 && pp < n) ? 8 * (L.off_lx + pp) : OOBW;
+                      : (o == n + 1 && pp < n) ? 8 * (L.off_lx + pp) : KP_OOB;
         }
 #pragma unroll
     for (int r = 0; r < 4; r++) {
@@ -574,16 +499,16 @@ k_forward_tiled_wide(RecLayout L, int T, int n_alpha, const double *__restrict__
 #pragma unroll
         for (int j = 0; j < MT; j++) {
             const int cu = 16 * j + c, ru = 16 * j + row;               // control index as a column / as a row
-            oKw[j][r] = (pw < n && cu < m) ? 8 * (pw * m + cu) : OOBW;
-            oB[j][r] = (ru < m && o < n) ? 8 * L.b(o, ru) : OOBW;
-            olu[j][r] = (ru < m) ? 8 * (L.off_lu + ru) : OOBW;
-            oub[j][r] = (ru < m) ? 8 * ru : OOBW;
+            oKw[j][r] = (pw < n && cu < m) ? 8 * (pw * m + cu) : KP_OOB;
+            oB[j][r] = (ru < m && o < n) ? 8 * L.b(o, ru) : KP_OOB;
+            olu[j][r] = (ru < m) ? 8 * (L.off_lu + ru) : KP_OOB;
+            oub[j][r] = (ru < m) ? 8 * ru : KP_OOB;
             lo[j][r] = (ru < m) ? ctrl_lim[2 * ru] : -1.0e300;
             hi[j][r] = (ru < m) ? ctrl_lim[2 * ru + 1] : 1.0e300;
 #pragma unroll
             for (int j2 = 0; j2 < MT; j2++) {
                 const int cu2 = 16 * j2 + c;
-                oLuu[j][j2][r] = (ru < m && cu2 < m) ? 8 * (L.off_luu + ru * m + cu2) : OOBW;     // l_uu(ru, cu2): tile (j, j2)
+                oLuu[j][j2][r] = (ru < m && cu2 < m) ? 8 * (L.off_luu + ru * m + cu2) : KP_OOB;     // l_uu(ru, cu2): tile (j, j2)
             }
         }
     }
@@ -597,19 +522,19 @@ k_forward_tiled_wide(RecLayout L, int T, int n_alpha, const double *__restrict__
             zr[r] = (row == n) ? my_alpha : (row == n + 1) ? 1.0 : 0.0;
         }
         Zi.x = zr[0]; Zi.y = zr[1]; Zi.z = zr[2]; Zi.w = zr[3];
-        wsts(zbuf[0] + wi * WTILE, lane, Zi);
+        kp_lds_store(zbuf[0] + wi * KP_TILE, lane, Zi);
     }
     const d4 zero = {0.0, 0.0, 0.0, 0.0};
     double partial = 0.0;
     struct Tiles { d4 Ykw[MT], Ya[NT], Lc[NT], Yb[MT], Luu[MT][MT], lu[MT], ub[MT]; };
     const int rec_bytes = L.rec * 8;
     auto ld4 = [&](__amdgpu_buffer_rsrc_t rs, const int *off) -> d4 {
-        d4 v; v.x = wbld(rs, off[0]); v.y = wbld(rs, off[1]); v.z = wbld(rs, off[2]); v.w = wbld(rs, off[3]);
+        d4 v; v.x = kp_bld(rs, off[0]); v.y = kp_bld(rs, off[1]); v.z = kp_bld(rs, off[2]); v.w = kp_bld(rs, off[3]);
         return v;
     };
     auto rs_of = [&](const double *base, size_t step_elems, int t, int bytes) {
         const bool ok = t < T;
-        return __builtin_amdgcn_make_buffer_rsrc((void *)(base + ((size_t)b * T + (ok ? t : 0)) * step_elems), 0, ok ? bytes : 0, 0x00020000);
+        return kp_rsrc(base + ((size_t)b * T + (ok ? t : 0)) * step_elems, ok ? bytes : 0);
     };
     Tiles cur;
     // Requests (round 5, late; as in tiled_mfma.hip's k_forward_tiled): every group of tiles is re-requested for step t+1 right behind
@@ -620,7 +545,7 @@ k_forward_tiled_wide(RecLayout L, int T, int n_alpha, const double *__restrict__
     int okn[MT];
     double kmask[4], kv[MT];
 #pragma unroll
-    for (int j = 0; j < MT; j++) { okn[j] = (k_here && q == (n & 3) && 16 * j + c < m) ? 8 * (16 * j + c) : OOBW; kv[j] = 0.0; }
+    for (int j = 0; j < MT; j++) { okn[j] = (k_here && q == (n & 3) && 16 * j + c < m) ? 8 * (16 * j + c) : KP_OOB; kv[j] = 0.0; }
 #pragma unroll
     for (int r = 0; r < 4; r++) kmask[r] = (r == ((n & 15) >> 2)) ? 1.0 : 0.0;
     auto load_all = [&](int t) {
@@ -628,7 +553,7 @@ k_forward_tiled_wide(RecLayout L, int T, int n_alpha, const double *__restrict__
         const __amdgpu_buffer_rsrc_t rk = rs_of(kin, m, t, m * 8), ru = rs_of(u_nom, m, t, m * 8);
 #pragma unroll
         for (int j = 0; j < MT; j++) {
-            cur.Ykw[j] = ld4(rK, oKw[j]); kv[j] = wbld(rk, okn[j]);
+            cur.Ykw[j] = ld4(rK, oKw[j]); kv[j] = kp_bld(rk, okn[j]);
             cur.Yb[j] = ld4(rR, oB[j]); cur.lu[j] = ld4(rR, olu[j]); cur.ub[j] = ld4(ru, oub[j]);
 #pragma unroll
             for (int j2 = 0; j2 < MT; j2++) cur.Luu[j][j2] = ld4(rR, oLuu[j][j2]);
@@ -650,20 +575,20 @@ k_forward_tiled_wide(RecLayout L, int T, int n_alpha, const double *__restrict__
             d4 Yk = cur.Ykw[j];
             Yk.x = __builtin_fma(kmask[0], kv[j], Yk.x); Yk.y = __builtin_fma(kmask[1], kv[j], Yk.y);
             Yk.z = __builtin_fma(kmask[2], kv[j], Yk.z); Yk.w = __builtin_fma(kmask[3], kv[j], Yk.w);
-            wsts(upart + (wi * MT + j) * WTILE, lane, WPn(Yk, Zi, zero, ncw));
-            cur.Ykw[j] = ld4(rKn, oKw[j]); kv[j] = wbld(rkn, okn[j]);
+            kp_lds_store(upart + (wi * MT + j) * KP_TILE, lane, kp_Pn(Yk, Zi, zero, ncw));
+            cur.Ykw[j] = ld4(rKn, oKw[j]); kv[j] = kp_bld(rkn, okn[j]);
         }
         __syncthreads();
         // ---- control law + clamp (every wave; :876-890) ----------------------------------------------------------------------
         d4 U[MT], dU[MT];
         d4 Zk[NT];
 #pragma unroll
-        for (int k = 0; k < NT; k++) Zk[k] = wlds(zc + k * WTILE, lane);
+        for (int k = 0; k < NT; k++) Zk[k] = kp_lds_tile(zc + k * KP_TILE, lane);
 #pragma unroll
         for (int j = 0; j < MT; j++) {
             d4 u = cur.ub[j];
 #pragma unroll
-            for (int k = 0; k < NT; k++) u = u + wlds(upart + (k * MT + j) * WTILE, lane);
+            for (int k = 0; k < NT; k++) u = u + kp_lds_tile(upart + (k * MT + j) * KP_TILE, lane);
             double v;
             v = u.x; if (v > hi[j][0]) v = hi[j][0]; if (v < lo[j][0]) v = lo[j][0]; u.x = v;
             v = u.y; if (v > hi[j][1]) v = hi[j][1]; if (v < lo[j][1]) v = lo[j][1]; u.y = v;
@@ -686,7 +611,7 @@ k_forward_tiled_wide(RecLayout L, int T, int n_alpha, const double *__restrict__
             for (int j = 0; j < MT; j++) {         // du' (l_uu du / 2 + l_u): rows of control tile j
                 d4 Wu = zero;
 #pragma unroll
-                for (int j2 = 0; j2 < MT; j2++) Wu = WPn(cur.Luu[j2][j], dU[j2], Wu, mch(j2));     // (l_uu(j2,j))' du(j2) = l_uu(j,j2) du(j2)
+                for (int j2 = 0; j2 < MT; j2++) Wu = kp_Pn(cur.Luu[j2][j], dU[j2], Wu, mch(j2));     // (l_uu(j2,j))' du(j2) = l_uu(j,j2) du(j2)
                 partial += dU[j].x * (0.5 * Wu.x + cur.lu[j].x) + dU[j].y * (0.5 * Wu.y + cur.lu[j].y)
                          + dU[j].z * (0.5 * Wu.z + cur.lu[j].z) + dU[j].w * (0.5 * Wu.w + cur.lu[j].w);
             }
@@ -701,7 +626,7 @@ k_forward_tiled_wide(RecLayout L, int T, int n_alpha, const double *__restrict__
         d4 Wz = zero, Zn = zero;
 #pragma unroll
         for (int k = 0; k < NT; k++) {
-            Wz = WPn(cur.Lc[k], Zk[k], Wz, k < NT - 1 ? 4 : ncl);
+            Wz = kp_Pn(cur.Lc[k], Zk[k], Wz, k < NT - 1 ? 4 : ncl);
             cur.Lc[k] = ld4(rRn, oLc[k]);
         }
         partial += 0.5 * (Zi.x * Wz.x + Zi.y * Wz.y + Zi.z * Wz.z + Zi.w * Wz.w);
@@ -709,16 +634,16 @@ k_forward_tiled_wide(RecLayout L, int T, int n_alpha, const double *__restrict__
         for (int k = 0; k < NT; k++) {
             d4 Ya = cur.Ya[k];
             if (k == tnz) { Ya.x += oneT[0]; Ya.y += oneT[1]; Ya.z += oneT[2]; Ya.w += oneT[3]; }
-            Zn = WPn(Ya, Zk[k], Zn, k < NT - 1 ? 4 : ncl);
+            Zn = kp_Pn(Ya, Zk[k], Zn, k < NT - 1 ? 4 : ncl);
             cur.Ya[k] = ld4(rRn, oA[k]);
         }
 #pragma unroll
         for (int j = 0; j < MT; j++) {
-            Zn = WPn(cur.Yb[j], dU[j], Zn, mch(j));
+            Zn = kp_Pn(cur.Yb[j], dU[j], Zn, mch(j));
             cur.Yb[j] = ld4(rRn, oB[j]);
         }
         Zi = Zn;
-        wsts(zn + wi * WTILE, lane, Zn);
+        kp_lds_store(zn + wi * KP_TILE, lane, Zn);
         __syncthreads();
     }
     partial += __shfl_xor(partial, 16);
@@ -741,7 +666,7 @@ bool forward_wide_supported(int n, int m, int n_alpha, int nt_min)
 template <int NT>
 static hipError_t launch_fw(Ctx *c, double *U_alpha_dev)
 {
-    const size_t lds = sizeof(double) * ((size_t)(2 * NT + NT * 2) * WTILE + NT * 64);
+    const size_t lds = sizeof(double) * ((size_t)(2 * NT + NT * 2) * KP_TILE + NT * 64);
     const auto kernel = c->sweep_list ? k_forward_tiled_wide<NT, 2, true> : k_forward_tiled_wide<NT, 2, false>;
     if (lds > 64 * 1024) {
         hipError_t e = hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
