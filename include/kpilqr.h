@@ -170,7 +170,8 @@ typedef struct {
                                            kpilqr_upload_nominal_partial, kpilqr_fd_interpolate_partial, kpilqr_cost_derivs_partial,
                                            kpilqr_backward_partial, kpilqr_forward_linear_partial, kpilqr_iterate_partial;
                                            kpilqr_iterate_streamed, kpilqr_iterate_streamed2, kpilqr_iterate_streamed3,
-                                           kpilqr_iterate_streamed4, kpilqr_iterate_streamed5; kpilqr_upload_fd, kpilqr_fd_slab_layout,
+                                           kpilqr_iterate_streamed4, kpilqr_iterate_streamed5, kpilqr_iterate_streamed6;
+                                           kpilqr_upload_fd, kpilqr_fd_slab_layout,
                                            kpilqr_upload_fd_slab; kpilqr_upload_states, kpilqr_upload_states_partial,
                                            kpilqr_generate_keypoints, kpilqr_generate_keypoints_partial, kpilqr_keypoint_error_test,
                                            kpilqr_get_keypoints, kpilqr_get_keypoints_partial; kpilqr_fd_difference, kpilqr_interpolate,
@@ -557,7 +558,8 @@ int  kpilqr_upload_kp_columns_f32_partial(kpilqr_ctx *ctx, int count, const int 
  * kpilqr_destroy (KPILQR_ERR_ALLOC when it cannot be had: the context is unchanged).
  * Out of scope: FP32 residual Jacobians inside the chunks of kpilqr_iterate_streamed* (a change of its own, as it was for the
  * columns); embedded contexts; r itself; a bounded staging arena; an environment switch.  KPILQR_VERSION is unchanged: detect the
- * calls by their symbols. */
+ * calls by their symbols.
+ * (since: kpilqr_iterate_streamed6, below, takes the per-step residual Jacobians as FP32 inside the chunks.) */
 int  kpilqr_upload_residual_jacobians_f32(kpilqr_ctx *ctx, const float *r_x32 /* [batch][T+1][nr][n] or NULL */,
                                           const float *r_u32 /* [batch][T+1][nr][m] or NULL */);
 int  kpilqr_upload_residual_jacobians_f32_partial(kpilqr_ctx *ctx, int count, const int *traj,
@@ -679,7 +681,8 @@ int  kpilqr_iterate_streamed2(kpilqr_ctx *ctx, const kpilqr_stream_io2 *io2, int
  * to kpilqr_stream_io or kpilqr_stream_io2; an environment switch.  KPILQR_VERSION is unchanged: detect the call by its symbol.
  * (Uploads of a subset inside the chunks have since arrived as kpilqr_iterate_streamed4, below; its sweeps still cover every trajectory.)
  * (since: the explicit calls sweep a listed subset -- "Sweeps of a subset"; the chunks still sweep every trajectory.)
- * (since: kpilqr_iterate_streamed5, below, linearises and sweeps a listed subset inside the chunks.) */
+ * (since: kpilqr_iterate_streamed5, below, linearises and sweeps a listed subset inside the chunks.)
+ * (since: kpilqr_iterate_streamed6, below, takes the per-step residual Jacobians as FP32 inside the chunks.) */
 typedef struct {
     size_t struct_size;                         /* sizeof(kpilqr_stream_io3) as the caller compiled it                   */
     kpilqr_stream_io2 io2;                      /* every field as for kpilqr_iterate_streamed2; io2.struct_size = sizeof(kpilqr_stream_io2) */
@@ -744,7 +747,8 @@ int  kpilqr_iterate_streamed3(kpilqr_ctx *ctx, const kpilqr_stream_io3 *io3, int
  * the chunks; the host classes and the batch shim (they do not use the streamed route); any change to kpilqr_stream_io, _io2 or
  * _io3; an environment switch.  KPILQR_VERSION is unchanged: detect the call by its symbol.
  * (since: the explicit calls sweep a listed subset -- "Sweeps of a subset"; the chunks still sweep every trajectory.)
- * (since: kpilqr_iterate_streamed5, below, linearises and sweeps a listed subset inside the chunks.) */
+ * (since: kpilqr_iterate_streamed5, below, linearises and sweeps a listed subset inside the chunks.)
+ * (since: kpilqr_iterate_streamed6, below, takes the per-step residual Jacobians as FP32 inside the chunks.) */
 typedef struct {
     size_t struct_size;                         /* sizeof(kpilqr_stream_io4) as the caller compiled it                   */
     kpilqr_stream_io3 io3;                      /* every field as for kpilqr_iterate_streamed3 (inner struct_sizes checked as there) */
@@ -800,7 +804,8 @@ int  kpilqr_iterate_streamed4(kpilqr_ctx *ctx, const kpilqr_stream_io4 *io4, int
  * Out of scope: differencing inside a listed sweep, or proportional to the list; job-list payloads with any list;
  * KPILQR_FLAG_UNION_KEYPOINTS in the chunks; the host classes and the batch shim; any change to kpilqr_stream_io ... _io4; an
  * environment switch.  KPILQR_VERSION is unchanged: detect the call by its symbol.  (profiles/streamed_subset_sweeps.txt holds the
- * byte and launch model and says what was measured.) */
+ * byte and launch model and says what was measured.)
+ * (since: kpilqr_iterate_streamed6, below, takes the per-step residual Jacobians as FP32 inside the chunks.) */
 typedef struct {
     size_t struct_size;                         /* sizeof(kpilqr_stream_io5) as the caller compiled it                   */
     kpilqr_stream_io4 io4;                      /* every field as for kpilqr_iterate_streamed4 (inner struct_sizes checked as there) */
@@ -808,6 +813,64 @@ typedef struct {
     const int *sweep_traj;                      /* NULL: every trajectory is swept, the call IS kpilqr_iterate_streamed4 */
 } kpilqr_stream_io5;
 int  kpilqr_iterate_streamed5(kpilqr_ctx *ctx, const kpilqr_stream_io5 *io5, int pd_check_stride, int nchunks);
+
+/* kpilqr_iterate_streamed5 taking the per-step residual Jacobians as FP32 inside the chunks -- what
+ * kpilqr_upload_residual_jacobians_f32[_partial] do for the explicit calls, in the chunk pipeline: a host whose residuals are not
+ * affine in the state sends half the bytes of its largest upload and keeps the overlap, the subset uploads of upload_traj and the
+ * subset sweeps of sweep_traj.  struct_size must be sizeof(kpilqr_stream_io6) as the caller compiled it and the inner struct_sizes as
+ * for kpilqr_iterate_streamed5, else KPILQR_ERR_ARG.  `io5` is the struct of kpilqr_iterate_streamed5, every field with the meaning it
+ * has there; with r_x32 = NULL and r_u32 = NULL the call IS kpilqr_iterate_streamed5 (one implementation, the same copies and launches
+ * in the same order).
+ * The arrays.  r_x32 [batch][T+1][nr][n] and r_u32 [batch][T+1][nr][m] in the layout of io.r_x / io.r_u; with upload_traj the listed
+ * trajectories' rows, [upload_count][T+1][nr][n] and [upload_count][T+1][nr][m], compact in list order, as io.r_x / io.r_u are there;
+ * NULL = not sent.  Both must be pinned (kpilqr_host_alloc) and 8-byte aligned, and are read until the iteration has completed.
+ * Per array, one transport per call: io.r_x together with r_x32, or io.r_u together with r_u32, is KPILQR_ERR_ARG; FP64 r_x beside
+ * r_u32, and the reverse, is allowed.  They combine with every other option of the older structs: any payload kind including
+ * kp_columns32, K32, gain_traj, upload_traj, sweep_traj, the lambda retry.
+ * Encoding and decoding are, word for word, those of kpilqr_upload_residual_jacobians_f32: the caller makes a plain (float) cast,
+ * the library widens exactly, dst = (double)src; FP32 subnormals widen to their value, +-inf stays +-inf, -0 stays -0, NaN stays
+ * NaN.  Results and state afterwards are, bit for bit, those of a kpilqr_iterate_streamed5 given FP64 io.r_x / io.r_u that hold the
+ * widened floats: the r_x / r_u buffers, K, k, cost_pred, delta_J, status and the kpilqr_last_launch strings (:ru0, :rxc); a whole
+ * r_x32 ends the constant-Jacobian mode, r_u32 counts r_u as non-zero -- recorded behind every check that can still reject the call.
+ * Lists.  With upload_traj the three refusals of kpilqr_upload_residuals_partial apply, with its code (KPILQR_ERR_STATE) and in its
+ * words: r_x32 of a subset while the context holds constant residual Jacobians; r_x32 of a subset before a whole r_x; r_u32 of a
+ * subset on a context that runs without control residuals (:ru0).  With sweep_traj the rule of kpilqr_iterate_streamed5 holds for
+ * the new arrays too: inputs come with an upload_traj inside sweep_traj, r_x32 or r_u32 without one is KPILQR_ERR_ARG.
+ * Rejections, all before anything is enqueued or the context is changed (a context in the constant-Jacobian mode stays in it):
+ * KPILQR_ERR_ARG for ctx = NULL or io6 = NULL, a wrong outer or inner struct_size, r_x32 or r_u32 not pinned or not 8-byte aligned,
+ * an array given through both transports, and the sweep_traj rule above; KPILQR_ERR_STATE for the three refusals of a subset.  Not
+ * on an embedded context (KPILQR_FLAG_EMBED_SHAPE: KPILQR_ERR_STATE, as listed there).  Every refusal of the older calls keeps its
+ * code.
+ * How.  Per chunk, on the chunk's own stream, ONE launch serves BOTH arrays (k_widen_jacobians, residuals_f32.hip; the sweeps are
+ * latency-bound, so a chunk does not pay two launches where one does): a block row is a trajectory of the chunk -- without a list
+ * the chunk's own, with upload_traj the chunk's slice of the device copy of the list, so a scattered list costs no copy per run --
+ * and a split of the grid's x range selects the array; an array that is not given costs no block.  r_x is widened in pairs (8-byte
+ * loads, 16-byte stores; n = 2 dof), r_u in pairs where (T+1)*nr*m is even and in single elements (4-byte loads, 8-byte stores)
+ * where it is odd: a chunk's slice of r_u32 can then start on an odd float, and nothing beyond 4-byte alignment is assumed of it.
+ * The source follows KPILQR_PIPE_COPY bit 0, as every other upload does.  Uploads by SDMA (the default): ONE copy per array of the
+ * chunk's slice into the staging buffer of kpilqr_upload_residual_jacobians_f32, laid out [r_x32 | r_u32] at whole-batch size, where
+ * the chunk's first trajectory's rows would land, with or without a list; then the launch.  Uploads by kernel (bit 0 set): the
+ * launch reads the caller's pinned floats itself; no staging buffer is reserved or touched and there is no second pass over device
+ * memory -- which is why the arrays must be 8-byte aligned.  A chunk without rows copies and launches nothing for the Jacobians.
+ * Overlap.  A region of the staging buffer is addressed by the chunk alone, so same-stream order protects it from the next call's
+ * upload whatever that call lists: consecutive calls overlap without a wait.  The explicit kpilqr_upload_residual_jacobians_f32 /
+ * _partial share the buffer and order themselves behind a streamed iteration in flight.
+ * Memory: the staging buffer, 4 bytes x batch x (T+1) x nr x (n + m), reserved on the context before the chunks are cut
+ * (KPILQR_ERR_ALLOC when it cannot be had) and kept; a call that has to grow it first orders itself behind the iteration in flight.
+ * A context that never passes r_x32 / r_u32 allocates and launches nothing new.
+ * Bytes: Panda reaching, T = 3000, nr = 14: 7.06 MB of residual Jacobians per trajectory become 3.53 MB; r, u_nom, the payload and
+ * the downloads stay and share the link (profiles/streamed_residual_jacobians_f32.txt holds the byte model and what was measured).
+ * Out of scope: FP32 for r, u_nom or k, or inside any sweep; the host classes and the batch shim (they do not use the streamed
+ * route); embedded contexts; a bounded staging arena; any change to kpilqr_stream_io ... _io5; an environment switch.
+ * KPILQR_VERSION is unchanged: detect the call by its symbol. */
+typedef struct {
+    size_t struct_size;                         /* sizeof(kpilqr_stream_io6) as the caller compiled it                   */
+    kpilqr_stream_io5 io5;                      /* every field as for kpilqr_iterate_streamed5 (inner struct_sizes checked as there) */
+    const float *r_x32;                         /* [batch][T+1][nr][n], or with upload_traj [upload_count][T+1][nr][n] compact in
+                                                   list order; NULL: not sent                                             */
+    const float *r_u32;                         /* [batch][T+1][nr][m], or compact likewise; NULL: not sent               */
+} kpilqr_stream_io6;
+int  kpilqr_iterate_streamed6(kpilqr_ctx *ctx, const kpilqr_stream_io6 *io6, int pd_check_stride, int nchunks);
 
 /* Differencing tail of Differentiator::DynamicsDerivatives (:166-222,286-321,386-423,441-457):
  * writes the key-point columns of A and B. */

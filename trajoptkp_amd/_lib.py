@@ -38,7 +38,7 @@ SYMBOLS = [
     "kpilqr_backward_partial", "kpilqr_forward_linear_partial", "kpilqr_iterate_partial",
     "kpilqr_upload_states_partial", "kpilqr_generate_keypoints_partial", "kpilqr_get_keypoints_partial",
     "kpilqr_get_carrier_dims",
-    "kpilqr_upload_residual_jacobians_f32", "kpilqr_upload_residual_jacobians_f32_partial",
+    "kpilqr_upload_residual_jacobians_f32", "kpilqr_upload_residual_jacobians_f32_partial", "kpilqr_iterate_streamed6",
 ]
 # entry points added without a version bump (include/kpilqr.h: "detect the entry point by its symbol"): bound only when the library
 # has them -- KPILQR_LIB may name an older build of the same major version
@@ -53,7 +53,7 @@ OPTIONAL_SYMBOLS = {"kpilqr_fd_interpolate", "kpilqr_get_union_keypoints", "kpil
                     "kpilqr_backward_partial", "kpilqr_forward_linear_partial", "kpilqr_iterate_partial",
                     "kpilqr_upload_states_partial", "kpilqr_generate_keypoints_partial", "kpilqr_get_keypoints_partial",
                     "kpilqr_get_carrier_dims",
-                    "kpilqr_upload_residual_jacobians_f32", "kpilqr_upload_residual_jacobians_f32_partial"}
+                    "kpilqr_upload_residual_jacobians_f32", "kpilqr_upload_residual_jacobians_f32_partial", "kpilqr_iterate_streamed6"}
 
 
 class Dims(C.Structure):
@@ -96,6 +96,11 @@ class StreamIO4(C.Structure):
 class StreamIO5(C.Structure):
     """kpilqr_stream_io5: StreamIO4 with the list of trajectories that are linearised and swept; struct_size = sizeof(StreamIO5)"""
     _fields_ = [("struct_size", C.c_size_t), ("io4", StreamIO4), ("sweep_count", C.c_int), ("sweep_traj", C.c_void_p)]
+
+
+class StreamIO6(C.Structure):
+    """kpilqr_stream_io6: StreamIO5 with the per-step residual Jacobians as FP32; struct_size = sizeof(StreamIO6)"""
+    _fields_ = [("struct_size", C.c_size_t), ("io5", StreamIO5), ("r_x32", C.c_void_p), ("r_u32", C.c_void_p)]
 
 
 class LambdaRetry(C.Structure):
@@ -226,6 +231,8 @@ def load():
         L.kpilqr_iterate_streamed4.argtypes = [vp, C.POINTER(StreamIO4), C.c_int, C.c_int]
     if hasattr(L, "kpilqr_iterate_streamed5"):
         L.kpilqr_iterate_streamed5.argtypes = [vp, C.POINTER(StreamIO5), C.c_int, C.c_int]
+    if hasattr(L, "kpilqr_iterate_streamed6"):
+        L.kpilqr_iterate_streamed6.argtypes = [vp, C.POINTER(StreamIO6), C.c_int, C.c_int]
     if hasattr(L, "kpilqr_backward_partial"):
         L.kpilqr_backward_partial.argtypes = [vp, C.c_int, vp, vp, C.c_int, vp, vp]
         L.kpilqr_forward_linear_partial.argtypes = [vp, C.c_int, vp, vp, vp, vp]

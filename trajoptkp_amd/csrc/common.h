@@ -434,6 +434,12 @@ hipError_t launch_kp_columns_f32_range(Ctx *c, hipStream_t s, int l0, int l1, co
 // residuals_f32.hip: `count` trajectories of `per` floats each, compact in src (device; 8-byte aligned when per is even), widened into
 // rows traj[i] (device; nullptr: rows 0 .. count-1) of dst, `per` doubles per trajectory, on the context's stream
 hipError_t launch_widen_rows(Ctx *c, const int *traj, int count, long long per, const float *src, double *dst);
+// the same for a chunk of kpilqr_iterate_streamed6, BOTH arrays in one launch on stream s: row i of `count` rows of src_x (perx floats
+// a row) and src_u (peru floats a row) widened into trajectory traj[i] (device; nullptr: first + i) of dst_x / dst_u.  A NULL source
+// is an array that is not given.  The sources may be device memory or the caller's pinned floats; src_x, and src_u when peru is even,
+// 8-byte aligned
+hipError_t launch_widen_jacobians(hipStream_t s, const int *traj, int first, int count, long long perx, const float *src_x, double *dst_x,
+                                  long long peru, const float *src_u, double *dst_u);
 // rows_in.hip, the chunks of kpilqr_iterate_streamed4 with upload_traj: rows of a chunk's staging region moved to their trajectories'
 // places on stream s.  Row i of `count` is trajectory traj[i] (device).  Fixed rows of `units` doubles: staging + i*units -> dst + traj[i]*units
 hipError_t launch_rows_in(hipStream_t s, const int *traj, int count, long long units, const double *staging, double *dst);

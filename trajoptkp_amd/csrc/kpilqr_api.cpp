@@ -2609,7 +2609,7 @@ struct StreamList {
 // The FD payload a streamed iteration brings, decided once (at the "one FD payload per iteration" refusal of stream_check)
 enum class StreamPayload { none, jobs, kp_ordered, columns, columns_f32 };
 
-// A streamed iteration, resolved: what the five entry points ask for (they fill the first group), what stream_check decides about the
+// A streamed iteration, resolved: what the six entry points ask for (they fill the first group), what stream_check decides about the
 // payload, and where stream_prepare found the device side of it.  The three kinds by key-point entry (kp_ordered, columns,
 // columns_f32) differ in the fields below and in nothing else: a chunk copies ONE contiguous range of `rec` bytes per entry from
 // `src` to `land` at its own first entry, and one launch may follow (stream_chunk_payload).
@@ -2621,6 +2621,7 @@ struct StreamCall {
     const float *kcols32 = nullptr;    // kpilqr_iterate_streamed3: the ENCODED FP32 key-point columns (kpilqr_upload_kp_columns_f32) for a payload
     StreamList rows;                   // kpilqr_iterate_streamed4: the inputs (payload, r, r_x, r_u, u_nom) of those trajectories alone, compact; read during the call only
     StreamList sweep;                  // kpilqr_iterate_streamed5: the linearisation and the sweeps of those trajectories alone; lambda, cost_pred, delta_J, status compact
+    const float *rx32 = nullptr, *ru32 = nullptr;      // kpilqr_iterate_streamed6: r_x / r_u as FP32 (kpilqr_upload_residual_jacobians_f32) instead of io->r_x / io->r_u; compact with `rows`
     // stream_check
     StreamPayload kind = StreamPayload::none;
     const char *src = nullptr;         // by entry: the host source ...
@@ -2812,7 +2813,7 @@ static int stream_check(kpilqr_ctx *c, StreamCall *call, unsigned long long *sig
         static const std::string w5("kpilqr_iterate_streamed5");
         if (!kp_traj_list_ok(B, sw.count, sw.traj)) return set_err(c, KPILQR_ERR_ARG, w5 + ": sweep_traj must be strictly increasing and within [0, batch)");
         if (io->fd_slab) return set_err(c, KPILQR_ERR_ARG, w5 + ": io.fd_slab with sweep_traj (job lists carry their own trajectory indices: out of scope)");
-        if (!u.listed && (call->kind != StreamPayload::none || io->r || io->r_x || io->r_u || io->u_nom))
+        if (!u.listed && (call->kind != StreamPayload::none || io->r || io->r_x || io->r_u || io->u_nom || call->rx32 || call->ru32))
             return set_err(c, KPILQR_ERR_ARG, w5 + ": inputs with sweep_traj come with an upload_traj inside it");
         for (int i = 0, j = 0; i < u.count; i++) {
             while (j < sw.count && sw.traj[j] < u.traj[i]) j++;
@@ -2821,11 +2822,12 @@ static int stream_check(kpilqr_ctx *c, StreamCall *call, unsigned long long *sig
         }
     }
     // (the refusals of kpilqr_upload_residuals_partial, in its words)
-    if (u.listed && io->r_x && c->rx_const_on)
+    const bool rx_given = io->r_x || call->rx32, ru_given = io->r_u || call->ru32;      // (either transport)
+    if (u.listed && rx_given && c->rx_const_on)
         return set_err(c, KPILQR_ERR_STATE, w + ": the context holds constant residual Jacobians; a whole r_x through kpilqr_upload_residuals ends that mode first");
-    if (u.listed && io->r_x && !(c->rx_buf_valid && c->rx_whole))
+    if (u.listed && rx_given && !(c->rx_buf_valid && c->rx_whole))
         return set_err(c, KPILQR_ERR_STATE, w + ": r_x of a subset before a whole r_x: kpilqr_upload_residuals first");
-    if (u.listed && io->r_u && c->ru_zero)
+    if (u.listed && ru_given && c->ru_zero)
         return set_err(c, KPILQR_ERR_STATE, w + ": r_u of a subset on a context that runs without control residuals: a whole r_u through kpilqr_upload_residuals first");
     const void *hostp[] = {kcols32, io->kp_columns, io->fd_kp_slab, io->fd_slab, io->r, io->r_x, io->r_u, io->u_nom, io->lambda, io->K, io->k, io->cost_pred, io->delta_J, io->status};
     for (const void *p : hostp) if (!is_pinned(p)) return set_err(c, KPILQR_ERR_ARG, "kpilqr_iterate_streamed: host buffers must be pinned (kpilqr_host_alloc)");
@@ -2833,6 +2835,11 @@ static int stream_check(kpilqr_ctx *c, StreamCall *call, unsigned long long *sig
         if (io->K) return set_err(c, KPILQR_ERR_ARG, "kpilqr_iterate_streamed2: io.K and K32 are exclusive");
         if (!is_pinned(call->K32) || ((size_t)call->K32 & 7)) return set_err(c, KPILQR_ERR_ARG, "kpilqr_iterate_streamed2: K32 must be pinned (kpilqr_host_alloc) and 8-byte aligned");
     }
+    // the Jacobians as FP32: per array one transport per call; the copy-kernel route reads the caller's floats in pairs
+    if ((io->r_x && call->rx32) || (io->r_u && call->ru32))
+        return set_err(c, KPILQR_ERR_ARG, "kpilqr_iterate_streamed6: io.r_x and r_x32 (io.r_u and r_u32) are exclusive: one transport per array and call");
+    for (const float *p : {call->rx32, call->ru32})
+        if (!is_pinned(p) || ((size_t)p & 7)) return set_err(c, KPILQR_ERR_ARG, "kpilqr_iterate_streamed6: r_x32 and r_u32 must be pinned (kpilqr_host_alloc) and 8-byte aligned");
     if (g.listed && !kp_traj_list_ok(B, g.count, g.traj))
         return set_err(c, KPILQR_ERR_ARG, "kpilqr_iterate_streamed2: gain_traj must be strictly increasing and within [0, batch)");
     if (c->fused) { const int rc = check_fused(c); if (rc) return rc; }
@@ -2919,6 +2926,16 @@ static int stream_reserve(kpilqr_ctx *c, StreamCall *call, unsigned long long si
         // and a chunk's upload could land in a range another chunk stream is still reading -- the rule of pipe_sig
         if (stage_pay && c->rows_pay_rec != call->rec) { rc = join_pipeline(c); if (rc) return rc; c->rows_pay_rec = call->rec; }
     }
+    // The Jacobians as FP32, uploads by SDMA: the staging buffer of kpilqr_upload_residual_jacobians_f32[_partial] (which join the
+    // pipeline on entry), laid out [r_x32 | r_u32] at whole-batch size -- a chunk's slice lands where its first trajectory's rows
+    // would, list or no list, so the chunk alone addresses a region and same-stream order protects it from the next call's upload, as
+    // for rows_stage.  The copy-kernel route reads the caller's floats itself: nothing is reserved or touched.
+    if ((call->rx32 || call->ru32) && !call->k_up && !(u.listed && u.count == 0)) {
+        const RowSizes per = row_sizes(c);
+        const size_t need = (size_t)B * (per.r_x + per.r_u) * sizeof(float);
+        rc = quiesce_for_growth(c, {{&c->rj32, need}}); if (rc) return rc;
+        rc = reserve(c, c->rj32, need, kExact, false); if (rc < 0) return rc;
+    }
     if (call->kind == StreamPayload::jobs) c->fd_payload = FdPayload::jobs;
     if (call->kind == StreamPayload::kp_ordered) c->fd_payload = FdPayload::kp_ordered;
     if (call->kind == StreamPayload::columns || call->kind == StreamPayload::columns_f32) { c->fd_payload = FdPayload::kp_columns; c->fdk_entries = pay_entries; c->fdk_first = 0; }
@@ -2993,8 +3010,8 @@ static int stream_prepare(kpilqr_ctx *c, StreamCall *call, unsigned long long si
     // Per-step Jacobians in this call end the constant mode -- recorded only HERE, behind every check that can still reject the
     // call (a rejected call must leave the context as it was: round-4 advisor; before, a call refused for an unpinned buffer had
     // already left the constant mode and the next sweep read an r_x buffer that never received the broadcast copy)
-    if (io->r_u) c->ru_zero = false;
-    if (io->r_x) { c->rx_const_on = false; c->rx_buf_valid = c->rx_whole = true; }
+    if (io->r_u || call->ru32) c->ru_zero = false;
+    if (io->r_x || call->rx32) { c->rx_const_on = false; c->rx_buf_valid = c->rx_whole = true; }
     // constant residual Jacobians and a kernel family that streams r_x: the broadcast copy is made here, on the context (the
     // chunks' wave organisation is the whole batch's: make_view gives a chunk its share of the SIMDs)
     if (!(c->fused && plan_backward_fused(c, false).rxc && plan_forward_fused(c).rxc)) { rc = ensure_rx_buffer(c); if (rc) return rc; }
@@ -3105,6 +3122,21 @@ static int stream_chunk_rows(kpilqr_ctx *c, const StreamCall &call, StreamChunk 
             KP_HIP(c, call.h2d(stg, src[kd] + (size_t)k.u0 * per, (size_t)k.urows * per * 8, k.s));
             KP_HIP(c, launch_rows_in(k.s, call.ulist + k.u0, k.urows, (long long)per, stg, dst[kd]));
         }
+    }
+    // r_x / r_u as FP32: the chunk's rows -- its own, or its slice of the compact listed ones -- widened into the CONTEXT's buffers by
+    // ONE launch for both arrays (residuals_f32.hip), from the chunk's region of the staging buffer behind ONE upload per array, or
+    // (uploads by kernel) from the caller's pinned floats themselves
+    const size_t frows = call.rows.listed ? (size_t)k.urows : cnt;
+    if ((call.rx32 || call.ru32) && frows) {
+        const size_t first = call.rows.listed ? (size_t)k.u0 : o;
+        const float *fx = call.rx32 ? call.rx32 + first * sz.r_x : nullptr, *fu = call.ru32 ? call.ru32 + first * sz.r_u : nullptr;
+        if (!call.k_up) {
+            float *const stx = (float *)c->rj32 + o * sz.r_x, *const stu = (float *)c->rj32 + (size_t)c->d.batch * sz.r_x + o * sz.r_u;
+            if (fx) { KP_HIP(c, call.h2d(stx, fx, frows * sz.r_x * sizeof(float), k.s)); fx = stx; }
+            if (fu) { KP_HIP(c, call.h2d(stu, fu, frows * sz.r_u * sizeof(float), k.s)); fu = stu; }
+        }
+        KP_HIP(c, launch_widen_jacobians(k.s, call.rows.listed ? call.ulist + k.u0 : nullptr, k.b0, (int)frows, (long long)sz.r_x, fx, c->r_x,
+                                         (long long)sz.r_u, fu, c->r_u));
     }
     // (the slot of the list may be written again once this stream has passed here)
     if (k.urows) {
@@ -3350,16 +3382,35 @@ int kpilqr_iterate_streamed4(kpilqr_ctx *c, const kpilqr_stream_io4 *io4, int pd
 }
 
 // kpilqr_iterate_streamed4 linearising and sweeping a list of trajectories alone: with sweep_traj == NULL it IS that call
+// the checks and the options of a kpilqr_stream_io5, for the two calls that carry one (call->io is &io5->io4.io3.io2.io)
+static int stream_sweep_of(kpilqr_ctx *c, const kpilqr_stream_io5 *io5, StreamCall *call)
+{
+    if (io5->struct_size != sizeof(kpilqr_stream_io5)) return set_err(c, KPILQR_ERR_ARG, "kpilqr_iterate_streamed5: struct_size is not sizeof(kpilqr_stream_io5) of this library");
+    if (const int rc = stream_rows_of(c, &io5->io4, call)) return rc;
+    if (io5->sweep_count < 0 || (io5->sweep_count > 0 && !io5->sweep_traj))
+        return set_err(c, KPILQR_ERR_ARG, "kpilqr_iterate_streamed5: sweep_count < 0, or listed trajectories without sweep_traj");
+    call->sweep.listed = io5->sweep_traj != nullptr; call->sweep.count = call->sweep.listed ? io5->sweep_count : 0; call->sweep.traj = io5->sweep_traj;
+    return KPILQR_OK;
+}
+
 int kpilqr_iterate_streamed5(kpilqr_ctx *c, const kpilqr_stream_io5 *io5, int pd_check_stride, int nchunks)
 {
     KP_NOT_EMBEDDED(c, "kpilqr_iterate_streamed5");
     if (!c || !io5) return KPILQR_ERR_ARG;
-    if (io5->struct_size != sizeof(kpilqr_stream_io5)) return set_err(c, KPILQR_ERR_ARG, "kpilqr_iterate_streamed5: struct_size is not sizeof(kpilqr_stream_io5) of this library");
     StreamCall call(&io5->io4.io3.io2.io, pd_check_stride, nchunks);
-    if (const int rc = stream_rows_of(c, &io5->io4, &call)) return rc;
-    if (io5->sweep_count < 0 || (io5->sweep_count > 0 && !io5->sweep_traj))
-        return set_err(c, KPILQR_ERR_ARG, "kpilqr_iterate_streamed5: sweep_count < 0, or listed trajectories without sweep_traj");
-    call.sweep.listed = io5->sweep_traj != nullptr; call.sweep.count = call.sweep.listed ? io5->sweep_count : 0; call.sweep.traj = io5->sweep_traj;
+    if (const int rc = stream_sweep_of(c, io5, &call)) return rc;
+    return iterate_streamed(c, call);
+}
+
+// kpilqr_iterate_streamed5 taking the per-step residual Jacobians as FP32 inside the chunks: with r_x32 == r_u32 == NULL it IS that call
+int kpilqr_iterate_streamed6(kpilqr_ctx *c, const kpilqr_stream_io6 *io6, int pd_check_stride, int nchunks)
+{
+    KP_NOT_EMBEDDED(c, "kpilqr_iterate_streamed6");
+    if (!c || !io6) return KPILQR_ERR_ARG;
+    if (io6->struct_size != sizeof(kpilqr_stream_io6)) return set_err(c, KPILQR_ERR_ARG, "kpilqr_iterate_streamed6: struct_size is not sizeof(kpilqr_stream_io6) of this library");
+    StreamCall call(&io6->io5.io4.io3.io2.io, pd_check_stride, nchunks);
+    if (const int rc = stream_sweep_of(c, &io6->io5, &call)) return rc;
+    call.rx32 = io6->r_x32; call.ru32 = io6->r_u32;
     return iterate_streamed(c, call);
 }
 

@@ -1,5 +1,5 @@
 // residuals_f32.hip -- kpilqr_upload_residual_jacobians_f32[_partial]: the device side of uploading the per-step residual Jacobians
-// r_x [batch][T+1][nr][n] and r_u [batch][T+1][nr][m] as FP32.
+// r_x [batch][T+1][nr][n] and r_u [batch][T+1][nr][m] as FP32 -- and, below, of taking them inside the chunks of kpilqr_iterate_streamed6.
 //
 // They are the largest upload of a host whose residuals are not affine in the state (7.06 MB per trajectory
 // at the headline shape, every linearisation).  The caller sends a plain (float) cast of them -- r_x has no unit entry that would eat
@@ -71,6 +71,74 @@ hipError_t launch_widen_rows(Ctx *c, const int *traj_dev, int count, long long p
         hipLaunchKernelGGL(k_widen_rows<true>, grid, dim3(RJ32_THREADS), 0, c->stream, count, units, traj_dev, (const float2 *)src, (double2 *)dst);
     else
         hipLaunchKernelGGL(k_widen_rows<false>, grid, dim3(RJ32_THREADS), 0, c->stream, count, units, traj_dev, src, dst);
+    return hipGetLastError();
+}
+
+// ---- the same widening inside the chunks of kpilqr_iterate_streamed6 ----------------------------------------------------------------
+// A chunk pays ONE launch for BOTH arrays (the sweeps are latency-bound): two descriptors, and a split of the x range of the grid
+// selects the array -- blocks [0, x.blocks) of a block row walk the slices of r_x, the next u.blocks those of r_u.  An array that is
+// not given has zero units and zero blocks.  src is row 0 of the launch: the chunk's slice of the staging buffer (uploads by SDMA) or
+// of the caller's pinned floats themselves (KPILQR_PIPE_COPY bit 0: no staging buffer, no second pass over HBM); dst is the
+// CONTEXT's buffer.
+struct Rj32Array {
+    const float *src;
+    double *dst;
+    long long units;              // per trajectory: pairs, or (r_u with an odd element count) elements
+    unsigned blocks;
+};
+
+// slices bx, bx + nbx, ... of row `row` of the source into trajectory b of the destination
+template <bool PAIR>
+__device__ __forceinline__ void rj32_widen_row(const Rj32Array &a, long long row, long long b, unsigned bx, unsigned nbx)
+{
+    constexpr int slice = RJ32_THREADS * RJ32_ITERS;
+    const auto *s = (const typename Rj32Unit<PAIR>::In *)a.src + row * a.units;
+    auto *q = (typename Rj32Unit<PAIR>::Out *)a.dst + b * a.units;
+    for (long long at = (long long)bx * slice; at < a.units; at += (long long)nbx * slice) {
+        const int len = (int)(at + slice < a.units ? slice : a.units - at);
+        const auto *ss = s + at;
+        auto *qs = q + at;
+#pragma unroll RJ32_ITERS
+        for (int p = threadIdx.x; p < len; p += RJ32_THREADS) qs[p] = rj32_widen(ss[p]);
+    }
+}
+
+// Block (x, y): rows y, y + gridDim.y, ... of `count` rows.  Row i is trajectory traj[i] (device: the chunk's slice of the upload
+// list) or, traj == nullptr, trajectory first + i.  r_x is always on pairs (n = 2 dof); PAIR_U: r_u is too.  The pair path assumes
+// 8-byte aligned sources (a trajectory's element count is even there, so every row of an 8-byte aligned array is); the element path
+// assumes nothing beyond the float: a chunk's slice of r_u32 can start on an odd one.
+template <bool PAIR_U>
+__global__ void __launch_bounds__(RJ32_THREADS)
+k_widen_jacobians(int count, int first, const int *__restrict__ traj, Rj32Array x, Rj32Array u)
+{
+    const bool is_x = blockIdx.x < x.blocks;
+    for (int i = (int)blockIdx.y; i < count; i += gridDim.y) {
+        const long long b = traj ? traj[i] : first + i;
+        if (is_x) rj32_widen_row<true>(x, i, b, blockIdx.x, x.blocks);
+        else rj32_widen_row<PAIR_U>(u, i, b, blockIdx.x - x.blocks, u.blocks);
+    }
+}
+
+static Rj32Array rj32_array(const float *src, double *dst, long long per, bool pair)
+{
+    constexpr long long slice = (long long)RJ32_THREADS * RJ32_ITERS;
+    if (!src || per <= 0) return {nullptr, nullptr, 0, 0};
+    const long long units = pair ? per / 2 : per, want = (units + slice - 1) / slice;
+    return {src, dst, units, (unsigned)(want > 256 ? 256 : want)};          // (up to 256 blocks per trajectory, as above)
+}
+
+// `count` rows on stream s: row i of src_x (perx floats, even) and of src_u (peru floats) widened into trajectory traj[i] (device;
+// nullptr: first + i) of dst_x / dst_u.  A NULL source is an array that is not given.  src_x, and src_u when peru is even, are 8-byte
+// aligned.
+hipError_t launch_widen_jacobians(hipStream_t s, const int *traj_dev, int first, int count, long long perx, const float *src_x, double *dst_x,
+                                  long long peru, const float *src_u, double *dst_u)
+{
+    const bool pair_u = peru % 2 == 0;
+    const Rj32Array x = rj32_array(src_x, dst_x, perx, true), u = rj32_array(src_u, dst_u, peru, pair_u);
+    if (count <= 0 || x.blocks + u.blocks == 0) return hipSuccess;
+    const dim3 grid(x.blocks + u.blocks, (unsigned)(count < 65535 ? count : 65535));
+    if (pair_u) hipLaunchKernelGGL(k_widen_jacobians<true>, grid, dim3(RJ32_THREADS), 0, s, count, first, traj_dev, x, u);
+    else hipLaunchKernelGGL(k_widen_jacobians<false>, grid, dim3(RJ32_THREADS), 0, s, count, first, traj_dev, x, u);
     return hipGetLastError();
 }
 

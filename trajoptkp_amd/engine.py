@@ -464,17 +464,23 @@ class Engine:
         linearisation and the sweeps of those trajectories alone, as iterate_partial runs them.  lam, cost_pred, delta_J and status are
         then compact, [len(sweep_traj)] rows in list order; upload_traj must lie inside sweep_traj; K / K32 / k keep following
         gain_traj.  Always takes the new entry point (with sweep_traj=None that call is kpilqr_iterate_streamed4)."""
+        io5 = _lib.StreamIO5()
+        lists = self._stream_io5(io5, kp_cols32, upload_traj, sweep_traj)      # (read during the call only: they live until it returns)
+        self._iterate_streamed(fd, fd_kp, kp_cols, eps, r, r_x, r_u, u_nom, lam, K, k, cost_pred, delta_J, status, pd_stride, nchunks,
+                               K32, gain_traj, io5.io4.io3, kp_cols32, io5.io4, io5)
+
+    def _stream_io5(self, io5, kp_cols32, upload_traj, sweep_traj):
+        """the struct sizes and the two lists of a kpilqr_stream_io5 (inside a kpilqr_stream_io6 too) -> the arrays the struct points to"""
         if kp_cols32 is not None:
             if kp_cols32.dtype != np.float32:
                 raise ValueError("kp_cols32 must be a float32 array (no silent rounding here: the encoding is the caller's)")
             if kp_cols32.size % (3 * self.n):
                 raise ValueError(f"kp_cols32 must hold whole entries of 3 * {self.n} floats")
-        io5 = _lib.StreamIO5()
         io5.struct_size = C.sizeof(_lib.StreamIO5)
         io4 = io5.io4
         io4.struct_size = C.sizeof(_lib.StreamIO4)
         io4.io3.struct_size = C.sizeof(_lib.StreamIO3)
-        lists = []                                                     # (read during the call only: they live until it returns)
+        lists = []
         for name, given in (("upload", upload_traj), ("sweep", sweep_traj)):
             if given is None:
                 continue
@@ -484,11 +490,30 @@ class Engine:
             tr = tr if len(tr) else np.zeros(1, np.int32)              # an empty list is still a list: a non-NULL pointer
             setattr(where, name + "_traj", tr.ctypes.data)
             lists.append(tr)
+        return lists
+
+    def iterate_streamed6(self, fd=None, fd_kp=None, kp_cols=None, eps=1e-6, r=None, r_x=None, r_u=None, u_nom=None, lam=None, K=None, k=None,
+                          cost_pred=None, delta_J=None, status=None, pd_stride=100, nchunks=0, K32=None, gain_traj=None, kp_cols32=None,
+                          upload_traj=None, sweep_traj=None, r_x32=None, r_u32=None):
+        """kpilqr_iterate_streamed6: iterate_streamed5 with r_x32 / r_u32 -- the per-step residual Jacobians as FP32 (a plain cast:
+        synth.residual_jacobians_f32), pinned float32 arrays in the layout of r_x / r_u (with upload_traj the listed trajectories' rows,
+        compact), instead of r_x / r_u.  The library widens them exactly inside the chunks.  Always takes the new entry point (with
+        neither array that call is kpilqr_iterate_streamed5)."""
+        io6 = _lib.StreamIO6()
+        io6.struct_size = C.sizeof(_lib.StreamIO6)
+        for name, a in (("r_x32", r_x32), ("r_u32", r_u32)):
+            if a is None:
+                continue
+            if a.dtype != np.float32:
+                raise ValueError(f"{name} must be a float32 array (no silent rounding here: the cast is the caller's)")
+            setattr(io6, name, a.ctypes.data)
+        io5 = io6.io5
+        lists = self._stream_io5(io5, kp_cols32, upload_traj, sweep_traj)      # (read during the call only: they live until it returns)
         self._iterate_streamed(fd, fd_kp, kp_cols, eps, r, r_x, r_u, u_nom, lam, K, k, cost_pred, delta_J, status, pd_stride, nchunks,
-                               K32, gain_traj, io4.io3, kp_cols32, io4, io5)
+                               K32, gain_traj, io5.io4.io3, kp_cols32, io5.io4, io5, io6)
 
     def _iterate_streamed(self, fd, fd_kp, kp_cols, eps, r, r_x, r_u, u_nom, lam, K, k, cost_pred, delta_J, status, pd_stride, nchunks,
-                          K32, gain_traj, io3, kp_cols32=None, io4=None, io5=None):
+                          K32, gain_traj, io3, kp_cols32=None, io4=None, io5=None, io6=None):
         io2 = None if io3 is None else io3.io2
         if io2 is not None or K32 is not None or gain_traj is not None:
             if io2 is None:
@@ -518,7 +543,9 @@ class Engine:
                         ("cost_pred", cost_pred), ("delta_J", delta_J), ("status", status)):
             if a is not None:
                 setattr(io, name, a.ctypes.data)
-        if io5 is not None:
+        if io6 is not None:
+            self._ck(self._partial("kpilqr_iterate_streamed6")(self._h, C.byref(io6), int(pd_stride), int(nchunks)))
+        elif io5 is not None:
             self._ck(self._partial("kpilqr_iterate_streamed5")(self._h, C.byref(io5), int(pd_stride), int(nchunks)))
         elif io4 is not None:
             self._ck(self._partial("kpilqr_iterate_streamed4")(self._h, C.byref(io4), int(pd_stride), int(nchunks)))
