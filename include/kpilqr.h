@@ -925,7 +925,9 @@ int  kpilqr_upload_residuals(kpilqr_ctx *ctx, const double *r, const double *r_x
  * relative of the per-step form (tests hold 1e-12).  The uniform one-wave backward sweep at n = 14, m = 7 forms Q_uu, Q_ux and
  * Q_xx from two matrix products on packed tiles instead of three ("...:w1:...:uni"): Q_uu and Q_ux keep their bits for a given value
  * function, V' moves at rounding level, so K, k, delta_J and the costs agree with the general form and with earlier versions to
- * ~1e-15 relative, not bit for bit; the two payload kinds still give each other's bits.  A call that is rejected (bad argument, unpinned buffer) leaves the mode
+ * ~1e-15 relative, not bit for bit; the two payload kinds still give each other's bits.  The uniform one-wave backward sweeps of
+ * every shape symmetrise Q_xx in front of the gains instead of V' behind them: V' carries the rounding asymmetry of one matrix
+ * product, and the same ~1e-15 statement holds against the general form, the wave pairs and earlier versions.  A call that is rejected (bad argument, unpinned buffer) leaves the mode
  * as it was.  version >= 400. */
 int  kpilqr_upload_residual_jacobians_const(kpilqr_ctx *ctx, const double *r_x, const double *r_u);
 /* ModelTranslator::CostDerivativesFromResiduals (src/ModelTranslator/ModelTranslator.cpp:552-583)

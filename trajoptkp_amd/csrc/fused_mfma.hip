@@ -59,6 +59,15 @@ typedef unsigned long long u64;
 #ifndef KP_PROBE_BWD
 #define KP_PROBE_BWD 0
 #endif
+// The uniform one-wave backward sweeps symmetrise the Qzz tile IN FRONT of the refresh and take V' = Qs + K'G as it leaves the
+// last product (ESYM in backward_fused_body).  0: V' symmetrised behind that product, as before (the A/B's other side).
+// KP_EARLY_SYM_AT: where the transposed half is read -- 1 right behind the write, 2 behind the refresh, in front of the gains product.
+#ifndef KP_EARLY_SYM
+#define KP_EARLY_SYM 1
+#endif
+#ifndef KP_EARLY_SYM_AT
+#define KP_EARLY_SYM_AT 1
+#endif
 // The launchers (and with them the kernel instantiations) of this file compile as THREE translation units (Makefile: -DKP_FUSED_PART=1|2|3;
 // unset or 0: everything in one): 1 one wave per trajectory backward + the form choices, 2 the backward consumer / helper pair,
 // 3 the forward sweeps -- the file takes two minutes as one unit.
@@ -534,6 +543,30 @@ __device__ __forceinline__ void backward_fused_body(double *sh, const double *pc
     // duplicated B columns are not stored to kpc (cs).  See the products in `step`.
     constexpr bool PACKQ = UNI && !PC && N == 14 && M == 7;
     static_assert(!PACKQ || (N + 1 > 8 && M <= 8 && (M + 3) / 4 <= 2), "packed Q tiles: split row 8");
+    // ESYM (uniform one-wave sweeps): of V' = Qzz + K'G only Qzz needs the transposition -- packed, its block rows 8.. x cols 0..7 is
+    // never computed; with a constant r_x, l_x sits on one side of it -- and Qzz is complete in front of the refresh; K'G is a full
+    // product, symmetric up to the rounding of its m terms.  So the tile goes through LDS right behind its product (packed: the merge),
+    // Qs = Qm/2 + (Qm/2)' | (Qzz + Qzz')/2, off the chain V -> T2 -> D2 -> refresh -> K -> V', and V = Qs + K'G leaves the last product
+    // as it is: no LDS round trip between the last product of a step and the first of the next.  V carries the rounding asymmetry of
+    // ONE product (|V - V'| / |V| ~ 1e-16, tools/early_symmetrise_error.py); Qzz is symmetrised exactly at every step, so it does not
+    // accumulate.  Measured at both placements of the read and on all four shapes: profiles/early_symmetrise.txt.
+    constexpr bool ESYM = HEADS && KP_EARLY_SYM;
+    auto esym_write = [&](const d4 &Q) {
+        sh[KP_LDS_V + (q) * KP_VS + c] = Q.x;
+        sh[KP_LDS_V + (4 + q) * KP_VS + c] = Q.y;
+        sh[KP_LDS_V + (8 + q) * KP_VS + c] = Q.z;
+        sh[KP_LDS_V + (12 + q) * KP_VS + c] = Q.w;
+        wsync();
+    };
+    auto esym_read = [&](d4 &Q) {                              // Q <- Q + Q' (packed: the tile is halved) | (Q + Q')/2 on the image in KP_LDS_V
+        Q.x += sh[KP_LDS_V + c * KP_VS + q];
+        Q.y += sh[KP_LDS_V + c * KP_VS + 4 + q];
+        Q.z += sh[KP_LDS_V + c * KP_VS + 8 + q];
+        Q.w += sh[KP_LDS_V + c * KP_VS + 12 + q];
+        if constexpr (!PACKQ) { Q.x *= 0.5; Q.y *= 0.5; Q.z *= 0.5; Q.w *= 0.5; }
+        wsync();
+    };
+    (void)esym_write; (void)esym_read;
     ColOffsN cs = cu;                                          // raw sweep: where a differenced column goes in kpc
     (void)cs;
     if constexpr (PACKQ) {
@@ -854,6 +887,10 @@ __device__ __forceinline__ void backward_fused_body(double *sh, const double *pc
             Qzz = kp_P<NCZ>(Fz, Tz, Lzz);
         }
         }
+        if constexpr (ESYM) {                          // Qs, in Qzz's registers
+            esym_write(Qzz);
+            if constexpr (KP_EARLY_SYM_AT == 1) esym_read(Qzz);
+        }
 #ifdef KP_CYC
         asm volatile("" :: "v"(Qr.x), "v"(Quz.x), "v"(Qzz.x));
         const unsigned long long cyc_s1 = __builtin_readcyclecounter();
@@ -884,6 +921,7 @@ __device__ __forceinline__ void backward_fused_body(double *sh, const double *pc
         const unsigned long long cyc_s2 = __builtin_readcyclecounter();
         cyc_c += cyc_s2 - cyc_s1;
 #endif
+        if constexpr (ESYM && KP_EARLY_SYM_AT == 2) esym_read(Qzz);      // (in front of the factor path's LDS images too)
         d4 Kp = zero;                                 // the gains -X
         if (refreshed) {
             d4 Xa = Xinv;
@@ -992,9 +1030,12 @@ __device__ __forceinline__ void backward_fused_body(double *sh, const double *pc
         // V' = Qzz + K'Quu K + K'Quz + Quz'K (:606-607) with K = -X, (Quu + lambda I) X = Quz:
         //    = Qzz - X'(Quz + lambda X) = Qzz + K'(Quz - lambda K)   -- one product; G = (Quu + 2 lambda I)K' is never formed
         // (PACKQ: Qzz is the merged tile Qm / 2 -- the block rows 8..n x cols 0..7 is never computed, its mirror image counts twice -- and
-        // acc + acc' below gives every entry of V what it was, up to the summation order)
+        // acc + acc' below gives every entry of V what it was, up to the summation order.  ESYM: Qzz is Qs by now, symmetric and whole.)
         d4 G;
-        if constexpr (PACKQ) {                           // G / 2 for the halved tile: NCU = 2 registers enter the product
+        if constexpr (PACKQ && ESYM) {                   // Qzz is Qs, whole: G whole, on the NCU = 2 live registers
+            G.x = __builtin_fma(-lam, Kp.x, Quz.x); G.y = __builtin_fma(-lam, Kp.y, Quz.y);
+            G.z = 0.0; G.w = 0.0;
+        } else if constexpr (PACKQ) {                    // G / 2 for the halved tile: NCU = 2 registers enter the product
             G.x = __builtin_fma(-0.5 * lam, Kp.x, 0.5 * Quz.x); G.y = __builtin_fma(-0.5 * lam, Kp.y, 0.5 * Quz.y);
             G.z = 0.0; G.w = 0.0;
         } else {
@@ -1007,6 +1048,10 @@ __device__ __forceinline__ void backward_fused_body(double *sh, const double *pc
         const unsigned long long cyc_s3 = __builtin_readcyclecounter();
         cyc_d += cyc_s3 - cyc_s2;
 #endif
+        if constexpr (ESYM) {                          // V' as the product leaves it: nothing between it and the next step's T2
+            V = acc;
+            if (lane_nn) kp_set_reg<REG_NN>(V, 0.0);
+        } else {
         sh[KP_LDS_V + (q) * KP_VS + c] = acc.x;
         sh[KP_LDS_V + (4 + q) * KP_VS + c] = acc.y;
         sh[KP_LDS_V + (8 + q) * KP_VS + c] = acc.z;
@@ -1030,6 +1075,7 @@ __device__ __forceinline__ void backward_fused_body(double *sh, const double *pc
         }
         if (PC) __syncthreads();                       // end of step: the ring slot is free, the next one is full
         else wsync();
+        }
 #ifdef KP_CYC
         asm volatile("" :: "v"(V.x));
         cyc_e += __builtin_readcyclecounter() - cyc_s3;
