@@ -49,7 +49,7 @@
  *   KPILQR_TILED_UW         tiled backward sweep (n + 2 > 16): 1 u-wave form | 0 column-wave form (default by tile count).
  *   KPILQR_TILED_A6         tiled sweeps: 1 / 0 cost derivatives (a6) inside the sweep (default: inside at four tiles from
  *                           ~100 trajectories).
- *   KPILQR_TILED_FSC        two-tile forward sweep: 1 / 0 state / cost wave groups (default: on while 2 NT B <= #SIMDs).
+ *   KPILQR_TILED_FSC        two-tile forward sweep: 1 / 0 state / cost wave groups (default: on while 2 NT B <= #SIMDs; never past 0x7fffff00 B of records a trajectory).
  *   KPILQR_TILED_NT_MIN     run the tiled kernels with at least this many tiles (test coverage of a tile count on a
  *                           small state).
  *   KPILQR_PIPE_COPY        kpilqr_iterate_streamed: bit 0 uploads / bit 1 downloads by copy kernels instead of SDMA

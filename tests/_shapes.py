@@ -10,6 +10,7 @@ T1_SHAPES = ((14, 7), (4, 1), (12, 3), (10, 3))        # KP_T1_SHAPES, mfma_comm
 BIGOFF = 0x40000000                                     # fused_mfma.hip:44
 TILE, TPAD = 256, 272                                   # KP_TILE, KP_TPAD, mfma_common.h:20-21
 LDS_MAX = 160 * 1024                                    # the LDS bound of the tiled and generic backward sweeps
+FSC_REC_BYTES_MAX = 0x7fffff00                          # KP_FSC_REC_BYTES_MAX, tiled_mfma.hip:27: one trajectory's records in one descriptor
 ENV_KEYS = ("KPILQR_FUSED_WAVES", "KPILQR_FUSED_FWD_WAVES", "KPILQR_TILED_NT_MIN", "KPILQR_TILED_A6", "KPILQR_TILED_UW",
             "KPILQR_TILED_FSC")
 
@@ -22,6 +23,10 @@ def _env(env, key, default):                            # read_tuning_from_env, 
 def _cdiv(a, b):                                        # C's int division (truncates toward zero)
     q = abs(a) // abs(b)
     return q if (a >= 0) == (b > 0) else -q
+
+
+def rec_stride(n, m):                                   # RecLayout::stride, common.h:29-37 (doubles; the record padded to 16)
+    return (2 * n * n + n * m + n + m * m + m + 15) & ~15
 
 
 def tiled_nt(n, nt_min=0):                              # tiled_nt, tiled_mfma.hip:562 (wide_nt, tiled_wide.hip:413, is the same)
@@ -151,7 +156,10 @@ def dispatch(dof, m, nr, T, n_alpha, batch, n_simd, flags, env=None, rx_const=Fa
     elif fv.startswith("mfma_f64_tiled"):
         a6 = fv.endswith("_a6")
         fsc = _env(env, "KPILQR_TILED_FSC", -1)
-        sc = nt == 2 and not a6 and m <= 8 and (fsc != 0 if fsc >= 0 else 2 * nt * batch <= n_simd)   # tiled_mfma.hip:1790-1796
+        # forward_tiled_sc_selected, tiled_mfma.hip:1814-1825: a horizon whose records outgrow the form's one descriptor per trajectory
+        # runs the general form, whatever KPILQR_TILED_FSC says
+        sc = (nt == 2 and not a6 and m <= 8 and T * rec_stride(n, m) * 8 <= FSC_REC_BYTES_MAX
+              and (fsc != 0 if fsc >= 0 else 2 * nt * batch <= n_simd))
         rows = n + 2 - 16 * (nt - 1)
         if sc:                                          # launch_ft_sc, :1771-1779
             ncl = 4 if rows >= 16 else 1 if rows < 1 else _cdiv(rows + 3, 4)

@@ -22,6 +22,9 @@
 #ifndef KP_FT_SETS
 #define KP_FT_SETS 2                // register sets of the two-tile forward sweep on materialised tiles (1: rounds 1-3, A/B builds)
 #endif
+// the most bytes of one trajectory's step records the state / cost wave forward sweep addresses (its one descriptor per trajectory;
+// forward_tiled_sc_selected keeps longer horizons off the form; mirrored in tests/_shapes.py)
+#define KP_FSC_REC_BYTES_MAX 0x7fffff00u
 
 // latency probe (-DKP_PROBE_SAMEB): every workgroup works on one of two trajectories, everything hits in cache
 #ifdef KP_PROBE_SAMEB
@@ -1518,7 +1521,7 @@ __device__ __forceinline__ void ft_state_role(double *zring, double *upart, doub
     // one descriptor per array for the whole trajectory; the step goes into the loads' scalar offset (behind the last step: step
     // T-1 again, never used)
     (void)rs_of;
-    const __amdgpu_buffer_rsrc_t rRec = kp_rsrc(rec + (size_t)b * T * L.stride, (int)((size_t)T * L.stride * 8 < 0x7fffff00u ? (size_t)T * L.stride * 8 : 0x7fffff00u));
+    const __amdgpu_buffer_rsrc_t rRec = kp_rsrc(rec + (size_t)b * T * L.stride, (int)((size_t)T * L.stride * 8 < KP_FSC_REC_BYTES_MAX ? (size_t)T * L.stride * 8 : KP_FSC_REC_BYTES_MAX));
     const __amdgpu_buffer_rsrc_t rKt = kp_rsrc(Kin + (size_t)b * T * m * n, T * m * n * 8);
     const __amdgpu_buffer_rsrc_t rkt = kp_rsrc(kin + (size_t)b * T * m, T * m * 8);
     const __amdgpu_buffer_rsrc_t rut = kp_rsrc(u_nom + (size_t)b * T * m, T * m * 8);
@@ -1683,7 +1686,7 @@ k_forward_tiled_sc(RecLayout L, int T, int n_alpha, const double *__restrict__ r
             olu[r] = (wi == NT - 1 && row < m) ? 8 * (L.off_lu + row) : KP_OOB;
         }
         struct CTiles { d4 Lc[NT], Luu, lu; } cur;
-        const __amdgpu_buffer_rsrc_t rRec = kp_rsrc(rec + (size_t)b * T * L.stride, (int)((size_t)T * L.stride * 8 < 0x7fffff00u ? (size_t)T * L.stride * 8 : 0x7fffff00u));
+        const __amdgpu_buffer_rsrc_t rRec = kp_rsrc(rec + (size_t)b * T * L.stride, (int)((size_t)T * L.stride * 8 < KP_FSC_REC_BYTES_MAX ? (size_t)T * L.stride * 8 : KP_FSC_REC_BYTES_MAX));
         const int recB = L.stride * 8;
         {
             __amdgpu_buffer_rsrc_t rR = rs_of(rec, L.stride, 0, rec_bytes);
@@ -1812,6 +1815,10 @@ bool forward_tiled_sc_selected(const Ctx *c)
 {
     const int nt = tiled_nt(c->n, c->tune.tiled_nt_min);
     if (nt != 2 || c->tiled_a6 || c->d.m > 8) return false;
+    // The form reaches a trajectory's records through ONE descriptor and puts the step into the loads' 32-bit scalar offset
+    // (ft_state_role, the cost waves): a horizon whose records outgrow that descriptor would read zeros behind it.  Such a horizon
+    // runs the general form -- a descriptor per step on a size_t base -- whatever KPILQR_TILED_FSC says.
+    if ((size_t)c->d.T * c->L.stride * 8 > KP_FSC_REC_BYTES_MAX) return false;
     if (c->tune.tiled_fsc >= 0) return c->tune.tiled_fsc != 0;
     return 2 * nt * c->d.batch <= c->n_simd;
 }
