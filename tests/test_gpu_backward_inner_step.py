@@ -23,135 +23,18 @@ tests/test_gpu_refresh.py's.)
 Everything is held to oracle.pipeline.run_trajectory at 1e-9 (K, k, delta_J, predicted costs; status exactly), forms of one sweep to
 each other at 1e-12.  The oracle's runs are made once per problem and shared; the CPU test at the bottom asserts that every input on
 which success is asserted succeeds on the oracle, and that the retry problem has both outcomes."""
-import functools
-import os
-
-import numpy as np
 import pytest
 
-from oracle import oracle as orc
-from oracle import pipeline
-from trajoptkp_amd import Engine, synth
-
-import _lambda_retry as lr
+from _one_wave_backward import (LEGS, RETRY, assert_bit_identical, assert_form, assert_forms_agree, assert_oracle, check_gated_twin,
+                                check_listed_twin, check_retry_outcomes_on_the_oracle, check_uniform_against_general, problem, reference, run)
 
 gpu = pytest.mark.gpu
 
-RTOL = 1e-9          # to the oracle
-FTOL = 1e-12         # between forms of the same sweep
-ALPHAS = orc.alphas(6)
-BATCH = 3
 HORIZONS = (2, 3, 4, 6, 11)
 INTERVALS = (1, 2, 5)                                        # key-points every min_N steps
-LEGS = {"rxc": (False, True), "per_step": (False, False), "dense": (True, False)}          # dense residuals, constant-Jacobian upload
 SMALL = {"hopper": "hopper", "pentabot": "pentabot", "acrobot": "acrobot"}                  # (12,3), (10,3), (4,1): NCU = 1
 PD_LOW = (2, 3)
-
-# the gated twin: Panda T = 11 under negative running weights, w_run = -(|w_run| + 1) * RETRY_SCALE as tests/_lambda_retry.py makes
-# sweeps fail (its own Panda problem has T = 64), a PD check every RETRY_PD steps.  On the oracle the constant-Jacobian leg (scale 20)
-# fails at lambda 1e-4 and settles from 0.1 on, the dense leg (scale 3) fails at 0.1 and settles from 1 on, each a decade or more away
-# from the edge (K moves by ~1 relative per relative change of lambda there: no conditioning to speak of).  Looked for on the oracle
-# alone; the CPU test below asserts what is relied on.
-RETRY_PD, RETRY_BATCH = 3, 4
-RETRY = {"rxc": (20.0, (1e-4, 0.1, 1e-4, 1.0)), "dense": (3.0, (0.1, 1.0, 10.0, 0.1))}          # leg: scale, start lambdas
 LISTED = [0, 2, 4]                                           # the listed twin: a scattered subset of five trajectories
-
-
-@functools.lru_cache(maxsize=None)
-def problem(task, T, min_N, dense, batch=BATCH):
-    return synth.make_problem(task=task, T=T, batch=batch, min_N=min_N, one_sided_frac=0.25, dense_residuals=dense)
-
-
-@functools.lru_cache(maxsize=None)
-def reference(task, T, min_N, dense, pd_stride=100, batch=BATCH):
-    p = problem(task, T, min_N, dense, batch)
-    return [pipeline.run_trajectory(p, b, pd_stride=pd_stride) for b in range(p["batch"])]
-
-
-@functools.lru_cache(maxsize=None)
-def retry_problem(leg):
-    scale, lam0 = RETRY[leg]
-    p = dict(synth.make_problem(task="panda_reaching", T=11, batch=RETRY_BATCH, min_N=5, dense_residuals=LEGS[leg][0]))
-    p["w_run"] = -(np.abs(p["w_run"]) + 1.0) * scale
-    p["lam0"] = np.array(lam0)
-    return p
-
-
-@functools.lru_cache(maxsize=None)
-def retry_reference(leg):
-    """tests/_lambda_retry.py's reference loop with the default schedule (factor 10, max_lambda 10, 6 attempts) on retry_problem()"""
-    p = retry_problem(leg)
-    out = []
-    for b in range(p["batch"]):
-        lam, seen = float(p["lam0"][b]), []
-        while True:
-            o = pipeline.run_trajectory(p, b, lam=lam, pd_stride=RETRY_PD)
-            seen.append(lam)
-            nxt, ex = lr.next_lambda(lam, lr.FACTOR, lr.MAX_LAMBDA)
-            if o["status"] == 0 or ex or len(seen) >= lr.MAX_ATTEMPTS:
-                break
-            lam = nxt
-        out.append(dict(out=o, visited=tuple(seen), lam=lam))
-    return out
-
-
-def relerr(a, b):
-    a, b = np.asarray(a, float), np.asarray(b, float)
-    return float(np.max(np.abs(a - b))) / max(float(np.max(np.abs(b))), 1e-300)
-
-
-@pytest.fixture(autouse=True)
-def one_wave(monkeypatch):
-    monkeypatch.delenv("KPILQR_FUSED_UNI", raising=False)
-    monkeypatch.setenv("KPILQR_FUSED_WAVES", "1")
-    monkeypatch.setenv("KPILQR_FUSED_FWD_WAVES", "1")
-
-
-def fresh_engine(p, general=False):
-    """(the environment is read when the context is created)"""
-    if general:
-        os.environ["KPILQR_FUSED_UNI"] = "0"
-    try:
-        return Engine(p["dof"], p["m"], p["T"], p["nr"], batch=p["batch"], fused=True)
-    finally:
-        os.environ.pop("KPILQR_FUSED_UNI", None)
-
-
-@functools.lru_cache(maxsize=None)
-def run(task, T, min_N, dense, payload, rx_const, pd_stride=100, general=False):
-    """One kpilqr_iterate of the problem on a fresh context."""
-    p = problem(task, T, min_N, dense)
-    with fresh_engine(p, general) as e:
-        synth.upload(e, p, kp_ordered=(payload == "raw"), rx_const=rx_const)
-        e.iterate(p["lam"], pd_stride, ALPHAS)
-        res = e.results()
-        K, k = e.gains()
-        return dict(K=K, k=k, launch=e.last_launch("backward"), **res)
-
-
-def assert_form(got, payload, rxc=None, general=False):
-    lb = got["launch"]
-    assert ":w1:" in lb and f":{payload}:" in lb, lb
-    assert (":uni" in lb) == (not general), lb
-    if rxc is not None:
-        assert (":rxc" in lb) == rxc, lb
-
-
-def figures(got, want, b=None):
-    sl = slice(None) if b is None else b
-    return dict(K=relerr(got["K"][sl], want["K"]), k=relerr(got["k"][sl], want["k"]),
-                delta_J=abs(float(got["delta_J"][sl]) - float(want["delta_J"])) / abs(float(want["delta_J"])) if b is not None
-                else relerr(got["delta_J"], want["delta_J"]),
-                cost_pred=relerr(got["cost_pred"][sl], want["cost_pred"]))
-
-
-def assert_oracle(got, refs, label, rows=None):
-    for i, o in enumerate(refs):
-        b = i if rows is None else rows[i]
-        fig = figures(got, o, b)
-        print(f"{label} b={b}: " + " ".join(f"{n} {v:.2e}" for n, v in fig.items()))
-        assert got["status"][b] == o["status"] == 0, (label, b, got["status"][b], o["status"])
-        assert all(v < RTOL for v in fig.values()), (label, b, fig)
 
 
 # ---- 1. Panda (14,7): every horizon, interval, leg and payload --------------------------------------------------------------------------
@@ -173,9 +56,7 @@ def test_panda_sweep_against_the_oracle(T, min_N, payload, leg):
 @pytest.mark.parametrize("T", HORIZONS)
 def test_payloads_agree_bit_for_bit(T, min_N, leg):
     dense, rx_const = LEGS[leg]
-    raw, kpc = run("panda_reaching", T, min_N, dense, "raw", rx_const), run("panda_reaching", T, min_N, dense, "kpc", rx_const)
-    for name in ("K", "k", "delta_J", "cost_pred", "status"):
-        assert np.array_equal(raw[name], kpc[name]), name
+    assert_bit_identical(run("panda_reaching", T, min_N, dense, "raw", rx_const), run("panda_reaching", T, min_N, dense, "kpc", rx_const))
 
 
 @gpu
@@ -185,10 +66,7 @@ def test_payloads_agree_bit_for_bit(T, min_N, leg):
 def test_constant_jacobian_leg_against_the_per_step_leg(T, min_N, payload):
     rxc, per = run("panda_reaching", T, min_N, False, payload, True), run("panda_reaching", T, min_N, False, payload, False)
     assert_form(rxc, payload, rxc=True); assert_form(per, payload, rxc=False)
-    fig = figures(rxc, per)
-    print(f"T={T} every {min_N} {payload} rxc vs per-step: " + " ".join(f"{n} {v:.2e}" for n, v in fig.items()))
-    assert np.array_equal(rxc["status"], per["status"])
-    assert all(v < FTOL for v in fig.values()), fig
+    assert_forms_agree(rxc, per, f"T={T} every {min_N} {payload} rxc vs per-step")
 
 
 # ---- 2. factorised steps among refreshed ones: the re-seed hands back heads ---------------------------------------------------------------
@@ -228,24 +106,7 @@ def test_small_shapes_with_pd_checks_below_the_horizon(task):
 @gpu
 @pytest.mark.parametrize("leg", sorted(RETRY))
 def test_gated_twin_under_a_lambda_retry_schedule(leg):
-    p, refs = retry_problem(leg), retry_reference(leg)
-    with fresh_engine(p) as e:
-        synth.upload(e, p, kp_ordered=True, rx_const=LEGS[leg][1])
-        e.set_lambda_retry()
-        st, dJ = e.backward(p["lam0"], pd_stride=RETRY_PD)
-        lam_used, att = e.lambda_retry()
-        K, k = e.gains()
-        lb = e.last_launch("backward")
-    assert ":w1:raw:uni" in lb and ((":rxc" in lb) == LEGS[leg][1]), lb
-    print(f"gated {leg}: status {list(st)} attempts {list(att)} lambda_used {list(lam_used)}")
-    assert list(att) == [len(r["visited"]) for r in refs] and max(att) > 1
-    assert list(lam_used) == [r["lam"] for r in refs]
-    for b, r in enumerate(refs):
-        o = r["out"]
-        assert st[b] == o["status"] == 0, (b, st[b], o["status"])
-        fig = dict(K=relerr(K[b], o["K"]), k=relerr(k[b], o["k"]), delta_J=abs(dJ[b] - o["delta_J"]) / abs(o["delta_J"]))
-        print(f"   b={b} lambda {r['lam']!r}: " + " ".join(f"{n} {v:.2e}" for n, v in fig.items()))
-        assert all(v < RTOL for v in fig.values()), (b, fig)
+    check_gated_twin(leg)
 
 
 @gpu
@@ -254,18 +115,7 @@ def test_listed_twin_on_a_scattered_subset(leg):
     dense, rx_const = LEGS[leg]
     p = problem("panda_reaching", 11, 5, dense, batch=5)
     refs = reference("panda_reaching", 11, 5, dense, batch=5)
-    with fresh_engine(p) as e:
-        synth.upload(e, p, kp_ordered=True, rx_const=rx_const)
-        st, dJ = e.backward_partial(LISTED, p["lam"])
-        K, k = e.gains()
-        lb = e.last_launch("backward")
-    assert ":w1:" in lb and ":uni" in lb and lb.endswith(":subset") and ((":rxc" in lb) == rx_const), lb
-    for i, b in enumerate(LISTED):
-        o = refs[b]
-        assert st[i] == o["status"] == 0, (b, st[i], o["status"])
-        fig = dict(K=relerr(K[b], o["K"]), k=relerr(k[b], o["k"]), delta_J=abs(dJ[i] - o["delta_J"]) / abs(o["delta_J"]))
-        print(f"listed {leg} b={b}: " + " ".join(f"{n} {v:.2e}" for n, v in fig.items()))
-        assert all(v < RTOL for v in fig.values()), (b, fig)
+    check_listed_twin(p, refs, LISTED, rx_const, f"listed {leg}")
 
 
 # ---- 5. the uniform form against the general form, which keeps its statements --------------------------------------------------------------
@@ -273,13 +123,7 @@ def test_listed_twin_on_a_scattered_subset(leg):
 @pytest.mark.parametrize("leg", sorted(LEGS))
 def test_uniform_form_against_the_general_form(leg):
     dense, rx_const = LEGS[leg]
-    uni = run("panda_reaching", 11, 5, dense, "raw", rx_const)
-    gen = run("panda_reaching", 11, 5, dense, "raw", rx_const, general=True)
-    assert_form(uni, "raw"); assert_form(gen, "raw", general=True)
-    fig = figures(uni, gen)
-    print(f"uniform vs general {leg}: " + " ".join(f"{n} {v:.2e}" for n, v in fig.items()))
-    assert np.array_equal(uni["status"], gen["status"])
-    assert all(v < FTOL for v in fig.values()), fig
+    check_uniform_against_general(f"uniform vs general {leg}", "panda_reaching", 11, 5, dense, rx_const)
 
 
 # ---- 6. the inputs (CPU) -----------------------------------------------------------------------------------------------------------------------
@@ -301,9 +145,4 @@ def test_inputs_succeed_on_the_oracle():
         assert all(o["status"] == 0 for o in reference(task, 11, 5, False, 3)), task
     for dense in (False, True):
         assert all(o["status"] == 0 for o in reference("panda_reaching", 11, 5, dense, batch=5)), dense
-    for leg in RETRY:
-        p, refs = retry_problem(leg), retry_reference(leg)
-        first = [pipeline.run_trajectory(p, b, lam=float(p["lam0"][b]), pd_stride=RETRY_PD)["status"] for b in range(p["batch"])]
-        assert any(s > 0 for s in first) and any(s == 0 for s in first), (leg, first)
-        assert all(r["out"]["status"] == 0 for r in refs), (leg, [r["out"]["status"] for r in refs])
-        assert [len(r["visited"]) > 1 for r in refs] == [s > 0 for s in first], leg
+    check_retry_outcomes_on_the_oracle()
