@@ -7,6 +7,7 @@ import os
 
 import numpy as np
 
+import _blockwise as BW
 from oracle import oracle as orc
 from oracle import pipeline
 from trajoptkp_amd import Engine, synth
@@ -97,4 +98,11 @@ def run_case(c, worst=None):
             for key, v in errs.items():
                 w[key] = max(w.get(key, 0.0), v)
         assert max(errs.values()) < TOL, (c["case"], c["task"], T, batch, c["min_N"], lam, pd, var, errs)
+        # ... and every block of K, k, U_alpha and the predicted costs to its own bar against the extended reference (_blockwise.py)
+        bb = BW.bars(p, b, lam, pd_stride=pd)
+        blk = BW.block_errors(dict(K=K[b], k=k[b], U_alpha=U[b], cost_pred=cost[b]), bb["ref"])
+        if worst is not None:
+            for key in BW.FAMILIES:
+                w["share:" + key] = max(w.get("share:" + key, 0.0), blk[key] / bb["bar"][key])
+        assert not BW.violations(blk, bb["bar"]), (c["case"], c["task"], T, batch, c["min_N"], lam, pd, var, BW.violations(blk, bb["bar"]))
     return var

@@ -3,6 +3,7 @@ the C ABI -- FD, interpolation, cost, backward, forward over the alphas --, the 
 table predicts, and the comparison with oracle.pipeline.run_trajectory."""
 import numpy as np
 
+import _blockwise as BW
 import _shapes as S
 from oracle import oracle as orc
 from trajoptkp_amd import Engine, synth
@@ -92,22 +93,35 @@ def _check_dispatch(c, g, n_simd):
         assert ":state_cost_waves" not in g["launch"][1], g["launch"]
 
 
-def _errs(g, o, b):
-    """Relative errors of trajectory b of a GPU result against its oracle o."""
+def _errs(g, o, b, p=None, ref_b=None, n_alpha=6, pd=100):
+    """Relative errors of trajectory b of a GPU result against its oracle o (the largest error over the largest entry).  With the
+    problem p whose trajectory ref_b (default b) the oracle o is: also `blockwise`, the families of tests/_blockwise.py that are over
+    their bar against the extended reference -- [] where every block of K, k, U_alpha and the predicted costs is within it."""
+    out = _global_errs(g, o, b)
+    if p is not None:
+        bb = BW.bars(p, b if ref_b is None else ref_b, n_alpha=n_alpha, pd_stride=pd)
+        out["blockwise"] = BW.violations(BW.block_errors(BW.gpu_result(g, b), bb["ref"]), bb["bar"])
+    return out
+
+
+def _global_errs(g, o, b):
     return dict(K=_rel(g["K"][b], o["K"]), k=_rel(g["k"][b], o["k"]),
                 delta_J=abs(g["delta_J"][b] - o["delta_J"]) / max(abs(o["delta_J"]), 1e-300),
                 cost=_rel(g["cost"][b], o["cost_pred"]), U=_rel(g["U"][b], o["U_alpha"]))
 
 
-def _check(g, refs, rows, tag):
-    """rows: the trajectories of the GPU result to check; refs[b % len(refs)] is the oracle of trajectory b."""
+def _check(g, refs, rows, tag, p=None, n_alpha=6):
+    """rows: the trajectories of the GPU result to check; refs[b % len(refs)] is the oracle of trajectory b.  p: the problem whose
+    trajectories the refs are, in their order -- with it every block is held to its bar as well (_errs)."""
     for b in rows:
         o = refs[b % len(refs)]
         assert g["status"][b] == o["status"], (tag, b, g["status"][b], o["status"])
         if o["status"] != 0:
             continue
-        errs = _errs(g, o, b)
+        errs = _errs(g, o, b, p, b % len(refs), n_alpha)
+        blockwise = errs.pop("blockwise", [])
         assert max(errs.values()) <= RTOL, (tag, b, g["launch"], errs)
+        assert not blockwise, (tag, b, g["launch"], blockwise)
 
 
 def _take(p, batch):

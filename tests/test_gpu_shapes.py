@@ -25,7 +25,7 @@ def test_shape_matches_oracle(c, monkeypatch):
     _check_dispatch(c, g, n_simd)
     refs = [pipeline.run_trajectory(p, b, n_alpha=c["n_alpha"], want_U=True) for b in range(p["batch"])]
     assert all(o["status"] == 0 for o in refs) or c["why"] == "long"
-    _check(g, refs, range(p["batch"]), _case_id(c))
+    _check(g, refs, range(p["batch"]), _case_id(c), p=p, n_alpha=c["n_alpha"])
 
 
 def test_batch_boundaries(monkeypatch):
@@ -39,7 +39,7 @@ def test_batch_boundaries(monkeypatch):
         p = _take(synth.tile_problem(base, -(-c["batch"] // 7)), c["batch"])
         g = _run(c, p, monkeypatch, kp_ordered=bool(c["flags"] & S.FLAG_FUSED))
         _check_dispatch(c, g, n_simd)
-        _check(g, refs, range(c["batch"]), _case_id(c))
+        _check(g, refs, range(c["batch"]), _case_id(c), p=base, n_alpha=c["n_alpha"])
 
 
 def test_generic_lds_limit_refused_at_create(monkeypatch):

@@ -23,67 +23,10 @@ sys.path.insert(0, ".")
 sys.path.insert(0, os.path.join(".", "tests"))
 import _fuzz
 from oracle import crosscheck as cc
+from oracle.extended import LD, ld_backward, ld_forward
 from oracle import pipeline
 from oracle import oracle as orc
 from trajoptkp_amd import Engine, synth
-
-LD = np.longdouble
-
-
-def ld_solve(M, R):
-    """M^-1 R, Gaussian elimination with partial pivoting in longdouble."""
-    M = M.astype(LD).copy(); R = R.astype(LD).copy()
-    m = M.shape[0]
-    for j in range(m):
-        p = j + int(np.argmax(np.abs(M[j:, j])))
-        if p != j:
-            M[[j, p]] = M[[p, j]]; R[[j, p]] = R[[p, j]]
-        piv = M[j, j]
-        f = M[j + 1:, j] / piv
-        M[j + 1:] -= f[:, None] * M[j][None, :]
-        R[j + 1:] -= f[:, None] * R[j][None, :]
-    for j in range(m - 1, -1, -1):
-        R[j] = (R[j] - M[j, j + 1:] @ R[j + 1:]) / M[j, j]
-    return R
-
-
-def ld_backward(A, B, l_x, l_xx, l_u, l_uu, lam):
-    A, B, l_x, l_xx, l_u, l_uu = (x.astype(LD) for x in (A, B, l_x, l_xx, l_u, l_uu))
-    T, n, m = A.shape[0], A.shape[1], B.shape[2]
-    K = np.zeros((T, m, n), LD); k = np.zeros((T, m), LD)
-    Vx = l_x[T - 1].copy(); Vxx = l_xx[T - 1].copy()
-    dJ = LD(0)
-    I = np.eye(m, dtype=LD)
-    for t in range(T - 1, -1, -1):
-        Qx = l_x[t] + A[t].T @ Vx
-        Qu = l_u[t] + B[t].T @ Vx
-        Qxx = l_xx[t] + A[t].T @ Vxx @ A[t]
-        Quu = l_uu[t] + B[t].T @ Vxx @ B[t]
-        Qux = B[t].T @ Vxx @ A[t]
-        inv = ld_solve(Quu + LD(lam) * I, I)
-        k[t] = -inv @ Qu
-        K[t] = -inv @ Qux
-        Vx = Qx + K[t].T @ (Quu @ k[t]) + K[t].T @ Qu + Qux.T @ k[t]
-        Vxx = Qxx + K[t].T @ (Quu @ K[t]) + K[t].T @ Qux + Qux.T @ K[t]
-        Vxx = (Vxx + Vxx.T) / 2
-        dJ += k[t] @ Qu + k[t] @ Quu @ k[t]
-    return K, k, dJ
-
-
-def ld_forward(A, B, K, k, l_x, l_xx, l_u, l_uu, u_nom, ctrl_lim, alphas):
-    A, B, K, k, l_x, l_xx, l_u, l_uu, u_nom = (np.asarray(x).astype(LD) for x in (A, B, K, k, l_x, l_xx, l_u, l_uu, u_nom))
-    T, n, m = A.shape[0], A.shape[1], B.shape[2]
-    lo, hi = ctrl_lim[0::2].astype(LD), ctrl_lim[1::2].astype(LD)
-    cost = np.zeros(len(alphas), LD); U = np.zeros((len(alphas), T, m), LD)
-    for a, alpha in enumerate(alphas):
-        dx = np.zeros(n, LD)
-        for t in range(T):
-            u = np.clip(u_nom[t] + LD(alpha) * k[t] + K[t] @ dx, lo, hi)
-            du = u - u_nom[t]
-            U[a, t] = u
-            cost[a] += l_x[t] @ dx + LD(0.5) * (dx @ l_xx[t] @ dx) + l_u[t] @ du + LD(0.5) * (du @ l_uu[t] @ du)
-            dx = A[t] @ dx + B[t] @ du
-    return cost, U
 
 
 def rel(a, b):

@@ -199,6 +199,34 @@ static inline bool kp_t1_carrier(int dof, int m, int *carrier_dof, int *carrier_
 // chosen from the measured residual so that the last one ends below 1e-15 (bound on the row sums of |I - Q Xinv|:
 // m * max entry).  Returns false, leaving Xinv untouched, when the residual is too large to converge in four
 // steps (the caller then factorises).  Q and Xinv are symmetric up to rounding, so Q'X = QX and X'R = XR.
+//
+// That count is normwise: e is the residual's largest entry.  An entry of the inverse that is small beside the diagonal and has
+// itself moved by a relative d since the last step (the coupling of a weak control to a strong one, where the units of the controls
+// are decades apart and drift) leaves e untouched, and every second-order step multiplies ITS relative error by twice the normwise
+// error of the moment only: d 2e after one step, d 4e^3 after two, d 8e^7, d 16e^15.  The row of K = -X Quz of the weak control
+// inherits it through X_j0 Quz_0.  So the first step also looks at every entry: where what the bin's steps will leave of its own
+// movement is over KP_NS_MOVE_TOL of the entry, AND the movement is under KP_NS_MOVE_NEGL of (largest residual entry) x (largest
+// entry of X) -- invisible to the count --, one more step follows the bin's own.  The second condition keeps entries that are small
+// by cancellation, whose movement is of the size of everybody's, from buying a step on every dense matrix.
+// (mirrored in tests/_refresh.py, MOVE_TOL / MOVE_NEGL; tests/test_gpu_blockwise.py is what sees it)
+#define KP_NS_MOVE_TOL 1.0e-14
+#define KP_NS_MOVE_NEGL 1.0e-2
+__device__ __forceinline__ double kp_wave_max(double v)
+{
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) v = fmax(v, __shfl_xor(v, o));
+    return v;
+}
+__device__ __forceinline__ double kp_ns_move_c(int iters, double e)     // 2e, 4e^3, 8e^7, 16e^15
+{
+    const double e2 = e * e, e3 = e2 * e, e7 = e3 * e3 * e;
+    return iters == 1 ? 2.0 * e : iters == 2 ? 4.0 * e3 : iters == 3 ? 8.0 * e7 : 16.0 * e7 * e7 * e;
+}
+__device__ __forceinline__ bool kp_ns_moved(double x0, double x1, double c, double negl)
+{
+    const double d = fabs(x1 - x0);
+    return d * c > KP_NS_MOVE_TOL * fabs(x1) && d < negl;
+}
 template <int NCU>
 __device__ __forceinline__ bool kp_inverse_refresh(const d4 &Qr, const d4 &Iu, d4 &Xinv, int m)
 {
@@ -214,7 +242,19 @@ __device__ __forceinline__ bool kp_inverse_refresh(const d4 &Qr, const d4 &Iu, d
     const int iters = (__builtin_amdgcn_ballot_w64(e >= 1.3e-2) != 0) ? 4
                     : (__builtin_amdgcn_ballot_w64(e >= 1.7e-4) != 0) ? 3
                     : (__builtin_amdgcn_ballot_w64(e >= 3.0e-8) != 0) ? 2 : 1;
+    const d4 X0 = Xinv;
+    double xmax = fabs(X0.x);
+    if (NCU > 1) xmax = fmax(xmax, fabs(X0.y));
+    if (NCU > 2) xmax = fmax(xmax, fabs(X0.z));
+    if (NCU > 3) xmax = fmax(xmax, fabs(X0.w));
+    const double ru = kp_wave_max(rmax);
+    const double c = kp_ns_move_c(iters, (double)m * ru), negl = KP_NS_MOVE_NEGL * ru * kp_wave_max(xmax);
     Xinv = kp_P<NCU>(Xinv, R, Xinv);
+    bool moved = kp_ns_moved(X0.x, Xinv.x, c, negl);
+    if (NCU > 1) moved = moved || kp_ns_moved(X0.y, Xinv.y, c, negl);
+    if (NCU > 2) moved = moved || kp_ns_moved(X0.z, Xinv.z, c, negl);
+    if (NCU > 3) moved = moved || kp_ns_moved(X0.w, Xinv.w, c, negl);
+    const bool extra = __builtin_amdgcn_ballot_w64(moved) != 0;
     if (iters > 1) {
         R = Iu - kp_P<NCU>(Qr, Xinv, zero); Xinv = kp_P<NCU>(Xinv, R, Xinv);
         if (iters > 2) {
@@ -222,6 +262,7 @@ __device__ __forceinline__ bool kp_inverse_refresh(const d4 &Qr, const d4 &Iu, d
             if (iters > 3) { R = Iu - kp_P<NCU>(Qr, Xinv, zero); Xinv = kp_P<NCU>(Xinv, R, Xinv); }
         }
     }
+    if (extra) { R = Iu - kp_P<NCU>(Qr, Xinv, zero); Xinv = kp_P<NCU>(Xinv, R, Xinv); }
     return true;
 }
 

@@ -296,6 +296,8 @@ k_backward_tiled_wide(RecLayout L, int T, const double *__restrict__ rec, const 
                     }
                 return rmax;
             };
+            bool moved = false;                 // an entry of the inverse that moved too far for the bin's count (kp_inverse_refresh)
+            double move_c = 0.0, move_negl = 0.0;   // > 0 on the first update alone
             auto update = [&]() {
                 d4 Xn[MT * MT];
 #pragma unroll
@@ -307,17 +309,36 @@ k_backward_tiled_wide(RecLayout L, int T, const double *__restrict__ rec, const 
                         for (int j = 0; j < MT; j++) acc = kp_Pn(Xinv[j * MT + a], R[j * MT + bb], acc, mch(j));
                         Xn[a * MT + bb] = acc;
                     }
+                if (move_c > 0.0) {
+#pragma unroll
+                    for (int i = 0; i < MT * MT; i++)
+                        moved = moved || kp_ns_moved(Xinv[i].x, Xn[i].x, move_c, move_negl) || kp_ns_moved(Xinv[i].y, Xn[i].y, move_c, move_negl)
+                                      || kp_ns_moved(Xinv[i].z, Xn[i].z, move_c, move_negl) || kp_ns_moved(Xinv[i].w, Xn[i].w, move_c, move_negl);
+                }
 #pragma unroll
                 for (int i = 0; i < MT * MT; i++) Xinv[i] = Xn[i];
             };
-            const double e = (double)m * residual();
+            const double rloc = residual();
+            const double e = (double)m * rloc;
             // (thresholds and step counts mirrored in tests/_refresh.py, family "wide")
             if (__builtin_amdgcn_ballot_w64(!(e < 0.11)) == 0) {
                 const int iters = (__builtin_amdgcn_ballot_w64(e >= 1.3e-2) != 0) ? 4
                                 : (__builtin_amdgcn_ballot_w64(e >= 1.7e-4) != 0) ? 3
                                 : (__builtin_amdgcn_ballot_w64(e >= 3.0e-8) != 0) ? 2 : 1;
+                {
+                    double xmax = 0.0;
+#pragma unroll
+                    for (int i = 0; i < MT * MT; i++)
+                        xmax = fmax(xmax, fmax(fmax(fabs(Xinv[i].x), fabs(Xinv[i].y)), fmax(fabs(Xinv[i].z), fabs(Xinv[i].w))));
+                    const double ru = kp_wave_max(rloc);
+                    move_c = kp_ns_move_c(iters, (double)m * ru);
+                    move_negl = KP_NS_MOVE_NEGL * ru * kp_wave_max(xmax);
+                }
                 update();
+                move_c = 0.0;
+                const bool extra = __builtin_amdgcn_ballot_w64(moved) != 0;
                 for (int it = 1; it < iters; it++) { (void)residual(); update(); }
+                if (extra) { (void)residual(); update(); }
                 done = true;
             }
         }
